@@ -6,7 +6,12 @@ One "step" = one pass of the hot path over one (umo, vmo) field, all device resi
 Inputs are in HBM before the timed region starts and the five CSC matrices are left in HBM.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload access1deg|quarterdeg|tenthdeg|small]
-                    [--scaling weak|strong] [--repeats R]
+                    [--scaling weak|strong] [--repeats R] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times EXACTLY K steps once and prints the headline line.  --full adds everything else the line
+can carry: per-kernel times and the roofline, the fused and given-operator steps, the other configurations (fresh processes),
+end_to_end, cpu_baseline, config2, box_probe, the communicator figures and config4 -- and repeats the K steps R = 5 times.
+--dump-outputs DIR: after the timed steps, the last step's matrices and face fluxes (a fixed, seeded sample) as DIR/<name>.npy.
 
 N > 1: one rank per GPU.  Launched by torch.distributed.run (RANK/LOCAL_RANK/WORLD_SIZE in the environment) each process
 is one rank; launched plainly (`python bench.py --gpus N`) this process only SPAWNS the N ranks -- before anything here
@@ -36,7 +41,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5, help="the K timed steps are repeated R times; ms_per_step is the median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the K timed steps are repeated R times; ms_per_step is the median (default: 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline too (see the module docstring); a plain run times the K steps and stops")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64, a fixed seeded sample; single GPU)")
     ap.add_argument("--workload", default="access1deg")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
     ap.add_argument("--rho", default="array", choices=["array", "scalar"])
@@ -59,9 +69,11 @@ def parse():
                     help="async: otmb_transportmatrix_dev (count -> scan -> fill enqueued back to back, outputs preallocated "
                          "at their upper bound); twophase: plan (host learns nnz) then fill, as a caller that sizes its outputs does")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
     args.steps = max(1, args.steps)
     args.warmup = max(0, args.warmup)
-    args.repeats = max(1, args.repeats)
+    args.repeats = max(1, args.repeats if args.repeats is not None else (5 if args.full else 1))
     return args
 
 
@@ -155,11 +167,12 @@ class Watchdog:
                 self.timer = None
 
 
-def first_contact(dist, torch, world, rank, dev, backend, plane_elems, rehearsal, dog):
+def first_contact(dist, torch, world, rank, dev, backend, plane_elems, rehearsal, dog, full=True):
     """Evidence a multi-rank line must carry about ITS OWN communicator: how many ranks answered an all_reduce, which
     library / version carried it, and what the one exchange of the path costs here -- a (nx, ny) plane of ϕtop from rank r to rank r - 1
     (the facefluxes chain, src/velocities.jl:236-243 across depth slabs), whole and in the row bands it is handed over in.  Every phase
-    runs under the watchdog.  Returns the record (every rank computes it; rank 0 prints it)."""
+    runs under the watchdog.  Returns the record (every rank computes it; rank 0 prints it).  full=False (a plain run): the all_reduce
+    alone, no hand-off timed."""
     limit = float(os.environ.get("OTMB_BENCH_PREFLIGHT_S", "120"))
     cdev = dev if backend == "nccl" else torch.device("cpu")
     rec = {"backend": backend, "world": world}
@@ -192,7 +205,7 @@ def first_contact(dist, torch, world, rank, dev, backend, plane_elems, rehearsal
 
     comm = odist.Comm()
     pieces = int(os.environ.get("OTMB_CHAIN_PIECES", "0")) or (4 if plane_elems >= (1 << 19) else 1)
-    if world > 1:
+    if world > 1 and full:
         dog.arm("preflight: point-to-point plane hand-off", limit)
         send = torch.full((plane_elems,), float(rank), dtype=torch.float64, device=dev)
         recv = torch.empty(plane_elems, dtype=torch.float64, device=dev)
@@ -389,7 +402,7 @@ def extra_configs_in_children(args):
     out = {}
     for wl in [w for w in args.extra_configs.split(",") if w and w != args.workload]:
         key = names.get(wl, "config_" + wl)
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--extra-configs", "", "--no-cpu-baseline", "--no-end-to-end",
+        cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--full", "--extra-configs", "", "--no-cpu-baseline", "--no-end-to-end",
                *(["--end-to-end-large"] if wl == "quarterdeg" and not args.no_end_to_end else []),
                "--steps", str(min(args.steps, 10)), "--warmup", "2", "--repeats", "2", "--rho", args.rho, "--seed", str(args.seed),
                "--placement-candidates", str(args.placement_candidates)]
@@ -570,6 +583,56 @@ def traffic_for(workload, kernel, args, world=1):
         return None
 
 
+DUMP_SAMPLE = 1 << 16  # columns (and cells) sampled: <= 25 entries per column over the five matrices -> <= 32 MB in all
+
+
+def dump_outputs(asm, outdir):
+    """--dump-outputs: what the timed path handed back in its last step, for an output-by-output comparison of two builds on the same
+    inputs.  Float64 .npy files in `outdir`: nnz.npy = [N, nnz of T, Tadv, TκH, TκVML, TκVdeep]; columns.npy = a sample of DUMP_SAMPLE
+    column indices, fixed by a constant seed and N; per matrix <name>_colptr.npy (first and one-past-last entry of each sampled column),
+    <name>_rowval.npy and <name>_nzval.npy (their entries, column after column); cells.npy and phi_<face>.npy: the six face fluxes on a
+    sample of cells drawn the same way.  An operator passed in (--given-ops) was not written by the step and is left out."""
+    import numpy as np
+    import torch
+
+    from otmb_amd.capi import MATS, PHI_ORDER
+
+    asm.ctx.synchronize()
+    os.makedirs(outdir, exist_ok=True)
+    names = dict(zip(MATS, ("T", "Tadv", "TkH", "TkVML", "TkVdeep")))
+    save = lambda name, a: np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    sample = lambda n: np.sort(np.random.default_rng(20260501).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    N = int(asm.N)
+    save("nnz", [N, *asm.nnz])
+    cols = sample(N)
+    save("columns", cols)
+    given = set(getattr(asm, "given", None) or ())
+    for k, m in enumerate(MATS):
+        if m in given:
+            continue
+        cp, rv, nz = asm.out[m]
+        nnz = int(asm.nnz[k])
+        if cp.numel() != N + 1 or rv.numel() < nnz or nz.numel() < nnz:
+            raise RuntimeError(f"--dump-outputs: {m}'s buffers do not hold N + 1 offsets and {nnz} entries")
+        base = int(cp[0].item())  # (1 for the reference's 1-based offsets)
+        lo = cp[torch.from_numpy(cols).to(cp.device)].cpu().numpy() - base
+        hi = cp[torch.from_numpy(cols + 1).to(cp.device)].cpu().numpy() - base
+        if not (np.all(lo <= hi) and np.all(lo >= 0) and np.all(hi <= nnz)):  # checked here: an index beyond the arrays never reaches the device
+            raise RuntimeError(f"--dump-outputs: {m}'s column offsets are not within [0, {nnz}]")
+        cnt = hi - lo
+        ent = np.repeat(lo - np.concatenate(([0], np.cumsum(cnt)[:-1])), cnt) + np.arange(int(cnt.sum()))
+        ent_d = torch.from_numpy(ent).to(cp.device)
+        save(names[m] + "_colptr", np.stack([lo, hi], axis=1))
+        save(names[m] + "_rowval", rv[ent_d].cpu().numpy())
+        save(names[m] + "_nzval", nz[ent_d].cpu().numpy())
+    if getattr(asm, "phi", None) is not None:
+        cells = sample(int(asm.G))
+        save("cells", cells)
+        cells_d = torch.from_numpy(cells).to(asm.phi[0].device)
+        for face, p in zip(PHI_ORDER, asm.phi):
+            save("phi_" + face, p[cells_d].cpu().numpy())
+
+
 def under_profiler():
     """A rocprofv3 / rocprof preload has initialised the GPU before this script started: no child processes then (they would inherit the
     profiler, write their dispatches into the same output directory and mix two grids in one summary)."""
@@ -584,7 +647,7 @@ def main(slab_backend_factory=None, cpu_rehearsal=False):
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args))
     extras = {}
-    if args.gpus == 1 and "RANK" not in os.environ and args.extra_configs and not cpu_rehearsal and not under_profiler():
+    if args.full and args.gpus == 1 and "RANK" not in os.environ and args.extra_configs and not cpu_rehearsal and not under_profiler():
         # Every configuration of the line is measured by a FRESH process that has the GPU to itself, the HEADLINE FIRST: a process that
         # starts after the 0.25 / 0.1 degree runs have allocated and freed 35 / 220 GB measures the same kernels 2-3 % slower
         # (profiles/r04/README.md section 7: 0.3775 against 0.3658 ms on one box; round 3 ran the headline last).  This process only
@@ -623,6 +686,8 @@ def main(slab_backend_factory=None, cpu_rehearsal=False):
     # OTMB_FORCE_SLAB=1: take the depth-slab (distributed) code path even with one rank, e.g. under
     # `torchrun --nproc-per-node 1`, to exercise RCCL initialisation and collectives on a one-GPU box
     force_slab = os.environ.get("OTMB_FORCE_SLAB") == "1" and "RANK" in os.environ
+    if args.dump_outputs is not None and (force_slab or cpu_rehearsal):
+        sys.exit("bench.py: --dump-outputs writes the single-GPU path's outputs; not with OTMB_FORCE_SLAB=1")
     # rehearsal (tests/bench_rehearsal.py only): the multi-rank orchestration of this script on a box without GPUs -- gloo, a
     # backend supplied by the test -- the line it prints is labelled as not being a measurement
     rehearsal = bool(cpu_rehearsal)
@@ -664,7 +729,7 @@ def main(slab_backend_factory=None, cpu_rehearsal=False):
     comm_rec = None
     if world > 1 or force_slab:
         nx_, ny_ = synthetic.PRESETS[args.workload][:2]
-        comm_rec = first_contact(dist, torch, world, rank, dev, backend, nx_ * ny_, rehearsal, dog)
+        comm_rec = first_contact(dist, torch, world, rank, dev, backend, nx_ * ny_, rehearsal, dog, full=args.full)
         if comm_rec["ranks_seen"] != world:
             print(f"bench.py: rank {rank}: all_reduce saw {comm_rec['ranks_seen']} of {world} ranks", file=sys.stderr, flush=True)
             os._exit(4)
@@ -911,10 +976,12 @@ def main(slab_backend_factory=None, cpu_rehearsal=False):
             elapsed = float(t.item())
         per_repeat.append(elapsed)
     elapsed = float(np.median(per_repeat))
+    if args.dump_outputs is not None:  # (before anything below runs other steps or overwrites the matrices)
+        dump_outputs(asm, args.dump_outputs)
 
     # per-kernel durations with HIP events on the launch stream, over one more pass of the same K steps
     ktimes = {}
-    if runner.ctx is not None:
+    if runner.ctx is not None and args.full:
         runner.ctx.timing_enable(True)
         for _ in range(args.steps):
             runner.step()
@@ -926,7 +993,7 @@ def main(slab_backend_factory=None, cpu_rehearsal=False):
     # vmo; the same five matrices bit for bit, tests/test_fused_step.py), measured the same way right after the headline and reported as an
     # EXTRA record: `value` stays the two-call path, which is what the reference's API is (facefluxesfrommasstransport returns six arrays).
     fused = None
-    if getattr(runner, "fused_available", False) and not rehearsal:
+    if getattr(runner, "fused_available", False) and not rehearsal and args.full:
         try:
             for _ in range(args.warmup):
                 runner.fused_step()
@@ -961,7 +1028,7 @@ def main(slab_backend_factory=None, cpu_rehearsal=False):
     # (one comparing pass, then cached), so the fill pass neither counts nor writes them.  An EXTRA record (never `value`: the headline returns
     # all five matrices); measured like the headline, two-call path (facefluxes -> transportmatrix).
     given_step = None
-    if getattr(runner, "given_available", False) and not rehearsal:
+    if getattr(runner, "given_available", False) and not rehearsal and args.full:
         try:
             given_step = runner.given_steps(args, barrier)
         except Exception as e:  # an extra record must never cost the headline
@@ -970,14 +1037,14 @@ def main(slab_backend_factory=None, cpu_rehearsal=False):
     # N > 1: BASELINE.json configs[3] (the fixed 0.25 degree grid cut into N depth slabs) beside the headline, unless it IS the headline
     config4 = None
     c4_workload = os.environ.get("OTMB_BENCH_CONFIG4_WORKLOAD", "quarterdeg")  # (tests rehearse this leg on a small grid)
-    if world > 1 and args.extra_configs and not (args.workload == c4_workload and args.scaling == "strong") and \
+    if world > 1 and args.full and args.extra_configs and not (args.workload == c4_workload and args.scaling == "strong") and \
             (not rehearsal or "OTMB_BENCH_CONFIG4_WORKLOAD" in os.environ):
         try:
             config4 = slab_config(c4_workload, args, world, rank, dev, local_rank, rehearsal, backend, make_backend)
         except Exception as e:  # every rank raises the same pipeline errors (dist.SlabRunner.finish), so nobody is left in a collective
             config4 = {"workload": c4_workload, "error": f"{type(e).__name__}: {e}"[:300]}
     kernels_by_rank = None
-    if dist.is_initialized() and (world > 1 or force_slab):
+    if dist.is_initialized() and (world > 1 or force_slab) and args.full:
         mine = {k: v[0] / v[1] for k, v in ktimes.items()}
         allk = [None] * world
         dist.all_gather_object(allk, mine)
@@ -1027,7 +1094,7 @@ def main(slab_backend_factory=None, cpu_rehearsal=False):
             "value": value, "unit": "wet-cells/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
             "higher_is_better": True, "scaling": args.scaling if world > 1 else "weak", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
+            "data": "synthetic", "full": bool(args.full),
             "config": {
                 "workload": f"{args.workload}: synthetic ACCESS-ESM1-5-like tripolar grid {shape}"
                             f", facefluxes + full transportmatrix (5 CSC matrices), rho={args.rho}, upwind"
@@ -1057,13 +1124,13 @@ def main(slab_backend_factory=None, cpu_rehearsal=False):
                 own = sum(v["max"] for k, v in kernels_by_rank.items() if k in ("facefluxes_kernel", "tilescan_kernel", "tm_kernel<fill>", "tm_count_kernel"))
                 out["comm"]["expected_step_ms"] = own + comm_rec["plane_hand_off"]["ms_by_pieces"][str(comm_rec["plane_hand_off"]["pieces"])]
                 out["comm"]["expected_step_note"] = "slowest rank's facefluxes + scan + fill (HIP events) + one plane hand-off; the measured ms_per_step above it is orchestration and skew"
-        if world == 1 and host_grid is not None and not rehearsal:
+        if world == 1 and host_grid is not None and not rehearsal and args.full:
             try:  # (an extra record must never cost the headline: the host-pointer legs allocate gigabytes of pinned memory and start threads)
                 out["end_to_end"] = None if args.no_end_to_end else end_to_end(*host_grid, n_total)
             except Exception as e:
                 out["end_to_end"] = {"error": f"{type(e).__name__}: {e}"[:300]}
             out["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(*host_grid, args.workload)
-        if world == 1 and host_grid is None and args.end_to_end_large and not rehearsal and not force_slab:
+        if world == 1 and host_grid is None and args.end_to_end_large and not rehearsal and not force_slab and args.full:
             try:  # (after everything that reads the assembler's matrices: it is released first -- the host-pointer engines stage the grid themselves)
                 import gc
 
@@ -1076,12 +1143,12 @@ def main(slab_backend_factory=None, cpu_rehearsal=False):
                 out["end_to_end"] = end_to_end(*hg, n_total, reps=3, warm=8, large=True)
             except Exception as e:
                 out["end_to_end"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if world == 1 and host_grid is not None and not rehearsal and dev.type == "cuda":
+        if world == 1 and host_grid is not None and not rehearsal and dev.type == "cuda" and args.full:
             try:  # an extra record must never cost the headline
                 out["config2"] = config2_bolus(*host_grid, dev, local_rank, min(args.steps, 10))
             except Exception as e:
                 out["config2"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if world == 1 and not rehearsal and dev.type == "cuda":
+        if world == 1 and not rehearsal and dev.type == "cuda" and args.full:
             try:  # after the timed region and not part of the measurement: it must never cost the line
                 torch.cuda.empty_cache()
                 out["box_probe"] = box_probe(dev)

@@ -18,7 +18,7 @@ def test_bench_spawns_its_ranks_and_prints_one_json_line(gpus, scaling):
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_rehearsal.py"), "--gpus", str(gpus), "--workload", "small", "--scaling", scaling,
-                        "--steps", "2", "--warmup", "1", "--repeats", "2"], env=env, capture_output=True, text=True, timeout=600)
+                        "--steps", "2", "--warmup", "1", "--repeats", "2", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout
@@ -43,6 +43,28 @@ def test_bench_spawns_its_ranks_and_prints_one_json_line(gpus, scaling):
         assert c4["wet_cells"] > 0 and c4["ms_per_step"] > 0
     else:
         assert "config4" not in d
+
+
+def test_plain_multi_rank_run_carries_the_headline_alone():
+    """Without --full the ranks time the K steps once and print the line: no plane hand-off, no per-kernel figures, no config4."""
+    env = dict(os.environ, OTMB_BENCH_CONFIG4_WORKLOAD="small")
+    env.pop("RANK", None)
+    env.pop("WORLD_SIZE", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_rehearsal.py"), "--gpus", "2", "--workload", "small", "--steps", "3",
+                        "--warmup", "1"], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["steps"] == 3 and d["repeats"]["n"] == 1 and d["full"] is False
+    assert d["config"]["ranks_seen"] == 2 and "plane_hand_off" not in d["comm"]
+    assert d["kernels_ms_over_ranks"] is None and "config4" not in d
+
+
+def test_dump_outputs_is_refused_for_several_gpus():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs", "unused"], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 2 and "--dump-outputs needs --gpus 1" in r.stderr and r.stdout == ""
 
 
 def test_a_rank_that_never_arrives_ends_the_run_with_its_name():

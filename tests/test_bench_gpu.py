@@ -14,7 +14,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--workload", "small", "--steps", "3", "--warmup", "1", "--repeats", "2", "--no-cpu-baseline", "--no-end-to-end", "--extra-configs="]
+COMMON = ["--workload", "small", "--steps", "3", "--warmup", "1", "--repeats", "2", "--no-cpu-baseline", "--no-end-to-end", "--extra-configs=", "--full"]
 CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
             "roofline")
 
@@ -60,3 +60,41 @@ def test_bench_as_one_rank_over_rccl():
     assert d["n_gpus"] == 1 and d["unit"] == "wet-cells/s" and d["value"] > 0
     assert d["config"].get("ranks_over") == "nccl", d["config"]  # the depth-slab path, its rank over RCCL
     assert d["roofline"] is not None and 0 < d["roofline"]["frac"] < 1
+
+
+def test_plain_run_times_k_steps_and_dumps_the_last_steps_outputs(tmp_path, oracle):
+    """Without --full the line carries the headline alone, over exactly K steps timed once; --dump-outputs writes the last step's matrices
+    and face fluxes, which on the small grid (fewer cells than the sample) are the whole outputs -- the oracle's, bit for bit."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import otmb_amd
+    from otmb_amd import synthetic
+
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "small", "--steps", "4", "--warmup", "1", "--dump-outputs", str(out)],
+                       env=_clean_env(), capture_output=True, text=True, timeout=600)
+    d = _one_json_line(r)
+    assert d["steps"] == 4 and d["repeats"]["n"] == 1 and d["full"] is False and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["roofline"] is None and d["kernels_ms"] == {}
+    for k in ("fused_step", "given_ops_step", "end_to_end", "cpu_baseline", "config2", "box_probe", "config3", "config5"):
+        assert k not in d, k
+    files = {p.name: np.load(p) for p in out.iterdir()}
+    assert all(a.dtype == np.float64 for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+
+    g = synthetic.make_grid(*synthetic.PRESETS["small"][:3], seed=d["config"]["seed"], land_fraction=synthetic.PRESETS["small"][3], rho="array")
+    gm = otmb_amd.makegridmetrics(areacello=g.areacello, volcello=g.volcello, lon=g.lon, lat=g.lat, lev=g.lev,
+                                  lon_vertices=g.lon_vertices, lat_vertices=g.lat_vertices)
+    idx = oracle.makeindices(gm.v3D)
+    phi = oracle.facefluxes(g.umo.data, g.vmo.data, idx["wet3D"], g.umo.properties["_FillValue"], gm.gridtopology.kind)
+    ref = oracle.transportmatrix(phi, gm, idx, g.rho, g.mlotst, g.kappaH, g.kappaVML, g.kappaVdeep, True)
+    N = idx["N"]
+    assert list(files["nnz.npy"]) == [N, *(len(ref[m][1]) for m in oracle.MATS)]
+    assert np.array_equal(files["columns.npy"], np.arange(N))
+    for m, name in zip(oracle.MATS, ("T", "Tadv", "TkH", "TkVML", "TkVdeep")):
+        cp, rv, nz = ref[m]
+        assert np.array_equal(files[name + "_colptr.npy"], np.stack([cp[:-1] - cp[0], cp[1:] - cp[0]], axis=1)), m
+        assert np.array_equal(files[name + "_rowval.npy"], rv) and np.array_equal(files[name + "_nzval.npy"], nz), m
+    assert np.array_equal(files["cells.npy"], np.arange(g.umo.data.size))
+    for face in ("east", "west", "north", "south", "top", "bottom"):
+        assert np.array_equal(files[f"phi_{face}.npy"], phi[face].ravel(order="F"), equal_nan=True), face

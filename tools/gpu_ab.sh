@@ -21,7 +21,7 @@ for r in $(seq 1 "$ROUNDS"); do
       [ -z "$e" ] && continue
       if [ "${e%%=*}" = LIB ]; then args+=("OTMB_LIB_OVERRIDE=$REPO/oceantransportmatrixbuilder.jl_amd/lib/libotmb_hip_${e#*=}.so"); else args+=("$e"); fi
     done
-    env "${args[@]}" timeout -k 10 600 python3 bench.py --workload "$WL" --extra-configs= --no-cpu-baseline --no-end-to-end --steps "$STEPS" --warmup 3 \
+    env "${args[@]}" timeout -k 10 600 python3 bench.py --full --workload "$WL" --extra-configs= --no-cpu-baseline --no-end-to-end --steps "$STEPS" --warmup 3 \
         --repeats 3 --placement-candidates 1 $BENCH_FLAGS 2>/dev/null | python3 -c "
 import json,sys
 d=json.load(sys.stdin)

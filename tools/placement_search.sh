@@ -7,7 +7,7 @@ mkdir -p $(dirname $OUTF)
 cd $REPO
 run() {  # run <tag> ENV...
   tag=$1; shift
-  env "$@" timeout -k 10 300 python3 bench.py --workload $WL --extra-configs= --no-cpu-baseline --no-end-to-end --warmup 3 --steps 10 --repeats 3 2>/dev/null | python3 -c "
+  env "$@" timeout -k 10 300 python3 bench.py --full --workload $WL --extra-configs= --no-cpu-baseline --no-end-to-end --warmup 3 --steps 10 --repeats 3 2>/dev/null | python3 -c "
 import json,sys; d=json.load(sys.stdin); print(json.dumps({'tag':'$tag','workload':'$WL','ms_per_step':round(d['ms_per_step'],4),'fill':round(d['kernels_ms']['tm_kernel<fill>'],4),'ff':round(d['kernels_ms']['facefluxes_kernel'],4),'count':round(d['kernels_ms']['tm_count_kernel'],4),'frac':round(d['roofline']['frac'],4)}))" | tee -a $OUTF
   rc=$?; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo STOP; exit 1; fi
 }

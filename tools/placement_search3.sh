@@ -7,7 +7,7 @@ mkdir -p $(dirname $OUTF)
 cd $REPO
 run() {  # run <workload> <tag> ENV...
   wl=$1; tag=$2; shift; shift
-  env "$@" timeout -k 10 300 python3 bench.py --workload $wl --extra-configs= --no-cpu-baseline --no-end-to-end --warmup 3 --steps 10 --repeats 3 2> $REPO/gpurun_out/ps3_last.err | python3 -c "
+  env "$@" timeout -k 10 300 python3 bench.py --full --workload $wl --extra-configs= --no-cpu-baseline --no-end-to-end --warmup 3 --steps 10 --repeats 3 2> "$(dirname "$OUTF")/ps3_last.err" | python3 -c "
 import json,sys; d=json.load(sys.stdin); print(json.dumps({'workload':'$wl','tag':'$tag','ms_per_step':round(d['ms_per_step'],4),'fill':round(d['kernels_ms']['tm_kernel<fill>'],4),'ff':round(d['kernels_ms']['facefluxes_kernel'],4),'count':round(d['kernels_ms']['tm_count_kernel'],4),'frac':round(d['roofline']['frac'],4)}))" | tee -a $OUTF
   rc=$?; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo STOP; exit 1; fi
 }

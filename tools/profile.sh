@@ -9,8 +9,8 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # the trace runs bench.py's default steps / warm-up / repeats (the fill pass needs ~20 steps to reach its steady rate: with
 # --steps 10 --warmup 2 it measures 0.40-0.43 ms where the default run measures 0.38-0.39); the counter passes are short
-TARGS="--no-cpu-baseline --no-end-to-end --extra-configs= $@"
-ARGS="--steps 10 --warmup 2 --repeats 1 --no-cpu-baseline --no-end-to-end --extra-configs= $@"
+TARGS="--full --no-cpu-baseline --no-end-to-end --extra-configs= $@"
+ARGS="--full --steps 10 --warmup 2 --repeats 1 --no-cpu-baseline --no-end-to-end --extra-configs= $@"
 rm -rf $OUT/trace
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $REPO/bench.py $TARGS > $OUT/bench_trace.json 2> $OUT/trace.err
 echo "trace rc=$?"

@@ -8,9 +8,9 @@ out=gpurun_out/r05/slab_probe.jsonl
 : > $out
 port=29520
 for r in 1 2 3 4; do
-  python bench.py --steps 300 --warmup 30 --no-cpu-baseline --no-end-to-end --extra-configs= 2>/dev/null | python tools/jsonl_tag.py single $r >> $out
+  python bench.py --full --steps 300 --warmup 30 --no-cpu-baseline --no-end-to-end --extra-configs= 2>/dev/null | python tools/jsonl_tag.py single $r >> $out
   port=$((port+1))
-  OTMB_FORCE_SLAB=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $port bench.py --gpus 1 --steps 300 --warmup 30 --no-cpu-baseline --no-end-to-end --extra-configs= 2>/dev/null | python tools/jsonl_tag.py forced_slab $r >> $out
+  OTMB_FORCE_SLAB=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $port bench.py --full --gpus 1 --steps 300 --warmup 30 --no-cpu-baseline --no-end-to-end --extra-configs= 2>/dev/null | python tools/jsonl_tag.py forced_slab $r >> $out
 done
 python - <<'PY'
 import json
