@@ -359,6 +359,19 @@ typedef struct {
                                   *    operands' counts); the asynchronous and multi-slab builds return OTMB_ERR_GIVEN_FOREIGN.
                                   * In a depth-slab launch (otmb_transportmatrix_set_slab) given[m] names the slab's columns: colptr
                                   * its n_wet + 1 entries (global numbering), rowval / nzval the entries from colptr[0] on, nnz their number. */
+    int32_t kept_ops;            /* _dev entry points only (the host-pointer and multi-slab builds ignore it); 0 = the reference's behaviour.
+                                  * Bit m (m = OTMB_TKH, OTMB_TKVML, OTMB_TKVDEEP -- grid constants, src/matrixbuilding.jl:51-120): the caller
+                                  * PROMISES that the output arrays it passes for operator m are the ones this context's previous successful
+                                  * call wrote for m, untouched since.  The library keeps a record per operator (output pointers, capacity,
+                                  * grid array addresses, κ, topology, n_wet, slab, the otmb_ctx_forget_given epoch, the nnz it wrote) and
+                                  * honours the bit only when the record matches this call: operator m is then re-derived in registers (T
+                                  * needs it) but neither counted nor stored, and its nnz comes back from the record.  Anything else --
+                                  * no record, other arguments, a given operator / skip_ops / only_t that left the slot unwritten, an
+                                  * asynchronous step that wrote it and failed, otmb_ctx_forget_given -- writes it in full.  An
+                                  * asynchronous step that relied on a step which then failed reports that step's status.  Two-phase
+                                  * protocol: fill must be handed the recorded arrays for a kept operator (otherwise OTMB_ERR_INVALID_ARG:
+                                  * plan again without the bit).  A write to those arrays the caller does not tell the library about
+                                  * (another library call, a raw pointer) must be followed by a call without the bit.                  */
 } otmb_tm_args;
 /* The verdicts on otmb_tm_args.given are keyed to array ADDRESSES (the given matrix's and the gridmetrics / indices arrays') and κ.
  * A device-resident caller that rewrites one of those arrays in place calls this before the next transportmatrix; the host-pointer

@@ -198,6 +198,7 @@ struct TmArgs
     ignore_ops::Int32             # bit m: nothing operator m alone would raise is raised
     skip_ops::Int32               # bit m: matrix m is not wanted -- neither counted, written nor copied home (buildT*)
     given::NTuple{5,Csc}          # operators the caller passes (Tadv = / TκH = / TκVML = / TκVdeep = keywords): not built, added as they are
+    kept_ops::Int32               # _dev entry points only (device output sets); always 0 here
 end
 
 # Output arrays in pinned host memory of the library (otmb_host_alloc): the DMA writes them in place -- no staging copy, no page
@@ -376,7 +377,7 @@ function tmargs(ϕ, mlotst, gridmetrics, indices, ρ, κH, κVML, κVdeep, upwin
         ρ isa Number ? Ptr{Float64}(C_NULL) : pointer(rho3), ρ isa Number ? Float64(ρ) : 0.0,
         pointer(lw3), pointer(lw), ntuple(i -> pointer(el[i]), 4), ntuple(i -> pointer(dn[i]), 4),
         pointer(ar), pointer(z), pointer(ml), Float64(κH), Float64(κVML), Float64(κVdeep), Ptr{UInt16}(C_NULL),
-        Int32(operators ? 0 : 1), ignore_ops, skip_ops, csc)
+        Int32(operators ? 0 : 1), ignore_ops, skip_ops, csc, Int32(0))
     return a, keep
 end
 

@@ -52,6 +52,7 @@ class TmArgs(C.Structure):
         ("ignore_ops", C.c_int32),
         ("skip_ops", C.c_int32),  # bit m: matrix m is not wanted (neither counted, written nor copied home)
         ("given", Csc * 5),  # operators the caller passes (transportmatrix's Tadv = / TκH = / TκVML = / TκVdeep = keywords)
+        ("kept_ops", C.c_int32),  # bit m (TκH, TκVML, TκVdeep): the output arrays hold what this context last wrote there (_dev only)
     ]
 
 

@@ -94,7 +94,9 @@ struct otmb_ctx {
     i64 tm_sticky_step = -1;
     std::string tm_sticky_msg;
     i64 tm_failed_step = -1;         // what the last otmb_transportmatrix_result found
-    struct TmStepRec { void *colptrT, *rowvalT, *nzvalT; i64 n_wet, nnz_base0; int ignore_ops; };
+    struct TmStepRec { void *colptrT, *rowvalT, *nzvalT; i64 n_wet, nnz_base0; int ignore_ops; unsigned wrote, kept; uint64_t serial; };
+                                     // (wrote / kept: the operators m = 2..4 the step stored / took from an earlier step, otmb_tm_args.kept_ops)
+    uint64_t tm_serial = 0;          // asynchronous steps issued on this context so far
     std::vector<TmStepRec> tm_rec;   // T's output arrays of the pending steps [tm_first, tm_next) (compaction after exact cancellation)
     struct TmStepResult { int32_t status; i64 nnz[5]; };
     std::vector<TmStepResult> tm_hist;  // verdict and nnz of every step since the previous otmb_transportmatrix_result
@@ -117,6 +119,26 @@ struct otmb_ctx {
     uint64_t given_epoch = 1;
     int given_state[5] = {0, 0, 0, 0, 0};  // the last plan's treatment of operator m: 0 not given, 1 derived, 2 foreign, 3 derived pattern with other values (otmb_ctx_given_state)
     long given_checks = 0;                 // comparing passes run so far (tests: the verdict is cached)
+    // ---- otmb_tm_args.kept_ops: what the last call that STORED operator m (TκH, TκVML, TκVdeep) wrote, and for which arguments.  A kept bit is
+    // honoured only when the record matches the call; every call that writes the slot refreshes it, every call that leaves it unwritten drops it.
+    struct KeptRecord {
+        bool valid = false;
+        bool nnz_known = false;   // the writing step has been folded (asynchronous) or was synchronous
+        uint64_t serial = 0;      // the writing asynchronous step (tm_serial), 0: a synchronous fill
+        uint64_t epoch = 0;       // given_epoch: otmb_ctx_forget_given and host uploads of grid arrays bump it
+        const void *colptr = nullptr, *rowval = nullptr, *nzval = nullptr;
+        int64_t cap = 0;
+        const void *lwet3d = nullptr, *lwet = nullptr, *v3d = nullptr, *thk = nullptr, *edge[4] = {nullptr, nullptr, nullptr, nullptr},
+                   *dist[4] = {nullptr, nullptr, nullptr, nullptr}, *area = nullptr, *zt = nullptr, *ml = nullptr;
+        int64_t nx = 0, ny = 0, nz = 0, n_wet = 0, wet_base = 0, nnz_base = 0;
+        int topo = -1;
+        double kappa = 0.0;
+        int64_t nnz = 0;
+    } kept_rec[5];
+    // ... and, in the order the asynchronous steps were issued, the most recent folded step that wrote operator m: its nnz and status are those of
+    // every later step that kept m (fold_pending)
+    int64_t kept_fold_nnz[5] = {0, 0, 0, 0, 0};
+    int32_t kept_fold_status[5] = {0, 0, 0, 0, 0};
     DevBuf given_tmp[6];                   // temporaries of the foreign path's sparse adds: two (colptr, rowval, nzval) triples
     CooPlan coo;
     SpPlan sp;

@@ -390,6 +390,7 @@ int32_t otmb_transportmatrix_plan(otmb_ctx *ctx, const otmb_tm_args *a, int64_t 
     const size_t P = (size_t)(a->nx * a->ny), G = P * (size_t)a->nz;
     otmb_tm_args d = *a;
     d.push_mask = nullptr;  // host entry point: a caller's mask pointer would be host memory; derive it on the device
+    d.kept_ops = 0;         // (the promise covers device output arrays of the _dev entry points: these outputs are staging slots)
     const void *p;
     otmb_tm_plan_invalidate(ctx);
     Uploads up;

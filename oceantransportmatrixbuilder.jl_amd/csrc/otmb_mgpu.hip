@@ -272,6 +272,7 @@ void plan_slab(otmb_mgpu *mg, int s, const otmb_tm_args *a, const std::function<
     d.nz = nze;
     d.n_wet = sl.n_own;
     d.push_mask = nullptr;
+    d.kept_ops = 0;  // (the slabs' outputs are staging: no promise)
     std::vector<OtmbXferItem> up;
     int32_t r;
     void *p;

@@ -52,6 +52,7 @@ struct TmPlan {
     unsigned skip = 0;         // matrices the kernels neither count nor write (TmParams.skip)
     bool want_t = true;        // the caller wants T (otmb_tm_args.skip_ops bit 0 clear)
     i64 built_nnz[5] = {0, 0, 0, 0, 0};  // (foreign) the counts of the matrices the kernel writes; nnz[0] is then the sparse adds' bound
+    unsigned kept = 0;         // (subset of skip) otmb_tm_args.kept_ops honoured: the operator is where the previous write left it
 };
 
 // fields of the packed count word (T:11 | Tadv:11 | TκH:11 | TκVML:10 | TκVdeep:10) that belong to the matrices NOT in `skip`
@@ -971,6 +972,40 @@ static int32_t classify_given(otmb_ctx *ctx, const otmb_tm_args &a, TmPlan &pl) 
     return OTMB_OK;
 }
 
+// ---- otmb_tm_args.kept_ops (host side) ------------------------------------------------------------------------------------------
+// The operators a caller may promise to have kept: functions of the grid and κ alone (src/matrixbuilding.jl:51-120)
+static const unsigned KEPT_OPS = (1u << OTMB_TKH) | (1u << OTMB_TKVML) | (1u << OTMB_TKVDEEP);
+static double kept_kappa(const otmb_tm_args &a, int m) { return m == OTMB_TKH ? a.kappa_h : m == OTMB_TKVML ? a.kappa_vml : a.kappa_vdeep; }
+// Does the record of operator m describe what this call would write?  out: the output arrays and capacity (two-phase plan: not known yet, NULL).
+static bool kept_matches(const otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl, int m, const void *const out[3], i64 cap) {
+    const otmb_ctx::KeptRecord &r = ctx->kept_rec[m];
+    if (!r.valid || r.epoch != ctx->given_epoch) return false;
+    if (out && (r.colptr != out[0] || r.rowval != out[1] || r.nzval != out[2] || r.cap != cap)) return false;
+    if (r.lwet3d != a.lwet3d || r.lwet != a.lwet || r.v3d != a.v3d || r.thk != a.thkcello || r.area != a.area2d || r.zt != a.zt ||
+        r.ml != a.mlotst)
+        return false;
+    for (int d = 0; d < 4; ++d)
+        if (r.edge[d] != a.edge_length[d] || r.dist[d] != a.dist_nbr[d]) return false;
+    return r.nx == a.nx && r.ny == a.ny && r.nz == a.nz && r.n_wet == a.n_wet && r.wet_base == pl.wet_base && r.nnz_base == pl.nnz_base[m] &&
+           r.topo == a.topology && r.kappa == kept_kappa(a, m);
+}
+// after a call has stored operator m into out[0..2] (nnz: its count, or < 0 while the asynchronous step `serial` is pending)
+static void kept_store(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl, int m, void *const out[3], i64 cap, i64 nnz, uint64_t serial) {
+    otmb_ctx::KeptRecord &r = ctx->kept_rec[m];
+    r.valid = true; r.epoch = ctx->given_epoch; r.serial = serial;
+    r.colptr = out[0]; r.rowval = out[1]; r.nzval = out[2]; r.cap = cap;
+    r.lwet3d = a.lwet3d; r.lwet = a.lwet; r.v3d = a.v3d; r.thk = a.thkcello; r.area = a.area2d; r.zt = a.zt; r.ml = a.mlotst;
+    for (int d = 0; d < 4; ++d) { r.edge[d] = a.edge_length[d]; r.dist[d] = a.dist_nbr[d]; }
+    r.nx = a.nx; r.ny = a.ny; r.nz = a.nz; r.n_wet = a.n_wet; r.wet_base = pl.wet_base; r.nnz_base = pl.nnz_base[m];
+    r.topo = a.topology; r.kappa = kept_kappa(a, m);
+    r.nnz_known = nnz >= 0; r.nnz = nnz >= 0 ? nnz : 0;
+}
+// every slot this call writes or leaves unwritten (all but the kept ones) loses its record before anything is enqueued
+static void kept_drop(otmb_ctx *ctx, unsigned keep) {
+    for (int m = OTMB_TKH; m <= OTMB_TKVDEEP; ++m)
+        if (!((keep >> m) & 1u)) ctx->kept_rec[m].valid = false;
+}
+
 // ignore: otmb_tm_args.ignore_ops -- errors that only an operator the caller already has would have raised
 static int32_t check_flags(otmb_ctx *ctx, const int *f = nullptr, int ignore = 0) {
     if (!f) f = ctx->h_flags;
@@ -1066,6 +1101,24 @@ static int32_t fold_pending(otmb_ctx *ctx) {
         const size_t q = (size_t)(s - ctx->tm_first);
         r.status = check_flags(ctx, f, q < ctx->tm_rec.size() ? ctx->tm_rec[q].ignore_ops : 0);  // sets ctx->err
         for (int m = 0; m < 5; ++m) r.nnz[m] = tot[m];
+        if (q < ctx->tm_rec.size()) {  // otmb_tm_args.kept_ops: a kept operator is what the most recent step that wrote it left
+            const otmb_ctx::TmStepRec &rec = ctx->tm_rec[q];
+            for (int m = OTMB_TKH; m <= OTMB_TKVDEEP; ++m) {
+                if ((rec.kept >> m) & 1u) {
+                    r.nnz[m] = ctx->kept_fold_nnz[m];
+                    if (!r.status && ctx->kept_fold_status[m]) r.status = ctx->kept_fold_status[m];
+                } else if ((rec.wrote >> m) & 1u) {
+                    ctx->kept_fold_nnz[m] = tot[m];
+                    // (stores that may be incomplete: what relied on them fails alike; the record is dropped on any failure)
+                    ctx->kept_fold_status[m] = (f[FLAG_NONCANONICAL] || f[FLAG_COUNT_MISMATCH] || f[FLAG_CAPACITY]) ? r.status : 0;
+                    otmb_ctx::KeptRecord &kr = ctx->kept_rec[m];
+                    if (kr.valid && kr.serial == rec.serial) {  // (this step is still the record's writer)
+                        if (r.status) kr.valid = false;
+                        else { kr.nnz = tot[m]; kr.nnz_known = true; }
+                    }
+                }
+            }
+        }
         if (r.status && !ctx->tm_sticky) { ctx->tm_sticky = r.status; ctx->tm_sticky_step = s; ctx->tm_sticky_msg = ctx->err; }
         if (!r.status && f[FLAG_T_CANCEL] && q < ctx->tm_rec.size()) {
             const otmb_ctx::TmStepRec &rec = ctx->tm_rec[q];
@@ -1164,6 +1217,14 @@ int32_t otmb_transportmatrix_plan_dev(otmb_ctx *ctx, const otmb_tm_args *a, int6
     pl.args = *a;
     pl.ntiles = ntiles;
     if ((rc = classify_given(ctx, *a, pl))) return rc;  // (may run the comparing pass: before anything of this plan is on the stream)
+    // otmb_tm_args.kept_ops: a record whose count is known (not a pending asynchronous step's) and no sparse add that would read the operator
+    pl.kept = 0;
+    if (!pl.foreign && ctx->tm_next == ctx->tm_first)
+        for (int m = OTMB_TKH; m <= OTMB_TKVDEEP; ++m)
+            if ((((unsigned)a->kept_ops & KEPT_OPS) >> m) & 1u && !((pl.skip >> m) & 1u) && ctx->kept_rec[m].nnz_known &&
+                kept_matches(ctx, *a, pl, m, nullptr, 0))
+                pl.kept |= 1u << m;
+    pl.skip |= pl.kept;
     TmParams p;
     fill_params(p, *a, ctx, &pl);
     int *dflags = (int *)ctx->flags.p;
@@ -1201,6 +1262,8 @@ int32_t otmb_transportmatrix_plan_dev(otmb_ctx *ctx, const otmb_tm_args *a, int6
     }
     if ((rc = check_flags(ctx, nullptr, a->ignore_ops | (int)pl.given))) return rc;
     for (int m = 0; m < 5; ++m) nnz[m] = pl.nnz[m] = pl.built_nnz[m] = ctx->h_tot[m];  // (0 for what is not materialised)
+    for (int m = OTMB_TKH; m <= OTMB_TKVDEEP; ++m)
+        if ((pl.kept >> m) & 1u) nnz[m] = pl.nnz[m] = ctx->kept_rec[m].nnz;  // (kept: the count of the write it was kept from)
     if (pl.foreign && pl.want_t) {
         // T = ((Tadv + TκH) + TκVML) + TκVdeep by the device sparse add (:147): its pattern is the union of the four operands', at most the
         // sum of their counts -- what the caller's T arrays must hold until otmb_transportmatrix_nnz gives the final count
@@ -1237,6 +1300,17 @@ int32_t otmb_transportmatrix_fill_dev(otmb_ctx *ctx, int64_t *const colptr[5], i
     TmParams p;
     fill_params(p, pl.args, ctx, &pl);
     p.rho_in_fill = pl.rho_in_fill ? 1 : 0;
+    // a kept operator must be handed the arrays its record names (and nothing has touched the record since the plan)
+    for (int m = OTMB_TKH; m <= OTMB_TKVDEEP; ++m) {
+        const void *out[3] = {colptr[m], rowval[m], nzval[m]};
+        const otmb_ctx::KeptRecord &r = ctx->kept_rec[m];
+        if (((pl.kept >> m) & 1u) && !(kept_matches(ctx, pl.args, pl, m, out, r.cap) && r.nnz_known && r.nnz == pl.nnz[m])) {
+            kept_drop(ctx, 0);
+            pl.valid = false;
+            return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "kept_ops: the output arrays of a kept operator are not the ones its record names (plan again without the bit)");
+        }
+    }
+    kept_drop(ctx, pl.kept);
     for (int m = 0; m < 5; ++m) {
         const bool wanted = !((pl.skip >> m) & 1u) || (m == 0 && pl.foreign && pl.want_t);  // (T of a foreign build: written by the sparse adds below)
         if (wanted && (!colptr[m] || (pl.nnz[m] > 0 && (!rowval[m] || !nzval[m])))) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null output");
@@ -1264,6 +1338,16 @@ int32_t otmb_transportmatrix_fill_dev(otmb_ctx *ctx, int64_t *const colptr[5], i
     // buffers sized from otmb_transportmatrix_nnz would overflow them -- plan again instead
     pl.valid = false;
     if ((rc = check_flags(ctx, nullptr, pl.args.ignore_ops | (int)pl.given))) return rc;
+    // the operators this fill stored: their records (a synchronous write, count known) -- only when no asynchronous step is pending, whose fold
+    // would take its counts for the steps that kept from IT
+    if (ctx->tm_next == ctx->tm_first)
+        for (int m = OTMB_TKH; m <= OTMB_TKVDEEP; ++m) {
+            void *out[3] = {p.colptr[m], p.rowval[m], p.nzval[m]};
+            if (!((pl.skip >> m) & 1u)) {
+                kept_store(ctx, pl.args, pl, m, out, 0, pl.nnz[m], 0);
+                ctx->kept_fold_nnz[m] = pl.nnz[m]; ctx->kept_fold_status[m] = 0;  // (what an asynchronous step that keeps from it reports)
+            }
+        }
     if (pl.foreign && pl.want_t) return foreign_sum(ctx, pl, p);
     if (pl.skip & 1u) return OTMB_OK;  // (no T: nothing to compact)
     if (ctx->h_flags[FLAG_T_CANCEL]) {
@@ -1355,6 +1439,16 @@ static int32_t transportmatrix_dev_impl(otmb_ctx *ctx, const otmb_tm_args *a, in
     // comparing pass and waits for its verdict: one stream synchronisation, like the tile order); a foreign one needs the two-phase protocol
     if ((rc = classify_given(ctx, *a, pl))) return rc;
     if (pl.foreign && pl.want_t) return otmb_fail(ctx, OTMB_ERR_GIVEN_FOREIGN);
+    // operators the caller kept (otmb_tm_args.kept_ops) whose record matches this call: re-derived in registers (T needs them), neither counted
+    // nor stored -- their nnz come from the step that wrote them (fold_pending).  Every other operator slot loses its record here.
+    pl.kept = 0;
+    for (int m = OTMB_TKH; m <= OTMB_TKVDEEP; ++m) {
+        const void *out[3] = {colptr[m], rowval[m], nzval[m]};
+        if ((((unsigned)a->kept_ops & KEPT_OPS) >> m) & 1u && !((pl.skip >> m) & 1u) && kept_matches(ctx, *a, pl, m, out, capacity[m]))
+            pl.kept |= 1u << m;
+    }
+    pl.skip |= pl.kept;
+    kept_drop(ctx, pl.kept);
     TmParams p;
     fill_params(p, *a, ctx, &pl);
     p.umo = fu.umo; p.vmo = fu.vmo; p.fillv = fu.fill; p.fused = fu.kind;
@@ -1435,7 +1529,13 @@ static int32_t transportmatrix_dev_impl(otmb_ctx *ctx, const otmb_tm_args *a, in
     }
     HIP_TRY(ctx, hipGetLastError());
     if (p.next_state) ctx->ring_clean |= 1ull << slot_after;
-    ctx->tm_rec.push_back({p.colptr[0], p.rowval[0], p.nzval[0], (i64)a->n_wet, p.nnz_base[0], (int)a->ignore_ops | (int)pl.given});
+    const uint64_t serial = ++ctx->tm_serial;
+    const unsigned wrote = KEPT_OPS & ~pl.skip;
+    for (int m = OTMB_TKH; m <= OTMB_TKVDEEP; ++m) {
+        void *out[3] = {p.colptr[m], p.rowval[m], p.nzval[m]};
+        if ((wrote >> m) & 1u) kept_store(ctx, *a, pl, m, out, capacity[m], -1, serial);  // (its nnz when the step is folded)
+    }
+    ctx->tm_rec.push_back({p.colptr[0], p.rowval[0], p.nzval[0], (i64)a->n_wet, p.nnz_base[0], (int)a->ignore_ops | (int)pl.given, wrote, pl.kept, serial});
     ctx->tm_next += 1;
     pl.onepass_pending = true;
     return OTMB_OK;

@@ -6,6 +6,7 @@ All arrays are flat torch tensors whose memory is Julia's column-major (nx,ny,nz
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -176,6 +177,7 @@ class DeviceAssembler:
             given[name] = (cp, rv, nz)
         self.given = given
         self._given_key = None
+        self._forget_kept()  # (a given operator's slot is left unwritten: the library drops its record too)
 
     def _given_versions(self):
         ts = [self.lwet3d, self.lwet, self.v3d, self.thk, self.area, self.zt, *self.edge, *self.dist]
@@ -186,6 +188,7 @@ class DeviceAssembler:
     def makeindices(self):
         """otmb_makeindices_dev on the resident v3D (src/matrixbuilding.jl:10-24)."""
         self._mask_key = None
+        self._forget_kept()
         self.given, self._given_key = {}, None  # (operators of another grid)  # (fluxes of an earlier facefluxes call no longer come with counts / a mask for THESE indices)
         self.lwet3d = self._empty(self.G, torch.int64)
         self.lwet = self._empty(self.G, torch.int64)
@@ -324,12 +327,14 @@ class DeviceAssembler:
             self._count_tables()
         self._mask_key = None
         a = self._args([self.phi_top] * 6)
+        a.kept_ops, kept = self._kept_ops(out)
         cp, rv, nz = self._out_ptrs(out)
         caps = (C.c_int64 * 5)(*[self.N * k + 1 for k in self.PER_COLUMN_MAX])
         self._note("_ff_seq")
-        self.ctx.check(self.lib.otmb_step_dev(self.ctx.handle, umo.data_ptr(), vmo.data_ptr(), int(umo.dtype == torch.float32), float(fill),
-                                              self.wetflags.data_ptr(), self.count_tables.data_ptr(), self.phi_top.data_ptr(), C.byref(a),
-                                              C.byref(cp), C.byref(rv), C.byref(nz), C.byref(caps)))
+        self._check(self.lib.otmb_step_dev(self.ctx.handle, umo.data_ptr(), vmo.data_ptr(), int(umo.dtype == torch.float32), float(fill),
+                                           self.wetflags.data_ptr(), self.count_tables.data_ptr(), self.phi_top.data_ptr(), C.byref(a),
+                                           C.byref(cp), C.byref(rv), C.byref(nz), C.byref(caps)))
+        self._kept_written(out, kept)
         self._note("_tm_seq")
         self._ff_pending = getattr(self, "_ff_pending", 0) + 1
         return out
@@ -348,6 +353,8 @@ class DeviceAssembler:
         ff_first = True
         if bad is not None and err is not None and err.step is not None and bad < len(ff_seq) and err.step < len(tm_seq):
             ff_first = ff_seq[bad] < tm_seq[err.step]  # which of the two calls was issued first
+        if bad is not None or err is not None:
+            self._forget_kept()
         if bad is not None and (err is None or err.step is None or ff_first):
             where = f" (asynchronous step {bad + 1} of {n})" if n > 1 else ""
             raise capi.OtmbError(8, self.lib.otmb_status_string(8).decode() + where, step=bad)
@@ -391,23 +398,81 @@ class DeviceAssembler:
         skip = set(getattr(self, "given", None) or ())
         return tuple(capi.ptr_array(5, [None if m in skip else out[m][q].data_ptr() for m in MATS]) for q in range(3))
 
+    # ---- kept operators (otmb_tm_args.kept_ops) ---------------------------------------------------------------------------------------------
+    # TκH, TκVML and TκVdeep depend on the grid, κ and mlotst alone.  An output set whose three operators the library wrote in an earlier
+    # successful call, untouched by torch since (the _version of its nine tensors is what it was then), is handed back with the promise: the fill
+    # pass then stores T and Tadv only.  The library checks the promise against its own record and writes in full where it does not hold.
+    KEPT = ("TκH", "TκVML", "TκVdeep")
+
+    def _forget_kept(self):
+        """The next call writes all five matrices (grid, κ, given operators changed; outputs overwritten; an error)."""
+        self._kept = None
+        self._kept_last = ()
+
+    def _kept_key(self, out):
+        # the output set's nine tensors (by identity: a recycled address is another set) and every grid array the three operators are derived from
+        ts = [t for m in self.KEPT for t in out[m]]
+        grid = [self.lwet3d, self.lwet, self.v3d, self.thk, self.area, self.zt, self.mlotst, *self.edge, *self.dist]
+        return ([weakref.ref(t) for t in ts], tuple((t.data_ptr(), t._version) for t in ts + grid) + tuple(self.kappa))
+
+    def _kept_ops(self, out):
+        """kept_ops for a call into `out`, and the names it covers."""
+        self._kept_last = ()
+        rec = getattr(self, "_kept", None)
+        if rec is None or getattr(self, "given", None) or getattr(self, "only_T", False):
+            return 0, ()
+        refs, key = self._kept_key(out)
+        if rec[1] != key or any(r() is not t() for r, t in zip(rec[0], refs)):
+            return 0, ()
+        return sum(1 << MATS.index(m) for m in self.KEPT), self.KEPT
+
+    def _kept_written(self, out, kept):
+        """After a call into `out` was accepted: it wrote (or kept) the three operators unless some were given / not wanted."""
+        self._kept_last = kept
+        off = getattr(self, "given", None) or getattr(self, "only_T", False) or os.environ.get("OTMB_KEPT", "1") == "0"  # (OTMB_KEPT=0: A/B)
+        self._kept = None if off else self._kept_key(out)
+
+    def _kept_steady(self):
+        """The operators a step of this loop does not store: those the last call kept, or -- after a full write that left the promise live -- those
+        the next call will keep (what every launch after the first one of a time loop writes: bench.py's roofline reads this after its extras)."""
+        return set(getattr(self, "_kept_last", ())) | (set(self.KEPT) if getattr(self, "_kept", None) is not None else set())
+
+    def _check(self, rc):
+        try:
+            self.ctx.check(rc)
+        except capi.OtmbError:
+            self._forget_kept()
+            raise
+
     def plan(self, phi):
         a = self._args(phi)
+        if self.out is not None:
+            a.kept_ops, kept = self._kept_ops(self.out)
+        else:
+            kept = ()
         nnz = (C.c_int64 * 5)()
-        self.ctx.check(self.lib.otmb_transportmatrix_plan_dev(self.ctx.handle, C.byref(a), C.byref(nnz)))
+        self._check(self.lib.otmb_transportmatrix_plan_dev(self.ctx.handle, C.byref(a), C.byref(nnz)))
         self.nnz = [int(x) for x in nnz]
+        self._plan_kept = (phi, kept)
         return self.nnz
 
     def fill(self):
         """Write the five CSC matrices into device tensors (allocated once per capacity)."""
         if self.out is None or any(self.out[m][1].numel() < self.nnz[k] for k, m in enumerate(MATS)):
+            phi, kept = getattr(self, "_plan_kept", (None, ()))
+            self._forget_kept()
+            if kept:  # (the plan counted on the old arrays of the kept operators: plan again without the promise, then allocate)
+                self.plan(phi)
             self._out_cap = None
             self.out = {m: (torch.empty(self.N + 1, dtype=torch.int64, device=self.device),
                             torch.empty(max(self.nnz[k], 1) + self.nnz[k] // 64, dtype=torch.int64, device=self.device),
                             torch.empty(max(self.nnz[k], 1) + self.nnz[k] // 64, dtype=torch.float64, device=self.device))
                         for k, m in enumerate(MATS)}
         cp, rv, nz = self._out_ptrs(self.out)
-        self.ctx.check(self.lib.otmb_transportmatrix_fill_dev(self.ctx.handle, C.byref(cp), C.byref(rv), C.byref(nz)))
+        kept = getattr(self, "_plan_kept", (None, ()))[1]
+        self._plan_kept = (None, ())
+        self._check(self.lib.otmb_transportmatrix_fill_dev(self.ctx.handle, C.byref(cp), C.byref(rv), C.byref(nz)))
+        self._kept_written(self.out, kept)
         final = (C.c_int64 * 5)()
         self.ctx.check(self.lib.otmb_transportmatrix_nnz(self.ctx.handle, C.byref(final)))
         self.nnz = [int(x) for x in final]  # T's planned count is an upper bound
@@ -443,6 +508,7 @@ class DeviceAssembler:
         output set is smaller than `min_output_bytes` (1 degree: the candidates differ by 1-2 % there, nothing to choose).  Returns a record of every
         candidate's time (bench.py prints it)."""
         rec = {"candidates": int(candidates), "facefluxes_ms": [], "fill_ms": [], "chosen": None}
+        self._forget_kept()  # (every candidate output set is written in full: what is timed is the full fill pass)
         if candidates < 2:
             return rec
         free_b, _ = torch.cuda.mem_get_info(self.device)
@@ -482,8 +548,10 @@ class DeviceAssembler:
         phi = self.facefluxes(umo, vmo, fill)
         outs = [self.new_output_set() for _ in range(candidates)]
         for o in outs:
-            rec["fill_ms"].append(timed(self.FILL_KERNELS, lambda: self.transportmatrix_onepass(phi, sync=False, out=o)))
+            self._forget_kept()
+            rec["fill_ms"].append(timed(self.FILL_KERNELS, lambda: (self._forget_kept(), self.transportmatrix_onepass(phi, sync=False, out=o))))
             self.result()
+        self._forget_kept()
         ko = int(np.argmin(rec["fill_ms"]))
         self.out, self._out_cap = outs[ko], [self.N * k + 1 for k in self.PER_COLUMN_MAX]
         del outs, o
@@ -501,10 +569,12 @@ class DeviceAssembler:
         if out is None:
             out = self.out
         a = self._args(phi)
+        a.kept_ops, kept = self._kept_ops(out)
         cp, rv, nz = self._out_ptrs(out)
         caps = (C.c_int64 * 5)(*[self.N * k + 1 for k in self.PER_COLUMN_MAX])
-        self.ctx.check(self.lib.otmb_transportmatrix_dev(self.ctx.handle, C.byref(a), C.byref(cp), C.byref(rv),
-                                                         C.byref(nz), C.byref(caps)))
+        self._check(self.lib.otmb_transportmatrix_dev(self.ctx.handle, C.byref(a), C.byref(cp), C.byref(rv),
+                                                      C.byref(nz), C.byref(caps)))
+        self._kept_written(out, kept)
         self._note("_tm_seq")
         return self.result() if sync else out
 
@@ -513,6 +583,7 @@ class DeviceAssembler:
         rc = self.lib.otmb_transportmatrix_result(self.ctx.handle, C.byref(nnz))
         self._tm_seq = []
         if rc != capi.OK:
+            self._forget_kept()
             step = C.c_int64(-1)
             self.lib.otmb_transportmatrix_failed_step(self.ctx.handle, C.byref(step))
             raise capi.OtmbError(rc, self.lib.otmb_last_error(self.ctx.handle).decode("utf-8"),
@@ -626,21 +697,27 @@ class DeviceAssembler:
 
     def algorithmic_bytes_split(self):
         """(bytes read, bytes written) of algorithmic_bytes().  An operator the caller passes and the fill pass re-derives (set_given) is
-        neither read nor written: its 16 nnz + 8 (N + 1) bytes are not part of the pass."""
+        neither read nor written: its 16 nnz + 8 (N + 1) bytes are not part of the pass.  Nor is one the last call kept where the previous
+        write left it, or that the next call keeps (otmb_tm_args.kept_ops: a time loop's steady state)."""
         n3d = 9 + (1 if self.rho is not None else 0)
-        skip = set(getattr(self, "given", None) or ())
+        skip = set(getattr(self, "given", None) or ()) | self._kept_steady()
         return (8 * self.G * n3d + 80 * self.nx * self.ny + 8 * self.nz,
                 sum(16 * z + 8 * (self.N + 1) for m, z in zip(MATS, self.nnz) if m not in skip))
 
     def fill_pass_stream_mix(self):
         """What an ideal streaming kernel reaches over the fill pass's OWN arrays (otmb_ctx_stream_mix): its ten 3-D inputs (+ the 2-D
         metrics) read once, its fifteen output arrays written once at their actual lengths, in as many slices as the pass has tiles.
-        DESTROYS the matrices of self.out: call it after the results have been used.  {columns per slice: GB/s}."""
+        DESTROYS the matrices of self.out: call it after the results have been used.  {columns per slice: GB/s}.  Operators the last call kept
+        (otmb_tm_args.kept_ops) are not among the pass's outputs."""
         b8 = lambda t, n=None: (t.data_ptr(), 8 * (t.numel() if n is None else n))
+        skip = self._kept_steady()
+        self._forget_kept()
         ins = [b8(p) for p in self.phi] + [b8(self.v3d), b8(self.thk), b8(self.lwet3d)] + ([b8(self.rho)] if self.rho is not None else [])
         ins += [b8(t) for t in (*self.edge, *self.dist, self.area, self.mlotst)]
         outs = []
         for k, m in enumerate(MATS):
+            if m in skip:
+                continue
             cp, rv, nz = self.out[m]
             outs += [b8(cp, self.N + 1), b8(rv, self.nnz[k]), b8(nz, self.nnz[k])]
         # the fill pass's own granularity (256 columns per slice) and longer slices: a plain stream likes them longer where the grid is large
