@@ -371,7 +371,12 @@ typedef struct {
                                   * asynchronous step that relied on a step which then failed reports that step's status.  Two-phase
                                   * protocol: fill must be handed the recorded arrays for a kept operator (otherwise OTMB_ERR_INVALID_ARG:
                                   * plan again without the bit).  A write to those arrays the caller does not tell the library about
-                                  * (another library call, a raw pointer) must be followed by a call without the bit.                  */
+                                  * (another library call, a raw pointer) must be followed by a call without the bit.  When all three
+                                  * bits are honoured, TκH's values are not re-derived either: they come from a table this context
+                                  * keeps (built by the first such call after any call without the TκH bit; OTMB_KEPT_HTAB=0: re-derived),
+                                  * so T itself then depends on it.  A write the library is not told about to a grid array TκH is
+                                  * derived from (v3d, thkcello, edge_length, dist_nbr, lwet3d, lwet) must therefore also be followed by
+                                  * a call without the bit.                                                                              */
 } otmb_tm_args;
 /* The verdicts on otmb_tm_args.given are keyed to array ADDRESSES (the given matrix's and the gridmetrics / indices arrays') and κ.
  * A device-resident caller that rewrites one of those arrays in place calls this before the next transportmatrix; the host-pointer
@@ -382,6 +387,9 @@ int32_t otmb_ctx_forget_given(otmb_ctx *ctx);
 int32_t otmb_ctx_given_state(const otmb_ctx *ctx, int32_t m);
 /* ... and how many comparing passes the context has run so far (a time loop with resident arrays runs ONE). */
 int64_t otmb_ctx_given_checks(const otmb_ctx *ctx);
+/* ... and whether the last fill pass on this context that kept all three diffusive operators (otmb_tm_args.kept_ops) read TκH from the
+ * context's table: 1 yes, 0 no (OTMB_KEPT_HTAB=0, nx < 3, the table could not be allocated), -1 no such fill yet. */
+int32_t otmb_ctx_kept_htab(const otmb_ctx *ctx);
 
 /* Two-phase protocol so the CALLER allocates the outputs (Julia owns its SparseMatrixCSC buffers).
  * plan: the nnz of the four operator matrices (exact: their patterns depend on the wet mask, the flux

@@ -99,6 +99,7 @@ SYMBOLS = {
     "otmb_ctx_forget_given": (C.c_int32, [_vp]),
     "otmb_ctx_given_state": (C.c_int32, [_vp, C.c_int32]),
     "otmb_ctx_given_checks": (C.c_int64, [_vp]),
+    "otmb_ctx_kept_htab": (C.c_int32, [_vp]),
     "otmb_last_error": (C.c_char_p, [_vp]),
     "otmb_status_string": (C.c_char_p, [C.c_int32]),
     "otmb_version": (C.c_char_p, []),
@@ -304,6 +305,10 @@ class Context:
     def given_state(self, m):
         """How the last plan / _dev call treated operator m (index into MATS): 0 not given, 1 given and derived, 2 given and foreign, 3 given with the derived rows and other values (another κ: read by the fill pass)."""
         return int(self._lib.otmb_ctx_given_state(self._h, int(m)))
+
+    def kept_htab(self):
+        """Whether the last fill that kept TκH, TκVML and TκVdeep read TκH from the context's table: 1 yes, 0 no, -1 no such fill yet."""
+        return int(self._lib.otmb_ctx_kept_htab(self._h))
 
     def use_own_stream(self):
         self.check(self._lib.otmb_ctx_set_stream(self._h, _vp(0)))

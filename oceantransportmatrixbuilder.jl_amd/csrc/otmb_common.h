@@ -28,7 +28,7 @@ struct SpPlan { const int64_t *I = nullptr, *J = nullptr; const double *V = null
 
 // kernel ids for the optional HIP-event timing (otmb_ctx_timing_*)
 enum {
-    K_TM_COUNT = 0, K_TILESCAN, K_TM_FILL, K_TM_FINISH, K_FACEFLUXES, K_IDX_COUNT, K_IDX_WRITE, K_VELFLUX, K_GM, K_GRIDMETRICS, K_PUSHMASK, K_TM_ORDER, K_FF_BASES, K_NKERNELS
+    K_TM_COUNT = 0, K_TILESCAN, K_TM_FILL, K_TM_FINISH, K_FACEFLUXES, K_IDX_COUNT, K_IDX_WRITE, K_VELFLUX, K_GM, K_GRIDMETRICS, K_PUSHMASK, K_TM_ORDER, K_FF_BASES, K_TM_HTAB, K_NKERNELS
 };
 #define OTMB_TIMING_POOL 2048
 
@@ -139,6 +139,13 @@ struct otmb_ctx {
     // every later step that kept m (fold_pending)
     int64_t kept_fold_nnz[5] = {0, 0, 0, 0, 0};
     int32_t kept_fold_status[5] = {0, 0, 0, 0, 0};
+    // ... and the TκH table of the steps that keep all three operators (otmb_transportmatrix.hip, kept_htab): five doubles per owned wet column and
+    // a NaN word, built for the arguments in htab_key; dropped by every call that does not keep TκH (kept_drop) and by a change of stream
+    DevBuf htab;
+    bool htab_valid = false;
+    KeptRecord htab_key;
+    size_t htab_nofit = 0;  // an allocation of this many bytes failed: the kept fill re-derives TκH instead
+    int htab_used = -1;     // the last fill that kept all three operators read the table (1) or re-derived TκH (0); -1: none yet (otmb_ctx_kept_htab)
     DevBuf given_tmp[6];                   // temporaries of the foreign path's sparse adds: two (colptr, rowval, nzval) triples
     CooPlan coo;
     SpPlan sp;

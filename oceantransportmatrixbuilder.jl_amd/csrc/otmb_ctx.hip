@@ -113,7 +113,7 @@ void otmb_ctx_destroy(otmb_ctx *ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     otmb_tm_plan_free(ctx);
     otmb_xfer_free(ctx);
-    for (DevBuf *b : {&ctx->blocksums, &ctx->blockoffs, &ctx->flags, &ctx->ring, &ctx->stamps, &ctx->tcount, &ctx->tfix[0], &ctx->tfix[1], &ctx->tfix[2], &ctx->tm_sums, &ctx->tm_offs, &ctx->sort[0], &ctx->sort[1], &ctx->sort[2], &ctx->sort[3], &ctx->sort[4], &ctx->ffc_sums[0], &ctx->ffc_sums[1], &ctx->xfer_narrow, &ctx->given_tmp[0], &ctx->given_tmp[1], &ctx->given_tmp[2], &ctx->given_tmp[3], &ctx->given_tmp[4], &ctx->given_tmp[5]})
+    for (DevBuf *b : {&ctx->blocksums, &ctx->blockoffs, &ctx->flags, &ctx->ring, &ctx->stamps, &ctx->tcount, &ctx->tfix[0], &ctx->tfix[1], &ctx->tfix[2], &ctx->tm_sums, &ctx->tm_offs, &ctx->sort[0], &ctx->sort[1], &ctx->sort[2], &ctx->sort[3], &ctx->sort[4], &ctx->ffc_sums[0], &ctx->ffc_sums[1], &ctx->xfer_narrow, &ctx->given_tmp[0], &ctx->given_tmp[1], &ctx->given_tmp[2], &ctx->given_tmp[3], &ctx->given_tmp[4], &ctx->given_tmp[5], &ctx->htab})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : ctx->stage)
         if (b.p) (void)hipFree(b.p);
@@ -130,17 +130,30 @@ void otmb_ctx_destroy(otmb_ctx *ctx) {
     delete ctx;
 }
 
+// A change of stream: the next kept step rebuilds the TκH table in place on the new stream.  Fills enqueued on the old one may still read
+// it (its NaN word is zeroed before the rebuild), so they finish first.
+static void drop_htab(otmb_ctx *ctx) {
+    if (ctx->htab_valid) (void)hipStreamSynchronize(ctx->stream);
+    ctx->htab_valid = false;
+}
+
 int32_t otmb_ctx_set_stream(otmb_ctx *ctx, void *s) {
     if (!ctx) return OTMB_ERR_INVALID_ARG;
     hipStream_t ns = s ? (hipStream_t)s : ctx->own_stream;
-    if (ns != ctx->stream) ctx->order_key = otmb_ctx::OrderKey();  // the cached tile order may still be in flight on the previous stream: build it again here
+    if (ns != ctx->stream) {  // the cached tile order and TκH table may still be in flight on the previous stream: build them again here
+        ctx->order_key = otmb_ctx::OrderKey();
+        drop_htab(ctx);
+    }
     ctx->stream = ns;
     return OTMB_OK;
 }
 
 int32_t otmb_ctx_use_default_stream(otmb_ctx *ctx) {
     if (!ctx) return OTMB_ERR_INVALID_ARG;
-    if (ctx->stream != nullptr) ctx->order_key = otmb_ctx::OrderKey();
+    if (ctx->stream != nullptr) {
+        ctx->order_key = otmb_ctx::OrderKey();
+        drop_htab(ctx);
+    }
     ctx->stream = nullptr;  // HIP's null stream: what torch calls its default stream
     return OTMB_OK;
 }
@@ -159,6 +172,7 @@ int32_t otmb_ctx_forget_given(otmb_ctx *ctx) {
 
 int32_t otmb_ctx_given_state(const otmb_ctx *ctx, int32_t m) { return (ctx && m >= 0 && m < 5) ? ctx->given_state[m] : -1; }
 int64_t otmb_ctx_given_checks(const otmb_ctx *ctx) { return ctx ? (int64_t)ctx->given_checks : -1; }
+int32_t otmb_ctx_kept_htab(const otmb_ctx *ctx) { return ctx ? ctx->htab_used : -1; }
 
 int32_t otmb_ctx_synchronize(otmb_ctx *ctx) {
     if (!ctx) return OTMB_ERR_INVALID_ARG;
@@ -205,7 +219,7 @@ const char *otmb_kernel_name(int32_t k) {
     static const char *names[K_NKERNELS] = {"tm_count_kernel", "tilescan_kernel", "tm_kernel<fill>", "tm_finish_colptr",
                                             "facefluxes_kernel", "indices_kernel<count>", "indices_kernel<write>",
                                             "velocity_flux_kernel", "gm_slopes+gm_dyad", "gridmetrics2d+3d",
-                                            "push_mask_kernel", "tm_order_kernels", "ff_count_bases_kernel"};
+                                            "push_mask_kernel", "tm_order_kernels", "ff_count_bases_kernel", "tm_htab_kernel"};
     return (k >= 0 && k < K_NKERNELS) ? names[k] : "";
 }
 

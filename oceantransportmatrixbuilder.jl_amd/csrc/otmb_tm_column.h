@@ -70,6 +70,11 @@ struct TmParams {
     int count_order;       // counting pass: 0 blockIdx order, 1 XCD-contiguous eighths, 2 XCD-contiguous eighths of `order`
     unsigned nt_order;     // number of tiles (the fill pass's grid may be a few workgroups larger: xcd_position)
     unsigned nheavy;       // `order` starts with this many HEAVY tiles (tripolar seam row: generic column builder), dealt over the XCDs
+    // (kept operators, otmb_tm_args.kept_ops) the context's TκH table: h_regular's five values of every regular owned column w, one array per
+    // slot (H_S ... H_N, htab_n doubles apart), built by tm_htab_kernel; htab_nan: whether a value it stored is NaN.  NULL: TκH is re-derived.
+    const double *htab;
+    i64 htab_n;
+    const int *htab_nan;
 };
 
 // Which position of the tile sequence does workgroup b take?  Workgroups are dealt round-robin over the 8 XCDs (each with its own L2):
@@ -440,7 +445,8 @@ struct Stencil {
     double tC, tE, tW, tS, tN;
     double eW_c, eE_c, eS_c, eN_c, dW_c, dE_c, dS_c, dN_c, eE_w, dE_w, eW_e, dW_e, eN_s, dN_s, eS_n, dS_n, ar, mld;
     double ztk, zta, ztb;
-    double hg[5];  // (HREAD) the first five entries of the given TκH's column c, in its row order: S, row-mates by index, N -- those that exist
+    double hg[5];  // (HREAD) the first five entries of the given TκH's column c, in its row order: S, row-mates by index, N -- those that exist;
+                   // (HTAB) the table's five values of column c, slots H_S ... H_N
 };
 
 // The regular-cell arithmetic on a Stencil -- THE one copy of it (src/matrixbuilding.jl:193-204, :244-296, :348-415, :426-435,
@@ -454,13 +460,36 @@ struct Stencil {
 __device__ __forceinline__ double pick5(const double (&g)[5], unsigned q) {
     return q == 0 ? g[0] : (q == 1 ? g[1] : (q == 2 ? g[2] : (q == 3 ? g[3] : g[4])));
 }
-template <bool HREAD = false>
+// TκH of a regular cell (:348-415, :426-435; oppdir = south away from the seam row, :407) -- THE one copy of it: the fill pass (column_compute)
+// and the kept operators' table (tm_htab_kernel) both call it.  Needs s.tC/tW/tE/tS/tN, s.vC/vW/vE/vS/vN and the 16 edge / distance values.
+// h5: the values of rows S, W, SELF, E, N (whether those rows exist is the caller's wet mask); returns whether a wet neighbour's pair is NaN (:61).
+enum { H_S = 0, H_WC, H_SELF, H_EC, H_N, NHTAB };
+__device__ __forceinline__ bool h_regular(double kH, const Stencil &s, bool wW, bool wE, bool wS, bool wN, double (&h5)[NHTAB]) {
+    const double vC = s.vC, tC = s.tC;
+    double ownW, inW, ownE, inE, ownS, inS, ownN, inN;
+    h_pair(kH, tC, s.eW_c, s.tW, s.eE_w, s.dW_c, vC, s.dE_w, s.vW, ownW, inW);
+    h_pair(kH, tC, s.eE_c, s.tE, s.eW_e, s.dE_c, vC, s.dW_e, s.vE, ownE, inE);
+    h_pair(kH, tC, s.eS_c, s.tS, s.eN_s, s.dS_c, vC, s.dN_s, s.vS, ownS, inS);
+    h_pair(kH, tC, s.eN_c, s.tN, s.eS_n, s.dN_c, vC, s.dS_n, s.vN, ownN, inN);
+    const bool bad = (wW & (isnan(ownW) | isnan(inW))) | (wE & (isnan(ownE) | isnan(inE))) |
+                     (wS & (isnan(ownS) | isnan(inS))) | (wN & (isnan(ownN) | isnan(inN)));
+    double h = NEG0;  // own pushes in direction order W, E, S, N
+    h += wW ? ownW : NEG0;
+    h += wE ? ownE : NEG0;
+    h += wS ? ownS : NEG0;
+    h += wN ? ownN : NEG0;
+    h5[H_S] = -inS; h5[H_WC] = -inW; h5[H_SELF] = h; h5[H_EC] = -inE; h5[H_N] = -inN;
+    return bad;
+}
+
+// HTAB: TκH's values are the table's (s.hg), stored by h_regular for this column; its NaN verdict is raised by the kernel (TmParams.htab_nan).
+template <bool HREAD = false, bool HTAB = false>
 __device__ __forceinline__ void column_compute(const TmParams &p, const Stencil &s, int i, int j, int k, i64 c, Column &col) {
     const int nx = p.nx, ny = p.ny, nz = p.nz, up = p.upwind;
     const bool hS = j > 0, hN = j + 1 < ny, hA = k > 0, hB = k + 1 < nz;
     const i64 xE = s.lE, xW = s.lW, xS = hS ? s.lS : 0, xN = hN ? s.lN : 0, xA = hA ? s.lA : 0, xB = hB ? s.lB : 0;
     const bool wE = xE != 0, wW = xW != 0, wS = xS != 0, wN = xN != 0, wA = xA != 0, wB = xB != 0;
-    const double vC = s.vC, rC = s.rC, tC = s.tC;
+    const double vC = s.vC, rC = s.rC;
 
     // ---- advective pushes towards this cell (:244-296) ----
     const double fE = wE ? sel_pos(s.gE, up) : 0.0;  // east cell pushes its west flux
@@ -538,20 +567,14 @@ __device__ __forceinline__ void column_compute(const TmParams &p, const Stencil 
         col.hh[S_A] = 0; col.hh[S_B] = 0; col.hh[S_FQ] = 0;
         col.phh = ((unsigned)wW << S_WC) | ((unsigned)wE << S_EC) | ((unsigned)wS << S_S) | ((unsigned)wN << S_N) | (any << S_SELF);
     } else {
-        double ownW, inW, ownE, inE, ownS, inS, ownN, inN;
-        h_pair(p.kH, tC, s.eW_c, s.tW, s.eE_w, s.dW_c, vC, s.dE_w, s.vW, ownW, inW);
-        h_pair(p.kH, tC, s.eE_c, s.tE, s.eW_e, s.dE_c, vC, s.dW_e, s.vE, ownE, inE);
-        h_pair(p.kH, tC, s.eS_c, s.tS, s.eN_s, s.dS_c, vC, s.dN_s, s.vS, ownS, inS);
-        h_pair(p.kH, tC, s.eN_c, s.tN, s.eS_n, s.dN_c, vC, s.dS_n, s.vN, ownN, inN);
-        const bool bad = (wW & (isnan(ownW) | isnan(inW))) | (wE & (isnan(ownE) | isnan(inE))) |
-                         (wS & (isnan(ownS) | isnan(inS))) | (wN & (isnan(ownN) | isnan(inN)));
-        if (bad) raise_flag(p.flags, FLAG_TKH_NAN);  // :61
-        double h = NEG0;  // own pushes in direction order W, E, S, N
-        h += wW ? ownW : NEG0;
-        h += wE ? ownE : NEG0;
-        h += wS ? ownS : NEG0;
-        h += wN ? ownN : NEG0;
-        col.hh[S_SELF] = h; col.hh[S_WC] = -inW; col.hh[S_EC] = -inE; col.hh[S_S] = -inS; col.hh[S_N] = -inN;
+        double h5[NHTAB];
+        if (HTAB) {
+#pragma unroll
+            for (int q = 0; q < NHTAB; ++q) h5[q] = s.hg[q];
+        } else if (h_regular(p.kH, s, wW, wE, wS, wN, h5)) {
+            raise_flag(p.flags, FLAG_TKH_NAN);  // :61
+        }
+        col.hh[S_SELF] = h5[H_SELF]; col.hh[S_WC] = h5[H_WC]; col.hh[S_EC] = h5[H_EC]; col.hh[S_S] = h5[H_S]; col.hh[S_N] = h5[H_N];
         col.hh[S_A] = 0; col.hh[S_B] = 0; col.hh[S_FQ] = 0;
         col.phh = ((unsigned)wW << S_WC) | ((unsigned)wE << S_EC) | ((unsigned)wS << S_S) | ((unsigned)wN << S_N) |
                   ((unsigned)(wW | wE | wS | wN) << S_SELF);
@@ -601,6 +624,7 @@ __device__ __forceinline__ void column_compute(const TmParams &p, const Stencil 
 struct TileBase {  // array pointers advanced to the tile's lowest neighbour (uniform per workgroup)
     const char *lw, *v, *thk, *rho, *pe, *pw, *pn, *ps, *pt, *pb, *mk;
     const char *pu, *pv;  // (fused step) umo / vmo, advanced likewise -- in THEIR element size
+    const char *ht;       // (HTAB) the TκH table's slot H_S advanced to the tile's first column
 };
 // (fused step) one mass transport value as Float64 (Array{Float64}(umo), :125-126), by byte offset in units of 8-byte elements
 template <int FUSED> __device__ __forceinline__ double ld_uv(const char *b, unsigned off8) {
@@ -613,7 +637,8 @@ __device__ __forceinline__ i64 ldi(const char *b, unsigned byteoff) { return *(c
 // (fast_presence / facefluxes_kernel<COUNTS>), not here.
 // Returns whether Lwet3D holds c at the cell itself (the canonical-indices check, loaded with the stencil).
 // HREAD: TκH's values come from the given matrix (p.hx at the column's offset hq) instead of thkcello and the 2-D metrics.
-template <int FUSED = 0, bool HREAD = false>
+// HTAB: they come from the context's table (tb.ht, hq = the column's position in the tile) instead of thkcello and the 2-D metrics.
+template <int FUSED = 0, bool HREAD = false, bool HTAB = false>
 __device__ __forceinline__ bool fast_column(const TmParams &p, const TileBase &tb, unsigned oC, int i, int j, int k,
                                             i64 c, Column &col, Stamps &st, i64 hq = 0) {
     const int nx = p.nx, ny = p.ny, nz = p.nz;
@@ -660,10 +685,15 @@ __device__ __forceinline__ bool fast_column(const TmParams &p, const TileBase &t
         const i64 q0 = hq < last ? hq : last, q1 = hq + 1 < last ? hq + 1 : last, q2 = hq + 2 < last ? hq + 2 : last, q3 = hq + 3 < last ? hq + 3 : last,
                   q4 = hq + 4 < last ? hq + 4 : last;
         hg0 = p.hx[q0]; hg1 = p.hx[q1]; hg2 = p.hx[q2]; hg3 = p.hx[q3]; hg4 = p.hx[q4];
+    } else if (HTAB) {  // one value per slot array at the column: read once per step, streamed like ϕ
+        const unsigned o = (unsigned)hq * 8u;
+        const size_t sl = (size_t)p.htab_n * 8u;
+        hg0 = LDPHI(tb.ht, o); hg1 = LDPHI(tb.ht + sl, o); hg2 = LDPHI(tb.ht + 2 * sl, o); hg3 = LDPHI(tb.ht + 3 * sl, o);
+        hg4 = LDPHI(tb.ht + 4 * sl, o);
     }
     double tC = 0, tE = 0, tW = 0, tS = 0, tN = 0;
     double eW_c = 0, eE_c = 0, eS_c = 0, eN_c = 0, dW_c = 0, dE_c = 0, dS_c = 0, dN_c = 0, eE_w = 0, dE_w = 0, eW_e = 0, dW_e = 0, eN_s = 0, dN_s = 0, eS_n = 0, dS_n = 0;
-    if (!HREAD) {
+    if (!HREAD && !HTAB) {
         tC = ldv(tb.thk, oC); tE = ldv(tb.thk, oE); tW = ldv(tb.thk, oW); tS = ldv(tb.thk, oS);
         tN = ldv(tb.thk, oN);
         const char *eWp = (const char *)p.edge[OTMB_DIR_WEST], *eEp = (const char *)p.edge[OTMB_DIR_EAST],
@@ -714,7 +744,7 @@ __device__ __forceinline__ bool fast_column(const TmParams &p, const TileBase &t
     s.eE_w = eE_w; s.dE_w = dE_w; s.eW_e = eW_e; s.dW_e = dW_e; s.eN_s = eN_s; s.dN_s = dN_s; s.eS_n = eS_n; s.dS_n = dS_n;
     s.ar = ar; s.mld = mld; s.ztk = ztk; s.zta = zta; s.ztb = ztb;
     s.hg[0] = hg0; s.hg[1] = hg1; s.hg[2] = hg2; s.hg[3] = hg3; s.hg[4] = hg4;
-    column_compute<HREAD>(p, s, i, j, k, c, col);
+    column_compute<HREAD, HTAB>(p, s, i, j, k, c, col);
     return lC == c;
 }
 

@@ -55,6 +55,9 @@ struct TmPlan {
     unsigned kept = 0;         // (subset of skip) otmb_tm_args.kept_ops honoured: the operator is where the previous write left it
 };
 
+// The operators a caller may promise to have kept (otmb_tm_args.kept_ops): functions of the grid and κ alone (src/matrixbuilding.jl:51-120)
+static constexpr unsigned KEPT_OPS = (1u << OTMB_TKH) | (1u << OTMB_TKVML) | (1u << OTMB_TKVDEEP);
+
 // fields of the packed count word (T:11 | Tadv:11 | TκH:11 | TκVML:10 | TκVdeep:10) that belong to the matrices NOT in `skip`
 static u64 keep_mask(unsigned skip) {
     static const u64 field[5] = {0x7ffull, 0x7ffull << 11, 0x7ffull << 22, 0x3ffull << 33, 0x3ffull << 43};
@@ -168,9 +171,16 @@ static_assert(TM_THREADS == (1 << FFC_TILE_SHIFT), "the counts in facefluxes are
 // fewer L1 requests per column when its values are the derived ones, the only way when they are not (another κH); bit 1 -- DREAD: a given
 // TκVdeep with the derived rows and OTHER values (another κVdeep) is read likewise (TmParams.dcp / dx).  Instantiations, not branches: a uniform
 // branch on dx in the default kernel measured +1 ... 2 % (profiles/r06/call17_dx_*.jsonl).
+// GIVEN bit 2 -- HTAB (alone): all three diffusive operators are kept (otmb_tm_args.kept_ops), so T and Tadv are the only matrices written
+// (TmParams.skip == KEPT_OPS as a constant: the other three staging loops are gone), and a regular column takes its TκH values from the
+// context's table (TmParams.htab: five streamed loads) instead of 5 thkcello + 16 metric loads and 8 divisions.
 template <int FUSED = 0, int GIVEN = 0>
 __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const TmParams p) {
-    constexpr bool HREAD = (GIVEN & 1) != 0, DREAD = (GIVEN & 2) != 0;
+    constexpr bool HREAD = (GIVEN & 1) != 0, DREAD = (GIVEN & 2) != 0, HTAB = (GIVEN & 4) != 0;
+    static_assert(!HTAB || GIVEN == 4, "the table serves the kept operators: nothing is given then");
+// (evaluated where used, as p.skip / p.keep were: a local copy at the top changes the other instantiations' register allocation)
+#define TM_SKIP (HTAB ? KEPT_OPS : p.skip)
+#define TM_KEEP (HTAB ? 0x3fffffull : p.keep)  // (HTAB: the count fields of T and Tadv, keep_mask(KEPT_OPS))
     __shared__ u64 wave_tot[TM_THREADS / 64];
     __shared__ i64 s_prefix[TM_NF];
     __shared__ unsigned s_presum[TM_NF];
@@ -186,6 +196,11 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt_entry)::"memory");
 #endif
     if (p.next_state && blockIdx.x == 0 && tid < (int)(OTMB_TM_STATE_BYTES / sizeof(int))) p.next_state[tid] = 0;
+    // (HTAB) the table's values are not re-derived here: a NaN among them is this step's error as it was when every step derived them (:61)
+    if (HTAB && blockIdx.x == 0) {
+        const int hnan = *p.htab_nan;
+        if (hnan && tid == 0) raise_flag(p.flags, FLAG_TKH_NAN);
+    }
 
     // Workgroups are dealt round-robin over the 8 XCDs (each with its own L2).  Give XCD x the x-th
     // contiguous eighth of the tiles, so that a tile's south/north rows and the levels above/below, which
@@ -260,6 +275,7 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
         tb.pv = (const char *)p.vmo + base_elem * (FUSED == 2 ? 4 : 8);
     }
     tb.mk = nullptr;  // the push mask is read by the counting pass only
+    tb.ht = HTAB ? (const char *)(p.htab + w0) : nullptr;
 
     // ---- 1. the column ----
     // T's rows are RESERVED as the union of the four operators' rows (known without arithmetic); the rows
@@ -285,7 +301,7 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
             bool canonical;
             const bool regular = (p.nx >= 3) && !(p.topo == OTMB_TRIPOLAR && cell.j == p.ny - 1);
             {
-                if (regular) canonical = fast_column<FUSED, HREAD>(p, tb, oC, cell.i, cell.j, cell.k, c, col, st, hq);  // (the value-free input checks ran with the counts)
+                if (regular) canonical = fast_column<FUSED, HREAD, HTAB>(p, tb, oC, cell.i, cell.j, cell.k, c, col, st, HTAB ? (i64)tid : hq);  // (the value-free input checks ran with the counts)
                 else {
                     canonical = ldi(tb.lw, oC) == c;
                     if (canonical) {
@@ -310,7 +326,7 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
                         col.tv[s] = t_value(col, s);
                         if (((uni >> s) & 1u) && col.tv[s] != 0.0) pT |= 1u << s;
                     }
-                    if (pT != uni && !(p.skip & 1u)) raise_flag(p.flags, FLAG_T_CANCEL);
+                    if (pT != uni && !(TM_SKIP & 1u)) raise_flag(p.flags, FLAG_T_CANCEL);
                 }
             }
         }
@@ -318,7 +334,7 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
 
     STAMP(st, 3, 0);  // the column's arithmetic is done
     // ---- 2. packed block scan: T:11 | Tadv:11 | TκH:11 | TκVML:10 | TκVdeep:10 bits ----
-    const u64 mine = ((u64)nU | ((u64)nA << 11) | ((u64)nH << 22) | ((u64)nM << 33) | ((u64)nD << 43)) & p.keep;  // (matrices that are not materialised: TmParams.skip)
+    const u64 mine = ((u64)nU | ((u64)nA << 11) | ((u64)nH << 22) | ((u64)nM << 33) | ((u64)nD << 43)) & TM_KEEP;  // (matrices that are not materialised: TmParams.skip)
     u64 incl = mine;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -370,7 +386,7 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
             if (p.gsum) p.totals[tid] = tot;
             i64 *cp = (tid == 0) ? p.colptr[0] : (tid == 1) ? p.colptr[1] : (tid == 2) ? p.colptr[2] : (tid == 3) ? p.colptr[3] : p.colptr[4];
             const i64 nb = (tid == 0) ? p.nnz_base[0] : (tid == 1) ? p.nnz_base[1] : (tid == 2) ? p.nnz_base[2] : (tid == 3) ? p.nnz_base[3] : p.nnz_base[4];
-            if (!((p.skip >> tid) & 1u)) cp[p.n_own] = nb + tot + 1;
+            if (!((TM_SKIP >> tid) & 1u)) cp[p.n_own] = nb + tot + 1;
         }
     }
 
@@ -382,14 +398,14 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
     if (live) {
 #pragma unroll
         for (int m = 0; m < TM_NF; ++m)
-            if (!((p.skip >> m) & 1u)) p.colptr[m][w] = p.nnz_base[m] + g0[m] + ex[m] + 1;  // (non-temporal here: no gain)
+            if (!((TM_SKIP >> m) & 1u)) p.colptr[m][w] = p.nnz_base[m] + g0[m] + ex[m] + 1;  // (non-temporal here: no gain)
     }
     // the vertical operators only ever hold the rows above, self and below (:438-479): lets the compiler drop
     // the other five slot tests of their staging loops
     const unsigned vslots = (1u << S_A) | (1u << S_SELF) | (1u << S_B);
     // matrices that are not materialised (T alone; a given operator): nothing of them is staged or stored
-    const unsigned on0 = (p.skip & 1u) ? 0u : ~0u, on1 = (p.skip & 2u) ? 0u : ~0u, on2 = (p.skip & 4u) ? 0u : ~0u, on3 = (p.skip & 8u) ? 0u : ~0u,
-                   on4 = (p.skip & 16u) ? 0u : ~0u;
+    const unsigned on0 = (TM_SKIP & 1u) ? 0u : ~0u, on1 = (TM_SKIP & 2u) ? 0u : ~0u, on2 = (TM_SKIP & 4u) ? 0u : ~0u, on3 = (TM_SKIP & 8u) ? 0u : ~0u,
+                   on4 = (TM_SKIP & 16u) ? 0u : ~0u;
     const unsigned pm[5] = {pT & on0, col.padv & on1, col.phh & on2, col.pml & vslots & on3, col.pdp & vslots & on4};
     // wave-uniform quantities go to scalar registers: the run's base pointers are then SGPR pairs, the stores
     // take the `global_store vaddr32, vdata, sbase` form and the copy loop is a scalar loop
@@ -411,6 +427,7 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
     i64 *my_val = my_row + TM_STAGE;  // a constant distance: one address register, the LDS offset field does the rest
 #pragma unroll
     for (int m = 0; m < TM_NF; ++m) {
+        if (HTAB && ((TM_SKIP >> m) & 1u)) continue;  // (a constant: the kept operators' staging and store loops are not compiled)
         // The run is streamed out with 16-byte stores (two entries per lane): 8-byte-per-lane stores are store-issue
         // bound per CU (measured: the write phase cost as much as loads + arithmetic).  The run starts at an arbitrary
         // 8-byte position; global_store_dwordx4 does not need more alignment than that, so pairs are simply counted from
@@ -484,6 +501,8 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
     }
 #endif
 }
+#undef TM_SKIP
+#undef TM_KEEP
 
 // ---- otmb_tm_args.given: the COMPARING pass ------------------------------------------------------------------------------------
 // Is a given operator bit for bit what the fill pass would write?  One thread per column builds the column exactly as tm_kernel does
@@ -768,7 +787,8 @@ static int32_t build_tile_order(otmb_ctx *ctx, const otmb_tm_args &a, i64 ntiles
 
 
 // ---- host side ------------------------------------------------------------------------------
-// One launch site for the fill pass's instantiations: FUSED (the fused step's flux re-derivation) x GIVEN (a given TκH / TκVdeep read where it lies).
+// One launch site for the fill pass's instantiations: FUSED (the fused step's flux re-derivation) x GIVEN (a given TκH / TκVdeep read where it lies;
+// 4: the kept operators' TκH table).
 template <int GIVEN> static void launch_fill_given(otmb_ctx *ctx, const TmParams &p, int fused, dim3 grid, dim3 block) {
     if (fused == 1) hipLaunchKernelGGL((tm_kernel<1, GIVEN>), grid, block, 0, ctx->stream, p);
     else if (fused == 2) hipLaunchKernelGGL((tm_kernel<2, GIVEN>), grid, block, 0, ctx->stream, p);
@@ -779,7 +799,8 @@ static void launch_fill(otmb_ctx *ctx, const TmParams &p, int fused) {
     // (a derived TκH: reading is a choice -- regular cells only, OTMB_GIVEN_READ=0 re-derives; the derived rows with other values: it is the only way)
     const bool hread = p.hcp != nullptr && (p.hmust || (env_read && p.nx >= 3)), dread = p.dcp != nullptr;
     const dim3 grid(xcd_grid(p.nt_order, p.nheavy)), block(TM_THREADS);
-    if (hread && dread) launch_fill_given<3>(ctx, p, fused, grid, block);
+    if (p.htab) launch_fill_given<4>(ctx, p, fused, grid, block);  // (all three operators kept: kept_htab)
+    else if (hread && dread) launch_fill_given<3>(ctx, p, fused, grid, block);
     else if (dread) launch_fill_given<2>(ctx, p, fused, grid, block);
     else if (hread) launch_fill_given<1>(ctx, p, fused, grid, block);
     else launch_fill_given<0>(ctx, p, fused, grid, block);
@@ -973,12 +994,10 @@ static int32_t classify_given(otmb_ctx *ctx, const otmb_tm_args &a, TmPlan &pl) 
 }
 
 // ---- otmb_tm_args.kept_ops (host side) ------------------------------------------------------------------------------------------
-// The operators a caller may promise to have kept: functions of the grid and κ alone (src/matrixbuilding.jl:51-120)
-static const unsigned KEPT_OPS = (1u << OTMB_TKH) | (1u << OTMB_TKVML) | (1u << OTMB_TKVDEEP);
 static double kept_kappa(const otmb_tm_args &a, int m) { return m == OTMB_TKH ? a.kappa_h : m == OTMB_TKVML ? a.kappa_vml : a.kappa_vdeep; }
-// Does the record of operator m describe what this call would write?  out: the output arrays and capacity (two-phase plan: not known yet, NULL).
-static bool kept_matches(const otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl, int m, const void *const out[3], i64 cap) {
-    const otmb_ctx::KeptRecord &r = ctx->kept_rec[m];
+// Does record r (of operator m) describe what this call would write?  out: the output arrays and capacity (two-phase plan: not known yet, NULL).
+static bool record_matches(const otmb_ctx::KeptRecord &r, const otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl, int m, const void *const out[3],
+                           i64 cap) {
     if (!r.valid || r.epoch != ctx->given_epoch) return false;
     if (out && (r.colptr != out[0] || r.rowval != out[1] || r.nzval != out[2] || r.cap != cap)) return false;
     if (r.lwet3d != a.lwet3d || r.lwet != a.lwet || r.v3d != a.v3d || r.thk != a.thkcello || r.area != a.area2d || r.zt != a.zt ||
@@ -989,21 +1008,112 @@ static bool kept_matches(const otmb_ctx *ctx, const otmb_tm_args &a, const TmPla
     return r.nx == a.nx && r.ny == a.ny && r.nz == a.nz && r.n_wet == a.n_wet && r.wet_base == pl.wet_base && r.nnz_base == pl.nnz_base[m] &&
            r.topo == a.topology && r.kappa == kept_kappa(a, m);
 }
-// after a call has stored operator m into out[0..2] (nnz: its count, or < 0 while the asynchronous step `serial` is pending)
-static void kept_store(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl, int m, void *const out[3], i64 cap, i64 nnz, uint64_t serial) {
-    otmb_ctx::KeptRecord &r = ctx->kept_rec[m];
-    r.valid = true; r.epoch = ctx->given_epoch; r.serial = serial;
-    r.colptr = out[0]; r.rowval = out[1]; r.nzval = out[2]; r.cap = cap;
+static bool kept_matches(const otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl, int m, const void *const out[3], i64 cap) {
+    return record_matches(ctx->kept_rec[m], ctx, a, pl, m, out, cap);
+}
+// record r (of operator m): this call's arguments
+static void record_set(otmb_ctx::KeptRecord &r, const otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl, int m) {
+    r.valid = true; r.epoch = ctx->given_epoch;
     r.lwet3d = a.lwet3d; r.lwet = a.lwet; r.v3d = a.v3d; r.thk = a.thkcello; r.area = a.area2d; r.zt = a.zt; r.ml = a.mlotst;
     for (int d = 0; d < 4; ++d) { r.edge[d] = a.edge_length[d]; r.dist[d] = a.dist_nbr[d]; }
     r.nx = a.nx; r.ny = a.ny; r.nz = a.nz; r.n_wet = a.n_wet; r.wet_base = pl.wet_base; r.nnz_base = pl.nnz_base[m];
     r.topo = a.topology; r.kappa = kept_kappa(a, m);
+}
+// after a call has stored operator m into out[0..2] (nnz: its count, or < 0 while the asynchronous step `serial` is pending)
+static void kept_store(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl, int m, void *const out[3], i64 cap, i64 nnz, uint64_t serial) {
+    otmb_ctx::KeptRecord &r = ctx->kept_rec[m];
+    record_set(r, ctx, a, pl, m);
+    r.serial = serial;
+    r.colptr = out[0]; r.rowval = out[1]; r.nzval = out[2]; r.cap = cap;
     r.nnz_known = nnz >= 0; r.nnz = nnz >= 0 ? nnz : 0;
 }
-// every slot this call writes or leaves unwritten (all but the kept ones) loses its record before anything is enqueued
+// every slot this call writes or leaves unwritten (all but the kept ones) loses its record before anything is enqueued -- and a call that does not
+// keep TκH, the TκH table: the table is valid only while no call has written TκH since it was built
 static void kept_drop(otmb_ctx *ctx, unsigned keep) {
     for (int m = OTMB_TKH; m <= OTMB_TKVDEEP; ++m)
         if (!((keep >> m) & 1u)) ctx->kept_rec[m].valid = false;
+    if (!((keep >> OTMB_TKH) & 1u)) ctx->htab_valid = false;
+}
+
+// ---- the kept operators' TκH table ---------------------------------------------------------------------------------------------------------
+// A step that keeps all three diffusive operators still needs TκH's values in T.  Re-deriving them per column costs 5 thkcello and 16 metric
+// loads and 8 divisions -- a third of the fill pass's L1 requests.  The context keeps them instead: h_regular's five values of every regular
+// owned column, one array per slot (H_S, H_WC, H_SELF, H_EC, H_N), in memory the caller never sees (the kept output arrays may have been
+// overwritten behind the library's back: T must not depend on them).  One thread per column, wet-rank order (once per grid); the loads and their
+// clamps are fast_column's, so every stored value is bit for bit what the fill pass derives.  Irregular columns (tripolar seam row, nx < 3) are
+// not stored: the fill pass builds them with build_column.  *nan: some wet neighbour's pair is NaN (the fill pass raises FLAG_TKH_NAN from it).
+__global__ __launch_bounds__(256) void tm_htab_kernel(const TmParams p, double *__restrict__ tab, int *nan) {
+    const i64 w = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (w >= p.n_own) return;
+    const i64 L = p.lwet[w] - 1;
+    if (L < 0 || L >= p.G) return;  // (indices that are not a makeindices result: the fill pass flags them)
+    const Cell cell = cell_of(L, p.nx, p.ny, p.P);
+    const int nx = p.nx, i = cell.i, j = cell.j;
+    if (nx < 3 || (p.topo == OTMB_TRIPOLAR && j == p.ny - 1)) return;
+    const bool hS = j > 0, hN = j + 1 < p.ny;
+    const int di_e = (i + 1 < nx) ? 1 : 1 - nx, di_w = (i > 0) ? -1 : nx - 1;
+    const i64 LE = L + di_e, LW = L + di_w, LS = hS ? L - nx : L, LN = hN ? L + nx : L;
+    const i64 s2 = (i64)j * nx + i, sE = s2 + di_e, sW = s2 + di_w, sS = hS ? s2 - nx : s2, sN = hN ? s2 + nx : s2;
+    const double *eW = p.edge[OTMB_DIR_WEST], *eE = p.edge[OTMB_DIR_EAST], *eS = p.edge[OTMB_DIR_SOUTH], *eN = p.edge[OTMB_DIR_NORTH];
+    const double *dW = p.dist[OTMB_DIR_WEST], *dE = p.dist[OTMB_DIR_EAST], *dS = p.dist[OTMB_DIR_SOUTH], *dN = p.dist[OTMB_DIR_NORTH];
+    Stencil s;
+    s.vC = p.v[L]; s.vE = p.v[LE]; s.vW = p.v[LW]; s.vS = p.v[LS]; s.vN = p.v[LN];
+    s.tC = p.thk[L]; s.tE = p.thk[LE]; s.tW = p.thk[LW]; s.tS = p.thk[LS]; s.tN = p.thk[LN];
+    s.eW_c = eW[s2]; s.eE_c = eE[s2]; s.eS_c = eS[s2]; s.eN_c = eN[s2];
+    s.dW_c = dW[s2]; s.dE_c = dE[s2]; s.dS_c = dS[s2]; s.dN_c = dN[s2];
+    s.eE_w = eE[sW]; s.dE_w = dE[sW]; s.eW_e = eW[sE]; s.dW_e = dW[sE];
+    s.eN_s = eN[sS]; s.dN_s = dN[sS]; s.eS_n = eS[sN]; s.dS_n = dS[sN];
+    const bool wE = p.lw[LE] != 0, wW = p.lw[LW] != 0, wS = hS && p.lw[LS] != 0, wN = hN && p.lw[LN] != 0;
+    double h5[NHTAB];
+    const bool bad = h_regular(p.kH, s, wW, wE, wS, wN, h5);
+#pragma unroll
+    for (int q = 0; q < NHTAB; ++q) tab[(i64)q * p.n_own + w] = h5[q];
+    if (bad) raise_flag(nan, 0);
+}
+
+// Point p at a valid table when this call keeps all three operators (the HTAB fill kernel), building it first -- on the call's stream, in front
+// of its fill -- when none is valid.  Valid: built after the last call on this context that did not keep TκH (kept_drop), for this call's grid
+// arrays, κH, topology, n_wet and slab (kept_matches' fields), and in the current given_epoch.  OTMB_KEPT_HTAB=0, or a table that cannot be
+// allocated: p is left alone, the kept fill re-derives TκH as before (no error).
+static int32_t kept_htab(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl, TmParams &p) {
+    static const bool env_on = [] { const char *e = getenv("OTMB_KEPT_HTAB"); return !(e && e[0] == '0'); }();
+    if (pl.kept != KEPT_OPS || p.skip != KEPT_OPS || p.hcp || p.dcp) return OTMB_OK;
+    ctx->htab_used = 0;  // (otmb_ctx_kept_htab: set to 1 below once p points at a valid table)
+    if (!env_on || a.nx < 3 || a.n_wet <= 0) return OTMB_OK;
+    const size_t n = (size_t)a.n_wet, vals = (size_t)NHTAB * n * sizeof(double), bytes = vals + 256;  // (+ the NaN word)
+    if (ctx->htab_valid && !record_matches(ctx->htab_key, ctx, a, pl, OTMB_TKH, nullptr, 0)) ctx->htab_valid = false;
+    if (!ctx->htab_valid) {
+        if (ctx->htab.cap < bytes) {
+            if (ctx->htab_nofit && bytes >= ctx->htab_nofit) return OTMB_OK;  // (a size that did not fit is not tried again every step)
+            if (ctx->htab.p) {
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (earlier fills may still read it)
+                (void)hipFree(ctx->htab.p);
+                ctx->htab.p = nullptr;
+                ctx->htab.cap = 0;
+            }
+            if (hipMalloc(&ctx->htab.p, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                ctx->htab.p = nullptr;
+                ctx->htab_nofit = bytes;
+                return OTMB_OK;
+            }
+            ctx->htab.cap = bytes;
+        }
+        int *nanw = (int *)((char *)ctx->htab.p + vals);
+        HIP_TRY(ctx, hipMemsetAsync(nanw, 0, sizeof(int), ctx->stream));
+        {
+            KernelTimer kt(ctx, K_TM_HTAB);
+            hipLaunchKernelGGL(tm_htab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, p, (double *)ctx->htab.p, nanw);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        record_set(ctx->htab_key, ctx, a, pl, OTMB_TKH);
+        ctx->htab_valid = true;
+    }
+    p.htab = (const double *)ctx->htab.p;
+    p.htab_n = (i64)n;
+    p.htab_nan = (const int *)((const char *)ctx->htab.p + vals);
+    ctx->htab_used = 1;
+    return OTMB_OK;
 }
 
 // ignore: otmb_tm_args.ignore_ops -- errors that only an operator the caller already has would have raised
@@ -1321,6 +1431,7 @@ int32_t otmb_transportmatrix_fill_dev(otmb_ctx *ctx, int64_t *const colptr[5], i
     int *dflags = (int *)ctx->flags.p;
     if (pl.ntiles > 0) {
         if ((rc = build_tile_order(ctx, pl.args, pl.ntiles, p))) return rc;
+        if ((rc = kept_htab(ctx, pl.args, pl, p))) return rc;
         KernelTimer kt(ctx, K_TM_FILL);
         launch_fill(ctx, p, 0);
     }
@@ -1523,6 +1634,7 @@ static int32_t transportmatrix_dev_impl(otmb_ctx *ctx, const otmb_tm_args *a, in
             p.status = (u64 *)ctx->stamps.p;
 #endif
             if ((rc = build_tile_order(ctx, *a, ntiles, p))) return rc;
+            if ((rc = kept_htab(ctx, *a, pl, p))) return rc;
             KernelTimer kt(ctx, K_TM_FILL);
             launch_fill(ctx, p, fu.kind);
         }

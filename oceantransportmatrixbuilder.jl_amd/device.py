@@ -14,6 +14,9 @@ import torch
 from . import capi
 from .capi import HDIRS, MATS, PHI_ORDER
 
+# the library reads OTMB_KEPT_HTAB once per process (the first kept fill): what it will find, for accounting before that fill
+_KEPT_HTAB_ON = os.environ.get("OTMB_KEPT_HTAB", "1")[:1] != "0"
+
 
 def _flat(a, dtype=np.float64):
     return np.asfortranarray(a, dtype=dtype).ravel(order="F")
@@ -437,6 +440,16 @@ class DeviceAssembler:
         the next call will keep (what every launch after the first one of a time loop writes: bench.py's roofline reads this after its extras)."""
         return set(getattr(self, "_kept_last", ())) | (set(self.KEPT) if getattr(self, "_kept", None) is not None else set())
 
+    def _htab_bytes(self, skip):
+        """Bytes of the library's TκH table that a fill pass which keeps all three operators (`skip`) reads: five Float64 per wet column.  Such
+        a pass does not read thkcello and the eight edge / distance arrays (the tripolar seam row aside: one row of cells).  Whether the table
+        is read is the library's answer for the last such fill (otmb_ctx_kept_htab; before the first one: the library's own rule -- nx >= 3
+        and OTMB_KEPT_HTAB as this process started).  0: TκH is re-derived from thkcello and the metrics."""
+        if not set(self.KEPT) <= skip or getattr(self, "given", None):
+            return 0
+        used = self.ctx.kept_htab()
+        return 40 * self.N if (used == 1 or (used < 0 and self.nx >= 3 and _KEPT_HTAB_ON)) else 0
+
     def _check(self, rc):
         try:
             self.ctx.check(rc)
@@ -698,22 +711,34 @@ class DeviceAssembler:
     def algorithmic_bytes_split(self):
         """(bytes read, bytes written) of algorithmic_bytes().  An operator the caller passes and the fill pass re-derives (set_given) is
         neither read nor written: its 16 nnz + 8 (N + 1) bytes are not part of the pass.  Nor is one the last call kept where the previous
-        write left it, or that the next call keeps (otmb_tm_args.kept_ops: a time loop's steady state)."""
-        n3d = 9 + (1 if self.rho is not None else 0)
+        write left it, or that the next call keeps (otmb_tm_args.kept_ops: a time loop's steady state); when all three are kept the pass reads
+        the library's TκH table instead of thkcello and the edge / distance metrics (_htab_bytes)."""
         skip = set(getattr(self, "given", None) or ()) | self._kept_steady()
-        return (8 * self.G * n3d + 80 * self.nx * self.ny + 8 * self.nz,
+        htab = self._htab_bytes(skip)
+        n3d = 9 + (1 if self.rho is not None else 0) - (1 if htab else 0)  # (thkcello)
+        n2d = 10 - (8 if htab else 0)  # (the edge lengths and distances: area and mlotst stay)
+        return (8 * self.G * n3d + 8 * n2d * self.nx * self.ny + 8 * self.nz + htab,
                 sum(16 * z + 8 * (self.N + 1) for m, z in zip(MATS, self.nnz) if m not in skip))
 
     def fill_pass_stream_mix(self):
         """What an ideal streaming kernel reaches over the fill pass's OWN arrays (otmb_ctx_stream_mix): its ten 3-D inputs (+ the 2-D
         metrics) read once, its fifteen output arrays written once at their actual lengths, in as many slices as the pass has tiles.
         DESTROYS the matrices of self.out: call it after the results have been used.  {columns per slice: GB/s}.  Operators the last call kept
-        (otmb_tm_args.kept_ops) are not among the pass's outputs."""
+        (otmb_tm_args.kept_ops) are not among the pass's outputs; when all three are kept, the pass's inputs are those of _htab_bytes: the TκH
+        table (a stand-in with its layout, five arrays of N Float64: the library's own is not addressable from here) instead of thkcello and
+        the edge / distance metrics."""
         b8 = lambda t, n=None: (t.data_ptr(), 8 * (t.numel() if n is None else n))
         skip = self._kept_steady()
+        htab = self._htab_bytes(skip)
         self._forget_kept()
-        ins = [b8(p) for p in self.phi] + [b8(self.v3d), b8(self.thk), b8(self.lwet3d)] + ([b8(self.rho)] if self.rho is not None else [])
-        ins += [b8(t) for t in (*self.edge, *self.dist, self.area, self.mlotst)]
+        ins = [b8(p) for p in self.phi] + [b8(self.v3d), b8(self.lwet3d)] + ([b8(self.rho)] if self.rho is not None else [])
+        ins += [b8(t) for t in (self.area, self.mlotst)]
+        if htab:
+            slot = self.N + (self.N & 1)  # (16-byte aligned slots)
+            stand_in = torch.empty(5 * slot, dtype=torch.float64, device=self.device)
+            ins += [(stand_in[q * slot:].data_ptr(), 8 * self.N) for q in range(5)]
+        else:
+            ins += [b8(self.thk)] + [b8(t) for t in (*self.edge, *self.dist)]
         outs = []
         for k, m in enumerate(MATS):
             if m in skip:

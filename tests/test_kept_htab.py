@@ -1,0 +1,156 @@
+"""The kept operators' TκH table (csrc/otmb_transportmatrix.hip, kept_htab): a step that keeps TκH, TκVML and TκVdeep takes TκH's values for T
+from a table the context builds once per grid instead of re-deriving them.  Every output array must be bit for bit what the same steps write with
+the table switched off (OTMB_KEPT_HTAB=0, a child process: the switch is read once per process) and what a full build writes; every way the table
+can go stale must lead to a rebuild; a NaN it holds must fail every step as before (run with -m gpu)."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import kept_htab_worker as W
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+# ---- GPU ------------------------------------------------------------------------------------------------------------------------------------
+
+
+@pytest.fixture(scope="module")
+def fallback(tmp_path_factory):
+    """Every scenario of kept_htab_worker, run once in a child process with OTMB_KEPT_HTAB=0."""
+    out = str(tmp_path_factory.mktemp("htab") / "fallback.json")
+    env = dict(os.environ, OTMB_KEPT_HTAB="0")
+    r = subprocess.run([sys.executable, os.path.join(HERE, "kept_htab_worker.py"), out], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                       timeout=1200)
+    assert r.returncode == 0, r.stdout.decode(errors="replace")[-3000:]
+    with open(out) as f:
+        return json.load(f)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,upwind,protocol", W.cases())
+def test_table_fallback_and_full_builds_are_bit_identical(fallback, name, upwind, protocol):
+    rec = W.run_case(name, upwind, protocol)
+    off = fallback["cases"][f"{name}|{upwind}|{protocol}"]
+    for k in range(len(rec["kept"])):
+        assert rec["kept"][k] == rec["full"][k], f"step {k}: table vs full build"
+        assert rec["kept"][k] == off["kept"][k], f"step {k}: table vs OTMB_KEPT_HTAB=0"
+    assert rec["kept_steps"] == off["kept_steps"]
+    assert sum(rec["kept_steps"]) >= (1 if protocol == "twophase" else 4)
+    # the table was used here, and never in the fallback process
+    assert rec["launches"].get("tm_htab_kernel", 0) >= 1
+    assert "tm_htab_kernel" not in off["launches"]
+    assert rec["launches"]["tm_kernel<fill>"] == off["launches"]["tm_kernel<fill>"]
+    assert rec["kept_htab"] == 1 and off["kept_htab"] == 0
+
+
+@pytest.mark.gpu
+def test_a_nan_in_the_table_fails_every_step_as_before(fallback):
+    got = W.run_nan_pipeline()
+    assert got["error"] is not None and got["error"][1] == 0, got["error"]  # (the first step: the one that wrote TκH)
+    assert list(got["error"]) == fallback["nan"]["error"]
+    assert got["steps"] == fallback["nan"]["steps"]
+    assert all(s[0] != 0 for s in got["steps"]), got["steps"]
+
+
+@pytest.mark.gpu
+def test_the_table_is_built_once_per_grid():
+    from test_kept_ops import _fields, _pair
+
+    g, gm, asm, full, umo, vmo, fill = _pair("small_rho3d")
+    asm.ctx.timing_enable(True)
+    for u, v in _fields(umo, vmo, 6, seed=5):
+        asm.step_async(u, v, fill)
+    asm.finish()
+    n = W.launches(asm)
+    assert n["tm_kernel<fill>"] == 6 and n["tm_htab_kernel"] == 1, n
+    asm.ctx.timing_enable(False)
+    # the roofline's bytes: the table's five Float64 per column are read instead of thkcello and the eight edge / distance arrays
+    assert asm.ctx.kept_htab() == 1
+    n3d = 9 + (asm.rho is not None)
+    full_read = 8 * asm.G * n3d + 80 * asm.nx * asm.ny + 8 * asm.nz
+    assert asm.algorithmic_bytes_split()[0] == full_read - 8 * asm.G - 64 * asm.nx * asm.ny + 40 * asm.N
+
+
+def _edit(asm, how, g, gm):
+    """One invalidation of the table on assembler `asm` (the full build gets the same grid edits)."""
+    L = W.wet_regular_cell(asm)
+    if how == "kappa":
+        asm.set_grid(gm, g.mlotst, g.rho, 2.0 * g.kappaH, g.kappaVML, g.kappaVdeep)
+    elif how == "set_grid":
+        asm.set_grid(gm, g.mlotst, g.rho, g.kappaH, g.kappaVML, g.kappaVdeep)
+    elif how == "thk":
+        asm.thk[L] *= 1.5
+    elif how == "edge":
+        s2 = L % (asm.nx * asm.ny)
+        asm.edge[1][s2] *= 0.75
+    elif how == "v3d":
+        asm.v3d[L] *= 1.25
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("how", ["kappa", "thk", "edge", "v3d", "set_grid", "forget_given", "second_output_set"])
+def test_every_invalidation_rebuilds_the_table(how):
+    """After the edit, the next kept step (the table built anew) equals a full build on the edited grid."""
+    from test_kept_ops import KEPT, _fields, _host, _pair, _run, _same
+
+    g, gm, asm, full, umo, vmo, fill = _pair("tiny_rho3d")
+    fields = _fields(umo, vmo, 3, seed=17)
+    for a in (asm, full):
+        _run(a, "async", *fields[0], fill)
+    _run(asm, "async", *fields[0], fill)
+    assert asm._kept_last == KEPT  # (the table exists for the old grid)
+    asm.ctx.timing_enable(True)
+    if how in ("kappa", "thk", "edge", "v3d", "set_grid"):
+        for a in (asm, full):
+            _edit(a, how, g, gm)
+    elif how == "forget_given":
+        asm.ctx.forget_given()
+    elif how == "second_output_set":
+        other = asm.new_output_set()
+        asm.transportmatrix_onepass(asm.facefluxes(*fields[1], fill), out=other)
+    for k in (1, 2):  # a full write or a kept one, then a kept one that must read a table of the edited grid
+        _run(asm, "async", *fields[k], fill)
+        _run(full, "async", *fields[k], fill)
+        _same(_host(asm), _host(full), f"{how}, step {k}")
+    assert asm._kept_last == KEPT
+    assert W.launches(asm).get("tm_htab_kernel", 0) == 1
+    asm.ctx.timing_enable(False)
+
+
+@pytest.mark.gpu
+def test_one_degree_kept_step_equals_a_full_build():
+    """The headline grid (bench.py access1deg): the second step keeps and reads the table; all five outputs as a full build's."""
+    import torch
+
+    import otmb_amd
+    from otmb_amd import synthetic
+    from otmb_amd.device import DeviceAssembler
+    from test_kept_ops import KEPT
+
+    nx, ny, nz, lf = synthetic.PRESETS["access1deg"]
+    g = synthetic.make_grid(nx, ny, nz, seed=20260501, land_fraction=lf, rho="array")
+    gm = otmb_amd.makegridmetrics(areacello=g.areacello, volcello=g.volcello, lon=g.lon, lat=g.lat, lev=g.lev,
+                                  lon_vertices=g.lon_vertices, lat_vertices=g.lat_vertices)
+    umo = torch.from_numpy(np.asfortranarray(g.umo.data).ravel(order="F")).cuda()
+    vmo = torch.from_numpy(np.asfortranarray(g.vmo.data).ravel(order="F")).cuda()
+    fill = g.umo.properties["_FillValue"]
+    digests = []
+    for promise in (True, False):
+        a = DeviceAssembler(0)
+        a.set_grid(gm, g.mlotst, g.rho, g.kappaH, g.kappaVML, g.kappaVdeep, upwind=True)
+        if not promise:
+            a._kept_ops = lambda out: (0, ())
+        a.ctx.timing_enable(True)
+        for _ in range(2):
+            a.step_async(umo, vmo, fill)
+            a.finish()
+        assert (a._kept_last == KEPT) == promise
+        assert ("tm_htab_kernel" in W.launches(a)) == (promise and os.environ.get("OTMB_KEPT_HTAB", "1") != "0")
+        digests.append(W.digest(a))
+        del a
+        torch.cuda.empty_cache()
+    assert digests[0] == digests[1]
