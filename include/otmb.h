@@ -596,6 +596,26 @@ int32_t otmb_lump_and_spray(otmb_ctx *ctx, const uint8_t *wet3d, const uint8_t *
                             int64_t dj, int64_t dk, int64_t *lump_rowval, double *lump_nzval, int64_t *spray_colptr,
                             int64_t *spray_rowval, double *vol_c, int64_t *n_coarse);
 
+/* ---- C = LUMP * T * SPRAY, the coarse operator of lump_and_spray's docstring (src/extratools.jl:14-16, test/local_full.jl:161):
+ *      SparseArrays' (LUMP * T) * SPRAY bit for bit (the 3-argument `*` multiplies left to right for these shapes; each `*` is
+ *      spmatmul: per column, the first touch of a row copies, later touches add in stored order, every touched row is stored,
+ *      exact zeros included).  A (LUMP): m x N with at most one stored entry per column; B (T or any operator): N x M; S (SPRAY):
+ *      M x n; all SparseMatrixCSC{Float64,Int64} arrays, 1-based, rows ascending inside a column.  A LUMP column with two or more
+ *      entries, a colptr that is not ascending inside [1, nnz + 1] or a row index out of range: OTMB_ERR_INVALID_ARG (checked
+ *      before anything is read through it).
+ * _dev: device pointers, two-phase (plan -> nnz of C, fill -> Cp (n+1), Ci, Cx (nnz)); one plan/fill pair per context at a time,
+ *   the inputs must stay alive and unchanged until the fill.
+ * otmb_coarsen_plan (host pointers, what the Julia shim calls): uploads the three matrices (every call) and plans;
+ *   otmb_coarsen_fetch fills and downloads.                                                                                  */
+int32_t otmb_coarsen_plan_dev(otmb_ctx *ctx, int64_t m, int64_t N, const int64_t *Ap, const int64_t *Ai, const double *Ax, int64_t M,
+                              const int64_t *Bp, const int64_t *Bi, const double *Bx, int64_t n, const int64_t *Sp, const int64_t *Si,
+                              const double *Sx, int64_t *nnz);
+int32_t otmb_coarsen_fill_dev(otmb_ctx *ctx, int64_t *Cp, int64_t *Ci, double *Cx);
+int32_t otmb_coarsen_plan(otmb_ctx *ctx, int64_t m, int64_t N, const int64_t *Ap, const int64_t *Ai, const double *Ax, int64_t M,
+                          const int64_t *Bp, const int64_t *Bi, const double *Bx, int64_t n, const int64_t *Sp, const int64_t *Si,
+                          const double *Sx, int64_t *nnz);
+int32_t otmb_coarsen_fetch(otmb_ctx *ctx, int64_t *Cp, int64_t *Ci, double *Cx);
+
 #ifdef __cplusplus
 }
 #endif

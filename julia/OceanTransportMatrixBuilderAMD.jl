@@ -9,6 +9,7 @@
 #                               src/velocities.jl:10-74,140-151, src/gridcellgeometry.jl:103-140 (round 5: bound here too, so that a script
 #                               that starts from uo / vo runs THIS module's facefluxes and not the reference's CPU one)
 #   lump_and_spray              src/extratools.jl:38-119
+#   coarsen                     LUMP * T * SPRAY (src/extratools.jl:14-16)
 #   bolus_GM_velocity           src/RediGM.jl:46-79 (unexported and experimental there, unexported here)
 #   makegridmetrics             src/gridcellgeometry.jl:265-311: the reference's own by default (its haversines are Julia's libm);
 #                               `makegridmetrics(...; gpu = true)` opts into the library's array work (distances within 1e-12)
@@ -27,7 +28,7 @@ import OceanTransportMatrixBuilder as OTMB
 
 # the reference's exported names (src/OceanTransportMatrixBuilder.jl:31-36), every one of them defined in THIS module
 export makegridmetrics, velocity2fluxes, fluxes2velocity, facefluxesfromvelocities
-export makeindices, facefluxesfrommasstransport, facefluxes, transportmatrix, lump_and_spray
+export makeindices, facefluxesfrommasstransport, facefluxes, transportmatrix, lump_and_spray, coarsen
 
 const LIBPATH = get(ENV, "OTMB_HIP_LIB", joinpath(@__DIR__, "..", "oceantransportmatrixbuilder.jl_amd", "lib", "libotmb_hip.so"))
 const lib = Ref{Ptr{Cvoid}}(C_NULL)
@@ -240,6 +241,24 @@ function spadd(A::SparseMatrixCSC{Float64,Int64}, B::SparseMatrixCSC{Float64,Int
     end
     resize!(Ci, k[]); resize!(Cx, k[])
     return SparseMatrixCSC{Float64,Int64}(size(A, 1), n, Cp, Ci, Cx)
+end
+
+# The coarse operator `LUMP * T * SPRAY` of lump_and_spray's docstring (src/extratools.jl:14-16, test/local_full.jl:161) on the
+# device: bit for bit SparseArrays' (LUMP * T) * SPRAY (otmb_coarsen_plan / otmb_coarsen_fetch).  `Base.*` stays SparseArrays'.
+function coarsen(LUMP::SparseMatrixCSC{Float64,Int64}, T::SparseMatrixCSC{Float64,Int64}, SPRAY::SparseMatrixCSC{Float64,Int64})
+    m, N = size(LUMP)
+    M, n = size(T, 2), size(SPRAY, 2)
+    (size(T, 1) == N && size(SPRAY, 1) == M) ||
+        throw(DimensionMismatch("LUMP $(size(LUMP)), T $(size(T)), SPRAY $(size(SPRAY))"))
+    k = Ref{Int64}(0)
+    lock(CALL_LOCK) do
+        check(ccall(sym(:otmb_coarsen_plan), Int32,
+            (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}),
+            context(), m, N, LUMP.colptr, LUMP.rowval, LUMP.nzval, M, T.colptr, T.rowval, T.nzval, n, SPRAY.colptr, SPRAY.rowval, SPRAY.nzval, k))
+        Cp = Vector{Int64}(undef, n + 1); Ci = Vector{Int64}(undef, k[]); Cx = Vector{Float64}(undef, k[])
+        check(ccall(sym(:otmb_coarsen_fetch), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}), ctx[], Cp, Ci, Cx))
+        return SparseMatrixCSC{Float64,Int64}(m, n, Cp, Ci, Cx)
+    end
 end
 
 const HDIRS = (:west, :east, :south, :north)      # OTMB_DIR_*

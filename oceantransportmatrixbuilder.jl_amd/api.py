@@ -763,6 +763,35 @@ def lump_and_spray(wet3D, vol, T, mask=None, *, di=2, dj=2, dk=1, device=0):
     return LUMP, SPRAY, vc[:Nc].copy()
 
 
+def coarsen(LUMP, T, SPRAY, *, device=0):
+    """The coarse operator `LUMP * T * SPRAY` of lump_and_spray's docstring (src/extratools.jl:14-16; the reference's workflow
+    forms it at test/local_full.jl:161), on the device.  Bit for bit SparseArrays' (LUMP * T) * SPRAY: per column the first touch
+    of a row copies, later touches add in stored order, every touched row is stored (exact zeros included).  LUMP: at most one
+    stored entry per column; T: any N x M operator (T, Tadv, TκH, ...); SPRAY: M x n.  Returns a SparseMatrixCSC (1-based)."""
+    ctx = context(device)
+    m, N = LUMP.shape
+    if T.m != N or SPRAY.m != T.n:
+        raise capi.OtmbError(11, f"DimensionMismatch: LUMP {LUMP.shape}, T {T.shape}, SPRAY {SPRAY.shape}")
+    M, n = T.n, SPRAY.n
+    arrs = [np.ascontiguousarray(x, dtype=t) for X in (LUMP, T, SPRAY)
+            for x, t in ((X.colptr, np.int64), (X.rowval, np.int64), (X.nzval, np.float64))]
+    for X, (p, i, v) in zip((LUMP, T, SPRAY), (arrs[0:3], arrs[3:6], arrs[6:9])):
+        if len(p) != X.n + 1 or len(p) == 0 or len(i) < p[-1] - 1 or len(v) < p[-1] - 1:
+            raise capi.OtmbError(11, f"invalid argument: SparseMatrixCSC arrays of a {X.shape} matrix have lengths "
+                                     f"{len(p)}, {len(i)}, {len(v)}")
+    nnz = C.c_int64(0)
+    lib = capi.lib()
+    ptr = [x.ctypes.data for x in arrs]
+    ctx.check(lib.otmb_coarsen_plan(ctx.handle, m, N, ptr[0], ptr[1], ptr[2], M, ptr[3], ptr[4], ptr[5], n, ptr[6], ptr[7], ptr[8],
+                                    C.byref(nnz)))
+    k = int(nnz.value)
+    Cp = np.empty(n + 1, dtype=np.int64)
+    Ci = np.empty(max(k, 1), dtype=np.int64)
+    Cx = np.empty(max(k, 1), dtype=np.float64)
+    ctx.check(lib.otmb_coarsen_fetch(ctx.handle, Cp.ctypes.data, Ci.ctypes.data, Cx.ctypes.data))
+    return SparseMatrixCSC(m, n, Cp, Ci[:k], Cx[:k])
+
+
 def as2D(x, wet3D):
     """src/extratools.jl:111-115: scatter a surface vector back onto the (nx,ny) grid, NaN on land."""
     wet = np.asfortranarray(wet3D).astype(bool)

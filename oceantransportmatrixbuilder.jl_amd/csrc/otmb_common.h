@@ -149,6 +149,16 @@ struct otmb_ctx {
     DevBuf given_tmp[6];                   // temporaries of the foreign path's sparse adds: two (colptr, rowval, nzval) triples
     CooPlan coo;
     SpPlan sp;
+    // LUMP * T * SPRAY (otmb_coarsen.hip): the pending plan (nnz < 0: none), its scratch, the staging of the host-pointer calls
+    struct CoPlan {
+        const int64_t *Ap = nullptr, *Ai = nullptr, *Bp = nullptr, *Bi = nullptr, *Sp = nullptr, *Si = nullptr;
+        const double *Ax = nullptr, *Bx = nullptr, *Sx = nullptr;
+        int64_t m = 0, N = 0, M = 0, n = 0, nS = 0, len = 0, nnz = -1;
+        int cap = 0;  // LDS capacity of the small path; 0: the sorted path
+        int rowbits = 0;
+        uint64_t invalid = 0;
+    } co_plan;
+    DevBuf co[10], co_host, co_out;
     // staging for the host-pointer entry points
     std::vector<DevBuf> stage;
     OtmbXfer *xfer = nullptr;

@@ -119,6 +119,10 @@ void otmb_ctx_destroy(otmb_ctx *ctx) {
         if (b.p) (void)hipFree(b.p);
     for (DevBuf &b : ctx->lump)
         if (b.p) (void)hipFree(b.p);
+    for (DevBuf &b : ctx->co)
+        if (b.p) (void)hipFree(b.p);
+    for (DevBuf *b : {&ctx->co_host, &ctx->co_out})
+        if (b->p) (void)hipFree(b->p);
     if (ctx->mask.p) (void)hipFree(ctx->mask.p);
     if (ctx->order.p) (void)hipFree(ctx->order.p);
     if (ctx->lump_host.p) (void)hipFree(ctx->lump_host.p);

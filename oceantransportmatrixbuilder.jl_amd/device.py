@@ -644,6 +644,30 @@ class DeviceAssembler:
                                                              vc.data_ptr()))
         return (L[0], L[1][:N], L[2][:N]), (S[0], S[1][:N], S[2][:N]), vc[:Nc]
 
+    def coarsen(self, L, S, matrix="T", m=None):
+        """C = L * matrix * S (the coarse operator; src/extratools.jl:14-16) on the device, bit for bit SparseArrays' (L * T) * S.
+        L, S: (colptr, rowval, nzval) device tensors as lump_and_spray returns them (L: Nc x N with at most one entry per column,
+        S: N x n); `matrix` is the resident result.  m: the rows of L (default n, as for lump_and_spray's pair).  Only nnz travels
+        to the host.  Returns (colptr, rowval, nzval) tensors."""
+        cp, rv, nz = self.out[matrix]
+        Lp, Li, Lx = (t.contiguous() for t in L)
+        Sp, Si, Sx = (t.contiguous() for t in S)
+        N = self.N
+        if Lp.numel() != N + 1 or Sp.numel() < 1:
+            raise ValueError("L must have N + 1 column pointers")
+        n = Sp.numel() - 1
+        m = n if m is None else int(m)
+        nnz = C.c_int64(0)
+        self.ctx.check(self.lib.otmb_coarsen_plan_dev(self.ctx.handle, m, N, Lp.data_ptr(), Li.data_ptr(), Lx.data_ptr(), N, cp.data_ptr(),
+                                                      rv.data_ptr(), nz.data_ptr(), n, Sp.data_ptr(), Si.data_ptr(), Sx.data_ptr(),
+                                                      C.byref(nnz)))
+        k = int(nnz.value)
+        Cp = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        Ci = torch.empty(max(k, 1), dtype=torch.int64, device=self.device)
+        Cx = torch.empty(max(k, 1), dtype=torch.float64, device=self.device)
+        self.ctx.check(self.lib.otmb_coarsen_fill_dev(self.ctx.handle, Cp.data_ptr(), Ci.data_ptr(), Cx.data_ptr()))
+        return Cp, Ci[:k], Cx[:k]
+
     def result_to_host(self):
         self.ctx.synchronize()
         if any(self.out[m][1].numel() < self.nnz[k] for k, m in enumerate(MATS)):
