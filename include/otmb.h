@@ -376,8 +376,17 @@ typedef struct {
                                   * keeps (built by the first such call after any call without the TκH bit; OTMB_KEPT_HTAB=0: re-derived),
                                   * so T itself then depends on it.  A write the library is not told about to a grid array TκH is
                                   * derived from (v3d, thkcello, edge_length, dist_nbr, lwet3d, lwet) must therefore also be followed by
-                                  * a call without the bit.                                                                              */
+                                  * a call without the bit.
+                                  * Bit 5, OTMB_KEPT_T_PATTERN: the colptr / rowval arrays passed for T are the ones this context last
+                                  * wrote T's pattern into, untouched since.  T's reserved pattern is a function of the wet mask and the
+                                  * topology alone, so a fill that keeps all three operators and reads the TκH table then stores T's
+                                  * VALUES only, at the positions that write left (otmb_ctx_kept_t_pattern).  The library honours it only
+                                  * when its own record matches: the last writer of T's pattern into exactly these arrays, for these
+                                  * arguments, finished without error or exact cancellation (a pending asynchronous step does not count).
+                                  * Anything else writes T in full.  Two-phase protocol: fill must be handed the recorded arrays when the
+                                  * plan honoured the bit (otherwise OTMB_ERR_INVALID_ARG).                                              */
 } otmb_tm_args;
+#define OTMB_KEPT_T_PATTERN (1 << 5)
 /* The verdicts on otmb_tm_args.given are keyed to array ADDRESSES (the given matrix's and the gridmetrics / indices arrays') and κ.
  * A device-resident caller that rewrites one of those arrays in place calls this before the next transportmatrix; the host-pointer
  * entry points do it themselves whenever they upload such an array (i.e. always, unless otmb_ctx_set_reuse_grid promises otherwise). */
@@ -390,6 +399,9 @@ int64_t otmb_ctx_given_checks(const otmb_ctx *ctx);
 /* ... and whether the last fill pass on this context that kept all three diffusive operators (otmb_tm_args.kept_ops) read TκH from the
  * context's table: 1 yes, 0 no (OTMB_KEPT_HTAB=0, nx < 3, the table could not be allocated), -1 no such fill yet. */
 int32_t otmb_ctx_kept_htab(const otmb_ctx *ctx);
+/* ... and whether that fill stored T's values only (otmb_tm_args.kept_ops & OTMB_KEPT_T_PATTERN honoured): 1 yes, 0 no (T written in full),
+ * -1 no such fill yet.  OTMB_KEPT_TPAT=0 in the environment always writes T in full. */
+int32_t otmb_ctx_kept_t_pattern(const otmb_ctx *ctx);
 
 /* Two-phase protocol so the CALLER allocates the outputs (Julia owns its SparseMatrixCSC buffers).
  * plan: the nnz of the four operator matrices (exact: their patterns depend on the wet mask, the flux

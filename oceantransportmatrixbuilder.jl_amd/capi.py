@@ -16,6 +16,7 @@ CAPACITY = 14
 PHI_ORDER = ("east", "west", "north", "south", "top", "bottom")  # OTMB_EAST..OTMB_BOTTOM
 HDIRS = ("west", "east", "south", "north")  # OTMB_DIR_*
 MATS = ("T", "Tadv", "TκH", "TκVML", "TκVdeep")  # OTMB_T..OTMB_TKVDEEP
+KEPT_T_PATTERN = 1 << 5  # OTMB_KEPT_T_PATTERN (otmb_tm_args.kept_ops): T's colptr / rowval are where this context last wrote T's pattern
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
@@ -52,7 +53,7 @@ class TmArgs(C.Structure):
         ("ignore_ops", C.c_int32),
         ("skip_ops", C.c_int32),  # bit m: matrix m is not wanted (neither counted, written nor copied home)
         ("given", Csc * 5),  # operators the caller passes (transportmatrix's Tadv = / TκH = / TκVML = / TκVdeep = keywords)
-        ("kept_ops", C.c_int32),  # bit m (TκH, TκVML, TκVdeep): the output arrays hold what this context last wrote there (_dev only)
+        ("kept_ops", C.c_int32),  # bit m (TκH, TκVML, TκVdeep): the output arrays hold what this context last wrote there (_dev only); KEPT_T_PATTERN
     ]
 
 
@@ -100,6 +101,7 @@ SYMBOLS = {
     "otmb_ctx_given_state": (C.c_int32, [_vp, C.c_int32]),
     "otmb_ctx_given_checks": (C.c_int64, [_vp]),
     "otmb_ctx_kept_htab": (C.c_int32, [_vp]),
+    "otmb_ctx_kept_t_pattern": (C.c_int32, [_vp]),
     "otmb_last_error": (C.c_char_p, [_vp]),
     "otmb_status_string": (C.c_char_p, [C.c_int32]),
     "otmb_version": (C.c_char_p, []),
@@ -313,6 +315,10 @@ class Context:
     def kept_htab(self):
         """Whether the last fill that kept TκH, TκVML and TκVdeep read TκH from the context's table: 1 yes, 0 no, -1 no such fill yet."""
         return int(self._lib.otmb_ctx_kept_htab(self._h))
+
+    def kept_t_pattern(self):
+        """Whether that fill stored T's values only, on the pattern of this context's last write of T (KEPT_T_PATTERN honoured): 1 yes, 0 no, -1 no such fill yet."""
+        return int(self._lib.otmb_ctx_kept_t_pattern(self._h))
 
     def use_own_stream(self):
         self.check(self._lib.otmb_ctx_set_stream(self._h, _vp(0)))

@@ -94,8 +94,9 @@ struct otmb_ctx {
     i64 tm_sticky_step = -1;
     std::string tm_sticky_msg;
     i64 tm_failed_step = -1;         // what the last otmb_transportmatrix_result found
-    struct TmStepRec { void *colptrT, *rowvalT, *nzvalT; i64 n_wet, nnz_base0; int ignore_ops; unsigned wrote, kept; uint64_t serial; };
-                                     // (wrote / kept: the operators m = 2..4 the step stored / took from an earlier step, otmb_tm_args.kept_ops)
+    struct TmStepRec { void *colptrT, *rowvalT, *nzvalT; i64 n_wet, nnz_base0; int ignore_ops; unsigned wrote, kept; uint64_t serial; bool tpat; };
+                                     // (wrote / kept: the operators m = 2..4 the step stored / took from an earlier step, otmb_tm_args.kept_ops;
+                                     // tpat: the step stored T's values only, on the pattern tpat_rec names)
     uint64_t tm_serial = 0;          // asynchronous steps issued on this context so far
     std::vector<TmStepRec> tm_rec;   // T's output arrays of the pending steps [tm_first, tm_next) (compaction after exact cancellation)
     struct TmStepResult { int32_t status; i64 nnz[5]; };
@@ -146,6 +147,12 @@ struct otmb_ctx {
     KeptRecord htab_key;
     size_t htab_nofit = 0;  // an allocation of this many bytes failed: the kept fill re-derives TκH instead
     int htab_used = -1;     // the last fill that kept all three operators read the table (1) or re-derived TκH (0); -1: none yet (otmb_ctx_kept_htab)
+    // ... and T's pattern (OTMB_KEPT_T_PATTERN): the last call that wrote T's full union pattern (colptr, rowval; nzval unused), its serial and
+    // arguments.  nnz_known: that writer finished cleanly -- folded without error or FLAG_T_CANCEL, or a synchronous fill without cancellation --
+    // and nnz is T's reserved count.  Dropped by a call that writes T elsewhere or not at all, a failed step that used it, a compaction of its
+    // arrays, and with the TκH table (a change of stream).
+    KeptRecord tpat_rec;
+    int tpat_used = -1;     // the last fill that kept all three operators stored T's values only (1) or all of T (0); -1: none yet
     DevBuf given_tmp[6];                   // temporaries of the foreign path's sparse adds: two (colptr, rowval, nzval) triples
     CooPlan coo;
     SpPlan sp;

@@ -139,6 +139,7 @@ void otmb_ctx_destroy(otmb_ctx *ctx) {
 static void drop_htab(otmb_ctx *ctx) {
     if (ctx->htab_valid) (void)hipStreamSynchronize(ctx->stream);
     ctx->htab_valid = false;
+    ctx->tpat_rec.valid = false;  // (T's values-only fills ride on the table's path)
 }
 
 int32_t otmb_ctx_set_stream(otmb_ctx *ctx, void *s) {
@@ -177,6 +178,7 @@ int32_t otmb_ctx_forget_given(otmb_ctx *ctx) {
 int32_t otmb_ctx_given_state(const otmb_ctx *ctx, int32_t m) { return (ctx && m >= 0 && m < 5) ? ctx->given_state[m] : -1; }
 int64_t otmb_ctx_given_checks(const otmb_ctx *ctx) { return ctx ? (int64_t)ctx->given_checks : -1; }
 int32_t otmb_ctx_kept_htab(const otmb_ctx *ctx) { return ctx ? ctx->htab_used : -1; }
+int32_t otmb_ctx_kept_t_pattern(const otmb_ctx *ctx) { return ctx ? ctx->tpat_used : -1; }
 
 int32_t otmb_ctx_synchronize(otmb_ctx *ctx) {
     if (!ctx) return OTMB_ERR_INVALID_ARG;

@@ -53,6 +53,7 @@ struct TmPlan {
     bool want_t = true;        // the caller wants T (otmb_tm_args.skip_ops bit 0 clear)
     i64 built_nnz[5] = {0, 0, 0, 0, 0};  // (foreign) the counts of the matrices the kernel writes; nnz[0] is then the sparse adds' bound
     unsigned kept = 0;         // (subset of skip) otmb_tm_args.kept_ops honoured: the operator is where the previous write left it
+    bool tpat = false;         // (two-phase) the plan honoured OTMB_KEPT_T_PATTERN: fill must be handed the recorded T arrays
 };
 
 // The operators a caller may promise to have kept (otmb_tm_args.kept_ops): functions of the grid and κ alone (src/matrixbuilding.jl:51-120)
@@ -174,10 +175,14 @@ static_assert(TM_THREADS == (1 << FFC_TILE_SHIFT), "the counts in facefluxes are
 // GIVEN bit 2 -- HTAB (alone): all three diffusive operators are kept (otmb_tm_args.kept_ops), so T and Tadv are the only matrices written
 // (TmParams.skip == KEPT_OPS as a constant: the other three staging loops are gone), and a regular column takes its TκH values from the
 // context's table (TmParams.htab: five streamed loads) instead of 5 thkcello + 16 metric loads and 8 divisions.
+// GIVEN bit 3 -- TPAT (with HTAB only): T's pattern is where the context's last full write of T left it (OTMB_KEPT_T_PATTERN, tpat_rec), so T
+// stores its VALUES only, at the union positions that write gave them: no T colptr (closing entry included), no T row staging or row stores.
+// A cancelled slot holds its zero sum (±0.0), its row is left as it is, and FLAG_T_CANCEL is raised as before (the compaction keys on values).
 template <int FUSED = 0, int GIVEN = 0>
 __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const TmParams p) {
-    constexpr bool HREAD = (GIVEN & 1) != 0, DREAD = (GIVEN & 2) != 0, HTAB = (GIVEN & 4) != 0;
-    static_assert(!HTAB || GIVEN == 4, "the table serves the kept operators: nothing is given then");
+    constexpr bool HREAD = (GIVEN & 1) != 0, DREAD = (GIVEN & 2) != 0, HTAB = (GIVEN & 4) != 0, TPAT = (GIVEN & 8) != 0;
+    static_assert(!HTAB || (GIVEN & ~8) == 4, "the table serves the kept operators: nothing is given then");
+    static_assert(!TPAT || HTAB, "T's kept pattern rides on the kept operators' path");
 // (evaluated where used, as p.skip / p.keep were: a local copy at the top changes the other instantiations' register allocation)
 #define TM_SKIP (HTAB ? KEPT_OPS : p.skip)
 #define TM_KEEP (HTAB ? 0x3fffffull : p.keep)  // (HTAB: the count fields of T and Tadv, keep_mask(KEPT_OPS))
@@ -282,7 +287,7 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
     // actually stored are those whose sum is non-zero (:147).  Exact cancellation is rare: the column is
     // written left-aligned in its reserved slots, the shortfall is flagged and the host compacts T.
     Column col;
-    unsigned pT = 0, nU = 0, nA = 0, nH = 0, nM = 0, nD = 0;
+    unsigned pT = 0, pU = 0, nU = 0, nA = 0, nH = 0, nM = 0, nD = 0;
     bool live = false;
     if (valid && span_ok) {
         const i64 L = L_own, Lnext = Lnext_own;
@@ -317,6 +322,7 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
                 live = true;
                 if (DREAD) given_values<(1u << S_A) | (1u << S_SELF) | (1u << S_B)>(col.dp, col.pdp, col.bef, p.dx, dq, p.dnnz);
                 const unsigned uni = col.padv | col.phh | col.pml | col.pdp;
+                if (TPAT) pU = uni;
                 nU = __popc(uni);
                 nA = __popc(col.padv); nH = __popc(col.phh); nM = __popc(col.pml); nD = __popc(col.pdp);
                 {
@@ -386,7 +392,7 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
             if (p.gsum) p.totals[tid] = tot;
             i64 *cp = (tid == 0) ? p.colptr[0] : (tid == 1) ? p.colptr[1] : (tid == 2) ? p.colptr[2] : (tid == 3) ? p.colptr[3] : p.colptr[4];
             const i64 nb = (tid == 0) ? p.nnz_base[0] : (tid == 1) ? p.nnz_base[1] : (tid == 2) ? p.nnz_base[2] : (tid == 3) ? p.nnz_base[3] : p.nnz_base[4];
-            if (!((TM_SKIP >> tid) & 1u)) cp[p.n_own] = nb + tot + 1;
+            if (!((TM_SKIP >> tid) & 1u) && !(TPAT && tid == 0)) cp[p.n_own] = nb + tot + 1;
         }
     }
 
@@ -398,7 +404,7 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
     if (live) {
 #pragma unroll
         for (int m = 0; m < TM_NF; ++m)
-            if (!((TM_SKIP >> m) & 1u)) p.colptr[m][w] = p.nnz_base[m] + g0[m] + ex[m] + 1;  // (non-temporal here: no gain)
+            if (!((TM_SKIP >> m) & 1u) && !(TPAT && m == 0)) p.colptr[m][w] = p.nnz_base[m] + g0[m] + ex[m] + 1;  // (non-temporal here: no gain)
     }
     // the vertical operators only ever hold the rows above, self and below (:438-479): lets the compiler drop
     // the other five slot tests of their staging loops
@@ -406,7 +412,7 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
     // matrices that are not materialised (T alone; a given operator): nothing of them is staged or stored
     const unsigned on0 = (TM_SKIP & 1u) ? 0u : ~0u, on1 = (TM_SKIP & 2u) ? 0u : ~0u, on2 = (TM_SKIP & 4u) ? 0u : ~0u, on3 = (TM_SKIP & 8u) ? 0u : ~0u,
                    on4 = (TM_SKIP & 16u) ? 0u : ~0u;
-    const unsigned pm[5] = {pT & on0, col.padv & on1, col.phh & on2, col.pml & vslots & on3, col.pdp & vslots & on4};
+    const unsigned pm[5] = {(TPAT ? pU : pT) & on0, col.padv & on1, col.phh & on2, col.pml & vslots & on3, col.pdp & vslots & on4};
     // wave-uniform quantities go to scalar registers: the run's base pointers are then SGPR pairs, the stores
     // take the `global_store vaddr32, vdata, sbase` form and the copy loop is a scalar loop
     const u64 ubefore = (u64)wave_uniform((i64)before);
@@ -428,6 +434,7 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
 #pragma unroll
     for (int m = 0; m < TM_NF; ++m) {
         if (HTAB && ((TM_SKIP >> m) & 1u)) continue;  // (a constant: the kept operators' staging and store loops are not compiled)
+        const bool vonly = TPAT && m == 0;            // (a constant: T's values alone, on the kept pattern)
         // The run is streamed out with 16-byte stores (two entries per lane): 8-byte-per-lane stores are store-issue
         // bound per CU (measured: the write phase cost as much as loads + arithmetic).  The run starts at an arbitrary
         // 8-byte position; global_store_dwordx4 does not need more alignment than that, so pairs are simply counted from
@@ -443,14 +450,14 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
                 if ((pm[m] >> s) & 1u) {
                     const unsigned q = q0 + __popc(pm[m] & col.bef[s]);  // position inside the wave's run
                     const double v = (m == 0) ? col.tv[s] : (m == 1) ? col.adv[s] : (m == 2) ? col.hh[s] : (m == 3) ? col.ml[s] : col.dp[s];
-                    my_row[q] = col.idx[s];
+                    if (!vonly) my_row[q] = col.idx[s];
                     my_val[q] = __double_as_longlong(v);
                 }
             }
             // T after an exact cancellation (rare): the column keeps its reserved (union) width, its entries are left-aligned
-            // and the unused slots carry row 0 -- which is how the compaction (tfix_*) finds a column's real length, for
+            // and the unused slots carry row 0 and value 0 -- which is how the compaction (tfix_*: non-zero values) finds a column's real length, for
             // any step of an asynchronous pipeline, from the step's own output arrays
-            if (m == 0 && on0 && (unsigned)__popc(pT) != nU) {
+            if (m == 0 && !vonly && on0 && (unsigned)__popc(pT) != nU) {
                 for (unsigned e = __popc(pT); e < nU; ++e) { my_row[q0 + e] = 0; my_val[q0 + e] = 0; }
             }
         }
@@ -469,12 +476,14 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
             for (unsigned base = 0; base < end; base += 128) {  // full pairs
                 const unsigned u = base + 2 * lane;
                 if (u + 1 < end) {
-                    TM_STORE(*(const i64x2 *)(my_row + u), (i64x2g *)(rvb + u * 8u));
+                    if (!vonly) TM_STORE(*(const i64x2 *)(my_row + u), (i64x2g *)(rvb + u * 8u));
                     TM_STORE(*(const i64x2 *)(my_val + u), (i64x2g *)(nzb + u * 8u));
                 }
             }
-            // an odd run's last entry: ONE 8-byte store instruction, lane 0 writes the row, lane 1 the value
-            if ((lane < 2) & ((end & 1u) == 1u)) {
+            // an odd run's last entry: ONE 8-byte store instruction, lane 0 writes the row, lane 1 the value (values only: lane 0 the value)
+            if (vonly) {
+                if ((lane == 0) & ((end & 1u) == 1u)) TM_STORE(my_val[end - 1], (i64 *)(nzb + (end - 1) * 8u));
+            } else if ((lane < 2) & ((end & 1u) == 1u)) {
                 const unsigned e = end - 1;
                 i64 *dst = (lane == 0) ? (i64 *)(rvb + e * 8u) : (i64 *)(nzb + e * 8u);
                 TM_STORE((lane == 0) ? my_row[e] : my_val[e], dst);
@@ -603,13 +612,17 @@ __global__ void tm_finish_colptr(i64 *c0, i64 *c1, i64 *c2, i64 *c3, i64 *c4, i6
 // union pattern.  Compact: per-column actual counts (tcount) -> scan -> move.  One thread per column.
 #define TFIX_THREADS 256
 #define TFIX_PER 4
-__global__ __launch_bounds__(TFIX_THREADS) void tfix_derive(const i64 *__restrict__ colptr, const i64 *__restrict__ rowval, i64 n, i64 nnz_base,
+// An entry is kept iff its value is not a zero (bits << 1 != 0: +0.0 and -0.0 alike).  T never stores an exact zero (:147), so this holds for
+// both layouts the fill pass leaves: a full write (entries left-aligned, unused slots row 0 and value 0) and a values-only write on the kept
+// pattern (OTMB_KEPT_T_PATTERN: entries at their union positions, a cancelled slot holds its zero sum).
+__device__ __forceinline__ bool tfix_live(const i64 *__restrict__ valbits, i64 e) { return ((u64)valbits[e] << 1) != 0; }
+__global__ __launch_bounds__(TFIX_THREADS) void tfix_derive(const i64 *__restrict__ colptr, const i64 *__restrict__ valbits, i64 n, i64 nnz_base,
                                                             uint8_t *__restrict__ tcount) {
     const i64 c = (i64)blockIdx.x * TFIX_THREADS + threadIdx.x;
     if (c >= n) return;
     const i64 lo = colptr[c] - 1 - nnz_base, hi = colptr[c + 1] - 1 - nnz_base;
     unsigned cnt = 0;
-    for (i64 e = lo; e < hi && e < lo + TM_MAXROWS; ++e) cnt += rowval[e] != 0;  // (rows are 1-based: 0 marks an unused slot)
+    for (i64 e = lo; e < hi && e < lo + TM_MAXROWS; ++e) cnt += tfix_live(valbits, e);
     tcount[c] = (uint8_t)cnt;
 }
 __global__ __launch_bounds__(TFIX_THREADS) void tfix_count(const uint8_t *__restrict__ tcount, i64 n, uint32_t *tilesums) {
@@ -653,11 +666,14 @@ __global__ __launch_bounds__(TFIX_THREADS) void tfix_move(const uint8_t *__restr
         __syncthreads();
         if (c < n) {
             const i64 dst = run + before + incl - mine;  // entries before this column (this launch)
-            const i64 src = old_colptr[c] - 1 - nnz_base;
+            const i64 lo = old_colptr[c] - 1 - nnz_base, hi = old_colptr[c + 1] - 1 - nnz_base;
             new_colptr[c] = nnz_base + dst + 1;
-            for (unsigned e = 0; e < mine; ++e) {
-                new_row[dst + e] = old_row[src + e];
-                new_val[dst + e] = old_val[src + e];
+            unsigned q = 0;
+            for (i64 e = lo; e < hi && e < lo + TM_MAXROWS; ++e) {  // the live entries in stored order (tfix_derive counted them)
+                if (!tfix_live((const i64 *)old_val, e)) continue;
+                new_row[dst + q] = old_row[e];
+                new_val[dst + q] = old_val[e];
+                ++q;
             }
         }
         run += all;
@@ -794,12 +810,14 @@ template <int GIVEN> static void launch_fill_given(otmb_ctx *ctx, const TmParams
     else if (fused == 2) hipLaunchKernelGGL((tm_kernel<2, GIVEN>), grid, block, 0, ctx->stream, p);
     else hipLaunchKernelGGL((tm_kernel<0, GIVEN>), grid, block, 0, ctx->stream, p);
 }
-static void launch_fill(otmb_ctx *ctx, const TmParams &p, int fused) {
+// tpat: T's values only, on the pattern of the context's last full write of T (tpat_take; the table's path only)
+static void launch_fill(otmb_ctx *ctx, const TmParams &p, int fused, bool tpat = false) {
     static const bool env_read = [] { const char *e = getenv("OTMB_GIVEN_READ"); return !(e && e[0] == '0'); }();
     // (a derived TκH: reading is a choice -- regular cells only, OTMB_GIVEN_READ=0 re-derives; the derived rows with other values: it is the only way)
     const bool hread = p.hcp != nullptr && (p.hmust || (env_read && p.nx >= 3)), dread = p.dcp != nullptr;
     const dim3 grid(xcd_grid(p.nt_order, p.nheavy)), block(TM_THREADS);
-    if (p.htab) launch_fill_given<4>(ctx, p, fused, grid, block);  // (all three operators kept: kept_htab)
+    if (p.htab && tpat) launch_fill_given<12>(ctx, p, fused, grid, block);
+    else if (p.htab) launch_fill_given<4>(ctx, p, fused, grid, block);  // (all three operators kept: kept_htab)
     else if (hread && dread) launch_fill_given<3>(ctx, p, fused, grid, block);
     else if (dread) launch_fill_given<2>(ctx, p, fused, grid, block);
     else if (hread) launch_fill_given<1>(ctx, p, fused, grid, block);
@@ -1116,6 +1134,37 @@ static int32_t kept_htab(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl,
     return OTMB_OK;
 }
 
+// ---- otmb_tm_args.kept_ops & OTMB_KEPT_T_PATTERN (host side) --------------------------------------------------------------------------------
+// T's reserved rows are uni = padv | phh | pml | pdp, and padv ⊆ phh | pdp (an advective row is a wet neighbour's, the diagonal comes with one),
+// pml ⊆ pdp: the pattern, colptr and rowval, is a function of the wet mask and the topology alone.  A kept fill whose T arrays hold the union
+// pattern of a clean earlier write stores T's values only (tm_kernel<FUSED, 12>).  The record (ctx->tpat_rec) names that write's arrays and
+// arguments; it counts once its writer is known to have finished without error or exact cancellation (nnz_known).
+static bool tpat_matches(const otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl, const void *colptrT, const void *rowvalT) {
+    const otmb_ctx::KeptRecord &r = ctx->tpat_rec;
+    return r.nnz_known && r.colptr == colptrT && r.rowval == rowvalT && record_matches(r, ctx, a, pl, OTMB_T, nullptr, 0);
+}
+// After kept_htab, for a fill with its outputs in p: does it store T's values only?  Only where the table is read (every invalidation of the kept
+// operators is then one of this promise too) and `allowed` (the two-phase plan honoured the bit).  A fill that keeps all three operators sets
+// otmb_ctx_kept_t_pattern's answer.
+static bool tpat_take(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl, const TmParams &p, bool allowed) {
+    static const bool env_on = [] { const char *e = getenv("OTMB_KEPT_TPAT"); return !(e && e[0] == '0'); }();
+    if (pl.kept != KEPT_OPS || p.skip != KEPT_OPS || p.hcp || p.dcp) return false;  // (not a kept fill: kept_htab's test)
+    const bool t = allowed && env_on && p.htab && (((unsigned)a.kept_ops & OTMB_KEPT_T_PATTERN) != 0) && tpat_matches(ctx, a, pl, p.colptr[0], p.rowval[0]);
+    ctx->tpat_used = t ? 1 : 0;
+    return t;
+}
+// A fill that did not take the record: it wrote T's full pattern into colptrT / rowvalT (the record's new writer: the asynchronous step `serial`,
+// pending, or a clean synchronous fill with serial 0 and count nnz) or left T unwritten (NULL: no record).
+static void tpat_store(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl, void *colptrT, void *rowvalT, uint64_t serial, i64 nnz) {
+    otmb_ctx::KeptRecord &r = ctx->tpat_rec;
+    if (!colptrT || !rowvalT) { r.valid = false; r.nnz_known = false; return; }
+    record_set(r, ctx, a, pl, OTMB_T);
+    r.serial = serial;
+    r.colptr = colptrT; r.rowval = rowvalT; r.nzval = nullptr; r.cap = 0;
+    r.nnz_known = nnz >= 0; r.nnz = nnz >= 0 ? nnz : 0;
+}
+static void tpat_drop(otmb_ctx *ctx) { ctx->tpat_rec.valid = false; ctx->tpat_rec.nnz_known = false; }
+
 // ignore: otmb_tm_args.ignore_ops -- errors that only an operator the caller already has would have raised
 static int32_t check_flags(otmb_ctx *ctx, const int *f = nullptr, int ignore = 0) {
     if (!f) f = ctx->h_flags;
@@ -1169,7 +1218,7 @@ static int32_t t_fixup(otmb_ctx *ctx, i64 n, i64 nnz_base, i64 reserved, i64 *co
     i64 *dtot = (i64 *)(dflags + OTMB_NFLAGS) + 8;
     uint8_t *tc = (uint8_t *)ctx->tcount.p;
     hipLaunchKernelGGL(tfix_derive, dim3((unsigned)((n + TFIX_THREADS - 1) / TFIX_THREADS)), dim3(TFIX_THREADS), 0, ctx->stream,
-                       (const i64 *)colptrT, (const i64 *)rowvalT, n, nnz_base, tc);
+                       (const i64 *)colptrT, (const i64 *)nzvalT, n, nnz_base, tc);
     hipLaunchKernelGGL(tfix_count, dim3((unsigned)nt), dim3(TFIX_THREADS), 0, ctx->stream, (const uint8_t *)tc, n, (uint32_t *)ctx->blocksums.p);
     otmb_launch_tilescan(ctx->stream, (const uint32_t *)ctx->blocksums.p, (i64 *)ctx->blockoffs.p, dtot, nt, 1,
                          (i64 *)ctx->blockoffs.p + (nt + 1));
@@ -1229,6 +1278,15 @@ static int32_t fold_pending(otmb_ctx *ctx) {
                 }
             }
         }
+        if (q < ctx->tm_rec.size()) {  // OTMB_KEPT_T_PATTERN: the record counts once its writer is folded clean; a failed step that used it drops it
+            const otmb_ctx::TmStepRec &rec = ctx->tm_rec[q];
+            otmb_ctx::KeptRecord &tr = ctx->tpat_rec;
+            if (tr.valid && rec.tpat && r.status) tpat_drop(ctx);
+            else if (tr.valid && !rec.tpat && tr.serial == rec.serial) {
+                if (r.status || f[FLAG_T_CANCEL]) tpat_drop(ctx);  // (a cancelling full write leaves its columns left-aligned: not the union pattern)
+                else { tr.nnz_known = true; tr.nnz = tot[0]; }
+            }
+        }
         if (r.status && !ctx->tm_sticky) { ctx->tm_sticky = r.status; ctx->tm_sticky_step = s; ctx->tm_sticky_msg = ctx->err; }
         if (!r.status && f[FLAG_T_CANCEL] && q < ctx->tm_rec.size()) {
             const otmb_ctx::TmStepRec &rec = ctx->tm_rec[q];
@@ -1239,6 +1297,7 @@ static int32_t fold_pending(otmb_ctx *ctx) {
                 i64 actual = r.nnz[0];
                 ret = t_fixup(ctx, rec.n_wet, rec.nnz_base0, r.nnz[0], (i64 *)rec.colptrT, (i64 *)rec.rowvalT, (double *)rec.nzvalT, &actual);
                 r.nnz[0] = actual;
+                if (ctx->tpat_rec.colptr == rec.colptrT || ctx->tpat_rec.rowval == rec.rowvalT) tpat_drop(ctx);  // (compacted: not the union pattern)
             }
         }
         ctx->tm_hist.push_back(r);
@@ -1335,6 +1394,10 @@ int32_t otmb_transportmatrix_plan_dev(otmb_ctx *ctx, const otmb_tm_args *a, int6
                 kept_matches(ctx, *a, pl, m, nullptr, 0))
                 pl.kept |= 1u << m;
     pl.skip |= pl.kept;
+    // OTMB_KEPT_T_PATTERN: a clean record for these arguments (its arrays are checked by fill, its count below)
+    const otmb_ctx::KeptRecord &tr = ctx->tpat_rec;
+    pl.tpat = (((unsigned)a->kept_ops & OTMB_KEPT_T_PATTERN) != 0) && pl.kept == KEPT_OPS && !(pl.skip & 1u) && ctx->tm_next == ctx->tm_first &&
+              tr.nnz_known && record_matches(tr, ctx, *a, pl, OTMB_T, nullptr, 0);
     TmParams p;
     fill_params(p, *a, ctx, &pl);
     int *dflags = (int *)ctx->flags.p;
@@ -1374,6 +1437,7 @@ int32_t otmb_transportmatrix_plan_dev(otmb_ctx *ctx, const otmb_tm_args *a, int6
     for (int m = 0; m < 5; ++m) nnz[m] = pl.nnz[m] = pl.built_nnz[m] = ctx->h_tot[m];  // (0 for what is not materialised)
     for (int m = OTMB_TKH; m <= OTMB_TKVDEEP; ++m)
         if ((pl.kept >> m) & 1u) nnz[m] = pl.nnz[m] = ctx->kept_rec[m].nnz;  // (kept: the count of the write it was kept from)
+    if (pl.tpat && pl.nnz[0] != tr.nnz) pl.tpat = false;  // (another pattern: the record is not about these arrays' contents)
     if (pl.foreign && pl.want_t) {
         // T = ((Tadv + TκH) + TκVML) + TκVdeep by the device sparse add (:147): its pattern is the union of the four operands', at most the
         // sum of their counts -- what the caller's T arrays must hold until otmb_transportmatrix_nnz gives the final count
@@ -1420,6 +1484,12 @@ int32_t otmb_transportmatrix_fill_dev(otmb_ctx *ctx, int64_t *const colptr[5], i
             return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "kept_ops: the output arrays of a kept operator are not the ones its record names (plan again without the bit)");
         }
     }
+    if (pl.tpat && !(tpat_matches(ctx, pl.args, pl, colptr[0], rowval[0]) && ctx->tpat_rec.nnz == pl.nnz[0])) {
+        kept_drop(ctx, 0);
+        tpat_drop(ctx);
+        pl.valid = false;
+        return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "kept_ops: T's arrays are not the ones the OTMB_KEPT_T_PATTERN record names (plan again without the bit)");
+    }
     kept_drop(ctx, pl.kept);
     for (int m = 0; m < 5; ++m) {
         const bool wanted = !((pl.skip >> m) & 1u) || (m == 0 && pl.foreign && pl.want_t);  // (T of a foreign build: written by the sparse adds below)
@@ -1429,11 +1499,16 @@ int32_t otmb_transportmatrix_fill_dev(otmb_ctx *ctx, int64_t *const colptr[5], i
     }
     int32_t rc;
     int *dflags = (int *)ctx->flags.p;
+    bool tpat = false;
     if (pl.ntiles > 0) {
         if ((rc = build_tile_order(ctx, pl.args, pl.ntiles, p))) return rc;
         if ((rc = kept_htab(ctx, pl.args, pl, p))) return rc;
+        tpat = tpat_take(ctx, pl.args, pl, p, pl.tpat);
+        if (!tpat) tpat_drop(ctx);  // (T is written in full, or not at all: a clean write below records itself)
         KernelTimer kt(ctx, K_TM_FILL);
-        launch_fill(ctx, p, 0);
+        launch_fill(ctx, p, 0, tpat);
+    } else {
+        tpat_drop(ctx);
     }
     if (pl.ntiles == 0) {  // (otherwise the fill kernel's last tile writes the closing colptr entries)
         KernelTimer kt(ctx, K_TM_FINISH);
@@ -1448,10 +1523,13 @@ int32_t otmb_transportmatrix_fill_dev(otmb_ctx *ctx, int64_t *const colptr[5], i
     // a plan is consumed by its fill: T's final count may be smaller than the reserved (union) one, so a second fill into
     // buffers sized from otmb_transportmatrix_nnz would overflow them -- plan again instead
     pl.valid = false;
-    if ((rc = check_flags(ctx, nullptr, pl.args.ignore_ops | (int)pl.given))) return rc;
+    if ((rc = check_flags(ctx, nullptr, pl.args.ignore_ops | (int)pl.given))) {
+        tpat_drop(ctx);
+        return rc;
+    }
     // the operators this fill stored: their records (a synchronous write, count known) -- only when no asynchronous step is pending, whose fold
     // would take its counts for the steps that kept from IT
-    if (ctx->tm_next == ctx->tm_first)
+    if (ctx->tm_next == ctx->tm_first) {
         for (int m = OTMB_TKH; m <= OTMB_TKVDEEP; ++m) {
             void *out[3] = {p.colptr[m], p.rowval[m], p.nzval[m]};
             if (!((pl.skip >> m) & 1u)) {
@@ -1459,9 +1537,13 @@ int32_t otmb_transportmatrix_fill_dev(otmb_ctx *ctx, int64_t *const colptr[5], i
                 ctx->kept_fold_nnz[m] = pl.nnz[m]; ctx->kept_fold_status[m] = 0;  // (what an asynchronous step that keeps from it reports)
             }
         }
+        // T's full pattern, written without cancellation: the record of OTMB_KEPT_T_PATTERN
+        if (!tpat && pl.ntiles > 0 && !(pl.skip & 1u) && !ctx->h_flags[FLAG_T_CANCEL]) tpat_store(ctx, pl.args, pl, p.colptr[0], p.rowval[0], 0, pl.nnz[0]);
+    }
     if (pl.foreign && pl.want_t) return foreign_sum(ctx, pl, p);
     if (pl.skip & 1u) return OTMB_OK;  // (no T: nothing to compact)
     if (ctx->h_flags[FLAG_T_CANCEL]) {
+        tpat_drop(ctx);  // (compacted below: not the union pattern any more)
         i64 actual = pl.nnz[0];
         if ((rc = t_fixup(ctx, pl.args.n_wet, pl.nnz_base[0], pl.nnz[0], p.colptr[0], p.rowval[0], p.nzval[0], &actual))) return rc;
         pl.nnz[0] = actual;
@@ -1596,6 +1678,7 @@ static int32_t transportmatrix_dev_impl(otmb_ctx *ctx, const otmb_tm_args *a, in
     }
     ctx->ring_clean &= ~(1ull << slot_after);
     p.next_state = (ntiles > 0) ? otmb_ring_tm((int *)ctx->ring.p, ctx->tm_next + 1) : nullptr;
+    bool tpat = false;
     if (ntiles == 0) {
         KernelTimer kt(ctx, K_TM_FINISH);
         hipLaunchKernelGGL(tm_finish_colptr, dim3(1), dim3(64), 0, ctx->stream, p.colptr[0], p.colptr[1], p.colptr[2],
@@ -1635,19 +1718,22 @@ static int32_t transportmatrix_dev_impl(otmb_ctx *ctx, const otmb_tm_args *a, in
 #endif
             if ((rc = build_tile_order(ctx, *a, ntiles, p))) return rc;
             if ((rc = kept_htab(ctx, *a, pl, p))) return rc;
+            tpat = tpat_take(ctx, *a, pl, p, true);
             KernelTimer kt(ctx, K_TM_FILL);
-            launch_fill(ctx, p, fu.kind);
+            launch_fill(ctx, p, fu.kind, tpat);
         }
     }
     HIP_TRY(ctx, hipGetLastError());
     if (p.next_state) ctx->ring_clean |= 1ull << slot_after;
     const uint64_t serial = ++ctx->tm_serial;
+    // OTMB_KEPT_T_PATTERN: a step that wrote T's full pattern is the record's new writer (it counts once folded clean); one that left T unwritten drops it
+    if (!tpat) tpat_store(ctx, *a, pl, ntiles > 0 ? p.colptr[0] : nullptr, ntiles > 0 ? p.rowval[0] : nullptr, serial, -1);
     const unsigned wrote = KEPT_OPS & ~pl.skip;
     for (int m = OTMB_TKH; m <= OTMB_TKVDEEP; ++m) {
         void *out[3] = {p.colptr[m], p.rowval[m], p.nzval[m]};
         if ((wrote >> m) & 1u) kept_store(ctx, *a, pl, m, out, capacity[m], -1, serial);  // (its nnz when the step is folded)
     }
-    ctx->tm_rec.push_back({p.colptr[0], p.rowval[0], p.nzval[0], (i64)a->n_wet, p.nnz_base[0], (int)a->ignore_ops | (int)pl.given, wrote, pl.kept, serial});
+    ctx->tm_rec.push_back({p.colptr[0], p.rowval[0], p.nzval[0], (i64)a->n_wet, p.nnz_base[0], (int)a->ignore_ops | (int)pl.given, wrote, pl.kept, serial, tpat});
     ctx->tm_next += 1;
     pl.onepass_pending = true;
     return OTMB_OK;

@@ -16,6 +16,7 @@ from .capi import HDIRS, MATS, PHI_ORDER
 
 # the library reads OTMB_KEPT_HTAB once per process (the first kept fill): what it will find, for accounting before that fill
 _KEPT_HTAB_ON = os.environ.get("OTMB_KEPT_HTAB", "1")[:1] != "0"
+_KEPT_TPAT_ON = os.environ.get("OTMB_KEPT_TPAT", "1")[:1] != "0"  # (likewise OTMB_KEPT_TPAT: T's values-only fills)
 
 
 def _flat(a, dtype=np.float64):
@@ -411,6 +412,22 @@ class DeviceAssembler:
         """The next call writes all five matrices (grid, κ, given operators changed; outputs overwritten; an error)."""
         self._kept = None
         self._kept_last = ()
+        self._tpat = None
+        self._tpat_last = False
+
+    # T's pattern (OTMB_KEPT_T_PATTERN) is a function of the wet mask and the topology alone: when T's colptr / rowval tensors are the ones the
+    # library last wrote, untouched by torch since, a step that keeps the three operators adds the bit and the fill stores T's values only (the
+    # library checks its own record as well).  Tracked apart from _kept / _kept_last.
+    def _tpat_key(self, out):
+        ts = out["T"][:2]
+        return [weakref.ref(t) for t in ts], tuple((t.data_ptr(), t._version) for t in ts)
+
+    def _tpat_promise(self, out):
+        rec = getattr(self, "_tpat", None)
+        if rec is None:
+            return False
+        refs, key = self._tpat_key(out)
+        return rec[1] == key and all(r() is t() for r, t in zip(rec[0], refs))
 
     def _kept_key(self, out):
         # the output set's nine tensors (by identity: a recycled address is another set) and every grid array the three operators are derived from
@@ -421,19 +438,22 @@ class DeviceAssembler:
     def _kept_ops(self, out):
         """kept_ops for a call into `out`, and the names it covers."""
         self._kept_last = ()
+        self._tpat_last = False
         rec = getattr(self, "_kept", None)
         if rec is None or getattr(self, "given", None) or getattr(self, "only_T", False):
             return 0, ()
         refs, key = self._kept_key(out)
         if rec[1] != key or any(r() is not t() for r, t in zip(rec[0], refs)):
             return 0, ()
-        return sum(1 << MATS.index(m) for m in self.KEPT), self.KEPT
+        self._tpat_last = self._tpat_promise(out)
+        return sum(1 << MATS.index(m) for m in self.KEPT) | (capi.KEPT_T_PATTERN if self._tpat_last else 0), self.KEPT
 
     def _kept_written(self, out, kept):
         """After a call into `out` was accepted: it wrote (or kept) the three operators unless some were given / not wanted."""
         self._kept_last = kept
         off = getattr(self, "given", None) or getattr(self, "only_T", False) or os.environ.get("OTMB_KEPT", "1") == "0"  # (OTMB_KEPT=0: A/B)
         self._kept = None if off else self._kept_key(out)
+        self._tpat = None if off else self._tpat_key(out)  # (T's pattern: written by this call, or where the last one left it)
 
     def _kept_steady(self):
         """The operators a step of this loop does not store: those the last call kept, or -- after a full write that left the promise live -- those
@@ -449,6 +469,17 @@ class DeviceAssembler:
             return 0
         used = self.ctx.kept_htab()
         return 40 * self.N if (used == 1 or (used < 0 and self.nx >= 3 and _KEPT_HTAB_ON)) else 0
+
+    def _tpat_steady(self, skip):
+        """Whether a kept step of this loop (`skip`) stores T's values only: its colptr and rowval are then not written.  Like _kept_steady, the
+        time loop's steady state: the promise was made or is live for the next call, the TκH table is read (the library takes the pattern on
+        that path only) and OTMB_KEPT_TPAT was not 0 as this process started.  (Whether the last fill took it, otmb_ctx_kept_t_pattern, also
+        depends on whether the record's writer has been folded yet: the first steps of a pipeline write T in full.)"""
+        if not set(self.KEPT) <= skip or getattr(self, "given", None) or "T" in skip:
+            return False
+        if not (getattr(self, "_tpat_last", False) or getattr(self, "_tpat", None) is not None):
+            return False
+        return _KEPT_TPAT_ON and self._htab_bytes(skip) > 0
 
     def _check(self, rc):
         try:
@@ -736,13 +767,15 @@ class DeviceAssembler:
         """(bytes read, bytes written) of algorithmic_bytes().  An operator the caller passes and the fill pass re-derives (set_given) is
         neither read nor written: its 16 nnz + 8 (N + 1) bytes are not part of the pass.  Nor is one the last call kept where the previous
         write left it, or that the next call keeps (otmb_tm_args.kept_ops: a time loop's steady state); when all three are kept the pass reads
-        the library's TκH table instead of thkcello and the edge / distance metrics (_htab_bytes)."""
+        the library's TκH table instead of thkcello and the edge / distance metrics (_htab_bytes), and writes T's values only when its pattern
+        is kept too (_tpat_steady: 8 nnz(T), no colptr, no rowval)."""
         skip = set(getattr(self, "given", None) or ()) | self._kept_steady()
         htab = self._htab_bytes(skip)
+        tpat = self._tpat_steady(skip)
         n3d = 9 + (1 if self.rho is not None else 0) - (1 if htab else 0)  # (thkcello)
         n2d = 10 - (8 if htab else 0)  # (the edge lengths and distances: area and mlotst stay)
         return (8 * self.G * n3d + 8 * n2d * self.nx * self.ny + 8 * self.nz + htab,
-                sum(16 * z + 8 * (self.N + 1) for m, z in zip(MATS, self.nnz) if m not in skip))
+                sum((8 * z if (m == "T" and tpat) else 16 * z + 8 * (self.N + 1)) for m, z in zip(MATS, self.nnz) if m not in skip))
 
     def fill_pass_stream_mix(self):
         """What an ideal streaming kernel reaches over the fill pass's OWN arrays (otmb_ctx_stream_mix): its ten 3-D inputs (+ the 2-D
@@ -754,6 +787,7 @@ class DeviceAssembler:
         b8 = lambda t, n=None: (t.data_ptr(), 8 * (t.numel() if n is None else n))
         skip = self._kept_steady()
         htab = self._htab_bytes(skip)
+        tpat = self._tpat_steady(skip)
         self._forget_kept()
         ins = [b8(p) for p in self.phi] + [b8(self.v3d), b8(self.lwet3d)] + ([b8(self.rho)] if self.rho is not None else [])
         ins += [b8(t) for t in (self.area, self.mlotst)]
@@ -768,7 +802,7 @@ class DeviceAssembler:
             if m in skip:
                 continue
             cp, rv, nz = self.out[m]
-            outs += [b8(cp, self.N + 1), b8(rv, self.nnz[k]), b8(nz, self.nnz[k])]
+            outs += [b8(nz, self.nnz[k])] if (m == "T" and tpat) else [b8(cp, self.N + 1), b8(rv, self.nnz[k]), b8(nz, self.nnz[k])]
         # the fill pass's own granularity (256 columns per slice) and longer slices: a plain stream likes them longer where the grid is large
         # enough to still fill the chip (profiles/r05: 4.3 / 4.3 / 3.9 / 3.7 TB/s at 1 degree, 4.9 / 5.4 / 5.6 / 5.5 TB/s at 0.25 degree)
         return {cols: self.ctx.stream_mix(ins, outs, max(8, self.N // cols)) for cols in (256, 512, 1024, 2048)}
