@@ -402,6 +402,10 @@ int32_t otmb_ctx_kept_htab(const otmb_ctx *ctx);
 /* ... and whether that fill stored T's values only (otmb_tm_args.kept_ops & OTMB_KEPT_T_PATTERN honoured): 1 yes, 0 no (T written in full),
  * -1 no such fill yet.  OTMB_KEPT_TPAT=0 in the environment always writes T in full. */
 int32_t otmb_ctx_kept_t_pattern(const otmb_ctx *ctx);
+/* ... and how many fills on this context have stored T's values only so far: unlike otmb_ctx_kept_t_pattern (which a fill that does not keep all
+ * three operators leaves as it was), the count changes with every such fill -- read it before and after a call to learn what THAT call did
+ * (DeviceAssembler decides with it whether a resident operator over T may keep its plan, otmb_op_*). */
+int64_t otmb_ctx_kept_t_pattern_fills(const otmb_ctx *ctx);
 
 /* Two-phase protocol so the CALLER allocates the outputs (Julia owns its SparseMatrixCSC buffers).
  * plan: the nnz of the four operator matrices (exact: their patterns depend on the wet mask, the flux
@@ -627,6 +631,34 @@ int32_t otmb_coarsen_plan(otmb_ctx *ctx, int64_t m, int64_t N, const int64_t *Ap
                           const int64_t *Bp, const int64_t *Bi, const double *Bx, int64_t n, const int64_t *Sp, const int64_t *Si,
                           const double *Sx, int64_t *nnz);
 int32_t otmb_coarsen_fetch(otmb_ctx *ctx, int64_t *Cp, int64_t *Ci, double *Cx);
+
+/* ---- A resident sparse operator: Y = α·A·X + β·Y and Y = α·Aᵀ·X + β·Y on the device -- what the reference's consumer checks compute
+ *      with the matrices it builds (test/local_full.jl:96-107: norm(T * e1), norm(T' * v)) and what a tracer simulation steps with
+ *      (README: ∂x/∂t + T x = …).  Bit for bit SparseArrays' 5-argument mul! of Julia 1.10 (Project.toml: julia = "1.10"):
+ *        β step first: β == 0 fills Y with +0.0, β == 1 leaves it, otherwise Y .*= β;
+ *        A·X: for each column c of X, for col = 1..n, αxj = X[col,c] * α, then Y[rowval[j],c] += nzval[j] * αxj in stored order;
+ *        Aᵀ·X: tmp = +0.0, tmp += nzval[j] * X[rowval[j],c] in stored order, then Y[col,c] += tmp * α.
+ *      No FMA.  A: m x n SparseMatrixCSC{Float64,Int64} arrays (1-based; rows need not be sorted or distinct inside a column); X, Y:
+ *      column-major Float64 with k >= 1 columns and leading dimensions ldx / ldy >= their rows.  `A * x` and `A' * v` are alpha = 1,
+ *      beta = 0.
+ * otmb_op_create_dev (device pointers, copied on the device) / otmb_op_create (host pointers, uploaded): checks colptr[1] == 1, colptr
+ *   non-decreasing, every rowval in 1:m (OTMB_ERR_INVALID_ARG before anything is read through them), then plans the row layout of A·X.
+ *   The operator owns copies of everything: no caller array is read after a call returns.  An opaque handle, not keyed to addresses.
+ * otmb_op_set_values[_dev]: new nzval (nnz of them) for the same pattern.
+ * otmb_op_mul_dev: X, Y device pointers, enqueued on the context's stream without a host sync.  otmb_op_mul: host pointers (uploads X,
+ *   and Y when beta != 0; downloads Y; the rows between ld and the row count are neither read nor written).
+ * Null arguments, k < 1, ldx / ldy too small: OTMB_ERR_INVALID_ARG with a message (otmb_last_error of the operator's context); the
+ *   operator stays usable.  An operator uses its context's stream and messages: destroy operators before their context.
+ *   otmb_op_destroy touches no context (a finalizer may run it after the context is gone); it waits for the device.            */
+typedef struct otmb_op otmb_op;
+int32_t otmb_op_create_dev(otmb_ctx *ctx, int64_t m, int64_t n, const int64_t *colptr, const int64_t *rowval, const double *nzval, otmb_op **out);
+int32_t otmb_op_create(otmb_ctx *ctx, int64_t m, int64_t n, const int64_t *colptr, const int64_t *rowval, const double *nzval, otmb_op **out);
+int32_t otmb_op_set_values_dev(otmb_op *op, const double *nzval, int64_t nnz);
+int32_t otmb_op_set_values(otmb_op *op, const double *nzval, int64_t nnz);
+int32_t otmb_op_mul_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy, double alpha, double beta);
+int32_t otmb_op_mul(otmb_op *op, int32_t adjoint, int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy, double alpha, double beta);
+int32_t otmb_op_info(const otmb_op *op, int64_t *m, int64_t *n, int64_t *nnz);
+void otmb_op_destroy(otmb_op *op);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,7 @@
 #                               that starts from uo / vo runs THIS module's facefluxes and not the reference's CPU one)
 #   lump_and_spray              src/extratools.jl:38-119
 #   coarsen                     LUMP * T * SPRAY (src/extratools.jl:14-16)
+#   DeviceOperator, setvalues!  T * x, T' * v, mul!(Y, T, X, α, β) on the GPU (test/local_full.jl:96-107; README: ∂x/∂t + T x = …)
 #   bolus_GM_velocity           src/RediGM.jl:46-79 (unexported and experimental there, unexported here)
 #   makegridmetrics             src/gridcellgeometry.jl:265-311: the reference's own by default (its haversines are Julia's libm);
 #                               `makegridmetrics(...; gpu = true)` opts into the library's array work (distances within 1e-12)
@@ -24,16 +25,19 @@ module OceanTransportMatrixBuilderAMD
 
 using SparseArrays
 using Libdl
+import LinearAlgebra
 import OceanTransportMatrixBuilder as OTMB
 
 # the reference's exported names (src/OceanTransportMatrixBuilder.jl:31-36), every one of them defined in THIS module
 export makegridmetrics, velocity2fluxes, fluxes2velocity, facefluxesfromvelocities
 export makeindices, facefluxesfrommasstransport, facefluxes, transportmatrix, lump_and_spray, coarsen
+export DeviceOperator, setvalues!
 
 const LIBPATH = get(ENV, "OTMB_HIP_LIB", joinpath(@__DIR__, "..", "oceantransportmatrixbuilder.jl_amd", "lib", "libotmb_hip.so"))
 const lib = Ref{Ptr{Cvoid}}(C_NULL)
 const ctx = Ref{Ptr{Cvoid}}(C_NULL)              # the single-GPU context: created by the first call that needs it (`context()`)
 const host_free_fn = Ref{Ptr{Cvoid}}(C_NULL)     # otmb_host_free, resolved once: finalizers must not look symbols up
+const op_destroy_fn = Ref{Ptr{Cvoid}}(C_NULL)    # otmb_op_destroy, likewise (DeviceOperator's finalizer)
 const MGPU = Dict{Vector{Int32},Ptr{Cvoid}}()    # otmb_mgpu objects by device list (`devices = 0:7`)
 # A context (and an otmb_mgpu) is "not shared between threads" (include/otmb.h): every public entry point of this module runs
 # its C calls under this lock, so tasks on several Julia threads may call the module freely.  Finalizers never take it: the one
@@ -48,6 +52,7 @@ function __init__()
     Libdl.dlopen(get(ENV, "OTMB_HIP_RUNTIME", "/opt/rocm/lib/libamdhip64.so"), Libdl.RTLD_GLOBAL)
     lib[] = Libdl.dlopen(LIBPATH)
     host_free_fn[] = Libdl.dlsym(lib[], :otmb_host_free)
+    op_destroy_fn[] = Libdl.dlsym(lib[], :otmb_op_destroy)
     # (no context yet: a caller that only ever passes `devices = 4:7` must not have one created on GPU 0 behind its back)
     # Julia runs atexit hooks BEFORE its final finalizer sweep: result arrays that are still alive are finalized AFTER this hook.
     # That is safe by construction: pinned blocks belong to a process-wide pool that no context owns (otmb_ctx_destroy frees none of
@@ -259,6 +264,97 @@ function coarsen(LUMP::SparseMatrixCSC{Float64,Int64}, T::SparseMatrixCSC{Float6
         check(ccall(sym(:otmb_coarsen_fetch), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}), ctx[], Cp, Ci, Cx))
         return SparseMatrixCSC{Float64,Int64}(m, n, Cp, Ci, Cx)
     end
+end
+
+# A sparse operator resident on the GPU (otmb_op_*): `mul!(Y, D, X, α, β)`, `mul!(Y, D', X, α, β)`, `D * x`, `D' * v` bit for bit
+# SparseArrays' 5-argument mul! of Julia 1.10 (the β step first, then one fold per output element in storage order, no FMA), for the
+# reference's consumer checks (test/local_full.jl:96-107: norm(T * e1), norm(T' * v)) and tracer stepping.  The operator owns device
+# copies of the matrix (A may change or go once the constructor returns); `setvalues!` gives it new nzval for the same pattern.  Methods
+# are defined for this module's own types only: `*` and `mul!` on a SparseMatrixCSC stay SparseArrays'.
+mutable struct DeviceOperator
+    handle::Ptr{Cvoid}
+    m::Int64
+    n::Int64
+    nnz::Int64
+end
+struct AdjointDeviceOperator
+    parent::DeviceOperator
+end
+Base.adjoint(D::DeviceOperator) = AdjointDeviceOperator(D)
+Base.adjoint(A::AdjointDeviceOperator) = A.parent
+Base.size(D::DeviceOperator) = (D.m, D.n)
+Base.size(A::AdjointDeviceOperator) = (A.parent.n, A.parent.m)
+# (not AbstractArrays: Base has no size(x, d) for them, so the operators get their own, with an AbstractArray's trailing 1s)
+Base.size(D::Union{DeviceOperator,AdjointDeviceOperator}, d::Integer) = d < 1 ? throw(ArgumentError("dimension $d out of range")) :
+    d <= 2 ? size(D)[d] : 1
+SparseArrays.nnz(D::DeviceOperator) = D.nnz
+
+function DeviceOperator(A::SparseMatrixCSC{Float64,Int64})
+    m, n = size(A)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    lock(CALL_LOCK) do
+        check(ccall(sym(:otmb_op_create), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Ptr{Cvoid}}),
+            context(), m, n, A.colptr, A.rowval, A.nzval, h))
+    end
+    D = DeviceOperator(h[], m, n, nnz(A))
+    finalizer(D) do d
+        release!(d)
+    end
+    return D
+end
+
+# DeviceOperator's finalizer.  otmb_op_destroy touches no context (safe after the atexit hook destroyed it) and is called through a
+# pointer resolved in __init__.  A finalizer must not wait for a lock (no task switch inside the collector): when a call holds the
+# module's lock, the finalizer is registered again and runs at a later collection.
+function release!(D::DeviceOperator)
+    D.handle == C_NULL && return nothing
+    if trylock(CALL_LOCK)
+        try
+            ccall(op_destroy_fn[], Cvoid, (Ptr{Cvoid},), D.handle)
+            D.handle = C_NULL
+        finally
+            unlock(CALL_LOCK)
+        end
+    else
+        finalizer(D) do d
+            release!(d)
+        end
+    end
+    return nothing
+end
+
+function opmul!(Y::StridedVecOrMat{Float64}, D::DeviceOperator, adjoint::Bool, X::StridedVecOrMat{Float64}, α::Number, β::Number)
+    rx, ry = adjoint ? (D.m, D.n) : (D.n, D.m)
+    (size(X, 1) == rx && size(Y, 1) == ry && size(X, 2) == size(Y, 2)) ||
+        throw(DimensionMismatch("$(adjoint ? "A'" : "A") of $((ry, rx)), X $(size(X)), Y $(size(Y))"))
+    (stride(X, 1) == 1 && stride(Y, 1) == 1) || throw(ArgumentError("X and Y need contiguous columns"))
+    k = size(X, 2)
+    ldx = X isa AbstractVector || k <= 1 ? max(rx, 1) : stride(X, 2)
+    ldy = Y isa AbstractVector || k <= 1 ? max(ry, 1) : stride(Y, 2)
+    lock(CALL_LOCK) do
+        D.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        check(ccall(sym(:otmb_op_mul), Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Float64, Float64),
+            D.handle, Int32(adjoint), k, X, ldx, Y, ldy, Float64(α), Float64(β)))
+    end
+    return Y
+end
+
+LinearAlgebra.mul!(Y::StridedVecOrMat{Float64}, D::DeviceOperator, X::StridedVecOrMat{Float64}, α::Number, β::Number) = opmul!(Y, D, false, X, α, β)
+LinearAlgebra.mul!(Y::StridedVecOrMat{Float64}, A::AdjointDeviceOperator, X::StridedVecOrMat{Float64}, α::Number, β::Number) =
+    opmul!(Y, A.parent, true, X, α, β)
+# `A * x` and `A' * v` are mul!(…, true, false): α = 1.0, β = 0.0
+LinearAlgebra.mul!(Y::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, X::StridedVecOrMat{Float64}) =
+    LinearAlgebra.mul!(Y, D, X, true, false)
+Base.:*(D::Union{DeviceOperator,AdjointDeviceOperator}, X::StridedVecOrMat{Float64}) =
+    LinearAlgebra.mul!(X isa AbstractVector ? Vector{Float64}(undef, size(D)[1]) : Matrix{Float64}(undef, size(D)[1], size(X, 2)), D, X, true, false)
+
+# new nzval for the pattern the operator was made with (the library checks the length it is told)
+function setvalues!(D::DeviceOperator, nzval::Vector{Float64})
+    lock(CALL_LOCK) do
+        D.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        check(ccall(sym(:otmb_op_set_values), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64), D.handle, nzval, length(nzval)))
+    end
+    return D
 end
 
 const HDIRS = (:west, :east, :south, :north)      # OTMB_DIR_*

@@ -19,7 +19,7 @@ def __getattr__(name):
     # api/capi import the HIP library lazily so that host-only helpers work without it
     if name in ("makeindices", "facefluxesfrommasstransport", "facefluxes", "transportmatrix", "velocity2fluxes",
                 "fluxes2velocity", "facefluxesfromvelocities", "interpolateontodefaultCgrid", "lump_and_spray", "as2D", "as3D",
-                "spadd", "coarsen", "bolus_GM_velocity",
+                "spadd", "coarsen", "DeviceOperator", "bolus_GM_velocity",
                 "buildTadv", "buildTκH", "buildTκVML", "buildTκVdeep", "buildTkH", "buildTkVML", "buildTkVdeep"):
         from . import api
         return getattr(api, name)

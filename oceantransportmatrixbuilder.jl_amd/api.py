@@ -792,6 +792,102 @@ def coarsen(LUMP, T, SPRAY, *, device=0):
     return SparseMatrixCSC(m, n, Cp, Ci[:k], Cx[:k])
 
 
+def _column_major(a):
+    """(array, leading dimension) of a 1-D or 2-D float64 array whose rows are contiguous (a Fortran-ordered array or a row slice of
+    one keeps its leading dimension); anything else is copied into Fortran order."""
+    if a.dtype != np.float64 or (a.ndim == 2 and a.strides[0] != 8) or (a.ndim == 1 and a.strides[0] != 8) or \
+            (a.ndim == 2 and a.shape[1] > 1 and (a.strides[1] % 8 != 0 or a.strides[1] < 8 * a.shape[0])):
+        a = np.asfortranarray(a, dtype=np.float64)
+    ld = a.shape[0] if a.ndim == 1 or a.shape[1] <= 1 else a.strides[1] // 8
+    return a, max(ld, a.shape[0])
+
+
+class DeviceOperator:
+    """A sparse operator resident on the device: Y = α·A·X + β·Y and Y = α·Aᵀ·X + β·Y, bit for bit SparseArrays' 5-argument mul! of
+    Julia 1.10 -- what the reference's consumer checks compute (test/local_full.jl:96-107: norm(T * e1), norm(T' * v)) and what a tracer
+    simulation steps with.  The contract (csrc/otmb_spmv.hip, tests/spmv_ref.py):
+      * β step first (LinearAlgebra._rmul_or_fill!): β == 0 fills Y with +0.0 (NaN / Inf in Y are discarded), β == 1 leaves Y, otherwise
+        Y[i,c] * β;
+      * A·X (_spmatmul!): for each tracer c, for col = 1..n, αxj = X[col,c] * α, then Y[rowval[j],c] += nzval[j] * αxj in stored order
+        -- each Y[i,c] a left fold from the β value in storage order (duplicate / unsorted rows included);
+      * Aᵀ·X (_At_or_Ac_mul_B!): tmp = +0.0, tmp += nzval[j] * X[rowval[j],c] in stored order, then Y[col,c] += tmp * α;
+      * no FMA; `A * x` and `A' * v` are α = 1.0, β = 0.0.
+    A: a SparseMatrixCSC (1-based).  The operator owns device copies of A: the arrays may change or go once the constructor returns.
+    The same C calls as the Julia shim's DeviceOperator: otmb_op_create; mul! -> otmb_op_mul; setvalues! -> otmb_op_set_values; the
+    finalizer -> otmb_op_destroy."""
+
+    def __init__(self, A, *, device=0):
+        self._h = C.c_void_p()
+        self.ctx = context(device)
+        p, i, v = (np.ascontiguousarray(x, dtype=t) for x, t in ((A.colptr, np.int64), (A.rowval, np.int64), (A.nzval, np.float64)))
+        if len(p) != A.n + 1 or len(i) < p[-1] - 1 or len(v) < p[-1] - 1:
+            raise capi.OtmbError(11, f"invalid argument: SparseMatrixCSC arrays of a {A.shape} matrix have lengths {len(p)}, {len(i)}, {len(v)}")
+        lib = capi.lib()
+        self.ctx.check(lib.otmb_op_create(self.ctx.handle, int(A.m), int(A.n), p.ctypes.data, i.ctypes.data, v.ctypes.data, C.byref(self._h)))
+        self.shape = (int(A.m), int(A.n))
+        self.nnz = int(p[-1] - 1)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def _live(self):
+        if not self._h.value:
+            raise ValueError("DeviceOperator is closed")
+
+    def mul(self, X, *, alpha=1.0, beta=0.0, Y=None, adjoint=False):
+        """α·A·X + β·Y (adjoint: α·Aᵀ·X + β·Y).  X: 1-D (one tracer) or 2-D (rows x k); Y: None (a new array; β must be 0) or an array of
+        the result's shape, updated in place and returned.  1-D in, 1-D out; 2-D results are Fortran-ordered."""
+        self._live()
+        m, n = self.shape
+        rx, ry = (m, n) if adjoint else (n, m)
+        X = np.asarray(X)
+        if X.ndim not in (1, 2) or X.shape[0] != rx:
+            raise capi.OtmbError(11, f"DimensionMismatch: {'Aᵀ' if adjoint else 'A'} of {(ry, rx)} times X of {X.shape}")
+        k = 1 if X.ndim == 1 else X.shape[1]
+        oshape = (ry,) if X.ndim == 1 else (ry, k)
+        if Y is None:
+            if beta != 0:
+                raise ValueError("beta != 0 needs Y")
+            Y = np.empty(oshape, dtype=np.float64, order="F")
+        if tuple(Y.shape) != oshape:
+            raise capi.OtmbError(11, f"DimensionMismatch: Y of {Y.shape}, expected {oshape}")
+        Xc, ldx = _column_major(X)
+        Yc, ldy = _column_major(Y)
+        lib = capi.lib()
+        self.ctx.check(lib.otmb_op_mul(self._h, int(bool(adjoint)), k, Xc.ctypes.data, ldx, Yc.ctypes.data, ldy, float(alpha), float(beta)))
+        if Yc is not Y:
+            Y[...] = Yc
+        return Y
+
+    def set_values(self, nzval):
+        """New nzval (nnz of them, in the stored order of the pattern the operator was made with)."""
+        self._live()
+        v = np.ascontiguousarray(nzval, dtype=np.float64)
+        lib = capi.lib()
+        self.ctx.check(lib.otmb_op_set_values(self._h, v.ctypes.data, len(v)))
+
+    def __matmul__(self, x):
+        return self.mul(x)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            capi.lib().otmb_op_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def as2D(x, wet3D):
     """src/extratools.jl:111-115: scatter a surface vector back onto the (nx,ny) grid, NaN on land."""
     wet = np.asfortranarray(wet3D).astype(bool)

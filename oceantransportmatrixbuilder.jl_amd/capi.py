@@ -102,6 +102,7 @@ SYMBOLS = {
     "otmb_ctx_given_checks": (C.c_int64, [_vp]),
     "otmb_ctx_kept_htab": (C.c_int32, [_vp]),
     "otmb_ctx_kept_t_pattern": (C.c_int32, [_vp]),
+    "otmb_ctx_kept_t_pattern_fills": (C.c_int64, [_vp]),
     "otmb_last_error": (C.c_char_p, [_vp]),
     "otmb_status_string": (C.c_char_p, [C.c_int32]),
     "otmb_version": (C.c_char_p, []),
@@ -167,6 +168,14 @@ SYMBOLS = {
     "otmb_coarsen_fill_dev": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "otmb_coarsen_plan": (C.c_int32, [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _ip]),
     "otmb_coarsen_fetch": (C.c_int32, [_vp, _vp, _vp, _vp]),
+    "otmb_op_create_dev": (C.c_int32, [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "otmb_op_create": (C.c_int32, [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "otmb_op_set_values_dev": (C.c_int32, [_vp, _vp, C.c_int64]),
+    "otmb_op_set_values": (C.c_int32, [_vp, _vp, C.c_int64]),
+    "otmb_op_mul_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double]),
+    "otmb_op_mul": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double]),
+    "otmb_op_info": (C.c_int32, [_vp, _ip, _ip, _ip]),
+    "otmb_op_destroy": (None, [_vp]),
     "otmb_transportmatrix_plan_dev": (C.c_int32, [_vp, C.POINTER(TmArgs), C.POINTER(C.c_int64 * 5)]),
     "otmb_transportmatrix_fill_dev": (C.c_int32, [_vp, C.POINTER(_vp * 5), C.POINTER(_vp * 5), C.POINTER(_vp * 5)]),
     "otmb_transportmatrix_plan": (C.c_int32, [_vp, C.POINTER(TmArgs), C.POINTER(C.c_int64 * 5)]),
@@ -319,6 +328,10 @@ class Context:
     def kept_t_pattern(self):
         """Whether that fill stored T's values only, on the pattern of this context's last write of T (KEPT_T_PATTERN honoured): 1 yes, 0 no, -1 no such fill yet."""
         return int(self._lib.otmb_ctx_kept_t_pattern(self._h))
+
+    def kept_t_pattern_fills(self):
+        """How many fills on this context have stored T's values only so far (changes with every such fill: compare before / after a call)."""
+        return int(self._lib.otmb_ctx_kept_t_pattern_fills(self._h))
 
     def use_own_stream(self):
         self.check(self._lib.otmb_ctx_set_stream(self._h, _vp(0)))

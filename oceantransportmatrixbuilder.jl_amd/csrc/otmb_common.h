@@ -153,6 +153,7 @@ struct otmb_ctx {
     // arrays, and with the TκH table (a change of stream).
     KeptRecord tpat_rec;
     int tpat_used = -1;     // the last fill that kept all three operators stored T's values only (1) or all of T (0); -1: none yet
+    int64_t tpat_fills = 0; // fills that stored T's values only, so far (otmb_ctx_kept_t_pattern_fills)
     DevBuf given_tmp[6];                   // temporaries of the foreign path's sparse adds: two (colptr, rowval, nzval) triples
     CooPlan coo;
     SpPlan sp;

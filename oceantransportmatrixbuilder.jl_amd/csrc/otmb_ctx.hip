@@ -179,6 +179,7 @@ int32_t otmb_ctx_given_state(const otmb_ctx *ctx, int32_t m) { return (ctx && m 
 int64_t otmb_ctx_given_checks(const otmb_ctx *ctx) { return ctx ? (int64_t)ctx->given_checks : -1; }
 int32_t otmb_ctx_kept_htab(const otmb_ctx *ctx) { return ctx ? ctx->htab_used : -1; }
 int32_t otmb_ctx_kept_t_pattern(const otmb_ctx *ctx) { return ctx ? ctx->tpat_used : -1; }
+int64_t otmb_ctx_kept_t_pattern_fills(const otmb_ctx *ctx) { return ctx ? (int64_t)ctx->tpat_fills : -1; }
 
 int32_t otmb_ctx_synchronize(otmb_ctx *ctx) {
     if (!ctx) return OTMB_ERR_INVALID_ARG;

@@ -1,0 +1,530 @@
+// otmb_spmv.hip -- a resident sparse operator: Y = α·A·X + β·Y and Y = α·Aᵀ·X + β·Y on the device (otmb_op_*).
+//
+// Semantics: SparseArrays' 5-argument mul! for Julia 1.10 (the reference's floor), restated as published (no reference test pins them):
+//   * β step first (LinearAlgebra._rmul_or_fill!): β == 0 fills Y with +0.0 (NaN / Inf already in Y are discarded), β == 1 leaves Y,
+//     otherwise Y[i,c] = Y[i,c] * β;
+//   * A·X (_spmatmul!): for each tracer c, for col = 1..n in order, αxj = X[col,c] * α, then Y[rowval[j],c] += nzval[j] * αxj for the
+//     stored j of column col in stored order.  Every Y[i,c] is a left fold from the β step's value over its contributions in STORAGE
+//     order (by column, inside a column by position; duplicate / unsorted rows included);
+//   * Aᵀ·X (_At_or_Ac_mul_B!; real, so the adjoint is the transpose): tmp = +0.0, tmp += nzval[j] * X[rowval[j],c] in stored order,
+//     then Y[col,c] += tmp * α (an empty column adds +0.0 * α).
+// No FMA (the library is built with -ffp-contract=off).  Exactness means ONE sequential fold per output element: parallelism comes from
+// rows, columns and tracers only, and a long row or column is one lane's dependent chain.
+//
+// Layouts, built once per pattern by the plan (otmb_op_create[_dev]); the operator owns every array, no caller array is read afterwards:
+//   CSC copy     colptr (Int64), rowval - 1 as Int32, nzval: what Aᵀ·X reads.  A wave takes 64 columns, whose entries are ONE contiguous
+//                run; it is staged through LDS in chunks by coalesced loads, then every lane folds its own column from LDS.
+//   row slices   the rows of A in groups of 64 (a slice = a wave).  Entry e of the slice's rows lies at sbase[slice] + 64 e + lane, for
+//                values (Float64) and column indices (Int32): the loads of one step e coalesce across the wave.  Each slice is as wide
+//                as its longest short row; a lane stops at its own row's length (padding is skipped, never added).  Inside a row the
+//                entries are in storage order: the plan's stable radix sort of (row, position) is the stable transposition.
+//   long rows    rows longer than SP_ELL_MAX, or longer than 32 and four times their slice's mean, would widen their whole slice: they
+//                are stored contiguously behind the slices and folded by spmv_long_kernel, one workgroup per row (coalesced chunks in
+//                LDS, one lane per tracer).
+//   dst          the position of every stored entry (CSC order) in the two layouts above: "set values" is one streaming scatter.
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include "otmb_common.h"
+
+#define SP_ELL_MAX 256   // longest row a slice takes
+#define SP_TCH 512       // entries per LDS chunk of the Aᵀ and long-row kernels
+#define SP_GRID(n) dim3((unsigned)(((n) + 255) / 256 < 65536 ? (((n) + 255) / 256 > 0 ? ((n) + 255) / 256 : 1) : 65536)), dim3(256), 0, op->ctx->stream
+
+struct otmb_op {
+    otmb_ctx *ctx = nullptr;
+    int device = 0;
+    i64 m = 0, n = 0, nnz = 0;
+    i64 nslices = 0, ell = 0, nlong = 0;  // slices, entries of the slice layout (padding included), long rows
+    DevBuf cp, rv, nz;                    // CSC copy: colptr (n + 1, Int64), rowval - 1 (Int32), nzval
+    DevBuf dst;                           // per stored entry: its position in val / col
+    DevBuf elen, sbase, loff, lrows;      // per row: length or -1 (long); per slice: first position; per row: long-row offset; long rows
+    DevBuf val, col;                      // slices then long rows: values and column indices (Int32, 0-based)
+    DevBuf xs, ys;                        // staging of otmb_op_mul
+};
+
+// ---- device helpers ------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double sp_beta(const double *__restrict__ y, int bmode, double beta) {
+    // LinearAlgebra._rmul_or_fill!: β == 0 -> +0.0 (Y is not read), β == 1 -> Y, otherwise Y * β
+    return bmode == 0 ? 0.0 : (bmode == 1 ? *y : *y * beta);
+}
+
+// ---- plan --------------------------------------------------------------------------------------------------------------------
+enum { SP_BAD_CP = 1, SP_BAD_RV = 2 };
+__global__ __launch_bounds__(256) void spmv_check_colptr_kernel(const i64 *__restrict__ p, i64 n, i64 nnz, unsigned *__restrict__ bad) {
+    for (i64 c = (i64)blockIdx.x * 256 + threadIdx.x; c < n; c += (i64)gridDim.x * 256) {
+        const i64 a = p[c], b = p[c + 1];
+        if (a < 1 || b < a || b > nnz + 1) atomicOr(bad, (unsigned)SP_BAD_CP);
+    }
+}
+// rowval in 1..m; writes rowval - 1 as Int32 (the sort keys and Aᵀ's row stream) and the identity permutation
+__global__ __launch_bounds__(256) void spmv_check_rowval_kernel(const i64 *__restrict__ r, i64 nnz, i64 m, int *__restrict__ rv32, i64 *__restrict__ iota,
+                                                                unsigned *__restrict__ bad) {
+    for (i64 e = (i64)blockIdx.x * 256 + threadIdx.x; e < nnz; e += (i64)gridDim.x * 256) {
+        const i64 i = r[e];
+        if (i < 1 || i > m) atomicOr(bad, (unsigned)SP_BAD_RV);
+        rv32[e] = (int)(i - 1);
+        iota[e] = e;
+    }
+}
+// rowptr[i] = first position p of the sorted keys with key >= i (i = 0..m)
+__global__ __launch_bounds__(256) void spmv_rowptr_kernel(const unsigned *__restrict__ keys, i64 nnz, i64 m, i64 *__restrict__ rowptr) {
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i <= m; i += (i64)gridDim.x * 256) {
+        i64 lo = 0, hi = nnz;
+        while (lo < hi) {
+            const i64 mid = (lo + hi) >> 1;
+            if ((i64)keys[mid] < i) lo = mid + 1; else hi = mid;
+        }
+        rowptr[i] = lo;
+    }
+}
+// one wave per slice: long rows, the slice's width; elen (-1: long), swidth (64 * width), lflag, lent (entries of a long row)
+__global__ __launch_bounds__(256) void spmv_slice_kernel(const i64 *__restrict__ rowptr, i64 m, i64 nslices, int *__restrict__ elen, i64 *__restrict__ swidth,
+                                                         i64 *__restrict__ lflag, i64 *__restrict__ lent) {
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    const i64 s = i >> 6;
+    const int lane = threadIdx.x & 63;
+    if (s > nslices) return;  // (whole waves: s is uniform across a wave)
+    const i64 len = i < m ? rowptr[i + 1] - rowptr[i] : 0;
+    i64 sum = len;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
+    const i64 rows = (s < nslices) ? min((i64)64, m - (s << 6)) : 1;
+    const i64 mean = (sum + rows - 1) / rows;
+    const bool lng = i < m && (len > SP_ELL_MAX || (len > 32 && len > 4 * mean));
+    i64 w = lng ? 0 : len;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) w = max(w, (i64)__shfl_xor(w, d));
+    if (i < m) {
+        elen[i] = lng ? -1 : (int)len;
+        lflag[i] = lng ? 1 : 0;
+        lent[i] = lng ? len : 0;
+    } else if (i == m) {
+        lflag[i] = 0;
+        lent[i] = 0;
+    }
+    if (lane == 0) swidth[s] = s < nslices ? 64 * w : 0;
+}
+// dst[perm[p]]: where the p-th entry in row order lies in the slices / behind them
+__global__ __launch_bounds__(256) void spmv_dst_kernel(const i64 *__restrict__ perm, const unsigned *__restrict__ keys, const i64 *__restrict__ rowptr,
+                                                       const int *__restrict__ elen, const i64 *__restrict__ sbase, const i64 *__restrict__ loff, i64 nnz, i64 ell,
+                                                       i64 *__restrict__ dst) {
+    for (i64 p = (i64)blockIdx.x * 256 + threadIdx.x; p < nnz; p += (i64)gridDim.x * 256) {
+        const i64 i = keys[p], e = p - rowptr[i];
+        dst[perm[p]] = elen[i] >= 0 ? sbase[i >> 6] + 64 * e + (i & 63) : ell + loff[i] + e;
+    }
+}
+__global__ __launch_bounds__(256) void spmv_lrows_kernel(const i64 *__restrict__ lflag, const i64 *__restrict__ lidx, i64 m, i64 *__restrict__ lrows) {
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < m; i += (i64)gridDim.x * 256)
+        if (lflag[i]) lrows[lidx[i]] = i;
+}
+__global__ __launch_bounds__(256) void spmv_colidx_kernel(const i64 *__restrict__ cp, i64 n, const i64 *__restrict__ dst, int *__restrict__ col) {
+    for (i64 c = (i64)blockIdx.x * 256 + threadIdx.x; c < n; c += (i64)gridDim.x * 256)
+        for (i64 j = cp[c] - 1; j < cp[c + 1] - 1; ++j) col[dst[j]] = (int)c;
+}
+// "set values": every stored value to its place in the slices / long rows (a streaming read, a scatter)
+__global__ __launch_bounds__(256) void spmv_relayout_kernel(const double *__restrict__ nz, const i64 *__restrict__ dst, i64 nnz, double *__restrict__ val) {
+    for (i64 j = (i64)blockIdx.x * 256 + threadIdx.x; j < nnz; j += (i64)gridDim.x * 256) val[dst[j]] = nz[j];
+}
+
+// ---- A·X: one lane per row ------------------------------------------------------------------------------------------------------
+template <int KB>
+__global__ __launch_bounds__(256) void spmv_rows_kernel(const double *__restrict__ val, const int *__restrict__ col, const i64 *__restrict__ sbase,
+                                                        const int *__restrict__ elen, i64 m, const double *__restrict__ X, i64 ldx, double *__restrict__ Y,
+                                                        i64 ldy, double alpha, double beta, int bmode) {
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const int len = elen[i];
+    if (len < 0) return;  // a long row: spmv_long_kernel
+    const i64 base = sbase[i >> 6] + (i & 63);
+    double acc[KB];
+#pragma unroll
+    for (int c = 0; c < KB; ++c) acc[c] = sp_beta(Y + i + c * ldy, bmode, beta);
+    for (int e = 0; e < len; ++e) {
+        const double v = val[base + 64 * (i64)e];
+        const i64 j = col[base + 64 * (i64)e];
+#pragma unroll
+        for (int c = 0; c < KB; ++c) {
+            const double axj = X[j + c * ldx] * alpha;
+            acc[c] = acc[c] + v * axj;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < KB; ++c) Y[i + c * ldy] = acc[c];
+}
+
+// one workgroup per long row: the row's entries in coalesced chunks through LDS, lane c folds tracer c (groups of 64 tracers)
+__global__ __launch_bounds__(64) void spmv_long_kernel(const double *__restrict__ val, const int *__restrict__ col, const i64 *__restrict__ lrows,
+                                                       const i64 *__restrict__ loff, i64 ell, int k, const double *__restrict__ X, i64 ldx,
+                                                       double *__restrict__ Y, i64 ldy, double alpha, double beta, int bmode) {
+    __shared__ double sv[SP_TCH];
+    __shared__ int sc[SP_TCH];
+    const int lane = threadIdx.x;
+    const i64 i = lrows[blockIdx.x];
+    const i64 b0 = ell + loff[i], len = loff[i + 1] - loff[i];
+    for (int c0 = 0; c0 < k; c0 += 64) {
+        const int c = c0 + lane;
+        double acc = c < k ? sp_beta(Y + i + c * ldy, bmode, beta) : 0.0;
+        for (i64 lo = 0; lo < len; lo += SP_TCH) {
+            const int w = (int)min((i64)SP_TCH, len - lo);
+            __syncthreads();
+            for (int t = lane; t < w; t += 64) {
+                sv[t] = val[b0 + lo + t];
+                sc[t] = col[b0 + lo + t];
+            }
+            __syncthreads();
+            if (c < k)
+                for (int t = 0; t < w; ++t) {
+                    const double axj = X[(i64)sc[t] + c * ldx] * alpha;
+                    acc = acc + sv[t] * axj;
+                }
+        }
+        if (c < k) Y[i + c * ldy] = acc;
+    }
+}
+
+// ---- Aᵀ·X: one lane per column of A, the wave's contiguous run of entries staged through LDS ---------------------------------------
+template <int KB>
+__global__ __launch_bounds__(64) void spmv_cols_kernel(const i64 *__restrict__ cp, const int *__restrict__ rv, const double *__restrict__ nz, i64 n,
+                                                       const double *__restrict__ X, i64 ldx, double *__restrict__ Y, i64 ldy, double alpha, double beta,
+                                                       int bmode) {
+    __shared__ double sv[SP_TCH];
+    __shared__ int sr[SP_TCH];
+    const int lane = threadIdx.x;
+    const i64 c0 = (i64)blockIdx.x * 64, colm = c0 + lane;
+    const bool has = colm < n;
+    const i64 last = min(c0 + 64, n);
+    const i64 wb = cp[c0] - 1, we = cp[last] - 1;
+    const i64 mb = has ? cp[colm] - 1 : 0, me = has ? cp[colm + 1] - 1 : 0;
+    double tmp[KB];
+#pragma unroll
+    for (int c = 0; c < KB; ++c) tmp[c] = 0.0;
+    for (i64 lo = wb; lo < we; lo += SP_TCH) {
+        const int w = (int)min((i64)SP_TCH, we - lo);
+        __syncthreads();
+        for (int t = lane; t < w; t += 64) {
+            sv[t] = nz[lo + t];
+            sr[t] = rv[lo + t];
+        }
+        __syncthreads();
+        const i64 a = max(mb, lo), b = min(me, lo + w);
+        for (i64 e = a; e < b; ++e) {
+            const double v = sv[e - lo];
+            const i64 r = sr[e - lo];
+#pragma unroll
+            for (int c = 0; c < KB; ++c) tmp[c] = tmp[c] + v * X[r + c * ldx];
+        }
+    }
+    if (has) {
+#pragma unroll
+        for (int c = 0; c < KB; ++c) {
+            const double y0 = sp_beta(Y + colm + c * ldy, bmode, beta);
+            const double t = tmp[c] * alpha;
+            Y[colm + c * ldy] = y0 + t;
+        }
+    }
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------------------
+static int32_t sp_reserve(otmb_op *op, DevBuf &b, size_t bytes) { return otmb_reserve(op->ctx, b, bytes > 0 ? bytes : 8); }
+static void sp_free(DevBuf &b) {
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+}
+static void sp_free_all(otmb_op *op) {
+    for (DevBuf *b : {&op->cp, &op->rv, &op->nz, &op->dst, &op->elen, &op->sbase, &op->loff, &op->lrows, &op->val, &op->col, &op->xs, &op->ys}) sp_free(*b);
+}
+
+static int32_t sp_scan(otmb_op *op, DevBuf &tmpb, const i64 *in, i64 *out, i64 n) {
+    size_t tmp = 0;
+    otmb_ctx *ctx = op->ctx;
+    if (rocprim::exclusive_scan(nullptr, tmp, in, out, (i64)0, (size_t)n, rocprim::plus<i64>(), ctx->stream) != hipSuccess)
+        return otmb_fail(ctx, OTMB_ERR_HIP, "scan (size)");
+    int32_t rc;
+    if ((rc = sp_reserve(op, tmpb, tmp + 16))) return rc;
+    if (rocprim::exclusive_scan(tmpb.p, tmp, in, out, (i64)0, (size_t)n, rocprim::plus<i64>(), ctx->stream) != hipSuccess)
+        return otmb_fail(ctx, OTMB_ERR_HIP, "scan");
+    return OTMB_OK;
+}
+
+static int sp_bits(i64 v) {  // bits v needs: v < 2^bits
+    int b = 1;
+    while (b < 63 && (v >> b) != 0) ++b;
+    return b;
+}
+
+// The plan, on op->cp / a copy of rowval / op->nz already on the device (nnz known): checks, then the layouts.  Scratch is released before
+// returning.
+static int32_t sp_plan(otmb_op *op, const i64 *rowval) {
+    otmb_ctx *ctx = op->ctx;
+    const i64 m = op->m, n = op->n, nnz = op->nnz;
+    int32_t rc;
+    struct Scratch {  // freed on every return (hipFree waits for the kernels that use it)
+        DevBuf flags, iota, keys, perm, rowptr, tmpb, lflag, lent, lidx, swidth;
+        ~Scratch() {
+            for (DevBuf *b : {&flags, &iota, &keys, &perm, &rowptr, &tmpb, &lflag, &lent, &lidx, &swidth}) sp_free(*b);
+        }
+    } S;
+    DevBuf &flags = S.flags, &iota = S.iota, &keys = S.keys, &perm = S.perm, &rowptr = S.rowptr, &tmpb = S.tmpb, &lflag = S.lflag, &lent = S.lent,
+           &lidx = S.lidx, &swidth = S.swidth;
+    auto done = [](int32_t r) { return r; };
+    if ((rc = sp_reserve(op, flags, 16))) return done(rc);
+    if ((rc = sp_reserve(op, op->rv, (size_t)nnz * 4))) return done(rc);
+    if ((rc = sp_reserve(op, iota, (size_t)nnz * 8))) return done(rc);
+    unsigned *bad = (unsigned *)flags.p;
+    HIP_TRY(ctx, hipMemsetAsync(bad, 0, 16, ctx->stream));
+    const i64 *cp = (const i64 *)op->cp.p;
+    if (n > 0) hipLaunchKernelGGL(spmv_check_colptr_kernel, SP_GRID(n), cp, n, nnz, bad);
+    if (nnz > 0) hipLaunchKernelGGL(spmv_check_rowval_kernel, SP_GRID(nnz), rowval, nnz, m, (int *)op->rv.p, (i64 *)iota.p, bad);
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned hb = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&hb, bad, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (hb & SP_BAD_CP) return done(otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "colptr not non-decreasing inside [1, nnz + 1]"));
+    if (hb & SP_BAD_RV) return done(otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "row index outside 1:m"));
+    // stable transposition: radix sort of (row) keys with the storage position as value (LSD radix sort is stable)
+    const i64 ns = (m + 63) / 64;
+    op->nslices = ns;
+    if ((rc = sp_reserve(op, keys, (size_t)nnz * 4))) return done(rc);
+    if ((rc = sp_reserve(op, perm, (size_t)nnz * 8))) return done(rc);
+    if ((rc = sp_reserve(op, rowptr, (size_t)(m + 1) * 8))) return done(rc);
+    unsigned *sk = (unsigned *)keys.p;
+    i64 *pm = (i64 *)perm.p;
+    if (nnz > 0) {
+        size_t tmp = 0;
+        const unsigned bits = (unsigned)sp_bits(m);
+        if (rocprim::radix_sort_pairs(nullptr, tmp, (const unsigned *)op->rv.p, sk, (const i64 *)iota.p, pm, (size_t)nnz, 0, bits, ctx->stream) != hipSuccess)
+            return done(otmb_fail(ctx, OTMB_ERR_HIP, "radix_sort_pairs (size)"));
+        if ((rc = sp_reserve(op, tmpb, tmp + 16))) return done(rc);
+        if (rocprim::radix_sort_pairs(tmpb.p, tmp, (const unsigned *)op->rv.p, sk, (const i64 *)iota.p, pm, (size_t)nnz, 0, bits, ctx->stream) != hipSuccess)
+            return done(otmb_fail(ctx, OTMB_ERR_HIP, "radix_sort_pairs"));
+    }
+    sp_free(iota);
+    i64 *rp = (i64 *)rowptr.p;
+    hipLaunchKernelGGL(spmv_rowptr_kernel, SP_GRID(m + 1), (const unsigned *)sk, nnz, m, rp);
+    // slices and long rows
+    if ((rc = sp_reserve(op, op->elen, (size_t)m * 4))) return done(rc);
+    if ((rc = sp_reserve(op, swidth, (size_t)(ns + 1) * 8))) return done(rc);
+    if ((rc = sp_reserve(op, op->sbase, (size_t)(ns + 1) * 8))) return done(rc);
+    if ((rc = sp_reserve(op, lflag, (size_t)(m + 1) * 8))) return done(rc);
+    if ((rc = sp_reserve(op, lent, (size_t)(m + 1) * 8))) return done(rc);
+    if ((rc = sp_reserve(op, lidx, (size_t)(m + 1) * 8))) return done(rc);
+    if ((rc = sp_reserve(op, op->loff, (size_t)(m + 1) * 8))) return done(rc);
+    i64 *sw = (i64 *)swidth.p, *sb = (i64 *)op->sbase.p, *lf = (i64 *)lflag.p, *le = (i64 *)lent.p, *li = (i64 *)lidx.p, *lo = (i64 *)op->loff.p;
+    int *el = (int *)op->elen.p;
+    {
+        const i64 threads = (ns + 1) * 64;  // every slice and one more wave for the trailing zeros
+        hipLaunchKernelGGL(spmv_slice_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, (const i64 *)rp, m, ns, el, sw, lf, le);
+    }
+    if ((rc = sp_scan(op, tmpb, sw, sb, ns + 1))) return done(rc);
+    if ((rc = sp_scan(op, tmpb, lf, li, m + 1))) return done(rc);
+    if ((rc = sp_scan(op, tmpb, le, lo, m + 1))) return done(rc);
+    HIP_TRY(ctx, hipGetLastError());
+    i64 tot[3] = {0, 0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(&tot[0], sb + ns, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&tot[1], li + m, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&tot[2], lo + m, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    op->ell = tot[0];
+    op->nlong = tot[1];
+    const i64 total = tot[0] + tot[2];
+    if ((rc = sp_reserve(op, op->val, (size_t)total * 8))) return done(rc);
+    if ((rc = sp_reserve(op, op->col, (size_t)total * 4))) return done(rc);
+    if ((rc = sp_reserve(op, op->lrows, (size_t)op->nlong * 8))) return done(rc);
+    if ((rc = sp_reserve(op, op->dst, (size_t)nnz * 8))) return done(rc);
+    i64 *dst = (i64 *)op->dst.p;
+    if (nnz > 0) hipLaunchKernelGGL(spmv_dst_kernel, SP_GRID(nnz), (const i64 *)pm, (const unsigned *)sk, (const i64 *)rp, (const int *)el, (const i64 *)sb,
+                                    (const i64 *)lo, nnz, op->ell, dst);
+    if (op->nlong > 0) hipLaunchKernelGGL(spmv_lrows_kernel, SP_GRID(m), (const i64 *)lf, (const i64 *)li, m, (i64 *)op->lrows.p);
+    if (n > 0 && nnz > 0) hipLaunchKernelGGL(spmv_colidx_kernel, SP_GRID(n), cp, n, (const i64 *)dst, (int *)op->col.p);
+    if (nnz > 0) hipLaunchKernelGGL(spmv_relayout_kernel, SP_GRID(nnz), (const double *)op->nz.p, (const i64 *)dst, nnz, (double *)op->val.p);
+    HIP_TRY(ctx, hipGetLastError());
+    return done(OTMB_OK);
+}
+
+// n + 1 column pointers are on the device at op->cp: read the first and the last, size nnz
+static int32_t sp_ends(otmb_op *op) {
+    otmb_ctx *ctx = op->ctx;
+    i64 e[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(&e[0], op->cp.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&e[1], (const i64 *)op->cp.p + op->n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (e[0] != 1) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "colptr[1] must be 1");
+    if (e[1] < 1) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "colptr[n + 1] - 1 (nnz) is negative");
+    op->nnz = e[1] - 1;
+    return OTMB_OK;
+}
+
+extern "C" void otmb_op_destroy(otmb_op *op);
+
+static int32_t sp_create(otmb_ctx *ctx, int64_t m, int64_t n, const int64_t *colptr, const int64_t *rowval, const double *nzval, otmb_op **out,
+                         hipMemcpyKind kind) {
+    if (!ctx) return OTMB_ERR_INVALID_ARG;
+    if (!out) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (!colptr) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
+    if (m < 0 || n < 0) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "sizes");
+    if (m >= (1ll << 31) || n >= (1ll << 31)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "matrix too large (m and n must be < 2^31)");
+    if (kind == hipMemcpyHostToDevice) {  // the host copy can be checked before anything is uploaded
+        if (colptr[0] != 1) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "colptr[1] must be 1");
+        if (colptr[n] < 1) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "colptr[n + 1] - 1 (nnz) is negative");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    struct Guard {  // the operator is handed out only when the plan succeeded
+        otmb_op *op = new otmb_op();
+        ~Guard() { otmb_op_destroy(op); }
+    } G;
+    otmb_op *op = G.op;
+    op->ctx = ctx;
+    op->device = ctx->device;
+    op->m = m;
+    op->n = n;
+    auto fail = [](int32_t rc) { return rc; };
+    int32_t rc;
+    if ((rc = sp_reserve(op, op->cp, (size_t)(n + 1) * 8))) return fail(rc);
+    HIP_TRY(ctx, hipMemcpyAsync(op->cp.p, colptr, (size_t)(n + 1) * 8, kind, ctx->stream));
+    if ((rc = sp_ends(op))) return fail(rc);
+    const i64 nnz = op->nnz;
+    if (nnz >= (1ll << 40)) return fail(otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "matrix too large"));
+    if (nnz > 0 && (!rowval || !nzval)) return fail(otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument"));
+    struct Rows {  // rowval as given (Int64), for the plan's checks only
+        DevBuf b;
+        ~Rows() { sp_free(b); }
+    } rows;
+    if ((rc = sp_reserve(op, rows.b, (size_t)nnz * 8))) return fail(rc);
+    if ((rc = sp_reserve(op, op->nz, (size_t)nnz * 8))) return fail(rc);
+    if (nnz > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(rows.b.p, rowval, (size_t)nnz * 8, kind, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(op->nz.p, nzval, (size_t)nnz * 8, kind, ctx->stream));
+        if (kind == hipMemcpyHostToDevice) ctx->uploaded_bytes += 16 * nnz + 8 * (n + 1);
+    }
+    if ((rc = sp_plan(op, (const i64 *)rows.b.p))) return fail(rc);
+    *out = op;
+    G.op = nullptr;
+    return OTMB_OK;
+}
+
+static int32_t sp_set_values(otmb_op *op, const double *nzval, int64_t nnz, hipMemcpyKind kind) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    otmb_ctx *ctx = op->ctx;
+    if (nnz != op->nnz) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "set_values: nnz differs from the operator's");
+    if (nnz > 0 && !nzval) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
+    HIP_TRY(ctx, hipSetDevice(op->device));
+    if (nnz == 0) return OTMB_OK;
+    HIP_TRY(ctx, hipMemcpyAsync(op->nz.p, nzval, (size_t)nnz * 8, kind, ctx->stream));
+    if (kind == hipMemcpyHostToDevice) ctx->uploaded_bytes += 8 * nnz;
+    hipLaunchKernelGGL(spmv_relayout_kernel, SP_GRID(nnz), (const double *)op->nz.p, (const i64 *)op->dst.p, nnz, (double *)op->val.p);
+    HIP_TRY(ctx, hipGetLastError());
+    return OTMB_OK;
+}
+
+template <int KB>
+static void sp_launch(otmb_op *op, int adjoint, const double *X, int64_t ldx, double *Y, int64_t ldy, double alpha, double beta, int bmode) {
+    hipStream_t s = op->ctx->stream;
+    if (adjoint) {
+        if (op->n > 0)
+            hipLaunchKernelGGL(spmv_cols_kernel<KB>, dim3((unsigned)((op->n + 63) / 64)), dim3(64), 0, s, (const i64 *)op->cp.p, (const int *)op->rv.p,
+                               (const double *)op->nz.p, op->n, X, ldx, Y, ldy, alpha, beta, bmode);
+    } else if (op->m > 0) {
+        hipLaunchKernelGGL(spmv_rows_kernel<KB>, dim3((unsigned)((op->m + 255) / 256)), dim3(256), 0, s, (const double *)op->val.p, (const int *)op->col.p,
+                           (const i64 *)op->sbase.p, (const int *)op->elen.p, op->m, X, ldx, Y, ldy, alpha, beta, bmode);
+    }
+}
+
+static int32_t sp_check_mul(otmb_op *op, int32_t adjoint, int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy) {
+    otmb_ctx *ctx = op->ctx;
+    const i64 rx = adjoint ? op->m : op->n, ry = adjoint ? op->n : op->m;
+    if (k < 1 || k >= (1ll << 31)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "k (tracers) must be >= 1");
+    if (ldx < rx || ldx < 0) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "ldx is smaller than the rows of X");
+    if (ldy < ry || ldy < 0) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "ldy is smaller than the rows of Y");
+    if ((rx > 0 && !X) || (ry > 0 && !Y)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
+    return OTMB_OK;
+}
+
+extern "C" {
+
+int32_t otmb_op_create_dev(otmb_ctx *ctx, int64_t m, int64_t n, const int64_t *colptr, const int64_t *rowval, const double *nzval, otmb_op **out) {
+    return sp_create(ctx, m, n, colptr, rowval, nzval, out, hipMemcpyDeviceToDevice);
+}
+
+int32_t otmb_op_create(otmb_ctx *ctx, int64_t m, int64_t n, const int64_t *colptr, const int64_t *rowval, const double *nzval, otmb_op **out) {
+    return sp_create(ctx, m, n, colptr, rowval, nzval, out, hipMemcpyHostToDevice);
+}
+
+int32_t otmb_op_set_values_dev(otmb_op *op, const double *nzval, int64_t nnz) { return sp_set_values(op, nzval, nnz, hipMemcpyDeviceToDevice); }
+
+int32_t otmb_op_set_values(otmb_op *op, const double *nzval, int64_t nnz) {
+    const int32_t rc = sp_set_values(op, nzval, nnz, hipMemcpyHostToDevice);
+    if (rc == OTMB_OK && op->nnz > 0) HIP_TRY(op->ctx, hipStreamSynchronize(op->ctx->stream));  // (the caller may reuse its array at once)
+    return rc;
+}
+
+int32_t otmb_op_mul_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy, double alpha, double beta) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    int32_t rc;
+    if ((rc = sp_check_mul(op, adjoint, k, X, ldx, Y, ldy))) return rc;
+    otmb_ctx *ctx = op->ctx;
+    HIP_TRY(ctx, hipSetDevice(op->device));
+    const int bmode = beta == 0.0 ? 0 : (beta == 1.0 ? 1 : 2);
+    for (i64 c0 = 0; c0 < k;) {  // register blocks of tracers: the matrix is read once per block
+        const i64 r = k - c0;
+        const double *Xc = X ? X + c0 * ldx : nullptr;
+        double *Yc = Y ? Y + c0 * ldy : nullptr;
+        if (r >= 8) { sp_launch<8>(op, adjoint, Xc, ldx, Yc, ldy, alpha, beta, bmode); c0 += 8; }
+        else if (r >= 4) { sp_launch<4>(op, adjoint, Xc, ldx, Yc, ldy, alpha, beta, bmode); c0 += 4; }
+        else if (r >= 2) { sp_launch<2>(op, adjoint, Xc, ldx, Yc, ldy, alpha, beta, bmode); c0 += 2; }
+        else { sp_launch<1>(op, adjoint, Xc, ldx, Yc, ldy, alpha, beta, bmode); c0 += 1; }
+    }
+    if (!adjoint && op->nlong > 0)
+        hipLaunchKernelGGL(spmv_long_kernel, dim3((unsigned)op->nlong), dim3(64), 0, ctx->stream, (const double *)op->val.p, (const int *)op->col.p,
+                           (const i64 *)op->lrows.p, (const i64 *)op->loff.p, op->ell, (int)k, X, ldx, Y, ldy, alpha, beta, bmode);
+    HIP_TRY(ctx, hipGetLastError());
+    return OTMB_OK;
+}
+
+int32_t otmb_op_mul(otmb_op *op, int32_t adjoint, int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy, double alpha, double beta) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    int32_t rc;
+    if ((rc = sp_check_mul(op, adjoint, k, X, ldx, Y, ldy))) return rc;
+    otmb_ctx *ctx = op->ctx;
+    HIP_TRY(ctx, hipSetDevice(op->device));
+    const i64 rx = adjoint ? op->m : op->n, ry = adjoint ? op->n : op->m;
+    // staged compactly (leading dimension = rows); the caller's padding rows are neither read nor written
+    if ((rc = sp_reserve(op, op->xs, (size_t)(rx * k) * 8))) return rc;
+    if ((rc = sp_reserve(op, op->ys, (size_t)(ry * k) * 8))) return rc;
+    double *dx = (double *)op->xs.p, *dy = (double *)op->ys.p;
+    if (rx > 0) {
+        HIP_TRY(ctx, hipMemcpy2DAsync(dx, (size_t)rx * 8, X, (size_t)ldx * 8, (size_t)rx * 8, (size_t)k, hipMemcpyHostToDevice, ctx->stream));
+        ctx->uploaded_bytes += 8 * rx * k;
+    }
+    if (ry > 0 && beta != 0.0) {  // (β == 0 discards Y)
+        HIP_TRY(ctx, hipMemcpy2DAsync(dy, (size_t)ry * 8, Y, (size_t)ldy * 8, (size_t)ry * 8, (size_t)k, hipMemcpyHostToDevice, ctx->stream));
+        ctx->uploaded_bytes += 8 * ry * k;
+    }
+    if ((rc = otmb_op_mul_dev(op, adjoint, k, dx, rx, dy, ry, alpha, beta))) return rc;
+    if (ry > 0) HIP_TRY(ctx, hipMemcpy2DAsync(Y, (size_t)ldy * 8, dy, (size_t)ry * 8, (size_t)ry * 8, (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return OTMB_OK;
+}
+
+int32_t otmb_op_info(const otmb_op *op, int64_t *m, int64_t *n, int64_t *nnz) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    if (m) *m = op->m;
+    if (n) *n = op->n;
+    if (nnz) *nnz = op->nnz;
+    return OTMB_OK;
+}
+
+// touches no context (a finalizer may call it after the context is gone): the operator's own device buffers only
+void otmb_op_destroy(otmb_op *op) {
+    if (!op) return;
+    (void)hipSetDevice(op->device);
+    (void)hipDeviceSynchronize();
+    sp_free_all(op);
+    delete op;
+}
+
+}  // extern "C"

@@ -1151,6 +1151,7 @@ static bool tpat_take(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl, co
     if (pl.kept != KEPT_OPS || p.skip != KEPT_OPS || p.hcp || p.dcp) return false;  // (not a kept fill: kept_htab's test)
     const bool t = allowed && env_on && p.htab && (((unsigned)a.kept_ops & OTMB_KEPT_T_PATTERN) != 0) && tpat_matches(ctx, a, pl, p.colptr[0], p.rowval[0]);
     ctx->tpat_used = t ? 1 : 0;
+    if (t) ctx->tpat_fills += 1;
     return t;
 }
 // A fill that did not take the record: it wrote T's full pattern into colptrT / rowvalT (the record's new writer: the asynchronous step `serial`,

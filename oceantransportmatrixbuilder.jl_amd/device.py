@@ -23,6 +23,99 @@ def _flat(a, dtype=np.float64):
     return np.asfortranarray(a, dtype=dtype).ravel(order="F")
 
 
+def _col_major(t, rows):
+    """(tensor, leading dimension) of a 1-D or 2-D float64 device tensor with unit row stride (a column-major matrix, or a row slice of
+    one); anything else is copied into that layout."""
+    if t.dtype != torch.float64:
+        raise ValueError("float64 tensors are required")
+    if t.dim() == 1:
+        t = t if t.stride(0) == 1 else t.contiguous()
+        return t, max(rows, 1)
+    if t.stride(0) != 1 or (t.shape[1] > 1 and t.stride(1) < rows):
+        t = t.t().contiguous().t()
+    return t, max(t.stride(1) if t.shape[1] > 1 else rows, rows, 1)
+
+
+def _on_device(t, device, what):
+    """A host tensor's pointer handed to a kernel would fault the device: refuse anything that is not on the operator's GPU."""
+    if not torch.is_tensor(t) or not t.is_cuda or t.device.index != device:
+        where = t.device if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"{what} must be a tensor on cuda:{device} (got {where})")
+
+
+class Operator:
+    """A resident sparse operator over device CSC arrays (otmb_op_create_dev): Y = α·A·X + β·Y and α·Aᵀ·X + β·Y on torch tensors, bit for
+    bit SparseArrays' 5-argument mul! (api.DeviceOperator states the contract).  The operator owns device copies of the matrix;
+    set_values_dev refreshes the values for the same pattern.  DeviceAssembler.operator() hands these out over its resident results."""
+
+    def __init__(self, ctx, m, n, colptr, rowval, nzval):
+        self.ctx, self.lib = ctx, capi.lib()
+        self._h = C.c_void_p()
+        self.device = int(ctx.device)
+        for t, what in ((colptr, "colptr"), (rowval, "rowval"), (nzval, "nzval")):
+            _on_device(t, self.device, what)
+        self.ctx.check(self.lib.otmb_op_create_dev(self.ctx.handle, int(m), int(n), colptr.data_ptr(), rowval.data_ptr(), nzval.data_ptr(),
+                                                   C.byref(self._h)))
+        mm, nn, z = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self.ctx.check(self.lib.otmb_op_info(self._h, C.byref(mm), C.byref(nn), C.byref(z)))
+        self.shape, self.nnz = (int(mm.value), int(nn.value)), int(z.value)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def set_values_dev(self, nzval):
+        _on_device(nzval, self.device, "nzval")
+        if nzval.dtype != torch.float64 or not nzval.is_contiguous() or nzval.numel() < self.nnz:
+            raise ValueError(f"nzval: a contiguous float64 tensor of at least {self.nnz} entries is required")
+        self.ctx.check(self.lib.otmb_op_set_values_dev(self._h, nzval.data_ptr(), self.nnz))
+
+    def mul(self, X, *, alpha=1.0, beta=0.0, Y=None, adjoint=False):
+        """X: 1-D or 2-D (rows x k, column-major) float64 device tensor; Y: None (a new tensor; β must be 0) or a tensor of the result's
+        shape, updated in place.  Enqueued on the context's stream; nothing travels to the host."""
+        if not self._h.value:
+            raise ValueError("operator is closed")
+        _on_device(X, self.device, "X")
+        if Y is not None:
+            _on_device(Y, self.device, "Y")
+        m, n = self.shape
+        rx, ry = (m, n) if adjoint else (n, m)
+        if X.dim() not in (1, 2) or X.shape[0] != rx:
+            raise capi.OtmbError(11, f"DimensionMismatch: {'Aᵀ' if adjoint else 'A'} of {(ry, rx)} times X of {tuple(X.shape)}")
+        k = 1 if X.dim() == 1 else X.shape[1]
+        oshape = (ry,) if X.dim() == 1 else (ry, k)
+        if Y is None:
+            if beta != 0:
+                raise ValueError("beta != 0 needs Y")
+            Y = torch.empty(ry, dtype=torch.float64, device=X.device) if X.dim() == 1 else \
+                torch.empty_strided((ry, k), (1, max(ry, 1)), dtype=torch.float64, device=X.device)
+        if tuple(Y.shape) != oshape:
+            raise capi.OtmbError(11, f"DimensionMismatch: Y of {tuple(Y.shape)}, expected {oshape}")
+        Xc, ldx = _col_major(X, rx)
+        Yc, ldy = _col_major(Y, ry)
+        self.ctx.check(self.lib.otmb_op_mul_dev(self._h, int(bool(adjoint)), k, Xc.data_ptr(), ldx, Yc.data_ptr(), ldy, float(alpha), float(beta)))
+        if Yc.data_ptr() != Y.data_ptr():
+            Y.copy_(Yc)
+        return Y
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.lib.otmb_op_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DeviceAssembler:
     """Holds one grid (gridmetrics + indices + parameters) in HBM and assembles transport matrices
     for successive (umo, vmo) fields -- the TMIP workflow of building T for many time slices."""
@@ -414,6 +507,8 @@ class DeviceAssembler:
         self._kept_last = ()
         self._tpat = None
         self._tpat_last = False
+        for rec in getattr(self, "_ops", {}).values():  # (and no operator's pattern can be vouched for any more)
+            rec["ok"] = False
 
     # T's pattern (OTMB_KEPT_T_PATTERN) is a function of the wet mask and the topology alone: when T's colptr / rowval tensors are the ones the
     # library last wrote, untouched by torch since, a step that keeps the three operators adds the bit and the fill stores T's values only (the
@@ -439,6 +534,7 @@ class DeviceAssembler:
         """kept_ops for a call into `out`, and the names it covers."""
         self._kept_last = ()
         self._tpat_last = False
+        self._tpat_fills0 = self.ctx.kept_t_pattern_fills()  # (what the library did with the promise: _ops_written compares)
         rec = getattr(self, "_kept", None)
         if rec is None or getattr(self, "given", None) or getattr(self, "only_T", False):
             return 0, ()
@@ -454,6 +550,65 @@ class DeviceAssembler:
         off = getattr(self, "given", None) or getattr(self, "only_T", False) or os.environ.get("OTMB_KEPT", "1") == "0"  # (OTMB_KEPT=0: A/B)
         self._kept = None if off else self._kept_key(out)
         self._tpat = None if off else self._tpat_key(out)  # (T's pattern: written by this call, or where the last one left it)
+        self._ops_written(out, kept)
+
+    # ---- resident operators (otmb_op_*): one per output matrix, re-planned unless its pattern is shown unchanged ----------------------------
+    def _ops_written(self, out, kept):
+        """A call into `out` was accepted: the values of its matrices changed; an operator over one of them keeps its plan only if this call
+        left the pattern where it was -- T: stored its values only (the KEPT_T_PATTERN promise made, and THIS fill took it: the library's count
+        of values-only fills, otmb_ctx_kept_t_pattern_fills, went up by one since the call's _kept_ops -- otmb_ctx_kept_t_pattern alone would
+        still hold an older fill's answer when the library declined the kept operators); TκH / TκVML / TκVdeep: kept; Tadv never.  (An exact
+        cancellation compacts T when the step is folded: operator() compares nnz as well.)"""
+        self._op_last_out = out
+        ops = getattr(self, "_ops", None)
+        if not ops:
+            return
+        f0 = getattr(self, "_tpat_fills0", None)
+        tpat = bool(getattr(self, "_tpat_last", False)) and f0 is not None and self.ctx.kept_t_pattern_fills() == f0 + 1
+        for name, rec in ops.items():
+            if not all(r() is t for r, t in zip(rec["refs"], out[name])):
+                continue  # another output set: untouched
+            rec["dirty"] = True
+            if name == "T":
+                rec["ok"] = rec["ok"] and tpat
+            else:
+                rec["ok"] = rec["ok"] and name in kept
+
+    def operator(self, matrix="T"):
+        """The resident operator over the result `matrix` of this assembler's output set (otmb_op_create_dev), for mul() on device
+        tensors.  Planned again unless every call since the plan left the pattern in place (see _ops_written) and nnz, the tensors and
+        their torch versions are those of the plan; otherwise, when only values can have changed, otmb_op_set_values_dev.  Pending
+        asynchronous steps are folded first (finish()).  The assembler owns the operator: it is replaced, not updated, by a re-plan."""
+        if getattr(self, "_tm_seq", None):
+            self.finish()
+        if self.out is None:
+            raise ValueError("no resident result: run a step first")
+        k = MATS.index(matrix)
+        cp, rv, nz = self.out[matrix]
+        if not hasattr(self, "_ops"):
+            self._ops = {}
+        rec = self._ops.get(matrix)
+        nnz_now = self.nnz[k] if getattr(self, "_op_last_out", None) is self.out else None
+        key = ((cp.data_ptr(), cp._version), (rv.data_ptr(), rv._version))
+        if (rec is not None and rec["ok"] and rec["op"].handle.value and all(r() is t for r, t in zip(rec["refs"], (cp, rv, nz)))
+                and rec["key"] == key and nnz_now is not None and rec["op"].nnz == nnz_now):
+            if rec["dirty"] or rec["nzv"] != (nz.data_ptr(), nz._version):
+                rec["op"].set_values_dev(nz)
+                rec["dirty"], rec["nzv"] = False, (nz.data_ptr(), nz._version)
+            self.op_reuses = getattr(self, "op_reuses", 0) + 1
+            return rec["op"]
+        if rec is not None:
+            rec["op"].close()
+        op = Operator(self.ctx, self.N, self.N, cp, rv, nz)
+        self._ops[matrix] = {"op": op, "refs": [weakref.ref(t) for t in (cp, rv, nz)], "key": key, "nzv": (nz.data_ptr(), nz._version),
+                             "ok": True, "dirty": False}
+        self.op_replans = getattr(self, "op_replans", 0) + 1
+        return op
+
+    def mul(self, matrix, X, *, alpha=1.0, beta=0.0, Y=None, adjoint=False):
+        """Y = α·M·X + β·Y (adjoint: α·Mᵀ·X + β·Y) with M the resident result `matrix`, on torch device tensors (1-D, or rows x k
+        column-major), bit for bit SparseArrays' mul!; no host round trip (besides folding pending asynchronous steps)."""
+        return self.operator(matrix).mul(X, alpha=alpha, beta=beta, Y=Y, adjoint=adjoint)
 
     def _kept_steady(self):
         """The operators a step of this loop does not store: those the last call kept, or -- after a full write that left the promise live -- those
