@@ -19,7 +19,7 @@ struct DevBuf {
     size_t cap = 0;
 };
 
-struct TmPlan;  // otmb_transportmatrix.hip
+struct TmPlan;  // otmb_tm.h
 struct OtmbXfer;  // otmb_xfer.h: pinned staging ring + host copy threads of the host-pointer entry points
 
 // pending plan of the general path (otmb_coo.hip): COO generator and sparse()
@@ -140,7 +140,7 @@ struct otmb_ctx {
     // every later step that kept m (fold_pending)
     int64_t kept_fold_nnz[5] = {0, 0, 0, 0, 0};
     int32_t kept_fold_status[5] = {0, 0, 0, 0, 0};
-    // ... and the TκH table of the steps that keep all three operators (otmb_transportmatrix.hip, kept_htab): five doubles per owned wet column and
+    // ... and the TκH table of the steps that keep all three operators (otmb_tm_kept.hip, kept_htab): five doubles per owned wet column and
     // a NaN word, built for the arguments in htab_key; dropped by every call that does not keep TκH (kept_drop) and by a change of stream
     DevBuf htab;
     bool htab_valid = false;
@@ -233,13 +233,8 @@ int32_t otmb_launch_push_mask(otmb_ctx *ctx, const double *const phi[6], const i
 int32_t otmb_facefluxes_top_counts(otmb_ctx *ctx, const void *umo, const void *vmo, int32_t src_is_f32, const uint8_t *wetflags, double fill,
                                    int64_t nx, int64_t ny, int64_t nz, int32_t topology, double *const phi[6], uint16_t *token,
                                    const otmb_ff_counts *counts);  // otmb_facefluxes.hip (the fused step)
-void otmb_tm_plan_free(otmb_ctx *ctx);                               // otmb_transportmatrix.hip
-void otmb_tm_plan_invalidate(otmb_ctx *ctx);                         // otmb_transportmatrix.hip
 void otmb_xfer_free(otmb_ctx *ctx);                                  // otmb_host.hip
 bool otmb_host_is_pinned(const otmb_ctx *ctx, const void *p, size_t bytes);  // otmb_host.hip: inside a block of otmb_host_alloc
-int32_t otmb_tm_plan_query(otmb_ctx *ctx, int64_t *nnz, int64_t *N);  // otmb_transportmatrix.hip
-bool otmb_tm_plan_foreign(otmb_ctx *ctx);                             // otmb_transportmatrix.hip: T of the last plan came out of the sparse adds
-unsigned otmb_tm_plan_skip(otmb_ctx *ctx);                            // otmb_transportmatrix.hip: matrices (bit m) the pending plan does not hand out
 
 #define HIP_TRY(ctx, call)                                                              \
     do {                                                                                \

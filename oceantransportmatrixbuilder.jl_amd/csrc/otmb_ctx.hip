@@ -2,6 +2,7 @@
 #include <cstdlib>
 
 #include "otmb_common.h"
+#include "otmb_tm.h"
 
 int32_t otmb_fail(otmb_ctx *ctx, int32_t status, const char *detail) {
     if (ctx) {
@@ -134,20 +135,12 @@ void otmb_ctx_destroy(otmb_ctx *ctx) {
     delete ctx;
 }
 
-// A change of stream: the next kept step rebuilds the TκH table in place on the new stream.  Fills enqueued on the old one may still read
-// it (its NaN word is zeroed before the rebuild), so they finish first.
-static void drop_htab(otmb_ctx *ctx) {
-    if (ctx->htab_valid) (void)hipStreamSynchronize(ctx->stream);
-    ctx->htab_valid = false;
-    ctx->tpat_rec.valid = false;  // (T's values-only fills ride on the table's path)
-}
-
 int32_t otmb_ctx_set_stream(otmb_ctx *ctx, void *s) {
     if (!ctx) return OTMB_ERR_INVALID_ARG;
     hipStream_t ns = s ? (hipStream_t)s : ctx->own_stream;
     if (ns != ctx->stream) {  // the cached tile order and TκH table may still be in flight on the previous stream: build them again here
         ctx->order_key = otmb_ctx::OrderKey();
-        drop_htab(ctx);
+        otmb_tm_kept_stream_changed(ctx);
     }
     ctx->stream = ns;
     return OTMB_OK;
@@ -157,7 +150,7 @@ int32_t otmb_ctx_use_default_stream(otmb_ctx *ctx) {
     if (!ctx) return OTMB_ERR_INVALID_ARG;
     if (ctx->stream != nullptr) {
         ctx->order_key = otmb_ctx::OrderKey();
-        drop_htab(ctx);
+        otmb_tm_kept_stream_changed(ctx);
     }
     ctx->stream = nullptr;  // HIP's null stream: what torch calls its default stream
     return OTMB_OK;

@@ -7,6 +7,7 @@
 #include <thread>
 
 #include "otmb_common.h"
+#include "otmb_tm.h"
 #include "otmb_xfer.h"
 
 // staging slots

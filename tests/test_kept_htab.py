@@ -1,4 +1,4 @@
-"""The kept operators' TκH table (csrc/otmb_transportmatrix.hip, kept_htab): a step that keeps TκH, TκVML and TκVdeep takes TκH's values for T
+"""The kept operators' TκH table (csrc/otmb_tm_kept.hip, kept_htab): a step that keeps TκH, TκVML and TκVdeep takes TκH's values for T
 from a table the context builds once per grid instead of re-deriving them.  Every output array must be bit for bit what the same steps write with
 the table switched off (OTMB_KEPT_HTAB=0, a child process: the switch is read once per process) and what a full build writes; every way the table
 can go stale must lead to a rebuild; a NaN it holds must fail every step as before (run with -m gpu)."""

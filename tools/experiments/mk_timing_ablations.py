@@ -101,14 +101,14 @@ edit(os.path.join(TMP, 'otmb_transportmatrix.hip'),[
 ("""            for (unsigned base = 0; base < end; base += 128) {  // full pairs
                 const unsigned u = base + 2 * lane;
                 if (u + 1 < end) {
-                    TM_STORE(*(const i64x2 *)(my_row + u), (i64x2g *)(rvb + u * 8u));
+                    if (!vonly) TM_STORE(*(const i64x2 *)(my_row + u), (i64x2g *)(rvb + u * 8u));
                     TM_STORE(*(const i64x2 *)(my_val + u), (i64x2g *)(nzb + u * 8u));
                 }
             }
 ""","""#ifdef OTMB_STORE_SPLIT  // experiment (profiles/r05): all rowval pieces of the run, then all nzval pieces -- one output stream per burst
             for (unsigned base = 0; base < end; base += 128) {
                 const unsigned u = base + 2 * lane;
-                if (u + 1 < end) TM_STORE(*(const i64x2 *)(my_row + u), (i64x2g *)(rvb + u * 8u));
+                if (u + 1 < end && !vonly) TM_STORE(*(const i64x2 *)(my_row + u), (i64x2g *)(rvb + u * 8u));
             }
             for (unsigned base = 0; base < end; base += 128) {
                 const unsigned u = base + 2 * lane;
@@ -118,7 +118,7 @@ edit(os.path.join(TMP, 'otmb_transportmatrix.hip'),[
             for (unsigned base = 0; base < end; base += 128) {  // full pairs
                 const unsigned u = base + 2 * lane;
                 if (u + 1 < end) {
-                    TM_STORE(*(const i64x2 *)(my_row + u), (i64x2g *)(rvb + u * 8u));
+                    if (!vonly) TM_STORE(*(const i64x2 *)(my_row + u), (i64x2g *)(rvb + u * 8u));
                     TM_STORE(*(const i64x2 *)(my_val + u), (i64x2g *)(nzb + u * 8u));
                 }
             }
