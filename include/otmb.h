@@ -48,8 +48,10 @@ typedef enum {
     OTMB_ERR_CAPACITY = 14,
     OTMB_ERR_PUSH_MASK = 15,       /* args.push_mask does not describe args.phi / args.lwet3d (nothing was written) */
     OTMB_ERR_ASYMMETRIC_PATTERN = 16, /* lump_and_spray: Graphs.SimpleGraph's ArgumentError for a one-directional T pattern */
-    OTMB_ERR_GIVEN_FOREIGN = 17    /* otmb_tm_args.given: an operator that is NOT what this library derives for these arguments was handed to an
+    OTMB_ERR_GIVEN_FOREIGN = 17,   /* otmb_tm_args.given: an operator that is NOT what this library derives for these arguments was handed to an
                                     * entry point that cannot add it (the asynchronous and the multi-slab builds): use otmb_transportmatrix_plan[_dev] */
+    OTMB_ERR_SINGULAR_PRECONDITIONER = 18, /* otmb_op_solve: an entry of diag(σ·I + diag(d) + A) is zero or not finite (the message names the first) */
+    OTMB_ERR_NOT_CONVERGED = 19    /* otmb_op_solve: some column stopped for another reason than convergence (reason[], relres[], iters[] say which) */
 } otmb_status;
 
 /* gridmetrics.gridtopology (src/gridtopology.jl:1-16) */
@@ -659,6 +661,35 @@ int32_t otmb_op_mul_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *X
 int32_t otmb_op_mul(otmb_op *op, int32_t adjoint, int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy, double alpha, double beta);
 int32_t otmb_op_info(const otmb_op *op, int64_t *m, int64_t *n, int64_t *nnz);
 void otmb_op_destroy(otmb_op *op);
+
+/* ---- M·X = B on the device with M = σ·I + diag(d) + A (adjoint: σ·I + diag(d) + Aᵀ), A the operator's matrix (square, otherwise
+ *      OTMB_ERR_INVALID_ARG): the `\` of the reference's ideal-age problem, Γ_c = (T_c + M_c) \ (LUMP * ones(N)) (test/local_full.jl:151-188),
+ *      a steady state, or an implicit time step (I/δt + T)·x⁺ = x/δt + s.  The operator is not modified: otmb_op_set_values then another solve
+ *      is the time loop.
+ *      Method: BiCGStab, right-preconditioned with P = diag(M) (Jacobi); diag(M)[i] = σ + d[i] plus the stored entries (i, i) of A in storage
+ *      order.  An entry that is zero or not finite: OTMB_ERR_SINGULAR_PRECONDITIONER before anything is iterated or written, the message names
+ *      the first such index.  d: n values or NULL (zero).  B, X: column-major n x k with leading dimensions ldb, ldx >= n (rows beyond n are
+ *      neither read nor written).  use_x0 = 0: X is not read, the start is zero.  rtol > 0, maxiter >= 0.
+ *      The k columns advance together, each with its own scalars; a column that has stopped is frozen.  Every sum is taken in a fixed order
+ *      that depends on n alone (no floating-point atomics): the same call gives the same bits, and column c of a k-column solve has the bits
+ *      of that column solved alone.
+ *      Stopping, per column: when the recursive residual reaches ‖r‖₂ <= rtol·‖b‖₂ the true residual b - M·x is computed; the column stops as
+ *      converged when that passes and otherwise goes on from the true residual with r̂ = r.  So it does when ρ = r̂·r is no more than the
+ *      rounding error of its own sum (|ρ| <= 2^-52·‖r̂‖₂·‖r‖₂, zero included): with B = 1 and a mass-conserving A, the first r̂ is a left
+ *      eigenvector of M and ρ is noise.  b = 0: x = 0, zero iterations, converged.  Otherwise it stops with OTMB_SOLVE_MAXITER (maxiter
+ *      iterations done), OTMB_SOLVE_BREAKDOWN (r̂·v, t·t or ω is zero) or OTMB_SOLVE_NONFINITE (a scalar is NaN or Inf: NaN in B, for
+ *      instance); X then holds the LAST iterate (not the best one).
+ *      iters[k], relres[k], reason[k] (HOST arrays in both variants; the call waits for the device): completed iterations, the residual
+ *      ratio ‖r‖₂/‖b‖₂ of the column's last residual evaluation -- the explicitly computed b - M·x when the column stopped on one (every
+ *      converged column, a start that already passes, maxiter reached on a failed check), the recursive one otherwise -- and an
+ *      otmb_solve_reason.  They are filled whenever the call returns OTMB_OK or OTMB_ERR_NOT_CONVERGED; the latter when any column's reason is
+ *      not OTMB_SOLVE_CONVERGED (X and the three arrays are valid: not converged is an answer, not a failure of the call).
+ * otmb_op_solve_dev: d, B, X device pointers, on the context's stream.  otmb_op_solve: host pointers, staged like otmb_op_mul.      */
+typedef enum { OTMB_SOLVE_CONVERGED = 0, OTMB_SOLVE_MAXITER = 1, OTMB_SOLVE_BREAKDOWN = 2, OTMB_SOLVE_NONFINITE = 3 } otmb_solve_reason;
+int32_t otmb_op_solve_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X,
+                          int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason);
+int32_t otmb_op_solve(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X, int64_t ldx,
+                      int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason);
 
 #ifdef __cplusplus
 }

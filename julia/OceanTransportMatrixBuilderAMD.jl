@@ -11,6 +11,7 @@
 #   lump_and_spray              src/extratools.jl:38-119
 #   coarsen                     LUMP * T * SPRAY (src/extratools.jl:14-16)
 #   DeviceOperator, setvalues!  T * x, T' * v, mul!(Y, T, X, α, β) on the GPU (test/local_full.jl:96-107; README: ∂x/∂t + T x = …)
+#   solve!, solve               (σ·I + Diagonal(d) + T) \ B on the GPU: the `\` of the ideal-age problem (test/local_full.jl:151-188)
 #   bolus_GM_velocity           src/RediGM.jl:46-79 (unexported and experimental there, unexported here)
 #   makegridmetrics             src/gridcellgeometry.jl:265-311: the reference's own by default (its haversines are Julia's libm);
 #                               `makegridmetrics(...; gpu = true)` opts into the library's array work (distances within 1e-12)
@@ -32,6 +33,7 @@ import OceanTransportMatrixBuilder as OTMB
 export makegridmetrics, velocity2fluxes, fluxes2velocity, facefluxesfromvelocities
 export makeindices, facefluxesfrommasstransport, facefluxes, transportmatrix, lump_and_spray, coarsen
 export DeviceOperator, setvalues!
+export solve!, solve
 
 const LIBPATH = get(ENV, "OTMB_HIP_LIB", joinpath(@__DIR__, "..", "oceantransportmatrixbuilder.jl_amd", "lib", "libotmb_hip.so"))
 const lib = Ref{Ptr{Cvoid}}(C_NULL)
@@ -356,6 +358,41 @@ function setvalues!(D::DeviceOperator, nzval::Vector{Float64})
     end
     return D
 end
+
+# (σ·I + Diagonal(d) + A) \ B on the resident operator (otmb_op_solve: Jacobi-preconditioned BiCGStab on the device; include/otmb.h states
+# the method, the stop rules and what is deterministic) -- `D'` solves with Aᵀ.  X holds the start when `x0 = true` and the solution
+# afterwards.  Returns (X, info): info.iterations, info.relres, info.reason (:converged, :maxiter, :breakdown, :nonfinite) and
+# info.converged, one entry per column of B.  A column that does not converge is REPORTED, not thrown (status 19): X then holds its last
+# iterate.  Argument errors throw ArgumentError; a zero or non-finite entry of the diagonal throws an ErrorException that names it.
+const SOLVE_REASONS = (:converged, :maxiter, :breakdown, :nonfinite)   # otmb_solve_reason
+function solve!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, B::StridedVecOrMat{Float64};
+                d::Union{Nothing,Vector{Float64}} = nothing, σ::Real = 0.0, rtol::Real = 1e-10, maxiter::Integer = 10000, x0::Bool = false)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    n = op.n
+    (size(B, 1) == n && size(X, 1) == n && size(X, 2) == size(B, 2)) || throw(DimensionMismatch("operator of $((op.m, op.n)), B $(size(B)), X $(size(X))"))
+    (d === nothing || length(d) == n) || throw(DimensionMismatch("d has $(length(d)) values, expected $n"))
+    (stride(X, 1) == 1 && stride(B, 1) == 1) || throw(ArgumentError("X and B need contiguous columns"))
+    k = size(B, 2)
+    ldb = B isa AbstractVector || k <= 1 ? max(n, 1) : stride(B, 2)
+    ldx = X isa AbstractVector || k <= 1 ? max(n, 1) : stride(X, 2)
+    iters = zeros(Int64, k)
+    relres = zeros(Float64, k)
+    reason = zeros(Int32, k)
+    lock(CALL_LOCK) do
+        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        solve_fn = sym(:otmb_op_solve)
+        rc = ccall(solve_fn, Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Float64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int32, Float64, Int64,
+                Ptr{Int64}, Ptr{Float64}, Ptr{Int32}),
+            op.handle, Int32(adjoint), k, d === nothing ? C_NULL : d, Float64(σ), B, ldb, X, ldx, Int32(x0), Float64(rtol), Int64(maxiter),
+            iters, relres, reason)
+        rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which column stopped why
+    end
+    why = [SOLVE_REASONS[r + 1] for r in reason]
+    return X, (iterations = iters, relres = relres, reason = why, converged = why .== :converged)
+end
+solve(D::Union{DeviceOperator,AdjointDeviceOperator}, B::StridedVecOrMat{Float64}; kwargs...) =
+    solve!(B isa AbstractVector ? zeros(Float64, size(B, 1)) : zeros(Float64, size(B, 1), size(B, 2)), D, B; kwargs...)
 
 const HDIRS = (:west, :east, :south, :north)      # OTMB_DIR_*
 f64(a) = Array{Float64}(replace(a, missing => NaN))

@@ -802,6 +802,22 @@ def _column_major(a):
     return a, max(ld, a.shape[0])
 
 
+class SolveInfo:
+    """What otmb_op_solve reports, one entry per column of B: iterations (completed), relres (‖r‖₂/‖b‖₂ of the column's last residual
+    evaluation: the explicitly computed b - M·x when it stopped on one, the recursive residual otherwise), reason ("converged", "maxiter",
+    "breakdown", "nonfinite") and converged; status is the call's own (0, or capi.NOT_CONVERGED when some column is not converged)."""
+
+    def __init__(self, status, iterations, relres, reason):
+        self.status = int(status)
+        self.iterations = np.asarray(iterations, dtype=np.int64)
+        self.relres = np.asarray(relres, dtype=np.float64)
+        self.reason = tuple(capi.SOLVE_REASONS[int(r)] for r in reason)
+        self.converged = np.array([r == "converged" for r in self.reason], dtype=bool)
+
+    def __repr__(self):
+        return f"SolveInfo(status={self.status}, iterations={self.iterations.tolist()}, relres={self.relres.tolist()}, reason={self.reason})"
+
+
 class DeviceOperator:
     """A sparse operator resident on the device: Y = α·A·X + β·Y and Y = α·Aᵀ·X + β·Y, bit for bit SparseArrays' 5-argument mul! of
     Julia 1.10 -- what the reference's consumer checks compute (test/local_full.jl:96-107: norm(T * e1), norm(T' * v)) and what a tracer
@@ -813,8 +829,8 @@ class DeviceOperator:
       * Aᵀ·X (_At_or_Ac_mul_B!): tmp = +0.0, tmp += nzval[j] * X[rowval[j],c] in stored order, then Y[col,c] += tmp * α;
       * no FMA; `A * x` and `A' * v` are α = 1.0, β = 0.0.
     A: a SparseMatrixCSC (1-based).  The operator owns device copies of A: the arrays may change or go once the constructor returns.
-    The same C calls as the Julia shim's DeviceOperator: otmb_op_create; mul! -> otmb_op_mul; setvalues! -> otmb_op_set_values; the
-    finalizer -> otmb_op_destroy."""
+    The same C calls as the Julia shim's DeviceOperator: otmb_op_create; mul! -> otmb_op_mul; setvalues! -> otmb_op_set_values; solve! ->
+    otmb_op_solve; the finalizer -> otmb_op_destroy."""
 
     def __init__(self, A, *, device=0):
         self._h = C.c_void_p()
@@ -866,6 +882,38 @@ class DeviceOperator:
         v = np.ascontiguousarray(nzval, dtype=np.float64)
         lib = capi.lib()
         self.ctx.check(lib.otmb_op_set_values(self._h, v.ctypes.data, len(v)))
+
+    def solve(self, B, d=None, sigma=0.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False):
+        """X with (σ·I + diag(d) + A)·X = B (adjoint: ... + Aᵀ) by Jacobi-preconditioned BiCGStab on the device (otmb_op_solve,
+        include/otmb.h: the method, the stop rules, what is deterministic).  B: 1-D or 2-D (n x k); d: None (zero) or n values; x0: None (start
+        from zero) or an array of B's shape (not modified).  Returns (X, info): X of B's shape (2-D: Fortran-ordered), info a SolveInfo with one
+        entry per column.  A column that does not converge is REPORTED (info.converged, info.reason), not raised: X then holds its last iterate.
+        Argument errors and a zero or non-finite diagonal (SINGULAR_PRECONDITIONER) raise OtmbError."""
+        self._live()
+        m, n = self.shape
+        B = np.asarray(B)
+        if B.ndim not in (1, 2) or B.shape[0] != m:
+            raise capi.OtmbError(11, f"DimensionMismatch: operator of {(m, n)}, B of {B.shape}")
+        k = 1 if B.ndim == 1 else B.shape[1]
+        Bc, ldb = _column_major(B)
+        X = np.zeros(B.shape, dtype=np.float64, order="F")
+        if x0 is not None:
+            if np.shape(x0) != B.shape:
+                raise capi.OtmbError(11, f"DimensionMismatch: x0 of {np.shape(x0)}, B of {B.shape}")
+            X[...] = x0
+        dc = None
+        if d is not None:
+            dc = np.ascontiguousarray(d, dtype=np.float64)
+            if dc.shape != (n,):
+                raise capi.OtmbError(11, f"DimensionMismatch: d of {dc.shape}, expected {(n,)}")
+        iters, relres, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
+        lib = capi.lib()
+        rc = lib.otmb_op_solve(self._h, int(bool(adjoint)), k, None if dc is None else dc.ctypes.data, float(sigma), Bc.ctypes.data, ldb,
+                               X.ctypes.data, max(X.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), iters.ctypes.data,
+                               relres.ctypes.data, reason.ctypes.data)
+        if rc != capi.NOT_CONVERGED:
+            self.ctx.check(rc)
+        return X, SolveInfo(rc, iters, relres, reason)
 
     def __matmul__(self, x):
         return self.mul(x)

@@ -10,9 +10,12 @@ STATUS_NAMES = {
     1: "RHO_NAN", 2: "TADV_NAN", 3: "TKH_NAN", 4: "TKVML_NAN", 5: "TKVDEEP_NAN", 6: "FLUX_INTO_LAND",
     7: "UNKNOWN_TOPOLOGY", 8: "ALL_MISSING", 9: "ALLOC", 10: "HIP", 11: "INVALID_ARG", 12: "NO_PLAN",
     13: "NONCANONICAL_INDICES", 14: "CAPACITY", 15: "PUSH_MASK", 16: "ASYMMETRIC_PATTERN", 17: "GIVEN_FOREIGN",
+    18: "SINGULAR_PRECONDITIONER", 19: "NOT_CONVERGED",
 }
 GIVEN_FOREIGN = 17
 CAPACITY = 14
+NOT_CONVERGED = 19  # otmb_op_solve: an answer (the per-column info says which column stopped why), not an exception
+SOLVE_REASONS = ("converged", "maxiter", "breakdown", "nonfinite")  # otmb_solve_reason
 PHI_ORDER = ("east", "west", "north", "south", "top", "bottom")  # OTMB_EAST..OTMB_BOTTOM
 HDIRS = ("west", "east", "south", "north")  # OTMB_DIR_*
 MATS = ("T", "Tadv", "TκH", "TκVML", "TκVdeep")  # OTMB_T..OTMB_TKVDEEP
@@ -174,6 +177,10 @@ SYMBOLS = {
     "otmb_op_set_values": (C.c_int32, [_vp, _vp, C.c_int64]),
     "otmb_op_mul_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double]),
     "otmb_op_mul": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double]),
+    "otmb_op_solve_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64,
+                                       _vp, _vp, _vp]),
+    "otmb_op_solve": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64,
+                                   _vp, _vp, _vp]),
     "otmb_op_info": (C.c_int32, [_vp, _ip, _ip, _ip]),
     "otmb_op_destroy": (None, [_vp]),
     "otmb_transportmatrix_plan_dev": (C.c_int32, [_vp, C.POINTER(TmArgs), C.POINTER(C.c_int64 * 5)]),

@@ -1,0 +1,661 @@
+// otmb_solve.hip -- (σ·I + diag(d) + A)·X = B and (σ·I + diag(d) + Aᵀ)·X = B on a resident operator (otmb_op_solve[_dev]): BiCGStab,
+// right-preconditioned with P = diag(M) (Jacobi).  The reference's use: Γ_c = (T_c + M_c) \ (LUMP * ones(N)), test/local_full.jl:151-188.
+//
+// Per column (k columns advance together, every one with its own scalars; a stopped column is frozen: nothing of it is written again):
+//     r = b - M·x (x = x0 or 0), r̂ = r, ρ = r̂·r, restart
+//     p = restart ? r : r + β·(p - ω·v);  p̂ = p ./ diag                                (kernel 1, sv_p_kernel)
+//     v = M·p̂;  α = ρ / (r̂·v)                                                          (kernel 2, sv_rows / sv_cols / sv_long, mode 0)
+//     s = r - α·v;  ŝ = s ./ diag;  ‖s‖²                                               (kernel 3, sv_s_kernel)
+//     t = M·ŝ;  ω = (t·s) / (t·t), or 0 when ‖s‖ ≤ rtol·‖b‖ already                    (kernel 4, mode 1)
+//     x = (x + α·p̂) + ω·ŝ;  r = s - ω·t;  ρ' = r̂·r, ‖r‖²;  β = (ρ'/ρ)·(α/ω)            (kernel 5, sv_x_kernel)
+//     ‖r‖ ≤ rtol·‖b‖: r = b - M·x again (mode 2): the column stops as converged when that TRUE residual passes, otherwise it goes on from
+//     the true residual with r̂ = r (restart).
+//     |ρ'| ≤ 2⁻⁵²·‖r̂‖·‖r‖: ρ' is no more than the rounding error of its own sum (exactly zero included), and β, the next p and α would be
+//     noise.  The column takes the same path: true residual, r̂ = r.  This is not rare here: the transport matrix conserves mass (1ᵀ·T = 0),
+//     so for B = 1 and M = σ·I + T the first r̂ is a left eigenvector of M, r̂·r_j is σ-polynomial times ‖b‖² in exact arithmetic and BiCG's
+//     shadow space never grows; measured on the CPU restatement (tests/solve_ref.py), the one-month system on tiny_bipolar stalls at
+//     ‖r‖/‖b‖ = 3.2e-6 with |ρ| ~ 1e-20 and then meets ρ = 0 exactly at iteration 284 without this rule, and converges in 253 with it.
+// M·z is the operator's product with the (σ + d_i)·z_i term added in the same lane: one fold per row in storage order over the row slices
+// (long rows: one workgroup per row, before the slices' kernel, which then takes their finished value into its dot products), or per
+// column over the CSC copy for the adjoint.  No FMA (-ffp-contract=off).
+//
+// Every reduction is deterministic: the grid of a kernel depends on n alone, a workgroup sums with a fixed tree (xor shuffles inside a
+// wave, the four waves in order), writes ONE partial per column and quantity, and one workgroup per column (sv_scalar_kernel) folds the
+// partials -- lane t takes t, t + 256, ... in index order, then the same tree -- and computes α, β, ω, ρ and the column's state in device
+// memory, where the next kernel reads them.  No floating-point atomics.  A column's arithmetic never sees another column: column c of a
+// k-column solve has the bits of that column solved alone.
+//
+// The host enqueues SV_POLL iterations (plain stream launches), then reads the k column records; it stops when every column has.
+// A column stops with: converged (true residual checked) | maxiter | breakdown (r̂·v = 0, t·t = 0, ω = 0) | nonfinite (any scalar).
+// X then holds the LAST iterate (a stop between kernels 2 and 5 leaves the previous one: x and r are only ever written together).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <type_traits>
+
+#include "otmb_op.h"
+
+#define SV_POLL 16  // iterations enqueued between two reads of the column records
+
+enum { SV_ACTIVE = 0, SV_VERIFY = 1, SV_STOPPED = 2 };  // state; a stopped column's reason: otmb_solve_reason
+enum { SV_S_INIT = 0, SV_S_VERIFY, SV_S_ALPHA, SV_S_OMEGA, SV_S_RHO };
+
+struct SvCol {  // one column's record (device; the host reads all k of them)
+    double rho, alpha, omega, beta, bnorm, relres, rhn;  // rhn = ‖r̂‖
+    int state, reason, restart, bzero;
+    i64 iters;
+};
+
+// ---- sums --------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double sv_wave_sum(double x) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) x = x + __shfl_xor(x, d);
+    return x;
+}
+// 256 threads, NV values each: thread 0 gets the sums (waves in order).  red: 4 * NV doubles of LDS.
+template <int NV>
+__device__ __forceinline__ void sv_block_sum(double (&x)[NV], double *red) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+        const double s = sv_wave_sum(x[q]);
+        if (lane == 0) red[w * NV + q] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) x[q] = ((red[q] + red[NV + q]) + red[2 * NV + q]) + red[3 * NV + q];
+    }
+}
+template <int KB>
+__device__ __forceinline__ bool sv_any(const SvCol *__restrict__ cs, int want) {
+    bool any = false;
+#pragma unroll
+    for (int c = 0; c < KB; ++c) any |= cs[c].state == want;
+    return any;
+}
+
+// ---- setup ---------------------------------------------------------------------------------------------------------------------
+// sh = σ + d, diag = sh + the stored entries (i, i) of column i in storage order; bad = the first i whose diag is zero or not finite
+__global__ __launch_bounds__(256) void sv_diag_kernel(const i64 *__restrict__ cp, const int *__restrict__ rv, const double *__restrict__ nz, i64 n,
+                                                      const double *__restrict__ d, double sigma, double *__restrict__ sh, double *__restrict__ diag,
+                                                      unsigned long long *__restrict__ bad) {
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double s0 = d ? sigma + d[i] : sigma;
+    double acc = s0;
+    for (i64 j = cp[i] - 1; j < cp[i + 1] - 1; ++j)
+        if (rv[j] == (int)i) acc = acc + nz[j];
+    sh[i] = s0;
+    diag[i] = acc;
+    if (acc == 0.0 || !isfinite(acc)) atomicMin(bad, (unsigned long long)i);
+}
+// ‖b‖² partials
+template <int KB>
+__global__ __launch_bounds__(256) void sv_bnorm_kernel(i64 n, const double *__restrict__ B, i64 ldb, double *__restrict__ part, i64 np) {
+    __shared__ double red[4 * KB];
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    double q[KB];
+#pragma unroll
+    for (int c = 0; c < KB; ++c) {
+        const double b = i < n ? B[i + c * ldb] : 0.0;
+        q[c] = b * b;
+    }
+    sv_block_sum<KB>(q, red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < KB; ++c) part[(i64)(2 * c) * np + blockIdx.x] = q[c];
+    }
+}
+// x = 0 unless a start was given (and b is not zero: b = 0 gives x = 0)
+template <int KB>
+__global__ __launch_bounds__(256) void sv_x0_kernel(const SvCol *__restrict__ cs, i64 n, int use_x0, double *__restrict__ X, i64 ldx) {
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+#pragma unroll
+    for (int c = 0; c < KB; ++c)
+        if (!use_x0 || cs[c].bzero) X[i + c * ldx] = 0.0;
+}
+
+// ---- kernel 1: p = r + β·(p - ω·v), p̂ = p ./ diag (restart: p = r, r̂ = r) ---------------------------------------------------------
+template <int KB>
+__global__ __launch_bounds__(256) void sv_p_kernel(const SvCol *__restrict__ cs, i64 n, const double *__restrict__ diag, const double *__restrict__ r,
+                                                   double *__restrict__ rh, double *__restrict__ p, const double *__restrict__ v,
+                                                   double *__restrict__ ph) {
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double dg = diag[i];
+#pragma unroll
+    for (int c = 0; c < KB; ++c) {
+        if (cs[c].state != SV_ACTIVE) continue;
+        const i64 e = i + c * n;
+        const double rr = r[e];
+        double pn;
+        if (cs[c].restart) {
+            pn = rr;
+            rh[e] = rr;
+        } else {
+            const double w = cs[c].omega * v[e];
+            const double u = cs[c].beta * (p[e] - w);
+            pn = rr + u;
+        }
+        p[e] = pn;
+        ph[e] = pn / dg;
+    }
+}
+
+// ---- kernels 2 and 4, and the true residual: W = M·Z (modes 0, 1) or U - M·Z (mode 2) -------------------------------------------
+// mode 0: partial of U·W (U = r̂);  mode 1: partials of W·U (U = s) and W·W;  mode 2: partial of W·W.
+// Only columns in state `want` are written.  part: [column][2][np].
+template <int KB, int MODE>
+__device__ __forceinline__ void sv_finish(const SvCol *__restrict__ cs, int want, bool has, bool store, i64 i, const double (&y)[KB],
+                                          const double *__restrict__ U, i64 ldu, double *__restrict__ W, i64 ldw, double (&q)[2 * KB]) {
+#pragma unroll
+    for (int c = 0; c < KB; ++c) {
+        q[2 * c] = 0.0;
+        q[2 * c + 1] = 0.0;
+        if (!has) continue;
+        const double u = U[i + c * ldu];
+        // a long row's value was finished by sv_long_kernel (store == false): it is taken as it lies
+        const double w = store ? (MODE == 2 ? u - y[c] : y[c]) : W[i + c * ldw];
+        if (store && cs[c].state == want) W[i + c * ldw] = w;
+        if (MODE == 0) q[2 * c] = u * w;
+        if (MODE == 1) { q[2 * c] = w * u; q[2 * c + 1] = w * w; }
+        if (MODE == 2) q[2 * c] = w * w;
+    }
+}
+
+template <int KB, int MODE>
+__global__ __launch_bounds__(256) void sv_rows_kernel(const SvCol *__restrict__ cs, int want, const double *__restrict__ val, const int *__restrict__ col,
+                                                      const i64 *__restrict__ sbase, const int *__restrict__ elen, i64 n, const double *__restrict__ sh,
+                                                      const double *__restrict__ Z, i64 ldz, const double *__restrict__ U, i64 ldu,
+                                                      double *__restrict__ W, i64 ldw, double *__restrict__ part, i64 np) {
+    __shared__ double red[4 * 2 * KB];
+    if (!sv_any<KB>(cs, want)) return;  // (uniform over the grid)
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    const bool has = i < n;
+    const int len = has ? elen[i] : 0;
+    double y[KB];
+#pragma unroll
+    for (int c = 0; c < KB; ++c) y[c] = 0.0;
+    if (has && len >= 0) {
+        const i64 base = sbase[i >> 6] + (i & 63);
+        for (int e = 0; e < len; ++e) {
+            const double a = val[base + 64 * (i64)e];
+            const i64 j = col[base + 64 * (i64)e];
+#pragma unroll
+            for (int c = 0; c < KB; ++c) y[c] = y[c] + a * Z[j + c * ldz];
+        }
+        const double s = sh[i];
+#pragma unroll
+        for (int c = 0; c < KB; ++c) y[c] = y[c] + s * Z[i + c * ldz];
+    }
+    double q[2 * KB];
+    sv_finish<KB, MODE>(cs, want, has, len >= 0, i, y, U, ldu, W, ldw, q);
+    sv_block_sum<2 * KB>(q, red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < KB; ++c) {
+            part[(i64)(2 * c) * np + blockIdx.x] = q[2 * c];
+            part[(i64)(2 * c + 1) * np + blockIdx.x] = q[2 * c + 1];
+        }
+    }
+}
+
+// one workgroup per long row (spmv_long_kernel's scheme): lane c folds column c; runs BEFORE sv_rows_kernel, which sums its value
+template <int MODE>
+__global__ __launch_bounds__(64) void sv_long_kernel(const SvCol *__restrict__ cs, int want, const double *__restrict__ val, const int *__restrict__ col,
+                                                     const i64 *__restrict__ lrows, const i64 *__restrict__ loff, i64 ell, int k,
+                                                     const double *__restrict__ sh, const double *__restrict__ Z, i64 ldz, const double *__restrict__ U,
+                                                     i64 ldu, double *__restrict__ W, i64 ldw) {
+    __shared__ double sv[SP_TCH];
+    __shared__ int sc[SP_TCH];
+    const int lane = threadIdx.x;
+    const i64 i = lrows[blockIdx.x];
+    const i64 b0 = ell + loff[i], len = loff[i + 1] - loff[i];
+    for (int c0 = 0; c0 < k; c0 += 64) {
+        const int c = c0 + lane;
+        const bool on = c < k && cs[c].state == want;
+        double acc = 0.0;
+        for (i64 lo = 0; lo < len; lo += SP_TCH) {
+            const int w = (int)min((i64)SP_TCH, len - lo);
+            __syncthreads();
+            for (int t = lane; t < w; t += 64) {
+                sv[t] = val[b0 + lo + t];
+                sc[t] = col[b0 + lo + t];
+            }
+            __syncthreads();
+            if (on)
+                for (int t = 0; t < w; ++t) acc = acc + sv[t] * Z[(i64)sc[t] + c * ldz];
+        }
+        if (on) {
+            const double y = acc + sh[i] * Z[i + c * ldz];
+            W[i + c * ldw] = MODE == 2 ? U[i + c * ldu] - y : y;
+        }
+    }
+}
+
+// the adjoint: one lane per column of A over the CSC copy (spmv_cols_kernel's scheme), 64 columns per workgroup
+template <int KB, int MODE>
+__global__ __launch_bounds__(64) void sv_cols_kernel(const SvCol *__restrict__ cs, int want, const i64 *__restrict__ cp, const int *__restrict__ rv,
+                                                     const double *__restrict__ nz, i64 n, const double *__restrict__ sh, const double *__restrict__ Z,
+                                                     i64 ldz, const double *__restrict__ U, i64 ldu, double *__restrict__ W, i64 ldw,
+                                                     double *__restrict__ part, i64 np) {
+    __shared__ double sv[SP_TCH];
+    __shared__ int sr[SP_TCH];
+    if (!sv_any<KB>(cs, want)) return;
+    const int lane = threadIdx.x;
+    const i64 c0 = (i64)blockIdx.x * 64, colm = c0 + lane;
+    const bool has = colm < n;
+    const i64 last = min(c0 + 64, n);
+    const i64 wb = cp[c0] - 1, we = cp[last] - 1;
+    const i64 mb = has ? cp[colm] - 1 : 0, me = has ? cp[colm + 1] - 1 : 0;
+    double y[KB];
+#pragma unroll
+    for (int c = 0; c < KB; ++c) y[c] = 0.0;
+    for (i64 lo = wb; lo < we; lo += SP_TCH) {
+        const int w = (int)min((i64)SP_TCH, we - lo);
+        __syncthreads();
+        for (int t = lane; t < w; t += 64) {
+            sv[t] = nz[lo + t];
+            sr[t] = rv[lo + t];
+        }
+        __syncthreads();
+        const i64 a = max(mb, lo), b = min(me, lo + w);
+        for (i64 e = a; e < b; ++e) {
+            const double x = sv[e - lo];
+            const i64 r = sr[e - lo];
+#pragma unroll
+            for (int c = 0; c < KB; ++c) y[c] = y[c] + x * Z[r + c * ldz];
+        }
+    }
+    if (has) {
+        const double s = sh[colm];
+#pragma unroll
+        for (int c = 0; c < KB; ++c) y[c] = y[c] + s * Z[colm + c * ldz];
+    }
+    double q[2 * KB];
+    sv_finish<KB, MODE>(cs, want, has, true, colm, y, U, ldu, W, ldw, q);
+#pragma unroll
+    for (int j = 0; j < 2 * KB; ++j) q[j] = sv_wave_sum(q[j]);
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < KB; ++c) {
+            part[(i64)(2 * c) * np + blockIdx.x] = q[2 * c];
+            part[(i64)(2 * c + 1) * np + blockIdx.x] = q[2 * c + 1];
+        }
+    }
+}
+
+// ---- kernel 3: s = r - α·v, ŝ = s ./ diag, ‖s‖² ------------------------------------------------------------------------------------
+template <int KB>
+__global__ __launch_bounds__(256) void sv_s_kernel(const SvCol *__restrict__ cs, i64 n, const double *__restrict__ diag, const double *__restrict__ r,
+                                                   const double *__restrict__ v, double *__restrict__ s, double *__restrict__ sh_, double *__restrict__ part,
+                                                   i64 np) {
+    __shared__ double red[4 * KB];
+    if (!sv_any<KB>(cs, SV_ACTIVE)) return;
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    const double dg = i < n ? diag[i] : 1.0;
+    double q[KB];
+#pragma unroll
+    for (int c = 0; c < KB; ++c) {
+        q[c] = 0.0;
+        if (i >= n || cs[c].state != SV_ACTIVE) continue;
+        const i64 e = i + c * n;
+        const double av = cs[c].alpha * v[e];
+        const double sn = r[e] - av;
+        s[e] = sn;
+        sh_[e] = sn / dg;
+        q[c] = sn * sn;
+    }
+    sv_block_sum<KB>(q, red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < KB; ++c) part[(i64)c * np + blockIdx.x] = q[c];
+    }
+}
+
+// ---- kernel 5: x = (x + α·p̂) + ω·ŝ, r = s - ω·t, partials of r̂·r and ‖r‖² --------------------------------------------------------
+template <int KB>
+__global__ __launch_bounds__(256) void sv_x_kernel(const SvCol *__restrict__ cs, i64 n, const double *__restrict__ ph, const double *__restrict__ sh_,
+                                                   const double *__restrict__ s, const double *__restrict__ t, const double *__restrict__ rh,
+                                                   double *__restrict__ r, double *__restrict__ X, i64 ldx, double *__restrict__ part, i64 np) {
+    __shared__ double red[4 * 2 * KB];
+    if (!sv_any<KB>(cs, SV_ACTIVE)) return;
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    double q[2 * KB];
+#pragma unroll
+    for (int c = 0; c < KB; ++c) {
+        q[2 * c] = 0.0;
+        q[2 * c + 1] = 0.0;
+        if (i >= n || cs[c].state != SV_ACTIVE) continue;
+        const i64 e = i + c * n;
+        const double al = cs[c].alpha, om = cs[c].omega;
+        const double ap = al * ph[e];
+        const double os = om * sh_[e];
+        const double x1 = X[i + c * ldx] + ap;
+        X[i + c * ldx] = x1 + os;
+        const double ot = om * t[e];
+        const double rn = s[e] - ot;
+        r[e] = rn;
+        q[2 * c] = rh[e] * rn;
+        q[2 * c + 1] = rn * rn;
+    }
+    sv_block_sum<2 * KB>(q, red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < KB; ++c) {
+            part[(i64)(2 * c) * np + blockIdx.x] = q[2 * c];
+            part[(i64)(2 * c + 1) * np + blockIdx.x] = q[2 * c + 1];
+        }
+    }
+}
+
+// ---- the scalars: workgroup c folds column c's partials and advances its record --------------------------------------------------
+__device__ __forceinline__ void sv_stop(SvCol &s, int reason) {
+    s.state = SV_STOPPED;
+    s.reason = reason;
+}
+// part: [column][2][np] (nb of them written), parts: [column][np] (kernel 3's ‖s‖², nbs written)
+__global__ __launch_bounds__(256) void sv_scalar_kernel(SvCol *__restrict__ cs, int step, const double *__restrict__ part, i64 np, i64 nb,
+                                                        const double *__restrict__ parts, i64 nbs, double rtol, i64 maxiter) {
+    __shared__ double red[4 * 3];
+    SvCol &s = cs[blockIdx.x];
+    const int want = step == SV_S_INIT ? -1 : (step == SV_S_VERIFY ? SV_VERIFY : SV_ACTIVE);
+    if (want >= 0 && s.state != want) return;  // (uniform over the workgroup)
+    const double *p0 = part + (i64)(2 * blockIdx.x) * np, *p1 = p0 + np, *p2 = parts + (i64)blockIdx.x * np;
+    double f[3] = {0.0, 0.0, 0.0};
+    for (i64 j = threadIdx.x; j < nb; j += 256) {
+        f[0] = f[0] + p0[j];
+        if (step == SV_S_OMEGA || step == SV_S_RHO) f[1] = f[1] + p1[j];
+    }
+    if (step == SV_S_OMEGA)
+        for (i64 j = threadIdx.x; j < nbs; j += 256) f[2] = f[2] + p2[j];
+    sv_block_sum<3>(f, red);
+    if (threadIdx.x != 0) return;
+    const double bn = s.bnorm;
+    switch (step) {
+        case SV_S_INIT: {  // f[0] = ‖b‖²
+            s.bnorm = sqrt(f[0]);
+            s.bzero = f[0] == 0.0;
+            s.rho = s.alpha = s.omega = 1.0;
+            s.beta = 0.0;
+            s.relres = 0.0;
+            s.iters = 0;
+            s.restart = 1;
+            s.reason = 0;
+            s.state = SV_VERIFY;
+            break;
+        }
+        case SV_S_VERIFY: {  // f[0] = ‖b - M·x‖², explicitly computed
+            const double rn = sqrt(f[0]);
+            if (s.bzero) {
+                s.relres = 0.0;
+                sv_stop(s, OTMB_SOLVE_CONVERGED);
+                break;
+            }
+            s.relres = rn / bn;
+            if (!isfinite(bn) || !isfinite(rn)) sv_stop(s, OTMB_SOLVE_NONFINITE);
+            else if (rn <= rtol * bn) sv_stop(s, OTMB_SOLVE_CONVERGED);
+            else if (s.iters >= maxiter) sv_stop(s, OTMB_SOLVE_MAXITER);
+            else {  // on from the true residual: r̂ = r, ρ = r·r, p = r
+                s.state = SV_ACTIVE;
+                s.restart = 1;
+                s.rho = f[0];
+                s.rhn = rn;
+            }
+            break;
+        }
+        case SV_S_ALPHA: {  // f[0] = r̂·v
+            if (!isfinite(f[0])) sv_stop(s, OTMB_SOLVE_NONFINITE);
+            else if (f[0] == 0.0) sv_stop(s, OTMB_SOLVE_BREAKDOWN);
+            else {
+                s.alpha = s.rho / f[0];
+                if (!isfinite(s.alpha)) sv_stop(s, OTMB_SOLVE_NONFINITE);
+            }
+            break;
+        }
+        case SV_S_OMEGA: {  // f[0] = t·s, f[1] = t·t, f[2] = ‖s‖²
+            if (!isfinite(f[0]) || !isfinite(f[1]) || !isfinite(f[2])) sv_stop(s, OTMB_SOLVE_NONFINITE);
+            else if (sqrt(f[2]) <= rtol * bn) s.omega = 0.0;  // s is already small enough: x += α·p̂, r = s, then the true residual decides
+            else if (f[1] == 0.0) sv_stop(s, OTMB_SOLVE_BREAKDOWN);
+            else {
+                s.omega = f[0] / f[1];
+                if (!isfinite(s.omega)) sv_stop(s, OTMB_SOLVE_NONFINITE);
+            }
+            break;
+        }
+        case SV_S_RHO: {  // f[0] = r̂·r, f[1] = ‖r‖²: the iteration is complete
+            s.iters += 1;
+            const double rn = sqrt(f[1]);
+            s.relres = rn / bn;
+            if (!isfinite(f[0]) || !isfinite(f[1])) sv_stop(s, OTMB_SOLVE_NONFINITE);
+            else if (rn <= rtol * bn) s.state = SV_VERIFY;
+            else if (s.iters >= maxiter) sv_stop(s, OTMB_SOLVE_MAXITER);
+            else if (fabs(f[0]) <= 0x1p-52 * s.rhn * rn) s.state = SV_VERIFY;  // ρ' is lost in the rounding of its own sum (zero included): a new r̂
+            else if (s.omega == 0.0) sv_stop(s, OTMB_SOLVE_BREAKDOWN);
+            else {
+                const double a = f[0] / s.rho, b = s.alpha / s.omega;
+                s.beta = a * b;
+                s.rho = f[0];
+                s.restart = 0;
+                if (!isfinite(s.beta)) sv_stop(s, OTMB_SOLVE_NONFINITE);
+            }
+            break;
+        }
+    }
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------------------
+struct SvWork {  // the solver's device arrays inside op->sw
+    double *sh, *diag, *r, *rh, *p, *v, *s, *t, *ph, *sh_, *part, *parts;
+    SvCol *cs;
+    unsigned long long *bad;
+    i64 np;
+};
+
+// every launch of a templated kernel over the columns in register blocks of 4, 2 and 1: F(KB, first column)
+template <class F>
+static void sv_blocks(i64 k, F f) {
+    for (i64 c0 = 0; c0 < k;) {
+        const i64 r = k - c0;
+        if (r >= 4) { f(std::integral_constant<int, 4>(), c0); c0 += 4; }
+        else if (r >= 2) { f(std::integral_constant<int, 2>(), c0); c0 += 2; }
+        else { f(std::integral_constant<int, 1>(), c0); c0 += 1; }
+    }
+}
+
+// W = M·Z (modes 0, 1) or U - M·Z (mode 2) for the columns in state `want`, with the partials of the mode's dot products
+template <int MODE>
+static void sv_apply(otmb_op *op, const SvWork &w, int adjoint, i64 k, int want, const double *Z, i64 ldz, const double *U, i64 ldu, double *W, i64 ldw) {
+    hipStream_t st = op->ctx->stream;
+    const i64 n = op->n;
+    if (!adjoint && op->nlong > 0)
+        hipLaunchKernelGGL(sv_long_kernel<MODE>, dim3((unsigned)op->nlong), dim3(64), 0, st, (const SvCol *)w.cs, want, (const double *)op->val.p,
+                           (const int *)op->col.p, (const i64 *)op->lrows.p, (const i64 *)op->loff.p, op->ell, (int)k, (const double *)w.sh, Z, ldz, U, ldu,
+                           W, ldw);
+    sv_blocks(k, [&](auto kb, i64 c0) {
+        constexpr int KB = decltype(kb)::value;
+        if (adjoint)
+            hipLaunchKernelGGL((sv_cols_kernel<KB, MODE>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, (const SvCol *)w.cs + c0, want,
+                               (const i64 *)op->cp.p, (const int *)op->rv.p, (const double *)op->nz.p, n, (const double *)w.sh, Z + c0 * ldz, ldz,
+                               U + c0 * ldu, ldu, W + c0 * ldw, ldw, w.part + 2 * c0 * w.np, w.np);
+        else
+            hipLaunchKernelGGL((sv_rows_kernel<KB, MODE>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const SvCol *)w.cs + c0, want,
+                               (const double *)op->val.p, (const int *)op->col.p, (const i64 *)op->sbase.p, (const int *)op->elen.p, n,
+                               (const double *)w.sh, Z + c0 * ldz, ldz, U + c0 * ldu, ldu, W + c0 * ldw, ldw, w.part + 2 * c0 * w.np, w.np);
+    });
+}
+
+static void sv_scalar(otmb_op *op, const SvWork &w, i64 k, int step, i64 nb, double rtol, i64 maxiter) {
+    hipLaunchKernelGGL(sv_scalar_kernel, dim3((unsigned)k), dim3(256), 0, op->ctx->stream, w.cs, step, (const double *)w.part, w.np, nb,
+                       (const double *)w.parts, (op->n + 255) / 256, rtol, maxiter);
+}
+
+// r = b - M·x for the columns that wait for it, and their verdict
+static void sv_verify(otmb_op *op, const SvWork &w, int adjoint, i64 k, const double *B, i64 ldb, double *X, i64 ldx, double rtol, i64 maxiter) {
+    const i64 n = op->n;
+    sv_apply<2>(op, w, adjoint, k, SV_VERIFY, X, ldx, B, ldb, w.r, n);
+    sv_scalar(op, w, k, SV_S_VERIFY, adjoint ? (n + 63) / 64 : (n + 255) / 256, rtol, maxiter);
+}
+
+static int32_t sv_check(otmb_op *op, int64_t k, const double *B, int64_t ldb, double *X, int64_t ldx, double rtol, int64_t maxiter, const int64_t *iters,
+                        const double *relres, const int32_t *reason) {
+    otmb_ctx *ctx = op->ctx;
+    if (op->m != op->n) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "solve: the operator's matrix must be square");
+    if (k < 1 || k >= (1ll << 31)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "k (right-hand sides) must be >= 1");
+    if (ldb < op->n || ldb < 0) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "ldb is smaller than the rows of B");
+    if (ldx < op->n || ldx < 0) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "ldx is smaller than the rows of X");
+    if (op->n > 0 && (!B || !X)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
+    if (!iters || !relres || !reason) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
+    if (!(rtol > 0.0)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "rtol must be > 0");
+    if (maxiter < 0) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "maxiter must be >= 0");
+    return OTMB_OK;
+}
+
+extern "C" {
+
+int32_t otmb_op_solve_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X, int64_t ldx,
+                          int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    int32_t rc;
+    if ((rc = sv_check(op, k, B, ldb, X, ldx, rtol, maxiter, iters, relres, reason))) return rc;
+    otmb_ctx *ctx = op->ctx;
+    const i64 n = op->n;
+    if (n == 0) {
+        for (i64 c = 0; c < k; ++c) { iters[c] = 0; relres[c] = 0.0; reason[c] = OTMB_SOLVE_CONVERGED; }
+        return OTMB_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(op->device));
+    hipStream_t st = ctx->stream;
+    const i64 nb = (n + 255) / 256, np = (n + 63) / 64;  // partials per column and quantity: rows / vector kernels write nb, the adjoint's np
+    const size_t vec = (size_t)n * (size_t)k;
+    const size_t doubles = 2 * (size_t)n + 8 * vec + 3 * (size_t)np * (size_t)k;
+    const size_t bytes = doubles * 8 + (size_t)k * sizeof(SvCol) + 64;
+    if ((rc = otmb_reserve(ctx, op->sw, bytes))) return rc;
+    SvWork w;
+    double *q = (double *)op->sw.p;
+    w.sh = q; q += n;
+    w.diag = q; q += n;
+    for (double **v : {&w.r, &w.rh, &w.p, &w.v, &w.s, &w.t, &w.ph, &w.sh_}) { *v = q; q += vec; }
+    w.part = q; q += 2 * (size_t)np * (size_t)k;
+    w.parts = q; q += (size_t)np * (size_t)k;
+    w.bad = (unsigned long long *)q; q += 1;
+    w.cs = (SvCol *)q;
+    w.np = np;
+    const dim3 grid((unsigned)nb), block(256);
+    // the preconditioner, checked before anything of X is touched
+    HIP_TRY(ctx, hipMemsetAsync(w.bad, 0xff, 8, st));
+    hipLaunchKernelGGL(sv_diag_kernel, grid, block, 0, st, (const i64 *)op->cp.p, (const int *)op->rv.p, (const double *)op->nz.p, n, d, sigma, w.sh, w.diag,
+                       w.bad);
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned long long bad = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&bad, w.bad, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (bad != ~0ull) {
+        char msg[128];
+        snprintf(msg, sizeof msg, "diag(M)[%lld] is zero or not finite (1-based; the first such index)", (long long)bad + 1);
+        return otmb_fail(ctx, OTMB_ERR_SINGULAR_PRECONDITIONER, msg);
+    }
+    // ‖b‖, the start, its true residual
+    sv_blocks(k, [&](auto kb, i64 c0) {
+        hipLaunchKernelGGL((sv_bnorm_kernel<decltype(kb)::value>), grid, block, 0, st, n, B + c0 * ldb, ldb, w.part + 2 * c0 * np, np);
+    });
+    sv_scalar(op, w, k, SV_S_INIT, nb, rtol, maxiter);
+    sv_blocks(k, [&](auto kb, i64 c0) {
+        hipLaunchKernelGGL((sv_x0_kernel<decltype(kb)::value>), grid, block, 0, st, (const SvCol *)w.cs + c0, n, (int)use_x0, X + c0 * ldx, ldx);
+    });
+    sv_verify(op, w, adjoint, k, B, ldb, X, ldx, rtol, maxiter);
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<SvCol> h((size_t)k);
+    auto running = [&]() -> int32_t {  // reads the records: 1 some column still runs, 0 none, < 0 a HIP error's status (negated)
+        if (hipMemcpyAsync(h.data(), w.cs, (size_t)k * sizeof(SvCol), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return -1;
+        for (const SvCol &c : h)
+            if (c.state != SV_STOPPED) return 1;
+        return 0;
+    };
+    const i64 nbm = adjoint ? np : nb;  // partials the operator's kernels write
+    int32_t run = running();
+    for (i64 done = 0; run == 1 && done < maxiter;) {
+        const i64 batch = std::min<i64>(SV_POLL, maxiter - done);
+        for (i64 it = 0; it < batch; ++it) {
+            sv_blocks(k, [&](auto kb, i64 c0) {
+                hipLaunchKernelGGL((sv_p_kernel<decltype(kb)::value>), grid, block, 0, st, (const SvCol *)w.cs + c0, n, (const double *)w.diag,
+                                   (const double *)w.r + c0 * n, w.rh + c0 * n, w.p + c0 * n, (const double *)w.v + c0 * n, w.ph + c0 * n);
+            });
+            sv_apply<0>(op, w, adjoint, k, SV_ACTIVE, w.ph, n, w.rh, n, w.v, n);
+            sv_scalar(op, w, k, SV_S_ALPHA, nbm, rtol, maxiter);
+            sv_blocks(k, [&](auto kb, i64 c0) {
+                hipLaunchKernelGGL((sv_s_kernel<decltype(kb)::value>), grid, block, 0, st, (const SvCol *)w.cs + c0, n, (const double *)w.diag,
+                                   (const double *)w.r + c0 * n, (const double *)w.v + c0 * n, w.s + c0 * n, w.sh_ + c0 * n, w.parts + c0 * np, np);
+            });
+            sv_apply<1>(op, w, adjoint, k, SV_ACTIVE, w.sh_, n, w.s, n, w.t, n);
+            sv_scalar(op, w, k, SV_S_OMEGA, nbm, rtol, maxiter);
+            sv_blocks(k, [&](auto kb, i64 c0) {
+                hipLaunchKernelGGL((sv_x_kernel<decltype(kb)::value>), grid, block, 0, st, (const SvCol *)w.cs + c0, n, (const double *)w.ph + c0 * n,
+                                   (const double *)w.sh_ + c0 * n, (const double *)w.s + c0 * n, (const double *)w.t + c0 * n,
+                                   (const double *)w.rh + c0 * n, w.r + c0 * n, X + c0 * ldx, ldx, w.part + 2 * c0 * np, np);
+            });
+            sv_scalar(op, w, k, SV_S_RHO, nb, rtol, maxiter);
+            sv_verify(op, w, adjoint, k, B, ldb, X, ldx, rtol, maxiter);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        done += batch;
+        run = running();
+    }
+    if (run < 0) return otmb_fail(ctx, OTMB_ERR_HIP, "solve: reading the column records");
+    if (run == 1) return otmb_fail(ctx, OTMB_ERR_HIP, "solve: a column was still running after maxiter iterations");  // (cannot happen: sv_scalar_kernel stops it)
+    i64 open = 0, first = -1;
+    for (i64 c = 0; c < k; ++c) {
+        iters[c] = h[(size_t)c].iters;
+        relres[c] = h[(size_t)c].relres;
+        reason[c] = h[(size_t)c].reason;
+        if (reason[c] != OTMB_SOLVE_CONVERGED && open++ == 0) first = c;
+    }
+    if (open > 0) {
+        static const char *const names[] = {"converged", "maxiter", "breakdown", "nonfinite"};
+        char msg[160];
+        snprintf(msg, sizeof msg, "%lld of %lld columns; the first is column %lld: %s after %lld iterations, relative residual %.3e", (long long)open,
+                 (long long)k, (long long)first + 1, names[reason[first] & 3], (long long)iters[first], relres[first]);
+        return otmb_fail(ctx, OTMB_ERR_NOT_CONVERGED, msg);
+    }
+    return OTMB_OK;
+}
+
+int32_t otmb_op_solve(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X, int64_t ldx,
+                      int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    int32_t rc;
+    if ((rc = sv_check(op, k, B, ldb, X, ldx, rtol, maxiter, iters, relres, reason))) return rc;
+    otmb_ctx *ctx = op->ctx;
+    HIP_TRY(ctx, hipSetDevice(op->device));
+    const i64 n = op->n;
+    // staged compactly (leading dimension = n); the caller's padding rows are neither read nor written
+    if ((rc = otmb_reserve(ctx, op->xs, (size_t)(n * k) * 8 + 8))) return rc;
+    if ((rc = otmb_reserve(ctx, op->ys, (size_t)(n * k) * 8 + 8))) return rc;
+    if ((rc = otmb_reserve(ctx, op->ds, (size_t)n * 8 + 8))) return rc;
+    double *db = (double *)op->xs.p, *dx = (double *)op->ys.p, *dd = d ? (double *)op->ds.p : nullptr;
+    if (n > 0) {
+        HIP_TRY(ctx, hipMemcpy2DAsync(db, (size_t)n * 8, B, (size_t)ldb * 8, (size_t)n * 8, (size_t)k, hipMemcpyHostToDevice, ctx->stream));
+        ctx->uploaded_bytes += 8 * n * k;
+        if (use_x0) {
+            HIP_TRY(ctx, hipMemcpy2DAsync(dx, (size_t)n * 8, X, (size_t)ldx * 8, (size_t)n * 8, (size_t)k, hipMemcpyHostToDevice, ctx->stream));
+            ctx->uploaded_bytes += 8 * n * k;
+        }
+        if (d) {
+            HIP_TRY(ctx, hipMemcpyAsync(dd, d, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+            ctx->uploaded_bytes += 8 * n;
+        }
+    }
+    rc = otmb_op_solve_dev(op, adjoint, k, dd, sigma, db, n, dx, n, use_x0, rtol, maxiter, iters, relres, reason);
+    if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED) return rc;
+    const std::string msg = ctx->err;  // (HIP_TRY below would replace the solver's message)
+    if (n > 0) HIP_TRY(ctx, hipMemcpy2DAsync(X, (size_t)ldx * 8, dx, (size_t)n * 8, (size_t)n * 8, (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->err = msg;
+    return rc;
+}
+
+}  // extern "C"

@@ -27,23 +27,9 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "otmb_common.h"
+#include "otmb_op.h"  // struct otmb_op, SP_ELL_MAX, SP_TCH
 
-#define SP_ELL_MAX 256   // longest row a slice takes
-#define SP_TCH 512       // entries per LDS chunk of the Aᵀ and long-row kernels
 #define SP_GRID(n) dim3((unsigned)(((n) + 255) / 256 < 65536 ? (((n) + 255) / 256 > 0 ? ((n) + 255) / 256 : 1) : 65536)), dim3(256), 0, op->ctx->stream
-
-struct otmb_op {
-    otmb_ctx *ctx = nullptr;
-    int device = 0;
-    i64 m = 0, n = 0, nnz = 0;
-    i64 nslices = 0, ell = 0, nlong = 0;  // slices, entries of the slice layout (padding included), long rows
-    DevBuf cp, rv, nz;                    // CSC copy: colptr (n + 1, Int64), rowval - 1 (Int32), nzval
-    DevBuf dst;                           // per stored entry: its position in val / col
-    DevBuf elen, sbase, loff, lrows;      // per row: length or -1 (long); per slice: first position; per row: long-row offset; long rows
-    DevBuf val, col;                      // slices then long rows: values and column indices (Int32, 0-based)
-    DevBuf xs, ys;                        // staging of otmb_op_mul
-};
 
 // ---- device helpers ------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double sp_beta(const double *__restrict__ y, int bmode, double beta) {
@@ -235,7 +221,8 @@ static void sp_free(DevBuf &b) {
     b.cap = 0;
 }
 static void sp_free_all(otmb_op *op) {
-    for (DevBuf *b : {&op->cp, &op->rv, &op->nz, &op->dst, &op->elen, &op->sbase, &op->loff, &op->lrows, &op->val, &op->col, &op->xs, &op->ys}) sp_free(*b);
+    for (DevBuf *b : {&op->cp, &op->rv, &op->nz, &op->dst, &op->elen, &op->sbase, &op->loff, &op->lrows, &op->val, &op->col, &op->xs, &op->ys, &op->ds, &op->sw})
+        sp_free(*b);
 }
 
 static int32_t sp_scan(otmb_op *op, DevBuf &tmpb, const i64 *in, i64 *out, i64 n) {

@@ -98,6 +98,41 @@ class Operator:
             Y.copy_(Yc)
         return Y
 
+    def solve(self, B, d=None, sigma=0.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False):
+        """X with (σ·I + diag(d) + A)·X = B (adjoint: ... + Aᵀ) on device tensors (otmb_op_solve_dev; api.DeviceOperator.solve states the
+        contract).  B: 1-D or 2-D (n x k, column-major) float64 device tensor; d: None or a device tensor of n values; x0: None or a tensor of
+        B's shape (not modified).  Returns (X, info): X a new device tensor, info an api.SolveInfo (the call waits for the device to read it)."""
+        from .api import SolveInfo
+
+        if not self._h.value:
+            raise ValueError("operator is closed")
+        _on_device(B, self.device, "B")
+        m, n = self.shape
+        if B.dim() not in (1, 2) or B.shape[0] != m:
+            raise capi.OtmbError(11, f"DimensionMismatch: operator of {(m, n)}, B of {tuple(B.shape)}")
+        k = 1 if B.dim() == 1 else B.shape[1]
+        Bc, ldb = _col_major(B, m)
+        X = torch.zeros(m, dtype=torch.float64, device=B.device) if B.dim() == 1 else \
+            torch.zeros(k * max(m, 1), dtype=torch.float64, device=B.device).as_strided((m, k), (1, max(m, 1)))
+        if x0 is not None:
+            _on_device(x0, self.device, "x0")
+            if tuple(x0.shape) != tuple(B.shape):
+                raise capi.OtmbError(11, f"DimensionMismatch: x0 of {tuple(x0.shape)}, B of {tuple(B.shape)}")
+            X.copy_(x0)
+        dp = None
+        if d is not None:
+            _on_device(d, self.device, "d")
+            if d.dtype != torch.float64 or tuple(d.shape) != (n,):
+                raise capi.OtmbError(11, f"DimensionMismatch: d must be {n} float64 values")
+            d = d.contiguous()
+            dp = d.data_ptr()
+        iters, relres, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
+        rc = self.lib.otmb_op_solve_dev(self._h, int(bool(adjoint)), k, dp, float(sigma), Bc.data_ptr(), ldb, X.data_ptr(), max(m, 1),
+                                        int(x0 is not None), float(rtol), int(maxiter), iters.ctypes.data, relres.ctypes.data, reason.ctypes.data)
+        if rc != capi.NOT_CONVERGED:
+            self.ctx.check(rc)
+        return X, SolveInfo(rc, iters, relres, reason)
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self.lib.otmb_op_destroy(self._h)
@@ -609,6 +644,11 @@ class DeviceAssembler:
         """Y = α·M·X + β·Y (adjoint: α·Mᵀ·X + β·Y) with M the resident result `matrix`, on torch device tensors (1-D, or rows x k
         column-major), bit for bit SparseArrays' mul!; no host round trip (besides folding pending asynchronous steps)."""
         return self.operator(matrix).mul(X, alpha=alpha, beta=beta, Y=Y, adjoint=adjoint)
+
+    def solve(self, matrix, B, d=None, sigma=0.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False):
+        """X with (σ·I + diag(d) + M)·X = B (adjoint: ... + Mᵀ), M the resident result `matrix`, on torch device tensors: Jacobi-BiCGStab on
+        the resident operator (Operator.solve).  Returns (X, info)."""
+        return self.operator(matrix).solve(B, d=d, sigma=sigma, rtol=rtol, maxiter=maxiter, x0=x0, adjoint=adjoint)
 
     def _kept_steady(self):
         """The operators a step of this loop does not store: those the last call kept, or -- after a full write that left the promise live -- those

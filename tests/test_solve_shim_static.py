@@ -1,0 +1,100 @@
+"""CPU: the Julia shim declares and exports solve! and solve over the resident operator, its ccall of otmb_op_solve has the return type,
+the argument types and the argument ORDER of the C prototype (include/otmb.h) and of the ctypes mirror, and the shim and
+api.DeviceOperator.solve hand the same values over in the same places (the Python side is what the GPU tests execute)."""
+import os
+import re
+
+from test_julia_shim_static import HEADER, SHIM, ctypes_kind, header_prototypes, julia_kind, split_top
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+API = open(os.path.join(ROOT, "oceantransportmatrixbuilder.jl_amd", "api.py"), encoding="utf-8").read()
+CODE = "\n".join(l.split("#")[0] for l in SHIM.splitlines())
+C_ORDER = ["op", "adjoint", "k", "d", "sigma", "B", "ldb", "X", "ldx", "use_x0", "rtol", "maxiter", "iters", "relres", "reason"]
+
+
+def _jl(name):
+    m = re.search(r"\nfunction " + re.escape(name) + r"\(.*?\n(.*?)\nend\n", SHIM, re.S)
+    assert m, name
+    return m.group(1)
+
+
+def _header_names(name):
+    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
+    args = re.search(r"\b" + name + r"\s*\(([^;{]*?)\)\s*;", text).group(1)
+    return [re.search(r"(\w+)\s*$", a).group(1) for a in split_top(" ".join(args.split()))]
+
+
+def test_header_mirror_and_status_codes():
+    from otmb_amd import capi
+
+    protos = header_prototypes()
+    for name in ("otmb_op_solve", "otmb_op_solve_dev"):
+        ret, args = protos[name]
+        res, argtypes = capi.SYMBOLS[name]
+        assert ctypes_kind(res) == [ret] == ["i32"], name
+        assert [k for t in argtypes for k in ctypes_kind(t)[:1]] == args, name
+        assert _header_names(name) == C_ORDER, name
+    assert protos["otmb_op_solve"] == protos["otmb_op_solve_dev"]
+    codes = dict(re.findall(r"(OTMB_ERR_\w+)\s*=\s*(\d+)", HEADER))
+    assert codes["OTMB_ERR_SINGULAR_PRECONDITIONER"] == "18" and codes["OTMB_ERR_NOT_CONVERGED"] == "19"
+    assert len(set(codes.values())) == len(codes)  # no code is used twice (1-8 carry the reference's error texts)
+    assert capi.STATUS_NAMES[18] == "SINGULAR_PRECONDITIONER" and capi.STATUS_NAMES[19] == "NOT_CONVERGED" and capi.NOT_CONVERGED == 19
+    reasons = re.search(r"typedef enum \{([^}]*)\} otmb_solve_reason;", HEADER).group(1)
+    assert re.findall(r"OTMB_SOLVE_(\w+) = (\d)", reasons) == [("CONVERGED", "0"), ("MAXITER", "1"), ("BREAKDOWN", "2"), ("NONFINITE", "3")]
+    assert capi.SOLVE_REASONS == ("converged", "maxiter", "breakdown", "nonfinite")
+    assert "const SOLVE_REASONS = (:converged, :maxiter, :breakdown, :nonfinite)" in SHIM
+    assert "test/local_full.jl:151-188" in HEADER  # (the reference lines the entry points serve)
+
+
+def test_shim_defines_and_exports_solve():
+    exported = set(re.findall(r"[\w!]+", " ".join(re.findall(r"^export (.*)$", CODE, re.M))))
+    assert {"solve!", "solve"} <= exported
+    assert re.search(r"^function solve!\(X::StridedVecOrMat\{Float64\}, D::Union\{DeviceOperator,AdjointDeviceOperator\}, B::StridedVecOrMat\{Float64\};",
+                     CODE, re.M)
+    sig = CODE[CODE.index("function solve!("):]
+    sig = sig[:sig.index(")\n") + 1]
+    for kw in ("d::", "σ::", "rtol::", "maxiter::"):
+        assert kw in sig, kw
+    assert re.search(r"^solve\(D::Union\{DeviceOperator,AdjointDeviceOperator\}, B::StridedVecOrMat\{Float64\}; kwargs\.\.\.\) =\n\s*solve!\(", CODE, re.M)
+    # for this module's own types only
+    assert "SparseMatrixCSC" not in sig
+
+
+def test_the_ccall_has_the_prototype_and_the_argument_order_of_the_header():
+    from otmb_amd import capi
+
+    body = _jl("solve!")
+    assert "solve_fn = sym(:otmb_op_solve)" in body
+    assert re.findall(r"sym\(:(otmb_\w+)\)", body) == ["otmb_op_solve"]
+    m = re.search(r"ccall\(solve_fn, (\w+), \((.*?)\),\n(.*?)\)\n", body, re.S)
+    assert m, "solve!'s ccall"
+    jargs = [k for a in split_top(m.group(2).replace("\n", " ")) for k in julia_kind(a)]
+    protos = header_prototypes()
+    assert (julia_kind(m.group(1))[0], jargs) == protos["otmb_op_solve"]
+    res, argtypes = capi.SYMBOLS["otmb_op_solve"]
+    assert [k for t in argtypes for k in ctypes_kind(t)[:1]] == jargs
+    # the values, place by place, in the header's order
+    passed = [" ".join(a.split()) for a in split_top(m.group(3).replace("\n", " "))]
+    want = ["op.handle", "Int32(adjoint)", "k", "d === nothing ? C_NULL : d", "Float64(σ)", "B", "ldb", "X", "ldx", "Int32(x0)", "Float64(rtol)",
+            "Int64(maxiter)", "iters", "relres", "reason"]
+    assert passed == want and len(want) == len(C_ORDER)
+    assert body.index("lock(CALL_LOCK) do") < body.index("ccall(")  # under the module's lock
+    assert "rc == 19 || check(rc)" in body  # not converged is an answer; everything else goes through check
+    assert "adjoint = D isa AdjointDeviceOperator" in body
+
+
+def test_python_makes_the_same_call():
+    cls = API[API.index("\nclass DeviceOperator:"):]
+    m = re.search(r"\n    def solve\(self, B, d=None, sigma=0\.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False\):.*?(?=\n    def )", cls, re.S)
+    assert m, "DeviceOperator.solve"
+    py = m.group(0)
+    assert re.findall(r"lib\.(otmb_\w+)\(", py) == ["otmb_op_solve"]
+    call = py[py.index("lib.otmb_op_solve("):]
+    call = " ".join(call[:call.index("reason.ctypes.data)") + len("reason.ctypes.data")].split())
+    passed = split_top(call[len("lib.otmb_op_solve("):])
+    want = ["self._h", "int(bool(adjoint))", "k", "None if dc is None else dc.ctypes.data", "float(sigma)", "Bc.ctypes.data", "ldb", "X.ctypes.data",
+            "max(X.shape[0], 1)", "int(x0 is not None)", "float(rtol)", "int(maxiter)", "iters.ctypes.data", "relres.ctypes.data", "reason.ctypes.data"]
+    assert passed == want
+    assert "if rc != capi.NOT_CONVERGED:" in py  # likewise: reported, not raised
+    # the same defaults on both sides
+    assert "rtol::Real = 1e-10, maxiter::Integer = 10000" in SHIM

@@ -1,0 +1,129 @@
+"""Time the device solver (otmb_op_solve_dev, csrc/otmb_solve.hip) on the 1 degree preset; one JSON line per measurement.
+
+    python tools/solve_time.py [--reps 10] [--maxiter 20000] [--host] [--out FILE.jsonl]
+
+Systems (B = 1, rtol = 1e-10):
+    age      d = 1 s⁻¹ on the level-1 wet cells, σ = 0, on the full T and on the 2 x 2 x 1 coarse operator LUMP * T * SPRAY with
+             d_c = (LUMP * issrf .> 0), b_c = LUMP * 1 (the reference's own case, test/local_full.jl:151-188)
+    month    σ = 1 / (30 d), d = 0, on T
+Each line: iterations, reason, relres, the median / min / max wall time of --reps solves after one warm-up (time.perf_counter around the
+call, which waits for the device), the time per iteration, and the time of two otmb_op_mul_dev products on the same operator (HIP events):
+the floor of an iteration, whose five vector passes and scalar kernels the fusion is to keep small.
+--host: the parent's only route as well -- result_to_host, then scipy.sparse.linalg.bicgstab with the same (Jacobi) preconditioner."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import otmb_amd  # noqa: E402
+import otmb_amd.api as api  # noqa: E402
+from otmb_amd import synthetic  # noqa: E402
+from otmb_amd.device import DeviceAssembler, Operator  # noqa: E402
+
+DAY = 86400.0
+
+
+def two_products(op, n, reps=30):
+    x = torch.randn(n, dtype=torch.float64, device="cuda")
+    y = torch.empty(n, dtype=torch.float64, device="cuda")
+    for _ in range(5):
+        op.mul(x, Y=y)
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        op.mul(x, Y=y)
+        op.mul(y, Y=x)
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) * 1e-3)
+    return float(np.median(out))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--maxiter", type=int, default=20000)
+    ap.add_argument("--host", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import scipy.sparse as sp
+    import scipy.sparse.linalg as spla
+
+    g = synthetic.preset("access1deg", rho="array")
+    gm = otmb_amd.makegridmetrics(areacello=g.areacello, volcello=g.volcello, lon=g.lon, lat=g.lat, lev=g.lev,
+                                  lon_vertices=g.lon_vertices, lat_vertices=g.lat_vertices)
+    asm = DeviceAssembler(0)
+    asm.set_grid(gm, g.mlotst, g.rho, g.kappaH, g.kappaVML, g.kappaVdeep)
+    umo = torch.from_numpy(np.asfortranarray(g.umo.data).ravel(order="F")).cuda()
+    vmo = torch.from_numpy(np.asfortranarray(g.vmo.data).ravel(order="F")).cuda()
+    asm.step(umo, vmo, 1e20)
+    N = asm.N
+    t0 = time.perf_counter()
+    h = asm.result_to_host()["T"]
+    t_download = time.perf_counter() - t0
+    wet = asm.wet3d.cpu().numpy().reshape(g.umo.data.shape, order="F") != 0
+    nsurf = int(np.count_nonzero(wet[:, :, 0]))
+    issrf = np.zeros(N)
+    issrf[:nsurf] = 1.0
+    T = api.SparseMatrixCSC(N, N, *h)
+    vol = np.asarray(gm.v3D).reshape(-1, order="F")[wet.reshape(-1, order="F")]
+    L, S, vc = api.lump_and_spray(wet, vol, T, None, di=2, dj=2, dk=1)
+    Nc = len(vc)
+    L = api.SparseMatrixCSC(Nc, N, L.colptr, L.rowval, L.nzval)
+    S = api.SparseMatrixCSC(N, Nc, S.colptr, S.rowval, S.nzval)
+    Tc = api.coarsen(L, T, S)
+    Ls = sp.csc_matrix((L.nzval, L.rowval - 1, L.colptr - 1), shape=(Nc, N))
+    cases = [("age, coarse 2x2x1", Tc, Nc, (Ls @ issrf > 0).astype(np.float64), 0.0, Ls @ np.ones(N)),
+             ("age, T", T, N, issrf, 0.0, np.ones(N)),
+             ("month, T", T, N, None, 1.0 / (30 * DAY), np.ones(N))]
+    lines = []
+    for what, A, n, d, sigma, b in cases:
+        cp, rv, nz = (torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (A.colptr, A.rowval, A.nzval))
+        op = Operator(asm.ctx, n, n, cp, rv, nz)
+        bd = torch.from_numpy(b).cuda()
+        dd = None if d is None else torch.from_numpy(d).cuda()
+        times = []
+        for rep in range(a.reps + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            X, info = op.solve(bd, d=dd, sigma=sigma, rtol=1e-10, maxiter=a.maxiter)
+            times.append(time.perf_counter() - t0)
+        times = times[1:]
+        its = int(info.iterations[0])
+        rec = {"what": what, "n": n, "nnz": int(op.nnz), "iterations": its, "reason": info.reason[0], "relres": float(info.relres[0]),
+               "median_s": float(np.median(times)), "min_s": float(np.min(times)), "max_s": float(np.max(times)), "reps": a.reps,
+               "per_iteration_us": float(np.median(times)) / max(its, 1) * 1e6, "two_products_us": two_products(op, n) * 1e6}
+        if a.host:
+            t0 = time.perf_counter()
+            M = (sp.diags(np.full(n, sigma) + (0.0 if d is None else d)) + sp.csc_matrix((A.nzval, A.rowval - 1, A.colptr - 1), shape=(n, n))).tocsr()
+            dg = M.diagonal()
+            count = [0]
+
+            def cb(_):
+                count[0] += 1
+
+            xh, flag = spla.bicgstab(M, b, rtol=1e-10, atol=0.0, maxiter=a.maxiter, M=spla.LinearOperator((n, n), matvec=lambda z: z / dg), callback=cb)
+            t_host = time.perf_counter() - t0
+            rec.update(host_scipy_s=t_host, host_download_s=t_download if A is T else 0.0, host_iterations=count[0], host_flag=int(flag),
+                       host_relres=float(np.linalg.norm(b - M @ xh) / np.linalg.norm(b)))
+        lines.append(rec)
+        print(json.dumps(rec), flush=True)
+        op.close()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            for r in lines:
+                f.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()
