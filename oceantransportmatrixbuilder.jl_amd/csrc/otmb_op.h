@@ -1,6 +1,9 @@
-// otmb_op.h -- the resident sparse operator's record, shared by its products (otmb_spmv.hip) and its solver (otmb_solve.hip).
+// otmb_op.h -- the resident sparse operator's record and the host helpers shared by its products (otmb_spmv.hip) and its solver
+// (otmb_solve.hip): register blocks of columns, compact staging of host matrices.  The device walks over the layouts: otmb_op_fold.h.
 // The layouts are described at the head of otmb_spmv.hip, which builds them and owns every buffer (sp_free_all).
 #pragma once
+#include <type_traits>
+
 #include "otmb_common.h"
 
 #define SP_ELL_MAX 256   // longest row a slice takes
@@ -18,3 +21,23 @@ struct otmb_op {
     DevBuf xs, ys;                        // staging of otmb_op_mul / otmb_op_solve (X and Y; B and X)
     DevBuf ds, sw;                        // otmb_op_solve: staging of d; the solver's vectors, partial sums and per-column records
 };
+
+// Register blocks of columns: f(std::integral_constant<int, B>, first column) for blocks of KB columns while that many are left from c0,
+// then of KB / 2, ..., 1 (the matrix is read once per block).
+template <int KB, class F>
+static void op_blocks(i64 c0, i64 k, F f) {
+    for (; k - c0 >= KB; c0 += KB) f(std::integral_constant<int, KB>(), c0);
+    if constexpr (KB > 1) op_blocks<KB / 2>(c0, k, f);
+}
+
+// Host matrices (rows x k, leading dimension ld) are staged compactly (leading dimension = rows): the caller's padding rows are neither
+// read nor written.
+static int32_t op_upload(otmb_ctx *ctx, double *dev, const double *host, i64 ld, i64 rows, i64 k) {
+    HIP_TRY(ctx, hipMemcpy2DAsync(dev, (size_t)rows * 8, host, (size_t)ld * 8, (size_t)rows * 8, (size_t)k, hipMemcpyHostToDevice, ctx->stream));
+    ctx->uploaded_bytes += 8 * rows * k;
+    return OTMB_OK;
+}
+static int32_t op_download(otmb_ctx *ctx, double *host, i64 ld, const double *dev, i64 rows, i64 k) {
+    HIP_TRY(ctx, hipMemcpy2DAsync(host, (size_t)ld * 8, dev, (size_t)rows * 8, (size_t)rows * 8, (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
+    return OTMB_OK;
+}

@@ -15,9 +15,10 @@
 //     so for B = 1 and M = σ·I + T the first r̂ is a left eigenvector of M, r̂·r_j is σ-polynomial times ‖b‖² in exact arithmetic and BiCG's
 //     shadow space never grows; measured on the CPU restatement (tests/solve_ref.py), the one-month system on tiny_bipolar stalls at
 //     ‖r‖/‖b‖ = 3.2e-6 with |ρ| ~ 1e-20 and then meets ρ = 0 exactly at iteration 284 without this rule, and converges in 253 with it.
-// M·z is the operator's product with the (σ + d_i)·z_i term added in the same lane: one fold per row in storage order over the row slices
-// (long rows: one workgroup per row, before the slices' kernel, which then takes their finished value into its dot products), or per
-// column over the CSC copy for the adjoint.  No FMA (-ffp-contract=off).
+// M·z is the operator's product with the (σ + d_i)·z_i term added last, in the same lane: one fold per row (adjoint: per column) in
+// storage order, over the same layouts by the same walks as the products (otmb_op_fold.h; the layouts: the head of otmb_spmv.hip).  The
+// long rows' kernel runs before the slices' kernel, which then takes their finished value into its dot products.  No FMA
+// (-ffp-contract=off).
 //
 // Every reduction is deterministic: the grid of a kernel depends on n alone, a workgroup sums with a fixed tree (xor shuffles inside a
 // wave, the four waves in order), writes ONE partial per column and quantity, and one workgroup per column (sv_scalar_kernel) folds the
@@ -32,11 +33,11 @@
 
 #include <algorithm>
 #include <cmath>
-#include <type_traits>
 
-#include "otmb_op.h"
+#include "otmb_op_fold.h"
 
 #define SV_POLL 16  // iterations enqueued between two reads of the column records
+#define SV_KB 4     // the solver's largest register block of columns (op_blocks: 4, 2, 1)
 
 enum { SV_ACTIVE = 0, SV_VERIFY = 1, SV_STOPPED = 2 };  // state; a stopped column's reason: otmb_solve_reason
 enum { SV_S_INIT = 0, SV_S_VERIFY, SV_S_ALPHA, SV_S_OMEGA, SV_S_RHO };
@@ -67,6 +68,12 @@ __device__ __forceinline__ void sv_block_sum(double (&x)[NV], double *red) {
 #pragma unroll
         for (int q = 0; q < NV; ++q) x[q] = ((red[q] + red[NV + q]) + red[2 * NV + q]) + red[3 * NV + q];
     }
+}
+// a workgroup's sums q[0..NV) to its place in the partials: quantity j of the launch at part[j * np + workgroup]
+template <int NV>
+__device__ __forceinline__ void sv_put(double *__restrict__ part, i64 np, const double (&q)[NV]) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) part[(i64)j * np + blockIdx.x] = q[j];
 }
 template <int KB>
 __device__ __forceinline__ bool sv_any(const SvCol *__restrict__ cs, int want) {
@@ -180,13 +187,10 @@ __global__ __launch_bounds__(256) void sv_rows_kernel(const SvCol *__restrict__ 
 #pragma unroll
     for (int c = 0; c < KB; ++c) y[c] = 0.0;
     if (has && len >= 0) {
-        const i64 base = sbase[i >> 6] + (i & 63);
-        for (int e = 0; e < len; ++e) {
-            const double a = val[base + 64 * (i64)e];
-            const i64 j = col[base + 64 * (i64)e];
+        op_fold_slice_row(val, col, sbase, i, len, [&](double a, i64 j) {
 #pragma unroll
             for (int c = 0; c < KB; ++c) y[c] = y[c] + a * Z[j + c * ldz];
-        }
+        });
         const double s = sh[i];
 #pragma unroll
         for (int c = 0; c < KB; ++c) y[c] = y[c] + s * Z[i + c * ldz];
@@ -194,16 +198,10 @@ __global__ __launch_bounds__(256) void sv_rows_kernel(const SvCol *__restrict__ 
     double q[2 * KB];
     sv_finish<KB, MODE>(cs, want, has, len >= 0, i, y, U, ldu, W, ldw, q);
     sv_block_sum<2 * KB>(q, red);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int c = 0; c < KB; ++c) {
-            part[(i64)(2 * c) * np + blockIdx.x] = q[2 * c];
-            part[(i64)(2 * c + 1) * np + blockIdx.x] = q[2 * c + 1];
-        }
-    }
+    if (threadIdx.x == 0) sv_put<2 * KB>(part, np, q);
 }
 
-// one workgroup per long row (spmv_long_kernel's scheme): lane c folds column c; runs BEFORE sv_rows_kernel, which sums its value
+// one workgroup per long row, lane c folds column c; runs BEFORE sv_rows_kernel, which sums its value
 template <int MODE>
 __global__ __launch_bounds__(64) void sv_long_kernel(const SvCol *__restrict__ cs, int want, const double *__restrict__ val, const int *__restrict__ col,
                                                      const i64 *__restrict__ lrows, const i64 *__restrict__ loff, i64 ell, int k,
@@ -218,17 +216,7 @@ __global__ __launch_bounds__(64) void sv_long_kernel(const SvCol *__restrict__ c
         const int c = c0 + lane;
         const bool on = c < k && cs[c].state == want;
         double acc = 0.0;
-        for (i64 lo = 0; lo < len; lo += SP_TCH) {
-            const int w = (int)min((i64)SP_TCH, len - lo);
-            __syncthreads();
-            for (int t = lane; t < w; t += 64) {
-                sv[t] = val[b0 + lo + t];
-                sc[t] = col[b0 + lo + t];
-            }
-            __syncthreads();
-            if (on)
-                for (int t = 0; t < w; ++t) acc = acc + sv[t] * Z[(i64)sc[t] + c * ldz];
-        }
+        op_fold_long_row(val, col, b0, len, sv, sc, lane, on, [&](double a, i64 j) { acc = acc + a * Z[j + c * ldz]; });
         if (on) {
             const double y = acc + sh[i] * Z[i + c * ldz];
             W[i + c * ldw] = MODE == 2 ? U[i + c * ldu] - y : y;
@@ -236,7 +224,7 @@ __global__ __launch_bounds__(64) void sv_long_kernel(const SvCol *__restrict__ c
     }
 }
 
-// the adjoint: one lane per column of A over the CSC copy (spmv_cols_kernel's scheme), 64 columns per workgroup
+// the adjoint: one lane per column of A over the CSC copy, 64 columns per workgroup
 template <int KB, int MODE>
 __global__ __launch_bounds__(64) void sv_cols_kernel(const SvCol *__restrict__ cs, int want, const i64 *__restrict__ cp, const int *__restrict__ rv,
                                                      const double *__restrict__ nz, i64 n, const double *__restrict__ sh, const double *__restrict__ Z,
@@ -246,30 +234,14 @@ __global__ __launch_bounds__(64) void sv_cols_kernel(const SvCol *__restrict__ c
     __shared__ int sr[SP_TCH];
     if (!sv_any<KB>(cs, want)) return;
     const int lane = threadIdx.x;
-    const i64 c0 = (i64)blockIdx.x * 64, colm = c0 + lane;
-    const bool has = colm < n;
-    const i64 last = min(c0 + 64, n);
-    const i64 wb = cp[c0] - 1, we = cp[last] - 1;
-    const i64 mb = has ? cp[colm] - 1 : 0, me = has ? cp[colm + 1] - 1 : 0;
+    i64 colm;
     double y[KB];
 #pragma unroll
     for (int c = 0; c < KB; ++c) y[c] = 0.0;
-    for (i64 lo = wb; lo < we; lo += SP_TCH) {
-        const int w = (int)min((i64)SP_TCH, we - lo);
-        __syncthreads();
-        for (int t = lane; t < w; t += 64) {
-            sv[t] = nz[lo + t];
-            sr[t] = rv[lo + t];
-        }
-        __syncthreads();
-        const i64 a = max(mb, lo), b = min(me, lo + w);
-        for (i64 e = a; e < b; ++e) {
-            const double x = sv[e - lo];
-            const i64 r = sr[e - lo];
+    const bool has = op_fold_csc_run(cp, rv, nz, n, sv, sr, (i64)blockIdx.x * 64, lane, colm, [&](double a, i64 r) {
 #pragma unroll
-            for (int c = 0; c < KB; ++c) y[c] = y[c] + x * Z[r + c * ldz];
-        }
-    }
+        for (int c = 0; c < KB; ++c) y[c] = y[c] + a * Z[r + c * ldz];
+    });
     if (has) {
         const double s = sh[colm];
 #pragma unroll
@@ -279,13 +251,7 @@ __global__ __launch_bounds__(64) void sv_cols_kernel(const SvCol *__restrict__ c
     sv_finish<KB, MODE>(cs, want, has, true, colm, y, U, ldu, W, ldw, q);
 #pragma unroll
     for (int j = 0; j < 2 * KB; ++j) q[j] = sv_wave_sum(q[j]);
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < KB; ++c) {
-            part[(i64)(2 * c) * np + blockIdx.x] = q[2 * c];
-            part[(i64)(2 * c + 1) * np + blockIdx.x] = q[2 * c + 1];
-        }
-    }
+    if (lane == 0) sv_put<2 * KB>(part, np, q);
 }
 
 // ---- kernel 3: s = r - α·v, ŝ = s ./ diag, ‖s‖² ------------------------------------------------------------------------------------
@@ -310,10 +276,7 @@ __global__ __launch_bounds__(256) void sv_s_kernel(const SvCol *__restrict__ cs,
         q[c] = sn * sn;
     }
     sv_block_sum<KB>(q, red);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int c = 0; c < KB; ++c) part[(i64)c * np + blockIdx.x] = q[c];
-    }
+    if (threadIdx.x == 0) sv_put<KB>(part, np, q);
 }
 
 // ---- kernel 5: x = (x + α·p̂) + ω·ŝ, r = s - ω·t, partials of r̂·r and ‖r‖² --------------------------------------------------------
@@ -343,13 +306,7 @@ __global__ __launch_bounds__(256) void sv_x_kernel(const SvCol *__restrict__ cs,
         q[2 * c + 1] = rn * rn;
     }
     sv_block_sum<2 * KB>(q, red);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int c = 0; c < KB; ++c) {
-            part[(i64)(2 * c) * np + blockIdx.x] = q[2 * c];
-            part[(i64)(2 * c + 1) * np + blockIdx.x] = q[2 * c + 1];
-        }
-    }
+    if (threadIdx.x == 0) sv_put<2 * KB>(part, np, q);
 }
 
 // ---- the scalars: workgroup c folds column c's partials and advances its record --------------------------------------------------
@@ -455,16 +412,6 @@ struct SvWork {  // the solver's device arrays inside op->sw
     i64 np;
 };
 
-// every launch of a templated kernel over the columns in register blocks of 4, 2 and 1: F(KB, first column)
-template <class F>
-static void sv_blocks(i64 k, F f) {
-    for (i64 c0 = 0; c0 < k;) {
-        const i64 r = k - c0;
-        if (r >= 4) { f(std::integral_constant<int, 4>(), c0); c0 += 4; }
-        else if (r >= 2) { f(std::integral_constant<int, 2>(), c0); c0 += 2; }
-        else { f(std::integral_constant<int, 1>(), c0); c0 += 1; }
-    }
-}
 
 // W = M·Z (modes 0, 1) or U - M·Z (mode 2) for the columns in state `want`, with the partials of the mode's dot products
 template <int MODE>
@@ -475,7 +422,7 @@ static void sv_apply(otmb_op *op, const SvWork &w, int adjoint, i64 k, int want,
         hipLaunchKernelGGL(sv_long_kernel<MODE>, dim3((unsigned)op->nlong), dim3(64), 0, st, (const SvCol *)w.cs, want, (const double *)op->val.p,
                            (const int *)op->col.p, (const i64 *)op->lrows.p, (const i64 *)op->loff.p, op->ell, (int)k, (const double *)w.sh, Z, ldz, U, ldu,
                            W, ldw);
-    sv_blocks(k, [&](auto kb, i64 c0) {
+    op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
         constexpr int KB = decltype(kb)::value;
         if (adjoint)
             hipLaunchKernelGGL((sv_cols_kernel<KB, MODE>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, (const SvCol *)w.cs + c0, want,
@@ -559,11 +506,11 @@ int32_t otmb_op_solve_dev(otmb_op *op, int32_t adjoint, int64_t k, const double 
         return otmb_fail(ctx, OTMB_ERR_SINGULAR_PRECONDITIONER, msg);
     }
     // ‖b‖, the start, its true residual
-    sv_blocks(k, [&](auto kb, i64 c0) {
+    op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
         hipLaunchKernelGGL((sv_bnorm_kernel<decltype(kb)::value>), grid, block, 0, st, n, B + c0 * ldb, ldb, w.part + 2 * c0 * np, np);
     });
     sv_scalar(op, w, k, SV_S_INIT, nb, rtol, maxiter);
-    sv_blocks(k, [&](auto kb, i64 c0) {
+    op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
         hipLaunchKernelGGL((sv_x0_kernel<decltype(kb)::value>), grid, block, 0, st, (const SvCol *)w.cs + c0, n, (int)use_x0, X + c0 * ldx, ldx);
     });
     sv_verify(op, w, adjoint, k, B, ldb, X, ldx, rtol, maxiter);
@@ -581,19 +528,19 @@ int32_t otmb_op_solve_dev(otmb_op *op, int32_t adjoint, int64_t k, const double 
     for (i64 done = 0; run == 1 && done < maxiter;) {
         const i64 batch = std::min<i64>(SV_POLL, maxiter - done);
         for (i64 it = 0; it < batch; ++it) {
-            sv_blocks(k, [&](auto kb, i64 c0) {
+            op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
                 hipLaunchKernelGGL((sv_p_kernel<decltype(kb)::value>), grid, block, 0, st, (const SvCol *)w.cs + c0, n, (const double *)w.diag,
                                    (const double *)w.r + c0 * n, w.rh + c0 * n, w.p + c0 * n, (const double *)w.v + c0 * n, w.ph + c0 * n);
             });
             sv_apply<0>(op, w, adjoint, k, SV_ACTIVE, w.ph, n, w.rh, n, w.v, n);
             sv_scalar(op, w, k, SV_S_ALPHA, nbm, rtol, maxiter);
-            sv_blocks(k, [&](auto kb, i64 c0) {
+            op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
                 hipLaunchKernelGGL((sv_s_kernel<decltype(kb)::value>), grid, block, 0, st, (const SvCol *)w.cs + c0, n, (const double *)w.diag,
                                    (const double *)w.r + c0 * n, (const double *)w.v + c0 * n, w.s + c0 * n, w.sh_ + c0 * n, w.parts + c0 * np, np);
             });
             sv_apply<1>(op, w, adjoint, k, SV_ACTIVE, w.sh_, n, w.s, n, w.t, n);
             sv_scalar(op, w, k, SV_S_OMEGA, nbm, rtol, maxiter);
-            sv_blocks(k, [&](auto kb, i64 c0) {
+            op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
                 hipLaunchKernelGGL((sv_x_kernel<decltype(kb)::value>), grid, block, 0, st, (const SvCol *)w.cs + c0, n, (const double *)w.ph + c0 * n,
                                    (const double *)w.sh_ + c0 * n, (const double *)w.s + c0 * n, (const double *)w.t + c0 * n,
                                    (const double *)w.rh + c0 * n, w.r + c0 * n, X + c0 * ldx, ldx, w.part + 2 * c0 * np, np);
@@ -632,18 +579,13 @@ int32_t otmb_op_solve(otmb_op *op, int32_t adjoint, int64_t k, const double *d, 
     otmb_ctx *ctx = op->ctx;
     HIP_TRY(ctx, hipSetDevice(op->device));
     const i64 n = op->n;
-    // staged compactly (leading dimension = n); the caller's padding rows are neither read nor written
     if ((rc = otmb_reserve(ctx, op->xs, (size_t)(n * k) * 8 + 8))) return rc;
     if ((rc = otmb_reserve(ctx, op->ys, (size_t)(n * k) * 8 + 8))) return rc;
     if ((rc = otmb_reserve(ctx, op->ds, (size_t)n * 8 + 8))) return rc;
     double *db = (double *)op->xs.p, *dx = (double *)op->ys.p, *dd = d ? (double *)op->ds.p : nullptr;
     if (n > 0) {
-        HIP_TRY(ctx, hipMemcpy2DAsync(db, (size_t)n * 8, B, (size_t)ldb * 8, (size_t)n * 8, (size_t)k, hipMemcpyHostToDevice, ctx->stream));
-        ctx->uploaded_bytes += 8 * n * k;
-        if (use_x0) {
-            HIP_TRY(ctx, hipMemcpy2DAsync(dx, (size_t)n * 8, X, (size_t)ldx * 8, (size_t)n * 8, (size_t)k, hipMemcpyHostToDevice, ctx->stream));
-            ctx->uploaded_bytes += 8 * n * k;
-        }
+        if ((rc = op_upload(ctx, db, B, ldb, n, k))) return rc;
+        if (use_x0 && (rc = op_upload(ctx, dx, X, ldx, n, k))) return rc;
         if (d) {
             HIP_TRY(ctx, hipMemcpyAsync(dd, d, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
             ctx->uploaded_bytes += 8 * n;
@@ -652,7 +594,8 @@ int32_t otmb_op_solve(otmb_op *op, int32_t adjoint, int64_t k, const double *d, 
     rc = otmb_op_solve_dev(op, adjoint, k, dd, sigma, db, n, dx, n, use_x0, rtol, maxiter, iters, relres, reason);
     if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED) return rc;
     const std::string msg = ctx->err;  // (HIP_TRY below would replace the solver's message)
-    if (n > 0) HIP_TRY(ctx, hipMemcpy2DAsync(X, (size_t)ldx * 8, dx, (size_t)n * 8, (size_t)n * 8, (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
+    int32_t rcd;
+    if (n > 0 && (rcd = op_download(ctx, X, ldx, dx, n, k))) return rcd;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->err = msg;
     return rc;

@@ -27,7 +27,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "otmb_op.h"  // struct otmb_op, SP_ELL_MAX, SP_TCH
+#include "otmb_op_fold.h"  // struct otmb_op, SP_ELL_MAX, SP_TCH; the walks over the layouts
 
 #define SP_GRID(n) dim3((unsigned)(((n) + 255) / 256 < 65536 ? (((n) + 255) / 256 > 0 ? ((n) + 255) / 256 : 1) : 65536)), dim3(256), 0, op->ctx->stream
 
@@ -124,19 +124,16 @@ __global__ __launch_bounds__(256) void spmv_rows_kernel(const double *__restrict
     if (i >= m) return;
     const int len = elen[i];
     if (len < 0) return;  // a long row: spmv_long_kernel
-    const i64 base = sbase[i >> 6] + (i & 63);
     double acc[KB];
 #pragma unroll
     for (int c = 0; c < KB; ++c) acc[c] = sp_beta(Y + i + c * ldy, bmode, beta);
-    for (int e = 0; e < len; ++e) {
-        const double v = val[base + 64 * (i64)e];
-        const i64 j = col[base + 64 * (i64)e];
+    op_fold_slice_row(val, col, sbase, i, len, [&](double v, i64 j) {
 #pragma unroll
         for (int c = 0; c < KB; ++c) {
             const double axj = X[j + c * ldx] * alpha;
             acc[c] = acc[c] + v * axj;
         }
-    }
+    });
 #pragma unroll
     for (int c = 0; c < KB; ++c) Y[i + c * ldy] = acc[c];
 }
@@ -153,20 +150,10 @@ __global__ __launch_bounds__(64) void spmv_long_kernel(const double *__restrict_
     for (int c0 = 0; c0 < k; c0 += 64) {
         const int c = c0 + lane;
         double acc = c < k ? sp_beta(Y + i + c * ldy, bmode, beta) : 0.0;
-        for (i64 lo = 0; lo < len; lo += SP_TCH) {
-            const int w = (int)min((i64)SP_TCH, len - lo);
-            __syncthreads();
-            for (int t = lane; t < w; t += 64) {
-                sv[t] = val[b0 + lo + t];
-                sc[t] = col[b0 + lo + t];
-            }
-            __syncthreads();
-            if (c < k)
-                for (int t = 0; t < w; ++t) {
-                    const double axj = X[(i64)sc[t] + c * ldx] * alpha;
-                    acc = acc + sv[t] * axj;
-                }
-        }
+        op_fold_long_row(val, col, b0, len, sv, sc, lane, c < k, [&](double v, i64 j) {
+            const double axj = X[j + c * ldx] * alpha;
+            acc = acc + v * axj;
+        });
         if (c < k) Y[i + c * ldy] = acc;
     }
 }
@@ -179,30 +166,14 @@ __global__ __launch_bounds__(64) void spmv_cols_kernel(const i64 *__restrict__ c
     __shared__ double sv[SP_TCH];
     __shared__ int sr[SP_TCH];
     const int lane = threadIdx.x;
-    const i64 c0 = (i64)blockIdx.x * 64, colm = c0 + lane;
-    const bool has = colm < n;
-    const i64 last = min(c0 + 64, n);
-    const i64 wb = cp[c0] - 1, we = cp[last] - 1;
-    const i64 mb = has ? cp[colm] - 1 : 0, me = has ? cp[colm + 1] - 1 : 0;
+    i64 colm;
     double tmp[KB];
 #pragma unroll
     for (int c = 0; c < KB; ++c) tmp[c] = 0.0;
-    for (i64 lo = wb; lo < we; lo += SP_TCH) {
-        const int w = (int)min((i64)SP_TCH, we - lo);
-        __syncthreads();
-        for (int t = lane; t < w; t += 64) {
-            sv[t] = nz[lo + t];
-            sr[t] = rv[lo + t];
-        }
-        __syncthreads();
-        const i64 a = max(mb, lo), b = min(me, lo + w);
-        for (i64 e = a; e < b; ++e) {
-            const double v = sv[e - lo];
-            const i64 r = sr[e - lo];
+    const bool has = op_fold_csc_run(cp, rv, nz, n, sv, sr, (i64)blockIdx.x * 64, lane, colm, [&](double v, i64 r) {
 #pragma unroll
-            for (int c = 0; c < KB; ++c) tmp[c] = tmp[c] + v * X[r + c * ldx];
-        }
-    }
+        for (int c = 0; c < KB; ++c) tmp[c] = tmp[c] + v * X[r + c * ldx];
+    });
     if (has) {
 #pragma unroll
         for (int c = 0; c < KB; ++c) {
@@ -257,10 +228,9 @@ static int32_t sp_plan(otmb_op *op, const i64 *rowval) {
     } S;
     DevBuf &flags = S.flags, &iota = S.iota, &keys = S.keys, &perm = S.perm, &rowptr = S.rowptr, &tmpb = S.tmpb, &lflag = S.lflag, &lent = S.lent,
            &lidx = S.lidx, &swidth = S.swidth;
-    auto done = [](int32_t r) { return r; };
-    if ((rc = sp_reserve(op, flags, 16))) return done(rc);
-    if ((rc = sp_reserve(op, op->rv, (size_t)nnz * 4))) return done(rc);
-    if ((rc = sp_reserve(op, iota, (size_t)nnz * 8))) return done(rc);
+    if ((rc = sp_reserve(op, flags, 16))) return rc;
+    if ((rc = sp_reserve(op, op->rv, (size_t)nnz * 4))) return rc;
+    if ((rc = sp_reserve(op, iota, (size_t)nnz * 8))) return rc;
     unsigned *bad = (unsigned *)flags.p;
     HIP_TRY(ctx, hipMemsetAsync(bad, 0, 16, ctx->stream));
     const i64 *cp = (const i64 *)op->cp.p;
@@ -270,45 +240,45 @@ static int32_t sp_plan(otmb_op *op, const i64 *rowval) {
     unsigned hb = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&hb, bad, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (hb & SP_BAD_CP) return done(otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "colptr not non-decreasing inside [1, nnz + 1]"));
-    if (hb & SP_BAD_RV) return done(otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "row index outside 1:m"));
+    if (hb & SP_BAD_CP) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "colptr not non-decreasing inside [1, nnz + 1]");
+    if (hb & SP_BAD_RV) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "row index outside 1:m");
     // stable transposition: radix sort of (row) keys with the storage position as value (LSD radix sort is stable)
     const i64 ns = (m + 63) / 64;
     op->nslices = ns;
-    if ((rc = sp_reserve(op, keys, (size_t)nnz * 4))) return done(rc);
-    if ((rc = sp_reserve(op, perm, (size_t)nnz * 8))) return done(rc);
-    if ((rc = sp_reserve(op, rowptr, (size_t)(m + 1) * 8))) return done(rc);
+    if ((rc = sp_reserve(op, keys, (size_t)nnz * 4))) return rc;
+    if ((rc = sp_reserve(op, perm, (size_t)nnz * 8))) return rc;
+    if ((rc = sp_reserve(op, rowptr, (size_t)(m + 1) * 8))) return rc;
     unsigned *sk = (unsigned *)keys.p;
     i64 *pm = (i64 *)perm.p;
     if (nnz > 0) {
         size_t tmp = 0;
         const unsigned bits = (unsigned)sp_bits(m);
         if (rocprim::radix_sort_pairs(nullptr, tmp, (const unsigned *)op->rv.p, sk, (const i64 *)iota.p, pm, (size_t)nnz, 0, bits, ctx->stream) != hipSuccess)
-            return done(otmb_fail(ctx, OTMB_ERR_HIP, "radix_sort_pairs (size)"));
-        if ((rc = sp_reserve(op, tmpb, tmp + 16))) return done(rc);
+            return otmb_fail(ctx, OTMB_ERR_HIP, "radix_sort_pairs (size)");
+        if ((rc = sp_reserve(op, tmpb, tmp + 16))) return rc;
         if (rocprim::radix_sort_pairs(tmpb.p, tmp, (const unsigned *)op->rv.p, sk, (const i64 *)iota.p, pm, (size_t)nnz, 0, bits, ctx->stream) != hipSuccess)
-            return done(otmb_fail(ctx, OTMB_ERR_HIP, "radix_sort_pairs"));
+            return otmb_fail(ctx, OTMB_ERR_HIP, "radix_sort_pairs");
     }
     sp_free(iota);
     i64 *rp = (i64 *)rowptr.p;
     hipLaunchKernelGGL(spmv_rowptr_kernel, SP_GRID(m + 1), (const unsigned *)sk, nnz, m, rp);
     // slices and long rows
-    if ((rc = sp_reserve(op, op->elen, (size_t)m * 4))) return done(rc);
-    if ((rc = sp_reserve(op, swidth, (size_t)(ns + 1) * 8))) return done(rc);
-    if ((rc = sp_reserve(op, op->sbase, (size_t)(ns + 1) * 8))) return done(rc);
-    if ((rc = sp_reserve(op, lflag, (size_t)(m + 1) * 8))) return done(rc);
-    if ((rc = sp_reserve(op, lent, (size_t)(m + 1) * 8))) return done(rc);
-    if ((rc = sp_reserve(op, lidx, (size_t)(m + 1) * 8))) return done(rc);
-    if ((rc = sp_reserve(op, op->loff, (size_t)(m + 1) * 8))) return done(rc);
+    if ((rc = sp_reserve(op, op->elen, (size_t)m * 4))) return rc;
+    if ((rc = sp_reserve(op, swidth, (size_t)(ns + 1) * 8))) return rc;
+    if ((rc = sp_reserve(op, op->sbase, (size_t)(ns + 1) * 8))) return rc;
+    if ((rc = sp_reserve(op, lflag, (size_t)(m + 1) * 8))) return rc;
+    if ((rc = sp_reserve(op, lent, (size_t)(m + 1) * 8))) return rc;
+    if ((rc = sp_reserve(op, lidx, (size_t)(m + 1) * 8))) return rc;
+    if ((rc = sp_reserve(op, op->loff, (size_t)(m + 1) * 8))) return rc;
     i64 *sw = (i64 *)swidth.p, *sb = (i64 *)op->sbase.p, *lf = (i64 *)lflag.p, *le = (i64 *)lent.p, *li = (i64 *)lidx.p, *lo = (i64 *)op->loff.p;
     int *el = (int *)op->elen.p;
     {
         const i64 threads = (ns + 1) * 64;  // every slice and one more wave for the trailing zeros
         hipLaunchKernelGGL(spmv_slice_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, (const i64 *)rp, m, ns, el, sw, lf, le);
     }
-    if ((rc = sp_scan(op, tmpb, sw, sb, ns + 1))) return done(rc);
-    if ((rc = sp_scan(op, tmpb, lf, li, m + 1))) return done(rc);
-    if ((rc = sp_scan(op, tmpb, le, lo, m + 1))) return done(rc);
+    if ((rc = sp_scan(op, tmpb, sw, sb, ns + 1))) return rc;
+    if ((rc = sp_scan(op, tmpb, lf, li, m + 1))) return rc;
+    if ((rc = sp_scan(op, tmpb, le, lo, m + 1))) return rc;
     HIP_TRY(ctx, hipGetLastError());
     i64 tot[3] = {0, 0, 0};
     HIP_TRY(ctx, hipMemcpyAsync(&tot[0], sb + ns, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -318,10 +288,10 @@ static int32_t sp_plan(otmb_op *op, const i64 *rowval) {
     op->ell = tot[0];
     op->nlong = tot[1];
     const i64 total = tot[0] + tot[2];
-    if ((rc = sp_reserve(op, op->val, (size_t)total * 8))) return done(rc);
-    if ((rc = sp_reserve(op, op->col, (size_t)total * 4))) return done(rc);
-    if ((rc = sp_reserve(op, op->lrows, (size_t)op->nlong * 8))) return done(rc);
-    if ((rc = sp_reserve(op, op->dst, (size_t)nnz * 8))) return done(rc);
+    if ((rc = sp_reserve(op, op->val, (size_t)total * 8))) return rc;
+    if ((rc = sp_reserve(op, op->col, (size_t)total * 4))) return rc;
+    if ((rc = sp_reserve(op, op->lrows, (size_t)op->nlong * 8))) return rc;
+    if ((rc = sp_reserve(op, op->dst, (size_t)nnz * 8))) return rc;
     i64 *dst = (i64 *)op->dst.p;
     if (nnz > 0) hipLaunchKernelGGL(spmv_dst_kernel, SP_GRID(nnz), (const i64 *)pm, (const unsigned *)sk, (const i64 *)rp, (const int *)el, (const i64 *)sb,
                                     (const i64 *)lo, nnz, op->ell, dst);
@@ -329,7 +299,7 @@ static int32_t sp_plan(otmb_op *op, const i64 *rowval) {
     if (n > 0 && nnz > 0) hipLaunchKernelGGL(spmv_colidx_kernel, SP_GRID(n), cp, n, (const i64 *)dst, (int *)op->col.p);
     if (nnz > 0) hipLaunchKernelGGL(spmv_relayout_kernel, SP_GRID(nnz), (const double *)op->nz.p, (const i64 *)dst, nnz, (double *)op->val.p);
     HIP_TRY(ctx, hipGetLastError());
-    return done(OTMB_OK);
+    return OTMB_OK;
 }
 
 // n + 1 column pointers are on the device at op->cp: read the first and the last, size nnz
@@ -369,26 +339,25 @@ static int32_t sp_create(otmb_ctx *ctx, int64_t m, int64_t n, const int64_t *col
     op->device = ctx->device;
     op->m = m;
     op->n = n;
-    auto fail = [](int32_t rc) { return rc; };
     int32_t rc;
-    if ((rc = sp_reserve(op, op->cp, (size_t)(n + 1) * 8))) return fail(rc);
+    if ((rc = sp_reserve(op, op->cp, (size_t)(n + 1) * 8))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(op->cp.p, colptr, (size_t)(n + 1) * 8, kind, ctx->stream));
-    if ((rc = sp_ends(op))) return fail(rc);
+    if ((rc = sp_ends(op))) return rc;
     const i64 nnz = op->nnz;
-    if (nnz >= (1ll << 40)) return fail(otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "matrix too large"));
-    if (nnz > 0 && (!rowval || !nzval)) return fail(otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument"));
+    if (nnz >= (1ll << 40)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "matrix too large");
+    if (nnz > 0 && (!rowval || !nzval)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
     struct Rows {  // rowval as given (Int64), for the plan's checks only
         DevBuf b;
         ~Rows() { sp_free(b); }
     } rows;
-    if ((rc = sp_reserve(op, rows.b, (size_t)nnz * 8))) return fail(rc);
-    if ((rc = sp_reserve(op, op->nz, (size_t)nnz * 8))) return fail(rc);
+    if ((rc = sp_reserve(op, rows.b, (size_t)nnz * 8))) return rc;
+    if ((rc = sp_reserve(op, op->nz, (size_t)nnz * 8))) return rc;
     if (nnz > 0) {
         HIP_TRY(ctx, hipMemcpyAsync(rows.b.p, rowval, (size_t)nnz * 8, kind, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(op->nz.p, nzval, (size_t)nnz * 8, kind, ctx->stream));
         if (kind == hipMemcpyHostToDevice) ctx->uploaded_bytes += 16 * nnz + 8 * (n + 1);
     }
-    if ((rc = sp_plan(op, (const i64 *)rows.b.p))) return fail(rc);
+    if ((rc = sp_plan(op, (const i64 *)rows.b.p))) return rc;
     *out = op;
     G.op = nullptr;
     return OTMB_OK;
@@ -456,15 +425,9 @@ int32_t otmb_op_mul_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *X
     otmb_ctx *ctx = op->ctx;
     HIP_TRY(ctx, hipSetDevice(op->device));
     const int bmode = beta == 0.0 ? 0 : (beta == 1.0 ? 1 : 2);
-    for (i64 c0 = 0; c0 < k;) {  // register blocks of tracers: the matrix is read once per block
-        const i64 r = k - c0;
-        const double *Xc = X ? X + c0 * ldx : nullptr;
-        double *Yc = Y ? Y + c0 * ldy : nullptr;
-        if (r >= 8) { sp_launch<8>(op, adjoint, Xc, ldx, Yc, ldy, alpha, beta, bmode); c0 += 8; }
-        else if (r >= 4) { sp_launch<4>(op, adjoint, Xc, ldx, Yc, ldy, alpha, beta, bmode); c0 += 4; }
-        else if (r >= 2) { sp_launch<2>(op, adjoint, Xc, ldx, Yc, ldy, alpha, beta, bmode); c0 += 2; }
-        else { sp_launch<1>(op, adjoint, Xc, ldx, Yc, ldy, alpha, beta, bmode); c0 += 1; }
-    }
+    op_blocks<8>(0, k, [&](auto kb, i64 c0) {
+        sp_launch<decltype(kb)::value>(op, adjoint, X ? X + c0 * ldx : nullptr, ldx, Y ? Y + c0 * ldy : nullptr, ldy, alpha, beta, bmode);
+    });
     if (!adjoint && op->nlong > 0)
         hipLaunchKernelGGL(spmv_long_kernel, dim3((unsigned)op->nlong), dim3(64), 0, ctx->stream, (const double *)op->val.p, (const int *)op->col.p,
                            (const i64 *)op->lrows.p, (const i64 *)op->loff.p, op->ell, (int)k, X, ldx, Y, ldy, alpha, beta, bmode);
@@ -479,20 +442,13 @@ int32_t otmb_op_mul(otmb_op *op, int32_t adjoint, int64_t k, const double *X, in
     otmb_ctx *ctx = op->ctx;
     HIP_TRY(ctx, hipSetDevice(op->device));
     const i64 rx = adjoint ? op->m : op->n, ry = adjoint ? op->n : op->m;
-    // staged compactly (leading dimension = rows); the caller's padding rows are neither read nor written
     if ((rc = sp_reserve(op, op->xs, (size_t)(rx * k) * 8))) return rc;
     if ((rc = sp_reserve(op, op->ys, (size_t)(ry * k) * 8))) return rc;
     double *dx = (double *)op->xs.p, *dy = (double *)op->ys.p;
-    if (rx > 0) {
-        HIP_TRY(ctx, hipMemcpy2DAsync(dx, (size_t)rx * 8, X, (size_t)ldx * 8, (size_t)rx * 8, (size_t)k, hipMemcpyHostToDevice, ctx->stream));
-        ctx->uploaded_bytes += 8 * rx * k;
-    }
-    if (ry > 0 && beta != 0.0) {  // (β == 0 discards Y)
-        HIP_TRY(ctx, hipMemcpy2DAsync(dy, (size_t)ry * 8, Y, (size_t)ldy * 8, (size_t)ry * 8, (size_t)k, hipMemcpyHostToDevice, ctx->stream));
-        ctx->uploaded_bytes += 8 * ry * k;
-    }
+    if (rx > 0 && (rc = op_upload(ctx, dx, X, ldx, rx, k))) return rc;
+    if (ry > 0 && beta != 0.0 && (rc = op_upload(ctx, dy, Y, ldy, ry, k))) return rc;  // (β == 0 discards Y)
     if ((rc = otmb_op_mul_dev(op, adjoint, k, dx, rx, dy, ry, alpha, beta))) return rc;
-    if (ry > 0) HIP_TRY(ctx, hipMemcpy2DAsync(Y, (size_t)ldy * 8, dy, (size_t)ry * 8, (size_t)ry * 8, (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
+    if (ry > 0 && (rc = op_download(ctx, Y, ldy, dy, ry, k))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return OTMB_OK;
 }

@@ -193,6 +193,23 @@ def arrow(n=5000, seed=3):
     return A.indptr.astype(np.int64) + 1, A.indices.astype(np.int64) + 1, A.data.astype(np.float64)
 
 
+def dominant(n=257, per_row=9, seed=5):
+    """Random nonsymmetric, strictly diagonally dominant matrix: per_row - 1 off-diagonal entries per row in random columns (a repeated
+    column is summed), diagonal = 2·Σ|off-diagonal| of its row.  n = 257: two workgroups of the row kernels, five of the column kernels,
+    a last slice of one row.  Julia's arrays."""
+    rng = np.random.default_rng(seed)
+    rows = np.repeat(np.arange(n), per_row - 1)
+    cols = rng.integers(0, n, rows.size)
+    vals = rng.uniform(0.5, 1.5, rows.size) * rng.choice([-1.0, 1.0], rows.size)
+    keep = rows != cols
+    A = sp.csr_matrix((vals[keep], (rows[keep], cols[keep])), shape=(n, n))
+    off = np.asarray(abs(A).sum(axis=1)).ravel()
+    assert (off > 0).all()
+    A = sp.csc_matrix(A + sp.diags(2.0 * off))
+    A.sort_indices()
+    return A.indptr.astype(np.int64) + 1, A.indices.astype(np.int64) + 1, A.data.astype(np.float64)
+
+
 def longest(A, adjoint):
     """L of the residual bound: the longest row of M's product -- a row of A (adjoint: a column) and the diagonal term."""
     A = sp.csc_matrix(A)

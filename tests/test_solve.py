@@ -98,6 +98,40 @@ def test_long_row_path():
             _check_residual(A, X, B, None, 0.0, adjoint, ("arrow", adjoint))
 
 
+def _small_system(which):
+    """(n, Julia's arrays, d, σ): the arrow matrix whose row 0 (600 entries) is a long row of two LDS chunks (SP_TCH = 512) and whose
+    column 0 is clipped across a chunk edge under the adjoint; the random matrix of two row workgroups, five column workgroups and a last
+    slice of one row, with d and σ."""
+    if which == "arrow":
+        return 600, R.arrow(600), None, 0.0
+    return 257, R.dominant(257), np.random.default_rng(13).uniform(0.0, 1.0, 257), 0.5
+
+
+@pytest.mark.parametrize("adjoint", [False, True])
+@pytest.mark.parametrize("which", ["arrow", "dominant"])
+def test_register_blocks_and_tracer_groups(which, adjoint):
+    """k = 7 is launched as register blocks of 4 + 2 + 1 columns, k = 65 has a second group of 64 columns in the long-row kernel: the
+    residual bound holds for every column, and columns 0, 3, 6 (one of each block) and 64 have the bits of that column solved alone."""
+    import otmb_amd.api as api
+
+    n, (p, i, v), d, sigma = _small_system(which)
+    A = R.csc_of(n, n, p, i, v)
+    if which == "arrow":
+        assert np.bincount(i - 1, minlength=n).max() > 512 and np.diff(p).max() > 512  # SP_TCH
+    B = _rhs(n, 65, seed=11)
+    with api.DeviceOperator(_csc(n, p, i, v)) as D:
+        alone = {c: D.solve(B[:, c], d=d, sigma=sigma, rtol=RTOL, maxiter=MAXITER, adjoint=adjoint) for c in (0, 3, 6, 64)}
+        for k in (7, 65):
+            X, info = D.solve(B[:, :k], d=d, sigma=sigma, rtol=RTOL, maxiter=MAXITER, adjoint=adjoint)
+            assert info.converged.all() and info.status == 0, info
+            _check_residual(A, X, B[:, :k], d, sigma, adjoint, (which, adjoint, k))
+            for c in (0, 3, 6, 64)[: 3 + (k == 65)]:
+                xc, ic = alone[c]
+                _same_bits(xc, X[:, c], ("column alone", which, adjoint, k, c))
+                assert ic.iterations[0] == info.iterations[c] and ic.reason[0] == info.reason[c]
+                _same_bits(ic.relres[0], info.relres[c], ("relres alone", which, adjoint, k, c))
+
+
 def test_time_loop_x0_and_padding(oracle):
     import otmb_amd.api as api
     from otmb_amd import capi

@@ -88,3 +88,26 @@ def test_stop_rules_of_the_restatement():
     assert e.value.index == 7
     with pytest.raises(ValueError):
         R.solve_ref(sp.csc_matrix((3, 4)), np.ones(3))
+
+
+@pytest.mark.parametrize("adjoint", [False, True])
+def test_the_small_systems_of_the_device_tests_are_what_they_claim(adjoint):
+    """arrow(600) and dominant(257) (tests/test_solve.py, tools/solve_bits.py): the shapes that put them at the device kernels' chunk and
+    block boundaries, and that the restatement solves them, so a device failure on them is the device's."""
+    import scipy.sparse as sp
+
+    p, i, v = R.arrow(600)
+    assert np.bincount(i - 1, minlength=600)[0] == 600 and np.diff(p)[0] == 600  # beyond SP_ELL_MAX = 256 and SP_TCH = 512
+    q, j, w = R.dominant(257)
+    D = R.csc_of(257, 257, q, j, w)
+    off = np.asarray(abs(D - sp.diags(D.diagonal())).sum(axis=1)).ravel()
+    assert (np.abs(D.diagonal()) > off).all() and abs(D - D.T).max() > 0  # strictly diagonally dominant, nonsymmetric
+    assert 8 <= len(w) / 257 <= 9
+    d = np.random.default_rng(13).uniform(0.0, 1.0, 257)
+    for A, dd, sigma in ((R.csc_of(600, 600, p, i, v), None, 0.0), (D, d, 0.5)):
+        B = np.ones((A.shape[0], 2), order="F")
+        B[:, 1] = np.random.default_rng(11).standard_normal(A.shape[0])
+        X, info = R.solve_ref(A, B, d=dd, sigma=sigma, rtol=RTOL, maxiter=MAXITER, adjoint=adjoint)
+        assert info["converged"].all(), info
+        for res, bound in R.residual_check(A, X, B, dd, sigma, adjoint, RTOL):
+            assert res <= bound
