@@ -34,6 +34,7 @@ export makegridmetrics, velocity2fluxes, fluxes2velocity, facefluxesfromvelociti
 export makeindices, facefluxesfrommasstransport, facefluxes, transportmatrix, lump_and_spray, coarsen
 export DeviceOperator, setvalues!
 export solve!, solve
+export setlines!, verticallines, precondition!
 
 const LIBPATH = get(ENV, "OTMB_HIP_LIB", joinpath(@__DIR__, "..", "oceantransportmatrixbuilder.jl_amd", "lib", "libotmb_hip.so"))
 const lib = Ref{Ptr{Cvoid}}(C_NULL)
@@ -365,10 +366,8 @@ end
 # info.converged, one entry per column of B.  A column that does not converge is REPORTED, not thrown (status 19): X then holds its last
 # iterate.  Argument errors throw ArgumentError; a zero or non-finite entry of the diagonal throws an ErrorException that names it.
 const SOLVE_REASONS = (:converged, :maxiter, :breakdown, :nonfinite)   # otmb_solve_reason
-function solve!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, B::StridedVecOrMat{Float64};
-                d::Union{Nothing,Vector{Float64}} = nothing, σ::Real = 0.0, rtol::Real = 1e-10, maxiter::Integer = 10000, x0::Bool = false)
-    adjoint = D isa AdjointDeviceOperator
-    op = adjoint ? D.parent : D
+# the checks and leading dimensions solve! and solvepc! share: (k, ldb, ldx)
+function solvedims(X, op::DeviceOperator, B, d)
     n = op.n
     (size(B, 1) == n && size(X, 1) == n && size(X, 2) == size(B, 2)) || throw(DimensionMismatch("operator of $((op.m, op.n)), B $(size(B)), X $(size(X))"))
     (d === nothing || length(d) == n) || throw(DimensionMismatch("d has $(length(d)) values, expected $n"))
@@ -376,6 +375,17 @@ function solve!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDevi
     k = size(B, 2)
     ldb = B isa AbstractVector || k <= 1 ? max(n, 1) : stride(B, 2)
     ldx = X isa AbstractVector || k <= 1 ? max(n, 1) : stride(X, 2)
+    return k, ldb, ldx
+end
+function solve!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, B::StridedVecOrMat{Float64};
+                d::Union{Nothing,Vector{Float64}} = nothing, σ::Real = 0.0, rtol::Real = 1e-10, maxiter::Integer = 10000, x0::Bool = false,
+                precond::Symbol = :jacobi)
+    # precond = :lines (after setlines!): the water columns' tridiagonals instead of the diagonal, through otmb_op_solve_pc.  (The body
+    # below stays the plain otmb_op_solve call because tests/test_solve_shim_static.py pins it place by place; solvepc! shares solvedims.)
+    precond === :jacobi || return solvepc!(X, D, B, precond; d = d, σ = σ, rtol = rtol, maxiter = maxiter, x0 = x0)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    k, ldb, ldx = solvedims(X, op, B, d)
     iters = zeros(Int64, k)
     relres = zeros(Float64, k)
     reason = zeros(Int32, k)
@@ -393,6 +403,77 @@ function solve!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDevi
 end
 solve(D::Union{DeviceOperator,AdjointDeviceOperator}, B::StridedVecOrMat{Float64}; kwargs...) =
     solve!(B isa AbstractVector ? zeros(Float64, size(B, 1)) : zeros(Float64, size(B, 1), size(B, 2)), D, B; kwargs...)
+
+# The line preconditioner (include/otmb.h states its contract): P = the part of σ·I + Diagonal(d) + A on caller-given lines, solved by the
+# Thomas recurrence.  `setlines!(D, next)`: next[i] is the successor of unknown i on its line or 0 (`nothing` clears the lines; they survive
+# setvalues!); `verticallines(indices)` gives the water columns of a makeindices result; `solve!(...; precond = :lines)` then iterates with
+# them, and `precondition!(Z, D, Y; ...)` applies P⁻¹ alone (for a Krylov method of the caller's own).
+const PRECONDS = (jacobi = Int32(0), lines = Int32(1))   # otmb_precond
+precondcode(p::Symbol) = haskey(PRECONDS, p) ? PRECONDS[p] : throw(ArgumentError("precond must be :jacobi or :lines, not :$p"))
+
+function setlines!(D::DeviceOperator, next::Union{Nothing,Vector{Int64}})
+    (next === nothing || length(next) == D.n) || throw(DimensionMismatch("next has $(length(next)) entries, expected $(D.n)"))
+    lock(CALL_LOCK) do
+        D.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        set_lines_fn = sym(:otmb_op_set_lines)
+        check(ccall(set_lines_fn, Int32, (Ptr{Cvoid}, Ptr{Int64}), D.handle, next === nothing ? C_NULL : next))
+    end
+    return D
+end
+
+function verticallines(indices)
+    L = indices.Lwet3D
+    next = zeros(Int64, indices.N)
+    for k in 1:size(L, 3) - 1, j in axes(L, 2), i in axes(L, 1)
+        a, b = L[i, j, k], L[i, j, k + 1]
+        (ismissing(a) || ismissing(b) || a == 0 || b == 0) && continue
+        next[a] = b
+    end
+    return next
+end
+
+function solvepc!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, B::StridedVecOrMat{Float64}, precond::Symbol;
+                  d::Union{Nothing,Vector{Float64}} = nothing, σ::Real = 0.0, rtol::Real = 1e-10, maxiter::Integer = 10000, x0::Bool = false)
+    pc = precondcode(precond)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    k, ldb, ldx = solvedims(X, op, B, d)
+    iters = zeros(Int64, k)
+    relres = zeros(Float64, k)
+    reason = zeros(Int32, k)
+    lock(CALL_LOCK) do
+        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        solve_pc_fn = sym(:otmb_op_solve_pc)
+        rc = ccall(solve_pc_fn, Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Float64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int32, Float64, Int64,
+                Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, Int32),
+            op.handle, Int32(adjoint), k, d === nothing ? C_NULL : d, Float64(σ), B, ldb, X, ldx, Int32(x0), Float64(rtol), Int64(maxiter),
+            iters, relres, reason, pc)
+        rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which column stopped why
+    end
+    why = [SOLVE_REASONS[r + 1] for r in reason]
+    return X, (iterations = iters, relres = relres, reason = why, converged = why .== :converged)
+end
+
+function precondition!(Z::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, Y::StridedVecOrMat{Float64};
+                       d::Union{Nothing,Vector{Float64}} = nothing, σ::Real = 0.0, precond::Symbol = :lines)
+    pc = precondcode(precond)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    n = op.n
+    (size(Y, 1) == n && size(Z, 1) == n && size(Z, 2) == size(Y, 2)) || throw(DimensionMismatch("operator of $((op.m, op.n)), Y $(size(Y)), Z $(size(Z))"))
+    (d === nothing || length(d) == n) || throw(DimensionMismatch("d has $(length(d)) values, expected $n"))
+    (stride(Z, 1) == 1 && stride(Y, 1) == 1) || throw(ArgumentError("Z and Y need contiguous columns"))
+    k = size(Y, 2)
+    ldy = Y isa AbstractVector || k <= 1 ? max(n, 1) : stride(Y, 2)
+    ldz = Z isa AbstractVector || k <= 1 ? max(n, 1) : stride(Z, 2)
+    lock(CALL_LOCK) do
+        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        precond_fn = sym(:otmb_op_precond)
+        check(ccall(precond_fn, Int32, (Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Float64}, Float64, Ptr{Float64}, Int64, Ptr{Float64}, Int64),
+            op.handle, Int32(adjoint), pc, k, d === nothing ? C_NULL : d, Float64(σ), Y, ldy, Z, ldz))
+    end
+    return Z
+end
 
 const HDIRS = (:west, :east, :south, :north)      # OTMB_DIR_*
 f64(a) = Array{Float64}(replace(a, missing => NaN))

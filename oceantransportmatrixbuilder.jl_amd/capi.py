@@ -16,6 +16,8 @@ GIVEN_FOREIGN = 17
 CAPACITY = 14
 NOT_CONVERGED = 19  # otmb_op_solve: an answer (the per-column info says which column stopped why), not an exception
 SOLVE_REASONS = ("converged", "maxiter", "breakdown", "nonfinite")  # otmb_solve_reason
+PRECONDS = {"jacobi": 0, "lines": 1}  # otmb_precond
+
 PHI_ORDER = ("east", "west", "north", "south", "top", "bottom")  # OTMB_EAST..OTMB_BOTTOM
 HDIRS = ("west", "east", "south", "north")  # OTMB_DIR_*
 MATS = ("T", "Tadv", "TκH", "TκVML", "TκVdeep")  # OTMB_T..OTMB_TKVDEEP
@@ -35,6 +37,13 @@ class OtmbError(RuntimeError):
         self.status = status
         self.name = STATUS_NAMES.get(status, str(status))
         self.step = step  # asynchronous pipelines: 0-based index of the first step that failed
+
+
+def precond_code(precond):
+    """otmb_precond of "jacobi" / "lines"."""
+    if precond not in PRECONDS:
+        raise OtmbError(11, f"invalid argument: precond must be one of {sorted(PRECONDS)}, not {precond!r}")
+    return PRECONDS[precond]
 
 
 class Csc(C.Structure):
@@ -181,6 +190,14 @@ SYMBOLS = {
                                        _vp, _vp, _vp]),
     "otmb_op_solve": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64,
                                    _vp, _vp, _vp]),
+    "otmb_op_set_lines_dev": (C.c_int32, [_vp, _vp]),
+    "otmb_op_set_lines": (C.c_int32, [_vp, _vp]),
+    "otmb_op_solve_pc_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64,
+                                          _vp, _vp, _vp, C.c_int32]),
+    "otmb_op_solve_pc": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64,
+                                      _vp, _vp, _vp, C.c_int32]),
+    "otmb_op_precond_dev": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int64, _vp, C.c_double, _vp, C.c_int64, _vp, C.c_int64]),
+    "otmb_op_precond": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int64, _vp, C.c_double, _vp, C.c_int64, _vp, C.c_int64]),
     "otmb_op_info": (C.c_int32, [_vp, _ip, _ip, _ip]),
     "otmb_op_destroy": (None, [_vp]),
     "otmb_transportmatrix_plan_dev": (C.c_int32, [_vp, C.POINTER(TmArgs), C.POINTER(C.c_int64 * 5)]),

@@ -56,7 +56,7 @@ const char *otmb_status_string(int32_t s) {
         case OTMB_ERR_PUSH_MASK: return "push_mask does not describe these face fluxes and wet mask";
         case OTMB_ERR_ASYMMETRIC_PATTERN: return "ArgumentError: Adjacency / distance matrices must be symmetric";
         case OTMB_ERR_GIVEN_FOREIGN: return "a given operator is not what the library derives for these arguments: use the two-phase protocol";
-        case OTMB_ERR_SINGULAR_PRECONDITIONER: return "singular Jacobi preconditioner";
+        case OTMB_ERR_SINGULAR_PRECONDITIONER: return "singular preconditioner";
         case OTMB_ERR_NOT_CONVERGED: return "solve: not converged";
         default: return "unknown status";
     }

@@ -20,6 +20,9 @@ struct otmb_op {
     DevBuf val, col;                      // slices then long rows: values and column indices (Int32, 0-based)
     DevBuf xs, ys;                        // staging of otmb_op_mul / otmb_op_solve (X and Y; B and X)
     DevBuf ds, sw;                        // otmb_op_solve: staging of d; the solver's vectors, partial sums and per-column records
+    DevBuf ln;                            // otmb_op_set_lines (Int32, 0-based, -1 = none): successor (n), predecessor (n), line heads ascending (nheads)
+    i64 nheads = 0;
+    bool lines = false;                   // lines are set (they belong to the pattern: otmb_op_set_values keeps them)
 };
 
 // Register blocks of columns: f(std::integral_constant<int, B>, first column) for blocks of KB columns while that many are left from c0,

@@ -29,24 +29,21 @@
 // The host enqueues SV_POLL iterations (plain stream launches), then reads the k column records; it stops when every column has.
 // A column stops with: converged (true residual checked) | maxiter | breakdown (r̂·v = 0, t·t = 0, ω = 0) | nonfinite (any scalar).
 // X then holds the LAST iterate (a stop between kernels 2 and 5 leaves the previous one: x and r are only ever written together).
+//
+// otmb_op_solve_pc with OTMB_PRECOND_LINES: P is the part of M on the operator's lines (otmb_op_set_lines; otmb_solve_lines.hip states the
+// factorisation and the sweep).  Kernels 1 and 3 then leave p̂ and ŝ to a line sweep launched after them (p̂ = P⁻¹·p, ŝ = P⁻¹·s); ‖s‖² still
+// comes from kernel 3's own grid.  Everything else, the Jacobi path's bits included, is as above.  otmb_op_precond applies either P⁻¹ alone.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 
 #include "otmb_op_fold.h"
+#include "otmb_solve.h"
 
 #define SV_POLL 16  // iterations enqueued between two reads of the column records
-#define SV_KB 4     // the solver's largest register block of columns (op_blocks: 4, 2, 1)
 
-enum { SV_ACTIVE = 0, SV_VERIFY = 1, SV_STOPPED = 2 };  // state; a stopped column's reason: otmb_solve_reason
 enum { SV_S_INIT = 0, SV_S_VERIFY, SV_S_ALPHA, SV_S_OMEGA, SV_S_RHO };
-
-struct SvCol {  // one column's record (device; the host reads all k of them)
-    double rho, alpha, omega, beta, bnorm, relres, rhn;  // rhn = ‖r̂‖
-    int state, reason, restart, bzero;
-    i64 iters;
-};
 
 // ---- sums --------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double sv_wave_sum(double x) {
@@ -126,13 +123,14 @@ __global__ __launch_bounds__(256) void sv_x0_kernel(const SvCol *__restrict__ cs
 }
 
 // ---- kernel 1: p = r + β·(p - ω·v), p̂ = p ./ diag (restart: p = r, r̂ = r) ---------------------------------------------------------
-template <int KB>
+// LINES: p̂ is left to the line sweep that follows (ln_sweep: p̂ = P⁻¹·p); likewise ŝ in kernel 3.
+template <int KB, bool LINES>
 __global__ __launch_bounds__(256) void sv_p_kernel(const SvCol *__restrict__ cs, i64 n, const double *__restrict__ diag, const double *__restrict__ r,
                                                    double *__restrict__ rh, double *__restrict__ p, const double *__restrict__ v,
                                                    double *__restrict__ ph) {
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const double dg = diag[i];
+    const double dg = LINES ? 1.0 : diag[i];
 #pragma unroll
     for (int c = 0; c < KB; ++c) {
         if (cs[c].state != SV_ACTIVE) continue;
@@ -148,7 +146,7 @@ __global__ __launch_bounds__(256) void sv_p_kernel(const SvCol *__restrict__ cs,
             pn = rr + u;
         }
         p[e] = pn;
-        ph[e] = pn / dg;
+        if (!LINES) ph[e] = pn / dg;
     }
 }
 
@@ -255,14 +253,14 @@ __global__ __launch_bounds__(64) void sv_cols_kernel(const SvCol *__restrict__ c
 }
 
 // ---- kernel 3: s = r - α·v, ŝ = s ./ diag, ‖s‖² ------------------------------------------------------------------------------------
-template <int KB>
+template <int KB, bool LINES>
 __global__ __launch_bounds__(256) void sv_s_kernel(const SvCol *__restrict__ cs, i64 n, const double *__restrict__ diag, const double *__restrict__ r,
                                                    const double *__restrict__ v, double *__restrict__ s, double *__restrict__ sh_, double *__restrict__ part,
                                                    i64 np) {
     __shared__ double red[4 * KB];
     if (!sv_any<KB>(cs, SV_ACTIVE)) return;
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
-    const double dg = i < n ? diag[i] : 1.0;
+    const double dg = !LINES && i < n ? diag[i] : 1.0;
     double q[KB];
 #pragma unroll
     for (int c = 0; c < KB; ++c) {
@@ -272,7 +270,7 @@ __global__ __launch_bounds__(256) void sv_s_kernel(const SvCol *__restrict__ cs,
         const double av = cs[c].alpha * v[e];
         const double sn = r[e] - av;
         s[e] = sn;
-        sh_[e] = sn / dg;
+        if (!LINES) sh_[e] = sn / dg;
         q[c] = sn * sn;
     }
     sv_block_sum<KB>(q, red);
@@ -405,12 +403,56 @@ __global__ __launch_bounds__(256) void sv_scalar_kernel(SvCol *__restrict__ cs, 
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-struct SvWork {  // the solver's device arrays inside op->sw
-    double *sh, *diag, *r, *rh, *p, *v, *s, *t, *ph, *sh_, *part, *parts;
+struct SvWork {  // the solver's device arrays inside op->sw (m, u, piv: the line preconditioner's, otherwise null)
+    double *sh, *diag, *m, *u, *piv, *r, *rh, *p, *v, *s, *t, *ph, *sh_, *part, *parts;
     SvCol *cs;
-    unsigned long long *bad;
+    unsigned long long *bad;  // [2]: the diagonal's, the pivots'
     i64 np;
 };
+
+// Z = Y ./ diag: the Jacobi preconditioner on its own (otmb_op_precond)
+template <int KB>
+__global__ __launch_bounds__(256) void sv_scale_kernel(i64 n, const double *__restrict__ diag, const double *Y, i64 ldy, double *Z, i64 ldz) {
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double dg = diag[i];
+#pragma unroll
+    for (int c = 0; c < KB; ++c) Z[i + c * ldz] = Y[i + c * ldy] / dg;
+}
+
+static int32_t sv_check_precond(otmb_op *op, int32_t precond) {
+    if (precond != OTMB_PRECOND_JACOBI && precond != OTMB_PRECOND_LINES)
+        return otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, "precond must be OTMB_PRECOND_JACOBI or OTMB_PRECOND_LINES");
+    if (precond == OTMB_PRECOND_LINES && !op->lines)
+        return otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, "OTMB_PRECOND_LINES needs lines: otmb_op_set_lines first");
+    return OTMB_OK;
+}
+
+// sh and diag and, with lines, u, the multipliers and the pivots; a singular preconditioner is refused here, before anything of the
+// caller's is touched.  Waits for the device.
+static int32_t sv_precond_setup(otmb_op *op, const SvWork &w, int adjoint, int32_t precond, const double *d, double sigma) {
+    otmb_ctx *ctx = op->ctx;
+    hipStream_t st = ctx->stream;
+    const i64 n = op->n;
+    HIP_TRY(ctx, hipMemsetAsync(w.bad, 0xff, 16, st));
+    hipLaunchKernelGGL(sv_diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const i64 *)op->cp.p, (const int *)op->rv.p,
+                       (const double *)op->nz.p, n, d, sigma, w.sh, w.diag, w.bad);
+    if (precond == OTMB_PRECOND_LINES) ln_factor(op, adjoint, w.diag, w.m, w.u, w.piv, w.bad + 1);
+    HIP_TRY(ctx, hipGetLastError());
+    unsigned long long bad[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(bad, w.bad, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    char msg[128];
+    if (precond == OTMB_PRECOND_JACOBI && bad[0] != ~0ull) {
+        snprintf(msg, sizeof msg, "diag(M)[%lld] is zero or not finite (1-based; the first such index)", (long long)bad[0] + 1);
+        return otmb_fail(ctx, OTMB_ERR_SINGULAR_PRECONDITIONER, msg);
+    }
+    if (precond == OTMB_PRECOND_LINES && bad[1] != ~0ull) {
+        snprintf(msg, sizeof msg, "pivot[%lld] of the line factorisation is zero or not finite (1-based; the smallest such index)", (long long)bad[1] + 1);
+        return otmb_fail(ctx, OTMB_ERR_SINGULAR_PRECONDITIONER, msg);
+    }
+    return OTMB_OK;
+}
 
 
 // W = M·Z (modes 0, 1) or U - M·Z (mode 2) for the columns in state `want`, with the partials of the mode's dot products
@@ -463,11 +505,13 @@ static int32_t sv_check(otmb_op *op, int64_t k, const double *B, int64_t ldb, do
 
 extern "C" {
 
-int32_t otmb_op_solve_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X, int64_t ldx,
-                          int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason) {
+int32_t otmb_op_solve_pc_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X,
+                             int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason, int32_t precond) {
     if (!op) return OTMB_ERR_INVALID_ARG;
     int32_t rc;
     if ((rc = sv_check(op, k, B, ldb, X, ldx, rtol, maxiter, iters, relres, reason))) return rc;
+    if ((rc = sv_check_precond(op, precond))) return rc;
+    const bool lines = precond == OTMB_PRECOND_LINES;
     otmb_ctx *ctx = op->ctx;
     const i64 n = op->n;
     if (n == 0) {
@@ -478,33 +522,25 @@ int32_t otmb_op_solve_dev(otmb_op *op, int32_t adjoint, int64_t k, const double 
     hipStream_t st = ctx->stream;
     const i64 nb = (n + 255) / 256, np = (n + 63) / 64;  // partials per column and quantity: rows / vector kernels write nb, the adjoint's np
     const size_t vec = (size_t)n * (size_t)k;
-    const size_t doubles = 2 * (size_t)n + 8 * vec + 3 * (size_t)np * (size_t)k;
+    const size_t doubles = (lines ? 5 : 2) * (size_t)n + 8 * vec + 3 * (size_t)np * (size_t)k;
     const size_t bytes = doubles * 8 + (size_t)k * sizeof(SvCol) + 64;
     if ((rc = otmb_reserve(ctx, op->sw, bytes))) return rc;
     SvWork w;
     double *q = (double *)op->sw.p;
     w.sh = q; q += n;
     w.diag = q; q += n;
+    w.m = w.u = w.piv = nullptr;
+    if (lines)
+        for (double **v : {&w.m, &w.u, &w.piv}) { *v = q; q += n; }
     for (double **v : {&w.r, &w.rh, &w.p, &w.v, &w.s, &w.t, &w.ph, &w.sh_}) { *v = q; q += vec; }
     w.part = q; q += 2 * (size_t)np * (size_t)k;
     w.parts = q; q += (size_t)np * (size_t)k;
-    w.bad = (unsigned long long *)q; q += 1;
+    w.bad = (unsigned long long *)q; q += 2;
     w.cs = (SvCol *)q;
     w.np = np;
     const dim3 grid((unsigned)nb), block(256);
     // the preconditioner, checked before anything of X is touched
-    HIP_TRY(ctx, hipMemsetAsync(w.bad, 0xff, 8, st));
-    hipLaunchKernelGGL(sv_diag_kernel, grid, block, 0, st, (const i64 *)op->cp.p, (const int *)op->rv.p, (const double *)op->nz.p, n, d, sigma, w.sh, w.diag,
-                       w.bad);
-    HIP_TRY(ctx, hipGetLastError());
-    unsigned long long bad = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&bad, w.bad, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (bad != ~0ull) {
-        char msg[128];
-        snprintf(msg, sizeof msg, "diag(M)[%lld] is zero or not finite (1-based; the first such index)", (long long)bad + 1);
-        return otmb_fail(ctx, OTMB_ERR_SINGULAR_PRECONDITIONER, msg);
-    }
+    if ((rc = sv_precond_setup(op, w, adjoint, precond, d, sigma))) return rc;
     // ‖b‖, the start, its true residual
     op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
         hipLaunchKernelGGL((sv_bnorm_kernel<decltype(kb)::value>), grid, block, 0, st, n, B + c0 * ldb, ldb, w.part + 2 * c0 * np, np);
@@ -529,15 +565,21 @@ int32_t otmb_op_solve_dev(otmb_op *op, int32_t adjoint, int64_t k, const double 
         const i64 batch = std::min<i64>(SV_POLL, maxiter - done);
         for (i64 it = 0; it < batch; ++it) {
             op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
-                hipLaunchKernelGGL((sv_p_kernel<decltype(kb)::value>), grid, block, 0, st, (const SvCol *)w.cs + c0, n, (const double *)w.diag,
-                                   (const double *)w.r + c0 * n, w.rh + c0 * n, w.p + c0 * n, (const double *)w.v + c0 * n, w.ph + c0 * n);
+                constexpr int KB = decltype(kb)::value;
+                hipLaunchKernelGGL((lines ? sv_p_kernel<KB, true> : sv_p_kernel<KB, false>), grid, block, 0, st, (const SvCol *)w.cs + c0, n,
+                                   (const double *)w.diag, (const double *)w.r + c0 * n, w.rh + c0 * n, w.p + c0 * n, (const double *)w.v + c0 * n,
+                                   w.ph + c0 * n);
             });
+            if (lines) ln_sweep(op, w.cs, k, w.m, w.u, w.piv, w.p, n, w.ph, n);
             sv_apply<0>(op, w, adjoint, k, SV_ACTIVE, w.ph, n, w.rh, n, w.v, n);
             sv_scalar(op, w, k, SV_S_ALPHA, nbm, rtol, maxiter);
             op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
-                hipLaunchKernelGGL((sv_s_kernel<decltype(kb)::value>), grid, block, 0, st, (const SvCol *)w.cs + c0, n, (const double *)w.diag,
-                                   (const double *)w.r + c0 * n, (const double *)w.v + c0 * n, w.s + c0 * n, w.sh_ + c0 * n, w.parts + c0 * np, np);
+                constexpr int KB = decltype(kb)::value;
+                hipLaunchKernelGGL((lines ? sv_s_kernel<KB, true> : sv_s_kernel<KB, false>), grid, block, 0, st, (const SvCol *)w.cs + c0, n,
+                                   (const double *)w.diag, (const double *)w.r + c0 * n, (const double *)w.v + c0 * n, w.s + c0 * n, w.sh_ + c0 * n,
+                                   w.parts + c0 * np, np);
             });
+            if (lines) ln_sweep(op, w.cs, k, w.m, w.u, w.piv, w.s, n, w.sh_, n);
             sv_apply<1>(op, w, adjoint, k, SV_ACTIVE, w.sh_, n, w.s, n, w.t, n);
             sv_scalar(op, w, k, SV_S_OMEGA, nbm, rtol, maxiter);
             op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
@@ -571,11 +613,12 @@ int32_t otmb_op_solve_dev(otmb_op *op, int32_t adjoint, int64_t k, const double 
     return OTMB_OK;
 }
 
-int32_t otmb_op_solve(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X, int64_t ldx,
-                      int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason) {
+int32_t otmb_op_solve_pc(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X, int64_t ldx,
+                         int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason, int32_t precond) {
     if (!op) return OTMB_ERR_INVALID_ARG;
     int32_t rc;
     if ((rc = sv_check(op, k, B, ldb, X, ldx, rtol, maxiter, iters, relres, reason))) return rc;
+    if ((rc = sv_check_precond(op, precond))) return rc;
     otmb_ctx *ctx = op->ctx;
     HIP_TRY(ctx, hipSetDevice(op->device));
     const i64 n = op->n;
@@ -591,7 +634,7 @@ int32_t otmb_op_solve(otmb_op *op, int32_t adjoint, int64_t k, const double *d, 
             ctx->uploaded_bytes += 8 * n;
         }
     }
-    rc = otmb_op_solve_dev(op, adjoint, k, dd, sigma, db, n, dx, n, use_x0, rtol, maxiter, iters, relres, reason);
+    rc = otmb_op_solve_pc_dev(op, adjoint, k, dd, sigma, db, n, dx, n, use_x0, rtol, maxiter, iters, relres, reason, precond);
     if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED) return rc;
     const std::string msg = ctx->err;  // (HIP_TRY below would replace the solver's message)
     int32_t rcd;
@@ -599,6 +642,77 @@ int32_t otmb_op_solve(otmb_op *op, int32_t adjoint, int64_t k, const double *d, 
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->err = msg;
     return rc;
+}
+
+int32_t otmb_op_solve_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X, int64_t ldx,
+                          int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason) {
+    return otmb_op_solve_pc_dev(op, adjoint, k, d, sigma, B, ldb, X, ldx, use_x0, rtol, maxiter, iters, relres, reason, OTMB_PRECOND_JACOBI);
+}
+
+int32_t otmb_op_solve(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X, int64_t ldx,
+                      int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason) {
+    return otmb_op_solve_pc(op, adjoint, k, d, sigma, B, ldb, X, ldx, use_x0, rtol, maxiter, iters, relres, reason, OTMB_PRECOND_JACOBI);
+}
+
+// Z = P⁻¹·Y: the preconditioner of otmb_op_solve_pc on its own
+static int32_t sv_check_apply(otmb_op *op, int32_t precond, int64_t k, const double *Y, int64_t ldy, double *Z, int64_t ldz) {
+    otmb_ctx *ctx = op->ctx;
+    if (op->m != op->n) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "precond: the operator's matrix must be square");
+    if (k < 1 || k >= (1ll << 31)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "k (columns) must be >= 1");
+    if (ldy < op->n || ldy < 0) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "ldy is smaller than the rows of Y");
+    if (ldz < op->n || ldz < 0) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "ldz is smaller than the rows of Z");
+    if (op->n > 0 && (!Y || !Z)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
+    return sv_check_precond(op, precond);
+}
+
+int32_t otmb_op_precond_dev(otmb_op *op, int32_t adjoint, int32_t precond, int64_t k, const double *d, double sigma, const double *Y, int64_t ldy,
+                            double *Z, int64_t ldz) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    int32_t rc;
+    if ((rc = sv_check_apply(op, precond, k, Y, ldy, Z, ldz))) return rc;
+    otmb_ctx *ctx = op->ctx;
+    const i64 n = op->n;
+    if (n == 0) return OTMB_OK;
+    HIP_TRY(ctx, hipSetDevice(op->device));
+    if ((rc = otmb_reserve(ctx, op->sw, 5 * (size_t)n * 8 + 64))) return rc;
+    SvWork w = {};
+    double *q = (double *)op->sw.p;
+    for (double **v : {&w.sh, &w.diag, &w.m, &w.u, &w.piv}) { *v = q; q += n; }
+    w.bad = (unsigned long long *)q;
+    if ((rc = sv_precond_setup(op, w, adjoint, precond, d, sigma))) return rc;
+    if (precond == OTMB_PRECOND_LINES)
+        ln_sweep(op, nullptr, k, w.m, w.u, w.piv, Y, ldy, Z, ldz);
+    else
+        op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
+            hipLaunchKernelGGL((sv_scale_kernel<decltype(kb)::value>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n,
+                               (const double *)w.diag, Y + c0 * ldy, ldy, Z + c0 * ldz, ldz);
+        });
+    HIP_TRY(ctx, hipGetLastError());
+    return OTMB_OK;
+}
+
+int32_t otmb_op_precond(otmb_op *op, int32_t adjoint, int32_t precond, int64_t k, const double *d, double sigma, const double *Y, int64_t ldy, double *Z,
+                        int64_t ldz) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    int32_t rc;
+    if ((rc = sv_check_apply(op, precond, k, Y, ldy, Z, ldz))) return rc;
+    otmb_ctx *ctx = op->ctx;
+    const i64 n = op->n;
+    if (n == 0) return OTMB_OK;
+    HIP_TRY(ctx, hipSetDevice(op->device));
+    if ((rc = otmb_reserve(ctx, op->xs, (size_t)(n * k) * 8 + 8))) return rc;
+    if ((rc = otmb_reserve(ctx, op->ys, (size_t)(n * k) * 8 + 8))) return rc;
+    if ((rc = otmb_reserve(ctx, op->ds, (size_t)n * 8 + 8))) return rc;
+    double *dy = (double *)op->xs.p, *dz = (double *)op->ys.p, *dd = d ? (double *)op->ds.p : nullptr;
+    if ((rc = op_upload(ctx, dy, Y, ldy, n, k))) return rc;
+    if (d) {
+        HIP_TRY(ctx, hipMemcpyAsync(dd, d, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+        ctx->uploaded_bytes += 8 * n;
+    }
+    if ((rc = otmb_op_precond_dev(op, adjoint, precond, k, dd, sigma, dy, n, dz, n))) return rc;
+    if ((rc = op_download(ctx, Z, ldz, dz, n, k))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return OTMB_OK;
 }
 
 }  // extern "C"

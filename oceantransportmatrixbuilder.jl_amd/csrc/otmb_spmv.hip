@@ -192,7 +192,7 @@ static void sp_free(DevBuf &b) {
     b.cap = 0;
 }
 static void sp_free_all(otmb_op *op) {
-    for (DevBuf *b : {&op->cp, &op->rv, &op->nz, &op->dst, &op->elen, &op->sbase, &op->loff, &op->lrows, &op->val, &op->col, &op->xs, &op->ys, &op->ds, &op->sw})
+    for (DevBuf *b : {&op->cp, &op->rv, &op->nz, &op->dst, &op->elen, &op->sbase, &op->loff, &op->lrows, &op->val, &op->col, &op->xs, &op->ys, &op->ds, &op->sw, &op->ln})
         sp_free(*b);
 }
 

@@ -98,14 +98,56 @@ class Operator:
             Y.copy_(Yc)
         return Y
 
-    def solve(self, B, d=None, sigma=0.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False):
-        """X with (σ·I + diag(d) + A)·X = B (adjoint: ... + Aᵀ) on device tensors (otmb_op_solve_dev; api.DeviceOperator.solve states the
+    def set_lines(self, next):
+        """The lines of the "lines" preconditioner (otmb_op_set_lines_dev): a contiguous int64 device tensor of n entries, next[i] the 1-based
+        successor of unknown i + 1 on its line or 0; None clears them.  Copied: the tensor may go afterwards."""
+        if not self._h.value:
+            raise ValueError("operator is closed")
+        if next is None:
+            self.ctx.check(self.lib.otmb_op_set_lines_dev(self._h, None))
+            return
+        _on_device(next, self.device, "next")
+        if next.dtype != torch.int64 or tuple(next.shape) != (self.shape[1],):
+            raise capi.OtmbError(11, f"DimensionMismatch: next must be {self.shape[1]} int64 values")
+        next = next.contiguous()
+        self.ctx.check(self.lib.otmb_op_set_lines_dev(self._h, next.data_ptr()))
+
+    def _d_ptr(self, d):
+        if d is None:
+            return None, None
+        _on_device(d, self.device, "d")
+        if d.dtype != torch.float64 or tuple(d.shape) != (self.shape[1],):
+            raise capi.OtmbError(11, f"DimensionMismatch: d must be {self.shape[1]} float64 values")
+        d = d.contiguous()
+        return d, d.data_ptr()
+
+    def precondition(self, Y, d=None, sigma=0.0, adjoint=False, precond="lines"):
+        """Z = P⁻¹·Y on device tensors (otmb_op_precond_dev; api.DeviceOperator.precondition).  Returns a new tensor of Y's shape."""
+        if not self._h.value:
+            raise ValueError("operator is closed")
+        pc = capi.precond_code(precond)
+        _on_device(Y, self.device, "Y")
+        m, n = self.shape
+        if Y.dim() not in (1, 2) or Y.shape[0] != m:
+            raise capi.OtmbError(11, f"DimensionMismatch: operator of {(m, n)}, Y of {tuple(Y.shape)}")
+        k = 1 if Y.dim() == 1 else Y.shape[1]
+        Yc, ldy = _col_major(Y, m)
+        Z = torch.zeros(m, dtype=torch.float64, device=Y.device) if Y.dim() == 1 else \
+            torch.zeros(k * max(m, 1), dtype=torch.float64, device=Y.device).as_strided((m, k), (1, max(m, 1)))
+        d, dp = self._d_ptr(d)
+        self.ctx.check(self.lib.otmb_op_precond_dev(self._h, int(bool(adjoint)), pc, k, dp, float(sigma), Yc.data_ptr(), ldy, Z.data_ptr(), max(m, 1)))
+        return Z
+
+    def solve(self, B, d=None, sigma=0.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False, precond="jacobi"):
+        """X with (σ·I + diag(d) + A)·X = B (adjoint: ... + Aᵀ) on device tensors (otmb_op_solve_pc_dev; api.DeviceOperator.solve states the
         contract).  B: 1-D or 2-D (n x k, column-major) float64 device tensor; d: None or a device tensor of n values; x0: None or a tensor of
-        B's shape (not modified).  Returns (X, info): X a new device tensor, info an api.SolveInfo (the call waits for the device to read it)."""
+        B's shape (not modified); precond: "jacobi" or "lines" (set_lines first).  Returns (X, info): X a new device tensor, info an
+        api.SolveInfo (the call waits for the device to read it)."""
         from .api import SolveInfo
 
         if not self._h.value:
             raise ValueError("operator is closed")
+        pc = capi.precond_code(precond)
         _on_device(B, self.device, "B")
         m, n = self.shape
         if B.dim() not in (1, 2) or B.shape[0] != m:
@@ -119,16 +161,11 @@ class Operator:
             if tuple(x0.shape) != tuple(B.shape):
                 raise capi.OtmbError(11, f"DimensionMismatch: x0 of {tuple(x0.shape)}, B of {tuple(B.shape)}")
             X.copy_(x0)
-        dp = None
-        if d is not None:
-            _on_device(d, self.device, "d")
-            if d.dtype != torch.float64 or tuple(d.shape) != (n,):
-                raise capi.OtmbError(11, f"DimensionMismatch: d must be {n} float64 values")
-            d = d.contiguous()
-            dp = d.data_ptr()
+        d, dp = self._d_ptr(d)
         iters, relres, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
-        rc = self.lib.otmb_op_solve_dev(self._h, int(bool(adjoint)), k, dp, float(sigma), Bc.data_ptr(), ldb, X.data_ptr(), max(m, 1),
-                                        int(x0 is not None), float(rtol), int(maxiter), iters.ctypes.data, relres.ctypes.data, reason.ctypes.data)
+        rc = self.lib.otmb_op_solve_pc_dev(self._h, int(bool(adjoint)), k, dp, float(sigma), Bc.data_ptr(), ldb, X.data_ptr(), max(m, 1),
+                                           int(x0 is not None), float(rtol), int(maxiter), iters.ctypes.data, relres.ctypes.data,
+                                           reason.ctypes.data, pc)
         if rc != capi.NOT_CONVERGED:
             self.ctx.check(rc)
         return X, SolveInfo(rc, iters, relres, reason)
@@ -635,20 +672,32 @@ class DeviceAssembler:
         if rec is not None:
             rec["op"].close()
         op = Operator(self.ctx, self.N, self.N, cp, rv, nz)
+        op.set_lines(self.vertical_lines())
         self._ops[matrix] = {"op": op, "refs": [weakref.ref(t) for t in (cp, rv, nz)], "key": key, "nzv": (nz.data_ptr(), nz._version),
                              "ok": True, "dirty": False}
         self.op_replans = getattr(self, "op_replans", 0) + 1
         return op
+
+    def vertical_lines(self):
+        """The water columns of this grid as the `next` tensor of Operator.set_lines (api.vertical_lines on the resident indices, with torch
+        ops): the wet rank of the cell below, where both are wet, else 0."""
+        lw = self.lwet3d.view(self.nz, self.nx * self.ny)  # (level, horizontal cell) of Julia's column-major (nx, ny, nz)
+        up, dn = lw[:-1].reshape(-1), lw[1:].reshape(-1)
+        both = (up > 0) & (dn > 0)
+        nxt = torch.zeros(self.N, dtype=torch.int64, device=self.device)
+        nxt[up[both] - 1] = dn[both]
+        return nxt
 
     def mul(self, matrix, X, *, alpha=1.0, beta=0.0, Y=None, adjoint=False):
         """Y = α·M·X + β·Y (adjoint: α·Mᵀ·X + β·Y) with M the resident result `matrix`, on torch device tensors (1-D, or rows x k
         column-major), bit for bit SparseArrays' mul!; no host round trip (besides folding pending asynchronous steps)."""
         return self.operator(matrix).mul(X, alpha=alpha, beta=beta, Y=Y, adjoint=adjoint)
 
-    def solve(self, matrix, B, d=None, sigma=0.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False):
-        """X with (σ·I + diag(d) + M)·X = B (adjoint: ... + Mᵀ), M the resident result `matrix`, on torch device tensors: Jacobi-BiCGStab on
-        the resident operator (Operator.solve).  Returns (X, info)."""
-        return self.operator(matrix).solve(B, d=d, sigma=sigma, rtol=rtol, maxiter=maxiter, x0=x0, adjoint=adjoint)
+    def solve(self, matrix, B, d=None, sigma=0.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False, precond="jacobi"):
+        """X with (σ·I + diag(d) + M)·X = B (adjoint: ... + Mᵀ), M the resident result `matrix`, on torch device tensors: BiCGStab on the
+        resident operator (Operator.solve), preconditioned by Jacobi or, precond="lines", by the grid's water columns (operator() sets them).
+        Returns (X, info)."""
+        return self.operator(matrix).solve(B, d=d, sigma=sigma, rtol=rtol, maxiter=maxiter, x0=x0, adjoint=adjoint, precond=precond)
 
     def _kept_steady(self):
         """The operators a step of this loop does not store: those the last call kept, or -- after a full write that left the promise live -- those

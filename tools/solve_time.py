@@ -1,11 +1,18 @@
 """Time the device solver (otmb_op_solve_dev, csrc/otmb_solve.hip) on the 1 degree preset; one JSON line per measurement.
 
-    python tools/solve_time.py [--reps 10] [--maxiter 20000] [--host] [--out FILE.jsonl]
+    python tools/solve_time.py [--reps 10] [--maxiter 20000] [--precond jacobi|lines|both] [--year] [--host] [--out FILE.jsonl]
 
 Systems (B = 1, rtol = 1e-10):
     age      d = 1 s⁻¹ on the level-1 wet cells, σ = 0, on the full T and on the 2 x 2 x 1 coarse operator LUMP * T * SPRAY with
              d_c = (LUMP * issrf .> 0), b_c = LUMP * 1 (the reference's own case, test/local_full.jl:151-188)
     month    σ = 1 / (30 d), d = 0, on T
+    year     σ = 1 / (365 d), d = 0, on T (--year; with Jacobi it runs into --maxiter)
+--precond: the preconditioner(s) to time.  lines: the water columns (DeviceAssembler.vertical_lines) on T; on the coarse operator the
+    fine columns seen through LUMP (a coarse cell's successor is the coarse cell of a fine successor: the first such pair per cell, and per
+    successor -- an ARBITRARY choice among the candidates, not a tuned coarse preconditioner: the record says so in lines_note).
+    A lines record also has setup_plus_one_sweep_us: one otmb_op_precond_dev call with k = 1, i.e. diagonal, extraction, factorisation, ONE
+    sweep and one wait for the device -- an upper bound of the extraction plus factorisation a solve pays once; with --precond both the
+    line after it estimates the sweep as half the difference of the two per-iteration times and subtracts it (setup_estimate_us).
 Each line: iterations, reason, relres, the median / min / max wall time of --reps solves after one warm-up (time.perf_counter around the
 call, which waits for the device), the time per iteration, and the time of two otmb_op_mul_dev products on the same operator (HIP events):
 the floor of an iteration, whose five vector passes and scalar kernels the fusion is to keep small.
@@ -53,6 +60,8 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--maxiter", type=int, default=20000)
     ap.add_argument("--host", action="store_true")
+    ap.add_argument("--precond", default="jacobi", choices=["jacobi", "lines", "both"])
+    ap.add_argument("--year", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import scipy.sparse as sp
@@ -82,26 +91,64 @@ def main():
     S = api.SparseMatrixCSC(N, Nc, S.colptr, S.rowval, S.nzval)
     Tc = api.coarsen(L, T, S)
     Ls = sp.csc_matrix((L.nzval, L.rowval - 1, L.colptr - 1), shape=(Nc, N))
-    cases = [("age, coarse 2x2x1", Tc, Nc, (Ls @ issrf > 0).astype(np.float64), 0.0, Ls @ np.ones(N)),
-             ("age, T", T, N, issrf, 0.0, np.ones(N)),
-             ("month, T", T, N, None, 1.0 / (30 * DAY), np.ones(N))]
+    nxt = asm.vertical_lines()
+    # the coarse operator's lines: the fine columns through LUMP (one entry per column of LUMP: rowval = the coarse cell of a fine cell)
+    fine = nxt.cpu().numpy()
+    i = np.flatnonzero(fine)
+    ci, cj = L.rowval[i], L.rowval[fine[i] - 1]
+    keep = cj > ci
+    ci, cj = ci[keep], cj[keep]
+    order = np.lexsort((cj, ci))
+    ci, cj = ci[order], cj[order]
+    first = np.r_[True, ci[1:] != ci[:-1]]  # one successor per coarse cell
+    ci, cj = ci[first], cj[first]
+    order = np.lexsort((ci, cj))
+    ci, cj = ci[order], cj[order]
+    first = np.r_[True, cj[1:] != cj[:-1]]  # nobody is the successor of two
+    nxt_c = np.zeros(Nc, dtype=np.int64)
+    nxt_c[ci[first] - 1] = cj[first]
+    cases = [("age, coarse 2x2x1", Tc, Nc, (Ls @ issrf > 0).astype(np.float64), 0.0, Ls @ np.ones(N), torch.from_numpy(nxt_c).cuda()),
+             ("age, T", T, N, issrf, 0.0, np.ones(N), nxt),
+             ("month, T", T, N, None, 1.0 / (30 * DAY), np.ones(N), nxt)]
+    if a.year:
+        cases.append(("year, T", T, N, None, 1.0 / (365 * DAY), np.ones(N), nxt))
+    preconds = ["jacobi", "lines"] if a.precond == "both" else [a.precond]
     lines = []
-    for what, A, n, d, sigma, b in cases:
+    for (what, A, n, d, sigma, b, nx), precond in ((c, p) for c in cases for p in preconds):
         cp, rv, nz = (torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (A.colptr, A.rowval, A.nzval))
         op = Operator(asm.ctx, n, n, cp, rv, nz)
         bd = torch.from_numpy(b).cuda()
         dd = None if d is None else torch.from_numpy(d).cuda()
+        if precond == "lines":
+            op.set_lines(nx)
         times = []
         for rep in range(a.reps + 1):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            X, info = op.solve(bd, d=dd, sigma=sigma, rtol=1e-10, maxiter=a.maxiter)
+            X, info = op.solve(bd, d=dd, sigma=sigma, rtol=1e-10, maxiter=a.maxiter, precond=precond)
             times.append(time.perf_counter() - t0)
         times = times[1:]
         its = int(info.iterations[0])
-        rec = {"what": what, "n": n, "nnz": int(op.nnz), "iterations": its, "reason": info.reason[0], "relres": float(info.relres[0]),
+        rec = {"what": what, "precond": precond, "n": n, "nnz": int(op.nnz), "iterations": its, "reason": info.reason[0],
+               "relres": float(info.relres[0]),
                "median_s": float(np.median(times)), "min_s": float(np.min(times)), "max_s": float(np.max(times)), "reps": a.reps,
                "per_iteration_us": float(np.median(times)) / max(its, 1) * 1e6, "two_products_us": two_products(op, n) * 1e6}
+        if precond == "lines":
+            tp = []
+            for rep in range(a.reps + 1):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                op.precondition(bd, d=dd, sigma=sigma)
+                torch.cuda.synchronize()
+                tp.append(time.perf_counter() - t0)
+            links = int(np.count_nonzero(nx.cpu().numpy()))
+            rec.update(lines=n - links, links=links, setup_plus_one_sweep_us=float(np.median(tp[1:])) * 1e6)
+            if nx is not nxt:
+                rec["lines_note"] = "coarse lines: the fine water columns through LUMP, the first successor per coarse cell (arbitrary)"
+            jac = [r for r in lines if r["what"] == what and r["precond"] == "jacobi"]
+            if jac:
+                sweep = (rec["per_iteration_us"] - jac[0]["per_iteration_us"]) / 2
+                rec.update(sweep_estimate_us=sweep, setup_estimate_us=rec["setup_plus_one_sweep_us"] - sweep)
         if a.host:
             t0 = time.perf_counter()
             M = (sp.diags(np.full(n, sigma) + (0.0 if d is None else d)) + sp.csc_matrix((A.nzval, A.rowval - 1, A.colptr - 1), shape=(n, n))).tocsr()
