@@ -360,18 +360,19 @@ function setvalues!(D::DeviceOperator, nzval::Vector{Float64})
     return D
 end
 
-# (σ·I + Diagonal(d) + A) \ B on the resident operator (otmb_op_solve: Jacobi-preconditioned BiCGStab on the device; include/otmb.h states
+# (σ·I + Diagonal(d) + A) \ B on the resident operator (otmb_op_solve_pc: preconditioned BiCGStab on the device; include/otmb.h states
 # the method, the stop rules and what is deterministic) -- `D'` solves with Aᵀ.  X holds the start when `x0 = true` and the solution
 # afterwards.  Returns (X, info): info.iterations, info.relres, info.reason (:converged, :maxiter, :breakdown, :nonfinite) and
 # info.converged, one entry per column of B.  A column that does not converge is REPORTED, not thrown (status 19): X then holds its last
 # iterate.  Argument errors throw ArgumentError; a zero or non-finite entry of the diagonal throws an ErrorException that names it.
 const SOLVE_REASONS = (:converged, :maxiter, :breakdown, :nonfinite)   # otmb_solve_reason
-# the checks and leading dimensions solve! and solvepc! share: (k, ldb, ldx)
-function solvedims(X, op::DeviceOperator, B, d)
+# the checks and leading dimensions solve! (B, X) and precondition! (Y, Z) share: (k, ld of the input, ld of the result)
+function systemdims(op::DeviceOperator, B, bname, X, xname, d)
     n = op.n
-    (size(B, 1) == n && size(X, 1) == n && size(X, 2) == size(B, 2)) || throw(DimensionMismatch("operator of $((op.m, op.n)), B $(size(B)), X $(size(X))"))
+    (size(B, 1) == n && size(X, 1) == n && size(X, 2) == size(B, 2)) ||
+        throw(DimensionMismatch("operator of $((op.m, op.n)), $bname $(size(B)), $xname $(size(X))"))
     (d === nothing || length(d) == n) || throw(DimensionMismatch("d has $(length(d)) values, expected $n"))
-    (stride(X, 1) == 1 && stride(B, 1) == 1) || throw(ArgumentError("X and B need contiguous columns"))
+    (stride(X, 1) == 1 && stride(B, 1) == 1) || throw(ArgumentError("$xname and $bname need contiguous columns"))
     k = size(B, 2)
     ldb = B isa AbstractVector || k <= 1 ? max(n, 1) : stride(B, 2)
     ldx = X isa AbstractVector || k <= 1 ? max(n, 1) : stride(X, 2)
@@ -380,22 +381,21 @@ end
 function solve!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, B::StridedVecOrMat{Float64};
                 d::Union{Nothing,Vector{Float64}} = nothing, σ::Real = 0.0, rtol::Real = 1e-10, maxiter::Integer = 10000, x0::Bool = false,
                 precond::Symbol = :jacobi)
-    # precond = :lines (after setlines!): the water columns' tridiagonals instead of the diagonal, through otmb_op_solve_pc.  (The body
-    # below stays the plain otmb_op_solve call because tests/test_solve_shim_static.py pins it place by place; solvepc! shares solvedims.)
-    precond === :jacobi || return solvepc!(X, D, B, precond; d = d, σ = σ, rtol = rtol, maxiter = maxiter, x0 = x0)
+    # precond = :lines (after setlines!): the water columns' tridiagonals instead of the diagonal
+    pc = precondcode(precond)
     adjoint = D isa AdjointDeviceOperator
     op = adjoint ? D.parent : D
-    k, ldb, ldx = solvedims(X, op, B, d)
+    k, ldb, ldx = systemdims(op, B, "B", X, "X", d)
     iters = zeros(Int64, k)
     relres = zeros(Float64, k)
     reason = zeros(Int32, k)
     lock(CALL_LOCK) do
         op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
-        solve_fn = sym(:otmb_op_solve)
+        solve_fn = sym(:otmb_op_solve_pc)
         rc = ccall(solve_fn, Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Float64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int32, Float64, Int64,
-                Ptr{Int64}, Ptr{Float64}, Ptr{Int32}),
+                Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, Int32),
             op.handle, Int32(adjoint), k, d === nothing ? C_NULL : d, Float64(σ), B, ldb, X, ldx, Int32(x0), Float64(rtol), Int64(maxiter),
-            iters, relres, reason)
+            iters, relres, reason, pc)
         rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which column stopped why
     end
     why = [SOLVE_REASONS[r + 1] for r in reason]
@@ -432,40 +432,12 @@ function verticallines(indices)
     return next
 end
 
-function solvepc!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, B::StridedVecOrMat{Float64}, precond::Symbol;
-                  d::Union{Nothing,Vector{Float64}} = nothing, σ::Real = 0.0, rtol::Real = 1e-10, maxiter::Integer = 10000, x0::Bool = false)
-    pc = precondcode(precond)
-    adjoint = D isa AdjointDeviceOperator
-    op = adjoint ? D.parent : D
-    k, ldb, ldx = solvedims(X, op, B, d)
-    iters = zeros(Int64, k)
-    relres = zeros(Float64, k)
-    reason = zeros(Int32, k)
-    lock(CALL_LOCK) do
-        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
-        solve_pc_fn = sym(:otmb_op_solve_pc)
-        rc = ccall(solve_pc_fn, Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Float64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int32, Float64, Int64,
-                Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, Int32),
-            op.handle, Int32(adjoint), k, d === nothing ? C_NULL : d, Float64(σ), B, ldb, X, ldx, Int32(x0), Float64(rtol), Int64(maxiter),
-            iters, relres, reason, pc)
-        rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which column stopped why
-    end
-    why = [SOLVE_REASONS[r + 1] for r in reason]
-    return X, (iterations = iters, relres = relres, reason = why, converged = why .== :converged)
-end
-
 function precondition!(Z::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, Y::StridedVecOrMat{Float64};
                        d::Union{Nothing,Vector{Float64}} = nothing, σ::Real = 0.0, precond::Symbol = :lines)
     pc = precondcode(precond)
     adjoint = D isa AdjointDeviceOperator
     op = adjoint ? D.parent : D
-    n = op.n
-    (size(Y, 1) == n && size(Z, 1) == n && size(Z, 2) == size(Y, 2)) || throw(DimensionMismatch("operator of $((op.m, op.n)), Y $(size(Y)), Z $(size(Z))"))
-    (d === nothing || length(d) == n) || throw(DimensionMismatch("d has $(length(d)) values, expected $n"))
-    (stride(Z, 1) == 1 && stride(Y, 1) == 1) || throw(ArgumentError("Z and Y need contiguous columns"))
-    k = size(Y, 2)
-    ldy = Y isa AbstractVector || k <= 1 ? max(n, 1) : stride(Y, 2)
-    ldz = Z isa AbstractVector || k <= 1 ? max(n, 1) : stride(Z, 2)
+    k, ldy, ldz = systemdims(op, Y, "Y", Z, "Z", d)
     lock(CALL_LOCK) do
         op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
         precond_fn = sym(:otmb_op_precond)

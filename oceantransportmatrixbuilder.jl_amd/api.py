@@ -10,7 +10,6 @@ with ccall).  Arrays are numpy, Fortran-ordered, Julia shapes; indices stay 1-ba
                                                             src/matrixbuilding.jl:128-150
 """
 import ctypes as C
-import functools
 import os
 import threading
 
@@ -804,7 +803,7 @@ def _column_major(a):
 
 
 class SolveInfo:
-    """What otmb_op_solve reports, one entry per column of B: iterations (completed), relres (‖r‖₂/‖b‖₂ of the column's last residual
+    """What otmb_op_solve_pc reports, one entry per column of B: iterations (completed), relres (‖r‖₂/‖b‖₂ of the column's last residual
     evaluation: the explicitly computed b - M·x when it stopped on one, the recursive residual otherwise), reason ("converged", "maxiter",
     "breakdown", "nonfinite") and converged; status is the call's own (0, or capi.NOT_CONVERGED when some column is not converged)."""
 
@@ -832,17 +831,6 @@ def vertical_lines(indices):
     return nxt
 
 
-def _precond_keyword(solve):
-    """Gives DeviceOperator.solve its keyword precond = "jacobi" | "lines".  "jacobi" is the method as written below (otmb_op_solve,
-    whose call the Julia shim mirrors place by place); any other value goes to _solve_pc (otmb_op_solve_pc)."""
-    @functools.wraps(solve)
-    def with_precond(self, *args, precond="jacobi", **kwargs):
-        if precond == "jacobi":
-            return solve(self, *args, **kwargs)
-        return self._solve_pc(*args, precond=precond, **kwargs)
-    return with_precond
-
-
 class DeviceOperator:
     """A sparse operator resident on the device: Y = α·A·X + β·Y and Y = α·Aᵀ·X + β·Y, bit for bit SparseArrays' 5-argument mul! of
     Julia 1.10 -- what the reference's consumer checks compute (test/local_full.jl:96-107: norm(T * e1), norm(T' * v)) and what a tracer
@@ -855,8 +843,7 @@ class DeviceOperator:
       * no FMA; `A * x` and `A' * v` are α = 1.0, β = 0.0.
     A: a SparseMatrixCSC (1-based).  The operator owns device copies of A: the arrays may change or go once the constructor returns.
     The same C calls as the Julia shim's DeviceOperator: otmb_op_create; mul! -> otmb_op_mul; setvalues! -> otmb_op_set_values; solve! ->
-    otmb_op_solve (precond = :lines: otmb_op_solve_pc); setlines! -> otmb_op_set_lines; precondition! -> otmb_op_precond; the finalizer ->
-    otmb_op_destroy."""
+    otmb_op_solve_pc; setlines! -> otmb_op_set_lines; precondition! -> otmb_op_precond; the finalizer -> otmb_op_destroy."""
 
     def __init__(self, A, *, device=0):
         self._h = C.c_void_p()
@@ -937,31 +924,6 @@ class DeviceOperator:
                 raise capi.OtmbError(11, f"DimensionMismatch: d of {dc.shape}, expected {(n,)}")
         return k, Bc, ldb, dc
 
-    def _solve_args(self, B, d, x0):
-        """What solve and _solve_pc hand to the library besides the scalars: (B, k, B column-major, ldb, d, X holding the start or zeros)."""
-        B = np.asarray(B)
-        k, Bc, ldb, dc = self._system_args(B, d)
-        X = np.zeros(B.shape, dtype=np.float64, order="F")
-        if x0 is not None:
-            if np.shape(x0) != B.shape:
-                raise capi.OtmbError(11, f"DimensionMismatch: x0 of {np.shape(x0)}, B of {B.shape}")
-            X[...] = x0
-        return B, k, Bc, ldb, dc, X
-
-    def _solve_pc(self, B, d=None, sigma=0.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False, precond="lines"):
-        """solve() with the preconditioner named (otmb_op_solve_pc): "lines" needs set_lines first."""
-        self._live()
-        pc = capi.precond_code(precond)
-        B, k, Bc, ldb, dc, X = self._solve_args(B, d, x0)
-        iters, relres, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
-        lib = capi.lib()
-        rc = lib.otmb_op_solve_pc(self._h, int(bool(adjoint)), k, None if dc is None else dc.ctypes.data, float(sigma), Bc.ctypes.data, ldb,
-                                  X.ctypes.data, max(X.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), iters.ctypes.data,
-                                  relres.ctypes.data, reason.ctypes.data, pc)
-        if rc != capi.NOT_CONVERGED:
-            self.ctx.check(rc)
-        return X, SolveInfo(rc, iters, relres, reason)
-
     def precondition(self, Y, d=None, sigma=0.0, adjoint=False, precond="lines"):
         """Z = P⁻¹·Y with the preconditioner solve(..., precond=precond) uses for M = σ·I + diag(d) + A (adjoint: Aᵀ) (otmb_op_precond): for a
         Krylov method of the caller's own.  Y: 1-D or 2-D (n x k); returns Z of Y's shape (2-D: Fortran-ordered)."""
@@ -975,27 +937,30 @@ class DeviceOperator:
                                            ldy, Z.ctypes.data, max(Z.shape[0], 1)))
         return Z
 
-    @_precond_keyword
-    def solve(self, B, d=None, sigma=0.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False):
-        """X with (σ·I + diag(d) + A)·X = B (adjoint: ... + Aᵀ) by Jacobi-preconditioned BiCGStab on the device (otmb_op_solve,
-        include/otmb.h: the method, the stop rules, what is deterministic).  B: 1-D or 2-D (n x k); d: None (zero) or n values; x0: None (start
-        from zero) or an array of B's shape (not modified).  Returns (X, info): X of B's shape (2-D: Fortran-ordered), info a SolveInfo with one
-        entry per column.  A column that does not converge is REPORTED (info.converged, info.reason), not raised: X then holds its last iterate.
+    def solve(self, B, d=None, sigma=0.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False, precond="jacobi"):
+        """X with (σ·I + diag(d) + A)·X = B (adjoint: ... + Aᵀ) by preconditioned BiCGStab on the device (otmb_op_solve_pc, include/otmb.h:
+        the method, the stop rules, what is deterministic).  B: 1-D or 2-D (n x k); d: None (zero) or n values; x0: None (start from zero) or
+        an array of B's shape (not modified).  Returns (X, info): X of B's shape (2-D: Fortran-ordered), info a SolveInfo with one entry per
+        column.  A column that does not converge is REPORTED (info.converged, info.reason), not raised: X then holds its last iterate.
         Argument errors and a zero or non-finite diagonal (SINGULAR_PRECONDITIONER) raise OtmbError.
-        Keyword precond = "jacobi" (default) | "lines": the preconditioner; "lines" is P = M on the lines of set_lines (the water columns'
-        tridiagonals: far fewer iterations on time-stepping systems) and goes through otmb_op_solve_pc.  With "lines" only the pivots of
+        precond = "jacobi" (default) | "lines": the preconditioner; "lines" is P = M on the lines of set_lines (the water columns'
+        tridiagonals: far fewer iterations on time-stepping systems) and needs set_lines first.  With "lines" only the pivots of
         the line factorisation are checked, not the diagonal: a zero or non-finite diag(M) entry is then reported, if it makes a pivot
         singular, as that pivot ("pivot[i] ...") -- also when next is all zero, where the results are Jacobi's but the message is not."""
-        # (This method stays the plain Jacobi call, and the keyword lives in the decorator and _solve_pc, because
-        # tests/test_solve_shim_static.py pins this signature and this single C call against the Julia shim's solve!; the checks and
-        # the staging are shared with _solve_pc through _solve_args, so only the call itself exists twice.)
         self._live()
-        B, k, Bc, ldb, dc, X = self._solve_args(B, d, x0)
+        pc = capi.precond_code(precond)
+        B = np.asarray(B)
+        k, Bc, ldb, dc = self._system_args(B, d)
+        X = np.zeros(B.shape, dtype=np.float64, order="F")
+        if x0 is not None:
+            if np.shape(x0) != B.shape:
+                raise capi.OtmbError(11, f"DimensionMismatch: x0 of {np.shape(x0)}, B of {B.shape}")
+            X[...] = x0
         iters, relres, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
         lib = capi.lib()
-        rc = lib.otmb_op_solve(self._h, int(bool(adjoint)), k, None if dc is None else dc.ctypes.data, float(sigma), Bc.ctypes.data, ldb,
-                               X.ctypes.data, max(X.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), iters.ctypes.data,
-                               relres.ctypes.data, reason.ctypes.data)
+        rc = lib.otmb_op_solve_pc(self._h, int(bool(adjoint)), k, None if dc is None else dc.ctypes.data, float(sigma), Bc.ctypes.data, ldb,
+                                  X.ctypes.data, max(X.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), iters.ctypes.data,
+                                  relres.ctypes.data, reason.ctypes.data, pc)
         if rc != capi.NOT_CONVERGED:
             self.ctx.check(rc)
         return X, SolveInfo(rc, iters, relres, reason)

@@ -1,7 +1,8 @@
 // otmb_op.h -- the resident sparse operator's record and the host helpers shared by its products (otmb_spmv.hip) and its solver
-// (otmb_solve.hip): register blocks of columns, compact staging of host matrices.  The device walks over the layouts: otmb_op_fold.h.
+// (otmb_solve.hip): register blocks of columns, compact staging of host matrices and of d.  The device walks over the layouts: otmb_op_fold.h.
 // The layouts are described at the head of otmb_spmv.hip, which builds them and owns every buffer (sp_free_all).
 #pragma once
+#include <algorithm>
 #include <type_traits>
 
 #include "otmb_common.h"
@@ -18,8 +19,8 @@ struct otmb_op {
     DevBuf dst;                           // per stored entry: its position in val / col
     DevBuf elen, sbase, loff, lrows;      // per row: length or -1 (long); per slice: first position; per row: long-row offset; long rows
     DevBuf val, col;                      // slices then long rows: values and column indices (Int32, 0-based)
-    DevBuf xs, ys;                        // staging of otmb_op_mul / otmb_op_solve (X and Y; B and X)
-    DevBuf ds, sw;                        // otmb_op_solve: staging of d; the solver's vectors, partial sums and per-column records
+    DevBuf xs, ys;                        // host entry points' staging (op_reserve_xy): otmb_op_mul X, Y; otmb_op_solve_pc B, X; otmb_op_precond Y, Z
+    DevBuf ds, sw;                        // staging of d (op_stage_d); the solver's arrays (SvWork, otmb_solve.hip): vectors, partial sums, column records
     DevBuf ln;                            // otmb_op_set_lines (Int32, 0-based, -1 = none): successor (n), predecessor (n), line heads ascending (nheads)
     i64 nheads = 0;
     bool lines = false;                   // lines are set (they belong to the pattern: otmb_op_set_values keeps them)
@@ -42,5 +43,23 @@ static int32_t op_upload(otmb_ctx *ctx, double *dev, const double *host, i64 ld,
 }
 static int32_t op_download(otmb_ctx *ctx, double *host, i64 ld, const double *dev, i64 rows, i64 k) {
     HIP_TRY(ctx, hipMemcpy2DAsync(host, (size_t)ld * 8, dev, (size_t)rows * 8, (size_t)rows * 8, (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
+    return OTMB_OK;
+}
+// xs and ys for staged matrices of rx x k and ry x k (never empty buffers)
+static int32_t op_reserve_xy(otmb_op *op, i64 rx, i64 ry, i64 k) {
+    int32_t rc;
+    if ((rc = otmb_reserve(op->ctx, op->xs, std::max<size_t>((size_t)(rx * k) * 8, 8)))) return rc;
+    return otmb_reserve(op->ctx, op->ys, std::max<size_t>((size_t)(ry * k) * 8, 8));
+}
+// An optional d (n host values) staged in ds: dev is its device copy, or null when there is none
+static int32_t op_stage_d(otmb_op *op, const double *d, double *&dev) {
+    otmb_ctx *ctx = op->ctx;
+    int32_t rc;
+    if ((rc = otmb_reserve(ctx, op->ds, (size_t)op->n * 8 + 8))) return rc;
+    dev = d ? (double *)op->ds.p : nullptr;
+    if (d && op->n > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(dev, d, (size_t)op->n * 8, hipMemcpyHostToDevice, ctx->stream));
+        ctx->uploaded_bytes += 8 * op->n;
+    }
     return OTMB_OK;
 }

@@ -1,5 +1,7 @@
-// otmb_solve.hip -- (σ·I + diag(d) + A)·X = B and (σ·I + diag(d) + Aᵀ)·X = B on a resident operator (otmb_op_solve[_dev]): BiCGStab,
-// right-preconditioned with P = diag(M) (Jacobi).  The reference's use: Γ_c = (T_c + M_c) \ (LUMP * ones(N)), test/local_full.jl:151-188.
+// otmb_solve.hip -- (σ·I + diag(d) + A)·X = B and (σ·I + diag(d) + Aᵀ)·X = B on a resident operator: BiCGStab, right-preconditioned with
+// P = diag(M) (Jacobi) or with M's part on the operator's lines.  The reference's use: Γ_c = (T_c + M_c) \ (LUMP * ones(N)),
+// test/local_full.jl:151-188.  Entry points: otmb_op_solve_pc[_dev], the preconditioner its last argument (otmb_op_solve[_dev] are this call
+// with OTMB_PRECOND_JACOBI), and otmb_op_precond[_dev], P⁻¹ alone; the host variants stage B, X and d (otmb_op.h) around the _dev ones.
 //
 // Per column (k columns advance together, every one with its own scalars; a stopped column is frozen: nothing of it is written again):
 //     r = b - M·x (x = x0 or 0), r̂ = r, ρ = r̂·r, restart
@@ -32,10 +34,11 @@
 //
 // otmb_op_solve_pc with OTMB_PRECOND_LINES: P is the part of M on the operator's lines (otmb_op_set_lines; otmb_solve_lines.hip states the
 // factorisation and the sweep).  Kernels 1 and 3 then leave p̂ and ŝ to a line sweep launched after them (p̂ = P⁻¹·p, ŝ = P⁻¹·s); ‖s‖² still
-// comes from kernel 3's own grid.  Everything else, the Jacobi path's bits included, is as above.  otmb_op_precond applies either P⁻¹ alone.
+// comes from kernel 3's own grid.  Everything else, the Jacobi path's bits included, is as above.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 
 #include "otmb_op_fold.h"
@@ -409,6 +412,26 @@ struct SvWork {  // the solver's device arrays inside op->sw (m, u, piv: the lin
     unsigned long long *bad;  // [2]: the diagonal's, the pivots'
     i64 np;
 };
+// reserves op->sw and carves it for k columns with np partials each; k = 0: the preconditioner's arrays alone (otmb_op_precond_dev)
+static int32_t sv_work(otmb_op *op, bool lines, i64 k, i64 np, SvWork &w) {
+    const size_t n = (size_t)op->n, vec = n * (size_t)k, parts = (size_t)np * (size_t)k;
+    const size_t doubles = (lines ? 5 : 2) * n + 8 * vec + 3 * parts;
+    int32_t rc;
+    if ((rc = otmb_reserve(op->ctx, op->sw, doubles * 8 + (size_t)k * sizeof(SvCol) + 64))) return rc;
+    double *q = (double *)op->sw.p;
+    w.sh = q; q += n;
+    w.diag = q; q += n;
+    w.m = w.u = w.piv = nullptr;
+    if (lines)
+        for (double **v : {&w.m, &w.u, &w.piv}) { *v = q; q += n; }
+    for (double **v : {&w.r, &w.rh, &w.p, &w.v, &w.s, &w.t, &w.ph, &w.sh_}) { *v = q; q += vec; }
+    w.part = q; q += 2 * parts;
+    w.parts = q; q += parts;
+    w.bad = (unsigned long long *)q; q += 2;
+    w.cs = (SvCol *)q;
+    w.np = np;
+    return OTMB_OK;
+}
 
 // Z = Y ./ diag: the Jacobi preconditioner on its own (otmb_op_precond)
 template <int KB>
@@ -418,14 +441,6 @@ __global__ __launch_bounds__(256) void sv_scale_kernel(i64 n, const double *__re
     const double dg = diag[i];
 #pragma unroll
     for (int c = 0; c < KB; ++c) Z[i + c * ldz] = Y[i + c * ldy] / dg;
-}
-
-static int32_t sv_check_precond(otmb_op *op, int32_t precond) {
-    if (precond != OTMB_PRECOND_JACOBI && precond != OTMB_PRECOND_LINES)
-        return otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, "precond must be OTMB_PRECOND_JACOBI or OTMB_PRECOND_LINES");
-    if (precond == OTMB_PRECOND_LINES && !op->lines)
-        return otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, "OTMB_PRECOND_LINES needs lines: otmb_op_set_lines first");
-    return OTMB_OK;
 }
 
 // sh and diag and, with lines, u, the multipliers and the pivots; a singular preconditioner is refused here, before anything of the
@@ -489,18 +504,29 @@ static void sv_verify(otmb_op *op, const SvWork &w, int adjoint, i64 k, const do
     sv_scalar(op, w, k, SV_S_VERIFY, adjoint ? (n + 63) / 64 : (n + 255) / 256, rtol, maxiter);
 }
 
-static int32_t sv_check(otmb_op *op, int64_t k, const double *B, int64_t ldb, double *X, int64_t ldx, double rtol, int64_t maxiter, const int64_t *iters,
-                        const double *relres, const int32_t *reason) {
-    otmb_ctx *ctx = op->ctx;
-    if (op->m != op->n) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "solve: the operator's matrix must be square");
-    if (k < 1 || k >= (1ll << 31)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "k (right-hand sides) must be >= 1");
-    if (ldb < op->n || ldb < 0) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "ldb is smaller than the rows of B");
-    if (ldx < op->n || ldx < 0) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "ldx is smaller than the rows of X");
-    if (op->n > 0 && (!B || !X)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
-    if (!iters || !relres || !reason) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
-    if (!(rtol > 0.0)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "rtol must be > 0");
-    if (maxiter < 0) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "maxiter must be >= 0");
+// The argument checks of otmb_op_solve_pc[_dev] (sv_check) and otmb_op_precond[_dev] (sv_check_apply), in one order: the matrices Y (ldy) and
+// Z (ldz) named y and z, then `more`, the caller's first complaint about its other arguments (null: none), then the preconditioner.
+static int32_t sv_check_system(otmb_op *op, int32_t precond, const char *what, const char *cols, char y, char z, i64 k, const double *Y, i64 ldy,
+                               const double *Z, i64 ldz, const char *more) {
+    const auto fail = [&](const std::string &m) { return otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, m.c_str()); };
+    const auto small = [&](char c) { return fail(std::string("ld") + (char)tolower(c) + " is smaller than the rows of " + c); };
+    if (op->m != op->n) return fail(std::string(what) + ": the operator's matrix must be square");
+    if (k < 1 || k >= (1ll << 31)) return fail(std::string("k (") + cols + ") must be >= 1");
+    if (ldy < op->n || ldy < 0) return small(y);
+    if (ldz < op->n || ldz < 0) return small(z);
+    if (op->n > 0 && (!Y || !Z)) return fail("null argument");
+    if (more) return fail(more);
+    if (precond != OTMB_PRECOND_JACOBI && precond != OTMB_PRECOND_LINES) return fail("precond must be OTMB_PRECOND_JACOBI or OTMB_PRECOND_LINES");
+    if (precond == OTMB_PRECOND_LINES && !op->lines) return fail("OTMB_PRECOND_LINES needs lines: otmb_op_set_lines first");
     return OTMB_OK;
+}
+static int32_t sv_check(otmb_op *op, int32_t precond, int64_t k, const double *B, int64_t ldb, double *X, int64_t ldx, double rtol, int64_t maxiter,
+                        const int64_t *iters, const double *relres, const int32_t *reason) {
+    const char *more = !iters || !relres || !reason ? "null argument" : !(rtol > 0.0) ? "rtol must be > 0" : maxiter < 0 ? "maxiter must be >= 0" : nullptr;
+    return sv_check_system(op, precond, "solve", "right-hand sides", 'B', 'X', k, B, ldb, X, ldx, more);
+}
+static int32_t sv_check_apply(otmb_op *op, int32_t precond, int64_t k, const double *Y, int64_t ldy, double *Z, int64_t ldz) {
+    return sv_check_system(op, precond, "precond", "columns", 'Y', 'Z', k, Y, ldy, Z, ldz, nullptr);
 }
 
 extern "C" {
@@ -509,8 +535,7 @@ int32_t otmb_op_solve_pc_dev(otmb_op *op, int32_t adjoint, int64_t k, const doub
                              int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason, int32_t precond) {
     if (!op) return OTMB_ERR_INVALID_ARG;
     int32_t rc;
-    if ((rc = sv_check(op, k, B, ldb, X, ldx, rtol, maxiter, iters, relres, reason))) return rc;
-    if ((rc = sv_check_precond(op, precond))) return rc;
+    if ((rc = sv_check(op, precond, k, B, ldb, X, ldx, rtol, maxiter, iters, relres, reason))) return rc;
     const bool lines = precond == OTMB_PRECOND_LINES;
     otmb_ctx *ctx = op->ctx;
     const i64 n = op->n;
@@ -521,23 +546,8 @@ int32_t otmb_op_solve_pc_dev(otmb_op *op, int32_t adjoint, int64_t k, const doub
     HIP_TRY(ctx, hipSetDevice(op->device));
     hipStream_t st = ctx->stream;
     const i64 nb = (n + 255) / 256, np = (n + 63) / 64;  // partials per column and quantity: rows / vector kernels write nb, the adjoint's np
-    const size_t vec = (size_t)n * (size_t)k;
-    const size_t doubles = (lines ? 5 : 2) * (size_t)n + 8 * vec + 3 * (size_t)np * (size_t)k;
-    const size_t bytes = doubles * 8 + (size_t)k * sizeof(SvCol) + 64;
-    if ((rc = otmb_reserve(ctx, op->sw, bytes))) return rc;
     SvWork w;
-    double *q = (double *)op->sw.p;
-    w.sh = q; q += n;
-    w.diag = q; q += n;
-    w.m = w.u = w.piv = nullptr;
-    if (lines)
-        for (double **v : {&w.m, &w.u, &w.piv}) { *v = q; q += n; }
-    for (double **v : {&w.r, &w.rh, &w.p, &w.v, &w.s, &w.t, &w.ph, &w.sh_}) { *v = q; q += vec; }
-    w.part = q; q += 2 * (size_t)np * (size_t)k;
-    w.parts = q; q += (size_t)np * (size_t)k;
-    w.bad = (unsigned long long *)q; q += 2;
-    w.cs = (SvCol *)q;
-    w.np = np;
+    if ((rc = sv_work(op, lines, k, np, w))) return rc;
     const dim3 grid((unsigned)nb), block(256);
     // the preconditioner, checked before anything of X is touched
     if ((rc = sv_precond_setup(op, w, adjoint, precond, d, sigma))) return rc;
@@ -617,22 +627,16 @@ int32_t otmb_op_solve_pc(otmb_op *op, int32_t adjoint, int64_t k, const double *
                          int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason, int32_t precond) {
     if (!op) return OTMB_ERR_INVALID_ARG;
     int32_t rc;
-    if ((rc = sv_check(op, k, B, ldb, X, ldx, rtol, maxiter, iters, relres, reason))) return rc;
-    if ((rc = sv_check_precond(op, precond))) return rc;
+    if ((rc = sv_check(op, precond, k, B, ldb, X, ldx, rtol, maxiter, iters, relres, reason))) return rc;
     otmb_ctx *ctx = op->ctx;
     HIP_TRY(ctx, hipSetDevice(op->device));
     const i64 n = op->n;
-    if ((rc = otmb_reserve(ctx, op->xs, (size_t)(n * k) * 8 + 8))) return rc;
-    if ((rc = otmb_reserve(ctx, op->ys, (size_t)(n * k) * 8 + 8))) return rc;
-    if ((rc = otmb_reserve(ctx, op->ds, (size_t)n * 8 + 8))) return rc;
-    double *db = (double *)op->xs.p, *dx = (double *)op->ys.p, *dd = d ? (double *)op->ds.p : nullptr;
+    double *dd;
+    if ((rc = op_reserve_xy(op, n, n, k)) || (rc = op_stage_d(op, d, dd))) return rc;
+    double *db = (double *)op->xs.p, *dx = (double *)op->ys.p;
     if (n > 0) {
         if ((rc = op_upload(ctx, db, B, ldb, n, k))) return rc;
         if (use_x0 && (rc = op_upload(ctx, dx, X, ldx, n, k))) return rc;
-        if (d) {
-            HIP_TRY(ctx, hipMemcpyAsync(dd, d, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-            ctx->uploaded_bytes += 8 * n;
-        }
     }
     rc = otmb_op_solve_pc_dev(op, adjoint, k, dd, sigma, db, n, dx, n, use_x0, rtol, maxiter, iters, relres, reason, precond);
     if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED) return rc;
@@ -655,16 +659,6 @@ int32_t otmb_op_solve(otmb_op *op, int32_t adjoint, int64_t k, const double *d, 
 }
 
 // Z = P⁻¹·Y: the preconditioner of otmb_op_solve_pc on its own
-static int32_t sv_check_apply(otmb_op *op, int32_t precond, int64_t k, const double *Y, int64_t ldy, double *Z, int64_t ldz) {
-    otmb_ctx *ctx = op->ctx;
-    if (op->m != op->n) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "precond: the operator's matrix must be square");
-    if (k < 1 || k >= (1ll << 31)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "k (columns) must be >= 1");
-    if (ldy < op->n || ldy < 0) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "ldy is smaller than the rows of Y");
-    if (ldz < op->n || ldz < 0) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "ldz is smaller than the rows of Z");
-    if (op->n > 0 && (!Y || !Z)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
-    return sv_check_precond(op, precond);
-}
-
 int32_t otmb_op_precond_dev(otmb_op *op, int32_t adjoint, int32_t precond, int64_t k, const double *d, double sigma, const double *Y, int64_t ldy,
                             double *Z, int64_t ldz) {
     if (!op) return OTMB_ERR_INVALID_ARG;
@@ -674,11 +668,8 @@ int32_t otmb_op_precond_dev(otmb_op *op, int32_t adjoint, int32_t precond, int64
     const i64 n = op->n;
     if (n == 0) return OTMB_OK;
     HIP_TRY(ctx, hipSetDevice(op->device));
-    if ((rc = otmb_reserve(ctx, op->sw, 5 * (size_t)n * 8 + 64))) return rc;
-    SvWork w = {};
-    double *q = (double *)op->sw.p;
-    for (double **v : {&w.sh, &w.diag, &w.m, &w.u, &w.piv}) { *v = q; q += n; }
-    w.bad = (unsigned long long *)q;
+    SvWork w;
+    if ((rc = sv_work(op, precond == OTMB_PRECOND_LINES, 0, 0, w))) return rc;
     if ((rc = sv_precond_setup(op, w, adjoint, precond, d, sigma))) return rc;
     if (precond == OTMB_PRECOND_LINES)
         ln_sweep(op, nullptr, k, w.m, w.u, w.piv, Y, ldy, Z, ldz);
@@ -700,15 +691,10 @@ int32_t otmb_op_precond(otmb_op *op, int32_t adjoint, int32_t precond, int64_t k
     const i64 n = op->n;
     if (n == 0) return OTMB_OK;
     HIP_TRY(ctx, hipSetDevice(op->device));
-    if ((rc = otmb_reserve(ctx, op->xs, (size_t)(n * k) * 8 + 8))) return rc;
-    if ((rc = otmb_reserve(ctx, op->ys, (size_t)(n * k) * 8 + 8))) return rc;
-    if ((rc = otmb_reserve(ctx, op->ds, (size_t)n * 8 + 8))) return rc;
-    double *dy = (double *)op->xs.p, *dz = (double *)op->ys.p, *dd = d ? (double *)op->ds.p : nullptr;
+    double *dd;
+    if ((rc = op_reserve_xy(op, n, n, k)) || (rc = op_stage_d(op, d, dd))) return rc;
+    double *dy = (double *)op->xs.p, *dz = (double *)op->ys.p;
     if ((rc = op_upload(ctx, dy, Y, ldy, n, k))) return rc;
-    if (d) {
-        HIP_TRY(ctx, hipMemcpyAsync(dd, d, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        ctx->uploaded_bytes += 8 * n;
-    }
     if ((rc = otmb_op_precond_dev(op, adjoint, precond, k, dd, sigma, dy, n, dz, n))) return rc;
     if ((rc = op_download(ctx, Z, ldz, dz, n, k))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

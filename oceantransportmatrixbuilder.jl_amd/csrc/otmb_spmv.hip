@@ -442,8 +442,7 @@ int32_t otmb_op_mul(otmb_op *op, int32_t adjoint, int64_t k, const double *X, in
     otmb_ctx *ctx = op->ctx;
     HIP_TRY(ctx, hipSetDevice(op->device));
     const i64 rx = adjoint ? op->m : op->n, ry = adjoint ? op->n : op->m;
-    if ((rc = sp_reserve(op, op->xs, (size_t)(rx * k) * 8))) return rc;
-    if ((rc = sp_reserve(op, op->ys, (size_t)(ry * k) * 8))) return rc;
+    if ((rc = op_reserve_xy(op, rx, ry, k))) return rc;
     double *dx = (double *)op->xs.p, *dy = (double *)op->ys.p;
     if (rx > 0 && (rc = op_upload(ctx, dx, X, ldx, rx, k))) return rc;
     if (ry > 0 && beta != 0.0 && (rc = op_upload(ctx, dy, Y, ldy, ry, k))) return rc;  // (β == 0 discards Y)

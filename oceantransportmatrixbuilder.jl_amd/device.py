@@ -121,21 +121,28 @@ class Operator:
         d = d.contiguous()
         return d, d.data_ptr()
 
-    def precondition(self, Y, d=None, sigma=0.0, adjoint=False, precond="lines"):
-        """Z = P⁻¹·Y on device tensors (otmb_op_precond_dev; api.DeviceOperator.precondition).  Returns a new tensor of Y's shape."""
+    def _system(self, B, what, precond):
+        """What solve (B) and precondition (Y) share: the operator is open, precond is known, the tensor is on the device and has the operator's
+        rows.  Returns (precond's code, k, the tensor column-major, its leading dimension, a zeroed result of its shape, strides (1, max(m, 1)))."""
         if not self._h.value:
             raise ValueError("operator is closed")
         pc = capi.precond_code(precond)
-        _on_device(Y, self.device, "Y")
+        _on_device(B, self.device, what)
         m, n = self.shape
-        if Y.dim() not in (1, 2) or Y.shape[0] != m:
-            raise capi.OtmbError(11, f"DimensionMismatch: operator of {(m, n)}, Y of {tuple(Y.shape)}")
-        k = 1 if Y.dim() == 1 else Y.shape[1]
-        Yc, ldy = _col_major(Y, m)
-        Z = torch.zeros(m, dtype=torch.float64, device=Y.device) if Y.dim() == 1 else \
-            torch.zeros(k * max(m, 1), dtype=torch.float64, device=Y.device).as_strided((m, k), (1, max(m, 1)))
+        if B.dim() not in (1, 2) or B.shape[0] != m:
+            raise capi.OtmbError(11, f"DimensionMismatch: operator of {(m, n)}, {what} of {tuple(B.shape)}")
+        k = 1 if B.dim() == 1 else B.shape[1]
+        Bc, ldb = _col_major(B, m)
+        X = torch.zeros(m, dtype=torch.float64, device=B.device) if B.dim() == 1 else \
+            torch.zeros(k * max(m, 1), dtype=torch.float64, device=B.device).as_strided((m, k), (1, max(m, 1)))
+        return pc, k, Bc, ldb, X
+
+    def precondition(self, Y, d=None, sigma=0.0, adjoint=False, precond="lines"):
+        """Z = P⁻¹·Y on device tensors (otmb_op_precond_dev; api.DeviceOperator.precondition).  Returns a new tensor of Y's shape."""
+        pc, k, Yc, ldy, Z = self._system(Y, "Y", precond)
         d, dp = self._d_ptr(d)
-        self.ctx.check(self.lib.otmb_op_precond_dev(self._h, int(bool(adjoint)), pc, k, dp, float(sigma), Yc.data_ptr(), ldy, Z.data_ptr(), max(m, 1)))
+        self.ctx.check(self.lib.otmb_op_precond_dev(self._h, int(bool(adjoint)), pc, k, dp, float(sigma), Yc.data_ptr(), ldy, Z.data_ptr(),
+                                                    max(self.shape[0], 1)))
         return Z
 
     def solve(self, B, d=None, sigma=0.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False, precond="jacobi"):
@@ -145,17 +152,7 @@ class Operator:
         api.SolveInfo (the call waits for the device to read it)."""
         from .api import SolveInfo
 
-        if not self._h.value:
-            raise ValueError("operator is closed")
-        pc = capi.precond_code(precond)
-        _on_device(B, self.device, "B")
-        m, n = self.shape
-        if B.dim() not in (1, 2) or B.shape[0] != m:
-            raise capi.OtmbError(11, f"DimensionMismatch: operator of {(m, n)}, B of {tuple(B.shape)}")
-        k = 1 if B.dim() == 1 else B.shape[1]
-        Bc, ldb = _col_major(B, m)
-        X = torch.zeros(m, dtype=torch.float64, device=B.device) if B.dim() == 1 else \
-            torch.zeros(k * max(m, 1), dtype=torch.float64, device=B.device).as_strided((m, k), (1, max(m, 1)))
+        pc, k, Bc, ldb, X = self._system(B, "B", precond)
         if x0 is not None:
             _on_device(x0, self.device, "x0")
             if tuple(x0.shape) != tuple(B.shape):
@@ -163,7 +160,7 @@ class Operator:
             X.copy_(x0)
         d, dp = self._d_ptr(d)
         iters, relres, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
-        rc = self.lib.otmb_op_solve_pc_dev(self._h, int(bool(adjoint)), k, dp, float(sigma), Bc.data_ptr(), ldb, X.data_ptr(), max(m, 1),
+        rc = self.lib.otmb_op_solve_pc_dev(self._h, int(bool(adjoint)), k, dp, float(sigma), Bc.data_ptr(), ldb, X.data_ptr(), max(self.shape[0], 1),
                                            int(x0 is not None), float(rtol), int(maxiter), iters.ctypes.data, relres.ctypes.data,
                                            reason.ctypes.data, pc)
         if rc != capi.NOT_CONVERGED:

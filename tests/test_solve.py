@@ -167,6 +167,34 @@ def test_time_loop_x0_and_padding(oracle):
         assert np.array_equal(it, info2.iterations)
 
 
+def test_the_jacobi_wrapper_has_the_bits_of_the_keyword():
+    """No binding calls otmb_op_solve any more (they hand precond to otmb_op_solve_pc): the wrapper, on padded arrays, still has the bits of
+    DeviceOperator.solve with the default and with precond="jacobi".  n = 257 is one full 256-row workgroup plus one row, k = 7 register
+    blocks of 4 + 2 + 1 columns."""
+    import otmb_amd.api as api
+    from otmb_amd import capi
+
+    n, (p, i, v), d, sigma = _small_system("dominant")
+    k, pad = 7, 5
+    B = _rhs(n, k, seed=17)
+    Bp = np.full((n + pad, k), np.nan, order="F")
+    Bp[:n] = B
+    with api.DeviceOperator(_csc(n, p, i, v)) as D:
+        for adjoint in (0, 1):
+            Xp = np.full((n + pad, k), 7.25, order="F")
+            it, rr, why = np.zeros(k, np.int64), np.zeros(k), np.zeros(k, np.int32)
+            rc = capi.lib().otmb_op_solve(D.handle, adjoint, k, d.ctypes.data, float(sigma), Bp.ctypes.data, n + pad, Xp.ctypes.data, n + pad, 0, RTOL,
+                                          MAXITER, it.ctypes.data, rr.ctypes.data, why.ctypes.data)
+            assert rc == 0 and (why == 0).all() and (it > 0).all()
+            assert (Xp[n:] == 7.25).all()
+            for kw in ({}, {"precond": "jacobi"}):
+                X, info = D.solve(B, d=d, sigma=sigma, rtol=RTOL, maxiter=MAXITER, adjoint=bool(adjoint), **kw)
+                assert info.status == 0 and info.converged.all(), info
+                _same_bits(X, Xp[:n], ("X", adjoint, kw))
+                assert np.array_equal(info.iterations, it), (adjoint, kw)
+                _same_bits(info.relres, rr, ("relres", adjoint, kw))
+
+
 def test_honest_failures(oracle):
     import otmb_amd.api as api
     from otmb_amd import capi

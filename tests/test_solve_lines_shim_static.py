@@ -36,10 +36,8 @@ def test_shim_defines_and_exports_the_lines_api():
     assert re.search(r"^function verticallines\(indices\)", CODE, re.M)
     assert re.search(r"^function precondition!\(Z::StridedVecOrMat\{Float64\}, D::Union\{DeviceOperator,AdjointDeviceOperator\}, Y::StridedVecOrMat\{Float64\};",
                      CODE, re.M)
-    # solve! takes the keyword and leaves anything but Jacobi to solvepc!, before its own ccall
-    body = _jl("solve!")
-    assert "precond::Symbol = :jacobi" in body
-    assert body.index("precond === :jacobi || return solvepc!(X, D, B, precond;") < body.index("ccall(")
+    # solve! takes the keyword (its single ccall hands the code over: test_solve_shim_static.py)
+    assert "precond::Symbol = :jacobi" in _jl("solve!")
 
 
 def _ccall(fn, var):
@@ -55,8 +53,8 @@ def test_the_ccalls_have_the_prototypes_and_the_argument_order_of_the_header():
     from otmb_amd import capi
 
     protos = header_prototypes()
-    body, ret, jargs, passed = _ccall("solvepc!", "solve_pc_fn")
-    assert "solve_pc_fn = sym(:otmb_op_solve_pc)" in body and re.findall(r"sym\(:(otmb_\w+)\)", body) == ["otmb_op_solve_pc"]
+    body, ret, jargs, passed = _ccall("solve!", "solve_fn")
+    assert "solve_fn = sym(:otmb_op_solve_pc)" in body and re.findall(r"sym\(:(otmb_\w+)\)", body) == ["otmb_op_solve_pc"]
     assert (ret, jargs) == protos["otmb_op_solve_pc"]
     assert [k for t in capi.SYMBOLS["otmb_op_solve_pc"][1] for k in ctypes_kind(t)[:1]] == jargs
     assert passed == ["op.handle", "Int32(adjoint)", "k", "d === nothing ? C_NULL : d", "Float64(σ)", "B", "ldb", "X", "ldx", "Int32(x0)", "Float64(rtol)",
@@ -87,7 +85,7 @@ def _method(name):
 
 
 def test_python_makes_the_same_calls():
-    py = _method("_solve_pc")
+    py = _method("solve")
     assert re.findall(r"lib\.(otmb_\w+)\(", py) == ["otmb_op_solve_pc"]
     call = py[py.index("lib.otmb_op_solve_pc(") + len("lib.otmb_op_solve_pc("):]
     passed = split_top(" ".join(call[:call.index(", pc)") + len(", pc")].split()))
@@ -105,7 +103,6 @@ def test_python_makes_the_same_calls():
     py = _method("set_lines")
     assert re.findall(r"lib\.(otmb_\w+)\(", py) == ["otmb_op_set_lines", "otmb_op_set_lines"]
     assert "lib.otmb_op_set_lines(self._h, None)" in py and "lib.otmb_op_set_lines(self._h, nx.ctypes.data)" in py
-    # solve keeps its signature for the Jacobi call; the keyword comes from the decorator
+    # solve carries the keyword in its own signature, Jacobi by default on both sides
     cls = API[API.index("\nclass DeviceOperator:"):]
-    assert "\n    @_precond_keyword\n    def solve(self, B, d=None, sigma=0.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False):" in cls
-    assert 'def with_precond(self, *args, precond="jacobi", **kwargs):' in API
+    assert '\n    def solve(self, B, d=None, sigma=0.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False, precond="jacobi"):' in cls

@@ -1,6 +1,6 @@
-"""CPU: the Julia shim declares and exports solve! and solve over the resident operator, its ccall of otmb_op_solve has the return type,
-the argument types and the argument ORDER of the C prototype (include/otmb.h) and of the ctypes mirror, and the shim and
-api.DeviceOperator.solve hand the same values over in the same places (the Python side is what the GPU tests execute)."""
+"""CPU: the Julia shim declares and exports solve! and solve over the resident operator, its one ccall (otmb_op_solve_pc: the preconditioner
+is an argument) has the return type, the argument types and the argument ORDER of the C prototype (include/otmb.h) and of the ctypes mirror,
+and the shim and api.DeviceOperator.solve hand the same values over in the same places (the Python side is what the GPU tests execute)."""
 import os
 import re
 
@@ -64,37 +64,47 @@ def test_the_ccall_has_the_prototype_and_the_argument_order_of_the_header():
     from otmb_amd import capi
 
     body = _jl("solve!")
-    assert "solve_fn = sym(:otmb_op_solve)" in body
-    assert re.findall(r"sym\(:(otmb_\w+)\)", body) == ["otmb_op_solve"]
+    assert "solve_fn = sym(:otmb_op_solve_pc)" in body
+    assert re.findall(r"sym\(:(otmb_\w+)\)", body) == ["otmb_op_solve_pc"]  # one route: the preconditioner is an argument
     m = re.search(r"ccall\(solve_fn, (\w+), \((.*?)\),\n(.*?)\)\n", body, re.S)
     assert m, "solve!'s ccall"
+    assert len(re.findall(r"\bccall\(", body)) == 1
     jargs = [k for a in split_top(m.group(2).replace("\n", " ")) for k in julia_kind(a)]
     protos = header_prototypes()
-    assert (julia_kind(m.group(1))[0], jargs) == protos["otmb_op_solve"]
-    res, argtypes = capi.SYMBOLS["otmb_op_solve"]
+    assert (julia_kind(m.group(1))[0], jargs) == protos["otmb_op_solve_pc"]
+    res, argtypes = capi.SYMBOLS["otmb_op_solve_pc"]
     assert [k for t in argtypes for k in ctypes_kind(t)[:1]] == jargs
     # the values, place by place, in the header's order
     passed = [" ".join(a.split()) for a in split_top(m.group(3).replace("\n", " "))]
     want = ["op.handle", "Int32(adjoint)", "k", "d === nothing ? C_NULL : d", "Float64(σ)", "B", "ldb", "X", "ldx", "Int32(x0)", "Float64(rtol)",
-            "Int64(maxiter)", "iters", "relres", "reason"]
-    assert passed == want and len(want) == len(C_ORDER)
+            "Int64(maxiter)", "iters", "relres", "reason", "pc"]
+    assert passed == want and len(want) == len(C_ORDER) + 1 == 16
+    assert "pc = precondcode(precond)" in body and body.index("pc = precondcode(precond)") < body.index("ccall(")
     assert body.index("lock(CALL_LOCK) do") < body.index("ccall(")  # under the module's lock
     assert "rc == 19 || check(rc)" in body  # not converged is an answer; everything else goes through check
     assert "adjoint = D isa AdjointDeviceOperator" in body
+    assert "solvepc!" not in SHIM  # no second route beside solve!
 
 
 def test_python_makes_the_same_call():
     cls = API[API.index("\nclass DeviceOperator:"):]
-    m = re.search(r"\n    def solve\(self, B, d=None, sigma=0\.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False\):.*?(?=\n    def )", cls, re.S)
+    m = re.search(r"\n    def solve\(self, B, d=None, sigma=0\.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False, precond=\"jacobi\"\):.*?(?=\n    def )",
+                  cls, re.S)
     assert m, "DeviceOperator.solve"
+    assert cls[m.start() - 1] == "\n"  # a blank line, no decorator, above it: this signature is the one help() shows
     py = m.group(0)
-    assert re.findall(r"lib\.(otmb_\w+)\(", py) == ["otmb_op_solve"]
-    call = py[py.index("lib.otmb_op_solve("):]
-    call = " ".join(call[:call.index("reason.ctypes.data)") + len("reason.ctypes.data")].split())
-    passed = split_top(call[len("lib.otmb_op_solve("):])
+    assert re.findall(r"lib\.(otmb_\w+)\(", py) == ["otmb_op_solve_pc"]
+    call = py[py.index("lib.otmb_op_solve_pc(") + len("lib.otmb_op_solve_pc("):]
+    passed = split_top(" ".join(call[:call.index(", pc)") + len(", pc")].split()))
     want = ["self._h", "int(bool(adjoint))", "k", "None if dc is None else dc.ctypes.data", "float(sigma)", "Bc.ctypes.data", "ldb", "X.ctypes.data",
-            "max(X.shape[0], 1)", "int(x0 is not None)", "float(rtol)", "int(maxiter)", "iters.ctypes.data", "relres.ctypes.data", "reason.ctypes.data"]
+            "max(X.shape[0], 1)", "int(x0 is not None)", "float(rtol)", "int(maxiter)", "iters.ctypes.data", "relres.ctypes.data", "reason.ctypes.data",
+            "pc"]
     assert passed == want
+    assert "pc = capi.precond_code(precond)" in py and py.index("pc = capi.precond_code(precond)") < py.index("lib.otmb_op_solve_pc(")
     assert "if rc != capi.NOT_CONVERGED:" in py  # likewise: reported, not raised
+    # no second route beside solve (the twin method was _solve_pc: the name may only occur as the tail of the C symbol's)
+    for gone in (r"_precond_keyword", r"(?<!otmb_op)_solve_pc", r"lib\.otmb_op_solve\("):
+        assert not re.search(gone, API), gone
     # the same defaults on both sides
     assert "rtol::Real = 1e-10, maxiter::Integer = 10000" in SHIM
+    assert "precond::Symbol = :jacobi)" in SHIM[SHIM.index("function solve!("):SHIM.index("function solve!(") + 500]

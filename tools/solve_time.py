@@ -1,4 +1,4 @@
-"""Time the device solver (otmb_op_solve_dev, csrc/otmb_solve.hip) on the 1 degree preset; one JSON line per measurement.
+"""Time the device solver (otmb_op_solve_pc_dev, csrc/otmb_solve.hip) on the 1 degree preset; one JSON line per measurement.
 
     python tools/solve_time.py [--reps 10] [--maxiter 20000] [--precond jacobi|lines|both] [--year] [--host] [--out FILE.jsonl]
 
