@@ -731,6 +731,57 @@ int32_t otmb_op_precond_dev(otmb_op *op, int32_t adjoint, int32_t precond, int64
 int32_t otmb_op_precond(otmb_op *op, int32_t adjoint, int32_t precond, int64_t k, const double *d, double sigma, const double *Y, int64_t ldy,
                         double *Z, int64_t ldz);
 
+/* ---- Value slots: several value sets over ONE pattern, resident together -- a year of monthly transport matrices, cycled by a time loop
+ *      without uploading or scattering anything again.  The operator holds nslots copies of its two value arrays (nzval of the CSC copy and
+ *      the row layout's values: 8·nnz bytes and 8·(nnz + the slices' padding) bytes per slot); the pattern, the index arrays and the lines
+ *      are shared.  A fresh operator has one slot, slot 0, selected.
+ * otmb_op_set_slots: nslots >= 1.  Growing keeps the existing slots; every new slot is a device copy of the SELECTED slot's values (never
+ *      undefined).  Shrinking frees the slots from nslots on (it waits for the stream); when the selected slot goes, slot 0 is selected.
+ *      A failed allocation (OTMB_ERR_ALLOC) leaves the operator with the slots it had.
+ * otmb_op_set_values_slot[_dev]: otmb_op_set_values[_dev] into slot `slot` (0-based), whichever is selected.
+ *      otmb_op_set_values[_dev] writes the selected slot.
+ * otmb_op_select_slot: a pointer switch -- nothing is enqueued, no data moves.  otmb_op_mul*, otmb_op_solve*, otmb_op_precond* called
+ *      afterwards read that slot (work already enqueued keeps the slot it was enqueued with).
+ * otmb_op_slots: the number of slots and the selected one (either pointer may be NULL).
+ * A slot outside 0..nslots-1, nslots < 1 or an nnz that is not the operator's: OTMB_ERR_INVALID_ARG with a message; the operator stays usable. */
+int32_t otmb_op_set_slots(otmb_op *op, int64_t nslots);
+int32_t otmb_op_set_values_slot_dev(otmb_op *op, int64_t slot, const double *nzval, int64_t nnz);
+int32_t otmb_op_set_values_slot(otmb_op *op, int64_t slot, const double *nzval, int64_t nnz);
+int32_t otmb_op_select_slot(otmb_op *op, int64_t slot);
+int32_t otmb_op_slots(const otmb_op *op, int64_t *nslots, int64_t *selected);
+
+/* ---- θ-steps of ∂x/∂t + (diag(d) + A)·x = s over the slots: X (n x k, in and out) advances through nsteps steps of length dt, step t
+ *      (0-based) with the matrix A of slot (first_slot + t) mod nslots (adjoint: Aᵀ).  S: the source, n x k with leading dimension lds, or NULL
+ *      (zero); d: n values or NULL.  dt > 0 and finite, 0 < theta <= 1 (1: implicit Euler, 0.5: Crank-Nicolson), nsteps >= 0,
+ *      0 <= first_slot < nslots, the operator square, rtol > 0, maxiter >= 0, precond as in otmb_op_solve_pc (OTMB_PRECOND_LINES needs lines),
+ *      ldx, lds >= n, steps_done not NULL, iters / relres / reason not NULL unless nsteps == 0: otherwise OTMB_ERR_INVALID_ARG before X is
+ *      touched.  The selected slot is the same after the call as before it.
+ * One step, as a contract in public calls -- every state has the bits of this composition, column by column, and column c of k has the bits of
+ * that column stepped alone:
+ *        σ = 1 / (theta·dt): the product theta * dt, then its reciprocal;
+ *        theta == 1:  b_i = σ·x_i + s_i (one multiplication, one addition);  without S: b_i = σ·x_i;
+ *        theta <  1:  w = A·x as otmb_op_mul_dev(alpha = 1, beta = 0) gives it;  c = (1 - theta) / theta;  e_i = d_i·x_i + w_i (without d: w_i);
+ *                     b_i = (σ·x_i + s_i/theta) - c·e_i in exactly that association (without S the s_i/theta term is absent);  no FMA;
+ *        then otmb_op_solve_pc_dev(op, adjoint, k, d, σ, B, X, use_x0 = 1, rtol, maxiter, ..., precond): the previous state is the start.
+ *      The right-hand side is one kernel per step (the product's fold ends in the elementwise line; theta == 1 reads no matrix).  A slot's
+ *      preconditioner -- Jacobi's diagonal or the line factorisation -- is computed on the slot's first visit of the call and reused on every
+ *      later visit: d, σ, adjoint and the values are fixed inside a call, and the factorisation is deterministic, so the bits are those of
+ *      separate solves.
+ * Stopping: a step whose solve leaves any column not converged ends the call: OTMB_ERR_NOT_CONVERGED, *steps_done = the number of steps
+ *      completed with every column converged, X = that step's last iterates.  A slot whose preconditioner is singular ends it with
+ *      OTMB_ERR_SINGULAR_PRECONDITIONER on the slot's first visit: X = the state after *steps_done steps.
+ *      iters, relres, reason: HOST arrays of nsteps·k entries, step-major (entry t·k + c), as otmb_op_solve reports them; written for the
+ *      steps 0 .. min(*steps_done, nsteps - 1) -- after a singular preconditioner for the steps before *steps_done only -- the rest is not
+ *      written.  nsteps == 0: OTMB_OK, *steps_done = 0, nothing else is touched.
+ * otmb_op_step_dev: d, S, X device pointers, on the context's stream.  otmb_op_step: host pointers; X, S and d are uploaded once and X is
+ *      downloaded once, however many steps.                                                                                           */
+int32_t otmb_op_step_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
+                         const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
+                         int64_t *iters, double *relres, int32_t *reason);
+int32_t otmb_op_step(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
+                     const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
+                     int64_t *iters, double *relres, int32_t *reason);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@
 #   lump_and_spray              src/extratools.jl:38-119
 #   coarsen                     LUMP * T * SPRAY (src/extratools.jl:14-16)
 #   DeviceOperator, setvalues!  T * x, T' * v, mul!(Y, T, X, α, β) on the GPU (test/local_full.jl:96-107; README: ∂x/∂t + T x = …)
+#   setslots!, step!, step      a year of monthly matrices resident as value slots, and θ-steps of the tracers through them on the GPU
 #   solve!, solve               (σ·I + Diagonal(d) + T) \ B on the GPU: the `\` of the ideal-age problem (test/local_full.jl:151-188)
 #   bolus_GM_velocity           src/RediGM.jl:46-79 (unexported and experimental there, unexported here)
 #   makegridmetrics             src/gridcellgeometry.jl:265-311: the reference's own by default (its haversines are Julia's libm);
@@ -35,6 +36,7 @@ export makeindices, facefluxesfrommasstransport, facefluxes, transportmatrix, lu
 export DeviceOperator, setvalues!
 export solve!, solve
 export setlines!, verticallines, precondition!
+export setslots!, selectslot!, slots, step!   # (`step` extends Base.step for this module's operators: nothing to export)
 
 const LIBPATH = get(ENV, "OTMB_HIP_LIB", joinpath(@__DIR__, "..", "oceantransportmatrixbuilder.jl_amd", "lib", "libotmb_hip.so"))
 const lib = Ref{Ptr{Cvoid}}(C_NULL)
@@ -446,6 +448,78 @@ function precondition!(Z::StridedVecOrMat{Float64}, D::Union{DeviceOperator,Adjo
     end
     return Z
 end
+
+# Value slots (include/otmb.h): several value sets over the operator's one pattern, resident together -- the twelve monthly matrices of a
+# climatological year.  Slots are numbered from 1 here (the C side counts from 0).  `setslots!(D, n)` grows (new slots are copies of the
+# selected one) or shrinks; `setvalues!(D, nzval, slot)` fills one (the slot is positional: `setvalues!(D, nzval)` writes the selected slot);
+# `selectslot!(D, slot)` is a pointer switch: `D * x`, `solve!` and `precondition!` read that slot afterwards; `slots(D)` = (n, selected).
+function setslots!(D::DeviceOperator, nslots::Integer)
+    lock(CALL_LOCK) do
+        D.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        set_slots_fn = sym(:otmb_op_set_slots)
+        check(ccall(set_slots_fn, Int32, (Ptr{Cvoid}, Int64), D.handle, Int64(nslots)))
+    end
+    return D
+end
+function setvalues!(D::DeviceOperator, nzval::Vector{Float64}, slot::Integer)
+    lock(CALL_LOCK) do
+        D.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        set_values_slot_fn = sym(:otmb_op_set_values_slot)
+        check(ccall(set_values_slot_fn, Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64), D.handle, Int64(slot - 1), nzval, length(nzval)))
+    end
+    return D
+end
+function selectslot!(D::DeviceOperator, slot::Integer)
+    lock(CALL_LOCK) do
+        D.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        select_slot_fn = sym(:otmb_op_select_slot)
+        check(ccall(select_slot_fn, Int32, (Ptr{Cvoid}, Int64), D.handle, Int64(slot - 1)))
+    end
+    return D
+end
+function slots(D::DeviceOperator)
+    n = Ref{Int64}(0)
+    sel = Ref{Int64}(0)
+    lock(CALL_LOCK) do
+        D.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        slots_fn = sym(:otmb_op_slots)
+        check(ccall(slots_fn, Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), D.handle, n, sel))
+    end
+    return (n[], sel[] + 1)
+end
+
+# θ-steps of ∂x/∂t + (Diagonal(d) + A)·x = source through the slots (otmb_op_step; include/otmb.h states the contract): X is advanced in
+# place through `nsteps` steps of length `dt`, step t = 0, 1, ... with slot firstslot + t (cyclically); `D'` steps with Aᵀ.  Returns
+# (X, info): info.stepsdone and, per step that ran a solve (rows) and column, info.iterations, info.relres, info.reason, info.converged.
+# A step that does not converge ends the call and is REPORTED, not thrown (status 19): X then holds that step's last iterates.
+function step!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}; dt::Real, θ::Real = 1.0, nsteps::Integer = 1,
+               firstslot::Integer = 1, source::Union{Nothing,StridedVecOrMat{Float64}} = nothing, d::Union{Nothing,Vector{Float64}} = nothing,
+               rtol::Real = 1e-10, maxiter::Integer = 10000, precond::Symbol = :jacobi)
+    pc = precondcode(precond)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    S = source === nothing ? X : source
+    k, lds, ldx = systemdims(op, S, "source", X, "X", d)
+    nrep = max(Int64(nsteps), 0)
+    iters = zeros(Int64, k, nrep)
+    relres = zeros(Float64, k, nrep)
+    reason = zeros(Int32, k, nrep)
+    done = Ref{Int64}(0)
+    lock(CALL_LOCK) do
+        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        step_fn = sym(:otmb_op_step)
+        rc = ccall(step_fn, Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Float64, Float64, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                Float64, Int64, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}),
+            op.handle, Int32(adjoint), k, d === nothing ? C_NULL : d, Float64(dt), Float64(θ), Int64(nsteps), Int64(firstslot - 1),
+            source === nothing ? C_NULL : source, lds, X, ldx, Float64(rtol), Int64(maxiter), pc, done, iters, relres, reason)
+        rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which step and column stopped why
+    end
+    ran = 1:min(done[] + 1, nrep)
+    why = permutedims([SOLVE_REASONS[r + 1] for r in reason[:, ran]])
+    return X, (stepsdone = done[], iterations = permutedims(iters[:, ran]), relres = permutedims(relres[:, ran]), reason = why,
+               converged = why .== :converged)
+end
+Base.step(D::Union{DeviceOperator,AdjointDeviceOperator}, X::StridedVecOrMat{Float64}; kwargs...) = step!(copy(X), D; kwargs...)
 
 const HDIRS = (:west, :east, :south, :north)      # OTMB_DIR_*
 f64(a) = Array{Float64}(replace(a, missing => NaN))

@@ -818,6 +818,29 @@ class SolveInfo:
         return f"SolveInfo(status={self.status}, iterations={self.iterations.tolist()}, relres={self.relres.tolist()}, reason={self.reason})"
 
 
+class StepInfo:
+    """What otmb_op_step reports: status (0, or capi.NOT_CONVERGED), steps_done (steps completed with every column converged) and, one row
+    per step that ran a solve (steps 0 .. min(steps_done, nsteps - 1)) and one entry per column: iterations, relres, reason (tuples of
+    "converged", "maxiter", "breakdown", "nonfinite") and converged -- each as SolveInfo has them for one solve."""
+
+    def __init__(self, status, steps_done, nsteps, iterations, relres, reason):
+        self.status, self.steps_done = int(status), int(steps_done)
+        ran = min(self.steps_done + 1, int(nsteps))
+        self.iterations = np.asarray(iterations, dtype=np.int64)[:ran]
+        self.relres = np.asarray(relres, dtype=np.float64)[:ran]
+        self.reason = tuple(tuple(capi.SOLVE_REASONS[int(r)] for r in row) for row in np.asarray(reason)[:ran])
+        self.converged = np.array([[r == "converged" for r in row] for row in self.reason], dtype=bool).reshape(self.iterations.shape)
+
+    def __repr__(self):
+        return f"StepInfo(status={self.status}, steps_done={self.steps_done}, iterations={self.iterations.tolist()}, reason={self.reason})"
+
+
+def step_arrays(nsteps, k):
+    """The three report arrays of otmb_op_step (nsteps x k, step-major)."""
+    shape = (max(int(nsteps), 0), int(k))
+    return np.zeros(shape, dtype=np.int64), np.zeros(shape, dtype=np.float64), np.zeros(shape, dtype=np.int32)
+
+
 def vertical_lines(indices):
     """The `next` array of otmb_op_set_lines / DeviceOperator.set_lines for the water columns of a makeindices result (anything with
     Lwet3D: the wet rank of every cell, 0 = land): next[Lwet3D[i,j,k] - 1] = Lwet3D[i,j,k+1] when both cells are wet, 0 otherwise
@@ -843,7 +866,8 @@ class DeviceOperator:
       * no FMA; `A * x` and `A' * v` are α = 1.0, β = 0.0.
     A: a SparseMatrixCSC (1-based).  The operator owns device copies of A: the arrays may change or go once the constructor returns.
     The same C calls as the Julia shim's DeviceOperator: otmb_op_create; mul! -> otmb_op_mul; setvalues! -> otmb_op_set_values; solve! ->
-    otmb_op_solve_pc; setlines! -> otmb_op_set_lines; precondition! -> otmb_op_precond; the finalizer -> otmb_op_destroy."""
+    otmb_op_solve_pc; setlines! -> otmb_op_set_lines; precondition! -> otmb_op_precond; setslots! / selectslot! / step! -> otmb_op_set_slots /
+    otmb_op_select_slot / otmb_op_step; the finalizer -> otmb_op_destroy."""
 
     def __init__(self, A, *, device=0):
         self._h = C.c_void_p()
@@ -889,12 +913,37 @@ class DeviceOperator:
             Y[...] = Yc
         return Y
 
-    def set_values(self, nzval):
-        """New nzval (nnz of them, in the stored order of the pattern the operator was made with)."""
+    def set_values(self, nzval, slot=None):
+        """New nzval (nnz of them, in the stored order of the pattern the operator was made with) for the selected slot, or for slot `slot`
+        (set_slots) whichever is selected."""
         self._live()
         v = np.ascontiguousarray(nzval, dtype=np.float64)
+        if slot is not None:
+            return self._set_slot_values(v, slot)
         lib = capi.lib()
         self.ctx.check(lib.otmb_op_set_values(self._h, v.ctypes.data, len(v)))
+
+    def _set_slot_values(self, v, slot):
+        self.ctx.check(capi.lib().otmb_op_set_values_slot(self._h, int(slot), v.ctypes.data, len(v)))
+
+    def set_slots(self, n):
+        """n >= 1 value slots over the one pattern (otmb_op_set_slots): a year of monthly matrices resident together.  Growing keeps the slots
+        there are and fills each new one with a device copy of the selected slot; shrinking below the selected slot selects slot 0."""
+        self._live()
+        self.ctx.check(capi.lib().otmb_op_set_slots(self._h, int(n)))
+
+    def select(self, slot):
+        """mul, solve and precondition read slot `slot` from now on (otmb_op_select_slot: a pointer switch, no data moves)."""
+        self._live()
+        self.ctx.check(capi.lib().otmb_op_select_slot(self._h, int(slot)))
+
+    @property
+    def slots(self):
+        """(number of slots, the selected slot)."""
+        self._live()
+        n, sel = C.c_int64(0), C.c_int64(0)
+        self.ctx.check(capi.lib().otmb_op_slots(self._h, C.byref(n), C.byref(sel)))
+        return int(n.value), int(sel.value)
 
     def set_lines(self, next):
         """The lines of the "lines" preconditioner (otmb_op_set_lines; include/otmb.h states the rules): next[i] is the 1-based successor of
@@ -964,6 +1013,32 @@ class DeviceOperator:
         if rc != capi.NOT_CONVERGED:
             self.ctx.check(rc)
         return X, SolveInfo(rc, iters, relres, reason)
+
+    def step(self, X, *, dt, theta=1.0, nsteps=1, first_slot=0, source=None, d=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi"):
+        """nsteps θ-steps of ∂x/∂t + (diag(d) + A)·x = source from the state X, step t with the matrix of slot (first_slot + t) mod nslots
+        (otmb_op_step; include/otmb.h states the contract: σ = 1 / (theta·dt), the right-hand side, then solve(..., x0 = the state)).  X: 1-D
+        or 2-D (n x k), not modified; source: None (zero) or an array of X's shape; d: None or n values.  Returns (X after the steps, info):
+        info a StepInfo.  A step that does not converge ends the call and is REPORTED as solve reports it (info.status, info.steps_done,
+        info.reason; X then holds that step's last iterates), not raised; argument errors and a singular preconditioner raise OtmbError."""
+        self._live()
+        pc = capi.precond_code(precond)
+        X0 = np.asarray(X)
+        k, _, _, dc = self._system_args(X0, d)
+        Xn = np.array(X0, dtype=np.float64, order="F")
+        Sc, lds = None, max(Xn.shape[0], 1)
+        if source is not None:
+            if np.shape(source) != X0.shape:
+                raise capi.OtmbError(11, f"DimensionMismatch: source of {np.shape(source)}, X of {X0.shape}")
+            Sc, lds = _column_major(np.asarray(source))
+        iters, relres, reason = step_arrays(nsteps, k)
+        done = C.c_int64(0)
+        lib = capi.lib()
+        rc = lib.otmb_op_step(self._h, int(bool(adjoint)), k, None if dc is None else dc.ctypes.data, float(dt), float(theta), int(nsteps),
+                              int(first_slot), None if Sc is None else Sc.ctypes.data, lds, Xn.ctypes.data, max(Xn.shape[0], 1), float(rtol),
+                              int(maxiter), pc, C.byref(done), iters.ctypes.data, relres.ctypes.data, reason.ctypes.data)
+        if rc != capi.NOT_CONVERGED:
+            self.ctx.check(rc)
+        return Xn, StepInfo(rc, done.value, nsteps, iters, relres, reason)
 
     def __matmul__(self, x):
         return self.mul(x)

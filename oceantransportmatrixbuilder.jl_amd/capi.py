@@ -198,6 +198,15 @@ SYMBOLS = {
                                       _vp, _vp, _vp, C.c_int32]),
     "otmb_op_precond_dev": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int64, _vp, C.c_double, _vp, C.c_int64, _vp, C.c_int64]),
     "otmb_op_precond": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int64, _vp, C.c_double, _vp, C.c_int64, _vp, C.c_int64]),
+    "otmb_op_set_slots": (C.c_int32, [_vp, C.c_int64]),
+    "otmb_op_set_values_slot_dev": (C.c_int32, [_vp, C.c_int64, _vp, C.c_int64]),
+    "otmb_op_set_values_slot": (C.c_int32, [_vp, C.c_int64, _vp, C.c_int64]),
+    "otmb_op_select_slot": (C.c_int32, [_vp, C.c_int64]),
+    "otmb_op_slots": (C.c_int32, [_vp, _ip, _ip]),
+    "otmb_op_step_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
+                                      C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp]),
+    "otmb_op_step": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
+                                  C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp]),
     "otmb_op_info": (C.c_int32, [_vp, _ip, _ip, _ip]),
     "otmb_op_destroy": (None, [_vp]),
     "otmb_transportmatrix_plan_dev": (C.c_int32, [_vp, C.POINTER(TmArgs), C.POINTER(C.c_int64 * 5)]),

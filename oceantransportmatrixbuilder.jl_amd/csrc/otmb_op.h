@@ -4,23 +4,31 @@
 #pragma once
 #include <algorithm>
 #include <type_traits>
+#include <vector>
 
 #include "otmb_common.h"
 
 #define SP_ELL_MAX 256   // longest row a slice takes
 #define SP_TCH 512       // entries per LDS chunk of the Aᵀ and long-row kernels
 
+struct OpSlot {  // one value set of the pattern (otmb_op_set_slots): nzval of the CSC copy, val of the row layout
+    DevBuf nz, val;
+};
+
 struct otmb_op {
     otmb_ctx *ctx = nullptr;
     int device = 0;
     i64 m = 0, n = 0, nnz = 0;
     i64 nslices = 0, ell = 0, nlong = 0;  // slices, entries of the slice layout (padding included), long rows
-    DevBuf cp, rv, nz;                    // CSC copy: colptr (n + 1, Int64), rowval - 1 (Int32), nzval
+    DevBuf cp, rv, nz;                    // CSC copy: colptr (n + 1, Int64), rowval - 1 (Int32), nzval (of the SELECTED slot: see slots)
     DevBuf dst;                           // per stored entry: its position in val / col
     DevBuf elen, sbase, loff, lrows;      // per row: length or -1 (long); per slice: first position; per row: long-row offset; long rows
-    DevBuf val, col;                      // slices then long rows: values and column indices (Int32, 0-based)
+    DevBuf val, col;                      // slices then long rows: values (of the SELECTED slot) and column indices (Int32, 0-based)
+    std::vector<OpSlot> slots;            // the value slots, which own every nz / val array once the plan stands: nz and val above are
+    i64 sel = 0, nval = 0;                // copies of slots[sel]'s records (otmb_op_select_slot switches them); nval: doubles of a val array
     DevBuf xs, ys;                        // host entry points' staging (op_reserve_xy): otmb_op_mul X, Y; otmb_op_solve_pc B, X; otmb_op_precond Y, Z
     DevBuf ds, sw;                        // staging of d (op_stage_d); the solver's arrays (SvWork, otmb_solve.hip): vectors, partial sums, column records
+    DevBuf st;                            // otmb_op_step: the right-hand side and the preconditioners of the slots it visits (otmb_step.hip)
     DevBuf ln;                            // otmb_op_set_lines (Int32, 0-based, -1 = none): successor (n), predecessor (n), line heads ascending (nheads)
     i64 nheads = 0;
     bool lines = false;                   // lines are set (they belong to the pattern: otmb_op_set_values keeps them)

@@ -469,6 +469,14 @@ static int32_t sv_precond_setup(otmb_op *op, const SvWork &w, int adjoint, int32
     return OTMB_OK;
 }
 
+// The same into arrays of the caller's (otmb_op_step keeps one set per slot it visits); op->sw lends the flags only.
+int32_t sv_prec_prepare(otmb_op *op, int adjoint, int32_t precond, const double *d, double sigma, const SvPrec &p) {
+    SvWork w;
+    int32_t rc;
+    if ((rc = sv_work(op, precond == OTMB_PRECOND_LINES, 0, 0, w))) return rc;
+    w.sh = p.sh; w.diag = p.diag; w.m = p.m; w.u = p.u; w.piv = p.piv;
+    return sv_precond_setup(op, w, adjoint, precond, d, sigma);
+}
 
 // W = M·Z (modes 0, 1) or U - M·Z (mode 2) for the columns in state `want`, with the partials of the mode's dot products
 template <int MODE>
@@ -525,17 +533,18 @@ static int32_t sv_check(otmb_op *op, int32_t precond, int64_t k, const double *B
     const char *more = !iters || !relres || !reason ? "null argument" : !(rtol > 0.0) ? "rtol must be > 0" : maxiter < 0 ? "maxiter must be >= 0" : nullptr;
     return sv_check_system(op, precond, "solve", "right-hand sides", 'B', 'X', k, B, ldb, X, ldx, more);
 }
+int32_t sv_check_step(otmb_op *op, int32_t precond, int64_t k, const double *S, int64_t lds, double *X, int64_t ldx, const char *more) {
+    return sv_check_system(op, precond, "step", "tracers", 'S', 'X', k, S ? S : X, S ? lds : ldx, X, ldx, more);
+}
 static int32_t sv_check_apply(otmb_op *op, int32_t precond, int64_t k, const double *Y, int64_t ldy, double *Z, int64_t ldz) {
     return sv_check_system(op, precond, "precond", "columns", 'Y', 'Z', k, Y, ldy, Z, ldz, nullptr);
 }
 
-extern "C" {
-
-int32_t otmb_op_solve_pc_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X,
-                             int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason, int32_t precond) {
-    if (!op) return OTMB_ERR_INVALID_ARG;
+// The solve behind otmb_op_solve_pc_dev, its arguments checked already.  prep == nullptr: the preconditioner is set up here, from d and σ;
+// otherwise it is taken as prepared (sv_prec_prepare, for this adjoint, precond, d, σ and the selected values) and d and σ are not read.
+int32_t sv_solve(otmb_op *op, int adjoint, i64 k, const double *d, double sigma, const double *B, i64 ldb, double *X, i64 ldx, int use_x0, double rtol,
+                 i64 maxiter, int64_t *iters, double *relres, int32_t *reason, int32_t precond, const SvPrec *prep) {
     int32_t rc;
-    if ((rc = sv_check(op, precond, k, B, ldb, X, ldx, rtol, maxiter, iters, relres, reason))) return rc;
     const bool lines = precond == OTMB_PRECOND_LINES;
     otmb_ctx *ctx = op->ctx;
     const i64 n = op->n;
@@ -550,7 +559,9 @@ int32_t otmb_op_solve_pc_dev(otmb_op *op, int32_t adjoint, int64_t k, const doub
     if ((rc = sv_work(op, lines, k, np, w))) return rc;
     const dim3 grid((unsigned)nb), block(256);
     // the preconditioner, checked before anything of X is touched
-    if ((rc = sv_precond_setup(op, w, adjoint, precond, d, sigma))) return rc;
+    if (prep) {
+        w.sh = prep->sh; w.diag = prep->diag; w.m = prep->m; w.u = prep->u; w.piv = prep->piv;
+    } else if ((rc = sv_precond_setup(op, w, adjoint, precond, d, sigma))) return rc;
     // ‖b‖, the start, its true residual
     op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
         hipLaunchKernelGGL((sv_bnorm_kernel<decltype(kb)::value>), grid, block, 0, st, n, B + c0 * ldb, ldb, w.part + 2 * c0 * np, np);
@@ -621,6 +632,16 @@ int32_t otmb_op_solve_pc_dev(otmb_op *op, int32_t adjoint, int64_t k, const doub
         return otmb_fail(ctx, OTMB_ERR_NOT_CONVERGED, msg);
     }
     return OTMB_OK;
+}
+
+extern "C" {
+
+int32_t otmb_op_solve_pc_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X,
+                             int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason, int32_t precond) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    int32_t rc;
+    if ((rc = sv_check(op, precond, k, B, ldb, X, ldx, rtol, maxiter, iters, relres, reason))) return rc;
+    return sv_solve(op, adjoint, k, d, sigma, B, ldb, X, ldx, use_x0, rtol, maxiter, iters, relres, reason, precond, nullptr);
 }
 
 int32_t otmb_op_solve_pc(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X, int64_t ldx,

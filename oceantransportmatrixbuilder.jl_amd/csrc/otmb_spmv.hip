@@ -192,7 +192,15 @@ static void sp_free(DevBuf &b) {
     b.cap = 0;
 }
 static void sp_free_all(otmb_op *op) {
-    for (DevBuf *b : {&op->cp, &op->rv, &op->nz, &op->dst, &op->elen, &op->sbase, &op->loff, &op->lrows, &op->val, &op->col, &op->xs, &op->ys, &op->ds, &op->sw, &op->ln})
+    // the slots own the value arrays; an operator whose plan never stood has no slot yet, and nz and val are then its own
+    for (OpSlot &s : op->slots) {
+        sp_free(s.nz);
+        sp_free(s.val);
+    }
+    if (!op->slots.empty()) op->nz = op->val = DevBuf();
+    op->slots.clear();
+    for (DevBuf *b : {&op->cp, &op->rv, &op->nz, &op->dst, &op->elen, &op->sbase, &op->loff, &op->lrows, &op->val, &op->col, &op->xs, &op->ys, &op->ds, &op->sw, &op->st,
+                      &op->ln})
         sp_free(*b);
 }
 
@@ -288,6 +296,7 @@ static int32_t sp_plan(otmb_op *op, const i64 *rowval) {
     op->ell = tot[0];
     op->nlong = tot[1];
     const i64 total = tot[0] + tot[2];
+    op->nval = total;
     if ((rc = sp_reserve(op, op->val, (size_t)total * 8))) return rc;
     if ((rc = sp_reserve(op, op->col, (size_t)total * 4))) return rc;
     if ((rc = sp_reserve(op, op->lrows, (size_t)op->nlong * 8))) return rc;
@@ -358,21 +367,25 @@ static int32_t sp_create(otmb_ctx *ctx, int64_t m, int64_t n, const int64_t *col
         if (kind == hipMemcpyHostToDevice) ctx->uploaded_bytes += 16 * nnz + 8 * (n + 1);
     }
     if ((rc = sp_plan(op, (const i64 *)rows.b.p))) return rc;
+    op->slots.push_back(OpSlot{op->nz, op->val});  // slot 0, selected
     *out = op;
     G.op = nullptr;
     return OTMB_OK;
 }
 
-static int32_t sp_set_values(otmb_op *op, const double *nzval, int64_t nnz, hipMemcpyKind kind) {
+// the scatter into slot `slot`, or into the selected one (slot == -1)
+static int32_t sp_set_values(otmb_op *op, int64_t slot, const double *nzval, int64_t nnz, hipMemcpyKind kind) {
     if (!op) return OTMB_ERR_INVALID_ARG;
     otmb_ctx *ctx = op->ctx;
+    if (slot < -1 || slot >= (i64)op->slots.size()) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "set_values: slot out of range (otmb_op_set_slots)");
+    const OpSlot &to = op->slots[(size_t)(slot < 0 ? op->sel : slot)];
     if (nnz != op->nnz) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "set_values: nnz differs from the operator's");
     if (nnz > 0 && !nzval) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
     HIP_TRY(ctx, hipSetDevice(op->device));
     if (nnz == 0) return OTMB_OK;
-    HIP_TRY(ctx, hipMemcpyAsync(op->nz.p, nzval, (size_t)nnz * 8, kind, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(to.nz.p, nzval, (size_t)nnz * 8, kind, ctx->stream));
     if (kind == hipMemcpyHostToDevice) ctx->uploaded_bytes += 8 * nnz;
-    hipLaunchKernelGGL(spmv_relayout_kernel, SP_GRID(nnz), (const double *)op->nz.p, (const i64 *)op->dst.p, nnz, (double *)op->val.p);
+    hipLaunchKernelGGL(spmv_relayout_kernel, SP_GRID(nnz), (const double *)to.nz.p, (const i64 *)op->dst.p, nnz, (double *)to.val.p);
     HIP_TRY(ctx, hipGetLastError());
     return OTMB_OK;
 }
@@ -410,12 +423,111 @@ int32_t otmb_op_create(otmb_ctx *ctx, int64_t m, int64_t n, const int64_t *colpt
     return sp_create(ctx, m, n, colptr, rowval, nzval, out, hipMemcpyHostToDevice);
 }
 
-int32_t otmb_op_set_values_dev(otmb_op *op, const double *nzval, int64_t nnz) { return sp_set_values(op, nzval, nnz, hipMemcpyDeviceToDevice); }
+int32_t otmb_op_set_values_dev(otmb_op *op, const double *nzval, int64_t nnz) { return sp_set_values(op, -1, nzval, nnz, hipMemcpyDeviceToDevice); }
 
-int32_t otmb_op_set_values(otmb_op *op, const double *nzval, int64_t nnz) {
-    const int32_t rc = sp_set_values(op, nzval, nnz, hipMemcpyHostToDevice);
+static int32_t sp_set_values_host(otmb_op *op, int64_t slot, const double *nzval, int64_t nnz) {
+    const int32_t rc = sp_set_values(op, slot, nzval, nnz, hipMemcpyHostToDevice);
     if (rc == OTMB_OK && op->nnz > 0) HIP_TRY(op->ctx, hipStreamSynchronize(op->ctx->stream));  // (the caller may reuse its array at once)
     return rc;
+}
+int32_t otmb_op_set_values(otmb_op *op, const double *nzval, int64_t nnz) { return sp_set_values_host(op, -1, nzval, nnz); }
+
+// ---- value slots: nslots copies of nzval / val over ONE pattern (dst, the index arrays and the lines are shared) -------------------
+// a slot's array at its exact size (otmb_reserve rounds up by an eighth for buffers that grow; a year of slots does not grow)
+static int32_t sp_exact(otmb_op *op, DevBuf &b, size_t bytes) {
+    bytes = bytes > 0 ? bytes : 8;
+    if (hipMalloc(&b.p, bytes) != hipSuccess) {
+        b.p = nullptr;
+        (void)hipGetLastError();  // (the refusal is reported here, not by the next call's error check)
+        return otmb_fail(op->ctx, OTMB_ERR_ALLOC, "hipMalloc (set_slots)");
+    }
+    b.cap = bytes;
+    return OTMB_OK;
+}
+static int32_t sp_slot_arg(otmb_op *op, int64_t slot, const char *what) {
+    if (slot >= 0 && slot < (i64)op->slots.size()) return OTMB_OK;
+    char msg[128];
+    snprintf(msg, sizeof msg, "%s: slot %lld is outside 0..%lld (otmb_op_set_slots)", what, (long long)slot, (long long)op->slots.size() - 1);
+    return otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, msg);
+}
+static void sp_select(otmb_op *op, i64 slot) {
+    op->sel = slot;
+    op->nz = op->slots[(size_t)slot].nz;
+    op->val = op->slots[(size_t)slot].val;
+}
+
+int32_t otmb_op_set_slots(otmb_op *op, int64_t nslots) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    otmb_ctx *ctx = op->ctx;
+    if (nslots < 1) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "set_slots: nslots must be >= 1");
+    HIP_TRY(ctx, hipSetDevice(op->device));
+    const i64 have = (i64)op->slots.size();
+    if (nslots > have) {  // every new slot is allocated before the operator changes: a failure leaves the slots it had
+        std::vector<OpSlot> add;
+        try {  // (the host's table of slots itself: a count no machine can hold is an allocation failure like the device's)
+            add.resize((size_t)(nslots - have));
+            op->slots.reserve((size_t)nslots);
+        } catch (const std::exception &) {
+            return otmb_fail(ctx, OTMB_ERR_ALLOC, "set_slots: the table of slots");
+        }
+        int32_t rc = OTMB_OK;
+        for (OpSlot &s : add)
+            if ((rc = sp_exact(op, s.nz, (size_t)op->nnz * 8)) || (rc = sp_exact(op, s.val, (size_t)op->nval * 8))) break;
+        hipError_t e = hipSuccess;
+        for (OpSlot &s : add) {  // a device copy of the selected slot: never undefined
+            if (rc || e != hipSuccess) break;
+            if (op->nnz > 0) e = hipMemcpyAsync(s.nz.p, op->nz.p, (size_t)op->nnz * 8, hipMemcpyDeviceToDevice, ctx->stream);
+            if (e == hipSuccess && op->nval > 0) e = hipMemcpyAsync(s.val.p, op->val.p, (size_t)op->nval * 8, hipMemcpyDeviceToDevice, ctx->stream);
+        }
+        if (rc || e != hipSuccess) {
+            (void)hipStreamSynchronize(ctx->stream);
+            for (OpSlot &s : add) {
+                sp_free(s.nz);
+                sp_free(s.val);
+            }
+            return rc ? rc : otmb_fail(ctx, OTMB_ERR_HIP, "set_slots: copying the selected slot");
+        }
+        op->slots.insert(op->slots.end(), add.begin(), add.end());
+    } else if (nslots < have) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (enqueued work may still read the slots that go; a failure changes nothing)
+        if (op->sel >= nslots) sp_select(op, 0);
+        for (i64 s = nslots; s < have; ++s) {
+            sp_free(op->slots[(size_t)s].nz);
+            sp_free(op->slots[(size_t)s].val);
+        }
+        op->slots.resize((size_t)nslots);
+    }
+    return OTMB_OK;
+}
+
+// a pointer switch: nothing is enqueued, no data moves; products, solves and preconditioners enqueued from now on read this slot
+int32_t otmb_op_select_slot(otmb_op *op, int64_t slot) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    int32_t rc;
+    if ((rc = sp_slot_arg(op, slot, "select_slot"))) return rc;
+    sp_select(op, slot);
+    return OTMB_OK;
+}
+
+int32_t otmb_op_slots(const otmb_op *op, int64_t *nslots, int64_t *selected) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    if (nslots) *nslots = (int64_t)op->slots.size();
+    if (selected) *selected = op->sel;
+    return OTMB_OK;
+}
+
+int32_t otmb_op_set_values_slot_dev(otmb_op *op, int64_t slot, const double *nzval, int64_t nnz) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    int32_t rc;
+    if ((rc = sp_slot_arg(op, slot, "set_values_slot"))) return rc;
+    return sp_set_values(op, slot, nzval, nnz, hipMemcpyDeviceToDevice);
+}
+
+int32_t otmb_op_set_values_slot(otmb_op *op, int64_t slot, const double *nzval, int64_t nnz) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    int32_t rc;
+    if ((rc = sp_slot_arg(op, slot, "set_values_slot"))) return rc;
+    return sp_set_values_host(op, slot, nzval, nnz);
 }
 
 int32_t otmb_op_mul_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *X, int64_t ldx, double *Y, int64_t ldy, double alpha, double beta) {

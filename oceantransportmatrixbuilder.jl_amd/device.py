@@ -64,11 +64,32 @@ class Operator:
     def handle(self):
         return self._h
 
-    def set_values_dev(self, nzval):
+    def set_values_dev(self, nzval, slot=None):
+        """New values from a device tensor for the selected slot, or for slot `slot` (set_slots)."""
         _on_device(nzval, self.device, "nzval")
         if nzval.dtype != torch.float64 or not nzval.is_contiguous() or nzval.numel() < self.nnz:
             raise ValueError(f"nzval: a contiguous float64 tensor of at least {self.nnz} entries is required")
-        self.ctx.check(self.lib.otmb_op_set_values_dev(self._h, nzval.data_ptr(), self.nnz))
+        if slot is None:
+            self.ctx.check(self.lib.otmb_op_set_values_dev(self._h, nzval.data_ptr(), self.nnz))
+        else:
+            self.ctx.check(self.lib.otmb_op_set_values_slot_dev(self._h, int(slot), nzval.data_ptr(), self.nnz))
+
+    set_values = set_values_dev
+
+    def set_slots(self, n):
+        """n >= 1 value slots over the one pattern (otmb_op_set_slots; api.DeviceOperator.set_slots)."""
+        self.ctx.check(self.lib.otmb_op_set_slots(self._h, int(n)))
+
+    def select(self, slot):
+        """mul, solve and precondition read slot `slot` from now on (a pointer switch)."""
+        self.ctx.check(self.lib.otmb_op_select_slot(self._h, int(slot)))
+
+    @property
+    def slots(self):
+        """(number of slots, the selected slot)."""
+        n, sel = C.c_int64(0), C.c_int64(0)
+        self.ctx.check(self.lib.otmb_op_slots(self._h, C.byref(n), C.byref(sel)))
+        return int(n.value), int(sel.value)
 
     def mul(self, X, *, alpha=1.0, beta=0.0, Y=None, adjoint=False):
         """X: 1-D or 2-D (rows x k, column-major) float64 device tensor; Y: None (a new tensor; β must be 0) or a tensor of the result's
@@ -166,6 +187,30 @@ class Operator:
         if rc != capi.NOT_CONVERGED:
             self.ctx.check(rc)
         return X, SolveInfo(rc, iters, relres, reason)
+
+    def step(self, X, *, dt, theta=1.0, nsteps=1, first_slot=0, source=None, d=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi"):
+        """nsteps θ-steps over the slots on device tensors (otmb_op_step_dev; api.DeviceOperator.step states the arguments).  X is not modified;
+        returns (a new tensor with the state after the steps, an api.StepInfo).  Nothing but the solver's column records travels to the host."""
+        from .api import StepInfo, step_arrays
+
+        pc, k, Xc, ldx, Xn = self._system(X, "X", precond)
+        Xn.copy_(X)
+        Sc, sp, lds = None, None, max(self.shape[0], 1)
+        if source is not None:
+            _on_device(source, self.device, "source")
+            if tuple(source.shape) != tuple(X.shape):
+                raise capi.OtmbError(11, f"DimensionMismatch: source of {tuple(source.shape)}, X of {tuple(X.shape)}")
+            Sc, lds = _col_major(source, self.shape[0])
+            sp = Sc.data_ptr()
+        d, dp = self._d_ptr(d)
+        iters, relres, reason = step_arrays(nsteps, k)
+        done = C.c_int64(0)
+        rc = self.lib.otmb_op_step_dev(self._h, int(bool(adjoint)), k, dp, float(dt), float(theta), int(nsteps), int(first_slot), sp, lds,
+                                       Xn.data_ptr(), max(self.shape[0], 1), float(rtol), int(maxiter), pc, C.byref(done), iters.ctypes.data,
+                                       relres.ctypes.data, reason.ctypes.data)
+        if rc != capi.NOT_CONVERGED:
+            self.ctx.check(rc)
+        return Xn, StepInfo(rc, done.value, nsteps, iters, relres, reason)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -643,11 +688,10 @@ class DeviceAssembler:
             else:
                 rec["ok"] = rec["ok"] and name in kept
 
-    def operator(self, matrix="T"):
-        """The resident operator over the result `matrix` of this assembler's output set (otmb_op_create_dev), for mul() on device
-        tensors.  Planned again unless every call since the plan left the pattern in place (see _ops_written) and nnz, the tensors and
-        their torch versions are those of the plan; otherwise, when only values can have changed, otmb_op_set_values_dev.  Pending
-        asynchronous steps are folded first (finish()).  The assembler owns the operator: it is replaced, not updated, by a re-plan."""
+    def _op_record(self, matrix):
+        """What operator() and keep_slot() decide on: (the record of the operator over `matrix` or None, whether its plan holds for the result
+        as it stands, the result's three tensors, their key).  Pending asynchronous steps are folded first (finish()).  A record whose
+        pattern cannot be vouched for but whose operator carries kept slots is compared with the copy of the pattern keep_slot took."""
         if getattr(self, "_tm_seq", None):
             self.finish()
         if self.out is None:
@@ -659,13 +703,39 @@ class DeviceAssembler:
         rec = self._ops.get(matrix)
         nnz_now = self.nnz[k] if getattr(self, "_op_last_out", None) is self.out else None
         key = ((cp.data_ptr(), cp._version), (rv.data_ptr(), rv._version))
-        if (rec is not None and rec["ok"] and rec["op"].handle.value and all(r() is t for r, t in zip(rec["refs"], (cp, rv, nz)))
-                and rec["key"] == key and nnz_now is not None and rec["op"].nnz == nnz_now):
+        live = rec is not None and bool(rec["op"].handle.value) and nnz_now is not None and rec["op"].nnz == nnz_now
+        holds = (live and rec["ok"] and all(r() is t for r, t in zip(rec["refs"], (cp, rv, nz))) and rec["key"] == key)
+        if live and not holds and rec.get("pattern") is not None:
+            self.ctx.synchronize()
+            if torch.equal(cp, rec["pattern"][0]) and torch.equal(rv[:nnz_now], rec["pattern"][1]):
+                rec.update(ok=True, dirty=True, key=key, refs=[weakref.ref(t) for t in (cp, rv, nz)])
+                holds = True
+        return rec, holds, (cp, rv, nz), key
+
+    @staticmethod
+    def _has_slots(rec):
+        return rec is not None and bool(rec["op"].handle.value) and rec["op"].slots[0] > 1
+
+    def operator(self, matrix="T"):
+        """The resident operator over the result `matrix` of this assembler's output set (otmb_op_create_dev), for mul() on device
+        tensors.  Planned again unless every call since the plan left the pattern in place (see _ops_written) and nnz, the tensors and
+        their torch versions are those of the plan; otherwise, when only values can have changed, otmb_op_set_values_dev.  Pending
+        asynchronous steps are folded first (finish()).  The assembler owns the operator: it is replaced, not updated, by a re-plan.
+        An operator with more than one slot is neither refreshed nor replaced here (either would overwrite or drop kept values): when the
+        result is newer than the selected slot this raises, and keep_slot() or forget_slots() says where the result goes."""
+        rec, holds, (cp, rv, nz), key = self._op_record(matrix)
+        if holds:
             if rec["dirty"] or rec["nzv"] != (nz.data_ptr(), nz._version):
+                if self._has_slots(rec):
+                    raise ValueError(f"the operator over {matrix} holds {rec['op'].slots[0]} slots and the result has changed since one was "
+                                     "written: keep_slot(slot) puts it into one, forget_slots() drops them")
                 rec["op"].set_values_dev(nz)
                 rec["dirty"], rec["nzv"] = False, (nz.data_ptr(), nz._version)
             self.op_reuses = getattr(self, "op_reuses", 0) + 1
             return rec["op"]
+        if self._has_slots(rec):
+            raise ValueError(f"the pattern of {matrix} changed (or cannot be shown unchanged) under an operator that holds "
+                             f"{rec['op'].slots[0]} slots: forget_slots() drops them, then the operator is planned again")
         if rec is not None:
             rec["op"].close()
         op = Operator(self.ctx, self.N, self.N, cp, rv, nz)
@@ -695,6 +765,46 @@ class DeviceAssembler:
         resident operator (Operator.solve), preconditioned by Jacobi or, precond="lines", by the grid's water columns (operator() sets them).
         Returns (X, info)."""
         return self.operator(matrix).solve(B, d=d, sigma=sigma, rtol=rtol, maxiter=maxiter, x0=x0, adjoint=adjoint, precond=precond)
+
+    def keep_slot(self, slot, nslots=None, matrix="T"):
+        """The resident result `matrix` as it stands becomes slot `slot` of its operator (the scatter from the device tensor, no host round
+        trip) and that slot is selected, so mul() and solve() go on reading the result as it stands; nslots: grow the operator to that many
+        slots first.  No other slot is written.  Built month by month, this is the year a tracer run cycles through.  The slots live on the
+        operator and share its pattern: where the library did not vouch for the pattern, it is compared with a copy taken at the first
+        keep_slot, and a result with another pattern raises (operator()) and leaves the slots as they are."""
+        rec, holds, (cp, rv, nz), _ = self._op_record(matrix)
+        if not holds:
+            self.operator(matrix)  # no operator yet: planned over this result (one with slots and another pattern: raises)
+            rec = self._ops[matrix]
+        op = rec["op"]
+        n, selected = op.slots
+        if not 0 <= int(slot) < max(n, nslots or 0):
+            raise ValueError(f"slot {slot} of {max(n, nslots or 0)}")
+        if nslots is not None and nslots > n:
+            op.set_slots(nslots)
+        if int(slot) != selected or rec["dirty"] or rec["nzv"] != (nz.data_ptr(), nz._version):
+            op.set_values_dev(nz, slot=slot)
+        op.select(slot)
+        rec["dirty"], rec["nzv"] = False, (nz.data_ptr(), nz._version)
+        if rec.get("pattern") is None:
+            self.ctx.synchronize()
+            rec["pattern"] = (cp.clone(), rv[: op.nnz].clone())
+        return op
+
+    def forget_slots(self, matrix="T"):
+        """Drop the operator over `matrix` with its slots; the next operator() / keep_slot() plans one over the result as it stands."""
+        rec = getattr(self, "_ops", {}).pop(matrix, None)
+        if rec is not None:
+            rec["op"].close()
+
+    def step_tracers(self, X, *, matrix="T", **kw):
+        """Operator.step on the resident operator over `matrix` (named apart from step(), which builds a matrix): θ-steps of the tracers X
+        through the slots keep_slot() filled, as they are -- a result built since and not kept takes no part; precond="lines" uses the
+        grid's water columns."""
+        rec = getattr(self, "_ops", {}).get(matrix)
+        if rec is None or not rec["op"].handle.value:
+            raise ValueError(f"no operator over {matrix}: keep_slot() first")
+        return rec["op"].step(X, **kw)
 
     def _kept_steady(self):
         """The operators a step of this loop does not store: those the last call kept, or -- after a full write that left the promise live -- those

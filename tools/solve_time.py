@@ -16,6 +16,17 @@ Systems (B = 1, rtol = 1e-10):
 Each line: iterations, reason, relres, the median / min / max wall time of --reps solves after one warm-up (time.perf_counter around the
 call, which waits for the device), the time per iteration, and the time of two otmb_op_mul_dev products on the same operator (HIP events):
 the floor of an iteration, whose five vector passes and scalar kernels the fusion is to keep small.
+--step [--step-route step|compose|both]: the time loop instead of the solves above -- T of the 1 degree preset and eleven copies of it
+    scaled by 1 + 0.02·m as twelve monthly matrices, k = 1, precond = lines, θ = 1, δt = 30 d, 24 steps (two years) from X = 1, the median
+    of --reps after one warm-up.  Route `step`: the twelve matrices in value slots, ONE otmb_op_step_dev call.  Route `compose`: the same
+    24 steps in the public device calls there were before the slots -- otmb_op_set_values_dev of the month's values, the right-hand side
+    σ·x as a torch operation, otmb_op_solve_pc_dev from x -- which is what runs against a library of an earlier commit as well (it uses
+    no newer symbol: --lib PATH loads another build of the library, an earlier commit's for the baseline).  The solve is called in place on
+    one X (no allocation or copy per step that the step call would not make either).  The record also times, around this process's calls:
+    a slot's first visit as otmb_op_precond_dev (setup plus one sweep and one wait, the upper bound of above), one solve with its setup, one
+    step call of one step, and from these a later visit (right-hand side plus solve).  rhs_torch_us is the COMPOSITION's right-hand side,
+    torch's σ·x (HIP events around 24 of them); the step call's own right-hand-side kernel has no entry point to time it through and is
+    read from a kernel trace of `--step --step-route step` instead.  The record carries the device memory the slots take.
 --host: the parent's only route as well -- result_to_host, then scipy.sparse.linalg.bicgstab with the same (Jacobi) preconditioner."""
 import argparse
 import json
@@ -55,6 +66,98 @@ def two_products(op, n, reps=30):
     return float(np.median(out))
 
 
+def step_times(asm, a):
+    nslots, nsteps, dt = 12, 24, 30 * DAY
+    N = asm.N
+    cp, rv, nz = asm.out["T"]
+    nnz = int(cp[N].item()) - 1
+    months = [(nz[:nnz] * (1.0 + 0.02 * m)).contiguous() for m in range(nslots)]
+    nxt = asm.vertical_lines()
+    x0 = torch.ones(N, dtype=torch.float64, device="cuda")
+    sigma = 1.0 / (1.0 * dt)
+    routes = ["step", "compose"] if a.step_route == "both" else [a.step_route]
+    recs = []
+    for route in routes:
+        free0 = torch.cuda.mem_get_info()[0]
+        op = Operator(asm.ctx, N, N, cp, rv, months[0])
+        op.set_lines(nxt)
+        rec = {"what": "24 monthly steps, T", "route": route, "n": N, "nnz": nnz, "nslots": nslots, "nsteps": nsteps, "precond": "lines",
+               "theta": 1.0, "dt_s": dt, "reps": a.reps}
+        if route == "step":
+            torch.cuda.synchronize()
+            free1 = torch.cuda.mem_get_info()[0]
+            op.set_slots(nslots)
+            for m in range(nslots):
+                op.set_values_dev(months[m], slot=m)
+            torch.cuda.synchronize()
+            rec["slots_bytes"] = int(free1 - torch.cuda.mem_get_info()[0])  # the eleven slots beyond the operator's own
+            rec["slot_bytes_exact"] = 8 * nnz  # + 8 x (the row layout's entries, padding included), per slot
+        times, its = [], None
+        for r in range(a.reps + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if route == "step":
+                X, info = op.step(x0, dt=dt, theta=1.0, nsteps=nsteps, first_slot=0, rtol=1e-10, maxiter=a.maxiter, precond="lines")
+                its = info.iterations[:, 0].tolist()
+                assert info.steps_done == nsteps, info
+            else:
+                X, B, its = x0.clone(), torch.empty_like(x0), []
+                it1, rr1, why1 = np.zeros(1, dtype=np.int64), np.zeros(1), np.zeros(1, dtype=np.int32)
+                for t in range(nsteps):
+                    op.set_values_dev(months[t % nslots])
+                    torch.mul(X, sigma, out=B)
+                    rc = op.lib.otmb_op_solve_pc_dev(op.handle, 0, 1, None, sigma, B.data_ptr(), N, X.data_ptr(), N, 1, 1e-10, a.maxiter,
+                                                     it1.ctypes.data, rr1.ctypes.data, why1.ctypes.data, 1)  # in place, from X, "lines"
+                    assert rc == 0, (rc, t, int(why1[0]))
+                    its.append(int(it1[0]))
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        times = times[1:]
+        rec.update(iterations=its, median_s=float(np.median(times)), min_s=float(np.min(times)), max_s=float(np.max(times)),
+                   per_step_us=float(np.median(times)) / nsteps * 1e6, checksum=float(X.sum().item()))
+        # the parts of a step that calls of this process can bracket: the composition's right-hand side (torch's), a slot's first visit, a solve
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        for _ in range(nsteps):
+            B = sigma * x0
+        ev[1].record()
+        ev[1].synchronize()
+        rec["rhs_torch_us"] = ev[0].elapsed_time(ev[1]) * 1e3 / nsteps
+        tp = []
+        for r in range(a.reps + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            op.precondition(x0, sigma=sigma)
+            torch.cuda.synchronize()
+            tp.append(time.perf_counter() - t0)
+        rec["first_visit_upper_bound_us"] = float(np.median(tp[1:])) * 1e6  # setup + one sweep + one wait
+        ts = []
+        for r in range(a.reps + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            op.solve(sigma * x0, sigma=sigma, rtol=1e-10, maxiter=a.maxiter, x0=x0, precond="lines")
+            ts.append(time.perf_counter() - t0)
+        rec["one_solve_us"] = float(np.median(ts[1:])) * 1e6  # setup included, as the composition pays it
+        if route == "step":
+            ts1 = []
+            for r in range(a.reps + 1):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                op.step(x0, dt=dt, nsteps=1, rtol=1e-10, maxiter=a.maxiter, precond="lines")
+                ts1.append(time.perf_counter() - t0)
+            rec["one_step_call_us"] = float(np.median(ts1[1:])) * 1e6  # first visit + right-hand side + solve
+            rec["later_visit_us"] = (rec["median_s"] * 1e6 - nslots * rec["one_step_call_us"]) / (nsteps - nslots)  # right-hand side + solve
+        recs.append(rec)
+        print(json.dumps(rec), flush=True)
+        op.close()
+        del op
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            for r in recs:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -63,7 +166,14 @@ def main():
     ap.add_argument("--precond", default="jacobi", choices=["jacobi", "lines", "both"])
     ap.add_argument("--year", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--step", action="store_true")
+    ap.add_argument("--step-route", default="both", choices=["step", "compose", "both"])
+    ap.add_argument("--lib", default=None)
     a = ap.parse_args()
+    if a.lib:
+        from otmb_amd import capi
+
+        capi.use_library(os.path.abspath(a.lib), lenient=True)
     import scipy.sparse as sp
     import scipy.sparse.linalg as spla
 
@@ -76,6 +186,8 @@ def main():
     vmo = torch.from_numpy(np.asfortranarray(g.vmo.data).ravel(order="F")).cuda()
     asm.step(umo, vmo, 1e20)
     N = asm.N
+    if a.step:
+        return step_times(asm, a)
     t0 = time.perf_counter()
     h = asm.result_to_host()["T"]
     t_download = time.perf_counter() - t0
