@@ -70,3 +70,60 @@ def step_ref(n, colptr, rowval, values, X, *, dt, theta=1.0, nsteps=1, first_slo
             break
         info["steps_done"] = t + 1
     return X, info
+
+
+STEP_LINE_OPS = 7  # the elementwise operations of st_line (csrc/otmb_step.hip): d·x, + w, c·e, σ·x, s/θ, + (s/θ), - c·e
+
+
+def step_rhs_scale(A_slot, X_prev, S, d, dt, theta, adjoint):
+    """σ·|x| + |s|/θ + ((1 - θ)/θ)·(|d|∘|x| + |A|·|x|): the magnitudes of the terms of a step's right-hand side, per entry."""
+    import scipy.sparse as sp
+
+    Aop = sp.csr_matrix(A_slot.T if adjoint else A_slot)
+    X = np.abs(np.asarray(X_prev, dtype=np.float64).reshape(Aop.shape[0], -1))
+    n, k = X.shape
+    s = np.zeros((n, k)) if S is None else np.abs(np.asarray(S, dtype=np.float64).reshape(n, k))
+    dd = np.zeros(n) if d is None else np.abs(np.asarray(d, dtype=np.float64))
+    return X / (theta * dt) + s / theta + ((1.0 - theta) / theta) * (dd[:, None] * X + abs(Aop) @ X)
+
+
+def step_residual_check(A_slot, X_prev, X_next, S, d, dt, theta, adjoint, rtol):
+    """One θ-step checked without the library's word, per column: -> (‖b(x) - M·x⁺‖₂, bound), everything in float64 with scipy's products.
+
+    The system is written down here from the differential equation, not from the header: the θ-method of ∂x/∂t + (diag(d) + A)·x = s is
+    (x⁺ - x)/δt + θ·(diag(d) + A)·x⁺ + (1 - θ)·(diag(d) + A)·x = s; divided by θ,
+        M·x⁺ = b(x),   M = I/(θ·δt) + diag(d) + A,   b(x) = x/(θ·δt) + s/θ - ((1 - θ)/θ)·(diag(d)·x + A·x)      (adjoint: Aᵀ for A).
+    A_slot: the step's matrix (scipy sparse); X_prev, X_next: the states before and after it; S, d: None or arrays.
+
+    bound = solve_ref.residual_check's for (M, x⁺, b) -- rtol·‖b‖₂ + 2·(L + 3)·ε·‖ |M|·|x⁺| + |b| ‖₂ --
+            + 2·(L + c)·ε·‖ σ·|x| + |s|/θ + ((1 - θ)/θ)·(|d|∘|x| + |A|·|x|) ‖₂,   c = STEP_LINE_OPS = 7.
+    The second term is what forming b twice, here and on the device, in different orders can differ by.  Its constant is counted on the code,
+    not fitted: a term of b goes through the fold of its row (at most L products and L additions: relative error γ_L; only the A·x term),
+    then through operations of st_line, each one rounding -- d·x: (d·x), (+ w), (c·e), (a - ce): 4;  A·x: (+ d·x), (c·e), (a - ce): 3;
+    σ·x: (σ·x), (+ s/θ), (a - ce): 3;  s/θ: (s/θ), (+), (a - ce): 3 -- and carries the roundings of its constant: σ = 1/(θ·δt) two, c =
+    (1 - θ)/θ two (this side may form them in another way, so they count).  The deepest term is A·x with L + 3 + 2 = L + 5 roundings, below
+    L + 7 = L + the seven operations st_line has in all; so each side is within γ_{L+5}·scale ≤ (L + 7)·ε·scale entrywise (the two spare ε
+    cover γ's second order and the device's rtol·‖b_device‖₂ against this side's rtol·‖b‖₂), and the two sides within twice that.  θ = 1 has
+    two operations and no product: the same bound holds with room."""
+    import scipy.sparse as sp
+
+    A = sp.csc_matrix(A_slot)
+    n = A.shape[0]
+    Aop = (A.T if adjoint else A).tocsr()
+    Xp = np.asarray(X_prev, dtype=np.float64).reshape(n, -1)
+    Xn = np.asarray(X_next, dtype=np.float64).reshape(n, -1)
+    sigma = 1.0 / (theta * dt)
+    B = Xp / (theta * dt)
+    if S is not None:
+        B = B + np.asarray(S, dtype=np.float64).reshape(n, -1) / theta
+    if theta != 1:
+        E = Aop @ Xp
+        if d is not None:
+            E = E + np.asarray(d, dtype=np.float64)[:, None] * Xp
+        B = B - ((1.0 - theta) / theta) * E
+    scale = step_rhs_scale(A, Xp, S, d, dt, theta, adjoint)
+    L = R.longest(A, adjoint)
+    out = []
+    for c, (res, bound) in enumerate(R.residual_check(A, Xn, B, d, sigma, adjoint, rtol)):
+        out.append((res, bound + 2 * (L + STEP_LINE_OPS) * R.EPS * np.linalg.norm(scale[:, c])))
+    return out

@@ -379,3 +379,101 @@ def test_the_device_route_has_the_same_bits():
         O.select(1)
         D.select(1)
         _same_bits(O.mul(Xd).cpu().numpy(), D.mul(X0), "select on the device route")
+
+
+# ---- the step without the library's word -------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def chain_grids(oracle):
+    """Per grid: the operator with the tests' three slots and the grid's water columns, and what scipy needs to judge it."""
+    made = {}
+
+    def get(name):
+        if name not in made:
+            T, N, nsurf, nxt = LR.grid(oracle, name)
+            made[name] = (_operator(N, *T, nxt=nxt), N, T, R.shift("age", N, nsurf)[0])
+        return made[name]
+
+    yield get
+    for D, *_ in made.values():
+        D.close()
+
+
+@pytest.mark.parametrize("precond", ["jacobi", "lines"])
+@pytest.mark.parametrize("adjoint", [False, True])
+@pytest.mark.parametrize("theta", [1.0, 0.5])
+@pytest.mark.parametrize("name", ["odd_nx_fold", "tiny_tripolar"])
+def test_every_step_against_scipy_and_the_chain_against_one_call(chain_grids, name, theta, adjoint, precond):
+    """Four steps of one month from slot 2 over three slots, the age d, a source of scale 1e-7, k = 3, as four nsteps = 1 calls fed into
+    each other with first_slot advanced by hand: every pair (X_{t-1}, X_t) meets step_ref.step_residual_check -- the θ-method written down
+    from the differential equation, in float64 with scipy's matrix of THAT slot, and a bound that is derived there -- which pins the slot
+    order, the adjoint, θ = 1, Jacobi and the constants σ, s/θ and (1 - θ)/θ without step_ref.rhs or any call of the library.  Then ONE
+    nsteps = 4 call returns X_4's bits and the same iteration rows: the multi-step call is tied to the checked chain."""
+    D, N, (p, i, v), d = chain_grids(name)
+    values = SR.slot_values(v, seed=1)
+    S = np.asfortranarray(np.random.default_rng(91).standard_normal((N, 3)) * 1e-7)
+    X0 = _start(N, 3, 92)
+    kw = dict(dt=SR.MONTH, theta=theta, source=S, d=d, adjoint=adjoint, precond=precond, rtol=RTOL, maxiter=MAXITER)
+    X, rows = X0, []
+    for t in range(4):
+        slot = (FIRST + t) % 3
+        Xn, info = D.step(X, nsteps=1, first_slot=slot, **kw)
+        assert info.status == 0 and info.steps_done == 1, (name, t, info)
+        rows.append(info.iterations[0])
+        A = R.csc_of(N, N, p, i, values[slot])
+        for c, (res, bound) in enumerate(SR.step_residual_check(A, X, Xn, S, d, SR.MONTH, theta, adjoint, RTOL)):
+            print(name, theta, adjoint, precond, "step", t, "slot", slot, "column", c, "iterations", int(info.iterations[0][c]), "residual", res,
+                  "bound", bound)
+            assert res <= bound, (name, t, c, res, bound)
+        X = Xn
+    X4, info = D.step(X0, nsteps=4, first_slot=FIRST, **kw)
+    assert info.status == 0 and info.steps_done == 4, info
+    _same_bits(X4, X, (name, "one call of four steps"))
+    assert np.array_equal(np.asarray(info.iterations), np.asarray(rows)), (info.iterations, rows)
+    assert D.slots == (3, 0)
+
+
+@pytest.mark.parametrize("precond", ["jacobi", "lines"])
+def test_a_steady_state_is_a_fixed_point_of_the_step(oracle, precond):
+    """(diag(d) + A)·x* = s (the steady ideal age on odd_nx_fold: s = 1, x* by scipy's LU with one refinement): in exact arithmetic
+    b - M·x* = (s - (diag(d) + A)·x*)/θ whatever σ is, so three steps from x* over three slots that all hold T take NO iteration and return
+    x*'s bits, for θ = 1, 0.5, 0.25 and δt = a day, a month.  A wrong s/θ, (1 - θ)/θ or σ on either side of the system breaks it, and nothing
+    here goes through step_ref.rhs.  tests/test_step_ref.py (the test of the same name) shows on the CPU that every pair starts a factor 100
+    below rtol and that no summation order can close that margin: all six pairs pass there, none is dropped."""
+    import otmb_amd.api as api
+    from test_step_ref import FIXED_POINT_PAIRS, steady_age
+
+    T, N, nxt, d, s, x = steady_age(oracle)
+    with api.DeviceOperator(_csc(N, *T)) as D:
+        D.set_slots(3)  # (every new slot is a copy of the selected one: three times T)
+        D.set_lines(nxt)
+        for theta, dt in FIXED_POINT_PAIRS:
+            X, info = D.step(x, dt=dt, theta=theta, nsteps=3, first_slot=0, source=s, d=d, rtol=RTOL, maxiter=MAXITER, precond=precond)
+            print("theta", theta, "dt", dt, precond, "iterations", np.asarray(info.iterations).tolist(), "relres", np.asarray(info.relres).tolist())
+            assert info.status == 0 and info.steps_done == 3, (theta, dt, info)
+            assert (np.asarray(info.iterations) == 0).all(), (theta, dt, info.iterations)
+            _same_bits(X, x, (theta, dt, "x* is a fixed point"))
+
+
+@pytest.mark.parametrize("precond", [0, 1])
+@pytest.mark.parametrize("adjoint", [0, 1])
+def test_a_nan_column_stops_the_call_and_spares_its_neighbours(small, adjoint, precond):
+    """k = 3 with one NaN in column 1 of the start, θ = 0.5, nsteps = 3: OTMB_ERR_NOT_CONVERGED at step 0, steps_done = 0, reasons
+    (converged, nonfinite, converged); column 1 is left as it was, columns 0 and 2 have the bits and the iterations of a clean one-step call
+    on those two columns, and the report rows of the steps that never ran keep their sentinels."""
+    D, N, dage = small
+    X0 = _start(N, 3, 95)
+    X0[5, 1] = np.nan
+    S = np.asfortranarray(np.random.default_rng(96).standard_normal((N, 3)) * 1e-7)
+    X = X0.copy(order="F")
+    rc, done, it, rr, why = _step_c(D, X, N, 3, S=S, lds=N, d=dage, theta=0.5, nsteps=3, first_slot=FIRST, precond=precond, adjoint=adjoint)
+    assert rc == 19 and done == 0, (rc, done)
+    assert why[0].tolist() == [0, 3, 0], why
+    assert it[0, 1] == 0 and np.isnan(rr[0, 1]) and (rr[0, [0, 2]] <= RTOL).all(), (it, rr)
+    assert (it[1:] == -7).all() and (why[1:] == -7).all() and (rr[1:] == 7.25).all()
+    _same_bits(X[:, 1], X0[:, 1], "the NaN column is left as it was")
+    clean, info = D.step(X0[:, [0, 2]], dt=SR.MONTH, theta=0.5, nsteps=1, first_slot=FIRST, source=S[:, [0, 2]], d=dage, rtol=RTOL, maxiter=MAXITER,
+                         precond=("jacobi", "lines")[precond], adjoint=bool(adjoint))
+    assert info.status == 0 and info.steps_done == 1
+    _same_bits(X[:, [0, 2]], clean, "the clean columns")
+    assert np.array_equal(it[0, [0, 2]], info.iterations[0])
+    assert D.slots == (3, 0)

@@ -113,3 +113,77 @@ def test_a_step_that_does_not_converge_ends_the_call(oracle):
     for bad in (dict(dt=0.0), dict(dt=1.0, theta=0.0), dict(dt=1.0, theta=1.5), dict(dt=1.0, nsteps=-1), dict(dt=1.0, first_slot=3)):
         with pytest.raises(ValueError):
             SR.step_ref(N, p, i, SR.slot_values(v), X0, **bad)
+
+
+@pytest.mark.parametrize("theta", [1.0, 0.5])
+@pytest.mark.parametrize("name,lines", [("odd_nx_fold", False), ("odd_nx_fold", True), ("tiny_tripolar", False), ("tiny_tripolar", True)])
+def test_step_residual_check_on_the_restatements_trajectory(oracle, name, lines, theta):
+    """step_ref.step_residual_check (the helper tests/test_step.py judges the device's steps with) on the restatement's own four steps from
+    slot 2, A and Aᵀ, the age d, a source of scale 1e-7, k = 3: every (X_{t-1}, X_t) pair meets the bound with its slot's matrix.  And the
+    helper can tell: with another slot's matrix, with the adjoint flipped, with another θ or without the source the same pair exceeds it."""
+    T, N, nsurf, nxt = LR.grid(oracle, name)
+    p, i, v = T
+    values = SR.slot_values(v, seed=1)
+    d = R.shift("age", N, nsurf)[0]
+    S = np.asfortranarray(np.random.default_rng(11).standard_normal((N, 3)) * 1e-7)
+    for adjoint in (False, True):
+        X0 = _start(N, 3, 12)
+        X, info = SR.step_ref(N, p, i, values, X0, dt=SR.MONTH, theta=theta, nsteps=4, first_slot=2, source=S, d=d, rtol=RTOL, maxiter=5000,
+                              adjoint=adjoint, next=nxt if lines else None)
+        assert info["steps_done"] == 4
+        Xprev = X0
+        for t, (slot, _, Xt) in enumerate(info["systems"]):
+            assert slot == (2 + t) % 3
+            A = R.csc_of(N, N, p, i, values[slot])
+            for c, (res, bound) in enumerate(SR.step_residual_check(A, Xprev, Xt, S, d, SR.MONTH, theta, adjoint, RTOL)):
+                print(name, "lines", lines, "theta", theta, "adjoint", adjoint, "step", t, "column", c, "residual", res, "bound", bound)
+                assert res <= bound
+            wrong = [dict(A=R.csc_of(N, N, p, i, values[(slot + 1) % 3])), dict(adjoint=not adjoint), dict(theta=0.75), dict(S=None)]
+            for kw in wrong:
+                a = dict(A=A, S=S, theta=theta, adjoint=adjoint)
+                a.update(kw)
+                out = SR.step_residual_check(a["A"], Xprev, Xt, a["S"], d, SR.MONTH, a["theta"], a["adjoint"], RTOL)
+                assert all(res > bound for res, bound in out), (t, sorted(kw), out)
+            Xprev = Xt
+
+
+# the (θ, δt) pairs of the fixed-point test (tests/test_step.py: test_a_steady_state_is_a_fixed_point_of_the_step has the same list)
+FIXED_POINT_PAIRS = [(theta, dt) for theta in (1.0, 0.5, 0.25) for dt in (R.DAY, SR.MONTH)]
+
+
+def steady_age(oracle, name="odd_nx_fold"):
+    """The steady ideal age on a grid: (T's arrays, N, next, d, s = 1, x*) with x* from scipy's sparse LU of diag(d) + A and one step of
+    iterative refinement in float64."""
+    T, N, nsurf, nxt = LR.grid(oracle, name)
+    d = R.shift("age", N, nsurf)[0]
+    M0 = (sp.diags(d) + R.csc_of(N, N, *T)).tocsc()
+    lu = spla.splu(M0)
+    s = np.ones(N)
+    x = lu.solve(s)
+    x = x + lu.solve(s - M0 @ x)
+    return T, N, nxt, d, s, x
+
+
+@pytest.mark.parametrize("theta,dt", FIXED_POINT_PAIRS)
+def test_a_steady_state_is_a_fixed_point_of_the_step(oracle, theta, dt):
+    """The CPU twin of the device test of the same name: with (diag(d) + A)·x* = s, b - M·x* = (s - (diag(d) + A)·x*)/θ whatever σ is, so a
+    step from x* needs no iteration -- if the constants are right.  So that the device test can neither fail nor pass for a reason of
+    rounding, two margins are asserted here for every (θ, δt) it runs, with rtol = 1e-10:
+      * the restatement starts every one of three steps at a relative residual ≤ rtol/100 (and so takes no iteration and returns x*'s bits);
+      * (L + c)·ε·‖ |M|·|x*| + |b| ‖₂ ≤ rtol·‖b‖₂/100 with c = step_ref.STEP_LINE_OPS: whatever order the device sums b and M·x* in, its
+        residual differs from the restatement's by far less than the margin the first line leaves."""
+    T, N, nxt, d, s, x = steady_age(oracle)
+    p, i, v = T
+    sigma, cc = SR.constants(dt, theta)
+    for lines in (False, True):
+        X, info = SR.step_ref(N, p, i, [v, v, v], x, dt=dt, theta=theta, nsteps=3, source=s, d=d, rtol=RTOL, next=nxt if lines else None)
+        print("theta", theta, "dt", dt, "lines", lines, "relres", [float(r[0]) for r in info["relres"]])
+        assert info["steps_done"] == 3 and all(int(it[0]) == 0 for it in info["iterations"])
+        assert all(float(r[0]) <= RTOL / 100 for r in info["relres"])
+        assert np.array_equal(X, x)
+    A = R.csc_of(N, N, p, i, v)
+    M = R.system(A, d, sigma, False)
+    b = info["systems"][0][1]
+    rounding = (R.longest(A, False) + SR.STEP_LINE_OPS) * R.EPS * np.linalg.norm(abs(M) @ np.abs(x) + np.abs(b))
+    print("theta", theta, "dt", dt, "rounding bound", rounding, "rtol·‖b‖/100", RTOL * np.linalg.norm(b) / 100)
+    assert rounding <= RTOL * np.linalg.norm(b) / 100
