@@ -53,6 +53,16 @@ static int32_t op_download(otmb_ctx *ctx, double *host, i64 ld, const double *de
     HIP_TRY(ctx, hipMemcpy2DAsync(host, (size_t)ld * 8, dev, (size_t)rows * 8, (size_t)rows * 8, (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
     return OTMB_OK;
 }
+// The tail of a host entry point that returns rc: the staged result (rows x k at dev; no rows: nothing) comes back and the stream is waited
+// for.  The context's message is rc's (a solver's report of columns that did not converge) and still is afterwards.
+static int32_t op_finish(otmb_ctx *ctx, int32_t rc, double *host, i64 ld, const double *dev, i64 rows, i64 k) {
+    const std::string msg = ctx->err;
+    int32_t rcd;
+    if (rows > 0 && (rcd = op_download(ctx, host, ld, dev, rows, k))) return rcd;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->err = msg;
+    return rc;
+}
 // xs and ys for staged matrices of rx x k and ry x k (never empty buffers)
 static int32_t op_reserve_xy(otmb_op *op, i64 rx, i64 ry, i64 k) {
     int32_t rc;

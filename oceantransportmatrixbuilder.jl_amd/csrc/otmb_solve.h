@@ -1,5 +1,5 @@
-// otmb_solve.h -- what the solver (otmb_solve.hip) and its line preconditioner (otmb_solve_lines.hip) share: a column's record and
-// state, the register block of right-hand sides, and the host entry points of the line kernels.
+// otmb_solve.h -- what the solver (otmb_solve.hip), its line preconditioner (otmb_solve_lines.hip) and the step (otmb_step.hip) share: a
+// column's record and state, the register block of right-hand sides, the preconditioner's record and the host entry points around it.
 #pragma once
 #include "otmb_op.h"
 
@@ -13,25 +13,36 @@ struct SvCol {  // one column's record (device; the host reads all k of them)
     i64 iters;
 };
 
-// The line preconditioner (otmb_solve_lines.hip); both enqueue on the context's stream and need op->lines.
-// ln_factor: u, l from the CSC copy, then pivots and multipliers head to tail.  diag: Jacobi's diagonal (a).  m, u, piv: n doubles each.
-//            *bad (preset to ~0) receives the smallest 0-based index whose pivot is zero or not finite.
-// ln_sweep:  Z = P⁻¹·Y for the columns whose record is SV_ACTIVE (cs == nullptr: every column).  Y and Z may be the same array.
-void ln_factor(otmb_op *op, int adjoint, const double *diag, double *m, double *u, double *piv, unsigned long long *bad);
-void ln_sweep(otmb_op *op, const SvCol *cs, i64 k, const double *m, const double *u, const double *piv, const double *Y, i64 ldy, double *Z,
-              i64 ldz);
-
-// A prepared preconditioner: sh = σ + d, diag (Jacobi's diagonal) and, for the lines, the multipliers, u and the pivots -- n doubles each
-// (m, u, piv: null for Jacobi).  For a fixed (values, d, σ, adjoint) the arrays are always the same bits, so otmb_op_step (otmb_step.hip)
-// computes them once per slot and call.
+// A preconditioner: sh = σ + d, diag (Jacobi's diagonal) and, for the lines, the multipliers, u and the pivots -- n doubles each (m, u, piv:
+// null for Jacobi).  For a fixed (values, d, σ, adjoint) the arrays are always the same bits, so otmb_op_step (otmb_step.hip) computes them
+// once per slot and call.
 struct SvPrec {
     double *sh, *diag, *m, *u, *piv;
 };
+// the record's arrays in a block of (lines ? 5 : 2) * n doubles: sh | diag | m | u | piv
+static inline SvPrec sv_prec_carve(double *a, i64 n, bool lines) {
+    return {a, a + n, lines ? a + 2 * n : nullptr, lines ? a + 3 * n : nullptr, lines ? a + 4 * n : nullptr};
+}
+
+// The line preconditioner (otmb_solve_lines.hip); both enqueue on the context's stream and need op->lines.
+// ln_factor: p.u, l from the CSC copy, then p.piv and p.m head to tail, from p.diag (Jacobi's diagonal, a).
+//            *bad (preset to ~0) receives the smallest 0-based index whose pivot is zero or not finite.
+// ln_sweep:  Z = P⁻¹·Y for the columns whose record is SV_ACTIVE (cs == nullptr: every column).  Y and Z may be the same array.
+void ln_factor(otmb_op *op, int adjoint, const SvPrec &p, unsigned long long *bad);
+void ln_sweep(otmb_op *op, const SvCol *cs, i64 k, const SvPrec &p, const double *Y, i64 ldy, double *Z, i64 ldz);
+
 // sv_prec_prepare: computes p's arrays from the SELECTED values; a singular preconditioner is refused (OTMB_ERR_SINGULAR_PRECONDITIONER).
 //                  Waits for the device.
-// sv_solve:        otmb_op_solve_pc_dev without its argument checks; prep != nullptr: d and σ are not read, the preconditioner is prep's.
+// sv_solve:        otmb_op_solve_pc_dev (n > 0) after its argument checks and its preconditioner: p is prepared, for this adjoint and
+//                  precond and for the call's d, σ and selected values.
 // sv_check_step:   the argument checks the step shares with the solver (S may be null), then `more`, then the preconditioner.
 int32_t sv_prec_prepare(otmb_op *op, int adjoint, int32_t precond, const double *d, double sigma, const SvPrec &p);
-int32_t sv_solve(otmb_op *op, int adjoint, i64 k, const double *d, double sigma, const double *B, i64 ldb, double *X, i64 ldx, int use_x0, double rtol,
-                 i64 maxiter, int64_t *iters, double *relres, int32_t *reason, int32_t precond, const SvPrec *prep);
+int32_t sv_solve(otmb_op *op, int adjoint, i64 k, const SvPrec &p, const double *B, i64 ldb, double *X, i64 ldx, int use_x0, double rtol, i64 maxiter,
+                 int64_t *iters, double *relres, int32_t *reason, int32_t precond);
 int32_t sv_check_step(otmb_op *op, int32_t precond, int64_t k, const double *S, int64_t lds, double *X, int64_t ldx, const char *more);
+
+// the report of an empty system (n = 0): every entry converged at once
+static inline int32_t sv_report_empty(i64 entries, int64_t *iters, double *relres, int32_t *reason) {
+    for (i64 e = 0; e < entries; ++e) { iters[e] = 0; relres[e] = 0.0; reason[e] = OTMB_SOLVE_CONVERGED; }
+    return OTMB_OK;
+}

@@ -406,30 +406,30 @@ __global__ __launch_bounds__(256) void sv_scalar_kernel(SvCol *__restrict__ cs, 
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-struct SvWork {  // the solver's device arrays inside op->sw (m, u, piv: the line preconditioner's, otherwise null)
-    double *sh, *diag, *m, *u, *piv, *r, *rh, *p, *v, *s, *t, *ph, *sh_, *part, *parts;
+struct SvWork {  // the solver's device arrays inside op->sw
+    SvPrec pc;    // the preconditioner the kernels read: the workspace's own block, or one prepared elsewhere (sv_solve)
+    double *r, *rh, *p, *v, *s, *t, *ph, *sh_, *part, *parts;
     SvCol *cs;
     unsigned long long *bad;  // [2]: the diagonal's, the pivots'
     i64 np;
 };
-// reserves op->sw and carves it for k columns with np partials each; k = 0: the preconditioner's arrays alone (otmb_op_precond_dev)
-static int32_t sv_work(otmb_op *op, bool lines, i64 k, i64 np, SvWork &w) {
-    const size_t n = (size_t)op->n, vec = n * (size_t)k, parts = (size_t)np * (size_t)k;
-    const size_t doubles = (lines ? 5 : 2) * n + 8 * vec + 3 * parts;
+// selects the operator's device, reserves op->sw and carves it for k columns (k = 0: the preconditioner's arrays alone, otmb_op_precond_dev)
+// with np = (n + 63) / 64 partials per column and quantity: the adjoint's kernels write np of them, the rows' and the vector kernels fewer
+static int32_t sv_work(otmb_op *op, int32_t precond, i64 k, SvWork &w) {
+    HIP_TRY(op->ctx, hipSetDevice(op->device));
+    const bool lines = precond == OTMB_PRECOND_LINES;
+    const size_t n = (size_t)op->n, vec = n * (size_t)k, np = (n + 63) / 64, parts = np * (size_t)k, pre = (lines ? 5 : 2) * n;
+    const size_t doubles = pre + 8 * vec + 3 * parts;
     int32_t rc;
     if ((rc = otmb_reserve(op->ctx, op->sw, doubles * 8 + (size_t)k * sizeof(SvCol) + 64))) return rc;
     double *q = (double *)op->sw.p;
-    w.sh = q; q += n;
-    w.diag = q; q += n;
-    w.m = w.u = w.piv = nullptr;
-    if (lines)
-        for (double **v : {&w.m, &w.u, &w.piv}) { *v = q; q += n; }
+    w.pc = sv_prec_carve(q, op->n, lines); q += pre;
     for (double **v : {&w.r, &w.rh, &w.p, &w.v, &w.s, &w.t, &w.ph, &w.sh_}) { *v = q; q += vec; }
     w.part = q; q += 2 * parts;
     w.parts = q; q += parts;
     w.bad = (unsigned long long *)q; q += 2;
     w.cs = (SvCol *)q;
-    w.np = np;
+    w.np = (i64)np;
     return OTMB_OK;
 }
 
@@ -443,39 +443,34 @@ __global__ __launch_bounds__(256) void sv_scale_kernel(i64 n, const double *__re
     for (int c = 0; c < KB; ++c) Z[i + c * ldz] = Y[i + c * ldy] / dg;
 }
 
-// sh and diag and, with lines, u, the multipliers and the pivots; a singular preconditioner is refused here, before anything of the
-// caller's is touched.  Waits for the device.
-static int32_t sv_precond_setup(otmb_op *op, const SvWork &w, int adjoint, int32_t precond, const double *d, double sigma) {
+// p's arrays -- sh and diag and, with lines, u, the multipliers and the pivots -- with flags[2] (device) for the verdict: a singular
+// preconditioner is refused here, before anything of the caller's is touched.  Waits for the device.
+static int32_t sv_precond_setup(otmb_op *op, int adjoint, int32_t precond, const double *d, double sigma, const SvPrec &p, unsigned long long *flags) {
     otmb_ctx *ctx = op->ctx;
     hipStream_t st = ctx->stream;
     const i64 n = op->n;
-    HIP_TRY(ctx, hipMemsetAsync(w.bad, 0xff, 16, st));
+    HIP_TRY(ctx, hipMemsetAsync(flags, 0xff, 16, st));
     hipLaunchKernelGGL(sv_diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const i64 *)op->cp.p, (const int *)op->rv.p,
-                       (const double *)op->nz.p, n, d, sigma, w.sh, w.diag, w.bad);
-    if (precond == OTMB_PRECOND_LINES) ln_factor(op, adjoint, w.diag, w.m, w.u, w.piv, w.bad + 1);
+                       (const double *)op->nz.p, n, d, sigma, p.sh, p.diag, flags);
+    if (precond == OTMB_PRECOND_LINES) ln_factor(op, adjoint, p, flags + 1);
     HIP_TRY(ctx, hipGetLastError());
     unsigned long long bad[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(bad, w.bad, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(bad, flags, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
+    const int lines = precond == OTMB_PRECOND_LINES;  // the flag that decides: the pivots' with lines, otherwise the diagonal's
+    if (bad[lines] == ~0ull) return OTMB_OK;
     char msg[128];
-    if (precond == OTMB_PRECOND_JACOBI && bad[0] != ~0ull) {
-        snprintf(msg, sizeof msg, "diag(M)[%lld] is zero or not finite (1-based; the first such index)", (long long)bad[0] + 1);
-        return otmb_fail(ctx, OTMB_ERR_SINGULAR_PRECONDITIONER, msg);
-    }
-    if (precond == OTMB_PRECOND_LINES && bad[1] != ~0ull) {
-        snprintf(msg, sizeof msg, "pivot[%lld] of the line factorisation is zero or not finite (1-based; the smallest such index)", (long long)bad[1] + 1);
-        return otmb_fail(ctx, OTMB_ERR_SINGULAR_PRECONDITIONER, msg);
-    }
-    return OTMB_OK;
+    snprintf(msg, sizeof msg, lines ? "pivot[%lld] of the line factorisation is zero or not finite (1-based; the smallest such index)"
+                                    : "diag(M)[%lld] is zero or not finite (1-based; the first such index)", (long long)bad[lines] + 1);
+    return otmb_fail(ctx, OTMB_ERR_SINGULAR_PRECONDITIONER, msg);
 }
 
-// The same into arrays of the caller's (otmb_op_step keeps one set per slot it visits); op->sw lends the flags only.
+// The same into arrays of the caller's (otmb_op_step keeps one set per slot it visits); op->sw lends the flags only, at its start (it is
+// reserved at the size of a workspace without columns, sv_work's k = 0).
 int32_t sv_prec_prepare(otmb_op *op, int adjoint, int32_t precond, const double *d, double sigma, const SvPrec &p) {
-    SvWork w;
     int32_t rc;
-    if ((rc = sv_work(op, precond == OTMB_PRECOND_LINES, 0, 0, w))) return rc;
-    w.sh = p.sh; w.diag = p.diag; w.m = p.m; w.u = p.u; w.piv = p.piv;
-    return sv_precond_setup(op, w, adjoint, precond, d, sigma);
+    if ((rc = otmb_reserve(op->ctx, op->sw, (precond == OTMB_PRECOND_LINES ? 5 : 2) * (size_t)op->n * 8 + 64))) return rc;
+    return sv_precond_setup(op, adjoint, precond, d, sigma, p, (unsigned long long *)op->sw.p);
 }
 
 // W = M·Z (modes 0, 1) or U - M·Z (mode 2) for the columns in state `want`, with the partials of the mode's dot products
@@ -485,18 +480,18 @@ static void sv_apply(otmb_op *op, const SvWork &w, int adjoint, i64 k, int want,
     const i64 n = op->n;
     if (!adjoint && op->nlong > 0)
         hipLaunchKernelGGL(sv_long_kernel<MODE>, dim3((unsigned)op->nlong), dim3(64), 0, st, (const SvCol *)w.cs, want, (const double *)op->val.p,
-                           (const int *)op->col.p, (const i64 *)op->lrows.p, (const i64 *)op->loff.p, op->ell, (int)k, (const double *)w.sh, Z, ldz, U, ldu,
+                           (const int *)op->col.p, (const i64 *)op->lrows.p, (const i64 *)op->loff.p, op->ell, (int)k, (const double *)w.pc.sh, Z, ldz, U, ldu,
                            W, ldw);
     op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
         constexpr int KB = decltype(kb)::value;
         if (adjoint)
             hipLaunchKernelGGL((sv_cols_kernel<KB, MODE>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, (const SvCol *)w.cs + c0, want,
-                               (const i64 *)op->cp.p, (const int *)op->rv.p, (const double *)op->nz.p, n, (const double *)w.sh, Z + c0 * ldz, ldz,
+                               (const i64 *)op->cp.p, (const int *)op->rv.p, (const double *)op->nz.p, n, (const double *)w.pc.sh, Z + c0 * ldz, ldz,
                                U + c0 * ldu, ldu, W + c0 * ldw, ldw, w.part + 2 * c0 * w.np, w.np);
         else
             hipLaunchKernelGGL((sv_rows_kernel<KB, MODE>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const SvCol *)w.cs + c0, want,
                                (const double *)op->val.p, (const int *)op->col.p, (const i64 *)op->sbase.p, (const int *)op->elen.p, n,
-                               (const double *)w.sh, Z + c0 * ldz, ldz, U + c0 * ldu, ldu, W + c0 * ldw, ldw, w.part + 2 * c0 * w.np, w.np);
+                               (const double *)w.pc.sh, Z + c0 * ldz, ldz, U + c0 * ldu, ldu, W + c0 * ldw, ldw, w.part + 2 * c0 * w.np, w.np);
     });
 }
 
@@ -540,28 +535,15 @@ static int32_t sv_check_apply(otmb_op *op, int32_t precond, int64_t k, const dou
     return sv_check_system(op, precond, "precond", "columns", 'Y', 'Z', k, Y, ldy, Z, ldz, nullptr);
 }
 
-// The solve behind otmb_op_solve_pc_dev, its arguments checked already.  prep == nullptr: the preconditioner is set up here, from d and σ;
-// otherwise it is taken as prepared (sv_prec_prepare, for this adjoint, precond, d, σ and the selected values) and d and σ are not read.
-int32_t sv_solve(otmb_op *op, int adjoint, i64 k, const double *d, double sigma, const double *B, i64 ldb, double *X, i64 ldx, int use_x0, double rtol,
-                 i64 maxiter, int64_t *iters, double *relres, int32_t *reason, int32_t precond, const SvPrec *prep) {
-    int32_t rc;
+// The solve proper, behind otmb_op_solve_pc_dev and the step: w.pc is a prepared preconditioner (for this adjoint, precond, d, σ and the
+// selected values), so a singular one was refused before this, with nothing of X touched.
+static int32_t sv_iterate(otmb_op *op, const SvWork &w, int adjoint, i64 k, const double *B, i64 ldb, double *X, i64 ldx, int use_x0, double rtol,
+                          i64 maxiter, int64_t *iters, double *relres, int32_t *reason, int32_t precond) {
     const bool lines = precond == OTMB_PRECOND_LINES;
     otmb_ctx *ctx = op->ctx;
-    const i64 n = op->n;
-    if (n == 0) {
-        for (i64 c = 0; c < k; ++c) { iters[c] = 0; relres[c] = 0.0; reason[c] = OTMB_SOLVE_CONVERGED; }
-        return OTMB_OK;
-    }
-    HIP_TRY(ctx, hipSetDevice(op->device));
     hipStream_t st = ctx->stream;
-    const i64 nb = (n + 255) / 256, np = (n + 63) / 64;  // partials per column and quantity: rows / vector kernels write nb, the adjoint's np
-    SvWork w;
-    if ((rc = sv_work(op, lines, k, np, w))) return rc;
+    const i64 n = op->n, nb = (n + 255) / 256, np = w.np;
     const dim3 grid((unsigned)nb), block(256);
-    // the preconditioner, checked before anything of X is touched
-    if (prep) {
-        w.sh = prep->sh; w.diag = prep->diag; w.m = prep->m; w.u = prep->u; w.piv = prep->piv;
-    } else if ((rc = sv_precond_setup(op, w, adjoint, precond, d, sigma))) return rc;
     // ‖b‖, the start, its true residual
     op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
         hipLaunchKernelGGL((sv_bnorm_kernel<decltype(kb)::value>), grid, block, 0, st, n, B + c0 * ldb, ldb, w.part + 2 * c0 * np, np);
@@ -588,19 +570,19 @@ int32_t sv_solve(otmb_op *op, int adjoint, i64 k, const double *d, double sigma,
             op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
                 constexpr int KB = decltype(kb)::value;
                 hipLaunchKernelGGL((lines ? sv_p_kernel<KB, true> : sv_p_kernel<KB, false>), grid, block, 0, st, (const SvCol *)w.cs + c0, n,
-                                   (const double *)w.diag, (const double *)w.r + c0 * n, w.rh + c0 * n, w.p + c0 * n, (const double *)w.v + c0 * n,
+                                   (const double *)w.pc.diag, (const double *)w.r + c0 * n, w.rh + c0 * n, w.p + c0 * n, (const double *)w.v + c0 * n,
                                    w.ph + c0 * n);
             });
-            if (lines) ln_sweep(op, w.cs, k, w.m, w.u, w.piv, w.p, n, w.ph, n);
+            if (lines) ln_sweep(op, w.cs, k, w.pc, w.p, n, w.ph, n);
             sv_apply<0>(op, w, adjoint, k, SV_ACTIVE, w.ph, n, w.rh, n, w.v, n);
             sv_scalar(op, w, k, SV_S_ALPHA, nbm, rtol, maxiter);
             op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
                 constexpr int KB = decltype(kb)::value;
                 hipLaunchKernelGGL((lines ? sv_s_kernel<KB, true> : sv_s_kernel<KB, false>), grid, block, 0, st, (const SvCol *)w.cs + c0, n,
-                                   (const double *)w.diag, (const double *)w.r + c0 * n, (const double *)w.v + c0 * n, w.s + c0 * n, w.sh_ + c0 * n,
+                                   (const double *)w.pc.diag, (const double *)w.r + c0 * n, (const double *)w.v + c0 * n, w.s + c0 * n, w.sh_ + c0 * n,
                                    w.parts + c0 * np, np);
             });
-            if (lines) ln_sweep(op, w.cs, k, w.m, w.u, w.piv, w.s, n, w.sh_, n);
+            if (lines) ln_sweep(op, w.cs, k, w.pc, w.s, n, w.sh_, n);
             sv_apply<1>(op, w, adjoint, k, SV_ACTIVE, w.sh_, n, w.s, n, w.t, n);
             sv_scalar(op, w, k, SV_S_OMEGA, nbm, rtol, maxiter);
             op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
@@ -634,6 +616,16 @@ int32_t sv_solve(otmb_op *op, int adjoint, i64 k, const double *d, double sigma,
     return OTMB_OK;
 }
 
+// The solve with a preconditioner prepared elsewhere (sv_prec_prepare): the step's, which keeps one per slot
+int32_t sv_solve(otmb_op *op, int adjoint, i64 k, const SvPrec &p, const double *B, i64 ldb, double *X, i64 ldx, int use_x0, double rtol, i64 maxiter,
+                 int64_t *iters, double *relres, int32_t *reason, int32_t precond) {
+    SvWork w;
+    int32_t rc;
+    if ((rc = sv_work(op, precond, k, w))) return rc;
+    w.pc = p;
+    return sv_iterate(op, w, adjoint, k, B, ldb, X, ldx, use_x0, rtol, maxiter, iters, relres, reason, precond);
+}
+
 extern "C" {
 
 int32_t otmb_op_solve_pc_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X,
@@ -641,7 +633,10 @@ int32_t otmb_op_solve_pc_dev(otmb_op *op, int32_t adjoint, int64_t k, const doub
     if (!op) return OTMB_ERR_INVALID_ARG;
     int32_t rc;
     if ((rc = sv_check(op, precond, k, B, ldb, X, ldx, rtol, maxiter, iters, relres, reason))) return rc;
-    return sv_solve(op, adjoint, k, d, sigma, B, ldb, X, ldx, use_x0, rtol, maxiter, iters, relres, reason, precond, nullptr);
+    if (op->n == 0) return sv_report_empty(k, iters, relres, reason);
+    SvWork w;
+    if ((rc = sv_work(op, precond, k, w)) || (rc = sv_precond_setup(op, adjoint, precond, d, sigma, w.pc, w.bad))) return rc;
+    return sv_iterate(op, w, adjoint, k, B, ldb, X, ldx, use_x0, rtol, maxiter, iters, relres, reason, precond);
 }
 
 int32_t otmb_op_solve_pc(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X, int64_t ldx,
@@ -661,12 +656,7 @@ int32_t otmb_op_solve_pc(otmb_op *op, int32_t adjoint, int64_t k, const double *
     }
     rc = otmb_op_solve_pc_dev(op, adjoint, k, dd, sigma, db, n, dx, n, use_x0, rtol, maxiter, iters, relres, reason, precond);
     if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED) return rc;
-    const std::string msg = ctx->err;  // (HIP_TRY below would replace the solver's message)
-    int32_t rcd;
-    if (n > 0 && (rcd = op_download(ctx, X, ldx, dx, n, k))) return rcd;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->err = msg;
-    return rc;
+    return op_finish(ctx, rc, X, ldx, dx, n, k);
 }
 
 int32_t otmb_op_solve_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X, int64_t ldx,
@@ -688,16 +678,14 @@ int32_t otmb_op_precond_dev(otmb_op *op, int32_t adjoint, int32_t precond, int64
     otmb_ctx *ctx = op->ctx;
     const i64 n = op->n;
     if (n == 0) return OTMB_OK;
-    HIP_TRY(ctx, hipSetDevice(op->device));
     SvWork w;
-    if ((rc = sv_work(op, precond == OTMB_PRECOND_LINES, 0, 0, w))) return rc;
-    if ((rc = sv_precond_setup(op, w, adjoint, precond, d, sigma))) return rc;
+    if ((rc = sv_work(op, precond, 0, w)) || (rc = sv_precond_setup(op, adjoint, precond, d, sigma, w.pc, w.bad))) return rc;
     if (precond == OTMB_PRECOND_LINES)
-        ln_sweep(op, nullptr, k, w.m, w.u, w.piv, Y, ldy, Z, ldz);
+        ln_sweep(op, nullptr, k, w.pc, Y, ldy, Z, ldz);
     else
         op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
             hipLaunchKernelGGL((sv_scale_kernel<decltype(kb)::value>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n,
-                               (const double *)w.diag, Y + c0 * ldy, ldy, Z + c0 * ldz, ldz);
+                               (const double *)w.pc.diag, Y + c0 * ldy, ldy, Z + c0 * ldz, ldz);
         });
     HIP_TRY(ctx, hipGetLastError());
     return OTMB_OK;
@@ -717,9 +705,7 @@ int32_t otmb_op_precond(otmb_op *op, int32_t adjoint, int32_t precond, int64_t k
     double *dy = (double *)op->xs.p, *dz = (double *)op->ys.p;
     if ((rc = op_upload(ctx, dy, Y, ldy, n, k))) return rc;
     if ((rc = otmb_op_precond_dev(op, adjoint, precond, k, dd, sigma, dy, n, dz, n))) return rc;
-    if ((rc = op_download(ctx, Z, ldz, dz, n, k))) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return OTMB_OK;
+    return op_finish(ctx, OTMB_OK, Z, ldz, dz, n, k);
 }
 
 }  // extern "C"

@@ -150,24 +150,29 @@ __global__ __launch_bounds__(64) void ln_sweep_kernel(const SvCol *__restrict__ 
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-void ln_factor(otmb_op *op, int adjoint, const double *diag, double *m, double *u, double *piv, ull *bad) {
-    hipStream_t st = op->ctx->stream;
-    const i64 n = op->n;
-    const int *nxt = (const int *)op->ln.p, *heads = nxt + 2 * n;
-    hipLaunchKernelGGL(ln_ul_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const i64 *)op->cp.p, (const int *)op->rv.p,
-                       (const double *)op->nz.p, n, nxt, adjoint, u, m);
-    hipLaunchKernelGGL(ln_factor_kernel, dim3((unsigned)((op->nheads + 63) / 64)), dim3(64), 0, st, heads, op->nheads, nxt, diag, (const double *)u, m,
-                       piv, bad);
+struct LnTables { const int *nxt, *prv, *heads; };  // op->ln as otmb_op_set_lines_dev leaves it: n successors, n predecessors, the heads
+static LnTables ln_tables(const otmb_op *op) {
+    const int *nxt = (const int *)op->ln.p;
+    return {nxt, nxt + op->n, nxt + 2 * op->n};
 }
 
-void ln_sweep(otmb_op *op, const SvCol *cs, i64 k, const double *m, const double *u, const double *piv, const double *Y, i64 ldy, double *Z,
-              i64 ldz) {
+void ln_factor(otmb_op *op, int adjoint, const SvPrec &p, ull *bad) {
     hipStream_t st = op->ctx->stream;
     const i64 n = op->n;
-    const int *nxt = (const int *)op->ln.p, *prv = nxt + n, *heads = nxt + 2 * n;
+    const LnTables ln = ln_tables(op);
+    hipLaunchKernelGGL(ln_ul_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const i64 *)op->cp.p, (const int *)op->rv.p,
+                       (const double *)op->nz.p, n, ln.nxt, adjoint, p.u, p.m);
+    hipLaunchKernelGGL(ln_factor_kernel, dim3((unsigned)((op->nheads + 63) / 64)), dim3(64), 0, st, ln.heads, op->nheads, ln.nxt,
+                       (const double *)p.diag, (const double *)p.u, p.m, p.piv, bad);
+}
+
+void ln_sweep(otmb_op *op, const SvCol *cs, i64 k, const SvPrec &p, const double *Y, i64 ldy, double *Z, i64 ldz) {
+    hipStream_t st = op->ctx->stream;
+    const LnTables ln = ln_tables(op);
     op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
         hipLaunchKernelGGL((ln_sweep_kernel<decltype(kb)::value>), dim3((unsigned)((op->nheads + 63) / 64)), dim3(64), 0, st, cs ? cs + c0 : nullptr,
-                           heads, op->nheads, nxt, prv, m, u, piv, Y + c0 * ldy, ldy, Z + c0 * ldz, ldz);
+                           ln.heads, op->nheads, ln.nxt, ln.prv, (const double *)p.m, (const double *)p.u, (const double *)p.piv, Y + c0 * ldy, ldy,
+                           Z + c0 * ldz, ldz);
     });
 }
 

@@ -559,9 +559,7 @@ int32_t otmb_op_mul(otmb_op *op, int32_t adjoint, int64_t k, const double *X, in
     if (rx > 0 && (rc = op_upload(ctx, dx, X, ldx, rx, k))) return rc;
     if (ry > 0 && beta != 0.0 && (rc = op_upload(ctx, dy, Y, ldy, ry, k))) return rc;  // (β == 0 discards Y)
     if ((rc = otmb_op_mul_dev(op, adjoint, k, dx, rx, dy, ry, alpha, beta))) return rc;
-    if (ry > 0 && (rc = op_download(ctx, Y, ldy, dy, ry, k))) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return OTMB_OK;
+    return op_finish(ctx, OTMB_OK, Y, ldy, dy, ry, k);
 }
 
 int32_t otmb_op_info(const otmb_op *op, int64_t *m, int64_t *n, int64_t *nnz) {

@@ -168,9 +168,8 @@ int32_t otmb_op_step_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *
     otmb_ctx *ctx = op->ctx;
     const i64 n = op->n, nslots = (i64)op->slots.size();
     if (n == 0) {
-        for (i64 e = 0; e < nsteps * k; ++e) { iters[e] = 0; relres[e] = 0.0; reason[e] = OTMB_SOLVE_CONVERGED; }
         *steps_done = nsteps;
-        return OTMB_OK;
+        return sv_report_empty(nsteps * k, iters, relres, reason);
     }
     HIP_TRY(ctx, hipSetDevice(op->device));
     const bool lines = precond == OTMB_PRECOND_LINES;
@@ -190,23 +189,18 @@ int32_t otmb_op_step_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *
     for (i64 t = 0; t < nsteps; ++t) {
         const i64 slot = (first_slot + t) % nslots;
         if ((rc = otmb_op_select_slot(op, slot))) return rc;
+        const auto here = [&](int32_t status) {  // the failure's message names the step and the slot
+            ctx->err += " (step " + std::to_string(t) + ", slot " + std::to_string(slot) + ")";
+            return status;
+        };
         SvPrec &p = prec[(size_t)slot];
         if (!p.sh) {  // the slot's first visit
-            double *a = pool + (taken++) * per * n;
-            const SvPrec fresh = {a, a + n, lines ? a + 2 * n : nullptr, lines ? a + 3 * n : nullptr, lines ? a + 4 * n : nullptr};
-            if ((rc = sv_prec_prepare(op, adjoint, precond, d, q.sigma, fresh))) {
-                ctx->err += " (step " + std::to_string(t) + ", slot " + std::to_string(slot) + ")";
-                return rc;
-            }
-            p = fresh;
+            p = sv_prec_carve(pool + (taken++) * per * n, n, lines);
+            if ((rc = sv_prec_prepare(op, adjoint, precond, d, q.sigma, p))) return here(rc);
         }
         st_rhs(op, adjoint, k, q, d, X, ldx, S, lds, B);
         HIP_TRY(ctx, hipGetLastError());
-        rc = sv_solve(op, adjoint, k, d, q.sigma, B, n, X, ldx, 1, rtol, maxiter, iters + t * k, relres + t * k, reason + t * k, precond, &p);
-        if (rc) {
-            ctx->err += " (step " + std::to_string(t) + ", slot " + std::to_string(slot) + ")";
-            return rc;
-        }
+        if ((rc = sv_solve(op, adjoint, k, p, B, n, X, ldx, 1, rtol, maxiter, iters + t * k, relres + t * k, reason + t * k, precond))) return here(rc);
         *steps_done = t + 1;
     }
     return OTMB_OK;
@@ -233,12 +227,7 @@ int32_t otmb_op_step(otmb_op *op, int32_t adjoint, int64_t k, const double *d, d
     rc = otmb_op_step_dev(op, adjoint, k, dd, dt, theta, nsteps, first_slot, ds, n, dx, n, rtol, maxiter, precond, steps_done, iters, relres, reason);
     // X comes back when it holds an answer: every step done, a step's last iterates, or the state before a slot whose preconditioner is singular
     if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED && !(rc == OTMB_ERR_SINGULAR_PRECONDITIONER && *steps_done > 0)) return rc;
-    const std::string msg = ctx->err;  // (HIP_TRY below would replace the step's message)
-    int32_t rcd;
-    if (n > 0 && (rcd = op_download(ctx, X, ldx, dx, n, k))) return rcd;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->err = msg;
-    return rc;
+    return op_finish(ctx, rc, X, ldx, dx, n, k);
 }
 
 }  // extern "C"

@@ -315,6 +315,37 @@ def test_a_step_that_does_not_converge_ends_the_call(small, oracle):
         assert np.array_equal(info.iterations[1], rows[1][0])
 
 
+def test_the_host_route_keeps_the_failing_steps_message(small, oracle):
+    """The later failure of the test above (slot 0 holds 1e-6·T, slot 1 holds T, maxiter = 20: step 1 does not converge) through
+    otmb_op_step: after X has come back and the stream was waited for, the context's message is still the solver's report, with the step's
+    suffix, and X has the bits the device route leaves on the device."""
+    import torch
+
+    import otmb_amd.api as api
+    from otmb_amd import capi, device
+
+    _, N, _ = small
+    X0 = _start(N, 2, 71)
+    T, _, _, _ = LR.grid(oracle, "odd_nx_fold")
+    kw = dict(dt=SR.MONTH, theta=1.0, nsteps=4, first_slot=0, rtol=RTOL, maxiter=20, precond="jacobi")
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(torch.device("cuda", 0))
+    ctx = device.DeviceAssembler(0).ctx
+    with api.DeviceOperator(_csc(N, T[0], T[1], 1e-6 * T[2])) as E, \
+            device.Operator(ctx, N, N, t(T[0], np.int64), t(T[1], np.int64), t(1e-6 * T[2], np.float64)) as O:
+        E.set_slots(2)
+        E.set_values(T[2], slot=1)
+        O.set_slots(2)
+        O.set_values_dev(t(T[2], np.float64), slot=1)
+        Xh, ih = E.step(X0, **kw)
+        msg = capi.lib().otmb_last_error(E.ctx.handle).decode()
+        print("host route:", ih.status, ih.steps_done, msg)
+        assert ih.status == capi.NOT_CONVERGED and ih.steps_done == 1
+        assert msg.startswith("solve: not converged") and msg.endswith("(step 1, slot 1)"), msg
+        Xg, ig = O.step(t(X0.T, np.float64).t(), **kw)
+        assert ig.status == capi.NOT_CONVERGED and ig.steps_done == 1
+        _same_bits(Xh, Xg.cpu().numpy(), "the host route's X against the device route's")
+
+
 def test_a_singular_slot_stops_the_call_before_its_step():
     """[[1, 4], [1, 1]] + σ·I with σ = 1 (δt = 1, θ = 1) on the line 1 -> 2: m_2 = 1 / 2, piv_2 = 2 - (1 / 2)·4 = 0 exactly (the matrix of
     tests/test_solve_lines.py, shifted).  It sits in slot 1: the call ends at step 1 with OTMB_ERR_SINGULAR_PRECONDITIONER, steps_done = 1,
