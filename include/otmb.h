@@ -402,6 +402,9 @@ int64_t otmb_ctx_given_checks(const otmb_ctx *ctx);
 /* ... and whether the last fill pass on this context that kept all three diffusive operators (otmb_tm_args.kept_ops) read TκH from the
  * context's table: 1 yes, 0 no (OTMB_KEPT_HTAB=0, nx < 3, the table could not be allocated), -1 no such fill yet. */
 int32_t otmb_ctx_kept_htab(const otmb_ctx *ctx);
+/* ... and whether it took the neighbours' wet ranks from the context's per-grid table instead of gathering Lwet3D: 1 yes, 0 no
+ * (OTMB_KEPT_NBTAB=0 or no TκH table, a depth slab, the table could not be allocated), -1 no such fill yet. */
+int32_t otmb_ctx_kept_nbtab(const otmb_ctx *ctx);
 /* ... and whether that fill stored T's values only (otmb_tm_args.kept_ops & OTMB_KEPT_T_PATTERN honoured): 1 yes, 0 no (T written in full),
  * -1 no such fill yet.  OTMB_KEPT_TPAT=0 in the environment always writes T in full. */
 int32_t otmb_ctx_kept_t_pattern(const otmb_ctx *ctx);

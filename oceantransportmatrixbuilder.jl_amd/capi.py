@@ -113,6 +113,7 @@ SYMBOLS = {
     "otmb_ctx_given_state": (C.c_int32, [_vp, C.c_int32]),
     "otmb_ctx_given_checks": (C.c_int64, [_vp]),
     "otmb_ctx_kept_htab": (C.c_int32, [_vp]),
+    "otmb_ctx_kept_nbtab": (C.c_int32, [_vp]),
     "otmb_ctx_kept_t_pattern": (C.c_int32, [_vp]),
     "otmb_ctx_kept_t_pattern_fills": (C.c_int64, [_vp]),
     "otmb_last_error": (C.c_char_p, [_vp]),
@@ -357,6 +358,10 @@ class Context:
     def kept_htab(self):
         """Whether the last fill that kept TκH, TκVML and TκVdeep read TκH from the context's table: 1 yes, 0 no, -1 no such fill yet."""
         return int(self._lib.otmb_ctx_kept_htab(self._h))
+
+    def kept_nbtab(self):
+        """Whether that fill took its neighbours' wet ranks from the context's neighbour table: 1 yes, 0 no (Lwet3D gathered), -1 no such fill yet."""
+        return int(self._lib.otmb_ctx_kept_nbtab(self._h))
 
     def kept_t_pattern(self):
         """Whether that fill stored T's values only, on the pattern of this context's last write of T (KEPT_T_PATTERN honoured): 1 yes, 0 no, -1 no such fill yet."""

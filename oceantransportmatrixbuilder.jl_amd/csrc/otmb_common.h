@@ -28,7 +28,7 @@ struct SpPlan { const int64_t *I = nullptr, *J = nullptr; const double *V = null
 
 // kernel ids for the optional HIP-event timing (otmb_ctx_timing_*)
 enum {
-    K_TM_COUNT = 0, K_TILESCAN, K_TM_FILL, K_TM_FINISH, K_FACEFLUXES, K_IDX_COUNT, K_IDX_WRITE, K_VELFLUX, K_GM, K_GRIDMETRICS, K_PUSHMASK, K_TM_ORDER, K_FF_BASES, K_TM_HTAB, K_NKERNELS
+    K_TM_COUNT = 0, K_TILESCAN, K_TM_FILL, K_TM_FINISH, K_FACEFLUXES, K_IDX_COUNT, K_IDX_WRITE, K_VELFLUX, K_GM, K_GRIDMETRICS, K_PUSHMASK, K_TM_ORDER, K_FF_BASES, K_TM_HTAB, K_TM_NBTAB, K_NKERNELS
 };
 #define OTMB_TIMING_POOL 2048
 
@@ -147,6 +147,10 @@ struct otmb_ctx {
     KeptRecord htab_key;
     size_t htab_nofit = 0;  // an allocation of this many bytes failed: the kept fill re-derives TκH instead
     int htab_used = -1;     // the last fill that kept all three operators read the table (1) or re-derived TκH (0); -1: none yet (otmb_ctx_kept_htab)
+    // ... and, behind the TκH table in the same allocation and valid with it, the neighbour table (kept_htab, tm_nbtab_kernel)
+    bool nbtab_built = false; // it was built for htab_key
+    size_t nbtab_nofit = 0;   // an allocation of this many bytes (both tables) failed: the TκH table alone is tried
+    int nbtab_used = -1;      // the last fill that kept all three operators read the neighbour table (1) or gathered Lwet3D (0); -1: none yet
     // ... and T's pattern (OTMB_KEPT_T_PATTERN): the last call that wrote T's full union pattern (colptr, rowval; nzval unused), its serial and
     // arguments.  nnz_known: that writer finished cleanly -- folded without error or FLAG_T_CANCEL, or a synchronous fill without cancellation --
     // and nnz is T's reserved count.  Dropped by a call that writes T elsewhere or not at all, a failed step that used it, a compaction of its

@@ -173,6 +173,7 @@ int32_t otmb_ctx_forget_given(otmb_ctx *ctx) {
 int32_t otmb_ctx_given_state(const otmb_ctx *ctx, int32_t m) { return (ctx && m >= 0 && m < 5) ? ctx->given_state[m] : -1; }
 int64_t otmb_ctx_given_checks(const otmb_ctx *ctx) { return ctx ? (int64_t)ctx->given_checks : -1; }
 int32_t otmb_ctx_kept_htab(const otmb_ctx *ctx) { return ctx ? ctx->htab_used : -1; }
+int32_t otmb_ctx_kept_nbtab(const otmb_ctx *ctx) { return ctx ? ctx->nbtab_used : -1; }
 int32_t otmb_ctx_kept_t_pattern(const otmb_ctx *ctx) { return ctx ? ctx->tpat_used : -1; }
 int64_t otmb_ctx_kept_t_pattern_fills(const otmb_ctx *ctx) { return ctx ? (int64_t)ctx->tpat_fills : -1; }
 
@@ -221,7 +222,7 @@ const char *otmb_kernel_name(int32_t k) {
     static const char *names[K_NKERNELS] = {"tm_count_kernel", "tilescan_kernel", "tm_kernel<fill>", "tm_finish_colptr",
                                             "facefluxes_kernel", "indices_kernel<count>", "indices_kernel<write>",
                                             "velocity_flux_kernel", "gm_slopes+gm_dyad", "gridmetrics2d+3d",
-                                            "push_mask_kernel", "tm_order_kernels", "ff_count_bases_kernel", "tm_htab_kernel"};
+                                            "push_mask_kernel", "tm_order_kernels", "ff_count_bases_kernel", "tm_htab_kernel", "tm_nbtab_kernel"};
     return (k >= 0 && k < K_NKERNELS) ? names[k] : "";
 }
 

@@ -15,6 +15,7 @@
 #include "otmb_common.h"
 #include "otmb_topology.h"
 
+#define NHTAB_SLOTS 5  // (NHTAB below)
 struct TmParams {
     const double *phi[6];
     // The fused step (otmb_step_dev): only ϕtop exists in memory (phi[OTMB_TOP]); the other five fluxes are what facefluxes WOULD have stored,
@@ -50,6 +51,7 @@ struct TmParams {
     u64 keep;          // the packed count word's fields of the matrices that ARE counted (T:11 | Tadv:11 | TκH:11 | TκVML:10 | TκVdeep:10)
     int rho_in_fill;   // the ρ-NaN check (:233) is done by the fill pass (which loads ρ anyway) instead of the counting pass:
                        // set when both passes run before the flags are read (otmb_transportmatrix_dev)
+    int nbtab;         // (kept operators, with htab) the neighbour table behind the TκH table is read (nb_layout)
     i64 P, G;
     i64 n_own;         // number of entries of lwet = columns produced
     i64 wet_base;      // wet rank of column 0 is wet_base + 1 (depth slabs; 0 otherwise)
@@ -76,6 +78,19 @@ struct TmParams {
     i64 htab_n;
     const int *htab_nan;
 };
+// ... and, behind the TκH table in the same allocation (TmParams.nbtab != 0), the neighbour table (tm_nbtab_kernel): of every regular owned
+// column, in wet-rank order, one 16-byte record {S, N, A, B} (nb16) and one 8-byte record {E, W} (nb8) of 32-bit wet ranks, 0 = the neighbour
+// does not exist or is dry; word[0]: Lwet3D[Lwet[w]] != w + 1 for some column, or a rank that is not one (the fill raises FLAG_NONCANONICAL).
+// Byte offsets from TmParams.htab, n = htab_n columns:
+struct NbLayout { size_t word, nb16, nb8, bytes; };
+__host__ __device__ __forceinline__ NbLayout nb_layout(size_t n) {
+    NbLayout l;
+    l.word = ((size_t)NHTAB_SLOTS * n * sizeof(double) + 256 + 255) & ~(size_t)255;  // (behind the TκH table and its NaN word, 256-byte aligned)
+    l.nb16 = l.word + 256; l.nb8 = l.nb16 + 16 * n; l.bytes = l.nb8 + 8 * n;
+    return l;
+}
+// one column's records of the neighbour table, as loaded
+struct NbRec { unsigned S, N, A, B, E, W; };
 
 // Which position of the tile sequence does workgroup b take?  Workgroups are dealt round-robin over the 8 XCDs (each with its own L2):
 // XCD x = b % 8 takes (1) every eighth of the sequence's first `nh` positions -- the HEAVY tiles, whose waves live about twice as
@@ -464,6 +479,7 @@ __device__ __forceinline__ double pick5(const double (&g)[5], unsigned q) {
 // and the kept operators' table (tm_htab_kernel) both call it.  Needs s.tC/tW/tE/tS/tN, s.vC/vW/vE/vS/vN and the 16 edge / distance values.
 // h5: the values of rows S, W, SELF, E, N (whether those rows exist is the caller's wet mask); returns whether a wet neighbour's pair is NaN (:61).
 enum { H_S = 0, H_WC, H_SELF, H_EC, H_N, NHTAB };
+static_assert(NHTAB == NHTAB_SLOTS, "nb_layout places the neighbour table behind NHTAB slot arrays");
 __device__ __forceinline__ bool h_regular(double kH, const Stencil &s, bool wW, bool wE, bool wS, bool wN, double (&h5)[NHTAB]) {
     const double vC = s.vC, tC = s.tC;
     double ownW, inW, ownE, inE, ownS, inS, ownN, inN;
@@ -638,9 +654,12 @@ __device__ __forceinline__ i64 ldi(const char *b, unsigned byteoff) { return *(c
 // Returns whether Lwet3D holds c at the cell itself (the canonical-indices check, loaded with the stencil).
 // HREAD: TκH's values come from the given matrix (p.hx at the column's offset hq) instead of thkcello and the 2-D metrics.
 // HTAB: they come from the context's table (tb.ht, hq = the column's position in the tile) instead of thkcello and the 2-D metrics.
-template <int FUSED = 0, bool HREAD = false, bool HTAB = false>
+// NB (with HTAB, wet_base == 0): the six neighbours' wet ranks are nb's (the neighbour table's records of this column, loaded by the caller with
+// Lwet[w]) instead of their six Lwet3D gathers, and the seventh, Lwet3D[c], is not issued either (the table's word is the canonical-indices
+// check: returns true).
+template <int FUSED = 0, bool HREAD = false, bool HTAB = false, bool NB = false>
 __device__ __forceinline__ bool fast_column(const TmParams &p, const TileBase &tb, unsigned oC, int i, int j, int k,
-                                            i64 c, Column &col, Stamps &st, i64 hq = 0) {
+                                            i64 c, Column &col, Stamps &st, i64 hq = 0, const NbRec &nb = NbRec()) {
     const int nx = p.nx, ny = p.ny, nz = p.nz;
     const bool hS = j > 0, hN = j + 1 < ny, hA = k > 0, hB = k + 1 < nz;
     const int di_e = (i + 1 < nx) ? 1 : 1 - nx, di_w = (i > 0) ? -1 : nx - 1;
@@ -653,8 +672,13 @@ __device__ __forceinline__ bool fast_column(const TmParams &p, const TileBase &t
     const unsigned sS = hS ? s2 - nx8 : s2, sN = hN ? s2 + nx8 : s2;
 
     // ---- all loads ----
-    const i64 lC = ldi(tb.lw, oC), lE = ldi(tb.lw, oE), lW = ldi(tb.lw, oW), lS = ldi(tb.lw, oS), lN = ldi(tb.lw, oN),
-              lA = ldi(tb.lw, oA), lB = ldi(tb.lw, oB);
+    i64 lC, lE, lW, lS, lN, lA, lB;
+    if (NB) {
+        lC = c; lE = nb.E; lW = nb.W; lS = nb.S; lN = nb.N; lA = nb.A; lB = nb.B;
+    } else {
+        lC = ldi(tb.lw, oC); lE = ldi(tb.lw, oE); lW = ldi(tb.lw, oW); lS = ldi(tb.lw, oS); lN = ldi(tb.lw, oN);
+        lA = ldi(tb.lw, oA); lB = ldi(tb.lw, oB);
+    }
     // each of the six flux arrays is read ONCE per cell (at one neighbour): streaming (non-temporal) loads, so that these lines do not
     // displace the v3D / ρ / Lwet3D lines that five neighbours share (A/B over several array placements: -3 % at 0.25 degree)
 #define LDPHI(b, o) __builtin_nontemporal_load((const double *)((b) + (o)))

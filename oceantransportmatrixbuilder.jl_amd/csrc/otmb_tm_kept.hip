@@ -11,7 +11,8 @@
 //   - a two-phase fill stores kept_rec[m] for every operator it wrote once its flags have been read clean, and tpat_rec when in addition no
 //     entry of T cancelled -- both only while no asynchronous step is pending, whose fold would take the counts for ITS keepers (kept_after_sync_fill);
 //   - a one-pass call stores them right after its enqueue, under the step's serial (kept_after_async_enqueue);
-//   - the table: its build has been enqueued in front of a kept fill (kept_htab).
+//   - the table: its build has been enqueued in front of a kept fill (kept_htab).  The neighbour table (tm_nbtab_kernel) lives in the same
+//     allocation, is built with it and is valid exactly while it is (nbtab_built: false when it was not built for htab_key).
 // KNOWN (nnz_known): the writer has finished and nnz is its count.  At once for a synchronous fill; for an asynchronous step when it is folded
 //   without error -- for T also without FLAG_T_CANCEL -- and is still the record's writer (kept_on_fold).  The two-phase plan honours known
 //   records only, and only with no step pending: it hands the count out.  A one-pass call honours a valid kept_rec[m] whose arrays and capacity
@@ -110,6 +111,51 @@ __global__ __launch_bounds__(256) void tm_htab_kernel(const TmParams p, double *
     if (bad) raise_flag(nan, 0);
 }
 
+// ---- the kept operators' neighbour table ---------------------------------------------------------------------------------------------------
+// The fill pass gathers Lwet3D at a column's cell and its six neighbours: 7 loads in CELL order, where the dry cells between the wet ones spread
+// a wave's 64 columns over more cache lines than 64 values need -- and the pass is bound by the L1 requests in flight.  Lwet3D is
+// a grid constant, so the context keeps its content in WET-RANK order, the order the fill walks in: per regular owned column w the six
+// neighbours' wet ranks (fast_column's clamps; 0: the neighbour does not exist or is dry -- what the masked gather yields), as one 16-byte record
+// {S, N, A, B} (nb16) and one 8-byte record {E, W} (nb8) of 32-bit words, read by the fill with two coalesced loads.  One thread per column,
+// wet-rank order, once per grid.  Irregular columns (tripolar seam row) are not read back: build_column reads Lwet3D.  *word: Lwet3D[Lwet[w]] !=
+// w + 1 for some column, or a neighbour's entry lies outside 0 .. G and would not fit a word (the fill raises FLAG_NONCANONICAL from it).  wet_base == 0 and
+// G < 2^31 (the host's conditions): every rank fits a word.
+__global__ __launch_bounds__(256) void tm_nbtab_kernel(const TmParams p, unsigned *__restrict__ nb16, unsigned *__restrict__ nb8, int *word) {
+    const i64 w = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (w >= p.n_own) return;
+    unsigned rS = 0, rN = 0, rA = 0, rB = 0, rE = 0, rW = 0;
+    const i64 L = p.lwet[w] - 1;
+    const bool inside = L >= 0 && L < p.G;  // (indices that are not a makeindices result: the fill pass flags them)
+    if (!inside || p.lw[L] != w + 1) raise_flag(word, 0);
+    const Cell cell = cell_of(inside ? L : 0, p.nx, p.ny, p.P);
+    const int nx = p.nx, i = cell.i, j = cell.j, k = cell.k;
+    if (inside && !(p.topo == OTMB_TRIPOLAR && j == p.ny - 1)) {
+        const bool hS = j > 0, hN = j + 1 < p.ny, hA = k > 0, hB = k + 1 < p.nz;
+        const int di_e = (i + 1 < nx) ? 1 : 1 - nx, di_w = (i > 0) ? -1 : nx - 1;
+        auto rank = [&](bool exists, i64 LX) -> unsigned {
+            if (!exists) return 0u;
+            const i64 r = p.lw[LX];
+            // (G, not n_own: the first slab of a deeper grid has wet_base == 0 and names its halo level's ranks, which lie beyond n_own; ranks are
+            // stored as row indices only, exactly as the gathers pass them on unverified -- the bound only keeps them inside a word)
+            if (r < 0 || r > p.G) { raise_flag(word, 0); return 0u; }
+            return (unsigned)r;
+        };
+        rE = rank(true, L + di_e); rW = rank(true, L + di_w); rS = rank(hS, L - nx); rN = rank(hN, L + nx);
+        rA = rank(hA, L - p.P); rB = rank(hB, L + p.P);
+    }
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    u32x4 q; q.x = rS; q.y = rN; q.z = rA; q.w = rB;
+    u32x2 e; e.x = rE; e.y = rW;
+    ((u32x4 *)nb16)[w] = q;
+    ((u32x2 *)nb8)[w] = e;
+}
+// OTMB_KEPT_NBTAB=0 (read once per process): no neighbour table.  OTMB_KEPT_HTAB=0 implies it.
+static bool nbtab_env_on() {
+    static const bool on = [] { const char *e = getenv("OTMB_KEPT_NBTAB"); return !(e && e[0] == '0'); }();
+    return on;
+}
+
 // Point p at a valid table when this call keeps all three operators (the HTAB fill kernel), building it first -- on the call's stream, in front
 // of its fill -- when none is valid.  Valid: built after the last call on this context that did not keep TκH (kept_drop), for this call's grid
 // arrays, κH, topology, n_wet and slab (kept_matches' fields), and in the current given_epoch.  OTMB_KEPT_HTAB=0, or a table that cannot be
@@ -118,19 +164,36 @@ static int32_t kept_htab(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl,
     static const bool env_on = [] { const char *e = getenv("OTMB_KEPT_HTAB"); return !(e && e[0] == '0'); }();
     if (!kept_is_kept_fill(pl, p)) return OTMB_OK;
     ctx->htab_used = 0;  // (otmb_ctx_kept_htab: set to 1 below once p points at a valid table)
+    ctx->nbtab_used = 0;  // (otmb_ctx_kept_nbtab likewise)
     if (!env_on || a.nx < 3 || a.n_wet <= 0) return OTMB_OK;
-    const size_t n = (size_t)a.n_wet, vals = (size_t)NHTAB * n * sizeof(double), bytes = vals + 256;  // (+ the NaN word)
+    const size_t n = (size_t)a.n_wet, vals = (size_t)NHTAB * n * sizeof(double), hbytes = vals + 256;  // (+ the NaN word)
+    // ... and behind it, 256-byte aligned: the neighbour table's word, nb16, nb8.  Wanted when every rank fits a record's 31 bits: ranks count
+    // from this grid's first cell (no depth slab: wet_base == 0) and the grid has fewer than 2^31 cells
+    const NbLayout lay = nb_layout(n);
+    const size_t nbbytes = lay.bytes;
+    bool want_nb = pl.wet_base == 0 && a.nx * a.ny * a.nz < (1ll << 31) && nbtab_env_on();
+    if (want_nb && ctx->nbtab_nofit && nbbytes >= ctx->nbtab_nofit && ctx->htab.cap < nbbytes) want_nb = false;
+    size_t bytes = want_nb ? nbbytes : hbytes;
     if (ctx->htab_valid && !record_matches(ctx->htab_key, ctx, a, pl, OTMB_TKH, nullptr, 0)) ctx->htab_valid = false;
     if (!ctx->htab_valid) {
         if (ctx->htab.cap < bytes) {
             if (ctx->htab_nofit && bytes >= ctx->htab_nofit) return OTMB_OK;  // (a size that did not fit is not tried again every step)
+            // (a buffer that still holds the TκH table alone is given up for the larger one before that is tried: after a failure the TκH
+            // table is allocated anew.  Deliberate: one sync, free and malloc more, once -- nbtab_nofit keeps it from happening again)
             if (ctx->htab.p) {
                 HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (earlier fills may still read it)
                 (void)hipFree(ctx->htab.p);
                 ctx->htab.p = nullptr;
                 ctx->htab.cap = 0;
             }
-            if (hipMalloc(&ctx->htab.p, bytes) != hipSuccess) {
+            if (want_nb && hipMalloc(&ctx->htab.p, bytes) != hipSuccess) {  // (both did not fit: the TκH table alone)
+                (void)hipGetLastError();
+                ctx->htab.p = nullptr;
+                ctx->nbtab_nofit = bytes;
+                want_nb = false;
+                bytes = hbytes;
+            }
+            if (!ctx->htab.p && hipMalloc(&ctx->htab.p, bytes) != hipSuccess) {
                 (void)hipGetLastError();
                 ctx->htab.p = nullptr;
                 ctx->htab_nofit = bytes;
@@ -138,6 +201,7 @@ static int32_t kept_htab(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl,
             }
             ctx->htab.cap = bytes;
         }
+        ctx->nbtab_built = false;
         int *nanw = (int *)((char *)ctx->htab.p + vals);
         HIP_TRY(ctx, hipMemsetAsync(nanw, 0, sizeof(int), ctx->stream));
         {
@@ -145,8 +209,24 @@ static int32_t kept_htab(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl,
             hipLaunchKernelGGL(tm_htab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, p, (double *)ctx->htab.p, nanw);
         }
         HIP_TRY(ctx, hipGetLastError());
+        if (want_nb) {
+            char *b = (char *)ctx->htab.p;
+            int *word = (int *)(b + lay.word);
+            HIP_TRY(ctx, hipMemsetAsync(word, 0, sizeof(int), ctx->stream));
+            {
+                KernelTimer kt(ctx, K_TM_NBTAB);
+                hipLaunchKernelGGL(tm_nbtab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, p, (unsigned *)(b + lay.nb16),
+                                   (unsigned *)(b + lay.nb8), word);
+            }
+            HIP_TRY(ctx, hipGetLastError());
+            ctx->nbtab_built = true;
+        }
         record_set(ctx->htab_key, ctx, a, pl, OTMB_TKH);
         ctx->htab_valid = true;
+    }
+    if (ctx->nbtab_built) {  // (the fill finds the table behind p.htab: nb_layout(p.htab_n))
+        p.nbtab = 1;
+        ctx->nbtab_used = 1;
     }
     p.htab = (const double *)ctx->htab.p;
     p.htab_n = (i64)n;

@@ -136,10 +136,16 @@ static_assert(TM_THREADS == (1 << FFC_TILE_SHIFT), "the counts in facefluxes are
 // GIVEN bit 3 -- TPAT (with HTAB only): T's pattern is where the context's last full write of T left it (OTMB_KEPT_T_PATTERN, tpat_rec), so T
 // stores its VALUES only, at the union positions that write gave them: no T colptr (closing entry included), no T row staging or row stores.
 // A cancelled slot holds its zero sum (±0.0), its row is left as it is, and FLAG_T_CANCEL is raised as before (the compaction keys on values).
+// GIVEN bit 4 -- NBTAB (with HTAB only): a regular column takes its six neighbours' wet ranks from the context's neighbour table (behind TmParams.htab
+// at nb_layout(htab_n): two streamed loads at the column's position in the tile, issued with Lwet[w]) instead of seven Lwet3D gathers in cell
+// order (the six neighbours' and the cell's own); the
+// canonical-indices check of Lwet3D was made when the table was built (its word).
 template <int FUSED = 0, int GIVEN = 0>
 __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const TmParams p) {
     constexpr bool HREAD = (GIVEN & 1) != 0, DREAD = (GIVEN & 2) != 0, HTAB = (GIVEN & 4) != 0, TPAT = (GIVEN & 8) != 0;
-    static_assert(!HTAB || (GIVEN & ~8) == 4, "the table serves the kept operators: nothing is given then");
+    constexpr bool NB = (GIVEN & 16) != 0;
+    static_assert(!HTAB || (GIVEN & ~(8 | 16)) == 4, "the table serves the kept operators: nothing is given then");
+    static_assert(!NB || HTAB, "the neighbour table rides on the kept operators' path");
     static_assert(!TPAT || HTAB, "T's kept pattern rides on the kept operators' path");
 // (evaluated where used, as p.skip / p.keep were: a local copy at the top changes the other instantiations' register allocation)
 #define TM_SKIP (HTAB ? KEPT_OPS : p.skip)
@@ -163,6 +169,11 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
     if (HTAB && blockIdx.x == 0) {
         const int hnan = *p.htab_nan;
         if (hnan && tid == 0) raise_flag(p.flags, FLAG_TKH_NAN);
+    }
+    // (NBTAB) ... and Lwet3D[Lwet[w]] == w + 1 was verified for every column when the neighbour table was built
+    if (NB && blockIdx.x == 0) {
+        const int bad = *(const int *)((const char *)p.htab + nb_layout((size_t)p.htab_n).word);
+        if (bad && tid == 0) raise_flag(p.flags, FLAG_NONCANONICAL);
     }
 
     // Workgroups are dealt round-robin over the 8 XCDs (each with its own L2).  Give XCD x the x-th
@@ -195,6 +206,17 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
     const i64 Lnext_own = (wcl + 1 < p.n_own) ? Lnext_ld : p.G;
     const i64 Lmin = p.lwet[w0] - 1;
     const i64 Lmax = p.lwet[wlast] - 1;
+    // (NBTAB) the column's two records of the neighbour table, streamed like ϕ: in flight with the index loads above
+    NbRec nb = NbRec();
+    if (NB) {
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+        const unsigned t = (unsigned)(wcl - w0);  // (tid; the last tile's idle lanes: its last column)
+        const NbLayout lay = nb_layout((size_t)p.htab_n);
+        const u32x4 q = __builtin_nontemporal_load((const u32x4 *)((const char *)p.htab + lay.nb16 + 16 * w0 + t * 16u));
+        const u32x2 e = __builtin_nontemporal_load((const u32x2 *)((const char *)p.htab + lay.nb8 + 8 * w0 + t * 8u));
+        nb.S = q.x; nb.N = q.y; nb.A = q.z; nb.B = q.w; nb.E = e.x; nb.W = e.y;
+    }
     i64 hq = 0, dq = 0;
     // (with the index loads: the column's first entry in the given matrix.  Never negative for the arrays the comparing pass saw; a device caller
     // who rewrote them in place without otmb_ctx_forget_given gets wrong values, not a fault: the reads below are clamped into the arrays)
@@ -264,7 +286,7 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
             bool canonical;
             const bool regular = (p.nx >= 3) && !(p.topo == OTMB_TRIPOLAR && cell.j == p.ny - 1);
             {
-                if (regular) canonical = fast_column<FUSED, HREAD, HTAB>(p, tb, oC, cell.i, cell.j, cell.k, c, col, st, HTAB ? (i64)tid : hq);  // (the value-free input checks ran with the counts)
+                if (regular) canonical = fast_column<FUSED, HREAD, HTAB, NB>(p, tb, oC, cell.i, cell.j, cell.k, c, col, st, HTAB ? (i64)tid : hq, nb);  // (the value-free input checks ran with the counts)
                 else {
                     canonical = ldi(tb.lw, oC) == c;
                     if (canonical) {
@@ -484,7 +506,7 @@ __global__ void tm_finish_colptr(i64 *c0, i64 *c1, i64 *c2, i64 *c3, i64 *c4, i6
 
 // ---- host side ------------------------------------------------------------------------------
 // One launch site for the fill pass's instantiations: FUSED (the fused step's flux re-derivation) x GIVEN (a given TκH / TκVdeep read where it lies;
-// 4: the kept operators' TκH table).
+// 4: the kept operators' TκH table, + 8: T's values only, + 16: the neighbour table).
 template <int GIVEN> static void launch_fill_given(otmb_ctx *ctx, const TmParams &p, int fused, dim3 grid, dim3 block) {
     if (fused == 1) hipLaunchKernelGGL((tm_kernel<1, GIVEN>), grid, block, 0, ctx->stream, p);
     else if (fused == 2) hipLaunchKernelGGL((tm_kernel<2, GIVEN>), grid, block, 0, ctx->stream, p);
@@ -496,7 +518,10 @@ static void launch_fill(otmb_ctx *ctx, const TmParams &p, int fused, bool tpat =
     // (a derived TκH: reading is a choice -- regular cells only, OTMB_GIVEN_READ=0 re-derives; the derived rows with other values: it is the only way)
     const bool hread = p.hcp != nullptr && (p.hmust || (env_read && p.nx >= 3)), dread = p.dcp != nullptr;
     const dim3 grid(xcd_grid(p.nt_order, p.nheavy)), block(TM_THREADS);
-    if (p.htab && tpat) launch_fill_given<12>(ctx, p, fused, grid, block);
+    if (p.htab && p.nbtab) {  // (... with the neighbour table: otmb_tm_kept.hip, kept_htab)
+        if (tpat) launch_fill_given<12 | 16>(ctx, p, fused, grid, block);
+        else launch_fill_given<4 | 16>(ctx, p, fused, grid, block);
+    } else if (p.htab && tpat) launch_fill_given<12>(ctx, p, fused, grid, block);
     else if (p.htab) launch_fill_given<4>(ctx, p, fused, grid, block);  // (all three operators kept: otmb_tm_kept.hip, kept_htab)
     else if (hread && dread) launch_fill_given<3>(ctx, p, fused, grid, block);
     else if (dread) launch_fill_given<2>(ctx, p, fused, grid, block);
