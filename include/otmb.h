@@ -785,6 +785,39 @@ int32_t otmb_op_step(otmb_op *op, int32_t adjoint, int64_t k, const double *d, d
                      const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
                      int64_t *iters, double *relres, int32_t *reason);
 
+/* ---- The periodic (cyclo-stationary) state of the stepped cycle: x = F(x), F(x) = otmb_op_step_dev over ncycle >= 1 steps from first_slot
+ *      with the source S (ncycle need not be a multiple of the slot count).  F is affine: F(x) = Φ·x + g, Φ·v the same call without S,
+ *      g = F(0).  X returns the state at the START of the cycle with ‖F(x) - x‖₂ <= ptol·‖g‖₂, column by column.
+ * Method (a contract; tests/periodic_ref.py restates it): per column restarted GMRES(restart) on (I - Φ)·δ = r, r = F(x) - x, without a
+ *      preconditioner.  One iteration is one step call (w = v - Φ·v) for the columns that iterate, then classical Gram-Schmidt twice against
+ *      the column's own basis; the Hessenberg column and the Givens rotations are the host's, in double.  When the recursive residual
+ *      reaches ptol·‖g‖, when the basis is full (restart vectors) or exhausted (‖w‖ = 0), and when only one cycle of maxcycles is left:
+ *      x += V·y, then r = F(x) - x explicitly (one cycle with S).  A column is accepted on that explicit value only; otherwise it goes on
+ *      from it.  An iteration is only begun when a verifying cycle can follow it (cycles + 2 <= maxcycles), so X is always the state of the
+ *      column's last explicit F(x) - x, and defect[c] = ‖F(x) - x‖₂ / ‖g‖₂ of exactly that X (NaN when none was computed).
+ *      cycles[c]: the step calls column c took part in, the verifying ones included; maxcycles bounds it.  With use_x0 the first call
+ *      carries x and 0 side by side (F(x) and g: 2k columns, one call); without, X is not read, the start is zero and g is the first r.
+ *      A call that another column's failure ended is repeated without that column and not counted.
+ *      S == NULL, or a column of S that is zero: g = 0, so x = 0, zero cycles, converged.
+ * Columns are independent and a stopped column is frozen: X, cycles and defect of column c of k have the bits of that column alone, and the
+ *      same call twice gives the same bits (every sum runs in an order fixed by n and the basis index; no floating-point atomics, no FMA).
+ * Arguments: as otmb_op_step (ncycle for nsteps, but >= 1), and ptol > 0, restart >= 1, maxcycles >= 0, cycles / defect / reason not NULL:
+ *      otherwise OTMB_ERR_INVALID_ARG before X is touched.  The selected slot is the same after the call as before it.
+ * Returns OTMB_OK, or OTMB_ERR_NOT_CONVERGED when any column's reason is not OTMB_PERIODIC_CONVERGED (X and the three arrays are valid: an
+ *      answer).  An inner step that leaves a column not converged stops that column with OTMB_PERIODIC_STEP_FAILED and the message carries
+ *      the step's own text (step and slot); a non-finite norm or product stops it with OTMB_PERIODIC_NONFINITE.  Such a column keeps the
+ *      state of its last explicit F(x) - x.  A singular preconditioner is the error otmb_op_step gives (X not written); the workspace --
+ *      (restart + 3)·n·k doubles and the partial sums, owned by the operator -- that cannot be had is OTMB_ERR_ALLOC with X untouched.
+ * cycles, defect, reason: HOST arrays of k entries.  otmb_op_periodic_dev: d, S, X device pointers, on the context's stream.
+ *      otmb_op_periodic: host pointers, staged once like otmb_op_step.                                                                  */
+typedef enum { OTMB_PERIODIC_CONVERGED = 0, OTMB_PERIODIC_MAXCYCLES = 1, OTMB_PERIODIC_STEP_FAILED = 2, OTMB_PERIODIC_NONFINITE = 3 } otmb_periodic_reason;
+int32_t otmb_op_periodic_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t ncycle, int64_t first_slot,
+                             const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond,
+                             double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason);
+int32_t otmb_op_periodic(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t ncycle, int64_t first_slot,
+                         const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond,
+                         double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason);
+
 #ifdef __cplusplus
 }
 #endif

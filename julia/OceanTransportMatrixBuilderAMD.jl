@@ -12,6 +12,7 @@
 #   coarsen                     LUMP * T * SPRAY (src/extratools.jl:14-16)
 #   DeviceOperator, setvalues!  T * x, T' * v, mul!(Y, T, X, α, β) on the GPU (test/local_full.jl:96-107; README: ∂x/∂t + T x = …)
 #   setslots!, step!, step      a year of monthly matrices resident as value slots, and θ-steps of the tracers through them on the GPU
+#   periodic!, periodic         the periodic (cyclo-stationary) state of that stepped cycle, by restarted GMRES on the cycle map
 #   solve!, solve               (σ·I + Diagonal(d) + T) \ B on the GPU: the `\` of the ideal-age problem (test/local_full.jl:151-188)
 #   bolus_GM_velocity           src/RediGM.jl:46-79 (unexported and experimental there, unexported here)
 #   makegridmetrics             src/gridcellgeometry.jl:265-311: the reference's own by default (its haversines are Julia's libm);
@@ -37,6 +38,7 @@ export DeviceOperator, setvalues!
 export solve!, solve
 export setlines!, verticallines, precondition!
 export setslots!, selectslot!, slots, step!   # (`step` extends Base.step for this module's operators: nothing to export)
+export periodic!, periodic
 
 const LIBPATH = get(ENV, "OTMB_HIP_LIB", joinpath(@__DIR__, "..", "oceantransportmatrixbuilder.jl_amd", "lib", "libotmb_hip.so"))
 const lib = Ref{Ptr{Cvoid}}(C_NULL)
@@ -520,6 +522,36 @@ function step!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDevic
                converged = why .== :converged)
 end
 Base.step(D::Union{DeviceOperator,AdjointDeviceOperator}, X::StridedVecOrMat{Float64}; kwargs...) = step!(copy(X), D; kwargs...)
+
+const PERIODIC_REASONS = (:converged, :maxcycles, :step_failed, :nonfinite)   # otmb_periodic_reason
+# The periodic state of the stepped cycle (otmb_op_periodic; include/otmb.h states the method): X with F(X) = X, F = `ncycle` steps of length
+# `dt` from slot `firstslot` with `source`, by restarted GMRES(restart) on the cycle map; `D'` cycles with Aᵀ.  X is overwritten with the state
+# at the start of the cycle (x0 = true: X is the start; false: X is not read).  Returns (X, info): per column info.cycles, info.defect
+# (‖F(x) - x‖₂ / ‖F(0)‖₂), info.reason, info.converged.  A column that does not converge is REPORTED, not thrown (status 19).
+function periodic!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, source::StridedVecOrMat{Float64}; dt::Real,
+                   ncycle::Integer, θ::Real = 1.0, firstslot::Integer = 1, d::Union{Nothing,Vector{Float64}} = nothing, x0::Bool = false,
+                   rtol::Real = 1e-10, maxiter::Integer = 10000, precond::Symbol = :jacobi, ptol::Real = 1e-8, restart::Integer = 30,
+                   maxcycles::Integer = 1000)
+    pc = precondcode(precond)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    k, lds, ldx = systemdims(op, source, "source", X, "X", d)
+    cycles = zeros(Int64, k)
+    defect = zeros(Float64, k)
+    reason = zeros(Int32, k)
+    lock(CALL_LOCK) do
+        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        periodic_fn = sym(:otmb_op_periodic)
+        rc = ccall(periodic_fn, Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Float64, Float64, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                Int32, Float64, Int64, Int32, Float64, Int64, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}),
+            op.handle, Int32(adjoint), k, d === nothing ? C_NULL : d, Float64(dt), Float64(θ), Int64(ncycle), Int64(firstslot - 1),
+            source, lds, X, ldx, Int32(x0), Float64(rtol), Int64(maxiter), pc, Float64(ptol), Int64(restart), Int64(maxcycles), cycles, defect, reason)
+        rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which column stopped why
+    end
+    why = [PERIODIC_REASONS[r + 1] for r in reason]
+    return X, (cycles = cycles, defect = defect, reason = why, converged = why .== :converged)
+end
+periodic(D::Union{DeviceOperator,AdjointDeviceOperator}, source::StridedVecOrMat{Float64}; kwargs...) = periodic!(zero(source), D, source; kwargs...)
 
 const HDIRS = (:west, :east, :south, :north)      # OTMB_DIR_*
 f64(a) = Array{Float64}(replace(a, missing => NaN))

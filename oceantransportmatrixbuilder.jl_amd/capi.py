@@ -17,6 +17,7 @@ CAPACITY = 14
 NOT_CONVERGED = 19  # otmb_op_solve: an answer (the per-column info says which column stopped why), not an exception
 SOLVE_REASONS = ("converged", "maxiter", "breakdown", "nonfinite")  # otmb_solve_reason
 PRECONDS = {"jacobi": 0, "lines": 1}  # otmb_precond
+PERIODIC_REASONS = ("converged", "maxcycles", "step_failed", "nonfinite")  # otmb_periodic_reason
 
 PHI_ORDER = ("east", "west", "north", "south", "top", "bottom")  # OTMB_EAST..OTMB_BOTTOM
 HDIRS = ("west", "east", "south", "north")  # OTMB_DIR_*
@@ -208,6 +209,10 @@ SYMBOLS = {
                                       C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp]),
     "otmb_op_step": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
                                   C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp]),
+    "otmb_op_periodic_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
+                                          C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp]),
+    "otmb_op_periodic": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
+                                      C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp]),
     "otmb_op_info": (C.c_int32, [_vp, _ip, _ip, _ip]),
     "otmb_op_destroy": (None, [_vp]),
     "otmb_transportmatrix_plan_dev": (C.c_int32, [_vp, C.POINTER(TmArgs), C.POINTER(C.c_int64 * 5)]),

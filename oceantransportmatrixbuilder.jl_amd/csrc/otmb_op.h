@@ -29,6 +29,7 @@ struct otmb_op {
     DevBuf xs, ys;                        // host entry points' staging (op_reserve_xy): otmb_op_mul X, Y; otmb_op_solve_pc B, X; otmb_op_precond Y, Z
     DevBuf ds, sw;                        // staging of d (op_stage_d); the solver's arrays (SvWork, otmb_solve.hip): vectors, partial sums, column records
     DevBuf st;                            // otmb_op_step: the right-hand side and the preconditioners of the slots it visits (otmb_step.hip)
+    DevBuf pd;                            // otmb_op_periodic: the Krylov bases, the cycle's in/out columns, partial sums and scalars (otmb_periodic.hip)
     DevBuf ln;                            // otmb_op_set_lines (Int32, 0-based, -1 = none): successor (n), predecessor (n), line heads ascending (nheads)
     i64 nheads = 0;
     bool lines = false;                   // lines are set (they belong to the pattern: otmb_op_set_values keeps them)

@@ -212,6 +212,28 @@ class Operator:
             self.ctx.check(rc)
         return Xn, StepInfo(rc, done.value, nsteps, iters, relres, reason)
 
+    def periodic(self, source, *, dt, ncycle, theta=1.0, first_slot=0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi",
+                 ptol=1e-8, restart=30, maxcycles=1000):
+        """The periodic state of the stepped cycle on device tensors (otmb_op_periodic_dev; api.DeviceOperator.periodic states the arguments).
+        source, x0: device tensors, not modified.  Returns (a new tensor with the state at the start of the cycle, an api.PeriodicInfo).  Per
+        round the host reads a few scalars a column; no vector travels."""
+        from .api import PeriodicInfo
+
+        pc, k, Sc, lds, X = self._system(source, "source", precond)
+        if x0 is not None:
+            _on_device(x0, self.device, "x0")
+            if tuple(x0.shape) != tuple(source.shape):
+                raise capi.OtmbError(11, f"DimensionMismatch: x0 of {tuple(x0.shape)}, source of {tuple(source.shape)}")
+            X.copy_(x0)
+        d, dp = self._d_ptr(d)
+        cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
+        rc = self.lib.otmb_op_periodic_dev(self._h, int(bool(adjoint)), k, dp, float(dt), float(theta), int(ncycle), int(first_slot), Sc.data_ptr(), lds,
+                                           X.data_ptr(), max(self.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), pc, float(ptol),
+                                           int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data, reason.ctypes.data)
+        if rc != capi.NOT_CONVERGED:
+            self.ctx.check(rc)
+        return X, PeriodicInfo(rc, cycles, defect, reason)
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self.lib.otmb_op_destroy(self._h)
@@ -805,6 +827,14 @@ class DeviceAssembler:
         if rec is None or not rec["op"].handle.value:
             raise ValueError(f"no operator over {matrix}: keep_slot() first")
         return rec["op"].step(X, **kw)
+
+    def periodic_tracers(self, source, *, matrix="T", **kw):
+        """Operator.periodic on the resident operator over `matrix`: the periodic state of the cycle through the slots keep_slot() filled, as
+        they are (step_tracers says which slots those are)."""
+        rec = getattr(self, "_ops", {}).get(matrix)
+        if rec is None or not rec["op"].handle.value:
+            raise ValueError(f"no operator over {matrix}: keep_slot() first")
+        return rec["op"].periodic(source, **kw)
 
     def _kept_steady(self):
         """The operators a step of this loop does not store: those the last call kept, or -- after a full write that left the promise live -- those

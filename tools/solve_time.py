@@ -27,6 +27,9 @@ the floor of an iteration, whose five vector passes and scalar kernels the fusio
     step call of one step, and from these a later visit (right-hand side plus solve).  rhs_torch_us is the COMPOSITION's right-hand side,
     torch's σ·x (HIP events around 24 of them); the step call's own right-hand-side kernel has no entry point to time it through and is
     read from a kernel trace of `--step --step-route step` instead.  The record carries the device memory the slots take.
+--periodic [--ptol --restart --maxcycles --rtol]: the periodic state of that year -- the twelve slots of --step, θ = 1, lines, the age system
+    (d = 1 s⁻¹ at the surface, s = 1), k = 1 -- by otmb_op_periodic_dev: cycles, wall time, defect; then, in the same process, the same
+    number of plain cycles by otmb_op_step_dev in a loop from zero: their wall time and the defect they leave.
 --host: the parent's only route as well -- result_to_host, then scipy.sparse.linalg.bicgstab with the same (Jacobi) preconditioner."""
 import argparse
 import json
@@ -158,6 +161,55 @@ def step_times(asm, a):
                 f.write(json.dumps(r) + "\n")
 
 
+def periodic_times(asm, a):
+    """--periodic: the twelve months of --step as value slots, θ = 1, δt = 30 d, `lines`, the age system (d = 1 s⁻¹ on the level-1 wet cells,
+    s = 1), k = 1: the periodic state by otmb_op_periodic_dev (GMRES(--restart) on the cycle of twelve steps, to --ptol, at most --maxcycles
+    cycles), its cycles and wall time, and -- in the same process, with the same library -- the same number of plain cycles by
+    otmb_op_step_dev called in a loop from zero, their wall time and the defect ‖F(x) - x‖₂/‖F(0)‖₂ they leave."""
+    nslots, dt = 12, 30 * DAY
+    N = asm.N
+    cp, rv, nz = asm.out["T"]
+    nnz = int(cp[N].item()) - 1
+    op = Operator(asm.ctx, N, N, cp, rv, (nz[:nnz] * 1.0).contiguous())
+    op.set_lines(asm.vertical_lines())
+    op.set_slots(nslots)
+    for m in range(nslots):
+        op.set_values_dev((nz[:nnz] * (1.0 + 0.02 * m)).contiguous(), slot=m)
+    nsurf = int(torch.count_nonzero(asm.wet3d.reshape(-1)[: asm.nx * asm.ny]).item())  # level 1 comes first, in the grid and among the wet cells
+    d = torch.zeros(N, dtype=torch.float64, device="cuda")
+    d[:nsurf] = 1.0
+    s = torch.ones(N, dtype=torch.float64, device="cuda")
+    kw = dict(dt=dt, theta=1.0, first_slot=0, d=d, rtol=a.rtol, maxiter=a.maxiter, precond="lines")
+    rec = {"what": "periodic state of twelve monthly steps, T, age system", "n": N, "nnz": nnz, "nslots": nslots, "ncycle": nslots, "precond": "lines",
+           "theta": 1.0, "dt_s": dt, "ptol": a.ptol, "restart": a.restart, "maxcycles": a.maxcycles, "rtol": a.rtol}
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    X, info = op.periodic(s, ncycle=nslots, ptol=a.ptol, restart=a.restart, maxcycles=a.maxcycles, **kw)
+    torch.cuda.synchronize()
+    rec.update(periodic_s=time.perf_counter() - t0, cycles=int(info.cycles[0]), defect=float(info.defect[0]), reason=info.reason[0],
+               checksum=float(X.sum().item()))
+    # the same number of plain cycles from zero, then one more to measure what they leave
+    G, si = op.step(torch.zeros_like(s), nsteps=nslots, source=s, **kw)
+    assert si.steps_done == nslots, si
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    Y = torch.zeros_like(s)
+    for _ in range(rec["cycles"]):
+        Y, si = op.step(Y, nsteps=nslots, source=s, **kw)
+        assert si.steps_done == nslots, si
+    torch.cuda.synchronize()
+    rec["plain_s"] = time.perf_counter() - t0
+    FY, si = op.step(Y, nsteps=nslots, source=s, **kw)
+    rec["plain_defect"] = float((torch.linalg.norm(FY - Y) / torch.linalg.norm(G)).item())
+    rec["per_cycle_s"] = rec["plain_s"] / max(rec["cycles"], 1)
+    print(json.dumps(rec), flush=True)
+    op.close()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(rec) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -168,6 +220,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--step", action="store_true")
     ap.add_argument("--step-route", default="both", choices=["step", "compose", "both"])
+    ap.add_argument("--periodic", action="store_true")
+    ap.add_argument("--ptol", type=float, default=1e-8)
+    ap.add_argument("--restart", type=int, default=30)
+    ap.add_argument("--maxcycles", type=int, default=200)
+    ap.add_argument("--rtol", type=float, default=1e-10)
     ap.add_argument("--lib", default=None)
     a = ap.parse_args()
     if a.lib:
@@ -188,6 +245,8 @@ def main():
     N = asm.N
     if a.step:
         return step_times(asm, a)
+    if a.periodic:
+        return periodic_times(asm, a)
     t0 = time.perf_counter()
     h = asm.result_to_host()["T"]
     t_download = time.perf_counter() - t0
