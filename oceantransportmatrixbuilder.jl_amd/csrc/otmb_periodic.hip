@@ -7,19 +7,24 @@
 //     iteration i:  w = V_i - Φ·V_i                                   (one step call for every column that iterates; pd_defect_kernel)
 //                   h' = V_0..iᵀ·w;  w -= V_0..i·h'                    (pd_dots_kernel + pd_fold_kernel, pd_update_kernel)
 //                   h'' = V_0..iᵀ·w; w -= V_0..i·h'', ‖w‖²             (the same two kernels again: CGS2; the update leaves ‖w‖²'s partials)
-//                   the host: H(0..i, i) = h' + h'', H(i+1, i) = ‖w‖, the old rotations, a new one, the recursive residual
+//                   the host: H(0..i, i) = h' + h'', H(i+1, i) = ‖w‖, the old rotations, a new one, the recursive residual   (GmresLsq::push)
 //                   V_{i+1} = w / ‖w‖                                  (pd_scale_kernel)
 //     at a recursive residual <= ptol·‖g‖, at i + 1 = m, at ‖w‖ = 0 and when one cycle of maxcycles is left:
-//                   y from the triangle;  x += V_0..i·y                (pd_combine_kernel), then r = F(x) - x again (one step call with S)
+//                   y from the triangle (GmresLsq::solve);  x += V_0..i·y  (pd_combine_kernel), then r = F(x) - x again (one step call with S)
 // h', h'' and ‖w‖² stay on the device between the kernels (the update reads them where the fold wrote them); the host reads them once per
 // round, for every column together: 2·(i + 2) doubles a column.
 //
 // Every sum is deterministic and a column's own: a workgroup of 256 lanes takes PD_ROWS rows fixed by n, lane t the row pairs t, t + 256, ...
 // of them in that order (16-byte loads: every array of the workspace has an even leading dimension on a 256-byte base), one accumulator per
-// basis vector in a register block (op_blocks over the basis, as the products block columns), the workgroup's tree is the solver's (xor
-// shuffles in a wave, the four waves in order), ONE partial per workgroup and quantity, and pd_fold_kernel adds a quantity's partials in
-// index order.  No floating-point atomics, no FMA (-ffp-contract=off), one operation per statement where the order is the contract.
-// LDS: the workgroup reduction only.
+// basis vector in a register block (op_blocks over the basis, as the products block columns), the workgroup's tree is the solver's, the one
+// copy of otmb_op_sum.h (xor shuffles in a wave, the four waves in order), ONE partial per workgroup and quantity, and pd_fold_kernel adds a
+// quantity's partials in index order.  No floating-point atomics, no FMA (-ffp-contract=off), one operation per statement where the order is
+// the contract.  LDS: the workgroup reduction only.
+//
+// The host part: the column's least-squares problem is otmb_gmres.h's (host C++ alone, tested without a device); PdRun holds one call -- its
+// arguments, the workspace, the columns, the host's copies -- and its member functions are the steps of otmb_op_periodic_dev's outline:
+// the sources' norms, the first call, the rounds (cycle, orthogonalise, read_hs, judged, advance) and the report (sv_report_open, which the
+// solver shares, as it shares the step's argument checks: otmb_solve.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -27,6 +32,8 @@
 #include <string>
 #include <vector>
 
+#include "otmb_gmres.h"
+#include "otmb_op_sum.h"
 #include "otmb_solve.h"
 
 #define PD_ROWS 2048  // rows per workgroup: 256 lanes x 4 pairs
@@ -55,28 +62,6 @@ __device__ __forceinline__ void pd_store(double *__restrict__ p, i64 i, i64 n, b
 }
 // the q-th row pair of this lane: its first row (>= n: the lane is done)
 __device__ __forceinline__ i64 pd_row(int q) { return 2 * ((i64)blockIdx.x * (PD_ROWS / 2) + threadIdx.x + 256 * q); }
-
-// ---- sums: the solver's tree ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double pd_wave_sum(double x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x = x + __shfl_xor(x, d);
-    return x;
-}
-// 256 threads, NV values each: thread 0 gets the sums (waves in order).  red: 4 * NV doubles of LDS.
-template <int NV>
-__device__ __forceinline__ void pd_block_sum(double (&x)[NV], double *red) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < NV; ++q) {
-        const double s = pd_wave_sum(x[q]);
-        if (lane == 0) red[w * NV + q] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < NV; ++q) x[q] = ((red[q] + red[NV + q]) + red[2 * NV + q]) + red[3 * NV + q];
-    }
-}
 
 // ---- h = Vᵀ·w for NB basis vectors (leading dimension ldv) and, NORM, ‖w‖²: a lane's share ------------------------------------------------
 template <int NB, bool NORM>
@@ -114,7 +99,7 @@ __global__ __launch_bounds__(256) void pd_dots_kernel(i64 n, const double *__res
     __shared__ double red[4 * (NB + 1)];
     double acc[NB + 1];
     pd_dots_lane<NB, NORM>(n, V, ldv, w, acc);
-    pd_block_sum<NB + 1>(acc, red);
+    op_block_sum<NB + 1>(acc, red);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int b = 0; b < NB; ++b) part[(i64)b * np + blockIdx.x] = acc[b];
@@ -164,7 +149,7 @@ __global__ __launch_bounds__(256) void pd_update_kernel(i64 n, const double *__r
     __shared__ double red[4];
     double acc[1] = {pd_update_lane<NORM>(n, V, ldv, nj, h, w)};
     if (NORM) {
-        pd_block_sum<1>(acc, red);
+        op_block_sum<1>(acc, red);
         if (threadIdx.x == 0) pnorm[blockIdx.x] = acc[0];
     }
 }
@@ -211,7 +196,7 @@ __global__ __launch_bounds__(256) void pd_defect_kernel(i64 n, const double *__r
         }
     }
     if (pnorm) {  // (uniform over the workgroup: every lane reaches the barrier)
-        pd_block_sum<1>(acc, red);
+        op_block_sum<1>(acc, red);
         if (threadIdx.x == 0) pnorm[blockIdx.x] = acc[0];
     }
 }
@@ -229,11 +214,12 @@ __global__ __launch_bounds__(256) void pd_scale_kernel(i64 n, double *__restrict
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
-struct PdCol {  // one column's iteration: the triangle R (column i at R[i * (m + 1) ..]), the rotations and the rotated right-hand side
+struct PdCol {  // one column's iteration; ls (otmb_gmres.h): the triangle, the rotations, the rotated right-hand side and the iteration ls.i
     int phase = PD_ARNOLDI, reason = OTMB_PERIODIC_CONVERGED;
-    i64 cycles = 0, i = 0;
+    i64 cycles = 0;
     double defect = NAN, gnorm = 0.0;
-    std::vector<double> R, cs, sn, gv;
+    GmresLsq ls;
+    void stop(int why) { phase = PD_STOPPED, reason = why; }
 };
 
 struct PdWork {  // the arrays inside op->pd; every vector has the leading dimension ld (even)
@@ -241,7 +227,8 @@ struct PdWork {  // the arrays inside op->pd; every vector has the leading dimen
     double *V, *W, *Sb, *part, *hs, *yv;  // V: k bases of m + 1 vectors; W, Sb: k columns each (contiguous: 2k for the first call)
     double *v(i64 c, i64 j) const { return V + (c * (m + 1) + j) * ld; }
     double *partc(i64 c) const { return part + c * (m + 2) * np; }
-    double *hsc(i64 c) const { return hs + c * 2 * (m + 2); }
+    i64 hso(i64 c) const { return c * 2 * (m + 2); }  // column c's scalars: h' (m + 2 doubles), then h''; the host's copy has the same layout
+    double *hsc(i64 c) const { return hs + hso(c); }
 };
 
 static int32_t pd_work(otmb_op *op, i64 k, i64 m, PdWork &w) {
@@ -264,23 +251,277 @@ static int32_t pd_work(otmb_op *op, i64 k, i64 m, PdWork &w) {
 static int32_t pd_check(otmb_op *op, int64_t k, double dt, double theta, int64_t ncycle, int64_t first_slot, const double *S, int64_t lds, double *X, int64_t ldx,
                         double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, const int64_t *cycles,
                         const double *defect, const int32_t *reason) {
-    const char *more = !cycles || !defect || !reason                           ? "null argument"
-                       : !(rtol > 0.0)                                         ? "rtol must be > 0"
-                       : maxiter < 0                                           ? "maxiter must be >= 0"
-                       : !(dt > 0.0) || !std::isfinite(dt)                     ? "dt must be > 0 and finite"
-                       : !(theta > 0.0 && theta <= 1.0)                        ? "theta must be in (0, 1]"
-                       : ncycle < 1                                            ? "ncycle must be >= 1"
-                       : first_slot < 0 || first_slot >= (i64)op->slots.size() ? "first_slot is not a slot of the operator (otmb_op_set_slots)"
-                       : !(ptol > 0.0)                                         ? "ptol must be > 0"
-                       : restart < 1 || restart >= (1ll << 20)                 ? "restart must be >= 1 (and below 2^20)"
-                       : maxcycles < 0                                         ? "maxcycles must be >= 0"
-                                                                               : nullptr;
+    const char *more = !cycles || !defect || !reason ? "null argument" : sv_step_complaint(op, rtol, maxiter, dt, theta, ncycle >= 1, "ncycle must be >= 1", first_slot);
+    if (!more)
+        more = !(ptol > 0.0)                           ? "ptol must be > 0"
+               : restart < 1 || restart >= (1ll << 20) ? "restart must be >= 1 (and below 2^20)"
+               : maxcycles < 0                         ? "maxcycles must be >= 0"
+                                                       : nullptr;
     return sv_check_step(op, precond, k, S, lds, X, ldx, more);
+}
+
+// g = 0: x = 0 at no cost
+static int32_t pd_all_zero(i64 k, int64_t *cycles, double *defect, int32_t *reason) {
+    for (i64 c = 0; c < k; ++c) cycles[c] = 0, defect[c] = 0.0, reason[c] = OTMB_PERIODIC_CONVERGED;
+    return OTMB_OK;
 }
 
 struct PdItem {  // a column of one step call: column col's state from its basis vector (from >= 0), from X (-1) or zero (-2)
     i64 col, from;
 };
+
+struct PdRun {  // one call: the operator, the call's arguments, the workspace, the columns and the host's copies
+    otmb_op *op;
+    otmb_ctx *ctx;
+    hipStream_t st;
+    int32_t adjoint;  // the arguments, in the call's order (restart is m)
+    i64 k;
+    const double *d;
+    double dt, theta;
+    i64 ncycle, first_slot;
+    const double *S;
+    i64 lds;
+    double *X;
+    i64 ldx;
+    int32_t use_x0;
+    double rtol;
+    i64 maxiter;
+    int32_t precond;
+    double ptol;
+    i64 m, maxcycles;
+    PdWork w{};
+    dim3 grid, block;
+    bool alx = false;  // X takes the 16-byte path
+    std::vector<PdCol> col;
+    std::vector<double> hs, yh;  // the host's copy of w.hs (read_hs; hsh), the y of the restarts
+    std::string step_msg;        // the text of the first step call that left a column not converged
+    std::vector<int64_t> s_it;   // a step call's report
+    std::vector<double> s_rr;
+    std::vector<int32_t> s_why;
+
+    const double *hsh(i64 c) const { return hs.data() + w.hso(c); }  // column c's scalars as the last read_hs left them
+    void fold(i64 c, i64 nq, double *out) { hipLaunchKernelGGL(pd_fold_kernel, dim3(1), block, 0, st, (const double *)w.partc(c), w.np, nq, out); }
+    int32_t prepare();
+    int32_t read_hs();
+    int32_t cycle(std::vector<PdItem> &items, bool withS, double *sbuf);
+    void defect_of(i64 c, i64 p, bool minus_x);
+    void judged(i64 c, double beta);
+    int32_t source_norms(std::vector<PdItem> &items);
+    int32_t first_call(std::vector<PdItem> &items);
+    void orthogonalise(i64 c, i64 i, i64 p);
+    int32_t advance(i64 c);
+    int32_t round(bool &more);
+    int32_t report(int64_t *cycles, double *defect, int32_t *reason);
+};
+
+int32_t PdRun::prepare() {
+    int32_t rc;
+    if ((rc = pd_work(op, k, m, w))) return rc;
+    grid = dim3((unsigned)w.np), block = dim3(256);
+    alx = ((uintptr_t)X & 15) == 0 && (ldx & 1) == 0;
+    col.resize((size_t)k);
+    hs.resize((size_t)(2 * (m + 2) * k)), yh.resize((size_t)(m * k));
+    return OTMB_OK;
+}
+
+int32_t PdRun::read_hs() {
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(hs.data(), w.hs, hs.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return OTMB_OK;
+}
+
+// One step call for `items` (in this order, compact in W from column 0; withS: their sources, gathered into sbuf): W = the cycle's end
+// states.  A call that leaves columns not converged stops those (STEP_FAILED) and is repeated without them; the call that completes
+// counts one cycle for each of its columns.  items comes back as the columns of that call (their positions in W).
+int32_t PdRun::cycle(std::vector<PdItem> &items, bool withS, double *sbuf) {
+    const i64 n = w.n, ld = w.ld;
+    while (!items.empty()) {
+        const i64 kk = (i64)items.size();
+        for (i64 p = 0; p < kk; ++p) {
+            const PdItem &it = items[(size_t)p];
+            if (it.from == -2)
+                HIP_TRY(ctx, hipMemsetAsync(w.W + p * ld, 0, (size_t)n * 8, st));
+            else
+                HIP_TRY(ctx, hipMemcpyAsync(w.W + p * ld, it.from >= 0 ? w.v(it.col, it.from) : X + it.col * ldx, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+            if (withS) HIP_TRY(ctx, hipMemcpyAsync(sbuf + p * ld, S + it.col * lds, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+        }
+        s_it.assign((size_t)(ncycle * kk), 0), s_rr.assign((size_t)(ncycle * kk), 0.0), s_why.assign((size_t)(ncycle * kk), 0);
+        int64_t done = 0;
+        const int32_t rc = otmb_op_step_dev(op, adjoint, kk, d, dt, theta, ncycle, first_slot, withS ? sbuf : nullptr, ld, w.W, ld, rtol, maxiter, precond, &done,
+                                            s_it.data(), s_rr.data(), s_why.data());
+        if (rc == OTMB_OK) {
+            std::vector<char> seen((size_t)k, 0);  // (the first call holds a column twice: one call, one cycle)
+            for (const PdItem &it : items)
+                if (!seen[(size_t)it.col]++) col[(size_t)it.col].cycles += 1;
+            return OTMB_OK;
+        }
+        if (rc != OTMB_ERR_NOT_CONVERGED) return rc;
+        if (step_msg.empty()) step_msg = ctx->err;
+        std::vector<PdItem> left;
+        for (i64 p = 0; p < kk; ++p)
+            if (s_why[(size_t)(done * kk + p)] != OTMB_SOLVE_CONVERGED) col[(size_t)items[(size_t)p].col].stop(OTMB_PERIODIC_STEP_FAILED);
+        for (const PdItem &it : items)
+            if (col[(size_t)it.col].phase != PD_STOPPED) left.push_back(it);
+        if (left.size() == items.size()) return otmb_fail(ctx, OTMB_ERR_HIP, "periodic: a step call failed without a failing column");  // (cannot happen)
+        items.swap(left);
+    }
+    return OTMB_OK;
+}
+
+// r = W[p] - x (or W[p]) -> V_0 of column c, ‖r‖² -> hs[c][0]
+void PdRun::defect_of(i64 c, i64 p, bool minus_x) {
+    hipLaunchKernelGGL(pd_defect_kernel, grid, block, 0, st, w.n, (const double *)(w.W + p * w.ld), minus_x ? (const double *)(X + c * ldx) : nullptr, alx,
+                       w.v(c, 0), w.partc(c));
+    fold(c, 1, w.hsc(c));
+}
+
+// column c starts a Krylov space from its explicit r (in V_0, norm beta), or is accepted on it
+void PdRun::judged(i64 c, double beta) {
+    PdCol &q = col[(size_t)c];
+    q.defect = beta / q.gnorm;
+    if (!std::isfinite(beta)) return q.stop(OTMB_PERIODIC_NONFINITE);
+    if (beta <= ptol * q.gnorm) return q.stop(OTMB_PERIODIC_CONVERGED);
+    hipLaunchKernelGGL(pd_scale_kernel, grid, block, 0, st, w.n, w.v(c, 0), beta);
+    q.phase = PD_ARNOLDI;
+    q.ls.start(m, beta);
+}
+
+// the sources' norms: a zero column has g = 0.  items: the columns of the first call
+int32_t PdRun::source_norms(std::vector<PdItem> &items) {
+    int32_t rc;
+    for (i64 c = 0; c < k; ++c) {
+        HIP_TRY(ctx, hipMemcpyAsync(w.W + c * w.ld, S + c * lds, (size_t)w.n * 8, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(pd_defect_kernel, grid, block, 0, st, w.n, (const double *)(w.W + c * w.ld), (const double *)nullptr, false, (double *)nullptr, w.partc(c));
+        fold(c, 1, w.hsc(c));
+    }
+    if ((rc = read_hs())) return rc;
+    for (i64 c = 0; c < k; ++c) {
+        PdCol &q = col[(size_t)c];
+        if (hsh(c)[0] == 0.0) {
+            q.stop(OTMB_PERIODIC_CONVERGED), q.defect = 0.0;
+        } else if (maxcycles < 1) {
+            q.stop(OTMB_PERIODIC_MAXCYCLES);
+        } else {
+            items.push_back({c, use_x0 ? (i64)-1 : (i64)-2});
+        }
+    }
+    return OTMB_OK;
+}
+
+// the first call: F(x) (and, with a start, g beside it), then every live column's first explicit r
+int32_t PdRun::first_call(std::vector<PdItem> &items) {
+    const i64 n = w.n, ld = w.ld;
+    int32_t rc;
+    if (use_x0)
+        for (size_t p = 0, live = items.size(); p < live; ++p) items.push_back({items[p].col, -2});
+    if ((rc = cycle(items, true, use_x0 ? w.V : w.Sb))) return rc;  // (with a start the 2k sources lie in the bases, which are not in use yet)
+    // from here on X is written: the zero columns, and a start of zero
+    for (i64 c = 0; c < k; ++c)
+        if (!use_x0 || (col[(size_t)c].phase == PD_STOPPED && col[(size_t)c].reason == OTMB_PERIODIC_CONVERGED))
+            HIP_TRY(ctx, hipMemsetAsync(X + c * ldx, 0, (size_t)n * 8, st));
+    const i64 live = use_x0 ? (i64)items.size() / 2 : (i64)items.size();
+    if (use_x0)  // ‖g‖² first: the defect's fold would overwrite the same slot, so it goes to the second half of the column's scalars
+        for (i64 p = 0; p < live; ++p) {
+            const i64 c = items[(size_t)p].col;
+            hipLaunchKernelGGL(pd_defect_kernel, grid, block, 0, st, n, (const double *)(w.W + (live + p) * ld), (const double *)nullptr, false, (double *)nullptr,
+                               w.partc(c));
+            fold(c, 1, w.hsc(c) + (m + 2));
+        }
+    for (i64 p = 0; p < live; ++p) defect_of(items[(size_t)p].col, p, use_x0 != 0);
+    if ((rc = read_hs())) return rc;
+    for (i64 p = 0; p < live; ++p) {
+        const i64 c = items[(size_t)p].col;
+        PdCol &q = col[(size_t)c];
+        const double beta = std::sqrt(hsh(c)[0]);
+        q.gnorm = use_x0 ? std::sqrt(hsh(c)[m + 2]) : beta;
+        if (q.gnorm == 0.0) {  // (a source that is not zero whose cycle underflows to zero)
+            HIP_TRY(ctx, hipMemsetAsync(X + c * ldx, 0, (size_t)n * 8, st));
+            q.stop(OTMB_PERIODIC_CONVERGED), q.defect = 0.0;
+        } else if (!std::isfinite(q.gnorm)) {
+            q.stop(OTMB_PERIODIC_NONFINITE);
+        } else {
+            judged(c, beta);
+        }
+    }
+    return OTMB_OK;
+}
+
+// iteration i of column c on the device, from Φ·V_i in W[p]: w = V_i - Φ·V_i into V_{i+1}, then CGS2 against V_0..i; h', h'' and ‖w‖² -> hs[c]
+void PdRun::orthogonalise(i64 c, i64 i, i64 p) {
+    const i64 n = w.n, ld = w.ld, np = w.np;
+    double *wv = w.v(c, i + 1), *h1 = w.hsc(c), *h2 = w.hsc(c) + (m + 2);
+    const double *V = w.v(c, 0);
+    hipLaunchKernelGGL(pd_defect_kernel, grid, block, 0, st, n, (const double *)w.v(c, i), (const double *)(w.W + p * ld), true, wv, (double *)nullptr);
+    for (int pass = 0; pass < 2; ++pass) {
+        double *h = pass ? h2 : h1;
+        op_blocks<PD_NB>(0, i + 1, [&](auto nb, i64 j0) {
+            constexpr int NB = decltype(nb)::value;
+            hipLaunchKernelGGL((j0 == 0 ? pd_dots_kernel<NB, true> : pd_dots_kernel<NB, false>), grid, block, 0, st, n, V + j0 * ld, ld, (const double *)wv,
+                               w.partc(c) + j0 * np, np, w.partc(c) + (i + 1) * np);
+        });
+        fold(c, i + 2, h);
+        if (pass == 0) {
+            hipLaunchKernelGGL(pd_update_kernel<false>, grid, block, 0, st, n, V, ld, i + 1, (const double *)h, wv, (double *)nullptr);
+        } else {
+            hipLaunchKernelGGL(pd_update_kernel<true>, grid, block, 0, st, n, V, ld, i + 1, (const double *)h, wv, w.partc(c) + (i + 1) * np);
+            hipLaunchKernelGGL(pd_fold_kernel, dim3(1), block, 0, st, (const double *)(w.partc(c) + (i + 1) * np), np, (i64)1, h + (i + 1));
+        }
+    }
+}
+
+// the host's part of column c's iteration, from the scalars read_hs left: the triangle's new column, then the next basis vector or,
+// where the column ends its Krylov space, y, x += V·y and the verifying cycle next
+int32_t PdRun::advance(i64 c) {
+    PdCol &q = col[(size_t)c];
+    const i64 i = q.ls.i;
+    double hn, est;
+    if (!q.ls.push(hsh(c), hsh(c) + (m + 2), &hn, &est)) {
+        q.stop(OTMB_PERIODIC_NONFINITE);
+        return OTMB_OK;
+    }
+    if (!(est <= ptol * q.gnorm || q.ls.i == m || hn == 0.0 || q.cycles + 1 >= maxcycles)) {
+        hipLaunchKernelGGL(pd_scale_kernel, grid, block, 0, st, w.n, w.v(c, i + 1), hn);
+        return OTMB_OK;
+    }
+    double *y = yh.data() + c * m;
+    q.ls.solve(y);
+    HIP_TRY(ctx, hipMemcpyAsync(w.yv + c * m, y, (size_t)q.ls.i * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(pd_combine_kernel, grid, block, 0, st, w.n, (const double *)w.v(c, 0), w.ld, q.ls.i, (const double *)(w.yv + c * m), X + c * ldx, alx);
+    q.phase = PD_VERIFY;
+    return OTMB_OK;
+}
+
+// one round: one step call for the columns that iterate, one for those that verify.  more = false: every column has stopped
+int32_t PdRun::round(bool &more) {
+    int32_t rc;
+    std::vector<PdItem> ia, iv;
+    for (i64 c = 0; c < k; ++c) {
+        PdCol &q = col[(size_t)c];
+        if (q.phase == PD_ARNOLDI && q.ls.i == 0 && q.cycles + 2 > maxcycles) q.stop(OTMB_PERIODIC_MAXCYCLES);  // no verifying cycle could follow
+        if (q.phase == PD_ARNOLDI) ia.push_back({c, q.ls.i});
+        if (q.phase == PD_VERIFY) iv.push_back({c, -1});
+    }
+    more = !(ia.empty() && iv.empty());
+    if (!more) return OTMB_OK;
+    if ((rc = cycle(ia, false, nullptr))) return rc;
+    for (size_t p = 0; p < ia.size(); ++p) orthogonalise(ia[p].col, ia[p].from, (i64)p);
+    if ((rc = cycle(iv, true, w.Sb))) return rc;
+    for (size_t p = 0; p < iv.size(); ++p) defect_of(iv[p].col, (i64)p, true);
+    if ((rc = read_hs())) return rc;
+    for (const PdItem &it : iv) judged(it.col, std::sqrt(hsh(it.col)[0]));
+    for (const PdItem &it : ia)
+        if ((rc = advance(it.col))) return rc;
+    HIP_TRY(ctx, hipGetLastError());
+    return OTMB_OK;
+}
+
+int32_t PdRun::report(int64_t *cycles, double *defect, int32_t *reason) {
+    for (i64 c = 0; c < k; ++c) cycles[c] = col[(size_t)c].cycles, defect[c] = col[(size_t)c].defect, reason[c] = col[(size_t)c].reason;
+    static const char *const names[] = {"converged", "maxcycles", "step failed", "nonfinite"};
+    return sv_report_open(ctx, "periodic: %lld of %lld columns; the first is column %lld: %s after %lld cycles, defect %.3e", names, k, reason, cycles, defect,
+                          step_msg.empty() ? step_msg : "; the step: " + step_msg);
+}
 
 extern "C" {
 
@@ -292,253 +533,20 @@ int32_t otmb_op_periodic_dev(otmb_op *op, int32_t adjoint, int64_t k, const doub
     if ((rc = pd_check(op, k, dt, theta, ncycle, first_slot, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect, reason)))
         return rc;
     otmb_ctx *ctx = op->ctx;
-    hipStream_t st = ctx->stream;
-    const i64 n = op->n, m = restart;
-    const auto all_zero = [&]() {  // g = 0: x = 0 at no cost
-        for (i64 c = 0; c < k; ++c) cycles[c] = 0, defect[c] = 0.0, reason[c] = OTMB_PERIODIC_CONVERGED;
-    };
-    if (n == 0) {
-        all_zero();
-        return OTMB_OK;
-    }
+    // the trivial answers: no rows, no source
+    if (op->n == 0) return pd_all_zero(k, cycles, defect, reason);
     HIP_TRY(ctx, hipSetDevice(op->device));
     if (!S) {
-        HIP_TRY(ctx, hipMemset2DAsync(X, (size_t)ldx * 8, 0, (size_t)n * 8, (size_t)k, st));
-        all_zero();
-        return OTMB_OK;
+        HIP_TRY(ctx, hipMemset2DAsync(X, (size_t)ldx * 8, 0, (size_t)op->n * 8, (size_t)k, ctx->stream));
+        return pd_all_zero(k, cycles, defect, reason);
     }
-    PdWork w;
-    if ((rc = pd_work(op, k, m, w))) return rc;
-    const i64 ld = w.ld, np = w.np;
-    const dim3 grid((unsigned)np), block(256);
-    const bool alx = ((uintptr_t)X & 15) == 0 && (ldx & 1) == 0;
-    std::vector<PdCol> col((size_t)k);
-    std::vector<double> hs((size_t)(2 * (m + 2) * k)), yh((size_t)(m * k));
-    std::string step_msg;  // the text of the first step call that left a column not converged
-
-    const auto stop = [&](PdCol &c, int why) { c.phase = PD_STOPPED, c.reason = why; };
-    const auto fold = [&](i64 c, i64 nq, double *out) { hipLaunchKernelGGL(pd_fold_kernel, dim3(1), block, 0, st, (const double *)w.partc(c), np, nq, out); };
-    const auto read_hs = [&]() -> int32_t {
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(hs.data(), w.hs, hs.size() * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        return OTMB_OK;
-    };
-    // One step call for `items` (in this order, compact in W from column 0; withS: their sources, gathered into sbuf): W = the cycle's end
-    // states.  A call that leaves columns not converged stops those (STEP_FAILED) and is repeated without them; the call that completes
-    // counts one cycle for each of its columns.  items comes back as the columns of that call (their positions in W).
-    std::vector<int64_t> s_it;
-    std::vector<double> s_rr;
-    std::vector<int32_t> s_why;
-    const auto cycle = [&](std::vector<PdItem> &items, bool withS, double *sbuf) -> int32_t {
-        while (!items.empty()) {
-            const i64 kk = (i64)items.size();
-            for (i64 p = 0; p < kk; ++p) {
-                const PdItem &it = items[(size_t)p];
-                if (it.from == -2)
-                    HIP_TRY(ctx, hipMemsetAsync(w.W + p * ld, 0, (size_t)n * 8, st));
-                else
-                    HIP_TRY(ctx, hipMemcpyAsync(w.W + p * ld, it.from >= 0 ? w.v(it.col, it.from) : X + it.col * ldx, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-                if (withS) HIP_TRY(ctx, hipMemcpyAsync(sbuf + p * ld, S + it.col * lds, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-            }
-            s_it.assign((size_t)(ncycle * kk), 0), s_rr.assign((size_t)(ncycle * kk), 0.0), s_why.assign((size_t)(ncycle * kk), 0);
-            int64_t done = 0;
-            rc = otmb_op_step_dev(op, adjoint, kk, d, dt, theta, ncycle, first_slot, withS ? sbuf : nullptr, ld, w.W, ld, rtol, maxiter, precond, &done,
-                                  s_it.data(), s_rr.data(), s_why.data());
-            if (rc == OTMB_OK) {
-                std::vector<char> seen((size_t)k, 0);  // (the first call holds a column twice: one call, one cycle)
-                for (const PdItem &it : items)
-                    if (!seen[(size_t)it.col]++) col[(size_t)it.col].cycles += 1;
-                return OTMB_OK;
-            }
-            if (rc != OTMB_ERR_NOT_CONVERGED) return rc;
-            if (step_msg.empty()) step_msg = ctx->err;
-            std::vector<PdItem> left;
-            for (i64 p = 0; p < kk; ++p)
-                if (s_why[(size_t)(done * kk + p)] != OTMB_SOLVE_CONVERGED) stop(col[(size_t)items[(size_t)p].col], OTMB_PERIODIC_STEP_FAILED);
-            for (const PdItem &it : items)
-                if (col[(size_t)it.col].phase != PD_STOPPED) left.push_back(it);
-            if (left.size() == items.size()) return otmb_fail(ctx, OTMB_ERR_HIP, "periodic: a step call failed without a failing column");  // (cannot happen)
-            items.swap(left);
-        }
-        return OTMB_OK;
-    };
-    // r = W[p] - x (or W[p]) -> V_0 of column c, ‖r‖² -> hs[c][0]
-    const auto defect_of = [&](i64 c, i64 p, bool minus_x) {
-        hipLaunchKernelGGL(pd_defect_kernel, grid, block, 0, st, n, (const double *)(w.W + p * ld), minus_x ? (const double *)(X + c * ldx) : nullptr, alx,
-                           w.v(c, 0), w.partc(c));
-        fold(c, 1, w.hsc(c));
-    };
-    // the column starts a Krylov space from its explicit r (in V_0, norm beta), or is accepted on it
-    const auto judged = [&](PdCol &c, i64 ci, double beta) {
-        c.defect = beta / c.gnorm;
-        if (!std::isfinite(beta)) return stop(c, OTMB_PERIODIC_NONFINITE);
-        if (beta <= ptol * c.gnorm) return stop(c, OTMB_PERIODIC_CONVERGED);
-        hipLaunchKernelGGL(pd_scale_kernel, grid, block, 0, st, n, w.v(ci, 0), beta);
-        c.phase = PD_ARNOLDI, c.i = 0;
-        c.R.assign((size_t)((m + 1) * m), 0.0), c.cs.assign((size_t)m, 0.0), c.sn.assign((size_t)m, 0.0), c.gv.assign((size_t)(m + 1), 0.0);
-        c.gv[0] = beta;
-    };
-
-    // ---- the sources' norms: a zero column has g = 0 ------------------------------------------------------------------------------------
-    for (i64 c = 0; c < k; ++c) {
-        HIP_TRY(ctx, hipMemcpyAsync(w.W + c * ld, S + c * lds, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(pd_defect_kernel, grid, block, 0, st, n, (const double *)(w.W + c * ld), (const double *)nullptr, false, (double *)nullptr, w.partc(c));
-        fold(c, 1, w.hsc(c));
-    }
-    if ((rc = read_hs())) return rc;
+    PdRun r{op, ctx, ctx->stream, adjoint, k, d, dt, theta, ncycle, first_slot, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles};
     std::vector<PdItem> items;
-    for (i64 c = 0; c < k; ++c) {
-        PdCol &q = col[(size_t)c];
-        if (hs[(size_t)(c * 2 * (m + 2))] == 0.0) {
-            stop(q, OTMB_PERIODIC_CONVERGED), q.defect = 0.0;
-        } else if (maxcycles < 1) {
-            stop(q, OTMB_PERIODIC_MAXCYCLES);
-        } else {
-            items.push_back({c, use_x0 ? (i64)-1 : (i64)-2});
-        }
-    }
-    // ---- the first call: F(x) (and, with a start, g beside it) --------------------------------------------------------------------------
-    if (use_x0)
-        for (size_t p = 0, live = items.size(); p < live; ++p) items.push_back({items[p].col, -2});
-    if ((rc = cycle(items, true, use_x0 ? w.V : w.Sb))) return rc;  // (with a start the 2k sources lie in the bases, which are not in use yet)
-    // from here on X is written: the zero columns, and a start of zero
-    for (i64 c = 0; c < k; ++c)
-        if (!use_x0 || (col[(size_t)c].phase == PD_STOPPED && col[(size_t)c].reason == OTMB_PERIODIC_CONVERGED))
-            HIP_TRY(ctx, hipMemsetAsync(X + c * ldx, 0, (size_t)n * 8, st));
-    {
-        const i64 live = use_x0 ? (i64)items.size() / 2 : (i64)items.size();
-        if (use_x0)  // ‖g‖² first: the defect's fold would overwrite the same slot, so it goes to the second half of the column's scalars
-            for (i64 p = 0; p < live; ++p) {
-                const i64 c = items[(size_t)p].col;
-                hipLaunchKernelGGL(pd_defect_kernel, grid, block, 0, st, n, (const double *)(w.W + (live + p) * ld), (const double *)nullptr, false,
-                                   (double *)nullptr, w.partc(c));
-                fold(c, 1, w.hsc(c) + (m + 2));
-            }
-        for (i64 p = 0; p < live; ++p) defect_of(items[(size_t)p].col, p, use_x0 != 0);
-        if ((rc = read_hs())) return rc;
-        for (i64 p = 0; p < live; ++p) {
-            const i64 c = items[(size_t)p].col;
-            PdCol &q = col[(size_t)c];
-            const double beta = std::sqrt(hs[(size_t)(c * 2 * (m + 2))]);
-            q.gnorm = use_x0 ? std::sqrt(hs[(size_t)(c * 2 * (m + 2) + (m + 2))]) : beta;
-            if (q.gnorm == 0.0) {  // (a source that is not zero whose cycle underflows to zero)
-                HIP_TRY(ctx, hipMemsetAsync(X + c * ldx, 0, (size_t)n * 8, st));
-                stop(q, OTMB_PERIODIC_CONVERGED), q.defect = 0.0;
-            } else if (!std::isfinite(q.gnorm)) {
-                stop(q, OTMB_PERIODIC_NONFINITE);
-            } else {
-                judged(q, c, beta);
-            }
-        }
-    }
-
-    // ---- rounds: one step call for the columns that iterate, one for those that verify ------------------------------------------------------
-    for (;;) {
-        std::vector<PdItem> ia, iv;
-        for (i64 c = 0; c < k; ++c) {
-            PdCol &q = col[(size_t)c];
-            if (q.phase == PD_ARNOLDI && q.i == 0 && q.cycles + 2 > maxcycles) stop(q, OTMB_PERIODIC_MAXCYCLES);  // no verifying cycle could follow
-            if (q.phase == PD_ARNOLDI) ia.push_back({c, q.i});
-            if (q.phase == PD_VERIFY) iv.push_back({c, -1});
-        }
-        if (ia.empty() && iv.empty()) break;
-        if ((rc = cycle(ia, false, nullptr))) return rc;
-        for (size_t p = 0; p < ia.size(); ++p) {
-            const i64 c = ia[p].col, i = ia[p].from;
-            double *wv = w.v(c, i + 1), *h1 = w.hsc(c), *h2 = w.hsc(c) + (m + 2);
-            const double *V = w.v(c, 0);
-            // w = V_i - Φ·V_i
-            hipLaunchKernelGGL(pd_defect_kernel, grid, block, 0, st, n, (const double *)w.v(c, i), (const double *)(w.W + (i64)p * ld), true, wv, (double *)nullptr);
-            for (int pass = 0; pass < 2; ++pass) {
-                double *h = pass ? h2 : h1;
-                op_blocks<PD_NB>(0, i + 1, [&](auto nb, i64 j0) {
-                    constexpr int NB = decltype(nb)::value;
-                    hipLaunchKernelGGL((j0 == 0 ? pd_dots_kernel<NB, true> : pd_dots_kernel<NB, false>), grid, block, 0, st, n, V + j0 * ld, ld, (const double *)wv,
-                                       w.partc(c) + j0 * np, np, w.partc(c) + (i + 1) * np);
-                });
-                fold(c, i + 2, h);
-                if (pass == 0) {
-                    hipLaunchKernelGGL(pd_update_kernel<false>, grid, block, 0, st, n, V, ld, i + 1, (const double *)h, wv, (double *)nullptr);
-                } else {
-                    hipLaunchKernelGGL(pd_update_kernel<true>, grid, block, 0, st, n, V, ld, i + 1, (const double *)h, wv, w.partc(c) + (i + 1) * np);
-                    hipLaunchKernelGGL(pd_fold_kernel, dim3(1), block, 0, st, (const double *)(w.partc(c) + (i + 1) * np), np, (i64)1, h + (i + 1));
-                }
-            }
-        }
-        if ((rc = cycle(iv, true, w.Sb))) return rc;
-        for (size_t p = 0; p < iv.size(); ++p) defect_of(iv[p].col, (i64)p, true);
-        if ((rc = read_hs())) return rc;
-        for (const PdItem &it : iv) {
-            const i64 c = it.col;
-            judged(col[(size_t)c], c, std::sqrt(hs[(size_t)(c * 2 * (m + 2))]));
-        }
-        for (const PdItem &it : ia) {
-            const i64 c = it.col, i = it.from;
-            PdCol &q = col[(size_t)c];
-            const double *h1 = hs.data() + c * 2 * (m + 2), *h2 = h1 + (m + 2);
-            double *r = q.R.data() + i * (m + 1);
-            bool finite = std::isfinite(h1[i + 1]) && std::isfinite(h2[i + 1]);
-            for (i64 j = 0; j <= i; ++j) {
-                r[j] = h1[j] + h2[j];
-                finite = finite && std::isfinite(r[j]);
-            }
-            const double hn = std::sqrt(h2[i + 1]);
-            if (!finite) {
-                stop(q, OTMB_PERIODIC_NONFINITE);
-                continue;
-            }
-            for (i64 j = 0; j < i; ++j) {  // the old rotations, then the one that clears H(i + 1, i)
-                const double t = q.cs[(size_t)j] * r[j] + q.sn[(size_t)j] * r[j + 1];
-                r[j + 1] = q.cs[(size_t)j] * r[j + 1] - q.sn[(size_t)j] * r[j];
-                r[j] = t;
-            }
-            const double rr = std::hypot(r[i], hn);
-            q.cs[(size_t)i] = rr > 0.0 ? r[i] / rr : 1.0;
-            q.sn[(size_t)i] = rr > 0.0 ? hn / rr : 0.0;
-            r[i] = rr;
-            q.gv[(size_t)(i + 1)] = -(q.sn[(size_t)i] * q.gv[(size_t)i]);
-            q.gv[(size_t)i] = q.cs[(size_t)i] * q.gv[(size_t)i];
-            q.i = i + 1;
-            const double est = std::fabs(q.gv[(size_t)(i + 1)]);
-            if (!(est <= ptol * q.gnorm || q.i == m || hn == 0.0 || q.cycles + 1 >= maxcycles)) {
-                hipLaunchKernelGGL(pd_scale_kernel, grid, block, 0, st, n, w.v(c, i + 1), hn);
-                continue;
-            }
-            // y from the triangle (back substitution), x += V·y, then the explicit r
-            double *y = yh.data() + c * m;
-            for (i64 a = q.i - 1; a >= 0; --a) {
-                double s = q.gv[(size_t)a];
-                for (i64 b = a + 1; b < q.i; ++b) {
-                    const double t = q.R[(size_t)(b * (m + 1) + a)] * y[b];
-                    s = s - t;
-                }
-                y[a] = s / q.R[(size_t)(a * (m + 1) + a)];
-            }
-            HIP_TRY(ctx, hipMemcpyAsync(w.yv + c * m, y, (size_t)q.i * 8, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(pd_combine_kernel, grid, block, 0, st, n, (const double *)w.v(c, 0), ld, q.i, (const double *)(w.yv + c * m), X + c * ldx, alx);
-            q.phase = PD_VERIFY;
-        }
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(st));  // (yh's uploads have been read)
-
-    i64 open = 0, first = -1;
-    for (i64 c = 0; c < k; ++c) {
-        const PdCol &q = col[(size_t)c];
-        cycles[c] = q.cycles, defect[c] = q.defect, reason[c] = q.reason;
-        if (q.reason != OTMB_PERIODIC_CONVERGED && open++ == 0) first = c;
-    }
-    if (open > 0) {
-        static const char *const names[] = {"converged", "maxcycles", "step failed", "nonfinite"};
-        char msg[200];
-        snprintf(msg, sizeof msg, "periodic: %lld of %lld columns; the first is column %lld: %s after %lld cycles, defect %.3e", (long long)open, (long long)k,
-                 (long long)first + 1, names[reason[first] & 3], (long long)cycles[first], defect[first]);
-        std::string full = msg;
-        if (!step_msg.empty()) full += "; the step: " + step_msg;
-        return otmb_fail(ctx, OTMB_ERR_NOT_CONVERGED, full.c_str());
-    }
-    return OTMB_OK;
+    if ((rc = r.prepare()) || (rc = r.source_norms(items)) || (rc = r.first_call(items))) return rc;
+    for (bool more = true; more;)
+        if ((rc = r.round(more))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (yh's uploads have been read)
+    return r.report(cycles, defect, reason);
 }
 
 int32_t otmb_op_periodic(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t ncycle, int64_t first_slot,

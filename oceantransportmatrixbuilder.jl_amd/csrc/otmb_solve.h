@@ -1,5 +1,6 @@
-// otmb_solve.h -- what the solver (otmb_solve.hip), its line preconditioner (otmb_solve_lines.hip) and the step (otmb_step.hip) share: a
-// column's record and state, the register block of right-hand sides, the preconditioner's record and the host entry points around it.
+// otmb_solve.h -- what the solver (otmb_solve.hip), its line preconditioner (otmb_solve_lines.hip), the step (otmb_step.hip) and the periodic
+// state (otmb_periodic.hip) share: a column's record and state, the register block of right-hand sides, the preconditioner's record, the
+// host entry points around it, the step's argument checks and the report of columns that did not converge.
 #pragma once
 #include "otmb_op.h"
 
@@ -39,7 +40,16 @@ void ln_sweep(otmb_op *op, const SvCol *cs, i64 k, const SvPrec &p, const double
 int32_t sv_prec_prepare(otmb_op *op, int adjoint, int32_t precond, const double *d, double sigma, const SvPrec &p);
 int32_t sv_solve(otmb_op *op, int adjoint, i64 k, const SvPrec &p, const double *B, i64 ldb, double *X, i64 ldx, int use_x0, double rtol, i64 maxiter,
                  int64_t *iters, double *relres, int32_t *reason, int32_t precond);
+// sv_step_complaint: the first complaint among rtol, maxiter, dt, theta, the count of steps (count_ok; the caller's text) and first_slot, in
+//                  that order, or null: what otmb_op_step and otmb_op_periodic ask of the arguments they share.
+// sv_report_open:  the end of a call that reports per column: OTMB_OK when every reason is 0 (converged); otherwise OTMB_ERR_NOT_CONVERGED with
+//                  fmt filled from the open columns' number, k, the first of them (1-based), names[its reason], count[it] and value[it],
+//                  and `tail` behind it.
 int32_t sv_check_step(otmb_op *op, int32_t precond, int64_t k, const double *S, int64_t lds, double *X, int64_t ldx, const char *more);
+const char *sv_step_complaint(const otmb_op *op, double rtol, int64_t maxiter, double dt, double theta, bool count_ok, const char *count_text,
+                              int64_t first_slot);
+int32_t sv_report_open(otmb_ctx *ctx, const char *fmt, const char *const *names, i64 k, const int32_t *reason, const int64_t *count, const double *value,
+                       const std::string &tail = std::string());
 
 // the report of an empty system (n = 0): every entry converged at once
 static inline int32_t sv_report_empty(i64 entries, int64_t *iters, double *relres, int32_t *reason) {

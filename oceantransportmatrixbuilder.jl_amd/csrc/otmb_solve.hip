@@ -23,10 +23,11 @@
 // (-ffp-contract=off).
 //
 // Every reduction is deterministic: the grid of a kernel depends on n alone, a workgroup sums with a fixed tree (xor shuffles inside a
-// wave, the four waves in order), writes ONE partial per column and quantity, and one workgroup per column (sv_scalar_kernel) folds the
-// partials -- lane t takes t, t + 256, ... in index order, then the same tree -- and computes α, β, ω, ρ and the column's state in device
-// memory, where the next kernel reads them.  No floating-point atomics.  A column's arithmetic never sees another column: column c of a
-// k-column solve has the bits of that column solved alone.
+// wave, the four waves in order: otmb_op_sum.h, the one copy, which the periodic state's kernels use as well), writes ONE partial per
+// column and quantity, and one workgroup per column (sv_scalar_kernel) folds the partials -- lane t takes t, t + 256, ... in index
+// order, then the same tree -- and computes α, β, ω, ρ and the column's state in device memory, where the next kernel reads them.  No
+// floating-point atomics.  A column's arithmetic never sees another column: column c of a k-column solve has the bits of that column
+// solved alone.
 //
 // The host enqueues SV_POLL iterations (plain stream launches), then reads the k column records; it stops when every column has.
 // A column stops with: converged (true residual checked) | maxiter | breakdown (r̂·v = 0, t·t = 0, ω = 0) | nonfinite (any scalar).
@@ -42,39 +43,14 @@
 #include <cmath>
 
 #include "otmb_op_fold.h"
+#include "otmb_op_sum.h"
 #include "otmb_solve.h"
 
 #define SV_POLL 16  // iterations enqueued between two reads of the column records
 
 enum { SV_S_INIT = 0, SV_S_VERIFY, SV_S_ALPHA, SV_S_OMEGA, SV_S_RHO };
 
-// ---- sums --------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double sv_wave_sum(double x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x = x + __shfl_xor(x, d);
-    return x;
-}
-// 256 threads, NV values each: thread 0 gets the sums (waves in order).  red: 4 * NV doubles of LDS.
-template <int NV>
-__device__ __forceinline__ void sv_block_sum(double (&x)[NV], double *red) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < NV; ++q) {
-        const double s = sv_wave_sum(x[q]);
-        if (lane == 0) red[w * NV + q] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < NV; ++q) x[q] = ((red[q] + red[NV + q]) + red[2 * NV + q]) + red[3 * NV + q];
-    }
-}
-// a workgroup's sums q[0..NV) to its place in the partials: quantity j of the launch at part[j * np + workgroup]
-template <int NV>
-__device__ __forceinline__ void sv_put(double *__restrict__ part, i64 np, const double (&q)[NV]) {
-#pragma unroll
-    for (int j = 0; j < NV; ++j) part[(i64)j * np + blockIdx.x] = q[j];
-}
+// ---- sums: the workgroup's tree and its place in the partials are otmb_op_sum.h's (op_wave_sum, op_block_sum, op_put) ------------------------
 template <int KB>
 __device__ __forceinline__ bool sv_any(const SvCol *__restrict__ cs, int want) {
     bool any = false;
@@ -109,7 +85,7 @@ __global__ __launch_bounds__(256) void sv_bnorm_kernel(i64 n, const double *__re
         const double b = i < n ? B[i + c * ldb] : 0.0;
         q[c] = b * b;
     }
-    sv_block_sum<KB>(q, red);
+    op_block_sum<KB>(q, red);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int c = 0; c < KB; ++c) part[(i64)(2 * c) * np + blockIdx.x] = q[c];
@@ -198,8 +174,8 @@ __global__ __launch_bounds__(256) void sv_rows_kernel(const SvCol *__restrict__ 
     }
     double q[2 * KB];
     sv_finish<KB, MODE>(cs, want, has, len >= 0, i, y, U, ldu, W, ldw, q);
-    sv_block_sum<2 * KB>(q, red);
-    if (threadIdx.x == 0) sv_put<2 * KB>(part, np, q);
+    op_block_sum<2 * KB>(q, red);
+    if (threadIdx.x == 0) op_put<2 * KB>(part, np, q);
 }
 
 // one workgroup per long row, lane c folds column c; runs BEFORE sv_rows_kernel, which sums its value
@@ -251,8 +227,8 @@ __global__ __launch_bounds__(64) void sv_cols_kernel(const SvCol *__restrict__ c
     double q[2 * KB];
     sv_finish<KB, MODE>(cs, want, has, true, colm, y, U, ldu, W, ldw, q);
 #pragma unroll
-    for (int j = 0; j < 2 * KB; ++j) q[j] = sv_wave_sum(q[j]);
-    if (lane == 0) sv_put<2 * KB>(part, np, q);
+    for (int j = 0; j < 2 * KB; ++j) q[j] = op_wave_sum(q[j]);
+    if (lane == 0) op_put<2 * KB>(part, np, q);
 }
 
 // ---- kernel 3: s = r - α·v, ŝ = s ./ diag, ‖s‖² ------------------------------------------------------------------------------------
@@ -276,8 +252,8 @@ __global__ __launch_bounds__(256) void sv_s_kernel(const SvCol *__restrict__ cs,
         if (!LINES) sh_[e] = sn / dg;
         q[c] = sn * sn;
     }
-    sv_block_sum<KB>(q, red);
-    if (threadIdx.x == 0) sv_put<KB>(part, np, q);
+    op_block_sum<KB>(q, red);
+    if (threadIdx.x == 0) op_put<KB>(part, np, q);
 }
 
 // ---- kernel 5: x = (x + α·p̂) + ω·ŝ, r = s - ω·t, partials of r̂·r and ‖r‖² --------------------------------------------------------
@@ -306,8 +282,8 @@ __global__ __launch_bounds__(256) void sv_x_kernel(const SvCol *__restrict__ cs,
         q[2 * c] = rh[e] * rn;
         q[2 * c + 1] = rn * rn;
     }
-    sv_block_sum<2 * KB>(q, red);
-    if (threadIdx.x == 0) sv_put<2 * KB>(part, np, q);
+    op_block_sum<2 * KB>(q, red);
+    if (threadIdx.x == 0) op_put<2 * KB>(part, np, q);
 }
 
 // ---- the scalars: workgroup c folds column c's partials and advances its record --------------------------------------------------
@@ -330,7 +306,7 @@ __global__ __launch_bounds__(256) void sv_scalar_kernel(SvCol *__restrict__ cs, 
     }
     if (step == SV_S_OMEGA)
         for (i64 j = threadIdx.x; j < nbs; j += 256) f[2] = f[2] + p2[j];
-    sv_block_sum<3>(f, red);
+    op_block_sum<3>(f, red);
     if (threadIdx.x != 0) return;
     const double bn = s.bnorm;
     switch (step) {
@@ -531,8 +507,29 @@ static int32_t sv_check(otmb_op *op, int32_t precond, int64_t k, const double *B
 int32_t sv_check_step(otmb_op *op, int32_t precond, int64_t k, const double *S, int64_t lds, double *X, int64_t ldx, const char *more) {
     return sv_check_system(op, precond, "step", "tracers", 'S', 'X', k, S ? S : X, S ? lds : ldx, X, ldx, more);
 }
+const char *sv_step_complaint(const otmb_op *op, double rtol, int64_t maxiter, double dt, double theta, bool count_ok, const char *count_text,
+                              int64_t first_slot) {
+    return !(rtol > 0.0)                                           ? "rtol must be > 0"
+           : maxiter < 0                                           ? "maxiter must be >= 0"
+           : !(dt > 0.0) || !std::isfinite(dt)                     ? "dt must be > 0 and finite"
+           : !(theta > 0.0 && theta <= 1.0)                        ? "theta must be in (0, 1]"
+           : !count_ok                                             ? count_text
+           : first_slot < 0 || first_slot >= (i64)op->slots.size() ? "first_slot is not a slot of the operator (otmb_op_set_slots)"
+                                                                   : nullptr;
+}
 static int32_t sv_check_apply(otmb_op *op, int32_t precond, int64_t k, const double *Y, int64_t ldy, double *Z, int64_t ldz) {
     return sv_check_system(op, precond, "precond", "columns", 'Y', 'Z', k, Y, ldy, Z, ldz, nullptr);
+}
+
+int32_t sv_report_open(otmb_ctx *ctx, const char *fmt, const char *const *names, i64 k, const int32_t *reason, const int64_t *count, const double *value,
+                       const std::string &tail) {
+    i64 open = 0, first = -1;
+    for (i64 c = 0; c < k; ++c)
+        if (reason[c] != 0 && open++ == 0) first = c;
+    if (open == 0) return OTMB_OK;
+    char msg[200];
+    snprintf(msg, sizeof msg, fmt, (long long)open, (long long)k, (long long)first + 1, names[reason[first] & 3], (long long)count[first], value[first]);
+    return otmb_fail(ctx, OTMB_ERR_NOT_CONVERGED, (msg + tail).c_str());
 }
 
 // The solve proper, behind otmb_op_solve_pc_dev and the step: w.pc is a prepared preconditioner (for this adjoint, precond, d, σ and the
@@ -599,21 +596,14 @@ static int32_t sv_iterate(otmb_op *op, const SvWork &w, int adjoint, i64 k, cons
     }
     if (run < 0) return otmb_fail(ctx, OTMB_ERR_HIP, "solve: reading the column records");
     if (run == 1) return otmb_fail(ctx, OTMB_ERR_HIP, "solve: a column was still running after maxiter iterations");  // (cannot happen: sv_scalar_kernel stops it)
-    i64 open = 0, first = -1;
     for (i64 c = 0; c < k; ++c) {
         iters[c] = h[(size_t)c].iters;
         relres[c] = h[(size_t)c].relres;
         reason[c] = h[(size_t)c].reason;
-        if (reason[c] != OTMB_SOLVE_CONVERGED && open++ == 0) first = c;
     }
-    if (open > 0) {
-        static const char *const names[] = {"converged", "maxiter", "breakdown", "nonfinite"};
-        char msg[160];
-        snprintf(msg, sizeof msg, "%lld of %lld columns; the first is column %lld: %s after %lld iterations, relative residual %.3e", (long long)open,
-                 (long long)k, (long long)first + 1, names[reason[first] & 3], (long long)iters[first], relres[first]);
-        return otmb_fail(ctx, OTMB_ERR_NOT_CONVERGED, msg);
-    }
-    return OTMB_OK;
+    static const char *const names[] = {"converged", "maxiter", "breakdown", "nonfinite"};
+    return sv_report_open(ctx, "%lld of %lld columns; the first is column %lld: %s after %lld iterations, relative residual %.3e", names, k, reason, iters,
+                          relres);
 }
 
 // The solve with a preconditioner prepared elsewhere (sv_prec_prepare): the step's, which keeps one per slot

@@ -144,14 +144,9 @@ static void st_rhs(otmb_op *op, int adjoint, i64 k, const StLine &q, const doubl
 static int32_t st_check(otmb_op *op, int64_t k, double dt, double theta, int64_t nsteps, int64_t first_slot, const double *S, int64_t lds, double *X,
                         int64_t ldx, double rtol, int64_t maxiter, int32_t precond, const int64_t *steps_done, const int64_t *iters, const double *relres,
                         const int32_t *reason) {
-    const char *more = !steps_done || (nsteps > 0 && (!iters || !relres || !reason)) ? "null argument"
-                       : !(rtol > 0.0)                                             ? "rtol must be > 0"
-                       : maxiter < 0                                               ? "maxiter must be >= 0"
-                       : !(dt > 0.0) || !std::isfinite(dt)                         ? "dt must be > 0 and finite"
-                       : !(theta > 0.0 && theta <= 1.0)                            ? "theta must be in (0, 1]"
-                       : nsteps < 0                                                ? "nsteps must be >= 0"
-                       : first_slot < 0 || first_slot >= (i64)op->slots.size()     ? "first_slot is not a slot of the operator (otmb_op_set_slots)"
-                                                                                   : nullptr;
+    const char *more = !steps_done || (nsteps > 0 && (!iters || !relres || !reason))
+                           ? "null argument"
+                           : sv_step_complaint(op, rtol, maxiter, dt, theta, nsteps >= 0, "nsteps must be >= 0", first_slot);
     return sv_check_step(op, precond, k, S, lds, X, ldx, more);
 }
 

@@ -21,6 +21,21 @@ REASONS = ("converged", "maxcycles", "step_failed", "nonfinite")
 PD_ROWS = 2048  # csrc/otmb_periodic.hip
 
 
+def givens_column(h, hn, cs, sn, gv, i):
+    """Column i of the Hessenberg matrix -- h = H(0..i, i), hn = H(i + 1, i) = ‖w‖ -- becomes column i of the triangle, in place: the old
+    rotations, then the one that clears hn (cs[i], sn[i]; nothing to clear: the identity), applied to the rotated right-hand side gv as
+    well.  GmresLsq::push of csrc/otmb_gmres.h in its order; tests/test_gmres_host.py compares the two bit for bit."""
+    for j in range(i):
+        t = cs[j] * h[j] + sn[j] * h[j + 1]
+        h[j + 1] = cs[j] * h[j + 1] - sn[j] * h[j]
+        h[j] = t
+    rr = float(np.hypot(h[i], hn))
+    cs[i], sn[i] = (h[i] / rr, hn / rr) if rr > 0 else (1.0, 0.0)
+    h[i] = rr
+    gv[i + 1] = -(sn[i] * gv[i])
+    gv[i] = cs[i] * gv[i]
+
+
 def periodic_column(F, Phi, n, *, x0=None, ptol=1e-8, restart=30, maxcycles=1000, source_is_zero=False):
     """One column.  F(x) -> F(x) or None (an inner step did not converge), Phi(v) likewise.
     -> (x, dict(cycles, defect, reason, history)): history = the explicit defects in order."""
@@ -81,16 +96,8 @@ def periodic_column(F, Phi, n, *, x0=None, ptol=1e-8, restart=30, maxcycles=1000
             if not (np.isfinite(h).all() and np.isfinite(hn)):
                 info["reason"] = "nonfinite"
                 return x, info
-            for j in range(i):
-                t = cs[j] * h[j] + sn[j] * h[j + 1]
-                h[j + 1] = cs[j] * h[j + 1] - sn[j] * h[j]
-                h[j] = t
-            rr = float(np.hypot(h[i], hn))
-            cs[i], sn[i] = (h[i] / rr, hn / rr) if rr > 0 else (1.0, 0.0)
-            h[i] = rr
+            givens_column(h, hn, cs, sn, gv, i)
             Rm[:i + 1, i] = h
-            gv[i + 1] = -(sn[i] * gv[i])
-            gv[i] = cs[i] * gv[i]
             i += 1
             if abs(gv[i]) <= ptol * gnorm or i == m or hn == 0.0 or info["cycles"] + 1 >= maxcycles:
                 break
@@ -215,7 +222,7 @@ def _lanes(prod):
 
 
 def _workgroup(acc):
-    """pd_block_sum: xor shuffles inside each wave of 64, then the four waves in order.  (workgroups, 256) -> (workgroups,)"""
+    """op_block_sum (csrc/otmb_op_sum.h): xor shuffles inside each wave of 64, then the four waves in order.  (workgroups, 256) -> (workgroups,)"""
     x = acc.reshape(-1, 4, 64)
     lane = np.arange(64)
     for dist in (32, 16, 8, 4, 2, 1):

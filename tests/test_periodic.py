@@ -168,6 +168,14 @@ def test_refusals_leave_x_the_selection_and_the_operator_as_they_were(small):
         rc, _, cyc, dft, why = _periodic_c(D, X, N, 2, **dict(dict(S=S, lds=N, use_x0=1), **kw))
         assert rc == 11, kw
         assert np.array_equal(X, X0) and (cyc == -7).all() and (dft == SENTINEL).all() and (why == -7).all() and D.slots == (3, 1), kw
+    # two bad arguments at once: the complaint is the first in the checks' order
+    slot_text = "first_slot is not a slot of the operator (otmb_op_set_slots)"
+    for kw, first in ((dict(rtol=0.0, dt=0.0), "rtol must be > 0"), (dict(theta=0.0, first_slot=99), "theta must be in (0, 1]"),
+                      (dict(ncycle=0, first_slot=99), "ncycle must be >= 1"), (dict(first_slot=99, ptol=0.0), slot_text)):
+        X = X0.copy(order="F")
+        assert _periodic_c(D, X, N, 2, **dict(dict(S=S, lds=N, use_x0=1), **kw))[0] == 11, kw
+        assert capi.lib().otmb_last_error(D.ctx.handle).decode() == f"{capi.lib().otmb_status_string(11).decode()}: {first}", kw
+        assert np.array_equal(X, X0) and D.slots == (3, 1), kw
     X = X0.copy(order="F")
     assert _periodic_c(D, X, N - 1, 2, S=S, lds=N)[0] == 11 and _periodic_c(D, X, N, 0, S=S, lds=N)[0] == 11 and _periodic_c(D, None, N, 2, S=S, lds=N)[0] == 11
     assert capi.lib().otmb_op_periodic(D.handle, 0, 2, None, 1.0, 1.0, 3, 0, S.ctypes.data, N, X.ctypes.data, N, 0, RTOL, 10, 0, PTOL, 5, 10, None, None,
@@ -196,6 +204,8 @@ def test_refusals_leave_x_the_selection_and_the_operator_as_they_were(small):
 def test_maxcycles_is_a_reported_answer(oracle):
     """tiny_tripolar, maxcycles = 2 (and 6): OTMB_ERR_NOT_CONVERGED, every column MAXCYCLES, cycles <= maxcycles, and defect is what one
     further step cycle from the returned X measures (to the rounding of two orders of one sum of N squares)."""
+    from otmb_amd import capi
+
     T, N, nsurf, nxt = LR.grid(oracle, "tiny_tripolar")
     d = R.shift("age", N, nsurf)[0]
     S = _start(N, 2, 131)
@@ -206,6 +216,10 @@ def test_maxcycles_is_a_reported_answer(oracle):
             X, info = D.periodic(S, ncycle=12, ptol=PTOL, restart=30, maxcycles=maxcycles, **kw)
             print("maxcycles", maxcycles, info)
             assert info.status == 19 and info.reason == ("maxcycles", "maxcycles") and (info.cycles <= maxcycles).all() and not info.converged.any()
+            if maxcycles == 2:
+                msg = capi.lib().otmb_last_error(D.ctx.handle).decode()
+                assert msg == (f"{capi.lib().otmb_status_string(19).decode()}: periodic: 2 of 2 columns; the first is column 1: maxcycles after "
+                               f"{int(info.cycles[0])} cycles, defect {info.defect[0]:.3e}"), msg
             FX, _ = D.step(X, nsteps=12, source=S, **kw)
             measured = np.linalg.norm(FX - X, axis=0) / np.linalg.norm(G, axis=0)
             assert np.allclose(info.defect, measured, rtol=N * 2.0 ** -52, atol=0.0), (info.defect, measured)
@@ -228,6 +242,7 @@ def test_a_nan_source_column_stops_alone(small):
     print(info, msg)
     assert info.status == 19 and info.reason[0] == info.reason[2] == "converged" and info.reason[1] in ("step_failed", "nonfinite"), info
     assert "(step 0, slot 2)" in msg, msg
+    assert "; the step: " in msg and msg.split("; the step: ", 1)[1].endswith("(step 0, slot 2)"), msg
     assert not X[:, 1].any()  # (the start, zero, is what it keeps)
     clean, ic = D.periodic(S[:, [0, 2]], **kw)
     assert ic.converged.all()

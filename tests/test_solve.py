@@ -211,7 +211,10 @@ def test_honest_failures(oracle):
         assert info.status == capi.NOT_CONVERGED == 19 and capi.STATUS_NAMES[19] == "NOT_CONVERGED"
         assert info.reason == ("maxiter",) * 3 and (info.iterations == 3).all() and not info.converged.any()
         assert np.isfinite(X).all() and np.isfinite(info.relres).all()
-        assert capi.lib().otmb_last_error(D.ctx.handle).decode().startswith("solve: not converged")
+        msg = capi.lib().otmb_last_error(D.ctx.handle).decode()
+        assert msg.startswith("solve: not converged")
+        assert msg == (f"{capi.lib().otmb_status_string(capi.NOT_CONVERGED).decode()}: 3 of 3 columns; the first is column 1: maxiter after "
+                       f"{int(info.iterations[0])} iterations, relative residual {info.relres[0]:.3e}"), msg
         X, info = D.solve(B, d=d, rtol=RTOL, maxiter=0)
         assert info.reason == ("maxiter",) * 3 and (info.iterations == 0).all() and not X.any()
         # B = 0: X = 0 in zero iterations, whatever the start

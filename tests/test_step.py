@@ -257,6 +257,13 @@ def test_refusals_leave_x_and_the_operator_unchanged(small):
         rc, done, it, rr, why = _step_c(D, X, N, 2, **kw)
         assert rc == 11, kw
         assert np.array_equal(X, X0) and (it == -7).all() and D.slots == (3, 0), kw
+    # two bad arguments at once: the complaint is the first in the checks' order
+    for kw, first in ((dict(rtol=0.0, dt=0.0), "rtol must be > 0"), (dict(theta=0.0, first_slot=99), "theta must be in (0, 1]"),
+                      (dict(nsteps=-1, first_slot=99), "nsteps must be >= 0")):
+        X = X0.copy(order="F")
+        assert _step_c(D, X, N, 2, **kw)[0] == 11, kw
+        assert capi.lib().otmb_last_error(D.ctx.handle).decode() == f"{capi.lib().otmb_status_string(11).decode()}: {first}", kw
+        assert np.array_equal(X, X0) and D.slots == (3, 0), kw
     X = X0.copy(order="F")
     assert _step_c(D, X, N - 1, 2)[0] == 11 and _step_c(D, X, N, 0)[0] == 11 and _step_c(D, None, N, 2)[0] == 11
     assert capi.lib().otmb_op_step(None, 0, 2, None, 1.0, 1.0, 1, 0, None, 0, X.ctypes.data, N, RTOL, 10, 0, None, None, None, None) == 11
