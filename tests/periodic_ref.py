@@ -11,7 +11,9 @@ F(x) = step(x, nsteps = ncycle, first_slot, source), by restarted GMRES on the c
 `cycles` counts the cycle calls (step calls) a column takes part in; with a start, F(x) and g come from ONE call of two columns.  The cycle
 itself is a pair of callables (cycle_maps: tests/step_ref.py's step_ref, the restated step; dense_cycle: numpy's dense solves of the same
 systems, which is what the tests afford for whole convergence histories).  device_dots / device_update restate the ORDER of the device's
-sums (a lane's rows, the workgroup's tree, the fold over workgroups): the host program of tests/test_periodic_host.py gives their bits."""
+sums (a lane's rows, the workgroup's tree, the fold over workgroups): the host program of tests/test_periodic_host.py gives their bits.
+With order="device" the whole iteration runs in that order, and over the device's own step() as the cycle it has otmb_op_periodic's bits
+(tests/test_periodic_rows.py)."""
 import numpy as np
 
 import solve_ref as R
@@ -36,9 +38,29 @@ def givens_column(h, hn, cs, sn, gv, i):
     gv[i] = cs[i] * gv[i]
 
 
-def periodic_column(F, Phi, n, *, x0=None, ptol=1e-8, restart=30, maxcycles=1000, source_is_zero=False):
+def back_substitution(Rm, gv, i):
+    """y (i entries) from the triangle Rm[:i, :i] and the rotated right-hand side gv, term by term in GmresLsq::solve's order: s = s - R·y[b],
+    b ascending, then the division (numpy's `@` adds in another order and does not agree).  tests/test_gmres_host.py compares the two bit
+    for bit."""
+    y = np.zeros(i)
+    for a in range(i - 1, -1, -1):
+        s = gv[a]
+        for b in range(a + 1, i):
+            t = Rm[a, b] * y[b]
+            s = s - t
+        y[a] = s / Rm[a, a]
+    return y
+
+
+def periodic_column(F, Phi, n, *, x0=None, ptol=1e-8, restart=30, maxcycles=1000, source_is_zero=False, order="numpy"):
     """One column.  F(x) -> F(x) or None (an inner step did not converge), Phi(v) likewise.
-    -> (x, dict(cycles, defect, reason, history)): history = the explicit defects in order."""
+    -> (x, dict(cycles, defect, reason, history)): history = the explicit defects in order.
+    order = "numpy": the sums are numpy's (`@`: the order belongs to the BLAS of the machine).  order = "device": every floating-point
+    operation in csrc/otmb_periodic.hip's and GmresLsq's order -- the sums by device_sum / device_dots, the updates by device_update, the
+    back substitution term by term, everything else elementwise -- so that on the same F and Phi the result has the library's bits."""
+    assert order in ("numpy", "device")
+    dev = order == "device"
+    sumsq = (lambda v: float(device_sum(v * v))) if dev else (lambda v: float(v @ v))
     x = np.zeros(n) if x0 is None else np.array(x0, dtype=np.float64)
     info = dict(cycles=0, defect=float("nan"), reason="converged", history=[])
     if source_is_zero:
@@ -54,7 +76,7 @@ def periodic_column(F, Phi, n, *, x0=None, ptol=1e-8, restart=30, maxcycles=1000
         info["reason"] = "step_failed"
         return x, info
     info["cycles"] = 1
-    gnorm = float(np.sqrt(g @ g))
+    gnorm = float(np.sqrt(sumsq(g)))
     if gnorm == 0.0:
         info["defect"] = 0.0
         return np.zeros(n), info
@@ -64,7 +86,7 @@ def periodic_column(F, Phi, n, *, x0=None, ptol=1e-8, restart=30, maxcycles=1000
     r = Fx - x
     m = int(restart)
     while True:
-        beta = float(np.sqrt(r @ r))
+        beta = float(np.sqrt(sumsq(r)))
         info["defect"] = beta / gnorm
         info["history"].append(info["defect"])
         if not np.isfinite(beta):
@@ -87,13 +109,21 @@ def periodic_column(F, Phi, n, *, x0=None, ptol=1e-8, restart=30, maxcycles=1000
                 return x, info
             info["cycles"] += 1
             w = V[i] - pv
-            h1 = V[:i + 1] @ w
-            w = w - h1 @ V[:i + 1]
-            h2 = V[:i + 1] @ w
-            w = w - h2 @ V[:i + 1]
-            hn = float(np.sqrt(w @ w))
+            if dev:  # CGS2 as the kernels run it; ‖w‖² of the first pass is read for finiteness only (GmresLsq::push)
+                h1, n1 = device_dots(V[:i + 1], w)
+                w = device_update(V[:i + 1], h1, w)
+                h2, _ = device_dots(V[:i + 1], w)
+                w = device_update(V[:i + 1], h2, w)
+                n2 = sumsq(w)
+            else:
+                h1 = V[:i + 1] @ w
+                w = w - h1 @ V[:i + 1]
+                h2 = V[:i + 1] @ w
+                w = w - h2 @ V[:i + 1]
+                n1, n2 = 0.0, float(w @ w)
+            hn = float(np.sqrt(n2))
             h = h1 + h2
-            if not (np.isfinite(h).all() and np.isfinite(hn)):
+            if not (np.isfinite(h).all() and np.isfinite(n1) and np.isfinite(n2)):
                 info["reason"] = "nonfinite"
                 return x, info
             givens_column(h, hn, cs, sn, gv, i)
@@ -102,10 +132,13 @@ def periodic_column(F, Phi, n, *, x0=None, ptol=1e-8, restart=30, maxcycles=1000
             if abs(gv[i]) <= ptol * gnorm or i == m or hn == 0.0 or info["cycles"] + 1 >= maxcycles:
                 break
             V[i] = w / hn
-        y = np.zeros(i)
-        for a in range(i - 1, -1, -1):
-            y[a] = (gv[a] - Rm[a, a + 1:i] @ y[a + 1:]) / Rm[a, a]
-        for j in range(i):
+        if dev:
+            y = back_substitution(Rm, gv, i)
+        else:
+            y = np.zeros(i)
+            for a in range(i - 1, -1, -1):
+                y[a] = (gv[a] - Rm[a, a + 1:i] @ y[a + 1:]) / Rm[a, a]
+        for j in range(i):  # (pd_combine_kernel: j ascending, one product and one addition at a time)
             x = x + y[j] * V[j]
         Fx = F(x)
         if Fx is None:

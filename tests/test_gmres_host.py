@@ -2,7 +2,8 @@
 when csrc/otmb_periodic.hip accepts, restarts or stops a column), the header as it stands, driven by a stand-alone host program under
 AddressSanitizer and UBSan: after every push the rotation, the triangle's diagonal entry, the rotated right-hand side, the recursive
 residual and the y of the back substitution have the BITS of the restatement -- tests/periodic_ref.py's givens_column, which periodic_column
-itself calls, and the back substitution restated here term by term in C's order (numpy's `@` adds in another order and does not agree)."""
+itself calls, and its back_substitution, term by term in C's order (numpy's `@` adds in another order and does not agree), which
+periodic_column calls in its device order."""
 import os
 import re
 import shutil
@@ -92,13 +93,7 @@ def _restated(m, beta, cols):
             PR.givens_column(h, hn, cs, sn, gv, i)
             Rm[:i + 1, i] = h
             i += 1
-            y = np.zeros(i)
-            for a in range(i - 1, -1, -1):  # C's order: s = s - R·y[b], b ascending, then the division
-                s = gv[a]
-                for b in range(a + 1, i):
-                    t = Rm[a, b] * y[b]
-                    s = s - t
-                y[a] = s / Rm[a, a]
+            y = PR.back_substitution(Rm, gv, i)  # C's order: s = s - R·y[b], b ascending, then the division
             out.append(_bits([cs[i - 1], sn[i - 1], Rm[i - 1, i - 1], gv[i], np.abs(gv[i])]) + _bits(y))
     return out
 

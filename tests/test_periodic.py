@@ -1,7 +1,8 @@
 """The periodic state of the stepped cycle on the device (csrc/otmb_periodic.hip; otmb_op_periodic[_dev]): restarted GMRES on the cycle map.
 Every answer is judged by step() itself -- one more cycle from the returned state, ‖F(x) - x‖₂ <= ptol·‖g‖₂ -- and against the dense fixed
 point (I - Φ)⁻¹·g of tests/periodic_ref.py; a column of k has the bits of the column alone; refusals, maxcycles, a NaN column, padded device
-arrays and the assembler's route."""
+arrays and the assembler's route.  Every fixture here has n <= 429, one workgroup of the file's kernels (PD_ROWS = 2048 rows) and one row
+pair a lane: tests/test_periodic_rows.py runs the sizes above that, bit for bit against the restatement in the device's order."""
 import ctypes as C
 
 import numpy as np

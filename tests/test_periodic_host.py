@@ -1,9 +1,11 @@
-"""CPU: the dots and update loops of csrc/otmb_periodic.hip (pd_dots_lane, pd_update_lane with the pair loads and stores under them, and
-pd_fold_kernel), text as it stands, compiled as plain C++ and executed lane by lane by a stand-alone host program under AddressSanitizer and
+"""CPU: the lane code of csrc/otmb_periodic.hip that needs no barrier (pd_dots_lane, pd_update_lane with the pair loads and stores under them,
+pd_fold_kernel, pd_scale_kernel and pd_combine_kernel), text as it stands, compiled as plain C++ and executed lane by lane by a stand-alone host program under AddressSanitizer and
 UBSan, on arrays of exactly the sizes the library's layout gives them (an even leading dimension, 16-byte aligned columns, NaN in the padding
 row): every lane's accumulators, the folded sums and the updated vector have the bits of the restatement's order (tests/periodic_ref.py:
-_lanes, _fold, device_update), no load is misaligned and nothing outside the arrays is touched.  The workgroup's tree runs shuffles between
-barriers and cannot be run one lane at a time: the GPU tests (tests/test_periodic.py) cover it."""
+_lanes, _fold, device_update), the scaled vector those of w / s and the combined x those of the sequential x + Σ y_j·V_j, on an aligned x and
+on one whose base is 8 bytes off a 16-byte boundary (alx false); no load is misaligned and nothing outside the arrays is touched.  The
+workgroup's tree runs shuffles between barriers and cannot be run one lane at a time: the GPU tests (tests/test_periodic.py,
+tests/test_periodic_rows.py) cover it."""
 import os
 import re
 import shutil
@@ -37,9 +39,14 @@ template <int NB, bool NORM> static void dots(i64 n, i64 np, const double *V, i6
         for (int b = 0; b < NB + (NORM ? 1 : 0); ++b) printf("%a\n", acc[b]);
     });
 }
-// in: n, nj, np, nq; V (nj columns of ld = n rounded up to even), w (ld), h (nj), partials (nq x np)
+static double *exactly(i64 count) {  // count doubles on a 256-byte base and not one more: the sanitizer sees a step too far
+    void *p = nullptr;
+    if (posix_memalign(&p, 256, (size_t)count * 8)) abort();
+    return (double *)p;
+}
+// in: n, nj, np, nq; V (nj columns of ld = n rounded up to even), w (ld), h (nj), partials (nq x np), s, y (nj), x (ld)
 // out: per register block of the basis (4, 2, 1; the first with ‖w‖²) and lane its accumulators; the folded partials; the updated w (n) and
-//      the lanes' ‖w‖² accumulators
+//      the lanes' ‖w‖² accumulators; w / s (n); x + Σ y_j·V_j on the aligned x (n) and on the x one element into its buffer (n)
 int main(int, char **argv) {
     FILE *f = fopen(argv[1], "r");
     long long n, nj, np, nq;
@@ -50,6 +57,13 @@ int main(int, char **argv) {
     for (i64 i = 0; i < ld; ++i) if (fscanf(f, "%la", w + i) != 1) return 2;
     for (i64 i = 0; i < nj; ++i) if (fscanf(f, "%la", h + i) != 1) return 2;
     for (i64 i = 0; i < nq * np; ++i) if (fscanf(f, "%la", part + i) != 1) return 2;
+    double s, *y = columns(nj), *ws = exactly(ld), *xa = exactly(ld), *xbuf = exactly(n + 1), *xm = xbuf + 1;
+    if (fscanf(f, "%la", &s) != 1) return 2;
+    for (i64 i = 0; i < nj; ++i) if (fscanf(f, "%la", y + i) != 1) return 2;
+    for (i64 i = 0; i < ld; ++i) if (fscanf(f, "%la", xa + i) != 1) return 2;
+    for (i64 i = 0; i < ld; ++i) ws[i] = w[i];
+    xbuf[0] = 7.25;
+    for (i64 i = 0; i < n; ++i) xm[i] = xa[i];
     i64 j0 = 0;
     for (int nb : {4, 2, 1})  // op_blocks<PD_NB> over the basis
         for (; nj - j0 >= nb; j0 += nb) {
@@ -65,7 +79,17 @@ int main(int, char **argv) {
     for (i64 i = 0; i < n; ++i) printf("%a\n", w[i]);
     for (double a : acc) printf("%a\n", a);
     if (ld > n && w[n] == w[n]) return 3;  // the padding row was written
-    free(V), free(w), free(h), free(part), free(out);
+    launch(np, 256, [&] { pd_scale_kernel(n, ws, s); });
+    for (i64 i = 0; i < n; ++i) printf("%a\n", ws[i]);
+    if (ld > n && ws[n] == ws[n]) return 4;
+    launch(np, 256, [&] { pd_combine_kernel(n, V, ld, nj, y, xa, true); });
+    for (i64 i = 0; i < n; ++i) printf("%a\n", xa[i]);
+    if (ld > n && xa[n] == xa[n]) return 5;
+    if (((uintptr_t)xm & 15) != 8) return 6;  // (the case: an X that the 16-byte path must not take)
+    launch(np, 256, [&] { pd_combine_kernel(n, V, ld, nj, y, xm, false); });
+    for (i64 i = 0; i < n; ++i) printf("%a\n", xm[i]);
+    if (xbuf[0] != 7.25) return 7;  // the element in front was written
+    free(V), free(w), free(h), free(part), free(out), free(y), free(ws), free(xa), free(xbuf);
     return 0;
 }
 """
@@ -78,7 +102,7 @@ def program(tmp_path_factory):
     src = open(SRC, encoding="utf-8").read()
     rows = re.search(r"^#define PD_ROWS \d+", src, re.M).group(0) + "\n"
     assert int(rows.split()[-1]) == PR.PD_ROWS
-    code = "".join(_definition(src, name) for name in ("Pd2", "pd_load", "pd_store", "pd_row", "pd_dots_lane", "pd_fold_kernel", "pd_update_lane"))
+    code = "".join(_definition(src, name) for name in ("Pd2", "pd_load", "pd_store", "pd_row", "pd_dots_lane", "pd_fold_kernel", "pd_update_lane", "pd_combine_kernel", "pd_scale_kernel"))
     d = tmp_path_factory.mktemp("periodic_host")
     cpp, exe = str(d / "periodic_host.cpp"), str(d / "periodic_host")
     with open(cpp, "w", encoding="utf-8") as f:
@@ -95,10 +119,13 @@ def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
-@pytest.mark.parametrize("n", [1, 118, 2 * PR.PD_ROWS + 513])
+@pytest.mark.parametrize("n", [1, 118, 512, 513, PR.PD_ROWS, PR.PD_ROWS + 1, 2 * PR.PD_ROWS + 513])
 def test_dots_and_update_loops_as_host_code_have_the_bits_of_the_restatement(program, n):
-    """n = 1 (one row, no pair), 118 (even: no padding row, one workgroup, lanes without rows), 4609 (odd, three workgroups, the last one
-    partly filled, the last pair a single row beside the NaN padding); 7 basis vectors: register blocks 4 + 2 + 1."""
+    """n = 1 (one row, no pair), 118 (even: no padding row, one workgroup, lanes without rows), 512 (every lane one pair, none a second),
+    513 (lane 0 a second pair of a single row), 2048 (one workgroup exactly full), 2049 (a second workgroup of one row beside the NaN
+    padding), 4609 (odd, three workgroups, the last one partly filled, the last pair a single row beside the NaN padding); 7 basis vectors:
+    register blocks 4 + 2 + 1.  pd_scale_kernel and pd_combine_kernel (no barrier, as pd_fold_kernel has none) run as whole kernels: w / s,
+    and x + Σ y_j·V_j at alx true (an x of the library's layout) and false (an x one element into a buffer of n + 1)."""
     exe, path = program
     nj, nq = 7, 9
     nwg = (n + PR.PD_ROWS - 1) // PR.PD_ROWS
@@ -106,10 +133,11 @@ def test_dots_and_update_loops_as_host_code_have_the_bits_of_the_restatement(pro
     rng = np.random.default_rng(n)
     V, w, h = rng.standard_normal((nj, n)), rng.standard_normal(n), rng.standard_normal(nj)
     part = rng.standard_normal((nq, nwg))
-    Vp, wp = np.full((nj, ld), np.nan), np.full(ld, np.nan)  # the padding row must be neither read into a sum nor written
-    Vp[:, :n], wp[:n] = V, w
+    s, y, x = float(rng.uniform(0.5, 3.0)), rng.standard_normal(nj), rng.standard_normal(n)
+    Vp, wp, xp = np.full((nj, ld), np.nan), np.full(ld, np.nan), np.full(ld, np.nan)  # the padding row must be neither read into a sum nor written
+    Vp[:, :n], wp[:n], xp[:n] = V, w, x
     with open(path, "w") as f:
-        f.write(f"{n} {nj} {nwg} {nq}\n{_hex(Vp.T)}\n{_hex(wp)}\n{_hex(h)}\n{_hex(part.T)}\n")  # (_hex writes column-major: V_j contiguous)
+        f.write(f"{n} {nj} {nwg} {nq}\n{_hex(Vp.T)}\n{_hex(wp)}\n{_hex(h)}\n{_hex(part.T)}\n{_hex([s])}\n{_hex(y)}\n{_hex(xp)}\n")  # (_hex writes column-major: V_j contiguous)
     r = subprocess.run([exe, path], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, (r.returncode, r.stderr[-3000:])  # (a sanitizer report ends the program with a non-zero status)
     out = np.array([float.fromhex(x) for x in r.stdout.split()])
@@ -132,4 +160,14 @@ def test_dots_and_update_loops_as_host_code_have_the_bits_of_the_restatement(pro
     want = PR.device_update(V, h, w)
     assert np.array_equal(_bits(out[at:at + n]), _bits(want)), (n, "update")
     at += n
-    assert np.array_equal(_bits(out[at:].reshape(nwg, 256)), _bits(PR._lanes(want * want))), (n, "‖w‖² of the update")
+    assert np.array_equal(_bits(out[at:at + nwg * 256].reshape(nwg, 256)), _bits(PR._lanes(want * want))), (n, "‖w‖² of the update")
+    at += nwg * 256
+    assert np.array_equal(_bits(out[at:at + n]), _bits(w / s)), (n, "scale")
+    at += n
+    combined = x.copy()
+    for j in range(nj):  # periodic_column's x += y_j·V_j
+        combined = combined + y[j] * V[j]
+    assert np.array_equal(_bits(out[at:at + n]), _bits(combined)), (n, "combine, alx")
+    at += n
+    assert np.array_equal(_bits(out[at:at + n]), _bits(combined)), (n, "combine, 8 bytes off")
+    assert at + n == len(out)

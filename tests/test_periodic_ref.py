@@ -134,3 +134,95 @@ def test_the_device_order_of_a_sum_is_a_sum():
             assert abs(h[j] - V[j] @ w) <= 2 * n * R.EPS * (np.abs(V[j]) @ np.abs(w))
         assert abs(nrm - w @ w) <= 2 * n * R.EPS * (w @ w)
         assert np.allclose(PR.device_update(V, h, w), w - h @ V, rtol=0, atol=1e-12 * np.abs(w).max() * 10)
+
+
+@pytest.mark.parametrize("adjoint", [False, True])
+@pytest.mark.parametrize("ncycle", [3, 12])
+@pytest.mark.parametrize("theta", [1.0, 0.5])
+def test_the_device_order_reaches_the_same_fixed_point_in_the_same_cycles(oracle, theta, ncycle, adjoint):
+    """order="device" (every sum, update and back substitution in the order of csrc/otmb_periodic.hip and GmresLsq) on odd_nx_fold over the
+    dense cycle, GMRES(20), s = 1 and a random source: it converges, in the cycles of the default order, to an X inside the bound of
+    test_restarted_gmres_reaches_the_dense_fixed_point (the same ptol, the same ‖(I - Φ)⁻¹‖₂, the same formula)."""
+    DC, N, _, _ = dense(oracle, "odd_nx_fold", theta, ncycle, adjoint)
+    S = np.ones((N, 2))
+    S[:, 1] = np.random.default_rng(3).standard_normal(N)
+    xs, gnorm, ninv = DC.fixed_point(S)
+    F, Phi = DC.maps(S)
+    X0, info0 = PR.periodic_ref(F, Phi, S, ptol=PTOL, restart=20, maxcycles=2000)
+    X, info = PR.periodic_ref(F, Phi, S, ptol=PTOL, restart=20, maxcycles=2000, order="device")
+    print(theta, ncycle, adjoint, "cycles", info["cycles"].tolist(), "default order", info0["cycles"].tolist(), "defect", info["defect"].tolist())
+    assert info["converged"].all() and (info["defect"] <= PTOL).all()
+    assert np.array_equal(info["cycles"], info0["cycles"])
+    for c in range(2):
+        err = np.linalg.norm(X[:, c] - xs[:, c])
+        bound = ninv * (PTOL * gnorm[c] + 1e-12 * np.linalg.norm(xs[:, c]))
+        print("  column", c, "error", err, "bound", bound)
+        assert err <= bound
+        assert np.linalg.norm(DC.F(X[:, c], S[:, c]) - X[:, c]) <= PTOL * gnorm[c] * (1 + 1e-6)
+
+
+def test_the_device_order_keeps_the_bookkeeping(oracle):
+    """From the returned state one cycle and the same state and defect; a zero source costs nothing; maxcycles is never exceeded."""
+    DC, N, _, _ = dense(oracle, "odd_nx_fold", 1.0, 3, False)
+    S = np.ones((N, 1))
+    F, Phi = DC.maps(S)
+    X, info = PR.periodic_ref(F, Phi, S, ptol=1e-8, restart=5, order="device")
+    assert info["converged"].all() and len(info["history"][0]) > 2
+    X1, info1 = PR.periodic_ref(F, Phi, S, x0=X, ptol=1e-8, restart=5, order="device")
+    assert info1["cycles"].tolist() == [1] and info1["converged"].all() and np.array_equal(X1, X) and info1["defect"][0] == info["defect"][0]
+    Z, infoz = PR.periodic_ref(F, Phi, np.zeros((N, 1)), x0=X, ptol=1e-8, restart=5, order="device")
+    assert infoz["cycles"].tolist() == [0] and not Z.any() and infoz["defect"][0] == 0.0
+    for maxcycles in (0, 1, 2, 3, 4, 9):
+        _, im = PR.periodic_ref(F, Phi, S, ptol=1e-8, restart=5, maxcycles=maxcycles, order="device")
+        assert im["reason"] == ["maxcycles"] and im["cycles"][0] <= maxcycles
+    with pytest.raises(AssertionError):
+        PR.periodic_ref(F, Phi, S, order="blas")
+
+
+def _written_out_sum(p):
+    """Σ p as csrc/otmb_periodic.hip adds it, in three plain loops over Python floats: a lane's row pairs (pd_row, pd_dots_lane), the
+    workgroup's tree (op_block_sum of csrc/otmb_op_sum.h), the fold over the workgroups (pd_fold_kernel)."""
+    p = [float(v) for v in p]
+    n = len(p)
+    nwg = (n + PR.PD_ROWS - 1) // PR.PD_ROWS
+    parts = []
+    for wg in range(nwg):
+        acc = [0.0] * 256
+        for t in range(256):  # the lanes
+            for q in range(PR.PD_ROWS // 512):
+                i = 2 * (wg * (PR.PD_ROWS // 2) + t + 256 * q)
+                if i >= n:
+                    break
+                acc[t] = acc[t] + p[i]
+                if i + 1 < n:
+                    acc[t] = acc[t] + p[i + 1]
+        waves = []
+        for w in range(4):  # the tree: xor shuffles in a wave, every lane at once
+            x = acc[64 * w:64 * w + 64]
+            for dist in (32, 16, 8, 4, 2, 1):
+                x = [x[lane] + x[lane ^ dist] for lane in range(64)]
+            waves.append(x[0])
+        parts.append(((waves[0] + waves[1]) + waves[2]) + waves[3])
+    s = parts[0]
+    for b in range(1, nwg):  # the fold
+        s = s + parts[b]
+    return s, parts
+
+
+@pytest.mark.parametrize("n", [1, 513, 2048, 2049, 4609])
+def test_device_sum_is_the_sum_written_out(n):
+    """_lanes / _workgroup / _fold against the three loops, bit for bit, with several workgroups in play (n = 4609: three, the last partly
+    filled; 2049: the second holds one row), on terms of mixed sign and magnitude so that the order shows; and the order does show:
+    reversing the terms changes the bits."""
+    rng = np.random.default_rng(40 + n)
+    p = rng.standard_normal(n) * 10.0 ** rng.uniform(-6, 6, n)
+    want, parts = _written_out_sum(p)
+    assert len(parts) == (n + 2047) // 2048
+    got = PR.device_sum(p)
+    assert np.float64(got).view(np.uint64) == np.float64(want).view(np.uint64), (n, got, want)
+    assert np.array_equal(PR._workgroup(PR._lanes(p)).view(np.uint64), np.array(parts).view(np.uint64))
+    V = rng.standard_normal((2, n))
+    h, nrm = PR.device_dots(V, p)
+    assert [float(x) for x in h] == [_written_out_sum(V[j] * p)[0] for j in range(2)] and float(nrm) == _written_out_sum(p * p)[0]
+    if n == 4609:
+        assert PR.device_sum(p[::-1]) != got
