@@ -753,6 +753,17 @@ int32_t otmb_op_set_values_slot(otmb_op *op, int64_t slot, const double *nzval, 
 int32_t otmb_op_select_slot(otmb_op *op, int64_t slot);
 int32_t otmb_op_slots(const otmb_op *op, int64_t *nslots, int64_t *selected);
 
+/* ---- otmb_op_combine_slots[_dev]: slot dst = Σ_s w[s]·(slot s), on the device -- the annual mean of a year of monthly matrices without
+ *      downloading one of them.  w: HOST array of nslots weights (both variants); dst: a slot, which may be one of the sources.
+ * In bits: for every stored entry, the slots with w[s] != 0 in ascending s; acc = w[s]·v_s for the first of them, acc = acc + w[s]·v_s for
+ *      each of the rest (one multiplication, one addition, no FMA); all w[s] zero: +0.0.  Both value arrays of slot dst are written with the
+ *      same arithmetic, elementwise (the row layout's padding included, which no product reads); the other slots and the selection are not
+ *      touched.  otmb_op_mul*, otmb_op_solve* on slot dst afterwards have the bits of otmb_op_set_values_slot with that fold of the nzvals.
+ * A weight that is not finite, dst outside 0..nslots-1 or w == NULL: OTMB_ERR_INVALID_ARG before anything is written; the operator stays
+ *      usable.  otmb_op_combine_slots_dev enqueues on the context's stream; otmb_op_combine_slots waits for it.                          */
+int32_t otmb_op_combine_slots_dev(otmb_op *op, const double *w, int64_t dst);
+int32_t otmb_op_combine_slots(otmb_op *op, const double *w, int64_t dst);
+
 /* ---- θ-steps of ∂x/∂t + (diag(d) + A)·x = s over the slots: X (n x k, in and out) advances through nsteps steps of length dt, step t
  *      (0-based) with the matrix A of slot (first_slot + t) mod nslots (adjoint: Aᵀ).  S: the source, n x k with leading dimension lds, or NULL
  *      (zero); d: n values or NULL.  dt > 0 and finite, 0 < theta <= 1 (1: implicit Euler, 0.5: Crank-Nicolson), nsteps >= 0,
@@ -817,6 +828,40 @@ int32_t otmb_op_periodic_dev(otmb_op *op, int32_t adjoint, int64_t k, const doub
 int32_t otmb_op_periodic(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t ncycle, int64_t first_slot,
                          const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond,
                          double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason);
+
+/* ---- otmb_op_periodic_pc[_dev]: otmb_op_periodic[_dev] with a choice of preconditioner for the outer GMRES.  The arguments are
+ *      otmb_op_periodic's, then outer (otmb_outer) and msolve_iters (HOST array of k entries or NULL).  otmb_op_periodic[_dev] is this call
+ *      with OTMB_OUTER_NONE and NULL.
+ * OTMB_OUTER_NONE: the method stated above, bit for bit; msolve_iters, if given, is zero.
+ * OTMB_OUTER_MEAN (a contract; tests/periodic_pc_ref.py restates it): flexible GMRES, right-preconditioned by the cycle-mean operator.  With
+ *      P = ncycle·dt and M̄ = diag(d) + Ā, Ā the visit-weighted mean of the cycle's slots, one implicit-Euler step over the whole period gives
+ *      Φ ≈ (I + P·M̄)⁻¹, hence (I - Φ)⁻¹ ≈ I + (P·M̄)⁻¹: one solve with M̄ at σ = 0.
+ *      The mean values: otmb_op_combine_slots' fold with w[s] = count_s / ncycle (one double division), count_s the visits of slot s by the
+ *      steps first_slot .. first_slot + ncycle - 1, into a value set private to the operator, made once per call; the caller's slots and
+ *      the selected slot are untouched.  P = (double)ncycle * dt.  The mean's preconditioner (precond, σ = 0, the call's d and adjoint) is
+ *      factorised once per call before X is touched: a singular one is OTMB_ERR_SINGULAR_PRECONDITIONER with X not written.
+ *      Iteration i, per column:  q from (diag(d) + Ā)·q = V_i by otmb_op_solve_pc_dev's own path on the mean values (σ = 0, use_x0 = 0, the
+ *      call's rtol, maxiter, precond), for the columns that iterate together, gathered compactly as for the step;
+ *      Z_i = V_i + q / P (one division, one addition);  w = Z_i - Φ·Z_i (one step call without the source);  Gram-Schmidt twice against V, the
+ *      Hessenberg column, the rotations and V_{i+1} as above;  at a restart x += Σ_j y_j·Z_j, j ascending.  The restart, verify and stop
+ *      rules, cycles (a mean solve is not a cycle) and defect are as above: an answer is accepted on the explicit F(x) - x only.
+ *      A column whose mean solve does not converge stops alone with OTMB_PERIODIC_PRECOND_FAILED, keeps the state of its last explicit
+ *      F(x) - x, and the message carries the solver's report; the solve is repeated without it, as a step call is.
+ *      msolve_iters[c]: the BiCGStab iterations column c spent in mean solves (those of a solve repeated for another column's sake are not
+ *      counted twice).  Columns stay independent: X, cycles, defect and msolve_iters of column c of k have the bits of the column alone.
+ *      Workspace: (2·restart + 3)·n·k doubles (the Z block behind the V block) and the mean's values and preconditioner; only this mode
+ *      allocates them, and a failure is OTMB_ERR_ALLOC with X untouched.
+ * outer neither value: OTMB_ERR_INVALID_ARG before X is touched.                                                                          */
+typedef enum { OTMB_OUTER_NONE = 0, OTMB_OUTER_MEAN = 1 } otmb_outer;
+typedef enum { OTMB_PERIODIC_PRECOND_FAILED = 4 } otmb_periodic_pc_reason; /* continues otmb_periodic_reason */
+int32_t otmb_op_periodic_pc_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t ncycle, int64_t first_slot,
+                                const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond,
+                                double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer,
+                                int64_t *msolve_iters);
+int32_t otmb_op_periodic_pc(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t ncycle, int64_t first_slot,
+                            const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond,
+                            double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer,
+                            int64_t *msolve_iters);
 
 #ifdef __cplusplus
 }

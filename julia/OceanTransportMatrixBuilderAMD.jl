@@ -13,6 +13,8 @@
 #   DeviceOperator, setvalues!  T * x, T' * v, mul!(Y, T, X, α, β) on the GPU (test/local_full.jl:96-107; README: ∂x/∂t + T x = …)
 #   setslots!, step!, step      a year of monthly matrices resident as value slots, and θ-steps of the tracers through them on the GPU
 #   periodic!, periodic         the periodic (cyclo-stationary) state of that stepped cycle, by restarted GMRES on the cycle map
+#                               (outer = :mean: preconditioned by the cycle-mean operator)
+#   combineslots!               a weighted sum of slots into a slot, on the device (the annual mean of the months)
 #   solve!, solve               (σ·I + Diagonal(d) + T) \ B on the GPU: the `\` of the ideal-age problem (test/local_full.jl:151-188)
 #   bolus_GM_velocity           src/RediGM.jl:46-79 (unexported and experimental there, unexported here)
 #   makegridmetrics             src/gridcellgeometry.jl:265-311: the reference's own by default (its haversines are Julia's libm);
@@ -38,7 +40,7 @@ export DeviceOperator, setvalues!
 export solve!, solve
 export setlines!, verticallines, precondition!
 export setslots!, selectslot!, slots, step!   # (`step` extends Base.step for this module's operators: nothing to export)
-export periodic!, periodic
+export periodic!, periodic, combineslots!
 
 const LIBPATH = get(ENV, "OTMB_HIP_LIB", joinpath(@__DIR__, "..", "oceantransportmatrixbuilder.jl_amd", "lib", "libotmb_hip.so"))
 const lib = Ref{Ptr{Cvoid}}(C_NULL)
@@ -479,6 +481,20 @@ function selectslot!(D::DeviceOperator, slot::Integer)
     end
     return D
 end
+# `combineslots!(D, w, dst)`: slot dst = Σ_s w[s]·(slot s) on the device (otmb_op_combine_slots; include/otmb.h states the fold) -- the
+# annual mean of the months without downloading one.  w: one finite weight per slot (a zero weight leaves its slot out); dst may be a source.
+function combineslots!(D::DeviceOperator, w::Vector{Float64}, dst::Integer)
+    lock(CALL_LOCK) do
+        D.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        combine_slots_fn = sym(:otmb_op_combine_slots)
+        nslots = Ref{Int64}(0)
+        slots_fn = sym(:otmb_op_slots)
+        check(ccall(slots_fn, Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), D.handle, nslots, C_NULL))
+        length(w) == nslots[] || throw(DimensionMismatch("w has $(length(w)) weights, the operator $(nslots[]) slots"))
+        check(ccall(combine_slots_fn, Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64), D.handle, w, Int64(dst - 1)))
+    end
+    return D
+end
 function slots(D::DeviceOperator)
     n = Ref{Int64}(0)
     sel = Ref{Int64}(0)
@@ -530,8 +546,10 @@ const PERIODIC_REASONS = (:converged, :maxcycles, :step_failed, :nonfinite)   # 
 # (‖F(x) - x‖₂ / ‖F(0)‖₂), info.reason, info.converged.  A column that does not converge is REPORTED, not thrown (status 19).
 function periodic!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, source::StridedVecOrMat{Float64}; dt::Real,
                    ncycle::Integer, θ::Real = 1.0, firstslot::Integer = 1, d::Union{Nothing,Vector{Float64}} = nothing, x0::Bool = false,
-                   rtol::Real = 1e-10, maxiter::Integer = 10000, precond::Symbol = :jacobi, ptol::Real = 1e-8, restart::Integer = 30,
+                   rtol::Real = 1e-10, maxiter::Integer = 10000, precond::Symbol = :jacobi, outer::Symbol = :none, ptol::Real = 1e-8, restart::Integer = 30,
                    maxcycles::Integer = 1000)
+    outer === :none || return periodicpc!(X, D, source, outercode(outer); dt = dt, ncycle = ncycle, θ = θ, firstslot = firstslot, d = d, x0 = x0,
+                                          rtol = rtol, maxiter = maxiter, precond = precond, ptol = ptol, restart = restart, maxcycles = maxcycles)
     pc = precondcode(precond)
     adjoint = D isa AdjointDeviceOperator
     op = adjoint ? D.parent : D
@@ -549,7 +567,41 @@ function periodic!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointD
         rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which column stopped why
     end
     why = [PERIODIC_REASONS[r + 1] for r in reason]
-    return X, (cycles = cycles, defect = defect, reason = why, converged = why .== :converged)
+    return X, (cycles = cycles, defect = defect, reason = why, converged = why .== :converged, msolve_iters = zeros(Int64, k))
+end
+const PERIODIC_PC_REASONS = (PERIODIC_REASONS..., :precond_failed)   # ... continued by otmb_periodic_pc_reason
+const OUTERS = (:none, :mean)                                       # otmb_outer
+function outercode(outer::Symbol)
+    i = findfirst(==(outer), OUTERS)
+    i === nothing && throw(ArgumentError("outer must be one of $(OUTERS), not :$(outer)"))
+    return Int32(i - 1)
+end
+# periodic! with `outer = :mean` (otmb_op_periodic_pc; include/otmb.h states the method): the outer GMRES is flexible and right-preconditioned
+# by the cycle-mean operator -- fewer cycles, one solve with the mean matrix per iteration.  info.msolve_iters: the BiCGStab iterations a
+# column spent in those solves; info.reason may be :precond_failed (a mean solve did not converge).
+function periodicpc!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, source::StridedVecOrMat{Float64}, oc::Int32; dt::Real,
+                     ncycle::Integer, θ::Real, firstslot::Integer, d::Union{Nothing,Vector{Float64}}, x0::Bool, rtol::Real, maxiter::Integer,
+                     precond::Symbol, ptol::Real, restart::Integer, maxcycles::Integer)
+    pc = precondcode(precond)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    k, lds, ldx = systemdims(op, source, "source", X, "X", d)
+    cycles = zeros(Int64, k)
+    defect = zeros(Float64, k)
+    reason = zeros(Int32, k)
+    msolve = zeros(Int64, k)
+    lock(CALL_LOCK) do
+        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        periodic_pc_fn = sym(:otmb_op_periodic_pc)
+        rc = ccall(periodic_pc_fn, Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Float64, Float64, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                Int32, Float64, Int64, Int32, Float64, Int64, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, Int32, Ptr{Int64}),
+            op.handle, Int32(adjoint), k, d === nothing ? C_NULL : d, Float64(dt), Float64(θ), Int64(ncycle), Int64(firstslot - 1),
+            source, lds, X, ldx, Int32(x0), Float64(rtol), Int64(maxiter), pc, Float64(ptol), Int64(restart), Int64(maxcycles), cycles, defect, reason,
+            oc, msolve)
+        rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which column stopped why
+    end
+    why = [PERIODIC_PC_REASONS[r + 1] for r in reason]
+    return X, (cycles = cycles, defect = defect, reason = why, converged = why .== :converged, msolve_iters = msolve)
 end
 periodic(D::Union{DeviceOperator,AdjointDeviceOperator}, source::StridedVecOrMat{Float64}; kwargs...) = periodic!(zero(source), D, source; kwargs...)
 

@@ -844,17 +844,20 @@ def step_arrays(nsteps, k):
 class PeriodicInfo:
     """What otmb_op_periodic reports, one entry per column: cycles (the step calls the column took part in, the verifying ones included),
     defect (‖F(x) - x‖₂/‖g‖₂ of the column's last explicitly computed F(x) - x; NaN when none was), reason ("converged", "maxcycles",
-    "step_failed", "nonfinite") and converged; status is the call's own (0, or capi.NOT_CONVERGED when some column is not converged)."""
+    "step_failed", "nonfinite", and with outer="mean" "precond_failed") and converged; msolve_iters: the BiCGStab iterations the column spent in
+    mean solves (outer="mean"; otherwise zero); status is the call's own (0, or capi.NOT_CONVERGED when some column is not converged)."""
 
-    def __init__(self, status, cycles, defect, reason):
+    def __init__(self, status, cycles, defect, reason, msolve_iters=None):
         self.status = int(status)
         self.cycles = np.asarray(cycles, dtype=np.int64)
         self.defect = np.asarray(defect, dtype=np.float64)
-        self.reason = tuple(capi.PERIODIC_REASONS[int(r)] for r in reason)
+        self.reason = tuple(capi.PERIODIC_PC_REASONS[int(r)] for r in reason)
         self.converged = np.array([r == "converged" for r in self.reason], dtype=bool)
+        self.msolve_iters = np.zeros(len(self.cycles), dtype=np.int64) if msolve_iters is None else np.asarray(msolve_iters, dtype=np.int64)
 
     def __repr__(self):
-        return f"PeriodicInfo(status={self.status}, cycles={self.cycles.tolist()}, defect={self.defect.tolist()}, reason={self.reason})"
+        return (f"PeriodicInfo(status={self.status}, cycles={self.cycles.tolist()}, defect={self.defect.tolist()}, reason={self.reason}, "
+                f"msolve_iters={self.msolve_iters.tolist()})")
 
 
 def vertical_lines(indices):
@@ -883,7 +886,8 @@ class DeviceOperator:
     A: a SparseMatrixCSC (1-based).  The operator owns device copies of A: the arrays may change or go once the constructor returns.
     The same C calls as the Julia shim's DeviceOperator: otmb_op_create; mul! -> otmb_op_mul; setvalues! -> otmb_op_set_values; solve! ->
     otmb_op_solve_pc; setlines! -> otmb_op_set_lines; precondition! -> otmb_op_precond; setslots! / selectslot! / step! -> otmb_op_set_slots /
-    otmb_op_select_slot / otmb_op_step; periodic! -> otmb_op_periodic; the finalizer -> otmb_op_destroy."""
+    otmb_op_select_slot / otmb_op_step; periodic! -> otmb_op_periodic (outer = :mean: otmb_op_periodic_pc); combineslots! ->
+    otmb_op_combine_slots; the finalizer -> otmb_op_destroy."""
 
     def __init__(self, A, *, device=0):
         self._h = C.c_void_p()
@@ -952,6 +956,15 @@ class DeviceOperator:
         """mul, solve and precondition read slot `slot` from now on (otmb_op_select_slot: a pointer switch, no data moves)."""
         self._live()
         self.ctx.check(capi.lib().otmb_op_select_slot(self._h, int(slot)))
+
+    def combine_slots(self, weights, dst):
+        """Slot dst = Σ_s weights[s]·(slot s) on the device (otmb_op_combine_slots; include/otmb.h states the fold): the annual mean of a year
+        of months without downloading one.  weights: one finite value per slot (a zero weight leaves its slot out); dst may be a source."""
+        self._live()
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (self.slots[0],):
+            raise capi.OtmbError(11, f"DimensionMismatch: weights of {w.shape}, expected {(self.slots[0],)}")
+        self.ctx.check(capi.lib().otmb_op_combine_slots(self._h, w.ctypes.data, int(dst)))
 
     @property
     def slots(self):
@@ -1056,13 +1069,16 @@ class DeviceOperator:
             self.ctx.check(rc)
         return Xn, StepInfo(rc, done.value, nsteps, iters, relres, reason)
 
+    @capi.outer_keyword
     def periodic(self, source, *, dt, ncycle, theta=1.0, first_slot=0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi",
                  ptol=1e-8, restart=30, maxcycles=1000):
         """The periodic state of the stepped cycle: X with F(X) = X, F = step(..., nsteps=ncycle, first_slot=first_slot, source=source), by
         restarted GMRES(restart) on the cycle map (otmb_op_periodic; include/otmb.h states the method and what is deterministic).  source:
         1-D or 2-D (n x k); x0: None (start from zero) or an array of source's shape (not modified); the other arguments are step's.  Returns
         (X, info): X the state at the start of the cycle, with ‖F(X) - X‖₂ <= ptol·‖F(0)‖₂ per converged column, info a PeriodicInfo.  A
-        column that does not converge is REPORTED (info.reason), not raised; argument errors and a singular preconditioner raise OtmbError."""
+        column that does not converge is REPORTED (info.reason), not raised; argument errors and a singular preconditioner raise OtmbError.
+        outer="mean" (outer_keyword): the outer GMRES is preconditioned by the cycle-mean operator -- fewer cycles, one solve with the mean
+        matrix per iteration (info.msolve_iters)."""
         self._live()
         pc = capi.precond_code(precond)
         S = np.asarray(source)
@@ -1081,6 +1097,29 @@ class DeviceOperator:
         if rc != capi.NOT_CONVERGED:
             self.ctx.check(rc)
         return X, PeriodicInfo(rc, cycles, defect, reason)
+
+    def _periodic_pc(self, source, outer, *, dt, ncycle, theta=1.0, first_slot=0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False,
+                     precond="jacobi", ptol=1e-8, restart=30, maxcycles=1000):
+        """periodic with outer = an otmb_outer code: otmb_op_periodic_pc."""
+        self._live()
+        pc = capi.precond_code(precond)
+        S = np.asarray(source)
+        k, Sc, lds, dc = self._system_args(S, d)
+        X = np.zeros(S.shape, dtype=np.float64, order="F")
+        if x0 is not None:
+            if np.shape(x0) != S.shape:
+                raise capi.OtmbError(11, f"DimensionMismatch: x0 of {np.shape(x0)}, source of {S.shape}")
+            X[...] = x0
+        cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
+        msolve = np.zeros(k, dtype=np.int64)
+        lib = capi.lib()
+        rc = lib.otmb_op_periodic_pc(self._h, int(bool(adjoint)), k, None if dc is None else dc.ctypes.data, float(dt), float(theta), int(ncycle),
+                                     int(first_slot), Sc.ctypes.data, lds, X.ctypes.data, max(X.shape[0], 1), int(x0 is not None), float(rtol),
+                                     int(maxiter), pc, float(ptol), int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data,
+                                     reason.ctypes.data, int(outer), msolve.ctypes.data)
+        if rc != capi.NOT_CONVERGED:
+            self.ctx.check(rc)
+        return X, PeriodicInfo(rc, cycles, defect, reason, msolve)
 
     def __matmul__(self, x):
         return self.mul(x)

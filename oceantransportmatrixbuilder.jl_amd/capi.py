@@ -1,5 +1,6 @@
 """ctypes binding of include/otmb.h (libotmb_hip.so).  No fallback: a missing library raises."""
 import ctypes as C
+import functools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -18,6 +19,8 @@ NOT_CONVERGED = 19  # otmb_op_solve: an answer (the per-column info says which c
 SOLVE_REASONS = ("converged", "maxiter", "breakdown", "nonfinite")  # otmb_solve_reason
 PRECONDS = {"jacobi": 0, "lines": 1}  # otmb_precond
 PERIODIC_REASONS = ("converged", "maxcycles", "step_failed", "nonfinite")  # otmb_periodic_reason
+PERIODIC_PC_REASONS = PERIODIC_REASONS + ("precond_failed",)  # ... continued by otmb_periodic_pc_reason
+OUTERS = {"none": 0, "mean": 1}  # otmb_outer
 
 PHI_ORDER = ("east", "west", "north", "south", "top", "bottom")  # OTMB_EAST..OTMB_BOTTOM
 HDIRS = ("west", "east", "south", "north")  # OTMB_DIR_*
@@ -45,6 +48,25 @@ def precond_code(precond):
     if precond not in PRECONDS:
         raise OtmbError(11, f"invalid argument: precond must be one of {sorted(PRECONDS)}, not {precond!r}")
     return PRECONDS[precond]
+
+
+def outer_code(outer):
+    """otmb_outer of "none" / "mean"."""
+    if outer not in OUTERS:
+        raise OtmbError(11, f"invalid argument: outer must be one of {sorted(OUTERS)}, not {outer!r}")
+    return OUTERS[outer]
+
+
+def outer_keyword(plain):
+    """periodic(..., outer="none" | "mean") over a periodic method `plain` that makes the unpreconditioned call (otmb_op_periodic[_dev]):
+    "none" is that call as it stands; "mean" goes to the object's _periodic_pc (otmb_op_periodic_pc[_dev] with OTMB_OUTER_MEAN: flexible
+    GMRES preconditioned by the cycle-mean operator; include/otmb.h states the method).  info.msolve_iters is filled either way."""
+    @functools.wraps(plain)
+    def periodic(self, source, *, outer="none", **kw):
+        code = outer_code(outer)
+        return plain(self, source, **kw) if code == OUTERS["none"] else self._periodic_pc(source, code, **kw)
+
+    return periodic
 
 
 class Csc(C.Structure):
@@ -213,6 +235,12 @@ SYMBOLS = {
                                           C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp]),
     "otmb_op_periodic": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
                                       C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp]),
+    "otmb_op_periodic_pc_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
+                                             C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int32, _vp]),
+    "otmb_op_periodic_pc": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
+                                         C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int32, _vp]),
+    "otmb_op_combine_slots_dev": (C.c_int32, [_vp, _vp, C.c_int64]),
+    "otmb_op_combine_slots": (C.c_int32, [_vp, _vp, C.c_int64]),
     "otmb_op_info": (C.c_int32, [_vp, _ip, _ip, _ip]),
     "otmb_op_destroy": (None, [_vp]),
     "otmb_transportmatrix_plan_dev": (C.c_int32, [_vp, C.POINTER(TmArgs), C.POINTER(C.c_int64 * 5)]),

@@ -25,6 +25,13 @@
 // arguments, the workspace, the columns, the host's copies -- and its member functions are the steps of otmb_op_periodic_dev's outline:
 // the sources' norms, the first call, the rounds (cycle, orthogonalise, read_hs, judged, advance) and the report (sv_report_open, which the
 // solver shares, as it shares the step's argument checks: otmb_solve.h).
+//
+// otmb_op_periodic_pc[_dev] with OTMB_OUTER_MEAN: flexible GMRES, right-preconditioned by the cycle-mean operator.  M̄ = diag(d) + Ā, Ā the
+// visit-weighted mean of the cycle's slots (cb_combine of otmb_combine.hip into op->mean, once per call), P = ncycle·δt; one implicit-Euler
+// step over the whole period gives Φ ≈ (I + P·M̄)⁻¹, so (I - Φ)⁻¹ ≈ I + (P·M̄)⁻¹.  Iteration i becomes
+//     q = M̄⁻¹·V_i      (the solver's own path on the mean values, σ = 0, from zero, the call's rtol / maxiter / precond: PdRun::msolve)
+//     Z_i = V_i + q / P  (pd_precond_kernel), kept behind the V block;   w = Z_i - Φ·Z_i;   CGS2 against V as before;   x += Z_0..i·y
+// and everything else -- the restart, verify and stop rules, cycles, defect -- is as above.  OTMB_OUTER_NONE is the method above, bit for bit.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -201,6 +208,21 @@ __global__ __launch_bounds__(256) void pd_defect_kernel(i64 n, const double *__r
     }
 }
 
+// ---- z = v + q / P: the preconditioned direction of OTMB_OUTER_MEAN (one division, one addition) ----------------------------------------
+__global__ __launch_bounds__(256) void pd_precond_kernel(i64 n, const double *__restrict__ v, const double *__restrict__ qv, double P, double *__restrict__ z) {
+    for (int q = 0; q < PD_ROWS / 512; ++q) {
+        const i64 i = pd_row(q);
+        if (i >= n) break;
+        Pd2 x = pd_load(v, i, n, true);
+        const Pd2 y = pd_load(qv, i, n, true);
+        const double ta = y.a / P;
+        x.a = x.a + ta;
+        const double tb = y.b / P;
+        x.b = x.b + tb;
+        pd_store(z, i, n, true, x);
+    }
+}
+
 // ---- v = w / s, in place: the new basis vector ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pd_scale_kernel(i64 n, double *__restrict__ w, double s) {
     for (int q = 0; q < PD_ROWS / 512; ++q) {
@@ -216,7 +238,7 @@ __global__ __launch_bounds__(256) void pd_scale_kernel(i64 n, double *__restrict
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
 struct PdCol {  // one column's iteration; ls (otmb_gmres.h): the triangle, the rotations, the rotated right-hand side and the iteration ls.i
     int phase = PD_ARNOLDI, reason = OTMB_PERIODIC_CONVERGED;
-    i64 cycles = 0;
+    i64 cycles = 0, msolve_iters = 0;  // msolve_iters: the BiCGStab iterations of its mean solves (OTMB_OUTER_MEAN)
     double defect = NAN, gnorm = 0.0;
     GmresLsq ls;
     void stop(int why) { phase = PD_STOPPED, reason = why; }
@@ -225,44 +247,56 @@ struct PdCol {  // one column's iteration; ls (otmb_gmres.h): the triangle, the 
 struct PdWork {  // the arrays inside op->pd; every vector has the leading dimension ld (even)
     i64 n, k, m, ld, np;
     double *V, *W, *Sb, *part, *hs, *yv;  // V: k bases of m + 1 vectors; W, Sb: k columns each (contiguous: 2k for the first call)
+    double *Z = nullptr, *mp = nullptr;   // OTMB_OUTER_MEAN: k blocks of m preconditioned directions behind Sb; the mean's preconditioner (n-vectors)
     double *v(i64 c, i64 j) const { return V + (c * (m + 1) + j) * ld; }
+    double *z(i64 c, i64 j) const { return Z + (c * m + j) * ld; }
     double *partc(i64 c) const { return part + c * (m + 2) * np; }
     i64 hso(i64 c) const { return c * 2 * (m + 2); }  // column c's scalars: h' (m + 2 doubles), then h''; the host's copy has the same layout
     double *hsc(i64 c) const { return hs + hso(c); }
 };
 
-static int32_t pd_work(otmb_op *op, i64 k, i64 m, PdWork &w) {
+// zvecs: the vectors of the Z block a column (0, or m with OTMB_OUTER_MEAN); pvecs: the n-vectors of the mean's preconditioner (0, 2 or 5)
+static int32_t pd_work(otmb_op *op, i64 k, i64 m, i64 zvecs, i64 pvecs, PdWork &w) {
     const i64 n = op->n;
     w.n = n, w.k = k, w.m = m, w.ld = (n + 1) & ~(i64)1, w.np = (n + PD_ROWS - 1) / PD_ROWS;
-    const double need = ((double)(m + 3) * (double)w.ld + (double)(m + 2) * (double)w.np + 3.0 * (double)(m + 2)) * (double)k * 8.0;
+    const double need = ((double)(m + 3 + zvecs) * (double)w.ld + (double)(m + 2) * (double)w.np + 3.0 * (double)(m + 2)) * (double)k * 8.0 +
+                        (double)pvecs * (double)w.ld * 8.0;
     if (need >= 9.0e18) return otmb_fail(op->ctx, OTMB_ERR_ALLOC, "periodic: the workspace's size overflows");
-    const size_t vec = (size_t)(m + 3) * (size_t)w.ld * (size_t)k;
+    const size_t vec = (size_t)(m + 3 + zvecs) * (size_t)w.ld * (size_t)k;
+    const size_t scal = (size_t)((m + 2) * w.np * k) + (size_t)(3 * (m + 2) * k);
     int32_t rc;
-    if ((rc = otmb_reserve(op->ctx, op->pd, (vec + (size_t)((m + 2) * w.np * k) + (size_t)(3 * (m + 2) * k)) * 8))) return rc;
+    if ((rc = otmb_reserve(op->ctx, op->pd, (vec + scal + (size_t)(pvecs * w.ld)) * 8))) return rc;
     w.V = (double *)op->pd.p;
     w.W = w.V + (size_t)(m + 1) * (size_t)w.ld * (size_t)k;
     w.Sb = w.W + w.ld * k;
+    w.Z = zvecs ? w.Sb + w.ld * k : nullptr;
     w.part = w.V + vec;
     w.hs = w.part + (m + 2) * w.np * k;
     w.yv = w.hs + 2 * (m + 2) * k;
+    w.mp = pvecs ? w.V + vec + scal : nullptr;
     return OTMB_OK;
 }
 
 static int32_t pd_check(otmb_op *op, int64_t k, double dt, double theta, int64_t ncycle, int64_t first_slot, const double *S, int64_t lds, double *X, int64_t ldx,
                         double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, const int64_t *cycles,
-                        const double *defect, const int32_t *reason) {
+                        const double *defect, const int32_t *reason, int32_t outer) {
     const char *more = !cycles || !defect || !reason ? "null argument" : sv_step_complaint(op, rtol, maxiter, dt, theta, ncycle >= 1, "ncycle must be >= 1", first_slot);
     if (!more)
         more = !(ptol > 0.0)                           ? "ptol must be > 0"
                : restart < 1 || restart >= (1ll << 20) ? "restart must be >= 1 (and below 2^20)"
                : maxcycles < 0                         ? "maxcycles must be >= 0"
                                                        : nullptr;
-    return sv_check_step(op, precond, k, S, lds, X, ldx, more);
+    const int32_t rc = sv_check_step(op, precond, k, S, lds, X, ldx, more);
+    if (rc == OTMB_OK && outer != OTMB_OUTER_NONE && outer != OTMB_OUTER_MEAN)
+        return otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, "outer must be OTMB_OUTER_NONE or OTMB_OUTER_MEAN");
+    return rc;
 }
 
 // g = 0: x = 0 at no cost
-static int32_t pd_all_zero(i64 k, int64_t *cycles, double *defect, int32_t *reason) {
+static int32_t pd_all_zero(i64 k, int64_t *cycles, double *defect, int32_t *reason, int64_t *msolve_iters) {
     for (i64 c = 0; c < k; ++c) cycles[c] = 0, defect[c] = 0.0, reason[c] = OTMB_PERIODIC_CONVERGED;
+    if (msolve_iters)
+        for (i64 c = 0; c < k; ++c) msolve_iters[c] = 0;
     return OTMB_OK;
 }
 
@@ -289,19 +323,26 @@ struct PdRun {  // one call: the operator, the call's arguments, the workspace, 
     int32_t precond;
     double ptol;
     i64 m, maxcycles;
+    int32_t outer;
     PdWork w{};
     dim3 grid, block;
     bool alx = false;  // X takes the 16-byte path
     std::vector<PdCol> col;
     std::vector<double> hs, yh;  // the host's copy of w.hs (read_hs; hsh), the y of the restarts
     std::string step_msg;        // the text of the first step call that left a column not converged
+    std::string msolve_msg;      // the same of the first mean solve
+    SvPrec mean_pc{};            // OTMB_OUTER_MEAN: the mean's preconditioner (σ = 0; in w.mp), and P = ncycle·δt
+    double period = 0.0;
     std::vector<int64_t> s_it;   // a step call's report
     std::vector<double> s_rr;
     std::vector<int32_t> s_why;
 
     const double *hsh(i64 c) const { return hs.data() + w.hso(c); }  // column c's scalars as the last read_hs left them
     void fold(i64 c, i64 nq, double *out) { hipLaunchKernelGGL(pd_fold_kernel, dim3(1), block, 0, st, (const double *)w.partc(c), w.np, nq, out); }
+    const double *dir(i64 c, i64 i) const { return outer == OTMB_OUTER_MEAN ? w.z(c, i) : w.v(c, i); }  // the direction Φ is applied to in iteration i
     int32_t prepare();
+    int32_t mean_setup();
+    int32_t msolve(std::vector<PdItem> &items);
     int32_t read_hs();
     int32_t cycle(std::vector<PdItem> &items, bool withS, double *sbuf);
     void defect_of(i64 c, i64 p, bool minus_x);
@@ -311,12 +352,13 @@ struct PdRun {  // one call: the operator, the call's arguments, the workspace, 
     void orthogonalise(i64 c, i64 i, i64 p);
     int32_t advance(i64 c);
     int32_t round(bool &more);
-    int32_t report(int64_t *cycles, double *defect, int32_t *reason);
+    int32_t report(int64_t *cycles, double *defect, int32_t *reason, int64_t *msolve_iters);
 };
 
 int32_t PdRun::prepare() {
     int32_t rc;
-    if ((rc = pd_work(op, k, m, w))) return rc;
+    const bool mean = outer == OTMB_OUTER_MEAN;
+    if ((rc = pd_work(op, k, m, mean ? m : 0, mean ? (precond == OTMB_PRECOND_LINES ? 5 : 2) : 0, w))) return rc;
     grid = dim3((unsigned)w.np), block = dim3(256);
     alx = ((uintptr_t)X & 15) == 0 && (ldx & 1) == 0;
     col.resize((size_t)k);
@@ -328,6 +370,77 @@ int32_t PdRun::read_hs() {
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(hs.data(), w.hs, hs.size() * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
+    return OTMB_OK;
+}
+
+// OTMB_OUTER_MEAN, once per call and before X is touched: the mean values Σ_s (count_s / ncycle)·(slot s) into op->mean, count_s the visits
+// of slot s by the cycle's steps, and their preconditioner at σ = 0 (a singular one is refused here).
+int32_t PdRun::mean_setup() {
+    const i64 nslots = (i64)op->slots.size();
+    int32_t rc;
+    for (DevBuf *b : {&op->mean.nz, &op->mean.val}) {  // at their exact sizes, like the slots
+        const size_t bytes = std::max<size_t>((size_t)(b == &op->mean.nz ? op->nnz : op->nval) * 8, 8);
+        if (b->p && b->cap == bytes) continue;
+        if (b->p) (void)hipFree(b->p);
+        b->p = nullptr, b->cap = 0;
+        if (hipMalloc(&b->p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            b->p = nullptr;
+            return otmb_fail(ctx, OTMB_ERR_ALLOC, "hipMalloc (periodic: the mean values)");
+        }
+        b->cap = bytes;
+    }
+    std::vector<i64> count((size_t)nslots, 0);
+    for (i64 t = 0; t < ncycle; ++t) count[(size_t)((first_slot + t) % nslots)] += 1;
+    std::vector<double> wt((size_t)nslots);
+    for (i64 s = 0; s < nslots; ++s) wt[(size_t)s] = (double)count[(size_t)s] / (double)ncycle;
+    if ((rc = cb_combine(op, wt.data(), op->mean))) return rc;
+    period = (double)ncycle * dt;
+    mean_pc = sv_prec_carve(w.mp, w.n, precond == OTMB_PRECOND_LINES);
+    SvValues on(op, op->mean);
+    if ((rc = sv_prec_prepare(op, adjoint, precond, d, 0.0, mean_pc))) ctx->err += " (the cycle-mean operator)";
+    return rc;
+}
+
+// OTMB_OUTER_MEAN: Z_i = V_i + M̄⁻¹·V_i / P for `items` (the columns that iterate; from = i).  One solve for all of them, gathered compactly:
+// right-hand sides in Sb (no source is in use in an iterating round), answers in W.  A solve that leaves columns not converged stops those
+// (PRECOND_FAILED) and is repeated without them; a column's msolve_iters counts the solve that completes, and the one that stopped it.
+int32_t PdRun::msolve(std::vector<PdItem> &items) {
+    const i64 n = w.n, ld = w.ld;
+    while (!items.empty()) {
+        const i64 kk = (i64)items.size();
+        for (i64 p = 0; p < kk; ++p)
+            HIP_TRY(ctx, hipMemcpyAsync(w.Sb + p * ld, w.v(items[(size_t)p].col, items[(size_t)p].from), (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+        s_it.assign((size_t)kk, 0), s_rr.assign((size_t)kk, 0.0), s_why.assign((size_t)kk, 0);
+        int32_t rc;
+        {
+            SvValues on(op, op->mean);
+            rc = sv_solve(op, adjoint, kk, mean_pc, w.Sb, ld, w.W, ld, 0, rtol, maxiter, s_it.data(), s_rr.data(), s_why.data(), precond);
+        }
+        if (rc == OTMB_OK) {
+            for (i64 p = 0; p < kk; ++p) {
+                const PdItem &it = items[(size_t)p];
+                col[(size_t)it.col].msolve_iters += s_it[(size_t)p];
+                hipLaunchKernelGGL(pd_precond_kernel, grid, block, 0, st, n, (const double *)w.v(it.col, it.from), (const double *)(w.W + p * ld), period,
+                                   w.z(it.col, it.from));
+            }
+            return OTMB_OK;
+        }
+        if (rc != OTMB_ERR_NOT_CONVERGED) return rc;
+        if (msolve_msg.empty()) msolve_msg = ctx->err;
+        std::vector<PdItem> left;
+        for (i64 p = 0; p < kk; ++p) {
+            PdCol &q = col[(size_t)items[(size_t)p].col];
+            if (s_why[(size_t)p] != OTMB_SOLVE_CONVERGED) {
+                q.msolve_iters += s_it[(size_t)p];
+                q.stop(OTMB_PERIODIC_PRECOND_FAILED);
+            } else {
+                left.push_back(items[(size_t)p]);
+            }
+        }
+        if (left.size() == items.size()) return otmb_fail(ctx, OTMB_ERR_HIP, "periodic: a mean solve failed without a failing column");  // (cannot happen)
+        items.swap(left);
+    }
     return OTMB_OK;
 }
 
@@ -343,7 +456,7 @@ int32_t PdRun::cycle(std::vector<PdItem> &items, bool withS, double *sbuf) {
             if (it.from == -2)
                 HIP_TRY(ctx, hipMemsetAsync(w.W + p * ld, 0, (size_t)n * 8, st));
             else
-                HIP_TRY(ctx, hipMemcpyAsync(w.W + p * ld, it.from >= 0 ? w.v(it.col, it.from) : X + it.col * ldx, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+                HIP_TRY(ctx, hipMemcpyAsync(w.W + p * ld, it.from >= 0 ? dir(it.col, it.from) : X + it.col * ldx, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
             if (withS) HIP_TRY(ctx, hipMemcpyAsync(sbuf + p * ld, S + it.col * lds, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
         }
         s_it.assign((size_t)(ncycle * kk), 0), s_rr.assign((size_t)(ncycle * kk), 0.0), s_why.assign((size_t)(ncycle * kk), 0);
@@ -447,12 +560,12 @@ int32_t PdRun::first_call(std::vector<PdItem> &items) {
     return OTMB_OK;
 }
 
-// iteration i of column c on the device, from Φ·V_i in W[p]: w = V_i - Φ·V_i into V_{i+1}, then CGS2 against V_0..i; h', h'' and ‖w‖² -> hs[c]
+// iteration i of column c on the device, from Φ·V_i in W[p] (OTMB_OUTER_MEAN: Z_i for V_i): w = V_i - Φ·V_i into V_{i+1}, then CGS2 against V_0..i; h', h'' and ‖w‖² -> hs[c]
 void PdRun::orthogonalise(i64 c, i64 i, i64 p) {
     const i64 n = w.n, ld = w.ld, np = w.np;
     double *wv = w.v(c, i + 1), *h1 = w.hsc(c), *h2 = w.hsc(c) + (m + 2);
     const double *V = w.v(c, 0);
-    hipLaunchKernelGGL(pd_defect_kernel, grid, block, 0, st, n, (const double *)w.v(c, i), (const double *)(w.W + p * ld), true, wv, (double *)nullptr);
+    hipLaunchKernelGGL(pd_defect_kernel, grid, block, 0, st, n, dir(c, i), (const double *)(w.W + p * ld), true, wv, (double *)nullptr);
     for (int pass = 0; pass < 2; ++pass) {
         double *h = pass ? h2 : h1;
         op_blocks<PD_NB>(0, i + 1, [&](auto nb, i64 j0) {
@@ -487,7 +600,7 @@ int32_t PdRun::advance(i64 c) {
     double *y = yh.data() + c * m;
     q.ls.solve(y);
     HIP_TRY(ctx, hipMemcpyAsync(w.yv + c * m, y, (size_t)q.ls.i * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(pd_combine_kernel, grid, block, 0, st, w.n, (const double *)w.v(c, 0), w.ld, q.ls.i, (const double *)(w.yv + c * m), X + c * ldx, alx);
+    hipLaunchKernelGGL(pd_combine_kernel, grid, block, 0, st, w.n, dir(c, 0), w.ld, q.ls.i, (const double *)(w.yv + c * m), X + c * ldx, alx);
     q.phase = PD_VERIFY;
     return OTMB_OK;
 }
@@ -504,6 +617,7 @@ int32_t PdRun::round(bool &more) {
     }
     more = !(ia.empty() && iv.empty());
     if (!more) return OTMB_OK;
+    if (outer == OTMB_OUTER_MEAN && (rc = msolve(ia))) return rc;
     if ((rc = cycle(ia, false, nullptr))) return rc;
     for (size_t p = 0; p < ia.size(); ++p) orthogonalise(ia[p].col, ia[p].from, (i64)p);
     if ((rc = cycle(iv, true, w.Sb))) return rc;
@@ -516,45 +630,48 @@ int32_t PdRun::round(bool &more) {
     return OTMB_OK;
 }
 
-int32_t PdRun::report(int64_t *cycles, double *defect, int32_t *reason) {
+int32_t PdRun::report(int64_t *cycles, double *defect, int32_t *reason, int64_t *msolve_iters) {
     for (i64 c = 0; c < k; ++c) cycles[c] = col[(size_t)c].cycles, defect[c] = col[(size_t)c].defect, reason[c] = col[(size_t)c].reason;
-    static const char *const names[] = {"converged", "maxcycles", "step failed", "nonfinite"};
+    if (msolve_iters)
+        for (i64 c = 0; c < k; ++c) msolve_iters[c] = col[(size_t)c].msolve_iters;
+    static const char *const names[] = {"converged", "maxcycles", "step failed", "nonfinite", "precond failed"};
     return sv_report_open(ctx, "periodic: %lld of %lld columns; the first is column %lld: %s after %lld cycles, defect %.3e", names, k, reason, cycles, defect,
-                          step_msg.empty() ? step_msg : "; the step: " + step_msg);
+                          (step_msg.empty() ? step_msg : "; the step: " + step_msg) + (msolve_msg.empty() ? msolve_msg : "; the mean solve: " + msolve_msg), 5);
 }
 
 extern "C" {
 
-int32_t otmb_op_periodic_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t ncycle, int64_t first_slot,
-                             const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond,
-                             double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason) {
+int32_t otmb_op_periodic_pc_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t ncycle, int64_t first_slot,
+                                const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond,
+                                double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer,
+                                int64_t *msolve_iters) {
     if (!op) return OTMB_ERR_INVALID_ARG;
     int32_t rc;
-    if ((rc = pd_check(op, k, dt, theta, ncycle, first_slot, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect, reason)))
+    if ((rc = pd_check(op, k, dt, theta, ncycle, first_slot, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect, reason, outer)))
         return rc;
     otmb_ctx *ctx = op->ctx;
     // the trivial answers: no rows, no source
-    if (op->n == 0) return pd_all_zero(k, cycles, defect, reason);
+    if (op->n == 0) return pd_all_zero(k, cycles, defect, reason, msolve_iters);
     HIP_TRY(ctx, hipSetDevice(op->device));
     if (!S) {
         HIP_TRY(ctx, hipMemset2DAsync(X, (size_t)ldx * 8, 0, (size_t)op->n * 8, (size_t)k, ctx->stream));
-        return pd_all_zero(k, cycles, defect, reason);
+        return pd_all_zero(k, cycles, defect, reason, msolve_iters);
     }
-    PdRun r{op, ctx, ctx->stream, adjoint, k, d, dt, theta, ncycle, first_slot, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles};
+    PdRun r{op, ctx, ctx->stream, adjoint, k, d, dt, theta, ncycle, first_slot, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, outer};
     std::vector<PdItem> items;
-    if ((rc = r.prepare()) || (rc = r.source_norms(items)) || (rc = r.first_call(items))) return rc;
+    if ((rc = r.prepare()) || (outer == OTMB_OUTER_MEAN && (rc = r.mean_setup())) || (rc = r.source_norms(items)) || (rc = r.first_call(items))) return rc;
     for (bool more = true; more;)
         if ((rc = r.round(more))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (yh's uploads have been read)
-    return r.report(cycles, defect, reason);
+    return r.report(cycles, defect, reason, msolve_iters);
 }
 
-int32_t otmb_op_periodic(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t ncycle, int64_t first_slot,
-                         const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol,
-                         int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason) {
+int32_t otmb_op_periodic_pc(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t ncycle, int64_t first_slot,
+                            const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol,
+                            int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters) {
     if (!op) return OTMB_ERR_INVALID_ARG;
     int32_t rc;
-    if ((rc = pd_check(op, k, dt, theta, ncycle, first_slot, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect, reason)))
+    if ((rc = pd_check(op, k, dt, theta, ncycle, first_slot, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect, reason, outer)))
         return rc;
     otmb_ctx *ctx = op->ctx;
     HIP_TRY(ctx, hipSetDevice(op->device));
@@ -566,10 +683,24 @@ int32_t otmb_op_periodic(otmb_op *op, int32_t adjoint, int64_t k, const double *
         if (use_x0 && (rc = op_upload(ctx, dx, X, ldx, n, k))) return rc;
         if (S && (rc = op_upload(ctx, ds, S, lds, n, k))) return rc;
     }
-    rc = otmb_op_periodic_dev(op, adjoint, k, dd, dt, theta, ncycle, first_slot, ds, n, dx, n, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, cycles,
-                              defect, reason);
+    rc = otmb_op_periodic_pc_dev(op, adjoint, k, dd, dt, theta, ncycle, first_slot, ds, n, dx, n, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, cycles,
+                                 defect, reason, outer, msolve_iters);
     if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED) return rc;
     return op_finish(ctx, rc, X, ldx, dx, n, k);
+}
+
+int32_t otmb_op_periodic_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t ncycle, int64_t first_slot,
+                             const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond,
+                             double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason) {
+    return otmb_op_periodic_pc_dev(op, adjoint, k, d, dt, theta, ncycle, first_slot, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles,
+                                   cycles, defect, reason, OTMB_OUTER_NONE, nullptr);
+}
+
+int32_t otmb_op_periodic(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t ncycle, int64_t first_slot,
+                         const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol,
+                         int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason) {
+    return otmb_op_periodic_pc(op, adjoint, k, d, dt, theta, ncycle, first_slot, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, cycles,
+                               defect, reason, OTMB_OUTER_NONE, nullptr);
 }
 
 }  // extern "C"

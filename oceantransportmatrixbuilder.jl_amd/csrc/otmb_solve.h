@@ -44,12 +44,27 @@ int32_t sv_solve(otmb_op *op, int adjoint, i64 k, const SvPrec &p, const double 
 //                  that order, or null: what otmb_op_step and otmb_op_periodic ask of the arguments they share.
 // sv_report_open:  the end of a call that reports per column: OTMB_OK when every reason is 0 (converged); otherwise OTMB_ERR_NOT_CONVERGED with
 //                  fmt filled from the open columns' number, k, the first of them (1-based), names[its reason], count[it] and value[it],
-//                  and `tail` behind it.
+//                  and `tail` behind it.  names holds nnames texts (a reason beyond them reads as names[0]).
 int32_t sv_check_step(otmb_op *op, int32_t precond, int64_t k, const double *S, int64_t lds, double *X, int64_t ldx, const char *more);
 const char *sv_step_complaint(const otmb_op *op, double rtol, int64_t maxiter, double dt, double theta, bool count_ok, const char *count_text,
                               int64_t first_slot);
 int32_t sv_report_open(otmb_ctx *ctx, const char *fmt, const char *const *names, i64 k, const int32_t *reason, const int64_t *count, const double *value,
-                       const std::string &tail = std::string());
+                       const std::string &tail = std::string(), int nnames = 4);
+
+// The solver, its preconditioner and the products read the values op->nz / op->val point at (the selected slot's).  SvValues points them at
+// another value set of the same pattern for its lifetime: sv_prec_prepare and sv_solve on an explicit value set (the periodic state's mean).
+struct SvValues {
+    otmb_op *op;
+    DevBuf nz, val;
+    SvValues(otmb_op *o, const OpSlot &s) : op(o), nz(o->nz), val(o->val) { op->nz = s.nz, op->val = s.val; }
+    ~SvValues() { op->nz = nz, op->val = val; }
+    SvValues(const SvValues &) = delete;
+    SvValues &operator=(const SvValues &) = delete;
+};
+
+// cb_combine (otmb_combine.hip): Σ_s w[s]·(slot s) into both value arrays of `to`, a slot of the operator or op->mean; w: nslots finite host
+// values.  Enqueued on the context's stream.
+int32_t cb_combine(otmb_op *op, const double *w, const OpSlot &to);
 
 // the report of an empty system (n = 0): every entry converged at once
 static inline int32_t sv_report_empty(i64 entries, int64_t *iters, double *relres, int32_t *reason) {

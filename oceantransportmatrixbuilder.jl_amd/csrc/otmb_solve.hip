@@ -522,13 +522,13 @@ static int32_t sv_check_apply(otmb_op *op, int32_t precond, int64_t k, const dou
 }
 
 int32_t sv_report_open(otmb_ctx *ctx, const char *fmt, const char *const *names, i64 k, const int32_t *reason, const int64_t *count, const double *value,
-                       const std::string &tail) {
+                       const std::string &tail, int nnames) {
     i64 open = 0, first = -1;
     for (i64 c = 0; c < k; ++c)
         if (reason[c] != 0 && open++ == 0) first = c;
     if (open == 0) return OTMB_OK;
     char msg[200];
-    snprintf(msg, sizeof msg, fmt, (long long)open, (long long)k, (long long)first + 1, names[reason[first] & 3], (long long)count[first], value[first]);
+    snprintf(msg, sizeof msg, fmt, (long long)open, (long long)k, (long long)first + 1, names[reason[first] >= 0 && reason[first] < nnames ? reason[first] : 0], (long long)count[first], value[first]);
     return otmb_fail(ctx, OTMB_ERR_NOT_CONVERGED, (msg + tail).c_str());
 }
 

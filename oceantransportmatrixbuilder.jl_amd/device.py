@@ -84,6 +84,14 @@ class Operator:
         """mul, solve and precondition read slot `slot` from now on (a pointer switch)."""
         self.ctx.check(self.lib.otmb_op_select_slot(self._h, int(slot)))
 
+    def combine_slots(self, weights, dst):
+        """Slot dst = Σ_s weights[s]·(slot s), enqueued on the context's stream (otmb_op_combine_slots_dev; api.DeviceOperator.combine_slots).
+        weights: host values, one per slot."""
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (self.slots[0],):
+            raise capi.OtmbError(11, f"DimensionMismatch: weights of {w.shape}, expected {(self.slots[0],)}")
+        self.ctx.check(self.lib.otmb_op_combine_slots_dev(self._h, w.ctypes.data, int(dst)))
+
     @property
     def slots(self):
         """(number of slots, the selected slot)."""
@@ -212,6 +220,7 @@ class Operator:
             self.ctx.check(rc)
         return Xn, StepInfo(rc, done.value, nsteps, iters, relres, reason)
 
+    @capi.outer_keyword
     def periodic(self, source, *, dt, ncycle, theta=1.0, first_slot=0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi",
                  ptol=1e-8, restart=30, maxcycles=1000):
         """The periodic state of the stepped cycle on device tensors (otmb_op_periodic_dev; api.DeviceOperator.periodic states the arguments).
@@ -233,6 +242,28 @@ class Operator:
         if rc != capi.NOT_CONVERGED:
             self.ctx.check(rc)
         return X, PeriodicInfo(rc, cycles, defect, reason)
+
+    def _periodic_pc(self, source, outer, *, dt, ncycle, theta=1.0, first_slot=0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False,
+                     precond="jacobi", ptol=1e-8, restart=30, maxcycles=1000):
+        """periodic with outer = an otmb_outer code: otmb_op_periodic_pc_dev."""
+        from .api import PeriodicInfo
+
+        pc, k, Sc, lds, X = self._system(source, "source", precond)
+        if x0 is not None:
+            _on_device(x0, self.device, "x0")
+            if tuple(x0.shape) != tuple(source.shape):
+                raise capi.OtmbError(11, f"DimensionMismatch: x0 of {tuple(x0.shape)}, source of {tuple(source.shape)}")
+            X.copy_(x0)
+        d, dp = self._d_ptr(d)
+        cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
+        msolve = np.zeros(k, dtype=np.int64)
+        rc = self.lib.otmb_op_periodic_pc_dev(self._h, int(bool(adjoint)), k, dp, float(dt), float(theta), int(ncycle), int(first_slot), Sc.data_ptr(),
+                                              lds, X.data_ptr(), max(self.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), pc, float(ptol),
+                                              int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data, reason.ctypes.data, int(outer),
+                                              msolve.ctypes.data)
+        if rc != capi.NOT_CONVERGED:
+            self.ctx.check(rc)
+        return X, PeriodicInfo(rc, cycles, defect, reason, msolve)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -828,9 +859,22 @@ class DeviceAssembler:
             raise ValueError(f"no operator over {matrix}: keep_slot() first")
         return rec["op"].step(X, **kw)
 
+    def combine_slots(self, weights, dst, matrix="T"):
+        """Operator.combine_slots on the resident operator over `matrix`: slot dst = Σ_s weights[s]·(slot s) over the slots keep_slot() filled
+        (the annual mean of the kept months).  The written slot is not the resident result: when it is the selected one, the operator counts
+        as changed since the result was put there, so operator() raises until keep_slot() or forget_slots() says where the result goes."""
+        rec = getattr(self, "_ops", {}).get(matrix)
+        if rec is None or not rec["op"].handle.value:
+            raise ValueError(f"no operator over {matrix}: keep_slot() first")
+        op = rec["op"]
+        op.combine_slots(weights, dst)
+        if int(dst) == op.slots[1]:
+            rec["dirty"] = True
+        return op
+
     def periodic_tracers(self, source, *, matrix="T", **kw):
         """Operator.periodic on the resident operator over `matrix`: the periodic state of the cycle through the slots keep_slot() filled, as
-        they are (step_tracers says which slots those are)."""
+        they are (step_tracers says which slots those are); outer="mean" preconditions the outer iteration with their cycle mean."""
         rec = getattr(self, "_ops", {}).get(matrix)
         if rec is None or not rec["op"].handle.value:
             raise ValueError(f"no operator over {matrix}: keep_slot() first")

@@ -27,9 +27,12 @@ the floor of an iteration, whose five vector passes and scalar kernels the fusio
     step call of one step, and from these a later visit (right-hand side plus solve).  rhs_torch_us is the COMPOSITION's right-hand side,
     torch's σ·x (HIP events around 24 of them); the step call's own right-hand-side kernel has no entry point to time it through and is
     read from a kernel trace of `--step --step-route step` instead.  The record carries the device memory the slots take.
---periodic [--ptol --restart --maxcycles --rtol]: the periodic state of that year -- the twelve slots of --step, θ = 1, lines, the age system
+--periodic [--outer none|mean --ptol --restart --maxcycles --rtol]: the periodic state of that year -- the twelve slots of --step, θ = 1, lines, the age system
     (d = 1 s⁻¹ at the surface, s = 1), k = 1 -- by otmb_op_periodic_dev: cycles, wall time, defect; then, in the same process, the same
-    number of plain cycles by otmb_op_step_dev in a loop from zero: their wall time and the defect they leave.
+    number of plain cycles by otmb_op_step_dev in a loop from zero: their wall time and the defect they leave.  --outer mean: the outer GMRES
+    preconditioned by the cycle-mean operator (otmb_op_periodic_pc_dev); the record then carries the mean solves' iterations and the wall time
+    of one mean solve (the twelve slots' mean by otmb_op_combine_slots_dev in a thirteenth slot, σ = 0, from zero) beside that of one cycle.
+    --outer none is the call of the commits before the keyword.
 --host: the parent's only route as well -- result_to_host, then scipy.sparse.linalg.bicgstab with the same (Jacobi) preconditioner."""
 import argparse
 import json
@@ -181,13 +184,13 @@ def periodic_times(asm, a):
     s = torch.ones(N, dtype=torch.float64, device="cuda")
     kw = dict(dt=dt, theta=1.0, first_slot=0, d=d, rtol=a.rtol, maxiter=a.maxiter, precond="lines")
     rec = {"what": "periodic state of twelve monthly steps, T, age system", "n": N, "nnz": nnz, "nslots": nslots, "ncycle": nslots, "precond": "lines",
-           "theta": 1.0, "dt_s": dt, "ptol": a.ptol, "restart": a.restart, "maxcycles": a.maxcycles, "rtol": a.rtol}
+           "theta": 1.0, "dt_s": dt, "ptol": a.ptol, "restart": a.restart, "maxcycles": a.maxcycles, "rtol": a.rtol, "outer": a.outer}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    X, info = op.periodic(s, ncycle=nslots, ptol=a.ptol, restart=a.restart, maxcycles=a.maxcycles, **kw)
+    X, info = op.periodic(s, ncycle=nslots, ptol=a.ptol, restart=a.restart, maxcycles=a.maxcycles, outer=a.outer, **kw)
     torch.cuda.synchronize()
     rec.update(periodic_s=time.perf_counter() - t0, cycles=int(info.cycles[0]), defect=float(info.defect[0]), reason=info.reason[0],
-               checksum=float(X.sum().item()))
+               msolve_iters=int(info.msolve_iters[0]), checksum=float(X.sum().item()))
     # the same number of plain cycles from zero, then one more to measure what they leave
     G, si = op.step(torch.zeros_like(s), nsteps=nslots, source=s, **kw)
     assert si.steps_done == nslots, si
@@ -202,6 +205,19 @@ def periodic_times(asm, a):
     FY, si = op.step(Y, nsteps=nslots, source=s, **kw)
     rec["plain_defect"] = float((torch.linalg.norm(FY - Y) / torch.linalg.norm(G)).item())
     rec["per_cycle_s"] = rec["plain_s"] / max(rec["cycles"], 1)
+    if a.outer == "mean":  # one mean solve on its own: the right-hand side a unit vector, as a basis vector is
+        op.set_slots(nslots + 1)
+        op.combine_slots([1.0 / nslots] * nslots + [0.0], nslots)
+        op.select(nslots)
+        v = s / torch.linalg.norm(s)
+        ts = []
+        for r in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            _, mi = op.solve(v, d=d, sigma=0.0, rtol=a.rtol, maxiter=a.maxiter, precond="lines")
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        rec.update(mean_solve_s=float(np.median(ts[1:])), mean_solve_iters=int(mi.iterations[0]), mean_solve_reason=mi.reason[0])
     print(json.dumps(rec), flush=True)
     op.close()
     if a.out:
@@ -221,6 +237,7 @@ def main():
     ap.add_argument("--step", action="store_true")
     ap.add_argument("--step-route", default="both", choices=["step", "compose", "both"])
     ap.add_argument("--periodic", action="store_true")
+    ap.add_argument("--outer", default="none", choices=["none", "mean"])
     ap.add_argument("--ptol", type=float, default=1e-8)
     ap.add_argument("--restart", type=int, default=30)
     ap.add_argument("--maxcycles", type=int, default=200)
