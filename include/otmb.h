@@ -201,7 +201,8 @@ int32_t otmb_facefluxes_flags_dev(otmb_ctx *ctx, const void *umo, const void *vm
  * grids only (no top_below, wet ranks from 1).  Falls back to otmb_facefluxes_flags_dev's behaviour (mask written, no counts) when
  * nx < 3 or OTMB_COUNT_IN_FF=0.
  * tables: once per grid by otmb_count_tables_dev from the indices and otmb_wetflags_dev's bytes (otmb_count_tables_bytes bytes: the wet
- * rank of the first wet cell of every 64-cell segment a wave of the kernel covers, and the static counts of every tile).  Both
+ * rank of the first wet cell of every segment a wave of the kernel covers -- 64 cells, or 32 where it marches two levels per wave,
+ * otmb_ctx_ff_pairs -- and the static counts of every tile).  Both
  * asynchronous.                                                                                                                   */
 typedef struct {
     const void *tables;      /* otmb_count_tables_dev */
@@ -243,6 +244,12 @@ int32_t otmb_facefluxes_slab_counts_dev(otmb_ctx *ctx, const void *umo, const vo
 /* 1 when the last facefluxes call on this context counted (its push_mask argument was therefore not written, and need not be completed
  * for halo planes by otmb_push_mask_dev), 0 when it took the plain kernel or the counts have been consumed.  No device work.   */
 int32_t otmb_facefluxes_counts_pending(const otmb_ctx *ctx);
+/* Which kernel the last facefluxes call on this context ran: 1 the one that marches two levels per wave (whole-plane counting calls on
+ * whole grids of two levels or more whose ceil(nx ny / 32) waves are all resident at once; OTMB_FF_PAIRS=0 never, =1 whatever the size),
+ * 0 the one-level kernel, -1 no call yet.  The count tables of such a grid hold segments of 32 columns: build them and call facefluxes
+ * on contexts created under the same OTMB_FF_PAIRS and OTMB_FF_ROWS (tables of another geometry are recognised: the transportmatrix
+ * then reports OTMB_ERR_PUSH_MASK, as for any counts that do not describe the fluxes).  No device work.                          */
+int32_t otmb_ctx_ff_pairs(const otmb_ctx *ctx);
 /* The same two flags for EVERY facefluxes call on this context since the previous call of this function, oldest
  * first (a pipeline of asynchronous steps: the reference asserts per call, src/velocities.jl:199-200, so a field
  * without a single valid value in step 3 of 12 must not be hidden by steps 4-12).  Synchronises.  At most the 64

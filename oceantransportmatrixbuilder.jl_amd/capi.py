@@ -135,6 +135,7 @@ SYMBOLS = {
     "otmb_ctx_forget_given": (C.c_int32, [_vp]),
     "otmb_ctx_given_state": (C.c_int32, [_vp, C.c_int32]),
     "otmb_ctx_given_checks": (C.c_int64, [_vp]),
+    "otmb_ctx_ff_pairs": (C.c_int32, [_vp]),
     "otmb_ctx_kept_htab": (C.c_int32, [_vp]),
     "otmb_ctx_kept_nbtab": (C.c_int32, [_vp]),
     "otmb_ctx_kept_t_pattern": (C.c_int32, [_vp]),
@@ -387,6 +388,10 @@ class Context:
     def given_state(self, m):
         """How the last plan / _dev call treated operator m (index into MATS): 0 not given, 1 given and derived, 2 given and foreign, 3 given with the derived rows and other values (another κ: read by the fill pass)."""
         return int(self._lib.otmb_ctx_given_state(self._h, int(m)))
+
+    def ff_pairs(self):
+        """Which kernel the last facefluxes call ran: 1 two levels per wave (facefluxes_pair_kernel), 0 one level per wave, -1 no call yet."""
+        return int(self._lib.otmb_ctx_ff_pairs(self._h))
 
     def kept_htab(self):
         """Whether the last fill that kept TκH, TκVML and TκVdeep read TκH from the context's table: 1 yes, 0 no, -1 no such fill yet."""

@@ -55,6 +55,9 @@ struct otmb_ctx {
     int ff_nt = -1;           // facefluxes' ϕ stores non-temporal (1), plain (0), by size (-1: beyond a gigabyte of fluxes) (experiments: OTMB_FF_NT)
     int ff_lds_south = 1;     // four-row facefluxes workgroups take a wave's south row from the neighbouring wave through LDS (experiments: OTMB_FF_LDS_SOUTH)
     int ff_rows = 0;          // facefluxes: rows per workgroup, 1 or 4; 0 = by grid size (experiments: OTMB_FF_ROWS)
+    int ff_pairs = -1;        // facefluxes: two levels per wave on whole-plane counting calls (facefluxes_pair_kernel): 1 wherever eligible, 0 never, -1 where all its waves are resident at once (OTMB_FF_PAIRS)
+    int ff_pairs_last = -1;   // the last facefluxes call ran facefluxes_pair_kernel (1) or facefluxes_kernel (0); -1: none yet (otmb_ctx_ff_pairs)
+    int n_cu = 0;             // compute units of the device
     int count_order = 2;      // counting pass: 0 = blockIdx (wet-rank) order, 1 = XCD-contiguous eighths of wet-rank order, 2 = of the fill pass's tile order (default: HBM fetch 1.06-1.11 x its inputs instead of 2.1-2.7 x, +2-4 % of this pass's time; OTMB_COUNT_ORDER)
     // ---- counts in facefluxes (otmb_facefluxes_counts_dev): the five per-tile row counts of the transportmatrix that will be built from the
     // fluxes a facefluxes call is writing are accumulated by that call (packed 64-bit atomics, one word per tile of 256 columns), so the

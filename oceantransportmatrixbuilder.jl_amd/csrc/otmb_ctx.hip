@@ -75,6 +75,8 @@ int32_t otmb_ctx_create(int32_t device_id, otmb_ctx **out) {
     if (const char *e = getenv("OTMB_MARCH_COLS")) c->march_cols = atoi(e);  // experiments
     if (const char *e = getenv("OTMB_FF_XCD")) c->ff_xcd_chunks = atoi(e);       // experiments (A/B in one library)
     if (const char *e = getenv("OTMB_FF_ROWS")) c->ff_rows = atoi(e);
+    if (const char *e = getenv("OTMB_FF_PAIRS")) c->ff_pairs = atoi(e) > 0 ? 1 : 0;
+    if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess) c->n_cu = 0;
     if (const char *e = getenv("OTMB_FF_LDS_SOUTH")) c->ff_lds_south = atoi(e);
     if (const char *e = getenv("OTMB_FF_NT")) c->ff_nt = atoi(e);
     if (const char *e = getenv("OTMB_COUNT_ORDER")) c->count_order = atoi(e);
@@ -172,6 +174,7 @@ int32_t otmb_ctx_forget_given(otmb_ctx *ctx) {
 
 int32_t otmb_ctx_given_state(const otmb_ctx *ctx, int32_t m) { return (ctx && m >= 0 && m < 5) ? ctx->given_state[m] : -1; }
 int64_t otmb_ctx_given_checks(const otmb_ctx *ctx) { return ctx ? (int64_t)ctx->given_checks : -1; }
+int32_t otmb_ctx_ff_pairs(const otmb_ctx *ctx) { return ctx ? ctx->ff_pairs_last : -1; }
 int32_t otmb_ctx_kept_htab(const otmb_ctx *ctx) { return ctx ? ctx->htab_used : -1; }
 int32_t otmb_ctx_kept_nbtab(const otmb_ctx *ctx) { return ctx ? ctx->nbtab_used : -1; }
 int32_t otmb_ctx_kept_t_pattern(const otmb_ctx *ctx) { return ctx ? ctx->tpat_used : -1; }

@@ -83,6 +83,7 @@ struct FfCountState {
     double zt_lo, zt_hi;        // lane l: zt[l - ha] / zt[64 + l - ha] (ha = 1 when a halo level lies above: its depth is needed too)
     bool ha, hb;                // (uniform) a halo level above the first / below the last level: depth slab of a deeper grid
     bool om_cur, om_below;      // zt[k] < mlotst for the level being counted / the level below it (a window that moves up with the march)
+    bool om_up;                 // (two levels per wave) ... and for the level above it: lanes 32-63 are one level further up
     unsigned amask;            // seam row: flag bit (E / W) of the row-mate the fold neighbour coincides with, else 0
     bool aclear;               // seam row: the fold neighbour is the east / west row-mate or the cell itself: it has no slot of its own
     bool fold;                 // the lane's cell is on the tripolar seam row
@@ -117,11 +118,62 @@ __device__ __forceinline__ double ff_level_f64(double lo, double hi, int k) {
     const int l = k & 63;
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
 }
+// ---- two levels per wave (facefluxes_pair_kernel): lanes 0-31 hold 32 columns at level k, lanes 32-63 the same columns at level k - 1 ----
+// v_permlane32_swap: lanes 32-63 of a change places with lanes 0-31 of b; the other two halves stay.  A VALU instruction: no LDS, no barrier.
+struct FfSwap { unsigned a, b; };
+__device__ __forceinline__ FfSwap ff_swap32(unsigned a, unsigned b) {
+    FfSwap r;
+#if __has_builtin(__builtin_amdgcn_permlane32_swap)
+    const auto v = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+    r.a = v[0]; r.b = v[1];
+#else
+    const bool up = (threadIdx.x & 32) != 0;
+    const unsigned ax = (unsigned)__shfl_xor((int)a, 32), bx = (unsigned)__shfl_xor((int)b, 32);
+    r.a = up ? bx : a; r.b = up ? b : ax;
+#endif
+    return r;
+}
+// lanes 0-31 keep a; lanes 32-63 take b of the lane 32 below them
+__device__ __forceinline__ double ff_up_from_low(double a, double b) {
+    return __hiloint2double((int)ff_swap32((unsigned)__double2hiint(a), (unsigned)__double2hiint(b)).a,
+                            (int)ff_swap32((unsigned)__double2loint(a), (unsigned)__double2loint(b)).a);
+}
+// lanes 0-31 take x of the lane 32 above them (lanes 32-63 keep theirs)
+__device__ __forceinline__ double ff_low_from_up(double x) {
+    return __hiloint2double((int)ff_swap32((unsigned)__double2hiint(x), (unsigned)__double2hiint(x)).b,
+                            (int)ff_swap32((unsigned)__double2loint(x), (unsigned)__double2loint(x)).b);
+}
+// x of the same column in the other half
+__device__ __forceinline__ unsigned ff_other_half(unsigned x, bool up) {
+    const FfSwap r = ff_swap32(x, x);
+    return up ? r.a : r.b;
+}
+// ff_wave_sum per half: without row_bcast:31, lanes 31 and 63 hold the totals of lanes 0-31 and 32-63
+__device__ __forceinline__ unsigned ff_half_sum(unsigned v, bool up) {
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);  // row_shr:1
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);  // row_shr:2
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);  // row_shr:4
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);  // row_shr:8
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)v, 31), hi = (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+    return up ? hi : lo;
+}
 // One level of one wave (all 64 lanes execute).  wc / f: the cell's wet flag and five-flag byte, fa: the flag byte of the cell above,
 // vn: vmo of the fold cell (seam-row lanes of waves with has_fold).
+// PAIR (two levels per wave): k is the LANE's level -- ks for lanes 0-31, ks - 1 for lanes 32-63 (`up`; k < 0: no such level, the half
+// idles) -- and ranks, the two-tile split, the sums and the atomic adds go per half.  Both halves hold the same columns, so the
+// mixed-layer window (three levels wide here) is the same in both and each half picks its two entries; wet_below is the caller's.
+template <bool PAIR = false>
 __device__ __forceinline__ void ff_count_level(const FfCountArgs &cnt, FfCountState &cs, int k, int nz, bool wc, unsigned f, unsigned fa,
-                                               double e, double w, double so, double n, double b, double t, double vn, double fill) {
-    const bool wet = cs.act & wc;
+                                               double e, double w, double so, double n, double b, double t, double vn, double fill,
+                                               int ks = 0, bool up = false) {
+    const bool wet = PAIR ? (cs.act & wc & (k >= 0)) : (cs.act & wc);
+    bool o2 = false, o3 = false;  // (PAIR) zt < mlotst two and three levels above ks
+    if (PAIR) {
+        o2 = ff_level_f64(cs.zt_lo, cs.zt_hi, ks >= 2 ? ks - 2 : 0) < cs.mld;
+        o3 = ff_level_f64(cs.zt_lo, cs.zt_hi, ks >= 3 ? ks - 3 : 0) < cs.mld;
+    }
+    const bool om_cur = PAIR ? (up ? cs.om_up : cs.om_cur) : cs.om_cur, om_below = PAIR ? (up ? cs.om_cur : cs.om_below) : cs.om_below;
     const u64 wetb = __builtin_amdgcn_ballot_w64(wet);
     if (wetb != 0) {  // (uniform)
         const bool hA = k > 0 || cs.ha, hB = k + 1 < nz || cs.hb;
@@ -149,28 +201,37 @@ __device__ __forceinline__ void ff_count_level(const FfCountArgs &cnt, FfCountSt
         const unsigned anyA = ab != 0;  // the diagonal's bit
         if (cs.has_fold && cs.aclear) ab = ff_fold_alias(ab, cs.amask);
         unsigned x = wet ? __popc(ab) + anyA : 0u;  // Tadv rows of this column
-        const unsigned base = ff_level_u32(cs.base_lo, cs.base_hi, k);
-        const bool in0 = ff_mbcnt(wetb) < 256u - (base & 255u);  // this lane's column still belongs to the wave's first tile
-        const unsigned sx = ff_wave_sum(in0 ? x : (x << 16));    // both tiles' sums in one word (<= 7 * 64 each)
+        unsigned base, rank = ff_mbcnt(wetb);
+        if (PAIR) {
+            const unsigned b0 = ff_level_u32(cs.base_lo, cs.base_hi, ks), b1 = ff_level_u32(cs.base_lo, cs.base_hi, ks >= 1 ? ks - 1 : 0);
+            base = up ? b1 : b0;
+            rank -= up ? (unsigned)__popc((unsigned)wetb) : 0u;  // wet lanes before this one in its own half
+        } else base = ff_level_u32(cs.base_lo, cs.base_hi, k);
+        const bool in0 = rank < 256u - (base & 255u);  // this lane's column still belongs to the wave's (the half's) first tile
+        const unsigned sx = PAIR ? ff_half_sum(in0 ? x : (x << 16), up) : ff_wave_sum(in0 ? x : (x << 16));  // both tiles' sums in one word (<= 7 * 64 each)
         u64 c0 = (u64)(sx & 0xffffu) << 11, c1 = (u64)(sx >> 16) << 11;
         // TκVML: only within the mixed layer -- Ω[c] = zt[k] < mlotst (:85; NaN compares false), and the same for the cells above / below
-        const bool omC = wet & cs.om_cur;
+        const bool omC = wet & om_cur;
         if (__builtin_amdgcn_ballot_w64(omC) != 0) {  // (uniform)
-            const bool om_above = ff_level_f64(cs.zt_lo, cs.zt_hi, (hA ? k - 1 : k) + (int)cs.ha) < cs.mld;
-            const unsigned ml = ((om_above ? 32u : 0u) | (cs.om_below ? 64u : 0u)) & vw;
+            const bool om_above = PAIR ? (up ? o2 : cs.om_up) : (ff_level_f64(cs.zt_lo, cs.zt_hi, (hA ? k - 1 : k) + (int)cs.ha) < cs.mld);
+            const unsigned ml = ((om_above ? 32u : 0u) | (om_below ? 64u : 0u)) & vw;
             const unsigned y = omC ? __popc(ml) + (ml != 0) : 0u;
-            const unsigned sy = ff_wave_sum(in0 ? y : (y << 16));
+            const unsigned sy = PAIR ? ff_half_sum(in0 ? y : (y << 16), up) : ff_wave_sum(in0 ? y : (y << 16));
             c0 |= (u64)(sy & 0xffffu) << 33;
             c1 |= (u64)(sy >> 16) << 33;
         }
         if (cnt.only_t) c0 = c1 = 0;
         const bool anybad = __builtin_amdgcn_ballot_w64(wet & bad) != 0;
-        if ((threadIdx.x & 63) == 0) {  // one lane: the sums are wave-uniform
+        if ((threadIdx.x & (PAIR ? 31 : 63)) == 0) {  // one lane: the sums are wave-uniform (PAIR: one lane per half)
             const unsigned t0 = base >> FFC_TILE_SHIFT;
             if (c0) __hip_atomic_fetch_add(cnt.sums + t0, c0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (c1) __hip_atomic_fetch_add(cnt.sums + t0 + 1, c1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (anybad) __hip_atomic_fetch_or(cnt.sums + t0, FFC_BAD_FLUX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (anybad && (!PAIR || !up)) __hip_atomic_fetch_or(cnt.sums + t0, FFC_BAD_FLUX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
+    }
+    if (PAIR) {  // the window moves up two levels
+        cs.om_below = cs.om_up; cs.om_cur = o2; cs.om_up = o3;
+        return;
     }
     cs.wet_below = wc;
     // the mixed-layer window moves up one level
@@ -180,9 +241,11 @@ __device__ __forceinline__ void ff_count_level(const FfCountArgs &cnt, FfCountSt
 
 // Before the march: the column's mixed-layer depth, the window at the deepest level and -- depth slab with a halo level below -- that
 // level's wet flag and its place in the mixed layer.
+template <bool PAIR = false>
 __device__ __forceinline__ void ff_count_begin(const FfCountArgs &cnt, FfCountState &cs, const uint8_t *__restrict__ wet, unsigned s, i64 P, int nz) {
     cs.mld = cnt.mlotst[s];
     cs.om_cur = ff_level_f64(cs.zt_lo, cs.zt_hi, nz - 1 + (int)cs.ha) < cs.mld;
+    if (PAIR) cs.om_up = ff_level_f64(cs.zt_lo, cs.zt_hi, nz >= 2 ? nz - 2 : 0) < cs.mld;  // (whole grids only: no halo levels)
     if (cs.hb) {  // (uniform)
         cs.wet_below = (wet[(i64)nz * P + s] & WF_C) != 0;
         cs.om_below = ff_level_f64(cs.zt_lo, cs.zt_hi, nz + (int)cs.ha) < cs.mld;
@@ -190,42 +253,67 @@ __device__ __forceinline__ void ff_count_begin(const FfCountArgs &cnt, FfCountSt
 }
 
 // load_vs (wave-uniform): false when the wave's south row comes from the neighbouring wave through LDS (ff_south_from_lds)
-template <typename T, bool FLAGS, bool COUNTS = false>
+// Two levels per wave: the step whose lanes 0-31 are at level ks.  The level base stays wave-uniform -- level kb = ks - 1, where lanes
+// 32-63 are -- and lanes 0-31 add one plane to their offsets (d; (s + P) * 8 < 2^32 since P < 2^28).  Clamped as ff_load clamps: a step
+// above the surface reads level 0, and so do lanes 32-63 of the step ks == 0 (nz odd), which have no level.
+__device__ __forceinline__ void ff_pair_level(int ks, bool up, i64 P, int &kb, unsigned &d) {
+    kb = ks >= 1 ? ks - 1 : 0;
+    d = (ks >= 1 && !up) ? (unsigned)P : 0u;
+}
+
+// PAIR: chunk entry q is the step k0 - 2 q (ff_pair_level), and wup the lane's own flag byte at the step after the chunk
+template <typename T, bool FLAGS, bool COUNTS = false, bool PAIR = false>
 __device__ __forceinline__ void ff_load(FfChunk<T> &c, const T *__restrict__ umo, const T *__restrict__ vmo,
                                         const uint8_t *__restrict__ wet, const FfCol &col, i64 P, int k0, bool load_vs = true,
-                                        bool load_vn = false, int kup_min = 0) {
+                                        bool load_vn = false, int kup_min = 0, bool up = false) {
 #pragma unroll
     for (int q = 0; q < FF_KB; ++q) {
-        const int k = (k0 - q >= 0) ? k0 - q : 0;  // clamped: loads are unconditional, the level is skipped later
+        int k = (k0 - q >= 0) ? k0 - q : 0;  // clamped: loads are unconditional, the level is skipped later
+        unsigned d = 0;
+        if (PAIR) ff_pair_level(k0 - 2 * q, up, P, k, d);
         const T *ul = umo + (i64)k * P, *vl = vmo + (i64)k * P;
         const uint8_t *wl = wet + (i64)k * P;
-        c.u[q] = ff_ld(ul, col.s); c.v[q] = ff_ld(vl, col.s);
-        c.uw[q] = ff_ld(ul, col.sW);
-        if (load_vs) c.vs[q] = ff_ld(vl, col.cS);
-        c.wc[q] = ff_ld(wl, col.s);
-        if (COUNTS && load_vn) c.vn[q] = ff_ld(vl, col.cN);
+        c.u[q] = ff_ld(ul, col.s + d); c.v[q] = ff_ld(vl, col.s + d);
+        c.uw[q] = ff_ld(ul, col.sW + d);
+        if (load_vs) c.vs[q] = ff_ld(vl, col.cS + d);
+        c.wc[q] = ff_ld(wl, col.s + d);
+        if (COUNTS && load_vn) c.vn[q] = ff_ld(vl, col.cN + d);
         if (!FLAGS) {
-            c.wE[q] = ff_ld(wl, col.sE); c.wW[q] = ff_ld(wl, col.sW); c.wS[q] = ff_ld(wl, col.cS);
-            c.wN[q] = ff_ld(wl, col.cN);
+            c.wE[q] = ff_ld(wl, col.sE + d); c.wW[q] = ff_ld(wl, col.sW + d); c.wS[q] = ff_ld(wl, col.cS + d);
+            c.wN[q] = ff_ld(wl, col.cN + d);
         }
     }
     if (COUNTS) {  // the wet flag above the chunk's last level (the next chunk's first level: not waited for here)
-        const int ku = (k0 - FF_KB >= 0) ? k0 - FF_KB : kup_min;  // (kup_min = -1: the halo level above a depth slab)
-        c.wup = ff_ld(wet + (i64)ku * P, col.s);
+        int ku = (k0 - FF_KB >= 0) ? k0 - FF_KB : kup_min;  // (kup_min = -1: the halo level above a depth slab)
+        unsigned d = 0;
+        if (PAIR) ff_pair_level(k0 - 2 * FF_KB, up, P, ku, d);
+        c.wup = ff_ld(wet + (i64)ku * P, col.s + d);
     }
 }
 
-template <typename T, bool FLAGS, bool NT, bool COUNTS = false, bool TOPONLY = false>
-__device__ __forceinline__ void ff_levels(const FfChunk<T> &c, const FfCol &col, i64 P, int k0, double fill, double &topbelow,
+// PAIR (two levels per wave, ff_pair_level): every lane does the level's work for its own (column, level); only the recurrence crosses the
+// halves.  topbelow is then meaningful in lanes 0-31 alone: lanes 32-63 take their ϕbottom from the lower half's ϕtop of the same step.
+template <typename T, bool FLAGS, bool NT, bool COUNTS = false, bool TOPONLY = false, bool PAIR = false>
+__device__ __forceinline__ void ff_levels(const FfChunk<T> &c, const FfCol &colu, i64 P, int k0, double fill, double &topbelow,
                                           bool &uvalid, bool &vvalid, double *__restrict__ east, double *__restrict__ west,
                                           double *__restrict__ north, double *__restrict__ south, double *__restrict__ top,
-                                          double *__restrict__ bottom, uint16_t *__restrict__ push_mask, bool active,
-                                          const FfCountArgs &cnt, FfCountState &cs, int nz) {
+                                          double *__restrict__ bottom, uint16_t *__restrict__ push_mask, bool lane_active,
+                                          const FfCountArgs &cnt, FfCountState &cs, int nz, bool up = false) {
     static_assert(!COUNTS || FLAGS, "the counts read the five-flag byte");
+    static_assert(!PAIR || COUNTS, "two levels per wave: counting calls only");
 #pragma unroll
     for (int q = 0; q < FF_KB; ++q) {
-        const int k = k0 - q;
+        int k = PAIR ? k0 - 2 * q : k0 - q;  // (PAIR: the level of lanes 0-31)
         if (k >= 0) {
+            FfCol col = colu;
+            bool active = lane_active;
+            const int ks = k, km = k - (int)up;  // (PAIR) the step, and the lane's own level: -1 for lanes 32-63 of the step 0, which store and count nothing
+            if (PAIR) {
+                unsigned d;
+                ff_pair_level(ks, up, P, k, d);
+                col.s += d;
+                active = lane_active && km >= 0;
+            }
             // (every lane computes: lanes beyond the row / rows beyond the grid of a four-row workgroup, and lanes beyond the plane of a counting
             // kernel, march along on clamped -- valid -- addresses; only their STORES and their validity flags are switched off.  A branch around
             // the arithmetic cost a save / restore of the execution mask and six zero-initialised doubles per level.)
@@ -249,7 +337,8 @@ __device__ __forceinline__ void ff_levels(const FfChunk<T> &c, const FfCol &col,
             double vs = (double)c.vs[q];
             if (!wS || !wc) vs = 0.0;
             const double so = col.hS ? ff_replace(vs, fill) : 0.0;
-            const double b = topbelow;                  // :238-240
+            double b = topbelow;                        // :238-240
+            if (PAIR) b = ff_up_from_low(topbelow, (((topbelow + w) + so) - e) - n);  // lanes 32-63: ϕtop of the level below, from the lane that has just formed it
             const double t = (((b + w) + so) - e) - n;  // :242
             if (active) {
                 if (!TOPONLY) {
@@ -259,8 +348,18 @@ __device__ __forceinline__ void ff_levels(const FfChunk<T> &c, const FfCol &col,
                 ff_st<NT>(top + o, col.s, t);  // (TOPONLY -- the fused step, otmb_step_dev: the other five are re-derived by the fill pass from umo / vmo / ϕtop)
                 if (push_mask && !COUNTS) ff_st<false>(push_mask + o, col.s, (uint16_t)otmb_push_bits(w, e, so, n, b, t, wc));
             }
-            topbelow = t;
-            if (COUNTS) {
+            topbelow = PAIR ? ff_low_from_up(t) : t;  // (PAIR: lanes 0-31 go on from the upper half's ϕtop, two levels up)
+            if (COUNTS && PAIR) {
+                // One exchange of two flag bytes: the cell above lanes 0-31 is the upper half's own cell, the cell above lanes 32-63 the lower
+                // half's cell of the NEXT step; and the cell below lanes 32-63 is the lower half's own, which also lies below lanes 0-31 next step.
+                const unsigned fnext = (q + 1 < FF_KB) ? c.wc[q + 1] : c.wup;
+                const unsigned y = ff_other_half(f | (fnext << 8), up);
+                const bool w_other = (y & WF_C) != 0;
+                if (up) cs.wet_below = w_other;
+                ff_count_level<true>(cnt, cs, km, nz, wc, f, up ? (y >> 8) & 0xffu : y & 0xffu, e, w, so, n, b, t, cs.has_fold ? (double)c.vn[q] : 0.0,
+                                     fill, ks, up);
+                if (!up) cs.wet_below = w_other;
+            } else if (COUNTS) {
                 // the cell above (level k - 1; at k == 0 it is the halo level above a depth slab -- c.wup -- or unused)
                 const unsigned fa = (q + 1 < FF_KB && k > 0) ? c.wc[q + 1] : c.wup;
                 ff_count_level(cnt, cs, k, nz, wc, f, fa, e, w, so, n, b, t, cs.has_fold ? (double)c.vn[q] : 0.0, fill);
@@ -433,6 +532,86 @@ __global__ __launch_bounds__(FF_THREADS * ROWS) __attribute__((amdgpu_waves_per_
     if (__any(vvalid) && (threadIdx.x & 63) == 0 && uv[1] != gen) atomicExch(&uv[1], gen);
 }
 
+// Two levels per wave, for grids with so few columns that the length of a wave's march bounds the kernel (1 degree: 1688 waves of 64
+// columns, 1.65 per SIMD, each a chain over 50 levels).  A workgroup is one wave over 32 consecutive columns of the plane: lanes 0-31 take
+// level k, lanes 32-63 the same columns at level k - 1, k = nz - 1, nz - 3, ...: twice the waves, half the steps.  Per step only the
+// recurrence is sequential -- the lower half forms its ϕtop, hands it up as the upper half's ϕbottom, the upper half forms its own and
+// hands it down for the next step -- by v_permlane32_swap, no LDS and no barrier; association and stored values are those of
+// facefluxes_kernel.  Whole planes of whole grids with counts only (no row band, no depth slab), table geometry FF_GEOM_PAIR.
+#define FF_GEOM_PAIR 2  // count-table geometry: wave segments of 32 consecutive columns (the other two: rows per workgroup, 1 and 4)
+#define FF_PAIR_COLS 32
+template <typename T, bool NT, bool TOPONLY>
+__global__ __launch_bounds__(FF_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void facefluxes_pair_kernel(
+    const T *__restrict__ umo, const T *__restrict__ vmo, const uint8_t *__restrict__ wet, double fill, int nx, int ny, int nz, int topo, i64 P,
+    double *__restrict__ east, double *__restrict__ west, double *__restrict__ north, double *__restrict__ south, double *__restrict__ top,
+    double *__restrict__ bottom, int *uv, int gen, int xcd_chunks,
+    const uint32_t *__restrict__ c_bases, const double *__restrict__ c_mlotst, const double *__restrict__ c_zt, unsigned long long *c_sums,
+    int c_upwind, int c_only_t, int c_nseg) {
+    FfCountArgs cnt;
+    cnt.bases = c_bases; cnt.mlotst = c_mlotst; cnt.zt = c_zt; cnt.sums = c_sums; cnt.upwind = c_upwind; cnt.only_t = c_only_t; cnt.nseg = c_nseg;
+    cnt.halo = 0;
+    unsigned cb = blockIdx.x;  // XCD x takes the x-th contiguous eighth of the column blocks, as in facefluxes_kernel
+    if (xcd_chunks) {
+        const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, x = blockIdx.x % 8, y = blockIdx.x / 8;
+        cb = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + y;
+    }
+    const unsigned lane = threadIdx.x;
+    const bool up = lane >= FF_PAIR_COLS;
+    unsigned s = cb * FF_PAIR_COLS + (lane & (FF_PAIR_COLS - 1));
+    const bool inside = s < (unsigned)P;
+    if (!inside) s = (unsigned)P - 1;  // lanes beyond the plane march along on the last column and store nothing
+    const unsigned j = s / (unsigned)nx, i = s - j * (unsigned)nx;
+    bool uvalid = false, vvalid = false;
+    FfCountState cs;
+    cs.mld = 0.0; cs.base_lo = cs.base_hi = 0; cs.zt_lo = cs.zt_hi = 0.0; cs.om_cur = cs.om_below = cs.om_up = false; cs.wet_below = false;
+    cs.ha = cs.hb = false;
+    cs.seg = cb;
+    cs.act = inside;
+    cs.fold = inside && topo == OTMB_TRIPOLAR && j + 1 == (unsigned)ny;
+    cs.has_fold = __builtin_amdgcn_ballot_w64(cs.fold) != 0;
+    const unsigned ifd = (unsigned)nx - 1 - i, ie = (i + 1 < (unsigned)nx) ? i + 1 : 0, iw = (i > 0) ? i - 1 : (unsigned)nx - 1;
+    cs.amask = cs.fold ? ((ifd == ie) ? (unsigned)WF_E : ((ifd == iw) ? (unsigned)WF_W : 0u)) : 0u;
+    cs.aclear = cs.fold && (ifd == ie || ifd == iw || ifd == i);
+    if (cnt.bases[0] == FFC_HEADER(FF_GEOM_PAIR, cnt.nseg)) {  // (uniform) this wave's table entries, one level per lane (nz <= FFC_MAX_NZ, checked on the host)
+        const unsigned l0 = (lane < (unsigned)nz) ? lane : (unsigned)nz - 1, l1 = (64 + lane < (unsigned)nz) ? 64 + lane : (unsigned)nz - 1;
+        const uint32_t *mine = cnt.bases + 1 + (size_t)cs.seg * (size_t)nz;
+        cs.base_lo = mine[l0]; cs.base_hi = mine[l1];
+    } else {  // a table for another wave geometry (it may be shorter: not read): count nothing, and say so
+        if (lane == 0) __hip_atomic_fetch_or(cnt.sums, FFC_BAD_TABLE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        cs.act = false;
+    }
+    {
+        const int zmax = nz - 1, z0 = (int)lane, z1 = 64 + (int)lane;
+        cs.zt_lo = cnt.zt[z0 < zmax ? z0 : zmax]; cs.zt_hi = cnt.zt[z1 < zmax ? z1 : zmax];
+    }
+    const unsigned row = j * (unsigned)nx;
+    FfCol col;
+    col.s = s;
+    col.sE = row + ((i + 1 < (unsigned)nx) ? i + 1 : 0);
+    col.sW = row + ((i > 0) ? i - 1 : nx - 1);
+    col.hS = j > 0;
+    const bool fold = (j + 1 >= (unsigned)ny) && (topo == OTMB_TRIPOLAR);
+    col.hN = (j + 1 < (unsigned)ny) || fold;
+    col.cS = col.hS ? s - nx : s;
+    col.cN = (j + 1 < (unsigned)ny) ? s + nx : (fold ? row + (nx - 1 - i) : s);
+    double topbelow = 0.0;  // seafloor ϕbottom (:238)
+    ff_count_begin<true>(cnt, cs, wet, s, P, nz);
+    FfChunk<T> A, B;
+    int k0 = nz - 1;
+    ff_load<T, true, true, true>(A, umo, vmo, wet, col, P, k0, true, cs.has_fold, 0, up);
+    while (k0 >= 0) {
+        ff_load<T, true, true, true>(B, umo, vmo, wet, col, P, k0 - 2 * FF_KB, true, cs.has_fold, 0, up);
+        ff_levels<T, true, NT, true, TOPONLY, true>(A, col, P, k0, fill, topbelow, uvalid, vvalid, east, west, north, south, top, bottom, nullptr, inside, cnt, cs, nz, up);
+        k0 -= 2 * FF_KB;
+        if (k0 < 0) break;
+        ff_load<T, true, true, true>(A, umo, vmo, wet, col, P, k0 - 2 * FF_KB, true, cs.has_fold, 0, up);
+        ff_levels<T, true, NT, true, TOPONLY, true>(B, col, P, k0, fill, topbelow, uvalid, vvalid, east, west, north, south, top, bottom, nullptr, inside, cnt, cs, nz, up);
+        k0 -= 2 * FF_KB;
+    }
+    if (__any(uvalid) && lane == 0 && uv[0] != gen) atomicExch(&uv[0], gen);
+    if (__any(vvalid) && lane == 0 && uv[1] != gen) atomicExch(&uv[1], gen);
+}
+
 // one thread per cell: the cell's wet byte and those of its east / west / south / north neighbours (periodic in i, closed in
 // j, tripolar fold at j == ny: src/gridtopology.jl:57-65,94) folded into one byte
 __global__ __launch_bounds__(256) void wetflags_kernel(const uint8_t *__restrict__ wet, int nx, int ny, i64 P, i64 G, int topo,
@@ -456,8 +635,19 @@ static int ff_rows_for(const otmb_ctx *ctx, i64 nx, i64 ny) {
     const i64 P = nx * ny;
     return ctx->ff_rows > 0 ? (ctx->ff_rows >= 4 ? 4 : 1) : ((P >= (1ll << 19) && nx >= 2 * FF_THREADS) ? 4 : 1);
 }
-// wave segments per level: what one wave of facefluxes_kernel covers at one level (64 consecutive cells of the plane, or of one row)
+// The wave geometry of a grid's counting calls, which is also the geometry of its count tables: 1 or 4 (rows per workgroup of
+// facefluxes_kernel), or FF_GEOM_PAIR -- facefluxes_pair_kernel -- on whole grids (not depth slabs: their tables keep the row geometry,
+// so that their calls go on counting) of two levels or more whose ceil(P / 32) waves are all resident at once, four per SIMD
+// (1 degree: 3375 against 4096).  ctx->ff_pairs (OTMB_FF_PAIRS): 0 never, 1 whatever the size.
+static int ff_geom_for(const otmb_ctx *ctx, i64 nx, i64 ny, i64 nz, bool slab = false) {
+    const int rows = ff_rows_for(ctx, nx, ny);
+    if (rows != 1 || slab || nz < 2 || ctx->ff_pairs == 0) return rows;
+    if (ctx->ff_pairs > 0) return FF_GEOM_PAIR;
+    return (nx * ny + FF_PAIR_COLS - 1) / FF_PAIR_COLS <= (i64)16 * ctx->n_cu ? FF_GEOM_PAIR : rows;
+}
+// wave segments per level: what one wave covers at one level (64 consecutive cells of the plane, or of one row; FF_GEOM_PAIR: what half a wave covers, 32 cells of the plane)
 static i64 ff_nseg(int rows, i64 nx, i64 ny) {
+    if (rows == FF_GEOM_PAIR) return (nx * ny + FF_PAIR_COLS - 1) / FF_PAIR_COLS;
     return rows == 1 ? (nx * ny + FF_THREADS - 1) / FF_THREADS : ((nx + FF_THREADS - 1) / FF_THREADS) * ny;
 }
 
@@ -472,7 +662,10 @@ __global__ __launch_bounds__(256) void ff_count_bases_kernel(const i64 *__restri
     const i64 k = gw / nseg, seg = gw - k * nseg;
     i64 s;
     bool valid;
-    if (rows == 1) {
+    if (rows == FF_GEOM_PAIR) {
+        s = seg * FF_PAIR_COLS + lane;
+        valid = lane < FF_PAIR_COLS && s < P;
+    } else if (rows == 1) {
         s = seg * FF_THREADS + lane;
         valid = s < P;
     } else {
@@ -547,7 +740,11 @@ static int32_t facefluxes_impl(otmb_ctx *ctx, const void *umo, const void *vmo, 
     }
     int *dflags = otmb_ring_ff((int *)ctx->ring.p, ctx->ff_gen);
     const int rows = ff_rows_for(ctx, nx, ny);
-    const unsigned nb = rows == 1 ? (unsigned)(((j1 - j0) * nx + FF_THREADS - 1) / FF_THREADS)
+    // two levels per wave: whole planes of whole grids with counts (anything else on such a grid keeps today's kernels)
+    const bool pair = counts && !slab && !top_below && j0 == 0 && j1 == ny && ff_geom_for(ctx, nx, ny, nz) == FF_GEOM_PAIR;
+    const int geom = pair ? FF_GEOM_PAIR : rows;
+    ctx->ff_pairs_last = pair ? 1 : 0;
+    const unsigned nb = pair ? (unsigned)((P + FF_PAIR_COLS - 1) / FF_PAIR_COLS) : rows == 1 ? (unsigned)(((j1 - j0) * nx + FF_THREADS - 1) / FF_THREADS)
                                   : (unsigned)(((nx + FF_THREADS - 1) / FF_THREADS) * ((j1 - j0 + rows - 1) / rows));
     // any facefluxes call on this context ends the validity of counts an earlier call left behind (they are keyed to ff_gen), and a full
     // mask written over a partial one makes that array an ordinary push mask again
@@ -580,12 +777,12 @@ static int32_t facefluxes_impl(otmb_ctx *ctx, const void *umo, const void *vmo, 
         ca.bases = (const uint32_t *)counts->tables; ca.mlotst = counts->mlotst; ca.zt = counts->zt + k_own0;
         ca.sums = (unsigned long long *)ctx->ffc_sums[buf].p;
         ca.upwind = counts->upwind; ca.only_t = counts->only_t;
-        ca.nseg = (int)ff_nseg(rows, nx, ny);
+        ca.nseg = (int)ff_nseg(geom, nx, ny);
         ca.halo = (k_own0 > 0 ? 1 : 0) | (k_own0 + nz < nz_ext ? 2 : 0);
         otmb_ctx::FfCountsKey &key = ctx->ffc;
         key.buf = buf; key.gen = ctx->ff_gen;
         for (int f = 0; f < 6; ++f) key.phi[f] = phi[f];
-        key.stat = (const char *)counts->tables + ff_tables_static_offset(rows, nx, ny, nz);
+        key.stat = (const char *)counts->tables + ff_tables_static_offset(geom, nx, ny, nz);
         key.mask = push_mask; key.mlotst = counts->mlotst; key.zt = counts->zt; key.lwet3d = counts->lwet3d;
         key.nx = nx; key.ny = ny; key.nz = nz_ext; key.n_wet = counts->n_wet;
         key.k_own0 = k_own0; key.wet_base = slab ? slab->wet_base : 0;
@@ -595,7 +792,9 @@ static int32_t facefluxes_impl(otmb_ctx *ctx, const void *umo, const void *vmo, 
     }
     {
     KernelTimer kt(ctx, K_FACEFLUXES);
-    const bool nt = ctx->ff_nt >= 0 ? ctx->ff_nt != 0 : (i64)48 * P * nz > (1ll << 30);  // six Float64 arrays beyond a gigabyte: streaming stores
+    // six Float64 arrays beyond a gigabyte: streaming stores.  The pair kernel always: its waves write two planes of every array at a time, and
+    // with plain stores those twelve streams cost it more than the shorter march gains (1 degree: 85.5 us against 64.9 us, profiles/r15)
+    const bool nt = ctx->ff_nt >= 0 ? ctx->ff_nt != 0 : (pair || (i64)48 * P * nz > (1ll << 30));
 #define FF_LAUNCH(T, FL, NTS, R, CN)                                                                                                   \
     FF_LAUNCH_T(T, FL, NTS, R, CN, false)
 #define FF_LAUNCH_T(T, FL, NTS, R, CN, TO)                                                                                             \
@@ -607,10 +806,20 @@ static int32_t facefluxes_impl(otmb_ctx *ctx, const void *umo, const void *vmo, 
                                    else { if (nt) FF_LAUNCH(T, FL, true, 1, CN); else FF_LAUNCH(T, FL, false, 1, CN); } } while (0)
 #define FF_LAUNCH2T(T) do { if (rows == 4) { if (nt) FF_LAUNCH_T(T, true, true, 4, true, true); else FF_LAUNCH_T(T, true, false, 4, true, true); } \
                             else { if (nt) FF_LAUNCH_T(T, true, true, 1, true, true); else FF_LAUNCH_T(T, true, false, 1, true, true); } } while (0)
-    if (with_counts && top_only) { if (src_is_f32) FF_LAUNCH2T(float); else FF_LAUNCH2T(double); }
+#define FF_LAUNCH_PAIR(T, NTS, TO)                                                                                                    \
+    hipLaunchKernelGGL((facefluxes_pair_kernel<T, NTS, TO>), dim3(nb), dim3(FF_THREADS), 0, ctx->stream, (const T *)umo, (const T *)vmo, wet3d, \
+                       fill, (int)nx, (int)ny, (int)nz, (int)topology, P, phi[OTMB_EAST], phi[OTMB_WEST], phi[OTMB_NORTH],           \
+                       phi[OTMB_SOUTH], phi[OTMB_TOP], phi[OTMB_BOTTOM], dflags, ctx->ff_gen, ctx->ff_xcd_chunks, ca.bases, ca.mlotst,  \
+                       ca.zt, ca.sums, ca.upwind, ca.only_t, ca.nseg)
+#define FF_LAUNCH_PAIR2(T) do { if (top_only) { if (nt) FF_LAUNCH_PAIR(T, true, true); else FF_LAUNCH_PAIR(T, false, true); } \
+                                else { if (nt) FF_LAUNCH_PAIR(T, true, false); else FF_LAUNCH_PAIR(T, false, false); } } while (0)
+    if (pair) { if (src_is_f32) FF_LAUNCH_PAIR2(float); else FF_LAUNCH_PAIR2(double); }
+    else if (with_counts && top_only) { if (src_is_f32) FF_LAUNCH2T(float); else FF_LAUNCH2T(double); }
     else if (with_counts) { if (src_is_f32) FF_LAUNCH2(float, true, true); else FF_LAUNCH2(double, true, true); }
     else if (src_is_f32) { if (flags) FF_LAUNCH2(float, true, false); else FF_LAUNCH2(float, false, false); }
     else { if (flags) FF_LAUNCH2(double, true, false); else FF_LAUNCH2(double, false, false); }
+#undef FF_LAUNCH_PAIR2
+#undef FF_LAUNCH_PAIR
 #undef FF_LAUNCH2T
 #undef FF_LAUNCH2
 #undef FF_LAUNCH_T
@@ -679,19 +888,21 @@ extern "C" int32_t otmb_facefluxes_flags_dev(otmb_ctx *ctx, const void *umo, con
 extern "C" int64_t otmb_count_tables_bytes(const otmb_ctx *ctx, int64_t nx, int64_t ny, int64_t nz, int64_t n_wet) {
     if (!ctx || nx < 1 || ny < 1 || nz < 1 || n_wet < 0) return 0;
     const i64 ntiles = (n_wet + (1ll << FFC_TILE_SHIFT) - 1) >> FFC_TILE_SHIFT;
-    return (int64_t)(ff_tables_static_offset(ff_rows_for(ctx, nx, ny), nx, ny, nz) + (size_t)(ntiles + 1) * sizeof(unsigned long long));
+    // (a depth slab's table keeps the row geometry and is never the longer one: one size serves both builders)
+    return (int64_t)(ff_tables_static_offset(ff_geom_for(ctx, nx, ny, nz), nx, ny, nz) + (size_t)(ntiles + 1) * sizeof(unsigned long long));
 }
 
 // nz levels from level k_own0 of a local grid of nz_ext levels (the whole grid: 0, nz); wet_base: the global 0-based wet rank of the first
 // owned wet cell.  lwet3d / wetflags: the local grid's arrays; lwet: the owned cells' local linear indices.
 static int32_t count_tables_impl(otmb_ctx *ctx, const int64_t *lwet3d, const int64_t *lwet, const uint8_t *wetflags, int64_t n_wet, int64_t nx,
-                                 int64_t ny, int64_t nz, int32_t topology, int64_t k_own0, int64_t nz_ext, int64_t wet_base, void *tables) {
+                                 int64_t ny, int64_t nz, int32_t topology, int64_t k_own0, int64_t nz_ext, int64_t wet_base, void *tables,
+                                 bool slab = false) {
     if (!ctx || !lwet3d || !wetflags || !tables || (n_wet > 0 && !lwet)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
     if (nx < 1 || ny < 1 || nz < 1 || n_wet < 0 || nx * ny >= (1ll << 28) || nx * ny * nz_ext >= (1ll << 32)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "grid size");
     if (k_own0 < 0 || k_own0 + nz > nz_ext || nz_ext > nz + 2 || wet_base < 0) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "depth slab");
     if (topology != OTMB_BIPOLAR && topology != OTMB_TRIPOLAR) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "topology");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int rows = ff_rows_for(ctx, nx, ny);
+    const int rows = ff_geom_for(ctx, nx, ny, nz, slab);
     const i64 nseg = ff_nseg(rows, nx, ny), nw = nz * nseg, ntiles = (n_wet + (1ll << FFC_TILE_SHIFT) - 1) >> FFC_TILE_SHIFT;
     KernelTimer kt(ctx, K_FF_BASES);
     hipLaunchKernelGGL(ff_count_bases_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, ctx->stream, (const i64 *)lwet3d + k_own0 * nx * ny,
@@ -711,7 +922,7 @@ extern "C" int32_t otmb_count_tables_dev(otmb_ctx *ctx, const int64_t *lwet3d, c
 extern "C" int32_t otmb_count_tables_slab_dev(otmb_ctx *ctx, const int64_t *lwet3d, const int64_t *lwet, const uint8_t *wetflags, int64_t n_wet,
                                               int64_t nx, int64_t ny, int64_t nz, int32_t topology, const otmb_ff_slab *slab, void *tables) {
     if (!slab) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
-    return count_tables_impl(ctx, lwet3d, lwet, wetflags, n_wet, nx, ny, nz, topology, slab->k_own0, slab->nz_ext, slab->wet_base, tables);
+    return count_tables_impl(ctx, lwet3d, lwet, wetflags, n_wet, nx, ny, nz, topology, slab->k_own0, slab->nz_ext, slab->wet_base, tables, true);
 }
 
 // facefluxes + the tile counts of the transportmatrix that will be built from its fluxes (see FfCountArgs).  Grids whose row-mates can
