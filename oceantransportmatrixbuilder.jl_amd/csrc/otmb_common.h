@@ -53,7 +53,6 @@ struct otmb_ctx {
     unsigned order_nheavy = 0;  // the order's first entries are this many heavy tiles (tripolar seam row), dealt over the XCDs
     int ff_xcd_chunks = 1;    // facefluxes: XCD x takes the x-th contiguous eighth of the column blocks (0 = blockIdx order; experiments: OTMB_FF_XCD)
     int ff_nt = -1;           // facefluxes' ϕ stores non-temporal (1), plain (0), by size (-1: beyond a gigabyte of fluxes) (experiments: OTMB_FF_NT)
-    int ff_lds_south = 1;     // four-row facefluxes workgroups take a wave's south row from the neighbouring wave through LDS (experiments: OTMB_FF_LDS_SOUTH)
     int ff_rows = 0;          // facefluxes: rows per workgroup, 1 or 4; 0 = by grid size (experiments: OTMB_FF_ROWS)
     int ff_pairs = -1;        // facefluxes: two levels per wave on whole-plane counting calls (facefluxes_pair_kernel): 1 wherever eligible, 0 never, -1 where all its waves are resident at once (OTMB_FF_PAIRS)
     int ff_pairs_last = -1;   // the last facefluxes call ran facefluxes_pair_kernel (1) or facefluxes_kernel (0); -1: none yet (otmb_ctx_ff_pairs)

@@ -77,7 +77,6 @@ int32_t otmb_ctx_create(int32_t device_id, otmb_ctx **out) {
     if (const char *e = getenv("OTMB_FF_ROWS")) c->ff_rows = atoi(e);
     if (const char *e = getenv("OTMB_FF_PAIRS")) c->ff_pairs = atoi(e) > 0 ? 1 : 0;
     if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess) c->n_cu = 0;
-    if (const char *e = getenv("OTMB_FF_LDS_SOUTH")) c->ff_lds_south = atoi(e);
     if (const char *e = getenv("OTMB_FF_NT")) c->ff_nt = atoi(e);
     if (const char *e = getenv("OTMB_COUNT_ORDER")) c->count_order = atoi(e);
     if (const char *e = getenv("OTMB_DEAL_HEAVY")) c->deal_heavy = atoi(e);

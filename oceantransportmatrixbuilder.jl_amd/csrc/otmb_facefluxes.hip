@@ -77,18 +77,18 @@ struct FfCountArgs {
 };
 #define FFC_MAX_NZ 128  // a wave keeps its per-level table entries and zt in registers, lane l = level l and level 64 + l
 struct FfCountState {
-    double mld;
-    unsigned seg;
-    unsigned base_lo, base_hi;  // lane l: 0-based wet rank of the first wet cell of this wave's segment at level l / 64 + l
-    double zt_lo, zt_hi;        // lane l: zt[l - ha] / zt[64 + l - ha] (ha = 1 when a halo level lies above: its depth is needed too)
-    bool ha, hb;                // (uniform) a halo level above the first / below the last level: depth slab of a deeper grid
-    bool om_cur, om_below;      // zt[k] < mlotst for the level being counted / the level below it (a window that moves up with the march)
-    bool om_up;                 // (two levels per wave) ... and for the level above it: lanes 32-63 are one level further up
-    unsigned amask;            // seam row: flag bit (E / W) of the row-mate the fold neighbour coincides with, else 0
-    bool aclear;               // seam row: the fold neighbour is the east / west row-mate or the cell itself: it has no slot of its own
-    bool fold;                 // the lane's cell is on the tripolar seam row
-    bool has_fold;             // (wave-uniform) so is some lane of this wave
-    bool act, wet_below;
+    double mld = 0.0;
+    unsigned seg = 0;
+    unsigned base_lo = 0, base_hi = 0;  // lane l: 0-based wet rank of the first wet cell of this wave's segment at level l / 64 + l
+    double zt_lo = 0.0, zt_hi = 0.0;    // lane l: zt[l - ha] / zt[64 + l - ha] (ha = 1 when a halo level lies above: its depth is needed too)
+    bool ha = false, hb = false;        // (uniform) a halo level above the first / below the last level: depth slab of a deeper grid
+    bool om_cur = false, om_below = false;  // zt[k] < mlotst for the level being counted / the level below it (a window that moves up with the march)
+    bool om_up = false;                 // (two levels per wave) ... and for the level above it: lanes 32-63 are one level further up
+    unsigned amask = 0;                 // seam row: flag bit (E / W) of the row-mate the fold neighbour coincides with, else 0
+    bool aclear = false;                // seam row: the fold neighbour is the east / west row-mate or the cell itself: it has no slot of its own
+    bool fold = false;                  // the lane's cell is on the tripolar seam row
+    bool has_fold = false;              // (wave-uniform) so is some lane of this wave
+    bool act = false, wet_below = false;
 };
 #define FFC_HEADER(rows, nseg) (((unsigned)(rows) << 28) ^ (unsigned)(nseg))
 __device__ __forceinline__ unsigned ff_mbcnt(u64 m) {
@@ -98,6 +98,16 @@ __device__ __forceinline__ bool ff_nonzero(double x) { return (x > 0.0) | (x < 0
 // the seam row's slot rule on a neighbour set: the fold neighbour's bit (N) moves onto the row-mate it coincides with, or vanishes
 // into the diagonal
 __device__ __forceinline__ unsigned ff_fold_alias(unsigned bits, unsigned amask) { return (bits & 16u) ? ((bits | amask) & ~16u) : bits; }
+// ... for the cell i of a seam row of nx cells: amask -- the flag bit (E / W) of the row-mate the fold cell nx - 1 - i coincides with, else
+// 0; aclear -- the fold cell is that row-mate or the cell itself (ff_fold_alias applies)
+struct FfSeamSlot { unsigned amask; bool aclear; };
+__device__ __forceinline__ FfSeamSlot ff_seam_slot(unsigned i, unsigned nx) {
+    const unsigned ifd = nx - 1 - i, ie = (i + 1 < nx) ? i + 1 : 0, iw = (i > 0) ? i - 1 : nx - 1;
+    FfSeamSlot sl;
+    sl.amask = (ifd == ie) ? (unsigned)WF_E : ((ifd == iw) ? (unsigned)WF_W : 0u);
+    sl.aclear = ifd == ie || ifd == iw || ifd == i;
+    return sl;
+}
 // Sum of one 32-bit value per lane over the wave (every lane active): four row_shr adds put each row's total in its last lane,
 // row_bcast:15 / :31 carry them to lane 63.
 __device__ __forceinline__ unsigned ff_wave_sum(unsigned v) {
@@ -241,7 +251,7 @@ __device__ __forceinline__ void ff_count_level(const FfCountArgs &cnt, FfCountSt
 
 // Before the march: the column's mixed-layer depth, the window at the deepest level and -- depth slab with a halo level below -- that
 // level's wet flag and its place in the mixed layer.
-template <bool PAIR = false>
+template <bool PAIR>
 __device__ __forceinline__ void ff_count_begin(const FfCountArgs &cnt, FfCountState &cs, const uint8_t *__restrict__ wet, unsigned s, i64 P, int nz) {
     cs.mld = cnt.mlotst[s];
     cs.om_cur = ff_level_f64(cs.zt_lo, cs.zt_hi, nz - 1 + (int)cs.ha) < cs.mld;
@@ -252,7 +262,6 @@ __device__ __forceinline__ void ff_count_begin(const FfCountArgs &cnt, FfCountSt
     }
 }
 
-// load_vs (wave-uniform): false when the wave's south row comes from the neighbouring wave through LDS (ff_south_from_lds)
 // Two levels per wave: the step whose lanes 0-31 are at level ks.  The level base stays wave-uniform -- level kb = ks - 1, where lanes
 // 32-63 are -- and lanes 0-31 add one plane to their offsets (d; (s + P) * 8 < 2^32 since P < 2^28).  Clamped as ff_load clamps: a step
 // above the surface reads level 0, and so do lanes 32-63 of the step ks == 0 (nz odd), which have no level.
@@ -262,10 +271,10 @@ __device__ __forceinline__ void ff_pair_level(int ks, bool up, i64 P, int &kb, u
 }
 
 // PAIR: chunk entry q is the step k0 - 2 q (ff_pair_level), and wup the lane's own flag byte at the step after the chunk
-template <typename T, bool FLAGS, bool COUNTS = false, bool PAIR = false>
+template <typename T, bool FLAGS, bool COUNTS, bool PAIR>
 __device__ __forceinline__ void ff_load(FfChunk<T> &c, const T *__restrict__ umo, const T *__restrict__ vmo,
-                                        const uint8_t *__restrict__ wet, const FfCol &col, i64 P, int k0, bool load_vs = true,
-                                        bool load_vn = false, int kup_min = 0, bool up = false) {
+                                        const uint8_t *__restrict__ wet, const FfCol &col, i64 P, int k0, bool load_vs,
+                                        bool load_vn, int kup_min, bool up) {
 #pragma unroll
     for (int q = 0; q < FF_KB; ++q) {
         int k = (k0 - q >= 0) ? k0 - q : 0;  // clamped: loads are unconditional, the level is skipped later
@@ -293,12 +302,12 @@ __device__ __forceinline__ void ff_load(FfChunk<T> &c, const T *__restrict__ umo
 
 // PAIR (two levels per wave, ff_pair_level): every lane does the level's work for its own (column, level); only the recurrence crosses the
 // halves.  topbelow is then meaningful in lanes 0-31 alone: lanes 32-63 take their ϕbottom from the lower half's ϕtop of the same step.
-template <typename T, bool FLAGS, bool NT, bool COUNTS = false, bool TOPONLY = false, bool PAIR = false>
+template <typename T, bool FLAGS, bool NT, bool COUNTS, bool TOPONLY, bool PAIR>
 __device__ __forceinline__ void ff_levels(const FfChunk<T> &c, const FfCol &colu, i64 P, int k0, double fill, double &topbelow,
                                           bool &uvalid, bool &vvalid, double *__restrict__ east, double *__restrict__ west,
                                           double *__restrict__ north, double *__restrict__ south, double *__restrict__ top,
                                           double *__restrict__ bottom, uint16_t *__restrict__ push_mask, bool lane_active,
-                                          const FfCountArgs &cnt, FfCountState &cs, int nz, bool up = false) {
+                                          const FfCountArgs &cnt, FfCountState &cs, int nz, bool up) {
     static_assert(!COUNTS || FLAGS, "the counts read the five-flag byte");
     static_assert(!PAIR || COUNTS, "two levels per wave: counting calls only");
 #pragma unroll
@@ -368,14 +377,105 @@ __device__ __forceinline__ void ff_levels(const FfChunk<T> &c, const FfCol &colu
     }
 }
 
+// ---- a wave's set-up, written once for facefluxes_kernel and facefluxes_pair_kernel ----------------------------------------------------
+// Workgroups are dealt round-robin over the 8 XCDs (each with its own L2).  In blockIdx order a wave's south row
+// (vmo[s - nx], nx / 64 blocks back) and the west cell of its first lane (the previous block) belong to workgroups of OTHER XCDs:
+// every XCD's L2 then fetches vmo twice and a quarter of umo again (profiles/r03: 3.27 GB fetched for 1.98 GB of inputs at
+// 0.25 degree).  Give XCD x the x-th contiguous eighth of the column blocks instead, as the fill pass does: those neighbours
+// are then lines the same L2 has just fetched.  Speed only: any bijection of the blocks is correct.
+__device__ __forceinline__ unsigned ff_xcd_block(int xcd_chunks) {
+    if (!xcd_chunks) return blockIdx.x;
+    const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, x = blockIdx.x % 8, y = blockIdx.x / 8;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + y;
+}
+// column s = (i, j) of the plane -- the caller has clamped it into the grid -- and its neighbour columns
+__device__ __forceinline__ FfCol ff_col(unsigned s, unsigned i, unsigned j, int nx, int ny, int topo) {
+    const unsigned row = j * (unsigned)nx;
+    FfCol col;
+    col.s = s;
+    col.sE = row + ((i + 1 < (unsigned)nx) ? i + 1 : 0);  // i₊₁, gridtopology.jl:57
+    col.sW = row + ((i > 0) ? i - 1 : nx - 1);            // i₋₁, :58
+    col.hS = j > 0;                                        // j₋₁, :63
+    const bool fold = (j + 1 >= (unsigned)ny) && (topo == OTMB_TRIPOLAR);
+    col.hN = (j + 1 < (unsigned)ny) || fold;               // j₊₁, :62; tripolar fold :94
+    col.cS = col.hS ? s - nx : s;                          // clamped neighbour columns: loads stay unconditional
+    col.cN = (j + 1 < (unsigned)ny) ? s + nx : (fold ? row + (nx - 1 - i) : s);
+    return col;
+}
+// (COUNTS) the lane's part in the counts: whether its column counts at all, and its place on the tripolar seam row
+__device__ __forceinline__ void ff_count_lane(FfCountState &cs, bool inside, unsigned i, unsigned j, int nx, int ny, int topo) {
+    cs.act = inside;
+    cs.fold = inside && topo == OTMB_TRIPOLAR && j + 1 == (unsigned)ny;
+    cs.has_fold = __builtin_amdgcn_ballot_w64(cs.fold) != 0;
+    const FfSeamSlot sl = ff_seam_slot(i, (unsigned)nx);
+    cs.amask = cs.fold ? sl.amask : 0u;
+    cs.aclear = cs.fold && sl.aclear;
+}
+// (COUNTS) this wave's table entries (segment cs.seg) and zt, one level per lane (nz <= FFC_MAX_NZ, checked on the host).  geom: the wave
+// geometry the table must have been built for; a table for another one may be shorter: it is not read, nothing is counted, and the sums
+// say so.  halo: FfCountArgs::halo -- zt of levels -ha ... nz - 1 + hb (a depth slab's halo levels take part in the mixed-layer test of
+// their neighbours, :85).
+__device__ __forceinline__ void ff_count_row(const FfCountArgs &cnt, FfCountState &cs, int geom, int nz, int halo) {
+    const unsigned lane = threadIdx.x & 63;
+    if (cnt.bases[0] == FFC_HEADER(geom, cnt.nseg)) {  // (uniform)
+        const unsigned l0 = (lane < (unsigned)nz) ? lane : (unsigned)nz - 1, l1 = (64 + lane < (unsigned)nz) ? 64 + lane : (unsigned)nz - 1;
+        const uint32_t *mine = cnt.bases + 1 + (size_t)cs.seg * (size_t)nz;
+        cs.base_lo = mine[l0]; cs.base_hi = mine[l1];
+    } else {
+        if (lane == 0) __hip_atomic_fetch_or(cnt.sums, FFC_BAD_TABLE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        cs.act = false;
+    }
+    cs.ha = (halo & 1) != 0; cs.hb = (halo & 2) != 0;
+    const int zmax = nz - 1 + (int)cs.hb, z0 = (int)lane - (int)cs.ha, z1 = 64 + (int)lane - (int)cs.ha;
+    cs.zt_lo = cnt.zt[z0 < zmax ? z0 : zmax]; cs.zt_hi = cnt.zt[z1 < zmax ? z1 : zmax];
+}
+
 // Software pipeline over chunks of FF_KB levels: while chunk A is turned into fluxes and stored, the loads of the
 // next chunk B are already in flight.  A column is one thread and the grid has few columns (1.7 waves per SIMD at
 // 1 degree), so nothing else hides the memory latency of a chunk.
+// PAIR (two levels per wave): a chunk is FF_KB steps of two levels.  topbelow: ϕbottom of the deepest level -- zero at the seafloor
+// (:238); for a depth slab that is not the deepest, the plane handed up by the slab below (its ϕtop at its first level) continues the
+// chain without re-association.  load_vs (wave-uniform): false when `hook` supplies the chunk's south row.  uv, gen: the validity words.
+// hook(chunk) runs once per chunk, between its loads and its levels, in every wave and the same number of times (ceil(nz / step)): it
+// may hold a workgroup barrier.  facefluxes_kernel<ROWS = 4> passes the exchange of the south row through LDS, the others nothing.
+template <typename T, bool FLAGS, bool NT, bool COUNTS, bool TOPONLY, bool PAIR, typename Hook>
+__device__ __forceinline__ void ff_march(const T *__restrict__ umo, const T *__restrict__ vmo, const uint8_t *__restrict__ wet, const FfCol &col,
+                                         i64 P, int nz, double fill, double topbelow, int *uv, int gen, double *__restrict__ east,
+                                         double *__restrict__ west, double *__restrict__ north, double *__restrict__ south,
+                                         double *__restrict__ top, double *__restrict__ bottom, uint16_t *__restrict__ push_mask,
+                                         bool lane_active, const FfCountArgs &cnt, FfCountState &cs, bool load_vs, bool up, Hook hook) {
+    constexpr int STEP = PAIR ? 2 * FF_KB : FF_KB;
+    bool uvalid = false, vvalid = false;
+    const int kup_min = (COUNTS && cs.ha) ? -1 : 0;
+    if (COUNTS) ff_count_begin<PAIR>(cnt, cs, wet, col.s, P, nz);
+    FfChunk<T> A, B;
+    int k0 = nz - 1;
+    ff_load<T, FLAGS, COUNTS, PAIR>(A, umo, vmo, wet, col, P, k0, load_vs, cs.has_fold, kup_min, up);
+    while (k0 >= 0) {
+        ff_load<T, FLAGS, COUNTS, PAIR>(B, umo, vmo, wet, col, P, k0 - STEP, load_vs, cs.has_fold, kup_min, up);
+        hook(A);
+        ff_levels<T, FLAGS, NT, COUNTS, TOPONLY, PAIR>(A, col, P, k0, fill, topbelow, uvalid, vvalid, east, west, north, south, top, bottom, push_mask, lane_active, cnt, cs, nz, up);
+        k0 -= STEP;
+        if (k0 < 0) break;
+        ff_load<T, FLAGS, COUNTS, PAIR>(A, umo, vmo, wet, col, P, k0 - STEP, load_vs, cs.has_fold, kup_min, up);
+        hook(B);
+        ff_levels<T, FLAGS, NT, COUNTS, TOPONLY, PAIR>(B, col, P, k0, fill, topbelow, uvalid, vvalid, east, west, north, south, top, bottom, push_mask, lane_active, cnt, cs, nz, up);
+        k0 -= STEP;
+    }
+    // "some value is valid" = the call's pair of words (ring slot gen % OTMB_RING) holds this call's number: no reset
+    // pass between calls, and the verdict on call g survives the next OTMB_RING - 1 calls
+    if (__any(uvalid) && (threadIdx.x & 63) == 0 && uv[0] != gen) atomicExch(&uv[0], gen);
+    if (__any(vvalid) && (threadIdx.x & 63) == 0 && uv[1] != gen) atomicExch(&uv[1], gen);
+}
+
 // ROWS: 1 = a workgroup is one wave, 64 consecutive columns of the (nx, ny) plane in linear order; 4 = a workgroup is four waves
 // over the SAME 64 values of i in four consecutive rows j: a wave's south row (vmo[s - nx]) is then the row of the wave next to it
-// in the same workgroup, marching through the same levels at the same time -- an L1 hit (or a ride on the fill already in flight)
-// instead of one more request to the L2 (4 of the ~14 read requests per level and wave).  Large grids only: the last chunk of a row
+// in the same workgroup, marching through the same levels at the same time.  Large grids only: the last chunk of a row
 // is partly idle (nx = 1440: 2 % more waves), and a grid with fewer waves than the chip has slots wants them spread singly.
+// The four waves pass the south row through LDS: wave r's south row IS wave r-1's own row, so every wave posts the vmo values of
+// its chunk in LDS and takes its south values from the wave below it -- no load at all for three waves out of four (the L1 kept
+// missing on them: the waves drift apart by more than it holds; profiles/r04/README.md section 4).  Every wave takes part in
+// the workgroup barriers, so lanes beyond the row and rows beyond the grid march along on clamped addresses and store nothing.
 #ifndef FF_COUNTS_WAVES
 #define FF_COUNTS_WAVES 1
 #endif
@@ -384,33 +484,25 @@ __global__ __launch_bounds__(FF_THREADS * ROWS) __attribute__((amdgpu_waves_per_
     const T *__restrict__ umo, const T *__restrict__ vmo, const uint8_t *__restrict__ wet, double fill, int nx,
     int ny, int nz, int topo, i64 P, double *__restrict__ east, double *__restrict__ west,
     double *__restrict__ north, double *__restrict__ south, double *__restrict__ top, double *__restrict__ bottom,
-    const double *__restrict__ top_below, uint16_t *__restrict__ push_mask, int *uv, int gen, int xcd_chunks, int lds_south,
+    const double *__restrict__ top_below, uint16_t *__restrict__ push_mask, int *uv, int gen, int xcd_chunks,
     int j_begin, int j_end,  // rows [j_begin, j_end) of the plane are computed (the whole plane: 0, ny; a piece: the chain over depth slabs, piece by piece)
     // (COUNTS) FfCountArgs, member by member: only a `const __restrict__` kernel argument lets the compiler read the wave-uniform table
     // entries and zt through the scalar cache -- as a vector load the table entry made every level wait for ALL outstanding vector memory
     // operations (s_waitcnt vmcnt(0)), i.e. for the next chunk's prefetch
     const uint32_t *__restrict__ c_bases, const double *__restrict__ c_mlotst, const double *__restrict__ c_zt, unsigned long long *c_sums,
     int c_upwind, int c_only_t, int c_nseg, int c_halo) {
-    FfCountArgs cnt;
-    cnt.bases = c_bases; cnt.mlotst = c_mlotst; cnt.zt = c_zt; cnt.sums = c_sums; cnt.upwind = c_upwind; cnt.only_t = c_only_t; cnt.nseg = c_nseg;
-    cnt.halo = c_halo;
-    // Workgroups are dealt round-robin over the 8 XCDs (each with its own L2).  In blockIdx order a wave's south row
-    // (vmo[s - nx], nx / 64 blocks back) and the west cell of its first lane (the previous block) belong to workgroups of OTHER XCDs:
-    // every XCD's L2 then fetches vmo twice and a quarter of umo again (profiles/r03: 3.27 GB fetched for 1.98 GB of inputs at
-    // 0.25 degree).  Give XCD x the x-th contiguous eighth of the column blocks instead, as the fill pass does: those neighbours
-    // are then lines the same L2 has just fetched.  Speed only: any bijection of the blocks is correct.
-    unsigned cb = blockIdx.x;
-    if (xcd_chunks) {
-        const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, x = blockIdx.x % 8, y = blockIdx.x / 8;
-        cb = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + y;
-    }
+    const FfCountArgs cnt = {c_bases, c_mlotst, c_zt, c_sums, c_upwind, c_only_t, c_nseg, c_halo};
+    const unsigned cb = ff_xcd_block(xcd_chunks);
     unsigned s, i, j, seg;
     bool inside;
     if (ROWS == 1) {
         seg = cb;  // (COUNTS: whole planes only, j_begin == 0)
         s = (unsigned)j_begin * (unsigned)nx + cb * FF_THREADS + threadIdx.x;
         inside = s < (unsigned)j_end * (unsigned)nx;
-        if (COUNTS && !inside) s = (unsigned)j_end * (unsigned)nx - 1;
+        if (!inside) {
+            if (!COUNTS) return;
+            s = (unsigned)j_end * (unsigned)nx - 1;  // every lane takes part in the wave sums: lanes beyond the plane march along on the last column and store nothing
+        }
         j = s / (unsigned)nx;
         i = s - j * (unsigned)nx;
     } else {
@@ -418,118 +510,35 @@ __global__ __launch_bounds__(FF_THREADS * ROWS) __attribute__((amdgpu_waves_per_
         i = chunk * FF_THREADS + (threadIdx.x & (FF_THREADS - 1));
         j = (unsigned)j_begin + grp * ROWS + threadIdx.x / FF_THREADS;
         inside = i < (unsigned)nx && j < (unsigned)j_end;
+        i = (i < (unsigned)nx) ? i : (unsigned)nx - 1;
+        j = (j < (unsigned)ny) ? j : (unsigned)ny - 1;
         s = j * (unsigned)nx + i;
-        seg = ((j < (unsigned)ny) ? j : (unsigned)ny - 1) * nchunk + chunk;
+        seg = j * nchunk + chunk;
     }
-    bool uvalid = false, vvalid = false;
-    const int kup_min = (COUNTS && (c_halo & 1)) ? -1 : 0;
     FfCountState cs;
-    cs.mld = 0.0; cs.seg = 0; cs.base_lo = cs.base_hi = 0; cs.zt_lo = cs.zt_hi = 0.0; cs.om_cur = cs.om_below = false; cs.amask = 0; cs.aclear = false; cs.fold = false; cs.has_fold = false; cs.act = false; cs.wet_below = false;
-    cs.ha = cs.hb = false;
     if (COUNTS) {
         cs.seg = (unsigned)__builtin_amdgcn_readfirstlane((int)seg);
-        cs.act = inside;
-        cs.fold = inside && topo == OTMB_TRIPOLAR && j + 1 == (unsigned)ny;
-        cs.has_fold = __builtin_amdgcn_ballot_w64(cs.fold) != 0;
-        const unsigned ifd = (unsigned)nx - 1 - i, ie = (i + 1 < (unsigned)nx) ? i + 1 : 0, iw = (i > 0) ? i - 1 : (unsigned)nx - 1;
-        cs.amask = cs.fold ? ((ifd == ie) ? (unsigned)WF_E : ((ifd == iw) ? (unsigned)WF_W : 0u)) : 0u;
-        cs.aclear = cs.fold && (ifd == ie || ifd == iw || ifd == i);
-        {   // this wave's table entries and zt, one level per lane (nz <= FFC_MAX_NZ, checked on the host)
-            const unsigned lane = threadIdx.x & 63, l0 = (lane < (unsigned)nz) ? lane : (unsigned)nz - 1, l1 = (64 + lane < (unsigned)nz) ? 64 + lane : (unsigned)nz - 1;
-            const uint32_t *mine = cnt.bases + 1 + (size_t)cs.seg * (size_t)nz;
-            cs.base_lo = mine[l0]; cs.base_hi = mine[l1];
-            // zt of levels -ha ... nz - 1 + hb (a depth slab's halo levels take part in the mixed-layer test of their neighbours, :85)
-            cs.ha = (cnt.halo & 1) != 0; cs.hb = (cnt.halo & 2) != 0;
-            const int zmax = nz - 1 + (int)cs.hb, z0 = (int)lane - (int)cs.ha, z1 = 64 + (int)lane - (int)cs.ha;
-            cs.zt_lo = cnt.zt[z0 < zmax ? z0 : zmax]; cs.zt_hi = cnt.zt[z1 < zmax ? z1 : zmax];
-        }
-        if (cnt.bases[0] != FFC_HEADER(ROWS, cnt.nseg)) {  // a table for another wave geometry: count nothing, and say so
-            if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_or(cnt.sums, FFC_BAD_TABLE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            cs.act = false;
-        }
+        ff_count_lane(cs, inside, i, j, nx, ny, topo);
+        ff_count_row(cnt, cs, ROWS, nz, cnt.halo);
     }
-    if (ROWS > 1 && lds_south) {
-        // Four-row workgroups, south row through LDS: wave r's south row IS wave r-1's own row, so every wave posts the vmo values of
-        // its chunk in LDS and takes its south values from the wave below it -- no load at all for three waves out of four (the L1 kept
-        // missing on them: the waves drift apart by more than it holds; profiles/r04/README.md section 4).  Every wave takes part in
-        // the workgroup barriers, so lanes beyond the row and rows beyond the grid march along on clamped addresses and store nothing.
-        __shared__ T s_v[2][ROWS][FF_KB][FF_THREADS];
-        const unsigned lane = threadIdx.x & (FF_THREADS - 1), r = threadIdx.x / FF_THREADS;
-        const unsigned ic = (i < (unsigned)nx) ? i : (unsigned)nx - 1, jc = (j < (unsigned)ny) ? j : (unsigned)ny - 1;
-        const unsigned sc = jc * (unsigned)nx + ic, row = jc * (unsigned)nx;
-        FfCol col;
-        col.s = sc;
-        col.sE = row + ((ic + 1 < (unsigned)nx) ? ic + 1 : 0);
-        col.sW = row + ((ic > 0) ? ic - 1 : nx - 1);
-        col.hS = jc > 0;
-        const bool fold = (jc + 1 >= (unsigned)ny) && (topo == OTMB_TRIPOLAR);
-        col.hN = (jc + 1 < (unsigned)ny) || fold;
-        col.cS = col.hS ? sc - nx : sc;
-        col.cN = (jc + 1 < (unsigned)ny) ? sc + nx : (fold ? row + (nx - 1 - ic) : sc);
-        double topbelow = top_below ? top_below[sc] : 0.0;
-        if (COUNTS) ff_count_begin(cnt, cs, wet, sc, P, nz);
-        const bool own_vs = r == 0;  // (wave-uniform) the first row of the workgroup has its south row in another workgroup
-        FfChunk<T> A, B;
-        int k0 = nz - 1, buf = 0;
-        auto south_from_lds = [&](FfChunk<T> &c) {
+    __shared__ T s_v[2][ROWS][FF_KB][FF_THREADS];  // (ROWS == 1: never referenced, no LDS)
+    const unsigned lane = threadIdx.x & (FF_THREADS - 1), r = threadIdx.x / FF_THREADS;
+    int buf = 0;
+    auto south_from_lds = [&](FfChunk<T> &c) {
+        if constexpr (ROWS > 1) {
 #pragma unroll
             for (int q = 0; q < FF_KB; ++q) s_v[buf][r][q][lane] = c.v[q];
             __syncthreads();
-            if (!own_vs) {
+            if (r != 0) {  // (wave-uniform) the first row of the workgroup has its south row in another workgroup: it loads it
 #pragma unroll
                 for (int q = 0; q < FF_KB; ++q) c.vs[q] = s_v[buf][r - 1][q][lane];
             }
             buf ^= 1;  // (the next chunk writes the other half: one barrier per chunk is enough, see the ordering argument in DESIGN.md 3.2)
-        };
-        ff_load<T, FLAGS, COUNTS>(A, umo, vmo, wet, col, P, k0, own_vs, cs.has_fold, kup_min);
-        while (k0 >= 0) {
-            ff_load<T, FLAGS, COUNTS>(B, umo, vmo, wet, col, P, k0 - FF_KB, own_vs, cs.has_fold, kup_min);
-            south_from_lds(A);
-            ff_levels<T, FLAGS, NT, COUNTS, TOPONLY>(A, col, P, k0, fill, topbelow, uvalid, vvalid, east, west, north, south, top, bottom, push_mask, inside, cnt, cs, nz);
-            k0 -= FF_KB;
-            if (k0 < 0) break;
-            ff_load<T, FLAGS, COUNTS>(A, umo, vmo, wet, col, P, k0 - FF_KB, own_vs, cs.has_fold, kup_min);
-            south_from_lds(B);
-            ff_levels<T, FLAGS, NT, COUNTS, TOPONLY>(B, col, P, k0, fill, topbelow, uvalid, vvalid, east, west, north, south, top, bottom, push_mask, inside, cnt, cs, nz);
-            k0 -= FF_KB;
         }
-    } else if (inside || COUNTS) {  // (COUNTS: every lane takes part in the wave sums; lanes beyond the plane march along on the last column and store nothing)
-        if (COUNTS && ROWS > 1 && !inside) {  // (ROWS == 1 clamped s above) lanes beyond the row or the plane: clamped addresses, as in the LDS branch
-            i = (i < (unsigned)nx) ? i : (unsigned)nx - 1;
-            j = (j < (unsigned)ny) ? j : (unsigned)ny - 1;
-            s = j * (unsigned)nx + i;
-        }
-        const unsigned row = j * (unsigned)nx;
-        FfCol col;
-        col.s = s;
-        col.sE = row + ((i + 1 < (unsigned)nx) ? i + 1 : 0);  // i₊₁, gridtopology.jl:57
-        col.sW = row + ((i > 0) ? i - 1 : nx - 1);            // i₋₁, :58
-        col.hS = j > 0;                                        // j₋₁, :63
-        const bool fold = (j + 1 >= (unsigned)ny) && (topo == OTMB_TRIPOLAR);
-        col.hN = (j + 1 < (unsigned)ny) || fold;               // j₊₁, :62; tripolar fold :94
-        col.cS = col.hS ? s - nx : s;                          // clamped neighbour columns: loads stay unconditional
-        col.cN = (j + 1 < (unsigned)ny) ? s + nx : (fold ? row + (nx - 1 - i) : s);
-        // seafloor ϕbottom is zero (:238); for a depth slab that is not the deepest, the plane handed up
-        // by the slab below (its ϕtop at its first level) continues the chain without re-association
-        double topbelow = top_below ? top_below[s] : 0.0;
-        if (COUNTS) ff_count_begin(cnt, cs, wet, s, P, nz);
-        FfChunk<T> A, B;
-        int k0 = nz - 1;
-        ff_load<T, FLAGS, COUNTS>(A, umo, vmo, wet, col, P, k0, true, cs.has_fold, kup_min);
-        while (k0 >= 0) {
-            ff_load<T, FLAGS, COUNTS>(B, umo, vmo, wet, col, P, k0 - FF_KB, true, cs.has_fold, kup_min);
-            ff_levels<T, FLAGS, NT, COUNTS, TOPONLY>(A, col, P, k0, fill, topbelow, uvalid, vvalid, east, west, north, south, top, bottom, push_mask, inside, cnt, cs, nz);
-            k0 -= FF_KB;
-            if (k0 < 0) break;
-            ff_load<T, FLAGS, COUNTS>(A, umo, vmo, wet, col, P, k0 - FF_KB, true, cs.has_fold, kup_min);
-            ff_levels<T, FLAGS, NT, COUNTS, TOPONLY>(B, col, P, k0, fill, topbelow, uvalid, vvalid, east, west, north, south, top, bottom, push_mask, inside, cnt, cs, nz);
-            k0 -= FF_KB;
-        }
-    }
-    // "some value is valid" = the call's pair of words (ring slot gen % OTMB_RING) holds this call's number: no reset
-    // pass between calls, and the verdict on call g survives the next OTMB_RING - 1 calls
-    if (__any(uvalid) && (threadIdx.x & 63) == 0 && uv[0] != gen) atomicExch(&uv[0], gen);
-    if (__any(vvalid) && (threadIdx.x & 63) == 0 && uv[1] != gen) atomicExch(&uv[1], gen);
+    };
+    ff_march<T, FLAGS, NT, COUNTS, TOPONLY, false>(umo, vmo, wet, ff_col(s, i, j, nx, ny, topo), P, nz, fill, top_below ? top_below[s] : 0.0, uv, gen,
+                                                   east, west, north, south, top, bottom, push_mask, inside, cnt, cs, ROWS == 1 || r == 0, false,
+                                                   south_from_lds);
 }
 
 // Two levels per wave, for grids with so few columns that the length of a wave's march bounds the kernel (1 degree: 1688 waves of 64
@@ -547,69 +556,19 @@ __global__ __launch_bounds__(FF_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
     double *__restrict__ bottom, int *uv, int gen, int xcd_chunks,
     const uint32_t *__restrict__ c_bases, const double *__restrict__ c_mlotst, const double *__restrict__ c_zt, unsigned long long *c_sums,
     int c_upwind, int c_only_t, int c_nseg) {
-    FfCountArgs cnt;
-    cnt.bases = c_bases; cnt.mlotst = c_mlotst; cnt.zt = c_zt; cnt.sums = c_sums; cnt.upwind = c_upwind; cnt.only_t = c_only_t; cnt.nseg = c_nseg;
-    cnt.halo = 0;
-    unsigned cb = blockIdx.x;  // XCD x takes the x-th contiguous eighth of the column blocks, as in facefluxes_kernel
-    if (xcd_chunks) {
-        const unsigned nb = gridDim.x, q = nb / 8, r = nb % 8, x = blockIdx.x % 8, y = blockIdx.x / 8;
-        cb = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + y;
-    }
-    const unsigned lane = threadIdx.x;
-    const bool up = lane >= FF_PAIR_COLS;
-    unsigned s = cb * FF_PAIR_COLS + (lane & (FF_PAIR_COLS - 1));
+    const FfCountArgs cnt = {c_bases, c_mlotst, c_zt, c_sums, c_upwind, c_only_t, c_nseg, 0};
+    const unsigned cb = ff_xcd_block(xcd_chunks);
+    const bool up = threadIdx.x >= FF_PAIR_COLS;
+    unsigned s = cb * FF_PAIR_COLS + (threadIdx.x & (FF_PAIR_COLS - 1));
     const bool inside = s < (unsigned)P;
     if (!inside) s = (unsigned)P - 1;  // lanes beyond the plane march along on the last column and store nothing
     const unsigned j = s / (unsigned)nx, i = s - j * (unsigned)nx;
-    bool uvalid = false, vvalid = false;
     FfCountState cs;
-    cs.mld = 0.0; cs.base_lo = cs.base_hi = 0; cs.zt_lo = cs.zt_hi = 0.0; cs.om_cur = cs.om_below = cs.om_up = false; cs.wet_below = false;
-    cs.ha = cs.hb = false;
     cs.seg = cb;
-    cs.act = inside;
-    cs.fold = inside && topo == OTMB_TRIPOLAR && j + 1 == (unsigned)ny;
-    cs.has_fold = __builtin_amdgcn_ballot_w64(cs.fold) != 0;
-    const unsigned ifd = (unsigned)nx - 1 - i, ie = (i + 1 < (unsigned)nx) ? i + 1 : 0, iw = (i > 0) ? i - 1 : (unsigned)nx - 1;
-    cs.amask = cs.fold ? ((ifd == ie) ? (unsigned)WF_E : ((ifd == iw) ? (unsigned)WF_W : 0u)) : 0u;
-    cs.aclear = cs.fold && (ifd == ie || ifd == iw || ifd == i);
-    if (cnt.bases[0] == FFC_HEADER(FF_GEOM_PAIR, cnt.nseg)) {  // (uniform) this wave's table entries, one level per lane (nz <= FFC_MAX_NZ, checked on the host)
-        const unsigned l0 = (lane < (unsigned)nz) ? lane : (unsigned)nz - 1, l1 = (64 + lane < (unsigned)nz) ? 64 + lane : (unsigned)nz - 1;
-        const uint32_t *mine = cnt.bases + 1 + (size_t)cs.seg * (size_t)nz;
-        cs.base_lo = mine[l0]; cs.base_hi = mine[l1];
-    } else {  // a table for another wave geometry (it may be shorter: not read): count nothing, and say so
-        if (lane == 0) __hip_atomic_fetch_or(cnt.sums, FFC_BAD_TABLE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        cs.act = false;
-    }
-    {
-        const int zmax = nz - 1, z0 = (int)lane, z1 = 64 + (int)lane;
-        cs.zt_lo = cnt.zt[z0 < zmax ? z0 : zmax]; cs.zt_hi = cnt.zt[z1 < zmax ? z1 : zmax];
-    }
-    const unsigned row = j * (unsigned)nx;
-    FfCol col;
-    col.s = s;
-    col.sE = row + ((i + 1 < (unsigned)nx) ? i + 1 : 0);
-    col.sW = row + ((i > 0) ? i - 1 : nx - 1);
-    col.hS = j > 0;
-    const bool fold = (j + 1 >= (unsigned)ny) && (topo == OTMB_TRIPOLAR);
-    col.hN = (j + 1 < (unsigned)ny) || fold;
-    col.cS = col.hS ? s - nx : s;
-    col.cN = (j + 1 < (unsigned)ny) ? s + nx : (fold ? row + (nx - 1 - i) : s);
-    double topbelow = 0.0;  // seafloor ϕbottom (:238)
-    ff_count_begin<true>(cnt, cs, wet, s, P, nz);
-    FfChunk<T> A, B;
-    int k0 = nz - 1;
-    ff_load<T, true, true, true>(A, umo, vmo, wet, col, P, k0, true, cs.has_fold, 0, up);
-    while (k0 >= 0) {
-        ff_load<T, true, true, true>(B, umo, vmo, wet, col, P, k0 - 2 * FF_KB, true, cs.has_fold, 0, up);
-        ff_levels<T, true, NT, true, TOPONLY, true>(A, col, P, k0, fill, topbelow, uvalid, vvalid, east, west, north, south, top, bottom, nullptr, inside, cnt, cs, nz, up);
-        k0 -= 2 * FF_KB;
-        if (k0 < 0) break;
-        ff_load<T, true, true, true>(A, umo, vmo, wet, col, P, k0 - 2 * FF_KB, true, cs.has_fold, 0, up);
-        ff_levels<T, true, NT, true, TOPONLY, true>(B, col, P, k0, fill, topbelow, uvalid, vvalid, east, west, north, south, top, bottom, nullptr, inside, cnt, cs, nz, up);
-        k0 -= 2 * FF_KB;
-    }
-    if (__any(uvalid) && lane == 0 && uv[0] != gen) atomicExch(&uv[0], gen);
-    if (__any(vvalid) && lane == 0 && uv[1] != gen) atomicExch(&uv[1], gen);
+    ff_count_lane(cs, inside, i, j, nx, ny, topo);
+    ff_count_row(cnt, cs, FF_GEOM_PAIR, nz, 0);
+    ff_march<T, true, NT, true, TOPONLY, true>(umo, vmo, wet, ff_col(s, i, j, nx, ny, topo), P, nz, fill, 0.0, uv, gen, east, west, north, south, top,
+                                               bottom, nullptr, inside, cnt, cs, true, up, [](FfChunk<T> &) {});
 }
 
 // one thread per cell: the cell's wet byte and those of its east / west / south / north neighbours (periodic in i, closed in
@@ -697,8 +656,8 @@ __global__ __launch_bounds__(256) void ff_static_counts_kernel(const i64 *__rest
         const unsigned vw = ((k > 0 && (flags[L - P] & WF_C)) ? 32u : 0u) | ((k + 1 < nz && (flags[L + P] & WF_C)) ? 64u : 0u);
         const unsigned anyH = hb != 0, anyU = (hb | vw) != 0;
         if (topo == OTMB_TRIPOLAR && j == ny - 1) {  // the fold neighbour's slot (see ff_fold_alias)
-            const int ifd = nx - 1 - i, ie = (i + 1 < nx) ? i + 1 : 0, iw = (i > 0) ? i - 1 : nx - 1;
-            if (ifd == ie || ifd == iw || ifd == i) hb = ff_fold_alias(hb, (ifd == ie) ? (unsigned)WF_E : ((ifd == iw) ? (unsigned)WF_W : 0u));
+            const FfSeamSlot sl = ff_seam_slot((unsigned)i, (unsigned)nx);
+            if (sl.aclear) hb = ff_fold_alias(hb, sl.amask);
         }
         const unsigned h = __popc(hb), d = __popc(vw);
         mine = (unsigned long long)(h + d + anyU) | ((unsigned long long)(h + anyH) << 22) | ((unsigned long long)(d + (vw != 0)) << 43);
@@ -715,120 +674,148 @@ static size_t ff_tables_static_offset(int rows, i64 nx, i64 ny, i64 nz) {
     return ((size_t)(1 + nz * ff_nseg(rows, nx, ny)) * sizeof(uint32_t) + 7) / 8 * 8;
 }
 
-static int32_t facefluxes_impl(otmb_ctx *ctx, const void *umo, const void *vmo, int32_t src_is_f32,
-                               const uint8_t *wet3d, double fill, int64_t nx, int64_t ny, int64_t nz,
-                               int32_t topology, double *const phi[6], const double *top_below, uint16_t *push_mask,
-                               bool check_missing, bool flags = false, const otmb_ff_counts *counts = nullptr, int64_t j0 = 0, int64_t j1 = -1,
-                               bool same_call = false, bool top_only = false, const otmb_ff_slab *slab = nullptr) {
-    // slab (with counts): the nz levels are levels [k_own0, k_own0 + nz) of an extended local grid of nz_ext levels; wet3d (the flag bytes),
+// One facefluxes call, as its entry point describes it to facefluxes_impl
+struct FfCall {
+    // inputs.  wet3d: the wet bytes, or (flags) the five-flag bytes; top_below: ϕtop of the level below the last one (a depth slab), or null
+    const void *umo = nullptr, *vmo = nullptr;
+    int32_t src_is_f32 = 0, topology = OTMB_UNKNOWN_TOPOLOGY;
+    const uint8_t *wet3d = nullptr;
+    double fill = 0.0;
+    int64_t nx = 0, ny = 0, nz = 0;
+    const double *top_below = nullptr;
+    // outputs
+    double *const *phi = nullptr;
+    uint16_t *push_mask = nullptr;
+    int64_t j0 = 0, j1 = -1;     // row band: rows [j0, j1) of the plane only (j1 < 0: all of them)
+    bool same_call = false;      // a further piece of the call that the previous piece began: their validity flags accumulate in ONE pair of words
+    bool top_only = false;       // (with counts) store ϕtop alone: the fused step
+    bool flags = false;          // wet3d holds the five-flag bytes
+    const otmb_ff_counts *counts = nullptr;
+    // (with counts) the nz levels are levels [k_own0, k_own0 + nz) of an extended local grid of nz_ext levels; wet3d (the flag bytes),
     // counts->zt and counts->lwet3d are arrays of THAT grid, everything else holds the owned levels only
-    // j0, j1: rows [j0, j1) of the plane only (j1 < 0: all of them); same_call: a further piece of the facefluxes call that the
-    // previous piece began -- the validity flags of the pieces accumulate in ONE pair of words
-    if (!ctx || !umo || !vmo || !wet3d || !phi) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
+    const otmb_ff_slab *slab = nullptr;
+    bool check_missing = false;  // synchronize and report @assert !all(missing) (:199-200)
+};
+static FfCall ff_call(const void *umo, const void *vmo, int32_t src_is_f32, const uint8_t *wet3d, double fill, int64_t nx, int64_t ny, int64_t nz,
+                      int32_t topology, double *const phi[6]) {
+    FfCall c;
+    c.umo = umo; c.vmo = vmo; c.src_is_f32 = src_is_f32; c.wet3d = wet3d; c.fill = fill; c.nx = nx; c.ny = ny; c.nz = nz; c.topology = topology;
+    c.phi = phi;
+    return c;
+}
+
+// A counting call's sums buffer -- reserved, zeroed, or (a further row band) the one the first piece took -- what the kernel needs of the
+// counts (ca), and what they will describe (ctx->ffc, the key the transportmatrix checks)
+static int32_t ff_counts_begin(otmb_ctx *ctx, const FfCall &c, int geom, bool later_piece, FfCountArgs &ca) {
+    // (the caller -- otmb_facefluxes_counts_dev / _slab_counts_dev -- has checked that this grid can be counted here)
+    const otmb_ff_counts *counts = c.counts;
+    const i64 P = c.nx * c.ny, k_own0 = c.slab ? c.slab->k_own0 : 0, nz_ext = c.slab ? c.slab->nz_ext : c.nz;
+    const i64 ntiles = (counts->n_wet + (1ll << FFC_TILE_SHIFT) - 1) >> FFC_TILE_SHIFT;
+    const size_t need = (size_t)(ntiles + 2) * sizeof(unsigned long long);
+    int buf;
+    if (later_piece) {
+        buf = ctx->ffc.buf;
+    } else {
+        buf = ctx->ffc_next;
+        ctx->ffc_next ^= 1;
+        if (!ctx->ffc_sums[buf].p || ctx->ffc_sums[buf].cap < need) {
+            if (int32_t rc = otmb_reserve(ctx, ctx->ffc_sums[buf], need)) return rc;
+            ctx->ffc_dirty[buf] = true;
+        }
+        if (ctx->ffc_dirty[buf]) HIP_TRY(ctx, hipMemsetAsync(ctx->ffc_sums[buf].p, 0, need, ctx->stream));
+        ctx->ffc_dirty[buf] = true;  // until a scan has consumed (and zeroed) it
+    }
+    ca.bases = (const uint32_t *)counts->tables; ca.mlotst = counts->mlotst; ca.zt = counts->zt + k_own0;
+    ca.sums = (unsigned long long *)ctx->ffc_sums[buf].p;
+    ca.upwind = counts->upwind; ca.only_t = counts->only_t;
+    ca.nseg = (int)ff_nseg(geom, c.nx, c.ny);
+    ca.halo = (k_own0 > 0 ? 1 : 0) | (k_own0 + c.nz < nz_ext ? 2 : 0);
+    otmb_ctx::FfCountsKey &key = ctx->ffc;
+    key.buf = buf; key.gen = ctx->ff_gen;
+    for (int f = 0; f < 6; ++f) key.phi[f] = c.phi[f];
+    key.stat = (const char *)counts->tables + ff_tables_static_offset(geom, c.nx, c.ny, c.nz);
+    key.mask = c.push_mask; key.mlotst = counts->mlotst; key.zt = counts->zt; key.lwet3d = counts->lwet3d;
+    key.nx = c.nx; key.ny = c.ny; key.nz = nz_ext; key.n_wet = counts->n_wet;
+    key.k_own0 = k_own0; key.wet_base = c.slab ? c.slab->wet_base : 0;
+    key.topo = c.topology; key.upwind = counts->upwind != 0; key.only_t = counts->only_t != 0;
+    ctx->ffc_partial_mask = c.push_mask ? c.push_mask - k_own0 * P : nullptr;  // (as the transportmatrix will name it: the extended grid's array)
+    return OTMB_OK;
+}
+
+// The kernels that exist, and no others: facefluxes_kernel in four families -- five wet bytes; the flag byte; with counts; with counts,
+// ϕtop only -- each for one and four rows per workgroup and both kinds of store, and facefluxes_pair_kernel (counts) for both kinds of
+// store, six arrays or ϕtop only
+template <typename T, bool FL, bool CN, bool TO> static auto ff_kernel(int rows, bool nt) {
+    return rows == 4 ? (nt ? &facefluxes_kernel<T, FL, true, 4, CN, TO> : &facefluxes_kernel<T, FL, false, 4, CN, TO>)
+                     : (nt ? &facefluxes_kernel<T, FL, true, 1, CN, TO> : &facefluxes_kernel<T, FL, false, 1, CN, TO>);
+}
+template <typename T>
+static void ff_launch(otmb_ctx *ctx, const FfCall &c, const uint8_t *wet3d, const FfCountArgs &ca, unsigned nb, int rows, bool pair, bool nt,
+                      int *dflags) {
+    const T *umo = (const T *)c.umo, *vmo = (const T *)c.vmo;
+    double *const *phi = c.phi;
+    const i64 P = c.nx * c.ny;
+    if (pair) {
+        const auto k = c.top_only ? (nt ? &facefluxes_pair_kernel<T, true, true> : &facefluxes_pair_kernel<T, false, true>)
+                                  : (nt ? &facefluxes_pair_kernel<T, true, false> : &facefluxes_pair_kernel<T, false, false>);
+        hipLaunchKernelGGL(k, dim3(nb), dim3(FF_THREADS), 0, ctx->stream, umo, vmo, wet3d, c.fill, (int)c.nx, (int)c.ny, (int)c.nz, (int)c.topology, P,
+                           phi[OTMB_EAST], phi[OTMB_WEST], phi[OTMB_NORTH], phi[OTMB_SOUTH], phi[OTMB_TOP], phi[OTMB_BOTTOM], dflags, ctx->ff_gen,
+                           ctx->ff_xcd_chunks, ca.bases, ca.mlotst, ca.zt, ca.sums, ca.upwind, ca.only_t, ca.nseg);
+        return;
+    }
+    const auto k = c.counts ? (c.top_only ? ff_kernel<T, true, true, true>(rows, nt) : ff_kernel<T, true, true, false>(rows, nt))
+                            : (c.flags ? ff_kernel<T, true, false, false>(rows, nt) : ff_kernel<T, false, false, false>(rows, nt));
+    hipLaunchKernelGGL(k, dim3(nb), dim3(FF_THREADS * rows), 0, ctx->stream, umo, vmo, wet3d, c.fill, (int)c.nx, (int)c.ny, (int)c.nz, (int)c.topology, P,
+                       phi[OTMB_EAST], phi[OTMB_WEST], phi[OTMB_NORTH], phi[OTMB_SOUTH], phi[OTMB_TOP], phi[OTMB_BOTTOM], c.top_below, c.push_mask, dflags,
+                       ctx->ff_gen, ctx->ff_xcd_chunks, (int)c.j0, (int)c.j1, ca.bases, ca.mlotst, ca.zt, ca.sums, ca.upwind, ca.only_t, ca.nseg, ca.halo);
+}
+
+static int32_t facefluxes_impl(otmb_ctx *ctx, FfCall c) {
+    if (!ctx || !c.umo || !c.vmo || !c.wet3d || !c.phi) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
     for (int f = 0; f < 6; ++f)
-        if (!phi[f] && !(top_only && f != OTMB_TOP)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null output");
-    if (nx < 1 || ny < 1 || nz < 1 || nx * ny >= (1ll << 28)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "grid size");
-    if (topology == OTMB_UNKNOWN_TOPOLOGY) return otmb_fail(ctx, OTMB_ERR_UNKNOWN_TOPOLOGY);  // :163 -> gridtopology.jl:111
-    if (topology != OTMB_BIPOLAR && topology != OTMB_TRIPOLAR) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "topology");
+        if (!c.phi[f] && !(c.top_only && f != OTMB_TOP)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null output");
+    const i64 nx = c.nx, ny = c.ny, nz = c.nz, P = nx * ny;
+    if (nx < 1 || ny < 1 || nz < 1 || P >= (1ll << 28)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "grid size");
+    if (c.topology == OTMB_UNKNOWN_TOPOLOGY) return otmb_fail(ctx, OTMB_ERR_UNKNOWN_TOPOLOGY);  // :163 -> gridtopology.jl:111
+    if (c.topology != OTMB_BIPOLAR && c.topology != OTMB_TRIPOLAR) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "topology");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const i64 P = nx * ny;
-    if (j1 < 0) j1 = ny;
-    if (j0 < 0 || j0 >= j1 || j1 > ny) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "row range");
-    if (!same_call || ctx->ff_gen == 0) {
+    if (c.j1 < 0) c.j1 = ny;
+    if (c.j0 < 0 || c.j0 >= c.j1 || c.j1 > ny) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "row range");
+    if (!c.same_call || ctx->ff_gen == 0) {
         if (ctx->ff_gen == 0x7fffffff) { ctx->ff_gen = 0; ctx->ff_first = 1; }
         ctx->ff_gen += 1;
     }
     int *dflags = otmb_ring_ff((int *)ctx->ring.p, ctx->ff_gen);
     const int rows = ff_rows_for(ctx, nx, ny);
     // two levels per wave: whole planes of whole grids with counts (anything else on such a grid keeps today's kernels)
-    const bool pair = counts && !slab && !top_below && j0 == 0 && j1 == ny && ff_geom_for(ctx, nx, ny, nz) == FF_GEOM_PAIR;
-    const int geom = pair ? FF_GEOM_PAIR : rows;
+    const bool pair = c.counts && !c.slab && !c.top_below && c.j0 == 0 && c.j1 == ny && ff_geom_for(ctx, nx, ny, nz) == FF_GEOM_PAIR;
     ctx->ff_pairs_last = pair ? 1 : 0;
-    const unsigned nb = pair ? (unsigned)((P + FF_PAIR_COLS - 1) / FF_PAIR_COLS) : rows == 1 ? (unsigned)(((j1 - j0) * nx + FF_THREADS - 1) / FF_THREADS)
-                                  : (unsigned)(((nx + FF_THREADS - 1) / FF_THREADS) * ((j1 - j0 + rows - 1) / rows));
+    const unsigned nb = pair ? (unsigned)((P + FF_PAIR_COLS - 1) / FF_PAIR_COLS) : rows == 1 ? (unsigned)(((c.j1 - c.j0) * nx + FF_THREADS - 1) / FF_THREADS)
+                                  : (unsigned)(((nx + FF_THREADS - 1) / FF_THREADS) * ((c.j1 - c.j0 + rows - 1) / rows));
     // any facefluxes call on this context ends the validity of counts an earlier call left behind (they are keyed to ff_gen), and a full
     // mask written over a partial one makes that array an ordinary push mask again
-    const bool later_piece = same_call && counts && ctx->ffc.pieces_open;  // a further row band of a counting call: same buffer, same key
+    const bool later_piece = c.same_call && c.counts && ctx->ffc.pieces_open;  // a further row band of a counting call: same buffer, same key
     if (!later_piece) ctx->ffc.valid = false;
     ctx->ffc.pieces_open = false;
-    if (push_mask && push_mask == ctx->ffc_partial_mask && !counts) ctx->ffc_partial_mask = nullptr;
-    FfCountArgs ca;
-    memset(&ca, 0, sizeof ca);
-    const bool with_counts = counts != nullptr;
-    const i64 k_own0 = slab ? slab->k_own0 : 0, nz_ext = slab ? slab->nz_ext : nz;
-    if (with_counts) {
-        // (the caller -- otmb_facefluxes_counts_dev / _slab_counts_dev -- has checked that this grid can be counted here)
-        const i64 ntiles = (counts->n_wet + (1ll << FFC_TILE_SHIFT) - 1) >> FFC_TILE_SHIFT;
-        const size_t need = (size_t)(ntiles + 2) * sizeof(unsigned long long);
-        int buf;
-        if (later_piece) {
-            buf = ctx->ffc.buf;
-        } else {
-            buf = ctx->ffc_next;
-            ctx->ffc_next ^= 1;
-            if (!ctx->ffc_sums[buf].p || ctx->ffc_sums[buf].cap < need) {
-                int32_t rc;
-                if ((rc = otmb_reserve(ctx, ctx->ffc_sums[buf], need))) return rc;
-                ctx->ffc_dirty[buf] = true;
-            }
-            if (ctx->ffc_dirty[buf]) HIP_TRY(ctx, hipMemsetAsync(ctx->ffc_sums[buf].p, 0, need, ctx->stream));
-            ctx->ffc_dirty[buf] = true;  // until a scan has consumed (and zeroed) it
-        }
-        ca.bases = (const uint32_t *)counts->tables; ca.mlotst = counts->mlotst; ca.zt = counts->zt + k_own0;
-        ca.sums = (unsigned long long *)ctx->ffc_sums[buf].p;
-        ca.upwind = counts->upwind; ca.only_t = counts->only_t;
-        ca.nseg = (int)ff_nseg(geom, nx, ny);
-        ca.halo = (k_own0 > 0 ? 1 : 0) | (k_own0 + nz < nz_ext ? 2 : 0);
-        otmb_ctx::FfCountsKey &key = ctx->ffc;
-        key.buf = buf; key.gen = ctx->ff_gen;
-        for (int f = 0; f < 6; ++f) key.phi[f] = phi[f];
-        key.stat = (const char *)counts->tables + ff_tables_static_offset(geom, nx, ny, nz);
-        key.mask = push_mask; key.mlotst = counts->mlotst; key.zt = counts->zt; key.lwet3d = counts->lwet3d;
-        key.nx = nx; key.ny = ny; key.nz = nz_ext; key.n_wet = counts->n_wet;
-        key.k_own0 = k_own0; key.wet_base = slab ? slab->wet_base : 0;
-        key.topo = topology; key.upwind = counts->upwind != 0; key.only_t = counts->only_t != 0;
-        ctx->ffc_partial_mask = push_mask ? push_mask - k_own0 * P : nullptr;  // (as the transportmatrix will name it: the extended grid's array)
-        wet3d += k_own0 * P;  // the kernel marches over the owned levels; a halo level is level -1 / nz to it
+    if (c.push_mask && c.push_mask == ctx->ffc_partial_mask && !c.counts) ctx->ffc_partial_mask = nullptr;
+    FfCountArgs ca = {};
+    const uint8_t *wet3d = c.wet3d;
+    if (c.counts) {
+        if (int32_t rc = ff_counts_begin(ctx, c, pair ? FF_GEOM_PAIR : rows, later_piece, ca)) return rc;
+        if (c.slab) wet3d += c.slab->k_own0 * P;  // the kernel marches over the owned levels; a halo level is level -1 / nz to it
     }
     {
-    KernelTimer kt(ctx, K_FACEFLUXES);
-    // six Float64 arrays beyond a gigabyte: streaming stores.  The pair kernel always: its waves write two planes of every array at a time, and
-    // with plain stores those twelve streams cost it more than the shorter march gains (1 degree: 85.5 us against 64.9 us, profiles/r15)
-    const bool nt = ctx->ff_nt >= 0 ? ctx->ff_nt != 0 : (pair || (i64)48 * P * nz > (1ll << 30));
-#define FF_LAUNCH(T, FL, NTS, R, CN)                                                                                                   \
-    FF_LAUNCH_T(T, FL, NTS, R, CN, false)
-#define FF_LAUNCH_T(T, FL, NTS, R, CN, TO)                                                                                             \
-    hipLaunchKernelGGL((facefluxes_kernel<T, FL, NTS, R, CN, TO>), dim3(nb), dim3(FF_THREADS * R), 0, ctx->stream, (const T *)umo, (const T *)vmo, wet3d, \
-                       fill, (int)nx, (int)ny, (int)nz, (int)topology, P, phi[OTMB_EAST], phi[OTMB_WEST], phi[OTMB_NORTH],           \
-                       phi[OTMB_SOUTH], phi[OTMB_TOP], phi[OTMB_BOTTOM], top_below, push_mask, dflags, ctx->ff_gen, ctx->ff_xcd_chunks, ctx->ff_lds_south, \
-                       (int)j0, (int)j1, ca.bases, ca.mlotst, ca.zt, ca.sums, ca.upwind, ca.only_t, ca.nseg, ca.halo)
-#define FF_LAUNCH2(T, FL, CN) do { if (rows == 4) { if (nt) FF_LAUNCH(T, FL, true, 4, CN); else FF_LAUNCH(T, FL, false, 4, CN); } \
-                                   else { if (nt) FF_LAUNCH(T, FL, true, 1, CN); else FF_LAUNCH(T, FL, false, 1, CN); } } while (0)
-#define FF_LAUNCH2T(T) do { if (rows == 4) { if (nt) FF_LAUNCH_T(T, true, true, 4, true, true); else FF_LAUNCH_T(T, true, false, 4, true, true); } \
-                            else { if (nt) FF_LAUNCH_T(T, true, true, 1, true, true); else FF_LAUNCH_T(T, true, false, 1, true, true); } } while (0)
-#define FF_LAUNCH_PAIR(T, NTS, TO)                                                                                                    \
-    hipLaunchKernelGGL((facefluxes_pair_kernel<T, NTS, TO>), dim3(nb), dim3(FF_THREADS), 0, ctx->stream, (const T *)umo, (const T *)vmo, wet3d, \
-                       fill, (int)nx, (int)ny, (int)nz, (int)topology, P, phi[OTMB_EAST], phi[OTMB_WEST], phi[OTMB_NORTH],           \
-                       phi[OTMB_SOUTH], phi[OTMB_TOP], phi[OTMB_BOTTOM], dflags, ctx->ff_gen, ctx->ff_xcd_chunks, ca.bases, ca.mlotst,  \
-                       ca.zt, ca.sums, ca.upwind, ca.only_t, ca.nseg)
-#define FF_LAUNCH_PAIR2(T) do { if (top_only) { if (nt) FF_LAUNCH_PAIR(T, true, true); else FF_LAUNCH_PAIR(T, false, true); } \
-                                else { if (nt) FF_LAUNCH_PAIR(T, true, false); else FF_LAUNCH_PAIR(T, false, false); } } while (0)
-    if (pair) { if (src_is_f32) FF_LAUNCH_PAIR2(float); else FF_LAUNCH_PAIR2(double); }
-    else if (with_counts && top_only) { if (src_is_f32) FF_LAUNCH2T(float); else FF_LAUNCH2T(double); }
-    else if (with_counts) { if (src_is_f32) FF_LAUNCH2(float, true, true); else FF_LAUNCH2(double, true, true); }
-    else if (src_is_f32) { if (flags) FF_LAUNCH2(float, true, false); else FF_LAUNCH2(float, false, false); }
-    else { if (flags) FF_LAUNCH2(double, true, false); else FF_LAUNCH2(double, false, false); }
-#undef FF_LAUNCH_PAIR2
-#undef FF_LAUNCH_PAIR
-#undef FF_LAUNCH2T
-#undef FF_LAUNCH2
-#undef FF_LAUNCH_T
-#undef FF_LAUNCH
+        KernelTimer kt(ctx, K_FACEFLUXES);
+        // six Float64 arrays beyond a gigabyte: streaming stores.  The pair kernel always: its waves write two planes of every array at a time, and
+        // with plain stores those twelve streams cost it more than the shorter march gains (1 degree: 85.5 us against 64.9 us, profiles/r15)
+        const bool nt = ctx->ff_nt >= 0 ? ctx->ff_nt != 0 : (pair || (i64)48 * P * nz > (1ll << 30));
+        if (c.src_is_f32) ff_launch<float>(ctx, c, wet3d, ca, nb, rows, pair, nt, dflags);
+        else ff_launch<double>(ctx, c, wet3d, ca, nb, rows, pair, nt, dflags);
     }
-    if (with_counts) { ctx->ffc.valid = true; ctx->ffc.pieces_open = true; }  // (valid for the caller once the last row band is enqueued)
+    if (c.counts) { ctx->ffc.valid = true; ctx->ffc.pieces_open = true; }  // (valid for the caller once the last row band is enqueued)
     HIP_TRY(ctx, hipGetLastError());
     // @assert !all(missing) (:199-200): needs the whole pass, so it is reported after the kernel
-    if (!check_missing) return OTMB_OK;  // slab / asynchronous: otmb_facefluxes_slab_flags fetches the flags when asked
+    if (!c.check_missing) return OTMB_OK;  // slab / asynchronous: otmb_facefluxes_slab_flags fetches the flags when asked
     int32_t u = 0, v = 0, rc;
     if ((rc = otmb_facefluxes_slab_flags(ctx, &u, &v))) return rc;
     if (!u || !v) return otmb_fail(ctx, OTMB_ERR_ALL_MISSING);
@@ -838,7 +825,9 @@ static int32_t facefluxes_impl(otmb_ctx *ctx, const void *umo, const void *vmo, 
 extern "C" int32_t otmb_facefluxes_dev(otmb_ctx *ctx, const void *umo, const void *vmo, int32_t src_is_f32,
                                        const uint8_t *wet3d, double fill, int64_t nx, int64_t ny, int64_t nz,
                                        int32_t topology, double *const phi[6]) {
-    return facefluxes_impl(ctx, umo, vmo, src_is_f32, wet3d, fill, nx, ny, nz, topology, phi, nullptr, nullptr, true);
+    FfCall c = ff_call(umo, vmo, src_is_f32, wet3d, fill, nx, ny, nz, topology, phi);
+    c.check_missing = true;
+    return facefluxes_impl(ctx, c);
 }
 
 // Depth-slab variant: the levels handed in are levels [k0,k1) of a deeper grid.  top_below (nx*ny, may
@@ -849,7 +838,9 @@ extern "C" int32_t otmb_facefluxes_slab_dev(otmb_ctx *ctx, const void *umo, cons
                                             const uint8_t *wet3d, double fill, int64_t nx, int64_t ny, int64_t nz,
                                             int32_t topology, double *const phi[6], const double *top_below,
                                             uint16_t *push_mask) {
-    return facefluxes_impl(ctx, umo, vmo, src_is_f32, wet3d, fill, nx, ny, nz, topology, phi, top_below, push_mask, false);
+    FfCall c = ff_call(umo, vmo, src_is_f32, wet3d, fill, nx, ny, nz, topology, phi);
+    c.top_below = top_below; c.push_mask = push_mask;
+    return facefluxes_impl(ctx, c);
 }
 
 // One row band of the plane: rows [j0, j1) of every level (0-based).  The chain over depth slabs runs piece by piece (slab s
@@ -860,8 +851,9 @@ extern "C" int32_t otmb_facefluxes_rows_dev(otmb_ctx *ctx, const void *umo, cons
                                             double fill, int64_t nx, int64_t ny, int64_t nz, int32_t topology, double *const phi[6],
                                             const double *top_below, uint16_t *push_mask, int64_t j0, int64_t j1, int32_t first) {
     if (j0 < 0 || j1 > ny || j0 >= j1) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "row range");
-    return facefluxes_impl(ctx, umo, vmo, src_is_f32, wet3d, fill, nx, ny, nz, topology, phi, top_below, push_mask, false, false, nullptr, j0, j1,
-                           first == 0);
+    FfCall c = ff_call(umo, vmo, src_is_f32, wet3d, fill, nx, ny, nz, topology, phi);
+    c.top_below = top_below; c.push_mask = push_mask; c.j0 = j0; c.j1 = j1; c.same_call = first == 0;
+    return facefluxes_impl(ctx, c);
 }
 
 extern "C" int32_t otmb_wetflags_dev(otmb_ctx *ctx, const uint8_t *wet3d, int64_t nx, int64_t ny, int64_t nz, int32_t topology,
@@ -882,7 +874,9 @@ extern "C" int32_t otmb_facefluxes_flags_dev(otmb_ctx *ctx, const void *umo, con
                                              const uint8_t *wetflags, double fill, int64_t nx, int64_t ny, int64_t nz,
                                              int32_t topology, double *const phi[6], const double *top_below,
                                              uint16_t *push_mask) {
-    return facefluxes_impl(ctx, umo, vmo, src_is_f32, wetflags, fill, nx, ny, nz, topology, phi, top_below, push_mask, false, true);
+    FfCall c = ff_call(umo, vmo, src_is_f32, wetflags, fill, nx, ny, nz, topology, phi);
+    c.top_below = top_below; c.push_mask = push_mask; c.flags = true;
+    return facefluxes_impl(ctx, c);
 }
 
 extern "C" int64_t otmb_count_tables_bytes(const otmb_ctx *ctx, int64_t nx, int64_t ny, int64_t nz, int64_t n_wet) {
@@ -935,8 +929,9 @@ extern "C" int32_t otmb_facefluxes_counts_dev(otmb_ctx *ctx, const void *umo, co
     if (!ctx || !counts) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
     const bool can = ctx->count_in_ff != 0 && nx >= 3 && push_mask && counts->tables && counts->lwet3d && counts->mlotst && counts->zt &&
                      counts->n_wet > 0 && nx * ny * nz < (1ll << 32) && nz <= FFC_MAX_NZ;
-    return facefluxes_impl(ctx, umo, vmo, src_is_f32, wetflags, fill, nx, ny, nz, topology, phi, nullptr, push_mask, false, true,
-                           can ? counts : nullptr);
+    FfCall c = ff_call(umo, vmo, src_is_f32, wetflags, fill, nx, ny, nz, topology, phi);
+    c.push_mask = push_mask; c.flags = true; c.counts = can ? counts : nullptr;
+    return facefluxes_impl(ctx, c);
 }
 
 // The same for a depth slab, optionally one row band at a time (the chain over depth slabs, otmb_facefluxes_rows_dev).  A row band other
@@ -957,11 +952,11 @@ extern "C" int32_t otmb_facefluxes_slab_counts_dev(otmb_ctx *ctx, const void *um
                (whole || ff_rows_for(ctx, nx, ny) == 4);
     // (a piece of a call whose first piece could not count must not start counting: the key of the call is the first piece's)
     if (!first && !ctx->ffc.pieces_open) can = false;
-    if (!can)
-        return facefluxes_impl(ctx, umo, vmo, src_is_f32, wetflags + slab->k_own0 * nx * ny, fill, nx, ny, nz, topology, phi, top_below, push_mask,
-                               false, true, nullptr, j0, j1, first == 0);
-    return facefluxes_impl(ctx, umo, vmo, src_is_f32, wetflags, fill, nx, ny, nz, topology, phi, top_below, push_mask, false, true, counts, j0, j1,
-                           first == 0, false, slab);
+    // (without counts the kernel is handed the owned levels' flag bytes, as otmb_facefluxes_rows_dev's caller hands them in)
+    FfCall c = ff_call(umo, vmo, src_is_f32, can ? wetflags : wetflags + slab->k_own0 * nx * ny, fill, nx, ny, nz, topology, phi);
+    c.top_below = top_below; c.push_mask = push_mask; c.flags = true; c.j0 = j0; c.j1 = j1; c.same_call = first == 0;
+    if (can) { c.counts = counts; c.slab = slab; }
+    return facefluxes_impl(ctx, c);
 }
 
 extern "C" int32_t otmb_facefluxes_counts_pending(const otmb_ctx *ctx) { return (ctx && ctx->ffc.valid) ? 1 : 0; }
@@ -971,7 +966,9 @@ extern "C" int32_t otmb_facefluxes_counts_pending(const otmb_ctx *ctx) { return 
 int32_t otmb_facefluxes_top_counts(otmb_ctx *ctx, const void *umo, const void *vmo, int32_t src_is_f32, const uint8_t *wetflags, double fill,
                                    int64_t nx, int64_t ny, int64_t nz, int32_t topology, double *const phi[6], uint16_t *token,
                                    const otmb_ff_counts *counts) {
-    return facefluxes_impl(ctx, umo, vmo, src_is_f32, wetflags, fill, nx, ny, nz, topology, phi, nullptr, token, false, true, counts, 0, -1, false, true);
+    FfCall c = ff_call(umo, vmo, src_is_f32, wetflags, fill, nx, ny, nz, topology, phi);
+    c.push_mask = token; c.flags = true; c.counts = counts; c.top_only = true;
+    return facefluxes_impl(ctx, c);
 }
 
 // Push mask of existing ϕ arrays (include/otmb.h): one thread per cell of [first, first + count).
