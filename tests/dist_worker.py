@@ -30,7 +30,9 @@ def run(rank, world, port, backend_kind, case, outdir):
     g = synthetic.make_slab(nx, ny, nz, k0, k1, seed=seed, rho=rho, topology=topo)
     gm = otmb_amd.makegridmetrics(areacello=g.areacello, volcello=g.volcello, lon=g.lon, lat=g.lat, lev=g.lev[k0:k1],
                                   lon_vertices=g.lon_vertices, lat_vertices=g.lat_vertices)
-    local = od.make_local_grid(gm, g.mlotst, g.rho, k0, k1, nz, g.lev, upwind=os.environ.get("OTMB_TEST_CENTRED") != "1")
+    # OTMB_TEST_ML_SCALE: the mixed layer so many times as deep (the synthetic one ends at 1000 m, far above level 64 of a deep grid)
+    mlotst = np.asfortranarray(g.mlotst * float(os.environ.get("OTMB_TEST_ML_SCALE", "1")))
+    local = od.make_local_grid(gm, mlotst, g.rho, k0, k1, nz, g.lev, upwind=os.environ.get("OTMB_TEST_CENTRED") != "1")
     if backend_kind == "hip":
         be = od.HipSlabBackend(rank if rccl else 0)
     else:

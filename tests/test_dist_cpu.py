@@ -25,13 +25,15 @@ def free_port():
     return p
 
 
-def whole_grid_reference(oracle, nx, ny, nz, seed, rho, topo, upwind=True):
+def whole_grid_reference(oracle, nx, ny, nz, seed, rho, topo, upwind=True, ml_scale=1.0):
+    """ml_scale: what the workers were told in OTMB_TEST_ML_SCALE (tests/dist_worker.py)."""
     g = synthetic.make_slab(nx, ny, nz, 0, nz, seed=seed, rho=rho, topology=topo)
+    mlotst = np.asfortranarray(g.mlotst * float(ml_scale))
     gm = otmb_amd.makegridmetrics(areacello=g.areacello, volcello=g.volcello, lon=g.lon, lat=g.lat, lev=g.lev,
                                   lon_vertices=g.lon_vertices, lat_vertices=g.lat_vertices)
     idx = oracle.makeindices(gm.v3D)
     phi = oracle.facefluxes(g.umo.data, g.vmo.data, idx["wet3D"], 1e20, gm.gridtopology.kind)
-    return idx, oracle.transportmatrix(phi, gm, idx, g.rho, g.mlotst, g.kappaH, g.kappaVML, g.kappaVdeep, upwind)
+    return idx, oracle.transportmatrix(phi, gm, idx, g.rho, mlotst, g.kappaH, g.kappaVML, g.kappaVdeep, upwind)
 
 
 def run_ranks(world, kind, case, outdir, timeout=300, async_mode=False, fault=None, rccl=False, pieces=None, extra_env=None):
@@ -49,12 +51,29 @@ def run_ranks(world, kind, case, outdir, timeout=300, async_mode=False, fault=No
     return np.load(os.path.join(outdir, "global.npz"))
 
 
-def check_against_whole_grid(oracle, z, case, upwind=True):
-    idx, ref = whole_grid_reference(oracle, *case, upwind=upwind)
+def check_against_whole_grid(oracle, z, case, upwind=True, ml_scale=1.0):
+    idx, ref = whole_grid_reference(oracle, *case, upwind=upwind, ml_scale=ml_scale)
     assert int(z["n"]) == idx["N"]
     for q, m in enumerate(MATS):
         got = (z[f"0_{q}"], z[f"1_{q}"], z[f"2_{q}"])
         assert_csc_equal(got, ref[m], m)
+    return idx, ref
+
+
+DEEP_SLABS = (24, 18, 130, 51, "array", "tripolar")  # depth slabs of more than 64 levels (tests/test_dist_gpu.py: the counting kernels' upper registers)
+
+
+def extended_slabs(case, world):
+    """Levels of every rank's extended local grid in a run of `case`: the slab the run's partition gives it, plus one halo level per
+    neighbouring slab."""
+    nx, ny, nz, seed, _, topo = case
+    parts = od.balanced_partition(synthetic.level_wet_counts(nx, ny, nz, seed=seed, topology=topo), world)
+    return [(k1 - k0) + (k0 > 0) + (k1 < nz) for k0, k1 in parts]
+
+
+def mixed_levels(idx, ref, P):
+    """Levels (0-based) of the cells whose column of TκVML holds an entry."""
+    return np.unique((idx["Lwet"][np.flatnonzero(np.diff(ref["TκVML"][0]) > 0)] - 1) // P)
 
 
 def test_balanced_partition_properties():
@@ -117,3 +136,15 @@ def test_slab_orchestration_gloo_world8_on_75_levels(oracle, tmp_path):
     case = (10, 8, 75, 24, "array", "tripolar")
     z = run_ranks(8, "oracle", case, tmp_path, async_mode=True)
     check_against_whole_grid(oracle, z, case)
+
+
+def test_slab_orchestration_gloo_deep_slabs_and_a_deep_mixed_layer(oracle, tmp_path):
+    """130 levels in three slabs, the mixed layer five times as deep (OTMB_TEST_ML_SCALE): some slab holds more than 64 levels and the
+    edge of the mixed layer passes level 64 -- the case of tests/test_dist_gpu.py, here with the oracle as backend, so that the
+    reference side of the switch is checked without a GPU."""
+    assert any(65 <= n <= 128 for n in extended_slabs(DEEP_SLABS, 3)), extended_slabs(DEEP_SLABS, 3)
+    z = run_ranks(3, "oracle", DEEP_SLABS, tmp_path, extra_env={"OTMB_TEST_ML_SCALE": "5"})
+    idx, ref = check_against_whole_grid(oracle, z, DEEP_SLABS, ml_scale=5)
+    assert mixed_levels(idx, ref, 24 * 18).max() >= 65
+    _, plain = whole_grid_reference(oracle, *DEEP_SLABS)
+    assert len(plain["TκVML"][1]) < len(ref["TκVML"][1])  # the scale does change the reference
