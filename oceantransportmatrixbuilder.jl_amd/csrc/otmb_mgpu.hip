@@ -139,6 +139,16 @@ int32_t mg_fail(otmb_mgpu *mg, int32_t st, const std::string &detail = std::stri
     return st;
 }
 
+// RCCL for n ranks of this process: the library, then the communicator; on failure `why` says which of the two was missing
+bool rccl_up(otmb_mgpu *mg, int n, const int32_t *device_ids, std::string &why) {
+    if (!mg->rccl.load(why)) return false;
+    mg->comms.assign(n, nullptr);
+    if (mg->rccl.CommInitAll(mg->comms.data(), n, device_ids) == ncclSuccess) return true;
+    mg->comms.clear();
+    why = "ncclCommInitAll failed";
+    return false;
+}
+
 template <typename F>
 void run_slabs(otmb_mgpu *mg, F &&fn) {  // one host thread per slab (the calling thread takes slab 0)
     const int n = (int)mg->slabs.size();
@@ -151,10 +161,69 @@ void run_slabs(otmb_mgpu *mg, F &&fn) {  // one host thread per slab (the callin
     if (caller_dev >= 0) (void)hipSetDevice(caller_dev);
 }
 
-int32_t reserve(Slab &sl, int b, size_t bytes, void **out) {
+template <typename T>
+int32_t reserve(Slab &sl, int b, size_t bytes, T **out) {
     const int32_t rc = otmb_reserve(sl.ctx, sl.buf[b], bytes ? bytes : 8);
-    *out = sl.buf[b].p;
+    *out = (T *)sl.buf[b].p;
     return rc;
+}
+
+// a slab's failure: its status and its context's message (collect_status reports the first one in the reference's order)
+void slab_fail(Slab &sl, int32_t st) {
+    sl.status = st;
+    sl.msg = otmb_last_error(sl.ctx);
+}
+
+bool enter(Slab &sl) {  // a slab thread's first step: its device
+    if (hipSetDevice(sl.device) == hipSuccess) return true;
+    otmb_fail(sl.ctx, OTMB_ERR_HIP, "hipSetDevice");
+    slab_fail(sl, OTMB_ERR_HIP);
+    return false;
+}
+
+// Scope guard: f runs on whatever path the scope is left by.  A slab thread that returned without releasing the thread that waits for
+// it would hang the call, so every such release (link_guard, plane_guard, publish_guard below) is one of these, never an early return's duty.
+template <typename F>
+struct AtExit {
+    F f;
+    ~AtExit() { f(); }
+};
+template <typename F>
+AtExit(F) -> AtExit<F>;
+
+// Slabs that share a device take its link in turn for their uploads.  A slab waits until ANOTHER one has left the link -- which one is
+// the caller's order: the nearest slab of its device below it (the facefluxes chain runs deepest first) or above it (the one-pass
+// build runs in slab order) -- and leaves when its own batch is through.
+struct LinkTurn {
+    std::mutex m;
+    std::condition_variable cv;
+    std::vector<char> left;
+    explicit LinkTurn(int n) : left(n, 0) {}
+    void wait_for(int other) {  // (other < 0: no slab of my device goes before me)
+        if (other < 0) return;
+        std::unique_lock<std::mutex> l(m);
+        cv.wait(l, [&] { return left[other] != 0; });
+    }
+    void leave(int s) {  // (idempotent)
+        { std::lock_guard<std::mutex> l(m); left[s] = 1; }
+        cv.notify_all();
+    }
+};
+
+// the nearest slab on the device of slab s, going up (dir = -1) or down (dir = +1) from it; -1: none
+int nearest_on_device(const otmb_mgpu *mg, int s, int dir) {
+    for (int q = s + dir; q >= 0 && q < (int)mg->slabs.size(); q += dir)
+        if (mg->slabs[q]->device == mg->slabs[s]->device) return q;
+    return -1;
+}
+
+// One slab of a device copies home at a time (`turns`: one mutex per device): two download streams side by side slowed the NEXT slab's
+// upload to 22 GB/s (profiles/r05/README.md section 9).  The turn ends with the slab's last DMA (otmb_xfer's link_free); its host
+// threads unpack the ring afterwards.
+int32_t download_in_turn(std::mutex (&turns)[16], Slab &sl, const std::vector<OtmbXferItem> &down) {
+    std::unique_lock<std::mutex> turn(turns[sl.device % 16]);
+    const std::function<void()> hand_on = [&] { if (turn.owns_lock()) turn.unlock(); };
+    return otmb_xfer(sl.ctx, false, down.data(), (int)down.size(), &hand_on);
 }
 
 // first failing slab in the reference's order; copies its message
@@ -260,13 +329,13 @@ void plan_slab(otmb_mgpu *mg, int s, const otmb_tm_args *a, const std::function<
     // for resident and build matrices from uninitialised memory.
     bool on_device = false;
     auto fail = [&](int32_t st) {
-        sl.status = st; sl.msg = otmb_last_error(sl.ctx);
+        slab_fail(sl, st);
         if (!on_device) {
             for (int b = 0; b < B_COUNT; ++b) sl.key[b] = Slab::Key();
             sl.phi_resident = false;
         }
     };
-    if (hipSetDevice(sl.device) != hipSuccess) { otmb_fail(sl.ctx, OTMB_ERR_HIP, "hipSetDevice"); return fail(OTMB_ERR_HIP); }
+    if (!enter(sl)) return fail(sl.status);
     const i64 e0 = sl.k0 - sl.ha, e1 = sl.k1 + sl.hb, nze = e1 - e0;
     const size_t Ge = (size_t)(nze * P), off = (size_t)e0 * P;
     otmb_tm_args d = *a;
@@ -276,7 +345,6 @@ void plan_slab(otmb_mgpu *mg, int s, const otmb_tm_args *a, const std::function<
     d.kept_ops = 0;  // (the slabs' outputs are staging: no promise)
     std::vector<OtmbXferItem> up;
     int32_t r;
-    void *p;
     // One staged array: uploaded unless the slot still holds this very host array (pointer, bytes, first level) and the caller has
     // promised not to have modified it (otmb_mgpu_set_reuse).  KIND 1: grid constant; 2: a face-flux array; 0: every call.
     auto put = [&](int B, const void *host, size_t bytes, int kind, void **out) -> int32_t {
@@ -297,46 +365,36 @@ void plan_slab(otmb_mgpu *mg, int s, const otmb_tm_args *a, const std::function<
         k.e0 = e0;
         return resident ? -1 : OTMB_OK;  // (-1: nothing was queued)
     };
+    // `count` elements from `host` on, staged in slot B; `field` (of the slab's arguments d) becomes the device array.  Returns what put returns.
+    auto stage = [&](int B, const auto *host, size_t count, int kind, auto &field) -> int32_t {
+        void *p = nullptr;
+        const int32_t rr = put(B, host, count * sizeof(*host), kind, &p);
+        field = static_cast<decltype(host)>(p);
+        return rr;
+    };
     // ϕ: what otmb_mgpu_facefluxes left on this device (already in the extended layout, halo fluxes filled in) is used when the
     // caller hands back the host arrays facefluxes wrote (reuse_fluxes); otherwise the levels [e0, e1) of the host arrays go up
     bool phi_here = mg->reuse_fluxes && sl.phi_resident && sl.buf[B_PHI0].cap >= Ge * 8;
     for (int f = 0; f < 6 && phi_here; ++f) phi_here = sl.phi_host[f] == (const void *)a->phi[f] && sl.buf[B_PHI0 + f].p;
     for (int f = 0; f < 6; ++f) {
-        if (phi_here) {
-            d.phi[f] = (const double *)sl.buf[B_PHI0 + f].p;
-        } else {
-            if ((r = put(B_PHI0 + f, (const char *)a->phi[f] + off * 8, Ge * 8, 0, &p)) > 0) return fail(r);
-            d.phi[f] = (const double *)p;
-        }
+        if (phi_here) d.phi[f] = (const double *)sl.buf[B_PHI0 + f].p;
+        else if ((r = stage(B_PHI0 + f, a->phi[f] + off, Ge, 0, d.phi[f])) > 0) return fail(r);
     }
     if (!phi_here) sl.phi_resident = false;
-    if ((r = put(B_V, (const char *)a->v3d + off * 8, Ge * 8, 1, &p)) > 0) return fail(r);
-    d.v3d = (const double *)p;
-    if ((r = put(B_THK, (const char *)a->thkcello + off * 8, Ge * 8, 1, &p)) > 0) return fail(r);
-    d.thkcello = (const double *)p;
-    if (a->rho) {
-        if ((r = put(B_RHO, (const char *)a->rho + off * 8, Ge * 8, 0, &p)) > 0) return fail(r);
-        d.rho = (const double *)p;
-    }
-    if ((r = put(B_LW, (const char *)a->lwet3d + off * 8, Ge * 8, 1, &p)) > 0) return fail(r);
-    d.lwet3d = (const int64_t *)p;
-    const int32_t lw_rc = put(B_LWET, (const char *)((const i64 *)a->lwet + sl.wet_base), (size_t)sl.n_own * 8, 1, &p);
+    if ((r = stage(B_V, a->v3d + off, Ge, 1, d.v3d)) > 0) return fail(r);
+    if ((r = stage(B_THK, a->thkcello + off, Ge, 1, d.thkcello)) > 0) return fail(r);
+    if (a->rho && (r = stage(B_RHO, a->rho + off, Ge, 0, d.rho)) > 0) return fail(r);
+    if ((r = stage(B_LW, a->lwet3d + off, Ge, 1, d.lwet3d)) > 0) return fail(r);
+    const int32_t lw_rc = stage(B_LWET, a->lwet + sl.wet_base, (size_t)sl.n_own, 1, d.lwet);
     if (lw_rc > 0) return fail(lw_rc);
-    d.lwet = (const int64_t *)p;
-    i64 *dlwet = (i64 *)p;
     const bool lwet_fresh = lw_rc == OTMB_OK;  // (a resident Lwet has been shifted to local indices already)
     for (int k = 0; k < 4; ++k) {
-        if ((r = put(B_EDGE0 + k, a->edge_length[k], (size_t)P * 8, 1, &p)) > 0) return fail(r);
-        d.edge_length[k] = (const double *)p;
-        if ((r = put(B_DIST0 + k, a->dist_nbr[k], (size_t)P * 8, 1, &p)) > 0) return fail(r);
-        d.dist_nbr[k] = (const double *)p;
+        if ((r = stage(B_EDGE0 + k, a->edge_length[k], (size_t)P, 1, d.edge_length[k])) > 0) return fail(r);
+        if ((r = stage(B_DIST0 + k, a->dist_nbr[k], (size_t)P, 1, d.dist_nbr[k])) > 0) return fail(r);
     }
-    if ((r = put(B_AREA, a->area2d, (size_t)P * 8, 1, &p)) > 0) return fail(r);
-    d.area2d = (const double *)p;
-    if ((r = put(B_ML, a->mlotst, (size_t)P * 8, 0, &p)) > 0) return fail(r);
-    d.mlotst = (const double *)p;
-    if ((r = put(B_ZT, a->zt + e0, (size_t)nze * 8, 1, &p)) > 0) return fail(r);
-    d.zt = (const double *)p;
+    if ((r = stage(B_AREA, a->area2d, (size_t)P, 1, d.area2d)) > 0) return fail(r);
+    if ((r = stage(B_ML, a->mlotst, (size_t)P, 0, d.mlotst)) > 0) return fail(r);
+    if ((r = stage(B_ZT, a->zt + e0, (size_t)nze, 1, d.zt)) > 0) return fail(r);
     // operators the caller passes (otmb_tm_args.given): this slab's columns -- colptr entries [wet_base, wet_base + n_own] (global numbering)
     // and the entries they delimit; grid constants of a time loop, so they fall under the reuse_grid promise
     for (int m = 1; m < 5; ++m) {
@@ -348,12 +406,9 @@ void plan_slab(otmb_mgpu *mg, int s, const otmb_tm_args *a, const std::function<
             return fail(OTMB_ERR_INVALID_ARG);
         }
         const int b0 = B_GIVEN0 + 3 * (m - 1);
-        if ((r = put(b0, g.colptr + sl.wet_base, (size_t)(sl.n_own + 1) * 8, 1, &p)) > 0) return fail(r);
-        d.given[m].colptr = (const int64_t *)p;
-        if ((r = put(b0 + 1, g.rowval + lo, (size_t)(hi - lo) * 8, 1, &p)) > 0) return fail(r);
-        d.given[m].rowval = (const int64_t *)p;
-        if ((r = put(b0 + 2, g.nzval + lo, (size_t)(hi - lo) * 8, 1, &p)) > 0) return fail(r);
-        d.given[m].nzval = (const double *)p;
+        if ((r = stage(b0, g.colptr + sl.wet_base, (size_t)(sl.n_own + 1), 1, d.given[m].colptr)) > 0) return fail(r);
+        if ((r = stage(b0 + 1, g.rowval + lo, (size_t)(hi - lo), 1, d.given[m].rowval)) > 0) return fail(r);
+        if ((r = stage(b0 + 2, g.nzval + lo, (size_t)(hi - lo), 1, d.given[m].nzval)) > 0) return fail(r);
         d.given[m].nnz = hi - lo;
     }
     if (before_upload) before_upload();  // (the pipelined build lets the slabs of one device take the link in turn)
@@ -362,7 +417,7 @@ void plan_slab(otmb_mgpu *mg, int s, const otmb_tm_args *a, const std::function<
     if (r) return fail(r);
     // Lwet of the owned cells as LOCAL linear indices of the extended grid (levels [e0, e1))
     if (lwet_fresh && sl.n_own > 0 && off > 0) {
-        hipLaunchKernelGGL(shift_i64_kernel, dim3((unsigned)((sl.n_own + 255) / 256)), dim3(256), 0, sl.ctx->stream, dlwet, sl.n_own, (i64)off);
+        hipLaunchKernelGGL(shift_i64_kernel, dim3((unsigned)((sl.n_own + 255) / 256)), dim3(256), 0, sl.ctx->stream, (i64 *)sl.buf[B_LWET].p, sl.n_own, (i64)off);
         if (hipGetLastError() != hipSuccess) { otmb_fail(sl.ctx, OTMB_ERR_HIP, "shift_i64_kernel"); return fail(OTMB_ERR_HIP); }
     }
     on_device = true;  // (errors from here on are the reference's own: the arrays ARE where the keys say)
@@ -382,6 +437,71 @@ unsigned wanted_mask(const otmb_tm_args &a) {
     for (int m = 1; m < 5; ++m)
         if (a.given[m].colptr) w &= ~(1u << m);
     return w;
+}
+
+// The prologue of a build (two-phase plan and one-pass): the checks of the arguments, the wet count per level, the cut.  outputs_ok is
+// the caller's verdict on its own output arguments, reported at its place in the order of the checks (behind the inputs').
+int32_t tm_begin(otmb_mgpu *mg, const otmb_tm_args *a, bool outputs_ok = true) {
+    if (a->nx < 1 || a->ny < 1 || a->nz < 1) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "grid size");
+    for (int f = 0; f < 6; ++f)
+        if (!a->phi[f]) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "phi");
+    for (int d = 0; d < 4; ++d)
+        if (!a->edge_length[d] || !a->dist_nbr[d]) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "metrics");
+    if (!a->v3d || !a->thkcello || !a->lwet3d || !a->area2d || !a->zt || !a->mlotst) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "null input array");
+    const i64 P = a->nx * a->ny, G = P * a->nz, N = a->n_wet;
+    if (N < 0 || N > G || (N > 0 && !a->lwet)) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "lwet / n_wet");
+    if (!outputs_ok) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "null output");
+    mg->planned = false;
+    // wet cells per level from Lwet (ascending 1-based linear indices, k slowest): positions of the level boundaries
+    std::vector<i64> counts(a->nz, 0);
+    i64 prev = 0;
+    for (i64 k = 0; k < a->nz; ++k) {
+        const i64 pos = (i64)(std::upper_bound(a->lwet, a->lwet + N, (k + 1) * P) - a->lwet);  // entries with L <= (k+1) P
+        counts[k] = pos - prev;
+        prev = pos;
+    }
+    if (prev != N) return mg_fail(mg, OTMB_ERR_NONCANONICAL_INDICES);
+    const int32_t rc = set_partition(mg, counts, a->nx, a->ny);
+    if (rc) return rc;
+    mg->args = *a;
+    mg->N = N;
+    return OTMB_OK;
+}
+
+// ---- a slab's fill and its way home: the steps of _fetch and _onepass ----
+struct SlabOut {  // the device arrays a slab's fill writes: those of the wanted matrices (bit m of `want`), null for the others
+    int64_t *cp[5] = {}, *rv[5] = {};
+    double *nz[5] = {};
+};
+
+int32_t reserve_outputs(Slab &sl, unsigned want, SlabOut &o) {
+    int32_t r;
+    for (int m = 0; m < 5; ++m)
+        if (((want >> m) & 1u) &&
+            ((r = reserve(sl, B_COLPTR0 + m, (size_t)(sl.n_own + 1) * 8, &o.cp[m])) || (r = reserve(sl, B_ROWVAL0 + m, (size_t)sl.nnz[m] * 8, &o.rv[m])) ||
+             (r = reserve(sl, B_NZVAL0 + m, (size_t)sl.nnz[m] * 8, &o.nz[m]))))
+            return r;
+    return OTMB_OK;
+}
+
+int32_t fill_slab(Slab &sl, const SlabOut &o) {  // behind sl.base; leaves the FINAL counts in sl.nnz (T may have lost entries that cancelled)
+    int32_t r;
+    if ((r = otmb_transportmatrix_set_nnz_base(sl.ctx, sl.base)) || (r = otmb_transportmatrix_fill_dev(sl.ctx, o.cp, o.rv, o.nz))) return r;
+    return otmb_transportmatrix_nnz(sl.ctx, sl.nnz);
+}
+
+// What goes home of matrix m of slab s, whose entries start at `base` of the caller's rowval / nzval: row indices (<= N) cross the link as
+// Int32 where they provably fit, column offsets as colptr_narrow says (otmb_xfer.h: `narrow`; 2 = one byte per column, for a column of
+// the matrices built here holds <= 7 entries).  The last slab's range ends with the matrix's closing offset.
+void add_download(std::vector<OtmbXferItem> &down, const otmb_mgpu *mg, int s, int m, i64 base, int64_t *colptr, int64_t *rowval, double *nzval,
+                  int colptr_narrow) {
+    const Slab &sl = *mg->slabs[s];
+    const bool last = s + 1 == (int)mg->slabs.size();
+    down.push_back({sl.buf[B_COLPTR0 + m].p, colptr + sl.wet_base, (size_t)(sl.n_own + (last ? 1 : 0)) * 8, colptr_narrow});
+    if (sl.nnz[m] > 0) {
+        down.push_back({sl.buf[B_ROWVAL0 + m].p, rowval + base, (size_t)sl.nnz[m] * 8, mg->N < ((i64)1 << 31)});
+        down.push_back({sl.buf[B_NZVAL0 + m].p, nzval + base, (size_t)sl.nnz[m] * 8});
+    }
 }
 
 }  // namespace
@@ -439,16 +559,13 @@ int32_t otmb_mgpu_create(int32_t ndev, const int32_t *device_ids, otmb_mgpu **ou
         sl->ctx->xfer_threads = std::max(1, std::min(8, (hw > 0 ? hw : 8) / ndev));
     }
     const char *tenv = getenv("OTMB_MGPU_TRANSPORT");
-    if (same && ndev == 1 && tenv && std::string(tenv) == "rccl") {
+    const std::string asked = tenv ? tenv : "";
+    std::string why;
+    if (same && ndev == 1 && asked == "rccl") {
         // (tests on a one-GPU box: load librccl.so and bring up a one-rank communicator, so that at least the loading and the
         // initialisation of the RCCL transport have run somewhere; a single slab never hands a plane over)
-        std::string why;
-        if (mg->rccl.load(why)) {
-            mg->comms.assign(1, nullptr);
-            if (mg->rccl.CommInitAll(mg->comms.data(), 1, device_ids) == ncclSuccess) mg->transport = 1;
-            else mg->comms.clear();
-        }
-        if (mg->transport != 1) { mg->err = "RCCL transport not available: " + (why.empty() ? std::string("ncclCommInitAll failed") : why); }
+        if (rccl_up(mg, 1, device_ids, why)) mg->transport = 1;
+        else mg->err = "RCCL transport not available: " + why;
     } else if (same) {
         mg->transport = 0;
     } else if (!distinct) {
@@ -457,15 +574,8 @@ int32_t otmb_mgpu_create(int32_t ndev, const int32_t *device_ids, otmb_mgpu **ou
     } else {
         // different devices: the single-process RCCL communicator (one rank per slab); peer copies only if RCCL cannot be loaded
         // or is refused by OTMB_MGPU_TRANSPORT=peer
-        const char *e = getenv("OTMB_MGPU_TRANSPORT");
-        const bool want_peer = e && std::string(e) == "peer";
-        mg->transport = 2;
-        std::string why;
-        if (!want_peer && mg->rccl.load(why)) {
-            mg->comms.assign(ndev, nullptr);
-            if (mg->rccl.CommInitAll(mg->comms.data(), ndev, device_ids) == ncclSuccess) mg->transport = 1;
-            else { mg->comms.clear(); why = "ncclCommInitAll failed"; }
-        }
+        const bool want_peer = asked == "peer";
+        mg->transport = !want_peer && rccl_up(mg, ndev, device_ids, why) ? 1 : 2;
         if (mg->transport == 2) {
             // which transport runs and why is the caller's to see (otmb_mgpu_last_error right after create, otmb_mgpu_transport; bench.py prints both)
             mg->err = want_peer ? "peer copies (OTMB_MGPU_TRANSPORT=peer)" : "peer copies, RCCL not used: " + why;
@@ -603,86 +713,63 @@ int32_t otmb_mgpu_facefluxes(otmb_mgpu *mg, const void *umo, const void *vmo, in
     }
     // Slabs that share a device take its link in turn: uploads deepest slab first (the chain's order), one slab downloading at a time -- the
     // deepest slab's six arrays go home while the slab above it uploads (the link is full duplex; section 9 of profiles/r05/README.md).
-    std::mutex turn_m;
-    std::condition_variable turn_cv;
-    std::vector<char> ff_uploaded(n, 0);
-    std::mutex ff_down_turn[16];
+    LinkTurn link(n);
+    std::mutex down_turn[16];
     run_slabs(mg, [&](int s) {
         Slab &sl = *mg->slabs[s];
-        int succ = -1;  // the nearest slab BELOW me on my device: I upload when it has
-        for (int q = s + 1; q < n && succ < 0; ++q)
-            if (mg->slabs[q]->device == sl.device) succ = q;
-        bool left = false;
-        auto leave_link = [&] {
-            if (left) return;
-            left = true;
-            { std::lock_guard<std::mutex> l(turn_m); ff_uploaded[s] = 1; }
-            turn_cv.notify_all();
-        };
-        struct Leave { std::function<void()> f; ~Leave() { f(); } } leave_guard{leave_link};  // (whatever path this slab returns by)
-        auto fail = [&](int32_t st) {
-            sl.status = st;
-            sl.msg = otmb_last_error(sl.ctx);
-            if (s > 0) fail_plane(mg, s - 1);
-        };
-        if (hipSetDevice(sl.device) != hipSuccess) { otmb_fail(sl.ctx, OTMB_ERR_HIP, "hipSetDevice"); return fail(OTMB_ERR_HIP); }
+        AtExit link_guard{[&] { link.leave(s); }};
+        // A slab that returns before all C pieces of its plane have left -- its own failure or that of the slab below it -- releases
+        // the slab above it, which is waiting for them.  Past the last piece there is nobody left to release.
+        int sent = 0;
+        AtExit plane_guard{[&] { if (s > 0 && sent < C) fail_plane(mg, s - 1); }};
+        if (!enter(sl)) return;
         const i64 nl = sl.k1 - sl.k0;
         const size_t Gl = (size_t)(nl * P), Ge = (size_t)((nl + sl.ha + sl.hb) * P);
-        void *du, *dv, *dw, *dplane, *dphi[6];
+        void *du, *dv, *dw, *dplane;
+        double *dp[6];
         int32_t r;
         sl.phi_resident = false;
         if ((r = reserve(sl, B_UMO, Gl * es, &du)) || (r = reserve(sl, B_VMO, Gl * es, &dv)) || (r = reserve(sl, B_WET, Gl, &dw)) ||
             (r = reserve(sl, B_PLANE, (size_t)P * 8, &dplane)))
-            return fail(r);
+            return slab_fail(sl, r);
         // the six ϕ arrays are kept in the layout otmb_mgpu_transportmatrix_plan wants (levels [k0 - ha, k1 + hb)): the owned levels are
         // computed in place behind the halo plane above; with otmb_mgpu_set_reuse(…, fluxes) the plan then uploads no ϕ at all
         for (int f = 0; f < 6; ++f) {
-            void *q;
-            if ((r = reserve(sl, B_PHI0 + f, Ge * 8, &q))) return fail(r);
+            double *q;
+            if ((r = reserve(sl, B_PHI0 + f, Ge * 8, &q))) return slab_fail(sl, r);
             sl.key[B_PHI0 + f] = Slab::Key();
-            if (sl.ha && hipMemsetAsync(q, 0, (size_t)P * 8, sl.ctx->stream) != hipSuccess) return fail(OTMB_ERR_HIP);
-            if (sl.hb && hipMemsetAsync((char *)q + (Ge - (size_t)P) * 8, 0, (size_t)P * 8, sl.ctx->stream) != hipSuccess) return fail(OTMB_ERR_HIP);
-            dphi[f] = (char *)q + (size_t)sl.ha * P * 8;
+            if (sl.ha && hipMemsetAsync(q, 0, (size_t)P * 8, sl.ctx->stream) != hipSuccess) return slab_fail(sl, OTMB_ERR_HIP);
+            if (sl.hb && hipMemsetAsync(q + (Ge - (size_t)P), 0, (size_t)P * 8, sl.ctx->stream) != hipSuccess) return slab_fail(sl, OTMB_ERR_HIP);
+            dp[f] = q + (size_t)sl.ha * P;
         }
         OtmbXferItem up[3] = {{du, (char *)umo + (size_t)sl.k0 * P * es, Gl * es}, {dv, (char *)vmo + (size_t)sl.k0 * P * es, Gl * es},
                               {dw, (char *)wet3d + (size_t)sl.k0 * P, Gl}};
-        if (succ >= 0) {
-            std::unique_lock<std::mutex> l(turn_m);
-            turn_cv.wait(l, [&] { return ff_uploaded[succ] != 0; });
-        }
+        link.wait_for(nearest_on_device(mg, s, +1));  // (the slab below me on my device: the chain's order)
         r = otmb_xfer(sl.ctx, true, up, 3);
-        leave_link();
-        if (r) return fail(r);
+        link.leave(s);
+        if (r) return slab_fail(sl, r);
         sl.uploaded += (i64)(2 * Gl * es + Gl);
-        double *dp[6];
-        for (int f = 0; f < 6; ++f) dp[f] = (double *)dphi[f];
         const bool by_event = !(mg->transport == 1 && s + 1 < n && mg->slabs[s + 1]->device != sl.device);
         for (int c = 0; c < C; ++c) {
             if (sl.hb) {  // the chain: piece c of ϕtop of the level below this slab
                 std::unique_lock<std::mutex> l(sl.m);
                 sl.cv.wait(l, [&] { return sl.pieces_ready > c; });
-                if (sl.plane_failed) {  // the slab below failed: its status is the one reported; release the slab above
-                    l.unlock();
-                    if (s > 0) fail_plane(mg, s - 1);
-                    return;
-                }
+                if (sl.plane_failed) return;  // the slab below failed: its status is the one reported (plane_guard releases the slab above)
                 l.unlock();
                 // (copy transports: this slab's stream waits for the copy of piece c -- an event, no host wait)
                 if (by_event && hipStreamWaitEvent(sl.ctx->stream, mg->slabs[s + 1]->piece_ev[c], 0) != hipSuccess) {
                     otmb_fail(sl.ctx, OTMB_ERR_HIP, "hipStreamWaitEvent");
-                    return fail(OTMB_ERR_HIP);
+                    return slab_fail(sl, OTMB_ERR_HIP);
                 }
             }
             if ((r = otmb_facefluxes_rows_dev(sl.ctx, du, dv, src_is_f32, (const uint8_t *)dw, fill, nx, ny, nl, topology, dp,
                                               sl.hb ? (const double *)dplane : nullptr, nullptr, jb[c], jb[c + 1], c == 0)))
-                return fail(r);
+                return slab_fail(sl, r);
             if (s > 0 && (r = send_piece(mg, s, s - 1, dp[OTMB_TOP], jb[c] * nx, (jb[c + 1] - jb[c]) * nx, c))) {  // ϕtop of this slab's first level goes up
                 otmb_fail(sl.ctx, r, sl.msg.empty() ? "plane hand-off" : sl.msg.c_str());
-                sl.status = r;
-                sl.msg = otmb_last_error(sl.ctx);
-                fail_plane(mg, s - 1);
-                return;
+                return slab_fail(sl, r);
             }
+            ++sent;
         }
         // the halo levels act as neighbours only; the one flux each of them pushes into an owned cell: the halo above pushes its ϕbottom =
         // this slab's first ϕtop (src/velocities.jl:240), the halo below its ϕtop = the plane received from the slab below
@@ -691,12 +778,7 @@ int32_t otmb_mgpu_facefluxes(otmb_mgpu *mg, const void *umo, const void *vmo, in
         if (sl.hb) halo_ok &= hipMemcpyAsync((char *)dp[OTMB_TOP] + Gl * 8, dplane, (size_t)P * 8, hipMemcpyDeviceToDevice, sl.ctx->stream) == hipSuccess;
         std::vector<OtmbXferItem> down;
         for (int f = 0; f < 6; ++f) down.push_back({dp[f], phi[f] + (size_t)sl.k0 * P, Gl * 8});
-        {
-            std::unique_lock<std::mutex> turn(ff_down_turn[sl.device % 16]);
-            const std::function<void()> hand_on = [&] { if (turn.owns_lock()) turn.unlock(); };
-            if ((r = otmb_xfer(sl.ctx, false, down.data(), (int)down.size(), &hand_on))) { sl.status = r; sl.msg = otmb_last_error(sl.ctx); return; }
-        }
-        if ((r = otmb_facefluxes_slab_flags(sl.ctx, &sl.u_valid, &sl.v_valid))) { sl.status = r; sl.msg = otmb_last_error(sl.ctx); return; }
+        if ((r = download_in_turn(down_turn, sl, down)) || (r = otmb_facefluxes_slab_flags(sl.ctx, &sl.u_valid, &sl.v_valid))) return slab_fail(sl, r);
         if (halo_ok) {
             sl.phi_resident = true;
             for (int f = 0; f < 6; ++f) sl.phi_host[f] = phi[f];
@@ -706,38 +788,14 @@ int32_t otmb_mgpu_facefluxes(otmb_mgpu *mg, const void *umo, const void *vmo, in
     bool u = false, v = false;
     for (Slab *sl : mg->slabs) { u |= sl->u_valid != 0; v |= sl->v_valid != 0; }
     if (!u || !v) return mg_fail(mg, OTMB_ERR_ALL_MISSING);  // @assert over the WHOLE grid (:199-200)
-    (void)n;
     return OTMB_OK;
 }
 
 // transportmatrix over the slabs, two-phase like otmb_transportmatrix_plan / _fetch: HOST pointers of the whole grid.
 int32_t otmb_mgpu_transportmatrix_plan(otmb_mgpu *mg, const otmb_tm_args *a, int64_t nnz[5]) {
     if (!mg || !a || !nnz) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "null argument");
-    if (a->nx < 1 || a->ny < 1 || a->nz < 1) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "grid size");
-    for (int f = 0; f < 6; ++f)
-        if (!a->phi[f]) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "phi");
-    for (int d = 0; d < 4; ++d)
-        if (!a->edge_length[d] || !a->dist_nbr[d]) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "metrics");
-    if (!a->v3d || !a->thkcello || !a->lwet3d || !a->area2d || !a->zt || !a->mlotst) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "null input array");
-    const i64 P = a->nx * a->ny, G = P * a->nz, N = a->n_wet;
-    if (N < 0 || N > G || (N > 0 && !a->lwet)) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "lwet / n_wet");
-    mg->planned = false;
-    // wet cells per level from Lwet (ascending 1-based linear indices, k slowest): positions of the level boundaries
-    std::vector<i64> counts(a->nz, 0);
-    {
-        const i64 *lw = (const i64 *)a->lwet;
-        i64 prev = 0;
-        for (i64 k = 0; k < a->nz; ++k) {
-            const i64 pos = (i64)(std::upper_bound(lw, lw + N, (k + 1) * P) - lw);  // entries with L <= (k+1) P
-            counts[k] = pos - prev;
-            prev = pos;
-        }
-        if (prev != N) return mg_fail(mg, OTMB_ERR_NONCANONICAL_INDICES);
-    }
     int32_t rc;
-    if ((rc = set_partition(mg, counts, a->nx, a->ny))) return rc;
-    mg->args = *a;
-    mg->N = N;
+    if ((rc = tm_begin(mg, a))) return rc;
     run_slabs(mg, [&](int s) { plan_slab(mg, s, a, nullptr, nullptr); });
     if ((rc = collect_status(mg))) return rc;
     for (int m = 0; m < 5; ++m) {
@@ -762,36 +820,14 @@ int32_t otmb_mgpu_transportmatrix_fetch(otmb_mgpu *mg, int64_t *const colptr[5],
     // since the plan); T's final count is only known now (entries that summed to exactly zero, src/matrixbuilding.jl:147)
     run_slabs(mg, [&](int s) {
         Slab &sl = *mg->slabs[s];
-        auto fail = [&](int32_t st) { sl.status = st; sl.msg = otmb_last_error(sl.ctx); };
-        if (hipSetDevice(sl.device) != hipSuccess) { otmb_fail(sl.ctx, OTMB_ERR_HIP, "hipSetDevice"); return fail(OTMB_ERR_HIP); }
+        if (!enter(sl)) return;
         int32_t r;
-        int64_t *dcp[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *drv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        double *dnz[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        void *p;
-        for (int m = 0; m < 5; ++m) {
-            if (!((want >> m) & 1u)) continue;
-            if ((r = reserve(sl, B_COLPTR0 + m, (size_t)(sl.n_own + 1) * 8, &p))) return fail(r);
-            dcp[m] = (int64_t *)p;
-            if ((r = reserve(sl, B_ROWVAL0 + m, (size_t)sl.nnz[m] * 8, &p))) return fail(r);
-            drv[m] = (int64_t *)p;
-            if ((r = reserve(sl, B_NZVAL0 + m, (size_t)sl.nnz[m] * 8, &p))) return fail(r);
-            dnz[m] = (double *)p;
-        }
-        if ((r = otmb_transportmatrix_set_nnz_base(sl.ctx, sl.base))) return fail(r);
-        if ((r = otmb_transportmatrix_fill_dev(sl.ctx, dcp, drv, dnz))) return fail(r);
-        if ((r = otmb_transportmatrix_nnz(sl.ctx, sl.nnz))) return fail(r);
+        SlabOut out;
+        if ((r = reserve_outputs(sl, want, out)) || (r = fill_slab(sl, out))) return slab_fail(sl, r);
         std::vector<OtmbXferItem> down;
-        const bool last = s + 1 == n;
-        const int small_rows = mg->N < ((i64)1 << 31);  // (otmb_xfer.h: `narrow`)
-        for (int m = 1; m < 5; ++m) {
-            if (!((want >> m) & 1u)) continue;
-            down.push_back({dcp[m], colptr[m] + sl.wet_base, (size_t)(sl.n_own + (last ? 1 : 0)) * 8, 2});  // (<= 7 entries per column: one byte each)
-            if (sl.nnz[m] > 0) {
-                down.push_back({drv[m], rowval[m] + sl.base[m], (size_t)sl.nnz[m] * 8, small_rows});
-                down.push_back({dnz[m], nzval[m] + sl.base[m], (size_t)sl.nnz[m] * 8});
-            }
-        }
-        if ((r = otmb_xfer(sl.ctx, false, down.data(), (int)down.size()))) return fail(r);
+        for (int m = 1; m < 5; ++m)
+            if ((want >> m) & 1u) add_download(down, mg, s, m, sl.base[m], colptr[m], rowval[m], nzval[m], 2);
+        if ((r = otmb_xfer(sl.ctx, false, down.data(), (int)down.size()))) return slab_fail(sl, r);
     });
     int32_t rc;
     if ((rc = collect_status(mg))) return rc;
@@ -802,21 +838,15 @@ int32_t otmb_mgpu_transportmatrix_fetch(otmb_mgpu *mg, int64_t *const colptr[5],
     run_slabs(mg, [&](int s) {
         Slab &sl = *mg->slabs[s];
         if (hipSetDevice(sl.device) != hipSuccess) { sl.status = OTMB_ERR_HIP; sl.msg = "hipSetDevice"; return; }
-        const bool last = s + 1 == n;
         std::vector<OtmbXferItem> down;
         // (T of a foreign build -- one slab only -- comes out of the sparse adds: no bound on a column's entries, Int32 offsets where they fit)
-        down.push_back({sl.buf[B_COLPTR0].p, colptr[0] + sl.wet_base, (size_t)(sl.n_own + (last ? 1 : 0)) * 8,
-                        otmb_tm_plan_foreign(sl.ctx) ? (mg->nnz[0] + 1 < ((i64)1 << 31) ? 1 : 0) : 2});
-        if (sl.nnz[0] > 0) {
-            down.push_back({sl.buf[B_ROWVAL0].p, rowval[0] + tbase[s], (size_t)sl.nnz[0] * 8, mg->N < ((i64)1 << 31)});
-            down.push_back({sl.buf[B_NZVAL0].p, nzval[0] + tbase[s], (size_t)sl.nnz[0] * 8});
-        }
+        add_download(down, mg, s, 0, tbase[s], colptr[0], rowval[0], nzval[0], otmb_tm_plan_foreign(sl.ctx) ? (mg->nnz[0] + 1 < ((i64)1 << 31) ? 1 : 0) : 2);
         const int32_t r = otmb_xfer(sl.ctx, false, down.data(), (int)down.size());
-        if (r) { sl.status = r; sl.msg = otmb_last_error(sl.ctx); return; }
+        if (r) return slab_fail(sl, r);
         const i64 delta = sl.base[0] - tbase[s];  // entries that the slabs above reserved and did not store
         if (delta > 0) {
             i64 *cp = colptr[0] + sl.wet_base;
-            const i64 cnt = sl.n_own + (last ? 1 : 0);
+            const i64 cnt = sl.n_own + (s + 1 == n ? 1 : 0);
             for (i64 q = 0; q < cnt; ++q) cp[q] -= delta;
         }
     });
@@ -839,38 +869,17 @@ int32_t otmb_mgpu_transportmatrix_fetch(otmb_mgpu *mg, int64_t *const colptr[5],
 int32_t otmb_mgpu_transportmatrix_onepass(otmb_mgpu *mg, const otmb_tm_args *a, int64_t *const colptr[5], int64_t *const rowval[5],
                                           double *const nzval[5], const int64_t capacity[5], int64_t nnz_out[5]) {
     if (!mg || !a || !colptr || !rowval || !nzval || !capacity || !nnz_out) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "null argument");
-    if (a->nx < 1 || a->ny < 1 || a->nz < 1) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "grid size");
-    for (int f = 0; f < 6; ++f)
-        if (!a->phi[f]) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "phi");
-    for (int d = 0; d < 4; ++d)
-        if (!a->edge_length[d] || !a->dist_nbr[d]) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "metrics");
-    if (!a->v3d || !a->thkcello || !a->lwet3d || !a->area2d || !a->zt || !a->mlotst) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "null input array");
-    const i64 P = a->nx * a->ny, G = P * a->nz, N = a->n_wet;
-    if (N < 0 || N > G || (N > 0 && !a->lwet)) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "lwet / n_wet");
     const unsigned want = wanted_mask(*a);
     const int n = (int)mg->slabs.size();
+    bool outputs_ok = true;
     for (int m = 0; m < 5; ++m)
-        if (((want >> m) & 1u) && (!colptr[m] || capacity[m] < 0 || (capacity[m] > 0 && (!rowval[m] || !nzval[m])))) return mg_fail(mg, OTMB_ERR_INVALID_ARG, "null output");
-    mg->planned = false;
-    std::vector<i64> counts(a->nz, 0);
-    {
-        const i64 *lw = (const i64 *)a->lwet;
-        i64 prev = 0;
-        for (i64 k = 0; k < a->nz; ++k) {
-            const i64 pos = (i64)(std::upper_bound(lw, lw + N, (k + 1) * P) - lw);
-            counts[k] = pos - prev;
-            prev = pos;
-        }
-        if (prev != N) return mg_fail(mg, OTMB_ERR_NONCANONICAL_INDICES);
-    }
+        if (((want >> m) & 1u) && (!colptr[m] || capacity[m] < 0 || (capacity[m] > 0 && (!rowval[m] || !nzval[m])))) outputs_ok = false;
     int32_t rc;
-    if ((rc = set_partition(mg, counts, a->nx, a->ny))) return rc;
-    mg->args = *a;
-    mg->N = N;
+    if ((rc = tm_begin(mg, a, outputs_ok))) return rc;
     // the pipeline's state: which slabs have left the link (uploads), which have published their final counts
+    LinkTurn link(n);
     std::mutex m;
     std::condition_variable cv;
-    std::vector<char> uploaded(n, 0);
     int published = 0;
     bool broken = false;  // a slab above failed: nobody below it stores anything
     i64 next_base[5] = {0, 0, 0, 0, 0};
@@ -880,19 +889,8 @@ int32_t otmb_mgpu_transportmatrix_onepass(otmb_mgpu *mg, const otmb_tm_args *a, 
     auto now_ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
     std::vector<std::array<double, 6>> stamps(n, std::array<double, 6>{{0, 0, 0, 0, 0, 0}});
     std::mutex down_turn[16];
-    const bool down_turns = !(getenv("OTMB_ONEPASS_DOWN_TURNS") && getenv("OTMB_ONEPASS_DOWN_TURNS")[0] == '0');
     run_slabs(mg, [&](int s) {
         Slab &sl = *mg->slabs[s];
-        int pred = -1;  // the nearest slab above me on MY device: I upload when it has
-        for (int q = s - 1; q >= 0 && pred < 0; --q)
-            if (mg->slabs[q]->device == sl.device) pred = q;
-        bool left_link = false;
-        auto leave_link = [&] {
-            if (left_link) return;
-            left_link = true;
-            { std::lock_guard<std::mutex> l(m); uploaded[s] = 1; }
-            cv.notify_all();
-        };
         bool have_published = false;
         auto publish = [&](bool ok) {  // my final counts are known (or never will be): release the slab below me
             if (have_published) return;
@@ -905,75 +903,38 @@ int32_t otmb_mgpu_transportmatrix_onepass(otmb_mgpu *mg, const otmb_tm_args *a, 
             }
             cv.notify_all();
         };
-        auto fail = [&](int32_t st) { sl.status = st; sl.msg = otmb_last_error(sl.ctx); };
-        plan_slab(mg, s, a,
-                  [&] {
-                      if (pred >= 0) {
-                          std::unique_lock<std::mutex> l(m);
-                          cv.wait(l, [&] { return uploaded[pred] != 0; });
-                      }
-                      stamps[s][0] = now_ms();
-                  },
-                  [&] { stamps[s][1] = now_ms(); leave_link(); }, true);
-        leave_link();  // (a slab that failed before its upload must not hold the link)
+        // a slab that returns before publish(true) -- its own failure or that of a slab above it -- publishes the failure
+        AtExit publish_guard{[&] { publish(false); }};
+        {
+            AtExit link_guard{[&] { link.leave(s); }};  // (a slab that failed before its upload must not hold the link)
+            const int pred = nearest_on_device(mg, s, -1);  // (the slab above me on my device: slab order)
+            plan_slab(mg, s, a, [&] { link.wait_for(pred); stamps[s][0] = now_ms(); }, [&] { stamps[s][1] = now_ms(); link.leave(s); }, true);
+        }
         stamps[s][2] = now_ms();
         {   // my turn to place my columns: every slab above me has published
             std::unique_lock<std::mutex> l(m);
             cv.wait(l, [&] { return published >= s; });
-            if (broken || sl.status != OTMB_OK) {
-                l.unlock();
-                return publish(false);
-            }
+            if (broken || sl.status != OTMB_OK) return;  // (l is released before publish_guard takes the mutex: it was locked later)
             for (int q = 0; q < 5; ++q) sl.base[q] = next_base[q];
         }
         stamps[s][3] = now_ms();
-        if (hipSetDevice(sl.device) != hipSuccess) { otmb_fail(sl.ctx, OTMB_ERR_HIP, "hipSetDevice"); fail(OTMB_ERR_HIP); return publish(false); }
+        if (!enter(sl)) return;
         for (int q = 0; q < 5; ++q)
             if (((want >> q) & 1u) && sl.base[q] + sl.nnz[q] > capacity[q]) {
                 otmb_fail(sl.ctx, OTMB_ERR_CAPACITY);
-                fail(OTMB_ERR_CAPACITY);
-                return publish(false);
+                return slab_fail(sl, OTMB_ERR_CAPACITY);
             }
         int32_t r;
-        int64_t *dcp[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *drv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        double *dnz[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        void *p;
-        for (int q = 0; q < 5; ++q) {
-            if (!((want >> q) & 1u)) continue;
-            if ((r = reserve(sl, B_COLPTR0 + q, (size_t)(sl.n_own + 1) * 8, &p))) { fail(r); return publish(false); }
-            dcp[q] = (int64_t *)p;
-            if ((r = reserve(sl, B_ROWVAL0 + q, (size_t)sl.nnz[q] * 8, &p))) { fail(r); return publish(false); }
-            drv[q] = (int64_t *)p;
-            if ((r = reserve(sl, B_NZVAL0 + q, (size_t)sl.nnz[q] * 8, &p))) { fail(r); return publish(false); }
-            dnz[q] = (double *)p;
-        }
-        if ((r = otmb_transportmatrix_set_nnz_base(sl.ctx, sl.base)) || (r = otmb_transportmatrix_fill_dev(sl.ctx, dcp, drv, dnz)) ||
-            (r = otmb_transportmatrix_nnz(sl.ctx, sl.nnz))) {
-            fail(r);
-            return publish(false);
-        }
+        SlabOut out;
+        if ((r = reserve_outputs(sl, want, out)) || (r = fill_slab(sl, out))) return slab_fail(sl, r);
         publish(true);  // (T's final count included: the slab below starts exactly where my entries end)
         stamps[s][4] = now_ms();
+        // (colptr as byte differences for T too: a foreign plan, whose T has no bound on a column's entries, never gets here --
+        // plan_slab(one_phase = true) has failed it with OTMB_ERR_GIVEN_FOREIGN)
         std::vector<OtmbXferItem> down;
-        const bool last = s + 1 == n;
-        // row indices (<= N) cross the link as Int32 where they provably fit, column offsets as one byte per column (otmb_xfer.h: `narrow`)
-        const int small_rows = N < ((i64)1 << 31);
-        for (int q = 0; q < 5; ++q) {
-            if (!((want >> q) & 1u)) continue;
-            down.push_back({dcp[q], colptr[q] + sl.wet_base, (size_t)(sl.n_own + (last ? 1 : 0)) * 8, 2});
-            if (sl.nnz[q] > 0) {
-                down.push_back({drv[q], rowval[q] + sl.base[q], (size_t)sl.nnz[q] * 8, small_rows});
-                down.push_back({dnz[q], nzval[q] + sl.base[q], (size_t)sl.nnz[q] * 8});
-            }
-        }
-        {   // One slab of a device copies home at a time: two download streams side by side slowed the NEXT slab's upload to 22 GB/s
-            // (profiles/r05/README.md section 9).  The turn ends with the slab's last DMA; its host threads unpack the ring afterwards.
-            // (experiment: OTMB_ONEPASS_DOWN_TURNS=0 lets the downloads overlap)
-            std::unique_lock<std::mutex> turn(down_turn[sl.device % 16], std::defer_lock);
-            if (down_turns) turn.lock();
-            const std::function<void()> hand_on = [&] { if (turn.owns_lock()) turn.unlock(); };
-            if ((r = otmb_xfer(sl.ctx, false, down.data(), (int)down.size(), &hand_on))) fail(r);
-        }
+        for (int q = 0; q < 5; ++q)
+            if ((want >> q) & 1u) add_download(down, mg, s, q, sl.base[q], colptr[q], rowval[q], nzval[q], 2);
+        if ((r = download_in_turn(down_turn, sl, down))) slab_fail(sl, r);
         stamps[s][5] = now_ms();
     });
     if (trace)

@@ -290,8 +290,8 @@ def test_mgpu_reuse_flags_keep_grid_and_fluxes_on_the_devices(oracle):
 def test_mgpu_facefluxes_chain_in_row_bands(oracle, ndev):
     """the chain over depth slabs is handed over piece by piece (row bands), slab s piece c waiting for slab s + 1 piece c
     only.  Any number of pieces -- 1, 2, 5 (bands of unequal height), one row per piece -- gives the oracle's six arrays bit for bit,
-    float32 inputs included; a hand-off that fails in the middle of the chain releases every slab (no deadlock), is reported, and
-    leaves the object usable."""
+    float32 inputs included; a hand-off that fails in the middle of the chain, or an upload that fails in every slab before its first
+    piece, releases every slab (no deadlock), is reported, and leaves the object usable."""
     import os
 
     import otmb_amd.api as api
@@ -318,6 +318,16 @@ def test_mgpu_facefluxes_chain_in_row_bands(oracle, ndev):
             assert "injected" in str(e.value)
         finally:
             del os.environ["OTMB_TEST_FAIL_PIECE"]
+        phi = api.facefluxesfrommasstransport(umo=g.umo, vmo=g.vmo, gridmetrics=gm, indices=idx, devices=devices)
+        for k in rphi:
+            assert np.array_equal(phi[k], rphi[k]), k
+        os.environ["OTMB_TEST_FAIL_UPLOAD"] = "1"  # every slab fails before its first piece: each releases the slab above it
+        try:
+            with pytest.raises(OtmbError) as e:
+                api.facefluxesfrommasstransport(umo=g.umo, vmo=g.vmo, gridmetrics=gm, indices=idx, devices=devices)
+            assert "injected" in str(e.value)
+        finally:
+            del os.environ["OTMB_TEST_FAIL_UPLOAD"]
         phi = api.facefluxesfrommasstransport(umo=g.umo, vmo=g.vmo, gridmetrics=gm, indices=idx, devices=devices)
         for k in rphi:
             assert np.array_equal(phi[k], rphi[k]), k
@@ -535,7 +545,10 @@ def test_onepass_places_every_slab_behind_the_final_counts_of_the_slabs_above(or
 @pytest.mark.gpu
 def test_onepass_errors_release_every_slab(oracle):
     """A failing slab in the middle of the pipeline: the slabs below it store nothing and return, the reference's error comes back with
-    the slab named, and the object builds the right matrices afterwards.  Too small an output array: OTMB_ERR_CAPACITY."""
+    the slab named, and the object builds the right matrices afterwards.  The same when every slab fails inside its upload turn.  Too
+    small an output array: OTMB_ERR_CAPACITY."""
+    import os
+
     import otmb_amd.api as api
     from otmb_amd import capi, synthetic
     from otmb_amd.capi import OtmbError
@@ -555,6 +568,17 @@ def test_onepass_errors_release_every_slab(oracle):
         tm = api.transportmatrix(ϕ=rphi, ρ=g.rho, **kw)
         for m in MATS:
             assert_csc_equal(tuple(tm[m]), rtm[m], m)
+    # every slab's upload fails (the host-side test hook of otmb_xfer.hip): each leaves the link and publishes the failure
+    os.environ["OTMB_TEST_FAIL_UPLOAD"] = "1"
+    try:
+        with pytest.raises(OtmbError) as e:
+            api.transportmatrix(ϕ=rphi, ρ=g.rho, **kw)
+        assert "injected" in str(e.value)
+    finally:
+        del os.environ["OTMB_TEST_FAIL_UPLOAD"]
+    tm = api.transportmatrix(ϕ=rphi, ρ=g.rho, **kw)
+    for m in MATS:
+        assert_csc_equal(tuple(tm[m]), rtm[m], m)
     # capacity: the C call with arrays one entry short for TκH
     keep, passthrough = [], []
     a = api._tm_args(rphi, g.mlotst, gm, idx, g.rho, g.kappaH, g.kappaVML, g.kappaVdeep, True, keep, passthrough)
