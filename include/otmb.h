@@ -394,9 +394,16 @@ typedef struct {
                                   * when its own record matches: the last writer of T's pattern into exactly these arrays, for these
                                   * arguments, finished without error or exact cancellation (a pending asynchronous step does not count).
                                   * Anything else writes T in full.  Two-phase protocol: fill must be handed the recorded arrays when the
-                                  * plan honoured the bit (otherwise OTMB_ERR_INVALID_ARG).                                              */
+                                  * plan honoured the bit (otherwise OTMB_ERR_INVALID_ARG).
+                                  * Bit 6, OTMB_KEPT_RHO: `rho` is the array, with the contents, of this context's previous successful
+                                  * call.  ρ is not among the kept operators' keys, so the library cannot know it is unchanged; with the
+                                  * promise, a fill that keeps all three operators and reads the neighbour table takes v3D and ρ (3-D
+                                  * only) from a table in wet-rank order that it builds from `rho` once (otmb_ctx_kept_vrtab;
+                                  * OTMB_KEPT_VRTAB=0: gathered as before).  Honoured on that path only; a call without the bit drops
+                                  * the table, so a loop whose ρ changes every step never builds it.                                   */
 } otmb_tm_args;
 #define OTMB_KEPT_T_PATTERN (1 << 5)
+#define OTMB_KEPT_RHO (1 << 6)
 /* The verdicts on otmb_tm_args.given are keyed to array ADDRESSES (the given matrix's and the gridmetrics / indices arrays') and κ.
  * A device-resident caller that rewrites one of those arrays in place calls this before the next transportmatrix; the host-pointer
  * entry points do it themselves whenever they upload such an array (i.e. always, unless otmb_ctx_set_reuse_grid promises otherwise). */
@@ -412,6 +419,10 @@ int32_t otmb_ctx_kept_htab(const otmb_ctx *ctx);
 /* ... and whether it took the neighbours' wet ranks from the context's per-grid table instead of gathering Lwet3D: 1 yes, 0 no
  * (OTMB_KEPT_NBTAB=0 or no TκH table, a depth slab, the table could not be allocated), -1 no such fill yet. */
 int32_t otmb_ctx_kept_nbtab(const otmb_ctx *ctx);
+/* ... and whether it took v3D and ρ from the context's {v3D, ρ} table in wet-rank order instead of gathering them: 1 yes, 0 no
+ * (no OTMB_KEPT_RHO promise, OTMB_KEPT_VRTAB=0 or no neighbour table, a scalar ρ, a depth slab, the table could not be allocated),
+ * -1 no such fill yet. */
+int32_t otmb_ctx_kept_vrtab(const otmb_ctx *ctx);
 /* ... and whether that fill stored T's values only (otmb_tm_args.kept_ops & OTMB_KEPT_T_PATTERN honoured): 1 yes, 0 no (T written in full),
  * -1 no such fill yet.  OTMB_KEPT_TPAT=0 in the environment always writes T in full. */
 int32_t otmb_ctx_kept_t_pattern(const otmb_ctx *ctx);

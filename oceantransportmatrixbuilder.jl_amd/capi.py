@@ -26,6 +26,7 @@ PHI_ORDER = ("east", "west", "north", "south", "top", "bottom")  # OTMB_EAST..OT
 HDIRS = ("west", "east", "south", "north")  # OTMB_DIR_*
 MATS = ("T", "Tadv", "TκH", "TκVML", "TκVdeep")  # OTMB_T..OTMB_TKVDEEP
 KEPT_T_PATTERN = 1 << 5  # OTMB_KEPT_T_PATTERN (otmb_tm_args.kept_ops): T's colptr / rowval are where this context last wrote T's pattern
+KEPT_RHO = 1 << 6        # OTMB_KEPT_RHO (otmb_tm_args.kept_ops): rho is the array, with the contents, of this context's previous successful call
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
@@ -138,6 +139,7 @@ SYMBOLS = {
     "otmb_ctx_ff_pairs": (C.c_int32, [_vp]),
     "otmb_ctx_kept_htab": (C.c_int32, [_vp]),
     "otmb_ctx_kept_nbtab": (C.c_int32, [_vp]),
+    "otmb_ctx_kept_vrtab": (C.c_int32, [_vp]),
     "otmb_ctx_kept_t_pattern": (C.c_int32, [_vp]),
     "otmb_ctx_kept_t_pattern_fills": (C.c_int64, [_vp]),
     "otmb_last_error": (C.c_char_p, [_vp]),
@@ -400,6 +402,10 @@ class Context:
     def kept_nbtab(self):
         """Whether that fill took its neighbours' wet ranks from the context's neighbour table: 1 yes, 0 no (Lwet3D gathered), -1 no such fill yet."""
         return int(self._lib.otmb_ctx_kept_nbtab(self._h))
+
+    def kept_vrtab(self):
+        """Whether that fill took v3D and ρ from the context's table in wet-rank order (KEPT_RHO honoured): 1 yes, 0 no (gathered), -1 no such fill yet."""
+        return int(self._lib.otmb_ctx_kept_vrtab(self._h))
 
     def kept_t_pattern(self):
         """Whether that fill stored T's values only, on the pattern of this context's last write of T (KEPT_T_PATTERN honoured): 1 yes, 0 no, -1 no such fill yet."""

@@ -28,7 +28,7 @@ struct SpPlan { const int64_t *I = nullptr, *J = nullptr; const double *V = null
 
 // kernel ids for the optional HIP-event timing (otmb_ctx_timing_*)
 enum {
-    K_TM_COUNT = 0, K_TILESCAN, K_TM_FILL, K_TM_FINISH, K_FACEFLUXES, K_IDX_COUNT, K_IDX_WRITE, K_VELFLUX, K_GM, K_GRIDMETRICS, K_PUSHMASK, K_TM_ORDER, K_FF_BASES, K_TM_HTAB, K_TM_NBTAB, K_NKERNELS
+    K_TM_COUNT = 0, K_TILESCAN, K_TM_FILL, K_TM_FINISH, K_FACEFLUXES, K_IDX_COUNT, K_IDX_WRITE, K_VELFLUX, K_GM, K_GRIDMETRICS, K_PUSHMASK, K_TM_ORDER, K_FF_BASES, K_TM_HTAB, K_TM_NBTAB, K_TM_VRTAB, K_NKERNELS
 };
 #define OTMB_TIMING_POOL 2048
 
@@ -153,6 +153,14 @@ struct otmb_ctx {
     bool nbtab_built = false; // it was built for htab_key
     size_t nbtab_nofit = 0;   // an allocation of this many bytes (both tables) failed: the TκH table alone is tried
     int nbtab_used = -1;      // the last fill that kept all three operators read the neighbour table (1) or gathered Lwet3D (0); -1: none yet
+    int nbtab_beyond = -1;    // the neighbour table names a rank beyond n_own (a first depth slab's halo level): 1, none: 0; -1: its word has not been read
+    // ... and the {v3D, ρ} table in wet-rank order (kept_vrtab, tm_vrtab_kernel), in a buffer of its own: valid while the two tables above are,
+    // ρ is the array it was built from and every call since promised that ρ is unchanged (OTMB_KEPT_RHO)
+    DevBuf vrtab;
+    bool vrtab_valid = false;
+    const void *vrtab_rho = nullptr;  // the ρ array it was built from
+    size_t vrtab_nofit = 0;   // an allocation of this many bytes failed: the kept fill gathers v3D and ρ instead
+    int vrtab_used = -1;      // the last fill that kept all three operators read it (1) or gathered v3D and ρ (0); -1: none yet (otmb_ctx_kept_vrtab)
     // ... and T's pattern (OTMB_KEPT_T_PATTERN): the last call that wrote T's full union pattern (colptr, rowval; nzval unused), its serial and
     // arguments.  nnz_known: that writer finished cleanly -- folded without error or FLAG_T_CANCEL, or a synchronous fill without cancellation --
     // and nnz is T's reserved count.  Dropped by a call that writes T elsewhere or not at all, a failed step that used it, a compaction of its

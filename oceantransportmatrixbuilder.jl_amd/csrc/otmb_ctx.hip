@@ -117,7 +117,7 @@ void otmb_ctx_destroy(otmb_ctx *ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     otmb_tm_plan_free(ctx);
     otmb_xfer_free(ctx);
-    for (DevBuf *b : {&ctx->blocksums, &ctx->blockoffs, &ctx->flags, &ctx->ring, &ctx->stamps, &ctx->tcount, &ctx->tfix[0], &ctx->tfix[1], &ctx->tfix[2], &ctx->tm_sums, &ctx->tm_offs, &ctx->sort[0], &ctx->sort[1], &ctx->sort[2], &ctx->sort[3], &ctx->sort[4], &ctx->ffc_sums[0], &ctx->ffc_sums[1], &ctx->xfer_narrow, &ctx->given_tmp[0], &ctx->given_tmp[1], &ctx->given_tmp[2], &ctx->given_tmp[3], &ctx->given_tmp[4], &ctx->given_tmp[5], &ctx->htab})
+    for (DevBuf *b : {&ctx->blocksums, &ctx->blockoffs, &ctx->flags, &ctx->ring, &ctx->stamps, &ctx->tcount, &ctx->tfix[0], &ctx->tfix[1], &ctx->tfix[2], &ctx->tm_sums, &ctx->tm_offs, &ctx->sort[0], &ctx->sort[1], &ctx->sort[2], &ctx->sort[3], &ctx->sort[4], &ctx->ffc_sums[0], &ctx->ffc_sums[1], &ctx->xfer_narrow, &ctx->given_tmp[0], &ctx->given_tmp[1], &ctx->given_tmp[2], &ctx->given_tmp[3], &ctx->given_tmp[4], &ctx->given_tmp[5], &ctx->htab, &ctx->vrtab})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : ctx->stage)
         if (b.p) (void)hipFree(b.p);
@@ -176,6 +176,7 @@ int64_t otmb_ctx_given_checks(const otmb_ctx *ctx) { return ctx ? (int64_t)ctx->
 int32_t otmb_ctx_ff_pairs(const otmb_ctx *ctx) { return ctx ? ctx->ff_pairs_last : -1; }
 int32_t otmb_ctx_kept_htab(const otmb_ctx *ctx) { return ctx ? ctx->htab_used : -1; }
 int32_t otmb_ctx_kept_nbtab(const otmb_ctx *ctx) { return ctx ? ctx->nbtab_used : -1; }
+int32_t otmb_ctx_kept_vrtab(const otmb_ctx *ctx) { return ctx ? ctx->vrtab_used : -1; }
 int32_t otmb_ctx_kept_t_pattern(const otmb_ctx *ctx) { return ctx ? ctx->tpat_used : -1; }
 int64_t otmb_ctx_kept_t_pattern_fills(const otmb_ctx *ctx) { return ctx ? (int64_t)ctx->tpat_fills : -1; }
 
@@ -224,7 +225,7 @@ const char *otmb_kernel_name(int32_t k) {
     static const char *names[K_NKERNELS] = {"tm_count_kernel", "tilescan_kernel", "tm_kernel<fill>", "tm_finish_colptr",
                                             "facefluxes_kernel", "indices_kernel<count>", "indices_kernel<write>",
                                             "velocity_flux_kernel", "gm_slopes+gm_dyad", "gridmetrics2d+3d",
-                                            "push_mask_kernel", "tm_order_kernels", "ff_count_bases_kernel", "tm_htab_kernel", "tm_nbtab_kernel"};
+                                            "push_mask_kernel", "tm_order_kernels", "ff_count_bases_kernel", "tm_htab_kernel", "tm_nbtab_kernel", "tm_vrtab_kernel"};
     return (k >= 0 && k < K_NKERNELS) ? names[k] : "";
 }
 

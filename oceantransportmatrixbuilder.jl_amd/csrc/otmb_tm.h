@@ -69,7 +69,7 @@ void otmb_tm_kept_decide(otmb_ctx *ctx, const otmb_tm_args &a, TmPlan &pl, int64
                          const int64_t capacity[5], bool two_phase);
 void otmb_tm_kept_plan_counts(otmb_ctx *ctx, TmPlan &pl, int64_t nnz[5]);
 int32_t otmb_tm_kept_check_fill(otmb_ctx *ctx, TmPlan &pl, int64_t *const colptr[5], int64_t *const rowval[5], double *const nzval[5]);
-void otmb_tm_kept_drop(otmb_ctx *ctx, unsigned keep);
+void otmb_tm_kept_drop(otmb_ctx *ctx, unsigned keep, bool rho_promised);
 int32_t otmb_tm_kept_before_fill(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl, TmParams &p, bool two_phase, bool *tpat);
 void otmb_tm_tpat_drop(otmb_ctx *ctx);
 void otmb_tm_kept_after_sync_fill(otmb_ctx *ctx, const TmPlan &pl, const TmParams &p, bool tpat, bool t_cancel);

@@ -77,6 +77,9 @@ struct TmParams {
     const double *htab;
     i64 htab_n;
     const int *htab_nan;
+    // (kept operators, with the neighbour table) the context's {v3D, ρ} table (tm_vrtab_kernel): of every owned column, in wet-rank order, one
+    // 16-byte record {v3D, ρ} at the column's cell.  NULL: the fill gathers v3D and ρ in cell order.  (Last: no other field moves.)
+    const void *vrtab;
 };
 // ... and, behind the TκH table in the same allocation (TmParams.nbtab != 0), the neighbour table (tm_nbtab_kernel): of every regular owned
 // column, in wet-rank order, one 16-byte record {S, N, A, B} (nb16) and one 8-byte record {E, W} (nb8) of 32-bit wet ranks, 0 = the neighbour
@@ -657,7 +660,12 @@ __device__ __forceinline__ i64 ldi(const char *b, unsigned byteoff) { return *(c
 // NB (with HTAB, wet_base == 0): the six neighbours' wet ranks are nb's (the neighbour table's records of this column, loaded by the caller with
 // Lwet[w]) instead of their six Lwet3D gathers, and the seventh, Lwet3D[c], is not issued either (the table's word is the canonical-indices
 // check: returns true).
-template <int FUSED = 0, bool HREAD = false, bool HTAB = false, bool NB = false>
+// VR (with NB, ρ 3-D): the seven {v3D, ρ} pairs come from the context's table in wet-rank order (p.vrtab: one 16-byte record per owned column,
+// scalar base + 32-bit offset (rank - 1) * 16) instead of 7 + 7 gathers in cell order.  A neighbour that does not exist or is dry (rank 0) loads
+// the column's own record and stays masked as before: every value that is used is bit for bit the gathered one.
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f64x2 ldvr(const char *b, unsigned byteoff) { return *(const f64x2 *)(b + byteoff); }
+template <int FUSED = 0, bool HREAD = false, bool HTAB = false, bool NB = false, bool VR = false>
 __device__ __forceinline__ bool fast_column(const TmParams &p, const TileBase &tb, unsigned oC, int i, int j, int k,
                                             i64 c, Column &col, Stamps &st, i64 hq = 0, const NbRec &nb = NbRec()) {
     const int nx = p.nx, ny = p.ny, nz = p.nz;
@@ -695,13 +703,25 @@ __device__ __forceinline__ bool fast_column(const TmParams &p, const TileBase &t
         gA0 = LDPHI(tb.pt, oC);         // ϕbottom[A] = ϕtop[c]  (:238-240)
         gB0 = LDPHI(tb.pt, oB);         // ϕtop[B]
     }
-    const double vC = ldv(tb.v, oC), vE = ldv(tb.v, oE), vW = ldv(tb.v, oW), vS = ldv(tb.v, oS), vN = ldv(tb.v, oN),
-                 vA = ldv(tb.v, oA), vB = ldv(tb.v, oB);
+    double vC, vE, vW, vS, vN, vA, vB;
     // (a scalar ρ is filled in AFTER the last load is issued: assigning it here makes the compiler drain the loads above first)
     double rC = 0, rE = 0, rW = 0, rS = 0, rN = 0, rA = 0, rB = 0;
-    if (tb.rho) {
-        rC = ldv(tb.rho, oC); rS = ldv(tb.rho, oS); rN = ldv(tb.rho, oN); rA = ldv(tb.rho, oA); rB = ldv(tb.rho, oB);
-        rE = ldv(tb.rho, oE); rW = ldv(tb.rho, oW);
+    if (VR) {
+        const char *vr = (const char *)p.vrtab;
+        const unsigned qC = (unsigned)(c - 1) * 16u;
+        const unsigned qE = nb.E ? (nb.E - 1u) * 16u : qC, qW = nb.W ? (nb.W - 1u) * 16u : qC, qS = nb.S ? (nb.S - 1u) * 16u : qC,
+                       qN = nb.N ? (nb.N - 1u) * 16u : qC, qA = nb.A ? (nb.A - 1u) * 16u : qC, qB = nb.B ? (nb.B - 1u) * 16u : qC;
+        const f64x2 xC = ldvr(vr, qC), xE = ldvr(vr, qE), xW = ldvr(vr, qW), xS = ldvr(vr, qS), xN = ldvr(vr, qN), xA = ldvr(vr, qA),
+                    xB = ldvr(vr, qB);
+        vC = xC.x; vE = xE.x; vW = xW.x; vS = xS.x; vN = xN.x; vA = xA.x; vB = xB.x;
+        rC = xC.y; rE = xE.y; rW = xW.y; rS = xS.y; rN = xN.y; rA = xA.y; rB = xB.y;
+    } else {
+        vC = ldv(tb.v, oC); vE = ldv(tb.v, oE); vW = ldv(tb.v, oW); vS = ldv(tb.v, oS); vN = ldv(tb.v, oN);
+        vA = ldv(tb.v, oA); vB = ldv(tb.v, oB);
+        if (tb.rho) {
+            rC = ldv(tb.rho, oC); rS = ldv(tb.rho, oS); rN = ldv(tb.rho, oN); rA = ldv(tb.rho, oA); rB = ldv(tb.rho, oB);
+            rE = ldv(tb.rho, oE); rW = ldv(tb.rho, oW);
+        }
     }
     double hg0 = 0, hg1 = 0, hg2 = 0, hg3 = 0, hg4 = 0;
     if (HREAD) {  // five consecutive entries from the column's first one (clamped to the array: entries beyond the column are never picked)
@@ -748,7 +768,7 @@ __device__ __forceinline__ bool fast_column(const TmParams &p, const TileBase &t
     }
 
     STAMP(st, 2, 1);  // every stencil load is back
-    if (!tb.rho) rC = rE = rW = rS = rN = rA = rB = p.rho_s;
+    if (!VR && !tb.rho) rC = rE = rW = rS = rN = rA = rB = p.rho_s;
     if (FUSED != 0) {
         // what facefluxes stores: a flux between two wet cells is the transport with NaN / fill replaced by zero, any other is zero
         // (nofluxboundaries! on the emitting cell, :161-175; c itself is wet)

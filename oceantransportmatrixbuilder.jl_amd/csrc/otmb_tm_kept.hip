@@ -13,6 +13,9 @@
 //   - a one-pass call stores them right after its enqueue, under the step's serial (kept_after_async_enqueue);
 //   - the table: its build has been enqueued in front of a kept fill (kept_htab).  The neighbour table (tm_nbtab_kernel) lives in the same
 //     allocation, is built with it and is valid exactly while it is (nbtab_built: false when it was not built for htab_key).
+//   - the {v3D, ρ} table (tm_vrtab_kernel, a buffer of its own): its build has been enqueued in front of a kept fill that reads the neighbour
+//     table and promised OTMB_KEPT_RHO (kept_vrtab); valid while the two tables above are, ρ is the array it was built from and every call
+//     since made the promise.
 // KNOWN (nnz_known): the writer has finished and nnz is its count.  At once for a synchronous fill; for an asynchronous step when it is folded
 //   without error -- for T also without FLAG_T_CANCEL -- and is still the record's writer (kept_on_fold).  The two-phase plan honours known
 //   records only, and only with no step pending: it hands the count out.  A one-pass call honours a valid kept_rec[m] whose arrays and capacity
@@ -21,6 +24,7 @@
 //   - kept_rec[m]: by every fill or one-pass call that does not keep m, before it enqueues anything (kept_drop; a plan drops nothing); all
 //     three by a fill that is refused (kept_check_fill); by its writer folding with an error (kept_on_fold).
 //   - the table: with kept_rec[TκH] (kept_drop); when it was built for other arguments (kept_htab rebuilds it); by a change of stream.
+//   - the {v3D, ρ} table: with the TκH table (htab_drop); by every fill or one-pass call without OTMB_KEPT_RHO (kept_drop); when ρ is another array.
 //   - tpat_rec: by a two-phase fill that does not take it, before its launch (a clean full write records itself afterwards), that fails its
 //     flags, or that compacts T; by a one-pass call that does not take it (the call is the new writer, or T stays unwritten: no record); by a
 //     folded step that took it and failed; by its writer folding with an error or a cancellation; by a compaction of the arrays it names
@@ -66,10 +70,13 @@ static void kept_store(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl, i
 }
 // every slot this call writes or leaves unwritten (all but the kept ones) loses its record before anything is enqueued -- and a call that does not
 // keep TκH, the TκH table: the table is valid only while no call has written TκH since it was built
-void otmb_tm_kept_drop(otmb_ctx *ctx, unsigned keep) {
+// -- and a call that does not promise OTMB_KEPT_RHO, the {v3D, ρ} table: ρ may have changed
+static void htab_drop(otmb_ctx *ctx) { ctx->htab_valid = false; ctx->vrtab_valid = false; }  // (the {v3D, ρ} table is valid only while the TκH table is)
+void otmb_tm_kept_drop(otmb_ctx *ctx, unsigned keep, bool rho_promised) {
     for (int m = OTMB_TKH; m <= OTMB_TKVDEEP; ++m)
         if (!((keep >> m) & 1u)) ctx->kept_rec[m].valid = false;
-    if (!((keep >> OTMB_TKH) & 1u)) ctx->htab_valid = false;
+    if (!((keep >> OTMB_TKH) & 1u)) htab_drop(ctx);
+    if (!rho_promised) ctx->vrtab_valid = false;
 }
 
 // A kept fill: all three operators kept and nothing of a given operator read (the instantiations tm_kernel<FUSED, 4 | 12>)
@@ -119,7 +126,8 @@ __global__ __launch_bounds__(256) void tm_htab_kernel(const TmParams p, double *
 // {S, N, A, B} (nb16) and one 8-byte record {E, W} (nb8) of 32-bit words, read by the fill with two coalesced loads.  One thread per column,
 // wet-rank order, once per grid.  Irregular columns (tripolar seam row) are not read back: build_column reads Lwet3D.  *word: Lwet3D[Lwet[w]] !=
 // w + 1 for some column, or a neighbour's entry lies outside 0 .. G and would not fit a word (the fill raises FLAG_NONCANONICAL from it).  wet_base == 0 and
-// G < 2^31 (the host's conditions): every rank fits a word.
+// G < 2^31 (the host's conditions): every rank fits a word.  word[1]: some rank exceeds n_own (a first depth slab names its halo level's ranks): the
+// {v3D, ρ} table, which holds the owned columns only, is then not used (kept_vrtab reads the word once per build).
 __global__ __launch_bounds__(256) void tm_nbtab_kernel(const TmParams p, unsigned *__restrict__ nb16, unsigned *__restrict__ nb8, int *word) {
     const i64 w = (i64)blockIdx.x * 256 + threadIdx.x;
     if (w >= p.n_own) return;
@@ -138,6 +146,7 @@ __global__ __launch_bounds__(256) void tm_nbtab_kernel(const TmParams p, unsigne
             // (G, not n_own: the first slab of a deeper grid has wet_base == 0 and names its halo level's ranks, which lie beyond n_own; ranks are
             // stored as row indices only, exactly as the gathers pass them on unverified -- the bound only keeps them inside a word)
             if (r < 0 || r > p.G) { raise_flag(word, 0); return 0u; }
+            if (r > p.n_own) raise_flag(word, 1);
             return (unsigned)r;
         };
         rE = rank(true, L + di_e); rW = rank(true, L + di_w); rS = rank(hS, L - nx); rN = rank(hN, L + nx);
@@ -165,6 +174,7 @@ static int32_t kept_htab(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl,
     if (!kept_is_kept_fill(pl, p)) return OTMB_OK;
     ctx->htab_used = 0;  // (otmb_ctx_kept_htab: set to 1 below once p points at a valid table)
     ctx->nbtab_used = 0;  // (otmb_ctx_kept_nbtab likewise)
+    ctx->vrtab_used = 0;  // (otmb_ctx_kept_vrtab likewise: kept_vrtab)
     if (!env_on || a.nx < 3 || a.n_wet <= 0) return OTMB_OK;
     const size_t n = (size_t)a.n_wet, vals = (size_t)NHTAB * n * sizeof(double), hbytes = vals + 256;  // (+ the NaN word)
     // ... and behind it, 256-byte aligned: the neighbour table's word, nb16, nb8.  Wanted when every rank fits a record's 31 bits: ranks count
@@ -174,7 +184,7 @@ static int32_t kept_htab(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl,
     bool want_nb = pl.wet_base == 0 && a.nx * a.ny * a.nz < (1ll << 31) && nbtab_env_on();
     if (want_nb && ctx->nbtab_nofit && nbbytes >= ctx->nbtab_nofit && ctx->htab.cap < nbbytes) want_nb = false;
     size_t bytes = want_nb ? nbbytes : hbytes;
-    if (ctx->htab_valid && !record_matches(ctx->htab_key, ctx, a, pl, OTMB_TKH, nullptr, 0)) ctx->htab_valid = false;
+    if (ctx->htab_valid && !record_matches(ctx->htab_key, ctx, a, pl, OTMB_TKH, nullptr, 0)) htab_drop(ctx);
     if (!ctx->htab_valid) {
         if (ctx->htab.cap < bytes) {
             if (ctx->htab_nofit && bytes >= ctx->htab_nofit) return OTMB_OK;  // (a size that did not fit is not tried again every step)
@@ -202,6 +212,8 @@ static int32_t kept_htab(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl,
             ctx->htab.cap = bytes;
         }
         ctx->nbtab_built = false;
+        ctx->nbtab_beyond = -1;
+        ctx->vrtab_valid = false;
         int *nanw = (int *)((char *)ctx->htab.p + vals);
         HIP_TRY(ctx, hipMemsetAsync(nanw, 0, sizeof(int), ctx->stream));
         {
@@ -212,7 +224,7 @@ static int32_t kept_htab(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl,
         if (want_nb) {
             char *b = (char *)ctx->htab.p;
             int *word = (int *)(b + lay.word);
-            HIP_TRY(ctx, hipMemsetAsync(word, 0, sizeof(int), ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(word, 0, 2 * sizeof(int), ctx->stream));
             {
                 KernelTimer kt(ctx, K_TM_NBTAB);
                 hipLaunchKernelGGL(tm_nbtab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, p, (unsigned *)(b + lay.nb16),
@@ -232,6 +244,70 @@ static int32_t kept_htab(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl,
     p.htab_n = (i64)n;
     p.htab_nan = (const int *)((const char *)ctx->htab.p + vals);
     ctx->htab_used = 1;
+    return OTMB_OK;
+}
+
+// ---- the kept operators' {v3D, ρ} table ---------------------------------------------------------------------------------------------------------
+// With the neighbour table in registers the largest group of gathers left in a regular column are 7 v3D and 7 ρ loads in CELL order.  The context
+// keeps both in WET-RANK order instead, one 16-byte record {v3D[Lwet[w] - 1], ρ[Lwet[w] - 1]} per owned column w, so the fill issues 7 loads of 16
+// bytes at the ranks the neighbour table names (fast_column<..., VR>).  The values are copied: every loaded value is bit for bit the gathered one.
+// v3D is a key of the TκH table's record; ρ is not (it is no grid constant), so the caller vouches for it: OTMB_KEPT_RHO.
+__global__ __launch_bounds__(256) void tm_vrtab_kernel(const TmParams p, double *__restrict__ tab) {
+    const i64 w = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (w >= p.n_own) return;
+    const i64 L = p.lwet[w] - 1;
+    const bool inside = L >= 0 && L < p.G;  // (indices that are not a makeindices result: the fill pass flags them)
+    f64x2 r;
+    r.x = inside ? p.v[L] : 0.0;
+    r.y = inside ? p.rho[L] : 0.0;
+    ((f64x2 *)tab)[w] = r;
+}
+// After kept_htab: point p at a valid {v3D, ρ} table when this fill reads the neighbour table (which implies wet_base == 0, nx >= 3 and a kept
+// fill), ρ is 3-D, every record's byte offset fits 32 bits, no neighbour rank lies beyond the owned columns and the caller promised
+// OTMB_KEPT_RHO -- building it first, on the call's stream in front of the fill, when none is valid.  OTMB_KEPT_VRTAB=0 (OTMB_KEPT_NBTAB=0 and
+// OTMB_KEPT_HTAB=0 imply it: no neighbour table), or a table that cannot be allocated: p is left alone, the fill gathers as before (no error).
+static int32_t kept_vrtab(otmb_ctx *ctx, const otmb_tm_args &a, TmParams &p) {
+    static const bool env_on = [] { const char *e = getenv("OTMB_KEPT_VRTAB"); return !(e && e[0] == '0'); }();
+    if (!p.nbtab || !p.htab) return OTMB_OK;
+    const size_t n = (size_t)a.n_wet, bytes = 16 * n;
+    if (!env_on || !a.rho || !(((unsigned)a.kept_ops & OTMB_KEPT_RHO) != 0) || bytes >= (1ull << 32)) return OTMB_OK;
+    if (ctx->nbtab_beyond < 0) {
+        // (once per build of the neighbour table: its word[1], whether a rank beyond n_own is named -- one stream synchronisation, like the tile order's)
+        int beyond = 1;
+        const int *word = (const int *)((const char *)ctx->htab.p + nb_layout(n).word);
+        HIP_TRY(ctx, hipMemcpyAsync(&beyond, word + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->nbtab_beyond = beyond != 0;
+    }
+    if (ctx->nbtab_beyond) return OTMB_OK;
+    if (ctx->vrtab_valid && ctx->vrtab_rho != (const void *)a.rho) ctx->vrtab_valid = false;
+    if (!ctx->vrtab_valid) {
+        if (ctx->vrtab.cap < bytes) {
+            if (ctx->vrtab_nofit && bytes >= ctx->vrtab_nofit) return OTMB_OK;  // (a size that did not fit is not tried again every step)
+            if (ctx->vrtab.p) {
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (earlier fills may still read it)
+                (void)hipFree(ctx->vrtab.p);
+                ctx->vrtab.p = nullptr;
+                ctx->vrtab.cap = 0;
+            }
+            if (hipMalloc(&ctx->vrtab.p, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                ctx->vrtab.p = nullptr;
+                ctx->vrtab_nofit = bytes;
+                return OTMB_OK;
+            }
+            ctx->vrtab.cap = bytes;
+        }
+        {
+            KernelTimer kt(ctx, K_TM_VRTAB);
+            hipLaunchKernelGGL(tm_vrtab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, p, (double *)ctx->vrtab.p);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        ctx->vrtab_rho = a.rho;
+        ctx->vrtab_valid = true;
+    }
+    p.vrtab = ctx->vrtab.p;
+    ctx->vrtab_used = 1;
     return OTMB_OK;
 }
 
@@ -308,13 +384,13 @@ int32_t otmb_tm_kept_check_fill(otmb_ctx *ctx, TmPlan &pl, int64_t *const colptr
         const void *out[3] = {colptr[m], rowval[m], nzval[m]};
         const otmb_ctx::KeptRecord &r = ctx->kept_rec[m];
         if (((pl.kept >> m) & 1u) && !(kept_matches(ctx, pl.args, pl, m, out, r.cap) && r.nnz_known && r.nnz == pl.nnz[m])) {
-            otmb_tm_kept_drop(ctx, 0);
+            otmb_tm_kept_drop(ctx, 0, false);
             pl.valid = false;
             return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "kept_ops: the output arrays of a kept operator are not the ones its record names (plan again without the bit)");
         }
     }
     if (pl.tpat && !(tpat_matches(ctx, pl.args, pl, colptr[0], rowval[0]) && ctx->tpat_rec.nnz == pl.nnz[0])) {
-        otmb_tm_kept_drop(ctx, 0);
+        otmb_tm_kept_drop(ctx, 0, false);
         otmb_tm_tpat_drop(ctx);
         pl.valid = false;
         return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "kept_ops: T's arrays are not the ones the OTMB_KEPT_T_PATTERN record names (plan again without the bit)");
@@ -328,6 +404,7 @@ int32_t otmb_tm_kept_before_fill(otmb_ctx *ctx, const otmb_tm_args &a, const TmP
     *tpat = false;
     int32_t rc;
     if ((rc = kept_htab(ctx, a, pl, p))) return rc;
+    if ((rc = kept_vrtab(ctx, a, p))) return rc;
     *tpat = tpat_take(ctx, a, pl, p, two_phase ? pl.tpat : true);
     if (two_phase && !*tpat) otmb_tm_tpat_drop(ctx);  // (T is written in full, or not at all: a clean write records itself, kept_after_sync_fill)
     return OTMB_OK;
@@ -392,6 +469,6 @@ void otmb_tm_kept_after_fixup(otmb_ctx *ctx, const void *colptrT, const void *ro
 // it (its NaN word is zeroed before the rebuild), so they finish first.
 void otmb_tm_kept_stream_changed(otmb_ctx *ctx) {
     if (ctx->htab_valid) (void)hipStreamSynchronize(ctx->stream);
-    ctx->htab_valid = false;
+    htab_drop(ctx);
     ctx->tpat_rec.valid = false;  // (T's values-only fills ride on the table's path)
 }

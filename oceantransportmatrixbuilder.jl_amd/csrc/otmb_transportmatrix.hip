@@ -140,12 +140,15 @@ static_assert(TM_THREADS == (1 << FFC_TILE_SHIFT), "the counts in facefluxes are
 // at nb_layout(htab_n): two streamed loads at the column's position in the tile, issued with Lwet[w]) instead of seven Lwet3D gathers in cell
 // order (the six neighbours' and the cell's own); the
 // canonical-indices check of Lwet3D was made when the table was built (its word).
+// GIVEN bit 5 -- VR (with NBTAB only, ρ 3-D): a regular column takes the seven {v3D, ρ} pairs from the context's table in wet-rank order
+// (TmParams.vrtab: seven 16-byte loads at the ranks the neighbour table names) instead of 7 + 7 gathers in cell order.
 template <int FUSED = 0, int GIVEN = 0>
 __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const TmParams p) {
     constexpr bool HREAD = (GIVEN & 1) != 0, DREAD = (GIVEN & 2) != 0, HTAB = (GIVEN & 4) != 0, TPAT = (GIVEN & 8) != 0;
-    constexpr bool NB = (GIVEN & 16) != 0;
-    static_assert(!HTAB || (GIVEN & ~(8 | 16)) == 4, "the table serves the kept operators: nothing is given then");
+    constexpr bool NB = (GIVEN & 16) != 0, VR = (GIVEN & 32) != 0;
+    static_assert(!HTAB || (GIVEN & ~(8 | 16 | 32)) == 4, "the table serves the kept operators: nothing is given then");
     static_assert(!NB || HTAB, "the neighbour table rides on the kept operators' path");
+    static_assert(!VR || NB, "the {v3D, rho} table is addressed by the neighbour table's ranks");
     static_assert(!TPAT || HTAB, "T's kept pattern rides on the kept operators' path");
 // (evaluated where used, as p.skip / p.keep were: a local copy at the top changes the other instantiations' register allocation)
 #define TM_SKIP (HTAB ? KEPT_OPS : p.skip)
@@ -286,7 +289,7 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
             bool canonical;
             const bool regular = (p.nx >= 3) && !(p.topo == OTMB_TRIPOLAR && cell.j == p.ny - 1);
             {
-                if (regular) canonical = fast_column<FUSED, HREAD, HTAB, NB>(p, tb, oC, cell.i, cell.j, cell.k, c, col, st, HTAB ? (i64)tid : hq, nb);  // (the value-free input checks ran with the counts)
+                if (regular) canonical = fast_column<FUSED, HREAD, HTAB, NB, VR>(p, tb, oC, cell.i, cell.j, cell.k, c, col, st, HTAB ? (i64)tid : hq, nb);  // (the value-free input checks ran with the counts)
                 else {
                     canonical = ldi(tb.lw, oC) == c;
                     if (canonical) {
@@ -506,7 +509,7 @@ __global__ void tm_finish_colptr(i64 *c0, i64 *c1, i64 *c2, i64 *c3, i64 *c4, i6
 
 // ---- host side ------------------------------------------------------------------------------
 // One launch site for the fill pass's instantiations: FUSED (the fused step's flux re-derivation) x GIVEN (a given TκH / TκVdeep read where it lies;
-// 4: the kept operators' TκH table, + 8: T's values only, + 16: the neighbour table).
+// 4: the kept operators' TκH table, + 8: T's values only, + 16: the neighbour table, + 32: the {v3D, ρ} table).
 template <int GIVEN> static void launch_fill_given(otmb_ctx *ctx, const TmParams &p, int fused, dim3 grid, dim3 block) {
     if (fused == 1) hipLaunchKernelGGL((tm_kernel<1, GIVEN>), grid, block, 0, ctx->stream, p);
     else if (fused == 2) hipLaunchKernelGGL((tm_kernel<2, GIVEN>), grid, block, 0, ctx->stream, p);
@@ -518,7 +521,10 @@ static void launch_fill(otmb_ctx *ctx, const TmParams &p, int fused, bool tpat =
     // (a derived TκH: reading is a choice -- regular cells only, OTMB_GIVEN_READ=0 re-derives; the derived rows with other values: it is the only way)
     const bool hread = p.hcp != nullptr && (p.hmust || (env_read && p.nx >= 3)), dread = p.dcp != nullptr;
     const dim3 grid(xcd_grid(p.nt_order, p.nheavy)), block(TM_THREADS);
-    if (p.htab && p.nbtab) {  // (... with the neighbour table: otmb_tm_kept.hip, kept_htab)
+    if (p.htab && p.nbtab && p.vrtab) {  // (... with the neighbour and {v3D, ρ} tables: otmb_tm_kept.hip, kept_vrtab)
+        if (tpat) launch_fill_given<12 | 16 | 32>(ctx, p, fused, grid, block);
+        else launch_fill_given<4 | 16 | 32>(ctx, p, fused, grid, block);
+    } else if (p.htab && p.nbtab) {  // (... with the neighbour table: otmb_tm_kept.hip, kept_htab)
         if (tpat) launch_fill_given<12 | 16>(ctx, p, fused, grid, block);
         else launch_fill_given<4 | 16>(ctx, p, fused, grid, block);
     } else if (p.htab && tpat) launch_fill_given<12>(ctx, p, fused, grid, block);
@@ -814,7 +820,7 @@ int32_t otmb_transportmatrix_fill_dev(otmb_ctx *ctx, int64_t *const colptr[5], i
     p.rho_in_fill = pl.rho_in_fill ? 1 : 0;
     int32_t rc;
     if ((rc = otmb_tm_kept_check_fill(ctx, pl, colptr, rowval, nzval))) return rc;
-    otmb_tm_kept_drop(ctx, pl.kept);
+    otmb_tm_kept_drop(ctx, pl.kept, ((unsigned)pl.args.kept_ops & OTMB_KEPT_RHO) != 0);
     if ((rc = tm_wire_outputs(ctx, pl, p, colptr, rowval, nzval, nullptr))) return rc;
     int *dflags = (int *)ctx->flags.p;
     bool tpat = false;
@@ -885,7 +891,7 @@ static int32_t transportmatrix_dev_impl(otmb_ctx *ctx, const otmb_tm_args *a, in
     // operators the caller kept (otmb_tm_args.kept_ops) whose record matches this call: re-derived in registers (T needs them), neither counted
     // nor stored -- their nnz come from the step that wrote them (fold_pending).  Every other operator slot loses its record here.
     otmb_tm_kept_decide(ctx, *a, pl, colptr, rowval, nzval, capacity, false);
-    otmb_tm_kept_drop(ctx, pl.kept);
+    otmb_tm_kept_drop(ctx, pl.kept, ((unsigned)a->kept_ops & OTMB_KEPT_RHO) != 0);
     TmParams p;
     otmb_tm_fill_params(p, *a, ctx, &pl);
     p.umo = fu.umo; p.vmo = fu.vmo; p.fillv = fu.fill; p.fused = fu.kind;

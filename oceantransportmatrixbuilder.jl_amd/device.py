@@ -674,6 +674,7 @@ class DeviceAssembler:
         self._kept_last = ()
         self._tpat = None
         self._tpat_last = False
+        self._rho_kept = None
         for rec in getattr(self, "_ops", {}).values():  # (and no operator's pattern can be vouched for any more)
             rec["ok"] = False
 
@@ -690,6 +691,17 @@ class DeviceAssembler:
             return False
         refs, key = self._tpat_key(out)
         return rec[1] == key and all(r() is t() for r, t in zip(rec[0], refs))
+
+    # ρ is no grid constant and none of the kept operators' keys, so the library cannot know that it is unchanged: OTMB_KEPT_RHO says that the
+    # ρ tensor is the one, at the version, of the last accepted call (by identity: a recycled address is another tensor).  The kept fill then
+    # takes v3D and ρ from a table it builds once; a loop whose ρ changes every step never makes the promise and never builds it.
+    def _rho_key(self):
+        rho = getattr(self, "rho", None)
+        return None if rho is None else (weakref.ref(rho), (rho.data_ptr(), rho._version))
+
+    def _rho_promise(self):
+        rec, now = getattr(self, "_rho_kept", None), self._rho_key()
+        return rec is not None and now is not None and rec[1] == now[1] and rec[0]() is now[0]()
 
     def _kept_key(self, out):
         # the output set's nine tensors (by identity: a recycled address is another set) and every grid array the three operators are derived from
@@ -709,7 +721,8 @@ class DeviceAssembler:
         if rec[1] != key or any(r() is not t() for r, t in zip(rec[0], refs)):
             return 0, ()
         self._tpat_last = self._tpat_promise(out)
-        return sum(1 << MATS.index(m) for m in self.KEPT) | (capi.KEPT_T_PATTERN if self._tpat_last else 0), self.KEPT
+        return (sum(1 << MATS.index(m) for m in self.KEPT) | (capi.KEPT_T_PATTERN if self._tpat_last else 0)
+                | (capi.KEPT_RHO if self._rho_promise() else 0)), self.KEPT
 
     def _kept_written(self, out, kept):
         """After a call into `out` was accepted: it wrote (or kept) the three operators unless some were given / not wanted."""
@@ -717,6 +730,7 @@ class DeviceAssembler:
         off = getattr(self, "given", None) or getattr(self, "only_T", False) or os.environ.get("OTMB_KEPT", "1") == "0"  # (OTMB_KEPT=0: A/B)
         self._kept = None if off else self._kept_key(out)
         self._tpat = None if off else self._tpat_key(out)  # (T's pattern: written by this call, or where the last one left it)
+        self._rho_kept = None if off else self._rho_key()  # (ρ as this call read it: OTMB_KEPT_RHO)
         self._ops_written(out, kept)
 
     # ---- resident operators (otmb_op_*): one per output matrix, re-planned unless its pattern is shown unchanged ----------------------------

@@ -30,19 +30,19 @@ __device__ __forceinline__ double ldv(const char *b, unsigned byteoff) { return 
 __device__ __forceinline__ double ldv(const char *b, unsigned byteoff) { return ldd(b, byteoff); }
 #endif
 """),
-("""    const double vC = ldv(tb.v, oC), vE = ldv(tb.v, oE), vW = ldv(tb.v, oW), vS = ldv(tb.v, oS), vN = ldv(tb.v, oN),
-                 vA = ldv(tb.v, oA), vB = ldv(tb.v, oB);
+("""        vC = ldv(tb.v, oC); vE = ldv(tb.v, oE); vW = ldv(tb.v, oW); vS = ldv(tb.v, oS); vN = ldv(tb.v, oN);
+        vA = ldv(tb.v, oA); vB = ldv(tb.v, oB);
 ""","""#ifdef OTMB_DBG_NOEW  // timing experiment only (wrong values): no second load instruction into lines that are in flight
-    const double vC = ldv(tb.v, oC), vE = vC, vW = vC, vS = ldv(tb.v, oS), vN = ldv(tb.v, oN), vA = ldv(tb.v, oA), vB = ldv(tb.v, oB);
+        vC = ldv(tb.v, oC); vE = vC; vW = vC; vS = ldv(tb.v, oS); vN = ldv(tb.v, oN); vA = ldv(tb.v, oA); vB = ldv(tb.v, oB);
 #else
-    const double vC = ldv(tb.v, oC), vE = ldv(tb.v, oE), vW = ldv(tb.v, oW), vS = ldv(tb.v, oS), vN = ldv(tb.v, oN),
-                 vA = ldv(tb.v, oA), vB = ldv(tb.v, oB);
+        vC = ldv(tb.v, oC); vE = ldv(tb.v, oE); vW = ldv(tb.v, oW); vS = ldv(tb.v, oS); vN = ldv(tb.v, oN);
+        vA = ldv(tb.v, oA); vB = ldv(tb.v, oB);
 #endif
 """),
-("        rE = ldv(tb.rho, oE); rW = ldv(tb.rho, oW);\n","""#ifdef OTMB_DBG_NOEW
-        rE = rC; rW = rC;
+("            rE = ldv(tb.rho, oE); rW = ldv(tb.rho, oW);\n","""#ifdef OTMB_DBG_NOEW
+            rE = rC; rW = rC;
 #else
-        rE = ldv(tb.rho, oE); rW = ldv(tb.rho, oW);
+            rE = ldv(tb.rho, oE); rW = ldv(tb.rho, oW);
 #endif
 """),
 ("""        tC = ldv(tb.thk, oC); tE = ldv(tb.thk, oE); tW = ldv(tb.thk, oW); tS = ldv(tb.thk, oS);
