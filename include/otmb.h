@@ -250,6 +250,13 @@ int32_t otmb_facefluxes_counts_pending(const otmb_ctx *ctx);
  * on contexts created under the same OTMB_FF_PAIRS and OTMB_FF_ROWS (tables of another geometry are recognised: the transportmatrix
  * then reports OTMB_ERR_PUSH_MASK, as for any counts that do not describe the fluxes).  No device work.                          */
 int32_t otmb_ctx_ff_pairs(const otmb_ctx *ctx);
+/* The tile scan of a transportmatrix.  Up to otmb_ctx_tm_infill_groups scan groups of 1024 tiles (64; OTMB_TM_INFILL_GROUPS = 0 .. 64,
+ * read when the context is created and clamped, lowers it for tests) a one-pass call scans inside the groups only and its fill pass adds
+ * the group bases; beyond, and in the two-phase plan, all scan levels run.  otmb_ctx_tm_infill: which of the two the last transportmatrix
+ * call with at least one tile took -- 1 the fill pass adds the bases, 0 all levels, -1 no such call yet.  The matrices are the same
+ * either way.  No device work.                                                                                                     */
+int32_t otmb_ctx_tm_infill_groups(const otmb_ctx *ctx);
+int32_t otmb_ctx_tm_infill(const otmb_ctx *ctx);
 /* The same two flags for EVERY facefluxes call on this context since the previous call of this function, oldest
  * first (a pipeline of asynchronous steps: the reference asserts per call, src/velocities.jl:199-200, so a field
  * without a single valid value in step 3 of 12 must not be hidden by steps 4-12).  Synchronises.  At most the 64

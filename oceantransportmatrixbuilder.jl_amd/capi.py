@@ -137,6 +137,8 @@ SYMBOLS = {
     "otmb_ctx_given_state": (C.c_int32, [_vp, C.c_int32]),
     "otmb_ctx_given_checks": (C.c_int64, [_vp]),
     "otmb_ctx_ff_pairs": (C.c_int32, [_vp]),
+    "otmb_ctx_tm_infill_groups": (C.c_int32, [_vp]),
+    "otmb_ctx_tm_infill": (C.c_int32, [_vp]),
     "otmb_ctx_kept_htab": (C.c_int32, [_vp]),
     "otmb_ctx_kept_nbtab": (C.c_int32, [_vp]),
     "otmb_ctx_kept_vrtab": (C.c_int32, [_vp]),
@@ -394,6 +396,14 @@ class Context:
     def ff_pairs(self):
         """Which kernel the last facefluxes call ran: 1 two levels per wave (facefluxes_pair_kernel), 0 one level per wave, -1 no call yet."""
         return int(self._lib.otmb_ctx_ff_pairs(self._h))
+
+    def tm_infill_groups(self):
+        """Up to how many scan groups of tile counts a one-pass transportmatrix leaves the group bases to its fill pass (64; OTMB_TM_INFILL_GROUPS)."""
+        return int(self._lib.otmb_ctx_tm_infill_groups(self._h))
+
+    def tm_infill(self):
+        """What the last transportmatrix call's tile scan did: 1 scanned inside the groups (the fill pass adds the bases), 0 all levels, -1 no call yet."""
+        return int(self._lib.otmb_ctx_tm_infill(self._h))
 
     def kept_htab(self):
         """Whether the last fill that kept TκH, TκVML and TκVdeep read TκH from the context's table: 1 yes, 0 no, -1 no such fill yet."""

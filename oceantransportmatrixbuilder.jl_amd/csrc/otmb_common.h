@@ -62,6 +62,9 @@ struct otmb_ctx {
     // fluxes a facefluxes call is writing are accumulated by that call (packed 64-bit atomics, one word per tile of 256 columns), so the
     // device-resident step has no counting pass.  Two buffers: the call after next may run beside the fill pass that consumes this one.
     int count_in_ff = 1;      // 0: otmb_facefluxes_counts_dev behaves as otmb_facefluxes_flags_dev (experiments / A-B: OTMB_COUNT_IN_FF)
+    int tm_infill_groups = 64;  // up to this many scan groups the fill pass adds the group bases itself; beyond, the one-pass protocol scans all
+                                // levels (tests reach that path on a grid of two groups: OTMB_TM_INFILL_GROUPS, 0 .. 64)
+    int tm_infill_last = -1;    // the last tile scan of a transportmatrix left the group bases to the fill pass (1) or scanned all levels (0); -1: none yet (otmb_ctx_tm_infill)
     DevBuf ffc_sums[2];
     bool ffc_dirty[2] = {true, true};  // the buffer is not known to be all zero
     int ffc_next = 0;

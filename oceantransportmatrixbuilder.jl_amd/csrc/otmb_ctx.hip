@@ -81,6 +81,7 @@ int32_t otmb_ctx_create(int32_t device_id, otmb_ctx **out) {
     if (const char *e = getenv("OTMB_COUNT_ORDER")) c->count_order = atoi(e);
     if (const char *e = getenv("OTMB_DEAL_HEAVY")) c->deal_heavy = atoi(e);
     if (const char *e = getenv("OTMB_COUNT_IN_FF")) c->count_in_ff = atoi(e);  // A/B in one library
+    if (const char *e = getenv("OTMB_TM_INFILL_GROUPS")) c->tm_infill_groups = atoi(e) < 0 ? 0 : (atoi(e) > 64 ? 64 : atoi(e));  // tests
     if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
         delete c;
         return OTMB_ERR_HIP;
@@ -174,6 +175,8 @@ int32_t otmb_ctx_forget_given(otmb_ctx *ctx) {
 int32_t otmb_ctx_given_state(const otmb_ctx *ctx, int32_t m) { return (ctx && m >= 0 && m < 5) ? ctx->given_state[m] : -1; }
 int64_t otmb_ctx_given_checks(const otmb_ctx *ctx) { return ctx ? (int64_t)ctx->given_checks : -1; }
 int32_t otmb_ctx_ff_pairs(const otmb_ctx *ctx) { return ctx ? ctx->ff_pairs_last : -1; }
+int32_t otmb_ctx_tm_infill_groups(const otmb_ctx *ctx) { return ctx ? ctx->tm_infill_groups : -1; }
+int32_t otmb_ctx_tm_infill(const otmb_ctx *ctx) { return ctx ? ctx->tm_infill_last : -1; }
 int32_t otmb_ctx_kept_htab(const otmb_ctx *ctx) { return ctx ? ctx->htab_used : -1; }
 int32_t otmb_ctx_kept_nbtab(const otmb_ctx *ctx) { return ctx ? ctx->nbtab_used : -1; }
 int32_t otmb_ctx_kept_vrtab(const otmb_ctx *ctx) { return ctx ? ctx->vrtab_used : -1; }

@@ -19,7 +19,6 @@
 #include "otmb_tm_column.h"
 #include "otmb_tm.h"
 
-#define TM_INFILL_GROUPS 64  // up to this many scan groups the fill pass adds the group bases itself
 #define TM_WSTAGE (64 * TM_MAXROWS + 2)  // per-wave staging entries (+2: parity shift for 16-byte stores)
 #define TM_STAGE ((TM_THREADS / 64) * TM_WSTAGE)
 
@@ -678,12 +677,13 @@ static int32_t tm_wire_outputs(otmb_ctx *ctx, const TmPlan &pl, TmParams &p, int
 }
 // The tile counts and their scan (pl.ntiles > 0): the counts that came with the fluxes (otmb_facefluxes_counts_dev; *fbuf: their buffer) and
 // the scan that unpacks them, or (*fbuf < 0) push mask -> tile order -> counting pass -> tile scan.  onepass: the totals stay on the device,
-// so up to TM_INFILL_GROUPS scan groups only the first scan level runs and the fill pass adds the group bases (p.gsum); the plan reads the
-// totals on the host and scans all levels.  fused: otmb_step_dev has no push mask to count from, its own facefluxes' counts must be there.
+// so up to ctx->tm_infill_groups scan groups (64; OTMB_TM_INFILL_GROUPS lowers it for tests) only the first scan level runs and the fill pass
+// adds the group bases (p.gsum); beyond, and in the plan, which reads the totals on the host, all levels are scanned
+// (ctx->tm_infill_last says which).  fused: otmb_step_dev has no push mask to count from, its own facefluxes' counts must be there.
 static int32_t tm_enqueue_counts(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl, TmParams &p, i64 *dtot, bool onepass, int fused, int *fbuf) {
     const i64 ntiles = pl.ntiles;
     i64 *offs = (i64 *)ctx->tm_offs.p, *gsum = offs + (ntiles + 1) * TM_NF;
-    const bool infill = onepass && ntiles <= TM_INFILL_GROUPS * OTMB_SCAN_GROUP;
+    const bool infill = onepass && ntiles <= (i64)ctx->tm_infill_groups * OTMB_SCAN_GROUP;
     int32_t rc;
     *fbuf = ffc_match(ctx, a, pl);
     if (*fbuf >= 0) {
@@ -703,6 +703,7 @@ static int32_t tm_enqueue_counts(otmb_ctx *ctx, const otmb_tm_args &a, const TmP
         else otmb_launch_tilescan(ctx->stream, p.tilesums, offs, dtot, ntiles, TM_NF, gsum);
     }
     if (infill) p.gsum = gsum;
+    ctx->tm_infill_last = infill ? 1 : 0;
     return OTMB_OK;
 }
 // No tile, so no fill kernel whose last tile would write them: the closing colptr entries, nnz_base (+ nnz, where a plan knows it) + 1
