@@ -821,6 +821,50 @@ int32_t otmb_op_step(otmb_op *op, int32_t adjoint, int64_t k, const double *d, d
                      const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
                      int64_t *iters, double *relres, int32_t *reason);
 
+/* ---- Observations of a state, and a record along the steps: obs[j, c] = Σ_i W[i, j]·X[i, c] for q observers -- the columns of W, n x q with
+ *      leading dimension ldw >= n: cell volumes for an inventory, a unit vector for a station, a region's weights -- and k tracers, X n x k
+ *      with ldx >= n, n the operator's columns.  obs: column-major q x k, entry j + q·c.  Rows beyond n are not read.
+ * The order of every sum is fixed by n alone and is a contract (tests/observe_ref.py restates it): the same call gives the same bits, and entry
+ *      (j, c) has the bits that observer and that tracer have alone, whatever q and k.
+ *        A workgroup has 256 lanes and takes 2048 rows; lane t of workgroup g takes the row pairs starting at rows 2·(1024·g + t + 256·p),
+ *        p = 0..3, in that order.  Within a lane acc starts at +0.0 and takes acc = acc + W[i,j]·X[i,c] for the pair's first row i, then for
+ *        row i + 1 if it is below n: one multiplication, one addition, no FMA.
+ *        The workgroup's sum: in each wave of 64 lanes xor shuffles at distances 32, 16, 8, 4, 2, 1 (x = x + the partner's x), then the four
+ *        waves' sums in wave order, ((w0 + w1) + w2) + w3: one partial per entry and workgroup.
+ *        An entry's partials are added in workgroup order, starting from partial 0.  n == 0: every entry is +0.0.
+ *      16-byte loads are taken where the base pointer is 16-byte aligned and the leading dimension even, 8-byte loads otherwise: the same bits.
+ * otmb_op_observe_dev: W, X, obs device pointers, enqueued on the context's stream.  otmb_op_observe: host pointers; W and X are staged
+ *      compactly and the call waits.  q == 0: nothing is done.  W and obs must not overlap X (not checked).
+ * q < 0, q > 0 with W or obs NULL or ldw < n, k < 1, ldx < n, X NULL with n > 0: OTMB_ERR_INVALID_ARG before anything is written, the message
+ *      names the call; the operator stays usable.
+ *
+ * otmb_op_step_obs[_dev]: otmb_op_step[_dev] -- the same 19 arguments, the same states, reports and stopping, bit for bit -- with a record:
+ *      after step t's solve has returned with every column converged, the pass above runs on the state where the solve left it.
+ *        obs: column-major (q, k, nsteps); obs[j + q·(c + k·t)] is observer j of tracer c after step t.
+ *        tw, Xbar (both or neither; NULL: no mean): tw holds nsteps finite weights, a HOST pointer in both variants; Xbar is n x k with
+ *        leading dimension ldm >= n.  After step t, in the same pass and from the same loads of X:  Xbar[i,c] = Xbar[i,c] + tw[t]·X[i,c], the
+ *        product first, then the sum (no FMA); at t = 0 the old value is +0.0, not what Xbar held.  With tw[t] = 1 / nsteps over one cycle
+ *        from the state otmb_op_periodic returned, Xbar is the cycle's mean state.
+ *      q == 0 runs no reduction, no mean stores nothing; with q == 0 and tw == NULL the call is otmb_op_step[_dev], which is this loop.
+ *      A step that does not converge, or a singular preconditioner, ends the call as it ends otmb_op_step: the blocks t >= *steps_done of obs
+ *      are left as passed in, and Xbar holds the fold over the completed steps (untouched when there were none).  n == 0: every observation
+ *      is +0.0.  nsteps == 0: nothing is touched.
+ *      otmb_op_step_obs_dev: d, S, X, W, obs, Xbar device pointers; the fold writes obs on the device and no wait for the host is added per
+ *      step.  otmb_op_step_obs: host pointers; W is staged once, and the written blocks of obs and Xbar come home once, when X does.
+ *      Refused with OTMB_ERR_INVALID_ARG before anything is written, after otmb_op_step's own checks, the message naming otmb_op_step_obs:
+ *      q < 0; q > 0 with W or obs NULL or ldw < n; one of tw / Xbar without the other; a weight that is not finite; ldm < n.
+ *      W, obs and Xbar must not overlap X or each other (not checked).                                                                  */
+int32_t otmb_op_observe_dev(otmb_op *op, int64_t k, int64_t q, const double *W, int64_t ldw, const double *X, int64_t ldx, double *obs);
+int32_t otmb_op_observe(otmb_op *op, int64_t k, int64_t q, const double *W, int64_t ldw, const double *X, int64_t ldx, double *obs);
+int32_t otmb_op_step_obs_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
+                             const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
+                             int64_t *iters, double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw,
+                             double *Xbar, int64_t ldm);
+int32_t otmb_op_step_obs(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
+                         const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
+                         int64_t *iters, double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw,
+                         double *Xbar, int64_t ldm);
+
 /* ---- The periodic (cyclo-stationary) state of the stepped cycle: x = F(x), F(x) = otmb_op_step_dev over ncycle >= 1 steps from first_slot
  *      with the source S (ncycle need not be a multiple of the slot count).  F is affine: F(x) = Φ·x + g, Φ·v the same call without S,
  *      g = F(0).  X returns the state at the START of the cycle with ‖F(x) - x‖₂ <= ptol·‖g‖₂, column by column.

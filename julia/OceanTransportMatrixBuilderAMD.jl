@@ -41,6 +41,7 @@ export solve!, solve
 export setlines!, verticallines, precondition!
 export setslots!, selectslot!, slots, step!   # (`step` extends Base.step for this module's operators: nothing to export)
 export periodic!, periodic, combineslots!
+export observe, stepobserve!
 
 const LIBPATH = get(ENV, "OTMB_HIP_LIB", joinpath(@__DIR__, "..", "oceantransportmatrixbuilder.jl_amd", "lib", "libotmb_hip.so"))
 const lib = Ref{Ptr{Cvoid}}(C_NULL)
@@ -538,6 +539,72 @@ function step!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDevic
                converged = why .== :converged)
 end
 Base.step(D::Union{DeviceOperator,AdjointDeviceOperator}, X::StridedVecOrMat{Float64}; kwargs...) = step!(copy(X), D; kwargs...)
+
+# Observers W (n x q, or n values: one observer) of an operator with n columns: (q, the leading dimension of W).
+function observerdims(op::DeviceOperator, W)
+    size(W, 1) == op.n || throw(DimensionMismatch("operator of $((op.m, op.n)), observers $(size(W))"))
+    stride(W, 1) == 1 || throw(ArgumentError("the observers need contiguous columns"))
+    q = size(W, 2)
+    return q, (W isa AbstractVector || q <= 1 ? max(op.n, 1) : stride(W, 2))
+end
+# Wᵀ·X on the device (otmb_op_observe; include/otmb.h states the order of the sums): the inventory (W = the cell volumes), stations, regional
+# means of the state X.  Returns a q x k matrix: entry (j, c) is observer j of tracer c.
+function observe(D::DeviceOperator, W::StridedVecOrMat{Float64}, X::StridedVecOrMat{Float64})
+    size(X, 1) == D.n || throw(DimensionMismatch("operator of $((D.m, D.n)), X $(size(X))"))
+    stride(X, 1) == 1 || throw(ArgumentError("X needs contiguous columns"))
+    k = size(X, 2)
+    ldx = X isa AbstractVector || k <= 1 ? max(D.n, 1) : stride(X, 2)
+    q, ldw = observerdims(D, W)
+    obs = zeros(Float64, q, k)
+    lock(CALL_LOCK) do
+        D.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        observe_fn = sym(:otmb_op_observe)
+        check(ccall(observe_fn, Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}),
+            D.handle, k, q, W, ldw, X, ldx, obs))
+    end
+    return obs
+end
+# step! with a record along the way (otmb_op_step_obs): `observers` (n x q) are applied to the state after every completed step, and
+# `timeweights` (nsteps values) fold the states into their weighted mean.  X is overwritten as by step!.  Returns (X, info): step!'s fields and
+# info.observations (q x k x stepsdone: [j, c, t] is observer j of tracer c after step t; nothing without observers) and info.mean (n x k,
+# Σ_t timeweights[t]·X_t over the completed steps; nothing without weights or when no step was completed).
+function stepobserve!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}; dt::Real, θ::Real = 1.0, nsteps::Integer = 1,
+                      firstslot::Integer = 1, source::Union{Nothing,StridedVecOrMat{Float64}} = nothing, d::Union{Nothing,Vector{Float64}} = nothing,
+                      rtol::Real = 1e-10, maxiter::Integer = 10000, precond::Symbol = :jacobi,
+                      observers::Union{Nothing,StridedVecOrMat{Float64}} = nothing, timeweights::Union{Nothing,Vector{Float64}} = nothing)
+    pc = precondcode(precond)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    S = source === nothing ? X : source
+    k, lds, ldx = systemdims(op, S, "source", X, "X", d)
+    nrep = max(Int64(nsteps), 0)
+    iters = zeros(Int64, k, nrep)
+    relres = zeros(Float64, k, nrep)
+    reason = zeros(Int32, k, nrep)
+    done = Ref{Int64}(0)
+    q, ldw = observers === nothing ? (0, max(op.n, 1)) : observerdims(op, observers)
+    obs = zeros(Float64, q, k, nrep)
+    timeweights === nothing || length(timeweights) == nrep || throw(DimensionMismatch("timeweights of $(length(timeweights)), nsteps $nrep"))
+    Xbar = timeweights === nothing ? nothing : zeros(Float64, size(X)...)
+    ldm = max(op.n, 1)
+    lock(CALL_LOCK) do
+        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        step_obs_fn = sym(:otmb_op_step_obs)
+        rc = ccall(step_obs_fn, Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Float64, Float64, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                Float64, Int64, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64},
+                Ptr{Float64}, Int64),
+            op.handle, Int32(adjoint), k, d === nothing ? C_NULL : d, Float64(dt), Float64(θ), Int64(nsteps), Int64(firstslot - 1),
+            source === nothing ? C_NULL : source, lds, X, ldx, Float64(rtol), Int64(maxiter), pc, done, iters, relres, reason,
+            Int64(q), observers === nothing ? C_NULL : observers, ldw, observers === nothing ? C_NULL : obs,
+            timeweights === nothing ? C_NULL : timeweights, Xbar === nothing ? C_NULL : Xbar, ldm)
+        rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which step and column stopped why
+    end
+    ran = 1:min(done[] + 1, nrep)
+    why = permutedims([SOLVE_REASONS[r + 1] for r in reason[:, ran]])
+    return X, (stepsdone = done[], iterations = permutedims(iters[:, ran]), relres = permutedims(relres[:, ran]), reason = why,
+               converged = why .== :converged, observations = observers === nothing ? nothing : obs[:, :, 1:done[]],
+               mean = done[] > 0 ? Xbar : nothing)
+end
 
 const PERIODIC_REASONS = (:converged, :maxcycles, :step_failed, :nonfinite)   # otmb_periodic_reason
 # The periodic state of the stepped cycle (otmb_op_periodic; include/otmb.h states the method): X with F(X) = X, F = `ncycle` steps of length

@@ -821,10 +821,15 @@ class SolveInfo:
 class StepInfo:
     """What otmb_op_step reports: status (0, or capi.NOT_CONVERGED), steps_done (steps completed with every column converged) and, one row
     per step that ran a solve (steps 0 .. min(steps_done, nsteps - 1)) and one entry per column: iterations, relres, reason (tuples of
-    "converged", "maxiter", "breakdown", "nonfinite") and converged -- each as SolveInfo has them for one solve."""
+    "converged", "maxiter", "breakdown", "nonfinite") and converged -- each as SolveInfo has them for one solve.  From
+    step(..., observe=W): observations, (steps_done, k, q), entry [t, c, j] = observer j of tracer c after step t (only the steps that were
+    completed); from step(..., time_weights=w): mean, n x k (n values for a 1-D state) = Σ_t w[t]·X_t over the completed steps, None when
+    no step was.  Both None otherwise."""
 
-    def __init__(self, status, steps_done, nsteps, iterations, relres, reason):
+    def __init__(self, status, steps_done, nsteps, iterations, relres, reason, observations=None, mean=None):
         self.status, self.steps_done = int(status), int(steps_done)
+        self.observations = None if observations is None else observations[:self.steps_done]
+        self.mean = mean if self.steps_done > 0 else None
         ran = min(self.steps_done + 1, int(nsteps))
         self.iterations = np.asarray(iterations, dtype=np.int64)[:ran]
         self.relres = np.asarray(relres, dtype=np.float64)[:ran]
@@ -833,6 +838,22 @@ class StepInfo:
 
     def __repr__(self):
         return f"StepInfo(status={self.status}, steps_done={self.steps_done}, iterations={self.iterations.tolist()}, reason={self.reason})"
+
+
+def observers(W, n):
+    """(W as a 2-D array n x q, q) of step(..., observe=W) / observe(W, X): n values are one observer."""
+    shape = tuple(W.shape)
+    if len(shape) not in (1, 2) or shape[0] != n:
+        raise capi.OtmbError(11, f"DimensionMismatch: observers of {shape}, expected {n} rows")
+    return (W.reshape(n, 1) if len(shape) == 1 else W), (1 if len(shape) == 1 else shape[1])
+
+
+def time_weights(w, nsteps):
+    """The mean's weights as nsteps float64 host values."""
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if w.shape != (max(int(nsteps), 0),):
+        raise capi.OtmbError(11, f"DimensionMismatch: time_weights of {w.shape}, expected {(max(int(nsteps), 0),)}")
+    return w
 
 
 def step_arrays(nsteps, k):
@@ -886,7 +907,7 @@ class DeviceOperator:
     A: a SparseMatrixCSC (1-based).  The operator owns device copies of A: the arrays may change or go once the constructor returns.
     The same C calls as the Julia shim's DeviceOperator: otmb_op_create; mul! -> otmb_op_mul; setvalues! -> otmb_op_set_values; solve! ->
     otmb_op_solve_pc; setlines! -> otmb_op_set_lines; precondition! -> otmb_op_precond; setslots! / selectslot! / step! -> otmb_op_set_slots /
-    otmb_op_select_slot / otmb_op_step; periodic! -> otmb_op_periodic (outer = :mean: otmb_op_periodic_pc); combineslots! ->
+    otmb_op_select_slot / otmb_op_step; observe / stepobserve! -> otmb_op_observe / otmb_op_step_obs; periodic! -> otmb_op_periodic (outer = :mean: otmb_op_periodic_pc); combineslots! ->
     otmb_op_combine_slots; the finalizer -> otmb_op_destroy."""
 
     def __init__(self, A, *, device=0):
@@ -1043,6 +1064,23 @@ class DeviceOperator:
             self.ctx.check(rc)
         return X, SolveInfo(rc, iters, relres, reason)
 
+    def observe(self, W, X):
+        """Wᵀ·X on the device (otmb_op_observe; include/otmb.h states the order of the sums): W n x q (or n values: one observer), X n x k or
+        1-D.  Returns an array (q, k), or (q,) for 1-D X: inventories (W = the cell volumes), stations, regional means of a state."""
+        self._live()
+        n = self.shape[1]
+        X = np.asarray(X)
+        if X.ndim not in (1, 2) or X.shape[0] != n:
+            raise capi.OtmbError(11, f"DimensionMismatch: operator of {self.shape}, X of {X.shape}")
+        W, q = observers(np.asarray(W), n)
+        k = 1 if X.ndim == 1 else X.shape[1]
+        Xc, ldx = _column_major(X)
+        Wc, ldw = _column_major(W)
+        obs = np.zeros((q, k), dtype=np.float64, order="F")
+        self.ctx.check(capi.lib().otmb_op_observe(self._h, k, q, Wc.ctypes.data, ldw, Xc.ctypes.data, ldx, obs.ctypes.data))
+        return obs[:, 0] if X.ndim == 1 else obs
+
+    @capi.observe_keywords
     def step(self, X, *, dt, theta=1.0, nsteps=1, first_slot=0, source=None, d=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi"):
         """nsteps θ-steps of ∂x/∂t + (diag(d) + A)·x = source from the state X, step t with the matrix of slot (first_slot + t) mod nslots
         (otmb_op_step; include/otmb.h states the contract: σ = 1 / (theta·dt), the right-hand side, then solve(..., x0 = the state)).  X: 1-D
@@ -1068,6 +1106,40 @@ class DeviceOperator:
         if rc != capi.NOT_CONVERGED:
             self.ctx.check(rc)
         return Xn, StepInfo(rc, done.value, nsteps, iters, relres, reason)
+
+    def _step_obs(self, X, observe, weights, *, dt, theta=1.0, nsteps=1, first_slot=0, source=None, d=None, rtol=1e-10, maxiter=10000, adjoint=False,
+                  precond="jacobi"):
+        """step with observers and / or the mean's weights: otmb_op_step_obs (capi.observe_keywords states the keywords)."""
+        self._live()
+        pc = capi.precond_code(precond)
+        X0 = np.asarray(X)
+        k, _, _, dc = self._system_args(X0, d)
+        n = self.shape[1]
+        Xn = np.array(X0, dtype=np.float64, order="F")
+        Sc, lds = None, max(Xn.shape[0], 1)
+        if source is not None:
+            if np.shape(source) != X0.shape:
+                raise capi.OtmbError(11, f"DimensionMismatch: source of {np.shape(source)}, X of {X0.shape}")
+            Sc, lds = _column_major(np.asarray(source))
+        q, Wc, ldw, obs, tw, mean = 0, None, max(n, 1), None, None, None
+        if observe is not None:
+            W, q = observers(np.asarray(observe), n)
+            Wc, ldw = _column_major(W)
+            obs = np.zeros((max(int(nsteps), 0), k, q), dtype=np.float64)
+        if weights is not None:
+            tw = time_weights(weights, nsteps)
+            mean = np.zeros(Xn.shape, dtype=np.float64, order="F")
+        iters, relres, reason = step_arrays(nsteps, k)
+        done = C.c_int64(0)
+        lib = capi.lib()
+        rc = lib.otmb_op_step_obs(self._h, int(bool(adjoint)), k, None if dc is None else dc.ctypes.data, float(dt), float(theta), int(nsteps),
+                                  int(first_slot), None if Sc is None else Sc.ctypes.data, lds, Xn.ctypes.data, max(Xn.shape[0], 1), float(rtol),
+                                  int(maxiter), pc, C.byref(done), iters.ctypes.data, relres.ctypes.data, reason.ctypes.data, q,
+                                  None if Wc is None else Wc.ctypes.data, ldw, None if obs is None else obs.ctypes.data,
+                                  None if tw is None else tw.ctypes.data, None if mean is None else mean.ctypes.data, max(n, 1))
+        if rc != capi.NOT_CONVERGED:
+            self.ctx.check(rc)
+        return Xn, StepInfo(rc, done.value, nsteps, iters, relres, reason, obs, mean)
 
     @capi.outer_keyword
     def periodic(self, source, *, dt, ncycle, theta=1.0, first_slot=0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi",

@@ -70,6 +70,18 @@ def outer_keyword(plain):
     return periodic
 
 
+def observe_keywords(plain):
+    """step(..., observe=None, time_weights=None) over a step method `plain` that makes the plain call (otmb_op_step[_dev]): with neither
+    keyword it is that call as it stands (info.observations and info.mean are None); with either it goes to the object's _step_obs
+    (otmb_op_step_obs[_dev]; include/otmb.h states the order of the sums and the mean's fold).  observe: W, n x q (or n values: one
+    observer) -> info.observations, (steps_done, k, q); time_weights: nsteps finite values -> info.mean = Σ_t time_weights[t]·X_t, n x k."""
+    @functools.wraps(plain)
+    def step(self, X, *, observe=None, time_weights=None, **kw):
+        return plain(self, X, **kw) if observe is None and time_weights is None else self._step_obs(X, observe, time_weights, **kw)
+
+    return step
+
+
 class Csc(C.Structure):
     """otmb_csc: a SparseMatrixCSC{Float64,Int64} by its three arrays (1-based)."""
     _fields_ = [("colptr", C.c_void_p), ("rowval", C.c_void_p), ("nzval", C.c_void_p), ("nnz", C.c_int64)]
@@ -236,6 +248,12 @@ SYMBOLS = {
                                       C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp]),
     "otmb_op_step": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
                                   C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp]),
+    "otmb_op_observe_dev": (C.c_int32, [_vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "otmb_op_observe": (C.c_int32, [_vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "otmb_op_step_obs_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
+                                          C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64]),
+    "otmb_op_step_obs": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
+                                      C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64]),
     "otmb_op_periodic_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
                                           C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp]),
     "otmb_op_periodic": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,

@@ -66,6 +66,17 @@ struct SvValues {
 // values.  Enqueued on the context's stream.
 int32_t cb_combine(otmb_op *op, const double *w, const OpSlot &to);
 
+// The observation pass (otmb_observe.hip), which the step runs after every completed step.
+// ob_reserve:   the partial sums of q x k entries in op->ob (may wait for the stream: before the loop, never inside it).
+// ob_pass:      obs (q x k, device) = Wᵀ·X and, Xbar not null, Xbar = (first ? +0.0 : Xbar) + tw·X, enqueued on the context's stream; q == 0
+//               runs no reduction, Xbar == null stores nothing but obs.
+// ob_complaint: the first complaint about the observers and the mean (tw: nsteps host values), naming otmb_op_step_obs (step) or
+//               otmb_op_observe, or null.
+int32_t ob_reserve(otmb_op *op, i64 k, i64 q);
+void ob_pass(otmb_op *op, i64 k, i64 q, const double *W, i64 ldw, const double *X, i64 ldx, double *obs, double *Xbar, i64 ldm, double tw, bool first);
+const char *ob_complaint(const otmb_op *op, bool step, i64 nsteps, i64 q, const double *W, i64 ldw, const double *obs, const double *tw, const double *Xbar,
+                         i64 ldm);
+
 // the report of an empty system (n = 0): every entry converged at once
 static inline int32_t sv_report_empty(i64 entries, int64_t *iters, double *relres, int32_t *reason) {
     for (i64 e = 0; e < entries; ++e) { iters[e] = 0; relres[e] = 0.0; reason[e] = OTMB_SOLVE_CONVERGED; }

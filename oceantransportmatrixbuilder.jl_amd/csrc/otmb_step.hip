@@ -141,38 +141,54 @@ static void st_rhs(otmb_op *op, int adjoint, i64 k, const StLine &q, const doubl
     });
 }
 
+struct StObs {  // what otmb_op_step_obs adds to a step call: q observers W (obs: q x k x nsteps) and the mean's weights and array (null: none)
+    i64 q;
+    const double *W;
+    i64 ldw;
+    double *obs;
+    const double *tw;
+    double *Xbar;
+    i64 ldm;
+};
+static const StObs ST_PLAIN = {0, nullptr, 0, nullptr, nullptr, nullptr, 0};  // otmb_op_step: no observers, no mean
+
 static int32_t st_check(otmb_op *op, int64_t k, double dt, double theta, int64_t nsteps, int64_t first_slot, const double *S, int64_t lds, double *X,
                         int64_t ldx, double rtol, int64_t maxiter, int32_t precond, const int64_t *steps_done, const int64_t *iters, const double *relres,
-                        const int32_t *reason) {
+                        const int32_t *reason, const StObs &o) {
     const char *more = !steps_done || (nsteps > 0 && (!iters || !relres || !reason))
                            ? "null argument"
                            : sv_step_complaint(op, rtol, maxiter, dt, theta, nsteps >= 0, "nsteps must be >= 0", first_slot);
+    if (!more) more = ob_complaint(op, true, nsteps, o.q, o.W, o.ldw, o.obs, o.tw, o.Xbar, o.ldm);
     return sv_check_step(op, precond, k, S, lds, X, ldx, more);
 }
 
-extern "C" {
-
-int32_t otmb_op_step_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
-                         const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
-                         int64_t *iters, double *relres, int32_t *reason) {
-    if (!op) return OTMB_ERR_INVALID_ARG;
+// The ONE loop behind otmb_op_step[_dev] (o = ST_PLAIN) and otmb_op_step_obs[_dev]: device pointers, the arguments checked.  After a step
+// whose solve left every column converged the observation pass reads X where the solve left it and its fold writes the step's q x k block
+// of o.obs; nothing of it waits for the host.
+static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot, const double *S,
+                      int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters, double *relres,
+                      int32_t *reason, const StObs &o) {
     int32_t rc;
-    if ((rc = st_check(op, k, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason))) return rc;
     *steps_done = 0;
     if (nsteps == 0) return OTMB_OK;
     otmb_ctx *ctx = op->ctx;
     const i64 n = op->n, nslots = (i64)op->slots.size();
     if (n == 0) {
         *steps_done = nsteps;
+        if (o.q > 0) {  // empty sums: +0.0
+            HIP_TRY(ctx, hipSetDevice(op->device));
+            HIP_TRY(ctx, hipMemsetAsync(o.obs, 0, (size_t)(o.q * k * nsteps) * 8, ctx->stream));
+        }
         return sv_report_empty(nsteps * k, iters, relres, reason);
     }
     HIP_TRY(ctx, hipSetDevice(op->device));
-    const bool lines = precond == OTMB_PRECOND_LINES;
+    const bool lines = precond == OTMB_PRECOND_LINES, watch = o.q > 0 || o.Xbar;
     const double tdt = theta * dt;
     const StLine q = {1.0 / tdt, theta, (1.0 - theta) / theta};
     // op->st: B, then one preconditioner per slot the call visits
     const i64 used = std::min(nsteps, nslots), per = lines ? 5 : 2;
     if ((rc = otmb_reserve(ctx, op->st, ((size_t)(n * k) + (size_t)(used * per * n)) * 8))) return rc;
+    if (watch && (rc = ob_reserve(op, k, o.q))) return rc;
     double *B = (double *)op->st.p, *pool = B + n * k;
     std::vector<SvPrec> prec((size_t)nslots, SvPrec{nullptr, nullptr, nullptr, nullptr, nullptr});
     i64 taken = 0;
@@ -196,17 +212,20 @@ int32_t otmb_op_step_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *
         st_rhs(op, adjoint, k, q, d, X, ldx, S, lds, B);
         HIP_TRY(ctx, hipGetLastError());
         if ((rc = sv_solve(op, adjoint, k, p, B, n, X, ldx, 1, rtol, maxiter, iters + t * k, relres + t * k, reason + t * k, precond))) return here(rc);
+        if (watch) {
+            ob_pass(op, k, o.q, o.W, o.ldw, X, ldx, o.q > 0 ? o.obs + o.q * k * t : nullptr, o.Xbar, o.ldm, o.tw ? o.tw[t] : 0.0, t == 0);
+            HIP_TRY(ctx, hipGetLastError());
+        }
         *steps_done = t + 1;
     }
     return OTMB_OK;
 }
 
-int32_t otmb_op_step(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
-                     const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
-                     int64_t *iters, double *relres, int32_t *reason) {
-    if (!op) return OTMB_ERR_INVALID_ARG;
+// The host variant of the loop: X, S, d, W staged once; X, the written rows of obs and Xbar come home once.
+static int32_t st_run_host(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
+                           const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
+                           int64_t *iters, double *relres, int32_t *reason, const StObs &o) {
     int32_t rc;
-    if ((rc = st_check(op, k, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason))) return rc;
     *steps_done = 0;
     const i64 n = op->n;
     if (nsteps == 0) return OTMB_OK;
@@ -219,10 +238,66 @@ int32_t otmb_op_step(otmb_op *op, int32_t adjoint, int64_t k, const double *d, d
         if ((rc = op_upload(ctx, dx, X, ldx, n, k))) return rc;
         if (S && (rc = op_upload(ctx, ds, S, lds, n, k))) return rc;
     }
-    rc = otmb_op_step_dev(op, adjoint, k, dd, dt, theta, nsteps, first_slot, ds, n, dx, n, rtol, maxiter, precond, steps_done, iters, relres, reason);
+    StObs od = ST_PLAIN;
+    if (o.q > 0 || o.Xbar) {  // op->oh: obs (q x k x nsteps) | W (n x q) | Xbar (n x k), compact
+        const i64 nobs = o.q * k * nsteps;
+        if ((rc = otmb_reserve(ctx, op->oh, std::max<size_t>((size_t)(nobs + n * o.q + (o.Xbar ? n * k : 0)) * 8, 8)))) return rc;
+        double *dobs = (double *)op->oh.p, *dw = dobs + nobs, *dm = dw + n * o.q;
+        if (o.q > 0 && n > 0 && (rc = op_upload(ctx, dw, o.W, o.ldw, n, o.q))) return rc;
+        od = {o.q, o.q > 0 ? dw : nullptr, n, o.q > 0 ? dobs : nullptr, o.tw, o.Xbar ? dm : nullptr, n};
+    }
+    rc = st_run(op, adjoint, k, dd, dt, theta, nsteps, first_slot, ds, n, dx, n, rtol, maxiter, precond, steps_done, iters, relres, reason, od);
     // X comes back when it holds an answer: every step done, a step's last iterates, or the state before a slot whose preconditioner is singular
     if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED && !(rc == OTMB_ERR_SINGULAR_PRECONDITIONER && *steps_done > 0)) return rc;
+    // ... and with it the observations of the completed steps and their mean
+    const std::string msg = ctx->err;
+    int32_t rcd;
+    if (od.q > 0 && *steps_done > 0 && (rcd = op_download(ctx, o.obs, od.q * k * *steps_done, od.obs, od.q * k * *steps_done, 1))) return rcd;
+    if (od.Xbar && *steps_done > 0 && n > 0 && (rcd = op_download(ctx, o.Xbar, o.ldm, od.Xbar, n, k))) return rcd;
+    ctx->err = msg;
     return op_finish(ctx, rc, X, ldx, dx, n, k);
+}
+
+extern "C" {
+
+int32_t otmb_op_step_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
+                         const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
+                         int64_t *iters, double *relres, int32_t *reason) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    int32_t rc;
+    if ((rc = st_check(op, k, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, ST_PLAIN))) return rc;
+    return st_run(op, adjoint, k, d, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, ST_PLAIN);
+}
+
+int32_t otmb_op_step(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
+                     const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
+                     int64_t *iters, double *relres, int32_t *reason) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    int32_t rc;
+    if ((rc = st_check(op, k, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, ST_PLAIN))) return rc;
+    return st_run_host(op, adjoint, k, d, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, ST_PLAIN);
+}
+
+int32_t otmb_op_step_obs_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
+                             const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
+                             int64_t *iters, double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw,
+                             double *Xbar, int64_t ldm) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    const StObs o = {q, W, ldw, obs, tw, Xbar, ldm};
+    int32_t rc;
+    if ((rc = st_check(op, k, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o))) return rc;
+    return st_run(op, adjoint, k, d, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o);
+}
+
+int32_t otmb_op_step_obs(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
+                         const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
+                         int64_t *iters, double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw,
+                         double *Xbar, int64_t ldm) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    const StObs o = {q, W, ldw, obs, tw, Xbar, ldm};
+    int32_t rc;
+    if ((rc = st_check(op, k, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o))) return rc;
+    return st_run_host(op, adjoint, k, d, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o);
 }
 
 }  // extern "C"

@@ -196,6 +196,33 @@ class Operator:
             self.ctx.check(rc)
         return X, SolveInfo(rc, iters, relres, reason)
 
+    def _observers(self, W):
+        """(W column-major, its leading dimension, q) of a device tensor n x q, or of n values: one observer."""
+        from .api import observers
+
+        _on_device(W, self.device, "observe")
+        n = self.shape[1]
+        W, q = observers(W, n)
+        Wc, ldw = _col_major(W, n)
+        return Wc, ldw, q
+
+    def observe(self, W, X):
+        """Wᵀ·X on device tensors (otmb_op_observe_dev; api.DeviceOperator.observe): a new tensor (q, k), or (q,) for 1-D X, enqueued on
+        the context's stream.  Nothing travels to the host."""
+        if not self._h.value:
+            raise ValueError("operator is closed")
+        _on_device(X, self.device, "X")
+        n = self.shape[1]
+        if X.dim() not in (1, 2) or X.shape[0] != n:
+            raise capi.OtmbError(11, f"DimensionMismatch: operator of {self.shape}, X of {tuple(X.shape)}")
+        k = 1 if X.dim() == 1 else X.shape[1]
+        Xc, ldx = _col_major(X, n)
+        Wc, ldw, q = self._observers(W)
+        obs = torch.zeros((k, q), dtype=torch.float64, device=X.device).t()  # column-major (q, k)
+        self.ctx.check(self.lib.otmb_op_observe_dev(self._h, k, q, Wc.data_ptr(), ldw, Xc.data_ptr(), ldx, obs.data_ptr()))
+        return obs[:, 0] if X.dim() == 1 else obs
+
+    @capi.observe_keywords
     def step(self, X, *, dt, theta=1.0, nsteps=1, first_slot=0, source=None, d=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi"):
         """nsteps θ-steps over the slots on device tensors (otmb_op_step_dev; api.DeviceOperator.step states the arguments).  X is not modified;
         returns (a new tensor with the state after the steps, an api.StepInfo).  Nothing but the solver's column records travels to the host."""
@@ -219,6 +246,42 @@ class Operator:
         if rc != capi.NOT_CONVERGED:
             self.ctx.check(rc)
         return Xn, StepInfo(rc, done.value, nsteps, iters, relres, reason)
+
+    def _step_obs(self, X, observe, weights, *, dt, theta=1.0, nsteps=1, first_slot=0, source=None, d=None, rtol=1e-10, maxiter=10000, adjoint=False,
+                  precond="jacobi"):
+        """step with observers and / or the mean's weights on device tensors: otmb_op_step_obs_dev (capi.observe_keywords states the
+        keywords).  info.observations and info.mean are device tensors; the weights are host values."""
+        from .api import StepInfo, step_arrays, time_weights
+
+        pc, k, Xc, ldx, Xn = self._system(X, "X", precond)
+        Xn.copy_(X)
+        n = self.shape[0]
+        Sc, sp, lds = None, None, max(n, 1)
+        if source is not None:
+            _on_device(source, self.device, "source")
+            if tuple(source.shape) != tuple(X.shape):
+                raise capi.OtmbError(11, f"DimensionMismatch: source of {tuple(source.shape)}, X of {tuple(X.shape)}")
+            Sc, lds = _col_major(source, n)
+            sp = Sc.data_ptr()
+        d, dp = self._d_ptr(d)
+        q, Wc, ldw, obs, tw, mean = 0, None, max(n, 1), None, None, None
+        if observe is not None:
+            Wc, ldw, q = self._observers(observe)
+            obs = torch.zeros((max(int(nsteps), 0), k, q), dtype=torch.float64, device=X.device)
+        if weights is not None:
+            tw = time_weights(weights, nsteps)
+            mean = torch.zeros_like(Xn) if X.dim() == 1 else \
+                torch.zeros(k * max(n, 1), dtype=torch.float64, device=X.device).as_strided((n, k), (1, max(n, 1)))
+        iters, relres, reason = step_arrays(nsteps, k)
+        done = C.c_int64(0)
+        rc = self.lib.otmb_op_step_obs_dev(self._h, int(bool(adjoint)), k, dp, float(dt), float(theta), int(nsteps), int(first_slot), sp, lds,
+                                           Xn.data_ptr(), max(n, 1), float(rtol), int(maxiter), pc, C.byref(done), iters.ctypes.data,
+                                           relres.ctypes.data, reason.ctypes.data, q, None if Wc is None else Wc.data_ptr(), ldw,
+                                           None if obs is None else obs.data_ptr(), None if tw is None else tw.ctypes.data,
+                                           None if mean is None else mean.data_ptr(), max(n, 1))
+        if rc != capi.NOT_CONVERGED:
+            self.ctx.check(rc)
+        return Xn, StepInfo(rc, done.value, nsteps, iters, relres, reason, obs, mean)
 
     @capi.outer_keyword
     def periodic(self, source, *, dt, ncycle, theta=1.0, first_slot=0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi",
