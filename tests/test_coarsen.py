@@ -5,6 +5,7 @@ import pytest
 
 from helpers import make_case
 from spmatmul_ref import coarse_ref
+from test_lump_and_spray import _same as _same_lump
 from test_oracle import LUMP_SETTINGS, lump_inputs, lump_mask
 
 pytestmark = pytest.mark.gpu
@@ -56,7 +57,8 @@ def test_coarsen_large_columns(oracle):
     wet, vol, tm, N = lump_inputs(oracle, "small_rho3d")
     T = api.SparseMatrixCSC(N, N, *tm["T"])
     for (di, dj, dk) in ((64, 64, 1), (16, 16, 16)):
-        L, S, _ = api.lump_and_spray(wet, vol, T, None, di=di, dj=dj, dk=dk)
+        L, S, vc = api.lump_and_spray(wet, vol, T, None, di=di, dj=dj, dk=dk)
+        _same_lump((L, S, vc), oracle.lump_and_spray(wet, vol, tm["T"], None, di, dj, dk), ("lump", di, dj, dk))  # a verified input
         for op in ("T", "TκH"):
             B = api.SparseMatrixCSC(N, N, *tm[op])
             _same(api.coarsen(L, B, S), coarse_ref(L, B, S), (di, dj, dk, op))
@@ -188,10 +190,14 @@ def test_coarsen_access1deg_bit_identical(oracle):
     T = api.SparseMatrixCSC(N, N, *host["T"])
     for mask in (None, somask):
         L, S, vc = api.lump_and_spray(wet, vol, T, mask, di=2, dj=2, dk=1)
+        lump_want = oracle.lump_and_spray(wet, vol, host["T"], mask, 2, 2, 1)
+        _same_lump((L, S, vc), lump_want, ("1deg", mask is not None, "host lump"))
         want = coarse_ref(L, T, S)
         _same(api.coarsen(L, T, S), want, ("1deg", mask is not None, "host"))
         dm = None if mask is None else torch.from_numpy(np.asfortranarray(mask).ravel(order="F").astype(np.uint8)).cuda()
-        Ld, Sd, _ = asm.lump_and_spray(dm, 2, 2, 1)
+        Ld, Sd, vcd = asm.lump_and_spray(dm, 2, 2, 1)
+        _same_lump((_csc(len(vcd), N, *(t.cpu().numpy() for t in Ld)), _csc(N, len(vcd), *(t.cpu().numpy() for t in Sd)), vcd.cpu().numpy()),
+                   lump_want, ("1deg", mask is not None, "device lump"))
         Cp, Ci, Cx = asm.coarsen(Ld, Sd)
         got = api.SparseMatrixCSC(len(vc), len(vc), Cp.cpu().numpy(), Ci.cpu().numpy(), Cx.cpu().numpy())
         _same(got, want, ("1deg", mask is not None, "device"))

@@ -3,6 +3,7 @@ structure and the coarse volumes bit for bit, LUMP's values bit for bit."""
 import numpy as np
 import pytest
 
+import lump_grids
 from helpers import CASES, MATS, make_case
 from test_oracle import LUMP_SETTINGS, lump_inputs, lump_mask
 
@@ -108,36 +109,8 @@ def test_lump_and_spray_random_sweep(oracle, seed):
     import otmb_amd.api as api
     from otmb_amd.capi import OtmbError
 
-    rng = np.random.default_rng(7000 + seed)
-    nx, ny, nz = int(rng.integers(1, 14)), int(rng.integers(1, 9)), int(rng.integers(1, 6))
-    wet = rng.random((nx, ny, nz)) < rng.uniform(0.3, 1.0)
-    if not wet.any():
-        wet[0, 0, 0] = True
-    N = int(wet.sum())
-    rank = np.zeros(wet.shape, dtype=np.int64)
-    rank.reshape(-1, order="F")[wet.reshape(-1, order="F")] = np.arange(1, N + 1)
-    # pattern: diagonal + a random subset of the 6-neighbour links (periodic in i), symmetric unless `broken`
-    broken = seed % 7 == 3
-    cols = [set([c]) for c in range(N + 1)]
-    for (a, b, c) in np.argwhere(wet):
-        for (da, db, dc) in ((1, 0, 0), (0, 1, 0), (0, 0, 1)):
-            a2, b2, c2 = (a + da) % nx, b + db, c + dc
-            if b2 < ny and c2 < nz and wet[a2, b2, c2] and rng.random() < 0.7:
-                r1, r2 = int(rank[a, b, c]), int(rank[a2, b2, c2])
-                cols[r1].add(r2)
-                if not (broken and rng.random() < 0.3):
-                    cols[r2].add(r1)
-    colptr = np.ones(N + 1, dtype=np.int64)
-    rowval = []
-    for c in range(1, N + 1):
-        rows = sorted(cols[c])
-        rowval.extend(rows)
-        colptr[c] = colptr[c - 1] + len(rows)
-    rowval = np.array(rowval, dtype=np.int64)
-    T = (colptr, rowval, np.ones(len(rowval)))
-    vol = rng.uniform(1.0, 1e6, N)
-    di, dj, dk = int(rng.integers(1, 6)), int(rng.integers(1, 5)), int(rng.integers(1, 4))
-    mask = None if rng.random() < 0.3 else (rng.random(wet.shape) < rng.uniform(0.2, 1.0))
+    wet, vol, T, mask, (di, dj, dk) = lump_grids.sweep_case(seed)
+    (nx, ny, nz), N = wet.shape, len(vol)
     Tm = api.SparseMatrixCSC(N, N, *T)
     try:
         want = oracle.lump_and_spray(wet, vol, T, mask, di, dj, dk)
@@ -165,18 +138,7 @@ def test_lump_and_spray_edge_grids(oracle):
     cases.append((w, (2, 3, 3)))
     for wet, (di, dj, dk) in cases:
         N = int(wet.sum())
-        rank = np.zeros(wet.shape, dtype=np.int64)
-        rank.reshape(-1, order="F")[wet.reshape(-1, order="F")] = np.arange(1, N + 1)
-        cols = [set([c]) for c in range(N + 1)]
-        for (a, b, c) in np.argwhere(wet):
-            for (da, db, dc) in ((1, 0, 0), (0, 1, 0), (0, 0, 1)):
-                a2, b2, c2 = a + da, b + db, c + dc
-                if a2 < wet.shape[0] and b2 < wet.shape[1] and c2 < wet.shape[2] and wet[a2, b2, c2]:
-                    cols[int(rank[a, b, c])].add(int(rank[a2, b2, c2])); cols[int(rank[a2, b2, c2])].add(int(rank[a, b, c]))
-        colptr = np.ones(N + 1, dtype=np.int64); rowval = []
-        for c in range(1, N + 1):
-            rowval.extend(sorted(cols[c])); colptr[c] = colptr[c - 1] + len(cols[c])
-        T = (colptr, np.array(rowval, dtype=np.int64), np.ones(len(rowval)))
+        T = lump_grids.neighbour_pattern(wet, None, keep=1.0, periodic_i=False)  # every link, nothing drawn
         vol = np.linspace(1.0, 2.0, N)
         for mask in (None, np.zeros(wet.shape, dtype=bool)):
             want = oracle.lump_and_spray(wet, vol, T, mask, di, dj, dk)
