@@ -932,6 +932,53 @@ int32_t otmb_op_periodic_pc(otmb_op *op, int32_t adjoint, int64_t k, const doubl
                             double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer,
                             int64_t *msolve_iters);
 
+/* ---- Per-column d: otmb_op_solve_dk, otmb_op_precond_dk, otmb_op_step_dk and otmb_op_periodic_dk [_dev].  Tracers that differ in their sink --
+ *      ideal age (a surface restoring rate), radiocarbon (the same plus a decay rate λ on every cell), a dye restored over its own patch --
+ *      share one call, one pass over the matrix per register block and one outer driver.  The arguments are those of otmb_op_solve_pc,
+ *      otmb_op_precond, otmb_op_step_obs (q == 0 and tw == NULL: the plain step) and otmb_op_periodic_pc, with `const double *d` replaced by
+ *      `const double *D, int64_t ldd`: D is column-major n x k with leading dimension ldd, column c the d of column c of B / S / X / x0.
+ * The contract: column c of a per-column call has the bits of the existing call made with k = 1, that column of B / S / X / x0, and
+ *      d = D[:, c], whatever the other columns hold and however many there are -- the state, iters, relres, reason, steps_done, the
+ *      observations and the mean, cycles, defect and msolve_iters, and what a column that did not converge leaves behind.
+ * D and ldd: D == NULL means zero, as for d.  Otherwise ldd >= n (rows beyond n are not read), or ldd == 0: the n values at D serve every
+ *      column, and the call is the existing one, bit for bit -- the existing entry points ARE these calls with ldd = 0.  Any other ldd is
+ *      OTMB_ERR_INVALID_ARG before anything is touched, and the message names the call.  _dev: D is a device pointer; the host variants
+ *      upload D's n x k block once per call.
+ * Workspace: with ldd != 0 a preconditioner holds σ + d, Jacobi's diagonal and, for the lines, the multipliers and the pivots per column,
+ *      and u once (it does not depend on d): 2·n·k doubles (Jacobi) or 4·n·k + n (lines) where the shared d takes 2·n or 5·n.  The step's
+ *      pool is n·k + used·(lines ? 4·k + 1 : 2·k)·n doubles, used = min(nsteps, slots): still one preconditioner per visited slot and call;
+ *      a failed reservation is OTMB_ERR_ALLOC with X untouched.  otmb_op_periodic_dk adds 2·k columns of gathered D and, with
+ *      OTMB_OUTER_MEAN, the mean's preconditioner for all k columns (made once per call) and a gathered copy of it.
+ * A singular preconditioner is refused before anything is iterated or written, as in the existing calls; with ldd != 0 the message is theirs
+ *      followed by " (column C of k)": C is the smallest 1-based column that has a bad entry, and the index is that column's first bad one.
+ *      otmb_op_periodic_dk names the caller's column and k as well; a column whose source is zero is answered with zero and never stepped,
+ *      as in the call with k = 1, so the step's preconditioner of such a column is not examined.  */
+int32_t otmb_op_solve_dk_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double sigma, const double *B, int64_t ldb,
+                             double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason,
+                             int32_t precond);
+int32_t otmb_op_solve_dk(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double sigma, const double *B, int64_t ldb, double *X,
+                         int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason, int32_t precond);
+int32_t otmb_op_precond_dk_dev(otmb_op *op, int32_t adjoint, int32_t precond, int64_t k, const double *D, int64_t ldd, double sigma, const double *Y,
+                               int64_t ldy, double *Z, int64_t ldz);
+int32_t otmb_op_precond_dk(otmb_op *op, int32_t adjoint, int32_t precond, int64_t k, const double *D, int64_t ldd, double sigma, const double *Y,
+                           int64_t ldy, double *Z, int64_t ldz);
+int32_t otmb_op_step_dk_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t nsteps,
+                            int64_t first_slot, const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond,
+                            int64_t *steps_done, int64_t *iters, double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs,
+                            const double *tw, double *Xbar, int64_t ldm);
+int32_t otmb_op_step_dk(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t nsteps,
+                        int64_t first_slot, const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond,
+                        int64_t *steps_done, int64_t *iters, double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs,
+                        const double *tw, double *Xbar, int64_t ldm);
+int32_t otmb_op_periodic_dk_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
+                                int64_t first_slot, const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter,
+                                int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
+                                int32_t outer, int64_t *msolve_iters);
+int32_t otmb_op_periodic_dk(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
+                            int64_t first_slot, const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter,
+                            int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
+                            int32_t outer, int64_t *msolve_iters);
+
 #ifdef __cplusplus
 }
 #endif

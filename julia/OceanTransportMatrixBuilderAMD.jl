@@ -672,6 +672,119 @@ function periodicpc!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,Adjoin
 end
 periodic(D::Union{DeviceOperator,AdjointDeviceOperator}, source::StridedVecOrMat{Float64}; kwargs...) = periodic!(zero(source), D, source; kwargs...)
 
+# Per-column d (otmb_op_solve_dk, otmb_op_precond_dk, otmb_op_step_dk, otmb_op_periodic_dk; include/otmb.h states the contract): tracers that
+# differ in their sink -- ideal age, radiocarbon with its decay rate, a dye restored over its own patch -- in ONE call.  `d` is a matrix of
+# the shape of B / X / source, passed as the last positional argument, one column per tracer; column c of the result has the bits of the call
+# above made for that column alone with `d = d[:, c]`.  The keywords and the returned info are those of the methods above.
+function dkdims(op::DeviceOperator, d::StridedMatrix{Float64}, X, xname)
+    (X isa AbstractMatrix && size(d) == size(X)) || throw(DimensionMismatch("d $(size(d)) is per column, $xname $(size(X))"))
+    stride(d, 1) == 1 || throw(ArgumentError("d needs contiguous columns"))
+    return Int64(stride(d, 2))   # ldd: a view of some columns, or of the leading rows, of a larger matrix keeps its parent's
+end
+function solve!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, B::StridedVecOrMat{Float64}, d::StridedMatrix{Float64};
+                σ::Real = 0.0, rtol::Real = 1e-10, maxiter::Integer = 10000, x0::Bool = false, precond::Symbol = :jacobi)
+    pc = precondcode(precond)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    k, ldb, ldx = systemdims(op, B, "B", X, "X", nothing)
+    ldd = dkdims(op, d, X, "X")
+    iters = zeros(Int64, k)
+    relres = zeros(Float64, k)
+    reason = zeros(Int32, k)
+    lock(CALL_LOCK) do
+        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        solve_dk_fn = sym(:otmb_op_solve_dk)
+        rc = ccall(solve_dk_fn, Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Int64, Float64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int32, Float64,
+                Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, Int32),
+            op.handle, Int32(adjoint), k, d, ldd, Float64(σ), B, ldb, X, ldx, Int32(x0), Float64(rtol), Int64(maxiter), iters, relres, reason, pc)
+        rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which column stopped why
+    end
+    why = [SOLVE_REASONS[r + 1] for r in reason]
+    return X, (iterations = iters, relres = relres, reason = why, converged = why .== :converged)
+end
+function precondition!(Z::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, Y::StridedVecOrMat{Float64},
+                       d::StridedMatrix{Float64}; σ::Real = 0.0, precond::Symbol = :lines)
+    pc = precondcode(precond)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    k, ldy, ldz = systemdims(op, Y, "Y", Z, "Z", nothing)
+    ldd = dkdims(op, d, Z, "Z")
+    lock(CALL_LOCK) do
+        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        precond_dk_fn = sym(:otmb_op_precond_dk)
+        check(ccall(precond_dk_fn, Int32, (Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Float64}, Int64, Float64, Ptr{Float64}, Int64, Ptr{Float64}, Int64),
+            op.handle, Int32(adjoint), pc, k, d, ldd, Float64(σ), Y, ldy, Z, ldz))
+    end
+    return Z
+end
+function stepobserve!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, d::StridedMatrix{Float64}; dt::Real, θ::Real = 1.0,
+                      nsteps::Integer = 1, firstslot::Integer = 1, source::Union{Nothing,StridedVecOrMat{Float64}} = nothing, rtol::Real = 1e-10,
+                      maxiter::Integer = 10000, precond::Symbol = :jacobi, observers::Union{Nothing,StridedVecOrMat{Float64}} = nothing,
+                      timeweights::Union{Nothing,Vector{Float64}} = nothing)
+    pc = precondcode(precond)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    S = source === nothing ? X : source
+    k, lds, ldx = systemdims(op, S, "source", X, "X", nothing)
+    ldd = dkdims(op, d, X, "X")
+    nrep = max(Int64(nsteps), 0)
+    iters = zeros(Int64, k, nrep)
+    relres = zeros(Float64, k, nrep)
+    reason = zeros(Int32, k, nrep)
+    done = Ref{Int64}(0)
+    q, ldw = observers === nothing ? (0, max(op.n, 1)) : observerdims(op, observers)
+    obs = zeros(Float64, q, k, nrep)
+    timeweights === nothing || length(timeweights) == nrep || throw(DimensionMismatch("timeweights of $(length(timeweights)), nsteps $nrep"))
+    Xbar = timeweights === nothing ? nothing : zeros(Float64, size(X)...)
+    ldm = max(op.n, 1)
+    lock(CALL_LOCK) do
+        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        step_dk_fn = sym(:otmb_op_step_dk)
+        rc = ccall(step_dk_fn, Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Int64, Float64, Float64, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64},
+                Int64, Float64, Int64, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64},
+                Ptr{Float64}, Int64),
+            op.handle, Int32(adjoint), k, d, ldd, Float64(dt), Float64(θ), Int64(nsteps), Int64(firstslot - 1),
+            source === nothing ? C_NULL : source, lds, X, ldx, Float64(rtol), Int64(maxiter), pc, done, iters, relres, reason,
+            Int64(q), observers === nothing ? C_NULL : observers, ldw, observers === nothing ? C_NULL : obs,
+            timeweights === nothing ? C_NULL : timeweights, Xbar === nothing ? C_NULL : Xbar, ldm)
+        rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which step and column stopped why
+    end
+    ran = 1:min(done[] + 1, nrep)
+    why = permutedims([SOLVE_REASONS[r + 1] for r in reason[:, ran]])
+    return X, (stepsdone = done[], iterations = permutedims(iters[:, ran]), relres = permutedims(relres[:, ran]), reason = why,
+               converged = why .== :converged, observations = observers === nothing ? nothing : obs[:, :, 1:done[]],
+               mean = done[] > 0 ? Xbar : nothing)
+end
+# (the plain step is the observed one without observers and weights: info.observations and info.mean are nothing)
+step!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, d::StridedMatrix{Float64}; kwargs...) = stepobserve!(X, D, d; kwargs...)
+function periodic!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, source::StridedVecOrMat{Float64},
+                   d::StridedMatrix{Float64}; dt::Real, ncycle::Integer, θ::Real = 1.0, firstslot::Integer = 1, x0::Bool = false, rtol::Real = 1e-10,
+                   maxiter::Integer = 10000, precond::Symbol = :jacobi, outer::Symbol = :none, ptol::Real = 1e-8, restart::Integer = 30,
+                   maxcycles::Integer = 1000)
+    oc = outercode(outer)
+    pc = precondcode(precond)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    k, lds, ldx = systemdims(op, source, "source", X, "X", nothing)
+    ldd = dkdims(op, d, X, "X")
+    cycles = zeros(Int64, k)
+    defect = zeros(Float64, k)
+    reason = zeros(Int32, k)
+    msolve = zeros(Int64, k)
+    lock(CALL_LOCK) do
+        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        periodic_dk_fn = sym(:otmb_op_periodic_dk)
+        rc = ccall(periodic_dk_fn, Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Int64, Float64, Float64, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64},
+                Int64, Int32, Float64, Int64, Int32, Float64, Int64, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, Int32, Ptr{Int64}),
+            op.handle, Int32(adjoint), k, d, ldd, Float64(dt), Float64(θ), Int64(ncycle), Int64(firstslot - 1),
+            source, lds, X, ldx, Int32(x0), Float64(rtol), Int64(maxiter), pc, Float64(ptol), Int64(restart), Int64(maxcycles), cycles, defect, reason,
+            oc, msolve)
+        rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which column stopped why
+    end
+    why = [PERIODIC_PC_REASONS[r + 1] for r in reason]
+    return X, (cycles = cycles, defect = defect, reason = why, converged = why .== :converged, msolve_iters = msolve)
+end
+
 const HDIRS = (:west, :east, :south, :north)      # OTMB_DIR_*
 f64(a) = Array{Float64}(replace(a, missing => NaN))
 # grid-constant arrays go to the library as they are when they already have the C layout: with reuse_grid the library

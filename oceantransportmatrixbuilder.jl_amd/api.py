@@ -1029,6 +1029,8 @@ class DeviceOperator:
         self._live()
         pc = capi.precond_code(precond)
         Y = np.asarray(Y)
+        if np.ndim(d) == 2:
+            return self._precondition_dk(Y, d, sigma, adjoint, pc)
         k, Yc, ldy, dc = self._system_args(Y, d)
         Z = np.zeros(Y.shape, dtype=np.float64, order="F")
         lib = capi.lib()
@@ -1049,6 +1051,8 @@ class DeviceOperator:
         self._live()
         pc = capi.precond_code(precond)
         B = np.asarray(B)
+        if np.ndim(d) == 2:
+            return self._solve_dk(B, d, sigma, rtol, maxiter, x0, adjoint, pc)
         k, Bc, ldb, dc = self._system_args(B, d)
         X = np.zeros(B.shape, dtype=np.float64, order="F")
         if x0 is not None:
@@ -1086,10 +1090,13 @@ class DeviceOperator:
         (otmb_op_step; include/otmb.h states the contract: σ = 1 / (theta·dt), the right-hand side, then solve(..., x0 = the state)).  X: 1-D
         or 2-D (n x k), not modified; source: None (zero) or an array of X's shape; d: None or n values.  Returns (X after the steps, info):
         info a StepInfo.  A step that does not converge ends the call and is REPORTED as solve reports it (info.status, info.steps_done,
-        info.reason; X then holds that step's last iterates), not raised; argument errors and a singular preconditioner raise OtmbError."""
+        info.reason; X then holds that step's last iterates), not raised; argument errors and a singular preconditioner raise OtmbError.
+        d of X's 2-D shape: every tracer has its own d (otmb_op_step_dk), and column c is the 1-D call with d[:, c]."""
         self._live()
         pc = capi.precond_code(precond)
         X0 = np.asarray(X)
+        if np.ndim(d) == 2:
+            return self._step_dk(X0, None, None, dt, theta, nsteps, first_slot, source, d, rtol, maxiter, adjoint, pc)
         k, _, _, dc = self._system_args(X0, d)
         Xn = np.array(X0, dtype=np.float64, order="F")
         Sc, lds = None, max(Xn.shape[0], 1)
@@ -1113,6 +1120,8 @@ class DeviceOperator:
         self._live()
         pc = capi.precond_code(precond)
         X0 = np.asarray(X)
+        if np.ndim(d) == 2:
+            return self._step_dk(X0, observe, weights, dt, theta, nsteps, first_slot, source, d, rtol, maxiter, adjoint, pc)
         k, _, _, dc = self._system_args(X0, d)
         n = self.shape[1]
         Xn = np.array(X0, dtype=np.float64, order="F")
@@ -1150,10 +1159,12 @@ class DeviceOperator:
         (X, info): X the state at the start of the cycle, with ‖F(X) - X‖₂ <= ptol·‖F(0)‖₂ per converged column, info a PeriodicInfo.  A
         column that does not converge is REPORTED (info.reason), not raised; argument errors and a singular preconditioner raise OtmbError.
         outer="mean" (outer_keyword): the outer GMRES is preconditioned by the cycle-mean operator -- fewer cycles, one solve with the mean
-        matrix per iteration (info.msolve_iters)."""
+        matrix per iteration (info.msolve_iters).  d of source's 2-D shape: every column has its own d (otmb_op_periodic_dk)."""
         self._live()
         pc = capi.precond_code(precond)
         S = np.asarray(source)
+        if np.ndim(d) == 2:
+            return self._periodic_dk(S, capi.OUTERS["none"], dt, ncycle, theta, first_slot, d, x0, rtol, maxiter, adjoint, pc, ptol, restart, maxcycles)
         k, Sc, lds, dc = self._system_args(S, d)
         X = np.zeros(S.shape, dtype=np.float64, order="F")
         if x0 is not None:
@@ -1176,6 +1187,8 @@ class DeviceOperator:
         self._live()
         pc = capi.precond_code(precond)
         S = np.asarray(source)
+        if np.ndim(d) == 2:
+            return self._periodic_dk(S, outer, dt, ncycle, theta, first_slot, d, x0, rtol, maxiter, adjoint, pc, ptol, restart, maxcycles)
         k, Sc, lds, dc = self._system_args(S, d)
         X = np.zeros(S.shape, dtype=np.float64, order="F")
         if x0 is not None:
@@ -1189,6 +1202,86 @@ class DeviceOperator:
                                      int(first_slot), Sc.ctypes.data, lds, X.ctypes.data, max(X.shape[0], 1), int(x0 is not None), float(rtol),
                                      int(maxiter), pc, float(ptol), int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data,
                                      reason.ctypes.data, int(outer), msolve.ctypes.data)
+        if rc != capi.NOT_CONVERGED:
+            self.ctx.check(rc)
+        return X, PeriodicInfo(rc, cycles, defect, reason, msolve)
+
+    # ---- per-column d: a 2-D d of B's / X's / source's shape goes to the otmb_op_*_dk exports (include/otmb.h states the contract: column c
+    # is the 1-D call with d[:, c], bit for bit).  A 1-D d never comes here: it keeps the calls above.
+    def _dk_args(self, B, d, what):
+        """(k, B as column-major, its leading dimension, D as float64 column-major n x k, its leading dimension)."""
+        D = np.asarray(d)
+        if B.ndim != 2:
+            raise capi.OtmbError(11, f"DimensionMismatch: d of {D.shape} is per column, {what} of {B.shape} has no columns")
+        k, Bc, ldb, _ = self._system_args(B, None)
+        if D.shape != B.shape:
+            raise capi.OtmbError(11, f"DimensionMismatch: d of {D.shape}, {what} of {B.shape}")
+        Dc, ldd = _column_major(np.asarray(D, dtype=np.float64))
+        return k, Bc, ldb, Dc, ldd
+
+    def _precondition_dk(self, Y, d, sigma, adjoint, pc):
+        k, Yc, ldy, Dc, ldd = self._dk_args(Y, d, "Y")
+        Z = np.zeros(Y.shape, dtype=np.float64, order="F")
+        self.ctx.check(capi.lib().otmb_op_precond_dk(self._h, int(bool(adjoint)), pc, k, Dc.ctypes.data, ldd, float(sigma), Yc.ctypes.data, ldy,
+                                                     Z.ctypes.data, max(Z.shape[0], 1)))
+        return Z
+
+    def _solve_dk(self, B, d, sigma, rtol, maxiter, x0, adjoint, pc):
+        k, Bc, ldb, Dc, ldd = self._dk_args(B, d, "B")
+        X = np.zeros(B.shape, dtype=np.float64, order="F")
+        if x0 is not None:
+            if np.shape(x0) != B.shape:
+                raise capi.OtmbError(11, f"DimensionMismatch: x0 of {np.shape(x0)}, B of {B.shape}")
+            X[...] = x0
+        iters, relres, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
+        rc = capi.lib().otmb_op_solve_dk(self._h, int(bool(adjoint)), k, Dc.ctypes.data, ldd, float(sigma), Bc.ctypes.data, ldb, X.ctypes.data,
+                                         max(X.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), iters.ctypes.data, relres.ctypes.data,
+                                         reason.ctypes.data, pc)
+        if rc != capi.NOT_CONVERGED:
+            self.ctx.check(rc)
+        return X, SolveInfo(rc, iters, relres, reason)
+
+    def _step_dk(self, X0, observe, weights, dt, theta, nsteps, first_slot, source, d, rtol, maxiter, adjoint, pc):
+        k, _, _, Dc, ldd = self._dk_args(X0, d, "X")
+        n = self.shape[1]
+        Xn = np.array(X0, dtype=np.float64, order="F")
+        Sc, lds = None, max(n, 1)
+        if source is not None:
+            if np.shape(source) != X0.shape:
+                raise capi.OtmbError(11, f"DimensionMismatch: source of {np.shape(source)}, X of {X0.shape}")
+            Sc, lds = _column_major(np.asarray(source))
+        q, Wc, ldw, obs, tw, mean = 0, None, max(n, 1), None, None, None
+        if observe is not None:
+            W, q = observers(np.asarray(observe), n)
+            Wc, ldw = _column_major(W)
+            obs = np.zeros((max(int(nsteps), 0), k, q), dtype=np.float64)
+        if weights is not None:
+            tw = time_weights(weights, nsteps)
+            mean = np.zeros(Xn.shape, dtype=np.float64, order="F")
+        iters, relres, reason = step_arrays(nsteps, k)
+        done = C.c_int64(0)
+        rc = capi.lib().otmb_op_step_dk(self._h, int(bool(adjoint)), k, Dc.ctypes.data, ldd, float(dt), float(theta), int(nsteps), int(first_slot),
+                                        None if Sc is None else Sc.ctypes.data, lds, Xn.ctypes.data, max(n, 1), float(rtol), int(maxiter), pc,
+                                        C.byref(done), iters.ctypes.data, relres.ctypes.data, reason.ctypes.data, q,
+                                        None if Wc is None else Wc.ctypes.data, ldw, None if obs is None else obs.ctypes.data,
+                                        None if tw is None else tw.ctypes.data, None if mean is None else mean.ctypes.data, max(n, 1))
+        if rc != capi.NOT_CONVERGED:
+            self.ctx.check(rc)
+        return Xn, StepInfo(rc, done.value, nsteps, iters, relres, reason, obs, mean)
+
+    def _periodic_dk(self, S, outer, dt, ncycle, theta, first_slot, d, x0, rtol, maxiter, adjoint, pc, ptol, restart, maxcycles):
+        k, Sc, lds, Dc, ldd = self._dk_args(S, d, "source")
+        X = np.zeros(S.shape, dtype=np.float64, order="F")
+        if x0 is not None:
+            if np.shape(x0) != S.shape:
+                raise capi.OtmbError(11, f"DimensionMismatch: x0 of {np.shape(x0)}, source of {S.shape}")
+            X[...] = x0
+        cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
+        msolve = np.zeros(k, dtype=np.int64)
+        rc = capi.lib().otmb_op_periodic_dk(self._h, int(bool(adjoint)), k, Dc.ctypes.data, ldd, float(dt), float(theta), int(ncycle), int(first_slot),
+                                            Sc.ctypes.data, lds, X.ctypes.data, max(X.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), pc,
+                                            float(ptol), int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data, reason.ctypes.data,
+                                            int(outer), msolve.ctypes.data)
         if rc != capi.NOT_CONVERGED:
             self.ctx.check(rc)
         return X, PeriodicInfo(rc, cycles, defect, reason, msolve)

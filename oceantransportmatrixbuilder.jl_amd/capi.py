@@ -262,6 +262,23 @@ SYMBOLS = {
                                              C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int32, _vp]),
     "otmb_op_periodic_pc": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
                                          C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int32, _vp]),
+    # per-column d (D, ldd in place of d): the arguments of solve_pc, precond, step_obs and periodic_pc
+    "otmb_op_solve_dk_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double,
+                                          C.c_int64, _vp, _vp, _vp, C.c_int32]),
+    "otmb_op_solve_dk": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double,
+                                      C.c_int64, _vp, _vp, _vp, C.c_int32]),
+    "otmb_op_precond_dk_dev": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, _vp, C.c_int64, _vp, C.c_int64]),
+    "otmb_op_precond_dk": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, _vp, C.c_int64, _vp, C.c_int64]),
+    "otmb_op_step_dk_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp,
+                                         C.c_int64, C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64]),
+    "otmb_op_step_dk": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp,
+                                     C.c_int64, C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64]),
+    "otmb_op_periodic_dk_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp,
+                                             C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int32,
+                                             _vp]),
+    "otmb_op_periodic_dk": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp,
+                                         C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int32,
+                                         _vp]),
     "otmb_op_combine_slots_dev": (C.c_int32, [_vp, _vp, C.c_int64]),
     "otmb_op_combine_slots": (C.c_int32, [_vp, _vp, C.c_int64]),
     "otmb_op_info": (C.c_int32, [_vp, _ip, _ip, _ip]),

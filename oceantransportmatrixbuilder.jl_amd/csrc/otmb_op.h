@@ -85,3 +85,20 @@ static int32_t op_stage_d(otmb_op *op, const double *d, double *&dev) {
     }
     return OTMB_OK;
 }
+// The same for the per-column calls (otmb_op_*_dk): ldd == 0 is the above (devld = 0); otherwise D's n x k block is staged compactly, once per
+// host call (devld = n).
+static int32_t op_stage_dk(otmb_op *op, const double *D, i64 ldd, i64 k, const double *&dev, i64 &devld) {
+    devld = 0;
+    if (!D || ldd == 0) {
+        double *one;
+        const int32_t rc = op_stage_d(op, D, one);
+        dev = one;
+        return rc;
+    }
+    otmb_ctx *ctx = op->ctx;
+    int32_t rc;
+    if ((rc = otmb_reserve(ctx, op->ds, (size_t)(op->n * k) * 8 + 8))) return rc;
+    dev = (const double *)op->ds.p;
+    devld = op->n;
+    return op->n > 0 ? op_upload(ctx, (double *)op->ds.p, D, ldd, op->n, k) : OTMB_OK;
+}

@@ -32,10 +32,16 @@
 //     q = M̄⁻¹·V_i      (the solver's own path on the mean values, σ = 0, from zero, the call's rtol / maxiter / precond: PdRun::msolve)
 //     Z_i = V_i + q / P  (pd_precond_kernel), kept behind the V block;   w = Z_i - Φ·Z_i;   CGS2 against V as before;   x += Z_0..i·y
 // and everything else -- the restart, verify and stop rules, cycles, defect -- is as above.  OTMB_OUTER_NONE is the method above, bit for bit.
+//
+// otmb_op_periodic_dk[_dev], every column with its own d (D, n x k): the step calls and the mean solves take the columns that iterate
+// gathered compactly, so their columns of D are gathered beside their states and sources (w.Dg), and the mean's preconditioner, made once
+// for all k columns, lends the gathered columns' sh, diag, multipliers and pivots to a compact copy (w.mpg).  The step and the solver give a
+// column the same bits at every position of a block, so a column's path does not depend on which other columns still run.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -247,7 +253,8 @@ struct PdCol {  // one column's iteration; ls (otmb_gmres.h): the triangle, the 
 struct PdWork {  // the arrays inside op->pd; every vector has the leading dimension ld (even)
     i64 n, k, m, ld, np;
     double *V, *W, *Sb, *part, *hs, *yv;  // V: k bases of m + 1 vectors; W, Sb: k columns each (contiguous: 2k for the first call)
-    double *Z = nullptr, *mp = nullptr;   // OTMB_OUTER_MEAN: k blocks of m preconditioned directions behind Sb; the mean's preconditioner (n-vectors)
+    double *Z = nullptr, *mp = nullptr;   // OTMB_OUTER_MEAN: k blocks of m preconditioned directions behind Sb; the mean's preconditioner
+    double *mpg = nullptr, *Dg = nullptr; // per-column d: the gathered columns of that preconditioner, and of D (2k columns: the first call's)
     double *v(i64 c, i64 j) const { return V + (c * (m + 1) + j) * ld; }
     double *z(i64 c, i64 j) const { return Z + (c * m + j) * ld; }
     double *partc(i64 c) const { return part + c * (m + 2) * np; }
@@ -255,17 +262,19 @@ struct PdWork {  // the arrays inside op->pd; every vector has the leading dimen
     double *hsc(i64 c) const { return hs + hso(c); }
 };
 
-// zvecs: the vectors of the Z block a column (0, or m with OTMB_OUTER_MEAN); pvecs: the n-vectors of the mean's preconditioner (0, 2 or 5)
-static int32_t pd_work(otmb_op *op, i64 k, i64 m, i64 zvecs, i64 pvecs, PdWork &w) {
+// zvecs: the vectors of the Z block a column (0, or m with OTMB_OUTER_MEAN); pdbl: the doubles of the mean's preconditioner (0 without);
+// percol: every column has its own d (a second block of pdbl doubles, and 2k gathered columns of D)
+static int32_t pd_work(otmb_op *op, i64 k, i64 m, i64 zvecs, size_t pdbl, bool percol, PdWork &w) {
     const i64 n = op->n;
     w.n = n, w.k = k, w.m = m, w.ld = (n + 1) & ~(i64)1, w.np = (n + PD_ROWS - 1) / PD_ROWS;
+    const size_t tail = (percol ? 2 : 1) * pdbl + (percol ? (size_t)(2 * k * w.ld) : 0);
     const double need = ((double)(m + 3 + zvecs) * (double)w.ld + (double)(m + 2) * (double)w.np + 3.0 * (double)(m + 2)) * (double)k * 8.0 +
-                        (double)pvecs * (double)w.ld * 8.0;
+                        (double)tail * 8.0;
     if (need >= 9.0e18) return otmb_fail(op->ctx, OTMB_ERR_ALLOC, "periodic: the workspace's size overflows");
     const size_t vec = (size_t)(m + 3 + zvecs) * (size_t)w.ld * (size_t)k;
     const size_t scal = (size_t)((m + 2) * w.np * k) + (size_t)(3 * (m + 2) * k);
     int32_t rc;
-    if ((rc = otmb_reserve(op->ctx, op->pd, (vec + scal + (size_t)(pvecs * w.ld)) * 8))) return rc;
+    if ((rc = otmb_reserve(op->ctx, op->pd, (vec + scal + tail) * 8))) return rc;
     w.V = (double *)op->pd.p;
     w.W = w.V + (size_t)(m + 1) * (size_t)w.ld * (size_t)k;
     w.Sb = w.W + w.ld * k;
@@ -273,7 +282,9 @@ static int32_t pd_work(otmb_op *op, i64 k, i64 m, i64 zvecs, i64 pvecs, PdWork &
     w.part = w.V + vec;
     w.hs = w.part + (m + 2) * w.np * k;
     w.yv = w.hs + 2 * (m + 2) * k;
-    w.mp = pvecs ? w.V + vec + scal : nullptr;
+    w.mp = pdbl ? w.V + vec + scal : nullptr;
+    w.mpg = pdbl && percol ? w.mp + pdbl : nullptr;
+    w.Dg = percol ? w.V + vec + scal + 2 * pdbl : nullptr;
     return OTMB_OK;
 }
 
@@ -310,7 +321,7 @@ struct PdRun {  // one call: the operator, the call's arguments, the workspace, 
     hipStream_t st;
     int32_t adjoint;  // the arguments, in the call's order (restart is m)
     i64 k;
-    const double *d;
+    SvD d;  // one d for every column, or D (n x k)
     double dt, theta;
     i64 ncycle, first_slot;
     const double *S;
@@ -331,7 +342,7 @@ struct PdRun {  // one call: the operator, the call's arguments, the workspace, 
     std::vector<double> hs, yh;  // the host's copy of w.hs (read_hs; hsh), the y of the restarts
     std::string step_msg;        // the text of the first step call that left a column not converged
     std::string msolve_msg;      // the same of the first mean solve
-    SvPrec mean_pc{};            // OTMB_OUTER_MEAN: the mean's preconditioner (σ = 0; in w.mp), and P = ncycle·δt
+    SvPrec mean_pc{};            // OTMB_OUTER_MEAN: the mean's preconditioner (σ = 0; in w.mp, for all k columns), and P = ncycle·δt
     double period = 0.0;
     std::vector<int64_t> s_it;   // a step call's report
     std::vector<double> s_rr;
@@ -358,7 +369,7 @@ struct PdRun {  // one call: the operator, the call's arguments, the workspace, 
 int32_t PdRun::prepare() {
     int32_t rc;
     const bool mean = outer == OTMB_OUTER_MEAN;
-    if ((rc = pd_work(op, k, m, mean ? m : 0, mean ? (precond == OTMB_PRECOND_LINES ? 5 : 2) : 0, w))) return rc;
+    if ((rc = pd_work(op, k, m, mean ? m : 0, mean ? sv_prec_doubles(op->n, precond == OTMB_PRECOND_LINES, sv_prec_cols(d, k)) : 0, d.percol(), w))) return rc;
     grid = dim3((unsigned)w.np), block = dim3(256);
     alx = ((uintptr_t)X & 15) == 0 && (ldx & 1) == 0;
     col.resize((size_t)k);
@@ -396,7 +407,7 @@ int32_t PdRun::mean_setup() {
     for (i64 s = 0; s < nslots; ++s) wt[(size_t)s] = (double)count[(size_t)s] / (double)ncycle;
     if ((rc = cb_combine(op, wt.data(), op->mean))) return rc;
     period = (double)ncycle * dt;
-    mean_pc = sv_prec_carve(w.mp, w.n, precond == OTMB_PRECOND_LINES);
+    mean_pc = sv_prec_carve(w.mp, w.n, precond == OTMB_PRECOND_LINES, sv_prec_cols(d, k), d.percol());
     SvValues on(op, op->mean);
     if ((rc = sv_prec_prepare(op, adjoint, precond, d, 0.0, mean_pc))) ctx->err += " (the cycle-mean operator)";
     return rc;
@@ -412,10 +423,19 @@ int32_t PdRun::msolve(std::vector<PdItem> &items) {
         for (i64 p = 0; p < kk; ++p)
             HIP_TRY(ctx, hipMemcpyAsync(w.Sb + p * ld, w.v(items[(size_t)p].col, items[(size_t)p].from), (size_t)n * 8, hipMemcpyDeviceToDevice, st));
         s_it.assign((size_t)kk, 0), s_rr.assign((size_t)kk, 0.0), s_why.assign((size_t)kk, 0);
+        SvPrec pc = mean_pc;
+        if (d.percol()) {  // the solve's column p is column items[p].col: its arrays of the preconditioner, gathered (u is every column's)
+            pc = sv_prec_carve(w.mpg, n, precond == OTMB_PRECOND_LINES, k, true);
+            pc.u = mean_pc.u;
+            double *const from[] = {mean_pc.sh, mean_pc.diag, mean_pc.m, mean_pc.piv}, *const to[] = {pc.sh, pc.diag, pc.m, pc.piv};
+            for (int a = 0; a < (pc.m ? 4 : 2); ++a)
+                for (i64 p = 0; p < kk; ++p)
+                    HIP_TRY(ctx, hipMemcpyAsync(to[a] + p * n, from[a] + items[(size_t)p].col * n, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+        }
         int32_t rc;
         {
             SvValues on(op, op->mean);
-            rc = sv_solve(op, adjoint, kk, mean_pc, w.Sb, ld, w.W, ld, 0, rtol, maxiter, s_it.data(), s_rr.data(), s_why.data(), precond);
+            rc = sv_solve(op, adjoint, kk, pc, w.Sb, ld, w.W, ld, 0, rtol, maxiter, s_it.data(), s_rr.data(), s_why.data(), precond);
         }
         if (rc == OTMB_OK) {
             for (i64 p = 0; p < kk; ++p) {
@@ -458,16 +478,26 @@ int32_t PdRun::cycle(std::vector<PdItem> &items, bool withS, double *sbuf) {
             else
                 HIP_TRY(ctx, hipMemcpyAsync(w.W + p * ld, it.from >= 0 ? dir(it.col, it.from) : X + it.col * ldx, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
             if (withS) HIP_TRY(ctx, hipMemcpyAsync(sbuf + p * ld, S + it.col * lds, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+            if (d.percol()) HIP_TRY(ctx, hipMemcpyAsync(w.Dg + p * ld, d.p + it.col * d.ld, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
         }
         s_it.assign((size_t)(ncycle * kk), 0), s_rr.assign((size_t)(ncycle * kk), 0.0), s_why.assign((size_t)(ncycle * kk), 0);
         int64_t done = 0;
-        const int32_t rc = otmb_op_step_dev(op, adjoint, kk, d, dt, theta, ncycle, first_slot, withS ? sbuf : nullptr, ld, w.W, ld, rtol, maxiter, precond, &done,
-                                            s_it.data(), s_rr.data(), s_why.data());
+        const int32_t rc = otmb_op_step_dk_dev(op, adjoint, kk, d.percol() ? w.Dg : d.p, d.percol() ? ld : 0, dt, theta, ncycle, first_slot, withS ? sbuf : nullptr,
+                                               ld, w.W, ld, rtol, maxiter, precond, &done, s_it.data(), s_rr.data(), s_why.data(), 0, nullptr, 0, nullptr, nullptr,
+                                               nullptr, 0);
         if (rc == OTMB_OK) {
             std::vector<char> seen((size_t)k, 0);  // (the first call holds a column twice: one call, one cycle)
             for (const PdItem &it : items)
                 if (!seen[(size_t)it.col]++) col[(size_t)it.col].cycles += 1;
             return OTMB_OK;
+        }
+        if (rc == OTMB_ERR_SINGULAR_PRECONDITIONER && d.percol()) {
+            // the step names the column by its place in the gathered block: the caller reads its own column and k.  (items hold the columns
+            // in rising order, a second copy of each behind them in the first call, so the smallest place is the smallest column.)
+            const size_t at = ctx->err.rfind(" (column "), end = at == std::string::npos ? at : ctx->err.find(')', at);
+            long long place = 0;
+            if (end != std::string::npos && sscanf(ctx->err.c_str() + at, " (column %lld", &place) == 1 && place >= 1 && place <= kk)
+                ctx->err.replace(at, end + 1 - at, " (column " + std::to_string(items[(size_t)(place - 1)].col + 1) + " of " + std::to_string(k) + ")");
         }
         if (rc != OTMB_ERR_NOT_CONVERGED) return rc;
         if (step_msg.empty()) step_msg = ctx->err;
@@ -641,13 +671,14 @@ int32_t PdRun::report(int64_t *cycles, double *defect, int32_t *reason, int64_t 
 
 extern "C" {
 
-int32_t otmb_op_periodic_pc_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t ncycle, int64_t first_slot,
-                                const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond,
-                                double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer,
-                                int64_t *msolve_iters) {
+int32_t otmb_op_periodic_dk_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
+                                int64_t first_slot, const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter,
+                                int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
+                                int32_t outer, int64_t *msolve_iters) {
     if (!op) return OTMB_ERR_INVALID_ARG;
     int32_t rc;
-    if ((rc = pd_check(op, k, dt, theta, ncycle, first_slot, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect, reason, outer)))
+    if ((rc = pd_check(op, k, dt, theta, ncycle, first_slot, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect, reason, outer)) ||
+        (rc = sv_check_d(op, "otmb_op_periodic_dk", D, ldd)))
         return rc;
     otmb_ctx *ctx = op->ctx;
     // the trivial answers: no rows, no source
@@ -657,7 +688,7 @@ int32_t otmb_op_periodic_pc_dev(otmb_op *op, int32_t adjoint, int64_t k, const d
         HIP_TRY(ctx, hipMemset2DAsync(X, (size_t)ldx * 8, 0, (size_t)op->n * 8, (size_t)k, ctx->stream));
         return pd_all_zero(k, cycles, defect, reason, msolve_iters);
     }
-    PdRun r{op, ctx, ctx->stream, adjoint, k, d, dt, theta, ncycle, first_slot, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, outer};
+    PdRun r{op, ctx, ctx->stream, adjoint, k, SvD{D, ldd}, dt, theta, ncycle, first_slot, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, outer};
     std::vector<PdItem> items;
     if ((rc = r.prepare()) || (outer == OTMB_OUTER_MEAN && (rc = r.mean_setup())) || (rc = r.source_norms(items)) || (rc = r.first_call(items))) return rc;
     for (bool more = true; more;)
@@ -666,27 +697,44 @@ int32_t otmb_op_periodic_pc_dev(otmb_op *op, int32_t adjoint, int64_t k, const d
     return r.report(cycles, defect, reason, msolve_iters);
 }
 
-int32_t otmb_op_periodic_pc(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t ncycle, int64_t first_slot,
+int32_t otmb_op_periodic_dk(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle, int64_t first_slot,
                             const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol,
                             int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters) {
     if (!op) return OTMB_ERR_INVALID_ARG;
     int32_t rc;
-    if ((rc = pd_check(op, k, dt, theta, ncycle, first_slot, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect, reason, outer)))
+    if ((rc = pd_check(op, k, dt, theta, ncycle, first_slot, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect, reason, outer)) ||
+        (rc = sv_check_d(op, "otmb_op_periodic_dk", D, ldd)))
         return rc;
     otmb_ctx *ctx = op->ctx;
     HIP_TRY(ctx, hipSetDevice(op->device));
     const i64 n = op->n;
-    double *dd;
-    if ((rc = op_reserve_xy(op, n, S ? n : 0, k)) || (rc = op_stage_d(op, d, dd))) return rc;
+    SvD dd;
+    if ((rc = op_reserve_xy(op, n, S ? n : 0, k)) || (rc = op_stage_dk(op, D, ldd, k, dd.p, dd.ld))) return rc;
     double *dx = (double *)op->xs.p, *ds = S ? (double *)op->ys.p : nullptr;
     if (n > 0) {  // staged once, however many cycles
         if (use_x0 && (rc = op_upload(ctx, dx, X, ldx, n, k))) return rc;
         if (S && (rc = op_upload(ctx, ds, S, lds, n, k))) return rc;
     }
-    rc = otmb_op_periodic_pc_dev(op, adjoint, k, dd, dt, theta, ncycle, first_slot, ds, n, dx, n, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, cycles,
-                                 defect, reason, outer, msolve_iters);
+    rc = otmb_op_periodic_dk_dev(op, adjoint, k, dd.p, dd.ld, dt, theta, ncycle, first_slot, ds, n, dx, n, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles,
+                                 cycles, defect, reason, outer, msolve_iters);
     if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED) return rc;
     return op_finish(ctx, rc, X, ldx, dx, n, k);
+}
+
+// the calls with one d for every column: ldd = 0 (otmb_op_periodic: OTMB_OUTER_NONE as well)
+int32_t otmb_op_periodic_pc_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t ncycle, int64_t first_slot,
+                                const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond,
+                                double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer,
+                                int64_t *msolve_iters) {
+    return otmb_op_periodic_dk_dev(op, adjoint, k, d, 0, dt, theta, ncycle, first_slot, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles,
+                                   cycles, defect, reason, outer, msolve_iters);
+}
+
+int32_t otmb_op_periodic_pc(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t ncycle, int64_t first_slot,
+                            const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol,
+                            int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters) {
+    return otmb_op_periodic_dk(op, adjoint, k, d, 0, dt, theta, ncycle, first_slot, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles,
+                               cycles, defect, reason, outer, msolve_iters);
 }
 
 int32_t otmb_op_periodic_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t ncycle, int64_t first_slot,

@@ -14,30 +14,54 @@ struct SvCol {  // one column's record (device; the host reads all k of them)
     i64 iters;
 };
 
-// A preconditioner: sh = σ + d, diag (Jacobi's diagonal) and, for the lines, the multipliers, u and the pivots -- n doubles each (m, u, piv:
-// null for Jacobi).  For a fixed (values, d, σ, adjoint) the arrays are always the same bits, so otmb_op_step (otmb_step.hip) computes them
-// once per slot and call.
-struct SvPrec {
-    double *sh, *diag, *m, *u, *piv;
+// The shift's diagonal part d: n values for every column (ld == 0, or p == null: none), or column c's own n values at p + c·ld (ld >= n):
+// the per-column calls (otmb_op_*_dk).  percol: a column's preconditioner is its own.
+struct SvD {
+    const double *p;
+    i64 ld;
+    bool percol() const { return p && ld != 0; }
 };
-// the record's arrays in a block of (lines ? 5 : 2) * n doubles: sh | diag | m | u | piv
-static inline SvPrec sv_prec_carve(double *a, i64 n, bool lines) {
-    return {a, a + n, lines ? a + 2 * n : nullptr, lines ? a + 3 * n : nullptr, lines ? a + 4 * n : nullptr};
+// the checks of D and ldd that the _dk calls add (`call`: the export's name), after the call's other checks and before anything is touched
+int32_t sv_check_d(otmb_op *op, const char *call, const double *D, int64_t ldd);
+
+// A preconditioner: sh = σ + d, diag (Jacobi's diagonal) and, for the lines, the multipliers, the pivots and u (m, piv, u: null for
+// Jacobi).  u does not depend on d and is n doubles; the others are n doubles when d is shared (cs = 0, kc = 1) and n x kc, column c at
+// + c·cs, when every column has its own d (cs = n, kc = the call's k).  For a fixed (values, d, σ, adjoint) the arrays are always the same
+// bits, so otmb_op_step (otmb_step.hip) computes them once per slot and call.
+struct SvPrec {
+    double *sh, *diag, *m, *piv, *u;
+    i64 cs, kc;
+};
+// the record's doubles, and its arrays in a block of that many: sh | diag | m | piv (n·kc each) | u (n)
+static inline size_t sv_prec_doubles(i64 n, bool lines, i64 kc) { return (size_t)(lines ? 4 * kc + 1 : 2 * kc) * (size_t)n; }
+static inline SvPrec sv_prec_carve(double *a, i64 n, bool lines, i64 kc, bool percol) {
+    const i64 b = n * kc;
+    return {a, a + b, lines ? a + 2 * b : nullptr, lines ? a + 3 * b : nullptr, lines ? a + 4 * b : nullptr, percol ? n : 0, kc};
+}
+// the columns a preconditioner for d and k columns holds
+static inline i64 sv_prec_cols(const SvD &d, i64 k) { return d.percol() ? k : 1; }
+// Column c's offset into arrays that are per column (PC: c·stride) or one for all (0).  The kernels that read sh, diag, m, piv or d inside a
+// register block are templates on PC: with one d the offset is the constant 0, the block's KB reads are one load of one address, and the
+// instantiation is the kernel as it was before columns could have their own d, in instructions and registers.
+template <bool PC>
+__device__ __forceinline__ i64 sv_pc(int c, i64 stride) {
+    return PC ? c * stride : 0;
 }
 
 // The line preconditioner (otmb_solve_lines.hip); both enqueue on the context's stream and need op->lines.
-// ln_factor: p.u, l from the CSC copy, then p.piv and p.m head to tail, from p.diag (Jacobi's diagonal, a).
-//            *bad (preset to ~0) receives the smallest 0-based index whose pivot is zero or not finite.
+// ln_factor: p.u and l (n doubles of scratch, which the factorisation alone reads) from the CSC copy, then every column's p.piv and p.m
+//            head to tail, from its p.diag (Jacobi's diagonal, a).  *bad (preset to ~0) receives the smallest (column << 32 | 0-based
+//            index) whose pivot is zero or not finite: the smallest column that has one, and its first.
 // ln_sweep:  Z = P⁻¹·Y for the columns whose record is SV_ACTIVE (cs == nullptr: every column).  Y and Z may be the same array.
-void ln_factor(otmb_op *op, int adjoint, const SvPrec &p, unsigned long long *bad);
+void ln_factor(otmb_op *op, int adjoint, const SvPrec &p, double *l, unsigned long long *bad);
 void ln_sweep(otmb_op *op, const SvCol *cs, i64 k, const SvPrec &p, const double *Y, i64 ldy, double *Z, i64 ldz);
 
-// sv_prec_prepare: computes p's arrays from the SELECTED values; a singular preconditioner is refused (OTMB_ERR_SINGULAR_PRECONDITIONER).
-//                  Waits for the device.
+// sv_prec_prepare: computes p's arrays (p.kc columns of them) from the SELECTED values; a singular preconditioner is refused
+//                  (OTMB_ERR_SINGULAR_PRECONDITIONER; per column: the message names the smallest column).  Waits for the device.
 // sv_solve:        otmb_op_solve_pc_dev (n > 0) after its argument checks and its preconditioner: p is prepared, for this adjoint and
 //                  precond and for the call's d, σ and selected values.
 // sv_check_step:   the argument checks the step shares with the solver (S may be null), then `more`, then the preconditioner.
-int32_t sv_prec_prepare(otmb_op *op, int adjoint, int32_t precond, const double *d, double sigma, const SvPrec &p);
+int32_t sv_prec_prepare(otmb_op *op, int adjoint, int32_t precond, const SvD &d, double sigma, const SvPrec &p);
 int32_t sv_solve(otmb_op *op, int adjoint, i64 k, const SvPrec &p, const double *B, i64 ldb, double *X, i64 ldx, int use_x0, double rtol, i64 maxiter,
                  int64_t *iters, double *relres, int32_t *reason, int32_t precond);
 // sv_step_complaint: the first complaint among rtol, maxiter, dt, theta, the count of steps (count_ok; the caller's text) and first_slot, in

@@ -36,6 +36,11 @@
 // otmb_op_solve_pc with OTMB_PRECOND_LINES: P is the part of M on the operator's lines (otmb_op_set_lines; otmb_solve_lines.hip states the
 // factorisation and the sweep).  Kernels 1 and 3 then leave p̂ and ŝ to a line sweep launched after them (p̂ = P⁻¹·p, ŝ = P⁻¹·s); ‖s‖² still
 // comes from kernel 3's own grid.  Everything else, the Jacobi path's bits included, is as above.
+//
+// otmb_op_solve_dk[_dev], otmb_op_precond_dk[_dev]: every column with its own d (D, n x k with leading dimension ldd; SvD).  The
+// preconditioner's arrays are then per column (SvPrec: column c at + c·cs, cs = n), and the kernels that read sh or diag take that stride
+// and are templates on PC (sv_pc, otmb_solve.h): with one d for all columns (ldd = 0: the exports above, which are these calls) the host
+// launches the PC = false instantiation, which reads the one sh[i] or diag[i] once for its register block and does not use the stride.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -60,19 +65,21 @@ __device__ __forceinline__ bool sv_any(const SvCol *__restrict__ cs, int want) {
 }
 
 // ---- setup ---------------------------------------------------------------------------------------------------------------------
-// sh = σ + d, diag = sh + the stored entries (i, i) of column i in storage order; bad = the first i whose diag is zero or not finite
+// sh = σ + d, diag = sh + the stored entries (i, i) of column i in storage order, for tracer column blockIdx.y + c0 (its d at + column·ldd,
+// its sh and diag at + column·cs); bad = the smallest (column << 32 | i) whose diag is zero or not finite: with one d for all, the first i
 __global__ __launch_bounds__(256) void sv_diag_kernel(const i64 *__restrict__ cp, const int *__restrict__ rv, const double *__restrict__ nz, i64 n,
-                                                      const double *__restrict__ d, double sigma, double *__restrict__ sh, double *__restrict__ diag,
-                                                      unsigned long long *__restrict__ bad) {
+                                                      const double *__restrict__ d, i64 ldd, double sigma, double *__restrict__ sh,
+                                                      double *__restrict__ diag, i64 cs, i64 c0, unsigned long long *__restrict__ bad) {
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const double s0 = d ? sigma + d[i] : sigma;
+    const unsigned long long c = (unsigned long long)(c0 + blockIdx.y);
+    const double s0 = d ? sigma + d[i + (i64)c * ldd] : sigma;
     double acc = s0;
     for (i64 j = cp[i] - 1; j < cp[i + 1] - 1; ++j)
         if (rv[j] == (int)i) acc = acc + nz[j];
-    sh[i] = s0;
-    diag[i] = acc;
-    if (acc == 0.0 || !isfinite(acc)) atomicMin(bad, (unsigned long long)i);
+    sh[i + (i64)c * cs] = s0;
+    diag[i + (i64)c * cs] = acc;
+    if (acc == 0.0 || !isfinite(acc)) atomicMin(bad, c << 32 | (unsigned long long)i);
 }
 // ‖b‖² partials
 template <int KB>
@@ -103,13 +110,17 @@ __global__ __launch_bounds__(256) void sv_x0_kernel(const SvCol *__restrict__ cs
 
 // ---- kernel 1: p = r + β·(p - ω·v), p̂ = p ./ diag (restart: p = r, r̂ = r) ---------------------------------------------------------
 // LINES: p̂ is left to the line sweep that follows (ln_sweep: p̂ = P⁻¹·p); likewise ŝ in kernel 3.
-template <int KB, bool LINES>
-__global__ __launch_bounds__(256) void sv_p_kernel(const SvCol *__restrict__ cs, i64 n, const double *__restrict__ diag, const double *__restrict__ r,
+// (diag: PC: column c's at + c·ds, as in kernel 3; otherwise one for all)
+template <int KB, bool LINES, bool PC>
+__global__ __launch_bounds__(256) void sv_p_kernel(const SvCol *__restrict__ cs, i64 n, const double *__restrict__ diag, i64 ds, const double *__restrict__ r,
                                                    double *__restrict__ rh, double *__restrict__ p, const double *__restrict__ v,
                                                    double *__restrict__ ph) {
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const double dg = LINES ? 1.0 : diag[i];
+    const double dg1 = LINES || PC ? 1.0 : diag[i];  // the one divisor of all columns
+    double dg[KB];  // (loaded ahead of the loop: the loads are in flight while the records are read)
+#pragma unroll
+    for (int c = 0; c < KB; ++c) dg[c] = PC && !LINES ? diag[i + c * ds] : dg1;
 #pragma unroll
     for (int c = 0; c < KB; ++c) {
         if (cs[c].state != SV_ACTIVE) continue;
@@ -125,13 +136,13 @@ __global__ __launch_bounds__(256) void sv_p_kernel(const SvCol *__restrict__ cs,
             pn = rr + u;
         }
         p[e] = pn;
-        if (!LINES) ph[e] = pn / dg;
+        if (!LINES) ph[e] = pn / dg[c];
     }
 }
 
 // ---- kernels 2 and 4, and the true residual: W = M·Z (modes 0, 1) or U - M·Z (mode 2) -------------------------------------------
 // mode 0: partial of U·W (U = r̂);  mode 1: partials of W·U (U = s) and W·W;  mode 2: partial of W·W.
-// Only columns in state `want` are written.  part: [column][2][np].
+// Only columns in state `want` are written.  part: [column][2][np].  sh: PC: column c's σ + d at + c·shs; otherwise one for all.
 template <int KB, int MODE>
 __device__ __forceinline__ void sv_finish(const SvCol *__restrict__ cs, int want, bool has, bool store, i64 i, const double (&y)[KB],
                                           const double *__restrict__ U, i64 ldu, double *__restrict__ W, i64 ldw, double (&q)[2 * KB]) {
@@ -150,10 +161,10 @@ __device__ __forceinline__ void sv_finish(const SvCol *__restrict__ cs, int want
     }
 }
 
-template <int KB, int MODE>
+template <int KB, int MODE, bool PC>
 __global__ __launch_bounds__(256) void sv_rows_kernel(const SvCol *__restrict__ cs, int want, const double *__restrict__ val, const int *__restrict__ col,
                                                       const i64 *__restrict__ sbase, const int *__restrict__ elen, i64 n, const double *__restrict__ sh,
-                                                      const double *__restrict__ Z, i64 ldz, const double *__restrict__ U, i64 ldu,
+                                                      i64 shs, const double *__restrict__ Z, i64 ldz, const double *__restrict__ U, i64 ldu,
                                                       double *__restrict__ W, i64 ldw, double *__restrict__ part, i64 np) {
     __shared__ double red[4 * 2 * KB];
     if (!sv_any<KB>(cs, want)) return;  // (uniform over the grid)
@@ -168,9 +179,8 @@ __global__ __launch_bounds__(256) void sv_rows_kernel(const SvCol *__restrict__ 
 #pragma unroll
             for (int c = 0; c < KB; ++c) y[c] = y[c] + a * Z[j + c * ldz];
         });
-        const double s = sh[i];
 #pragma unroll
-        for (int c = 0; c < KB; ++c) y[c] = y[c] + s * Z[i + c * ldz];
+        for (int c = 0; c < KB; ++c) y[c] = y[c] + sh[i + sv_pc<PC>(c, shs)] * Z[i + c * ldz];
     }
     double q[2 * KB];
     sv_finish<KB, MODE>(cs, want, has, len >= 0, i, y, U, ldu, W, ldw, q);
@@ -179,11 +189,11 @@ __global__ __launch_bounds__(256) void sv_rows_kernel(const SvCol *__restrict__ 
 }
 
 // one workgroup per long row, lane c folds column c; runs BEFORE sv_rows_kernel, which sums its value
-template <int MODE>
+template <int MODE, bool PC>
 __global__ __launch_bounds__(64) void sv_long_kernel(const SvCol *__restrict__ cs, int want, const double *__restrict__ val, const int *__restrict__ col,
                                                      const i64 *__restrict__ lrows, const i64 *__restrict__ loff, i64 ell, int k,
-                                                     const double *__restrict__ sh, const double *__restrict__ Z, i64 ldz, const double *__restrict__ U,
-                                                     i64 ldu, double *__restrict__ W, i64 ldw) {
+                                                     const double *__restrict__ sh, i64 shs, const double *__restrict__ Z, i64 ldz,
+                                                     const double *__restrict__ U, i64 ldu, double *__restrict__ W, i64 ldw) {
     __shared__ double sv[SP_TCH];
     __shared__ int sc[SP_TCH];
     const int lane = threadIdx.x;
@@ -195,17 +205,17 @@ __global__ __launch_bounds__(64) void sv_long_kernel(const SvCol *__restrict__ c
         double acc = 0.0;
         op_fold_long_row(val, col, b0, len, sv, sc, lane, on, [&](double a, i64 j) { acc = acc + a * Z[j + c * ldz]; });
         if (on) {
-            const double y = acc + sh[i] * Z[i + c * ldz];
+            const double y = acc + sh[i + sv_pc<PC>(c, shs)] * Z[i + c * ldz];
             W[i + c * ldw] = MODE == 2 ? U[i + c * ldu] - y : y;
         }
     }
 }
 
 // the adjoint: one lane per column of A over the CSC copy, 64 columns per workgroup
-template <int KB, int MODE>
+template <int KB, int MODE, bool PC>
 __global__ __launch_bounds__(64) void sv_cols_kernel(const SvCol *__restrict__ cs, int want, const i64 *__restrict__ cp, const int *__restrict__ rv,
-                                                     const double *__restrict__ nz, i64 n, const double *__restrict__ sh, const double *__restrict__ Z,
-                                                     i64 ldz, const double *__restrict__ U, i64 ldu, double *__restrict__ W, i64 ldw,
+                                                     const double *__restrict__ nz, i64 n, const double *__restrict__ sh, i64 shs,
+                                                     const double *__restrict__ Z, i64 ldz, const double *__restrict__ U, i64 ldu, double *__restrict__ W, i64 ldw,
                                                      double *__restrict__ part, i64 np) {
     __shared__ double sv[SP_TCH];
     __shared__ int sr[SP_TCH];
@@ -220,9 +230,8 @@ __global__ __launch_bounds__(64) void sv_cols_kernel(const SvCol *__restrict__ c
         for (int c = 0; c < KB; ++c) y[c] = y[c] + a * Z[r + c * ldz];
     });
     if (has) {
-        const double s = sh[colm];
 #pragma unroll
-        for (int c = 0; c < KB; ++c) y[c] = y[c] + s * Z[colm + c * ldz];
+        for (int c = 0; c < KB; ++c) y[c] = y[c] + sh[colm + sv_pc<PC>(c, shs)] * Z[colm + c * ldz];
     }
     double q[2 * KB];
     sv_finish<KB, MODE>(cs, want, has, true, colm, y, U, ldu, W, ldw, q);
@@ -232,15 +241,17 @@ __global__ __launch_bounds__(64) void sv_cols_kernel(const SvCol *__restrict__ c
 }
 
 // ---- kernel 3: s = r - α·v, ŝ = s ./ diag, ‖s‖² ------------------------------------------------------------------------------------
-template <int KB, bool LINES>
-__global__ __launch_bounds__(256) void sv_s_kernel(const SvCol *__restrict__ cs, i64 n, const double *__restrict__ diag, const double *__restrict__ r,
+template <int KB, bool LINES, bool PC>
+__global__ __launch_bounds__(256) void sv_s_kernel(const SvCol *__restrict__ cs, i64 n, const double *__restrict__ diag, i64 ds, const double *__restrict__ r,
                                                    const double *__restrict__ v, double *__restrict__ s, double *__restrict__ sh_, double *__restrict__ part,
                                                    i64 np) {
     __shared__ double red[4 * KB];
     if (!sv_any<KB>(cs, SV_ACTIVE)) return;
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
-    const double dg = !LINES && i < n ? diag[i] : 1.0;
-    double q[KB];
+    const double dg1 = !LINES && !PC && i < n ? diag[i] : 1.0;  // the one divisor of all columns
+    double q[KB], dg[KB];
+#pragma unroll
+    for (int c = 0; c < KB; ++c) dg[c] = PC && !LINES && i < n ? diag[i + c * ds] : dg1;
 #pragma unroll
     for (int c = 0; c < KB; ++c) {
         q[c] = 0.0;
@@ -249,7 +260,7 @@ __global__ __launch_bounds__(256) void sv_s_kernel(const SvCol *__restrict__ cs,
         const double av = cs[c].alpha * v[e];
         const double sn = r[e] - av;
         s[e] = sn;
-        if (!LINES) sh_[e] = sn / dg;
+        if (!LINES) sh_[e] = sn / dg[c];
         q[c] = sn * sn;
     }
     op_block_sum<KB>(q, red);
@@ -386,89 +397,116 @@ struct SvWork {  // the solver's device arrays inside op->sw
     SvPrec pc;    // the preconditioner the kernels read: the workspace's own block, or one prepared elsewhere (sv_solve)
     double *r, *rh, *p, *v, *s, *t, *ph, *sh_, *part, *parts;
     SvCol *cs;
-    unsigned long long *bad;  // [2]: the diagonal's, the pivots'
+    unsigned long long *bad;  // the setup's scratch (sv_precond_setup): [2] flags, the diagonal's and the pivots', then l
     i64 np;
 };
+// the setup's scratch for a preconditioner of kc columns: two flags and, behind them, the n doubles of l where the factorisation reads l
+// from there: the lines with several columns (one column passes l through m: ln_factor)
+static size_t sv_setup_doubles(i64 n, bool lines, i64 kc) { return 2 + (lines && kc > 1 ? (size_t)n : 0); }
 // selects the operator's device, reserves op->sw and carves it for k columns (k = 0: the preconditioner's arrays alone, otmb_op_precond_dev)
-// with np = (n + 63) / 64 partials per column and quantity: the adjoint's kernels write np of them, the rows' and the vector kernels fewer
-static int32_t sv_work(otmb_op *op, int32_t precond, i64 k, SvWork &w) {
+// with np = (n + 63) / 64 partials per column and quantity: the adjoint's kernels write np of them, the rows' and the vector kernels fewer.
+// kc: the columns of the workspace's own preconditioner (sv_prec_cols; 0: none, the caller brings a prepared one: sv_solve).  The layout,
+// in doubles, every size computed here once:
+//     pre (sh | diag | m | piv | u of kc columns) | 8 vectors of n·k | part: 2·np·k | parts: np·k | setup (flags, l) | the k records
+// kc = 0 keeps the block of ONE column in front, unused, so that the vectors lie where they lie in a call that makes its own preconditioner.
+static int32_t sv_work(otmb_op *op, int32_t precond, i64 k, i64 kc, bool percol, SvWork &w) {
     HIP_TRY(op->ctx, hipSetDevice(op->device));
     const bool lines = precond == OTMB_PRECOND_LINES;
-    const size_t n = (size_t)op->n, vec = n * (size_t)k, np = (n + 63) / 64, parts = np * (size_t)k, pre = (lines ? 5 : 2) * n;
-    const size_t doubles = pre + 8 * vec + 3 * parts;
+    const i64 pcols = std::max<i64>(kc, 1);
+    const size_t n = (size_t)op->n, vec = n * (size_t)k, np = (n + 63) / 64, parts = np * (size_t)k;
+    const size_t pre = sv_prec_doubles(op->n, lines, pcols), setup = sv_setup_doubles(op->n, lines, kc);
     int32_t rc;
-    if ((rc = otmb_reserve(op->ctx, op->sw, doubles * 8 + (size_t)k * sizeof(SvCol) + 64))) return rc;
+    if ((rc = otmb_reserve(op->ctx, op->sw, (pre + 8 * vec + 3 * parts + setup) * 8 + (size_t)k * sizeof(SvCol) + 64))) return rc;
     double *q = (double *)op->sw.p;
-    w.pc = sv_prec_carve(q, op->n, lines); q += pre;
+    w.pc = sv_prec_carve(q, op->n, lines, pcols, percol); q += pre;
     for (double **v : {&w.r, &w.rh, &w.p, &w.v, &w.s, &w.t, &w.ph, &w.sh_}) { *v = q; q += vec; }
     w.part = q; q += 2 * parts;
     w.parts = q; q += parts;
-    w.bad = (unsigned long long *)q; q += 2;
+    w.bad = (unsigned long long *)q; q += setup;
     w.cs = (SvCol *)q;
     w.np = (i64)np;
     return OTMB_OK;
 }
 
 // Z = Y ./ diag: the Jacobi preconditioner on its own (otmb_op_precond)
-template <int KB>
-__global__ __launch_bounds__(256) void sv_scale_kernel(i64 n, const double *__restrict__ diag, const double *Y, i64 ldy, double *Z, i64 ldz) {
+template <int KB, bool PC>
+__global__ __launch_bounds__(256) void sv_scale_kernel(i64 n, const double *__restrict__ diag, i64 ds, const double *Y, i64 ldy, double *Z, i64 ldz) {
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const double dg = diag[i];
+    double dg[KB];  // (ahead of the stores: Y and Z may be one array, so no load would move across them)
 #pragma unroll
-    for (int c = 0; c < KB; ++c) Z[i + c * ldz] = Y[i + c * ldy] / dg;
+    for (int c = 0; c < KB; ++c) dg[c] = diag[i + sv_pc<PC>(c, ds)];
+#pragma unroll
+    for (int c = 0; c < KB; ++c) Z[i + c * ldz] = Y[i + c * ldy] / dg[c];
 }
 
-// p's arrays -- sh and diag and, with lines, u, the multipliers and the pivots -- with flags[2] (device) for the verdict: a singular
-// preconditioner is refused here, before anything of the caller's is touched.  Waits for the device.
-static int32_t sv_precond_setup(otmb_op *op, int adjoint, int32_t precond, const double *d, double sigma, const SvPrec &p, unsigned long long *flags) {
+// p's arrays -- sh and diag and, with lines, u, the multipliers and the pivots, p.kc columns of all but u -- with flags (device:
+// sv_setup_doubles of scratch, the two flags first) for the verdict: a singular preconditioner is refused here, before anything of the
+// caller's is touched.  Waits for the device.
+static int32_t sv_precond_setup(otmb_op *op, int adjoint, int32_t precond, const SvD &d, double sigma, const SvPrec &p, unsigned long long *flags) {
     otmb_ctx *ctx = op->ctx;
     hipStream_t st = ctx->stream;
     const i64 n = op->n;
     HIP_TRY(ctx, hipMemsetAsync(flags, 0xff, 16, st));
-    hipLaunchKernelGGL(sv_diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const i64 *)op->cp.p, (const int *)op->rv.p,
-                       (const double *)op->nz.p, n, d, sigma, p.sh, p.diag, flags);
-    if (precond == OTMB_PRECOND_LINES) ln_factor(op, adjoint, p, flags + 1);
+    for (i64 c0 = 0; c0 < p.kc; c0 += 65535)  // (a grid's y extent)
+        hipLaunchKernelGGL(sv_diag_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)std::min<i64>(p.kc - c0, 65535)), dim3(256), 0, st,
+                           (const i64 *)op->cp.p, (const int *)op->rv.p, (const double *)op->nz.p, n, d.p, d.percol() ? d.ld : 0, sigma, p.sh, p.diag, p.cs,
+                           c0, flags);
+    if (precond == OTMB_PRECOND_LINES) ln_factor(op, adjoint, p, (double *)(flags + 2), flags + 1);
     HIP_TRY(ctx, hipGetLastError());
     unsigned long long bad[2] = {0, 0};
     HIP_TRY(ctx, hipMemcpyAsync(bad, flags, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     const int lines = precond == OTMB_PRECOND_LINES;  // the flag that decides: the pivots' with lines, otherwise the diagonal's
     if (bad[lines] == ~0ull) return OTMB_OK;
-    char msg[128];
+    char msg[128], col[64] = "";
     snprintf(msg, sizeof msg, lines ? "pivot[%lld] of the line factorisation is zero or not finite (1-based; the smallest such index)"
-                                    : "diag(M)[%lld] is zero or not finite (1-based; the first such index)", (long long)bad[lines] + 1);
-    return otmb_fail(ctx, OTMB_ERR_SINGULAR_PRECONDITIONER, msg);
+                                    : "diag(M)[%lld] is zero or not finite (1-based; the first such index)", (long long)(bad[lines] & 0xffffffffull) + 1);
+    if (p.cs) snprintf(col, sizeof col, " (column %lld of %lld)", (long long)(bad[lines] >> 32) + 1, (long long)p.kc);
+    return otmb_fail(ctx, OTMB_ERR_SINGULAR_PRECONDITIONER, (std::string(msg) + col).c_str());
 }
 
-// The same into arrays of the caller's (otmb_op_step keeps one set per slot it visits); op->sw lends the flags only, at its start (it is
-// reserved at the size of a workspace without columns, sv_work's k = 0).
-int32_t sv_prec_prepare(otmb_op *op, int adjoint, int32_t precond, const double *d, double sigma, const SvPrec &p) {
+int32_t sv_check_d(otmb_op *op, const char *call, const double *D, int64_t ldd) {
+    if (!D || ldd == 0 || ldd >= op->n) return OTMB_OK;
+    return otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, (std::string(call) + ": ldd must be 0 (the n values at D serve every column) or >= n").c_str());
+}
+
+// The same into arrays of the caller's (otmb_op_step keeps one set per slot it visits); op->sw lends the setup's scratch only, at its start
+// (it is reserved at the size of a workspace without columns, sv_work's k = 0).
+int32_t sv_prec_prepare(otmb_op *op, int adjoint, int32_t precond, const SvD &d, double sigma, const SvPrec &p) {
+    const bool lines = precond == OTMB_PRECOND_LINES;
     int32_t rc;
-    if ((rc = otmb_reserve(op->ctx, op->sw, (precond == OTMB_PRECOND_LINES ? 5 : 2) * (size_t)op->n * 8 + 64))) return rc;
+    if ((rc = otmb_reserve(op->ctx, op->sw, (sv_prec_doubles(op->n, lines, p.kc) + sv_setup_doubles(op->n, lines, p.kc)) * 8 + 64))) return rc;
     return sv_precond_setup(op, adjoint, precond, d, sigma, p, (unsigned long long *)op->sw.p);
 }
 
 // W = M·Z (modes 0, 1) or U - M·Z (mode 2) for the columns in state `want`, with the partials of the mode's dot products
-template <int MODE>
-static void sv_apply(otmb_op *op, const SvWork &w, int adjoint, i64 k, int want, const double *Z, i64 ldz, const double *U, i64 ldu, double *W, i64 ldw) {
+template <int MODE, bool PC>
+static void sv_apply_pc(otmb_op *op, const SvWork &w, int adjoint, i64 k, int want, const double *Z, i64 ldz, const double *U, i64 ldu, double *W, i64 ldw) {
     hipStream_t st = op->ctx->stream;
     const i64 n = op->n;
     if (!adjoint && op->nlong > 0)
-        hipLaunchKernelGGL(sv_long_kernel<MODE>, dim3((unsigned)op->nlong), dim3(64), 0, st, (const SvCol *)w.cs, want, (const double *)op->val.p,
-                           (const int *)op->col.p, (const i64 *)op->lrows.p, (const i64 *)op->loff.p, op->ell, (int)k, (const double *)w.pc.sh, Z, ldz, U, ldu,
-                           W, ldw);
+        hipLaunchKernelGGL((sv_long_kernel<MODE, PC>), dim3((unsigned)op->nlong), dim3(64), 0, st, (const SvCol *)w.cs, want, (const double *)op->val.p,
+                           (const int *)op->col.p, (const i64 *)op->lrows.p, (const i64 *)op->loff.p, op->ell, (int)k, (const double *)w.pc.sh, w.pc.cs, Z, ldz, U,
+                           ldu, W, ldw);
     op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
         constexpr int KB = decltype(kb)::value;
         if (adjoint)
-            hipLaunchKernelGGL((sv_cols_kernel<KB, MODE>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, (const SvCol *)w.cs + c0, want,
-                               (const i64 *)op->cp.p, (const int *)op->rv.p, (const double *)op->nz.p, n, (const double *)w.pc.sh, Z + c0 * ldz, ldz,
+            hipLaunchKernelGGL((sv_cols_kernel<KB, MODE, PC>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, (const SvCol *)w.cs + c0, want,
+                               (const i64 *)op->cp.p, (const int *)op->rv.p, (const double *)op->nz.p, n, (const double *)w.pc.sh + c0 * w.pc.cs, w.pc.cs, Z + c0 * ldz, ldz,
                                U + c0 * ldu, ldu, W + c0 * ldw, ldw, w.part + 2 * c0 * w.np, w.np);
         else
-            hipLaunchKernelGGL((sv_rows_kernel<KB, MODE>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const SvCol *)w.cs + c0, want,
+            hipLaunchKernelGGL((sv_rows_kernel<KB, MODE, PC>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const SvCol *)w.cs + c0, want,
                                (const double *)op->val.p, (const int *)op->col.p, (const i64 *)op->sbase.p, (const int *)op->elen.p, n,
-                               (const double *)w.pc.sh, Z + c0 * ldz, ldz, U + c0 * ldu, ldu, W + c0 * ldw, ldw, w.part + 2 * c0 * w.np, w.np);
+                               (const double *)w.pc.sh + c0 * w.pc.cs, w.pc.cs, Z + c0 * ldz, ldz, U + c0 * ldu, ldu, W + c0 * ldw, ldw,
+                               w.part + 2 * c0 * w.np, w.np);
     });
+}
+
+template <int MODE>
+static void sv_apply(otmb_op *op, const SvWork &w, int adjoint, i64 k, int want, const double *Z, i64 ldz, const double *U, i64 ldu, double *W, i64 ldw) {
+    if (w.pc.cs) sv_apply_pc<MODE, true>(op, w, adjoint, k, want, Z, ldz, U, ldu, W, ldw);
+    else sv_apply_pc<MODE, false>(op, w, adjoint, k, want, Z, ldz, U, ldu, W, ldw);
 }
 
 static void sv_scalar(otmb_op *op, const SvWork &w, i64 k, int step, i64 nb, double rtol, i64 maxiter) {
@@ -536,7 +574,7 @@ int32_t sv_report_open(otmb_ctx *ctx, const char *fmt, const char *const *names,
 // selected values), so a singular one was refused before this, with nothing of X touched.
 static int32_t sv_iterate(otmb_op *op, const SvWork &w, int adjoint, i64 k, const double *B, i64 ldb, double *X, i64 ldx, int use_x0, double rtol,
                           i64 maxiter, int64_t *iters, double *relres, int32_t *reason, int32_t precond) {
-    const bool lines = precond == OTMB_PRECOND_LINES;
+    const bool lines = precond == OTMB_PRECOND_LINES, pc = w.pc.cs != 0;  // (with lines kernels 1 and 3 read no diag: PC = false)
     otmb_ctx *ctx = op->ctx;
     hipStream_t st = ctx->stream;
     const i64 n = op->n, nb = (n + 255) / 256, np = w.np;
@@ -566,8 +604,8 @@ static int32_t sv_iterate(otmb_op *op, const SvWork &w, int adjoint, i64 k, cons
         for (i64 it = 0; it < batch; ++it) {
             op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
                 constexpr int KB = decltype(kb)::value;
-                hipLaunchKernelGGL((lines ? sv_p_kernel<KB, true> : sv_p_kernel<KB, false>), grid, block, 0, st, (const SvCol *)w.cs + c0, n,
-                                   (const double *)w.pc.diag, (const double *)w.r + c0 * n, w.rh + c0 * n, w.p + c0 * n, (const double *)w.v + c0 * n,
+                hipLaunchKernelGGL((lines ? sv_p_kernel<KB, true, false> : pc ? sv_p_kernel<KB, false, true> : sv_p_kernel<KB, false, false>), grid, block, 0, st, (const SvCol *)w.cs + c0, n,
+                                   (const double *)w.pc.diag + c0 * w.pc.cs, w.pc.cs, (const double *)w.r + c0 * n, w.rh + c0 * n, w.p + c0 * n, (const double *)w.v + c0 * n,
                                    w.ph + c0 * n);
             });
             if (lines) ln_sweep(op, w.cs, k, w.pc, w.p, n, w.ph, n);
@@ -575,8 +613,8 @@ static int32_t sv_iterate(otmb_op *op, const SvWork &w, int adjoint, i64 k, cons
             sv_scalar(op, w, k, SV_S_ALPHA, nbm, rtol, maxiter);
             op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
                 constexpr int KB = decltype(kb)::value;
-                hipLaunchKernelGGL((lines ? sv_s_kernel<KB, true> : sv_s_kernel<KB, false>), grid, block, 0, st, (const SvCol *)w.cs + c0, n,
-                                   (const double *)w.pc.diag, (const double *)w.r + c0 * n, (const double *)w.v + c0 * n, w.s + c0 * n, w.sh_ + c0 * n,
+                hipLaunchKernelGGL((lines ? sv_s_kernel<KB, true, false> : pc ? sv_s_kernel<KB, false, true> : sv_s_kernel<KB, false, false>), grid, block, 0, st, (const SvCol *)w.cs + c0, n,
+                                   (const double *)w.pc.diag + c0 * w.pc.cs, w.pc.cs, (const double *)w.r + c0 * n, (const double *)w.v + c0 * n, w.s + c0 * n, w.sh_ + c0 * n,
                                    w.parts + c0 * np, np);
             });
             if (lines) ln_sweep(op, w.cs, k, w.pc, w.s, n, w.sh_, n);
@@ -611,42 +649,54 @@ int32_t sv_solve(otmb_op *op, int adjoint, i64 k, const SvPrec &p, const double 
                  int64_t *iters, double *relres, int32_t *reason, int32_t precond) {
     SvWork w;
     int32_t rc;
-    if ((rc = sv_work(op, precond, k, w))) return rc;
+    if ((rc = sv_work(op, precond, k, 0, false, w))) return rc;
     w.pc = p;
     return sv_iterate(op, w, adjoint, k, B, ldb, X, ldx, use_x0, rtol, maxiter, iters, relres, reason, precond);
 }
 
 extern "C" {
 
-int32_t otmb_op_solve_pc_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X,
+int32_t otmb_op_solve_dk_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double sigma, const double *B, int64_t ldb, double *X,
                              int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason, int32_t precond) {
     if (!op) return OTMB_ERR_INVALID_ARG;
     int32_t rc;
-    if ((rc = sv_check(op, precond, k, B, ldb, X, ldx, rtol, maxiter, iters, relres, reason))) return rc;
+    if ((rc = sv_check(op, precond, k, B, ldb, X, ldx, rtol, maxiter, iters, relres, reason)) || (rc = sv_check_d(op, "otmb_op_solve_dk", D, ldd))) return rc;
     if (op->n == 0) return sv_report_empty(k, iters, relres, reason);
+    const SvD d = {D, ldd};
     SvWork w;
-    if ((rc = sv_work(op, precond, k, w)) || (rc = sv_precond_setup(op, adjoint, precond, d, sigma, w.pc, w.bad))) return rc;
+    if ((rc = sv_work(op, precond, k, sv_prec_cols(d, k), d.percol(), w)) || (rc = sv_precond_setup(op, adjoint, precond, d, sigma, w.pc, w.bad))) return rc;
     return sv_iterate(op, w, adjoint, k, B, ldb, X, ldx, use_x0, rtol, maxiter, iters, relres, reason, precond);
 }
 
-int32_t otmb_op_solve_pc(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X, int64_t ldx,
-                         int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason, int32_t precond) {
+int32_t otmb_op_solve_dk(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double sigma, const double *B, int64_t ldb, double *X,
+                         int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason, int32_t precond) {
     if (!op) return OTMB_ERR_INVALID_ARG;
     int32_t rc;
-    if ((rc = sv_check(op, precond, k, B, ldb, X, ldx, rtol, maxiter, iters, relres, reason))) return rc;
+    if ((rc = sv_check(op, precond, k, B, ldb, X, ldx, rtol, maxiter, iters, relres, reason)) || (rc = sv_check_d(op, "otmb_op_solve_dk", D, ldd))) return rc;
     otmb_ctx *ctx = op->ctx;
     HIP_TRY(ctx, hipSetDevice(op->device));
     const i64 n = op->n;
-    double *dd;
-    if ((rc = op_reserve_xy(op, n, n, k)) || (rc = op_stage_d(op, d, dd))) return rc;
+    SvD dd;
+    if ((rc = op_reserve_xy(op, n, n, k)) || (rc = op_stage_dk(op, D, ldd, k, dd.p, dd.ld))) return rc;
     double *db = (double *)op->xs.p, *dx = (double *)op->ys.p;
     if (n > 0) {
         if ((rc = op_upload(ctx, db, B, ldb, n, k))) return rc;
         if (use_x0 && (rc = op_upload(ctx, dx, X, ldx, n, k))) return rc;
     }
-    rc = otmb_op_solve_pc_dev(op, adjoint, k, dd, sigma, db, n, dx, n, use_x0, rtol, maxiter, iters, relres, reason, precond);
+    rc = otmb_op_solve_dk_dev(op, adjoint, k, dd.p, dd.ld, sigma, db, n, dx, n, use_x0, rtol, maxiter, iters, relres, reason, precond);
     if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED) return rc;
     return op_finish(ctx, rc, X, ldx, dx, n, k);
+}
+
+// the calls with one d for every column: ldd = 0
+int32_t otmb_op_solve_pc_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X,
+                             int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason, int32_t precond) {
+    return otmb_op_solve_dk_dev(op, adjoint, k, d, 0, sigma, B, ldb, X, ldx, use_x0, rtol, maxiter, iters, relres, reason, precond);
+}
+
+int32_t otmb_op_solve_pc(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X, int64_t ldx,
+                         int32_t use_x0, double rtol, int64_t maxiter, int64_t *iters, double *relres, int32_t *reason, int32_t precond) {
+    return otmb_op_solve_dk(op, adjoint, k, d, 0, sigma, B, ldb, X, ldx, use_x0, rtol, maxiter, iters, relres, reason, precond);
 }
 
 int32_t otmb_op_solve_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double sigma, const double *B, int64_t ldb, double *X, int64_t ldx,
@@ -659,43 +709,55 @@ int32_t otmb_op_solve(otmb_op *op, int32_t adjoint, int64_t k, const double *d, 
     return otmb_op_solve_pc(op, adjoint, k, d, sigma, B, ldb, X, ldx, use_x0, rtol, maxiter, iters, relres, reason, OTMB_PRECOND_JACOBI);
 }
 
-// Z = P⁻¹·Y: the preconditioner of otmb_op_solve_pc on its own
-int32_t otmb_op_precond_dev(otmb_op *op, int32_t adjoint, int32_t precond, int64_t k, const double *d, double sigma, const double *Y, int64_t ldy,
-                            double *Z, int64_t ldz) {
+// Z = P⁻¹·Y: the preconditioner of otmb_op_solve_dk on its own
+int32_t otmb_op_precond_dk_dev(otmb_op *op, int32_t adjoint, int32_t precond, int64_t k, const double *D, int64_t ldd, double sigma, const double *Y,
+                               int64_t ldy, double *Z, int64_t ldz) {
     if (!op) return OTMB_ERR_INVALID_ARG;
     int32_t rc;
-    if ((rc = sv_check_apply(op, precond, k, Y, ldy, Z, ldz))) return rc;
+    if ((rc = sv_check_apply(op, precond, k, Y, ldy, Z, ldz)) || (rc = sv_check_d(op, "otmb_op_precond_dk", D, ldd))) return rc;
     otmb_ctx *ctx = op->ctx;
     const i64 n = op->n;
     if (n == 0) return OTMB_OK;
+    const SvD d = {D, ldd};
     SvWork w;
-    if ((rc = sv_work(op, precond, 0, w)) || (rc = sv_precond_setup(op, adjoint, precond, d, sigma, w.pc, w.bad))) return rc;
+    if ((rc = sv_work(op, precond, 0, sv_prec_cols(d, k), d.percol(), w)) || (rc = sv_precond_setup(op, adjoint, precond, d, sigma, w.pc, w.bad))) return rc;
     if (precond == OTMB_PRECOND_LINES)
         ln_sweep(op, nullptr, k, w.pc, Y, ldy, Z, ldz);
     else
         op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
-            hipLaunchKernelGGL((sv_scale_kernel<decltype(kb)::value>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n,
-                               (const double *)w.pc.diag, Y + c0 * ldy, ldy, Z + c0 * ldz, ldz);
+            constexpr int KB = decltype(kb)::value;
+            hipLaunchKernelGGL((w.pc.cs ? sv_scale_kernel<KB, true> : sv_scale_kernel<KB, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n,
+                               (const double *)w.pc.diag + c0 * w.pc.cs, w.pc.cs, Y + c0 * ldy, ldy, Z + c0 * ldz, ldz);
         });
     HIP_TRY(ctx, hipGetLastError());
     return OTMB_OK;
 }
 
-int32_t otmb_op_precond(otmb_op *op, int32_t adjoint, int32_t precond, int64_t k, const double *d, double sigma, const double *Y, int64_t ldy, double *Z,
-                        int64_t ldz) {
+int32_t otmb_op_precond_dk(otmb_op *op, int32_t adjoint, int32_t precond, int64_t k, const double *D, int64_t ldd, double sigma, const double *Y, int64_t ldy,
+                           double *Z, int64_t ldz) {
     if (!op) return OTMB_ERR_INVALID_ARG;
     int32_t rc;
-    if ((rc = sv_check_apply(op, precond, k, Y, ldy, Z, ldz))) return rc;
+    if ((rc = sv_check_apply(op, precond, k, Y, ldy, Z, ldz)) || (rc = sv_check_d(op, "otmb_op_precond_dk", D, ldd))) return rc;
     otmb_ctx *ctx = op->ctx;
     const i64 n = op->n;
     if (n == 0) return OTMB_OK;
     HIP_TRY(ctx, hipSetDevice(op->device));
-    double *dd;
-    if ((rc = op_reserve_xy(op, n, n, k)) || (rc = op_stage_d(op, d, dd))) return rc;
+    SvD dd;
+    if ((rc = op_reserve_xy(op, n, n, k)) || (rc = op_stage_dk(op, D, ldd, k, dd.p, dd.ld))) return rc;
     double *dy = (double *)op->xs.p, *dz = (double *)op->ys.p;
     if ((rc = op_upload(ctx, dy, Y, ldy, n, k))) return rc;
-    if ((rc = otmb_op_precond_dev(op, adjoint, precond, k, dd, sigma, dy, n, dz, n))) return rc;
+    if ((rc = otmb_op_precond_dk_dev(op, adjoint, precond, k, dd.p, dd.ld, sigma, dy, n, dz, n))) return rc;
     return op_finish(ctx, OTMB_OK, Z, ldz, dz, n, k);
+}
+
+int32_t otmb_op_precond_dev(otmb_op *op, int32_t adjoint, int32_t precond, int64_t k, const double *d, double sigma, const double *Y, int64_t ldy,
+                            double *Z, int64_t ldz) {
+    return otmb_op_precond_dk_dev(op, adjoint, precond, k, d, 0, sigma, Y, ldy, Z, ldz);
+}
+
+int32_t otmb_op_precond(otmb_op *op, int32_t adjoint, int32_t precond, int64_t k, const double *d, double sigma, const double *Y, int64_t ldy, double *Z,
+                        int64_t ldz) {
+    return otmb_op_precond_dk(op, adjoint, precond, k, d, 0, sigma, Y, ldy, Z, ldz);
 }
 
 }  // extern "C"

@@ -3,7 +3,7 @@
 // are tridiagonal and are solved by the Thomas recurrence.  For the transport matrices a line is one water column, top to bottom: the
 // vertical coupling (TκVML: ~1e-3 s⁻¹ against horizontal rates of ~1e-7 s⁻¹) is then inside the preconditioner.
 //
-// Per solve, with j = next[i] (include/otmb.h states this as the contract; tests/solve_lines_ref.py restates it bit for bit):
+// Per solve and, where every column has its own d (otmb_op_*_dk), per column -- a is the column's, u and l are not --, with j = next[i] (include/otmb.h states this as the contract; tests/solve_lines_ref.py restates it bit for bit):
 //     a_i = Jacobi's diag[i];  u_i = Σ stored (i, j) of A, l_i = Σ stored (j, i) of A, each from +0.0 in storage order (adjoint: swapped)
 //     piv_head = a_head;  m_j = l_i / piv_i;  piv_j = a_j - m_j·u_i            (no pivoting, no FMA; a zero or non-finite pivot is refused)
 //     z = P⁻¹·y:  y'_head = y_head, y'_j = y_j - m_j·y'_i;  z_tail = y'_tail / piv_tail, z_i = (y'_i - u_i·z_j) / piv_i
@@ -74,36 +74,46 @@ __global__ __launch_bounds__(256) void ln_ul_kernel(const i64 *__restrict__ cp, 
     l[i] = adjoint ? up : lo;
 }
 
-// ---- the factorisation: m holds l on entry (by i) and the multipliers on return (by j; 0 at a head) ------------------------------
+// ---- the factorisation: u and l (by i) are the lines' own; diag, m (the multipliers, by j; 0 at a head) and piv are a column's ------------
+// One lane owns one line of ONE column: a line is a short dependent chain of divisions, so the kc columns go to more lanes (the workgroups
+// of column c follow those of column c - 1), not to a loop inside the lane that owns the line.  Column c's arrays lie at + c·cs.  l == null
+// (one column): m holds l on entry, as ln_ul_kernel left it; otherwise l is an array of its own, which every column reads.
+// bad: the smallest (column << 32 | index): with one column, the smallest index.
 __global__ __launch_bounds__(64) void ln_factor_kernel(const int *__restrict__ heads, i64 nheads, const int *__restrict__ nxt,
-                                                       const double *__restrict__ diag, const double *__restrict__ u, double *__restrict__ m,
-                                                       double *__restrict__ piv, ull *__restrict__ bad) {
-    const i64 h = (i64)blockIdx.x * 64 + threadIdx.x;
+                                                       const double *__restrict__ diag, const double *__restrict__ u, double *m,
+                                                       double *__restrict__ piv, ull *__restrict__ bad, const double *l = nullptr, i64 cs = 0) {
+    const i64 nhb = (nheads + 63) / 64;
+    const ull c = (ull)(blockIdx.x / nhb);
+    const i64 h = ((i64)blockIdx.x - (i64)c * nhb) * 64 + threadIdx.x;
     if (h >= nheads) return;
+    const i64 o = (i64)c * cs;
+    if (!l) l = m;
     int i = heads[h];
-    double pv = diag[i], l = m[i];
-    m[i] = 0.0;
+    double pv = diag[i + o], lv = l[i];
+    m[i + o] = 0.0;
     for (;;) {
-        piv[i] = pv;
-        if (pv == 0.0 || !isfinite(pv)) atomicMin(bad, (ull)i);
+        piv[i + o] = pv;
+        if (pv == 0.0 || !isfinite(pv)) atomicMin(bad, c << 32 | (ull)i);
         const int j = nxt[i];
         if (j < 0) break;
-        const double mj = l / pv;
-        l = m[j];
-        m[j] = mj;
+        const double mj = lv / pv;
+        lv = l[j];
+        m[j + o] = mj;
         const double t = mj * u[i];
-        pv = diag[j] - t;
+        pv = diag[j + o] - t;
         i = j;
     }
 }
 
 // ---- the sweep: Z = P⁻¹·Y, forward to the tail (y' is parked in Z), then back ------------------------------------------------------
-// Only columns in state SV_ACTIVE are read or written (cs == nullptr: all of them).  Y and Z may be the same array.
-template <int KB>
+// Only columns in state SV_ACTIVE are read or written (cs == nullptr: all of them).  Y and Z may be the same array.  PC: column c's multipliers
+// and pivots lie at + c·ps; otherwise there is one set for all columns, read once per row of the register block as before columns could
+// have their own.
+template <int KB, bool PC = false>
 __global__ __launch_bounds__(64) void ln_sweep_kernel(const SvCol *__restrict__ cs, const int *__restrict__ heads, i64 nheads,
                                                       const int *__restrict__ nxt, const int *__restrict__ prv, const double *__restrict__ m,
                                                       const double *__restrict__ u, const double *__restrict__ piv, const double *Y, i64 ldy,
-                                                      double *Z, i64 ldz) {
+                                                      double *Z, i64 ldz, i64 ps = 0) {
     bool on[KB], any = false;
 #pragma unroll
     for (int c = 0; c < KB; ++c) {
@@ -118,31 +128,31 @@ __global__ __launch_bounds__(64) void ln_sweep_kernel(const SvCol *__restrict__ 
 #pragma unroll
     for (int c = 0; c < KB; ++c) y[c] = on[c] ? Y[i + c * ldy] : 0.0;
     for (int j = nxt[i]; j >= 0; j = nxt[i]) {
-        const double mj = m[j];
+        const double mj = PC ? 0.0 : m[j];
 #pragma unroll
         for (int c = 0; c < KB; ++c) {
             if (!on[c]) continue;
             Z[i + c * ldz] = y[c];
-            const double t = mj * y[c];
+            const double t = (PC ? m[j + c * ps] : mj) * y[c];
             y[c] = Y[j + c * ldy] - t;
         }
         i = j;
     }
-    double pv = piv[i];
+    double pv = PC ? 0.0 : piv[i];
 #pragma unroll
     for (int c = 0; c < KB; ++c) {
         if (!on[c]) continue;
-        y[c] = y[c] / pv;
+        y[c] = y[c] / (PC ? piv[i + c * ps] : pv);
         Z[i + c * ldz] = y[c];
     }
     for (int p = prv[i]; p >= 0; p = prv[i]) {
         const double up = u[p];
-        pv = piv[p];
+        if (!PC) pv = piv[p];
 #pragma unroll
         for (int c = 0; c < KB; ++c) {
             if (!on[c]) continue;
             const double t = up * y[c];
-            y[c] = (Z[p + c * ldz] - t) / pv;
+            y[c] = (Z[p + c * ldz] - t) / (PC ? piv[p + c * ps] : pv);
             Z[p + c * ldz] = y[c];
         }
         i = p;
@@ -156,23 +166,25 @@ static LnTables ln_tables(const otmb_op *op) {
     return {nxt, nxt + op->n, nxt + 2 * op->n};
 }
 
-void ln_factor(otmb_op *op, int adjoint, const SvPrec &p, ull *bad) {
+void ln_factor(otmb_op *op, int adjoint, const SvPrec &p, double *l, ull *bad) {
+    if (p.kc == 1) l = nullptr;  // one column: l goes through m, no scratch
     hipStream_t st = op->ctx->stream;
     const i64 n = op->n;
     const LnTables ln = ln_tables(op);
     hipLaunchKernelGGL(ln_ul_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const i64 *)op->cp.p, (const int *)op->rv.p,
-                       (const double *)op->nz.p, n, ln.nxt, adjoint, p.u, p.m);
-    hipLaunchKernelGGL(ln_factor_kernel, dim3((unsigned)((op->nheads + 63) / 64)), dim3(64), 0, st, ln.heads, op->nheads, ln.nxt,
-                       (const double *)p.diag, (const double *)p.u, p.m, p.piv, bad);
+                       (const double *)op->nz.p, n, ln.nxt, adjoint, p.u, l ? l : p.m);
+    hipLaunchKernelGGL(ln_factor_kernel, dim3((unsigned)((op->nheads + 63) / 64 * p.kc)), dim3(64), 0, st, ln.heads, op->nheads, ln.nxt,
+                       (const double *)p.diag, (const double *)p.u, p.m, p.piv, bad, (const double *)l, p.cs);
 }
 
 void ln_sweep(otmb_op *op, const SvCol *cs, i64 k, const SvPrec &p, const double *Y, i64 ldy, double *Z, i64 ldz) {
     hipStream_t st = op->ctx->stream;
     const LnTables ln = ln_tables(op);
     op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
-        hipLaunchKernelGGL((ln_sweep_kernel<decltype(kb)::value>), dim3((unsigned)((op->nheads + 63) / 64)), dim3(64), 0, st, cs ? cs + c0 : nullptr,
-                           ln.heads, op->nheads, ln.nxt, ln.prv, (const double *)p.m, (const double *)p.u, (const double *)p.piv, Y + c0 * ldy, ldy,
-                           Z + c0 * ldz, ldz);
+        constexpr int KB = decltype(kb)::value;
+        hipLaunchKernelGGL((p.cs ? ln_sweep_kernel<KB, true> : ln_sweep_kernel<KB, false>), dim3((unsigned)((op->nheads + 63) / 64)), dim3(64), 0, st, cs ? cs + c0 : nullptr,
+                           ln.heads, op->nheads, ln.nxt, ln.prv, (const double *)p.m + c0 * p.cs, (const double *)p.u, (const double *)p.piv + c0 * p.cs, Y + c0 * ldy,
+                           ldy, Z + c0 * ldz, ldz, p.cs);
     });
 }
 

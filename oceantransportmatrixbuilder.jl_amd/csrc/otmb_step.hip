@@ -24,7 +24,8 @@
 struct StLine {  // the elementwise line's constants
     double sigma, theta, c;
 };
-// b from x, the finished fold w and the row's s and d (null: none).  One operation per statement: the contract's association.
+// b from x, the finished fold w and the row's s and d (null: none; d: the tracer's own column, or the one all share).  One operation per
+// statement: the contract's association.
 __device__ __forceinline__ double st_line(const StLine &q, double x, double w, const double *__restrict__ d, i64 i, const double *__restrict__ s) {
     double e = w;
     if (d) {
@@ -53,11 +54,11 @@ __global__ __launch_bounds__(256) void st_stream_kernel(i64 n, double sigma, con
     }
 }
 
-// ---- θ < 1, A: one lane per short row; the long rows are st_long_kernel's ------------------------------------------------------------------
-template <int KB>
+// ---- θ < 1, A: one lane per short row; the long rows are st_long_kernel's.  PC (here and below): tracer c's d lies at d + c·ldd, otherwise all share one --
+template <int KB, bool PC = false>
 __global__ __launch_bounds__(256) void st_rows_kernel(StLine q, const double *__restrict__ val, const int *__restrict__ col, const i64 *__restrict__ sbase,
                                                       const int *__restrict__ elen, i64 n, const double *__restrict__ d, const double *__restrict__ X, i64 ldx,
-                                                      const double *__restrict__ S, i64 lds, double *__restrict__ B, i64 ldb) {
+                                                      const double *__restrict__ S, i64 lds, double *__restrict__ B, i64 ldb, i64 ldd = 0) {
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int len = elen[i];
@@ -70,13 +71,14 @@ __global__ __launch_bounds__(256) void st_rows_kernel(StLine q, const double *__
         for (int c = 0; c < KB; ++c) w[c] = w[c] + a * X[j + c * ldx];
     });
 #pragma unroll
-    for (int c = 0; c < KB; ++c) B[i + c * ldb] = st_line(q, X[i + c * ldx], w[c], d, i, S ? S + i + c * lds : nullptr);
+    for (int c = 0; c < KB; ++c) B[i + c * ldb] = st_line(q, X[i + c * ldx], w[c], d ? d + (PC ? c * ldd : 0) : nullptr, i, S ? S + i + c * lds : nullptr);
 }
 
 // one workgroup per long row, lane c folds tracer c (groups of 64 tracers)
+template <bool PC = false>
 __global__ __launch_bounds__(64) void st_long_kernel(StLine q, const double *__restrict__ val, const int *__restrict__ col, const i64 *__restrict__ lrows,
                                                      const i64 *__restrict__ loff, i64 ell, int k, const double *__restrict__ d, const double *__restrict__ X,
-                                                     i64 ldx, const double *__restrict__ S, i64 lds, double *__restrict__ B, i64 ldb) {
+                                                     i64 ldx, const double *__restrict__ S, i64 lds, double *__restrict__ B, i64 ldb, i64 ldd = 0) {
     __shared__ double sv[SP_TCH];
     __shared__ int sc[SP_TCH];
     const int lane = threadIdx.x;
@@ -86,15 +88,15 @@ __global__ __launch_bounds__(64) void st_long_kernel(StLine q, const double *__r
         const int c = c0 + lane;
         double w = 0.0;
         op_fold_long_row(val, col, b0, len, sv, sc, lane, c < k, [&](double a, i64 j) { w = w + a * X[j + c * ldx]; });
-        if (c < k) B[i + c * ldb] = st_line(q, X[i + c * ldx], w, d, i, S ? S + i + c * lds : nullptr);
+        if (c < k) B[i + c * ldb] = st_line(q, X[i + c * ldx], w, d ? d + (PC ? c * ldd : 0) : nullptr, i, S ? S + i + c * lds : nullptr);
     }
 }
 
 // ---- θ < 1, Aᵀ: one lane per column of A over the CSC copy ------------------------------------------------------------------------------
-template <int KB>
+template <int KB, bool PC = false>
 __global__ __launch_bounds__(64) void st_cols_kernel(StLine q, const i64 *__restrict__ cp, const int *__restrict__ rv, const double *__restrict__ nz, i64 n,
                                                      const double *__restrict__ d, const double *__restrict__ X, i64 ldx, const double *__restrict__ S, i64 lds,
-                                                     double *__restrict__ B, i64 ldb) {
+                                                     double *__restrict__ B, i64 ldb, i64 ldd = 0) {
     __shared__ double sv[SP_TCH];
     __shared__ int sr[SP_TCH];
     const int lane = threadIdx.x;
@@ -110,15 +112,16 @@ __global__ __launch_bounds__(64) void st_cols_kernel(StLine q, const i64 *__rest
 #pragma unroll
     for (int c = 0; c < KB; ++c) {
         const double w = 0.0 + tmp[c];  // (the product's last step, y = +0.0 + tmp·1: a sum of -0.0 becomes +0.0)
-        B[colm + c * ldb] = st_line(q, X[colm + c * ldx], w, d, colm, S ? S + colm + c * lds : nullptr);
+        B[colm + c * ldb] = st_line(q, X[colm + c * ldx], w, d ? d + (PC ? c * ldd : 0) : nullptr, colm, S ? S + colm + c * lds : nullptr);
     }
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
 // B (n x k, leading dimension n) = the step's right-hand side from X, with the SELECTED slot's matrix
-static void st_rhs(otmb_op *op, int adjoint, i64 k, const StLine &q, const double *d, const double *X, i64 ldx, const double *S, i64 lds, double *B) {
+static void st_rhs(otmb_op *op, int adjoint, i64 k, const StLine &q, const SvD &dk, const double *X, i64 ldx, const double *S, i64 lds, double *B) {
     hipStream_t st = op->ctx->stream;
-    const i64 n = op->n;
+    const i64 n = op->n, ldd = dk.percol() ? dk.ld : 0;
+    const double *d = dk.p;
     if (q.theta == 1.0) {
         op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
             hipLaunchKernelGGL((st_stream_kernel<decltype(kb)::value>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, q.sigma, X + c0 * ldx, ldx,
@@ -127,17 +130,17 @@ static void st_rhs(otmb_op *op, int adjoint, i64 k, const StLine &q, const doubl
         return;
     }
     if (!adjoint && op->nlong > 0)
-        hipLaunchKernelGGL(st_long_kernel, dim3((unsigned)op->nlong), dim3(64), 0, st, q, (const double *)op->val.p, (const int *)op->col.p,
-                           (const i64 *)op->lrows.p, (const i64 *)op->loff.p, op->ell, (int)k, d, X, ldx, S, lds, B, n);
+        hipLaunchKernelGGL((ldd ? st_long_kernel<true> : st_long_kernel<false>), dim3((unsigned)op->nlong), dim3(64), 0, st, q, (const double *)op->val.p, (const int *)op->col.p,
+                           (const i64 *)op->lrows.p, (const i64 *)op->loff.p, op->ell, (int)k, d, X, ldx, S, lds, B, n, ldd);
     op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
         constexpr int KB = decltype(kb)::value;
-        const double *Sc = S ? S + c0 * lds : nullptr;
+        const double *Sc = S ? S + c0 * lds : nullptr, *dc = d ? d + c0 * ldd : nullptr;
         if (adjoint)
-            hipLaunchKernelGGL((st_cols_kernel<KB>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, q, (const i64 *)op->cp.p, (const int *)op->rv.p,
-                               (const double *)op->nz.p, n, d, X + c0 * ldx, ldx, Sc, lds, B + c0 * n, n);
+            hipLaunchKernelGGL((ldd ? st_cols_kernel<KB, true> : st_cols_kernel<KB, false>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, q, (const i64 *)op->cp.p, (const int *)op->rv.p,
+                               (const double *)op->nz.p, n, dc, X + c0 * ldx, ldx, Sc, lds, B + c0 * n, n, ldd);
         else
-            hipLaunchKernelGGL((st_rows_kernel<KB>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, q, (const double *)op->val.p, (const int *)op->col.p,
-                               (const i64 *)op->sbase.p, (const int *)op->elen.p, n, d, X + c0 * ldx, ldx, Sc, lds, B + c0 * n, n);
+            hipLaunchKernelGGL((ldd ? st_rows_kernel<KB, true> : st_rows_kernel<KB, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, q, (const double *)op->val.p, (const int *)op->col.p,
+                               (const i64 *)op->sbase.p, (const int *)op->elen.p, n, dc, X + c0 * ldx, ldx, Sc, lds, B + c0 * n, n, ldd);
     });
 }
 
@@ -150,7 +153,7 @@ struct StObs {  // what otmb_op_step_obs adds to a step call: q observers W (obs
     double *Xbar;
     i64 ldm;
 };
-static const StObs ST_PLAIN = {0, nullptr, 0, nullptr, nullptr, nullptr, 0};  // otmb_op_step: no observers, no mean
+static const StObs ST_PLAIN = {0, nullptr, 0, nullptr, nullptr, nullptr, 0};  // no observers, no mean
 
 static int32_t st_check(otmb_op *op, int64_t k, double dt, double theta, int64_t nsteps, int64_t first_slot, const double *S, int64_t lds, double *X,
                         int64_t ldx, double rtol, int64_t maxiter, int32_t precond, const int64_t *steps_done, const int64_t *iters, const double *relres,
@@ -165,7 +168,7 @@ static int32_t st_check(otmb_op *op, int64_t k, double dt, double theta, int64_t
 // The ONE loop behind otmb_op_step[_dev] (o = ST_PLAIN) and otmb_op_step_obs[_dev]: device pointers, the arguments checked.  After a step
 // whose solve left every column converged the observation pass reads X where the solve left it and its fold writes the step's q x k block
 // of o.obs; nothing of it waits for the host.
-static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot, const double *S,
+static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, double dt, double theta, int64_t nsteps, int64_t first_slot, const double *S,
                       int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters, double *relres,
                       int32_t *reason, const StObs &o) {
     int32_t rc;
@@ -185,12 +188,14 @@ static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const double *d, 
     const bool lines = precond == OTMB_PRECOND_LINES, watch = o.q > 0 || o.Xbar;
     const double tdt = theta * dt;
     const StLine q = {1.0 / tdt, theta, (1.0 - theta) / theta};
-    // op->st: B, then one preconditioner per slot the call visits
-    const i64 used = std::min(nsteps, nslots), per = lines ? 5 : 2;
-    if ((rc = otmb_reserve(ctx, op->st, ((size_t)(n * k) + (size_t)(used * per * n)) * 8))) return rc;
+    // op->st: B, then one preconditioner per slot the call visits (per column where every tracer has its own d)
+    const i64 used = std::min(nsteps, nslots), kc = sv_prec_cols(d, k);
+    const size_t per = sv_prec_doubles(n, lines, kc);
+    if ((double)n * (double)k + (double)used * (double)per >= 1.0e18) return otmb_fail(ctx, OTMB_ERR_ALLOC, "step: the workspace's size overflows");
+    if ((rc = otmb_reserve(ctx, op->st, ((size_t)(n * k) + (size_t)used * per) * 8))) return rc;
     if (watch && (rc = ob_reserve(op, k, o.q))) return rc;
     double *B = (double *)op->st.p, *pool = B + n * k;
-    std::vector<SvPrec> prec((size_t)nslots, SvPrec{nullptr, nullptr, nullptr, nullptr, nullptr});
+    std::vector<SvPrec> prec((size_t)nslots, SvPrec{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0});
     i64 taken = 0;
     struct Reselect {  // the caller's selection comes back on every return
         otmb_op *op;
@@ -206,7 +211,7 @@ static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const double *d, 
         };
         SvPrec &p = prec[(size_t)slot];
         if (!p.sh) {  // the slot's first visit
-            p = sv_prec_carve(pool + (taken++) * per * n, n, lines);
+            p = sv_prec_carve(pool + (size_t)(taken++) * per, n, lines, kc, d.percol());
             if ((rc = sv_prec_prepare(op, adjoint, precond, d, q.sigma, p))) return here(rc);
         }
         st_rhs(op, adjoint, k, q, d, X, ldx, S, lds, B);
@@ -222,7 +227,7 @@ static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const double *d, 
 }
 
 // The host variant of the loop: X, S, d, W staged once; X, the written rows of obs and Xbar come home once.
-static int32_t st_run_host(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
+static int32_t st_run_host(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, double dt, double theta, int64_t nsteps, int64_t first_slot,
                            const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
                            int64_t *iters, double *relres, int32_t *reason, const StObs &o) {
     int32_t rc;
@@ -231,8 +236,8 @@ static int32_t st_run_host(otmb_op *op, int32_t adjoint, int64_t k, const double
     if (nsteps == 0) return OTMB_OK;
     otmb_ctx *ctx = op->ctx;
     HIP_TRY(ctx, hipSetDevice(op->device));
-    double *dd;
-    if ((rc = op_reserve_xy(op, n, S ? n : 0, k)) || (rc = op_stage_d(op, d, dd))) return rc;
+    SvD dd;
+    if ((rc = op_reserve_xy(op, n, S ? n : 0, k)) || (rc = op_stage_dk(op, d.p, d.ld, k, dd.p, dd.ld))) return rc;
     double *dx = (double *)op->xs.p, *ds = S ? (double *)op->ys.p : nullptr;
     if (n > 0) {  // staged once, however many steps
         if ((rc = op_upload(ctx, dx, X, ldx, n, k))) return rc;
@@ -260,44 +265,61 @@ static int32_t st_run_host(otmb_op *op, int32_t adjoint, int64_t k, const double
 
 extern "C" {
 
-int32_t otmb_op_step_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
-                         const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
-                         int64_t *iters, double *relres, int32_t *reason) {
+int32_t otmb_op_step_dk_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t nsteps,
+                            int64_t first_slot, const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond,
+                            int64_t *steps_done, int64_t *iters, double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs,
+                            const double *tw, double *Xbar, int64_t ldm) {
     if (!op) return OTMB_ERR_INVALID_ARG;
+    const StObs o = {q, W, ldw, obs, tw, Xbar, ldm};
     int32_t rc;
-    if ((rc = st_check(op, k, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, ST_PLAIN))) return rc;
-    return st_run(op, adjoint, k, d, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, ST_PLAIN);
+    if ((rc = st_check(op, k, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o)) ||
+        (rc = sv_check_d(op, "otmb_op_step_dk", D, ldd)))
+        return rc;
+    return st_run(op, adjoint, k, SvD{D, ldd}, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o);
 }
 
-int32_t otmb_op_step(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
-                     const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
-                     int64_t *iters, double *relres, int32_t *reason) {
+int32_t otmb_op_step_dk(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t nsteps, int64_t first_slot,
+                        const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
+                        int64_t *iters, double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw,
+                        double *Xbar, int64_t ldm) {
     if (!op) return OTMB_ERR_INVALID_ARG;
+    const StObs o = {q, W, ldw, obs, tw, Xbar, ldm};
     int32_t rc;
-    if ((rc = st_check(op, k, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, ST_PLAIN))) return rc;
-    return st_run_host(op, adjoint, k, d, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, ST_PLAIN);
+    if ((rc = st_check(op, k, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o)) ||
+        (rc = sv_check_d(op, "otmb_op_step_dk", D, ldd)))
+        return rc;
+    return st_run_host(op, adjoint, k, SvD{D, ldd}, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o);
 }
 
+// the calls with one d for every tracer: ldd = 0 (otmb_op_step: no observers, no mean either)
 int32_t otmb_op_step_obs_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
                              const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
                              int64_t *iters, double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw,
                              double *Xbar, int64_t ldm) {
-    if (!op) return OTMB_ERR_INVALID_ARG;
-    const StObs o = {q, W, ldw, obs, tw, Xbar, ldm};
-    int32_t rc;
-    if ((rc = st_check(op, k, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o))) return rc;
-    return st_run(op, adjoint, k, d, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o);
+    return otmb_op_step_dk_dev(op, adjoint, k, d, 0, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, q,
+                               W, ldw, obs, tw, Xbar, ldm);
 }
 
 int32_t otmb_op_step_obs(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
                          const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
                          int64_t *iters, double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw,
                          double *Xbar, int64_t ldm) {
-    if (!op) return OTMB_ERR_INVALID_ARG;
-    const StObs o = {q, W, ldw, obs, tw, Xbar, ldm};
-    int32_t rc;
-    if ((rc = st_check(op, k, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o))) return rc;
-    return st_run_host(op, adjoint, k, d, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o);
+    return otmb_op_step_dk(op, adjoint, k, d, 0, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, q, W,
+                           ldw, obs, tw, Xbar, ldm);
+}
+
+int32_t otmb_op_step_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
+                         const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
+                         int64_t *iters, double *relres, int32_t *reason) {
+    return otmb_op_step_dk_dev(op, adjoint, k, d, 0, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, 0,
+                               nullptr, 0, nullptr, nullptr, nullptr, 0);
+}
+
+int32_t otmb_op_step(otmb_op *op, int32_t adjoint, int64_t k, const double *d, double dt, double theta, int64_t nsteps, int64_t first_slot,
+                     const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
+                     int64_t *iters, double *relres, int32_t *reason) {
+    return otmb_op_step_dk(op, adjoint, k, d, 0, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, 0,
+                           nullptr, 0, nullptr, nullptr, nullptr, 0);
 }
 
 }  // extern "C"

@@ -36,6 +36,11 @@ def _col_major(t, rows):
     return t, max(t.stride(1) if t.shape[1] > 1 else rows, rows, 1)
 
 
+def _per_column(d):
+    """d is a matrix: one column per tracer (the otmb_op_*_dk calls); n values, or None, are the calls with one d."""
+    return d is not None and getattr(d, "ndim", 1) == 2
+
+
 def _on_device(t, device, what):
     """A host tensor's pointer handed to a kernel would fault the device: refuse anything that is not on the operator's GPU."""
     if not torch.is_tensor(t) or not t.is_cuda or t.device.index != device:
@@ -150,6 +155,16 @@ class Operator:
         d = d.contiguous()
         return d, d.data_ptr()
 
+    def _dk_ptr(self, D, B, what):
+        """(D column-major, its leading dimension) of a per-column d for the otmb_op_*_dk_dev calls: a 2-D float64 device tensor of B's shape
+        (include/otmb.h states the contract: column c is the 1-D call with d[:, c])."""
+        _on_device(D, self.device, "d")
+        if B.dim() != 2:
+            raise capi.OtmbError(11, f"DimensionMismatch: d of {tuple(D.shape)} is per column, {what} of {tuple(B.shape)} has no columns")
+        if D.dtype != torch.float64 or tuple(D.shape) != tuple(B.shape):
+            raise capi.OtmbError(11, f"DimensionMismatch: d must be float64 of {what}'s shape {tuple(B.shape)}, not {tuple(D.shape)}")
+        return _col_major(D, self.shape[1])
+
     def _system(self, B, what, precond):
         """What solve (B) and precondition (Y) share: the operator is open, precond is known, the tensor is on the device and has the operator's
         rows.  Returns (precond's code, k, the tensor column-major, its leading dimension, a zeroed result of its shape, strides (1, max(m, 1)))."""
@@ -169,6 +184,11 @@ class Operator:
     def precondition(self, Y, d=None, sigma=0.0, adjoint=False, precond="lines"):
         """Z = P⁻¹·Y on device tensors (otmb_op_precond_dev; api.DeviceOperator.precondition).  Returns a new tensor of Y's shape."""
         pc, k, Yc, ldy, Z = self._system(Y, "Y", precond)
+        if _per_column(d):
+            Dc, ldd = self._dk_ptr(d, Y, "Y")
+            self.ctx.check(self.lib.otmb_op_precond_dk_dev(self._h, int(bool(adjoint)), pc, k, Dc.data_ptr(), ldd, float(sigma), Yc.data_ptr(), ldy,
+                                                           Z.data_ptr(), max(self.shape[0], 1)))
+            return Z
         d, dp = self._d_ptr(d)
         self.ctx.check(self.lib.otmb_op_precond_dev(self._h, int(bool(adjoint)), pc, k, dp, float(sigma), Yc.data_ptr(), ldy, Z.data_ptr(),
                                                     max(self.shape[0], 1)))
@@ -187,8 +207,16 @@ class Operator:
             if tuple(x0.shape) != tuple(B.shape):
                 raise capi.OtmbError(11, f"DimensionMismatch: x0 of {tuple(x0.shape)}, B of {tuple(B.shape)}")
             X.copy_(x0)
-        d, dp = self._d_ptr(d)
         iters, relres, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
+        if _per_column(d):
+            Dc, ldd = self._dk_ptr(d, B, "B")
+            rc = self.lib.otmb_op_solve_dk_dev(self._h, int(bool(adjoint)), k, Dc.data_ptr(), ldd, float(sigma), Bc.data_ptr(), ldb, X.data_ptr(),
+                                               max(self.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), iters.ctypes.data,
+                                               relres.ctypes.data, reason.ctypes.data, pc)
+            if rc != capi.NOT_CONVERGED:
+                self.ctx.check(rc)
+            return X, SolveInfo(rc, iters, relres, reason)
+        d, dp = self._d_ptr(d)
         rc = self.lib.otmb_op_solve_pc_dev(self._h, int(bool(adjoint)), k, dp, float(sigma), Bc.data_ptr(), ldb, X.data_ptr(), max(self.shape[0], 1),
                                            int(x0 is not None), float(rtol), int(maxiter), iters.ctypes.data, relres.ctypes.data,
                                            reason.ctypes.data, pc)
@@ -228,6 +256,9 @@ class Operator:
         returns (a new tensor with the state after the steps, an api.StepInfo).  Nothing but the solver's column records travels to the host."""
         from .api import StepInfo, step_arrays
 
+        if _per_column(d):
+            return self._step_obs(X, None, None, dt=dt, theta=theta, nsteps=nsteps, first_slot=first_slot, source=source, d=d, rtol=rtol, maxiter=maxiter,
+                                  adjoint=adjoint, precond=precond)
         pc, k, Xc, ldx, Xn = self._system(X, "X", precond)
         Xn.copy_(X)
         Sc, sp, lds = None, None, max(self.shape[0], 1)
@@ -263,7 +294,11 @@ class Operator:
                 raise capi.OtmbError(11, f"DimensionMismatch: source of {tuple(source.shape)}, X of {tuple(X.shape)}")
             Sc, lds = _col_major(source, n)
             sp = Sc.data_ptr()
-        d, dp = self._d_ptr(d)
+        Dc = None
+        if _per_column(d):
+            Dc, ldd = self._dk_ptr(d, X, "X")
+        else:
+            d, dp = self._d_ptr(d)
         q, Wc, ldw, obs, tw, mean = 0, None, max(n, 1), None, None, None
         if observe is not None:
             Wc, ldw, q = self._observers(observe)
@@ -274,6 +309,15 @@ class Operator:
                 torch.zeros(k * max(n, 1), dtype=torch.float64, device=X.device).as_strided((n, k), (1, max(n, 1)))
         iters, relres, reason = step_arrays(nsteps, k)
         done = C.c_int64(0)
+        if Dc is not None:  # every tracer has its own d: otmb_op_step_dk_dev, the same arguments with D and its leading dimension
+            rc = self.lib.otmb_op_step_dk_dev(self._h, int(bool(adjoint)), k, Dc.data_ptr(), ldd, float(dt), float(theta), int(nsteps), int(first_slot), sp,
+                                              lds, Xn.data_ptr(), max(n, 1), float(rtol), int(maxiter), pc, C.byref(done), iters.ctypes.data,
+                                              relres.ctypes.data, reason.ctypes.data, q, None if Wc is None else Wc.data_ptr(), ldw,
+                                              None if obs is None else obs.data_ptr(), None if tw is None else tw.ctypes.data,
+                                              None if mean is None else mean.data_ptr(), max(n, 1))
+            if rc != capi.NOT_CONVERGED:
+                self.ctx.check(rc)
+            return Xn, StepInfo(rc, done.value, nsteps, iters, relres, reason, obs, mean)
         rc = self.lib.otmb_op_step_obs_dev(self._h, int(bool(adjoint)), k, dp, float(dt), float(theta), int(nsteps), int(first_slot), sp, lds,
                                            Xn.data_ptr(), max(n, 1), float(rtol), int(maxiter), pc, C.byref(done), iters.ctypes.data,
                                            relres.ctypes.data, reason.ctypes.data, q, None if Wc is None else Wc.data_ptr(), ldw,
@@ -291,6 +335,9 @@ class Operator:
         round the host reads a few scalars a column; no vector travels."""
         from .api import PeriodicInfo
 
+        if _per_column(d):
+            return self._periodic_pc(source, capi.OUTERS["none"], dt=dt, ncycle=ncycle, theta=theta, first_slot=first_slot, d=d, x0=x0, rtol=rtol,
+                                     maxiter=maxiter, adjoint=adjoint, precond=precond, ptol=ptol, restart=restart, maxcycles=maxcycles)
         pc, k, Sc, lds, X = self._system(source, "source", precond)
         if x0 is not None:
             _on_device(x0, self.device, "x0")
@@ -317,9 +364,18 @@ class Operator:
             if tuple(x0.shape) != tuple(source.shape):
                 raise capi.OtmbError(11, f"DimensionMismatch: x0 of {tuple(x0.shape)}, source of {tuple(source.shape)}")
             X.copy_(x0)
-        d, dp = self._d_ptr(d)
         cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
         msolve = np.zeros(k, dtype=np.int64)
+        if _per_column(d):
+            Dc, ldd = self._dk_ptr(d, source, "source")
+            rc = self.lib.otmb_op_periodic_dk_dev(self._h, int(bool(adjoint)), k, Dc.data_ptr(), ldd, float(dt), float(theta), int(ncycle), int(first_slot),
+                                                  Sc.data_ptr(), lds, X.data_ptr(), max(self.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter),
+                                                  pc, float(ptol), int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data,
+                                                  reason.ctypes.data, int(outer), msolve.ctypes.data)
+            if rc != capi.NOT_CONVERGED:
+                self.ctx.check(rc)
+            return X, PeriodicInfo(rc, cycles, defect, reason, msolve)
+        d, dp = self._d_ptr(d)
         rc = self.lib.otmb_op_periodic_pc_dev(self._h, int(bool(adjoint)), k, dp, float(dt), float(theta), int(ncycle), int(first_slot), Sc.data_ptr(),
                                               lds, X.data_ptr(), max(self.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), pc, float(ptol),
                                               int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data, reason.ctypes.data, int(outer),
