@@ -18,6 +18,7 @@ import numpy as np
 from . import capi
 from ._nt import NT, data_and_props
 from .capi import HDIRS, MATS, PHI_ORDER
+from .operator_calls import OperatorCalls, PeriodicInfo, SolveInfo, StepInfo, observers, step_arrays, time_weights  # noqa: F401 (this module's names too)
 
 _ctx = {}
 _mgpu = {}
@@ -802,85 +803,6 @@ def _column_major(a):
     return a, max(ld, a.shape[0])
 
 
-class SolveInfo:
-    """What otmb_op_solve_pc reports, one entry per column of B: iterations (completed), relres (‖r‖₂/‖b‖₂ of the column's last residual
-    evaluation: the explicitly computed b - M·x when it stopped on one, the recursive residual otherwise), reason ("converged", "maxiter",
-    "breakdown", "nonfinite") and converged; status is the call's own (0, or capi.NOT_CONVERGED when some column is not converged)."""
-
-    def __init__(self, status, iterations, relres, reason):
-        self.status = int(status)
-        self.iterations = np.asarray(iterations, dtype=np.int64)
-        self.relres = np.asarray(relres, dtype=np.float64)
-        self.reason = tuple(capi.SOLVE_REASONS[int(r)] for r in reason)
-        self.converged = np.array([r == "converged" for r in self.reason], dtype=bool)
-
-    def __repr__(self):
-        return f"SolveInfo(status={self.status}, iterations={self.iterations.tolist()}, relres={self.relres.tolist()}, reason={self.reason})"
-
-
-class StepInfo:
-    """What otmb_op_step reports: status (0, or capi.NOT_CONVERGED), steps_done (steps completed with every column converged) and, one row
-    per step that ran a solve (steps 0 .. min(steps_done, nsteps - 1)) and one entry per column: iterations, relres, reason (tuples of
-    "converged", "maxiter", "breakdown", "nonfinite") and converged -- each as SolveInfo has them for one solve.  From
-    step(..., observe=W): observations, (steps_done, k, q), entry [t, c, j] = observer j of tracer c after step t (only the steps that were
-    completed); from step(..., time_weights=w): mean, n x k (n values for a 1-D state) = Σ_t w[t]·X_t over the completed steps, None when
-    no step was.  Both None otherwise."""
-
-    def __init__(self, status, steps_done, nsteps, iterations, relres, reason, observations=None, mean=None):
-        self.status, self.steps_done = int(status), int(steps_done)
-        self.observations = None if observations is None else observations[:self.steps_done]
-        self.mean = mean if self.steps_done > 0 else None
-        ran = min(self.steps_done + 1, int(nsteps))
-        self.iterations = np.asarray(iterations, dtype=np.int64)[:ran]
-        self.relres = np.asarray(relres, dtype=np.float64)[:ran]
-        self.reason = tuple(tuple(capi.SOLVE_REASONS[int(r)] for r in row) for row in np.asarray(reason)[:ran])
-        self.converged = np.array([[r == "converged" for r in row] for row in self.reason], dtype=bool).reshape(self.iterations.shape)
-
-    def __repr__(self):
-        return f"StepInfo(status={self.status}, steps_done={self.steps_done}, iterations={self.iterations.tolist()}, reason={self.reason})"
-
-
-def observers(W, n):
-    """(W as a 2-D array n x q, q) of step(..., observe=W) / observe(W, X): n values are one observer."""
-    shape = tuple(W.shape)
-    if len(shape) not in (1, 2) or shape[0] != n:
-        raise capi.OtmbError(11, f"DimensionMismatch: observers of {shape}, expected {n} rows")
-    return (W.reshape(n, 1) if len(shape) == 1 else W), (1 if len(shape) == 1 else shape[1])
-
-
-def time_weights(w, nsteps):
-    """The mean's weights as nsteps float64 host values."""
-    w = np.ascontiguousarray(w, dtype=np.float64)
-    if w.shape != (max(int(nsteps), 0),):
-        raise capi.OtmbError(11, f"DimensionMismatch: time_weights of {w.shape}, expected {(max(int(nsteps), 0),)}")
-    return w
-
-
-def step_arrays(nsteps, k):
-    """The three report arrays of otmb_op_step (nsteps x k, step-major)."""
-    shape = (max(int(nsteps), 0), int(k))
-    return np.zeros(shape, dtype=np.int64), np.zeros(shape, dtype=np.float64), np.zeros(shape, dtype=np.int32)
-
-
-class PeriodicInfo:
-    """What otmb_op_periodic reports, one entry per column: cycles (the step calls the column took part in, the verifying ones included),
-    defect (‖F(x) - x‖₂/‖g‖₂ of the column's last explicitly computed F(x) - x; NaN when none was), reason ("converged", "maxcycles",
-    "step_failed", "nonfinite", and with outer="mean" "precond_failed") and converged; msolve_iters: the BiCGStab iterations the column spent in
-    mean solves (outer="mean"; otherwise zero); status is the call's own (0, or capi.NOT_CONVERGED when some column is not converged)."""
-
-    def __init__(self, status, cycles, defect, reason, msolve_iters=None):
-        self.status = int(status)
-        self.cycles = np.asarray(cycles, dtype=np.int64)
-        self.defect = np.asarray(defect, dtype=np.float64)
-        self.reason = tuple(capi.PERIODIC_PC_REASONS[int(r)] for r in reason)
-        self.converged = np.array([r == "converged" for r in self.reason], dtype=bool)
-        self.msolve_iters = np.zeros(len(self.cycles), dtype=np.int64) if msolve_iters is None else np.asarray(msolve_iters, dtype=np.int64)
-
-    def __repr__(self):
-        return (f"PeriodicInfo(status={self.status}, cycles={self.cycles.tolist()}, defect={self.defect.tolist()}, reason={self.reason}, "
-                f"msolve_iters={self.msolve_iters.tolist()})")
-
-
 def vertical_lines(indices):
     """The `next` array of otmb_op_set_lines / DeviceOperator.set_lines for the water columns of a makeindices result (anything with
     Lwet3D: the wet rank of every cell, 0 = land): next[Lwet3D[i,j,k] - 1] = Lwet3D[i,j,k+1] when both cells are wet, 0 otherwise
@@ -894,7 +816,7 @@ def vertical_lines(indices):
     return nxt
 
 
-class DeviceOperator:
+class DeviceOperator(OperatorCalls):
     """A sparse operator resident on the device: Y = α·A·X + β·Y and Y = α·Aᵀ·X + β·Y, bit for bit SparseArrays' 5-argument mul! of
     Julia 1.10 -- what the reference's consumer checks compute (test/local_full.jl:96-107: norm(T * e1), norm(T' * v)) and what a tracer
     simulation steps with.  The contract (csrc/otmb_spmv.hip, tests/spmv_ref.py):
@@ -908,7 +830,8 @@ class DeviceOperator:
     The same C calls as the Julia shim's DeviceOperator: otmb_op_create; mul! -> otmb_op_mul; setvalues! -> otmb_op_set_values; solve! ->
     otmb_op_solve_pc; setlines! -> otmb_op_set_lines; precondition! -> otmb_op_precond; setslots! / selectslot! / step! -> otmb_op_set_slots /
     otmb_op_select_slot / otmb_op_step; observe / stepobserve! -> otmb_op_observe / otmb_op_step_obs; periodic! -> otmb_op_periodic (outer = :mean: otmb_op_periodic_pc); combineslots! ->
-    otmb_op_combine_slots; the finalizer -> otmb_op_destroy."""
+    otmb_op_combine_slots; the finalizer -> otmb_op_destroy.  precondition, solve, observe, step and periodic are OperatorCalls' (a matrix d:
+    the otmb_op_*_dk exports), over the numpy hooks below: a 1-D input gives a 1-D result, 2-D results are Fortran-ordered."""
 
     def __init__(self, A, *, device=0):
         self._h = C.c_void_p()
@@ -928,6 +851,25 @@ class DeviceOperator:
     def _live(self):
         if not self._h.value:
             raise ValueError("DeviceOperator is closed")
+
+    # OperatorCalls' arrays: numpy, the library looked up at call time
+    def _library(self):
+        return capi.lib()
+
+    def _array(self, a, what):
+        return np.atleast_1d(a) if what == "d" else np.asarray(a)  # (a scalar d is one value: the d of a 1 x 1 operator)
+
+    def _matrix(self, a, rows):
+        return _column_major(a)
+
+    def _ptr(self, a):
+        return None if a is None else a.ctypes.data
+
+    def _zeros(self, shape, order="F"):
+        return np.zeros(shape, dtype=np.float64, order=order)
+
+    def _assign(self, X, a):
+        X[...] = a
 
     def mul(self, X, *, alpha=1.0, beta=0.0, Y=None, adjoint=False):
         """α·A·X + β·Y (adjoint: α·Aᵀ·X + β·Y).  X: 1-D (one tracer) or 2-D (rows x k); Y: None (a new array; β must be 0) or an array of
@@ -1008,283 +950,6 @@ class DeviceOperator:
         if nx.shape != (self.shape[1],):
             raise capi.OtmbError(11, f"DimensionMismatch: next of {nx.shape}, expected {(self.shape[1],)}")
         self.ctx.check(lib.otmb_op_set_lines(self._h, nx.ctypes.data))
-
-    def _system_args(self, B, d):
-        """(k, B as column-major, its leading dimension, d as float64 or None) for the solver's entry points."""
-        m, n = self.shape
-        if B.ndim not in (1, 2) or B.shape[0] != m:
-            raise capi.OtmbError(11, f"DimensionMismatch: operator of {(m, n)}, B of {B.shape}")
-        k = 1 if B.ndim == 1 else B.shape[1]
-        Bc, ldb = _column_major(B)
-        dc = None
-        if d is not None:
-            dc = np.ascontiguousarray(d, dtype=np.float64)
-            if dc.shape != (n,):
-                raise capi.OtmbError(11, f"DimensionMismatch: d of {dc.shape}, expected {(n,)}")
-        return k, Bc, ldb, dc
-
-    def precondition(self, Y, d=None, sigma=0.0, adjoint=False, precond="lines"):
-        """Z = P⁻¹·Y with the preconditioner solve(..., precond=precond) uses for M = σ·I + diag(d) + A (adjoint: Aᵀ) (otmb_op_precond): for a
-        Krylov method of the caller's own.  Y: 1-D or 2-D (n x k); returns Z of Y's shape (2-D: Fortran-ordered)."""
-        self._live()
-        pc = capi.precond_code(precond)
-        Y = np.asarray(Y)
-        if np.ndim(d) == 2:
-            return self._precondition_dk(Y, d, sigma, adjoint, pc)
-        k, Yc, ldy, dc = self._system_args(Y, d)
-        Z = np.zeros(Y.shape, dtype=np.float64, order="F")
-        lib = capi.lib()
-        self.ctx.check(lib.otmb_op_precond(self._h, int(bool(adjoint)), pc, k, None if dc is None else dc.ctypes.data, float(sigma), Yc.ctypes.data,
-                                           ldy, Z.ctypes.data, max(Z.shape[0], 1)))
-        return Z
-
-    def solve(self, B, d=None, sigma=0.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False, precond="jacobi"):
-        """X with (σ·I + diag(d) + A)·X = B (adjoint: ... + Aᵀ) by preconditioned BiCGStab on the device (otmb_op_solve_pc, include/otmb.h:
-        the method, the stop rules, what is deterministic).  B: 1-D or 2-D (n x k); d: None (zero) or n values; x0: None (start from zero) or
-        an array of B's shape (not modified).  Returns (X, info): X of B's shape (2-D: Fortran-ordered), info a SolveInfo with one entry per
-        column.  A column that does not converge is REPORTED (info.converged, info.reason), not raised: X then holds its last iterate.
-        Argument errors and a zero or non-finite diagonal (SINGULAR_PRECONDITIONER) raise OtmbError.
-        precond = "jacobi" (default) | "lines": the preconditioner; "lines" is P = M on the lines of set_lines (the water columns'
-        tridiagonals: far fewer iterations on time-stepping systems) and needs set_lines first.  With "lines" only the pivots of
-        the line factorisation are checked, not the diagonal: a zero or non-finite diag(M) entry is then reported, if it makes a pivot
-        singular, as that pivot ("pivot[i] ...") -- also when next is all zero, where the results are Jacobi's but the message is not."""
-        self._live()
-        pc = capi.precond_code(precond)
-        B = np.asarray(B)
-        if np.ndim(d) == 2:
-            return self._solve_dk(B, d, sigma, rtol, maxiter, x0, adjoint, pc)
-        k, Bc, ldb, dc = self._system_args(B, d)
-        X = np.zeros(B.shape, dtype=np.float64, order="F")
-        if x0 is not None:
-            if np.shape(x0) != B.shape:
-                raise capi.OtmbError(11, f"DimensionMismatch: x0 of {np.shape(x0)}, B of {B.shape}")
-            X[...] = x0
-        iters, relres, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
-        lib = capi.lib()
-        rc = lib.otmb_op_solve_pc(self._h, int(bool(adjoint)), k, None if dc is None else dc.ctypes.data, float(sigma), Bc.ctypes.data, ldb,
-                                  X.ctypes.data, max(X.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), iters.ctypes.data,
-                                  relres.ctypes.data, reason.ctypes.data, pc)
-        if rc != capi.NOT_CONVERGED:
-            self.ctx.check(rc)
-        return X, SolveInfo(rc, iters, relres, reason)
-
-    def observe(self, W, X):
-        """Wᵀ·X on the device (otmb_op_observe; include/otmb.h states the order of the sums): W n x q (or n values: one observer), X n x k or
-        1-D.  Returns an array (q, k), or (q,) for 1-D X: inventories (W = the cell volumes), stations, regional means of a state."""
-        self._live()
-        n = self.shape[1]
-        X = np.asarray(X)
-        if X.ndim not in (1, 2) or X.shape[0] != n:
-            raise capi.OtmbError(11, f"DimensionMismatch: operator of {self.shape}, X of {X.shape}")
-        W, q = observers(np.asarray(W), n)
-        k = 1 if X.ndim == 1 else X.shape[1]
-        Xc, ldx = _column_major(X)
-        Wc, ldw = _column_major(W)
-        obs = np.zeros((q, k), dtype=np.float64, order="F")
-        self.ctx.check(capi.lib().otmb_op_observe(self._h, k, q, Wc.ctypes.data, ldw, Xc.ctypes.data, ldx, obs.ctypes.data))
-        return obs[:, 0] if X.ndim == 1 else obs
-
-    @capi.observe_keywords
-    def step(self, X, *, dt, theta=1.0, nsteps=1, first_slot=0, source=None, d=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi"):
-        """nsteps θ-steps of ∂x/∂t + (diag(d) + A)·x = source from the state X, step t with the matrix of slot (first_slot + t) mod nslots
-        (otmb_op_step; include/otmb.h states the contract: σ = 1 / (theta·dt), the right-hand side, then solve(..., x0 = the state)).  X: 1-D
-        or 2-D (n x k), not modified; source: None (zero) or an array of X's shape; d: None or n values.  Returns (X after the steps, info):
-        info a StepInfo.  A step that does not converge ends the call and is REPORTED as solve reports it (info.status, info.steps_done,
-        info.reason; X then holds that step's last iterates), not raised; argument errors and a singular preconditioner raise OtmbError.
-        d of X's 2-D shape: every tracer has its own d (otmb_op_step_dk), and column c is the 1-D call with d[:, c]."""
-        self._live()
-        pc = capi.precond_code(precond)
-        X0 = np.asarray(X)
-        if np.ndim(d) == 2:
-            return self._step_dk(X0, None, None, dt, theta, nsteps, first_slot, source, d, rtol, maxiter, adjoint, pc)
-        k, _, _, dc = self._system_args(X0, d)
-        Xn = np.array(X0, dtype=np.float64, order="F")
-        Sc, lds = None, max(Xn.shape[0], 1)
-        if source is not None:
-            if np.shape(source) != X0.shape:
-                raise capi.OtmbError(11, f"DimensionMismatch: source of {np.shape(source)}, X of {X0.shape}")
-            Sc, lds = _column_major(np.asarray(source))
-        iters, relres, reason = step_arrays(nsteps, k)
-        done = C.c_int64(0)
-        lib = capi.lib()
-        rc = lib.otmb_op_step(self._h, int(bool(adjoint)), k, None if dc is None else dc.ctypes.data, float(dt), float(theta), int(nsteps),
-                              int(first_slot), None if Sc is None else Sc.ctypes.data, lds, Xn.ctypes.data, max(Xn.shape[0], 1), float(rtol),
-                              int(maxiter), pc, C.byref(done), iters.ctypes.data, relres.ctypes.data, reason.ctypes.data)
-        if rc != capi.NOT_CONVERGED:
-            self.ctx.check(rc)
-        return Xn, StepInfo(rc, done.value, nsteps, iters, relres, reason)
-
-    def _step_obs(self, X, observe, weights, *, dt, theta=1.0, nsteps=1, first_slot=0, source=None, d=None, rtol=1e-10, maxiter=10000, adjoint=False,
-                  precond="jacobi"):
-        """step with observers and / or the mean's weights: otmb_op_step_obs (capi.observe_keywords states the keywords)."""
-        self._live()
-        pc = capi.precond_code(precond)
-        X0 = np.asarray(X)
-        if np.ndim(d) == 2:
-            return self._step_dk(X0, observe, weights, dt, theta, nsteps, first_slot, source, d, rtol, maxiter, adjoint, pc)
-        k, _, _, dc = self._system_args(X0, d)
-        n = self.shape[1]
-        Xn = np.array(X0, dtype=np.float64, order="F")
-        Sc, lds = None, max(Xn.shape[0], 1)
-        if source is not None:
-            if np.shape(source) != X0.shape:
-                raise capi.OtmbError(11, f"DimensionMismatch: source of {np.shape(source)}, X of {X0.shape}")
-            Sc, lds = _column_major(np.asarray(source))
-        q, Wc, ldw, obs, tw, mean = 0, None, max(n, 1), None, None, None
-        if observe is not None:
-            W, q = observers(np.asarray(observe), n)
-            Wc, ldw = _column_major(W)
-            obs = np.zeros((max(int(nsteps), 0), k, q), dtype=np.float64)
-        if weights is not None:
-            tw = time_weights(weights, nsteps)
-            mean = np.zeros(Xn.shape, dtype=np.float64, order="F")
-        iters, relres, reason = step_arrays(nsteps, k)
-        done = C.c_int64(0)
-        lib = capi.lib()
-        rc = lib.otmb_op_step_obs(self._h, int(bool(adjoint)), k, None if dc is None else dc.ctypes.data, float(dt), float(theta), int(nsteps),
-                                  int(first_slot), None if Sc is None else Sc.ctypes.data, lds, Xn.ctypes.data, max(Xn.shape[0], 1), float(rtol),
-                                  int(maxiter), pc, C.byref(done), iters.ctypes.data, relres.ctypes.data, reason.ctypes.data, q,
-                                  None if Wc is None else Wc.ctypes.data, ldw, None if obs is None else obs.ctypes.data,
-                                  None if tw is None else tw.ctypes.data, None if mean is None else mean.ctypes.data, max(n, 1))
-        if rc != capi.NOT_CONVERGED:
-            self.ctx.check(rc)
-        return Xn, StepInfo(rc, done.value, nsteps, iters, relres, reason, obs, mean)
-
-    @capi.outer_keyword
-    def periodic(self, source, *, dt, ncycle, theta=1.0, first_slot=0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi",
-                 ptol=1e-8, restart=30, maxcycles=1000):
-        """The periodic state of the stepped cycle: X with F(X) = X, F = step(..., nsteps=ncycle, first_slot=first_slot, source=source), by
-        restarted GMRES(restart) on the cycle map (otmb_op_periodic; include/otmb.h states the method and what is deterministic).  source:
-        1-D or 2-D (n x k); x0: None (start from zero) or an array of source's shape (not modified); the other arguments are step's.  Returns
-        (X, info): X the state at the start of the cycle, with ‖F(X) - X‖₂ <= ptol·‖F(0)‖₂ per converged column, info a PeriodicInfo.  A
-        column that does not converge is REPORTED (info.reason), not raised; argument errors and a singular preconditioner raise OtmbError.
-        outer="mean" (outer_keyword): the outer GMRES is preconditioned by the cycle-mean operator -- fewer cycles, one solve with the mean
-        matrix per iteration (info.msolve_iters).  d of source's 2-D shape: every column has its own d (otmb_op_periodic_dk)."""
-        self._live()
-        pc = capi.precond_code(precond)
-        S = np.asarray(source)
-        if np.ndim(d) == 2:
-            return self._periodic_dk(S, capi.OUTERS["none"], dt, ncycle, theta, first_slot, d, x0, rtol, maxiter, adjoint, pc, ptol, restart, maxcycles)
-        k, Sc, lds, dc = self._system_args(S, d)
-        X = np.zeros(S.shape, dtype=np.float64, order="F")
-        if x0 is not None:
-            if np.shape(x0) != S.shape:
-                raise capi.OtmbError(11, f"DimensionMismatch: x0 of {np.shape(x0)}, source of {S.shape}")
-            X[...] = x0
-        cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
-        lib = capi.lib()
-        rc = lib.otmb_op_periodic(self._h, int(bool(adjoint)), k, None if dc is None else dc.ctypes.data, float(dt), float(theta), int(ncycle),
-                                  int(first_slot), Sc.ctypes.data, lds, X.ctypes.data, max(X.shape[0], 1), int(x0 is not None), float(rtol),
-                                  int(maxiter), pc, float(ptol), int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data,
-                                  reason.ctypes.data)
-        if rc != capi.NOT_CONVERGED:
-            self.ctx.check(rc)
-        return X, PeriodicInfo(rc, cycles, defect, reason)
-
-    def _periodic_pc(self, source, outer, *, dt, ncycle, theta=1.0, first_slot=0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False,
-                     precond="jacobi", ptol=1e-8, restart=30, maxcycles=1000):
-        """periodic with outer = an otmb_outer code: otmb_op_periodic_pc."""
-        self._live()
-        pc = capi.precond_code(precond)
-        S = np.asarray(source)
-        if np.ndim(d) == 2:
-            return self._periodic_dk(S, outer, dt, ncycle, theta, first_slot, d, x0, rtol, maxiter, adjoint, pc, ptol, restart, maxcycles)
-        k, Sc, lds, dc = self._system_args(S, d)
-        X = np.zeros(S.shape, dtype=np.float64, order="F")
-        if x0 is not None:
-            if np.shape(x0) != S.shape:
-                raise capi.OtmbError(11, f"DimensionMismatch: x0 of {np.shape(x0)}, source of {S.shape}")
-            X[...] = x0
-        cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
-        msolve = np.zeros(k, dtype=np.int64)
-        lib = capi.lib()
-        rc = lib.otmb_op_periodic_pc(self._h, int(bool(adjoint)), k, None if dc is None else dc.ctypes.data, float(dt), float(theta), int(ncycle),
-                                     int(first_slot), Sc.ctypes.data, lds, X.ctypes.data, max(X.shape[0], 1), int(x0 is not None), float(rtol),
-                                     int(maxiter), pc, float(ptol), int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data,
-                                     reason.ctypes.data, int(outer), msolve.ctypes.data)
-        if rc != capi.NOT_CONVERGED:
-            self.ctx.check(rc)
-        return X, PeriodicInfo(rc, cycles, defect, reason, msolve)
-
-    # ---- per-column d: a 2-D d of B's / X's / source's shape goes to the otmb_op_*_dk exports (include/otmb.h states the contract: column c
-    # is the 1-D call with d[:, c], bit for bit).  A 1-D d never comes here: it keeps the calls above.
-    def _dk_args(self, B, d, what):
-        """(k, B as column-major, its leading dimension, D as float64 column-major n x k, its leading dimension)."""
-        D = np.asarray(d)
-        if B.ndim != 2:
-            raise capi.OtmbError(11, f"DimensionMismatch: d of {D.shape} is per column, {what} of {B.shape} has no columns")
-        k, Bc, ldb, _ = self._system_args(B, None)
-        if D.shape != B.shape:
-            raise capi.OtmbError(11, f"DimensionMismatch: d of {D.shape}, {what} of {B.shape}")
-        Dc, ldd = _column_major(np.asarray(D, dtype=np.float64))
-        return k, Bc, ldb, Dc, ldd
-
-    def _precondition_dk(self, Y, d, sigma, adjoint, pc):
-        k, Yc, ldy, Dc, ldd = self._dk_args(Y, d, "Y")
-        Z = np.zeros(Y.shape, dtype=np.float64, order="F")
-        self.ctx.check(capi.lib().otmb_op_precond_dk(self._h, int(bool(adjoint)), pc, k, Dc.ctypes.data, ldd, float(sigma), Yc.ctypes.data, ldy,
-                                                     Z.ctypes.data, max(Z.shape[0], 1)))
-        return Z
-
-    def _solve_dk(self, B, d, sigma, rtol, maxiter, x0, adjoint, pc):
-        k, Bc, ldb, Dc, ldd = self._dk_args(B, d, "B")
-        X = np.zeros(B.shape, dtype=np.float64, order="F")
-        if x0 is not None:
-            if np.shape(x0) != B.shape:
-                raise capi.OtmbError(11, f"DimensionMismatch: x0 of {np.shape(x0)}, B of {B.shape}")
-            X[...] = x0
-        iters, relres, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
-        rc = capi.lib().otmb_op_solve_dk(self._h, int(bool(adjoint)), k, Dc.ctypes.data, ldd, float(sigma), Bc.ctypes.data, ldb, X.ctypes.data,
-                                         max(X.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), iters.ctypes.data, relres.ctypes.data,
-                                         reason.ctypes.data, pc)
-        if rc != capi.NOT_CONVERGED:
-            self.ctx.check(rc)
-        return X, SolveInfo(rc, iters, relres, reason)
-
-    def _step_dk(self, X0, observe, weights, dt, theta, nsteps, first_slot, source, d, rtol, maxiter, adjoint, pc):
-        k, _, _, Dc, ldd = self._dk_args(X0, d, "X")
-        n = self.shape[1]
-        Xn = np.array(X0, dtype=np.float64, order="F")
-        Sc, lds = None, max(n, 1)
-        if source is not None:
-            if np.shape(source) != X0.shape:
-                raise capi.OtmbError(11, f"DimensionMismatch: source of {np.shape(source)}, X of {X0.shape}")
-            Sc, lds = _column_major(np.asarray(source))
-        q, Wc, ldw, obs, tw, mean = 0, None, max(n, 1), None, None, None
-        if observe is not None:
-            W, q = observers(np.asarray(observe), n)
-            Wc, ldw = _column_major(W)
-            obs = np.zeros((max(int(nsteps), 0), k, q), dtype=np.float64)
-        if weights is not None:
-            tw = time_weights(weights, nsteps)
-            mean = np.zeros(Xn.shape, dtype=np.float64, order="F")
-        iters, relres, reason = step_arrays(nsteps, k)
-        done = C.c_int64(0)
-        rc = capi.lib().otmb_op_step_dk(self._h, int(bool(adjoint)), k, Dc.ctypes.data, ldd, float(dt), float(theta), int(nsteps), int(first_slot),
-                                        None if Sc is None else Sc.ctypes.data, lds, Xn.ctypes.data, max(n, 1), float(rtol), int(maxiter), pc,
-                                        C.byref(done), iters.ctypes.data, relres.ctypes.data, reason.ctypes.data, q,
-                                        None if Wc is None else Wc.ctypes.data, ldw, None if obs is None else obs.ctypes.data,
-                                        None if tw is None else tw.ctypes.data, None if mean is None else mean.ctypes.data, max(n, 1))
-        if rc != capi.NOT_CONVERGED:
-            self.ctx.check(rc)
-        return Xn, StepInfo(rc, done.value, nsteps, iters, relres, reason, obs, mean)
-
-    def _periodic_dk(self, S, outer, dt, ncycle, theta, first_slot, d, x0, rtol, maxiter, adjoint, pc, ptol, restart, maxcycles):
-        k, Sc, lds, Dc, ldd = self._dk_args(S, d, "source")
-        X = np.zeros(S.shape, dtype=np.float64, order="F")
-        if x0 is not None:
-            if np.shape(x0) != S.shape:
-                raise capi.OtmbError(11, f"DimensionMismatch: x0 of {np.shape(x0)}, source of {S.shape}")
-            X[...] = x0
-        cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
-        msolve = np.zeros(k, dtype=np.int64)
-        rc = capi.lib().otmb_op_periodic_dk(self._h, int(bool(adjoint)), k, Dc.ctypes.data, ldd, float(dt), float(theta), int(ncycle), int(first_slot),
-                                            Sc.ctypes.data, lds, X.ctypes.data, max(X.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), pc,
-                                            float(ptol), int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data, reason.ctypes.data,
-                                            int(outer), msolve.ctypes.data)
-        if rc != capi.NOT_CONVERGED:
-            self.ctx.check(rc)
-        return X, PeriodicInfo(rc, cycles, defect, reason, msolve)
 
     def __matmul__(self, x):
         return self.mul(x)

@@ -1,6 +1,5 @@
 """ctypes binding of include/otmb.h (libotmb_hip.so).  No fallback: a missing library raises."""
 import ctypes as C
-import functools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -56,30 +55,6 @@ def outer_code(outer):
     if outer not in OUTERS:
         raise OtmbError(11, f"invalid argument: outer must be one of {sorted(OUTERS)}, not {outer!r}")
     return OUTERS[outer]
-
-
-def outer_keyword(plain):
-    """periodic(..., outer="none" | "mean") over a periodic method `plain` that makes the unpreconditioned call (otmb_op_periodic[_dev]):
-    "none" is that call as it stands; "mean" goes to the object's _periodic_pc (otmb_op_periodic_pc[_dev] with OTMB_OUTER_MEAN: flexible
-    GMRES preconditioned by the cycle-mean operator; include/otmb.h states the method).  info.msolve_iters is filled either way."""
-    @functools.wraps(plain)
-    def periodic(self, source, *, outer="none", **kw):
-        code = outer_code(outer)
-        return plain(self, source, **kw) if code == OUTERS["none"] else self._periodic_pc(source, code, **kw)
-
-    return periodic
-
-
-def observe_keywords(plain):
-    """step(..., observe=None, time_weights=None) over a step method `plain` that makes the plain call (otmb_op_step[_dev]): with neither
-    keyword it is that call as it stands (info.observations and info.mean are None); with either it goes to the object's _step_obs
-    (otmb_op_step_obs[_dev]; include/otmb.h states the order of the sums and the mean's fold).  observe: W, n x q (or n values: one
-    observer) -> info.observations, (steps_done, k, q); time_weights: nsteps finite values -> info.mean = Σ_t time_weights[t]·X_t, n x k."""
-    @functools.wraps(plain)
-    def step(self, X, *, observe=None, time_weights=None, **kw):
-        return plain(self, X, **kw) if observe is None and time_weights is None else self._step_obs(X, observe, time_weights, **kw)
-
-    return step
 
 
 class Csc(C.Structure):

@@ -13,6 +13,7 @@ import torch
 
 from . import capi
 from .capi import HDIRS, MATS, PHI_ORDER
+from .operator_calls import OperatorCalls
 
 # the library reads OTMB_KEPT_HTAB once per process (the first kept fill): what it will find, for accounting before that fill
 _KEPT_HTAB_ON = os.environ.get("OTMB_KEPT_HTAB", "1")[:1] != "0"
@@ -36,11 +37,6 @@ def _col_major(t, rows):
     return t, max(t.stride(1) if t.shape[1] > 1 else rows, rows, 1)
 
 
-def _per_column(d):
-    """d is a matrix: one column per tracer (the otmb_op_*_dk calls); n values, or None, are the calls with one d."""
-    return d is not None and getattr(d, "ndim", 1) == 2
-
-
 def _on_device(t, device, what):
     """A host tensor's pointer handed to a kernel would fault the device: refuse anything that is not on the operator's GPU."""
     if not torch.is_tensor(t) or not t.is_cuda or t.device.index != device:
@@ -48,10 +44,14 @@ def _on_device(t, device, what):
         raise ValueError(f"{what} must be a tensor on cuda:{device} (got {where})")
 
 
-class Operator:
+class Operator(OperatorCalls):
     """A resident sparse operator over device CSC arrays (otmb_op_create_dev): Y = α·A·X + β·Y and α·Aᵀ·X + β·Y on torch tensors, bit for
     bit SparseArrays' 5-argument mul! (api.DeviceOperator states the contract).  The operator owns device copies of the matrix;
-    set_values_dev refreshes the values for the same pattern.  DeviceAssembler.operator() hands these out over its resident results."""
+    set_values_dev refreshes the values for the same pattern.  DeviceAssembler.operator() hands these out over its resident results.
+    precondition, solve, observe, step and periodic are OperatorCalls' over the tensor hooks below (the `_dev` exports): a column-major
+    tensor, or a row slice of one, is passed uncopied with its parent's leading dimension; results are new tensors."""
+
+    _suffix = "_dev"
 
     def __init__(self, ctx, m, n, colptr, rowval, nzval):
         self.ctx, self.lib = ctx, capi.lib()
@@ -68,6 +68,39 @@ class Operator:
     @property
     def handle(self):
         return self._h
+
+    # OperatorCalls' arrays: float64 tensors on this operator's GPU
+    def _live(self):
+        if not self._h.value:
+            raise ValueError("operator is closed")
+
+    def _library(self):
+        return self.lib
+
+    def _array(self, a, what):
+        _on_device(a, self.device, what)
+        return a
+
+    def _matrix(self, a, rows):
+        return _col_major(a, rows)
+
+    def _ptr(self, a):
+        return None if a is None else a.data_ptr()
+
+    def _zeros(self, shape, order="F"):
+        dev = torch.device("cuda", self.device)
+        if order == "C" or len(shape) == 1:
+            return torch.zeros(shape, dtype=torch.float64, device=dev)
+        rows, k = shape
+        return torch.zeros(k * max(rows, 1), dtype=torch.float64, device=dev).as_strided((rows, k), (1, max(rows, 1)))
+
+    def _assign(self, X, a):
+        X.copy_(a)
+
+    def _check_d(self, d, want, what):
+        if d.dtype != torch.float64 or tuple(d.shape) != want:
+            raise capi.OtmbError(11, "DimensionMismatch: d must be " + (f"{want[0]} float64 values" if len(want) == 1 else
+                                                                       f"float64 of {what}'s shape {want}, not {tuple(d.shape)}"))
 
     def set_values_dev(self, nzval, slot=None):
         """New values from a device tensor for the selected slot, or for slot `slot` (set_slots)."""
@@ -145,244 +178,6 @@ class Operator:
             raise capi.OtmbError(11, f"DimensionMismatch: next must be {self.shape[1]} int64 values")
         next = next.contiguous()
         self.ctx.check(self.lib.otmb_op_set_lines_dev(self._h, next.data_ptr()))
-
-    def _d_ptr(self, d):
-        if d is None:
-            return None, None
-        _on_device(d, self.device, "d")
-        if d.dtype != torch.float64 or tuple(d.shape) != (self.shape[1],):
-            raise capi.OtmbError(11, f"DimensionMismatch: d must be {self.shape[1]} float64 values")
-        d = d.contiguous()
-        return d, d.data_ptr()
-
-    def _dk_ptr(self, D, B, what):
-        """(D column-major, its leading dimension) of a per-column d for the otmb_op_*_dk_dev calls: a 2-D float64 device tensor of B's shape
-        (include/otmb.h states the contract: column c is the 1-D call with d[:, c])."""
-        _on_device(D, self.device, "d")
-        if B.dim() != 2:
-            raise capi.OtmbError(11, f"DimensionMismatch: d of {tuple(D.shape)} is per column, {what} of {tuple(B.shape)} has no columns")
-        if D.dtype != torch.float64 or tuple(D.shape) != tuple(B.shape):
-            raise capi.OtmbError(11, f"DimensionMismatch: d must be float64 of {what}'s shape {tuple(B.shape)}, not {tuple(D.shape)}")
-        return _col_major(D, self.shape[1])
-
-    def _system(self, B, what, precond):
-        """What solve (B) and precondition (Y) share: the operator is open, precond is known, the tensor is on the device and has the operator's
-        rows.  Returns (precond's code, k, the tensor column-major, its leading dimension, a zeroed result of its shape, strides (1, max(m, 1)))."""
-        if not self._h.value:
-            raise ValueError("operator is closed")
-        pc = capi.precond_code(precond)
-        _on_device(B, self.device, what)
-        m, n = self.shape
-        if B.dim() not in (1, 2) or B.shape[0] != m:
-            raise capi.OtmbError(11, f"DimensionMismatch: operator of {(m, n)}, {what} of {tuple(B.shape)}")
-        k = 1 if B.dim() == 1 else B.shape[1]
-        Bc, ldb = _col_major(B, m)
-        X = torch.zeros(m, dtype=torch.float64, device=B.device) if B.dim() == 1 else \
-            torch.zeros(k * max(m, 1), dtype=torch.float64, device=B.device).as_strided((m, k), (1, max(m, 1)))
-        return pc, k, Bc, ldb, X
-
-    def precondition(self, Y, d=None, sigma=0.0, adjoint=False, precond="lines"):
-        """Z = P⁻¹·Y on device tensors (otmb_op_precond_dev; api.DeviceOperator.precondition).  Returns a new tensor of Y's shape."""
-        pc, k, Yc, ldy, Z = self._system(Y, "Y", precond)
-        if _per_column(d):
-            Dc, ldd = self._dk_ptr(d, Y, "Y")
-            self.ctx.check(self.lib.otmb_op_precond_dk_dev(self._h, int(bool(adjoint)), pc, k, Dc.data_ptr(), ldd, float(sigma), Yc.data_ptr(), ldy,
-                                                           Z.data_ptr(), max(self.shape[0], 1)))
-            return Z
-        d, dp = self._d_ptr(d)
-        self.ctx.check(self.lib.otmb_op_precond_dev(self._h, int(bool(adjoint)), pc, k, dp, float(sigma), Yc.data_ptr(), ldy, Z.data_ptr(),
-                                                    max(self.shape[0], 1)))
-        return Z
-
-    def solve(self, B, d=None, sigma=0.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False, precond="jacobi"):
-        """X with (σ·I + diag(d) + A)·X = B (adjoint: ... + Aᵀ) on device tensors (otmb_op_solve_pc_dev; api.DeviceOperator.solve states the
-        contract).  B: 1-D or 2-D (n x k, column-major) float64 device tensor; d: None or a device tensor of n values; x0: None or a tensor of
-        B's shape (not modified); precond: "jacobi" or "lines" (set_lines first).  Returns (X, info): X a new device tensor, info an
-        api.SolveInfo (the call waits for the device to read it)."""
-        from .api import SolveInfo
-
-        pc, k, Bc, ldb, X = self._system(B, "B", precond)
-        if x0 is not None:
-            _on_device(x0, self.device, "x0")
-            if tuple(x0.shape) != tuple(B.shape):
-                raise capi.OtmbError(11, f"DimensionMismatch: x0 of {tuple(x0.shape)}, B of {tuple(B.shape)}")
-            X.copy_(x0)
-        iters, relres, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
-        if _per_column(d):
-            Dc, ldd = self._dk_ptr(d, B, "B")
-            rc = self.lib.otmb_op_solve_dk_dev(self._h, int(bool(adjoint)), k, Dc.data_ptr(), ldd, float(sigma), Bc.data_ptr(), ldb, X.data_ptr(),
-                                               max(self.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), iters.ctypes.data,
-                                               relres.ctypes.data, reason.ctypes.data, pc)
-            if rc != capi.NOT_CONVERGED:
-                self.ctx.check(rc)
-            return X, SolveInfo(rc, iters, relres, reason)
-        d, dp = self._d_ptr(d)
-        rc = self.lib.otmb_op_solve_pc_dev(self._h, int(bool(adjoint)), k, dp, float(sigma), Bc.data_ptr(), ldb, X.data_ptr(), max(self.shape[0], 1),
-                                           int(x0 is not None), float(rtol), int(maxiter), iters.ctypes.data, relres.ctypes.data,
-                                           reason.ctypes.data, pc)
-        if rc != capi.NOT_CONVERGED:
-            self.ctx.check(rc)
-        return X, SolveInfo(rc, iters, relres, reason)
-
-    def _observers(self, W):
-        """(W column-major, its leading dimension, q) of a device tensor n x q, or of n values: one observer."""
-        from .api import observers
-
-        _on_device(W, self.device, "observe")
-        n = self.shape[1]
-        W, q = observers(W, n)
-        Wc, ldw = _col_major(W, n)
-        return Wc, ldw, q
-
-    def observe(self, W, X):
-        """Wᵀ·X on device tensors (otmb_op_observe_dev; api.DeviceOperator.observe): a new tensor (q, k), or (q,) for 1-D X, enqueued on
-        the context's stream.  Nothing travels to the host."""
-        if not self._h.value:
-            raise ValueError("operator is closed")
-        _on_device(X, self.device, "X")
-        n = self.shape[1]
-        if X.dim() not in (1, 2) or X.shape[0] != n:
-            raise capi.OtmbError(11, f"DimensionMismatch: operator of {self.shape}, X of {tuple(X.shape)}")
-        k = 1 if X.dim() == 1 else X.shape[1]
-        Xc, ldx = _col_major(X, n)
-        Wc, ldw, q = self._observers(W)
-        obs = torch.zeros((k, q), dtype=torch.float64, device=X.device).t()  # column-major (q, k)
-        self.ctx.check(self.lib.otmb_op_observe_dev(self._h, k, q, Wc.data_ptr(), ldw, Xc.data_ptr(), ldx, obs.data_ptr()))
-        return obs[:, 0] if X.dim() == 1 else obs
-
-    @capi.observe_keywords
-    def step(self, X, *, dt, theta=1.0, nsteps=1, first_slot=0, source=None, d=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi"):
-        """nsteps θ-steps over the slots on device tensors (otmb_op_step_dev; api.DeviceOperator.step states the arguments).  X is not modified;
-        returns (a new tensor with the state after the steps, an api.StepInfo).  Nothing but the solver's column records travels to the host."""
-        from .api import StepInfo, step_arrays
-
-        if _per_column(d):
-            return self._step_obs(X, None, None, dt=dt, theta=theta, nsteps=nsteps, first_slot=first_slot, source=source, d=d, rtol=rtol, maxiter=maxiter,
-                                  adjoint=adjoint, precond=precond)
-        pc, k, Xc, ldx, Xn = self._system(X, "X", precond)
-        Xn.copy_(X)
-        Sc, sp, lds = None, None, max(self.shape[0], 1)
-        if source is not None:
-            _on_device(source, self.device, "source")
-            if tuple(source.shape) != tuple(X.shape):
-                raise capi.OtmbError(11, f"DimensionMismatch: source of {tuple(source.shape)}, X of {tuple(X.shape)}")
-            Sc, lds = _col_major(source, self.shape[0])
-            sp = Sc.data_ptr()
-        d, dp = self._d_ptr(d)
-        iters, relres, reason = step_arrays(nsteps, k)
-        done = C.c_int64(0)
-        rc = self.lib.otmb_op_step_dev(self._h, int(bool(adjoint)), k, dp, float(dt), float(theta), int(nsteps), int(first_slot), sp, lds,
-                                       Xn.data_ptr(), max(self.shape[0], 1), float(rtol), int(maxiter), pc, C.byref(done), iters.ctypes.data,
-                                       relres.ctypes.data, reason.ctypes.data)
-        if rc != capi.NOT_CONVERGED:
-            self.ctx.check(rc)
-        return Xn, StepInfo(rc, done.value, nsteps, iters, relres, reason)
-
-    def _step_obs(self, X, observe, weights, *, dt, theta=1.0, nsteps=1, first_slot=0, source=None, d=None, rtol=1e-10, maxiter=10000, adjoint=False,
-                  precond="jacobi"):
-        """step with observers and / or the mean's weights on device tensors: otmb_op_step_obs_dev (capi.observe_keywords states the
-        keywords).  info.observations and info.mean are device tensors; the weights are host values."""
-        from .api import StepInfo, step_arrays, time_weights
-
-        pc, k, Xc, ldx, Xn = self._system(X, "X", precond)
-        Xn.copy_(X)
-        n = self.shape[0]
-        Sc, sp, lds = None, None, max(n, 1)
-        if source is not None:
-            _on_device(source, self.device, "source")
-            if tuple(source.shape) != tuple(X.shape):
-                raise capi.OtmbError(11, f"DimensionMismatch: source of {tuple(source.shape)}, X of {tuple(X.shape)}")
-            Sc, lds = _col_major(source, n)
-            sp = Sc.data_ptr()
-        Dc = None
-        if _per_column(d):
-            Dc, ldd = self._dk_ptr(d, X, "X")
-        else:
-            d, dp = self._d_ptr(d)
-        q, Wc, ldw, obs, tw, mean = 0, None, max(n, 1), None, None, None
-        if observe is not None:
-            Wc, ldw, q = self._observers(observe)
-            obs = torch.zeros((max(int(nsteps), 0), k, q), dtype=torch.float64, device=X.device)
-        if weights is not None:
-            tw = time_weights(weights, nsteps)
-            mean = torch.zeros_like(Xn) if X.dim() == 1 else \
-                torch.zeros(k * max(n, 1), dtype=torch.float64, device=X.device).as_strided((n, k), (1, max(n, 1)))
-        iters, relres, reason = step_arrays(nsteps, k)
-        done = C.c_int64(0)
-        if Dc is not None:  # every tracer has its own d: otmb_op_step_dk_dev, the same arguments with D and its leading dimension
-            rc = self.lib.otmb_op_step_dk_dev(self._h, int(bool(adjoint)), k, Dc.data_ptr(), ldd, float(dt), float(theta), int(nsteps), int(first_slot), sp,
-                                              lds, Xn.data_ptr(), max(n, 1), float(rtol), int(maxiter), pc, C.byref(done), iters.ctypes.data,
-                                              relres.ctypes.data, reason.ctypes.data, q, None if Wc is None else Wc.data_ptr(), ldw,
-                                              None if obs is None else obs.data_ptr(), None if tw is None else tw.ctypes.data,
-                                              None if mean is None else mean.data_ptr(), max(n, 1))
-            if rc != capi.NOT_CONVERGED:
-                self.ctx.check(rc)
-            return Xn, StepInfo(rc, done.value, nsteps, iters, relres, reason, obs, mean)
-        rc = self.lib.otmb_op_step_obs_dev(self._h, int(bool(adjoint)), k, dp, float(dt), float(theta), int(nsteps), int(first_slot), sp, lds,
-                                           Xn.data_ptr(), max(n, 1), float(rtol), int(maxiter), pc, C.byref(done), iters.ctypes.data,
-                                           relres.ctypes.data, reason.ctypes.data, q, None if Wc is None else Wc.data_ptr(), ldw,
-                                           None if obs is None else obs.data_ptr(), None if tw is None else tw.ctypes.data,
-                                           None if mean is None else mean.data_ptr(), max(n, 1))
-        if rc != capi.NOT_CONVERGED:
-            self.ctx.check(rc)
-        return Xn, StepInfo(rc, done.value, nsteps, iters, relres, reason, obs, mean)
-
-    @capi.outer_keyword
-    def periodic(self, source, *, dt, ncycle, theta=1.0, first_slot=0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi",
-                 ptol=1e-8, restart=30, maxcycles=1000):
-        """The periodic state of the stepped cycle on device tensors (otmb_op_periodic_dev; api.DeviceOperator.periodic states the arguments).
-        source, x0: device tensors, not modified.  Returns (a new tensor with the state at the start of the cycle, an api.PeriodicInfo).  Per
-        round the host reads a few scalars a column; no vector travels."""
-        from .api import PeriodicInfo
-
-        if _per_column(d):
-            return self._periodic_pc(source, capi.OUTERS["none"], dt=dt, ncycle=ncycle, theta=theta, first_slot=first_slot, d=d, x0=x0, rtol=rtol,
-                                     maxiter=maxiter, adjoint=adjoint, precond=precond, ptol=ptol, restart=restart, maxcycles=maxcycles)
-        pc, k, Sc, lds, X = self._system(source, "source", precond)
-        if x0 is not None:
-            _on_device(x0, self.device, "x0")
-            if tuple(x0.shape) != tuple(source.shape):
-                raise capi.OtmbError(11, f"DimensionMismatch: x0 of {tuple(x0.shape)}, source of {tuple(source.shape)}")
-            X.copy_(x0)
-        d, dp = self._d_ptr(d)
-        cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
-        rc = self.lib.otmb_op_periodic_dev(self._h, int(bool(adjoint)), k, dp, float(dt), float(theta), int(ncycle), int(first_slot), Sc.data_ptr(), lds,
-                                           X.data_ptr(), max(self.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), pc, float(ptol),
-                                           int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data, reason.ctypes.data)
-        if rc != capi.NOT_CONVERGED:
-            self.ctx.check(rc)
-        return X, PeriodicInfo(rc, cycles, defect, reason)
-
-    def _periodic_pc(self, source, outer, *, dt, ncycle, theta=1.0, first_slot=0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False,
-                     precond="jacobi", ptol=1e-8, restart=30, maxcycles=1000):
-        """periodic with outer = an otmb_outer code: otmb_op_periodic_pc_dev."""
-        from .api import PeriodicInfo
-
-        pc, k, Sc, lds, X = self._system(source, "source", precond)
-        if x0 is not None:
-            _on_device(x0, self.device, "x0")
-            if tuple(x0.shape) != tuple(source.shape):
-                raise capi.OtmbError(11, f"DimensionMismatch: x0 of {tuple(x0.shape)}, source of {tuple(source.shape)}")
-            X.copy_(x0)
-        cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
-        msolve = np.zeros(k, dtype=np.int64)
-        if _per_column(d):
-            Dc, ldd = self._dk_ptr(d, source, "source")
-            rc = self.lib.otmb_op_periodic_dk_dev(self._h, int(bool(adjoint)), k, Dc.data_ptr(), ldd, float(dt), float(theta), int(ncycle), int(first_slot),
-                                                  Sc.data_ptr(), lds, X.data_ptr(), max(self.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter),
-                                                  pc, float(ptol), int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data,
-                                                  reason.ctypes.data, int(outer), msolve.ctypes.data)
-            if rc != capi.NOT_CONVERGED:
-                self.ctx.check(rc)
-            return X, PeriodicInfo(rc, cycles, defect, reason, msolve)
-        d, dp = self._d_ptr(d)
-        rc = self.lib.otmb_op_periodic_pc_dev(self._h, int(bool(adjoint)), k, dp, float(dt), float(theta), int(ncycle), int(first_slot), Sc.data_ptr(),
-                                              lds, X.data_ptr(), max(self.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), pc, float(ptol),
-                                              int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data, reason.ctypes.data, int(outer),
-                                              msolve.ctypes.data)
-        if rc != capi.NOT_CONVERGED:
-            self.ctx.check(rc)
-        return X, PeriodicInfo(rc, cycles, defect, reason, msolve)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

@@ -1,0 +1,289 @@
+"""The resident operator's solver calls, marshalled once for both bindings: api.DeviceOperator (numpy arrays, the host-pointer exports) and
+device.Operator (torch tensors, the `_dev` exports) derive from OperatorCalls, which validates the arguments, assembles each export's argument
+list in the order of include/otmb.h and turns the status into a report.  The two classes differ only in how they handle arrays.  No torch
+here: api.py imports without it."""
+import ctypes as C
+
+import numpy as np
+
+from . import capi
+
+
+class SolveInfo:
+    """What otmb_op_solve_pc reports, one entry per column of B: iterations (completed), relres (‖r‖₂/‖b‖₂ of the column's last residual
+    evaluation: the explicitly computed b - M·x when it stopped on one, the recursive residual otherwise), reason ("converged", "maxiter",
+    "breakdown", "nonfinite") and converged; status is the call's own (0, or capi.NOT_CONVERGED when some column is not converged)."""
+
+    def __init__(self, status, iterations, relres, reason):
+        self.status = int(status)
+        self.iterations = np.asarray(iterations, dtype=np.int64)
+        self.relres = np.asarray(relres, dtype=np.float64)
+        self.reason = tuple(capi.SOLVE_REASONS[int(r)] for r in reason)
+        self.converged = np.array([r == "converged" for r in self.reason], dtype=bool)
+
+    def __repr__(self):
+        return f"SolveInfo(status={self.status}, iterations={self.iterations.tolist()}, relres={self.relres.tolist()}, reason={self.reason})"
+
+
+class StepInfo:
+    """What otmb_op_step reports: status (0, or capi.NOT_CONVERGED), steps_done (steps completed with every column converged) and, one row
+    per step that ran a solve (steps 0 .. min(steps_done, nsteps - 1)) and one entry per column: iterations, relres, reason (tuples of
+    "converged", "maxiter", "breakdown", "nonfinite") and converged -- each as SolveInfo has them for one solve.  From
+    step(..., observe=W): observations, (steps_done, k, q), entry [t, c, j] = observer j of tracer c after step t (only the steps that were
+    completed); from step(..., time_weights=w): mean, n x k (n values for a 1-D state) = Σ_t w[t]·X_t over the completed steps, None when
+    no step was.  Both None otherwise."""
+
+    def __init__(self, status, steps_done, nsteps, iterations, relres, reason, observations=None, mean=None):
+        self.status, self.steps_done = int(status), int(steps_done)
+        self.observations = None if observations is None else observations[:self.steps_done]
+        self.mean = mean if self.steps_done > 0 else None
+        ran = min(self.steps_done + 1, int(nsteps))
+        self.iterations = np.asarray(iterations, dtype=np.int64)[:ran]
+        self.relres = np.asarray(relres, dtype=np.float64)[:ran]
+        self.reason = tuple(tuple(capi.SOLVE_REASONS[int(r)] for r in row) for row in np.asarray(reason)[:ran])
+        self.converged = np.array([[r == "converged" for r in row] for row in self.reason], dtype=bool).reshape(self.iterations.shape)
+
+    def __repr__(self):
+        return f"StepInfo(status={self.status}, steps_done={self.steps_done}, iterations={self.iterations.tolist()}, reason={self.reason})"
+
+
+def observers(W, n):
+    """(W as a 2-D array n x q, q) of step(..., observe=W) / observe(W, X): n values are one observer."""
+    shape = tuple(W.shape)
+    if len(shape) not in (1, 2) or shape[0] != n:
+        raise capi.OtmbError(11, f"DimensionMismatch: observers of {shape}, expected {n} rows")
+    return (W.reshape(n, 1) if len(shape) == 1 else W), (1 if len(shape) == 1 else shape[1])
+
+
+def time_weights(w, nsteps):
+    """The mean's weights as nsteps float64 host values."""
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if w.shape != (max(int(nsteps), 0),):
+        raise capi.OtmbError(11, f"DimensionMismatch: time_weights of {w.shape}, expected {(max(int(nsteps), 0),)}")
+    return w
+
+
+_as_weights = time_weights  # step has a keyword time_weights: inside it the function goes by this name
+
+
+def step_arrays(nsteps, k):
+    """The three report arrays of otmb_op_step (nsteps x k, step-major)."""
+    shape = (max(int(nsteps), 0), int(k))
+    return np.zeros(shape, dtype=np.int64), np.zeros(shape, dtype=np.float64), np.zeros(shape, dtype=np.int32)
+
+
+class PeriodicInfo:
+    """What otmb_op_periodic reports, one entry per column: cycles (the step calls the column took part in, the verifying ones included),
+    defect (‖F(x) - x‖₂/‖g‖₂ of the column's last explicitly computed F(x) - x; NaN when none was), reason ("converged", "maxcycles",
+    "step_failed", "nonfinite", and with outer="mean" "precond_failed") and converged; msolve_iters: the BiCGStab iterations the column spent in
+    mean solves (outer="mean"; otherwise zero); status is the call's own (0, or capi.NOT_CONVERGED when some column is not converged)."""
+
+    def __init__(self, status, cycles, defect, reason, msolve_iters=None):
+        self.status = int(status)
+        self.cycles = np.asarray(cycles, dtype=np.int64)
+        self.defect = np.asarray(defect, dtype=np.float64)
+        self.reason = tuple(capi.PERIODIC_PC_REASONS[int(r)] for r in reason)
+        self.converged = np.array([r == "converged" for r in self.reason], dtype=bool)
+        self.msolve_iters = np.zeros(len(self.cycles), dtype=np.int64) if msolve_iters is None else np.asarray(msolve_iters, dtype=np.int64)
+
+    def __repr__(self):
+        return (f"PeriodicInfo(status={self.status}, cycles={self.cycles.tolist()}, defect={self.defect.tolist()}, reason={self.reason}, "
+                f"msolve_iters={self.msolve_iters.tolist()})")
+
+
+class OperatorCalls:
+    """precondition, solve, observe, step and periodic of a resident operator (its handle `_h`, `shape` and context `ctx`), written once.
+    Arrays below are numpy arrays for api.DeviceOperator and float64 tensors on the operator's GPU for device.Operator, whose results --
+    the states, info.observations and info.mean -- are new device tensors; the reports' per-column records and time_weights are host values
+    for both.  What a subclass says about its arrays:
+      _suffix               of the exports' names: "" (host pointers) or "_dev" (device pointers)
+      _live()               raises ValueError when the operator is closed
+      _library()            the loaded library
+      _array(a, what)       the argument as an array of the class's kind (`what` names it in a refusal)
+      _matrix(a, rows)      (a column-major, its leading dimension): `a` itself when its rows are contiguous, a copy otherwise
+      _ptr(a)               the address the library is given (None stays None)
+      _zeros(shape, order)  a zeroed float64 result: "F" column-major (rows x k with leading dimension max(rows, 1)), "C" row-major
+      _assign(X, a)         copies a into the result X
+    Every refusal is raised before the library is called."""
+
+    _suffix = ""
+
+    def _call(self, name, *args):
+        return getattr(self._library(), name + self._suffix)(self._h, *args)
+
+    def _status(self, rc):
+        """NOT_CONVERGED is an answer (the info object says which column stopped why); every other status but 0 raises."""
+        if rc != capi.NOT_CONVERGED:
+            self.ctx.check(rc)
+        return rc
+
+    def _state(self, B, what):
+        """(B as an array, k, B column-major, its leading dimension) of the argument that has the state's shape: m values or m x k."""
+        B = self._array(B, what)
+        m, n = self.shape
+        if B.ndim not in (1, 2) or B.shape[0] != m:
+            raise capi.OtmbError(11, f"DimensionMismatch: operator of {(m, n)}, {what} of {tuple(B.shape)}")
+        Bc, ldb = self._matrix(B, m)
+        return B, (1 if B.ndim == 1 else B.shape[1]), Bc, ldb
+
+    def _like(self, a, what, B, of):
+        """x0 or source as an array: it has the shape of the state B (the argument `of`)."""
+        a = self._array(a, what)
+        if tuple(a.shape) != tuple(B.shape):
+            raise capi.OtmbError(11, f"DimensionMismatch: {what} of {tuple(a.shape)}, {of} of {tuple(B.shape)}")
+        return a
+
+    def _check_d(self, d, want, what):
+        """d has the shape `want`: (n,), or that of the state `what` for one d per column.  (device.Operator's also refuses other dtypes,
+        which numpy converts, in the wording its tests know.)"""
+        if tuple(d.shape) != want:
+            raise capi.OtmbError(11, f"DimensionMismatch: d of {tuple(d.shape)}, " + (f"expected {want}" if len(want) == 1 else f"{what} of {want}"))
+
+    def _d(self, d, B, what):
+        """(what keeps d alive, d's part of an argument list): [pointer or None] for n values or None -- the exports with one d -- and
+        [pointer, ldd] for a matrix of B's shape, one d per column: the otmb_op_*_dk exports (include/otmb.h: column c is the 1-D call with
+        d[:, c], bit for bit)."""
+        if d is None:
+            return None, [None]
+        d = self._array(d, "d")
+        if d.ndim != 2:
+            self._check_d(d, (self.shape[1],), what)
+            dc, _ = self._matrix(d, self.shape[1])
+            return dc, [self._ptr(dc)]
+        if B.ndim != 2:
+            raise capi.OtmbError(11, f"DimensionMismatch: d of {tuple(d.shape)} is per column, {what} of {tuple(B.shape)} has no columns")
+        self._check_d(d, tuple(B.shape), what)
+        Dc, ldd = self._matrix(d, self.shape[1])
+        return Dc, [self._ptr(Dc), ldd]
+
+    def _start(self, x0, B, of):
+        """The zeroed result of B's shape, with x0 copied in when one is given."""
+        if x0 is not None:
+            x0 = self._like(x0, "x0", B, of)
+        X = self._zeros(tuple(B.shape))
+        if x0 is not None:
+            self._assign(X, x0)
+        return X
+
+    def precondition(self, Y, d=None, sigma=0.0, adjoint=False, precond="lines"):
+        """Z = P⁻¹·Y with the preconditioner solve(..., precond=precond) uses for M = σ·I + diag(d) + A (adjoint: Aᵀ) (otmb_op_precond): for a
+        Krylov method of the caller's own.  Y: 1-D or 2-D (n x k); d as in solve; returns a new Z of Y's shape (2-D: column-major)."""
+        self._live()
+        pc = capi.precond_code(precond)
+        Y, k, Yc, ldy = self._state(Y, "Y")
+        dc, dargs = self._d(d, Y, "Y")
+        Z = self._zeros(tuple(Y.shape))
+        name = "otmb_op_precond_dk" if len(dargs) == 2 else "otmb_op_precond"
+        self.ctx.check(self._call(name, int(bool(adjoint)), pc, k, *dargs, float(sigma), self._ptr(Yc), ldy, self._ptr(Z), max(self.shape[0], 1)))
+        return Z
+
+    def solve(self, B, d=None, sigma=0.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False, precond="jacobi"):
+        """X with (σ·I + diag(d) + A)·X = B (adjoint: ... + Aᵀ) by preconditioned BiCGStab on the device (otmb_op_solve_pc, include/otmb.h:
+        the method, the stop rules, what is deterministic).  B: 1-D or 2-D (n x k); d: None (zero), n values, or a matrix of B's 2-D shape:
+        every column has its own d (otmb_op_solve_dk); x0: None (start from zero) or an array of B's shape (not modified).  Returns (X, info):
+        a new X of B's shape (2-D: column-major), info a SolveInfo with one entry per column (the call waits for the device to read it).  A
+        column that does not converge is REPORTED (info.converged, info.reason), not raised: X then holds its last iterate.
+        Argument errors and a zero or non-finite diagonal (SINGULAR_PRECONDITIONER) raise OtmbError.
+        precond = "jacobi" (default) | "lines": the preconditioner; "lines" is P = M on the lines of set_lines (the water columns'
+        tridiagonals: far fewer iterations on time-stepping systems) and needs set_lines first.  With "lines" only the pivots of
+        the line factorisation are checked, not the diagonal: a zero or non-finite diag(M) entry is then reported, if it makes a pivot
+        singular, as that pivot ("pivot[i] ...") -- also when next is all zero, where the results are Jacobi's but the message is not."""
+        self._live()
+        pc = capi.precond_code(precond)
+        B, k, Bc, ldb = self._state(B, "B")
+        dc, dargs = self._d(d, B, "B")
+        X = self._start(x0, B, "B")
+        iters, relres, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
+        name = "otmb_op_solve_dk" if len(dargs) == 2 else "otmb_op_solve_pc"
+        rc = self._call(name, int(bool(adjoint)), k, *dargs, float(sigma), self._ptr(Bc), ldb, self._ptr(X), max(self.shape[0], 1), int(x0 is not None),
+                        float(rtol), int(maxiter), iters.ctypes.data, relres.ctypes.data, reason.ctypes.data, pc)
+        return X, SolveInfo(self._status(rc), iters, relres, reason)
+
+    def observe(self, W, X):
+        """Wᵀ·X on the device (otmb_op_observe; include/otmb.h states the order of the sums): W n x q (or n values: one observer), X n x k or
+        1-D.  Returns a new array (q, k), or (q,) for 1-D X: inventories (W = the cell volumes), stations, regional means of a state.  On
+        device tensors it is enqueued on the context's stream and nothing travels to the host."""
+        self._live()
+        n = self.shape[1]
+        X = self._array(X, "X")
+        if X.ndim not in (1, 2) or X.shape[0] != n:
+            raise capi.OtmbError(11, f"DimensionMismatch: operator of {self.shape}, X of {tuple(X.shape)}")
+        k = 1 if X.ndim == 1 else X.shape[1]
+        Xc, ldx = self._matrix(X, n)
+        W, q = observers(self._array(W, "observe"), n)
+        Wc, ldw = self._matrix(W, n)
+        obs = self._zeros((q, k))
+        self.ctx.check(self._call("otmb_op_observe", k, q, self._ptr(Wc), ldw, self._ptr(Xc), ldx, self._ptr(obs)))
+        return obs[:, 0] if X.ndim == 1 else obs
+
+    def step(self, X, *, dt, theta=1.0, nsteps=1, first_slot=0, source=None, d=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi",
+             observe=None, time_weights=None):
+        """nsteps θ-steps of ∂x/∂t + (diag(d) + A)·x = source from the state X, step t with the matrix of slot (first_slot + t) mod nslots
+        (otmb_op_step; include/otmb.h states the contract: σ = 1 / (theta·dt), the right-hand side, then solve(..., x0 = the state)).  X: 1-D
+        or 2-D (n x k), not modified: the steps run on a copy; source: None (zero) or an array of X's shape; d: None, n values, or a matrix of
+        X's 2-D shape: every tracer has its own d (otmb_op_step_dk), and column c is the 1-D call with d[:, c].  Returns (X after the steps,
+        info): info a StepInfo.  A step that does not converge ends the call and is REPORTED as solve reports it (info.status,
+        info.steps_done, info.reason; X then holds that step's last iterates), not raised; argument errors and a singular preconditioner
+        raise OtmbError.  Nothing but the solver's column records travels to the host.
+        observe: W, n x q (or n values: one observer) -> info.observations, (steps_done, k, q); time_weights: nsteps finite host values ->
+        info.mean = Σ_t time_weights[t]·X_t, n x k.  With either the call is otmb_op_step_obs (include/otmb.h states the order of the sums
+        and the mean's fold); with neither it is the plain one, and info.observations and info.mean are None."""
+        self._live()
+        pc = capi.precond_code(precond)
+        X, k, Xc, _ = self._state(X, "X")
+        dc, dargs = self._d(d, X, "X")
+        (m, n), ld = self.shape, max(self.shape[0], 1)
+        Sc, lds = None, ld
+        if source is not None:
+            Sc, lds = self._matrix(self._like(source, "source", X, "X"), m)
+        q, Wc, ldw, obs, tw, mean = 0, None, max(n, 1), None, None, None
+        if observe is not None:
+            W, q = observers(self._array(observe, "observe"), n)
+            Wc, ldw = self._matrix(W, n)
+            obs = self._zeros((max(int(nsteps), 0), k, q), "C")
+        if time_weights is not None:
+            tw = _as_weights(time_weights, nsteps)
+            mean = self._zeros(tuple(X.shape))
+        Xn = self._zeros(tuple(X.shape))
+        self._assign(Xn, Xc)
+        iters, relres, reason = step_arrays(nsteps, k)
+        done = C.c_int64(0)
+        args = [int(bool(adjoint)), k, *dargs, float(dt), float(theta), int(nsteps), int(first_slot), self._ptr(Sc), lds, self._ptr(Xn), ld, float(rtol),
+                int(maxiter), pc, C.byref(done), iters.ctypes.data, relres.ctypes.data, reason.ctypes.data]
+        record = len(dargs) == 2 or obs is not None or tw is not None
+        name = "otmb_op_step_dk" if len(dargs) == 2 else "otmb_op_step_obs" if record else "otmb_op_step"
+        if record:  # the record's arguments; q = 0 and nulls make the per-column call the plain step
+            args += [q, self._ptr(Wc), ldw, self._ptr(obs), None if tw is None else tw.ctypes.data, self._ptr(mean), ld]
+        rc = self._call(name, *args)
+        return Xn, StepInfo(self._status(rc), done.value, nsteps, iters, relres, reason, obs, mean)
+
+    def periodic(self, source, *, dt, ncycle, theta=1.0, first_slot=0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi",
+                 ptol=1e-8, restart=30, maxcycles=1000, outer="none"):
+        """The periodic state of the stepped cycle: X with F(X) = X, F = step(..., nsteps=ncycle, first_slot=first_slot, source=source), by
+        restarted GMRES(restart) on the cycle map (otmb_op_periodic; include/otmb.h states the method and what is deterministic).  source:
+        1-D or 2-D (n x k); x0: None (start from zero) or an array of source's shape (not modified); d: None, n values, or a matrix of
+        source's 2-D shape: every column has its own d (otmb_op_periodic_dk); the other arguments are step's.  Returns (X, info): a new X,
+        the state at the start of the cycle, with ‖F(X) - X‖₂ <= ptol·‖F(0)‖₂ per converged column, info a PeriodicInfo.  A column that
+        does not converge is REPORTED (info.reason), not raised; argument errors and a singular preconditioner raise OtmbError.  Per round
+        the host reads a few scalars a column; no vector travels.
+        outer = "none" (default) | "mean": with "mean" the outer GMRES is flexible and preconditioned by the cycle-mean operator
+        (otmb_op_periodic_pc with OTMB_OUTER_MEAN; include/otmb.h states the method) -- fewer cycles, one solve with the mean matrix per
+        iteration (info.msolve_iters; zero with "none")."""
+        oc = capi.outer_code(outer)
+        self._live()
+        pc = capi.precond_code(precond)
+        S, k, Sc, lds = self._state(source, "source")
+        dc, dargs = self._d(d, S, "source")
+        X = self._start(x0, S, "source")
+        cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
+        args = [int(bool(adjoint)), k, *dargs, float(dt), float(theta), int(ncycle), int(first_slot), self._ptr(Sc), lds, self._ptr(X),
+                max(self.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), pc, float(ptol), int(restart), int(maxcycles), cycles.ctypes.data,
+                defect.ctypes.data, reason.ctypes.data]
+        outer_args = len(dargs) == 2 or oc != capi.OUTERS["none"]
+        name = "otmb_op_periodic_dk" if len(dargs) == 2 else "otmb_op_periodic_pc" if outer_args else "otmb_op_periodic"
+        msolve = None
+        if outer_args:
+            msolve = np.zeros(k, dtype=np.int64)
+            args += [oc, msolve.ctypes.data]
+        rc = self._call(name, *args)
+        return X, PeriodicInfo(self._status(rc), cycles, defect, reason, msolve)

@@ -1,12 +1,15 @@
 """CPU: otmb_op_periodic_pc[_dev] and otmb_op_combine_slots[_dev] have the same types in the same order in the C prototypes (include/otmb.h),
 the ctypes mirror and the Julia shim's ccalls; the shim's `outer` keyword and `combineslots!`, api.DeviceOperator and device.Operator hand the
 same values over in the same places; and the unpreconditioned call is still the one tests/test_periodic_shim_static.py pins."""
+import inspect
 import os
 import re
 
+import numpy as np
+from operator_calls_rec import CASES, K, N, PERIODIC, has, host_operator, the_call
 from test_julia_shim_static import SHIM, ctypes_kind, header_prototypes, julia_kind, split_top
-from test_periodic_shim_static import KINDS, ORDER, _passed
-from test_solve_shim_static import API, CODE, ROOT, _header_names, _jl
+from test_periodic_shim_static import KINDS, ORDER
+from test_solve_shim_static import API, CALLS, CODE, ROOT, _header_names, _jl
 from test_step_shim_static import _ccall
 
 PC_ORDER = ORDER + ["outer", "msolve_iters"]
@@ -91,46 +94,34 @@ def _cls(text, start):
     return text[text.index(start):]
 
 
-def test_python_makes_the_same_calls():
-    from otmb_amd import capi
+def test_python_makes_the_same_calls(monkeypatch):
+    from otmb_amd import api, capi, device, operator_calls
 
     dev = open(os.path.join(ROOT, "oceantransportmatrixbuilder.jl_amd", "device.py"), encoding="utf-8").read()
-    sig = '(self, source, outer, *, dt, ncycle, theta=1.0, first_slot=0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False,\n' \
-          '                     precond="jacobi", ptol=1e-8, restart=30, maxcycles=1000):'
-    for text, cls, fn, first, middle in ((API, "\nclass DeviceOperator:", "lib.otmb_op_periodic_pc", ["self._h", "int(bool(adjoint))", "k",
-                                          "None if dc is None else dc.ctypes.data"], ["Sc.ctypes.data", "lds", "X.ctypes.data", "max(X.shape[0], 1)"]),
-                                         (dev, "\nclass Operator:", "self.lib.otmb_op_periodic_pc_dev", ["self._h", "int(bool(adjoint))", "k", "dp"],
-                                          ["Sc.data_ptr()", "lds", "X.data_ptr()", "max(self.shape[0], 1)"])):
-        body = _cls(text, cls)
-        m = re.search(r"\n    def _periodic_pc\(self.*?(?=\n    def )", body, re.S)
-        assert m and "\n    def _periodic_pc" + sig in m.group(0), fn
-        assert _passed(m.group(0), fn, "msolve.ctypes.data") == first + ["float(dt)", "float(theta)", "int(ncycle)", "int(first_slot)"] + middle + [
-            "int(x0 is not None)", "float(rtol)", "int(maxiter)", "pc", "float(ptol)", "int(restart)", "int(maxcycles)", "cycles.ctypes.data",
-            "defect.ctypes.data", "reason.ctypes.data", "int(outer)", "msolve.ctypes.data"], fn
-        assert "if rc != capi.NOT_CONVERGED:" in m.group(0) and "PeriodicInfo(rc, cycles, defect, reason, msolve)" in m.group(0)
-        # the public method is the pinned one under the keyword's decorator
-        assert re.search(r"\n    @capi\.outer_keyword\n    def periodic\(self, source, \*, dt, ncycle,", body), fn
-        c = re.search(r"\n    def combine_slots\(self, weights, dst\):.*?(?=\n    (?:def |@))", body, re.S).group(0)
-        want = "otmb_op_combine_slots_dev" if "data_ptr" in middle[0] else "otmb_op_combine_slots"
-        assert re.findall(r"\.(otmb_op_combine\w+)\(", c) == [want] and "(self._h, w.ctypes.data, int(dst))" in c, fn
-    src = open(os.path.join(ROOT, "oceantransportmatrixbuilder.jl_amd", "capi.py"), encoding="utf-8").read()
-    m = re.search(r"\ndef outer_keyword\(plain\):.*?\n    return periodic\n", src, re.S).group(0)
-    assert 'def periodic(self, source, *, outer="none", **kw):' in m
-    assert 'return plain(self, source, **kw) if code == OUTERS["none"] else self._periodic_pc(source, code, **kw)' in m
-    assert re.search(r"\n    def combine_slots\(self, weights, dst, matrix=\"T\"\):.*?op\.combine_slots\(weights, dst\)", dev, re.S)
-    # the keyword behaves without a device: unknown values are refused before anything is called
-    class Fake:
-        @capi.outer_keyword
-        def periodic(self, source, *, dt):
-            return ("plain", source, dt)
-
-        def _periodic_pc(self, source, outer, *, dt):
-            return ("pc", source, outer, dt)
-
-    assert Fake().periodic(1, dt=2) == Fake().periodic(1, dt=2, outer="none") == ("plain", 1, 2)
-    assert Fake().periodic(1, dt=2, outer="mean") == ("pc", 1, 1, 2)
+    D, rec = host_operator(monkeypatch, rc=19)
+    S, d, x0 = np.asfortranarray(np.ones((N + 2, K)))[:N], np.arange(1.0, N + 1), np.full((N, K), 2.0)
+    for start, (given, sent) in ((start, case) for start in (x0, None) for case in CASES):  # (no 0/1 argument follows another through all four)
+        X, info = D.periodic(S, d=d, x0=start, outer="mean", **given, **PERIODIC)
+        a = the_call(rec, "otmb_op_periodic_pc")
+        assert list(a) == PC_ORDER
+        has(a, k=K, d=d.ctypes.data, S=S.ctypes.data, lds=N + 2, X=X.ctypes.data, ldx=N, use_x0=int(start is not None), cycles=info.cycles.ctypes.data,
+            defect=info.defect.ctypes.data, outer=capi.OUTERS["mean"], msolve_iters=info.msolve_iters.ctypes.data, **sent, **PERIODIC)
+        assert info.status == 19 and D.ctx.checked == [] and info.msolve_iters.shape == (K,)  # reported, not raised; the same fields either way
+    # the keyword on the real method: "none" is the default and the unpreconditioned export, unknown values are refused before anything is called
+    D.periodic(S, dt=2.0, ncycle=2)
+    D.periodic(S, dt=2.0, ncycle=2, outer="none")
+    assert [name for name, _ in rec.calls] == ["otmb_op_periodic", "otmb_op_periodic"]
+    del rec.calls[:]
     try:
-        Fake().periodic(1, dt=2, outer="annual")
+        D.periodic(S, dt=2.0, ncycle=2, outer="annual")
         raise AssertionError("an unknown outer was accepted")
     except capi.OtmbError as e:
-        assert e.name == "INVALID_ARG"
+        assert e.name == "INVALID_ARG" and rec.calls == []
+    for text, cls, klass, want in ((API, "\nclass DeviceOperator(", api.DeviceOperator, "otmb_op_combine_slots"),
+                                   (dev, "\nclass Operator(", device.Operator, "otmb_op_combine_slots_dev")):
+        # the public method is the one method of both classes, outer in its own signature
+        assert klass.periodic is operator_calls.OperatorCalls.periodic and inspect.signature(klass.periodic).parameters["outer"].default == "none"
+        c = re.search(r"\n    def combine_slots\(self, weights, dst\):.*?(?=\n    (?:def |@))", _cls(text, cls), re.S).group(0)
+        assert re.findall(r"\.(otmb_op_combine\w+)\(", c) == [want] and "(self._h, w.ctypes.data, int(dst))" in c, want
+    assert len(re.findall('"otmb_op_periodic_pc"', CALLS)) == 1 and '"otmb_op_periodic' not in API + dev  # no second route
+    assert re.search(r"\n    def combine_slots\(self, weights, dst, matrix=\"T\"\):.*?op\.combine_slots\(weights, dst\)", dev, re.S)

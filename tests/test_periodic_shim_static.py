@@ -1,12 +1,15 @@
 """CPU: otmb_op_periodic and otmb_op_periodic_dev have the same types in the same order in the C prototypes (include/otmb.h), the ctypes mirror
 and the Julia shim's ccall, and the shim, api.DeviceOperator and device.Operator hand the same values over in the same places (the Python side
 is what the GPU tests execute)."""
+import inspect
 import os
 import re
 
+import numpy as np
+from operator_calls_rec import CASES, K, N, PERIODIC, SIGNATURES, has, host_operator, the_call
 from test_julia_shim_static import SHIM, ctypes_kind, header_prototypes, julia_kind, split_top
-from test_solve_shim_static import API, CODE, ROOT, _header_names
-from test_step_shim_static import _ccall, _method
+from test_solve_shim_static import API, CALLS, CODE, ROOT, _header_names
+from test_step_shim_static import _ccall
 
 ORDER = ["op", "adjoint", "k", "d", "dt", "theta", "ncycle", "first_slot", "S", "lds", "X", "ldx", "use_x0", "rtol", "maxiter", "precond", "ptol",
          "restart", "maxcycles", "cycles", "defect", "reason"]
@@ -58,29 +61,25 @@ def test_the_shim_defines_exports_and_calls_it():
     assert len(re.findall(r"\bccall\(", body)) == 1
 
 
-def _passed(py, fn, last):
-    call = py[py.index(fn + "(") + len(fn) + 1:]
-    return split_top(" ".join(call[:call.index(last + ")") + len(last)].split()))
+def test_python_makes_the_same_calls(monkeypatch):
+    from otmb_amd import api, device, operator_calls
 
-
-def test_python_makes_the_same_calls():
-    sig = '(self, source, *, dt, ncycle, theta=1.0, first_slot=0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi",\n' \
-          '                 ptol=1e-8, restart=30, maxcycles=1000):'
-    py = _method("periodic")
-    assert "\n    def periodic" + sig in py
-    assert re.findall(r"lib\.(otmb_\w+)\(", py) == ["otmb_op_periodic"]
-    assert _passed(py, "lib.otmb_op_periodic", "reason.ctypes.data") == [
-        "self._h", "int(bool(adjoint))", "k", "None if dc is None else dc.ctypes.data", "float(dt)", "float(theta)", "int(ncycle)", "int(first_slot)",
-        "Sc.ctypes.data", "lds", "X.ctypes.data", "max(X.shape[0], 1)", "int(x0 is not None)", "float(rtol)", "int(maxiter)", "pc", "float(ptol)",
-        "int(restart)", "int(maxcycles)", "cycles.ctypes.data", "defect.ctypes.data", "reason.ctypes.data"]
-    assert "pc = capi.precond_code(precond)" in py and "if rc != capi.NOT_CONVERGED:" in py
+    D, rec = host_operator(monkeypatch, rc=19)
+    S, d, x0 = np.asfortranarray(np.ones((N + 2, K)))[:N], np.arange(1.0, N + 1), np.full((N, K), 2.0)
+    for start, (given, sent) in ((start, case) for start in (None, x0) for case in CASES):  # (no 0/1 argument follows another through all four)
+        X, info = D.periodic(S, d=d, x0=start, **given, **PERIODIC)
+        a = the_call(rec, "otmb_op_periodic")  # outer="none", the default: the unpreconditioned call
+        assert list(a) == ORDER
+        has(a, k=K, d=d.ctypes.data, S=S.ctypes.data, lds=N + 2, X=X.ctypes.data, ldx=N, use_x0=int(start is not None), cycles=info.cycles.ctypes.data,
+            defect=info.defect.ctypes.data, **sent, **PERIODIC)
+        assert a["op"] is D._h and np.array_equal(X, np.zeros((N, K)) if start is None else x0) and X.flags.f_contiguous
+        assert info.status == 19 and D.ctx.checked == [] and not info.msolve_iters.any()  # reported, not raised
+    # both classes: the one method, its keywords in its own signature; device.Operator's reaches otmb_op_periodic_dev
+    for cls, suffix in ((api.DeviceOperator, ""), (device.Operator, "_dev")):
+        assert cls.periodic is operator_calls.OperatorCalls.periodic and cls._suffix == suffix
+        assert str(inspect.signature(cls.periodic)) == SIGNATURES["periodic"] and not hasattr(cls.periodic, "__wrapped__")
     dev = open(os.path.join(ROOT, "oceantransportmatrixbuilder.jl_amd", "device.py"), encoding="utf-8").read()
-    m = re.search(r"\n    def periodic\(self.*?(?=\n    def )", dev, re.S)
-    assert m and "\n    def periodic" + sig in m.group(0)
-    assert _passed(m.group(0), "self.lib.otmb_op_periodic_dev", "reason.ctypes.data") == [
-        "self._h", "int(bool(adjoint))", "k", "dp", "float(dt)", "float(theta)", "int(ncycle)", "int(first_slot)", "Sc.data_ptr()", "lds", "X.data_ptr()",
-        "max(self.shape[0], 1)", "int(x0 is not None)", "float(rtol)", "int(maxiter)", "pc", "float(ptol)", "int(restart)", "int(maxcycles)",
-        "cycles.ctypes.data", "defect.ctypes.data", "reason.ctypes.data"]
+    assert len(re.findall('"otmb_op_periodic"', CALLS)) == 1 and '"otmb_op_periodic' not in API + dev
     assert re.search(r"\n    def periodic_tracers\(self, source, \*, matrix=\"T\", \*\*kw\):.*?return rec\[\"op\"\]\.periodic\(source, \*\*kw\)", dev, re.S)
     # the same defaults on both sides
     assert "ptol::Real = 1e-8, restart::Integer = 30" in SHIM and "maxcycles::Integer = 1000)" in SHIM

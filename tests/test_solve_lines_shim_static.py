@@ -1,8 +1,11 @@
 """CPU: the line preconditioner's entry points (otmb_op_set_lines, otmb_op_solve_pc, otmb_op_precond and their _dev variants) have the same
 types in the same order in the C prototypes (include/otmb.h), the ctypes mirrors and the Julia shim's ccalls, and the shim and
 api.DeviceOperator hand the same values over in the same places (the Python side is what the GPU tests execute)."""
+import inspect
 import re
 
+import numpy as np
+from operator_calls_rec import CASES, K, N, SIGNATURES, has, host_operator, only, the_call
 from test_julia_shim_static import HEADER, SHIM, ctypes_kind, header_prototypes, julia_kind, split_top
 from test_solve_shim_static import API, C_ORDER, CODE, _header_names, _jl
 
@@ -78,31 +81,33 @@ def test_the_ccalls_have_the_prototypes_and_the_argument_order_of_the_header():
 
 
 def _method(name):
-    cls = API[API.index("\nclass DeviceOperator:"):]
+    cls = API[API.index("\nclass DeviceOperator("):]
     m = re.search(r"\n    def " + name + r"\(self.*?(?=\n    (?:def |@))", cls, re.S)
     assert m, name
     return m.group(0)
 
 
-def test_python_makes_the_same_calls():
-    py = _method("solve")
-    assert re.findall(r"lib\.(otmb_\w+)\(", py) == ["otmb_op_solve_pc"]
-    call = py[py.index("lib.otmb_op_solve_pc(") + len("lib.otmb_op_solve_pc("):]
-    passed = split_top(" ".join(call[:call.index(", pc)") + len(", pc")].split()))
-    assert passed == ["self._h", "int(bool(adjoint))", "k", "None if dc is None else dc.ctypes.data", "float(sigma)", "Bc.ctypes.data", "ldb",
-                      "X.ctypes.data", "max(X.shape[0], 1)", "int(x0 is not None)", "float(rtol)", "int(maxiter)", "iters.ctypes.data",
-                      "relres.ctypes.data", "reason.ctypes.data", "pc"]
-    assert "pc = capi.precond_code(precond)" in py and "if rc != capi.NOT_CONVERGED:" in py
-    py = _method("precondition")
-    assert re.findall(r"lib\.(otmb_\w+)\(", py) == ["otmb_op_precond"]
-    call = py[py.index("lib.otmb_op_precond(") + len("lib.otmb_op_precond("):]
-    passed = split_top(" ".join(call[:call.index("max(Z.shape[0], 1)") + len("max(Z.shape[0], 1)")].split()))
-    assert passed == ["self._h", "int(bool(adjoint))", "pc", "k", "None if dc is None else dc.ctypes.data", "float(sigma)", "Yc.ctypes.data", "ldy",
-                      "Z.ctypes.data", "max(Z.shape[0], 1)"]
-    assert 'precond="lines"):' in py.split("\n")[1] and "precond::Symbol = :lines)" in SHIM  # the same default on both sides
+def test_python_makes_the_same_calls(monkeypatch):
+    from otmb_amd import api
+
+    D, rec = host_operator(monkeypatch, rc=19)
+    B, d = np.asfortranarray(np.ones((N, K))), np.arange(1.0, N + 1)
+    for given, sent in CASES:  # adjoint with "jacobi" (0), then no adjoint with "lines" (otmb_precond's 1): the two never agree
+        X, info = D.solve(B, d=d, sigma=0.125, **only(given, "adjoint", "precond", "rtol", "maxiter"))
+        a = the_call(rec, "otmb_op_solve_pc")
+        assert list(a) == C_ORDER + ["precond"]
+        has(a, k=K, d=d.ctypes.data, sigma=0.125, B=B.ctypes.data, ldb=N, X=X.ctypes.data, ldx=N, use_x0=0, iters=info.iterations.ctypes.data,
+            relres=info.relres.ctypes.data, **only(sent, "adjoint", "precond", "rtol", "maxiter"))
+        assert info.status == 19 and D.ctx.checked == []
+        Z = D.precondition(B, d=d, sigma=0.125, **only(given, "adjoint", "precond"))
+        a = the_call(rec, "otmb_op_precond")
+        assert list(a) == PRECOND_ORDER
+        has(a, k=K, d=d.ctypes.data, sigma=0.125, Y=B.ctypes.data, ldy=N, Z=Z.ctypes.data, ldz=N, **only(sent, "adjoint", "precond"))
+        assert D.ctx.checked.pop() == 19 and D.ctx.checked == []  # (no report to put a status in: the context judges it)
+    assert inspect.signature(api.DeviceOperator.precondition).parameters["precond"].default == "lines"
+    assert "precond::Symbol = :lines)" in SHIM  # the same default on both sides
     py = _method("set_lines")
     assert re.findall(r"lib\.(otmb_\w+)\(", py) == ["otmb_op_set_lines", "otmb_op_set_lines"]
     assert "lib.otmb_op_set_lines(self._h, None)" in py and "lib.otmb_op_set_lines(self._h, nx.ctypes.data)" in py
     # solve carries the keyword in its own signature, Jacobi by default on both sides
-    cls = API[API.index("\nclass DeviceOperator:"):]
-    assert '\n    def solve(self, B, d=None, sigma=0.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False, precond="jacobi"):' in cls
+    assert str(inspect.signature(api.DeviceOperator.solve)) == SIGNATURES["solve"]

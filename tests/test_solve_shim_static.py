@@ -1,13 +1,18 @@
 """CPU: the Julia shim declares and exports solve! and solve over the resident operator, its one ccall (otmb_op_solve_pc: the preconditioner
 is an argument) has the return type, the argument types and the argument ORDER of the C prototype (include/otmb.h) and of the ctypes mirror,
 and the shim and api.DeviceOperator.solve hand the same values over in the same places (the Python side is what the GPU tests execute)."""
+import inspect
 import os
 import re
 
+import numpy as np
+from operator_calls_rec import CASES, K, N, SIGNATURES, has, host_operator, only, the_call
+from operator_calls_rec import header_names as _header_names  # noqa: F401 (the other static tests take it from here)
 from test_julia_shim_static import HEADER, SHIM, ctypes_kind, header_prototypes, julia_kind, split_top
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 API = open(os.path.join(ROOT, "oceantransportmatrixbuilder.jl_amd", "api.py"), encoding="utf-8").read()
+CALLS = open(os.path.join(ROOT, "oceantransportmatrixbuilder.jl_amd", "operator_calls.py"), encoding="utf-8").read()  # DeviceOperator's solver calls
 CODE = "\n".join(l.split("#")[0] for l in SHIM.splitlines())
 C_ORDER = ["op", "adjoint", "k", "d", "sigma", "B", "ldb", "X", "ldx", "use_x0", "rtol", "maxiter", "iters", "relres", "reason"]
 
@@ -16,12 +21,6 @@ def _jl(name):
     m = re.search(r"\nfunction " + re.escape(name) + r"\(.*?\n(.*?)\nend\n", SHIM, re.S)
     assert m, name
     return m.group(1)
-
-
-def _header_names(name):
-    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    args = re.search(r"\b" + name + r"\s*\(([^;{]*?)\)\s*;", text).group(1)
-    return [re.search(r"(\w+)\s*$", a).group(1) for a in split_top(" ".join(args.split()))]
 
 
 def test_header_mirror_and_status_codes():
@@ -86,25 +85,23 @@ def test_the_ccall_has_the_prototype_and_the_argument_order_of_the_header():
     assert "solvepc!" not in SHIM  # no second route beside solve!
 
 
-def test_python_makes_the_same_call():
-    cls = API[API.index("\nclass DeviceOperator:"):]
-    m = re.search(r"\n    def solve\(self, B, d=None, sigma=0\.0, rtol=1e-10, maxiter=10000, x0=None, adjoint=False, precond=\"jacobi\"\):.*?(?=\n    def )",
-                  cls, re.S)
-    assert m, "DeviceOperator.solve"
-    assert cls[m.start() - 1] == "\n"  # a blank line, no decorator, above it: this signature is the one help() shows
-    py = m.group(0)
-    assert re.findall(r"lib\.(otmb_\w+)\(", py) == ["otmb_op_solve_pc"]
-    call = py[py.index("lib.otmb_op_solve_pc(") + len("lib.otmb_op_solve_pc("):]
-    passed = split_top(" ".join(call[:call.index(", pc)") + len(", pc")].split()))
-    want = ["self._h", "int(bool(adjoint))", "k", "None if dc is None else dc.ctypes.data", "float(sigma)", "Bc.ctypes.data", "ldb", "X.ctypes.data",
-            "max(X.shape[0], 1)", "int(x0 is not None)", "float(rtol)", "int(maxiter)", "iters.ctypes.data", "relres.ctypes.data", "reason.ctypes.data",
-            "pc"]
-    assert passed == want
-    assert "pc = capi.precond_code(precond)" in py and py.index("pc = capi.precond_code(precond)") < py.index("lib.otmb_op_solve_pc(")
-    assert "if rc != capi.NOT_CONVERGED:" in py  # likewise: reported, not raised
+def test_python_makes_the_same_call(monkeypatch):
+    from otmb_amd import api
+
+    # no decorator: this signature is the one help() shows
+    assert str(inspect.signature(api.DeviceOperator.solve)) == SIGNATURES["solve"] and not hasattr(api.DeviceOperator.solve, "__wrapped__")
+    D, rec = host_operator(monkeypatch, rc=19)
+    B, d = np.asfortranarray(np.ones((N, K))), np.arange(1.0, N + 1)
+    for given, sent in CASES:  # (adjoint and the precond code differ in each: neither can stand in the other's place)
+        X, info = D.solve(B, d=d, sigma=0.125, **only(given, "adjoint", "precond", "rtol", "maxiter"))
+        a = the_call(rec, "otmb_op_solve_pc")  # one call, one route: the preconditioner is an argument
+        assert list(a) == C_ORDER + ["precond"] and len(a) == 16  # the values, place by place, in the header's order
+        has(a, k=K, d=d.ctypes.data, sigma=0.125, B=B.ctypes.data, ldb=N, X=X.ctypes.data, ldx=N, use_x0=0, iters=info.iterations.ctypes.data,
+            relres=info.relres.ctypes.data, **only(sent, "adjoint", "precond", "rtol", "maxiter"))
+        assert a["op"] is D._h and info.status == 19 and D.ctx.checked == []  # likewise: reported, not raised
     # no second route beside solve (the twin method was _solve_pc: the name may only occur as the tail of the C symbol's)
-    for gone in (r"_precond_keyword", r"(?<!otmb_op)_solve_pc", r"lib\.otmb_op_solve\("):
-        assert not re.search(gone, API), gone
+    for gone in (r"_precond_keyword", r"(?<!otmb_op)_solve_pc", r"lib\.otmb_op_solve\(", r"\"otmb_op_solve\""):
+        assert not re.search(gone, API + CALLS), gone
     # the same defaults on both sides
     assert "rtol::Real = 1e-10, maxiter::Integer = 10000" in SHIM
     assert "precond::Symbol = :jacobi)" in SHIM[SHIM.index("function solve!("):SHIM.index("function solve!(") + 500]

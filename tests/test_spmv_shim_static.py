@@ -21,7 +21,7 @@ def _jl(name):
 
 
 def _py_method(name):
-    cls = API[API.index("\nclass DeviceOperator:"):]
+    cls = API[API.index("\nclass DeviceOperator("):]
     cls = cls[:re.search(r"\n(?:def |class )", cls[1:]).start() + 1]
     m = re.search(r"\n    def " + name + r"\(.*?(?=\n    def |\Z)", cls, re.S)
     assert m, name

@@ -1,12 +1,15 @@
 """CPU: the observations' entry points (otmb_op_observe, otmb_op_step_obs and the _dev variants) have the same types in the same order in the
 C prototypes (include/otmb.h), the ctypes mirror and the Julia shim's ccalls; the first 19 arguments of otmb_op_step_obs are otmb_op_step's;
-the shim exports its two new functions; and the Python bindings reach the new entries through private methods only when a new keyword is
-given, so step's own call site stays as tests/test_step_shim_static.py reads it."""
+the shim exports its two new functions; and the Python bindings reach the new entries only when a new keyword is given, so step's own call
+stays as tests/test_step_shim_static.py reads it."""
+import inspect
 import re
 
+import numpy as np
+from operator_calls_rec import CASES, K, N, SIGNATURES, has, host_operator, the_call
 from test_julia_shim_static import ctypes_kind, header_prototypes, split_top
-from test_solve_shim_static import API, CODE, _header_names
-from test_step_shim_static import STEP_ORDER, _ccall, _method
+from test_solve_shim_static import API, CALLS, CODE, _header_names
+from test_step_shim_static import STEP_ORDER, _ccall
 
 OBSERVE_ORDER = ["op", "k", "q", "W", "ldw", "X", "ldx", "obs"]
 STEP_OBS_ORDER = STEP_ORDER + ["q", "W", "ldw", "obs", "tw", "Xbar", "ldm"]
@@ -58,37 +61,37 @@ def test_the_shim_exports_and_calls_them_with_the_headers_types_and_order():
     assert re.findall(r"sym\(:(otmb_\w+)\)", _ccall("step!", "step_fn")[0]) == ["otmb_op_step"]
 
 
-def test_python_reaches_the_new_entries_through_private_methods():
-    from otmb_amd import capi
+def test_python_reaches_the_new_entries_only_when_a_keyword_is_given(monkeypatch):
+    from otmb_amd import api, device, operator_calls
 
-    dev = open(capi.__file__.replace("capi.py", "device.py"), encoding="utf-8").read()
-    assert re.findall(r"lib\.(otmb_\w+)\(", _method("step")) == ["otmb_op_step"]
-    obs = _method("_step_obs")
-    assert re.findall(r"lib\.(otmb_\w+)\(", obs) == ["otmb_op_step_obs"]
-    call = obs[obs.index("lib.otmb_op_step_obs(") + len("lib.otmb_op_step_obs("):]
-    passed = split_top(" ".join(call[:call.index("max(n, 1))") + len("max(n, 1)")].split()))
-    plain = _method("step")
-    plain = plain[plain.index("lib.otmb_op_step(") + len("lib.otmb_op_step("):]
-    assert passed[:19] == split_top(" ".join(plain[:plain.index("reason.ctypes.data)") + len("reason.ctypes.data")].split()))
-    assert passed[19:] == ["q", "None if Wc is None else Wc.ctypes.data", "ldw", "None if obs is None else obs.ctypes.data",
-                           "None if tw is None else tw.ctypes.data", "None if mean is None else mean.ctypes.data", "max(n, 1)"]
-    assert re.findall(r"lib\(\)\.(otmb_\w+)\(", _method("observe")) == ["otmb_op_observe"]
-    assert "    @capi.observe_keywords\n    def step(self, X, *, dt," in API and "    @capi.observe_keywords\n    def step(self, X, *, dt," in dev
-    for text, plain_sym, obs_sym, one in ((dev, "otmb_op_step_dev", "otmb_op_step_obs_dev", "otmb_op_observe_dev"),):
-        assert len(re.findall(r"self\.lib\." + plain_sym + r"\(", text)) == 1 and len(re.findall(r"self\.lib\." + obs_sym + r"\(", text)) == 1
-        assert len(re.findall(r"self\.lib\." + one + r"\(", text)) == 1
-    # the keywords' switch: neither keyword is the plain method as it stands
-    calls = []
-
-    class Probe:
-        @capi.observe_keywords
-        def step(self, X, **kw):
-            calls.append(("plain", kw))
-
-        def _step_obs(self, X, observe, weights, **kw):
-            calls.append(("obs", observe, weights, kw))
-
-    Probe().step(0, dt=1.0)
-    Probe().step(0, dt=1.0, observe="W")
-    Probe().step(0, dt=1.0, time_weights="w")
-    assert calls == [("plain", {"dt": 1.0}), ("obs", "W", None, {"dt": 1.0}), ("obs", None, "w", {"dt": 1.0})]
+    dev = open(device.__file__, encoding="utf-8").read()
+    D, rec = host_operator(monkeypatch, rc=19)
+    X, W, tw = np.asfortranarray(np.ones((N, K))), np.asfortranarray(np.ones((N + 2, 2)))[:N], np.array([0.25, 0.75])
+    for given, sent in CASES:  # (adjoint and the precond code differ in each)
+        D.step(X, nsteps=2, **given)
+        plain = the_call(rec, "otmb_op_step")  # neither keyword: the plain call as tests/test_step_shim_static.py reads it
+        has(plain, k=K, nsteps=2, **sent)
+        Xn, info = D.step(X, nsteps=2, observe=W, time_weights=tw, **given)
+        a = the_call(rec, "otmb_op_step_obs")
+        assert list(a) == STEP_OBS_ORDER and list(a)[:19] == list(plain)
+        scalars = [n for n in STEP_ORDER if n not in ("op", "X", "steps_done", "iters", "relres", "reason")]  # (each call has its own state and reports)
+        assert [a[n] for n in scalars] == [plain[n] for n in scalars] and a["op"] is plain["op"] is D._h and a["X"] == Xn.ctypes.data
+        has(a, q=2, W=W.ctypes.data, ldw=N + 2, tw=tw.ctypes.data, ldm=N)
+        assert a["obs"] is not None and a["Xbar"] is not None and info.observations.shape == (0, K, 2) and info.status == 19 and D.ctx.checked == []
+        # the keywords' switch: either keyword is the observed call, with null for the other's arrays
+        D.step(X, nsteps=2, observe=np.ones(N), **given)
+        a = the_call(rec, "otmb_op_step_obs")
+        has(a, q=1, ldw=N, tw=None, Xbar=None, ldm=N)
+        assert a["W"] is not None and a["obs"] is not None
+        _, info = D.step(X, nsteps=2, time_weights=tw, **given)
+        a = the_call(rec, "otmb_op_step_obs")
+        has(a, q=0, W=None, ldw=N, obs=None, tw=tw.ctypes.data, ldm=N)
+        assert a["Xbar"] is not None and info.observations is None
+    obs = D.observe(W, X)
+    has(the_call(rec, "otmb_op_observe"), k=K, q=2, W=W.ctypes.data, ldw=N + 2, X=X.ctypes.data, ldx=N, obs=obs.ctypes.data)
+    # both classes take the keywords in step's own signature and make these calls with the one method: device.Operator's reach the _dev exports
+    for cls, suffix in ((api.DeviceOperator, ""), (device.Operator, "_dev")):
+        assert cls.step is operator_calls.OperatorCalls.step and cls.observe is operator_calls.OperatorCalls.observe and cls._suffix == suffix
+        assert str(inspect.signature(cls.step)) == SIGNATURES["step"] and not hasattr(cls.step, "__wrapped__")
+    for name in ("otmb_op_step", "otmb_op_step_obs", "otmb_op_observe"):  # each export is named once, its suffix the class's
+        assert len(re.findall('"' + name + '"', CALLS)) == 1 and '"' + name not in API + dev, name

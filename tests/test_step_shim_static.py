@@ -2,8 +2,11 @@
 otmb_op_step and the _dev variants) have the same types in the same order in the C prototypes (include/otmb.h), the ctypes mirror and the
 Julia shim's ccalls, and the shim and api.DeviceOperator hand the same values over in the same places (the Python side is what the GPU
 tests execute)."""
+import inspect
 import re
 
+import numpy as np
+from operator_calls_rec import CASES, K, N, SIGNATURES, has, host_operator, the_call
 from test_julia_shim_static import SHIM, ctypes_kind, header_prototypes, julia_kind, split_top
 from test_solve_shim_static import API, CODE, _header_names, _jl
 
@@ -86,24 +89,27 @@ def test_the_ccalls_have_the_prototypes_and_the_argument_order_of_the_header():
 
 
 def _method(name):
-    cls = API[API.index("\nclass DeviceOperator:"):]
+    cls = API[API.index("\nclass DeviceOperator("):]
     m = re.search(r"\n    def " + name + r"\(self.*?(?=\n    (?:def |@))", cls, re.S)
     assert m, name
     return m.group(0)
 
 
-def test_python_makes_the_same_calls():
-    py = _method("step")
-    assert '\n    def step(self, X, *, dt, theta=1.0, nsteps=1, first_slot=0, source=None, d=None, rtol=1e-10, maxiter=10000, adjoint=False, ' \
-           'precond="jacobi"):' in py
-    assert re.findall(r"lib\.(otmb_\w+)\(", py) == ["otmb_op_step"]
-    call = py[py.index("lib.otmb_op_step(") + len("lib.otmb_op_step("):]
-    passed = split_top(" ".join(call[:call.index("reason.ctypes.data)") + len("reason.ctypes.data")].split()))
-    assert passed == ["self._h", "int(bool(adjoint))", "k", "None if dc is None else dc.ctypes.data", "float(dt)", "float(theta)", "int(nsteps)",
-                      "int(first_slot)", "None if Sc is None else Sc.ctypes.data", "lds", "Xn.ctypes.data", "max(Xn.shape[0], 1)", "float(rtol)",
-                      "int(maxiter)", "pc", "C.byref(done)", "iters.ctypes.data", "relres.ctypes.data", "reason.ctypes.data"]
-    assert len(passed) == len(STEP_ORDER)
-    assert "pc = capi.precond_code(precond)" in py and "if rc != capi.NOT_CONVERGED:" in py
+def test_python_makes_the_same_calls(monkeypatch):
+    from otmb_amd import api
+
+    assert str(inspect.signature(api.DeviceOperator.step)) == SIGNATURES["step"]
+    D, rec = host_operator(monkeypatch, rc=19)
+    X, d = np.asfortranarray(np.ones((N, K))), np.arange(1.0, N + 1)
+    S = np.asfortranarray(np.ones((N + 2, K)))[:N]
+    for given, sent in CASES:  # (adjoint and the precond code differ in each, and no two integers of a call are equal)
+        Xn, info = D.step(X, nsteps=2, source=S, d=d, **given)
+        a = the_call(rec, "otmb_op_step")
+        assert list(a) == STEP_ORDER
+        has(a, k=K, d=d.ctypes.data, nsteps=2, S=S.ctypes.data, lds=N + 2, X=Xn.ctypes.data, ldx=N, iters=info.iterations.ctypes.data,
+            relres=info.relres.ctypes.data, **sent)
+        assert a["op"] is D._h and a["X"] != X.ctypes.data and np.array_equal(Xn, X)  # the steps run on a copy
+        assert info.status == 19 and D.ctx.checked == []  # reported, not raised
     for name, sym in (("set_slots", "otmb_op_set_slots"), ("select", "otmb_op_select_slot"), ("slots", "otmb_op_slots"),
                       ("_set_slot_values", "otmb_op_set_values_slot")):
         assert re.findall(r"lib\(\)\.(otmb_\w+)\(", _method(name)) == [sym], name
