@@ -7,6 +7,7 @@ All arrays are flat torch tensors whose memory is Julia's column-major (nx,ny,nz
 import ctypes as C
 import os
 import weakref
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -140,8 +141,7 @@ class Operator(OperatorCalls):
     def mul(self, X, *, alpha=1.0, beta=0.0, Y=None, adjoint=False):
         """X: 1-D or 2-D (rows x k, column-major) float64 device tensor; Y: None (a new tensor; β must be 0) or a tensor of the result's
         shape, updated in place.  Enqueued on the context's stream; nothing travels to the host."""
-        if not self._h.value:
-            raise ValueError("operator is closed")
+        self._live()
         _on_device(X, self.device, "X")
         if Y is not None:
             _on_device(Y, self.device, "Y")
@@ -168,8 +168,7 @@ class Operator(OperatorCalls):
     def set_lines(self, next):
         """The lines of the "lines" preconditioner (otmb_op_set_lines_dev): a contiguous int64 device tensor of n entries, next[i] the 1-based
         successor of unknown i + 1 on its line or 0; None clears them.  Copied: the tensor may go afterwards."""
-        if not self._h.value:
-            raise ValueError("operator is closed")
+        self._live()
         if next is None:
             self.ctx.check(self.lib.otmb_op_set_lines_dev(self._h, None))
             return
@@ -197,11 +196,44 @@ class Operator(OperatorCalls):
             pass
 
 
+class _Snapshot:
+    """The single definition of "unchanged since": `same` tensors recorded by identity (a weak reference: a recycled address is another
+    tensor) and by (data_ptr, _version) -- any in-place torch op bumps _version; `also` tensors by (data_ptr, _version) alone; `values`
+    by equality.  The kept promises and the operator records are snapshots, compared with what a call is about to be handed."""
+    __slots__ = ("refs", "key")
+
+    def __init__(self, same, also=(), values=()):
+        self.refs = [weakref.ref(t) for t in same]
+        self.key = self._key(same, also, values)
+
+    @staticmethod
+    def _key(same, also, values):
+        return tuple((t.data_ptr(), t._version) for t in (*same, *also)) + tuple(values)
+
+    def same_objects(self, same):  # (the recorded tensors themselves, whatever torch did to them since)
+        return len(same) == len(self.refs) and all(r() is t for r, t in zip(self.refs, same))
+
+    def matches(self, same, also=(), values=()):
+        return self.same_objects(same) and self.key == self._key(same, also, values)
+
+
+@dataclass
+class OpRecord:
+    """A resident operator over one of the assembler's result matrices and what is known of that result since the operator was planned."""
+    op: object
+    snapshot: _Snapshot = None  # the result's (colptr, rowval) as planned
+    nzv: _Snapshot = None  # the result's (nzval,) as the operator last read it
+    ok: bool = True  # every call since the plan left the pattern in place (_ops_written)
+    dirty: bool = False  # the values were written since the operator read them
+    pattern: tuple = None  # keep_slot's copy of (colptr, rowval[:nnz]): compared where `ok` cannot vouch
+
+
 class DeviceAssembler:
     """Holds one grid (gridmetrics + indices + parameters) in HBM and assembles transport matrices
     for successive (umo, vmo) fields -- the TMIP workflow of building T for many time slices."""
 
     def __init__(self, device=0):
+        self._init_state()
         if not torch.cuda.is_available():
             raise RuntimeError("DeviceAssembler needs a GPU (no CPU fallback)")
         self.device = torch.device("cuda", device)
@@ -209,14 +241,34 @@ class DeviceAssembler:
         self.ctx = capi.Context(device)
         self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
         self.lib = capi.lib()
-        self.out = None
+
+    def _init_state(self):
+        """Every attribute the bookkeeping reads, at its "nothing yet" (tests that make an assembler without a GPU call this, not __init__)."""
+        # grid (set_grid*, makeindices; _wetflags_version: wet3d._version when wetflags was folded): another grid forgets all but the counters
+        self.shape = self.nx = self.ny = self.nz = self.G = self.N = self.topology = None
+        self.v3d = self.thk = self.area = self.zt = self.mlotst = self.z3d = None
+        self.edge, self.dist, self.dist_edge = [], [], []
+        self.rho, self.rho_scalar, self.kappa, self.upwind = None, 0.0, None, True
+        self.lwet3d = self.lwet = self.wet3d = self.wetflags = self.count_tables = self._wetflags_version = None
+        # given operators (set_given): name -> (colptr, rowval, nzval), what the library's verdicts on them were keyed to; T alone (extension)
+        self.given, self._given_key, self.only_T = {}, None, False
+        # fluxes and mask (facefluxes_async, step_fused_async); _mask_key: the _phi_key the push mask and the tile counts describe, or None
+        self.phi = self.push_mask = self.phi_top = self._mask_key = None
         # facefluxes also accumulates the tile counts of the transportmatrix that follows (otmb_facefluxes_counts_dev); False: the plain
         # kernel + the whole push mask + a counting pass, as before round 5 (A/B, and tests that look at the mask itself)
         self.count_in_ff = os.environ.get("OTMB_COUNT_IN_FF", "1") != "0"
-        arena_gb = float(os.environ.get("OTMB_ARENA_GB", "0"))
-        if arena_gb > 0 and os.environ.get("OTMB_ARENA_WHEN", "start") == "start":  # (see _empty)
-            _arena = torch.empty(int(arena_gb * 2 ** 30), dtype=torch.uint8, device=self.device)
-            del _arena
+        # pipeline sequence (_note, finish): the asynchronous calls not yet drained, each kind's numbers in the one sequence
+        self._seq, self._ff_pending, self._ff_seq, self._tm_seq, self._ff_seq_drained = 0, 0, [], [], []
+        # results: the output set of the last call, its capacities when made by new_output_set (None: sized by fill()), nnz, the two-phase plan
+        self.out, self._out_cap, self.nnz, self._plan_kept = None, None, None, (None, ())
+        # kept promises (_kept_ops / _kept_written): snapshots taken when a call was accepted, None: no promise; what the last call promised
+        self._kept_on = os.environ.get("OTMB_KEPT", "1") != "0"  # (OTMB_KEPT=0: A/B)
+        self._kept = self._tpat = self._rho_kept = None
+        self._kept_last, self._tpat_last, self._tpat_fills0 = (), False, None
+        # resident operators (operator, keep_slot): matrix name -> OpRecord, the output set the last accepted call wrote
+        self._ops, self._op_last_out = {}, None
+        # counters: operators handed out again, operators planned
+        self.op_reuses = self.op_replans = 0
 
     def _t(self, a, dtype=np.float64):
         h = torch.from_numpy(_flat(a, dtype))
@@ -225,28 +277,8 @@ class DeviceAssembler:
         return d
 
     def _empty(self, n, dtype):
-        """Device array of n elements.  Placement experiments (profiles/r04/README.md section 8; tools/placement_search.sh):
-        OTMB_ARENA_GB=<GB> reserves one block when the assembler is created and hands it back to torch's caching allocator, so
-        that every later array is carved out of that ONE device allocation, back to back; OTMB_ARENA_ALIGN=<bytes> rounds every
-        array's size up to a multiple (array starts on that grid), OTMB_ARENA_PAD=<bytes> leaves a gap behind every array.
-        OTMB_STAGGER=<bytes> (round 3, tools/placement_study.py) starts the k-th array k*stagger bytes into its allocation."""
-        stagger = int(os.environ.get("OTMB_STAGGER", "0"))
-        align = int(os.environ.get("OTMB_ARENA_ALIGN", "0"))
-        gap = int(os.environ.get("OTMB_ARENA_PAD", "0"))
-        item = torch.empty(0, dtype=dtype).element_size()
-        if align > 0 or gap > 0:
-            nbytes = max(n * item, 1)
-            if align > 0:
-                nbytes = (nbytes + align - 1) // align * align
-            raw = torch.empty(nbytes + gap, dtype=torch.uint8, device=self.device)
-            return raw[: n * item].view(dtype)
-        if stagger <= 0:
-            return torch.empty(n, dtype=dtype, device=self.device)
-        self._nalloc = getattr(self, "_nalloc", 0) + 1
-        pad = (self._nalloc * stagger) % (1 << 21)
-        pad -= pad % 256
-        raw = torch.empty(n * item + pad, dtype=torch.uint8, device=self.device)
-        return raw[pad:pad + n * item].view(dtype)
+        """Device array of n elements (tools/placement_alloc.py overrides this for the placement experiments)."""
+        return torch.empty(n, dtype=dtype, device=self.device)
 
     # ---- grid ---------------------------------------------------------------------------------
     def set_grid(self, gridmetrics, mlotst, rho, kappaH=500.0, kappaVML=0.1, kappaVdeep=1.0e-5, upwind=True):
@@ -342,7 +374,7 @@ class DeviceAssembler:
         counted -- its values are re-derived in registers or read where they lie (those of another κ included: ctx.given_state(m) == 3);
         any other matrix makes T a device sparse add (two-phase protocol only: transportmatrix(); the asynchronous calls raise
         GIVEN_FOREIGN)."""
-        given = dict(getattr(self, "given", {}) or {})
+        given = dict(self.given)
         for name, triple in ops.items():
             if name not in MATS[1:]:
                 raise ValueError(f"{name}: not an operator of transportmatrix")
@@ -378,11 +410,21 @@ class DeviceAssembler:
         self.N = int(n.value)
         # the five wet bytes nofluxboundaries! reads per cell and level, folded into one (otmb_wetflags_dev): once per grid
         self.wetflags = torch.empty(self.G, dtype=torch.uint8, device=self.device)
+        self._wetflags_version = None
+        self._fold_wet_mask(tables=True)
+        return self.N
+
+    def _fold_wet_mask(self, tables):
+        """Fold wet3d into wetflags again when it is new or was edited in place since the last fold (tests do); tables: the count tables are
+        then built again as well.  makeindices and step_fused_async ask for that, facefluxes_async does not and never did: whether its counts
+        should follow an edited mask is an open question, and the asymmetry is left as it was found."""
+        if self.wet3d._version == self._wetflags_version:
+            return
         self.ctx.check(self.lib.otmb_wetflags_dev(self.ctx.handle, self.wet3d.data_ptr(), self.nx, self.ny, self.nz, self.topology,
                                                   self.wetflags.data_ptr()))
         self._wetflags_version = self.wet3d._version
-        self._count_tables()
-        return self.N
+        if tables:
+            self._count_tables()
 
     def _count_tables(self):
         """Counts in facefluxes (otmb_facefluxes_counts_dev), once per grid: the wet rank at which every 64-cell wave segment starts and the
@@ -404,16 +446,13 @@ class DeviceAssembler:
         """Same kernel, no host round trip: the "all values missing" assertion is evaluated by finish().  The
         kernel also writes the push mask of these fluxes (include/otmb.h), which lets the counting pass of the
         following transportmatrix skip the six ϕ arrays."""
-        if getattr(self, "phi", None) is None:
+        if self.phi is None:
             self.phi = [self._empty(self.G, torch.float64) for _ in range(6)]
             self.push_mask = self._empty(self.G, torch.int16)
         ptrs = capi.ptr_array(6, [p.data_ptr() for p in self.phi])
         self._mask_key = None
-        self._note("_ff_seq")
-        if self.wet3d._version != self._wetflags_version:  # the mask was edited in place (tests do): fold it again
-            self.ctx.check(self.lib.otmb_wetflags_dev(self.ctx.handle, self.wet3d.data_ptr(), self.nx, self.ny, self.nz, self.topology,
-                                                      self.wetflags.data_ptr()))
-            self._wetflags_version = self.wet3d._version
+        self._note(self._ff_seq)
+        self._fold_wet_mask(tables=False)
         # The kernel also accumulates the tile counts of the transportmatrix these fluxes will be handed to (same mlotst, weighting, indices):
         # that call then has no counting pass.  (The library falls back to the plain kernel where it cannot count: nx < 3, OTMB_COUNT_IN_FF=0.)
         if not self.count_in_ff:
@@ -426,7 +465,7 @@ class DeviceAssembler:
         cnt = capi.FfCounts()
         cnt.tables, cnt.lwet3d = self.count_tables.data_ptr(), self.lwet3d.data_ptr()
         cnt.mlotst, cnt.zt, cnt.n_wet = self.mlotst.data_ptr(), self.zt.data_ptr(), self.N
-        cnt.upwind, cnt.only_t = int(self.upwind), 1 if getattr(self, "only_T", False) else 0
+        cnt.upwind, cnt.only_t = int(self.upwind), 1 if self.only_T else 0
         self.ctx.check(self.lib.otmb_facefluxes_counts_dev(self.ctx.handle, umo.data_ptr(), vmo.data_ptr(),
                                                            int(umo.dtype == torch.float32), self.wetflags.data_ptr(), float(fill),
                                                            self.nx, self.ny, self.nz, self.topology, C.byref(ptrs),
@@ -434,19 +473,17 @@ class DeviceAssembler:
         self._mask_key = self._phi_key(self.phi)
         return self.phi
 
-    def _note(self, which):
-        """Asynchronous calls of both kinds are numbered in one sequence, so that finish() can tell which of a facefluxes
-        failure (counted among facefluxes calls) and a transportmatrix failure (counted among transportmatrix calls) came
+    def _note(self, calls):
+        """Asynchronous calls of both kinds (calls: _ff_seq or _tm_seq) are numbered in one sequence, so that finish() can tell which of a
+        facefluxes failure (counted among facefluxes calls) and a transportmatrix failure (counted among transportmatrix calls) came
         FIRST even when the two kinds of call were not issued in pairs."""
-        self._seq = getattr(self, "_seq", 0) + 1
-        if not hasattr(self, which):
-            setattr(self, which, [])
-        getattr(self, which).append(self._seq)
+        self._seq += 1
+        calls.append(self._seq)
 
     def _phi_key(self, phi):
         # the mask (and the tile counts that came with it) describes exactly the values facefluxes wrote, and the mixed-layer inputs and
         # weighting it was told: any later in-place torch op bumps _version
-        return tuple((p.data_ptr(), p._version) for p in (*phi, self.mlotst, self.zt)) + (bool(self.upwind), bool(getattr(self, "only_T", False)))
+        return tuple((p.data_ptr(), p._version) for p in (*phi, self.mlotst, self.zt)) + (bool(self.upwind), bool(self.only_T))
 
     PIPELINE_DEPTH = 60  # the library remembers the verdicts of its 64 most recent asynchronous calls: drain before that
 
@@ -457,7 +494,7 @@ class DeviceAssembler:
         u, v, n = (C.c_int32 * cap)(), (C.c_int32 * cap)(), C.c_int32(0)
         self.ctx.check(self.lib.otmb_facefluxes_pending_flags(self.ctx.handle, cap, u, v, C.byref(n)))
         self._ff_pending = 0
-        self._ff_seq_drained, self._ff_seq = getattr(self, "_ff_seq", [])[-n.value:] if n.value else [], []
+        self._ff_seq_drained, self._ff_seq = self._ff_seq[-n.value:] if n.value else [], []
         for q in range(n.value):
             if not (u[q] and v[q]):
                 return q, n.value
@@ -479,42 +516,36 @@ class DeviceAssembler:
         """Enqueue one pass of the hot path (facefluxes -> count -> scan -> fill) without any host synchronisation;
         successive calls pipeline on the stream.  finish() synchronises and raises what the FIRST failing pass found
         (every pass keeps its own error flags on the device; OtmbError.step is its index)."""
-        if getattr(self, "_ff_pending", 0) >= self.PIPELINE_DEPTH:
-            self.finish()
+        self._make_room()
         out = self.transportmatrix_onepass(self.facefluxes_async(umo, vmo, fill), sync=False)
-        self._ff_pending = getattr(self, "_ff_pending", 0) + 1
+        self._ff_pending += 1
         return out
+
+    def _make_room(self):  # (drain before a step that would make the pipeline deeper than the library's memory of verdicts)
+        if self._ff_pending >= self.PIPELINE_DEPTH:
+            self.finish()
 
     def step_fused_async(self, umo, vmo, fill, out=None):
         """Extension (otmb_step_dev): one pass from (umo, vmo) to the five matrices WITHOUT the six ϕ arrays in memory -- only ϕtop is stored,
         the fill pass re-derives the other five fluxes from umo / vmo where it uses them.  The same matrices bit for bit as step_async, 64
         bytes per cell less HBM traffic.  Not the drop-in path: facefluxesfrommasstransport returns the six arrays."""
-        if getattr(self, "_ff_pending", 0) >= self.PIPELINE_DEPTH:
-            self.finish()
-        if getattr(self, "phi_top", None) is None:
+        self._make_room()
+        if self.phi_top is None:
             self.phi_top = self._empty(self.G, torch.float64)
-        if out is None and (self.out is None or getattr(self, "_out_cap", None) is None):
-            self.out = self.new_output_set()
-            self._out_cap = [self.N * k + 1 for k in self.PER_COLUMN_MAX]
-        if out is None:
-            out = self.out
-        if self.wet3d._version != self._wetflags_version:
-            self.ctx.check(self.lib.otmb_wetflags_dev(self.ctx.handle, self.wet3d.data_ptr(), self.nx, self.ny, self.nz, self.topology,
-                                                      self.wetflags.data_ptr()))
-            self._wetflags_version = self.wet3d._version
-            self._count_tables()
+        out = self._output_set(out)
+        self._fold_wet_mask(tables=True)
         self._mask_key = None
         a = self._args([self.phi_top] * 6)
         a.kept_ops, kept = self._kept_ops(out)
         cp, rv, nz = self._out_ptrs(out)
-        caps = (C.c_int64 * 5)(*[self.N * k + 1 for k in self.PER_COLUMN_MAX])
-        self._note("_ff_seq")
+        caps = (C.c_int64 * 5)(*self._capacities())
+        self._note(self._ff_seq)
         self._check(self.lib.otmb_step_dev(self.ctx.handle, umo.data_ptr(), vmo.data_ptr(), int(umo.dtype == torch.float32), float(fill),
                                            self.wetflags.data_ptr(), self.count_tables.data_ptr(), self.phi_top.data_ptr(), C.byref(a),
                                            C.byref(cp), C.byref(rv), C.byref(nz), C.byref(caps)))
         self._kept_written(out, kept)
-        self._note("_tm_seq")
-        self._ff_pending = getattr(self, "_ff_pending", 0) + 1
+        self._note(self._tm_seq)
+        self._ff_pending += 1
         return out
 
     def finish(self):
@@ -522,7 +553,7 @@ class DeviceAssembler:
         the reference (facefluxes runs before transportmatrix)."""
         bad, n = self._first_missing()
         ff_seq = self._ff_seq_drained
-        tm_seq, self._tm_seq = getattr(self, "_tm_seq", []), []
+        tm_seq, self._tm_seq = self._tm_seq, []
         err = None
         try:
             out = self.result()
@@ -557,10 +588,10 @@ class DeviceAssembler:
         a.area2d, a.zt, a.mlotst = self.area.data_ptr(), self.zt.data_ptr(), self.mlotst.data_ptr()
         a.kappa_h, a.kappa_vml, a.kappa_vdeep = self.kappa
         # ϕ straight from this object's facefluxes and untouched since: hand over its push mask
-        fresh = getattr(self, "_mask_key", None) is not None and self._mask_key == self._phi_key(phi)
+        fresh = self._mask_key is not None and self._mask_key == self._phi_key(phi)
         a.push_mask = self.push_mask.data_ptr() if fresh else None
-        a.only_t = 1 if getattr(self, "only_T", False) else 0  # extension: materialise T alone (outputs of the operators unused)
-        if getattr(self, "given", None):
+        a.only_t = 1 if self.only_T else 0  # extension: materialise T alone (outputs of the operators unused)
+        if self.given:
             for m, name in enumerate(MATS):
                 if name in self.given:
                     cp, rv, nz = self.given[name]
@@ -573,7 +604,7 @@ class DeviceAssembler:
 
     def _out_ptrs(self, out):
         """The three pointer arrays of an output set; NULL for an operator the caller passes (nothing of it is written)."""
-        skip = set(getattr(self, "given", None) or ())
+        skip = set(self.given)
         return tuple(capi.ptr_array(5, [None if m in skip else out[m][q].data_ptr() for m in MATS]) for q in range(3))
 
     # ---- kept operators (otmb_tm_args.kept_ops) ---------------------------------------------------------------------------------------------
@@ -584,67 +615,41 @@ class DeviceAssembler:
 
     def _forget_kept(self):
         """The next call writes all five matrices (grid, κ, given operators changed; outputs overwritten; an error)."""
-        self._kept = None
-        self._kept_last = ()
-        self._tpat = None
-        self._tpat_last = False
-        self._rho_kept = None
-        for rec in getattr(self, "_ops", {}).values():  # (and no operator's pattern can be vouched for any more)
-            rec["ok"] = False
+        self._kept = self._tpat = self._rho_kept = None
+        self._kept_last, self._tpat_last = (), False
+        for rec in self._ops.values():  # (and no operator's pattern can be vouched for any more)
+            rec.ok = False
+
+    def _kept_inputs(self, out):
+        # the output set's nine tensors (by identity: a recycled address is another set), every grid array the three operators are derived from, κ
+        same = [t for m in self.KEPT for t in out[m]]
+        grid = [self.lwet3d, self.lwet, self.v3d, self.thk, self.area, self.zt, self.mlotst, *self.edge, *self.dist]
+        return same, grid, self.kappa
 
     # T's pattern (OTMB_KEPT_T_PATTERN) is a function of the wet mask and the topology alone: when T's colptr / rowval tensors are the ones the
     # library last wrote, untouched by torch since, a step that keeps the three operators adds the bit and the fill stores T's values only (the
-    # library checks its own record as well).  Tracked apart from _kept / _kept_last.
-    def _tpat_key(self, out):
-        ts = out["T"][:2]
-        return [weakref.ref(t) for t in ts], tuple((t.data_ptr(), t._version) for t in ts)
-
-    def _tpat_promise(self, out):
-        rec = getattr(self, "_tpat", None)
-        if rec is None:
-            return False
-        refs, key = self._tpat_key(out)
-        return rec[1] == key and all(r() is t() for r, t in zip(rec[0], refs))
-
+    # library checks its own record as well).  Tracked apart from _kept / _kept_last: the snapshot _tpat of out["T"][:2].
     # ρ is no grid constant and none of the kept operators' keys, so the library cannot know that it is unchanged: OTMB_KEPT_RHO says that the
     # ρ tensor is the one, at the version, of the last accepted call (by identity: a recycled address is another tensor).  The kept fill then
     # takes v3D and ρ from a table it builds once; a loop whose ρ changes every step never makes the promise and never builds it.
-    def _rho_key(self):
-        rho = getattr(self, "rho", None)
-        return None if rho is None else (weakref.ref(rho), (rho.data_ptr(), rho._version))
-
-    def _rho_promise(self):
-        rec, now = getattr(self, "_rho_kept", None), self._rho_key()
-        return rec is not None and now is not None and rec[1] == now[1] and rec[0]() is now[0]()
-
-    def _kept_key(self, out):
-        # the output set's nine tensors (by identity: a recycled address is another set) and every grid array the three operators are derived from
-        ts = [t for m in self.KEPT for t in out[m]]
-        grid = [self.lwet3d, self.lwet, self.v3d, self.thk, self.area, self.zt, self.mlotst, *self.edge, *self.dist]
-        return ([weakref.ref(t) for t in ts], tuple((t.data_ptr(), t._version) for t in ts + grid) + tuple(self.kappa))
-
     def _kept_ops(self, out):
         """kept_ops for a call into `out`, and the names it covers."""
-        self._kept_last = ()
-        self._tpat_last = False
+        self._kept_last, self._tpat_last = (), False
         self._tpat_fills0 = self.ctx.kept_t_pattern_fills()  # (what the library did with the promise: _ops_written compares)
-        rec = getattr(self, "_kept", None)
-        if rec is None or getattr(self, "given", None) or getattr(self, "only_T", False):
+        if self._kept is None or self.given or self.only_T or not self._kept.matches(*self._kept_inputs(out)):
             return 0, ()
-        refs, key = self._kept_key(out)
-        if rec[1] != key or any(r() is not t() for r, t in zip(rec[0], refs)):
-            return 0, ()
-        self._tpat_last = self._tpat_promise(out)
+        self._tpat_last = self._tpat is not None and self._tpat.matches(out["T"][:2])
+        rho = self._rho_kept is not None and self.rho is not None and self._rho_kept.matches((self.rho,))
         return (sum(1 << MATS.index(m) for m in self.KEPT) | (capi.KEPT_T_PATTERN if self._tpat_last else 0)
-                | (capi.KEPT_RHO if self._rho_promise() else 0)), self.KEPT
+                | (capi.KEPT_RHO if rho else 0)), self.KEPT
 
     def _kept_written(self, out, kept):
         """After a call into `out` was accepted: it wrote (or kept) the three operators unless some were given / not wanted."""
         self._kept_last = kept
-        off = getattr(self, "given", None) or getattr(self, "only_T", False) or os.environ.get("OTMB_KEPT", "1") == "0"  # (OTMB_KEPT=0: A/B)
-        self._kept = None if off else self._kept_key(out)
-        self._tpat = None if off else self._tpat_key(out)  # (T's pattern: written by this call, or where the last one left it)
-        self._rho_kept = None if off else self._rho_key()  # (ρ as this call read it: OTMB_KEPT_RHO)
+        off = self.given or self.only_T or not self._kept_on
+        self._kept = None if off else _Snapshot(*self._kept_inputs(out))
+        self._tpat = None if off else _Snapshot(out["T"][:2])  # (T's pattern: written by this call, or where the last one left it)
+        self._rho_kept = None if off or self.rho is None else _Snapshot((self.rho,))  # (ρ as this call read it: OTMB_KEPT_RHO)
         self._ops_written(out, kept)
 
     # ---- resident operators (otmb_op_*): one per output matrix, re-planned unless its pattern is shown unchanged ----------------------------
@@ -655,47 +660,51 @@ class DeviceAssembler:
         still hold an older fill's answer when the library declined the kept operators); TκH / TκVML / TκVdeep: kept; Tadv never.  (An exact
         cancellation compacts T when the step is folded: operator() compares nnz as well.)"""
         self._op_last_out = out
-        ops = getattr(self, "_ops", None)
-        if not ops:
+        if not self._ops:
             return
-        f0 = getattr(self, "_tpat_fills0", None)
-        tpat = bool(getattr(self, "_tpat_last", False)) and f0 is not None and self.ctx.kept_t_pattern_fills() == f0 + 1
-        for name, rec in ops.items():
-            if not all(r() is t for r, t in zip(rec["refs"], out[name])):
+        f0 = self._tpat_fills0
+        tpat = bool(self._tpat_last) and f0 is not None and self.ctx.kept_t_pattern_fills() == f0 + 1
+        for name, rec in self._ops.items():
+            if not (rec.snapshot.same_objects(out[name][:2]) and rec.nzv.same_objects(out[name][2:])):
                 continue  # another output set: untouched
-            rec["dirty"] = True
+            rec.dirty = True
             if name == "T":
-                rec["ok"] = rec["ok"] and tpat
+                rec.ok = rec.ok and tpat
             else:
-                rec["ok"] = rec["ok"] and name in kept
+                rec.ok = rec.ok and name in kept
 
     def _op_record(self, matrix):
         """What operator() and keep_slot() decide on: (the record of the operator over `matrix` or None, whether its plan holds for the result
-        as it stands, the result's three tensors, their key).  Pending asynchronous steps are folded first (finish()).  A record whose
+        as it stands, the result's three tensors).  Pending asynchronous steps are folded first (finish()).  A record whose
         pattern cannot be vouched for but whose operator carries kept slots is compared with the copy of the pattern keep_slot took."""
-        if getattr(self, "_tm_seq", None):
+        if self._tm_seq:
             self.finish()
         if self.out is None:
             raise ValueError("no resident result: run a step first")
         k = MATS.index(matrix)
         cp, rv, nz = self.out[matrix]
-        if not hasattr(self, "_ops"):
-            self._ops = {}
         rec = self._ops.get(matrix)
-        nnz_now = self.nnz[k] if getattr(self, "_op_last_out", None) is self.out else None
-        key = ((cp.data_ptr(), cp._version), (rv.data_ptr(), rv._version))
-        live = rec is not None and bool(rec["op"].handle.value) and nnz_now is not None and rec["op"].nnz == nnz_now
-        holds = (live and rec["ok"] and all(r() is t for r, t in zip(rec["refs"], (cp, rv, nz))) and rec["key"] == key)
-        if live and not holds and rec.get("pattern") is not None:
+        nnz_now = self.nnz[k] if self._op_last_out is self.out else None
+        live = rec is not None and bool(rec.op.handle.value) and nnz_now is not None and rec.op.nnz == nnz_now
+        holds = live and rec.ok and rec.nzv.same_objects((nz,)) and rec.snapshot.matches((cp, rv))
+        if live and not holds and rec.pattern is not None:
             self.ctx.synchronize()
-            if torch.equal(cp, rec["pattern"][0]) and torch.equal(rv[:nnz_now], rec["pattern"][1]):
-                rec.update(ok=True, dirty=True, key=key, refs=[weakref.ref(t) for t in (cp, rv, nz)])
+            if torch.equal(cp, rec.pattern[0]) and torch.equal(rv[:nnz_now], rec.pattern[1]):
+                # (dirty: whatever nzv says, the values are read again before the operator is handed out)
+                rec.ok, rec.dirty, rec.snapshot, rec.nzv = True, True, _Snapshot((cp, rv)), _Snapshot((nz,))
                 holds = True
-        return rec, holds, (cp, rv, nz), key
+        return rec, holds, (cp, rv, nz)
+
+    def _slotted(self, matrix):
+        """The record of the live operator over `matrix`, for the calls that work on its kept slots."""
+        rec = self._ops.get(matrix)
+        if rec is None or not rec.op.handle.value:
+            raise ValueError(f"no operator over {matrix}: keep_slot() first")
+        return rec
 
     @staticmethod
     def _has_slots(rec):
-        return rec is not None and bool(rec["op"].handle.value) and rec["op"].slots[0] > 1
+        return rec is not None and bool(rec.op.handle.value) and rec.op.slots[0] > 1
 
     def operator(self, matrix="T"):
         """The resident operator over the result `matrix` of this assembler's output set (otmb_op_create_dev), for mul() on device
@@ -704,26 +713,25 @@ class DeviceAssembler:
         asynchronous steps are folded first (finish()).  The assembler owns the operator: it is replaced, not updated, by a re-plan.
         An operator with more than one slot is neither refreshed nor replaced here (either would overwrite or drop kept values): when the
         result is newer than the selected slot this raises, and keep_slot() or forget_slots() says where the result goes."""
-        rec, holds, (cp, rv, nz), key = self._op_record(matrix)
+        rec, holds, (cp, rv, nz) = self._op_record(matrix)
         if holds:
-            if rec["dirty"] or rec["nzv"] != (nz.data_ptr(), nz._version):
+            if rec.dirty or not rec.nzv.matches((nz,)):
                 if self._has_slots(rec):
-                    raise ValueError(f"the operator over {matrix} holds {rec['op'].slots[0]} slots and the result has changed since one was "
+                    raise ValueError(f"the operator over {matrix} holds {rec.op.slots[0]} slots and the result has changed since one was "
                                      "written: keep_slot(slot) puts it into one, forget_slots() drops them")
-                rec["op"].set_values_dev(nz)
-                rec["dirty"], rec["nzv"] = False, (nz.data_ptr(), nz._version)
-            self.op_reuses = getattr(self, "op_reuses", 0) + 1
-            return rec["op"]
+                rec.op.set_values_dev(nz)
+                rec.dirty, rec.nzv = False, _Snapshot((nz,))
+            self.op_reuses += 1
+            return rec.op
         if self._has_slots(rec):
             raise ValueError(f"the pattern of {matrix} changed (or cannot be shown unchanged) under an operator that holds "
-                             f"{rec['op'].slots[0]} slots: forget_slots() drops them, then the operator is planned again")
+                             f"{rec.op.slots[0]} slots: forget_slots() drops them, then the operator is planned again")
         if rec is not None:
-            rec["op"].close()
+            rec.op.close()
         op = Operator(self.ctx, self.N, self.N, cp, rv, nz)
         op.set_lines(self.vertical_lines())
-        self._ops[matrix] = {"op": op, "refs": [weakref.ref(t) for t in (cp, rv, nz)], "key": key, "nzv": (nz.data_ptr(), nz._version),
-                             "ok": True, "dirty": False}
-        self.op_replans = getattr(self, "op_replans", 0) + 1
+        self._ops[matrix] = OpRecord(op, snapshot=_Snapshot((cp, rv)), nzv=_Snapshot((nz,)))
+        self.op_replans += 1
         return op
 
     def vertical_lines(self):
@@ -753,72 +761,63 @@ class DeviceAssembler:
         slots first.  No other slot is written.  Built month by month, this is the year a tracer run cycles through.  The slots live on the
         operator and share its pattern: where the library did not vouch for the pattern, it is compared with a copy taken at the first
         keep_slot, and a result with another pattern raises (operator()) and leaves the slots as they are."""
-        rec, holds, (cp, rv, nz), _ = self._op_record(matrix)
+        rec, holds, (cp, rv, nz) = self._op_record(matrix)
         if not holds:
             self.operator(matrix)  # no operator yet: planned over this result (one with slots and another pattern: raises)
             rec = self._ops[matrix]
-        op = rec["op"]
+        op = rec.op
         n, selected = op.slots
         if not 0 <= int(slot) < max(n, nslots or 0):
             raise ValueError(f"slot {slot} of {max(n, nslots or 0)}")
         if nslots is not None and nslots > n:
             op.set_slots(nslots)
-        if int(slot) != selected or rec["dirty"] or rec["nzv"] != (nz.data_ptr(), nz._version):
+        if int(slot) != selected or rec.dirty or not rec.nzv.matches((nz,)):
             op.set_values_dev(nz, slot=slot)
         op.select(slot)
-        rec["dirty"], rec["nzv"] = False, (nz.data_ptr(), nz._version)
-        if rec.get("pattern") is None:
+        rec.dirty, rec.nzv = False, _Snapshot((nz,))
+        if rec.pattern is None:
             self.ctx.synchronize()
-            rec["pattern"] = (cp.clone(), rv[: op.nnz].clone())
+            rec.pattern = (cp.clone(), rv[: op.nnz].clone())
         return op
 
     def forget_slots(self, matrix="T"):
         """Drop the operator over `matrix` with its slots; the next operator() / keep_slot() plans one over the result as it stands."""
-        rec = getattr(self, "_ops", {}).pop(matrix, None)
+        rec = self._ops.pop(matrix, None)
         if rec is not None:
-            rec["op"].close()
+            rec.op.close()
 
     def step_tracers(self, X, *, matrix="T", **kw):
         """Operator.step on the resident operator over `matrix` (named apart from step(), which builds a matrix): θ-steps of the tracers X
         through the slots keep_slot() filled, as they are -- a result built since and not kept takes no part; precond="lines" uses the
         grid's water columns."""
-        rec = getattr(self, "_ops", {}).get(matrix)
-        if rec is None or not rec["op"].handle.value:
-            raise ValueError(f"no operator over {matrix}: keep_slot() first")
-        return rec["op"].step(X, **kw)
+        return self._slotted(matrix).op.step(X, **kw)
 
     def combine_slots(self, weights, dst, matrix="T"):
         """Operator.combine_slots on the resident operator over `matrix`: slot dst = Σ_s weights[s]·(slot s) over the slots keep_slot() filled
         (the annual mean of the kept months).  The written slot is not the resident result: when it is the selected one, the operator counts
         as changed since the result was put there, so operator() raises until keep_slot() or forget_slots() says where the result goes."""
-        rec = getattr(self, "_ops", {}).get(matrix)
-        if rec is None or not rec["op"].handle.value:
-            raise ValueError(f"no operator over {matrix}: keep_slot() first")
-        op = rec["op"]
-        op.combine_slots(weights, dst)
-        if int(dst) == op.slots[1]:
-            rec["dirty"] = True
-        return op
+        rec = self._slotted(matrix)
+        rec.op.combine_slots(weights, dst)
+        if int(dst) == rec.op.slots[1]:
+            rec.dirty = True
+        return rec.op
 
     def periodic_tracers(self, source, *, matrix="T", **kw):
         """Operator.periodic on the resident operator over `matrix`: the periodic state of the cycle through the slots keep_slot() filled, as
         they are (step_tracers says which slots those are); outer="mean" preconditions the outer iteration with their cycle mean."""
-        rec = getattr(self, "_ops", {}).get(matrix)
-        if rec is None or not rec["op"].handle.value:
-            raise ValueError(f"no operator over {matrix}: keep_slot() first")
-        return rec["op"].periodic(source, **kw)
+        return self._slotted(matrix).op.periodic(source, **kw)
 
     def _kept_steady(self):
         """The operators a step of this loop does not store: those the last call kept, or -- after a full write that left the promise live -- those
         the next call will keep (what every launch after the first one of a time loop writes: bench.py's roofline reads this after its extras)."""
-        return set(getattr(self, "_kept_last", ())) | (set(self.KEPT) if getattr(self, "_kept", None) is not None else set())
+        return set(self._kept_last) | (set(self.KEPT) if self._kept is not None else set())
 
     def _htab_bytes(self, skip):
         """Bytes of the library's TκH table that a fill pass which keeps all three operators (`skip`) reads: five Float64 per wet column.  Such
         a pass does not read thkcello and the eight edge / distance arrays (the tripolar seam row aside: one row of cells).  Whether the table
         is read is the library's answer for the last such fill (otmb_ctx_kept_htab; before the first one: the library's own rule -- nx >= 3
         and OTMB_KEPT_HTAB as this process started).  0: TκH is re-derived from thkcello and the metrics."""
-        if not set(self.KEPT) <= skip or getattr(self, "given", None):
+        if not set(self.KEPT) <= skip or self.given:
             return 0
         used = self.ctx.kept_htab()
         return 40 * self.N if (used == 1 or (used < 0 and self.nx >= 3 and _KEPT_HTAB_ON)) else 0
@@ -828,9 +827,9 @@ class DeviceAssembler:
         time loop's steady state: the promise was made or is live for the next call, the TκH table is read (the library takes the pattern on
         that path only) and OTMB_KEPT_TPAT was not 0 as this process started.  (Whether the last fill took it, otmb_ctx_kept_t_pattern, also
         depends on whether the record's writer has been folded yet: the first steps of a pipeline write T in full.)"""
-        if not set(self.KEPT) <= skip or getattr(self, "given", None) or "T" in skip:
+        if not set(self.KEPT) <= skip or self.given or "T" in skip:
             return False
-        if not (getattr(self, "_tpat_last", False) or getattr(self, "_tpat", None) is not None):
+        if not (self._tpat_last or self._tpat is not None):
             return False
         return _KEPT_TPAT_ON and self._htab_bytes(skip) > 0
 
@@ -843,10 +842,9 @@ class DeviceAssembler:
 
     def plan(self, phi):
         a = self._args(phi)
+        kept = ()
         if self.out is not None:
             a.kept_ops, kept = self._kept_ops(self.out)
-        else:
-            kept = ()
         nnz = (C.c_int64 * 5)()
         self._check(self.lib.otmb_transportmatrix_plan_dev(self.ctx.handle, C.byref(a), C.byref(nnz)))
         self.nnz = [int(x) for x in nnz]
@@ -856,17 +854,14 @@ class DeviceAssembler:
     def fill(self):
         """Write the five CSC matrices into device tensors (allocated once per capacity)."""
         if self.out is None or any(self.out[m][1].numel() < self.nnz[k] for k, m in enumerate(MATS)):
-            phi, kept = getattr(self, "_plan_kept", (None, ()))
+            phi, kept = self._plan_kept
             self._forget_kept()
             if kept:  # (the plan counted on the old arrays of the kept operators: plan again without the promise, then allocate)
                 self.plan(phi)
             self._out_cap = None
-            self.out = {m: (torch.empty(self.N + 1, dtype=torch.int64, device=self.device),
-                            torch.empty(max(self.nnz[k], 1) + self.nnz[k] // 64, dtype=torch.int64, device=self.device),
-                            torch.empty(max(self.nnz[k], 1) + self.nnz[k] // 64, dtype=torch.float64, device=self.device))
-                        for k, m in enumerate(MATS)}
+            self.out = {m: self._csc(self.N, max(z, 1) + z // 64) for m, z in zip(MATS, self.nnz)}
         cp, rv, nz = self._out_ptrs(self.out)
-        kept = getattr(self, "_plan_kept", (None, ()))[1]
+        kept = self._plan_kept[1]
         self._plan_kept = (None, ())
         self._check(self.lib.otmb_transportmatrix_fill_dev(self.ctx.handle, C.byref(cp), C.byref(rv), C.byref(nz)))
         self._kept_written(self.out, kept)
@@ -886,13 +881,25 @@ class DeviceAssembler:
     def new_output_set(self):
         """A set of five CSC output buffers at their upper bound (for transportmatrix_onepass(out=...): a pipeline whose
         steps each keep their own matrices)."""
-        cap = [self.N * k + 1 for k in self.PER_COLUMN_MAX]
-        if os.environ.get("OTMB_ARENA_WHEN") == "outputs" and float(os.environ.get("OTMB_ARENA_GB", "0")) > 0 and not getattr(self, "_arena_done", False):
-            self._arena_done = True  # experiment: only the OUTPUT arrays are carved out of one allocation
-            _arena = torch.empty(int(float(os.environ["OTMB_ARENA_GB"]) * 2 ** 30), dtype=torch.uint8, device=self.device)
-            del _arena
-        return {m: (self._empty(self.N + 1, torch.int64), self._empty(cap[k], torch.int64),
-                    self._empty(cap[k], torch.float64)) for k, m in enumerate(MATS)}
+        return {m: self._csc(self.N, cap) for m, cap in zip(MATS, self._capacities())}
+
+    def _csc(self, cols, cap):
+        """(colptr, rowval, nzval) device arrays of a matrix of `cols` columns with room for `cap` entries."""
+        return self._empty(cols + 1, torch.int64), self._empty(cap, torch.int64), self._empty(cap, torch.float64)
+
+    def _capacities(self):
+        """Entries the five matrices can hold at most, + 1 (the lengths of new_output_set()'s rowval / nzval arrays)."""
+        return [self.N * k + 1 for k in self.PER_COLUMN_MAX]
+
+    def _output_set(self, out):
+        """The output set an asynchronous call writes: `out`, or this object's own at the capacities -- made at the first call, and again
+        where fill() left one sized to its plan."""
+        if out is not None:
+            return out
+        if self.out is None or self._out_cap is None:
+            self.out = self.new_output_set()
+            self._out_cap = self._capacities()
+        return self.out
 
     def choose_placement(self, umo, vmo, fill, candidates=4, reps=3, budget_fraction=0.6, min_output_bytes=4 << 30):
         """Set-up time only, never results: pick WHERE this assembler's flux arrays and output matrices live.
@@ -910,7 +917,7 @@ class DeviceAssembler:
             return rec
         free_b, _ = torch.cuda.mem_get_info(self.device)
         phi_bytes = self.G * (6 * 8 + 2)
-        out_bytes = sum((self.N * k + 1) * 16 + (self.N + 1) * 8 for k in self.PER_COLUMN_MAX)
+        out_bytes = sum(cap * 16 + (self.N + 1) * 8 for cap in self._capacities())
         if out_bytes < min_output_bytes:
             rec["skipped"] = "small grid: placements differ by 1-2 %"
             return rec
@@ -950,7 +957,7 @@ class DeviceAssembler:
             self.result()
         self._forget_kept()
         ko = int(np.argmin(rec["fill_ms"]))
-        self.out, self._out_cap = outs[ko], [self.N * k + 1 for k in self.PER_COLUMN_MAX]
+        self.out, self._out_cap = outs[ko], self._capacities()
         del outs, o
         torch.cuda.empty_cache()  # the candidates that were not kept go back to the driver
         rec["chosen"] = [kp, ko]
@@ -960,19 +967,15 @@ class DeviceAssembler:
         """Asynchronous protocol (otmb_transportmatrix_dev): outputs preallocated at their upper bound, count ->
         scan -> fill enqueued without a host round trip.  With sync=False the nnz/errors are collected later by
         result().  out: an output set of new_output_set() (default: this object's one set, overwritten by every call)."""
-        if out is None and (self.out is None or getattr(self, "_out_cap", None) is None):
-            self.out = self.new_output_set()
-            self._out_cap = [self.N * k + 1 for k in self.PER_COLUMN_MAX]
-        if out is None:
-            out = self.out
+        out = self._output_set(out)
         a = self._args(phi)
         a.kept_ops, kept = self._kept_ops(out)
         cp, rv, nz = self._out_ptrs(out)
-        caps = (C.c_int64 * 5)(*[self.N * k + 1 for k in self.PER_COLUMN_MAX])
+        caps = (C.c_int64 * 5)(*self._capacities())
         self._check(self.lib.otmb_transportmatrix_dev(self.ctx.handle, C.byref(a), C.byref(cp), C.byref(rv),
                                                       C.byref(nz), C.byref(caps)))
         self._kept_written(out, kept)
-        self._note("_tm_seq")
+        self._note(self._tm_seq)
         return self.result() if sync else out
 
     def result(self):
@@ -1046,9 +1049,7 @@ class DeviceAssembler:
                                                       rv.data_ptr(), nz.data_ptr(), n, Sp.data_ptr(), Si.data_ptr(), Sx.data_ptr(),
                                                       C.byref(nnz)))
         k = int(nnz.value)
-        Cp = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-        Ci = torch.empty(max(k, 1), dtype=torch.int64, device=self.device)
-        Cx = torch.empty(max(k, 1), dtype=torch.float64, device=self.device)
+        Cp, Ci, Cx = self._csc(n, max(k, 1))
         self.ctx.check(self.lib.otmb_coarsen_fill_dev(self.ctx.handle, Cp.data_ptr(), Ci.data_ptr(), Cx.data_ptr()))
         return Cp, Ci[:k], Cx[:k]
 
@@ -1085,9 +1086,7 @@ class DeviceAssembler:
         self.ctx.check(self.lib.otmb_sparse_plan_dev(self.ctx.handle, I.data_ptr(), J.data_ptr(), V.data_ptr(), I.numel(), m, n,
                                                      C.byref(nnz)))
         k = int(nnz.value)
-        cp = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-        rv = torch.empty(max(k, 1), dtype=torch.int64, device=self.device)
-        nz = torch.empty(max(k, 1), dtype=torch.float64, device=self.device)
+        cp, rv, nz = self._csc(n, max(k, 1))
         self.ctx.check(self.lib.otmb_sparse_fill_dev(self.ctx.handle, cp.data_ptr(), rv.data_ptr(), nz.data_ptr()))
         self.ctx.synchronize()
         return cp, rv[:k], nz[:k]
@@ -1101,9 +1100,7 @@ class DeviceAssembler:
         self.ctx.check(self.lib.otmb_spadd_plan_dev(self.ctx.handle, n, Ap.data_ptr(), Ai.data_ptr(), Ax.data_ptr(), Bp.data_ptr(),
                                                     Bi.data_ptr(), Bx.data_ptr(), C.byref(nnz)))
         k = int(nnz.value)
-        Cp = torch.empty(n + 1, dtype=torch.int64, device=self.device)
-        Ci = torch.empty(max(k, 1), dtype=torch.int64, device=self.device)
-        Cx = torch.empty(max(k, 1), dtype=torch.float64, device=self.device)
+        Cp, Ci, Cx = self._csc(n, max(k, 1))
         self.ctx.check(self.lib.otmb_spadd_fill_dev(self.ctx.handle, n, Ap.data_ptr(), Ai.data_ptr(), Ax.data_ptr(), Bp.data_ptr(),
                                                     Bi.data_ptr(), Bx.data_ptr(), Cp.data_ptr(), Ci.data_ptr(), Cx.data_ptr()))
         self.ctx.synchronize()
@@ -1122,7 +1119,7 @@ class DeviceAssembler:
         write left it, or that the next call keeps (otmb_tm_args.kept_ops: a time loop's steady state); when all three are kept the pass reads
         the library's TκH table instead of thkcello and the edge / distance metrics (_htab_bytes), and writes T's values only when its pattern
         is kept too (_tpat_steady: 8 nnz(T), no colptr, no rowval)."""
-        skip = set(getattr(self, "given", None) or ()) | self._kept_steady()
+        skip = set(self.given) | self._kept_steady()
         htab = self._htab_bytes(skip)
         tpat = self._tpat_steady(skip)
         n3d = 9 + (1 if self.rho is not None else 0) - (1 if htab else 0)  # (thkcello)

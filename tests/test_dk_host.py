@@ -95,7 +95,7 @@ def test_shapes_are_refused_before_the_library_is_called(op):
 def test_the_assembler_forwards_d_and_the_other_keywords_to_its_operator():
     """DeviceAssembler.solve / .step_tracers / .periodic_tracers are one-line forwards to device.Operator: a 2-D d, the observers, the weights
     and outer arrive as given (an operator that records stands in for the resident one)."""
-    from otmb_amd.device import DeviceAssembler
+    from otmb_amd.device import DeviceAssembler, OpRecord
 
     class _Op:
         handle = C.c_void_p(1)
@@ -113,7 +113,8 @@ def test_the_assembler_forwards_d_and_the_other_keywords_to_its_operator():
             self.calls.append(("periodic", S, kw))
 
     asm, op = DeviceAssembler.__new__(DeviceAssembler), _Op()
-    asm._ops = {"T": {"op": op}}
+    asm._init_state()
+    asm._ops = {"T": OpRecord(op)}
     asm.operator = lambda matrix="T": op
     X, d, W, tw = np.ones((N, K)), np.full((N, K), 2.0), np.ones(N), np.ones(2)
     asm.solve("T", X, d=d, sigma=0.5, precond="lines")

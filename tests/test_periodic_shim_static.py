@@ -80,7 +80,7 @@ def test_python_makes_the_same_calls(monkeypatch):
         assert str(inspect.signature(cls.periodic)) == SIGNATURES["periodic"] and not hasattr(cls.periodic, "__wrapped__")
     dev = open(os.path.join(ROOT, "oceantransportmatrixbuilder.jl_amd", "device.py"), encoding="utf-8").read()
     assert len(re.findall('"otmb_op_periodic"', CALLS)) == 1 and '"otmb_op_periodic' not in API + dev
-    assert re.search(r"\n    def periodic_tracers\(self, source, \*, matrix=\"T\", \*\*kw\):.*?return rec\[\"op\"\]\.periodic\(source, \*\*kw\)", dev, re.S)
+    assert re.search(r"\n    def periodic_tracers\(self, source, \*, matrix=\"T\", \*\*kw\):.*?return self\._slotted\(matrix\)\.op\.periodic\(source, \*\*kw\)", dev, re.S)
     # the same defaults on both sides
     assert "ptol::Real = 1e-8, restart::Integer = 30" in SHIM and "maxcycles::Integer = 1000)" in SHIM
     assert "θ::Real = 1.0, firstslot::Integer = 1" in SHIM

@@ -71,7 +71,7 @@ def test_months_kept_one_by_one_step_like_an_operator_over_the_same_values(monke
             assert ia.steps_done == io.steps_done == 7 and np.array_equal(ia.iterations, io.iterations)
             _same_bits(Xa.cpu().numpy(), Xo, ("step_tracers", theta))
             _same_bits(ia.relres, io.relres, ("relres", theta))
-    op = asm._ops["T"]["op"]
+    op = asm._ops["T"].op
     assert op.slots == (MONTHS, MONTHS - 1)
     for m in range(MONTHS):  # every slot still holds its own month
         op.select(m)
@@ -113,7 +113,7 @@ def test_a_month_with_another_pattern_is_refused_and_the_slots_stay():
     assert asm.nnz[MATS.index("T")] < len(kept[0][2])  # (the cancellations compacted T)
     with pytest.raises(ValueError, match="forget_slots"):
         asm.keep_slot(2)
-    assert op.slots == (3, 1) and asm._ops["T"]["op"] is op
+    assert op.slots == (3, 1) and asm._ops["T"].op is op
     for m, h in enumerate((kept[0], kept[1], kept[0])):  # (growing copied the selected slot: the third holds the first month)
         op.select(m)
         _same_bits(op.mul(xd).cpu().numpy(), spmv_ref(N, N, *h, x), ("slot", m))

@@ -68,6 +68,7 @@ def asm(monkeypatch):
     monkeypatch.setattr(device, "Operator", _Op)
     _Op.made = 0
     a = object.__new__(DeviceAssembler)
+    a._init_state()
     a.ctx, a.N = _Ctx(), N
     a.vertical_lines = lambda: None
     a.out = {m: (torch.arange(1, N + 2), torch.arange(1, NNZ + 3), torch.zeros(NNZ + 2, dtype=torch.float64)) for m in device.MATS}
@@ -144,3 +145,159 @@ def test_one_slot_behaves_as_before(asm):
     _build(asm, 3, False)
     op3 = asm.operator("T")
     assert op3 is not op and not op.handle.value and _months(op3) == [3.0] and asm.op_replans == 2
+
+
+# ---- which promises a call may make (_kept_ops) after an accepted call (_kept_written), on CPU tensors ------------------------------------
+KEPT = DeviceAssembler.KEPT
+K = sum(1 << device.MATS.index(m) for m in KEPT)  # the three operator bits
+P, R = device.capi.KEPT_T_PATTERN, device.capi.KEPT_RHO
+GRID = ("lwet3d", "lwet", "v3d", "thk", "area", "zt", "mlotst") + tuple(f"{w}{q}" for w in ("edge", "dist") for q in range(4))
+
+
+def _grid_asm():
+    """An assembler with a grid of CPU tensors and a stand-in context, and a five-matrix output set of its own."""
+    f = lambda n=4: torch.zeros(n, dtype=torch.float64)
+    i = lambda n=4: torch.zeros(n, dtype=torch.int64)
+    a = object.__new__(DeviceAssembler)
+    a._init_state()
+    a.ctx, a.N = _Ctx(), N
+    a.lwet3d, a.lwet, a.v3d, a.thk, a.area, a.zt, a.mlotst = i(), i(), f(), f(), f(), f(), f()
+    a.edge, a.dist = [f() for _ in range(4)], [f() for _ in range(4)]
+    a.kappa, a.rho = (500.0, 0.1, 1e-5), f()
+    return a, {m: (i(N + 1), i(NNZ), f(NNZ)) for m in device.MATS}
+
+
+@pytest.fixture
+def kept(monkeypatch):
+    monkeypatch.delenv("OTMB_KEPT", raising=False)
+    return _grid_asm()
+
+
+def _grid_tensor(a, name):
+    return getattr(a, name[:4])[int(name[4])] if name[:4] in ("edge", "dist") else getattr(a, name)
+
+
+def test_no_promise_before_anything_was_written(kept):
+    a, out = kept
+    assert a._kept_ops(out) == (0, ())
+
+
+def test_every_promise_when_nothing_happened_since(kept):
+    a, out = kept
+    a._kept_written(out, ())
+    assert a._kept_ops(out) == (K | P | R, KEPT)
+    a._kept_written(out, KEPT)
+    assert a._kept_ops(out) == (K | P | R, KEPT)
+    assert a._kept_last == () and a._tpat_last is True  # (of the call being prepared, until _kept_written says it was accepted)
+    a._kept_written(out, KEPT)
+    assert a._kept_last == KEPT and a._kept_steady() == set(KEPT)
+
+
+@pytest.mark.parametrize("q", [0, 1])
+def test_an_edit_of_T_pattern_withdraws_the_pattern_alone(kept, q):
+    a, out = kept
+    a._kept_written(out, KEPT)
+    out["T"][q].add_(0)
+    assert a._kept_ops(out) == (K | R, KEPT) and a._tpat_last is False
+
+
+@pytest.mark.parametrize("m,q", [("T", 2), ("Tadv", 0), ("Tadv", 1), ("Tadv", 2)])
+def test_an_edit_of_T_values_or_of_Tadv_withdraws_nothing(kept, m, q):
+    a, out = kept
+    a._kept_written(out, KEPT)
+    out[m][q].add_(0)
+    assert a._kept_ops(out) == (K | P | R, KEPT)
+
+
+@pytest.mark.parametrize("how", ["clone", "inplace"])
+def test_another_rho_withdraws_rho_alone(kept, how):
+    a, out = kept
+    a._kept_written(out, KEPT)
+    if how == "clone":
+        a.rho = a.rho.clone()
+    else:
+        a.rho.add_(0)
+    assert a._kept_ops(out) == (K | P, KEPT)
+
+
+@pytest.mark.parametrize("m", KEPT)
+@pytest.mark.parametrize("q", [0, 1, 2])
+def test_an_edit_of_a_kept_operator_withdraws_everything(kept, m, q):
+    a, out = kept
+    a._kept_written(out, KEPT)
+    out[m][q].add_(0)
+    assert a._kept_ops(out) == (0, ())
+
+
+@pytest.mark.parametrize("name", GRID)
+def test_an_edit_of_a_grid_tensor_withdraws_everything(kept, name):
+    a, out = kept
+    a._kept_written(out, KEPT)
+    _grid_tensor(a, name).add_(0)
+    assert a._kept_ops(out) == (0, ())
+
+
+def test_another_kappa_only_T_or_a_given_operator_withdraw_everything(kept):
+    a, out = kept
+    a._kept_written(out, KEPT)
+    a.kappa = (1.0, 0.1, 1e-5)
+    assert a._kept_ops(out) == (0, ())
+    a.kappa = (500.0, 0.1, 1e-5)
+    assert a._kept_ops(out) == (K | P | R, KEPT)
+    a.only_T = True
+    assert a._kept_ops(out) == (0, ())
+    a.only_T = False
+    assert a._kept_ops(out) == (K | P | R, KEPT)
+    a.given = {"TκH": out["TκH"]}
+    assert a._kept_ops(out) == (0, ())
+    a.given = {}
+    assert a._kept_ops(out) == (K | P | R, KEPT)
+
+
+def test_a_call_with_a_given_operator_leaves_no_promise_behind(kept):
+    a, out = kept
+    a._kept_written(out, KEPT)
+    a.given = {"TκH": out["TκH"]}
+    a._kept_written(out, ())
+    a.given = {}
+    assert a._kept_ops(out) == (0, ())
+
+
+def test_a_call_for_T_alone_leaves_no_promise_behind(kept):
+    a, out = kept
+    a.only_T = True
+    a._kept_written(out, ())
+    a.only_T = False
+    assert a._kept_ops(out) == (0, ())
+
+
+def test_another_output_set_with_equal_contents_gets_no_promise(kept):
+    a, out = kept
+    a._kept_written(out, KEPT)
+    other = {m: tuple(t.clone() for t in out[m]) for m in device.MATS}
+    assert a._kept_ops(other) == (0, ())
+    assert a._kept_ops(out) == (K | P | R, KEPT)  # (asking is no edit)
+
+
+def test_forget_kept_withdraws_everything(kept):
+    a, out = kept
+    a._kept_written(out, KEPT)
+    a._forget_kept()
+    assert a._kept_last == () and a._tpat_last is False and a._kept_steady() == set()
+    assert a._kept_ops(out) == (0, ())
+    assert a._kept_last == () and a._tpat_last is False
+
+
+def test_OTMB_KEPT_0_makes_no_promise(monkeypatch):
+    monkeypatch.setenv("OTMB_KEPT", "0")
+    a, out = _grid_asm()
+    a._kept_written(out, ())
+    assert a._kept_ops(out) == (0, ()) and a._kept_steady() == set()
+
+
+def test_two_assemblers_share_no_state(kept):
+    a, out = kept
+    b, out_b = _grid_asm()
+    a._kept_written(out, KEPT)
+    a.given = {"TκH": out["TκH"]}
+    assert b._kept_ops(out_b) == (0, ()) and b._kept_steady() == set() and not getattr(b, "given", None)

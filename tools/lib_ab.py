@@ -7,7 +7,7 @@ sys.path.insert(0, ROOT)
 ap = argparse.ArgumentParser()
 ap.add_argument("--libs", default="default"); ap.add_argument("--rows", default="0"); ap.add_argument("--workload", default="quarterdeg")
 ap.add_argument("--rounds", type=int, default=4); ap.add_argument("--steps", type=int, default=10)
-ap.add_argument("--stagger", default="0", help="OTMB_STAGGER values (bytes): the k-th array of an assembler starts k*stagger bytes into its allocation")
+ap.add_argument("--stagger", default="0", help="staggers (bytes): the k-th array of an assembler starts k*stagger bytes into its allocation (tools/placement_alloc.py)")
 ap.add_argument("--bipolar", action="store_true", help="also time every assembler with the topology flag forced to bipolar (no seam row: what the generic column path costs)")
 ap.add_argument("--only-bipolar", action="store_true", help="time ONLY with the topology flag forced to bipolar (variants that cannot do the seam row)")
 ap.add_argument("--reps", type=int, default=1, help="assemblers per library (the placement of the arrays in HBM moves the fill pass by +-5 %)")
@@ -15,18 +15,23 @@ a = ap.parse_args()
 import numpy as np, torch
 import otmb_amd
 from otmb_amd import capi, synthetic, synthetic_device
-from otmb_amd.device import DeviceAssembler
+from placement_alloc import PlacedAssembler
 dev = torch.device("cuda", 0)
 if a.workload in ("quarterdeg", "tenthdeg"):
     dg = synthetic_device.make_device_grid(a.workload, dev, seed=20260501, rho="array"); umo, vmo, fill = dg.umo, dg.vmo, dg.fill
-    mk = lambda: synthetic_device.assembler_for(dg, 0)
+    def mk(stg):  # (synthetic_device.assembler_for with the staggering allocator)
+        x = PlacedAssembler(0, stagger=stg)
+        x.set_grid_tensors(shape=(dg.nx, dg.ny, dg.k1 - dg.k0), topology=dg.topology, v3d=dg.v3d, thkcello=dg.thkcello, edge_length=dg.edge_length,
+                           dist_nbr=dg.dist_nbr, area2d=dg.area2d, zt=dg.zt, mlotst=dg.mlotst, rho=dg.rho, kappaH=dg.kappaH, kappaVML=dg.kappaVML,
+                           kappaVdeep=dg.kappaVdeep)
+        return x
 else:
     nx, ny, nz, lf = synthetic.PRESETS[a.workload]
     g = synthetic.make_grid(nx, ny, nz, seed=20260501, land_fraction=lf, rho="array")
     gm = otmb_amd.makegridmetrics(areacello=g.areacello, volcello=g.volcello, lon=g.lon, lat=g.lat, lev=g.lev, lon_vertices=g.lon_vertices, lat_vertices=g.lat_vertices)
     umo = torch.from_numpy(np.asfortranarray(g.umo.data).ravel(order="F")).to(dev); vmo = torch.from_numpy(np.asfortranarray(g.vmo.data).ravel(order="F")).to(dev); fill = 1e20
-    def mk():
-        x = DeviceAssembler(0); x.set_grid(gm, g.mlotst, g.rho, g.kappaH, g.kappaVML, g.kappaVdeep); return x
+    def mk(stg):
+        x = PlacedAssembler(0, stagger=stg); x.set_grid(gm, g.mlotst, g.rho, g.kappaH, g.kappaVML, g.kappaVdeep); return x
 asms = []
 for rep in range(a.reps):
     names = a.libs.split(",")
@@ -34,8 +39,7 @@ for rep in range(a.reps):
     for name in names:
         for stg in a.stagger.split(","):
             capi.use_library(os.path.join(ROOT, "oceantransportmatrixbuilder.jl_amd", "lib", "libotmb_hip.so" if name == "default" else f"libotmb_hip_{name}.so"), lenient=True)
-            os.environ["OTMB_STAGGER"] = stg
-            x = mk(); x.ctx.set_formulation(0); asms.append((name + ("" if stg == "0" else "+stagger" + stg), rep, x))
+            x = mk(int(stg)); x.ctx.set_formulation(0); asms.append((name + ("" if stg == "0" else "+stagger" + stg), rep, x))
 rows = [int(r) for r in a.rows.split(",")]
 res = {}
 allk = {}

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """How much does the placement of the arrays in HBM move the kernel times?  Several assemblers per setting (each with its
-own allocations), interleaved rounds, HIP-event kernel times.  OTMB_STAGGER=<bytes> offsets the k-th array by k*bytes.
+own allocations), interleaved rounds, HIP-event kernel times.  Each argument is a stagger in bytes: the k-th array is offset by k*bytes
+(tools/placement_alloc.py).
    python tools/placement_study.py 0 4352 135424     [WORKLOAD=access1deg REPS=4]"""
 import os, sys
 import numpy as np
@@ -9,7 +10,7 @@ sys.path.insert(0, ROOT)
 import torch
 import otmb_amd
 from otmb_amd import synthetic
-from otmb_amd.device import DeviceAssembler
+from placement_alloc import PlacedAssembler
 wl = os.environ.get("WORKLOAD", "access1deg")
 reps = int(os.environ.get("REPS", "4"))
 nx, ny, nz, lf = synthetic.PRESETS[wl]
@@ -21,8 +22,7 @@ hv = torch.from_numpy(np.asfortranarray(g.vmo.data).ravel(order="F"))
 asms = []
 for rep in range(reps):
     for st in sys.argv[1:]:
-        os.environ["OTMB_STAGGER"] = st
-        a = DeviceAssembler(0)
+        a = PlacedAssembler(0, stagger=int(st))
         a.set_grid(gm, g.mlotst, g.rho, g.kappaH, g.kappaVML, g.kappaVdeep)
         umo, vmo = a._t(hu.numpy()), a._t(hv.numpy())
         a.step(umo, vmo, 1e20)
