@@ -979,6 +979,62 @@ int32_t otmb_op_periodic_dk(otmb_op *op, int32_t adjoint, int64_t k, const doubl
                             int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
                             int32_t outer, int64_t *msolve_iters);
 
+/* ---- A schedule for the time axis: otmb_op_step_sched[_dev] and otmb_op_periodic_sched[_dev].  Several steps inside one slot (four
+ *      implicit steps inside January before February begins), a source per slot (gas exchange under a seasonal ice cover) and, for the step,
+ *      a history: one factor per step and tracer on a fixed spatial pattern (CFC-11, SF6, bomb radiocarbon).  The arguments are those of
+ *      otmb_op_step_dk and otmb_op_periodic_dk with `const double *S, int64_t lds` replaced by
+ *      `int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, const double *scale` (the periodic call takes no scale: a history
+ *      is not periodic).  For a call of nsteps steps from first_slot on an operator with nslots slots:
+ *        substeps = m >= 1: step t (0-based) runs with slot(t) = (first_slot + t / m) mod nslots, the division an integer one; m = 1 is the
+ *          rule of otmb_op_step.
+ *        S: an array of nsrc pointers to blocks, each n x k with leading dimension lds >= n (separate arrays need no stacking copy).  nsrc is
+ *          0 (no source; S may be NULL), 1 (every step takes block 0) or nslots (step t takes block slot(t): the source of the month).
+ *        scale: NULL, or a HOST array (in both variants, like tw) of nsteps·k finite values, step-major, entry t·k + c.  The source of step t,
+ *          tracer c, row i is S_j[i,c] * scale[t·k + c]: one multiplication, made before anything else touches s.
+ *        Everything else is otmb_op_step_dk's: D / ldd, dt, theta, the observers, tw / Xbar, the reports, the stopping rules and the
+ *          restored selection.
+ * In bits: step t of a scheduled call has the bits of otmb_op_step_dk_dev(nsteps = 1, first_slot = slot(t), S = S_eff) made from the state
+ *      step t - 1 left, S_eff[i,c] = S_j[i,c] * scale[t·k + c], and S_j itself without scale.  The reports land at t·k + c, the observation
+ *      block at t, and the mean's fold runs over t, as in otmb_op_step_obs.  Column c of k has the bits of that column alone with its own column
+ *      of every source block, of scale and of D.  In the elementwise line:  sf = s * f;  theta == 1: b = a + sf;  theta < 1: sf / theta -- one
+ *      operation per statement, no FMA; a scale of all 1.0 gives the bits of no scale (finite sources).  The k scale values of a step reach
+ *      the right-hand-side kernels as a device pointer into a block of nsteps·k doubles staged once per call.
+ *      A slot's preconditioner is made on the slot's first visit of the call and reused on every later step in that slot, the sub-steps
+ *      included: sigma, d, adjoint and the values are fixed inside a call, so the bits are those of separate solves.  The workspace is still
+ *      one preconditioner per visited slot: n·k + used·(a preconditioner's doubles) + (scale ? nsteps·k : 0) doubles,
+ *      used = min(ceil(nsteps / m), nslots).  A failure's message names the step and the slot the schedule gave it.
+ *      otmb_op_step_dk[_dev] and everything layered on it ARE this loop with substeps = 1, nsrc = (S ? 1 : 0) and scale = NULL, bit for bit.
+ *      otmb_op_step_sched_dev: S is a HOST array of nsrc device pointers; D, X, W, obs, Xbar device pointers.  otmb_op_step_sched: nsrc host
+ *      pointers; every block and D are staged once, and X, the observations and the mean come home once.
+ * otmb_op_periodic_sched[_dev]: F is the scheduled step over ncycle steps, Φ·v the same call without sources, g = F(0); the method, the
+ *      restart / verify / stop rules, the reasons and column independence are otmb_op_periodic_dk's for both values of outer.  A column is
+ *      answered with zero and never stepped only when it is zero in EVERY source block.  With OTMB_OUTER_MEAN w[s] = count_s / ncycle, count_s
+ *      the number of steps t in 0 .. ncycle - 1 with slot(t) = s, and P = (double)ncycle * dt.  The step calls take the columns that iterate
+ *      gathered compactly, with those columns of all nsrc blocks: with nsrc > 1 the operator's workspace grows by nsrc·2k·n doubles (the
+ *      first call's 2k columns need every block twice); with nsrc <= 1 it is otmb_op_periodic_dk's.  A failed reservation is OTMB_ERR_ALLOC
+ *      with X untouched.  otmb_op_periodic_dk[_dev] and everything layered on it ARE this call with substeps = 1 and nsrc = (S ? 1 : 0).
+ * Refused with OTMB_ERR_INVALID_ARG before anything is written, after the checks of the call they extend, the message naming
+ *      otmb_op_step_sched or otmb_op_periodic_sched, the operator staying usable: substeps < 1; nsrc outside {0, 1, nslots}; nsrc > 0 with S
+ *      NULL or any block NULL; lds < n; scale without a source, or with an entry that is not finite.
+ * Not built: interpolation of the matrices between slots (a private value set and a fresh preconditioner per sub-step), and sources at
+ *      sub-step resolution.                                                                                                               */
+int32_t otmb_op_step_sched_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t nsteps,
+                               int64_t first_slot, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, const double *scale, double *X,
+                               int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters, double *relres,
+                               int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw, double *Xbar, int64_t ldm);
+int32_t otmb_op_step_sched(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t nsteps,
+                           int64_t first_slot, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, const double *scale, double *X, int64_t ldx,
+                           double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters, double *relres, int32_t *reason, int64_t q,
+                           const double *W, int64_t ldw, double *obs, const double *tw, double *Xbar, int64_t ldm);
+int32_t otmb_op_periodic_sched_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
+                                   int64_t first_slot, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx,
+                                   int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles,
+                                   int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters);
+int32_t otmb_op_periodic_sched(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
+                               int64_t first_slot, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0,
+                               double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect,
+                               int32_t *reason, int32_t outer, int64_t *msolve_iters);
+
 #ifdef __cplusplus
 }
 #endif

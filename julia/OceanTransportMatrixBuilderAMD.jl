@@ -42,6 +42,7 @@ export setlines!, verticallines, precondition!
 export setslots!, selectslot!, slots, step!   # (`step` extends Base.step for this module's operators: nothing to export)
 export periodic!, periodic, combineslots!
 export observe, stepobserve!
+export stepsched!, periodicsched!
 
 const LIBPATH = get(ENV, "OTMB_HIP_LIB", joinpath(@__DIR__, "..", "oceantransportmatrixbuilder.jl_amd", "lib", "libotmb_hip.so"))
 const lib = Ref{Ptr{Cvoid}}(C_NULL)
@@ -784,6 +785,130 @@ function periodic!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointD
     why = [PERIODIC_PC_REASONS[r + 1] for r in reason]
     return X, (cycles = cycles, defect = defect, reason = why, converged = why .== :converged, msolve_iters = msolve)
 end
+
+# A schedule for the time axis (otmb_op_step_sched, otmb_op_periodic_sched; include/otmb.h states the contract).  `substeps = m`: step t runs
+# with slot firstslot + t ÷ m (cyclically) -- m implicit steps inside January before February begins, each slot's preconditioner made once.
+# `source`: nothing, an array of X's shape, or a vector of such arrays, one (every step takes it) or one per slot (step t takes its slot's: a
+# seasonal source); the blocks stay where they are, their addresses travel.  `sourcescale` (step only): nothing or a k x nsteps matrix (nsteps
+# values for a vector X), entry [c, t] the factor of tracer c's source at step t: a fixed pattern times a history (CFC-11, SF6, bomb
+# radiocarbon).  `d`: nothing, n values, or a matrix of X's shape (one d per tracer).  step!, stepobserve! and periodic! keep their methods:
+# with substeps = 1, one array and no scale these calls give their bits.  The other keywords and the returned info are theirs.
+function schedsources(op::DeviceOperator, source, X, nslots::Integer)
+    source === nothing && return Ptr{Float64}[], Int64(max(op.n, 1)), ()
+    blocks = source isa AbstractVector{<:StridedVecOrMat{Float64}} ? source : [source]
+    length(blocks) in (1, nslots) || throw(DimensionMismatch("$(length(blocks)) source blocks, expected 1 or one per slot ($nslots)"))
+    for S in blocks
+        size(S) == size(X) || throw(DimensionMismatch("source $(size(S)), X $(size(X))"))
+        stride(S, 1) == 1 || throw(ArgumentError("the source blocks need contiguous columns"))
+    end
+    ld(S) = Int64(S isa AbstractVector || size(S, 2) <= 1 ? max(op.n, 1) : stride(S, 2))
+    if !all(ld(S) == ld(blocks[1]) for S in blocks)   # one lds for all: blocks whose leading dimensions differ are copied compactly
+        blocks = [ld(S) == max(op.n, 1) ? S : copy(S) for S in blocks]
+    end
+    return Ptr{Float64}[pointer(S) for S in blocks], ld(blocks[1]), blocks
+end
+function scheddims(op::DeviceOperator, X, d)
+    size(X, 1) == op.n == op.m || throw(DimensionMismatch("operator of $((op.m, op.n)), X $(size(X))"))
+    stride(X, 1) == 1 || throw(ArgumentError("X needs contiguous columns"))
+    k = Int64(size(X, 2))
+    ldx = Int64(X isa AbstractVector || k <= 1 ? max(op.n, 1) : stride(X, 2))
+    ldd = d isa AbstractMatrix ? dkdims(op, d, X, "X") : Int64(0)
+    d isa AbstractVector && length(d) != op.n && throw(DimensionMismatch("d has $(length(d)) values, the operator $(op.n) columns"))
+    return k, ldx, ldd
+end
+function stepsched!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}; dt::Real, θ::Real = 1.0, nsteps::Integer = 1,
+                    firstslot::Integer = 1, substeps::Integer = 1,
+                    source::Union{Nothing,StridedVecOrMat{Float64},AbstractVector{<:StridedVecOrMat{Float64}}} = nothing,
+                    sourcescale::Union{Nothing,StridedVecOrMat{Float64}} = nothing,
+                    d::Union{Nothing,Vector{Float64},StridedMatrix{Float64}} = nothing, rtol::Real = 1e-10, maxiter::Integer = 10000,
+                    precond::Symbol = :jacobi, observers::Union{Nothing,StridedVecOrMat{Float64}} = nothing,
+                    timeweights::Union{Nothing,Vector{Float64}} = nothing)
+    pc = precondcode(precond)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    k, ldx, ldd = scheddims(op, X, d)
+    nrep = max(Int64(nsteps), 0)
+    iters = zeros(Int64, k, nrep)
+    relres = zeros(Float64, k, nrep)
+    reason = zeros(Int32, k, nrep)
+    done = Ref{Int64}(0)
+    q, ldw = observers === nothing ? (0, max(op.n, 1)) : observerdims(op, observers)
+    obs = zeros(Float64, q, k, nrep)
+    timeweights === nothing || length(timeweights) == nrep || throw(DimensionMismatch("timeweights of $(length(timeweights)), nsteps $nrep"))
+    Xbar = timeweights === nothing ? nothing : zeros(Float64, size(X)...)
+    ldm = max(op.n, 1)
+    scale = nothing
+    if sourcescale !== nothing   # the library reads entry t·k + c: column-major k x nsteps
+        source === nothing && throw(ArgumentError("sourcescale needs a source"))
+        size(sourcescale) == (X isa AbstractVector ? (nrep,) : (k, nrep)) ||
+            throw(DimensionMismatch("sourcescale $(size(sourcescale)), expected $(X isa AbstractVector ? (nrep,) : (k, nrep))"))
+        scale = Array{Float64}(sourcescale)
+    end
+    lock(CALL_LOCK) do
+        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        nslots = Ref{Int64}(0)
+        slots_fn = sym(:otmb_op_slots)
+        check(ccall(slots_fn, Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), op.handle, nslots, C_NULL))
+        ptrs, lds, blocks = schedsources(op, source, X, nslots[])
+        step_sched_fn = sym(:otmb_op_step_sched)
+        GC.@preserve blocks begin
+            rc = ccall(step_sched_fn, Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Int64, Float64, Float64, Int64, Int64, Int64, Int64,
+                    Ptr{Ptr{Float64}}, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Float64, Int64, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Float64},
+                    Ptr{Int32}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64),
+                op.handle, Int32(adjoint), k, d === nothing ? C_NULL : d, ldd, Float64(dt), Float64(θ), Int64(nsteps), Int64(firstslot - 1),
+                Int64(substeps), Int64(length(ptrs)), isempty(ptrs) ? C_NULL : ptrs, lds, scale === nothing ? C_NULL : scale, X, ldx,
+                Float64(rtol), Int64(maxiter), pc, done, iters, relres, reason,
+                Int64(q), observers === nothing ? C_NULL : observers, ldw, observers === nothing ? C_NULL : obs,
+                timeweights === nothing ? C_NULL : timeweights, Xbar === nothing ? C_NULL : Xbar, ldm)
+            rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which step and column stopped why
+        end
+    end
+    ran = 1:min(done[] + 1, nrep)
+    why = permutedims([SOLVE_REASONS[r + 1] for r in reason[:, ran]])
+    return X, (stepsdone = done[], iterations = permutedims(iters[:, ran]), relres = permutedims(relres[:, ran]), reason = why,
+               converged = why .== :converged, observations = observers === nothing ? nothing : obs[:, :, 1:done[]],
+               mean = (Xbar !== nothing && done[] > 0) ? Xbar : nothing)
+end
+function periodicsched!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator},
+                        source::Union{StridedVecOrMat{Float64},AbstractVector{<:StridedVecOrMat{Float64}}}; dt::Real, ncycle::Integer, θ::Real = 1.0,
+                        firstslot::Integer = 1, substeps::Integer = 1, d::Union{Nothing,Vector{Float64},StridedMatrix{Float64}} = nothing,
+                        x0::Bool = false, rtol::Real = 1e-10, maxiter::Integer = 10000, precond::Symbol = :jacobi, outer::Symbol = :none,
+                        ptol::Real = 1e-8, restart::Integer = 30, maxcycles::Integer = 1000)
+    oc = outercode(outer)
+    pc = precondcode(precond)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    k, ldx, ldd = scheddims(op, X, d)
+    cycles = zeros(Int64, k)
+    defect = zeros(Float64, k)
+    reason = zeros(Int32, k)
+    msolve = zeros(Int64, k)
+    lock(CALL_LOCK) do
+        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        nslots = Ref{Int64}(0)
+        slots_fn = sym(:otmb_op_slots)
+        check(ccall(slots_fn, Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), op.handle, nslots, C_NULL))
+        ptrs, lds, blocks = schedsources(op, source, X, nslots[])
+        periodic_sched_fn = sym(:otmb_op_periodic_sched)
+        GC.@preserve blocks begin
+            rc = ccall(periodic_sched_fn, Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Int64, Float64, Float64, Int64, Int64, Int64, Int64,
+                    Ptr{Ptr{Float64}}, Int64, Ptr{Float64}, Int64, Int32, Float64, Int64, Int32, Float64, Int64, Int64, Ptr{Int64}, Ptr{Float64},
+                    Ptr{Int32}, Int32, Ptr{Int64}),
+                op.handle, Int32(adjoint), k, d === nothing ? C_NULL : d, ldd, Float64(dt), Float64(θ), Int64(ncycle), Int64(firstslot - 1),
+                Int64(substeps), Int64(length(ptrs)), ptrs, lds, X, ldx, Int32(x0), Float64(rtol), Int64(maxiter), pc, Float64(ptol),
+                Int64(restart), Int64(maxcycles), cycles, defect, reason, oc, msolve)
+            rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which column stopped why
+        end
+    end
+    why = [PERIODIC_PC_REASONS[r + 1] for r in reason]
+    return X, (cycles = cycles, defect = defect, reason = why, converged = why .== :converged, msolve_iters = msolve)
+end
+# a vector of source blocks is a schedule by itself: periodic!'s positional source dispatches on it (step! and stepobserve! take their source
+# as a keyword, which does not dispatch: their scheduled form is stepsched!)
+periodic!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, source::AbstractVector{<:StridedVecOrMat{Float64}};
+          kwargs...) = periodicsched!(X, D, source; kwargs...)
+periodic!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, source::AbstractVector{<:StridedVecOrMat{Float64}},
+          d::StridedMatrix{Float64}; kwargs...) = periodicsched!(X, D, source; d = d, kwargs...)
 
 const HDIRS = (:west, :east, :south, :north)      # OTMB_DIR_*
 f64(a) = Array{Float64}(replace(a, missing => NaN))

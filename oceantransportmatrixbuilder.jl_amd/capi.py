@@ -254,6 +254,19 @@ SYMBOLS = {
     "otmb_op_periodic_dk": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp,
                                          C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int32,
                                          _vp]),
+    # a schedule (substeps, nsrc, S: nsrc pointers, lds[, scale] in place of S, lds): the arguments of step_dk and periodic_dk
+    "otmb_op_step_sched_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp,
+                                            C.c_int64, _vp, _vp, C.c_int64, C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp,
+                                            _vp, _vp, C.c_int64]),
+    "otmb_op_step_sched": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp,
+                                        C.c_int64, _vp, _vp, C.c_int64, C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp,
+                                        _vp, _vp, C.c_int64]),
+    "otmb_op_periodic_sched_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                                _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp,
+                                                _vp, _vp, C.c_int32, _vp]),
+    "otmb_op_periodic_sched": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                            _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp,
+                                            _vp, _vp, C.c_int32, _vp]),
     "otmb_op_combine_slots_dev": (C.c_int32, [_vp, _vp, C.c_int64]),
     "otmb_op_combine_slots": (C.c_int32, [_vp, _vp, C.c_int64]),
     "otmb_op_info": (C.c_int32, [_vp, _ip, _ip, _ip]),

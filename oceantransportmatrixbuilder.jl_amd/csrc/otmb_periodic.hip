@@ -37,6 +37,11 @@
 // gathered compactly, so their columns of D are gathered beside their states and sources (w.Dg), and the mean's preconditioner, made once
 // for all k columns, lends the gathered columns' sh, diag, multipliers and pivots to a compact copy (w.mpg).  The step and the solver give a
 // column the same bits at every position of a block, so a column's path does not depend on which other columns still run.
+//
+// otmb_op_periodic_sched[_dev], the cycle with a schedule (sub-steps inside a slot, a source block per slot): F is otmb_op_step_sched_dev,
+// the gathered step calls carry the live columns of every block (one block: in w.Sb or, the first call's 2k, in the bases, as ever; more:
+// in w.Sg, block j's columns behind block j - 1's), a column is zero only when it is zero in every block, and the mean's weights count
+// the schedule's visits.  Every other periodic export is this call with substeps = 1 and at most one block.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -255,6 +260,7 @@ struct PdWork {  // the arrays inside op->pd; every vector has the leading dimen
     double *V, *W, *Sb, *part, *hs, *yv;  // V: k bases of m + 1 vectors; W, Sb: k columns each (contiguous: 2k for the first call)
     double *Z = nullptr, *mp = nullptr;   // OTMB_OUTER_MEAN: k blocks of m preconditioned directions behind Sb; the mean's preconditioner
     double *mpg = nullptr, *Dg = nullptr; // per-column d: the gathered columns of that preconditioner, and of D (2k columns: the first call's)
+    double *Sg = nullptr;                 // more than one source block: the gathered columns of all of them (nsrc blocks of 2k columns)
     double *v(i64 c, i64 j) const { return V + (c * (m + 1) + j) * ld; }
     double *z(i64 c, i64 j) const { return Z + (c * m + j) * ld; }
     double *partc(i64 c) const { return part + c * (m + 2) * np; }
@@ -263,11 +269,14 @@ struct PdWork {  // the arrays inside op->pd; every vector has the leading dimen
 };
 
 // zvecs: the vectors of the Z block a column (0, or m with OTMB_OUTER_MEAN); pdbl: the doubles of the mean's preconditioner (0 without);
-// percol: every column has its own d (a second block of pdbl doubles, and 2k gathered columns of D)
-static int32_t pd_work(otmb_op *op, i64 k, i64 m, i64 zvecs, size_t pdbl, bool percol, PdWork &w) {
+// percol: every column has its own d (a second block of pdbl doubles, and 2k gathered columns of D); nsrc: the source blocks (more than
+// one: nsrc·2k gathered columns behind everything else; one block's columns lie in Sb or, the first call's 2k, in the bases as ever)
+static int32_t pd_work(otmb_op *op, i64 k, i64 m, i64 zvecs, size_t pdbl, bool percol, i64 nsrc, PdWork &w) {
     const i64 n = op->n;
     w.n = n, w.k = k, w.m = m, w.ld = (n + 1) & ~(i64)1, w.np = (n + PD_ROWS - 1) / PD_ROWS;
-    const size_t tail = (percol ? 2 : 1) * pdbl + (percol ? (size_t)(2 * k * w.ld) : 0);
+    const size_t head = (percol ? 2 : 1) * pdbl + (percol ? (size_t)(2 * k * w.ld) : 0);
+    if (nsrc > 1 && (double)nsrc * 2.0 * (double)k * (double)w.ld >= 1.0e18) return otmb_fail(op->ctx, OTMB_ERR_ALLOC, "periodic: the workspace's size overflows");
+    const size_t tail = head + (nsrc > 1 ? (size_t)(nsrc * 2 * k * w.ld) : 0);
     const double need = ((double)(m + 3 + zvecs) * (double)w.ld + (double)(m + 2) * (double)w.np + 3.0 * (double)(m + 2)) * (double)k * 8.0 +
                         (double)tail * 8.0;
     if (need >= 9.0e18) return otmb_fail(op->ctx, OTMB_ERR_ALLOC, "periodic: the workspace's size overflows");
@@ -285,9 +294,11 @@ static int32_t pd_work(otmb_op *op, i64 k, i64 m, i64 zvecs, size_t pdbl, bool p
     w.mp = pdbl ? w.V + vec + scal : nullptr;
     w.mpg = pdbl && percol ? w.mp + pdbl : nullptr;
     w.Dg = percol ? w.V + vec + scal + 2 * pdbl : nullptr;
+    w.Sg = nsrc > 1 ? w.V + vec + scal + head : nullptr;
     return OTMB_OK;
 }
 
+// (S: the first source block, or null without one)
 static int32_t pd_check(otmb_op *op, int64_t k, double dt, double theta, int64_t ncycle, int64_t first_slot, const double *S, int64_t lds, double *X, int64_t ldx,
                         double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, const int64_t *cycles,
                         const double *defect, const int32_t *reason, int32_t outer) {
@@ -324,7 +335,8 @@ struct PdRun {  // one call: the operator, the call's arguments, the workspace, 
     SvD d;  // one d for every column, or D (n x k)
     double dt, theta;
     i64 ncycle, first_slot;
-    const double *S;
+    i64 substeps, nsrc;  // the schedule (include/otmb.h): nsrc source blocks, S a host array of their device pointers
+    const double *const *S;
     i64 lds;
     double *X;
     i64 ldx;
@@ -355,6 +367,7 @@ struct PdRun {  // one call: the operator, the call's arguments, the workspace, 
     int32_t mean_setup();
     int32_t msolve(std::vector<PdItem> &items);
     int32_t read_hs();
+    double *sources(bool first) const { return nsrc > 1 ? w.Sg : first && use_x0 ? w.V : w.Sb; }  // where a step call's gathered sources go
     int32_t cycle(std::vector<PdItem> &items, bool withS, double *sbuf);
     void defect_of(i64 c, i64 p, bool minus_x);
     void judged(i64 c, double beta);
@@ -369,7 +382,7 @@ struct PdRun {  // one call: the operator, the call's arguments, the workspace, 
 int32_t PdRun::prepare() {
     int32_t rc;
     const bool mean = outer == OTMB_OUTER_MEAN;
-    if ((rc = pd_work(op, k, m, mean ? m : 0, mean ? sv_prec_doubles(op->n, precond == OTMB_PRECOND_LINES, sv_prec_cols(d, k)) : 0, d.percol(), w))) return rc;
+    if ((rc = pd_work(op, k, m, mean ? m : 0, mean ? sv_prec_doubles(op->n, precond == OTMB_PRECOND_LINES, sv_prec_cols(d, k)) : 0, d.percol(), nsrc, w))) return rc;
     grid = dim3((unsigned)w.np), block = dim3(256);
     alx = ((uintptr_t)X & 15) == 0 && (ldx & 1) == 0;
     col.resize((size_t)k);
@@ -402,7 +415,7 @@ int32_t PdRun::mean_setup() {
         b->cap = bytes;
     }
     std::vector<i64> count((size_t)nslots, 0);
-    for (i64 t = 0; t < ncycle; ++t) count[(size_t)((first_slot + t) % nslots)] += 1;
+    for (i64 t = 0; t < ncycle; ++t) count[(size_t)((first_slot + t / substeps) % nslots)] += 1;
     std::vector<double> wt((size_t)nslots);
     for (i64 s = 0; s < nslots; ++s) wt[(size_t)s] = (double)count[(size_t)s] / (double)ncycle;
     if ((rc = cb_combine(op, wt.data(), op->mean))) return rc;
@@ -464,8 +477,8 @@ int32_t PdRun::msolve(std::vector<PdItem> &items) {
     return OTMB_OK;
 }
 
-// One step call for `items` (in this order, compact in W from column 0; withS: their sources, gathered into sbuf): W = the cycle's end
-// states.  A call that leaves columns not converged stops those (STEP_FAILED) and is repeated without them; the call that completes
+// One step call for `items` (in this order, compact in W from column 0; withS: their sources, gathered into sbuf, block j's kk columns
+// behind block j - 1's): W = the cycle's end states.  A call that leaves columns not converged stops those (STEP_FAILED) and is repeated without them; the call that completes
 // counts one cycle for each of its columns.  items comes back as the columns of that call (their positions in W).
 int32_t PdRun::cycle(std::vector<PdItem> &items, bool withS, double *sbuf) {
     const i64 n = w.n, ld = w.ld;
@@ -477,14 +490,17 @@ int32_t PdRun::cycle(std::vector<PdItem> &items, bool withS, double *sbuf) {
                 HIP_TRY(ctx, hipMemsetAsync(w.W + p * ld, 0, (size_t)n * 8, st));
             else
                 HIP_TRY(ctx, hipMemcpyAsync(w.W + p * ld, it.from >= 0 ? dir(it.col, it.from) : X + it.col * ldx, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-            if (withS) HIP_TRY(ctx, hipMemcpyAsync(sbuf + p * ld, S + it.col * lds, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+            for (i64 j = 0; withS && j < nsrc; ++j)
+                HIP_TRY(ctx, hipMemcpyAsync(sbuf + (j * kk + p) * ld, S[j] + it.col * lds, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
             if (d.percol()) HIP_TRY(ctx, hipMemcpyAsync(w.Dg + p * ld, d.p + it.col * d.ld, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
         }
         s_it.assign((size_t)(ncycle * kk), 0), s_rr.assign((size_t)(ncycle * kk), 0.0), s_why.assign((size_t)(ncycle * kk), 0);
         int64_t done = 0;
-        const int32_t rc = otmb_op_step_dk_dev(op, adjoint, kk, d.percol() ? w.Dg : d.p, d.percol() ? ld : 0, dt, theta, ncycle, first_slot, withS ? sbuf : nullptr,
-                                               ld, w.W, ld, rtol, maxiter, precond, &done, s_it.data(), s_rr.data(), s_why.data(), 0, nullptr, 0, nullptr, nullptr,
-                                               nullptr, 0);
+        std::vector<const double *> sp((size_t)(withS ? nsrc : 0));
+        for (size_t j = 0; j < sp.size(); ++j) sp[j] = sbuf + (i64)j * kk * ld;
+        const int32_t rc = otmb_op_step_sched_dev(op, adjoint, kk, d.percol() ? w.Dg : d.p, d.percol() ? ld : 0, dt, theta, ncycle, first_slot, substeps,
+                                                  (i64)sp.size(), sp.data(), ld, nullptr, w.W, ld, rtol, maxiter, precond, &done, s_it.data(), s_rr.data(),
+                                                  s_why.data(), 0, nullptr, 0, nullptr, nullptr, nullptr, 0);
         if (rc == OTMB_OK) {
             std::vector<char> seen((size_t)k, 0);  // (the first call holds a column twice: one call, one cycle)
             for (const PdItem &it : items)
@@ -530,18 +546,23 @@ void PdRun::judged(i64 c, double beta) {
     q.ls.start(m, beta);
 }
 
-// the sources' norms: a zero column has g = 0.  items: the columns of the first call
+// the sources' norms, block by block: a column that is zero in every block has g = 0.  items: the columns of the first call
 int32_t PdRun::source_norms(std::vector<PdItem> &items) {
     int32_t rc;
-    for (i64 c = 0; c < k; ++c) {
-        HIP_TRY(ctx, hipMemcpyAsync(w.W + c * w.ld, S + c * lds, (size_t)w.n * 8, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(pd_defect_kernel, grid, block, 0, st, w.n, (const double *)(w.W + c * w.ld), (const double *)nullptr, false, (double *)nullptr, w.partc(c));
-        fold(c, 1, w.hsc(c));
+    std::vector<char> zero((size_t)k, 1);
+    for (i64 j = 0; j < nsrc; ++j) {
+        for (i64 c = 0; c < k; ++c) {
+            HIP_TRY(ctx, hipMemcpyAsync(w.W + c * w.ld, S[j] + c * lds, (size_t)w.n * 8, hipMemcpyDeviceToDevice, st));
+            hipLaunchKernelGGL(pd_defect_kernel, grid, block, 0, st, w.n, (const double *)(w.W + c * w.ld), (const double *)nullptr, false, (double *)nullptr, w.partc(c));
+            fold(c, 1, w.hsc(c));
+        }
+        if ((rc = read_hs())) return rc;
+        for (i64 c = 0; c < k; ++c)
+            if (!(hsh(c)[0] == 0.0)) zero[(size_t)c] = 0;
     }
-    if ((rc = read_hs())) return rc;
     for (i64 c = 0; c < k; ++c) {
         PdCol &q = col[(size_t)c];
-        if (hsh(c)[0] == 0.0) {
+        if (zero[(size_t)c]) {
             q.stop(OTMB_PERIODIC_CONVERGED), q.defect = 0.0;
         } else if (maxcycles < 1) {
             q.stop(OTMB_PERIODIC_MAXCYCLES);
@@ -558,7 +579,7 @@ int32_t PdRun::first_call(std::vector<PdItem> &items) {
     int32_t rc;
     if (use_x0)
         for (size_t p = 0, live = items.size(); p < live; ++p) items.push_back({items[p].col, -2});
-    if ((rc = cycle(items, true, use_x0 ? w.V : w.Sb))) return rc;  // (with a start the 2k sources lie in the bases, which are not in use yet)
+    if ((rc = cycle(items, true, sources(true)))) return rc;  // (with a start one block's 2k sources lie in the bases, which are not in use yet)
     // from here on X is written: the zero columns, and a start of zero
     for (i64 c = 0; c < k; ++c)
         if (!use_x0 || (col[(size_t)c].phase == PD_STOPPED && col[(size_t)c].reason == OTMB_PERIODIC_CONVERGED))
@@ -650,7 +671,7 @@ int32_t PdRun::round(bool &more) {
     if (outer == OTMB_OUTER_MEAN && (rc = msolve(ia))) return rc;
     if ((rc = cycle(ia, false, nullptr))) return rc;
     for (size_t p = 0; p < ia.size(); ++p) orthogonalise(ia[p].col, ia[p].from, (i64)p);
-    if ((rc = cycle(iv, true, w.Sb))) return rc;
+    if ((rc = cycle(iv, true, sources(false)))) return rc;
     for (size_t p = 0; p < iv.size(); ++p) defect_of(iv[p].col, (i64)p, true);
     if ((rc = read_hs())) return rc;
     for (const PdItem &it : iv) judged(it.col, std::sqrt(hsh(it.col)[0]));
@@ -671,24 +692,35 @@ int32_t PdRun::report(int64_t *cycles, double *defect, int32_t *reason, int64_t 
 
 extern "C" {
 
-int32_t otmb_op_periodic_dk_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
-                                int64_t first_slot, const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter,
-                                int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
-                                int32_t outer, int64_t *msolve_iters) {
-    if (!op) return OTMB_ERR_INVALID_ARG;
+// the checks of a periodic call (call: the export the refusals of D / ldd name; sched: the scheduled call's own, after those of the call it extends)
+static int32_t pd_check_call(otmb_op *op, const char *call, bool sched, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
+                             int64_t first_slot, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, double rtol,
+                             int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, const int64_t *cycles, const double *defect,
+                             const int32_t *reason, int32_t outer) {
     int32_t rc;
-    if ((rc = pd_check(op, k, dt, theta, ncycle, first_slot, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect, reason, outer)) ||
-        (rc = sv_check_d(op, "otmb_op_periodic_dk", D, ldd)))
+    if ((rc = pd_check(op, k, dt, theta, ncycle, first_slot, nsrc > 0 && S ? S[0] : nullptr, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles,
+                       defect, reason, outer)) ||
+        (rc = sv_check_d(op, call, D, ldd)))
         return rc;
+    const char *more = sched ? sv_sched_complaint(op, substeps, nsrc, S, lds) : nullptr;
+    return more ? otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, (std::string("otmb_op_periodic_sched: ") + more).c_str()) : OTMB_OK;
+}
+
+// the call proper: device pointers (S: a host array of nsrc of them), the arguments checked
+static int32_t pd_run_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle, int64_t first_slot,
+                          int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol,
+                          int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
+                          int32_t outer, int64_t *msolve_iters) {
+    int32_t rc;
     otmb_ctx *ctx = op->ctx;
     // the trivial answers: no rows, no source
     if (op->n == 0) return pd_all_zero(k, cycles, defect, reason, msolve_iters);
     HIP_TRY(ctx, hipSetDevice(op->device));
-    if (!S) {
+    if (nsrc == 0) {
         HIP_TRY(ctx, hipMemset2DAsync(X, (size_t)ldx * 8, 0, (size_t)op->n * 8, (size_t)k, ctx->stream));
         return pd_all_zero(k, cycles, defect, reason, msolve_iters);
     }
-    PdRun r{op, ctx, ctx->stream, adjoint, k, SvD{D, ldd}, dt, theta, ncycle, first_slot, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, outer};
+    PdRun r{op, ctx, ctx->stream, adjoint, k, SvD{D, ldd}, dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, outer};
     std::vector<PdItem> items;
     if ((rc = r.prepare()) || (outer == OTMB_OUTER_MEAN && (rc = r.mean_setup())) || (rc = r.source_norms(items)) || (rc = r.first_call(items))) return rc;
     for (bool more = true; more;)
@@ -697,28 +729,85 @@ int32_t otmb_op_periodic_dk_dev(otmb_op *op, int32_t adjoint, int64_t k, const d
     return r.report(cycles, defect, reason, msolve_iters);
 }
 
-int32_t otmb_op_periodic_dk(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle, int64_t first_slot,
-                            const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol,
-                            int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters) {
-    if (!op) return OTMB_ERR_INVALID_ARG;
+// the host variant: the start, every source block and D staged once, X home once
+static int32_t pd_run_host(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle, int64_t first_slot,
+                           int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol,
+                           int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
+                           int32_t outer, int64_t *msolve_iters) {
     int32_t rc;
-    if ((rc = pd_check(op, k, dt, theta, ncycle, first_slot, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect, reason, outer)) ||
-        (rc = sv_check_d(op, "otmb_op_periodic_dk", D, ldd)))
-        return rc;
     otmb_ctx *ctx = op->ctx;
     HIP_TRY(ctx, hipSetDevice(op->device));
     const i64 n = op->n;
     SvD dd;
-    if ((rc = op_reserve_xy(op, n, S ? n : 0, k)) || (rc = op_stage_dk(op, D, ldd, k, dd.p, dd.ld))) return rc;
-    double *dx = (double *)op->xs.p, *ds = S ? (double *)op->ys.p : nullptr;
+    if ((rc = op_reserve_xy(op, n, nsrc * n, k)) || (rc = op_stage_dk(op, D, ldd, k, dd.p, dd.ld))) return rc;
+    double *dx = (double *)op->xs.p;
+    std::vector<const double *> ds((size_t)nsrc);  // block j compact behind block j - 1
+    for (i64 j = 0; j < nsrc; ++j) ds[(size_t)j] = (const double *)op->ys.p + j * n * k;
     if (n > 0) {  // staged once, however many cycles
         if (use_x0 && (rc = op_upload(ctx, dx, X, ldx, n, k))) return rc;
-        if (S && (rc = op_upload(ctx, ds, S, lds, n, k))) return rc;
+        for (i64 j = 0; j < nsrc; ++j)
+            if ((rc = op_upload(ctx, (double *)op->ys.p + j * n * k, S[j], lds, n, k))) return rc;
     }
-    rc = otmb_op_periodic_dk_dev(op, adjoint, k, dd.p, dd.ld, dt, theta, ncycle, first_slot, ds, n, dx, n, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles,
-                                 cycles, defect, reason, outer, msolve_iters);
+    rc = pd_run_dev(op, adjoint, k, dd.p, dd.ld, dt, theta, ncycle, first_slot, substeps, nsrc, ds.data(), n, dx, n, use_x0, rtol, maxiter, precond, ptol, restart,
+                    maxcycles, cycles, defect, reason, outer, msolve_iters);
     if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED) return rc;
     return op_finish(ctx, rc, X, ldx, dx, n, k);
+}
+
+int32_t otmb_op_periodic_sched_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
+                                   int64_t first_slot, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx,
+                                   int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles,
+                                   int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    int32_t rc;
+    if ((rc = pd_check_call(op, "otmb_op_periodic_sched", true, k, D, ldd, dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, rtol, maxiter, precond,
+                            ptol, restart, maxcycles, cycles, defect, reason, outer)))
+        return rc;
+    return pd_run_dev(op, adjoint, k, D, ldd, dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart,
+                      maxcycles, cycles, defect, reason, outer, msolve_iters);
+}
+
+int32_t otmb_op_periodic_sched(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
+                               int64_t first_slot, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0,
+                               double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect,
+                               int32_t *reason, int32_t outer, int64_t *msolve_iters) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    int32_t rc;
+    if ((rc = pd_check_call(op, "otmb_op_periodic_sched", true, k, D, ldd, dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, rtol, maxiter, precond,
+                            ptol, restart, maxcycles, cycles, defect, reason, outer)))
+        return rc;
+    return pd_run_host(op, adjoint, k, D, ldd, dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart,
+                       maxcycles, cycles, defect, reason, outer, msolve_iters);
+}
+
+// the calls from before the schedule: substeps = 1, the one source or none
+int32_t otmb_op_periodic_dk_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
+                                int64_t first_slot, const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter,
+                                int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
+                                int32_t outer, int64_t *msolve_iters) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    const double *const one[1] = {S};
+    const int64_t nsrc = S ? 1 : 0;
+    int32_t rc;
+    if ((rc = pd_check_call(op, "otmb_op_periodic_dk", false, k, D, ldd, dt, theta, ncycle, first_slot, 1, nsrc, one, lds, X, ldx, rtol, maxiter, precond, ptol,
+                            restart, maxcycles, cycles, defect, reason, outer)))
+        return rc;
+    return pd_run_dev(op, adjoint, k, D, ldd, dt, theta, ncycle, first_slot, 1, nsrc, one, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles,
+                      cycles, defect, reason, outer, msolve_iters);
+}
+
+int32_t otmb_op_periodic_dk(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle, int64_t first_slot,
+                            const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol,
+                            int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    const double *const one[1] = {S};
+    const int64_t nsrc = S ? 1 : 0;
+    int32_t rc;
+    if ((rc = pd_check_call(op, "otmb_op_periodic_dk", false, k, D, ldd, dt, theta, ncycle, first_slot, 1, nsrc, one, lds, X, ldx, rtol, maxiter, precond, ptol,
+                            restart, maxcycles, cycles, defect, reason, outer)))
+        return rc;
+    return pd_run_host(op, adjoint, k, D, ldd, dt, theta, ncycle, first_slot, 1, nsrc, one, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles,
+                       cycles, defect, reason, outer, msolve_iters);
 }
 
 // the calls with one d for every column: ldd = 0 (otmb_op_periodic: OTMB_OUTER_NONE as well)

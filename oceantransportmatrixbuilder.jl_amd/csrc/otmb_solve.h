@@ -74,6 +74,9 @@ const char *sv_step_complaint(const otmb_op *op, double rtol, int64_t maxiter, d
                               int64_t first_slot);
 int32_t sv_report_open(otmb_ctx *ctx, const char *fmt, const char *const *names, i64 k, const int32_t *reason, const int64_t *count, const double *value,
                        const std::string &tail = std::string(), int nnames = 4);
+// sv_sched_complaint (otmb_step.hip): the first complaint about a schedule -- substeps, nsrc, the source blocks (S: nsrc pointers) and lds --
+//                  or null: what otmb_op_step_sched and otmb_op_periodic_sched add to the checks of the calls they extend.
+const char *sv_sched_complaint(const otmb_op *op, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds);
 
 // The solver, its preconditioner and the products read the values op->nz / op->val point at (the selected slot's).  SvValues points them at
 // another value set of the same pattern for its lifetime: sv_prec_prepare and sv_solve on an explicit value set (the periodic state's mean).

@@ -12,6 +12,11 @@
 // and each slot's preconditioner (σ + d, Jacobi's diagonal, for the lines u, the multipliers and the pivots) is computed on the slot's first
 // visit and kept in op->st for the rest of the call: d, σ, adjoint and the values are fixed inside one call, so nothing can go stale, and
 // the arrays have the bits a solve of its own would compute.  The host variant stages X, S and d once and downloads X once.
+//
+// otmb_op_step_sched[_dev] is the same loop with a schedule (StSrc): step t takes slot (first_slot + t / substeps) mod nslots, the source
+// block of that slot (or the one block, or none) and, with a scale, s·f for the step's factor f of the tracer -- one more multiplication in
+// the lane that holds s, before the line above touches it.  The factors are staged once per call behind the preconditioners; a kernel gets
+// the step's k of them as a device pointer (null: none).  Every other step call is this one with substeps = 1, at most one block, no scale.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -24,9 +29,10 @@
 struct StLine {  // the elementwise line's constants
     double sigma, theta, c;
 };
-// b from x, the finished fold w and the row's s and d (null: none; d: the tracer's own column, or the one all share).  One operation per
-// statement: the contract's association.
-__device__ __forceinline__ double st_line(const StLine &q, double x, double w, const double *__restrict__ d, i64 i, const double *__restrict__ s) {
+// b from x, the finished fold w and the row's s and d (null: none; d: the tracer's own column, or the one all share); f: the step's scale
+// of this tracer's source (null: none), sf = s * f before anything else touches s.  One operation per statement: the contract's association.
+__device__ __forceinline__ double st_line(const StLine &q, double x, double w, const double *__restrict__ d, i64 i, const double *__restrict__ s,
+                                          const double *__restrict__ f) {
     double e = w;
     if (d) {
         const double dx = d[i] * x;
@@ -35,22 +41,31 @@ __device__ __forceinline__ double st_line(const StLine &q, double x, double w, c
     const double ce = q.c * e;
     double a = q.sigma * x;
     if (s) {
-        const double st = *s / q.theta;
+        double sf = *s;
+        if (f) sf = sf * *f;
+        const double st = sf / q.theta;
         a = a + st;
     }
     return a - ce;
 }
 
-// ---- θ = 1: b = σ·x + s, no matrix read ----------------------------------------------------------------------------------------------
+// ---- θ = 1: b = σ·x + s, no matrix read.  f (here and below, the last argument): the step's scales of this block's tracers, f[c] tracer c's
+// (null: none)
 template <int KB>
 __global__ __launch_bounds__(256) void st_stream_kernel(i64 n, double sigma, const double *__restrict__ X, i64 ldx, const double *__restrict__ S, i64 lds,
-                                                        double *__restrict__ B, i64 ldb) {
+                                                        double *__restrict__ B, i64 ldb, const double *__restrict__ f = nullptr) {
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
 #pragma unroll
     for (int c = 0; c < KB; ++c) {
         const double a = sigma * X[i + c * ldx];
-        B[i + c * ldb] = S ? a + S[i + c * lds] : a;
+        if (S) {
+            double sf = S[i + c * lds];
+            if (f) sf = sf * f[c];
+            B[i + c * ldb] = a + sf;
+        } else {
+            B[i + c * ldb] = a;
+        }
     }
 }
 
@@ -58,7 +73,8 @@ __global__ __launch_bounds__(256) void st_stream_kernel(i64 n, double sigma, con
 template <int KB, bool PC = false>
 __global__ __launch_bounds__(256) void st_rows_kernel(StLine q, const double *__restrict__ val, const int *__restrict__ col, const i64 *__restrict__ sbase,
                                                       const int *__restrict__ elen, i64 n, const double *__restrict__ d, const double *__restrict__ X, i64 ldx,
-                                                      const double *__restrict__ S, i64 lds, double *__restrict__ B, i64 ldb, i64 ldd = 0) {
+                                                      const double *__restrict__ S, i64 lds, double *__restrict__ B, i64 ldb, i64 ldd = 0,
+                                                      const double *__restrict__ f = nullptr) {
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int len = elen[i];
@@ -71,14 +87,15 @@ __global__ __launch_bounds__(256) void st_rows_kernel(StLine q, const double *__
         for (int c = 0; c < KB; ++c) w[c] = w[c] + a * X[j + c * ldx];
     });
 #pragma unroll
-    for (int c = 0; c < KB; ++c) B[i + c * ldb] = st_line(q, X[i + c * ldx], w[c], d ? d + (PC ? c * ldd : 0) : nullptr, i, S ? S + i + c * lds : nullptr);
+    for (int c = 0; c < KB; ++c) B[i + c * ldb] = st_line(q, X[i + c * ldx], w[c], d ? d + (PC ? c * ldd : 0) : nullptr, i, S ? S + i + c * lds : nullptr, f ? f + c : nullptr);
 }
 
-// one workgroup per long row, lane c folds tracer c (groups of 64 tracers)
+// one workgroup per long row, lane c folds tracer c (groups of 64 tracers) and reads its scale f[c]: f is the whole step's, not a block's
 template <bool PC = false>
 __global__ __launch_bounds__(64) void st_long_kernel(StLine q, const double *__restrict__ val, const int *__restrict__ col, const i64 *__restrict__ lrows,
                                                      const i64 *__restrict__ loff, i64 ell, int k, const double *__restrict__ d, const double *__restrict__ X,
-                                                     i64 ldx, const double *__restrict__ S, i64 lds, double *__restrict__ B, i64 ldb, i64 ldd = 0) {
+                                                     i64 ldx, const double *__restrict__ S, i64 lds, double *__restrict__ B, i64 ldb, i64 ldd = 0,
+                                                     const double *__restrict__ f = nullptr) {
     __shared__ double sv[SP_TCH];
     __shared__ int sc[SP_TCH];
     const int lane = threadIdx.x;
@@ -88,7 +105,7 @@ __global__ __launch_bounds__(64) void st_long_kernel(StLine q, const double *__r
         const int c = c0 + lane;
         double w = 0.0;
         op_fold_long_row(val, col, b0, len, sv, sc, lane, c < k, [&](double a, i64 j) { w = w + a * X[j + c * ldx]; });
-        if (c < k) B[i + c * ldb] = st_line(q, X[i + c * ldx], w, d ? d + (PC ? c * ldd : 0) : nullptr, i, S ? S + i + c * lds : nullptr);
+        if (c < k) B[i + c * ldb] = st_line(q, X[i + c * ldx], w, d ? d + (PC ? c * ldd : 0) : nullptr, i, S ? S + i + c * lds : nullptr, f ? f + c : nullptr);
     }
 }
 
@@ -96,7 +113,7 @@ __global__ __launch_bounds__(64) void st_long_kernel(StLine q, const double *__r
 template <int KB, bool PC = false>
 __global__ __launch_bounds__(64) void st_cols_kernel(StLine q, const i64 *__restrict__ cp, const int *__restrict__ rv, const double *__restrict__ nz, i64 n,
                                                      const double *__restrict__ d, const double *__restrict__ X, i64 ldx, const double *__restrict__ S, i64 lds,
-                                                     double *__restrict__ B, i64 ldb, i64 ldd = 0) {
+                                                     double *__restrict__ B, i64 ldb, i64 ldd = 0, const double *__restrict__ f = nullptr) {
     __shared__ double sv[SP_TCH];
     __shared__ int sr[SP_TCH];
     const int lane = threadIdx.x;
@@ -112,35 +129,38 @@ __global__ __launch_bounds__(64) void st_cols_kernel(StLine q, const i64 *__rest
 #pragma unroll
     for (int c = 0; c < KB; ++c) {
         const double w = 0.0 + tmp[c];  // (the product's last step, y = +0.0 + tmp·1: a sum of -0.0 becomes +0.0)
-        B[colm + c * ldb] = st_line(q, X[colm + c * ldx], w, d ? d + (PC ? c * ldd : 0) : nullptr, colm, S ? S + colm + c * lds : nullptr);
+        B[colm + c * ldb] = st_line(q, X[colm + c * ldx], w, d ? d + (PC ? c * ldd : 0) : nullptr, colm, S ? S + colm + c * lds : nullptr,
+                                    f ? f + c : nullptr);
     }
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
-// B (n x k, leading dimension n) = the step's right-hand side from X, with the SELECTED slot's matrix
-static void st_rhs(otmb_op *op, int adjoint, i64 k, const StLine &q, const SvD &dk, const double *X, i64 ldx, const double *S, i64 lds, double *B) {
+// B (n x k, leading dimension n) = the step's right-hand side from X, with the SELECTED slot's matrix; f: the step's k scales on the device
+// (null: none), of which register block c0 reads f + c0
+static void st_rhs(otmb_op *op, int adjoint, i64 k, const StLine &q, const SvD &dk, const double *X, i64 ldx, const double *S, i64 lds, const double *f,
+                   double *B) {
     hipStream_t st = op->ctx->stream;
     const i64 n = op->n, ldd = dk.percol() ? dk.ld : 0;
     const double *d = dk.p;
     if (q.theta == 1.0) {
         op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
             hipLaunchKernelGGL((st_stream_kernel<decltype(kb)::value>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, q.sigma, X + c0 * ldx, ldx,
-                               S ? S + c0 * lds : nullptr, lds, B + c0 * n, n);
+                               S ? S + c0 * lds : nullptr, lds, B + c0 * n, n, S && f ? f + c0 : nullptr);
         });
         return;
     }
     if (!adjoint && op->nlong > 0)
         hipLaunchKernelGGL((ldd ? st_long_kernel<true> : st_long_kernel<false>), dim3((unsigned)op->nlong), dim3(64), 0, st, q, (const double *)op->val.p, (const int *)op->col.p,
-                           (const i64 *)op->lrows.p, (const i64 *)op->loff.p, op->ell, (int)k, d, X, ldx, S, lds, B, n, ldd);
+                           (const i64 *)op->lrows.p, (const i64 *)op->loff.p, op->ell, (int)k, d, X, ldx, S, lds, B, n, ldd, S ? f : nullptr);
     op_blocks<SV_KB>(0, k, [&](auto kb, i64 c0) {
         constexpr int KB = decltype(kb)::value;
-        const double *Sc = S ? S + c0 * lds : nullptr, *dc = d ? d + c0 * ldd : nullptr;
+        const double *Sc = S ? S + c0 * lds : nullptr, *dc = d ? d + c0 * ldd : nullptr, *fc = S && f ? f + c0 : nullptr;
         if (adjoint)
             hipLaunchKernelGGL((ldd ? st_cols_kernel<KB, true> : st_cols_kernel<KB, false>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, q, (const i64 *)op->cp.p, (const int *)op->rv.p,
-                               (const double *)op->nz.p, n, dc, X + c0 * ldx, ldx, Sc, lds, B + c0 * n, n, ldd);
+                               (const double *)op->nz.p, n, dc, X + c0 * ldx, ldx, Sc, lds, B + c0 * n, n, ldd, fc);
         else
             hipLaunchKernelGGL((ldd ? st_rows_kernel<KB, true> : st_rows_kernel<KB, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, q, (const double *)op->val.p, (const int *)op->col.p,
-                               (const i64 *)op->sbase.p, (const int *)op->elen.p, n, dc, X + c0 * ldx, ldx, Sc, lds, B + c0 * n, n, ldd);
+                               (const i64 *)op->sbase.p, (const int *)op->elen.p, n, dc, X + c0 * ldx, ldx, Sc, lds, B + c0 * n, n, ldd, fc);
     });
 }
 
@@ -155,22 +175,56 @@ struct StObs {  // what otmb_op_step_obs adds to a step call: q observers W (obs
 };
 static const StObs ST_PLAIN = {0, nullptr, 0, nullptr, nullptr, nullptr, 0};  // no observers, no mean
 
-static int32_t st_check(otmb_op *op, int64_t k, double dt, double theta, int64_t nsteps, int64_t first_slot, const double *S, int64_t lds, double *X,
-                        int64_t ldx, double rtol, int64_t maxiter, int32_t precond, const int64_t *steps_done, const int64_t *iters, const double *relres,
-                        const int32_t *reason, const StObs &o) {
+// The schedule of otmb_op_step_sched: step t runs with slot (first_slot + t / substeps) mod nslots and the source block at(slot) of nsrc
+// (0: none; 1: block 0 on every step; nslots: the slot's), each n x k with leading dimension lds; scale: nsteps·k HOST values or null.
+struct StSrc {
+    i64 substeps, nsrc;
+    const double *const *S;
+    i64 lds;
+    const double *scale;
+    const double *at(i64 slot) const { return nsrc == 0 ? nullptr : S[nsrc == 1 ? 0 : slot]; }
+};
+
+static int32_t st_check(otmb_op *op, int64_t k, double dt, double theta, int64_t nsteps, int64_t first_slot, const StSrc &src, double *X, int64_t ldx, double rtol,
+                        int64_t maxiter, int32_t precond, const int64_t *steps_done, const int64_t *iters, const double *relres, const int32_t *reason,
+                        const StObs &o) {
     const char *more = !steps_done || (nsteps > 0 && (!iters || !relres || !reason))
                            ? "null argument"
                            : sv_step_complaint(op, rtol, maxiter, dt, theta, nsteps >= 0, "nsteps must be >= 0", first_slot);
     if (!more) more = ob_complaint(op, true, nsteps, o.q, o.W, o.ldw, o.obs, o.tw, o.Xbar, o.ldm);
-    return sv_check_step(op, precond, k, S, lds, X, ldx, more);
+    return sv_check_step(op, precond, k, src.nsrc > 0 && src.S ? src.S[0] : nullptr, src.lds, X, ldx, more);
 }
 
-// The ONE loop behind otmb_op_step[_dev] (o = ST_PLAIN) and otmb_op_step_obs[_dev]: device pointers, the arguments checked.  After a step
-// whose solve left every column converged the observation pass reads X where the solve left it and its fold writes the step's q x k block
-// of o.obs; nothing of it waits for the host.
-static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, double dt, double theta, int64_t nsteps, int64_t first_slot, const double *S,
-                      int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters, double *relres,
-                      int32_t *reason, const StObs &o) {
+// What the scheduled calls add to the checks of the calls they extend (sv_sched_complaint, shared with otmb_op_periodic_sched), and the
+// step's own: a scale needs a source and finite entries.
+const char *sv_sched_complaint(const otmb_op *op, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds) {
+    if (substeps < 1) return "substeps must be >= 1";
+    if (nsrc != 0 && nsrc != 1 && nsrc != (i64)op->slots.size()) return "nsrc must be 0, 1 or the number of slots";
+    if (nsrc > 0) {
+        if (!S) return "S is null with nsrc > 0";
+        for (i64 j = 0; j < nsrc; ++j)
+            if (!S[j]) return "a source block is null";
+        if (lds < op->n) return "lds is smaller than the rows of S";
+    }
+    return nullptr;
+}
+static int32_t st_check_sched(otmb_op *op, int64_t k, int64_t nsteps, const StSrc &src) {
+    const char *more = sv_sched_complaint(op, src.substeps, src.nsrc, src.S, src.lds);
+    if (!more && src.scale) {
+        if (src.nsrc == 0) more = "scale needs a source (nsrc > 0)";
+        for (i64 e = 0; !more && e < nsteps * k; ++e)
+            if (!std::isfinite(src.scale[e])) more = "a scale value is not finite";
+    }
+    return more ? otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, (std::string("otmb_op_step_sched: ") + more).c_str()) : OTMB_OK;
+}
+
+// The ONE loop behind every step call: otmb_op_step_sched[_dev], and otmb_op_step_dk[_dev] with what is layered on it (substeps = 1, at
+// most one source, no scale; o = ST_PLAIN: no record).  Device pointers (src.S: a host array of them; src.scale: host values), the arguments
+// checked.  After a step whose solve left every column converged the observation pass reads X where the solve left it and its fold writes
+// the step's q x k block of o.obs; nothing of it waits for the host.
+static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, double dt, double theta, int64_t nsteps, int64_t first_slot, const StSrc &src,
+                      double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters, double *relres, int32_t *reason,
+                      const StObs &o) {
     int32_t rc;
     *steps_done = 0;
     if (nsteps == 0) return OTMB_OK;
@@ -188,13 +242,18 @@ static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, dou
     const bool lines = precond == OTMB_PRECOND_LINES, watch = o.q > 0 || o.Xbar;
     const double tdt = theta * dt;
     const StLine q = {1.0 / tdt, theta, (1.0 - theta) / theta};
-    // op->st: B, then one preconditioner per slot the call visits (per column where every tracer has its own d)
-    const i64 used = std::min(nsteps, nslots), kc = sv_prec_cols(d, k);
+    // op->st: B, then one preconditioner per slot the call visits (per column where every tracer has its own d), then the scales (nsteps x k)
+    const i64 used = std::min((nsteps - 1) / src.substeps + 1, nslots), kc = sv_prec_cols(d, k);
     const size_t per = sv_prec_doubles(n, lines, kc);
-    if ((double)n * (double)k + (double)used * (double)per >= 1.0e18) return otmb_fail(ctx, OTMB_ERR_ALLOC, "step: the workspace's size overflows");
-    if ((rc = otmb_reserve(ctx, op->st, ((size_t)(n * k) + (size_t)used * per) * 8))) return rc;
+    const double nscale = src.scale ? (double)nsteps * (double)k : 0.0;
+    if ((double)n * (double)k + (double)used * (double)per + nscale >= 1.0e18) return otmb_fail(ctx, OTMB_ERR_ALLOC, "step: the workspace's size overflows");
+    if ((rc = otmb_reserve(ctx, op->st, ((size_t)(n * k) + (size_t)used * per + (size_t)nscale) * 8))) return rc;
     if (watch && (rc = ob_reserve(op, k, o.q))) return rc;
-    double *B = (double *)op->st.p, *pool = B + n * k;
+    double *B = (double *)op->st.p, *pool = B + n * k, *fdev = src.scale ? pool + (size_t)used * per : nullptr;
+    if (fdev) {  // staged once per call; the first preconditioner's setup waits for the stream before the call can return
+        HIP_TRY(ctx, hipMemcpyAsync(fdev, src.scale, (size_t)(nsteps * k) * 8, hipMemcpyHostToDevice, ctx->stream));
+        ctx->uploaded_bytes += 8 * nsteps * k;
+    }
     std::vector<SvPrec> prec((size_t)nslots, SvPrec{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0});
     i64 taken = 0;
     struct Reselect {  // the caller's selection comes back on every return
@@ -203,9 +262,9 @@ static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, dou
         ~Reselect() { (void)otmb_op_select_slot(op, slot); }
     } back{op, op->sel};
     for (i64 t = 0; t < nsteps; ++t) {
-        const i64 slot = (first_slot + t) % nslots;
+        const i64 slot = (first_slot + t / src.substeps) % nslots;
         if ((rc = otmb_op_select_slot(op, slot))) return rc;
-        const auto here = [&](int32_t status) {  // the failure's message names the step and the slot
+        const auto here = [&](int32_t status) {  // the failure's message names the step and the slot the schedule gave it
             ctx->err += " (step " + std::to_string(t) + ", slot " + std::to_string(slot) + ")";
             return status;
         };
@@ -214,7 +273,7 @@ static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, dou
             p = sv_prec_carve(pool + (size_t)(taken++) * per, n, lines, kc, d.percol());
             if ((rc = sv_prec_prepare(op, adjoint, precond, d, q.sigma, p))) return here(rc);
         }
-        st_rhs(op, adjoint, k, q, d, X, ldx, S, lds, B);
+        st_rhs(op, adjoint, k, q, d, X, ldx, src.at(slot), src.lds, fdev ? fdev + t * k : nullptr, B);
         HIP_TRY(ctx, hipGetLastError());
         if ((rc = sv_solve(op, adjoint, k, p, B, n, X, ldx, 1, rtol, maxiter, iters + t * k, relres + t * k, reason + t * k, precond))) return here(rc);
         if (watch) {
@@ -226,10 +285,10 @@ static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, dou
     return OTMB_OK;
 }
 
-// The host variant of the loop: X, S, d, W staged once; X, the written rows of obs and Xbar come home once.
+// The host variant of the loop: X, every source block, d, W staged once; X, the written rows of obs and Xbar come home once.
 static int32_t st_run_host(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, double dt, double theta, int64_t nsteps, int64_t first_slot,
-                           const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
-                           int64_t *iters, double *relres, int32_t *reason, const StObs &o) {
+                           const StSrc &src, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters,
+                           double *relres, int32_t *reason, const StObs &o) {
     int32_t rc;
     *steps_done = 0;
     const i64 n = op->n;
@@ -237,11 +296,14 @@ static int32_t st_run_host(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d
     otmb_ctx *ctx = op->ctx;
     HIP_TRY(ctx, hipSetDevice(op->device));
     SvD dd;
-    if ((rc = op_reserve_xy(op, n, S ? n : 0, k)) || (rc = op_stage_dk(op, d.p, d.ld, k, dd.p, dd.ld))) return rc;
-    double *dx = (double *)op->xs.p, *ds = S ? (double *)op->ys.p : nullptr;
+    if ((rc = op_reserve_xy(op, n, src.nsrc * n, k)) || (rc = op_stage_dk(op, d.p, d.ld, k, dd.p, dd.ld))) return rc;
+    double *dx = (double *)op->xs.p;
+    std::vector<const double *> ds((size_t)src.nsrc);  // block j compact behind block j - 1
+    for (i64 j = 0; j < src.nsrc; ++j) ds[(size_t)j] = (const double *)op->ys.p + j * n * k;
     if (n > 0) {  // staged once, however many steps
         if ((rc = op_upload(ctx, dx, X, ldx, n, k))) return rc;
-        if (S && (rc = op_upload(ctx, ds, S, lds, n, k))) return rc;
+        for (i64 j = 0; j < src.nsrc; ++j)
+            if ((rc = op_upload(ctx, (double *)op->ys.p + j * n * k, src.S[j], src.lds, n, k))) return rc;
     }
     StObs od = ST_PLAIN;
     if (o.q > 0 || o.Xbar) {  // op->oh: obs (q x k x nsteps) | W (n x q) | Xbar (n x k), compact
@@ -251,7 +313,8 @@ static int32_t st_run_host(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d
         if (o.q > 0 && n > 0 && (rc = op_upload(ctx, dw, o.W, o.ldw, n, o.q))) return rc;
         od = {o.q, o.q > 0 ? dw : nullptr, n, o.q > 0 ? dobs : nullptr, o.tw, o.Xbar ? dm : nullptr, n};
     }
-    rc = st_run(op, adjoint, k, dd, dt, theta, nsteps, first_slot, ds, n, dx, n, rtol, maxiter, precond, steps_done, iters, relres, reason, od);
+    const StSrc sd = {src.substeps, src.nsrc, ds.data(), n, src.scale};
+    rc = st_run(op, adjoint, k, dd, dt, theta, nsteps, first_slot, sd, dx, n, rtol, maxiter, precond, steps_done, iters, relres, reason, od);
     // X comes back when it holds an answer: every step done, a step's last iterates, or the state before a slot whose preconditioner is singular
     if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED && !(rc == OTMB_ERR_SINGULAR_PRECONDITIONER && *steps_done > 0)) return rc;
     // ... and with it the observations of the completed steps and their mean
@@ -263,32 +326,56 @@ static int32_t st_run_host(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d
     return op_finish(ctx, rc, X, ldx, dx, n, k);
 }
 
+// one body for the two variants of a call (DEV: device pointers); call: the export named by the refusals of D / ldd; sched: the scheduled
+// call's own checks, after those of the call it extends
+template <bool DEV>
+static int32_t st_call(otmb_op *op, const char *call, bool sched, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta,
+                       int64_t nsteps, int64_t first_slot, const StSrc &src, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond,
+                       int64_t *steps_done, int64_t *iters, double *relres, int32_t *reason, const StObs &o) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    int32_t rc;
+    if ((rc = st_check(op, k, dt, theta, nsteps, first_slot, src, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o)) ||
+        (rc = sv_check_d(op, call, D, ldd)) || (sched && (rc = st_check_sched(op, k, nsteps, src))))
+        return rc;
+    return (DEV ? st_run : st_run_host)(op, adjoint, k, SvD{D, ldd}, dt, theta, nsteps, first_slot, src, X, ldx, rtol, maxiter, precond, steps_done, iters, relres,
+                                        reason, o);
+}
+
 extern "C" {
 
+int32_t otmb_op_step_sched_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t nsteps,
+                               int64_t first_slot, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, const double *scale, double *X,
+                               int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters, double *relres,
+                               int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw, double *Xbar, int64_t ldm) {
+    return st_call<true>(op, "otmb_op_step_sched", true, adjoint, k, D, ldd, dt, theta, nsteps, first_slot, StSrc{substeps, nsrc, S, lds, scale}, X, ldx, rtol,
+                         maxiter, precond, steps_done, iters, relres, reason, StObs{q, W, ldw, obs, tw, Xbar, ldm});
+}
+
+int32_t otmb_op_step_sched(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t nsteps,
+                           int64_t first_slot, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, const double *scale, double *X, int64_t ldx,
+                           double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters, double *relres, int32_t *reason, int64_t q,
+                           const double *W, int64_t ldw, double *obs, const double *tw, double *Xbar, int64_t ldm) {
+    return st_call<false>(op, "otmb_op_step_sched", true, adjoint, k, D, ldd, dt, theta, nsteps, first_slot, StSrc{substeps, nsrc, S, lds, scale}, X, ldx, rtol,
+                          maxiter, precond, steps_done, iters, relres, reason, StObs{q, W, ldw, obs, tw, Xbar, ldm});
+}
+
+// the calls from before the schedule: substeps = 1, the one source or none, no scale
 int32_t otmb_op_step_dk_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t nsteps,
                             int64_t first_slot, const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond,
                             int64_t *steps_done, int64_t *iters, double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs,
                             const double *tw, double *Xbar, int64_t ldm) {
-    if (!op) return OTMB_ERR_INVALID_ARG;
-    const StObs o = {q, W, ldw, obs, tw, Xbar, ldm};
-    int32_t rc;
-    if ((rc = st_check(op, k, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o)) ||
-        (rc = sv_check_d(op, "otmb_op_step_dk", D, ldd)))
-        return rc;
-    return st_run(op, adjoint, k, SvD{D, ldd}, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o);
+    const double *const one[1] = {S};
+    return st_call<true>(op, "otmb_op_step_dk", false, adjoint, k, D, ldd, dt, theta, nsteps, first_slot, StSrc{1, S ? 1 : 0, one, lds, nullptr}, X, ldx, rtol,
+                         maxiter, precond, steps_done, iters, relres, reason, StObs{q, W, ldw, obs, tw, Xbar, ldm});
 }
 
 int32_t otmb_op_step_dk(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t nsteps, int64_t first_slot,
                         const double *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
                         int64_t *iters, double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw,
                         double *Xbar, int64_t ldm) {
-    if (!op) return OTMB_ERR_INVALID_ARG;
-    const StObs o = {q, W, ldw, obs, tw, Xbar, ldm};
-    int32_t rc;
-    if ((rc = st_check(op, k, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o)) ||
-        (rc = sv_check_d(op, "otmb_op_step_dk", D, ldd)))
-        return rc;
-    return st_run_host(op, adjoint, k, SvD{D, ldd}, dt, theta, nsteps, first_slot, S, lds, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o);
+    const double *const one[1] = {S};
+    return st_call<false>(op, "otmb_op_step_dk", false, adjoint, k, D, ldd, dt, theta, nsteps, first_slot, StSrc{1, S ? 1 : 0, one, lds, nullptr}, X, ldx, rtol,
+                          maxiter, precond, steps_done, iters, relres, reason, StObs{q, W, ldw, obs, tw, Xbar, ldm});
 }
 
 // the calls with one d for every tracer: ldd = 0 (otmb_op_step: no observers, no mean either)

@@ -792,6 +792,11 @@ class DeviceAssembler:
         grid's water columns."""
         return self._slotted(matrix).op.step(X, **kw)
 
+    def step_tracers_sched(self, X, *, matrix="T", **kw):
+        """Operator.step_sched on the resident operator over `matrix`: step_tracers with sub-steps per slot (substeps), a source per kept slot
+        (a list of tensors) and a history (source_scale)."""
+        return self._slotted(matrix).op.step_sched(X, **kw)
+
     def combine_slots(self, weights, dst, matrix="T"):
         """Operator.combine_slots on the resident operator over `matrix`: slot dst = Σ_s weights[s]·(slot s) over the slots keep_slot() filled
         (the annual mean of the kept months).  The written slot is not the resident result: when it is the selected one, the operator counts
@@ -806,6 +811,10 @@ class DeviceAssembler:
         """Operator.periodic on the resident operator over `matrix`: the periodic state of the cycle through the slots keep_slot() filled, as
         they are (step_tracers says which slots those are); outer="mean" preconditions the outer iteration with their cycle mean."""
         return self._slotted(matrix).op.periodic(source, **kw)
+
+    def periodic_tracers_sched(self, source, *, matrix="T", **kw):
+        """Operator.periodic_sched on the resident operator over `matrix`: periodic_tracers with sub-steps per slot and a source per kept slot."""
+        return self._slotted(matrix).op.periodic_sched(source, **kw)
 
     def _kept_steady(self):
         """The operators a step of this loop does not store: those the last call kept, or -- after a full write that left the promise live -- those

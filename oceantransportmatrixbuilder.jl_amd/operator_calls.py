@@ -165,6 +165,25 @@ class OperatorCalls:
             self._assign(X, x0)
         return X
 
+    def _sources(self, source, B, of):
+        """(the blocks column-major, their common leading dimension) of a source given as a list or tuple of arrays of B's shape -- one for
+        every step, or one per slot: the scheduled calls' array of pointers (include/otmb.h).  Blocks whose leading dimensions differ are
+        copied compactly; nothing is stacked."""
+        nslots = self.slots[0]
+        if len(source) not in (1, nslots):
+            raise capi.OtmbError(11, f"DimensionMismatch: {len(source)} source blocks, expected 1 or one per slot ({nslots})")
+        m = self.shape[0]
+        blocks = [self._matrix(self._like(a, "source", B, of), m) for a in source]
+        if len({ld for _, ld in blocks}) > 1:
+            blocks = [(a, ld) if ld == max(m, 1) else (self._start(a, B, of), max(m, 1)) for a, ld in blocks]
+        return [a for a, _ in blocks], blocks[0][1]
+
+    def _source_args(self, blocks, lds):
+        """(nsrc, the array of the blocks' addresses or None, lds) as the scheduled exports take them."""
+        if not blocks:
+            return [0, None, lds]
+        return [len(blocks), (C.c_void_p * len(blocks))(*[self._ptr(a) for a in blocks]), lds]
+
     def precondition(self, Y, d=None, sigma=0.0, adjoint=False, precond="lines"):
         """Z = P⁻¹·Y with the preconditioner solve(..., precond=precond) uses for M = σ·I + diag(d) + A (adjoint: Aᵀ) (otmb_op_precond): for a
         Krylov method of the caller's own.  Y: 1-D or 2-D (n x k); d as in solve; returns a new Z of Y's shape (2-D: column-major)."""
@@ -227,15 +246,41 @@ class OperatorCalls:
         raise OtmbError.  Nothing but the solver's column records travels to the host.
         observe: W, n x q (or n values: one observer) -> info.observations, (steps_done, k, q); time_weights: nsteps finite host values ->
         info.mean = Σ_t time_weights[t]·X_t, n x k.  With either the call is otmb_op_step_obs (include/otmb.h states the order of the sums
-        and the mean's fold); with neither it is the plain one, and info.observations and info.mean are None."""
+        and the mean's fold); with neither it is the plain one, and info.observations and info.mean are None.
+        source may also be a list or tuple of arrays of X's shape, one (every step takes it) or one per slot (step t takes the block of its
+        slot: the source of the month): the call is then step_sched's, which also has sub-steps and a history."""
+        return self.step_sched(X, dt=dt, theta=theta, nsteps=nsteps, first_slot=first_slot, source=source, d=d, rtol=rtol, maxiter=maxiter,
+                               adjoint=adjoint, precond=precond, observe=observe, time_weights=time_weights)
+
+    def step_sched(self, X, *, dt, theta=1.0, nsteps=1, first_slot=0, substeps=1, source=None, source_scale=None, d=None, rtol=1e-10, maxiter=10000,
+                   adjoint=False, precond="jacobi", observe=None, time_weights=None):
+        """step with a schedule for the time axis (otmb_op_step_sched; include/otmb.h states the contract).  substeps = m >= 1: step t runs
+        with slot (first_slot + t // m) mod nslots -- m implicit steps inside January before February begins; each slot's preconditioner is
+        made once and reused by its sub-steps.  source: None, an array of X's shape, or a list or tuple of such arrays, one (every step) or one
+        per slot (step t takes its slot's: a seasonal source); for device.Operator the blocks are separate tensors, and nothing is stacked.
+        source_scale: None, or host values of shape (nsteps, k) -- (nsteps,) for a 1-D X --: the source of step t and tracer c is
+        source·source_scale[t, c], a fixed pattern times a history (CFC-11, SF6, bomb radiocarbon).  Step t has the bits of step(nsteps=1,
+        first_slot=its slot, source=source·source_scale[t]) from the state before it.  Everything else, and what is returned, is step's;
+        with substeps=1, a single array and no source_scale the call IS step's, made through the same exports."""
         self._live()
         pc = capi.precond_code(precond)
         X, k, Xc, _ = self._state(X, "X")
         dc, dargs = self._d(d, X, "X")
         (m, n), ld = self.shape, max(self.shape[0], 1)
-        Sc, lds = None, ld
-        if source is not None:
+        Sc, lds, blocks = None, ld, None
+        if isinstance(source, (list, tuple)):
+            blocks, lds = self._sources(source, X, "X")
+        elif source is not None:
             Sc, lds = self._matrix(self._like(source, "source", X, "X"), m)
+        scale = None
+        if source_scale is not None:
+            if source is None:
+                raise capi.OtmbError(11, "invalid argument: source_scale needs a source")
+            scale = np.ascontiguousarray(source_scale, dtype=np.float64)
+            want = (max(int(nsteps), 0),) + tuple(X.shape[1:])
+            if scale.shape != want:
+                raise capi.OtmbError(11, f"DimensionMismatch: source_scale of {scale.shape}, expected {want}")
+        sched = blocks is not None or scale is not None or int(substeps) != 1
         q, Wc, ldw, obs, tw, mean = 0, None, max(n, 1), None, None, None
         if observe is not None:
             W, q = observers(self._array(observe, "observe"), n)
@@ -248,10 +293,15 @@ class OperatorCalls:
         self._assign(Xn, Xc)
         iters, relres, reason = step_arrays(nsteps, k)
         done = C.c_int64(0)
-        args = [int(bool(adjoint)), k, *dargs, float(dt), float(theta), int(nsteps), int(first_slot), self._ptr(Sc), lds, self._ptr(Xn), ld, float(rtol),
+        if sched:  # the schedule in place of S, lds; one d for every tracer is ldd = 0
+            dargs = dargs if len(dargs) == 2 else dargs + [0]
+            sargs = [int(substeps), *self._source_args([Sc] if blocks is None and Sc is not None else blocks, lds), None if scale is None else scale.ctypes.data]
+        else:
+            sargs = [self._ptr(Sc), lds]
+        args = [int(bool(adjoint)), k, *dargs, float(dt), float(theta), int(nsteps), int(first_slot), *sargs, self._ptr(Xn), ld, float(rtol),
                 int(maxiter), pc, C.byref(done), iters.ctypes.data, relres.ctypes.data, reason.ctypes.data]
-        record = len(dargs) == 2 or obs is not None or tw is not None
-        name = "otmb_op_step_dk" if len(dargs) == 2 else "otmb_op_step_obs" if record else "otmb_op_step"
+        record = sched or len(dargs) == 2 or obs is not None or tw is not None
+        name = "otmb_op_step_sched" if sched else "otmb_op_step_dk" if len(dargs) == 2 else "otmb_op_step_obs" if record else "otmb_op_step"
         if record:  # the record's arguments; q = 0 and nulls make the per-column call the plain step
             args += [q, self._ptr(Wc), ldw, self._ptr(obs), None if tw is None else tw.ctypes.data, self._ptr(mean), ld]
         rc = self._call(name, *args)
@@ -268,19 +318,43 @@ class OperatorCalls:
         the host reads a few scalars a column; no vector travels.
         outer = "none" (default) | "mean": with "mean" the outer GMRES is flexible and preconditioned by the cycle-mean operator
         (otmb_op_periodic_pc with OTMB_OUTER_MEAN; include/otmb.h states the method) -- fewer cycles, one solve with the mean matrix per
-        iteration (info.msolve_iters; zero with "none")."""
+        iteration (info.msolve_iters; zero with "none").
+        source may also be a list or tuple of arrays of one shape, one or one per slot: the call is then periodic_sched's."""
+        return self.periodic_sched(source, dt=dt, ncycle=ncycle, theta=theta, first_slot=first_slot, d=d, x0=x0, rtol=rtol, maxiter=maxiter,
+                                   adjoint=adjoint, precond=precond, ptol=ptol, restart=restart, maxcycles=maxcycles, outer=outer)
+
+    def periodic_sched(self, source, *, dt, ncycle, theta=1.0, first_slot=0, substeps=1, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False,
+                       precond="jacobi", ptol=1e-8, restart=30, maxcycles=1000, outer="none"):
+        """periodic with a schedule (otmb_op_periodic_sched; include/otmb.h): F is step_sched over ncycle steps with `substeps` and `source`,
+        an array or a list or tuple of arrays of one shape, one or one per slot (a seasonal source; the cycle map stays affine).  A column is
+        answered with zero only when it is zero in every block; with outer="mean" the mean's weights are the slots' shares of the cycle's
+        steps.  No source_scale: a history is not periodic.  Everything else, and what is returned, is periodic's; with substeps=1 and a
+        single array the call IS periodic's, made through the same exports."""
         oc = capi.outer_code(outer)
         self._live()
         pc = capi.precond_code(precond)
-        S, k, Sc, lds = self._state(source, "source")
+        blocks = None
+        if isinstance(source, (list, tuple)):
+            if not source:
+                raise capi.OtmbError(11, "DimensionMismatch: 0 source blocks, expected 1 or one per slot")
+            S, k, Sc, lds = self._state(source[0], "source")
+            blocks, lds = self._sources(source, S, "source")
+        else:
+            S, k, Sc, lds = self._state(source, "source")
+        sched = blocks is not None or int(substeps) != 1
         dc, dargs = self._d(d, S, "source")
         X = self._start(x0, S, "source")
         cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
-        args = [int(bool(adjoint)), k, *dargs, float(dt), float(theta), int(ncycle), int(first_slot), self._ptr(Sc), lds, self._ptr(X),
+        if sched:  # the schedule in place of S, lds; one d for every column is ldd = 0
+            dargs = dargs if len(dargs) == 2 else dargs + [0]
+            sargs = [int(substeps), *self._source_args([Sc] if blocks is None else blocks, lds)]
+        else:
+            sargs = [self._ptr(Sc), lds]
+        args = [int(bool(adjoint)), k, *dargs, float(dt), float(theta), int(ncycle), int(first_slot), *sargs, self._ptr(X),
                 max(self.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), pc, float(ptol), int(restart), int(maxcycles), cycles.ctypes.data,
                 defect.ctypes.data, reason.ctypes.data]
-        outer_args = len(dargs) == 2 or oc != capi.OUTERS["none"]
-        name = "otmb_op_periodic_dk" if len(dargs) == 2 else "otmb_op_periodic_pc" if outer_args else "otmb_op_periodic"
+        outer_args = sched or len(dargs) == 2 or oc != capi.OUTERS["none"]
+        name = "otmb_op_periodic_sched" if sched else "otmb_op_periodic_dk" if len(dargs) == 2 else "otmb_op_periodic_pc" if outer_args else "otmb_op_periodic"
         msolve = None
         if outer_args:
             msolve = np.zeros(k, dtype=np.int64)

@@ -27,6 +27,8 @@ the floor of an iteration, whose five vector passes and scalar kernels the fusio
     step call of one step, and from these a later visit (right-hand side plus solve).  rhs_torch_us is the COMPOSITION's right-hand side,
     torch's σ·x (HIP events around 24 of them); the step call's own right-hand-side kernel has no entry point to time it through and is
     read from a kernel trace of `--step --step-route step` instead.  The record carries the device memory the slots take.
+--step --substeps M: M implicit steps inside every one of the twelve months, the age system -- ONE otmb_op_step_sched_dev call against the same
+    12·M steps as one-step otmb_op_step_dev calls, alternating in one process (substeps_times).
 --periodic [--outer none|mean --ptol --restart --maxcycles --rtol]: the periodic state of that year -- the twelve slots of --step, θ = 1, lines, the age system
     (d = 1 s⁻¹ at the surface, s = 1), k = 1 -- by otmb_op_periodic_dev: cycles, wall time, defect; then, in the same process, the same
     number of plain cycles by otmb_op_step_dev in a loop from zero: their wall time and the defect they leave.  --outer mean: the outer GMRES
@@ -164,6 +166,63 @@ def step_times(asm, a):
                 f.write(json.dumps(r) + "\n")
 
 
+def substeps_times(asm, a):
+    """--step --substeps M: the twelve months of --step as value slots, θ = 1, `lines`, the age system (d = 1 s⁻¹ on the level-1 wet cells,
+    s = 1), k = 1, M implicit steps of δt = 30 d / M inside every month: 12·M steps from zero.  Route `sched`: ONE otmb_op_step_sched_dev call
+    (one preconditioner per slot, no wait per step).  Route `loop`: the same 12·M steps as 12·M one-step otmb_op_step_dev calls, what the
+    interface offered before the schedule (a fresh preconditioner and a host round trip per sub-step).  Both in this process with this
+    library, alternating, the median of --reps (at least 5) after one warm-up of each; the two routes' states are compared bit for bit."""
+    nslots, m = 12, int(a.substeps)
+    nsteps, dt = nslots * m, 30 * DAY / m
+    N = asm.N
+    cp, rv, nz = asm.out["T"]
+    nnz = int(cp[N].item()) - 1
+    op = Operator(asm.ctx, N, N, cp, rv, (nz[:nnz] * 1.0).contiguous())
+    op.set_lines(asm.vertical_lines())
+    op.set_slots(nslots)
+    for s in range(nslots):
+        op.set_values_dev((nz[:nnz] * (1.0 + 0.02 * s)).contiguous(), slot=s)
+    nsurf = int(torch.count_nonzero(asm.wet3d.reshape(-1)[: asm.nx * asm.ny]).item())
+    d = torch.zeros(N, dtype=torch.float64, device="cuda")
+    d[:nsurf] = 1.0
+    src, x0 = torch.ones(N, dtype=torch.float64, device="cuda"), torch.zeros(N, dtype=torch.float64, device="cuda")
+    kw = dict(dt=dt, theta=1.0, source=src, d=d, rtol=a.rtol, maxiter=a.maxiter, precond="lines")
+
+    def sched():
+        X, info = op.step_sched(x0, nsteps=nsteps, first_slot=0, substeps=m, **kw)
+        assert info.steps_done == nsteps, info
+        return X, int(info.iterations.sum())
+
+    def loop():
+        X, its = x0, 0
+        for t in range(nsteps):
+            X, info = op.step(X, nsteps=1, first_slot=(t // m) % nslots, **kw)
+            assert info.steps_done == 1, (t, info)
+            its += int(info.iterations.sum())
+        return X, its
+
+    times, out = {"sched": [], "loop": []}, {}
+    for r in range(max(a.reps, 5) + 1):
+        for name, route in (("sched", sched), ("loop", loop)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out[name] = route()
+            torch.cuda.synchronize()
+            times[name].append(time.perf_counter() - t0)
+    rec = {"what": "12 months x M implicit sub-steps, T, age system", "n": N, "nnz": nnz, "nslots": nslots, "substeps": m, "nsteps": nsteps, "precond": "lines",
+           "theta": 1.0, "dt_s": dt, "reps": max(a.reps, 5), "iterations": out["sched"][1], "loop_iterations": out["loop"][1],
+           "same_bits": bool(torch.equal(out["sched"][0], out["loop"][0])), "checksum": float(out["sched"][0].sum().item())}
+    for name in times:
+        t = times[name][1:]
+        rec.update({name + "_median_s": float(np.median(t)), name + "_min_s": float(np.min(t)), name + "_max_s": float(np.max(t))})
+    print(json.dumps(rec), flush=True)
+    op.close()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(rec) + "\n")
+
+
 def periodic_times(asm, a):
     """--periodic: the twelve months of --step as value slots, θ = 1, δt = 30 d, `lines`, the age system (d = 1 s⁻¹ on the level-1 wet cells,
     s = 1), k = 1: the periodic state by otmb_op_periodic_dev (GMRES(--restart) on the cycle of twelve steps, to --ptol, at most --maxcycles
@@ -236,6 +295,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--step", action="store_true")
     ap.add_argument("--step-route", default="both", choices=["step", "compose", "both"])
+    ap.add_argument("--substeps", type=int, default=0)
     ap.add_argument("--periodic", action="store_true")
     ap.add_argument("--outer", default="none", choices=["none", "mean"])
     ap.add_argument("--ptol", type=float, default=1e-8)
@@ -260,6 +320,8 @@ def main():
     vmo = torch.from_numpy(np.asfortranarray(g.vmo.data).ravel(order="F")).cuda()
     asm.step(umo, vmo, 1e20)
     N = asm.N
+    if a.step and a.substeps > 0:
+        return substeps_times(asm, a)
     if a.step:
         return step_times(asm, a)
     if a.periodic:
