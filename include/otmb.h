@@ -430,6 +430,10 @@ int32_t otmb_ctx_kept_nbtab(const otmb_ctx *ctx);
  * (no OTMB_KEPT_RHO promise, OTMB_KEPT_VRTAB=0 or no neighbour table, a scalar ρ, a depth slab, the table could not be allocated),
  * -1 no such fill yet. */
 int32_t otmb_ctx_kept_vrtab(const otmb_ctx *ctx);
+/* ... and whether it ran as the lean instantiation of the fill kernel, which fits four waves per SIMD instead of three: 1 yes (whenever
+ * the {v3D, ρ} table is read), 0 no (that table is not read, or OTMB_KEPT_OCC4=0 in the environment), -1 no such fill yet.  The columns
+ * written are bit for bit the same either way. */
+int32_t otmb_ctx_kept_occ4(const otmb_ctx *ctx);
 /* ... and whether that fill stored T's values only (otmb_tm_args.kept_ops & OTMB_KEPT_T_PATTERN honoured): 1 yes, 0 no (T written in full),
  * -1 no such fill yet.  OTMB_KEPT_TPAT=0 in the environment always writes T in full. */
 int32_t otmb_ctx_kept_t_pattern(const otmb_ctx *ctx);

@@ -129,6 +129,7 @@ SYMBOLS = {
     "otmb_ctx_kept_htab": (C.c_int32, [_vp]),
     "otmb_ctx_kept_nbtab": (C.c_int32, [_vp]),
     "otmb_ctx_kept_vrtab": (C.c_int32, [_vp]),
+    "otmb_ctx_kept_occ4": (C.c_int32, [_vp]),
     "otmb_ctx_kept_t_pattern": (C.c_int32, [_vp]),
     "otmb_ctx_kept_t_pattern_fills": (C.c_int64, [_vp]),
     "otmb_last_error": (C.c_char_p, [_vp]),
@@ -439,6 +440,10 @@ class Context:
     def kept_vrtab(self):
         """Whether that fill took v3D and ρ from the context's table in wet-rank order (KEPT_RHO honoured): 1 yes, 0 no (gathered), -1 no such fill yet."""
         return int(self._lib.otmb_ctx_kept_vrtab(self._h))
+
+    def kept_occ4(self):
+        """Whether that fill ran the lean instantiation of the fill kernel (four waves per SIMD; OTMB_KEPT_OCC4=0 keeps the other): 1 yes, 0 no, -1 no such fill yet."""
+        return int(self._lib.otmb_ctx_kept_occ4(self._h))
 
     def kept_t_pattern(self):
         """Whether that fill stored T's values only, on the pattern of this context's last write of T (KEPT_T_PATTERN honoured): 1 yes, 0 no, -1 no such fill yet."""

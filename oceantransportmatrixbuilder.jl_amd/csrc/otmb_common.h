@@ -164,6 +164,7 @@ struct otmb_ctx {
     const void *vrtab_rho = nullptr;  // the ρ array it was built from
     size_t vrtab_nofit = 0;   // an allocation of this many bytes failed: the kept fill gathers v3D and ρ instead
     int vrtab_used = -1;      // the last fill that kept all three operators read it (1) or gathered v3D and ρ (0); -1: none yet (otmb_ctx_kept_vrtab)
+    int occ4_used = -1;       // ... and ran the lean instantiation, four waves per SIMD (1), or another (0); -1: none yet (otmb_ctx_kept_occ4, launch_fill)
     // ... and T's pattern (OTMB_KEPT_T_PATTERN): the last call that wrote T's full union pattern (colptr, rowval; nzval unused), its serial and
     // arguments.  nnz_known: that writer finished cleanly -- folded without error or FLAG_T_CANCEL, or a synchronous fill without cancellation --
     // and nnz is T's reserved count.  Dropped by a call that writes T elsewhere or not at all, a failed step that used it, a compaction of its

@@ -180,6 +180,7 @@ int32_t otmb_ctx_tm_infill(const otmb_ctx *ctx) { return ctx ? ctx->tm_infill_la
 int32_t otmb_ctx_kept_htab(const otmb_ctx *ctx) { return ctx ? ctx->htab_used : -1; }
 int32_t otmb_ctx_kept_nbtab(const otmb_ctx *ctx) { return ctx ? ctx->nbtab_used : -1; }
 int32_t otmb_ctx_kept_vrtab(const otmb_ctx *ctx) { return ctx ? ctx->vrtab_used : -1; }
+int32_t otmb_ctx_kept_occ4(const otmb_ctx *ctx) { return ctx ? ctx->occ4_used : -1; }
 int32_t otmb_ctx_kept_t_pattern(const otmb_ctx *ctx) { return ctx ? ctx->tpat_used : -1; }
 int64_t otmb_ctx_kept_t_pattern_fills(const otmb_ctx *ctx) { return ctx ? (int64_t)ctx->tpat_fills : -1; }
 

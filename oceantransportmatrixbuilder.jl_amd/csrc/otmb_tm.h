@@ -11,7 +11,9 @@
 #endif
 #define TM_NF 5
 #ifndef TM_WAVES_PER_SIMD
-#define TM_WAVES_PER_SIMD 3  // measured: capping at 128 VGPRs (4 waves/SIMD) spills and is 8 % slower
+// Governs every tm_kernel instantiation but the lean kept ones (GIVEN bit 6: <., 4 | 16 | 32 | 64> and <., 12 | 16 | 32 | 64>), which are bounded at
+// four waves per SIMD and fit 128 VGPRs without scratch.  Measured on the five-matrix kernel: capping it at 128 VGPRs spills and is 8 % slower.
+#define TM_WAVES_PER_SIMD 3
 #endif
 #define TM_MAXROWS 7  // rows per column: A, S, W, SELF, E, N|fold, B
 

@@ -214,6 +214,10 @@ __device__ __forceinline__ void v_pair(double kar, double d, double vc, double v
 }
 
 // Build the column of wet cell `cell` (c = own wet rank > 0): generic path, any topology corner case.
+// STAGED (the lean kept fill, tm_kernel's GIVEN bit 6): the loads of TκH and of the vertical operators are issued where those sections start,
+// behind scheduling barriers, instead of up front with Tadv's: four round trips for a seam-row wave instead of one, and at most 52 instead of
+// 114 registers of loads in flight, which is what lets that kernel keep four waves per SIMD.  The same loads and the same arithmetic either way.
+template <bool STAGED = false>
 __device__ __forceinline__ void build_column(const TmParams &p, const Cell &cell, i64 c, Column &col) {
     const int nx = p.nx, ny = p.ny, nz = p.nz, up = p.upwind;
     const i64 L = cell.L;
@@ -267,15 +271,33 @@ __device__ __forceinline__ void build_column(const TmParams &p, const Cell &cell
     const double rc = p.rho ? p.rho[L] : p.rho_s;
     const double rEc = p.rho ? p.rho[LEc] : p.rho_s, rWc = p.rho ? p.rho[LWc] : p.rho_s, rS_ = p.rho ? p.rho[cS] : p.rho_s,
                  rN_ = p.rho ? p.rho[cN] : p.rho_s, rA_ = p.rho ? p.rho[cA] : p.rho_s, rB_ = p.rho ? p.rho[cB] : p.rho_s;
-    const double thc = p.thk[L], tEc = p.thk[LEc], tWc = p.thk[LWc], tS_ = p.thk[cS], tN_ = p.thk[cN];
-    const double *edgeNc = fold ? p.edge[OTMB_DIR_NORTH] : p.edge[OTMB_DIR_SOUTH];  // oppdir (:407): the neighbour's facing edge through the seam is its NORTH edge
-    const double *distNc = fold ? p.dist[OTMB_DIR_NORTH] : p.dist[OTMB_DIR_SOUTH];
-    const double eW_c = p.edge[OTMB_DIR_WEST][s2], eE_c = p.edge[OTMB_DIR_EAST][s2], eS_c = p.edge[OTMB_DIR_SOUTH][s2], eN_c = p.edge[OTMB_DIR_NORTH][s2];
-    const double dW_c = p.dist[OTMB_DIR_WEST][s2], dE_c = p.dist[OTMB_DIR_EAST][s2], dS_c = p.dist[OTMB_DIR_SOUTH][s2], dN_c = p.dist[OTMB_DIR_NORTH][s2];
-    const double eE_w = p.edge[OTMB_DIR_EAST][s2W], dE_w = p.dist[OTMB_DIR_EAST][s2W], eW_e = p.edge[OTMB_DIR_WEST][s2E], dW_e = p.dist[OTMB_DIR_WEST][s2E];
-    const double eN_s = p.edge[OTMB_DIR_NORTH][s2S], dN_s = p.dist[OTMB_DIR_NORTH][s2S], eX_n = edgeNc[s2N], dX_n = distNc[s2N];
-    const double ar = p.area[s2], mld = p.ml[s2];
-    const double ztk = p.zt[k], zta_ = p.zt[k > 0 ? k - 1 : k], ztb_ = p.zt[k + 1 < nz ? k + 1 : k];
+    const double *edgeNc, *distNc;
+    double thc, tEc, tWc, tS_, tN_, eW_c, eE_c, eS_c, eN_c, dW_c, dE_c, dS_c, dN_c, eE_w, dE_w, eW_e, dW_e, eN_s, dN_s, eX_n, dX_n;
+    double ar, mld, ztk, zta_, ztb_;
+#define BC_SEAM_EDGE /* oppdir (:407): the neighbour's facing edge through the seam is its NORTH edge */                                                \
+    edgeNc = fold ? p.edge[OTMB_DIR_NORTH] : p.edge[OTMB_DIR_SOUTH];                                                                                    \
+    distNc = fold ? p.dist[OTMB_DIR_NORTH] : p.dist[OTMB_DIR_SOUTH];
+#define BC_LOADS_H                                                                                                                                      \
+    thc = p.thk[L]; tEc = p.thk[LEc]; tWc = p.thk[LWc]; tS_ = p.thk[cS]; tN_ = p.thk[cN];                                                                \
+    BC_SEAM_EDGE                                                                                                                                        \
+    eW_c = p.edge[OTMB_DIR_WEST][s2]; eE_c = p.edge[OTMB_DIR_EAST][s2]; eS_c = p.edge[OTMB_DIR_SOUTH][s2]; eN_c = p.edge[OTMB_DIR_NORTH][s2];            \
+    dW_c = p.dist[OTMB_DIR_WEST][s2]; dE_c = p.dist[OTMB_DIR_EAST][s2]; dS_c = p.dist[OTMB_DIR_SOUTH][s2]; dN_c = p.dist[OTMB_DIR_NORTH][s2];            \
+    eE_w = p.edge[OTMB_DIR_EAST][s2W]; dE_w = p.dist[OTMB_DIR_EAST][s2W]; eW_e = p.edge[OTMB_DIR_WEST][s2E]; dW_e = p.dist[OTMB_DIR_WEST][s2E];          \
+    eN_s = p.edge[OTMB_DIR_NORTH][s2S]; dN_s = p.dist[OTMB_DIR_NORTH][s2S]; eX_n = edgeNc[s2N]; dX_n = distNc[s2N];
+// (STAGED) the same 25 loads in two stages: the west / east pairs' operands, then the south / north pairs'
+#define BC_LOADS_H_WE                                                                                                                                   \
+    thc = p.thk[L]; tEc = p.thk[LEc]; tWc = p.thk[LWc];                                                                                                 \
+    eW_c = p.edge[OTMB_DIR_WEST][s2]; eE_c = p.edge[OTMB_DIR_EAST][s2]; dW_c = p.dist[OTMB_DIR_WEST][s2]; dE_c = p.dist[OTMB_DIR_EAST][s2];              \
+    eE_w = p.edge[OTMB_DIR_EAST][s2W]; dE_w = p.dist[OTMB_DIR_EAST][s2W]; eW_e = p.edge[OTMB_DIR_WEST][s2E]; dW_e = p.dist[OTMB_DIR_WEST][s2E];
+#define BC_LOADS_H_SN                                                                                                                                   \
+    tS_ = p.thk[cS]; tN_ = p.thk[cN];                                                                                                                   \
+    BC_SEAM_EDGE                                                                                                                                        \
+    eS_c = p.edge[OTMB_DIR_SOUTH][s2]; eN_c = p.edge[OTMB_DIR_NORTH][s2]; dS_c = p.dist[OTMB_DIR_SOUTH][s2]; dN_c = p.dist[OTMB_DIR_NORTH][s2];          \
+    eN_s = p.edge[OTMB_DIR_NORTH][s2S]; dN_s = p.dist[OTMB_DIR_NORTH][s2S]; eX_n = edgeNc[s2N]; dX_n = distNc[s2N];
+#define BC_LOADS_V                                                                                                                                      \
+    ar = p.area[s2]; mld = p.ml[s2];                                                                                                                    \
+    ztk = p.zt[k]; zta_ = p.zt[k > 0 ? k - 1 : k]; ztb_ = p.zt[k + 1 < nz ? k + 1 : k];
+    if (!STAGED) { BC_LOADS_H BC_LOADS_V }
 
     const i64 xEc = lEc, xWc = lWc;
     const i64 xS = (LS >= 0) ? lS_ : 0, xNq = (LNq >= 0) ? lN_ : 0;
@@ -377,6 +399,7 @@ __device__ __forceinline__ void build_column(const TmParams &p, const Cell &cell
     // ---- TκH (:348-415, pushTmixingvalues! :426-435) ------------------------------------------
     // For each horizontal neighbour X: a = min(thk_c*edge[c->X][c], thk_X*edge[X->c][X]) is shared by
     // c's own push towards X (+Tval on the diagonal) and X's push towards c (-Tval' on row X).
+    if (STAGED) { __builtin_amdgcn_sched_barrier(0); BC_LOADS_H_WE }
     {
         bool anynan = false;
         double ownW = 0, ownE = 0, ownS = 0, ownN = 0, inW = 0, inE = 0, inS = 0, inN = 0;
@@ -387,6 +410,11 @@ __device__ __forceinline__ void build_column(const TmParams &p, const Cell &cell
     }
         H_VALUES(xWc != 0, tWc, vWc, eW_c, eE_w, dW_c, dE_w, ownW, inW)
         H_VALUES(xEc != 0, tEc, vEc, eE_c, eW_e, dE_c, dW_e, ownE, inE)
+        if (STAGED) { __builtin_amdgcn_sched_barrier(0); BC_LOADS_H_SN }
+#undef BC_LOADS_H
+#undef BC_SEAM_EDGE
+#undef BC_LOADS_H_WE
+#undef BC_LOADS_H_SN
         H_VALUES(xS != 0, tS_, vS_, eS_c, eN_s, dS_c, dN_s, ownS, inS)
         // oppdir (:407): through the seam the neighbour's facing edge is its NORTH edge (edgeNc / distNc above)
         H_VALUES(xNq != 0, tN_, vN_, eN_c, eX_n, dN_c, dX_n, ownN, inN)
@@ -414,6 +442,8 @@ __device__ __forceinline__ void build_column(const TmParams &p, const Cell &cell
     }
 
     // ---- TκVML / TκVdeep (:450-477) -------------------------------------------------------------
+    if (STAGED) { __builtin_amdgcn_sched_barrier(0); BC_LOADS_V }
+#undef BC_LOADS_V
     {
         const bool omc = ztk < mld;  // Ω (:85); NaN (missing) compares false
         bool nanml = false, nandp = false;

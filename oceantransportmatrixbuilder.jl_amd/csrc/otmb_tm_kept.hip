@@ -175,6 +175,7 @@ static int32_t kept_htab(otmb_ctx *ctx, const otmb_tm_args &a, const TmPlan &pl,
     ctx->htab_used = 0;  // (otmb_ctx_kept_htab: set to 1 below once p points at a valid table)
     ctx->nbtab_used = 0;  // (otmb_ctx_kept_nbtab likewise)
     ctx->vrtab_used = 0;  // (otmb_ctx_kept_vrtab likewise: kept_vrtab)
+    ctx->occ4_used = 0;   // (otmb_ctx_kept_occ4 likewise: launch_fill)
     if (!env_on || a.nx < 3 || a.n_wet <= 0) return OTMB_OK;
     const size_t n = (size_t)a.n_wet, vals = (size_t)NHTAB * n * sizeof(double), hbytes = vals + 256;  // (+ the NaN word)
     // ... and behind it, 256-byte aligned: the neighbour table's word, nb16, nb8.  Wanted when every rank fits a record's 31 bits: ranks count

@@ -141,11 +141,16 @@ static_assert(TM_THREADS == (1 << FFC_TILE_SHIFT), "the counts in facefluxes are
 // canonical-indices check of Lwet3D was made when the table was built (its word).
 // GIVEN bit 5 -- VR (with NBTAB only, ρ 3-D): a regular column takes the seven {v3D, ρ} pairs from the context's table in wet-rank order
 // (TmParams.vrtab: seven 16-byte loads at the ranks the neighbour table names) instead of 7 + 7 gathers in cell order.
+// GIVEN bit 6 -- LEAN (with VR only): the same columns from the same loads and arithmetic in at most 128 registers, so that four waves per
+// SIMD are resident instead of TM_WAVES_PER_SIMD.  A regular column needs about 100 as it is; what filled the budget was the seam row's generic
+// builder, whose 51 up-front loads are in flight while the regular lanes' finished column is held beside them.  Here it issues them in four
+// stages (build_column<STAGED>).
 template <int FUSED = 0, int GIVEN = 0>
-__global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const TmParams p) {
+__global__ __launch_bounds__(TM_THREADS, (GIVEN & 64) ? 4 : TM_WAVES_PER_SIMD) void tm_kernel(const TmParams p) {
     constexpr bool HREAD = (GIVEN & 1) != 0, DREAD = (GIVEN & 2) != 0, HTAB = (GIVEN & 4) != 0, TPAT = (GIVEN & 8) != 0;
-    constexpr bool NB = (GIVEN & 16) != 0, VR = (GIVEN & 32) != 0;
-    static_assert(!HTAB || (GIVEN & ~(8 | 16 | 32)) == 4, "the table serves the kept operators: nothing is given then");
+    constexpr bool NB = (GIVEN & 16) != 0, VR = (GIVEN & 32) != 0, LEAN = (GIVEN & 64) != 0;
+    static_assert(!HTAB || (GIVEN & ~(8 | 16 | 32 | 64)) == 4, "the table serves the kept operators: nothing is given then");
+    static_assert(!LEAN || VR, "the lean instantiation is one of the {v3D, rho} table's path");
     static_assert(!NB || HTAB, "the neighbour table rides on the kept operators' path");
     static_assert(!VR || NB, "the {v3D, rho} table is addressed by the neighbour table's ranks");
     static_assert(!TPAT || HTAB, "T's kept pattern rides on the kept operators' path");
@@ -292,7 +297,7 @@ __global__ __launch_bounds__(TM_THREADS, TM_WAVES_PER_SIMD) void tm_kernel(const
                 else {
                     canonical = ldi(tb.lw, oC) == c;
                     if (canonical) {
-                        build_column(p, cell, c, col);
+                        build_column<LEAN>(p, cell, c, col);
                         // (seam row, nx < 3: the generic builder derived TκH's values; the given ones take their place)
                         if (HREAD) given_values<(1u << S_S) | (1u << S_SELF) | (1u << S_EC) | (1u << S_WC) | (1u << S_FQ) | (1u << S_N)>(col.hh, col.phh, col.bef, p.hx, hq, p.hnnz);
                     }
@@ -508,7 +513,7 @@ __global__ void tm_finish_colptr(i64 *c0, i64 *c1, i64 *c2, i64 *c3, i64 *c4, i6
 
 // ---- host side ------------------------------------------------------------------------------
 // One launch site for the fill pass's instantiations: FUSED (the fused step's flux re-derivation) x GIVEN (a given TκH / TκVdeep read where it lies;
-// 4: the kept operators' TκH table, + 8: T's values only, + 16: the neighbour table, + 32: the {v3D, ρ} table).
+// 4: the kept operators' TκH table, + 8: T's values only, + 16: the neighbour table, + 32: the {v3D, ρ} table, + 64: in 128 registers).
 template <int GIVEN> static void launch_fill_given(otmb_ctx *ctx, const TmParams &p, int fused, dim3 grid, dim3 block) {
     if (fused == 1) hipLaunchKernelGGL((tm_kernel<1, GIVEN>), grid, block, 0, ctx->stream, p);
     else if (fused == 2) hipLaunchKernelGGL((tm_kernel<2, GIVEN>), grid, block, 0, ctx->stream, p);
@@ -521,7 +526,13 @@ static void launch_fill(otmb_ctx *ctx, const TmParams &p, int fused, bool tpat =
     const bool hread = p.hcp != nullptr && (p.hmust || (env_read && p.nx >= 3)), dread = p.dcp != nullptr;
     const dim3 grid(xcd_grid(p.nt_order, p.nheavy)), block(TM_THREADS);
     if (p.htab && p.nbtab && p.vrtab) {  // (... with the neighbour and {v3D, ρ} tables: otmb_tm_kept.hip, kept_vrtab)
-        if (tpat) launch_fill_given<12 | 16 | 32>(ctx, p, fused, grid, block);
+        // the lean instantiation (four waves per SIMD) unless OTMB_KEPT_OCC4=0, read once per process; otmb_ctx_kept_occ4 reports which
+        static const bool env_occ4 = [] { const char *e = getenv("OTMB_KEPT_OCC4"); return !(e && e[0] == '0'); }();
+        ctx->occ4_used = env_occ4 ? 1 : 0;
+        if (env_occ4) {
+            if (tpat) launch_fill_given<12 | 16 | 32 | 64>(ctx, p, fused, grid, block);
+            else launch_fill_given<4 | 16 | 32 | 64>(ctx, p, fused, grid, block);
+        } else if (tpat) launch_fill_given<12 | 16 | 32>(ctx, p, fused, grid, block);
         else launch_fill_given<4 | 16 | 32>(ctx, p, fused, grid, block);
     } else if (p.htab && p.nbtab) {  // (... with the neighbour table: otmb_tm_kept.hip, kept_htab)
         if (tpat) launch_fill_given<12 | 16>(ctx, p, fused, grid, block);
