@@ -1020,8 +1020,7 @@ int32_t otmb_op_periodic_dk(otmb_op *op, int32_t adjoint, int64_t k, const doubl
  * Refused with OTMB_ERR_INVALID_ARG before anything is written, after the checks of the call they extend, the message naming
  *      otmb_op_step_sched or otmb_op_periodic_sched, the operator staying usable: substeps < 1; nsrc outside {0, 1, nslots}; nsrc > 0 with S
  *      NULL or any block NULL; lds < n; scale without a source, or with an entry that is not finite.
- * Not built: interpolation of the matrices between slots (a private value set and a fresh preconditioner per sub-step), and sources at
- *      sub-step resolution.                                                                                                               */
+ * Not built: sources at sub-step resolution (interpolation of the matrices between slots: below).                                       */
 int32_t otmb_op_step_sched_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t nsteps,
                                int64_t first_slot, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, const double *scale, double *X,
                                int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters, double *relres,
@@ -1038,6 +1037,61 @@ int32_t otmb_op_periodic_sched(otmb_op *op, int32_t adjoint, int64_t k, const do
                                int64_t first_slot, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0,
                                double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect,
                                int32_t *reason, int32_t outer, int64_t *msolve_iters);
+
+/* ---- Matrices interpolated between slots: otmb_op_step_interp[_dev] and otmb_op_periodic_interp[_dev].  The convention of offline
+ *      transport-matrix models (Khatiwala 2007): a monthly mean is valid at mid-month, and every time step takes the linear interpolation of
+ *      the two neighbouring months.  The arguments are those of otmb_op_step_sched[_dev] and otmb_op_periodic_sched[_dev] with
+ *      `int64_t first_slot, int64_t substeps` replaced by `const int64_t *slot_a, const int64_t *slot_b, const double *weight`: three HOST
+ *      arrays (in both variants, like scale and tw) of nsteps entries, ncycle for the periodic call.  The schedule is explicit: the library
+ *      blends what it is told to blend, and the convention is one small host rule (interp_schedule of the Python package, interpschedule of
+ *      the Julia shim).
+ *      The step's matrix: for step t let a = slot_a[t], b = slot_b[t], w = weight[t].  The step is PLAIN on slot a when a == b or w == 0.0,
+ *      plain on slot b when w == 1.0, and otherwise BLENDED with
+ *          A_t = (1.0 - w)·A_a + w·A_b:   wa = 1.0 - w, one double subtraction on the host;  per stored entry  pa = wa * va;  pb = w * vb;
+ *          v = pa + pb  -- one operation per statement, no FMA: otmb_op_combine_slots' fold for two terms (IEEE addition commutes, so the
+ *      order of the two terms cannot matter).  The same A_t stands on both sides of the θ-step, in the right-hand side and in the system.
+ * In bits: a plain step has the bits of otmb_op_step_dk_dev(nsteps = 1, first_slot = that slot, S = S_eff); a blended step those of
+ *      otmb_op_combine_slots_dev with the weights 1.0 - w at a, w at b and zero elsewhere into a spare slot c, followed by
+ *      otmb_op_step_dk_dev(nsteps = 1, first_slot = c, S = S_eff); both from the state step t - 1 left, S_eff as in the scheduled step.  This
+ *      holds for the states, steps_done, iterations, relres and reasons; the observation blocks and the mean are those of the chain's
+ *      states; column c of k has the bits of that column alone.
+ *      Sources and scale: nsrc is 0 or 1 (a source block per slot together with interpolation is refused), scale is the scheduled step's;
+ *      the periodic call takes no scale.  The observers, tw and Xbar are otmb_op_step_sched's tail, unchanged.
+ *      On the device a blended step writes its values into a private value set of the operator (two arrays sized like a slot's, allocated
+ *      on the first blended step and freed with the operator; not the set of OTMB_OUTER_MEAN, which the periodic call keeps beside it) in
+ *      ONE launch, makes its preconditioner afresh into one block that all blended steps share, then forms the right-hand side and solves.
+ *      A plain slot's preconditioner is made on the slot's first plain visit and kept for the call.  The workspace does not grow with the
+ *      number of blended steps: n·k + used·(a preconditioner's doubles) + (scale ? nsteps·k : 0) doubles, used = (the distinct slots of the
+ *      plain steps) + (1 if any step is blended).  That the preconditioner's setup, its wait for the device included, runs on EVERY blended
+ *      step is the cost of the convention.  A failure inside step t names the step, both slots and the weight; the caller's selection is
+ *      restored on every return.
+ * otmb_op_periodic_interp[_dev]: F is otmb_op_step_interp_dev over the ncycle steps of the schedule, Φ·v the same call without a source,
+ *      g = F(0); the cycle map stays affine; the method, the restart / verify / stop rules, the reasons and column independence are
+ *      otmb_op_periodic_dk's for both values of outer.  With OTMB_OUTER_MEAN w[s] = acc_s / (double)ncycle, acc_s accumulated over t in
+ *      ascending order -- a plain step adds 1.0 to its slot, a blended step adds 1.0 - w to a, then w to b -- and P = (double)ncycle * dt.
+ * Refused with OTMB_ERR_INVALID_ARG before anything is written, after the checks of the call they extend, the message naming
+ *      otmb_op_step_interp or otmb_op_periodic_interp, the operator staying usable: nsrc outside {0, 1}; what the scheduled calls refuse about
+ *      S, lds and scale; a NULL schedule array with nsteps > 0; a slot outside 0 .. nslots - 1; a weight that is not finite or lies outside
+ *      [0, 1].
+ * Not built: a source block per slot under interpolation, a periodic scale, different matrices on the two sides of a θ-step, and reusing a
+ *      blended preconditioner across steps of equal (a, b, w).                                                                            */
+int32_t otmb_op_step_interp_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t nsteps,
+                                const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S, int64_t lds,
+                                const double *scale, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters,
+                                double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw, double *Xbar,
+                                int64_t ldm);
+int32_t otmb_op_step_interp(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t nsteps,
+                            const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S, int64_t lds,
+                            const double *scale, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters,
+                            double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw, double *Xbar, int64_t ldm);
+int32_t otmb_op_periodic_interp_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
+                                    const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S, int64_t lds,
+                                    double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart,
+                                    int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters);
+int32_t otmb_op_periodic_interp(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
+                                const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S, int64_t lds, double *X,
+                                int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles,
+                                int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters);
 
 #ifdef __cplusplus
 }

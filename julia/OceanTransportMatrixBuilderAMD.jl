@@ -43,6 +43,7 @@ export setslots!, selectslot!, slots, step!   # (`step` extends Base.step for th
 export periodic!, periodic, combineslots!
 export observe, stepobserve!
 export stepsched!, periodicsched!
+export stepinterp!, periodicinterp!, interpschedule
 
 const LIBPATH = get(ENV, "OTMB_HIP_LIB", joinpath(@__DIR__, "..", "oceantransportmatrixbuilder.jl_amd", "lib", "libotmb_hip.so"))
 const lib = Ref{Ptr{Cvoid}}(C_NULL)
@@ -909,6 +910,123 @@ periodic!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOper
           kwargs...) = periodicsched!(X, D, source; kwargs...)
 periodic!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}, source::AbstractVector{<:StridedVecOrMat{Float64}},
           d::StridedMatrix{Float64}; kwargs...) = periodicsched!(X, D, source; d = d, kwargs...)
+
+# Matrices interpolated between slots (otmb_op_step_interp, otmb_op_periodic_interp; include/otmb.h states the contract).  Step t runs with
+# (1 - weight[t])·(slot slota[t]) + weight[t]·(slot slotb[t]) -- the slot itself where the two are one or the weight is 0 or 1; the three vectors
+# have one length, which is the number of steps (slots 1-based here, as firstslot is).  interpschedule makes them for the convention of
+# offline transport-matrix models (Khatiwala 2007): slot s is valid at the middle of its interval of `substeps` steps and step t is evaluated
+# at its start, middle or end.  In integers, m = substeps, t 0-based:  h = 2t + (0, 1, 2)[at];  g = h - m + 2·m·nslots;
+# a = (firstslot - 1 + g ÷ 2m) mod nslots;  b = (a + 1) mod nslots;  w = Float64(g mod 2m) / Float64(2m), one division.
+# `source`: nothing, an array of X's shape, or a vector of ONE such array (a source per slot is not built with interpolation); everything else
+# is stepsched!'s / periodicsched!'s.
+function interpschedule(nslots::Integer, substeps::Integer; ncycles::Integer = 1, firstslot::Integer = 1, at::Symbol = :mid)
+    (nslots >= 1 && substeps >= 1 && ncycles >= 0 && 1 <= firstslot <= nslots) ||
+        throw(ArgumentError("interpschedule: nslots >= 1, substeps >= 1, ncycles >= 0 and 1 <= firstslot <= nslots"))
+    at in (:start, :mid, :end) || throw(ArgumentError("interpschedule: at must be :start, :mid or :end"))
+    m = Int64(substeps)
+    off = at === :start ? 0 : at === :mid ? 1 : 2
+    nsteps = Int64(ncycles) * nslots * m
+    slota, slotb, weight = zeros(Int64, nsteps), zeros(Int64, nsteps), zeros(Float64, nsteps)
+    for t in 0:nsteps-1
+        g = 2t + off - m + 2m * nslots
+        a = mod(firstslot - 1 + fld(g, 2m), nslots)
+        slota[t+1], slotb[t+1] = a + 1, mod(a + 1, nslots) + 1
+        weight[t+1] = Float64(mod(g, 2m)) / Float64(2m)
+    end
+    return slota, slotb, weight
+end
+function interpargs(op::DeviceOperator, slota, slotb, weight, source)
+    length(slota) == length(slotb) == length(weight) ||
+        throw(DimensionMismatch("slota of $(length(slota)), slotb of $(length(slotb)), weight of $(length(weight))"))
+    all(w -> isfinite(w) && 0.0 <= w <= 1.0, weight) || throw(ArgumentError("weight must be finite and in [0, 1]"))
+    source isa AbstractVector{<:StridedVecOrMat{Float64}} && length(source) != 1 &&
+        throw(DimensionMismatch("$(length(source)) source blocks, expected 1 (a source per slot is not built with interpolation)"))
+    return Vector{Int64}(slota) .- 1, Vector{Int64}(slotb) .- 1, Vector{Float64}(weight)
+end
+function stepinterp!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}; dt::Real, slota::AbstractVector{<:Integer},
+                     slotb::AbstractVector{<:Integer}, weight::AbstractVector{<:Real}, θ::Real = 1.0,
+                     source::Union{Nothing,StridedVecOrMat{Float64},AbstractVector{<:StridedVecOrMat{Float64}}} = nothing,
+                     sourcescale::Union{Nothing,StridedVecOrMat{Float64}} = nothing,
+                     d::Union{Nothing,Vector{Float64},StridedMatrix{Float64}} = nothing, rtol::Real = 1e-10, maxiter::Integer = 10000,
+                     precond::Symbol = :jacobi, observers::Union{Nothing,StridedVecOrMat{Float64}} = nothing,
+                     timeweights::Union{Nothing,Vector{Float64}} = nothing)
+    pc = precondcode(precond)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    k, ldx, ldd = scheddims(op, X, d)
+    sa, sb, w = interpargs(op, slota, slotb, weight, source)
+    nrep = Int64(length(w))
+    iters = zeros(Int64, k, nrep)
+    relres = zeros(Float64, k, nrep)
+    reason = zeros(Int32, k, nrep)
+    done = Ref{Int64}(0)
+    q, ldw = observers === nothing ? (0, max(op.n, 1)) : observerdims(op, observers)
+    obs = zeros(Float64, q, k, nrep)
+    timeweights === nothing || length(timeweights) == nrep || throw(DimensionMismatch("timeweights of $(length(timeweights)), nsteps $nrep"))
+    Xbar = timeweights === nothing ? nothing : zeros(Float64, size(X)...)
+    ldm = max(op.n, 1)
+    scale = nothing
+    if sourcescale !== nothing   # the library reads entry t·k + c: column-major k x nsteps
+        source === nothing && throw(ArgumentError("sourcescale needs a source"))
+        size(sourcescale) == (X isa AbstractVector ? (nrep,) : (k, nrep)) ||
+            throw(DimensionMismatch("sourcescale $(size(sourcescale)), expected $(X isa AbstractVector ? (nrep,) : (k, nrep))"))
+        scale = Array{Float64}(sourcescale)
+    end
+    lock(CALL_LOCK) do
+        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        ptrs, lds, blocks = schedsources(op, source, X, 1)
+        step_interp_fn = sym(:otmb_op_step_interp)
+        GC.@preserve blocks begin
+            rc = ccall(step_interp_fn, Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Int64, Float64, Float64, Int64, Ptr{Int64}, Ptr{Int64},
+                    Ptr{Float64}, Int64, Ptr{Ptr{Float64}}, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Float64, Int64, Int32, Ptr{Int64}, Ptr{Int64},
+                    Ptr{Float64}, Ptr{Int32}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64),
+                op.handle, Int32(adjoint), k, d === nothing ? C_NULL : d, ldd, Float64(dt), Float64(θ), nrep, sa, sb, w,
+                Int64(length(ptrs)), isempty(ptrs) ? C_NULL : ptrs, lds, scale === nothing ? C_NULL : scale, X, ldx,
+                Float64(rtol), Int64(maxiter), pc, done, iters, relres, reason,
+                Int64(q), observers === nothing ? C_NULL : observers, ldw, observers === nothing ? C_NULL : obs,
+                timeweights === nothing ? C_NULL : timeweights, Xbar === nothing ? C_NULL : Xbar, ldm)
+            rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which step and column stopped why
+        end
+    end
+    ran = 1:min(done[] + 1, nrep)
+    why = permutedims([SOLVE_REASONS[r + 1] for r in reason[:, ran]])
+    return X, (stepsdone = done[], iterations = permutedims(iters[:, ran]), relres = permutedims(relres[:, ran]), reason = why,
+               converged = why .== :converged, observations = observers === nothing ? nothing : obs[:, :, 1:done[]],
+               mean = (Xbar !== nothing && done[] > 0) ? Xbar : nothing)
+end
+function periodicinterp!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator},
+                         source::Union{StridedVecOrMat{Float64},AbstractVector{<:StridedVecOrMat{Float64}}}; dt::Real,
+                         slota::AbstractVector{<:Integer}, slotb::AbstractVector{<:Integer}, weight::AbstractVector{<:Real}, θ::Real = 1.0,
+                         d::Union{Nothing,Vector{Float64},StridedMatrix{Float64}} = nothing, x0::Bool = false, rtol::Real = 1e-10,
+                         maxiter::Integer = 10000, precond::Symbol = :jacobi, outer::Symbol = :none, ptol::Real = 1e-8, restart::Integer = 30,
+                         maxcycles::Integer = 1000)
+    oc = outercode(outer)
+    pc = precondcode(precond)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    k, ldx, ldd = scheddims(op, X, d)
+    sa, sb, w = interpargs(op, slota, slotb, weight, source)
+    cycles = zeros(Int64, k)
+    defect = zeros(Float64, k)
+    reason = zeros(Int32, k)
+    msolve = zeros(Int64, k)
+    lock(CALL_LOCK) do
+        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        ptrs, lds, blocks = schedsources(op, source, X, 1)
+        periodic_interp_fn = sym(:otmb_op_periodic_interp)
+        GC.@preserve blocks begin
+            rc = ccall(periodic_interp_fn, Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Int64, Float64, Float64, Int64, Ptr{Int64}, Ptr{Int64},
+                    Ptr{Float64}, Int64, Ptr{Ptr{Float64}}, Int64, Ptr{Float64}, Int64, Int32, Float64, Int64, Int32, Float64, Int64, Int64, Ptr{Int64},
+                    Ptr{Float64}, Ptr{Int32}, Int32, Ptr{Int64}),
+                op.handle, Int32(adjoint), k, d === nothing ? C_NULL : d, ldd, Float64(dt), Float64(θ), Int64(length(w)), sa, sb, w,
+                Int64(length(ptrs)), ptrs, lds, X, ldx, Int32(x0), Float64(rtol), Int64(maxiter), pc, Float64(ptol),
+                Int64(restart), Int64(maxcycles), cycles, defect, reason, oc, msolve)
+            rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which column stopped why
+        end
+    end
+    why = [PERIODIC_PC_REASONS[r + 1] for r in reason]
+    return X, (cycles = cycles, defect = defect, reason = why, converged = why .== :converged, msolve_iters = msolve)
+end
 
 const HDIRS = (:west, :east, :south, :north)      # OTMB_DIR_*
 f64(a) = Array{Float64}(replace(a, missing => NaN))

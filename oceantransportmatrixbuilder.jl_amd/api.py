@@ -816,6 +816,26 @@ def vertical_lines(indices):
     return nxt
 
 
+def interp_schedule(nslots, substeps, *, ncycles=1, first_slot=0, at="mid"):
+    """(slot_a, slot_b, weight) of step_interp / periodic_interp for the convention of offline transport-matrix models (Khatiwala 2007):
+    slot s is valid at the middle of its interval of `substeps` steps, and step t -- evaluated at its start, middle or end (`at`) -- takes
+    the linear interpolation of the two slots whose mid-points enclose that time, wrapping round the cycle.  ncycles·nslots·substeps steps,
+    the first interval being first_slot's.  In integers, with m = substeps:  h = 2t + {0, 1, 2}[at];  g = h - m + 2·m·nslots;
+    a = (first_slot + g // (2m)) mod nslots;  b = (a + 1) mod nslots;  w = float(g mod 2m) / float(2m), one division.  Over one whole
+    cycle every slot's total weight is exactly `substeps`."""
+    nslots, m, ncycles, first_slot = int(nslots), int(substeps), int(ncycles), int(first_slot)
+    if nslots < 1 or m < 1 or ncycles < 0 or not 0 <= first_slot < nslots:
+        raise ValueError("interp_schedule: nslots >= 1, substeps >= 1, ncycles >= 0 and 0 <= first_slot < nslots")
+    if at not in ("start", "mid", "end"):
+        raise ValueError("interp_schedule: at must be 'start', 'mid' or 'end'")
+    t = np.arange(ncycles * nslots * m, dtype=np.int64)
+    g = 2 * t + {"start": 0, "mid": 1, "end": 2}[at] - m + 2 * m * nslots
+    a = (first_slot + g // (2 * m)) % nslots
+    b = (a + 1) % nslots
+    w = (g % (2 * m)).astype(np.float64) / float(2 * m)
+    return a, b, w
+
+
 class DeviceOperator(OperatorCalls):
     """A sparse operator resident on the device: Y = α·A·X + β·Y and Y = α·Aᵀ·X + β·Y, bit for bit SparseArrays' 5-argument mul! of
     Julia 1.10 -- what the reference's consumer checks compute (test/local_full.jl:96-107: norm(T * e1), norm(T' * v)) and what a tracer

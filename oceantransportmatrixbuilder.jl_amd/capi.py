@@ -268,6 +268,19 @@ SYMBOLS = {
     "otmb_op_periodic_sched": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                             _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp,
                                             _vp, _vp, C.c_int32, _vp]),
+    # an interpolated schedule (slot_a, slot_b, weight: three host arrays in place of first_slot, substeps): the arguments of the scheduled calls
+    "otmb_op_step_interp_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp,
+                                             C.c_int64, _vp, _vp, C.c_int64, C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp,
+                                             _vp, _vp, C.c_int64]),
+    "otmb_op_step_interp": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp,
+                                         C.c_int64, _vp, _vp, C.c_int64, C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp,
+                                         _vp, _vp, C.c_int64]),
+    "otmb_op_periodic_interp_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp, C.c_int64,
+                                                 _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp,
+                                                 _vp, _vp, C.c_int32, _vp]),
+    "otmb_op_periodic_interp": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp, C.c_int64,
+                                             _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp,
+                                             _vp, _vp, C.c_int32, _vp]),
     "otmb_op_combine_slots_dev": (C.c_int32, [_vp, _vp, C.c_int64]),
     "otmb_op_combine_slots": (C.c_int32, [_vp, _vp, C.c_int64]),
     "otmb_op_info": (C.c_int32, [_vp, _ip, _ip, _ip]),

@@ -31,6 +31,7 @@ struct otmb_op {
     DevBuf st;                            // otmb_op_step: the right-hand side and the preconditioners of the slots it visits (otmb_step.hip)
     DevBuf pd;                            // otmb_op_periodic: the Krylov bases, the cycle's in/out columns, partial sums and scalars (otmb_periodic.hip)
     OpSlot mean;                          // otmb_op_periodic_pc, OTMB_OUTER_MEAN: the cycle-mean values, private like pd (made once per call)
+    OpSlot interp;                        // otmb_op_step_interp: the values of a blended step, (1 - w)·(slot a) + w·(slot b) (otmb_interp.hip); never mean
     DevBuf ob, oh;                        // the observations (otmb_observe.hip): the partial sums; the host entry points' staging of obs, W, X / Xbar
     DevBuf cb;                            // otmb_op_combine_slots: the table of slot pointers and weights, beyond the 16 that travel as arguments
     DevBuf ln;                            // otmb_op_set_lines (Int32, 0-based, -1 = none): successor (n), predecessor (n), line heads ascending (nheads)

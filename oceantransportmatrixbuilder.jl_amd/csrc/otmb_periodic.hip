@@ -42,6 +42,10 @@
 // the gathered step calls carry the live columns of every block (one block: in w.Sb or, the first call's 2k, in the bases, as ever; more:
 // in w.Sg, block j's columns behind block j - 1's), a column is zero only when it is zero in every block, and the mean's weights count
 // the schedule's visits.  Every other periodic export is this call with substeps = 1 and at most one block.
+//
+// otmb_op_periodic_interp[_dev], the cycle of interpolated steps: PdRun holds the schedule (mix) in place of first_slot / substeps, F is
+// otmb_op_step_interp_dev (cycle), and the mean's weights are the slots' shares of the schedule's weights, accumulated step by step in
+// the contract's order (mean_setup).  op->mean and the step's op->interp are different value sets: the call needs both at once.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -347,6 +351,7 @@ struct PdRun {  // one call: the operator, the call's arguments, the workspace, 
     double ptol;
     i64 m, maxcycles;
     int32_t outer;
+    const StMix *mix;  // otmb_op_periodic_interp: the interpolated schedule of ncycle steps in place of first_slot / substeps (null: none)
     PdWork w{};
     dim3 grid, block;
     bool alx = false;  // X takes the 16-byte path
@@ -414,10 +419,28 @@ int32_t PdRun::mean_setup() {
         }
         b->cap = bytes;
     }
-    std::vector<i64> count((size_t)nslots, 0);
-    for (i64 t = 0; t < ncycle; ++t) count[(size_t)((first_slot + t / substeps) % nslots)] += 1;
     std::vector<double> wt((size_t)nslots);
-    for (i64 s = 0; s < nslots; ++s) wt[(size_t)s] = (double)count[(size_t)s] / (double)ncycle;
+    if (mix) {  // acc_s over t ascending: a plain step adds 1.0 to its slot, a blended one 1.0 - w to a, then w to b; wt[s] = acc_s / ncycle
+        std::vector<double> acc((size_t)nslots, 0.0);
+        for (i64 t = 0; t < ncycle; ++t) {
+            const i64 a = mix->a[t], b = mix->b[t];
+            const double wb = mix->w[t];
+            if (a == b || wb == 0.0) {
+                acc[(size_t)a] = acc[(size_t)a] + 1.0;
+            } else if (wb == 1.0) {
+                acc[(size_t)b] = acc[(size_t)b] + 1.0;
+            } else {
+                const double wa = 1.0 - wb;
+                acc[(size_t)a] = acc[(size_t)a] + wa;
+                acc[(size_t)b] = acc[(size_t)b] + wb;
+            }
+        }
+        for (i64 s = 0; s < nslots; ++s) wt[(size_t)s] = acc[(size_t)s] / (double)ncycle;
+    } else {
+        std::vector<i64> count((size_t)nslots, 0);
+        for (i64 t = 0; t < ncycle; ++t) count[(size_t)((first_slot + t / substeps) % nslots)] += 1;
+        for (i64 s = 0; s < nslots; ++s) wt[(size_t)s] = (double)count[(size_t)s] / (double)ncycle;
+    }
     if ((rc = cb_combine(op, wt.data(), op->mean))) return rc;
     period = (double)ncycle * dt;
     mean_pc = sv_prec_carve(w.mp, w.n, precond == OTMB_PRECOND_LINES, sv_prec_cols(d, k), d.percol());
@@ -498,9 +521,13 @@ int32_t PdRun::cycle(std::vector<PdItem> &items, bool withS, double *sbuf) {
         int64_t done = 0;
         std::vector<const double *> sp((size_t)(withS ? nsrc : 0));
         for (size_t j = 0; j < sp.size(); ++j) sp[j] = sbuf + (i64)j * kk * ld;
-        const int32_t rc = otmb_op_step_sched_dev(op, adjoint, kk, d.percol() ? w.Dg : d.p, d.percol() ? ld : 0, dt, theta, ncycle, first_slot, substeps,
-                                                  (i64)sp.size(), sp.data(), ld, nullptr, w.W, ld, rtol, maxiter, precond, &done, s_it.data(), s_rr.data(),
-                                                  s_why.data(), 0, nullptr, 0, nullptr, nullptr, nullptr, 0);
+        const int32_t rc =
+            mix ? otmb_op_step_interp_dev(op, adjoint, kk, d.percol() ? w.Dg : d.p, d.percol() ? ld : 0, dt, theta, ncycle, mix->a, mix->b, mix->w, (i64)sp.size(),
+                                          sp.data(), ld, nullptr, w.W, ld, rtol, maxiter, precond, &done, s_it.data(), s_rr.data(), s_why.data(), 0, nullptr, 0,
+                                          nullptr, nullptr, nullptr, 0)
+                : otmb_op_step_sched_dev(op, adjoint, kk, d.percol() ? w.Dg : d.p, d.percol() ? ld : 0, dt, theta, ncycle, first_slot, substeps, (i64)sp.size(),
+                                         sp.data(), ld, nullptr, w.W, ld, rtol, maxiter, precond, &done, s_it.data(), s_rr.data(), s_why.data(), 0, nullptr, 0,
+                                         nullptr, nullptr, nullptr, 0);
         if (rc == OTMB_OK) {
             std::vector<char> seen((size_t)k, 0);  // (the first call holds a column twice: one call, one cycle)
             for (const PdItem &it : items)
@@ -696,21 +723,22 @@ extern "C" {
 static int32_t pd_check_call(otmb_op *op, const char *call, bool sched, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
                              int64_t first_slot, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, double rtol,
                              int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, const int64_t *cycles, const double *defect,
-                             const int32_t *reason, int32_t outer) {
+                             const int32_t *reason, int32_t outer, const StMix *mix = nullptr) {
     int32_t rc;
     if ((rc = pd_check(op, k, dt, theta, ncycle, first_slot, nsrc > 0 && S ? S[0] : nullptr, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles,
                        defect, reason, outer)) ||
         (rc = sv_check_d(op, call, D, ldd)))
         return rc;
-    const char *more = sched ? sv_sched_complaint(op, substeps, nsrc, S, lds) : nullptr;
-    return more ? otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, (std::string("otmb_op_periodic_sched: ") + more).c_str()) : OTMB_OK;
+    char text[160];
+    const char *more = mix ? sv_interp_complaint(op, ncycle, *mix, nsrc, S, lds, text) : sched ? sv_sched_complaint(op, substeps, nsrc, S, lds) : nullptr;
+    return more ? otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, (std::string(mix ? "otmb_op_periodic_interp: " : "otmb_op_periodic_sched: ") + more).c_str()) : OTMB_OK;
 }
 
 // the call proper: device pointers (S: a host array of nsrc of them), the arguments checked
 static int32_t pd_run_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle, int64_t first_slot,
                           int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol,
                           int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
-                          int32_t outer, int64_t *msolve_iters) {
+                          int32_t outer, int64_t *msolve_iters, const StMix *mix = nullptr) {
     int32_t rc;
     otmb_ctx *ctx = op->ctx;
     // the trivial answers: no rows, no source
@@ -720,7 +748,7 @@ static int32_t pd_run_dev(otmb_op *op, int32_t adjoint, int64_t k, const double 
         HIP_TRY(ctx, hipMemset2DAsync(X, (size_t)ldx * 8, 0, (size_t)op->n * 8, (size_t)k, ctx->stream));
         return pd_all_zero(k, cycles, defect, reason, msolve_iters);
     }
-    PdRun r{op, ctx, ctx->stream, adjoint, k, SvD{D, ldd}, dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, outer};
+    PdRun r{op, ctx, ctx->stream, adjoint, k, SvD{D, ldd}, dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, outer, mix};
     std::vector<PdItem> items;
     if ((rc = r.prepare()) || (outer == OTMB_OUTER_MEAN && (rc = r.mean_setup())) || (rc = r.source_norms(items)) || (rc = r.first_call(items))) return rc;
     for (bool more = true; more;)
@@ -733,7 +761,7 @@ static int32_t pd_run_dev(otmb_op *op, int32_t adjoint, int64_t k, const double 
 static int32_t pd_run_host(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle, int64_t first_slot,
                            int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol,
                            int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
-                           int32_t outer, int64_t *msolve_iters) {
+                           int32_t outer, int64_t *msolve_iters, const StMix *mix = nullptr) {
     int32_t rc;
     otmb_ctx *ctx = op->ctx;
     HIP_TRY(ctx, hipSetDevice(op->device));
@@ -749,7 +777,7 @@ static int32_t pd_run_host(otmb_op *op, int32_t adjoint, int64_t k, const double
             if ((rc = op_upload(ctx, (double *)op->ys.p + j * n * k, S[j], lds, n, k))) return rc;
     }
     rc = pd_run_dev(op, adjoint, k, dd.p, dd.ld, dt, theta, ncycle, first_slot, substeps, nsrc, ds.data(), n, dx, n, use_x0, rtol, maxiter, precond, ptol, restart,
-                    maxcycles, cycles, defect, reason, outer, msolve_iters);
+                    maxcycles, cycles, defect, reason, outer, msolve_iters, mix);
     if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED) return rc;
     return op_finish(ctx, rc, X, ldx, dx, n, k);
 }
@@ -778,6 +806,35 @@ int32_t otmb_op_periodic_sched(otmb_op *op, int32_t adjoint, int64_t k, const do
         return rc;
     return pd_run_host(op, adjoint, k, D, ldd, dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart,
                        maxcycles, cycles, defect, reason, outer, msolve_iters);
+}
+
+// the interpolated schedule: slot_a, slot_b, weight (ncycle host values each) in place of first_slot, substeps; F is otmb_op_step_interp_dev
+int32_t otmb_op_periodic_interp_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
+                                    const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S, int64_t lds,
+                                    double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart,
+                                    int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    const StMix mix = {slot_a, slot_b, weight};
+    int32_t rc;
+    if ((rc = pd_check_call(op, "otmb_op_periodic_interp", true, k, D, ldd, dt, theta, ncycle, 0, 1, nsrc, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart,
+                            maxcycles, cycles, defect, reason, outer, &mix)))
+        return rc;
+    return pd_run_dev(op, adjoint, k, D, ldd, dt, theta, ncycle, 0, 1, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect,
+                      reason, outer, msolve_iters, &mix);
+}
+
+int32_t otmb_op_periodic_interp(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
+                                const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S, int64_t lds, double *X,
+                                int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles,
+                                int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    const StMix mix = {slot_a, slot_b, weight};
+    int32_t rc;
+    if ((rc = pd_check_call(op, "otmb_op_periodic_interp", true, k, D, ldd, dt, theta, ncycle, 0, 1, nsrc, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart,
+                            maxcycles, cycles, defect, reason, outer, &mix)))
+        return rc;
+    return pd_run_host(op, adjoint, k, D, ldd, dt, theta, ncycle, 0, 1, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect,
+                       reason, outer, msolve_iters, &mix);
 }
 
 // the calls from before the schedule: substeps = 1, the one source or none

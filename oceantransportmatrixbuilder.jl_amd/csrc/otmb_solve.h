@@ -93,6 +93,22 @@ struct SvValues {
 // values.  Enqueued on the context's stream.
 int32_t cb_combine(otmb_op *op, const double *w, const OpSlot &to);
 
+// The blended values of otmb_op_step_interp (otmb_interp.hip).
+// ip_reserve: op->interp at the slots' sizes (allocated on first use; may wait for the device).
+// ip_blend:   wa·(slot a) + wb·(slot b) into both value arrays of op->interp, ONE launch enqueued on the context's stream.
+int32_t ip_reserve(otmb_op *op);
+int32_t ip_blend(otmb_op *op, i64 a, i64 b, double wa, double wb);
+
+// An interpolated schedule (include/otmb.h): step t blends slots a[t] and b[t] with the weight w[t]; three HOST arrays.  st_interp_dev
+// (otmb_step.hip) is otmb_op_step_interp_dev behind its checks, for the periodic driver.
+struct StMix {
+    const int64_t *a, *b;
+    const double *w;
+};
+// sv_interp_complaint (otmb_step.hip): the first complaint about an interpolated schedule of `count` steps and its nsrc, or null (text: at
+//                  least 160 chars of scratch for a message that names an entry).
+const char *sv_interp_complaint(const otmb_op *op, int64_t count, const StMix &mix, int64_t nsrc, const double *const *S, int64_t lds, char *text);
+
 // The observation pass (otmb_observe.hip), which the step runs after every completed step.
 // ob_reserve:   the partial sums of q x k entries in op->ob (may wait for the stream: before the loop, never inside it).
 // ob_pass:      obs (q x k, device) = Wᵀ·X and, Xbar not null, Xbar = (first ? +0.0 : Xbar) + tw·X, enqueued on the context's stream; q == 0

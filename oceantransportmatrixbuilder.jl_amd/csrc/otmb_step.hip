@@ -17,6 +17,11 @@
 // block of that slot (or the one block, or none) and, with a scale, s·f for the step's factor f of the tracer -- one more multiplication in
 // the lane that holds s, before the line above touches it.  The factors are staged once per call behind the preconditioners; a kernel gets
 // the step's k of them as a device pointer (null: none).  Every other step call is this one with substeps = 1, at most one block, no scale.
+//
+// otmb_op_step_interp[_dev] is the same loop again with an interpolated schedule (StMix: slot_a, slot_b, weight per step): a step whose two
+// slots are one, or whose weight is 0 or 1, is a step of the loop as it stands; a blended step writes (1 - w)·(slot a) + w·(slot b) into
+// op->interp (ip_blend of otmb_interp.hip, one launch), points the values at it (SvValues) and makes its preconditioner afresh into one
+// block that all blended steps share -- the setup and its wait for the device on every such step are the cost of the convention.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -185,6 +190,19 @@ struct StSrc {
     const double *at(i64 slot) const { return nsrc == 0 ? nullptr : S[nsrc == 1 ? 0 : slot]; }
 };
 
+// What the interpolated schedule makes of step t: its slot when it is plain (a == b or w == 0.0: a; w == 1.0: b), or a blend of a and b.
+struct StStep {
+    i64 slot;
+    bool blend;
+};
+static StStep st_step_of(const StMix &mix, i64 t) {
+    const i64 a = mix.a[t], b = mix.b[t];
+    const double w = mix.w[t];
+    if (a == b || w == 0.0) return {a, false};
+    if (w == 1.0) return {b, false};
+    return {a, true};
+}
+
 static int32_t st_check(otmb_op *op, int64_t k, double dt, double theta, int64_t nsteps, int64_t first_slot, const StSrc &src, double *X, int64_t ldx, double rtol,
                         int64_t maxiter, int32_t precond, const int64_t *steps_done, const int64_t *iters, const double *relres, const int32_t *reason,
                         const StObs &o) {
@@ -208,23 +226,50 @@ const char *sv_sched_complaint(const otmb_op *op, int64_t substeps, int64_t nsrc
     }
     return nullptr;
 }
-static int32_t st_check_sched(otmb_op *op, int64_t k, int64_t nsteps, const StSrc &src) {
-    const char *more = sv_sched_complaint(op, src.substeps, src.nsrc, src.S, src.lds);
+// What otmb_op_step_interp and otmb_op_periodic_interp add (shared like the above): nsrc is 0 or 1, then the schedule's complaints about the
+// source, then the three arrays -- none null, every slot one of the operator's, every weight finite and in [0, 1].
+const char *sv_interp_complaint(const otmb_op *op, int64_t count, const StMix &mix, int64_t nsrc, const double *const *S, int64_t lds, char *text) {
+    if (nsrc != 0 && nsrc != 1) return "nsrc must be 0 or 1 (a source per slot is not built with interpolation)";
+    if (const char *more = sv_sched_complaint(op, 1, nsrc, S, lds)) return more;
+    if (count > 0 && (!mix.a || !mix.b || !mix.w)) return "slot_a, slot_b or weight is null";
+    const i64 nslots = (i64)op->slots.size();
+    for (i64 t = 0; t < count; ++t) {
+        for (const int64_t s : {mix.a[t], mix.b[t]})
+            if (s < 0 || s >= nslots) {
+                snprintf(text, 160, "step %lld: slot %lld is outside 0..%lld (otmb_op_set_slots)", (long long)t, (long long)s, (long long)nslots - 1);
+                return text;
+            }
+        if (!std::isfinite(mix.w[t]) || mix.w[t] < 0.0 || mix.w[t] > 1.0) {
+            snprintf(text, 160, "step %lld: the weight %g is not finite or outside [0, 1]", (long long)t, mix.w[t]);
+            return text;
+        }
+    }
+    return nullptr;
+}
+// (call: the export the message names; mix: the interpolated schedule, null without one)
+static int32_t st_check_sched(otmb_op *op, const char *call, int64_t k, int64_t nsteps, const StSrc &src, const StMix *mix) {
+    char text[160];
+    const char *more = mix ? sv_interp_complaint(op, nsteps, *mix, src.nsrc, src.S, src.lds, text) : sv_sched_complaint(op, src.substeps, src.nsrc, src.S, src.lds);
     if (!more && src.scale) {
         if (src.nsrc == 0) more = "scale needs a source (nsrc > 0)";
         for (i64 e = 0; !more && e < nsteps * k; ++e)
             if (!std::isfinite(src.scale[e])) more = "a scale value is not finite";
     }
-    return more ? otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, (std::string("otmb_op_step_sched: ") + more).c_str()) : OTMB_OK;
+    return more ? otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, (std::string(call) + ": " + more).c_str()) : OTMB_OK;
 }
 
 // The ONE loop behind every step call: otmb_op_step_sched[_dev], and otmb_op_step_dk[_dev] with what is layered on it (substeps = 1, at
 // most one source, no scale; o = ST_PLAIN: no record).  Device pointers (src.S: a host array of them; src.scale: host values), the arguments
 // checked.  After a step whose solve left every column converged the observation pass reads X where the solve left it and its fold writes
 // the step's q x k block of o.obs; nothing of it waits for the host.
+//
+// mix (null: none) is the interpolated schedule of otmb_op_step_interp: step t is plain on mix->a[t] (a == b or w == 0.0), plain on mix->b[t]
+// (w == 1.0) or blended.  A blended step points the values at op->interp (SvValues) for its blend, its preconditioner -- made afresh into
+// the ONE block all blended steps share, behind the plain slots' --, its right-hand side and its solve.  Without mix nothing here differs
+// from the loop as it was: the same launches in the same order.
 static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, double dt, double theta, int64_t nsteps, int64_t first_slot, const StSrc &src,
                       double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters, double *relres, int32_t *reason,
-                      const StObs &o) {
+                      const StObs &o, const StMix *mix = nullptr) {
     int32_t rc;
     *steps_done = 0;
     if (nsteps == 0) return OTMB_OK;
@@ -243,7 +288,24 @@ static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, dou
     const double tdt = theta * dt;
     const StLine q = {1.0 / tdt, theta, (1.0 - theta) / theta};
     // op->st: B, then one preconditioner per slot the call visits (per column where every tracer has its own d), then the scales (nsteps x k)
-    const i64 used = std::min((nsteps - 1) / src.substeps + 1, nslots), kc = sv_prec_cols(d, k);
+    i64 used = std::min((nsteps - 1) / src.substeps + 1, nslots);
+    const i64 kc = sv_prec_cols(d, k);
+    if (mix) {  // the plain slots the schedule visits, and one block for every blended step together
+        std::vector<char> seen((size_t)nslots, 0);
+        bool blended = false;
+        used = 0;
+        for (i64 t = 0; t < nsteps; ++t) {
+            const StStep s = st_step_of(*mix, t);
+            if (s.blend)
+                blended = true;
+            else if (!seen[(size_t)s.slot]++)
+                used += 1;
+        }
+        if (blended) {
+            used += 1;
+            if ((rc = ip_reserve(op))) return rc;
+        }
+    }
     const size_t per = sv_prec_doubles(n, lines, kc);
     const double nscale = src.scale ? (double)nsteps * (double)k : 0.0;
     if ((double)n * (double)k + (double)used * (double)per + nscale >= 1.0e18) return otmb_fail(ctx, OTMB_ERR_ALLOC, "step: the workspace's size overflows");
@@ -261,21 +323,41 @@ static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, dou
         i64 slot;
         ~Reselect() { (void)otmb_op_select_slot(op, slot); }
     } back{op, op->sel};
+    SvPrec shared{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};  // the blended steps' block, carved on the first of them
     for (i64 t = 0; t < nsteps; ++t) {
-        const i64 slot = (first_slot + t / src.substeps) % nslots;
-        if ((rc = otmb_op_select_slot(op, slot))) return rc;
-        const auto here = [&](int32_t status) {  // the failure's message names the step and the slot the schedule gave it
-            ctx->err += " (step " + std::to_string(t) + ", slot " + std::to_string(slot) + ")";
+        const StStep s = mix ? st_step_of(*mix, t) : StStep{(first_slot + t / src.substeps) % nslots, false};
+        const i64 slot = s.slot;
+        const auto here = [&](int32_t status) {  // the failure's message names the step and the slot(s) the schedule gave it
+            if (mix) {
+                char w[40];
+                snprintf(w, sizeof w, "%.17g", mix->w[t]);
+                ctx->err += " (step " + std::to_string(t) + ", slots " + std::to_string(mix->a[t]) + " and " + std::to_string(mix->b[t]) + ", weight " + w + ")";
+            } else {
+                ctx->err += " (step " + std::to_string(t) + ", slot " + std::to_string(slot) + ")";
+            }
             return status;
         };
-        SvPrec &p = prec[(size_t)slot];
-        if (!p.sh) {  // the slot's first visit
-            p = sv_prec_carve(pool + (size_t)(taken++) * per, n, lines, kc, d.percol());
-            if ((rc = sv_prec_prepare(op, adjoint, precond, d, q.sigma, p))) return here(rc);
+        if (s.blend) {
+            const double w = mix->w[t];
+            const double wa = 1.0 - w;
+            if ((rc = ip_blend(op, mix->a[t], mix->b[t], wa, w))) return here(rc);
+            SvValues on(op, op->interp);
+            if (!shared.sh) shared = sv_prec_carve(pool + (size_t)(taken++) * per, n, lines, kc, d.percol());
+            if ((rc = sv_prec_prepare(op, adjoint, precond, d, q.sigma, shared))) return here(rc);
+            st_rhs(op, adjoint, k, q, d, X, ldx, src.at(slot), src.lds, fdev ? fdev + t * k : nullptr, B);
+            HIP_TRY(ctx, hipGetLastError());
+            if ((rc = sv_solve(op, adjoint, k, shared, B, n, X, ldx, 1, rtol, maxiter, iters + t * k, relres + t * k, reason + t * k, precond))) return here(rc);
+        } else {
+            if ((rc = otmb_op_select_slot(op, slot))) return rc;
+            SvPrec &p = prec[(size_t)slot];
+            if (!p.sh) {  // the slot's first visit
+                p = sv_prec_carve(pool + (size_t)(taken++) * per, n, lines, kc, d.percol());
+                if ((rc = sv_prec_prepare(op, adjoint, precond, d, q.sigma, p))) return here(rc);
+            }
+            st_rhs(op, adjoint, k, q, d, X, ldx, src.at(slot), src.lds, fdev ? fdev + t * k : nullptr, B);
+            HIP_TRY(ctx, hipGetLastError());
+            if ((rc = sv_solve(op, adjoint, k, p, B, n, X, ldx, 1, rtol, maxiter, iters + t * k, relres + t * k, reason + t * k, precond))) return here(rc);
         }
-        st_rhs(op, adjoint, k, q, d, X, ldx, src.at(slot), src.lds, fdev ? fdev + t * k : nullptr, B);
-        HIP_TRY(ctx, hipGetLastError());
-        if ((rc = sv_solve(op, adjoint, k, p, B, n, X, ldx, 1, rtol, maxiter, iters + t * k, relres + t * k, reason + t * k, precond))) return here(rc);
         if (watch) {
             ob_pass(op, k, o.q, o.W, o.ldw, X, ldx, o.q > 0 ? o.obs + o.q * k * t : nullptr, o.Xbar, o.ldm, o.tw ? o.tw[t] : 0.0, t == 0);
             HIP_TRY(ctx, hipGetLastError());
@@ -288,7 +370,7 @@ static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, dou
 // The host variant of the loop: X, every source block, d, W staged once; X, the written rows of obs and Xbar come home once.
 static int32_t st_run_host(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, double dt, double theta, int64_t nsteps, int64_t first_slot,
                            const StSrc &src, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters,
-                           double *relres, int32_t *reason, const StObs &o) {
+                           double *relres, int32_t *reason, const StObs &o, const StMix *mix = nullptr) {
     int32_t rc;
     *steps_done = 0;
     const i64 n = op->n;
@@ -314,7 +396,7 @@ static int32_t st_run_host(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d
         od = {o.q, o.q > 0 ? dw : nullptr, n, o.q > 0 ? dobs : nullptr, o.tw, o.Xbar ? dm : nullptr, n};
     }
     const StSrc sd = {src.substeps, src.nsrc, ds.data(), n, src.scale};
-    rc = st_run(op, adjoint, k, dd, dt, theta, nsteps, first_slot, sd, dx, n, rtol, maxiter, precond, steps_done, iters, relres, reason, od);
+    rc = st_run(op, adjoint, k, dd, dt, theta, nsteps, first_slot, sd, dx, n, rtol, maxiter, precond, steps_done, iters, relres, reason, od, mix);
     // X comes back when it holds an answer: every step done, a step's last iterates, or the state before a slot whose preconditioner is singular
     if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED && !(rc == OTMB_ERR_SINGULAR_PRECONDITIONER && *steps_done > 0)) return rc;
     // ... and with it the observations of the completed steps and their mean
@@ -327,18 +409,18 @@ static int32_t st_run_host(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d
 }
 
 // one body for the two variants of a call (DEV: device pointers); call: the export named by the refusals of D / ldd; sched: the scheduled
-// call's own checks, after those of the call it extends
+// call's own checks, after those of the call it extends, under the name `sched` (null: none); mix: the interpolated schedule (null: none)
 template <bool DEV>
-static int32_t st_call(otmb_op *op, const char *call, bool sched, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta,
+static int32_t st_call(otmb_op *op, const char *call, const char *sched, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta,
                        int64_t nsteps, int64_t first_slot, const StSrc &src, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond,
-                       int64_t *steps_done, int64_t *iters, double *relres, int32_t *reason, const StObs &o) {
+                       int64_t *steps_done, int64_t *iters, double *relres, int32_t *reason, const StObs &o, const StMix *mix = nullptr) {
     if (!op) return OTMB_ERR_INVALID_ARG;
     int32_t rc;
     if ((rc = st_check(op, k, dt, theta, nsteps, first_slot, src, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o)) ||
-        (rc = sv_check_d(op, call, D, ldd)) || (sched && (rc = st_check_sched(op, k, nsteps, src))))
+        (rc = sv_check_d(op, call, D, ldd)) || (sched && (rc = st_check_sched(op, sched, k, nsteps, src, mix))))
         return rc;
     return (DEV ? st_run : st_run_host)(op, adjoint, k, SvD{D, ldd}, dt, theta, nsteps, first_slot, src, X, ldx, rtol, maxiter, precond, steps_done, iters, relres,
-                                        reason, o);
+                                        reason, o, mix);
 }
 
 extern "C" {
@@ -347,7 +429,7 @@ int32_t otmb_op_step_sched_dev(otmb_op *op, int32_t adjoint, int64_t k, const do
                                int64_t first_slot, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, const double *scale, double *X,
                                int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters, double *relres,
                                int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw, double *Xbar, int64_t ldm) {
-    return st_call<true>(op, "otmb_op_step_sched", true, adjoint, k, D, ldd, dt, theta, nsteps, first_slot, StSrc{substeps, nsrc, S, lds, scale}, X, ldx, rtol,
+    return st_call<true>(op, "otmb_op_step_sched", "otmb_op_step_sched", adjoint, k, D, ldd, dt, theta, nsteps, first_slot, StSrc{substeps, nsrc, S, lds, scale}, X, ldx, rtol,
                          maxiter, precond, steps_done, iters, relres, reason, StObs{q, W, ldw, obs, tw, Xbar, ldm});
 }
 
@@ -355,8 +437,28 @@ int32_t otmb_op_step_sched(otmb_op *op, int32_t adjoint, int64_t k, const double
                            int64_t first_slot, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, const double *scale, double *X, int64_t ldx,
                            double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters, double *relres, int32_t *reason, int64_t q,
                            const double *W, int64_t ldw, double *obs, const double *tw, double *Xbar, int64_t ldm) {
-    return st_call<false>(op, "otmb_op_step_sched", true, adjoint, k, D, ldd, dt, theta, nsteps, first_slot, StSrc{substeps, nsrc, S, lds, scale}, X, ldx, rtol,
+    return st_call<false>(op, "otmb_op_step_sched", "otmb_op_step_sched", adjoint, k, D, ldd, dt, theta, nsteps, first_slot, StSrc{substeps, nsrc, S, lds, scale}, X, ldx, rtol,
                           maxiter, precond, steps_done, iters, relres, reason, StObs{q, W, ldw, obs, tw, Xbar, ldm});
+}
+
+// the interpolated schedule: slot_a, slot_b, weight (nsteps host values each) in place of first_slot, substeps
+int32_t otmb_op_step_interp_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t nsteps,
+                                const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S, int64_t lds,
+                                const double *scale, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters,
+                                double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw, double *Xbar,
+                                int64_t ldm) {
+    const StMix mix = {slot_a, slot_b, weight};
+    return st_call<true>(op, "otmb_op_step_interp", "otmb_op_step_interp", adjoint, k, D, ldd, dt, theta, nsteps, 0, StSrc{1, nsrc, S, lds, scale}, X, ldx, rtol,
+                         maxiter, precond, steps_done, iters, relres, reason, StObs{q, W, ldw, obs, tw, Xbar, ldm}, &mix);
+}
+
+int32_t otmb_op_step_interp(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t nsteps,
+                            const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S, int64_t lds,
+                            const double *scale, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters,
+                            double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw, double *Xbar, int64_t ldm) {
+    const StMix mix = {slot_a, slot_b, weight};
+    return st_call<false>(op, "otmb_op_step_interp", "otmb_op_step_interp", adjoint, k, D, ldd, dt, theta, nsteps, 0, StSrc{1, nsrc, S, lds, scale}, X, ldx, rtol,
+                          maxiter, precond, steps_done, iters, relres, reason, StObs{q, W, ldw, obs, tw, Xbar, ldm}, &mix);
 }
 
 // the calls from before the schedule: substeps = 1, the one source or none, no scale
@@ -365,7 +467,7 @@ int32_t otmb_op_step_dk_dev(otmb_op *op, int32_t adjoint, int64_t k, const doubl
                             int64_t *steps_done, int64_t *iters, double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs,
                             const double *tw, double *Xbar, int64_t ldm) {
     const double *const one[1] = {S};
-    return st_call<true>(op, "otmb_op_step_dk", false, adjoint, k, D, ldd, dt, theta, nsteps, first_slot, StSrc{1, S ? 1 : 0, one, lds, nullptr}, X, ldx, rtol,
+    return st_call<true>(op, "otmb_op_step_dk", nullptr, adjoint, k, D, ldd, dt, theta, nsteps, first_slot, StSrc{1, S ? 1 : 0, one, lds, nullptr}, X, ldx, rtol,
                          maxiter, precond, steps_done, iters, relres, reason, StObs{q, W, ldw, obs, tw, Xbar, ldm});
 }
 
@@ -374,7 +476,7 @@ int32_t otmb_op_step_dk(otmb_op *op, int32_t adjoint, int64_t k, const double *D
                         int64_t *iters, double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw,
                         double *Xbar, int64_t ldm) {
     const double *const one[1] = {S};
-    return st_call<false>(op, "otmb_op_step_dk", false, adjoint, k, D, ldd, dt, theta, nsteps, first_slot, StSrc{1, S ? 1 : 0, one, lds, nullptr}, X, ldx, rtol,
+    return st_call<false>(op, "otmb_op_step_dk", nullptr, adjoint, k, D, ldd, dt, theta, nsteps, first_slot, StSrc{1, S ? 1 : 0, one, lds, nullptr}, X, ldx, rtol,
                           maxiter, precond, steps_done, iters, relres, reason, StObs{q, W, ldw, obs, tw, Xbar, ldm});
 }
 

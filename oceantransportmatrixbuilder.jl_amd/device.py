@@ -797,6 +797,15 @@ class DeviceAssembler:
         (a list of tensors) and a history (source_scale)."""
         return self._slotted(matrix).op.step_sched(X, **kw)
 
+    def step_tracers_interp(self, X, *, matrix="T", **kw):
+        """Operator.step_interp on the resident operator over `matrix`: step_tracers with the kept slots' matrices interpolated between slots
+        (slot_a, slot_b, weight: api.interp_schedule makes them for monthly means valid at mid-month)."""
+        return self._slotted(matrix).op.step_interp(X, **kw)
+
+    def periodic_tracers_interp(self, source, *, matrix="T", **kw):
+        """Operator.periodic_interp on the resident operator over `matrix`: periodic_tracers over a cycle of interpolated steps."""
+        return self._slotted(matrix).op.periodic_interp(source, **kw)
+
     def combine_slots(self, weights, dst, matrix="T"):
         """Operator.combine_slots on the resident operator over `matrix`: slot dst = Σ_s weights[s]·(slot s) over the slots keep_slot() filled
         (the annual mean of the kept months).  The written slot is not the resident result: when it is the selected one, the operator counts

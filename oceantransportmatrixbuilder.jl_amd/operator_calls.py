@@ -307,6 +307,107 @@ class OperatorCalls:
         rc = self._call(name, *args)
         return Xn, StepInfo(self._status(rc), done.value, nsteps, iters, relres, reason, obs, mean)
 
+    def _interp(self, slot_a, slot_b, weight):
+        """The interpolated schedule as the exports take it: (slot_a, slot_b as int64, weight as float64 host arrays of one length, that
+        length).  Integer slots of the operator and finite weights in [0, 1] only: refused here, before the library is called."""
+        arrays = []
+        for name, a in (("slot_a", slot_a), ("slot_b", slot_b)):
+            a = np.asarray(a)
+            if a.ndim != 1 or not (np.issubdtype(a.dtype, np.integer) or a.size == 0):
+                raise capi.OtmbError(11, f"invalid argument: {name} must be a 1-D array of integers, got {a.dtype} of {a.shape}")
+            arrays.append(np.ascontiguousarray(a, dtype=np.int64))
+        w = np.asarray(weight)
+        if w.ndim != 1 or not (np.issubdtype(w.dtype, np.floating) or np.issubdtype(w.dtype, np.integer) or w.size == 0):
+            raise capi.OtmbError(11, f"invalid argument: weight must be a 1-D array of real numbers, got {w.dtype} of {w.shape}")
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        a, b = arrays
+        if not (a.shape == b.shape == w.shape):
+            raise capi.OtmbError(11, f"DimensionMismatch: slot_a of {a.shape}, slot_b of {b.shape}, weight of {w.shape}")
+        nslots = self.slots[0]
+        for name, s in (("slot_a", a), ("slot_b", b)):
+            if s.size and (s.min() < 0 or s.max() >= nslots):
+                raise capi.OtmbError(11, f"invalid argument: {name} holds a slot outside 0..{nslots - 1}")
+        if w.size and not (np.isfinite(w).all() and w.min() >= 0.0 and w.max() <= 1.0):
+            raise capi.OtmbError(11, "invalid argument: weight must be finite and in [0, 1]")
+        return a, b, w, int(w.shape[0])
+
+    def _one_source(self, source, B, of):
+        """(the source block column-major or None, lds) of the interpolated calls: None, an array of B's shape, or a list or tuple of ONE."""
+        if isinstance(source, (list, tuple)):
+            if len(source) != 1:
+                raise capi.OtmbError(11, f"DimensionMismatch: {len(source)} source blocks, expected 1 (a source per slot is not built with interpolation)")
+            source = source[0]
+        if source is None:
+            return None, max(self.shape[0], 1)
+        return self._matrix(self._like(source, "source", B, of), self.shape[0])
+
+    def step_interp(self, X, *, dt, slot_a, slot_b, weight, theta=1.0, source=None, source_scale=None, d=None, rtol=1e-10, maxiter=10000,
+                    adjoint=False, precond="jacobi", observe=None, time_weights=None):
+        """step with the matrices interpolated between slots (otmb_op_step_interp; include/otmb.h states the contract): step t runs with
+        (1 - weight[t])·(slot slot_a[t]) + weight[t]·(slot slot_b[t]) -- the slot itself where the two are one or the weight is 0 or 1.  The
+        three 1-D host arrays have one length, which is the number of steps; interp_schedule (api.py) makes them for the TMM convention
+        (monthly means valid at mid-month).  source: None, an array of X's shape, or a list of one; source_scale, d, observe, time_weights
+        and what is returned are step_sched's.  A blended step has the bits of combine_slots into a spare slot followed by step(nsteps=1)
+        on it; its preconditioner is made afresh, which is the cost of the convention."""
+        self._live()
+        pc = capi.precond_code(precond)
+        X, k, Xc, _ = self._state(X, "X")
+        dc, dargs = self._d(d, X, "X")
+        sa, sb, w, nsteps = self._interp(slot_a, slot_b, weight)
+        (m, n), ld = self.shape, max(self.shape[0], 1)
+        Sc, lds = self._one_source(source, X, "X")
+        scale = None
+        if source_scale is not None:
+            if Sc is None:
+                raise capi.OtmbError(11, "invalid argument: source_scale needs a source")
+            scale = np.ascontiguousarray(source_scale, dtype=np.float64)
+            want = (nsteps,) + tuple(X.shape[1:])
+            if scale.shape != want:
+                raise capi.OtmbError(11, f"DimensionMismatch: source_scale of {scale.shape}, expected {want}")
+        q, Wc, ldw, obs, tw, mean = 0, None, max(n, 1), None, None, None
+        if observe is not None:
+            W, q = observers(self._array(observe, "observe"), n)
+            Wc, ldw = self._matrix(W, n)
+            obs = self._zeros((nsteps, k, q), "C")
+        if time_weights is not None:
+            tw = _as_weights(time_weights, nsteps)
+            mean = self._zeros(tuple(X.shape))
+        Xn = self._zeros(tuple(X.shape))
+        self._assign(Xn, Xc)
+        iters, relres, reason = step_arrays(nsteps, k)
+        done = C.c_int64(0)
+        dargs = dargs if len(dargs) == 2 else dargs + [0]
+        rc = self._call("otmb_op_step_interp", int(bool(adjoint)), k, *dargs, float(dt), float(theta), nsteps, sa.ctypes.data, sb.ctypes.data, w.ctypes.data,
+                        *self._source_args([] if Sc is None else [Sc], lds), None if scale is None else scale.ctypes.data, self._ptr(Xn), ld, float(rtol),
+                        int(maxiter), pc, C.byref(done), iters.ctypes.data, relres.ctypes.data, reason.ctypes.data, q, self._ptr(Wc), ldw, self._ptr(obs),
+                        None if tw is None else tw.ctypes.data, self._ptr(mean), ld)
+        return Xn, StepInfo(self._status(rc), done.value, nsteps, iters, relres, reason, obs, mean)
+
+    def periodic_interp(self, source, *, dt, slot_a, slot_b, weight, theta=1.0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False,
+                        precond="jacobi", ptol=1e-8, restart=30, maxcycles=1000, outer="none"):
+        """periodic over a cycle of interpolated steps (otmb_op_periodic_interp; include/otmb.h): F is step_interp over the schedule, whose
+        length is the cycle's number of steps; source: an array, or a list of one.  With outer="mean" the mean's weights are the slots'
+        shares of the schedule's weights.  No source_scale: a history is not periodic.  Everything else, and what is returned, is
+        periodic's."""
+        oc = capi.outer_code(outer)
+        self._live()
+        pc = capi.precond_code(precond)
+        if isinstance(source, (list, tuple)):
+            if len(source) != 1:
+                raise capi.OtmbError(11, f"DimensionMismatch: {len(source)} source blocks, expected 1 (a source per slot is not built with interpolation)")
+            source = source[0]
+        S, k, Sc, lds = self._state(source, "source")
+        sa, sb, w, ncycle = self._interp(slot_a, slot_b, weight)
+        dc, dargs = self._d(d, S, "source")
+        dargs = dargs if len(dargs) == 2 else dargs + [0]
+        X = self._start(x0, S, "source")
+        cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
+        msolve = np.zeros(k, dtype=np.int64)
+        rc = self._call("otmb_op_periodic_interp", int(bool(adjoint)), k, *dargs, float(dt), float(theta), ncycle, sa.ctypes.data, sb.ctypes.data,
+                        w.ctypes.data, *self._source_args([Sc], lds), self._ptr(X), max(self.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), pc,
+                        float(ptol), int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data, reason.ctypes.data, oc, msolve.ctypes.data)
+        return X, PeriodicInfo(self._status(rc), cycles, defect, reason, msolve)
+
     def periodic(self, source, *, dt, ncycle, theta=1.0, first_slot=0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi",
                  ptol=1e-8, restart=30, maxcycles=1000, outer="none"):
         """The periodic state of the stepped cycle: X with F(X) = X, F = step(..., nsteps=ncycle, first_slot=first_slot, source=source), by

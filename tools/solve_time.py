@@ -29,6 +29,12 @@ the floor of an iteration, whose five vector passes and scalar kernels the fusio
     read from a kernel trace of `--step --step-route step` instead.  The record carries the device memory the slots take.
 --step --substeps M: M implicit steps inside every one of the twelve months, the age system -- ONE otmb_op_step_sched_dev call against the same
     12·M steps as one-step otmb_op_step_dev calls, alternating in one process (substeps_times).
+--step --interp: the TMM convention on that year -- twelve slots, `lines`, θ = 1, the age system, k = 1, four sub-steps a month, the schedule
+    of api.interp_schedule(12, 4): 48 steps, every one blended.  Route `interp`: ONE otmb_op_step_interp_dev call.  Route `chain`: the same 48
+    steps in the public calls there were before it -- otmb_op_combine_slots_dev into a thirteenth slot, then a one-step otmb_op_step_dev on
+    it -- which is what runs against an earlier commit's library as well (--lib PATH: only `chain` runs then).  Medians of 7 after one
+    warm-up of each (interp_times); the record also times one blend by otmb_op_combine_slots_dev (HIP events) and a preconditioner's setup
+    plus one sweep and one wait (otmb_op_precond_dev), the upper bound of what every blended step pays.
 --periodic [--outer none|mean --ptol --restart --maxcycles --rtol]: the periodic state of that year -- the twelve slots of --step, θ = 1, lines, the age system
     (d = 1 s⁻¹ at the surface, s = 1), k = 1 -- by otmb_op_periodic_dev: cycles, wall time, defect; then, in the same process, the same
     number of plain cycles by otmb_op_step_dev in a loop from zero: their wall time and the defect they leave.  --outer mean: the outer GMRES
@@ -223,6 +229,99 @@ def substeps_times(asm, a):
             f.write(json.dumps(rec) + "\n")
 
 
+def interp_times(asm, a):
+    """--step --interp: see the module's text.  The two routes' states are compared bit for bit when both run."""
+    nslots, m, reps = 12, 4, 7
+    nsteps, dt = nslots * m, 30 * DAY / m
+    N = asm.N
+    cp, rv, nz = asm.out["T"]
+    nnz = int(cp[N].item()) - 1
+    op = Operator(asm.ctx, N, N, cp, rv, (nz[:nnz] * 1.0).contiguous())
+    op.set_lines(asm.vertical_lines())
+    op.set_slots(nslots + 1)  # the thirteenth: the chain's scratch
+    for s in range(nslots):
+        op.set_values_dev((nz[:nnz] * (1.0 + 0.02 * s)).contiguous(), slot=s)
+    nsurf = int(torch.count_nonzero(asm.wet3d.reshape(-1)[: asm.nx * asm.ny]).item())
+    d = torch.zeros(N, dtype=torch.float64, device="cuda")
+    d[:nsurf] = 1.0
+    src, x0 = torch.ones(N, dtype=torch.float64, device="cuda"), torch.zeros(N, dtype=torch.float64, device="cuda")
+    kw = dict(dt=dt, theta=1.0, source=src, d=d, rtol=a.rtol, maxiter=a.maxiter, precond="lines")
+    sa, sb, w = api.interp_schedule(nslots, m)
+    assert len(w) == nsteps and ((w > 0) & (w < 1)).all()
+
+    def interp():
+        X, info = op.step_interp(x0, slot_a=sa, slot_b=sb, weight=w, **kw)
+        assert info.steps_done == nsteps, info
+        return X, int(info.iterations.sum())
+
+    def chain():
+        X, its = x0, 0
+        for t in range(nsteps):
+            wt = np.zeros(nslots + 1)
+            wt[sa[t]], wt[sb[t]] = 1.0 - float(w[t]), float(w[t])
+            op.combine_slots(wt, nslots)
+            X, info = op.step(X, nsteps=1, first_slot=nslots, **kw)
+            assert info.steps_done == 1, (t, info)
+            its += int(info.iterations.sum())
+        return X, its
+
+    # the row layout's entries, padding included, by the plan's rule (csrc/otmb_spmv.hip): slices of 64 rows as wide as their longest short row,
+    # the long rows (more than 256 entries, or more than 32 and four times the slice's mean) behind them
+    lens = torch.bincount(rv[:nnz] - 1, minlength=N).cpu().numpy().astype(np.int64)
+    L = np.zeros(-(-N // 64) * 64, dtype=np.int64)
+    L[:N] = lens
+    L = L.reshape(-1, 64)
+    rows = np.minimum(64, N - 64 * np.arange(len(L)))
+    mean = -(-L.sum(axis=1) // np.maximum(rows, 1))
+    lng = (L > 256) | ((L > 32) & (L > 4 * mean[:, None]))
+    nval = int(64 * np.where(lng, 0, L).max(axis=1).sum() + L[lng].sum())
+    routes = [("chain", chain)] + ([("interp", interp)] if hasattr(op.lib, "otmb_op_step_interp_dev") else [])
+    times, out = {name: [] for name, _ in routes}, {}
+    for r in range(reps + 1):
+        for name, route in routes:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out[name] = route()
+            torch.cuda.synchronize()
+            times[name].append(time.perf_counter() - t0)
+    rec = {"what": "12 months x 4 sub-steps, TMM interpolation, T, age system", "n": N, "nnz": nnz, "nslots": nslots, "substeps": m, "nsteps": nsteps,
+           "precond": "lines", "theta": 1.0, "dt_s": dt, "reps": reps, "lib": a.lib or "this build", "nval": nval, "blend_bytes": 24 * (nnz + nval), "iterations": out["chain"][1],
+           "checksum": float(out["chain"][0].sum().item())}
+    if "interp" in out:
+        rec.update(interp_iterations=out["interp"][1], same_bits=bool(torch.equal(out["interp"][0], out["chain"][0])))
+    for name in times:
+        t = times[name][1:]
+        rec.update({name + "_median_s": float(np.median(t)), name + "_min_s": float(np.min(t)), name + "_max_s": float(np.max(t))})
+    # one blend through the public combine (two launches), and a preconditioner's setup + one sweep + one wait on the blended values
+    wt = np.zeros(nslots + 1)
+    wt[0], wt[1] = 0.375, 0.625
+    ev = []
+    for r in range(12):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        op.combine_slots(wt, nslots)
+        e1.record()
+        e1.synchronize()
+        ev.append(e0.elapsed_time(e1) * 1e-3)
+    rec["combine_slots_event_s"] = float(np.median(ev[2:]))
+    op.select(nslots)
+    ts = []
+    for r in range(8):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        op.precondition(src, d=d, sigma=1.0 / dt, precond="lines")
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    op.select(0)
+    rec["setup_plus_one_sweep_s"] = float(np.median(ts[1:]))
+    print(json.dumps(rec), flush=True)
+    op.close()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(rec) + "\n")
+
+
 def periodic_times(asm, a):
     """--periodic: the twelve months of --step as value slots, θ = 1, δt = 30 d, `lines`, the age system (d = 1 s⁻¹ on the level-1 wet cells,
     s = 1), k = 1: the periodic state by otmb_op_periodic_dev (GMRES(--restart) on the cycle of twelve steps, to --ptol, at most --maxcycles
@@ -296,6 +395,7 @@ def main():
     ap.add_argument("--step", action="store_true")
     ap.add_argument("--step-route", default="both", choices=["step", "compose", "both"])
     ap.add_argument("--substeps", type=int, default=0)
+    ap.add_argument("--interp", action="store_true")
     ap.add_argument("--periodic", action="store_true")
     ap.add_argument("--outer", default="none", choices=["none", "mean"])
     ap.add_argument("--ptol", type=float, default=1e-8)
@@ -320,6 +420,8 @@ def main():
     vmo = torch.from_numpy(np.asfortranarray(g.vmo.data).ravel(order="F")).cuda()
     asm.step(umo, vmo, 1e20)
     N = asm.N
+    if a.step and a.interp:
+        return interp_times(asm, a)
     if a.step and a.substeps > 0:
         return substeps_times(asm, a)
     if a.step:
