@@ -1073,8 +1073,8 @@ int32_t otmb_op_periodic_sched(otmb_op *op, int32_t adjoint, int64_t k, const do
  *      otmb_op_step_interp or otmb_op_periodic_interp, the operator staying usable: nsrc outside {0, 1}; what the scheduled calls refuse about
  *      S, lds and scale; a NULL schedule array with nsteps > 0; a slot outside 0 .. nslots - 1; a weight that is not finite or lies outside
  *      [0, 1].
- * Not built: a source block per slot under interpolation, a periodic scale, different matrices on the two sides of a θ-step, and reusing a
- *      blended preconditioner across steps of equal (a, b, w).                                                                            */
+ * Not built here: a source block per slot under interpolation (otmb_op_step_season, below, takes one).  Not built at all: a periodic scale,
+ *      different matrices on the two sides of a θ-step, and reusing a blended preconditioner across steps of equal (a, b, w).              */
 int32_t otmb_op_step_interp_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t nsteps,
                                 const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S, int64_t lds,
                                 const double *scale, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters,
@@ -1090,6 +1090,69 @@ int32_t otmb_op_periodic_interp_dev(otmb_op *op, int32_t adjoint, int64_t k, con
                                     int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters);
 int32_t otmb_op_periodic_interp(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
                                 const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S, int64_t lds, double *X,
+                                int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles,
+                                int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters);
+
+/* ---- d and the source per slot, blended with the matrices: otmb_op_step_season[_dev] and otmb_op_periodic_season[_dev].  Gas exchange under
+ *      a seasonal ice cover scales the source kw·(1 - ice)·C_sat/Δz AND the restoring rate d = kw·(1 - ice)/Δz by the same factor; so do
+ *      CFCs, SF6, radiocarbon, oxygen and any surface restoring under a seasonal mixed layer.  Here every per-step field follows the calendar
+ *      the way the matrix does.  The arguments are those of otmb_op_step_interp[_dev] and otmb_op_periodic_interp[_dev] with
+ *      `const double *D, int64_t ldd` replaced by `int64_t nd, const double *const *D, int64_t ldd`.  The schedule is the explicit one
+ *      (slot_a, slot_b, weight: three HOST arrays in both variants); a step with a == b is plain, so it holds the piecewise-constant schedule
+ *      of otmb_op_step_sched as well (plain_schedule of the Python package, plainschedule of the Julia shim).
+ *        D: a HOST array of nd pointers (device pointers in _dev, as S is) to blocks with the one ldd: ldd == 0, the n values of a block serve
+ *          every column; ldd >= n, a block is n x k and column c is tracer c's.  nd is 0 (no d; D may be NULL), 1 (the block serves every
+ *          step) or nslots (a block per slot).
+ *        S: as in otmb_op_step_sched; nsrc is 0, 1 or nslots -- a block per slot is in order under interpolation in this family.
+ *      The field of step t, with a = slot_a[t], b = slot_b[t], w = weight[t] and plain / blended decided exactly as for the matrix:
+ *        a field given once (nd == 1, nsrc == 1) is used as it is on every step; it is never blended with itself (wa·x + w·x is not x in bits);
+ *        a field given per slot is, on a plain step, the slot's block -- a's, or b's when w == 1.0;
+ *        on a blended step wa = 1.0 - w (the host's subtraction, the matrix's), and per entry  pa = wa * xa;  pb = w * xb;  x = pa + pb  -- one
+ *          operation per statement, no FMA: the fold the matrix gets.  The blended source is formed first; the step's scale then
+ *          multiplies it as in the scheduled step.
+ * In bits: step t has the bits of the chain of existing calls -- otmb_op_combine_slots_dev into a spare slot on a blended step, then the
+ *      one-step otmb_op_step_dk_dev with D = D_t and S = S_t·scale from the state step t - 1 left -- in the states, steps_done, iters, relres,
+ *      reason, the observation blocks and the mean.  Column c of k has the bits of that column alone with its own column of every block.
+ *      With nd <= 1 and nsrc <= 1 the call has the bits of otmb_op_step_interp[_dev] / otmb_op_periodic_interp[_dev].
+ *      A plain slot's preconditioner is made on the slot's first plain visit with that slot's d and kept for the call: d is a function of
+ *      the slot, so this stays exact.  A blended step makes its own from D_t into the one shared block.  The workspace formula is
+ *      otmb_op_step_interp's; the blended fields live in a scratch of the operator's, n·kc + n·k doubles (kc = k with ldd != 0, else 1),
+ *      reserved by the first call with a blended step that needs it and freed with the operator.  On the device the two-term fold of a
+ *      field is ONE launch over all columns (csrc/otmb_season.hip), which reads the caller's blocks where they lie: any 8-byte alignment,
+ *      padded leading dimensions, 16-byte accesses only in a column whose every operand allows them.
+ *      A failure names step, slots and weight as otmb_op_step_interp does; a singular preconditioner with a d per column adds
+ *      " (column C of k)".
+ * otmb_op_periodic_season[_dev]: F is otmb_op_step_season_dev over the schedule, Φ·v the same call without sources and with the same D blocks,
+ *      g = F(0); the map stays affine; the method, the restart / verify / stop rules, the reasons and column independence are unchanged.  A
+ *      column is answered with zero and never stepped only when it is zero in EVERY source block.  The step calls take the live columns
+ *      gathered compactly; with ldd != 0 and nd > 1 that includes those columns of every D block: nd·2k·n doubles more, on the pattern of the
+ *      sources' nsrc·2k·n.  A failed reservation is OTMB_ERR_ALLOC with X untouched.
+ *      OTMB_OUTER_MEAN: the weights wt[s] = acc_s / ncycle are otmb_op_periodic_interp's, and M̄ = diag(d̄) + Ā.  With nd == nslots d̄ is the
+ *      fold of otmb_op_combine_slots over the D blocks: the slots with wt[s] != 0.0 in ascending s, acc = wt[s]·D_s for the first, then
+ *      acc = acc + wt[s]·D_s, no FMA -- the same kernel, one launch, up to 16 terms as kernel arguments and more through a table on the
+ *      device -- written once per call before the mean's preconditioner is made.  With nd <= 1 d̄ is the given block, untouched.  d̄ changes
+ *      only how fast the outer iteration converges: an answer is still accepted on the explicit F(x) - x alone.
+ * Refused with OTMB_ERR_INVALID_ARG before anything is written, after the checks of the calls they extend, the message naming
+ *      otmb_op_step_season or otmb_op_periodic_season, the operator staying usable: what otmb_op_step_interp / otmb_op_periodic_interp refuse
+ *      about S, lds, scale and the schedule, except that nsrc = nslots is in order; nd outside {0, 1, nslots}; nd > 0 with D NULL or any
+ *      block NULL; ldd neither 0 nor >= n.
+ * Not built: a periodic scale, different matrices on the two sides of a θ-step, reuse of a blended preconditioner.                          */
+int32_t otmb_op_step_season_dev(otmb_op *op, int32_t adjoint, int64_t k, int64_t nd, const double *const *D, int64_t ldd, double dt, double theta,
+                                int64_t nsteps, const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S,
+                                int64_t lds, const double *scale, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
+                                int64_t *iters, double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw,
+                                double *Xbar, int64_t ldm);
+int32_t otmb_op_step_season(otmb_op *op, int32_t adjoint, int64_t k, int64_t nd, const double *const *D, int64_t ldd, double dt, double theta, int64_t nsteps,
+                            const int64_t *slot_a, const int64_t *slot_b, const double *weight,
+                            int64_t nsrc, const double *const *S, int64_t lds, const double *scale, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters,
+                            double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw, double *Xbar, int64_t ldm);
+int32_t otmb_op_periodic_season_dev(otmb_op *op, int32_t adjoint, int64_t k, int64_t nd, const double *const *D, int64_t ldd, double dt, double theta,
+                                    int64_t ncycle, const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S,
+                                    int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol,
+                                    int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters);
+int32_t otmb_op_periodic_season(otmb_op *op, int32_t adjoint, int64_t k, int64_t nd, const double *const *D, int64_t ldd, double dt, double theta, int64_t ncycle,
+                                const int64_t *slot_a, const int64_t *slot_b, const double *weight,
+                                int64_t nsrc, const double *const *S, int64_t lds, double *X,
                                 int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles,
                                 int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters);
 

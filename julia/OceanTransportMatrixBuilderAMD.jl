@@ -44,6 +44,7 @@ export periodic!, periodic, combineslots!
 export observe, stepobserve!
 export stepsched!, periodicsched!
 export stepinterp!, periodicinterp!, interpschedule
+export stepseason!, periodicseason!, plainschedule
 
 const LIBPATH = get(ENV, "OTMB_HIP_LIB", joinpath(@__DIR__, "..", "oceantransportmatrixbuilder.jl_amd", "lib", "libotmb_hip.so"))
 const lib = Ref{Ptr{Cvoid}}(C_NULL)
@@ -1019,6 +1020,131 @@ function periodicinterp!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,Ad
                     Ptr{Float64}, Int64, Ptr{Ptr{Float64}}, Int64, Ptr{Float64}, Int64, Int32, Float64, Int64, Int32, Float64, Int64, Int64, Ptr{Int64},
                     Ptr{Float64}, Ptr{Int32}, Int32, Ptr{Int64}),
                 op.handle, Int32(adjoint), k, d === nothing ? C_NULL : d, ldd, Float64(dt), Float64(θ), Int64(length(w)), sa, sb, w,
+                Int64(length(ptrs)), ptrs, lds, X, ldx, Int32(x0), Float64(rtol), Int64(maxiter), pc, Float64(ptol),
+                Int64(restart), Int64(maxcycles), cycles, defect, reason, oc, msolve)
+            rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which column stopped why
+        end
+    end
+    why = [PERIODIC_PC_REASONS[r + 1] for r in reason]
+    return X, (cycles = cycles, defect = defect, reason = why, converged = why .== :converged, msolve_iters = msolve)
+end
+
+# d and the source per slot, blended with the matrices (otmb_op_step_season, otmb_op_periodic_season; include/otmb.h states the contract): the
+# interpolated calls with `d` nothing, n values, a matrix of X's shape, or a vector of one or nslots such arrays of one shape, and `source`
+# likewise with one block or one per slot.  A field given once serves every step as it is; a field given per slot is the slot's block on a plain
+# step and (1 - weight[t])·(block slota[t]) + weight[t]·(block slotb[t]) on a blended one.  The library counts the blocks against its slots, so each
+# method makes ONE C call.  plainschedule states the scheduled step's rule as explicit vectors: every step plain.
+function plainschedule(nslots::Integer, nsteps::Integer; firstslot::Integer = 1, substeps::Integer = 1)
+    (nslots >= 1 && nsteps >= 0 && substeps >= 1 && 1 <= firstslot <= nslots) ||
+        throw(ArgumentError("plainschedule: nslots >= 1, nsteps >= 0, substeps >= 1 and 1 <= firstslot <= nslots"))
+    slota = Int64[mod(firstslot - 1 + fld(t, substeps), nslots) + 1 for t in 0:nsteps-1]
+    return slota, copy(slota), zeros(Float64, nsteps)
+end
+function seasonargs(slota, slotb, weight)
+    length(slota) == length(slotb) == length(weight) ||
+        throw(DimensionMismatch("slota of $(length(slota)), slotb of $(length(slotb)), weight of $(length(weight))"))
+    all(w -> isfinite(w) && 0.0 <= w <= 1.0, weight) || throw(ArgumentError("weight must be finite and in [0, 1]"))
+    return Vector{Int64}(slota) .- 1, Vector{Int64}(slotb) .- 1, Vector{Float64}(weight)
+end
+# (the blocks' addresses, their one leading dimension -- 0 for blocks of n values with `shared` --, what to preserve)
+function seasonblocks(op::DeviceOperator, field, X, what::String, shared::Bool)
+    field === nothing && return Ptr{Float64}[], Int64(shared ? 0 : max(op.n, 1)), ()
+    blocks = field isa AbstractVector{<:StridedVecOrMat{Float64}} ? field : [field]
+    isempty(blocks) && throw(DimensionMismatch("0 $what blocks, expected 1 or one per slot"))
+    all(size(B) == size(blocks[1]) for B in blocks) || throw(DimensionMismatch("$what blocks of different shapes"))
+    if shared && blocks[1] isa AbstractVector
+        length(blocks[1]) == op.n || throw(DimensionMismatch("$what has $(length(blocks[1])) values, the operator $(op.n) columns"))
+        all(stride(B, 1) == 1 for B in blocks) || throw(ArgumentError("the $what blocks need contiguous columns"))
+        return Ptr{Float64}[pointer(B) for B in blocks], Int64(0), blocks
+    end
+    for B in blocks
+        size(B) == size(X) || throw(DimensionMismatch("$what $(size(B)), X $(size(X))"))
+        stride(B, 1) == 1 || throw(ArgumentError("the $what blocks need contiguous columns"))
+    end
+    ld(B) = Int64(B isa AbstractVector || size(B, 2) <= 1 ? max(op.n, 1) : stride(B, 2))
+    if !all(ld(B) == ld(blocks[1]) for B in blocks)   # one leading dimension for all: blocks whose own differ are copied compactly
+        blocks = [ld(B) == max(op.n, 1) ? B : copy(B) for B in blocks]
+    end
+    return Ptr{Float64}[pointer(B) for B in blocks], ld(blocks[1]), blocks
+end
+function stepseason!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator}; dt::Real, slota::AbstractVector{<:Integer},
+                     slotb::AbstractVector{<:Integer}, weight::AbstractVector{<:Real}, θ::Real = 1.0,
+                     d::Union{Nothing,StridedVecOrMat{Float64},AbstractVector{<:StridedVecOrMat{Float64}}} = nothing,
+                     source::Union{Nothing,StridedVecOrMat{Float64},AbstractVector{<:StridedVecOrMat{Float64}}} = nothing,
+                     sourcescale::Union{Nothing,StridedVecOrMat{Float64}} = nothing, rtol::Real = 1e-10, maxiter::Integer = 10000,
+                     precond::Symbol = :jacobi, observers::Union{Nothing,StridedVecOrMat{Float64}} = nothing,
+                     timeweights::Union{Nothing,Vector{Float64}} = nothing)
+    pc = precondcode(precond)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    k, ldx, _ = scheddims(op, X, nothing)
+    sa, sb, w = seasonargs(slota, slotb, weight)
+    nrep = Int64(length(w))
+    iters = zeros(Int64, k, nrep)
+    relres = zeros(Float64, k, nrep)
+    reason = zeros(Int32, k, nrep)
+    done = Ref{Int64}(0)
+    q, ldw = observers === nothing ? (0, max(op.n, 1)) : observerdims(op, observers)
+    obs = zeros(Float64, q, k, nrep)
+    timeweights === nothing || length(timeweights) == nrep || throw(DimensionMismatch("timeweights of $(length(timeweights)), nsteps $nrep"))
+    Xbar = timeweights === nothing ? nothing : zeros(Float64, size(X)...)
+    ldm = max(op.n, 1)
+    scale = nothing
+    if sourcescale !== nothing   # the library reads entry t·k + c: column-major k x nsteps
+        source === nothing && throw(ArgumentError("sourcescale needs a source"))
+        size(sourcescale) == (X isa AbstractVector ? (nrep,) : (k, nrep)) ||
+            throw(DimensionMismatch("sourcescale $(size(sourcescale)), expected $(X isa AbstractVector ? (nrep,) : (k, nrep))"))
+        scale = Array{Float64}(sourcescale)
+    end
+    lock(CALL_LOCK) do
+        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        dptrs, ldd, dblocks = seasonblocks(op, d, X, "d", true)
+        ptrs, lds, blocks = seasonblocks(op, source, X, "source", false)
+        step_season_fn = sym(:otmb_op_step_season)
+        GC.@preserve dblocks blocks begin
+            rc = ccall(step_season_fn, Int32, (Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Ptr{Float64}}, Int64, Float64, Float64, Int64, Ptr{Int64}, Ptr{Int64},
+                    Ptr{Float64}, Int64, Ptr{Ptr{Float64}}, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Float64, Int64, Int32, Ptr{Int64}, Ptr{Int64},
+                    Ptr{Float64}, Ptr{Int32}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64),
+                op.handle, Int32(adjoint), k, Int64(length(dptrs)), isempty(dptrs) ? C_NULL : dptrs, ldd, Float64(dt), Float64(θ), nrep, sa, sb, w,
+                Int64(length(ptrs)), isempty(ptrs) ? C_NULL : ptrs, lds, scale === nothing ? C_NULL : scale, X, ldx,
+                Float64(rtol), Int64(maxiter), pc, done, iters, relres, reason,
+                Int64(q), observers === nothing ? C_NULL : observers, ldw, observers === nothing ? C_NULL : obs,
+                timeweights === nothing ? C_NULL : timeweights, Xbar === nothing ? C_NULL : Xbar, ldm)
+            rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which step and column stopped why
+        end
+    end
+    ran = 1:min(done[] + 1, nrep)
+    why = permutedims([SOLVE_REASONS[r + 1] for r in reason[:, ran]])
+    return X, (stepsdone = done[], iterations = permutedims(iters[:, ran]), relres = permutedims(relres[:, ran]), reason = why,
+               converged = why .== :converged, observations = observers === nothing ? nothing : obs[:, :, 1:done[]],
+               mean = (Xbar !== nothing && done[] > 0) ? Xbar : nothing)
+end
+function periodicseason!(X::StridedVecOrMat{Float64}, D::Union{DeviceOperator,AdjointDeviceOperator},
+                         source::Union{StridedVecOrMat{Float64},AbstractVector{<:StridedVecOrMat{Float64}}}; dt::Real,
+                         slota::AbstractVector{<:Integer}, slotb::AbstractVector{<:Integer}, weight::AbstractVector{<:Real}, θ::Real = 1.0,
+                         d::Union{Nothing,StridedVecOrMat{Float64},AbstractVector{<:StridedVecOrMat{Float64}}} = nothing, x0::Bool = false,
+                         rtol::Real = 1e-10, maxiter::Integer = 10000, precond::Symbol = :jacobi, outer::Symbol = :none, ptol::Real = 1e-8,
+                         restart::Integer = 30, maxcycles::Integer = 1000)
+    oc = outercode(outer)
+    pc = precondcode(precond)
+    adjoint = D isa AdjointDeviceOperator
+    op = adjoint ? D.parent : D
+    k, ldx, _ = scheddims(op, X, nothing)
+    sa, sb, w = seasonargs(slota, slotb, weight)
+    cycles = zeros(Int64, k)
+    defect = zeros(Float64, k)
+    reason = zeros(Int32, k)
+    msolve = zeros(Int64, k)
+    lock(CALL_LOCK) do
+        op.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        dptrs, ldd, dblocks = seasonblocks(op, d, X, "d", true)
+        ptrs, lds, blocks = seasonblocks(op, source, X, "source", false)
+        periodic_season_fn = sym(:otmb_op_periodic_season)
+        GC.@preserve dblocks blocks begin
+            rc = ccall(periodic_season_fn, Int32, (Ptr{Cvoid}, Int32, Int64, Int64, Ptr{Ptr{Float64}}, Int64, Float64, Float64, Int64, Ptr{Int64}, Ptr{Int64},
+                    Ptr{Float64}, Int64, Ptr{Ptr{Float64}}, Int64, Ptr{Float64}, Int64, Int32, Float64, Int64, Int32, Float64, Int64, Int64, Ptr{Int64},
+                    Ptr{Float64}, Ptr{Int32}, Int32, Ptr{Int64}),
+                op.handle, Int32(adjoint), k, Int64(length(dptrs)), isempty(dptrs) ? C_NULL : dptrs, ldd, Float64(dt), Float64(θ), Int64(length(w)), sa, sb, w,
                 Int64(length(ptrs)), ptrs, lds, X, ldx, Int32(x0), Float64(rtol), Int64(maxiter), pc, Float64(ptol),
                 Int64(restart), Int64(maxcycles), cycles, defect, reason, oc, msolve)
             rc == 19 || check(rc)      # OTMB_ERR_NOT_CONVERGED is an answer: info says which column stopped why

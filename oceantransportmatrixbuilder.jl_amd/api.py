@@ -836,6 +836,16 @@ def interp_schedule(nslots, substeps, *, ncycles=1, first_slot=0, at="mid"):
     return a, b, w
 
 
+def plain_schedule(nslots, nsteps, *, first_slot=0, substeps=1):
+    """(slot_a, slot_b, weight) = (a, a, zeros) with a[t] = (first_slot + t // substeps) mod nslots: the scheduled step's rule as the
+    explicit arrays of step_season / periodic_season (and step_interp), every step plain."""
+    nslots, nsteps, first_slot, m = int(nslots), int(nsteps), int(first_slot), int(substeps)
+    if nslots < 1 or nsteps < 0 or m < 1 or not 0 <= first_slot < nslots:
+        raise ValueError("plain_schedule: nslots >= 1, nsteps >= 0, substeps >= 1 and 0 <= first_slot < nslots")
+    a = (first_slot + np.arange(nsteps, dtype=np.int64) // m) % nslots
+    return a, a.copy(), np.zeros(nsteps, dtype=np.float64)
+
+
 class DeviceOperator(OperatorCalls):
     """A sparse operator resident on the device: Y = α·A·X + β·Y and Y = α·Aᵀ·X + β·Y, bit for bit SparseArrays' 5-argument mul! of
     Julia 1.10 -- what the reference's consumer checks compute (test/local_full.jl:96-107: norm(T * e1), norm(T' * v)) and what a tracer

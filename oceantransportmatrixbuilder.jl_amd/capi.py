@@ -281,6 +281,19 @@ SYMBOLS = {
     "otmb_op_periodic_interp": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp, C.c_int64,
                                              _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp,
                                              _vp, _vp, C.c_int32, _vp]),
+    # d per slot (nd, D: nd pointers, ldd in place of D, ldd): the arguments of the interpolated calls
+    "otmb_op_step_season_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp, C.c_int64,
+                                             _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64,
+                                             _vp, _vp, _vp, C.c_int64]),
+    "otmb_op_step_season": (C.c_int32, [_vp, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp, C.c_int64,
+                                         _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64,
+                                         _vp, _vp, _vp, C.c_int64]),
+    "otmb_op_periodic_season_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp,
+                                                 C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64,
+                                                 C.c_int64, _vp, _vp, _vp, C.c_int32, _vp]),
+    "otmb_op_periodic_season": (C.c_int32, [_vp, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp,
+                                             C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64,
+                                             C.c_int64, _vp, _vp, _vp, C.c_int32, _vp]),
     "otmb_op_combine_slots_dev": (C.c_int32, [_vp, _vp, C.c_int64]),
     "otmb_op_combine_slots": (C.c_int32, [_vp, _vp, C.c_int64]),
     "otmb_op_info": (C.c_int32, [_vp, _ip, _ip, _ip]),

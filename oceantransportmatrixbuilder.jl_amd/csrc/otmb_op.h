@@ -32,6 +32,7 @@ struct otmb_op {
     DevBuf pd;                            // otmb_op_periodic: the Krylov bases, the cycle's in/out columns, partial sums and scalars (otmb_periodic.hip)
     OpSlot mean;                          // otmb_op_periodic_pc, OTMB_OUTER_MEAN: the cycle-mean values, private like pd (made once per call)
     OpSlot interp;                        // otmb_op_step_interp: the values of a blended step, (1 - w)·(slot a) + w·(slot b) (otmb_interp.hip); never mean
+    DevBuf season, setab;                 // otmb_op_step_season: d and the source of a blended step (n·kc + n·k doubles); the fold's table of terms beyond 16 (otmb_season.hip)
     DevBuf ob, oh;                        // the observations (otmb_observe.hip): the partial sums; the host entry points' staging of obs, W, X / Xbar
     DevBuf cb;                            // otmb_op_combine_slots: the table of slot pointers and weights, beyond the 16 that travel as arguments
     DevBuf ln;                            // otmb_op_set_lines (Int32, 0-based, -1 = none): successor (n), predecessor (n), line heads ascending (nheads)
@@ -102,4 +103,21 @@ static int32_t op_stage_dk(otmb_op *op, const double *D, i64 ldd, i64 k, const d
     dev = (const double *)op->ds.p;
     devld = op->n;
     return op->n > 0 ? op_upload(ctx, (double *)op->ds.p, D, ldd, op->n, k) : OTMB_OK;
+}
+// The same for a list of nd blocks with the one ldd (otmb_op_*_season): nd <= 1 is the above with the one block or none; otherwise block j is
+// staged compactly behind block j - 1 (n values each when ldd == 0, n x k otherwise).  dev: the nd device pointers (one, maybe null, for nd <= 1)
+static int32_t op_stage_dl(otmb_op *op, i64 nd, const double *const *D, i64 ldd, i64 k, std::vector<const double *> &dev, i64 &devld) {
+    dev.assign((size_t)std::max<i64>(nd, 1), nullptr);
+    if (nd <= 1) return op_stage_dk(op, nd == 1 ? D[0] : nullptr, ldd, k, dev[0], devld);
+    otmb_ctx *ctx = op->ctx;
+    const i64 n = op->n, kc = ldd == 0 ? 1 : k;
+    int32_t rc;
+    if ((rc = otmb_reserve(ctx, op->ds, (size_t)(nd * n * kc) * 8 + 8))) return rc;
+    devld = ldd == 0 ? 0 : n;
+    for (i64 j = 0; j < nd; ++j) {
+        double *to = (double *)op->ds.p + j * n * kc;
+        dev[(size_t)j] = to;
+        if (n > 0 && (rc = op_upload(ctx, to, D[j], ldd == 0 ? n : ldd, n, kc))) return rc;
+    }
+    return OTMB_OK;
 }

@@ -46,6 +46,11 @@
 // otmb_op_periodic_interp[_dev], the cycle of interpolated steps: PdRun holds the schedule (mix) in place of first_slot / substeps, F is
 // otmb_op_step_interp_dev (cycle), and the mean's weights are the slots' shares of the schedule's weights, accumulated step by step in
 // the contract's order (mean_setup).  op->mean and the step's op->interp are different value sets: the call needs both at once.
+//
+// otmb_op_periodic_season[_dev], that cycle with d and the source per slot: F is otmb_op_step_season_dev; with a d per column and per slot
+// the gathered step calls carry the live columns of every d block (w.Dg: block j's columns behind block j - 1's, as w.Sg holds the
+// sources); and the mean operator is diag(d̄) + Ā with d̄ the fold of the d blocks under the mean's own weights (se_fold of otmb_season.hip
+// into w.dbar, once per call, before the mean's preconditioner is made).  With one block d̄ is that block, untouched.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -265,6 +270,7 @@ struct PdWork {  // the arrays inside op->pd; every vector has the leading dimen
     double *Z = nullptr, *mp = nullptr;   // OTMB_OUTER_MEAN: k blocks of m preconditioned directions behind Sb; the mean's preconditioner
     double *mpg = nullptr, *Dg = nullptr; // per-column d: the gathered columns of that preconditioner, and of D (2k columns: the first call's)
     double *Sg = nullptr;                 // more than one source block: the gathered columns of all of them (nsrc blocks of 2k columns)
+    double *dbar = nullptr;               // OTMB_OUTER_MEAN with a d per slot: the cycle-mean d̄ (n values, or n x k with the leading dimension ld)
     double *v(i64 c, i64 j) const { return V + (c * (m + 1) + j) * ld; }
     double *z(i64 c, i64 j) const { return Z + (c * m + j) * ld; }
     double *partc(i64 c) const { return part + c * (m + 2) * np; }
@@ -275,12 +281,15 @@ struct PdWork {  // the arrays inside op->pd; every vector has the leading dimen
 // zvecs: the vectors of the Z block a column (0, or m with OTMB_OUTER_MEAN); pdbl: the doubles of the mean's preconditioner (0 without);
 // percol: every column has its own d (a second block of pdbl doubles, and 2k gathered columns of D); nsrc: the source blocks (more than
 // one: nsrc·2k gathered columns behind everything else; one block's columns lie in Sb or, the first call's 2k, in the bases as ever)
-static int32_t pd_work(otmb_op *op, i64 k, i64 m, i64 zvecs, size_t pdbl, bool percol, i64 nsrc, PdWork &w) {
+// nd: the d blocks (with percol the 2k gathered columns of each; more than one and a mean: d̄ behind everything else)
+static int32_t pd_work(otmb_op *op, i64 k, i64 m, i64 zvecs, size_t pdbl, bool percol, i64 nsrc, i64 nd, PdWork &w) {
     const i64 n = op->n;
     w.n = n, w.k = k, w.m = m, w.ld = (n + 1) & ~(i64)1, w.np = (n + PD_ROWS - 1) / PD_ROWS;
-    const size_t head = (percol ? 2 : 1) * pdbl + (percol ? (size_t)(2 * k * w.ld) : 0);
-    if (nsrc > 1 && (double)nsrc * 2.0 * (double)k * (double)w.ld >= 1.0e18) return otmb_fail(op->ctx, OTMB_ERR_ALLOC, "periodic: the workspace's size overflows");
-    const size_t tail = head + (nsrc > 1 ? (size_t)(nsrc * 2 * k * w.ld) : 0);
+    const i64 ndg = percol ? std::max<i64>(nd, 1) : 0;
+    if ((double)(nsrc + ndg + 1) * 2.0 * (double)k * (double)w.ld >= 1.0e18) return otmb_fail(op->ctx, OTMB_ERR_ALLOC, "periodic: the workspace's size overflows");
+    const size_t head = (percol ? 2 : 1) * pdbl + (size_t)(ndg * 2 * k * w.ld);
+    const size_t body = head + (nsrc > 1 ? (size_t)(nsrc * 2 * k * w.ld) : 0);
+    const size_t tail = body + (nd > 1 && pdbl ? (size_t)((percol ? k : 1) * w.ld) : 0);
     const double need = ((double)(m + 3 + zvecs) * (double)w.ld + (double)(m + 2) * (double)w.np + 3.0 * (double)(m + 2)) * (double)k * 8.0 +
                         (double)tail * 8.0;
     if (need >= 9.0e18) return otmb_fail(op->ctx, OTMB_ERR_ALLOC, "periodic: the workspace's size overflows");
@@ -299,6 +308,7 @@ static int32_t pd_work(otmb_op *op, i64 k, i64 m, i64 zvecs, size_t pdbl, bool p
     w.mpg = pdbl && percol ? w.mp + pdbl : nullptr;
     w.Dg = percol ? w.V + vec + scal + 2 * pdbl : nullptr;
     w.Sg = nsrc > 1 ? w.V + vec + scal + head : nullptr;
+    w.dbar = nd > 1 && pdbl ? w.V + vec + scal + body : nullptr;
     return OTMB_OK;
 }
 
@@ -352,6 +362,8 @@ struct PdRun {  // one call: the operator, the call's arguments, the workspace, 
     i64 m, maxcycles;
     int32_t outer;
     const StMix *mix;  // otmb_op_periodic_interp: the interpolated schedule of ncycle steps in place of first_slot / substeps (null: none)
+    StD dl;            // d as a list of blocks; d above is its first (or none).  More than one: otmb_op_periodic_season
+    bool season;       // F is otmb_op_step_season_dev
     PdWork w{};
     dim3 grid, block;
     bool alx = false;  // X takes the 16-byte path
@@ -387,7 +399,7 @@ struct PdRun {  // one call: the operator, the call's arguments, the workspace, 
 int32_t PdRun::prepare() {
     int32_t rc;
     const bool mean = outer == OTMB_OUTER_MEAN;
-    if ((rc = pd_work(op, k, m, mean ? m : 0, mean ? sv_prec_doubles(op->n, precond == OTMB_PRECOND_LINES, sv_prec_cols(d, k)) : 0, d.percol(), nsrc, w))) return rc;
+    if ((rc = pd_work(op, k, m, mean ? m : 0, mean ? sv_prec_doubles(op->n, precond == OTMB_PRECOND_LINES, sv_prec_cols(d, k)) : 0, d.percol(), nsrc, dl.nd, w))) return rc;
     grid = dim3((unsigned)w.np), block = dim3(256);
     alx = ((uintptr_t)X & 15) == 0 && (ldx & 1) == 0;
     col.resize((size_t)k);
@@ -442,10 +454,19 @@ int32_t PdRun::mean_setup() {
         for (i64 s = 0; s < nslots; ++s) wt[(size_t)s] = (double)count[(size_t)s] / (double)ncycle;
     }
     if ((rc = cb_combine(op, wt.data(), op->mean))) return rc;
+    SvD dm = d;
+    if (dl.nd > 1) {  // d̄: the fold of the d blocks under the same weights -- the slots with a weight that is not zero, in ascending order
+        std::vector<const double *> blocks;
+        std::vector<double> terms;
+        for (i64 s = 0; s < nslots; ++s)
+            if (wt[(size_t)s] != 0.0) blocks.push_back(dl.D[s]), terms.push_back(wt[(size_t)s]);
+        if ((rc = se_fold(op, blocks, terms, w.n, sv_prec_cols(d, k), dl.ldd, w.dbar, w.ld))) return rc;
+        dm = SvD{w.dbar, d.percol() ? w.ld : 0};
+    }
     period = (double)ncycle * dt;
     mean_pc = sv_prec_carve(w.mp, w.n, precond == OTMB_PRECOND_LINES, sv_prec_cols(d, k), d.percol());
     SvValues on(op, op->mean);
-    if ((rc = sv_prec_prepare(op, adjoint, precond, d, 0.0, mean_pc))) ctx->err += " (the cycle-mean operator)";
+    if ((rc = sv_prec_prepare(op, adjoint, precond, dm, 0.0, mean_pc))) ctx->err += " (the cycle-mean operator)";
     return rc;
 }
 
@@ -515,14 +536,20 @@ int32_t PdRun::cycle(std::vector<PdItem> &items, bool withS, double *sbuf) {
                 HIP_TRY(ctx, hipMemcpyAsync(w.W + p * ld, it.from >= 0 ? dir(it.col, it.from) : X + it.col * ldx, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
             for (i64 j = 0; withS && j < nsrc; ++j)
                 HIP_TRY(ctx, hipMemcpyAsync(sbuf + (j * kk + p) * ld, S[j] + it.col * lds, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-            if (d.percol()) HIP_TRY(ctx, hipMemcpyAsync(w.Dg + p * ld, d.p + it.col * d.ld, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+            for (i64 j = 0; d.percol() && j < dl.nd; ++j)
+                HIP_TRY(ctx, hipMemcpyAsync(w.Dg + (j * kk + p) * ld, dl.D[j] + it.col * dl.ldd, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
         }
         s_it.assign((size_t)(ncycle * kk), 0), s_rr.assign((size_t)(ncycle * kk), 0.0), s_why.assign((size_t)(ncycle * kk), 0);
         int64_t done = 0;
         std::vector<const double *> sp((size_t)(withS ? nsrc : 0));
         for (size_t j = 0; j < sp.size(); ++j) sp[j] = sbuf + (i64)j * kk * ld;
+        std::vector<const double *> dp((size_t)dl.nd);  // the step call's d blocks: the gathered columns, or the shared blocks as they are
+        for (size_t j = 0; j < dp.size(); ++j) dp[j] = d.percol() ? w.Dg + (i64)j * kk * ld : dl.D[j];
         const int32_t rc =
-            mix ? otmb_op_step_interp_dev(op, adjoint, kk, d.percol() ? w.Dg : d.p, d.percol() ? ld : 0, dt, theta, ncycle, mix->a, mix->b, mix->w, (i64)sp.size(),
+            season ? otmb_op_step_season_dev(op, adjoint, kk, dl.nd, dp.data(), d.percol() ? ld : 0, dt, theta, ncycle, mix->a, mix->b, mix->w, (i64)sp.size(),
+                                             sp.data(), ld, nullptr, w.W, ld, rtol, maxiter, precond, &done, s_it.data(), s_rr.data(), s_why.data(), 0, nullptr, 0,
+                                             nullptr, nullptr, nullptr, 0)
+            : mix ? otmb_op_step_interp_dev(op, adjoint, kk, d.percol() ? w.Dg : d.p, d.percol() ? ld : 0, dt, theta, ncycle, mix->a, mix->b, mix->w, (i64)sp.size(),
                                           sp.data(), ld, nullptr, w.W, ld, rtol, maxiter, precond, &done, s_it.data(), s_rr.data(), s_why.data(), 0, nullptr, 0,
                                           nullptr, nullptr, nullptr, 0)
                 : otmb_op_step_sched_dev(op, adjoint, kk, d.percol() ? w.Dg : d.p, d.percol() ? ld : 0, dt, theta, ncycle, first_slot, substeps, (i64)sp.size(),
@@ -734,8 +761,8 @@ static int32_t pd_check_call(otmb_op *op, const char *call, bool sched, int64_t 
     return more ? otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, (std::string(mix ? "otmb_op_periodic_interp: " : "otmb_op_periodic_sched: ") + more).c_str()) : OTMB_OK;
 }
 
-// the call proper: device pointers (S: a host array of nsrc of them), the arguments checked
-static int32_t pd_run_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle, int64_t first_slot,
+// the call proper: device pointers (S: a host array of nsrc of them; dl: d as a list of blocks), the arguments checked
+static int32_t pd_run_dl(otmb_op *op, int32_t adjoint, int64_t k, const StD &dl, bool season, double dt, double theta, int64_t ncycle, int64_t first_slot,
                           int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol,
                           int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
                           int32_t outer, int64_t *msolve_iters, const StMix *mix = nullptr) {
@@ -748,7 +775,7 @@ static int32_t pd_run_dev(otmb_op *op, int32_t adjoint, int64_t k, const double 
         HIP_TRY(ctx, hipMemset2DAsync(X, (size_t)ldx * 8, 0, (size_t)op->n * 8, (size_t)k, ctx->stream));
         return pd_all_zero(k, cycles, defect, reason, msolve_iters);
     }
-    PdRun r{op, ctx, ctx->stream, adjoint, k, SvD{D, ldd}, dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, outer, mix};
+    PdRun r{op, ctx, ctx->stream, adjoint, k, dl.at(0), dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, outer, mix, dl, season};
     std::vector<PdItem> items;
     if ((rc = r.prepare()) || (outer == OTMB_OUTER_MEAN && (rc = r.mean_setup())) || (rc = r.source_norms(items)) || (rc = r.first_call(items))) return rc;
     for (bool more = true; more;)
@@ -757,8 +784,18 @@ static int32_t pd_run_dev(otmb_op *op, int32_t adjoint, int64_t k, const double 
     return r.report(cycles, defect, reason, msolve_iters);
 }
 
-// the host variant: the start, every source block and D staged once, X home once
-static int32_t pd_run_host(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle, int64_t first_slot,
+// every call but the season's: at most the one block of d
+static int32_t pd_run_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle, int64_t first_slot,
+                          int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol,
+                          int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
+                          int32_t outer, int64_t *msolve_iters, const StMix *mix = nullptr) {
+    const double *const one[1] = {D};
+    return pd_run_dl(op, adjoint, k, StD{D ? 1 : 0, one, ldd}, false, dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond,
+                     ptol, restart, maxcycles, cycles, defect, reason, outer, msolve_iters, mix);
+}
+
+// the host variant: the start, every source block and every d block staged once, X home once
+static int32_t pd_run_host_dl(otmb_op *op, int32_t adjoint, int64_t k, const StD &dl, bool season, double dt, double theta, int64_t ncycle, int64_t first_slot,
                            int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol,
                            int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
                            int32_t outer, int64_t *msolve_iters, const StMix *mix = nullptr) {
@@ -766,8 +803,9 @@ static int32_t pd_run_host(otmb_op *op, int32_t adjoint, int64_t k, const double
     otmb_ctx *ctx = op->ctx;
     HIP_TRY(ctx, hipSetDevice(op->device));
     const i64 n = op->n;
-    SvD dd;
-    if ((rc = op_reserve_xy(op, n, nsrc * n, k)) || (rc = op_stage_dk(op, D, ldd, k, dd.p, dd.ld))) return rc;
+    std::vector<const double *> dd;
+    i64 lddev = 0;
+    if ((rc = op_reserve_xy(op, n, nsrc * n, k)) || (rc = op_stage_dl(op, dl.nd, dl.D, dl.ldd, k, dd, lddev))) return rc;
     double *dx = (double *)op->xs.p;
     std::vector<const double *> ds((size_t)nsrc);  // block j compact behind block j - 1
     for (i64 j = 0; j < nsrc; ++j) ds[(size_t)j] = (const double *)op->ys.p + j * n * k;
@@ -776,10 +814,61 @@ static int32_t pd_run_host(otmb_op *op, int32_t adjoint, int64_t k, const double
         for (i64 j = 0; j < nsrc; ++j)
             if ((rc = op_upload(ctx, (double *)op->ys.p + j * n * k, S[j], lds, n, k))) return rc;
     }
-    rc = pd_run_dev(op, adjoint, k, dd.p, dd.ld, dt, theta, ncycle, first_slot, substeps, nsrc, ds.data(), n, dx, n, use_x0, rtol, maxiter, precond, ptol, restart,
-                    maxcycles, cycles, defect, reason, outer, msolve_iters, mix);
+    rc = pd_run_dl(op, adjoint, k, StD{dd[0] ? dl.nd : 0, dd.data(), lddev}, season, dt, theta, ncycle, first_slot, substeps, nsrc, ds.data(), n, dx, n, use_x0, rtol,
+                   maxiter, precond, ptol, restart, maxcycles, cycles, defect, reason, outer, msolve_iters, mix);
     if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED) return rc;
     return op_finish(ctx, rc, X, ldx, dx, n, k);
+}
+static int32_t pd_run_host(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle, int64_t first_slot,
+                           int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol,
+                           int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
+                           int32_t outer, int64_t *msolve_iters, const StMix *mix = nullptr) {
+    const double *const one[1] = {D};
+    return pd_run_host_dl(op, adjoint, k, StD{D ? 1 : 0, one, ldd}, false, dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter,
+                          precond, ptol, restart, maxcycles, cycles, defect, reason, outer, msolve_iters, mix);
+}
+
+// the checks of the season call: those of the call it extends, then the schedule's and the sources' (a block per slot is in order), then the d blocks'
+static int32_t pd_check_season(otmb_op *op, int64_t k, const StD &dl, double dt, double theta, int64_t ncycle, const StMix &mix, int64_t nsrc,
+                               const double *const *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, double ptol,
+                               int64_t restart, int64_t maxcycles, const int64_t *cycles, const double *defect, const int32_t *reason, int32_t outer) {
+    int32_t rc;
+    if ((rc = pd_check(op, k, dt, theta, ncycle, 0, nsrc > 0 && S ? S[0] : nullptr, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect,
+                       reason, outer)))
+        return rc;
+    char text[160];
+    const char *more = sv_interp_complaint(op, ncycle, mix, nsrc, S, lds, text, true);
+    if (!more) more = sv_season_complaint(op, dl.nd, dl.D, dl.ldd);
+    return more ? otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, (std::string("otmb_op_periodic_season: ") + more).c_str()) : OTMB_OK;
+}
+
+// the interpolated schedule with d and the source per slot: nd, D (nd pointers), ldd in place of D, ldd; F is otmb_op_step_season_dev
+int32_t otmb_op_periodic_season_dev(otmb_op *op, int32_t adjoint, int64_t k, int64_t nd, const double *const *D, int64_t ldd, double dt, double theta,
+                                    int64_t ncycle, const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S,
+                                    int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol,
+                                    int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    const StMix mix = {slot_a, slot_b, weight};
+    const StD dl = {nd, D, ldd};
+    int32_t rc;
+    if ((rc = pd_check_season(op, k, dl, dt, theta, ncycle, mix, nsrc, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect, reason, outer)))
+        return rc;
+    return pd_run_dl(op, adjoint, k, dl, true, dt, theta, ncycle, 0, 1, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect,
+                     reason, outer, msolve_iters, &mix);
+}
+
+int32_t otmb_op_periodic_season(otmb_op *op, int32_t adjoint, int64_t k, int64_t nd, const double *const *D, int64_t ldd, double dt, double theta, int64_t ncycle,
+                                const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S, int64_t lds, double *X,
+                                int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles,
+                                int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    const StMix mix = {slot_a, slot_b, weight};
+    const StD dl = {nd, D, ldd};
+    int32_t rc;
+    if ((rc = pd_check_season(op, k, dl, dt, theta, ncycle, mix, nsrc, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect, reason, outer)))
+        return rc;
+    return pd_run_host_dl(op, adjoint, k, dl, true, dt, theta, ncycle, 0, 1, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, cycles,
+                          defect, reason, outer, msolve_iters, &mix);
 }
 
 int32_t otmb_op_periodic_sched_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,

@@ -107,7 +107,28 @@ struct StMix {
 };
 // sv_interp_complaint (otmb_step.hip): the first complaint about an interpolated schedule of `count` steps and its nsrc, or null (text: at
 //                  least 160 chars of scratch for a message that names an entry).
-const char *sv_interp_complaint(const otmb_op *op, int64_t count, const StMix &mix, int64_t nsrc, const double *const *S, int64_t lds, char *text);
+//                  per_slot: nsrc may also be the number of slots (otmb_op_*_season); otherwise it is 0 or 1.
+const char *sv_interp_complaint(const otmb_op *op, int64_t count, const StMix &mix, int64_t nsrc, const double *const *S, int64_t lds, char *text,
+                                bool per_slot = false);
+
+// d as a list of blocks (otmb_op_*_season, include/otmb.h): nd = 0 (none), 1 (the block serves every step) or nslots (a block per slot), each
+// n values (ldd == 0) or n x k (ldd >= n); D: a HOST array of nd pointers.  Every other call passes at most one block.
+struct StD {
+    i64 nd;
+    const double *const *D;
+    i64 ldd;
+    SvD at(i64 slot) const { return nd == 0 ? SvD{nullptr, 0} : SvD{D[nd == 1 ? 0 : slot], ldd}; }
+    bool percol() const { return nd > 0 && ldd != 0 && D[0]; }
+};
+// sv_season_complaint (otmb_step.hip): the first complaint about such a list, or null: what the season calls add to the checks.
+const char *sv_season_complaint(const otmb_op *op, int64_t nd, const double *const *D, int64_t ldd);
+
+// The fold of dense blocks (otmb_season.hip): a blended step's d and source, and the cycle-mean d̄.
+// se_reserve: op->season at that many doubles (allocated on first use; may wait for the device).
+// se_fold:    Σ_t wt[t]·src[t] in the vectors' order (each rows x cols with leading dimension ld) into dst (leading dimension ldo), ONE launch
+//             enqueued on the context's stream; more than 16 terms travel through a device table, whose write waits for the stream.
+int32_t se_reserve(otmb_op *op, size_t doubles);
+int32_t se_fold(otmb_op *op, const std::vector<const double *> &src, const std::vector<double> &wt, i64 rows, i64 cols, i64 ld, double *dst, i64 ldo);
 
 // The observation pass (otmb_observe.hip), which the step runs after every completed step.
 // ob_reserve:   the partial sums of q x k entries in op->ob (may wait for the stream: before the loop, never inside it).

@@ -22,6 +22,10 @@
 // slots are one, or whose weight is 0 or 1, is a step of the loop as it stands; a blended step writes (1 - w)·(slot a) + w·(slot b) into
 // op->interp (ip_blend of otmb_interp.hip, one launch), points the values at it (SvValues) and makes its preconditioner afresh into one
 // block that all blended steps share -- the setup and its wait for the device on every such step are the cost of the convention.
+//
+// otmb_op_step_season[_dev] is that loop with d, and the source, per slot as well (StD, StSrc with nsrc = nslots): a plain step takes its
+// slot's blocks, a blended step folds the two slots' blocks with the step's own weights into op->season (se_fold of otmb_season.hip, one
+// launch per field) before its preconditioner is made.  A field given once is never folded.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -228,8 +232,9 @@ const char *sv_sched_complaint(const otmb_op *op, int64_t substeps, int64_t nsrc
 }
 // What otmb_op_step_interp and otmb_op_periodic_interp add (shared like the above): nsrc is 0 or 1, then the schedule's complaints about the
 // source, then the three arrays -- none null, every slot one of the operator's, every weight finite and in [0, 1].
-const char *sv_interp_complaint(const otmb_op *op, int64_t count, const StMix &mix, int64_t nsrc, const double *const *S, int64_t lds, char *text) {
-    if (nsrc != 0 && nsrc != 1) return "nsrc must be 0 or 1 (a source per slot is not built with interpolation)";
+const char *sv_interp_complaint(const otmb_op *op, int64_t count, const StMix &mix, int64_t nsrc, const double *const *S, int64_t lds, char *text,
+                                bool per_slot) {
+    if (!per_slot && nsrc != 0 && nsrc != 1) return "nsrc must be 0 or 1 (a source per slot is not built with interpolation)";
     if (const char *more = sv_sched_complaint(op, 1, nsrc, S, lds)) return more;
     if (count > 0 && (!mix.a || !mix.b || !mix.w)) return "slot_a, slot_b or weight is null";
     const i64 nslots = (i64)op->slots.size();
@@ -246,15 +251,28 @@ const char *sv_interp_complaint(const otmb_op *op, int64_t count, const StMix &m
     }
     return nullptr;
 }
-// (call: the export the message names; mix: the interpolated schedule, null without one)
-static int32_t st_check_sched(otmb_op *op, const char *call, int64_t k, int64_t nsteps, const StSrc &src, const StMix *mix) {
+// What otmb_op_step_season and otmb_op_periodic_season add (shared like the above): the list of d blocks.
+const char *sv_season_complaint(const otmb_op *op, int64_t nd, const double *const *D, int64_t ldd) {
+    if (nd != 0 && nd != 1 && nd != (i64)op->slots.size()) return "nd must be 0, 1 or the number of slots";
+    if (nd > 0) {
+        if (!D) return "D is null with nd > 0";
+        for (i64 j = 0; j < nd; ++j)
+            if (!D[j]) return "a d block is null";
+        if (ldd != 0 && ldd < op->n) return "ldd must be 0 (the n values of a block serve every column) or >= n";
+    }
+    return nullptr;
+}
+// (call: the export the message names; mix: the interpolated schedule, null without one; dl: the season call's list of d blocks, null
+// without one -- a source per slot is then in order under interpolation)
+static int32_t st_check_sched(otmb_op *op, const char *call, int64_t k, int64_t nsteps, const StSrc &src, const StMix *mix, const StD *dl = nullptr) {
     char text[160];
-    const char *more = mix ? sv_interp_complaint(op, nsteps, *mix, src.nsrc, src.S, src.lds, text) : sv_sched_complaint(op, src.substeps, src.nsrc, src.S, src.lds);
+    const char *more = mix ? sv_interp_complaint(op, nsteps, *mix, src.nsrc, src.S, src.lds, text, dl != nullptr) : sv_sched_complaint(op, src.substeps, src.nsrc, src.S, src.lds);
     if (!more && src.scale) {
         if (src.nsrc == 0) more = "scale needs a source (nsrc > 0)";
         for (i64 e = 0; !more && e < nsteps * k; ++e)
             if (!std::isfinite(src.scale[e])) more = "a scale value is not finite";
     }
+    if (!more && dl) more = sv_season_complaint(op, dl->nd, dl->D, dl->ldd);
     return more ? otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, (std::string(call) + ": " + more).c_str()) : OTMB_OK;
 }
 
@@ -267,7 +285,12 @@ static int32_t st_check_sched(otmb_op *op, const char *call, int64_t k, int64_t 
 // (w == 1.0) or blended.  A blended step points the values at op->interp (SvValues) for its blend, its preconditioner -- made afresh into
 // the ONE block all blended steps share, behind the plain slots' --, its right-hand side and its solve.  Without mix nothing here differs
 // from the loop as it was: the same launches in the same order.
-static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, double dt, double theta, int64_t nsteps, int64_t first_slot, const StSrc &src,
+//
+// dl is d as a list of blocks: at most one for every call but otmb_op_step_season, whose plain steps take their slot's block -- d is then a
+// function of the slot, so a slot's kept preconditioner stays exact -- and whose blended steps fold the two slots' blocks of d, and of the
+// source when it is per slot, into op->season (se_fold of otmb_season.hip, one launch each) before the preconditioner is made.  With one
+// block each nothing is folded and nothing is reserved.
+static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const StD &dl, double dt, double theta, int64_t nsteps, int64_t first_slot, const StSrc &src,
                       double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters, double *relres, int32_t *reason,
                       const StObs &o, const StMix *mix = nullptr) {
     int32_t rc;
@@ -289,7 +312,7 @@ static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, dou
     const StLine q = {1.0 / tdt, theta, (1.0 - theta) / theta};
     // op->st: B, then one preconditioner per slot the call visits (per column where every tracer has its own d), then the scales (nsteps x k)
     i64 used = std::min((nsteps - 1) / src.substeps + 1, nslots);
-    const i64 kc = sv_prec_cols(d, k);
+    const i64 kc = dl.percol() ? k : 1;
     if (mix) {  // the plain slots the schedule visits, and one block for every blended step together
         std::vector<char> seen((size_t)nslots, 0);
         bool blended = false;
@@ -304,6 +327,7 @@ static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, dou
         if (blended) {
             used += 1;
             if ((rc = ip_reserve(op))) return rc;
+            if ((dl.nd > 1 || src.nsrc > 1) && (rc = se_reserve(op, (size_t)(n * kc) + (size_t)(n * k)))) return rc;
         }
     }
     const size_t per = sv_prec_doubles(n, lines, kc);
@@ -341,17 +365,31 @@ static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, dou
             const double w = mix->w[t];
             const double wa = 1.0 - w;
             if ((rc = ip_blend(op, mix->a[t], mix->b[t], wa, w))) return here(rc);
+            SvD d = dl.at(slot);
+            const double *St = src.at(slot);
+            i64 ldst = src.lds;
+            if (dl.nd > 1) {  // d of the step: wa·(block a) + w·(block b), compact in op->season
+                double *Dt = (double *)op->season.p;
+                if ((rc = se_fold(op, {dl.D[mix->a[t]], dl.D[mix->b[t]]}, {wa, w}, n, kc, dl.ldd, Dt, n))) return here(rc);
+                d = SvD{Dt, dl.ldd ? n : 0};
+            }
+            if (src.nsrc > 1) {  // and its source, behind it; the step's scale multiplies the blend (st_line)
+                double *Sm = (double *)op->season.p + n * kc;
+                if ((rc = se_fold(op, {src.S[mix->a[t]], src.S[mix->b[t]]}, {wa, w}, n, k, src.lds, Sm, n))) return here(rc);
+                St = Sm, ldst = n;
+            }
             SvValues on(op, op->interp);
-            if (!shared.sh) shared = sv_prec_carve(pool + (size_t)(taken++) * per, n, lines, kc, d.percol());
+            if (!shared.sh) shared = sv_prec_carve(pool + (size_t)(taken++) * per, n, lines, kc, dl.percol());
             if ((rc = sv_prec_prepare(op, adjoint, precond, d, q.sigma, shared))) return here(rc);
-            st_rhs(op, adjoint, k, q, d, X, ldx, src.at(slot), src.lds, fdev ? fdev + t * k : nullptr, B);
+            st_rhs(op, adjoint, k, q, d, X, ldx, St, ldst, fdev ? fdev + t * k : nullptr, B);
             HIP_TRY(ctx, hipGetLastError());
             if ((rc = sv_solve(op, adjoint, k, shared, B, n, X, ldx, 1, rtol, maxiter, iters + t * k, relres + t * k, reason + t * k, precond))) return here(rc);
         } else {
             if ((rc = otmb_op_select_slot(op, slot))) return rc;
+            const SvD d = dl.at(slot);
             SvPrec &p = prec[(size_t)slot];
             if (!p.sh) {  // the slot's first visit
-                p = sv_prec_carve(pool + (size_t)(taken++) * per, n, lines, kc, d.percol());
+                p = sv_prec_carve(pool + (size_t)(taken++) * per, n, lines, kc, dl.percol());
                 if ((rc = sv_prec_prepare(op, adjoint, precond, d, q.sigma, p))) return here(rc);
             }
             st_rhs(op, adjoint, k, q, d, X, ldx, src.at(slot), src.lds, fdev ? fdev + t * k : nullptr, B);
@@ -368,7 +406,7 @@ static int32_t st_run(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, dou
 }
 
 // The host variant of the loop: X, every source block, d, W staged once; X, the written rows of obs and Xbar come home once.
-static int32_t st_run_host(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d, double dt, double theta, int64_t nsteps, int64_t first_slot,
+static int32_t st_run_host(otmb_op *op, int32_t adjoint, int64_t k, const StD &dl, double dt, double theta, int64_t nsteps, int64_t first_slot,
                            const StSrc &src, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters,
                            double *relres, int32_t *reason, const StObs &o, const StMix *mix = nullptr) {
     int32_t rc;
@@ -377,8 +415,9 @@ static int32_t st_run_host(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d
     if (nsteps == 0) return OTMB_OK;
     otmb_ctx *ctx = op->ctx;
     HIP_TRY(ctx, hipSetDevice(op->device));
-    SvD dd;
-    if ((rc = op_reserve_xy(op, n, src.nsrc * n, k)) || (rc = op_stage_dk(op, d.p, d.ld, k, dd.p, dd.ld))) return rc;
+    std::vector<const double *> dd;
+    i64 lddev = 0;
+    if ((rc = op_reserve_xy(op, n, src.nsrc * n, k)) || (rc = op_stage_dl(op, dl.nd, dl.D, dl.ldd, k, dd, lddev))) return rc;
     double *dx = (double *)op->xs.p;
     std::vector<const double *> ds((size_t)src.nsrc);  // block j compact behind block j - 1
     for (i64 j = 0; j < src.nsrc; ++j) ds[(size_t)j] = (const double *)op->ys.p + j * n * k;
@@ -396,7 +435,7 @@ static int32_t st_run_host(otmb_op *op, int32_t adjoint, int64_t k, const SvD &d
         od = {o.q, o.q > 0 ? dw : nullptr, n, o.q > 0 ? dobs : nullptr, o.tw, o.Xbar ? dm : nullptr, n};
     }
     const StSrc sd = {src.substeps, src.nsrc, ds.data(), n, src.scale};
-    rc = st_run(op, adjoint, k, dd, dt, theta, nsteps, first_slot, sd, dx, n, rtol, maxiter, precond, steps_done, iters, relres, reason, od, mix);
+    rc = st_run(op, adjoint, k, StD{dd[0] ? dl.nd : 0, dd.data(), lddev}, dt, theta, nsteps, first_slot, sd, dx, n, rtol, maxiter, precond, steps_done, iters, relres, reason, od, mix);
     // X comes back when it holds an answer: every step done, a step's last iterates, or the state before a slot whose preconditioner is singular
     if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED && !(rc == OTMB_ERR_SINGULAR_PRECONDITIONER && *steps_done > 0)) return rc;
     // ... and with it the observations of the completed steps and their mean
@@ -419,8 +458,21 @@ static int32_t st_call(otmb_op *op, const char *call, const char *sched, int32_t
     if ((rc = st_check(op, k, dt, theta, nsteps, first_slot, src, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o)) ||
         (rc = sv_check_d(op, call, D, ldd)) || (sched && (rc = st_check_sched(op, sched, k, nsteps, src, mix))))
         return rc;
-    return (DEV ? st_run : st_run_host)(op, adjoint, k, SvD{D, ldd}, dt, theta, nsteps, first_slot, src, X, ldx, rtol, maxiter, precond, steps_done, iters, relres,
-                                        reason, o, mix);
+    const double *const one[1] = {D};
+    return (DEV ? st_run : st_run_host)(op, adjoint, k, StD{D ? 1 : 0, one, ldd}, dt, theta, nsteps, first_slot, src, X, ldx, rtol, maxiter, precond, steps_done,
+                                        iters, relres, reason, o, mix);
+}
+// the season calls: d as a list of blocks (dl), the interpolated schedule, a source per slot in order; their own checks come last
+template <bool DEV>
+static int32_t st_call_season(otmb_op *op, int32_t adjoint, int64_t k, const StD &dl, double dt, double theta, int64_t nsteps, const StMix &mix, const StSrc &src,
+                              double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters, double *relres,
+                              int32_t *reason, const StObs &o) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    int32_t rc;
+    if ((rc = st_check(op, k, dt, theta, nsteps, 0, src, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o)) ||
+        (rc = st_check_sched(op, "otmb_op_step_season", k, nsteps, src, &mix, &dl)))
+        return rc;
+    return (DEV ? st_run : st_run_host)(op, adjoint, k, dl, dt, theta, nsteps, 0, src, X, ldx, rtol, maxiter, precond, steps_done, iters, relres, reason, o, &mix);
 }
 
 extern "C" {
@@ -459,6 +511,24 @@ int32_t otmb_op_step_interp(otmb_op *op, int32_t adjoint, int64_t k, const doubl
     const StMix mix = {slot_a, slot_b, weight};
     return st_call<false>(op, "otmb_op_step_interp", "otmb_op_step_interp", adjoint, k, D, ldd, dt, theta, nsteps, 0, StSrc{1, nsrc, S, lds, scale}, X, ldx, rtol,
                           maxiter, precond, steps_done, iters, relres, reason, StObs{q, W, ldw, obs, tw, Xbar, ldm}, &mix);
+}
+
+// the interpolated schedule with d and the source per slot: nd, D (nd pointers), ldd in place of D, ldd; nsrc may be the number of slots
+int32_t otmb_op_step_season_dev(otmb_op *op, int32_t adjoint, int64_t k, int64_t nd, const double *const *D, int64_t ldd, double dt, double theta,
+                                int64_t nsteps, const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S,
+                                int64_t lds, const double *scale, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done,
+                                int64_t *iters, double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw,
+                                double *Xbar, int64_t ldm) {
+    return st_call_season<true>(op, adjoint, k, StD{nd, D, ldd}, dt, theta, nsteps, StMix{slot_a, slot_b, weight}, StSrc{1, nsrc, S, lds, scale}, X, ldx, rtol,
+                                maxiter, precond, steps_done, iters, relres, reason, StObs{q, W, ldw, obs, tw, Xbar, ldm});
+}
+
+int32_t otmb_op_step_season(otmb_op *op, int32_t adjoint, int64_t k, int64_t nd, const double *const *D, int64_t ldd, double dt, double theta, int64_t nsteps,
+                            const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S, int64_t lds,
+                            const double *scale, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, int64_t *steps_done, int64_t *iters,
+                            double *relres, int32_t *reason, int64_t q, const double *W, int64_t ldw, double *obs, const double *tw, double *Xbar, int64_t ldm) {
+    return st_call_season<false>(op, adjoint, k, StD{nd, D, ldd}, dt, theta, nsteps, StMix{slot_a, slot_b, weight}, StSrc{1, nsrc, S, lds, scale}, X, ldx, rtol,
+                                 maxiter, precond, steps_done, iters, relres, reason, StObs{q, W, ldw, obs, tw, Xbar, ldm});
 }
 
 // the calls from before the schedule: substeps = 1, the one source or none, no scale

@@ -806,6 +806,15 @@ class DeviceAssembler:
         """Operator.periodic_interp on the resident operator over `matrix`: periodic_tracers over a cycle of interpolated steps."""
         return self._slotted(matrix).op.periodic_interp(source, **kw)
 
+    def step_tracers_season(self, X, *, matrix="T", **kw):
+        """Operator.step_season on the resident operator over `matrix`: step_tracers_interp with d and the source per slot as well (lists of
+        one or nslots tensors), blended with the matrices."""
+        return self._slotted(matrix).op.step_season(X, **kw)
+
+    def periodic_tracers_season(self, source, *, matrix="T", **kw):
+        """Operator.periodic_season on the resident operator over `matrix`: the periodic state under a seasonal d and a seasonal source."""
+        return self._slotted(matrix).op.periodic_season(source, **kw)
+
     def combine_slots(self, weights, dst, matrix="T"):
         """Operator.combine_slots on the resident operator over `matrix`: slot dst = Σ_s weights[s]·(slot s) over the slots keep_slot() filled
         (the annual mean of the kept months).  The written slot is not the resident result: when it is the selected one, the operator counts

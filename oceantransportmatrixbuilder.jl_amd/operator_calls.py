@@ -408,6 +408,116 @@ class OperatorCalls:
                         float(ptol), int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data, reason.ctypes.data, oc, msolve.ctypes.data)
         return X, PeriodicInfo(self._status(rc), cycles, defect, reason, msolve)
 
+    def _ds(self, d, B, what):
+        """(what keeps the blocks alive, [nd, the array of the blocks' addresses or None, ldd]) of the season calls' d: None, n values, an array
+        of the state's shape, or a list or tuple of one or nslots such arrays of one shape -- n values each (ldd = 0: they serve every column)
+        or of B's 2-D shape (column c is tracer c's).  Blocks whose leading dimensions differ are copied compactly; nothing is stacked."""
+        if d is None:
+            return None, [0, None, 0]
+        blocks = list(d) if isinstance(d, (list, tuple)) else [d]
+        nslots = self.slots[0]
+        if len(blocks) not in (1, nslots):
+            raise capi.OtmbError(11, f"DimensionMismatch: {len(blocks)} d blocks, expected 1 or one per slot ({nslots})")
+        blocks = [self._array(a, "d") for a in blocks]
+        if len({tuple(a.shape) for a in blocks}) > 1:
+            raise capi.OtmbError(11, f"DimensionMismatch: d blocks of different shapes: {sorted({tuple(a.shape) for a in blocks})}")
+        n = self.shape[1]
+        if blocks[0].ndim != 2:
+            for a in blocks:
+                self._check_d(a, (n,), what)
+            kept = [self._matrix(a, n)[0] for a in blocks]
+            return kept, [len(kept), (C.c_void_p * len(kept))(*[self._ptr(a) for a in kept]), 0]
+        if B.ndim != 2:
+            raise capi.OtmbError(11, f"DimensionMismatch: d of {tuple(blocks[0].shape)} is per column, {what} of {tuple(B.shape)} has no columns")
+        for a in blocks:
+            self._check_d(a, tuple(B.shape), what)
+        pairs = [self._matrix(a, n) for a in blocks]
+        if len({ld for _, ld in pairs}) > 1:
+            pairs = [(a, ld) if ld == max(n, 1) else (self._start(a, B, what), max(n, 1)) for a, ld in pairs]
+        kept = [a for a, _ in pairs]
+        return kept, [len(kept), (C.c_void_p * len(kept))(*[self._ptr(a) for a in kept]), pairs[0][1]]
+
+    def _season_sources(self, source, B, of):
+        """(the source blocks column-major, lds) of the season calls: None, an array of B's shape, or a list or tuple of one or nslots."""
+        if source is None:
+            return [], max(self.shape[0], 1)
+        if not isinstance(source, (list, tuple)):
+            Sc, lds = self._matrix(self._like(source, "source", B, of), self.shape[0])
+            return [Sc], lds
+        if not source:
+            raise capi.OtmbError(11, "DimensionMismatch: 0 source blocks, expected 1 or one per slot")
+        return self._sources(source, B, of)
+
+    def step_season(self, X, *, dt, slot_a, slot_b, weight, theta=1.0, d=None, source=None, source_scale=None, rtol=1e-10, maxiter=10000,
+                    adjoint=False, precond="jacobi", observe=None, time_weights=None):
+        """step_interp with d and the source per slot as well (otmb_op_step_season; include/otmb.h states the contract): every per-step field
+        follows the calendar the way the matrix does.  d: None, n values, an array of X's shape, or a list or tuple of one or nslots such
+        arrays of one shape; source: None, an array of X's shape, or a list or tuple of one or nslots.  A field given once serves every
+        step as it is.  A field given per slot is the slot's block on a plain step and (1 - weight[t])·(block slot_a[t]) +
+        weight[t]·(block slot_b[t]) on a blended one, folded as the matrix is; source_scale then multiplies the blended source.  With
+        plain_schedule (api.py) the explicit schedule is step_sched's.  Step t has the bits of combine_slots into a spare slot followed by
+        step(nsteps=1) with that step's d and source.  Everything else, and what is returned, is step_interp's."""
+        self._live()
+        pc = capi.precond_code(precond)
+        X, k, Xc, _ = self._state(X, "X")
+        dkeep, dargs = self._ds(d, X, "X")
+        sa, sb, w, nsteps = self._interp(slot_a, slot_b, weight)
+        (m, n), ld = self.shape, max(self.shape[0], 1)
+        blocks, lds = self._season_sources(source, X, "X")
+        scale = None
+        if source_scale is not None:
+            if not blocks:
+                raise capi.OtmbError(11, "invalid argument: source_scale needs a source")
+            scale = np.ascontiguousarray(source_scale, dtype=np.float64)
+            want = (nsteps,) + tuple(X.shape[1:])
+            if scale.shape != want:
+                raise capi.OtmbError(11, f"DimensionMismatch: source_scale of {scale.shape}, expected {want}")
+        q, Wc, ldw, obs, tw, mean = 0, None, max(n, 1), None, None, None
+        if observe is not None:
+            W, q = observers(self._array(observe, "observe"), n)
+            Wc, ldw = self._matrix(W, n)
+            obs = self._zeros((nsteps, k, q), "C")
+        if time_weights is not None:
+            tw = _as_weights(time_weights, nsteps)
+            mean = self._zeros(tuple(X.shape))
+        Xn = self._zeros(tuple(X.shape))
+        self._assign(Xn, Xc)
+        iters, relres, reason = step_arrays(nsteps, k)
+        done = C.c_int64(0)
+        rc = self._call("otmb_op_step_season", int(bool(adjoint)), k, *dargs, float(dt), float(theta), nsteps, sa.ctypes.data, sb.ctypes.data, w.ctypes.data,
+                        *self._source_args(blocks, lds), None if scale is None else scale.ctypes.data, self._ptr(Xn), ld, float(rtol), int(maxiter), pc,
+                        C.byref(done), iters.ctypes.data, relres.ctypes.data, reason.ctypes.data, q, self._ptr(Wc), ldw, self._ptr(obs),
+                        None if tw is None else tw.ctypes.data, self._ptr(mean), ld)
+        return Xn, StepInfo(self._status(rc), done.value, nsteps, iters, relres, reason, obs, mean)
+
+    def periodic_season(self, source, *, dt, slot_a, slot_b, weight, theta=1.0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False,
+                        precond="jacobi", ptol=1e-8, restart=30, maxcycles=1000, outer="none"):
+        """periodic over a cycle of step_season's steps (otmb_op_periodic_season; include/otmb.h): the cyclo-stationary state under a seasonal
+        d and a seasonal source.  source: an array, or a list or tuple of one or nslots arrays of one shape; d: as in step_season.  A column is
+        answered with zero only when it is zero in every source block.  With outer="mean" the mean operator is diag(d̄) + Ā, d̄ the fold of
+        the d blocks under the mean's own weights; it changes only how fast the iteration converges.  No source_scale: a history is not
+        periodic.  Everything else, and what is returned, is periodic_interp's."""
+        oc = capi.outer_code(outer)
+        self._live()
+        pc = capi.precond_code(precond)
+        if isinstance(source, (list, tuple)):
+            if not source:
+                raise capi.OtmbError(11, "DimensionMismatch: 0 source blocks, expected 1 or one per slot")
+            S, k, Sc, lds = self._state(source[0], "source")
+            blocks, lds = self._sources(source, S, "source")
+        else:
+            S, k, Sc, lds = self._state(source, "source")
+            blocks = [Sc]
+        sa, sb, w, ncycle = self._interp(slot_a, slot_b, weight)
+        dkeep, dargs = self._ds(d, S, "source")
+        X = self._start(x0, S, "source")
+        cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
+        msolve = np.zeros(k, dtype=np.int64)
+        rc = self._call("otmb_op_periodic_season", int(bool(adjoint)), k, *dargs, float(dt), float(theta), ncycle, sa.ctypes.data, sb.ctypes.data,
+                        w.ctypes.data, *self._source_args(blocks, lds), self._ptr(X), max(self.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), pc,
+                        float(ptol), int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data, reason.ctypes.data, oc, msolve.ctypes.data)
+        return X, PeriodicInfo(self._status(rc), cycles, defect, reason, msolve)
+
     def periodic(self, source, *, dt, ncycle, theta=1.0, first_slot=0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi",
                  ptol=1e-8, restart=30, maxcycles=1000, outer="none"):
         """The periodic state of the stepped cycle: X with F(X) = X, F = step(..., nsteps=ncycle, first_slot=first_slot, source=source), by

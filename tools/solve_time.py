@@ -35,6 +35,12 @@ the floor of an iteration, whose five vector passes and scalar kernels the fusio
     it -- which is what runs against an earlier commit's library as well (--lib PATH: only `chain` runs then).  Medians of 7 after one
     warm-up of each (interp_times); the record also times one blend by otmb_op_combine_slots_dev (HIP events) and a preconditioner's setup
     plus one sweep and one wait (otmb_op_precond_dev), the upper bound of what every blended step pays.
+--season: the same 48 blended steps with d and the source per slot -- the age d and a unit source, each scaled by a monthly factor (an ice
+    cover).  Route `season`: ONE otmb_op_step_season_dev call.  Route `chain`: otmb_op_combine_slots_dev into a thirteenth slot, d_t and s_t
+    blended by tensor operations, then a one-step otmb_op_step_dev -- public calls of the commits before it, so it runs against an earlier
+    library as well (--lib PATH: only `chain` runs then).  Medians of 7 after one warm-up of each, the routes alternating, the states
+    compared bit for bit (season_times).  The fold kernel's own time is read from a kernel trace of this run; at k = 1 it moves
+    3·8·n bytes a launch, which is a launch-bound size.
 --periodic [--outer none|mean --ptol --restart --maxcycles --rtol]: the periodic state of that year -- the twelve slots of --step, θ = 1, lines, the age system
     (d = 1 s⁻¹ at the surface, s = 1), k = 1 -- by otmb_op_periodic_dev: cycles, wall time, defect; then, in the same process, the same
     number of plain cycles by otmb_op_step_dev in a loop from zero: their wall time and the defect they leave.  --outer mean: the outer GMRES
@@ -229,6 +235,74 @@ def substeps_times(asm, a):
             f.write(json.dumps(rec) + "\n")
 
 
+def season_times(asm, a):
+    """--season: see the module's text.  The two routes' states are compared bit for bit when both run."""
+    nslots, m, reps = 12, 4, 7
+    nsteps, dt = nslots * m, 30 * DAY / m
+    N = asm.N
+    cp, rv, nz = asm.out["T"]
+    nnz = int(cp[N].item()) - 1
+    op = Operator(asm.ctx, N, N, cp, rv, (nz[:nnz] * 1.0).contiguous())
+    op.set_lines(asm.vertical_lines())
+    op.set_slots(nslots + 1)  # the thirteenth: the chain's scratch
+    for s in range(nslots):
+        op.set_values_dev((nz[:nnz] * (1.0 + 0.02 * s)).contiguous(), slot=s)
+    nsurf = int(torch.count_nonzero(asm.wet3d.reshape(-1)[: asm.nx * asm.ny]).item())
+    d = torch.zeros(N, dtype=torch.float64, device="cuda")
+    d[:nsurf] = 1.0
+    ice = [0.55 + 0.45 * float(np.cos(2.0 * np.pi * s / nslots)) for s in range(nslots)]  # the monthly factor 1 - ice, in 0.1 .. 1
+    spare = torch.full((N,), float("nan"), dtype=torch.float64, device="cuda")  # the scratch slot's block: no step names it
+    ds = [(d * f).contiguous() for f in ice] + [spare]
+    ss = [torch.full((N,), f, dtype=torch.float64, device="cuda") for f in ice] + [spare]
+    x0 = torch.zeros(N, dtype=torch.float64, device="cuda")
+    kw = dict(dt=dt, theta=1.0, rtol=a.rtol, maxiter=a.maxiter, precond="lines")
+    sa, sb, w = api.interp_schedule(nslots, m)
+    assert len(w) == nsteps and ((w > 0) & (w < 1)).all()
+
+    def season():
+        X, info = op.step_season(x0, slot_a=sa, slot_b=sb, weight=w, d=ds, source=ss, **kw)
+        assert info.steps_done == nsteps, info
+        return X, int(info.iterations.sum())
+
+    def chain():
+        X, its = x0, 0
+        for t in range(nsteps):
+            wa, wb = 1.0 - float(w[t]), float(w[t])
+            wt = np.zeros(nslots + 1)
+            wt[sa[t]], wt[sb[t]] = wa, wb
+            op.combine_slots(wt, nslots)
+            dt_ = wa * ds[sa[t]] + wb * ds[sb[t]]  # (two products and a sum, each rounded: tensor operations do not contract)
+            st = wa * ss[sa[t]] + wb * ss[sb[t]]
+            X, info = op.step(X, nsteps=1, first_slot=nslots, d=dt_, source=st, **kw)
+            assert info.steps_done == 1, (t, info)
+            its += int(info.iterations.sum())
+        return X, its
+
+    routes = [("chain", chain)] + ([("season", season)] if hasattr(op.lib, "otmb_op_step_season_dev") else [])
+    times, out = {name: [] for name, _ in routes}, {}
+    for r in range(reps + 1):
+        for name, route in routes:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out[name] = route()
+            torch.cuda.synchronize()
+            times[name].append(time.perf_counter() - t0)
+    rec = {"what": "12 months x 4 sub-steps, TMM interpolation, T, age d and unit source scaled by a monthly factor", "n": N, "nnz": nnz, "nslots": nslots,
+           "substeps": m, "nsteps": nsteps, "precond": "lines", "theta": 1.0, "dt_s": dt, "reps": reps, "lib": a.lib or "this build",
+           "fold_bytes": 3 * 8 * N, "fold_launches": 2 * nsteps, "iterations": out["chain"][1], "checksum": float(out["chain"][0].sum().item())}
+    if "season" in out:
+        rec.update(season_iterations=out["season"][1], same_bits=bool(torch.equal(out["season"][0], out["chain"][0])))
+    for name in times:
+        t = times[name][1:]
+        rec.update({name + "_median_s": float(np.median(t)), name + "_min_s": float(np.min(t)), name + "_max_s": float(np.max(t))})
+    print(json.dumps(rec), flush=True)
+    op.close()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(rec) + "\n")
+
+
 def interp_times(asm, a):
     """--step --interp: see the module's text.  The two routes' states are compared bit for bit when both run."""
     nslots, m, reps = 12, 4, 7
@@ -396,6 +470,7 @@ def main():
     ap.add_argument("--step-route", default="both", choices=["step", "compose", "both"])
     ap.add_argument("--substeps", type=int, default=0)
     ap.add_argument("--interp", action="store_true")
+    ap.add_argument("--season", action="store_true")
     ap.add_argument("--periodic", action="store_true")
     ap.add_argument("--outer", default="none", choices=["none", "mean"])
     ap.add_argument("--ptol", type=float, default=1e-8)
@@ -420,6 +495,8 @@ def main():
     vmo = torch.from_numpy(np.asfortranarray(g.vmo.data).ravel(order="F")).cuda()
     asm.step(umo, vmo, 1e20)
     N = asm.N
+    if a.season:
+        return season_times(asm, a)
     if a.step and a.interp:
         return interp_times(asm, a)
     if a.step and a.substeps > 0:
