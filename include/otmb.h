@@ -793,6 +793,47 @@ int32_t otmb_op_slots(const otmb_op *op, int64_t *nslots, int64_t *selected);
 int32_t otmb_op_combine_slots_dev(otmb_op *op, const double *w, int64_t dst);
 int32_t otmb_op_combine_slots(otmb_op *op, const double *w, int64_t dst);
 
+/* ---- The operator's domain: A[rows, cols] as a new resident operator, without leaving the device -- prescribed (Dirichlet) boundary values
+ *      (A_II·x_I = s_I - A_IB·x_B needs the blocks A[I, I] and A[I, B]), regional problems -- and what an operator can say of itself.
+ * otmb_op_submatrix_dev (device pointers) / otmb_op_submatrix (host pointers): rows[nr], cols[nc] (Int64, 1-based like rowval), each STRICTLY
+ *      ASCENDING inside 1..m / 1..n.  Checked on the device before anything is allocated for the child: a violation is OTMB_ERR_INVALID_ARG, the
+ *      message names the first offending 1-based position of the list and says whether it is a row or a column.  The parent is never modified;
+ *      *out is written only on success.  The child is a new, independent operator on the parent's context (destroy it like any other; the parent
+ *      may be destroyed first).
+ * In bits: the child is the operator otmb_op_create makes from SparseArrays' A[rows, cols] -- column j' holds the stored entries of column
+ *      cols[j'] whose row is selected, IN STORED ORDER (unsorted and duplicate rows survive as they are), rows renumbered by their rank in
+ *      `rows`, values copied bit for bit (NaN payloads, -0.0) -- planned by otmb_op_create_dev's own plan, so every product, solve, step and
+ *      observation on it has the bits of that operator.  It has the parent's number of slots, slot s holding the parent's slot s restricted,
+ *      and the parent's selection.  Lines: when the selection is PRINCIPAL (nr == nc and rows[i] == cols[i] for all i, decided on the device)
+ *      and the parent has lines, the child has next'[rank(i)] = rank(next[i]) where i and next[i] are both selected and 0 elsewhere (a dropped
+ *      cell cuts its line in two; the renumbering is monotone, so otmb_op_set_lines' rules are inherited), set through otmb_op_set_lines_dev;
+ *      otherwise it has none.  An empty selection (nr == 0 or nc == 0) is what otmb_op_create_dev makes of the empty nr x nc matrix.
+ * otmb_op_take_values: slot child_slot of a child becomes slot parent_slot of its parent, restricted -- the monthly refresh when the parent's
+ *      values were rebuilt.  Device work only, ONE streaming launch enqueued on the context's stream (the child keeps its gather table; it keeps
+ *      no pointer to the parent).  In bits it is otmb_op_set_values_slot_dev(child, child_slot, the gathered nzval): both value arrays of the
+ *      slot are written, nothing else; the selection and the lines are untouched.  The child knows its parent by a process-wide serial number
+ *      every operator gets at creation, not by its address: an operator that is not the parent (one created at a destroyed parent's address
+ *      included), one on another context, a `child` that no otmb_op_submatrix made, and a slot outside either operator's 0..nslots-1 (there is no
+ *      "selected slot" here) are each OTMB_ERR_INVALID_ARG with nothing written.  The parent's pattern cannot change, so a child stays valid
+ *      for as long as the parent lives, whatever is done to the parent's values, slots and lines.
+ * otmb_op_fetch_dev (device pointers, enqueued) / otmb_op_fetch (host pointers, waits): the operator's matrix as otmb_op_create took it: colptr
+ *      (n + 1), rowval (nnz, 1-based: widened back from the operator's Int32 copy) and nzval (nnz) of slot `slot`, -1: the selected slot.  Any of
+ *      the three may be NULL.  fetch after create returns the arrays given, bit for bit; sizes: otmb_op_info.
+ * otmb_op_get_lines_dev (next: device pointer) / otmb_op_get_lines (host pointer): *has_lines (a HOST int32 in both variants; may be NULL) = 1
+ *      and next[n] in otmb_op_set_lines' convention when the operator has lines; *has_lines = 0 and next not written when it has none.  next may
+ *      be NULL (the question alone).
+ * Every argument error leaves every operator involved usable.  Not built: permutations and repeated indices (the lists must ascend strictly;
+ *      a caller who needs an order permutes the vectors), a submatrix of a submatrix refreshed from the grandparent (take_values takes the
+ *      direct parent only), and a child that follows a parent's later otmb_op_set_slots (a slot it lacks is refused; otmb_op_set_slots on the
+ *      child, then take_values, fills it).                                                                                              */
+int32_t otmb_op_submatrix_dev(otmb_op *parent, int64_t nr, const int64_t *rows, int64_t nc, const int64_t *cols, otmb_op **out);
+int32_t otmb_op_submatrix(otmb_op *parent, int64_t nr, const int64_t *rows, int64_t nc, const int64_t *cols, otmb_op **out);
+int32_t otmb_op_take_values(otmb_op *child, const otmb_op *parent, int64_t parent_slot, int64_t child_slot);
+int32_t otmb_op_fetch_dev(const otmb_op *op, int64_t slot, int64_t *colptr, int64_t *rowval, double *nzval);
+int32_t otmb_op_fetch(const otmb_op *op, int64_t slot, int64_t *colptr, int64_t *rowval, double *nzval);
+int32_t otmb_op_get_lines_dev(const otmb_op *op, int64_t *next, int32_t *has_lines);
+int32_t otmb_op_get_lines(const otmb_op *op, int64_t *next, int32_t *has_lines);
+
 /* ---- θ-steps of ∂x/∂t + (diag(d) + A)·x = s over the slots: X (n x k, in and out) advances through nsteps steps of length dt, step t
  *      (0-based) with the matrix A of slot (first_slot + t) mod nslots (adjoint: Aᵀ).  S: the source, n x k with leading dimension lds, or NULL
  *      (zero); d: n values or NULL.  dt > 0 and finite, 0 < theta <= 1 (1: implicit Euler, 0.5: Crank-Nicolson), nsteps >= 0,

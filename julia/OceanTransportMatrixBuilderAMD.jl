@@ -45,6 +45,7 @@ export observe, stepobserve!
 export stepsched!, periodicsched!
 export stepinterp!, periodicinterp!, interpschedule
 export stepseason!, periodicseason!, plainschedule
+export submatrix, takevalues!, lines, sparse   # (`sparse` is SparseArrays' own, extended here and passed on; `D[I, J]` extends Base.getindex)
 
 const LIBPATH = get(ENV, "OTMB_HIP_LIB", joinpath(@__DIR__, "..", "oceantransportmatrixbuilder.jl_amd", "lib", "libotmb_hip.so"))
 const lib = Ref{Ptr{Cvoid}}(C_NULL)
@@ -508,6 +509,78 @@ function slots(D::DeviceOperator)
         check(ccall(slots_fn, Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), D.handle, n, sel))
     end
     return (n[], sel[] + 1)
+end
+
+# The operator's domain (include/otmb.h states the contract).  `submatrix(D, I, J = I)`, also written `D[I, J]`: A[I, J] as a new DeviceOperator on
+# the device -- I and J strictly ascending index vectors (or Bool masks), the result bit for bit the operator of SparseArrays' A[I, J] (stored
+# order kept), with D's slots, each restricted, D's selection and, when J is I, D's lines restricted.  Permutations and repeated indices are not
+# built: the library refuses them and names the first offending position.  `takevalues!(child, parent; slot, parentslot)`: slot `slot` of a
+# submatrix (default: its selected slot) becomes slot `parentslot` (default: the same number) of the operator it was taken from, restricted --
+# one launch on the device, the refresh after `setvalues!(parent, ...)`.  `sparse(D; slot)`: the operator's matrix back as a SparseMatrixCSC
+# (slot: default the selected one).  `lines(D)`: `next` as `setlines!` took it, or `nothing`.
+function submatrix(D::DeviceOperator, I::AbstractVector{<:Integer}, J::AbstractVector{<:Integer} = I)
+    rows = I isa AbstractVector{Bool} ? Vector{Int64}(findall(I)) : Vector{Int64}(I)
+    cols = J === I ? rows : J isa AbstractVector{Bool} ? Vector{Int64}(findall(J)) : Vector{Int64}(J)
+    (I isa AbstractVector{Bool} && length(I) != D.m) && throw(DimensionMismatch("row mask of $(length(I)), the operator has $(D.m) rows"))
+    (J isa AbstractVector{Bool} && length(J) != D.n) && throw(DimensionMismatch("column mask of $(length(J)), the operator has $(D.n) columns"))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    z = Ref{Int64}(0)
+    lock(CALL_LOCK) do
+        D.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        submatrix_fn = sym(:otmb_op_submatrix)
+        info_fn = sym(:otmb_op_info)
+        check(ccall(submatrix_fn, Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Ptr{Cvoid}}),
+            D.handle, length(rows), rows, length(cols), cols, h))
+        check(ccall(info_fn, Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), h[], C_NULL, C_NULL, z))
+    end
+    S = DeviceOperator(h[], length(rows), length(cols), z[])
+    finalizer(S) do d
+        release!(d)
+    end
+    return S
+end
+Base.getindex(D::DeviceOperator, I::AbstractVector{<:Integer}, J::AbstractVector{<:Integer}) = submatrix(D, I, J)
+
+function takevalues!(child::DeviceOperator, parent::DeviceOperator; slot::Union{Nothing,Integer} = nothing, parentslot::Union{Nothing,Integer} = nothing)
+    lock(CALL_LOCK) do
+        (child.handle == C_NULL || parent.handle == C_NULL) && throw(ArgumentError("the DeviceOperator has been released"))
+        s = slot
+        if s === nothing
+            sel = Ref{Int64}(0)
+            slots_fn = sym(:otmb_op_slots)
+            check(ccall(slots_fn, Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), child.handle, C_NULL, sel))
+            s = sel[] + 1
+        end
+        ps = parentslot === nothing ? s : parentslot
+        take_values_fn = sym(:otmb_op_take_values)
+        check(ccall(take_values_fn, Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64), child.handle, parent.handle, Int64(ps - 1), Int64(s - 1)))
+    end
+    return child
+end
+
+function SparseArrays.sparse(D::DeviceOperator; slot::Union{Nothing,Integer} = nothing)
+    (slot === nothing || slot >= 1) || throw(ArgumentError("slot must be >= 1"))
+    colptr = Vector{Int64}(undef, D.n + 1)
+    rowval = Vector{Int64}(undef, D.nnz)
+    nzval = Vector{Float64}(undef, D.nnz)
+    lock(CALL_LOCK) do
+        D.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        fetch_fn = sym(:otmb_op_fetch)
+        check(ccall(fetch_fn, Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}),
+            D.handle, Int64(slot === nothing ? -1 : slot - 1), colptr, rowval, nzval))
+    end
+    return SparseMatrixCSC{Float64,Int64}(D.m, D.n, colptr, rowval, nzval)
+end
+
+function lines(D::DeviceOperator)
+    next = Vector{Int64}(undef, D.n)
+    has = Ref{Int32}(0)
+    lock(CALL_LOCK) do
+        D.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        get_lines_fn = sym(:otmb_op_get_lines)
+        check(ccall(get_lines_fn, Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}), D.handle, next, has))
+    end
+    return has[] == 0 ? nothing : next
 end
 
 # θ-steps of ∂x/∂t + (Diagonal(d) + A)·x = source through the slots (otmb_op_step; include/otmb.h states the contract): X is advanced in

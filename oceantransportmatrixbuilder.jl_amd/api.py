@@ -860,7 +860,8 @@ class DeviceOperator(OperatorCalls):
     The same C calls as the Julia shim's DeviceOperator: otmb_op_create; mul! -> otmb_op_mul; setvalues! -> otmb_op_set_values; solve! ->
     otmb_op_solve_pc; setlines! -> otmb_op_set_lines; precondition! -> otmb_op_precond; setslots! / selectslot! / step! -> otmb_op_set_slots /
     otmb_op_select_slot / otmb_op_step; observe / stepobserve! -> otmb_op_observe / otmb_op_step_obs; periodic! -> otmb_op_periodic (outer = :mean: otmb_op_periodic_pc); combineslots! ->
-    otmb_op_combine_slots; the finalizer -> otmb_op_destroy.  precondition, solve, observe, step and periodic are OperatorCalls' (a matrix d:
+    otmb_op_combine_slots; submatrix / getindex -> otmb_op_submatrix; takevalues! -> otmb_op_take_values; sparse -> otmb_op_fetch; lines ->
+    otmb_op_get_lines; the finalizer -> otmb_op_destroy.  submatrix, take_values, to_csc, lines, precondition, solve, observe, step and periodic are OperatorCalls' (a matrix d:
     the otmb_op_*_dk exports), over the numpy hooks below: a 1-D input gives a 1-D result, 2-D results are Fortran-ordered."""
 
     def __init__(self, A, *, device=0):
@@ -900,6 +901,29 @@ class DeviceOperator(OperatorCalls):
 
     def _assign(self, X, a):
         X[...] = a
+
+    # ... and of the domain calls (submatrix, take_values, to_csc, lines: OperatorCalls')
+    def _selection(self, s, limit, what):
+        s = np.asarray(s)
+        if s.dtype == bool:
+            if s.shape != (limit,):
+                raise capi.OtmbError(11, f"DimensionMismatch: {what} mask of {s.shape}, expected {(limit,)}")
+            return np.flatnonzero(s).astype(np.int64) + 1
+        if s.ndim != 1 or not (np.issubdtype(s.dtype, np.integer) or s.size == 0):
+            raise capi.OtmbError(11, f"invalid argument: {what} must be a boolean mask or a 1-D array of integers, got {s.dtype} of {s.shape}")
+        return s.astype(np.int64) + 1
+
+    def _empty(self, n, dtype):
+        return np.empty(n, dtype=dtype)
+
+    def _csc(self, cp, rv, nz):
+        return SparseMatrixCSC(self.shape[0], self.shape[1], cp, rv, nz)
+
+    def _adopt(self, h):
+        D = DeviceOperator.__new__(DeviceOperator)
+        D._h, D.ctx = h, self.ctx
+        D.shape, D.nnz = self._info(h)
+        return D
 
     def mul(self, X, *, alpha=1.0, beta=0.0, Y=None, adjoint=False):
         """α·A·X + β·Y (adjoint: α·Aᵀ·X + β·Y).  X: 1-D (one tracer) or 2-D (rows x k); Y: None (a new array; β must be 0) or an array of
@@ -1000,6 +1024,34 @@ class DeviceOperator(OperatorCalls):
             self.close()
         except Exception:
             pass
+
+
+def dirichlet_blocks(op, boundary):
+    """(A_II, A_IB, interior, boundary) of a square resident operator -- an api.DeviceOperator or a device.Operator -- for PRESCRIBED values
+    on the unknowns `boundary` (a boolean mask of n entries or an ascending 0-based index array): two submatrix calls and nothing more.
+    interior and boundary come back as ascending 0-based index arrays of the operator's kind (numpy, or tensors on its GPU).  A_II is
+    principal, so it has the operator's lines, restricted; both blocks have its slots.  The exact statement of A·x = s with x_B given is
+    A_II·x_I = s_I - A_IB·x_B, in place of a fast restoring rate in d:
+      steady      x_I, info = A_II.solve(s[interior] - A_IB.mul(x_B))
+      periodic    with a value x_B(s) per slot s, the source blocks are S_s = s_I(s) - A_IB(slot s)·x_B(s): A_IB.select(s) then
+                  A_IB.mul(x_B[s]) for each slot, then A_II.periodic_sched([S_0, ...], dt=..., ncycle=...) (or periodic_season with an
+                  interpolated schedule).
+    After the parent's values were rebuilt, A_II.take_values(op, slot) and A_IB.take_values(op, slot) refresh both blocks on the device."""
+    m, n = op.shape
+    if m != n:
+        raise capi.OtmbError(11, f"invalid argument: dirichlet_blocks needs a square operator, got {op.shape}")
+    b = op._selection(boundary, n, "boundary") - 1
+    if isinstance(b, np.ndarray):
+        inside = np.ones(n, dtype=bool)
+        inside[b] = False
+        i = np.flatnonzero(inside)
+    else:  # tensors on the operator's GPU
+        import torch
+
+        inside = torch.ones(n, dtype=torch.bool, device=b.device)
+        inside[b] = False
+        i = torch.nonzero(inside).flatten()
+    return op.submatrix(i), op.submatrix(i, b), i, b
 
 
 def as2D(x, wet3D):

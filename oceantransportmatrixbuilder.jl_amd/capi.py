@@ -296,6 +296,13 @@ SYMBOLS = {
                                              C.c_int64, _vp, _vp, _vp, C.c_int32, _vp]),
     "otmb_op_combine_slots_dev": (C.c_int32, [_vp, _vp, C.c_int64]),
     "otmb_op_combine_slots": (C.c_int32, [_vp, _vp, C.c_int64]),
+    "otmb_op_submatrix_dev": (C.c_int32, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.POINTER(_vp)]),
+    "otmb_op_submatrix": (C.c_int32, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.POINTER(_vp)]),
+    "otmb_op_take_values": (C.c_int32, [_vp, _vp, C.c_int64, C.c_int64]),
+    "otmb_op_fetch_dev": (C.c_int32, [_vp, C.c_int64, _vp, _vp, _vp]),
+    "otmb_op_fetch": (C.c_int32, [_vp, C.c_int64, _vp, _vp, _vp]),
+    "otmb_op_get_lines_dev": (C.c_int32, [_vp, _vp, C.POINTER(C.c_int32)]),
+    "otmb_op_get_lines": (C.c_int32, [_vp, _vp, C.POINTER(C.c_int32)]),
     "otmb_op_info": (C.c_int32, [_vp, _ip, _ip, _ip]),
     "otmb_op_destroy": (None, [_vp]),
     "otmb_transportmatrix_plan_dev": (C.c_int32, [_vp, C.POINTER(TmArgs), C.POINTER(C.c_int64 * 5)]),

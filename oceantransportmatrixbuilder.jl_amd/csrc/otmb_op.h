@@ -3,6 +3,7 @@
 // The layouts are described at the head of otmb_spmv.hip, which builds them and owns every buffer (sp_free_all).
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 #include <vector>
 
@@ -15,8 +16,15 @@ struct OpSlot {  // one value set of the pattern (otmb_op_set_slots): nzval of t
     DevBuf nz, val;
 };
 
+// every operator of the process has another serial number: a child of otmb_op_submatrix knows its parent by it, not by an address
+inline uint64_t op_new_serial() {
+    static std::atomic<uint64_t> next{1};
+    return next.fetch_add(1);
+}
+
 struct otmb_op {
     otmb_ctx *ctx = nullptr;
+    uint64_t serial = op_new_serial();
     int device = 0;
     i64 m = 0, n = 0, nnz = 0;
     i64 nslices = 0, ell = 0, nlong = 0;  // slices, entries of the slice layout (padding included), long rows
@@ -38,7 +46,14 @@ struct otmb_op {
     DevBuf ln;                            // otmb_op_set_lines (Int32, 0-based, -1 = none): successor (n), predecessor (n), line heads ascending (nheads)
     i64 nheads = 0;
     bool lines = false;                   // lines are set (they belong to the pattern: otmb_op_set_values keeps them)
+    DevBuf src;                           // otmb_op_submatrix's child: per stored entry, its position in the parent's nzval (the gather table)
+    uint64_t parent_serial = 0;           // ... and the parent's serial (0: not such a child), its nnz: what otmb_op_take_values accepts
+    i64 parent_nnz = 0;
 };
+
+// otmb_spmv.hip, for otmb_submatrix.hip: the rest of a creation from arrays the library already owns -- op->cp (n + 1), op->nz and rowval
+// (Int64, 1-based; read by the plan only) on the device, m, n and nnz set: the plan's checks and layouts, then slot 0
+int32_t sp_plan_resident(otmb_op *op, const i64 *rowval);
 
 // Register blocks of columns: f(std::integral_constant<int, B>, first column) for blocks of KB columns while that many are left from c0,
 // then of KB / 2, ..., 1 (the matrix is read once per block).

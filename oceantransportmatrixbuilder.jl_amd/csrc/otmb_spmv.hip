@@ -200,7 +200,7 @@ static void sp_free_all(otmb_op *op) {
     if (!op->slots.empty()) op->nz = op->val = DevBuf();
     op->slots.clear();
     for (DevBuf *b : {&op->cp, &op->rv, &op->nz, &op->dst, &op->elen, &op->sbase, &op->loff, &op->lrows, &op->val, &op->col, &op->xs, &op->ys, &op->ds, &op->sw, &op->st,
-                      &op->pd, &op->mean.nz, &op->mean.val, &op->interp.nz, &op->interp.val, &op->season, &op->setab, &op->cb, &op->ln, &op->ob, &op->oh})
+                      &op->pd, &op->mean.nz, &op->mean.val, &op->interp.nz, &op->interp.val, &op->season, &op->setab, &op->cb, &op->ln, &op->ob, &op->oh, &op->src})
         sp_free(*b);
 }
 
@@ -311,6 +311,14 @@ static int32_t sp_plan(otmb_op *op, const i64 *rowval) {
     return OTMB_OK;
 }
 
+// (declared in otmb_op.h: otmb_op_submatrix's child starts here, from arrays it made on the device)
+int32_t sp_plan_resident(otmb_op *op, const i64 *rowval) {
+    int32_t rc;
+    if ((rc = sp_plan(op, rowval))) return rc;
+    op->slots.push_back(OpSlot{op->nz, op->val});  // slot 0, selected
+    return OTMB_OK;
+}
+
 // n + 1 column pointers are on the device at op->cp: read the first and the last, size nnz
 static int32_t sp_ends(otmb_op *op) {
     otmb_ctx *ctx = op->ctx;
@@ -366,8 +374,7 @@ static int32_t sp_create(otmb_ctx *ctx, int64_t m, int64_t n, const int64_t *col
         HIP_TRY(ctx, hipMemcpyAsync(op->nz.p, nzval, (size_t)nnz * 8, kind, ctx->stream));
         if (kind == hipMemcpyHostToDevice) ctx->uploaded_bytes += 16 * nnz + 8 * (n + 1);
     }
-    if ((rc = sp_plan(op, (const i64 *)rows.b.p))) return rc;
-    op->slots.push_back(OpSlot{op->nz, op->val});  // slot 0, selected
+    if ((rc = sp_plan_resident(op, (const i64 *)rows.b.p))) return rc;
     *out = op;
     G.op = nullptr;
     return OTMB_OK;

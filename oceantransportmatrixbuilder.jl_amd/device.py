@@ -103,6 +103,31 @@ class Operator(OperatorCalls):
             raise capi.OtmbError(11, "DimensionMismatch: d must be " + (f"{want[0]} float64 values" if len(want) == 1 else
                                                                        f"float64 of {what}'s shape {want}, not {tuple(d.shape)}"))
 
+    # ... and of the domain calls (submatrix, take_values, to_csc, lines: OperatorCalls'): masks become index tensors on the device
+    def _selection(self, s, limit, what):
+        if not torch.is_tensor(s):
+            s = torch.as_tensor(np.asarray(s), device=torch.device("cuda", self.device))
+        _on_device(s, self.device, what)
+        if s.dtype == torch.bool:
+            if tuple(s.shape) != (limit,):
+                raise capi.OtmbError(11, f"DimensionMismatch: {what} mask of {tuple(s.shape)}, expected {(limit,)}")
+            return torch.nonzero(s).flatten() + 1
+        if s.dim() != 1 or (s.is_floating_point() and s.numel() > 0) or s.is_complex():
+            raise capi.OtmbError(11, f"invalid argument: {what} must be a boolean mask or a 1-D tensor of integers, got {s.dtype} of {tuple(s.shape)}")
+        return s.to(torch.int64).contiguous() + 1
+
+    def _empty(self, n, dtype):
+        return torch.empty(n, dtype=getattr(torch, dtype), device=torch.device("cuda", self.device))
+
+    def _csc(self, cp, rv, nz):
+        return cp, rv, nz
+
+    def _adopt(self, h):
+        D = Operator.__new__(Operator)
+        D.ctx, D.lib, D._h, D.device = self.ctx, self.lib, h, self.device
+        D.shape, D.nnz = self._info(h)
+        return D
+
     def set_values_dev(self, nzval, slot=None):
         """New values from a device tensor for the selected slot, or for slot `slot` (set_slots)."""
         _on_device(nzval, self.device, "nzval")
@@ -733,6 +758,16 @@ class DeviceAssembler:
         self._ops[matrix] = OpRecord(op, snapshot=_Snapshot((cp, rv)), nzv=_Snapshot((nz,)))
         self.op_replans += 1
         return op
+
+    def submatrix(self, rows, cols=None, matrix="T"):
+        """Operator.submatrix of the resident operator over `matrix`: the kept slots' operator as it stands where slots are kept, operator()
+        otherwise.  rows, cols: boolean masks or ascending 0-based index tensors on this GPU; cols=None: the principal submatrix, which has
+        the grid's water columns restricted as its lines.  The CALLER owns the result (close it, or let it go): the assembler keeps no record
+        of it, never refreshes or replaces it, and its own operator and slots are as they were; child.take_values(asm.operator(matrix))
+        refreshes it after the next step while the assembler's operator is the same one."""
+        rec = self._ops.get(matrix)
+        op = rec.op if self._has_slots(rec) else self.operator(matrix)
+        return op.submatrix(rows, cols)
 
     def vertical_lines(self):
         """The water columns of this grid as the `next` tensor of Operator.set_lines (api.vertical_lines on the resident indices, with torch

@@ -104,7 +104,12 @@ class OperatorCalls:
       _ptr(a)               the address the library is given (None stays None)
       _zeros(shape, order)  a zeroed float64 result: "F" column-major (rows x k with leading dimension max(rows, 1)), "C" row-major
       _assign(X, a)         copies a into the result X
-    Every refusal is raised before the library is called."""
+    and, for the calls on the operator's domain (submatrix, take_values, to_csc, lines):
+      _selection(s, limit, what)  a boolean mask of `limit` entries or an ascending 0-based index array as 1-based int64 indices of the class's kind
+      _empty(n, dtype)      an uninitialised 1-D array of "int64" or "float64" for the library to fill
+      _csc(cp, rv, nz)      what to_csc returns of the three filled arrays
+      _adopt(h)             a new operator of the class over the handle h, on this operator's context
+    Every refusal is raised before the library is called, but for the order of a selection's indices, which the library checks on the device."""
 
     _suffix = ""
 
@@ -183,6 +188,55 @@ class OperatorCalls:
         if not blocks:
             return [0, None, lds]
         return [len(blocks), (C.c_void_p * len(blocks))(*[self._ptr(a) for a in blocks]), lds]
+
+    def submatrix(self, rows, cols=None):
+        """A[rows, cols] as a new resident operator of this class (otmb_op_submatrix; include/otmb.h states the contract): each argument a
+        boolean mask (m entries for rows, n for cols) or an ascending 0-based index array; cols=None means rows again: the principal
+        submatrix, which inherits the lines, restricted.  The child is the operator that would be made from SparseArrays' A[rows, cols]:
+        stored order kept, values bit for bit, the parent's slots (each restricted) and selection.  Indices that do not ascend strictly or
+        leave the matrix raise OtmbError, the message naming the first offending position; permutations and repeats are not built.  The caller
+        owns the child; this operator is not modified."""
+        self._live()
+        m, n = self.shape
+        r = self._selection(rows, m, "rows")
+        c = r if cols is None else self._selection(cols, n, "cols")
+        h = C.c_void_p()
+        self.ctx.check(self._call("otmb_op_submatrix", int(r.shape[0]), self._ptr(r), int(c.shape[0]), self._ptr(c), C.byref(h)))
+        return self._adopt(h)
+
+    def take_values(self, parent, slot=None, parent_slot=None):
+        """Slot `slot` of this operator -- a submatrix of `parent` -- becomes slot `parent_slot` of parent, restricted (otmb_op_take_values:
+        one streaming launch on the device, nothing travels): the refresh after parent's values were rebuilt.  slot=None: the selected slot;
+        parent_slot=None: the slot of the same number.  An operator that is not the parent this one was taken from raises OtmbError."""
+        self._live()
+        parent._live()
+        slot = self.slots[1] if slot is None else int(slot)
+        parent_slot = slot if parent_slot is None else int(parent_slot)
+        self.ctx.check(self._library().otmb_op_take_values(self._h, parent._h, parent_slot, slot))
+
+    def to_csc(self, slot=None):
+        """The operator's matrix as it was created (otmb_op_fetch): colptr, 1-based rowval and the nzval of slot `slot` (None: the selected
+        one) -- an api.SparseMatrixCSC from api.DeviceOperator, three device tensors (colptr, rowval, nzval) from device.Operator."""
+        self._live()
+        if slot is not None and int(slot) < 0:
+            raise capi.OtmbError(11, f"invalid argument: slot {slot}")
+        cp, rv, nz = self._empty(self.shape[1] + 1, "int64"), self._empty(self.nnz, "int64"), self._empty(self.nnz, "float64")
+        self.ctx.check(self._call("otmb_op_fetch", -1 if slot is None else int(slot), self._ptr(cp), self._ptr(rv), self._ptr(nz)))
+        return self._csc(cp, rv, nz)
+
+    @property
+    def lines(self):
+        """`next` as set_lines took it (otmb_op_get_lines: n int64 values, 1-based successors, 0 = none), or None when the operator has no lines."""
+        self._live()
+        nx, has = self._empty(self.shape[1], "int64"), C.c_int32(0)
+        self.ctx.check(self._call("otmb_op_get_lines", self._ptr(nx), C.byref(has)))
+        return nx if has.value else None
+
+    def _info(self, h):
+        """((m, n), nnz) of the operator behind the handle h."""
+        m, n, z = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self.ctx.check(self._library().otmb_op_info(h, C.byref(m), C.byref(n), C.byref(z)))
+        return (int(m.value), int(n.value)), int(z.value)
 
     def precondition(self, Y, d=None, sigma=0.0, adjoint=False, precond="lines"):
         """Z = P⁻¹·Y with the preconditioner solve(..., precond=precond) uses for M = σ·I + diag(d) + A (adjoint: Aᵀ) (otmb_op_precond): for a
