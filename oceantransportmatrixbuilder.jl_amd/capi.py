@@ -220,22 +220,14 @@ SYMBOLS = {
     "otmb_op_set_values_slot": (C.c_int32, [_vp, C.c_int64, _vp, C.c_int64]),
     "otmb_op_select_slot": (C.c_int32, [_vp, C.c_int64]),
     "otmb_op_slots": (C.c_int32, [_vp, _ip, _ip]),
-    "otmb_op_step_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
-                                      C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp]),
     "otmb_op_step": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
                                   C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp]),
     "otmb_op_observe_dev": (C.c_int32, [_vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "otmb_op_observe": (C.c_int32, [_vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp]),
-    "otmb_op_step_obs_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
-                                          C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64]),
     "otmb_op_step_obs": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
                                       C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64]),
-    "otmb_op_periodic_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
-                                          C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp]),
     "otmb_op_periodic": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
                                       C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp]),
-    "otmb_op_periodic_pc_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
-                                             C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int32, _vp]),
     "otmb_op_periodic_pc": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, C.c_int64,
                                          C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int32, _vp]),
     # per-column d (D, ldd in place of d): the arguments of solve_pc, precond, step_obs and periodic_pc
@@ -245,52 +237,29 @@ SYMBOLS = {
                                       C.c_int64, _vp, _vp, _vp, C.c_int32]),
     "otmb_op_precond_dk_dev": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, _vp, C.c_int64, _vp, C.c_int64]),
     "otmb_op_precond_dk": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, _vp, C.c_int64, _vp, C.c_int64]),
-    "otmb_op_step_dk_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp,
-                                         C.c_int64, C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64]),
     "otmb_op_step_dk": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp,
                                      C.c_int64, C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64]),
-    "otmb_op_periodic_dk_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp,
-                                             C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int32,
-                                             _vp]),
     "otmb_op_periodic_dk": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, _vp, C.c_int64, _vp,
                                          C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int32,
                                          _vp]),
     # a schedule (substeps, nsrc, S: nsrc pointers, lds[, scale] in place of S, lds): the arguments of step_dk and periodic_dk
-    "otmb_op_step_sched_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp,
-                                            C.c_int64, _vp, _vp, C.c_int64, C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp,
-                                            _vp, _vp, C.c_int64]),
     "otmb_op_step_sched": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp,
                                         C.c_int64, _vp, _vp, C.c_int64, C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp,
                                         _vp, _vp, C.c_int64]),
-    "otmb_op_periodic_sched_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                                                _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp,
-                                                _vp, _vp, C.c_int32, _vp]),
     "otmb_op_periodic_sched": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                             _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp,
                                             _vp, _vp, C.c_int32, _vp]),
     # an interpolated schedule (slot_a, slot_b, weight: three host arrays in place of first_slot, substeps): the arguments of the scheduled calls
-    "otmb_op_step_interp_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp,
-                                             C.c_int64, _vp, _vp, C.c_int64, C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp,
-                                             _vp, _vp, C.c_int64]),
     "otmb_op_step_interp": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp,
                                          C.c_int64, _vp, _vp, C.c_int64, C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp,
                                          _vp, _vp, C.c_int64]),
-    "otmb_op_periodic_interp_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp, C.c_int64,
-                                                 _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp,
-                                                 _vp, _vp, C.c_int32, _vp]),
     "otmb_op_periodic_interp": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp, C.c_int64,
                                              _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64, _vp,
                                              _vp, _vp, C.c_int32, _vp]),
     # d per slot (nd, D: nd pointers, ldd in place of D, ldd): the arguments of the interpolated calls
-    "otmb_op_step_season_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp, C.c_int64,
-                                             _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64,
-                                             _vp, _vp, _vp, C.c_int64]),
     "otmb_op_step_season": (C.c_int32, [_vp, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp, C.c_int64,
                                          _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_double, C.c_int64, C.c_int32, _ip, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64,
                                          _vp, _vp, _vp, C.c_int64]),
-    "otmb_op_periodic_season_dev": (C.c_int32, [_vp, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp,
-                                                 C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64,
-                                                 C.c_int64, _vp, _vp, _vp, C.c_int32, _vp]),
     "otmb_op_periodic_season": (C.c_int32, [_vp, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp,
                                              C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int64,
                                              C.c_int64, _vp, _vp, _vp, C.c_int32, _vp]),
@@ -311,6 +280,8 @@ SYMBOLS = {
     "otmb_transportmatrix_fetch": (C.c_int32, [_vp, C.POINTER(_vp * 5), C.POINTER(_vp * 5), C.POINTER(_vp * 5), C.POINTER(C.c_int64 * 5)]),
     "otmb_transportmatrix_nnz": (C.c_int32, [_vp, C.POINTER(C.c_int64 * 5)]),
 }
+# the step and periodic families are listed above by their host exports only: the `_dev` twin of each takes the same list, with device pointers
+SYMBOLS.update({name + "_dev": (res, list(args)) for name, (res, args) in list(SYMBOLS.items()) if name.startswith(("otmb_op_step", "otmb_op_periodic"))})
 
 _lib = None
 

@@ -1,5 +1,5 @@
 // otmb_op.h -- the resident sparse operator's record and the host helpers shared by its products (otmb_spmv.hip) and its solver
-// (otmb_solve.hip): register blocks of columns, compact staging of host matrices and of d.  The device walks over the layouts: otmb_op_fold.h.
+// (otmb_solve.hip): register blocks of columns, compact staging of host matrices, of d and of a stepped call.  The device walks over the layouts: otmb_op_fold.h.
 // The layouts are described at the head of otmb_spmv.hip, which builds them and owns every buffer (sp_free_all).
 #pragma once
 #include <algorithm>
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "otmb_common.h"
+#include "otmb_sched.h"
 
 #define SP_ELL_MAX 256   // longest row a slice takes
 #define SP_TCH 512       // entries per LDS chunk of the Aᵀ and long-row kernels
@@ -134,5 +135,33 @@ static int32_t op_stage_dl(otmb_op *op, i64 nd, const double *const *D, i64 ldd,
         dev[(size_t)j] = to;
         if (n > 0 && (rc = op_upload(ctx, to, D[j], ldd == 0 ? n : ldd, n, kc))) return rc;
     }
+    return OTMB_OK;
+}
+
+// What the host variant of a step or periodic call runs on: X compact in op->xs (n x k; uploaded when X is not null), source block j compact
+// behind block j - 1 in op->ys, the d blocks in op->ds (op_stage_dl), and the lists of their device pointers as the device variant takes
+// them.  d and src point into the record's own vectors: it stays where it was filled.
+struct OpStaged {
+    double *X;
+    std::vector<const double *> dptr, sptr;
+    StD d;
+    StSrc src;
+};
+static int32_t op_stage_call(otmb_op *op, i64 k, const StD &d, const StSrc &src, const double *X, i64 ldx, OpStaged &g) {
+    otmb_ctx *ctx = op->ctx;
+    const i64 n = op->n;
+    int32_t rc;
+    i64 lddev = 0;
+    if ((rc = op_reserve_xy(op, n, src.nsrc * n, k)) || (rc = op_stage_dl(op, d.nd, d.D, d.ldd, k, g.dptr, lddev))) return rc;
+    g.X = (double *)op->xs.p;
+    g.sptr.resize((size_t)src.nsrc);
+    for (i64 j = 0; j < src.nsrc; ++j) g.sptr[(size_t)j] = (const double *)op->ys.p + j * n * k;
+    if (n > 0) {  // staged once, however many steps or cycles
+        if (X && (rc = op_upload(ctx, g.X, X, ldx, n, k))) return rc;
+        for (i64 j = 0; j < src.nsrc; ++j)
+            if ((rc = op_upload(ctx, (double *)op->ys.p + j * n * k, src.S[j], src.lds, n, k))) return rc;
+    }
+    g.d = StD{g.dptr[0] ? d.nd : 0, g.dptr.data(), lddev};
+    g.src = StSrc{src.nsrc, g.sptr.data(), n, src.scale};
     return OTMB_OK;
 }

@@ -1,5 +1,5 @@
 // otmb_periodic.hip -- the periodic state of the stepped cycle, x = F(x), on a resident operator with value slots: otmb_op_periodic[_dev].
-// F(x) = otmb_op_step_dev over ncycle steps from first_slot with the source S; F is affine, F(x) = Φ·x + g with Φ·v the same call without S
+// F(x) = the step call over the cycle's ncycle steps with the source S; F is affine, F(x) = Φ·x + g with Φ·v the same call without S
 // and g = F(0).  include/otmb.h states the contract; tests/periodic_ref.py restates it in numpy.
 //
 // Per column (columns are independent; a stopped column is frozen): restarted GMRES(m) on (I - Φ)·δ = r, r = F(x) - x, no preconditioner.
@@ -21,10 +21,11 @@
 // quantity's partials in index order.  No floating-point atomics, no FMA (-ffp-contract=off), one operation per statement where the order is
 // the contract.  LDS: the workgroup reduction only.
 //
-// The host part: the column's least-squares problem is otmb_gmres.h's (host C++ alone, tested without a device); PdRun holds one call -- its
-// arguments, the workspace, the columns, the host's copies -- and its member functions are the steps of otmb_op_periodic_dev's outline:
-// the sources' norms, the first call, the rounds (cycle, orthogonalise, read_hs, judged, advance) and the report (sv_report_open, which the
-// solver shares, as it shares the step's argument checks: otmb_solve.h).
+// The host part: the column's least-squares problem is otmb_gmres.h's and the schedule's rules are otmb_sched.h's (host C++ alone, each
+// tested without a device); every export states its call as one record (PdCall, otmb_solve.h: the step call's head and the outer
+// iteration's arguments); PdRun holds one call -- that record, the workspace, the columns, the host's copies -- and its member functions are
+// the steps of pd_run's outline: the sources' norms, the first call, the rounds (cycle, orthogonalise, read_hs, judged, advance) and the
+// report (sv_report_open, which the solver shares, as it shares the step's argument checks: otmb_solve.h).
 //
 // otmb_op_periodic_pc[_dev] with OTMB_OUTER_MEAN: flexible GMRES, right-preconditioned by the cycle-mean operator.  M̄ = diag(d) + Ā, Ā the
 // visit-weighted mean of the cycle's slots (cb_combine of otmb_combine.hip into op->mean, once per call), P = ncycle·δt; one implicit-Euler
@@ -38,19 +39,20 @@
 // for all k columns, lends the gathered columns' sh, diag, multipliers and pivots to a compact copy (w.mpg).  The step and the solver give a
 // column the same bits at every position of a block, so a column's path does not depend on which other columns still run.
 //
-// otmb_op_periodic_sched[_dev], the cycle with a schedule (sub-steps inside a slot, a source block per slot): F is otmb_op_step_sched_dev,
-// the gathered step calls carry the live columns of every block (one block: in w.Sb or, the first call's 2k, in the bases, as ever; more:
-// in w.Sg, block j's columns behind block j - 1's), a column is zero only when it is zero in every block, and the mean's weights count
-// the schedule's visits.  Every other periodic export is this call with substeps = 1 and at most one block.
-//
-// otmb_op_periodic_interp[_dev], the cycle of interpolated steps: PdRun holds the schedule (mix) in place of first_slot / substeps, F is
-// otmb_op_step_interp_dev (cycle), and the mean's weights are the slots' shares of the schedule's weights, accumulated step by step in
-// the contract's order (mean_setup).  op->mean and the step's op->interp are different value sets: the call needs both at once.
-//
-// otmb_op_periodic_season[_dev], that cycle with d and the source per slot: F is otmb_op_step_season_dev; with a d per column and per slot
-// the gathered step calls carry the live columns of every d block (w.Dg: block j's columns behind block j - 1's, as w.Sg holds the
-// sources); and the mean operator is diag(d̄) + Ā with d̄ the fold of the d blocks under the mean's own weights (se_fold of otmb_season.hip
-// into w.dbar, once per call, before the mean's preconditioner is made).  With one block d̄ is that block, untouched.
+// What the record's fields switch on.  F is ONE step call (PdRun::cycle -> st_call of otmb_step.hip) of the columns that iterate, gathered
+// compactly, with the record's schedule, and everything the step does with a field it does here:
+//   sched  cyclic (otmb_op_periodic, _pc, _dk: substeps = 1; otmb_op_periodic_sched) or listed (otmb_op_periodic_interp, _season).  The
+//          mean's weights are the schedule's (StSched::mean_weights): the slots' shares of the cycle's steps, a blended step counting for
+//          its two slots by its weights.  op->mean and a blended step's op->interp are different value sets: the call needs both at once.
+//   d      one block for every column, or per column (D, n x k): the gathered step calls and mean solves then carry the live columns of D
+//          beside their states and sources (w.Dg), and the mean's preconditioner, made once for all k columns, lends the gathered columns'
+//          sh, diag, multipliers and pivots to a compact copy (w.mpg).  The step and the solver give a column the same bits at every
+//          position of a block, so a column's path does not depend on which other columns still run.  Per slot (otmb_op_periodic_season):
+//          w.Dg holds block j's live columns behind block j - 1's, and the mean operator is diag(d̄) + Ā with d̄ the fold of the d blocks
+//          under the mean's own weights (se_fold of otmb_season.hip into w.dbar, once per call, before the mean's preconditioner is made).
+//          With one block d̄ is that block, untouched.
+//   src    one block (its live columns in w.Sb or, the first call's 2k, in the bases) or a block per slot (w.Sg: block j's columns behind
+//          block j - 1's); a column is zero only when it is zero in every block.  Never a scale: a history is not periodic.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -312,20 +314,22 @@ static int32_t pd_work(otmb_op *op, i64 k, i64 m, i64 zvecs, size_t pdbl, bool p
     return OTMB_OK;
 }
 
-// (S: the first source block, or null without one)
-static int32_t pd_check(otmb_op *op, int64_t k, double dt, double theta, int64_t ncycle, int64_t first_slot, const double *S, int64_t lds, double *X, int64_t ldx,
-                        double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, const int64_t *cycles,
-                        const double *defect, const int32_t *reason, int32_t outer) {
-    const char *more = !cycles || !defect || !reason ? "null argument" : sv_step_complaint(op, rtol, maxiter, dt, theta, ncycle >= 1, "ncycle must be >= 1", first_slot);
+// The checks of a periodic call, in the step's order (st_call): the arguments it shares with the step and its own, then D and ldd under the
+// export's name (a season call's d is a list, which has its own checks), then the schedule's (st_check_sched).
+static int32_t pd_check(otmb_op *op, const PdCall &c) {
+    const char *more = !c.cycles || !c.defect || !c.reason
+                           ? "null argument"
+                           : sv_step_complaint(op, c.rtol, c.maxiter, c.dt, c.theta, c.nsteps >= 1, "ncycle must be >= 1", c.sched.first_slot);
     if (!more)
-        more = !(ptol > 0.0)                           ? "ptol must be > 0"
-               : restart < 1 || restart >= (1ll << 20) ? "restart must be >= 1 (and below 2^20)"
-               : maxcycles < 0                         ? "maxcycles must be >= 0"
-                                                       : nullptr;
-    const int32_t rc = sv_check_step(op, precond, k, S, lds, X, ldx, more);
-    if (rc == OTMB_OK && outer != OTMB_OUTER_NONE && outer != OTMB_OUTER_MEAN)
-        return otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, "outer must be OTMB_OUTER_NONE or OTMB_OUTER_MEAN");
-    return rc;
+        more = !(c.ptol > 0.0)                               ? "ptol must be > 0"
+               : c.restart < 1 || c.restart >= (1ll << 20)   ? "restart must be >= 1 (and below 2^20)"
+               : c.maxcycles < 0                             ? "maxcycles must be >= 0"
+                                                             : nullptr;
+    int32_t rc = sv_check_step(op, c.precond, c.k, c.src.nsrc > 0 && c.src.S ? c.src.S[0] : nullptr, c.src.lds, c.X, c.ldx, more);
+    if (rc == OTMB_OK && c.outer != OTMB_OUTER_NONE && c.outer != OTMB_OUTER_MEAN)
+        rc = otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, "outer must be OTMB_OUTER_NONE or OTMB_OUTER_MEAN");
+    if (rc || (!c.season && (rc = sv_check_d(op, c.call, c.d.nd ? c.d.D[0] : nullptr, c.d.ldd)))) return rc;
+    return c.sched_checks ? st_check_sched(op, c) : OTMB_OK;
 }
 
 // g = 0: x = 0 at no cost
@@ -340,30 +344,11 @@ struct PdItem {  // a column of one step call: column col's state from its basis
     i64 col, from;
 };
 
-struct PdRun {  // one call: the operator, the call's arguments, the workspace, the columns and the host's copies
+struct PdRun {  // one call: the operator, the call's record, the workspace, the columns and the host's copies
     otmb_op *op;
     otmb_ctx *ctx;
     hipStream_t st;
-    int32_t adjoint;  // the arguments, in the call's order (restart is m)
-    i64 k;
-    SvD d;  // one d for every column, or D (n x k)
-    double dt, theta;
-    i64 ncycle, first_slot;
-    i64 substeps, nsrc;  // the schedule (include/otmb.h): nsrc source blocks, S a host array of their device pointers
-    const double *const *S;
-    i64 lds;
-    double *X;
-    i64 ldx;
-    int32_t use_x0;
-    double rtol;
-    i64 maxiter;
-    int32_t precond;
-    double ptol;
-    i64 m, maxcycles;
-    int32_t outer;
-    const StMix *mix;  // otmb_op_periodic_interp: the interpolated schedule of ncycle steps in place of first_slot / substeps (null: none)
-    StD dl;            // d as a list of blocks; d above is its first (or none).  More than one: otmb_op_periodic_season
-    bool season;       // F is otmb_op_step_season_dev
+    const PdCall &call;  // (restart is the m of the method's description)
     PdWork w{};
     dim3 grid, block;
     bool alx = false;  // X takes the 16-byte path
@@ -379,12 +364,13 @@ struct PdRun {  // one call: the operator, the call's arguments, the workspace, 
 
     const double *hsh(i64 c) const { return hs.data() + w.hso(c); }  // column c's scalars as the last read_hs left them
     void fold(i64 c, i64 nq, double *out) { hipLaunchKernelGGL(pd_fold_kernel, dim3(1), block, 0, st, (const double *)w.partc(c), w.np, nq, out); }
-    const double *dir(i64 c, i64 i) const { return outer == OTMB_OUTER_MEAN ? w.z(c, i) : w.v(c, i); }  // the direction Φ is applied to in iteration i
+    SvD d() const { return call.d.at(0); }  // one d for every column, or D (n x k); of a list of blocks, the first
+    const double *dir(i64 c, i64 i) const { return call.outer == OTMB_OUTER_MEAN ? w.z(c, i) : w.v(c, i); }  // the direction Φ is applied to in iteration i
     int32_t prepare();
     int32_t mean_setup();
     int32_t msolve(std::vector<PdItem> &items);
     int32_t read_hs();
-    double *sources(bool first) const { return nsrc > 1 ? w.Sg : first && use_x0 ? w.V : w.Sb; }  // where a step call's gathered sources go
+    double *sources(bool first) const { return call.src.nsrc > 1 ? w.Sg : first && call.use_x0 ? w.V : w.Sb; }  // where a step call's gathered sources go
     int32_t cycle(std::vector<PdItem> &items, bool withS, double *sbuf);
     void defect_of(i64 c, i64 p, bool minus_x);
     void judged(i64 c, double beta);
@@ -393,17 +379,17 @@ struct PdRun {  // one call: the operator, the call's arguments, the workspace, 
     void orthogonalise(i64 c, i64 i, i64 p);
     int32_t advance(i64 c);
     int32_t round(bool &more);
-    int32_t report(int64_t *cycles, double *defect, int32_t *reason, int64_t *msolve_iters);
+    int32_t report();
 };
 
 int32_t PdRun::prepare() {
     int32_t rc;
-    const bool mean = outer == OTMB_OUTER_MEAN;
-    if ((rc = pd_work(op, k, m, mean ? m : 0, mean ? sv_prec_doubles(op->n, precond == OTMB_PRECOND_LINES, sv_prec_cols(d, k)) : 0, d.percol(), nsrc, dl.nd, w))) return rc;
+    const bool mean = call.outer == OTMB_OUTER_MEAN;
+    if ((rc = pd_work(op, call.k, call.restart, mean ? call.restart : 0, mean ? sv_prec_doubles(op->n, call.precond == OTMB_PRECOND_LINES, sv_prec_cols(d(), call.k)) : 0, d().percol(), call.src.nsrc, call.d.nd, w))) return rc;
     grid = dim3((unsigned)w.np), block = dim3(256);
-    alx = ((uintptr_t)X & 15) == 0 && (ldx & 1) == 0;
-    col.resize((size_t)k);
-    hs.resize((size_t)(2 * (m + 2) * k)), yh.resize((size_t)(m * k));
+    alx = ((uintptr_t)call.X & 15) == 0 && (call.ldx & 1) == 0;
+    col.resize((size_t)call.k);
+    hs.resize((size_t)(2 * (call.restart + 2) * call.k)), yh.resize((size_t)(call.restart * call.k));
     return OTMB_OK;
 }
 
@@ -414,8 +400,8 @@ int32_t PdRun::read_hs() {
     return OTMB_OK;
 }
 
-// OTMB_OUTER_MEAN, once per call and before X is touched: the mean values Σ_s (count_s / ncycle)·(slot s) into op->mean, count_s the visits
-// of slot s by the cycle's steps, and their preconditioner at σ = 0 (a singular one is refused here).
+// OTMB_OUTER_MEAN, once per call and before X is touched: the mean values Σ_s wt[s]·(slot s) into op->mean, wt the schedule's mean weights
+// (the slots' shares of the cycle's steps), and their preconditioner at σ = 0 (a singular one is refused here).
 int32_t PdRun::mean_setup() {
     const i64 nslots = (i64)op->slots.size();
     int32_t rc;
@@ -432,41 +418,21 @@ int32_t PdRun::mean_setup() {
         b->cap = bytes;
     }
     std::vector<double> wt((size_t)nslots);
-    if (mix) {  // acc_s over t ascending: a plain step adds 1.0 to its slot, a blended one 1.0 - w to a, then w to b; wt[s] = acc_s / ncycle
-        std::vector<double> acc((size_t)nslots, 0.0);
-        for (i64 t = 0; t < ncycle; ++t) {
-            const i64 a = mix->a[t], b = mix->b[t];
-            const double wb = mix->w[t];
-            if (a == b || wb == 0.0) {
-                acc[(size_t)a] = acc[(size_t)a] + 1.0;
-            } else if (wb == 1.0) {
-                acc[(size_t)b] = acc[(size_t)b] + 1.0;
-            } else {
-                const double wa = 1.0 - wb;
-                acc[(size_t)a] = acc[(size_t)a] + wa;
-                acc[(size_t)b] = acc[(size_t)b] + wb;
-            }
-        }
-        for (i64 s = 0; s < nslots; ++s) wt[(size_t)s] = acc[(size_t)s] / (double)ncycle;
-    } else {
-        std::vector<i64> count((size_t)nslots, 0);
-        for (i64 t = 0; t < ncycle; ++t) count[(size_t)((first_slot + t / substeps) % nslots)] += 1;
-        for (i64 s = 0; s < nslots; ++s) wt[(size_t)s] = (double)count[(size_t)s] / (double)ncycle;
-    }
+    call.sched.mean_weights(call.nsteps, nslots, wt.data());
     if ((rc = cb_combine(op, wt.data(), op->mean))) return rc;
-    SvD dm = d;
-    if (dl.nd > 1) {  // d̄: the fold of the d blocks under the same weights -- the slots with a weight that is not zero, in ascending order
+    SvD dm = d();
+    if (call.d.nd > 1) {  // d̄: the fold of the d blocks under the same weights -- the slots with a weight that is not zero, in ascending order
         std::vector<const double *> blocks;
         std::vector<double> terms;
         for (i64 s = 0; s < nslots; ++s)
-            if (wt[(size_t)s] != 0.0) blocks.push_back(dl.D[s]), terms.push_back(wt[(size_t)s]);
-        if ((rc = se_fold(op, blocks, terms, w.n, sv_prec_cols(d, k), dl.ldd, w.dbar, w.ld))) return rc;
-        dm = SvD{w.dbar, d.percol() ? w.ld : 0};
+            if (wt[(size_t)s] != 0.0) blocks.push_back(call.d.D[s]), terms.push_back(wt[(size_t)s]);
+        if ((rc = se_fold(op, blocks, terms, w.n, sv_prec_cols(d(), call.k), call.d.ldd, w.dbar, w.ld))) return rc;
+        dm = SvD{w.dbar, d().percol() ? w.ld : 0};
     }
-    period = (double)ncycle * dt;
-    mean_pc = sv_prec_carve(w.mp, w.n, precond == OTMB_PRECOND_LINES, sv_prec_cols(d, k), d.percol());
+    period = (double)call.nsteps * call.dt;
+    mean_pc = sv_prec_carve(w.mp, w.n, call.precond == OTMB_PRECOND_LINES, sv_prec_cols(d(), call.k), d().percol());
     SvValues on(op, op->mean);
-    if ((rc = sv_prec_prepare(op, adjoint, precond, dm, 0.0, mean_pc))) ctx->err += " (the cycle-mean operator)";
+    if ((rc = sv_prec_prepare(op, call.adjoint, call.precond, dm, 0.0, mean_pc))) ctx->err += " (the cycle-mean operator)";
     return rc;
 }
 
@@ -481,8 +447,8 @@ int32_t PdRun::msolve(std::vector<PdItem> &items) {
             HIP_TRY(ctx, hipMemcpyAsync(w.Sb + p * ld, w.v(items[(size_t)p].col, items[(size_t)p].from), (size_t)n * 8, hipMemcpyDeviceToDevice, st));
         s_it.assign((size_t)kk, 0), s_rr.assign((size_t)kk, 0.0), s_why.assign((size_t)kk, 0);
         SvPrec pc = mean_pc;
-        if (d.percol()) {  // the solve's column p is column items[p].col: its arrays of the preconditioner, gathered (u is every column's)
-            pc = sv_prec_carve(w.mpg, n, precond == OTMB_PRECOND_LINES, k, true);
+        if (d().percol()) {  // the solve's column p is column items[p].col: its arrays of the preconditioner, gathered (u is every column's)
+            pc = sv_prec_carve(w.mpg, n, call.precond == OTMB_PRECOND_LINES, call.k, true);
             pc.u = mean_pc.u;
             double *const from[] = {mean_pc.sh, mean_pc.diag, mean_pc.m, mean_pc.piv}, *const to[] = {pc.sh, pc.diag, pc.m, pc.piv};
             for (int a = 0; a < (pc.m ? 4 : 2); ++a)
@@ -492,7 +458,7 @@ int32_t PdRun::msolve(std::vector<PdItem> &items) {
         int32_t rc;
         {
             SvValues on(op, op->mean);
-            rc = sv_solve(op, adjoint, kk, pc, w.Sb, ld, w.W, ld, 0, rtol, maxiter, s_it.data(), s_rr.data(), s_why.data(), precond);
+            rc = sv_solve(op, call.adjoint, kk, pc, w.Sb, ld, w.W, ld, 0, call.rtol, call.maxiter, s_it.data(), s_rr.data(), s_why.data(), call.precond);
         }
         if (rc == OTMB_OK) {
             for (i64 p = 0; p < kk; ++p) {
@@ -533,41 +499,39 @@ int32_t PdRun::cycle(std::vector<PdItem> &items, bool withS, double *sbuf) {
             if (it.from == -2)
                 HIP_TRY(ctx, hipMemsetAsync(w.W + p * ld, 0, (size_t)n * 8, st));
             else
-                HIP_TRY(ctx, hipMemcpyAsync(w.W + p * ld, it.from >= 0 ? dir(it.col, it.from) : X + it.col * ldx, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-            for (i64 j = 0; withS && j < nsrc; ++j)
-                HIP_TRY(ctx, hipMemcpyAsync(sbuf + (j * kk + p) * ld, S[j] + it.col * lds, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-            for (i64 j = 0; d.percol() && j < dl.nd; ++j)
-                HIP_TRY(ctx, hipMemcpyAsync(w.Dg + (j * kk + p) * ld, dl.D[j] + it.col * dl.ldd, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+                HIP_TRY(ctx, hipMemcpyAsync(w.W + p * ld, it.from >= 0 ? dir(it.col, it.from) : call.X + it.col * call.ldx, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+            for (i64 j = 0; withS && j < call.src.nsrc; ++j)
+                HIP_TRY(ctx, hipMemcpyAsync(sbuf + (j * kk + p) * ld, call.src.S[j] + it.col * call.src.lds, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+            for (i64 j = 0; d().percol() && j < call.d.nd; ++j)
+                HIP_TRY(ctx, hipMemcpyAsync(w.Dg + (j * kk + p) * ld, call.d.D[j] + it.col * call.d.ldd, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
         }
-        s_it.assign((size_t)(ncycle * kk), 0), s_rr.assign((size_t)(ncycle * kk), 0.0), s_why.assign((size_t)(ncycle * kk), 0);
+        s_it.assign((size_t)(call.nsteps * kk), 0), s_rr.assign((size_t)(call.nsteps * kk), 0.0), s_why.assign((size_t)(call.nsteps * kk), 0);
         int64_t done = 0;
-        std::vector<const double *> sp((size_t)(withS ? nsrc : 0));
+        std::vector<const double *> sp((size_t)(withS ? call.src.nsrc : 0));
         for (size_t j = 0; j < sp.size(); ++j) sp[j] = sbuf + (i64)j * kk * ld;
-        std::vector<const double *> dp((size_t)dl.nd);  // the step call's d blocks: the gathered columns, or the shared blocks as they are
-        for (size_t j = 0; j < dp.size(); ++j) dp[j] = d.percol() ? w.Dg + (i64)j * kk * ld : dl.D[j];
-        const int32_t rc =
-            season ? otmb_op_step_season_dev(op, adjoint, kk, dl.nd, dp.data(), d.percol() ? ld : 0, dt, theta, ncycle, mix->a, mix->b, mix->w, (i64)sp.size(),
-                                             sp.data(), ld, nullptr, w.W, ld, rtol, maxiter, precond, &done, s_it.data(), s_rr.data(), s_why.data(), 0, nullptr, 0,
-                                             nullptr, nullptr, nullptr, 0)
-            : mix ? otmb_op_step_interp_dev(op, adjoint, kk, d.percol() ? w.Dg : d.p, d.percol() ? ld : 0, dt, theta, ncycle, mix->a, mix->b, mix->w, (i64)sp.size(),
-                                          sp.data(), ld, nullptr, w.W, ld, rtol, maxiter, precond, &done, s_it.data(), s_rr.data(), s_why.data(), 0, nullptr, 0,
-                                          nullptr, nullptr, nullptr, 0)
-                : otmb_op_step_sched_dev(op, adjoint, kk, d.percol() ? w.Dg : d.p, d.percol() ? ld : 0, dt, theta, ncycle, first_slot, substeps, (i64)sp.size(),
-                                         sp.data(), ld, nullptr, w.W, ld, rtol, maxiter, precond, &done, s_it.data(), s_rr.data(), s_why.data(), 0, nullptr, 0,
-                                         nullptr, nullptr, nullptr, 0);
+        std::vector<const double *> dp((size_t)call.d.nd);  // the step call's d blocks: the gathered columns, or the shared blocks as they are
+        for (size_t j = 0; j < dp.size(); ++j) dp[j] = d().percol() ? w.Dg + (i64)j * kk * ld : call.d.D[j];
+        // the cycle as a step call of the gathered columns, under the name of the step export of this call's family and behind its checks
+        StCall step = {call, &done, s_it.data(), s_rr.data(), s_why.data(), ST_PLAIN};
+        step.call = call.season ? "otmb_op_step_season" : call.sched.listed ? "otmb_op_step_interp" : "otmb_op_step_sched";
+        step.sched_checks = true;
+        step.k = kk, step.X = w.W, step.ldx = ld;
+        step.d = StD{(i64)dp.size(), dp.data(), d().percol() ? ld : 0};
+        step.src = StSrc{(i64)sp.size(), sp.data(), ld, nullptr};
+        const int32_t rc = st_call<true>(op, step);
         if (rc == OTMB_OK) {
-            std::vector<char> seen((size_t)k, 0);  // (the first call holds a column twice: one call, one cycle)
+            std::vector<char> seen((size_t)call.k, 0);  // (the first call holds a column twice: one call, one cycle)
             for (const PdItem &it : items)
                 if (!seen[(size_t)it.col]++) col[(size_t)it.col].cycles += 1;
             return OTMB_OK;
         }
-        if (rc == OTMB_ERR_SINGULAR_PRECONDITIONER && d.percol()) {
+        if (rc == OTMB_ERR_SINGULAR_PRECONDITIONER && d().percol()) {
             // the step names the column by its place in the gathered block: the caller reads its own column and k.  (items hold the columns
             // in rising order, a second copy of each behind them in the first call, so the smallest place is the smallest column.)
             const size_t at = ctx->err.rfind(" (column "), end = at == std::string::npos ? at : ctx->err.find(')', at);
             long long place = 0;
             if (end != std::string::npos && sscanf(ctx->err.c_str() + at, " (column %lld", &place) == 1 && place >= 1 && place <= kk)
-                ctx->err.replace(at, end + 1 - at, " (column " + std::to_string(items[(size_t)(place - 1)].col + 1) + " of " + std::to_string(k) + ")");
+                ctx->err.replace(at, end + 1 - at, " (column " + std::to_string(items[(size_t)(place - 1)].col + 1) + " of " + std::to_string(call.k) + ")");
         }
         if (rc != OTMB_ERR_NOT_CONVERGED) return rc;
         if (step_msg.empty()) step_msg = ctx->err;
@@ -584,7 +548,7 @@ int32_t PdRun::cycle(std::vector<PdItem> &items, bool withS, double *sbuf) {
 
 // r = W[p] - x (or W[p]) -> V_0 of column c, ‖r‖² -> hs[c][0]
 void PdRun::defect_of(i64 c, i64 p, bool minus_x) {
-    hipLaunchKernelGGL(pd_defect_kernel, grid, block, 0, st, w.n, (const double *)(w.W + p * w.ld), minus_x ? (const double *)(X + c * ldx) : nullptr, alx,
+    hipLaunchKernelGGL(pd_defect_kernel, grid, block, 0, st, w.n, (const double *)(w.W + p * w.ld), minus_x ? (const double *)(call.X + c * call.ldx) : nullptr, alx,
                        w.v(c, 0), w.partc(c));
     fold(c, 1, w.hsc(c));
 }
@@ -594,34 +558,34 @@ void PdRun::judged(i64 c, double beta) {
     PdCol &q = col[(size_t)c];
     q.defect = beta / q.gnorm;
     if (!std::isfinite(beta)) return q.stop(OTMB_PERIODIC_NONFINITE);
-    if (beta <= ptol * q.gnorm) return q.stop(OTMB_PERIODIC_CONVERGED);
+    if (beta <= call.ptol * q.gnorm) return q.stop(OTMB_PERIODIC_CONVERGED);
     hipLaunchKernelGGL(pd_scale_kernel, grid, block, 0, st, w.n, w.v(c, 0), beta);
     q.phase = PD_ARNOLDI;
-    q.ls.start(m, beta);
+    q.ls.start(call.restart, beta);
 }
 
 // the sources' norms, block by block: a column that is zero in every block has g = 0.  items: the columns of the first call
 int32_t PdRun::source_norms(std::vector<PdItem> &items) {
     int32_t rc;
-    std::vector<char> zero((size_t)k, 1);
-    for (i64 j = 0; j < nsrc; ++j) {
-        for (i64 c = 0; c < k; ++c) {
-            HIP_TRY(ctx, hipMemcpyAsync(w.W + c * w.ld, S[j] + c * lds, (size_t)w.n * 8, hipMemcpyDeviceToDevice, st));
+    std::vector<char> zero((size_t)call.k, 1);
+    for (i64 j = 0; j < call.src.nsrc; ++j) {
+        for (i64 c = 0; c < call.k; ++c) {
+            HIP_TRY(ctx, hipMemcpyAsync(w.W + c * w.ld, call.src.S[j] + c * call.src.lds, (size_t)w.n * 8, hipMemcpyDeviceToDevice, st));
             hipLaunchKernelGGL(pd_defect_kernel, grid, block, 0, st, w.n, (const double *)(w.W + c * w.ld), (const double *)nullptr, false, (double *)nullptr, w.partc(c));
             fold(c, 1, w.hsc(c));
         }
         if ((rc = read_hs())) return rc;
-        for (i64 c = 0; c < k; ++c)
+        for (i64 c = 0; c < call.k; ++c)
             if (!(hsh(c)[0] == 0.0)) zero[(size_t)c] = 0;
     }
-    for (i64 c = 0; c < k; ++c) {
+    for (i64 c = 0; c < call.k; ++c) {
         PdCol &q = col[(size_t)c];
         if (zero[(size_t)c]) {
             q.stop(OTMB_PERIODIC_CONVERGED), q.defect = 0.0;
-        } else if (maxcycles < 1) {
+        } else if (call.maxcycles < 1) {
             q.stop(OTMB_PERIODIC_MAXCYCLES);
         } else {
-            items.push_back({c, use_x0 ? (i64)-1 : (i64)-2});
+            items.push_back({c, call.use_x0 ? (i64)-1 : (i64)-2});
         }
     }
     return OTMB_OK;
@@ -631,30 +595,30 @@ int32_t PdRun::source_norms(std::vector<PdItem> &items) {
 int32_t PdRun::first_call(std::vector<PdItem> &items) {
     const i64 n = w.n, ld = w.ld;
     int32_t rc;
-    if (use_x0)
+    if (call.use_x0)
         for (size_t p = 0, live = items.size(); p < live; ++p) items.push_back({items[p].col, -2});
     if ((rc = cycle(items, true, sources(true)))) return rc;  // (with a start one block's 2k sources lie in the bases, which are not in use yet)
     // from here on X is written: the zero columns, and a start of zero
-    for (i64 c = 0; c < k; ++c)
-        if (!use_x0 || (col[(size_t)c].phase == PD_STOPPED && col[(size_t)c].reason == OTMB_PERIODIC_CONVERGED))
-            HIP_TRY(ctx, hipMemsetAsync(X + c * ldx, 0, (size_t)n * 8, st));
-    const i64 live = use_x0 ? (i64)items.size() / 2 : (i64)items.size();
-    if (use_x0)  // ‖g‖² first: the defect's fold would overwrite the same slot, so it goes to the second half of the column's scalars
+    for (i64 c = 0; c < call.k; ++c)
+        if (!call.use_x0 || (col[(size_t)c].phase == PD_STOPPED && col[(size_t)c].reason == OTMB_PERIODIC_CONVERGED))
+            HIP_TRY(ctx, hipMemsetAsync(call.X + c * call.ldx, 0, (size_t)n * 8, st));
+    const i64 live = call.use_x0 ? (i64)items.size() / 2 : (i64)items.size();
+    if (call.use_x0)  // ‖g‖² first: the defect's fold would overwrite the same slot, so it goes to the second half of the column's scalars
         for (i64 p = 0; p < live; ++p) {
             const i64 c = items[(size_t)p].col;
             hipLaunchKernelGGL(pd_defect_kernel, grid, block, 0, st, n, (const double *)(w.W + (live + p) * ld), (const double *)nullptr, false, (double *)nullptr,
                                w.partc(c));
-            fold(c, 1, w.hsc(c) + (m + 2));
+            fold(c, 1, w.hsc(c) + (call.restart + 2));
         }
-    for (i64 p = 0; p < live; ++p) defect_of(items[(size_t)p].col, p, use_x0 != 0);
+    for (i64 p = 0; p < live; ++p) defect_of(items[(size_t)p].col, p, call.use_x0 != 0);
     if ((rc = read_hs())) return rc;
     for (i64 p = 0; p < live; ++p) {
         const i64 c = items[(size_t)p].col;
         PdCol &q = col[(size_t)c];
         const double beta = std::sqrt(hsh(c)[0]);
-        q.gnorm = use_x0 ? std::sqrt(hsh(c)[m + 2]) : beta;
+        q.gnorm = call.use_x0 ? std::sqrt(hsh(c)[call.restart + 2]) : beta;
         if (q.gnorm == 0.0) {  // (a source that is not zero whose cycle underflows to zero)
-            HIP_TRY(ctx, hipMemsetAsync(X + c * ldx, 0, (size_t)n * 8, st));
+            HIP_TRY(ctx, hipMemsetAsync(call.X + c * call.ldx, 0, (size_t)n * 8, st));
             q.stop(OTMB_PERIODIC_CONVERGED), q.defect = 0.0;
         } else if (!std::isfinite(q.gnorm)) {
             q.stop(OTMB_PERIODIC_NONFINITE);
@@ -668,7 +632,7 @@ int32_t PdRun::first_call(std::vector<PdItem> &items) {
 // iteration i of column c on the device, from Φ·V_i in W[p] (OTMB_OUTER_MEAN: Z_i for V_i): w = V_i - Φ·V_i into V_{i+1}, then CGS2 against V_0..i; h', h'' and ‖w‖² -> hs[c]
 void PdRun::orthogonalise(i64 c, i64 i, i64 p) {
     const i64 n = w.n, ld = w.ld, np = w.np;
-    double *wv = w.v(c, i + 1), *h1 = w.hsc(c), *h2 = w.hsc(c) + (m + 2);
+    double *wv = w.v(c, i + 1), *h1 = w.hsc(c), *h2 = w.hsc(c) + (call.restart + 2);
     const double *V = w.v(c, 0);
     hipLaunchKernelGGL(pd_defect_kernel, grid, block, 0, st, n, dir(c, i), (const double *)(w.W + p * ld), true, wv, (double *)nullptr);
     for (int pass = 0; pass < 2; ++pass) {
@@ -694,18 +658,18 @@ int32_t PdRun::advance(i64 c) {
     PdCol &q = col[(size_t)c];
     const i64 i = q.ls.i;
     double hn, est;
-    if (!q.ls.push(hsh(c), hsh(c) + (m + 2), &hn, &est)) {
+    if (!q.ls.push(hsh(c), hsh(c) + (call.restart + 2), &hn, &est)) {
         q.stop(OTMB_PERIODIC_NONFINITE);
         return OTMB_OK;
     }
-    if (!(est <= ptol * q.gnorm || q.ls.i == m || hn == 0.0 || q.cycles + 1 >= maxcycles)) {
+    if (!(est <= call.ptol * q.gnorm || q.ls.i == call.restart || hn == 0.0 || q.cycles + 1 >= call.maxcycles)) {
         hipLaunchKernelGGL(pd_scale_kernel, grid, block, 0, st, w.n, w.v(c, i + 1), hn);
         return OTMB_OK;
     }
-    double *y = yh.data() + c * m;
+    double *y = yh.data() + c * call.restart;
     q.ls.solve(y);
-    HIP_TRY(ctx, hipMemcpyAsync(w.yv + c * m, y, (size_t)q.ls.i * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(pd_combine_kernel, grid, block, 0, st, w.n, dir(c, 0), w.ld, q.ls.i, (const double *)(w.yv + c * m), X + c * ldx, alx);
+    HIP_TRY(ctx, hipMemcpyAsync(w.yv + c * call.restart, y, (size_t)q.ls.i * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(pd_combine_kernel, grid, block, 0, st, w.n, dir(c, 0), w.ld, q.ls.i, (const double *)(w.yv + c * call.restart), call.X + c * call.ldx, alx);
     q.phase = PD_VERIFY;
     return OTMB_OK;
 }
@@ -714,15 +678,15 @@ int32_t PdRun::advance(i64 c) {
 int32_t PdRun::round(bool &more) {
     int32_t rc;
     std::vector<PdItem> ia, iv;
-    for (i64 c = 0; c < k; ++c) {
+    for (i64 c = 0; c < call.k; ++c) {
         PdCol &q = col[(size_t)c];
-        if (q.phase == PD_ARNOLDI && q.ls.i == 0 && q.cycles + 2 > maxcycles) q.stop(OTMB_PERIODIC_MAXCYCLES);  // no verifying cycle could follow
+        if (q.phase == PD_ARNOLDI && q.ls.i == 0 && q.cycles + 2 > call.maxcycles) q.stop(OTMB_PERIODIC_MAXCYCLES);  // no verifying cycle could follow
         if (q.phase == PD_ARNOLDI) ia.push_back({c, q.ls.i});
         if (q.phase == PD_VERIFY) iv.push_back({c, -1});
     }
     more = !(ia.empty() && iv.empty());
     if (!more) return OTMB_OK;
-    if (outer == OTMB_OUTER_MEAN && (rc = msolve(ia))) return rc;
+    if (call.outer == OTMB_OUTER_MEAN && (rc = msolve(ia))) return rc;
     if ((rc = cycle(ia, false, nullptr))) return rc;
     for (size_t p = 0; p < ia.size(); ++p) orthogonalise(ia[p].col, ia[p].from, (i64)p);
     if ((rc = cycle(iv, true, sources(false)))) return rc;
@@ -735,225 +699,139 @@ int32_t PdRun::round(bool &more) {
     return OTMB_OK;
 }
 
-int32_t PdRun::report(int64_t *cycles, double *defect, int32_t *reason, int64_t *msolve_iters) {
-    for (i64 c = 0; c < k; ++c) cycles[c] = col[(size_t)c].cycles, defect[c] = col[(size_t)c].defect, reason[c] = col[(size_t)c].reason;
+int32_t PdRun::report() {
+    int64_t *cycles = call.cycles, *msolve_iters = call.msolve_iters;
+    double *defect = call.defect;
+    int32_t *reason = call.reason;
+    for (i64 c = 0; c < call.k; ++c) cycles[c] = col[(size_t)c].cycles, defect[c] = col[(size_t)c].defect, reason[c] = col[(size_t)c].reason;
     if (msolve_iters)
-        for (i64 c = 0; c < k; ++c) msolve_iters[c] = col[(size_t)c].msolve_iters;
+        for (i64 c = 0; c < call.k; ++c) msolve_iters[c] = col[(size_t)c].msolve_iters;
     static const char *const names[] = {"converged", "maxcycles", "step failed", "nonfinite", "precond failed"};
-    return sv_report_open(ctx, "periodic: %lld of %lld columns; the first is column %lld: %s after %lld cycles, defect %.3e", names, k, reason, cycles, defect,
+    return sv_report_open(ctx, "periodic: %lld of %lld columns; the first is column %lld: %s after %lld cycles, defect %.3e", names, call.k, reason, cycles, defect,
                           (step_msg.empty() ? step_msg : "; the step: " + step_msg) + (msolve_msg.empty() ? msolve_msg : "; the mean solve: " + msolve_msg), 5);
+}
+
+// The call proper: device pointers (c.src.S, c.d.D: host arrays of them), the arguments checked.
+static int32_t pd_run(otmb_op *op, const PdCall &c) {
+    int32_t rc;
+    otmb_ctx *ctx = op->ctx;
+    // the trivial answers: no rows, no source
+    if (op->n == 0) return pd_all_zero(c.k, c.cycles, c.defect, c.reason, c.msolve_iters);
+    HIP_TRY(ctx, hipSetDevice(op->device));
+    if (c.src.nsrc == 0) {
+        HIP_TRY(ctx, hipMemset2DAsync(c.X, (size_t)c.ldx * 8, 0, (size_t)op->n * 8, (size_t)c.k, ctx->stream));
+        return pd_all_zero(c.k, c.cycles, c.defect, c.reason, c.msolve_iters);
+    }
+    PdRun r{op, ctx, ctx->stream, c};
+    std::vector<PdItem> items;
+    if ((rc = r.prepare()) || (c.outer == OTMB_OUTER_MEAN && (rc = r.mean_setup())) || (rc = r.source_norms(items)) || (rc = r.first_call(items))) return rc;
+    for (bool more = true; more;)
+        if ((rc = r.round(more))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (yh's uploads have been read)
+    return r.report();
+}
+
+// One body for every periodic call (DEV: device pointers).  The host variant stages the start, every source block and every d block once
+// (op_stage_call) and brings X home once.
+template <bool DEV>
+static int32_t pd_call(otmb_op *op, const PdCall &c) {
+    if (!op) return OTMB_ERR_INVALID_ARG;
+    int32_t rc;
+    if ((rc = pd_check(op, c))) return rc;
+    if (DEV) return pd_run(op, c);
+    otmb_ctx *ctx = op->ctx;
+    HIP_TRY(ctx, hipSetDevice(op->device));
+    const i64 n = op->n;
+    OpStaged g;
+    if ((rc = op_stage_call(op, c.k, c.d, c.src, c.use_x0 ? c.X : nullptr, c.ldx, g))) return rc;
+    PdCall dev = c;
+    dev.d = g.d, dev.src = g.src, dev.X = g.X, dev.ldx = n;
+    rc = pd_run(op, dev);
+    if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED) return rc;
+    return op_finish(ctx, rc, c.X, c.ldx, g.X, n, c.k);
 }
 
 extern "C" {
 
-// the checks of a periodic call (call: the export the refusals of D / ldd name; sched: the scheduled call's own, after those of the call it extends)
-static int32_t pd_check_call(otmb_op *op, const char *call, bool sched, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
-                             int64_t first_slot, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, double rtol,
-                             int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, const int64_t *cycles, const double *defect,
-                             const int32_t *reason, int32_t outer, const StMix *mix = nullptr) {
-    int32_t rc;
-    if ((rc = pd_check(op, k, dt, theta, ncycle, first_slot, nsrc > 0 && S ? S[0] : nullptr, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles,
-                       defect, reason, outer)) ||
-        (rc = sv_check_d(op, call, D, ldd)))
-        return rc;
-    char text[160];
-    const char *more = mix ? sv_interp_complaint(op, ncycle, *mix, nsrc, S, lds, text) : sched ? sv_sched_complaint(op, substeps, nsrc, S, lds) : nullptr;
-    return more ? otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, (std::string(mix ? "otmb_op_periodic_interp: " : "otmb_op_periodic_sched: ") + more).c_str()) : OTMB_OK;
-}
-
-// the call proper: device pointers (S: a host array of nsrc of them; dl: d as a list of blocks), the arguments checked
-static int32_t pd_run_dl(otmb_op *op, int32_t adjoint, int64_t k, const StD &dl, bool season, double dt, double theta, int64_t ncycle, int64_t first_slot,
-                          int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol,
-                          int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
-                          int32_t outer, int64_t *msolve_iters, const StMix *mix = nullptr) {
-    int32_t rc;
-    otmb_ctx *ctx = op->ctx;
-    // the trivial answers: no rows, no source
-    if (op->n == 0) return pd_all_zero(k, cycles, defect, reason, msolve_iters);
-    HIP_TRY(ctx, hipSetDevice(op->device));
-    if (nsrc == 0) {
-        HIP_TRY(ctx, hipMemset2DAsync(X, (size_t)ldx * 8, 0, (size_t)op->n * 8, (size_t)k, ctx->stream));
-        return pd_all_zero(k, cycles, defect, reason, msolve_iters);
-    }
-    PdRun r{op, ctx, ctx->stream, adjoint, k, dl.at(0), dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, outer, mix, dl, season};
-    std::vector<PdItem> items;
-    if ((rc = r.prepare()) || (outer == OTMB_OUTER_MEAN && (rc = r.mean_setup())) || (rc = r.source_norms(items)) || (rc = r.first_call(items))) return rc;
-    for (bool more = true; more;)
-        if ((rc = r.round(more))) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (yh's uploads have been read)
-    return r.report(cycles, defect, reason, msolve_iters);
-}
-
-// every call but the season's: at most the one block of d
-static int32_t pd_run_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle, int64_t first_slot,
-                          int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol,
-                          int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
-                          int32_t outer, int64_t *msolve_iters, const StMix *mix = nullptr) {
-    const double *const one[1] = {D};
-    return pd_run_dl(op, adjoint, k, StD{D ? 1 : 0, one, ldd}, false, dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond,
-                     ptol, restart, maxcycles, cycles, defect, reason, outer, msolve_iters, mix);
-}
-
-// the host variant: the start, every source block and every d block staged once, X home once
-static int32_t pd_run_host_dl(otmb_op *op, int32_t adjoint, int64_t k, const StD &dl, bool season, double dt, double theta, int64_t ncycle, int64_t first_slot,
-                           int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol,
-                           int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
-                           int32_t outer, int64_t *msolve_iters, const StMix *mix = nullptr) {
-    int32_t rc;
-    otmb_ctx *ctx = op->ctx;
-    HIP_TRY(ctx, hipSetDevice(op->device));
-    const i64 n = op->n;
-    std::vector<const double *> dd;
-    i64 lddev = 0;
-    if ((rc = op_reserve_xy(op, n, nsrc * n, k)) || (rc = op_stage_dl(op, dl.nd, dl.D, dl.ldd, k, dd, lddev))) return rc;
-    double *dx = (double *)op->xs.p;
-    std::vector<const double *> ds((size_t)nsrc);  // block j compact behind block j - 1
-    for (i64 j = 0; j < nsrc; ++j) ds[(size_t)j] = (const double *)op->ys.p + j * n * k;
-    if (n > 0) {  // staged once, however many cycles
-        if (use_x0 && (rc = op_upload(ctx, dx, X, ldx, n, k))) return rc;
-        for (i64 j = 0; j < nsrc; ++j)
-            if ((rc = op_upload(ctx, (double *)op->ys.p + j * n * k, S[j], lds, n, k))) return rc;
-    }
-    rc = pd_run_dl(op, adjoint, k, StD{dd[0] ? dl.nd : 0, dd.data(), lddev}, season, dt, theta, ncycle, first_slot, substeps, nsrc, ds.data(), n, dx, n, use_x0, rtol,
-                   maxiter, precond, ptol, restart, maxcycles, cycles, defect, reason, outer, msolve_iters, mix);
-    if (rc != OTMB_OK && rc != OTMB_ERR_NOT_CONVERGED) return rc;
-    return op_finish(ctx, rc, X, ldx, dx, n, k);
-}
-static int32_t pd_run_host(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle, int64_t first_slot,
-                           int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol,
-                           int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
-                           int32_t outer, int64_t *msolve_iters, const StMix *mix = nullptr) {
-    const double *const one[1] = {D};
-    return pd_run_host_dl(op, adjoint, k, StD{D ? 1 : 0, one, ldd}, false, dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter,
-                          precond, ptol, restart, maxcycles, cycles, defect, reason, outer, msolve_iters, mix);
-}
-
-// the checks of the season call: those of the call it extends, then the schedule's and the sources' (a block per slot is in order), then the d blocks'
-static int32_t pd_check_season(otmb_op *op, int64_t k, const StD &dl, double dt, double theta, int64_t ncycle, const StMix &mix, int64_t nsrc,
-                               const double *const *S, int64_t lds, double *X, int64_t ldx, double rtol, int64_t maxiter, int32_t precond, double ptol,
-                               int64_t restart, int64_t maxcycles, const int64_t *cycles, const double *defect, const int32_t *reason, int32_t outer) {
-    int32_t rc;
-    if ((rc = pd_check(op, k, dt, theta, ncycle, 0, nsrc > 0 && S ? S[0] : nullptr, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect,
-                       reason, outer)))
-        return rc;
-    char text[160];
-    const char *more = sv_interp_complaint(op, ncycle, mix, nsrc, S, lds, text, true);
-    if (!more) more = sv_season_complaint(op, dl.nd, dl.D, dl.ldd);
-    return more ? otmb_fail(op->ctx, OTMB_ERR_INVALID_ARG, (std::string("otmb_op_periodic_season: ") + more).c_str()) : OTMB_OK;
-}
-
-// the interpolated schedule with d and the source per slot: nd, D (nd pointers), ldd in place of D, ldd; F is otmb_op_step_season_dev
+// the listed schedule with d and the source per slot: nd, D (nd pointers), ldd in place of D, ldd; F is the step call of otmb_op_step_season
 int32_t otmb_op_periodic_season_dev(otmb_op *op, int32_t adjoint, int64_t k, int64_t nd, const double *const *D, int64_t ldd, double dt, double theta,
                                     int64_t ncycle, const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S,
                                     int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol,
                                     int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters) {
-    if (!op) return OTMB_ERR_INVALID_ARG;
-    const StMix mix = {slot_a, slot_b, weight};
-    const StD dl = {nd, D, ldd};
-    int32_t rc;
-    if ((rc = pd_check_season(op, k, dl, dt, theta, ncycle, mix, nsrc, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect, reason, outer)))
-        return rc;
-    return pd_run_dl(op, adjoint, k, dl, true, dt, theta, ncycle, 0, 1, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect,
-                     reason, outer, msolve_iters, &mix);
+    return pd_call<true>(op, {{"otmb_op_periodic_season", true, true, adjoint, k, StD{nd, D, ldd}, dt, theta, ncycle, StSched::list(slot_a, slot_b, weight), StSrc{nsrc, S, lds, nullptr},
+                            X, ldx, rtol, maxiter, precond},
+                           use_x0, ptol, restart, maxcycles, outer, cycles, defect, reason, msolve_iters});
 }
 
 int32_t otmb_op_periodic_season(otmb_op *op, int32_t adjoint, int64_t k, int64_t nd, const double *const *D, int64_t ldd, double dt, double theta, int64_t ncycle,
                                 const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S, int64_t lds, double *X,
                                 int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles,
                                 int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters) {
-    if (!op) return OTMB_ERR_INVALID_ARG;
-    const StMix mix = {slot_a, slot_b, weight};
-    const StD dl = {nd, D, ldd};
-    int32_t rc;
-    if ((rc = pd_check_season(op, k, dl, dt, theta, ncycle, mix, nsrc, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect, reason, outer)))
-        return rc;
-    return pd_run_host_dl(op, adjoint, k, dl, true, dt, theta, ncycle, 0, 1, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, cycles,
-                          defect, reason, outer, msolve_iters, &mix);
+    return pd_call<false>(op, {{"otmb_op_periodic_season", true, true, adjoint, k, StD{nd, D, ldd}, dt, theta, ncycle, StSched::list(slot_a, slot_b, weight), StSrc{nsrc, S, lds, nullptr},
+                            X, ldx, rtol, maxiter, precond},
+                           use_x0, ptol, restart, maxcycles, outer, cycles, defect, reason, msolve_iters});
 }
 
+// the cyclic schedule with sub-steps and a list of source blocks; F is the step call of otmb_op_step_sched
 int32_t otmb_op_periodic_sched_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
                                    int64_t first_slot, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx,
                                    int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles,
                                    int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters) {
-    if (!op) return OTMB_ERR_INVALID_ARG;
-    int32_t rc;
-    if ((rc = pd_check_call(op, "otmb_op_periodic_sched", true, k, D, ldd, dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, rtol, maxiter, precond,
-                            ptol, restart, maxcycles, cycles, defect, reason, outer)))
-        return rc;
-    return pd_run_dev(op, adjoint, k, D, ldd, dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart,
-                      maxcycles, cycles, defect, reason, outer, msolve_iters);
+    const double *const one[1] = {D};
+    return pd_call<true>(op, {{"otmb_op_periodic_sched", true, false, adjoint, k, StD{D ? 1 : 0, one, ldd}, dt, theta, ncycle, StSched::cyclic(first_slot, substeps), StSrc{nsrc, S, lds, nullptr},
+                            X, ldx, rtol, maxiter, precond},
+                           use_x0, ptol, restart, maxcycles, outer, cycles, defect, reason, msolve_iters});
 }
 
 int32_t otmb_op_periodic_sched(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
                                int64_t first_slot, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0,
                                double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect,
                                int32_t *reason, int32_t outer, int64_t *msolve_iters) {
-    if (!op) return OTMB_ERR_INVALID_ARG;
-    int32_t rc;
-    if ((rc = pd_check_call(op, "otmb_op_periodic_sched", true, k, D, ldd, dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, rtol, maxiter, precond,
-                            ptol, restart, maxcycles, cycles, defect, reason, outer)))
-        return rc;
-    return pd_run_host(op, adjoint, k, D, ldd, dt, theta, ncycle, first_slot, substeps, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart,
-                       maxcycles, cycles, defect, reason, outer, msolve_iters);
+    const double *const one[1] = {D};
+    return pd_call<false>(op, {{"otmb_op_periodic_sched", true, false, adjoint, k, StD{D ? 1 : 0, one, ldd}, dt, theta, ncycle, StSched::cyclic(first_slot, substeps), StSrc{nsrc, S, lds, nullptr},
+                            X, ldx, rtol, maxiter, precond},
+                           use_x0, ptol, restart, maxcycles, outer, cycles, defect, reason, msolve_iters});
 }
 
-// the interpolated schedule: slot_a, slot_b, weight (ncycle host values each) in place of first_slot, substeps; F is otmb_op_step_interp_dev
+// the listed schedule: slot_a, slot_b, weight (ncycle host values each) in place of first_slot, substeps; F is the step call of otmb_op_step_interp
 int32_t otmb_op_periodic_interp_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
                                     const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S, int64_t lds,
                                     double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart,
                                     int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters) {
-    if (!op) return OTMB_ERR_INVALID_ARG;
-    const StMix mix = {slot_a, slot_b, weight};
-    int32_t rc;
-    if ((rc = pd_check_call(op, "otmb_op_periodic_interp", true, k, D, ldd, dt, theta, ncycle, 0, 1, nsrc, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart,
-                            maxcycles, cycles, defect, reason, outer, &mix)))
-        return rc;
-    return pd_run_dev(op, adjoint, k, D, ldd, dt, theta, ncycle, 0, 1, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect,
-                      reason, outer, msolve_iters, &mix);
+    const double *const one[1] = {D};
+    return pd_call<true>(op, {{"otmb_op_periodic_interp", true, false, adjoint, k, StD{D ? 1 : 0, one, ldd}, dt, theta, ncycle, StSched::list(slot_a, slot_b, weight), StSrc{nsrc, S, lds, nullptr},
+                            X, ldx, rtol, maxiter, precond},
+                           use_x0, ptol, restart, maxcycles, outer, cycles, defect, reason, msolve_iters});
 }
 
 int32_t otmb_op_periodic_interp(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
                                 const int64_t *slot_a, const int64_t *slot_b, const double *weight, int64_t nsrc, const double *const *S, int64_t lds, double *X,
                                 int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol, int64_t restart, int64_t maxcycles,
                                 int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters) {
-    if (!op) return OTMB_ERR_INVALID_ARG;
-    const StMix mix = {slot_a, slot_b, weight};
-    int32_t rc;
-    if ((rc = pd_check_call(op, "otmb_op_periodic_interp", true, k, D, ldd, dt, theta, ncycle, 0, 1, nsrc, S, lds, X, ldx, rtol, maxiter, precond, ptol, restart,
-                            maxcycles, cycles, defect, reason, outer, &mix)))
-        return rc;
-    return pd_run_host(op, adjoint, k, D, ldd, dt, theta, ncycle, 0, 1, nsrc, S, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles, cycles, defect,
-                       reason, outer, msolve_iters, &mix);
+    const double *const one[1] = {D};
+    return pd_call<false>(op, {{"otmb_op_periodic_interp", true, false, adjoint, k, StD{D ? 1 : 0, one, ldd}, dt, theta, ncycle, StSched::list(slot_a, slot_b, weight), StSrc{nsrc, S, lds, nullptr},
+                            X, ldx, rtol, maxiter, precond},
+                           use_x0, ptol, restart, maxcycles, outer, cycles, defect, reason, msolve_iters});
 }
 
-// the calls from before the schedule: substeps = 1, the one source or none
+// the calls from before the schedule: substeps = 1, the one source or none, none of the schedule's checks
 int32_t otmb_op_periodic_dk_dev(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle,
                                 int64_t first_slot, const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter,
                                 int32_t precond, double ptol, int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason,
                                 int32_t outer, int64_t *msolve_iters) {
-    if (!op) return OTMB_ERR_INVALID_ARG;
-    const double *const one[1] = {S};
-    const int64_t nsrc = S ? 1 : 0;
-    int32_t rc;
-    if ((rc = pd_check_call(op, "otmb_op_periodic_dk", false, k, D, ldd, dt, theta, ncycle, first_slot, 1, nsrc, one, lds, X, ldx, rtol, maxiter, precond, ptol,
-                            restart, maxcycles, cycles, defect, reason, outer)))
-        return rc;
-    return pd_run_dev(op, adjoint, k, D, ldd, dt, theta, ncycle, first_slot, 1, nsrc, one, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles,
-                      cycles, defect, reason, outer, msolve_iters);
+    const double *const one[1] = {D}, *const src[1] = {S};
+    return pd_call<true>(op, {{"otmb_op_periodic_dk", false, false, adjoint, k, StD{D ? 1 : 0, one, ldd}, dt, theta, ncycle, StSched::cyclic(first_slot, 1), StSrc{S ? 1 : 0, src, lds, nullptr},
+                            X, ldx, rtol, maxiter, precond},
+                           use_x0, ptol, restart, maxcycles, outer, cycles, defect, reason, msolve_iters});
 }
 
 int32_t otmb_op_periodic_dk(otmb_op *op, int32_t adjoint, int64_t k, const double *D, int64_t ldd, double dt, double theta, int64_t ncycle, int64_t first_slot,
                             const double *S, int64_t lds, double *X, int64_t ldx, int32_t use_x0, double rtol, int64_t maxiter, int32_t precond, double ptol,
                             int64_t restart, int64_t maxcycles, int64_t *cycles, double *defect, int32_t *reason, int32_t outer, int64_t *msolve_iters) {
-    if (!op) return OTMB_ERR_INVALID_ARG;
-    const double *const one[1] = {S};
-    const int64_t nsrc = S ? 1 : 0;
-    int32_t rc;
-    if ((rc = pd_check_call(op, "otmb_op_periodic_dk", false, k, D, ldd, dt, theta, ncycle, first_slot, 1, nsrc, one, lds, X, ldx, rtol, maxiter, precond, ptol,
-                            restart, maxcycles, cycles, defect, reason, outer)))
-        return rc;
-    return pd_run_host(op, adjoint, k, D, ldd, dt, theta, ncycle, first_slot, 1, nsrc, one, lds, X, ldx, use_x0, rtol, maxiter, precond, ptol, restart, maxcycles,
-                       cycles, defect, reason, outer, msolve_iters);
+    const double *const one[1] = {D}, *const src[1] = {S};
+    return pd_call<false>(op, {{"otmb_op_periodic_dk", false, false, adjoint, k, StD{D ? 1 : 0, one, ldd}, dt, theta, ncycle, StSched::cyclic(first_slot, 1), StSrc{S ? 1 : 0, src, lds, nullptr},
+                            X, ldx, rtol, maxiter, precond},
+                           use_x0, ptol, restart, maxcycles, outer, cycles, defect, reason, msolve_iters});
 }
 
 // the calls with one d for every column: ldd = 0 (otmb_op_periodic: OTMB_OUTER_NONE as well)

@@ -1,6 +1,7 @@
 // otmb_solve.h -- what the solver (otmb_solve.hip), its line preconditioner (otmb_solve_lines.hip), the step (otmb_step.hip) and the periodic
 // state (otmb_periodic.hip) share: a column's record and state, the register block of right-hand sides, the preconditioner's record, the
-// host entry points around it, the step's argument checks and the report of columns that did not converge.
+// host entry points around it, the step's argument checks, the call records of the step and the periodic state (StCall, PdCall) and the
+// report of columns that did not converge.  The schedule's own types and rules are otmb_sched.h's, which otmb_op.h includes.
 #pragma once
 #include "otmb_op.h"
 
@@ -14,14 +15,7 @@ struct SvCol {  // one column's record (device; the host reads all k of them)
     i64 iters;
 };
 
-// The shift's diagonal part d: n values for every column (ld == 0, or p == null: none), or column c's own n values at p + c·ld (ld >= n):
-// the per-column calls (otmb_op_*_dk).  percol: a column's preconditioner is its own.
-struct SvD {
-    const double *p;
-    i64 ld;
-    bool percol() const { return p && ld != 0; }
-};
-// the checks of D and ldd that the _dk calls add (`call`: the export's name), after the call's other checks and before anything is touched
+// The checks of D and ldd that the _dk calls add (`call`: the export's name), after the call's other checks and before anything is touched
 int32_t sv_check_d(otmb_op *op, const char *call, const double *D, int64_t ldd);
 
 // A preconditioner: sh = σ + d, diag (Jacobi's diagonal) and, for the lines, the multipliers, the pivots and u (m, piv, u: null for
@@ -74,9 +68,6 @@ const char *sv_step_complaint(const otmb_op *op, double rtol, int64_t maxiter, d
                               int64_t first_slot);
 int32_t sv_report_open(otmb_ctx *ctx, const char *fmt, const char *const *names, i64 k, const int32_t *reason, const int64_t *count, const double *value,
                        const std::string &tail = std::string(), int nnames = 4);
-// sv_sched_complaint (otmb_step.hip): the first complaint about a schedule -- substeps, nsrc, the source blocks (S: nsrc pointers) and lds --
-//                  or null: what otmb_op_step_sched and otmb_op_periodic_sched add to the checks of the calls they extend.
-const char *sv_sched_complaint(const otmb_op *op, int64_t substeps, int64_t nsrc, const double *const *S, int64_t lds);
 
 // The solver, its preconditioner and the products read the values op->nz / op->val point at (the selected slot's).  SvValues points them at
 // another value set of the same pattern for its lifetime: sv_prec_prepare and sv_solve on an explicit value set (the periodic state's mean).
@@ -99,29 +90,6 @@ int32_t cb_combine(otmb_op *op, const double *w, const OpSlot &to);
 int32_t ip_reserve(otmb_op *op);
 int32_t ip_blend(otmb_op *op, i64 a, i64 b, double wa, double wb);
 
-// An interpolated schedule (include/otmb.h): step t blends slots a[t] and b[t] with the weight w[t]; three HOST arrays.  st_interp_dev
-// (otmb_step.hip) is otmb_op_step_interp_dev behind its checks, for the periodic driver.
-struct StMix {
-    const int64_t *a, *b;
-    const double *w;
-};
-// sv_interp_complaint (otmb_step.hip): the first complaint about an interpolated schedule of `count` steps and its nsrc, or null (text: at
-//                  least 160 chars of scratch for a message that names an entry).
-//                  per_slot: nsrc may also be the number of slots (otmb_op_*_season); otherwise it is 0 or 1.
-const char *sv_interp_complaint(const otmb_op *op, int64_t count, const StMix &mix, int64_t nsrc, const double *const *S, int64_t lds, char *text,
-                                bool per_slot = false);
-
-// d as a list of blocks (otmb_op_*_season, include/otmb.h): nd = 0 (none), 1 (the block serves every step) or nslots (a block per slot), each
-// n values (ldd == 0) or n x k (ldd >= n); D: a HOST array of nd pointers.  Every other call passes at most one block.
-struct StD {
-    i64 nd;
-    const double *const *D;
-    i64 ldd;
-    SvD at(i64 slot) const { return nd == 0 ? SvD{nullptr, 0} : SvD{D[nd == 1 ? 0 : slot], ldd}; }
-    bool percol() const { return nd > 0 && ldd != 0 && D[0]; }
-};
-// sv_season_complaint (otmb_step.hip): the first complaint about such a list, or null: what the season calls add to the checks.
-const char *sv_season_complaint(const otmb_op *op, int64_t nd, const double *const *D, int64_t ldd);
 
 // The fold of dense blocks (otmb_season.hip): a blended step's d and source, and the cycle-mean d̄.
 // se_reserve: op->season at that many doubles (allocated on first use; may wait for the device).
@@ -140,6 +108,67 @@ int32_t ob_reserve(otmb_op *op, i64 k, i64 q);
 void ob_pass(otmb_op *op, i64 k, i64 q, const double *W, i64 ldw, const double *X, i64 ldx, double *obs, double *Xbar, i64 ldm, double tw, bool first);
 const char *ob_complaint(const otmb_op *op, bool step, i64 nsteps, i64 q, const double *W, i64 ldw, const double *obs, const double *tw, const double *Xbar,
                          i64 ldm);
+
+// What otmb_op_step_obs adds to a step call: q observers W (obs: q x k x nsteps) and the mean's weights and array (null: none).
+struct StObs {
+    i64 q;
+    const double *W;
+    i64 ldw;
+    double *obs;
+    const double *tw;
+    double *Xbar;
+    i64 ldm;
+};
+static const StObs ST_PLAIN = {0, nullptr, 0, nullptr, nullptr, nullptr, 0};  // no observers, no mean
+
+// One stepped call, as every export of otmb_step.hip and otmb_periodic.hip states it.  The head is what the two families share:
+//   call            the export that refusals cite
+//   sched_checks, season   which checks follow the call's own (and sv_check_d, which every call but a season call runs under `call`):
+//                   sched_checks -- the schedule's (sv_sched_complaint, or sv_interp_complaint when the schedule is listed) and the scale's; season -- d is a list
+//                   of blocks: no sv_check_d, a source per slot is in order under a listed schedule, the list's own checks come last
+//   d               at most one block for every call but a season call (a shared d: ldd = 0); per slot, plain steps take their slot's block
+//                   and blended steps the fold of the two slots' blocks
+//   nsteps          the steps of the call, or of the periodic state's cycle
+//   sched           cyclic, or listed: a listed schedule may blend (op->interp, and op->season for fields per slot)
+//   src             nsrc = nslots: a block per slot, picked and folded like d; scale: a factor per step and tracer (never periodic)
+// A record never outlives its call: the arrays it points at may live on the export's stack.
+struct StHead {
+    const char *call;
+    bool sched_checks, season;
+    int32_t adjoint;
+    i64 k;
+    StD d;
+    double dt, theta;
+    i64 nsteps;
+    StSched sched;
+    StSrc src;
+    double *X;
+    i64 ldx;
+    double rtol;
+    i64 maxiter;
+    int32_t precond;
+};
+struct StCall : StHead {  // a step call: the head, the report (nsteps x k, step-major) and the observers (ST_PLAIN: none)
+    int64_t *steps_done, *iters;
+    double *relres;
+    int32_t *reason;
+    StObs obs;
+};
+struct PdCall : StHead {  // a periodic call: the head (nsteps = ncycle), the outer iteration's arguments and its report, one entry per column
+    int32_t use_x0;
+    double ptol;
+    i64 restart, maxcycles;
+    int32_t outer;
+    int64_t *cycles;
+    double *defect;
+    int32_t *reason;
+    int64_t *msolve_iters;
+};
+// (otmb_step.hip) st_check_sched: the checks `sched_checks` and `season` select, the refusal under h.call.
+//                 st_call:        a step call behind its checks; DEV: device pointers (otmb_periodic.hip's cycle is st_call<true>)
+int32_t st_check_sched(otmb_op *op, const StHead &h);
+template <bool DEV>
+int32_t st_call(otmb_op *op, const StCall &c);
 
 // the report of an empty system (n = 0): every entry converged at once
 static inline int32_t sv_report_empty(i64 entries, int64_t *iters, double *relres, int32_t *reason) {

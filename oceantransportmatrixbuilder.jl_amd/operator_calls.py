@@ -320,21 +320,34 @@ class OperatorCalls:
         pc = capi.precond_code(precond)
         X, k, Xc, _ = self._state(X, "X")
         dc, dargs = self._d(d, X, "X")
-        (m, n), ld = self.shape, max(self.shape[0], 1)
-        Sc, lds, blocks = None, ld, None
+        Sc, lds, blocks = None, max(self.shape[0], 1), None
         if isinstance(source, (list, tuple)):
             blocks, lds = self._sources(source, X, "X")
         elif source is not None:
-            Sc, lds = self._matrix(self._like(source, "source", X, "X"), m)
+            Sc, lds = self._matrix(self._like(source, "source", X, "X"), self.shape[0])
+        sched = blocks is not None or source_scale is not None or int(substeps) != 1
+        if sched:  # the schedule in place of S, lds; one d for every tracer is ldd = 0
+            dargs = dargs if len(dargs) == 2 else dargs + [0]
+        record = sched or len(dargs) == 2 or observe is not None or time_weights is not None
+        name = "otmb_op_step_sched" if sched else "otmb_op_step_dk" if len(dargs) == 2 else "otmb_op_step_obs" if record else "otmb_op_step"
+        return self._step_call(name, X, k, Xc, dargs, nsteps, [int(first_slot), int(substeps)] if sched else [int(first_slot)],
+                               ([] if Sc is None else [Sc]) if blocks is None else blocks, lds, dt=dt, theta=theta, source_scale=source_scale, rtol=rtol,
+                               maxiter=maxiter, adjoint=adjoint, pc=pc, observe=observe, time_weights=time_weights, listed=sched, record=record)
+
+    def _step_call(self, name, X, k, Xc, dargs, nsteps, sched_args, blocks, lds, *, dt, theta, source_scale, rtol, maxiter, adjoint, pc, observe,
+                   time_weights, listed=True, record=True):
+        """What every step method does once its d (dargs), its schedule (sched_args, behind nsteps in the export's list) and its source blocks
+        are marshalled: the scale, the observers and the mean's weights, the copy of the state, the report arrays, the call and its StepInfo.
+        listed: the source goes as nsrc, S, lds, scale (the scheduled exports), otherwise as S, lds; record: the export takes the observers."""
+        n, ld = self.shape[1], max(self.shape[0], 1)
         scale = None
         if source_scale is not None:
-            if source is None:
+            if not blocks:
                 raise capi.OtmbError(11, "invalid argument: source_scale needs a source")
             scale = np.ascontiguousarray(source_scale, dtype=np.float64)
             want = (max(int(nsteps), 0),) + tuple(X.shape[1:])
             if scale.shape != want:
                 raise capi.OtmbError(11, f"DimensionMismatch: source_scale of {scale.shape}, expected {want}")
-        sched = blocks is not None or scale is not None or int(substeps) != 1
         q, Wc, ldw, obs, tw, mean = 0, None, max(n, 1), None, None, None
         if observe is not None:
             W, q = observers(self._array(observe, "observe"), n)
@@ -347,15 +360,12 @@ class OperatorCalls:
         self._assign(Xn, Xc)
         iters, relres, reason = step_arrays(nsteps, k)
         done = C.c_int64(0)
-        if sched:  # the schedule in place of S, lds; one d for every tracer is ldd = 0
-            dargs = dargs if len(dargs) == 2 else dargs + [0]
-            sargs = [int(substeps), *self._source_args([Sc] if blocks is None and Sc is not None else blocks, lds), None if scale is None else scale.ctypes.data]
+        if listed:
+            sargs = [*self._source_args(blocks, lds), None if scale is None else scale.ctypes.data]
         else:
-            sargs = [self._ptr(Sc), lds]
-        args = [int(bool(adjoint)), k, *dargs, float(dt), float(theta), int(nsteps), int(first_slot), *sargs, self._ptr(Xn), ld, float(rtol),
-                int(maxiter), pc, C.byref(done), iters.ctypes.data, relres.ctypes.data, reason.ctypes.data]
-        record = sched or len(dargs) == 2 or obs is not None or tw is not None
-        name = "otmb_op_step_sched" if sched else "otmb_op_step_dk" if len(dargs) == 2 else "otmb_op_step_obs" if record else "otmb_op_step"
+            sargs = [self._ptr(blocks[0] if blocks else None), lds]
+        args = [int(bool(adjoint)), k, *dargs, float(dt), float(theta), int(nsteps), *sched_args, *sargs, self._ptr(Xn), ld, float(rtol), int(maxiter), pc,
+                C.byref(done), iters.ctypes.data, relres.ctypes.data, reason.ctypes.data]
         if record:  # the record's arguments; q = 0 and nulls make the per-column call the plain step
             args += [q, self._ptr(Wc), ldw, self._ptr(obs), None if tw is None else tw.ctypes.data, self._ptr(mean), ld]
         rc = self._call(name, *args)
@@ -385,15 +395,13 @@ class OperatorCalls:
             raise capi.OtmbError(11, "invalid argument: weight must be finite and in [0, 1]")
         return a, b, w, int(w.shape[0])
 
-    def _one_source(self, source, B, of):
-        """(the source block column-major or None, lds) of the interpolated calls: None, an array of B's shape, or a list or tuple of ONE."""
+    def _one_source(self, source):
+        """The source of the interpolated calls as they take it -- None, an array, or a list or tuple of ONE -- without its wrapping."""
         if isinstance(source, (list, tuple)):
             if len(source) != 1:
                 raise capi.OtmbError(11, f"DimensionMismatch: {len(source)} source blocks, expected 1 (a source per slot is not built with interpolation)")
             source = source[0]
-        if source is None:
-            return None, max(self.shape[0], 1)
-        return self._matrix(self._like(source, "source", B, of), self.shape[0])
+        return source
 
     def step_interp(self, X, *, dt, slot_a, slot_b, weight, theta=1.0, source=None, source_scale=None, d=None, rtol=1e-10, maxiter=10000,
                     adjoint=False, precond="jacobi", observe=None, time_weights=None):
@@ -408,34 +416,11 @@ class OperatorCalls:
         X, k, Xc, _ = self._state(X, "X")
         dc, dargs = self._d(d, X, "X")
         sa, sb, w, nsteps = self._interp(slot_a, slot_b, weight)
-        (m, n), ld = self.shape, max(self.shape[0], 1)
-        Sc, lds = self._one_source(source, X, "X")
-        scale = None
-        if source_scale is not None:
-            if Sc is None:
-                raise capi.OtmbError(11, "invalid argument: source_scale needs a source")
-            scale = np.ascontiguousarray(source_scale, dtype=np.float64)
-            want = (nsteps,) + tuple(X.shape[1:])
-            if scale.shape != want:
-                raise capi.OtmbError(11, f"DimensionMismatch: source_scale of {scale.shape}, expected {want}")
-        q, Wc, ldw, obs, tw, mean = 0, None, max(n, 1), None, None, None
-        if observe is not None:
-            W, q = observers(self._array(observe, "observe"), n)
-            Wc, ldw = self._matrix(W, n)
-            obs = self._zeros((nsteps, k, q), "C")
-        if time_weights is not None:
-            tw = _as_weights(time_weights, nsteps)
-            mean = self._zeros(tuple(X.shape))
-        Xn = self._zeros(tuple(X.shape))
-        self._assign(Xn, Xc)
-        iters, relres, reason = step_arrays(nsteps, k)
-        done = C.c_int64(0)
-        dargs = dargs if len(dargs) == 2 else dargs + [0]
-        rc = self._call("otmb_op_step_interp", int(bool(adjoint)), k, *dargs, float(dt), float(theta), nsteps, sa.ctypes.data, sb.ctypes.data, w.ctypes.data,
-                        *self._source_args([] if Sc is None else [Sc], lds), None if scale is None else scale.ctypes.data, self._ptr(Xn), ld, float(rtol),
-                        int(maxiter), pc, C.byref(done), iters.ctypes.data, relres.ctypes.data, reason.ctypes.data, q, self._ptr(Wc), ldw, self._ptr(obs),
-                        None if tw is None else tw.ctypes.data, self._ptr(mean), ld)
-        return Xn, StepInfo(self._status(rc), done.value, nsteps, iters, relres, reason, obs, mean)
+        source = self._one_source(source)
+        Sc, lds = (None, max(self.shape[0], 1)) if source is None else self._matrix(self._like(source, "source", X, "X"), self.shape[0])
+        return self._step_call("otmb_op_step_interp", X, k, Xc, dargs if len(dargs) == 2 else dargs + [0], nsteps, [sa.ctypes.data, sb.ctypes.data, w.ctypes.data],
+                               [] if Sc is None else [Sc], lds, dt=dt, theta=theta, source_scale=source_scale, rtol=rtol, maxiter=maxiter, adjoint=adjoint, pc=pc,
+                               observe=observe, time_weights=time_weights)
 
     def periodic_interp(self, source, *, dt, slot_a, slot_b, weight, theta=1.0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False,
                         precond="jacobi", ptol=1e-8, restart=30, maxcycles=1000, outer="none"):
@@ -446,21 +431,12 @@ class OperatorCalls:
         oc = capi.outer_code(outer)
         self._live()
         pc = capi.precond_code(precond)
-        if isinstance(source, (list, tuple)):
-            if len(source) != 1:
-                raise capi.OtmbError(11, f"DimensionMismatch: {len(source)} source blocks, expected 1 (a source per slot is not built with interpolation)")
-            source = source[0]
-        S, k, Sc, lds = self._state(source, "source")
+        S, k, Sc, lds = self._state(self._one_source(source), "source")
         sa, sb, w, ncycle = self._interp(slot_a, slot_b, weight)
         dc, dargs = self._d(d, S, "source")
-        dargs = dargs if len(dargs) == 2 else dargs + [0]
-        X = self._start(x0, S, "source")
-        cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
-        msolve = np.zeros(k, dtype=np.int64)
-        rc = self._call("otmb_op_periodic_interp", int(bool(adjoint)), k, *dargs, float(dt), float(theta), ncycle, sa.ctypes.data, sb.ctypes.data,
-                        w.ctypes.data, *self._source_args([Sc], lds), self._ptr(X), max(self.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), pc,
-                        float(ptol), int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data, reason.ctypes.data, oc, msolve.ctypes.data)
-        return X, PeriodicInfo(self._status(rc), cycles, defect, reason, msolve)
+        return self._periodic_call("otmb_op_periodic_interp", S, k, dargs if len(dargs) == 2 else dargs + [0], ncycle, [sa.ctypes.data, sb.ctypes.data, w.ctypes.data],
+                                   self._source_args([Sc], lds), dt=dt, theta=theta, x0=x0, rtol=rtol, maxiter=maxiter, adjoint=adjoint, pc=pc, ptol=ptol,
+                                   restart=restart, maxcycles=maxcycles, oc=oc)
 
     def _ds(self, d, B, what):
         """(what keeps the blocks alive, [nd, the array of the blocks' addresses or None, ldd]) of the season calls' d: None, n values, an array
@@ -502,6 +478,18 @@ class OperatorCalls:
             raise capi.OtmbError(11, "DimensionMismatch: 0 source blocks, expected 1 or one per slot")
         return self._sources(source, B, of)
 
+    def _periodic_sources(self, source):
+        """(the first block as given, k, it column-major, the blocks' lds, the blocks column-major) of a periodic call's source: an array of
+        the state's shape, or a list or tuple of one or nslots such arrays."""
+        if not isinstance(source, (list, tuple)):
+            S, k, Sc, lds = self._state(source, "source")
+            return S, k, Sc, lds, [Sc]
+        if not source:
+            raise capi.OtmbError(11, "DimensionMismatch: 0 source blocks, expected 1 or one per slot")
+        S, k, Sc, _ = self._state(source[0], "source")
+        blocks, lds = self._sources(source, S, "source")
+        return S, k, Sc, lds, blocks
+
     def step_season(self, X, *, dt, slot_a, slot_b, weight, theta=1.0, d=None, source=None, source_scale=None, rtol=1e-10, maxiter=10000,
                     adjoint=False, precond="jacobi", observe=None, time_weights=None):
         """step_interp with d and the source per slot as well (otmb_op_step_season; include/otmb.h states the contract): every per-step field
@@ -516,33 +504,9 @@ class OperatorCalls:
         X, k, Xc, _ = self._state(X, "X")
         dkeep, dargs = self._ds(d, X, "X")
         sa, sb, w, nsteps = self._interp(slot_a, slot_b, weight)
-        (m, n), ld = self.shape, max(self.shape[0], 1)
         blocks, lds = self._season_sources(source, X, "X")
-        scale = None
-        if source_scale is not None:
-            if not blocks:
-                raise capi.OtmbError(11, "invalid argument: source_scale needs a source")
-            scale = np.ascontiguousarray(source_scale, dtype=np.float64)
-            want = (nsteps,) + tuple(X.shape[1:])
-            if scale.shape != want:
-                raise capi.OtmbError(11, f"DimensionMismatch: source_scale of {scale.shape}, expected {want}")
-        q, Wc, ldw, obs, tw, mean = 0, None, max(n, 1), None, None, None
-        if observe is not None:
-            W, q = observers(self._array(observe, "observe"), n)
-            Wc, ldw = self._matrix(W, n)
-            obs = self._zeros((nsteps, k, q), "C")
-        if time_weights is not None:
-            tw = _as_weights(time_weights, nsteps)
-            mean = self._zeros(tuple(X.shape))
-        Xn = self._zeros(tuple(X.shape))
-        self._assign(Xn, Xc)
-        iters, relres, reason = step_arrays(nsteps, k)
-        done = C.c_int64(0)
-        rc = self._call("otmb_op_step_season", int(bool(adjoint)), k, *dargs, float(dt), float(theta), nsteps, sa.ctypes.data, sb.ctypes.data, w.ctypes.data,
-                        *self._source_args(blocks, lds), None if scale is None else scale.ctypes.data, self._ptr(Xn), ld, float(rtol), int(maxiter), pc,
-                        C.byref(done), iters.ctypes.data, relres.ctypes.data, reason.ctypes.data, q, self._ptr(Wc), ldw, self._ptr(obs),
-                        None if tw is None else tw.ctypes.data, self._ptr(mean), ld)
-        return Xn, StepInfo(self._status(rc), done.value, nsteps, iters, relres, reason, obs, mean)
+        return self._step_call("otmb_op_step_season", X, k, Xc, dargs, nsteps, [sa.ctypes.data, sb.ctypes.data, w.ctypes.data], blocks, lds, dt=dt, theta=theta,
+                               source_scale=source_scale, rtol=rtol, maxiter=maxiter, adjoint=adjoint, pc=pc, observe=observe, time_weights=time_weights)
 
     def periodic_season(self, source, *, dt, slot_a, slot_b, weight, theta=1.0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False,
                         precond="jacobi", ptol=1e-8, restart=30, maxcycles=1000, outer="none"):
@@ -554,23 +518,12 @@ class OperatorCalls:
         oc = capi.outer_code(outer)
         self._live()
         pc = capi.precond_code(precond)
-        if isinstance(source, (list, tuple)):
-            if not source:
-                raise capi.OtmbError(11, "DimensionMismatch: 0 source blocks, expected 1 or one per slot")
-            S, k, Sc, lds = self._state(source[0], "source")
-            blocks, lds = self._sources(source, S, "source")
-        else:
-            S, k, Sc, lds = self._state(source, "source")
-            blocks = [Sc]
+        S, k, Sc, lds, blocks = self._periodic_sources(source)
         sa, sb, w, ncycle = self._interp(slot_a, slot_b, weight)
         dkeep, dargs = self._ds(d, S, "source")
-        X = self._start(x0, S, "source")
-        cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
-        msolve = np.zeros(k, dtype=np.int64)
-        rc = self._call("otmb_op_periodic_season", int(bool(adjoint)), k, *dargs, float(dt), float(theta), ncycle, sa.ctypes.data, sb.ctypes.data,
-                        w.ctypes.data, *self._source_args(blocks, lds), self._ptr(X), max(self.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), pc,
-                        float(ptol), int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data, reason.ctypes.data, oc, msolve.ctypes.data)
-        return X, PeriodicInfo(self._status(rc), cycles, defect, reason, msolve)
+        return self._periodic_call("otmb_op_periodic_season", S, k, dargs, ncycle, [sa.ctypes.data, sb.ctypes.data, w.ctypes.data], self._source_args(blocks, lds),
+                                   dt=dt, theta=theta, x0=x0, rtol=rtol, maxiter=maxiter, adjoint=adjoint, pc=pc, ptol=ptol, restart=restart, maxcycles=maxcycles,
+                                   oc=oc)
 
     def periodic(self, source, *, dt, ncycle, theta=1.0, first_slot=0, d=None, x0=None, rtol=1e-10, maxiter=10000, adjoint=False, precond="jacobi",
                  ptol=1e-8, restart=30, maxcycles=1000, outer="none"):
@@ -598,28 +551,29 @@ class OperatorCalls:
         oc = capi.outer_code(outer)
         self._live()
         pc = capi.precond_code(precond)
-        blocks = None
-        if isinstance(source, (list, tuple)):
-            if not source:
-                raise capi.OtmbError(11, "DimensionMismatch: 0 source blocks, expected 1 or one per slot")
-            S, k, Sc, lds = self._state(source[0], "source")
-            blocks, lds = self._sources(source, S, "source")
-        else:
-            S, k, Sc, lds = self._state(source, "source")
-        sched = blocks is not None or int(substeps) != 1
+        S, k, Sc, lds, blocks = self._periodic_sources(source)
+        sched = isinstance(source, (list, tuple)) or int(substeps) != 1
         dc, dargs = self._d(d, S, "source")
-        X = self._start(x0, S, "source")
-        cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
         if sched:  # the schedule in place of S, lds; one d for every column is ldd = 0
             dargs = dargs if len(dargs) == 2 else dargs + [0]
-            sargs = [int(substeps), *self._source_args([Sc] if blocks is None else blocks, lds)]
+            sargs = [int(first_slot), int(substeps), *self._source_args(blocks, lds)]
         else:
-            sargs = [self._ptr(Sc), lds]
-        args = [int(bool(adjoint)), k, *dargs, float(dt), float(theta), int(ncycle), int(first_slot), *sargs, self._ptr(X),
-                max(self.shape[0], 1), int(x0 is not None), float(rtol), int(maxiter), pc, float(ptol), int(restart), int(maxcycles), cycles.ctypes.data,
-                defect.ctypes.data, reason.ctypes.data]
+            sargs = [int(first_slot), self._ptr(Sc), lds]
         outer_args = sched or len(dargs) == 2 or oc != capi.OUTERS["none"]
         name = "otmb_op_periodic_sched" if sched else "otmb_op_periodic_dk" if len(dargs) == 2 else "otmb_op_periodic_pc" if outer_args else "otmb_op_periodic"
+        return self._periodic_call(name, S, k, dargs, ncycle, sargs, [], dt=dt, theta=theta, x0=x0, rtol=rtol, maxiter=maxiter, adjoint=adjoint, pc=pc, ptol=ptol,
+                                   restart=restart, maxcycles=maxcycles, oc=oc, outer_args=outer_args)
+
+    def _periodic_call(self, name, S, k, dargs, ncycle, sched_args, source_args, *, dt, theta, x0, rtol, maxiter, adjoint, pc, ptol, restart, maxcycles, oc,
+                       outer_args=True):
+        """What every periodic method does once its source (S: the state-shaped first block), its d, its schedule and its source arguments
+        (sched_args, source_args: behind ncycle in the export's list) are marshalled: the start, the report arrays, the call and its
+        PeriodicInfo.  outer_args: the export takes outer and msolve_iters."""
+        X = self._start(x0, S, "source")
+        cycles, defect, reason = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32)
+        args = [int(bool(adjoint)), k, *dargs, float(dt), float(theta), int(ncycle), *sched_args, *source_args, self._ptr(X), max(self.shape[0], 1),
+                int(x0 is not None), float(rtol), int(maxiter), pc, float(ptol), int(restart), int(maxcycles), cycles.ctypes.data, defect.ctypes.data,
+                reason.ctypes.data]
         msolve = None
         if outer_args:
             msolve = np.zeros(k, dtype=np.int64)

@@ -41,6 +41,11 @@ def kind(a, b, w):
     return "blend", None
 
 
+def prec_blocks(kinds):
+    """The preconditioners a call keeps for steps of these kinds: one per slot its plain steps visit, and one that every blended step shares."""
+    return len({slot for what, slot in kinds if what == "plain"}) + int(any(what == "blend" for what, _ in kinds))
+
+
 def combine_weights(nslots, a, b, w):
     """The weights of the chain's combine_slots call for a blended step: 1.0 - w at a, w at b, zero elsewhere."""
     wt = np.zeros(nslots)
