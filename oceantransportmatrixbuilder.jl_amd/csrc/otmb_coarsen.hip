@@ -24,16 +24,13 @@
 //                sparse(I, J, V) (otmb_coo.hip); one path per call keeps the output positions a plain scan in both.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
-#include "otmb_common.h"
+#include "otmb_prims.h"
 
 #define CO_SEQ_BITS 12                      // iteration index inside a column (< CO_MAX_CAP)
 #define CO_MAX_CAP 2048                     // largest per-column work of the small path (LDS: 22 B per contribution)
 #define CO_MAX_ROW (1ll << (64 - CO_SEQ_BITS - 1))
 enum { CO_BAD_AP = 1, CO_BAD_MULTI = 2, CO_BAD_AI = 4, CO_BAD_BP = 8, CO_BAD_BI = 16, CO_BAD_SP = 32, CO_BAD_SI = 64 };
-#define CO_GRID(n) dim3((unsigned)(((n) + 255) / 256 < 65536 ? (((n) + 255) / 256 > 0 ? ((n) + 255) / 256 : 1) : 65536)), dim3(256), 0, ctx->stream
+#define CO_GRID(n) OTMB_GRID_STRIDE(n, ctx->stream)  // (every 256-thread kernel of this file strides over the grid)
 
 struct CoArgs {
     const i64 *Ap, *Ai, *Bp, *Bi, *Sp, *Si;
@@ -252,19 +249,6 @@ __global__ __launch_bounds__(256) void co_sorted_fill_kernel(const u64 *__restri
 
 __global__ void co_one_kernel(i64 *p) { p[0] = 1; }
 
-static int32_t co_scan(otmb_ctx *ctx, const i64 *in, i64 *out, i64 n, bool inclusive) {
-    size_t tmp = 0;
-    hipError_t e = inclusive ? rocprim::inclusive_scan(nullptr, tmp, in, out, (size_t)n, rocprim::plus<i64>(), ctx->stream)
-                             : rocprim::exclusive_scan(nullptr, tmp, in, out, (i64)0, (size_t)n, rocprim::plus<i64>(), ctx->stream);
-    if (e != hipSuccess) return otmb_fail(ctx, OTMB_ERR_HIP, "scan (size)");
-    int32_t rc;
-    if ((rc = otmb_reserve(ctx, ctx->co[9], tmp + 16))) return rc;
-    e = inclusive ? rocprim::inclusive_scan(ctx->co[9].p, tmp, in, out, (size_t)n, rocprim::plus<i64>(), ctx->stream)
-                  : rocprim::exclusive_scan(ctx->co[9].p, tmp, in, out, (i64)0, (size_t)n, rocprim::plus<i64>(), ctx->stream);
-    if (e != hipSuccess) return otmb_fail(ctx, OTMB_ERR_HIP, "scan");
-    return OTMB_OK;
-}
-
 static CoArgs co_args(const otmb_ctx::CoPlan &p) { return CoArgs{p.Ap, p.Ai, p.Bp, p.Bi, p.Sp, p.Si, p.Ax, p.Bx, p.Sx}; }
 
 template <bool WRITE>
@@ -275,12 +259,6 @@ static void co_small_launch(otmb_ctx *ctx, int cap, const CoArgs &a, const i64 *
         case 256: hipLaunchKernelGGL((co_small_kernel<256, WRITE>), g, b, 0, ctx->stream, a, woff, cnt, colptr, Ci, Cx); break;
         default: hipLaunchKernelGGL((co_small_kernel<CO_MAX_CAP, WRITE>), g, b, 0, ctx->stream, a, woff, cnt, colptr, Ci, Cx); break;
     }
-}
-
-static int co_bits(i64 v) {  // bits v needs: v < 2^bits
-    int b = 1;
-    while (b < 63 && (v >> b) != 0) ++b;
-    return b;
 }
 
 extern "C" {
@@ -309,13 +287,13 @@ int32_t otmb_coarsen_plan_dev(otmb_ctx *ctx, int64_t m, int64_t N, const int64_t
     if (ends[4] != 1 || nS < 0) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "SPRAY: colptr");
     if ((nA > 0 && (!Ai || !Ax)) || (nB > 0 && (!Bi || !Bx)) || (nS > 0 && (!Si || !Sx))) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
     int32_t rc;
-    // co[0]: flags (bad bits, wmax) | co[1]: w / woff (nS + 1) | co[2]: cnt (n + 1) | co[3]: colptr (n + 1) | co[4..8]: sorted path
-    if ((rc = otmb_reserve(ctx, ctx->co[0], 64))) return rc;
-    if ((rc = otmb_reserve(ctx, ctx->co[1], (size_t)(nS + 1) * 16 + 16))) return rc;
-    unsigned *bad = (unsigned *)ctx->co[0].p;
-    unsigned long long *wmax = (unsigned long long *)((char *)ctx->co[0].p + 8);
-    i64 *w = (i64 *)ctx->co[1].p, *woff = w + (nS + 1);
-    HIP_TRY(ctx, hipMemsetAsync(ctx->co[0].p, 0, 16, ctx->stream));
+    otmb_ctx::CoScratch &S = ctx->co;  // (otmb_common.h says what each member holds)
+    if ((rc = otmb_reserve(ctx, S.flags, 64))) return rc;
+    if ((rc = otmb_reserve(ctx, S.woff, (size_t)(nS + 1) * 16 + 16))) return rc;
+    unsigned *bad = (unsigned *)S.flags.p;
+    unsigned long long *wmax = (unsigned long long *)((char *)S.flags.p + 8);
+    i64 *w = (i64 *)S.woff.p, *woff = w + (nS + 1);
+    HIP_TRY(ctx, hipMemsetAsync(S.flags.p, 0, 16, ctx->stream));
     if (N > 0) hipLaunchKernelGGL(co_check_colptr_kernel, CO_GRID(N), (const i64 *)Ap, (i64)N, (i64)nA, 1, (unsigned)CO_BAD_AP, bad);
     if (M > 0) hipLaunchKernelGGL(co_check_colptr_kernel, CO_GRID(M), (const i64 *)Bp, (i64)M, (i64)nB, -1, (unsigned)CO_BAD_BP, bad);
     if (n > 0) hipLaunchKernelGGL(co_check_colptr_kernel, CO_GRID(n), (const i64 *)Sp, (i64)n, (i64)nS, -1, (unsigned)CO_BAD_SP, bad);
@@ -324,12 +302,12 @@ int32_t otmb_coarsen_plan_dev(otmb_ctx *ctx, int64_t m, int64_t N, const int64_t
     if (nS > 0) hipLaunchKernelGGL(co_check_rowval_kernel, CO_GRID(nS), (const i64 *)Si, (i64)nS, (i64)M, (unsigned)CO_BAD_SI, bad);
     // (the kernels below return at once when a check failed: they would dereference the offending index)
     hipLaunchKernelGGL(co_width_kernel, CO_GRID(nS + 1), (const i64 *)Si, (const i64 *)Bp, (i64)nS, (const unsigned *)bad, w);
-    if ((rc = co_scan(ctx, w, woff, nS + 1, false))) return rc;
+    if ((rc = otmb_exclusive_scan(ctx, S.prim_tmp, w, woff, nS + 1))) return rc;
     if (n > 0) hipLaunchKernelGGL(co_colwork_kernel, CO_GRID(n), (const i64 *)Sp, (const i64 *)woff, (i64)n, (const unsigned *)bad, wmax);
     HIP_TRY(ctx, hipGetLastError());
     unsigned long long st[2] = {0, 0};
     i64 total = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(st, ctx->co[0].p, 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(st, S.flags.p, 16, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(&total, woff + nS, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const unsigned b = (unsigned)st[0];
@@ -345,36 +323,29 @@ int32_t otmb_coarsen_plan_dev(otmb_ctx *ctx, int64_t m, int64_t N, const int64_t
     p.Ap = Ap; p.Ai = Ai; p.Ax = Ax; p.Bp = Bp; p.Bi = Bi; p.Bx = Bx; p.Sp = Sp; p.Si = Si; p.Sx = Sx;
     p.m = m; p.N = N; p.M = M; p.n = n; p.nS = nS; p.len = total;
     p.cap = work <= 64 ? 64 : work <= 256 ? 256 : work <= CO_MAX_CAP ? CO_MAX_CAP : 0;
-    if ((rc = otmb_reserve(ctx, ctx->co[2], (size_t)(n + 1) * 8))) return rc;
-    if ((rc = otmb_reserve(ctx, ctx->co[3], (size_t)(n + 1) * 8))) return rc;
-    i64 *cnt = (i64 *)ctx->co[2].p, *colptr = (i64 *)ctx->co[3].p;
+    if ((rc = otmb_reserve(ctx, S.cnt, (size_t)(n + 1) * 8))) return rc;
+    if ((rc = otmb_reserve(ctx, S.colptr, (size_t)(n + 1) * 8))) return rc;
+    i64 *cnt = (i64 *)S.cnt.p, *colptr = (i64 *)S.colptr.p;
     const CoArgs a = co_args(p);
     if (p.cap > 0) {
         hipLaunchKernelGGL(co_one_kernel, dim3(1), dim3(1), 0, ctx->stream, cnt);
         if (n > 0) co_small_launch<false>(ctx, p.cap, a, woff, n, cnt, nullptr, nullptr, nullptr);
-        if ((rc = co_scan(ctx, cnt, colptr, n + 1, true))) return rc;  // colptr[J] = 1 + Σ_{J' < J} cnt
+        if ((rc = otmb_inclusive_scan(ctx, S.prim_tmp, cnt, colptr, n + 1))) return rc;  // colptr[J] = 1 + Σ_{J' < J} cnt
     } else {
         const i64 L = total;
-        const int rowbits = co_bits(m), colbits = co_bits(n + 1);
+        const int rowbits = otmb_bits(m), colbits = otmb_bits(n + 1);
         if (rowbits + colbits > 64) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "matrix too large for 64-bit (column, row) sort keys");
         const u64 invalid = (rowbits + colbits == 64) ? ~0ull : (1ull << (rowbits + colbits)) - 1ull;
-        for (int q = 4; q <= 7; ++q)
-            if ((rc = otmb_reserve(ctx, ctx->co[q], (size_t)L * 16 + 16))) return rc;
-        if ((rc = otmb_reserve(ctx, ctx->co[8], (size_t)(L + 1) * 16 + 16))) return rc;
-        u64 *k0 = (u64 *)ctx->co[4].p, *k1 = k0 + L, *v0 = (u64 *)ctx->co[5].p, *v1 = v0 + L;
-        double *val = (double *)ctx->co[6].p;
-        i64 *sid = (i64 *)ctx->co[7].p, *h = (i64 *)ctx->co[8].p, *hr = h + (L + 1);
+        for (DevBuf *b : {&S.keys, &S.idx, &S.val, &S.sid})
+            if ((rc = otmb_reserve(ctx, *b, (size_t)L * 16 + 16))) return rc;
+        if ((rc = otmb_reserve(ctx, S.heads, (size_t)(L + 1) * 16 + 16))) return rc;
+        u64 *k0 = (u64 *)S.keys.p, *k1 = k0 + L, *v0 = (u64 *)S.idx.p, *v1 = v0 + L;
+        double *val = (double *)S.val.p;
+        i64 *sid = (i64 *)S.sid.p, *h = (i64 *)S.heads.p, *hr = h + (L + 1);
         if (nS > 0) hipLaunchKernelGGL(co_expand_kernel, CO_GRID(nS), a, (const i64 *)woff, (i64)nS, (i64)n, rowbits, invalid, k0, v0, val, sid);
-        if (L > 0) {
-            size_t tmp = 0;
-            if (rocprim::radix_sort_pairs(nullptr, tmp, k0, k1, v0, v1, (size_t)L, 0, (unsigned)(rowbits + colbits), ctx->stream) != hipSuccess)
-                return otmb_fail(ctx, OTMB_ERR_HIP, "radix_sort_pairs (size)");
-            if ((rc = otmb_reserve(ctx, ctx->co[9], tmp + 16))) return rc;
-            if (rocprim::radix_sort_pairs(ctx->co[9].p, tmp, k0, k1, v0, v1, (size_t)L, 0, (unsigned)(rowbits + colbits), ctx->stream) != hipSuccess)
-                return otmb_fail(ctx, OTMB_ERR_HIP, "radix_sort_pairs");
-        }
+        if (L > 0 && (rc = otmb_sort_pairs(ctx, S.prim_tmp, k0, k1, v0, v1, L, rowbits + colbits))) return rc;
         hipLaunchKernelGGL(co_heads_kernel, CO_GRID(L + 1), (const u64 *)k1, (i64)L, invalid, h);
-        if ((rc = co_scan(ctx, h, hr, L + 1, false))) return rc;
+        if ((rc = otmb_exclusive_scan(ctx, S.prim_tmp, h, hr, L + 1))) return rc;
         hipLaunchKernelGGL(co_sorted_colptr_kernel, CO_GRID(n + 1), (const u64 *)k1, (const i64 *)hr, (i64)L, (i64)n, rowbits, colptr);
         p.rowbits = rowbits;
         p.invalid = invalid;
@@ -395,17 +366,18 @@ int32_t otmb_coarsen_fill_dev(otmb_ctx *ctx, int64_t *Cp, int64_t *Ci, double *C
     if (!Cp || (p.nnz > 0 && (!Ci || !Cx))) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null output");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const i64 n = p.n;
-    const i64 *colptr = (const i64 *)ctx->co[3].p;
+    const otmb_ctx::CoScratch &S = ctx->co;
+    const i64 *colptr = (const i64 *)S.colptr.p;
     const CoArgs a = co_args(p);
     if (p.nnz > 0) {
         if (p.cap > 0) {
-            const i64 *woff = (const i64 *)ctx->co[1].p + (p.nS + 1);  // (behind w)
+            const i64 *woff = (const i64 *)S.woff.p + (p.nS + 1);  // (behind w)
             co_small_launch<true>(ctx, p.cap, a, woff, n, nullptr, colptr, (i64 *)Ci, Cx);
         } else {
             const i64 L = p.len;
-            const u64 *k1 = (const u64 *)ctx->co[4].p + L, *v1 = (const u64 *)ctx->co[5].p + L;
-            const i64 *hr = (const i64 *)ctx->co[8].p + (L + 1);
-            hipLaunchKernelGGL(co_sorted_fill_kernel, CO_GRID(L), k1, v1, (const double *)ctx->co[6].p, (const i64 *)ctx->co[7].p, hr, L, p.invalid,
+            const u64 *k1 = (const u64 *)S.keys.p + L, *v1 = (const u64 *)S.idx.p + L;
+            const i64 *hr = (const i64 *)S.heads.p + (L + 1);
+            hipLaunchKernelGGL(co_sorted_fill_kernel, CO_GRID(L), k1, v1, (const double *)S.val.p, (const i64 *)S.sid.p, hr, L, p.invalid,
                                p.rowbits, p.Sx, (i64 *)Ci, Cx);
         }
     }
@@ -429,13 +401,12 @@ int32_t otmb_coarsen_plan(otmb_ctx *ctx, int64_t m, int64_t N, const int64_t *Ap
     if (Sp[0] != 1 || nS < 0) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "SPRAY: colptr");
     if ((nA > 0 && (!Ai || !Ax)) || (nB > 0 && (!Bi || !Bx)) || (nS > 0 && (!Si || !Sx))) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_ap = take((size_t)(N + 1) * 8), o_ai = take((size_t)nA * 8), o_ax = take((size_t)nA * 8), o_bp = take((size_t)(M + 1) * 8),
-                 o_bi = take((size_t)nB * 8), o_bx = take((size_t)nB * 8), o_sp = take((size_t)(n + 1) * 8), o_si = take((size_t)nS * 8),
-                 o_sx = take((size_t)nS * 8);
+    DevArena R;
+    const size_t o_ap = R.take((size_t)(N + 1) * 8), o_ai = R.take((size_t)nA * 8), o_ax = R.take((size_t)nA * 8), o_bp = R.take((size_t)(M + 1) * 8),
+                 o_bi = R.take((size_t)nB * 8), o_bx = R.take((size_t)nB * 8), o_sp = R.take((size_t)(n + 1) * 8), o_si = R.take((size_t)nS * 8),
+                 o_sx = R.take((size_t)nS * 8);
     int32_t rc;
-    if ((rc = otmb_reserve(ctx, ctx->co_host, off + 256))) return rc;
+    if ((rc = otmb_reserve(ctx, ctx->co_host, R.total() + 256))) return rc;
     char *d = (char *)ctx->co_host.p;
     const struct { size_t o; const void *h; size_t bytes; } up[9] = {
         {o_ap, Ap, (size_t)(N + 1) * 8}, {o_ai, Ai, (size_t)nA * 8}, {o_ax, Ax, (size_t)nA * 8},

@@ -25,6 +25,11 @@ struct OtmbXfer;  // otmb_xfer.h: pinned staging ring + host copy threads of the
 // pending plan of the general path (otmb_coo.hip): COO generator and sparse()
 struct CooPlan { int which = -1; otmb_tm_args args; int64_t ntiles = 0, len = 0; };
 struct SpPlan { const int64_t *I = nullptr, *J = nullptr; const double *V = nullptr; int64_t len = -1, m = 0, n = 0, nnz = 0; int rowbits = 32; };  // rowbits: the sort keys are (column << rowbits) | row
+struct SpScratch {   // sparse()'s sort: L = max(len, 1) words each
+    DevBuf keys_in;  // u64 L: the keys as packed; the fill hands it over to the list of long runs of empty columns
+    DevBuf keys_out, idx_in, idx_out;  // u64 L each: the sorted keys (the fill reads them), the input positions before and after the sort
+    DevBuf prim_tmp;                   // rocPRIM's temporary
+};
 
 // kernel ids for the optional HIP-event timing (otmb_ctx_timing_*)
 enum {
@@ -39,7 +44,7 @@ struct otmb_ctx {
     std::string err;
     // scratch for the scans / flags
     DevBuf blocksums, blockoffs, flags, stamps, tcount, tfix[3];  // (stamps: diagnostic builds, OTMB_DBG_STAMPS)
-    DevBuf sort[5];            // radix-sort keys/values/temporary of the general sparse() path
+    SpScratch sort;           // of the general sparse() path (otmb_coo.hip)
     DevBuf tm_sums, tm_offs;  // tile sums/offsets of the pending transportmatrix plan (must survive until fill)
     DevBuf mask;              // push mask derived by the library when the caller passes none
     DevBuf order;             // tile order of the fill pass (march order: otmb_ctx_set_tile_order) + its bucket scratch
@@ -80,7 +85,21 @@ struct otmb_ctx {
         bool pieces_open = false;  // the last facefluxes call counted: a further row band of it (otmb_facefluxes_slab_counts_dev, first = 0) adds to the same buffer
     } ffc;
     const void *ffc_partial_mask = nullptr;  // the push_mask argument of the last counting facefluxes call: NOT written by it, never a counting pass's input
-    DevBuf lump[11];          // lump_and_spray scratch (otmb_lump.hip)
+    // lump_and_spray (otmb_lump.hip): the plan's scratch, which the fill goes on using.  G cells, N wet cells, Nc coarse cells, numbers 2 .. cmax - 1.
+    // A member that is handed over to another array in the course of a call says so here and at the hand-over.
+    struct LumpScratch {
+        DevBuf isanchor;  // u8 G
+        DevBuf owner;     // u32 G: the last anchor whose block covers a cell
+        DevBuf ncomp;     // u32 G: components of every anchor's block; handed over to counts (u32 Nc + 1, the coarse cells' sizes), which the fill reads
+        DevBuf arank;     // i64 G + 2: anchors before a cell
+        DevBuf inc;       // i64 G + 2: what a scan reads -- anchor flags, numbers consumed per cell, `used` widened, in the fill the counts widened (+ their offsets)
+        DevBuf cbase;     // i64 G + 2: the counter c at every cell; handed over to the fill's sort: keys out, values in, values out (i64 N each)
+        DevBuf labels;    // u16 per anchor and block cell: component numbers
+        DevBuf cnum;      // i64 N numbers of the wet cells | i64 N their coarse rows (crow)
+        DevBuf used;      // i64 cmax + 2 newidx (number -> coarse row) | u8 cmax + 1 used (the number holds a wet cell)
+        DevBuf prim_tmp;  // rocPRIM's temporary (scans, the fill's sort)
+        DevBuf covk;      // int nx * ny, dk > 1 only: the last level a column is covered to
+    } lump;
     DevBuf lump_host;         // staging of the host-pointer entry point
     bool lump_valid = false;
     i64 lump_N = 0, lump_Nc = 0;
@@ -184,7 +203,19 @@ struct otmb_ctx {
         int rowbits = 0;
         uint64_t invalid = 0;
     } co_plan;
-    DevBuf co[10], co_host, co_out;
+    struct CoScratch {
+        DevBuf flags;     // bad bits (unsigned) | wmax (u64 at + 8)
+        DevBuf woff;      // i64 nS + 1 widths w | i64 nS + 1 their exclusive scan woff (the fill reads woff)
+        DevBuf cnt;       // i64 n + 1: 1, then the distinct rows of every column (small path)
+        DevBuf colptr;    // i64 n + 1: kept for the fill
+        // sorted path (len = contributions):
+        DevBuf keys;      // u64 len as expanded | u64 len sorted
+        DevBuf idx;       // u64 len iteration indices | u64 len sorted
+        DevBuf val, sid;  // f64 len products a * b; i64 len the entry of S they belong to
+        DevBuf heads;     // i64 len + 1 segment heads | i64 len + 1 their exclusive scan
+        DevBuf prim_tmp;  // rocPRIM's temporary (scans, the sort)
+    } co;
+    DevBuf co_host, co_out;
     // staging for the host-pointer entry points
     std::vector<DevBuf> stage;
     OtmbXfer *xfer = nullptr;
@@ -220,6 +251,9 @@ struct KernelTimer {
 };
 
 #define OTMB_NFLAGS 16
+// the 16 i64 totals behind the flag words (ctx->h_tot and its device twin): [0, 8) transportmatrix, [8] T's compaction, [9] the sparse add,
+// then the general path's three (otmb_coo.hip), [13] makeindices, [14] the tile order's histogram word
+enum { TOT_COO_LEN = 10 /* triplets of a COO generator */, TOT_SP_NNZ = 11 /* sparse(): stored entries */, TOT_SP_BAD = 12 /* ... triplets with an index out of range */ };
 enum {
     FLAG_RHO_NAN = 0, FLAG_TADV_NAN, FLAG_TKH_NAN, FLAG_TKVML_NAN, FLAG_TKVDEEP_NAN,
     FLAG_FLUX_INTO_LAND, FLAG_NONCANONICAL, FLAG_GIVEN_MISMATCH /* the comparing pass (otmb_tm_args.given): an entry differs */, FLAG_CAPACITY,

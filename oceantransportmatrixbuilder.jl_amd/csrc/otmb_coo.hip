@@ -15,8 +15,8 @@
 #include <cstring>
 #include <string.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
+#include "otmb_prims.h"
+#include "otmb_tm.h"  // otmb_tm_fill_params, otmb_tm_check_flags
 #include "otmb_tm_column.h"
 
 #define COO_THREADS 256
@@ -207,18 +207,9 @@ __global__ __launch_bounds__(256) void sp_heads_kernel(const u64 *__restrict__ k
 }
 
 
-static void coo_params(TmParams &p, const otmb_tm_args &a, otmb_ctx *ctx) {
-    memset(&p, 0, sizeof p);
-    for (int f = 0; f < 6; ++f) p.phi[f] = a.phi[f];
-    p.v = a.v3d; p.thk = a.thkcello; p.rho = a.rho; p.rho_s = a.rho_scalar;
-    p.lw = (const i64 *)a.lwet3d; p.lwet = (const i64 *)a.lwet;
-    for (int d = 0; d < 4; ++d) { p.edge[d] = a.edge_length[d]; p.dist[d] = a.dist_nbr[d]; }
-    p.area = a.area2d; p.zt = a.zt; p.ml = a.mlotst;
-    p.kH = a.kappa_h; p.kML = a.kappa_vml; p.kDeep = a.kappa_vdeep;
-    p.nx = (int)a.nx; p.ny = (int)a.ny; p.nz = (int)a.nz; p.topo = a.topology; p.upwind = a.upwind;
-    p.P = a.nx * a.ny; p.G = p.P * a.nz; p.n_own = a.n_wet;
-    p.flags = (int *)ctx->flags.p;
-}
+// the parameters of a call without a plan: wet_base = 0, nothing given or kept; coo_kernel reads none of the fields that describe the
+// fused path's tiles (skip, keep, tilesums, tileoffs, the tile order), which this fills in as well
+static void coo_params(TmParams &p, const otmb_tm_args &a, otmb_ctx *ctx) { otmb_tm_fill_params(p, a, ctx, nullptr); }
 
 template <bool WRITE>
 static void coo_launch(int which, unsigned nt, hipStream_t s, const TmParams &p, uint32_t *sums, const i64 *offs, i64 *I, i64 *J, double *V) {
@@ -228,17 +219,6 @@ static void coo_launch(int which, unsigned nt, hipStream_t s, const TmParams &p,
         case COO_VML: hipLaunchKernelGGL((coo_kernel<COO_VML, WRITE>), dim3(nt), dim3(COO_THREADS), 0, s, p, sums, offs, I, J, V); break;
         default: hipLaunchKernelGGL((coo_kernel<COO_VDEEP, WRITE>), dim3(nt), dim3(COO_THREADS), 0, s, p, sums, offs, I, J, V); break;
     }
-}
-
-static int32_t flags_to_status(otmb_ctx *ctx) {
-    const int *f = ctx->h_flags;
-    if (f[FLAG_RHO_NAN]) return otmb_fail(ctx, OTMB_ERR_RHO_NAN);
-    if (f[FLAG_FLUX_INTO_LAND]) return otmb_fail(ctx, OTMB_ERR_FLUX_INTO_LAND);
-    if (f[FLAG_TADV_NAN]) return otmb_fail(ctx, OTMB_ERR_TADV_NAN);
-    if (f[FLAG_TKH_NAN]) return otmb_fail(ctx, OTMB_ERR_TKH_NAN);
-    if (f[FLAG_TKVML_NAN]) return otmb_fail(ctx, OTMB_ERR_TKVML_NAN);
-    if (f[FLAG_TKVDEEP_NAN]) return otmb_fail(ctx, OTMB_ERR_TKVDEEP_NAN);
-    return OTMB_OK;
 }
 
 extern "C" {
@@ -258,7 +238,7 @@ int32_t otmb_sparse_entries_plan_dev(otmb_ctx *ctx, int32_t which, const otmb_tm
     TmParams p;
     coo_params(p, *a, ctx);
     int *dflags = (int *)ctx->flags.p;
-    i64 *dtot = (i64 *)(dflags + OTMB_NFLAGS) + 10;
+    i64 *dtot = (i64 *)(dflags + OTMB_NFLAGS) + TOT_COO_LEN;
     HIP_TRY(ctx, hipMemsetAsync(dflags, 0, OTMB_NFLAGS_TM * sizeof(int), ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(dtot, 0, sizeof(i64), ctx->stream));
     if (nt > 0) {
@@ -267,10 +247,11 @@ int32_t otmb_sparse_entries_plan_dev(otmb_ctx *ctx, int32_t which, const otmb_tm
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_flags, dflags, OTMB_NFLAGS_TM * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_tot + 10, dtot, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_tot + TOT_COO_LEN, dtot, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if ((rc = flags_to_status(ctx))) return rc;
-    ctx->coo.which = which; ctx->coo.args = *a; ctx->coo.ntiles = nt; ctx->coo.len = ctx->h_tot[10];
+    // (all OTMB_NFLAGS_TM words were zeroed above and coo_kernel raises none of NONCANONICAL, COUNT_MISMATCH, CAPACITY: the fuller check's extra tests stay silent)
+    if ((rc = otmb_tm_check_flags(ctx, nullptr, 0))) return rc;
+    ctx->coo.which = which; ctx->coo.args = *a; ctx->coo.ntiles = nt; ctx->coo.len = ctx->h_tot[TOT_COO_LEN];
     *len = ctx->coo.len;
     return OTMB_OK;
 }
@@ -297,40 +278,35 @@ int32_t otmb_sparse_plan_dev(otmb_ctx *ctx, const int64_t *I, const int64_t *J, 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int32_t rc;
     const size_t L = (size_t)(len > 0 ? len : 1);
-    if ((rc = otmb_reserve(ctx, ctx->sort[0], L * 8))) return rc;  // keys in
-    if ((rc = otmb_reserve(ctx, ctx->sort[1], L * 8))) return rc;  // keys out
-    if ((rc = otmb_reserve(ctx, ctx->sort[2], L * 8))) return rc;  // idx in
-    if ((rc = otmb_reserve(ctx, ctx->sort[3], L * 8))) return rc;  // idx out
-    u64 *k0 = (u64 *)ctx->sort[0].p, *k1 = (u64 *)ctx->sort[1].p, *v0 = (u64 *)ctx->sort[2].p, *v1 = (u64 *)ctx->sort[3].p;
+    SpScratch &S = ctx->sort;
+    for (DevBuf *b : {&S.keys_in, &S.keys_out, &S.idx_in, &S.idx_out})
+        if ((rc = otmb_reserve(ctx, *b, L * 8))) return rc;
+    u64 *k0 = (u64 *)S.keys_in.p, *k1 = (u64 *)S.keys_out.p, *v0 = (u64 *)S.idx_in.p, *v1 = (u64 *)S.idx_out.p;
     const i64 nt = (len + 255) / 256;
     if ((rc = otmb_reserve(ctx, ctx->blocksums, (size_t)(nt + 1) * sizeof(uint32_t)))) return rc;
     if ((rc = otmb_reserve(ctx, ctx->blockoffs, (size_t)(nt + 1) * sizeof(i64) + otmb_scan_scratch(nt, 1)))) return rc;
-    i64 *dtot = (i64 *)((int *)ctx->flags.p + OTMB_NFLAGS) + 11;  // [11] nnz, [12] triplets with an index out of range
-    ctx->sp.len = -1;                                               // no valid plan until this one succeeds
+    static_assert(TOT_SP_BAD == TOT_SP_NNZ + 1, "one memset clears both");
+    i64 *dtot = (i64 *)((int *)ctx->flags.p + OTMB_NFLAGS) + TOT_SP_NNZ, *dbad = dtot + 1;
+    ctx->sp.len = -1;  // no valid plan until this one succeeds
     HIP_TRY(ctx, hipMemsetAsync(dtot, 0, 2 * sizeof(i64), ctx->stream));
-    int rowbits = 1, colbits = 1;
-    while (rowbits < 32 && (m >> rowbits) != 0) ++rowbits;  // 1 <= row <= m < 2^rowbits
-    while (colbits < 32 && (n >> colbits) != 0) ++colbits;
+    const int rowbits = otmb_bits(m), colbits = otmb_bits(n);  // 1 <= row <= m < 2^rowbits; m, n < 2^32 (refused above): at most 32 each
     if (len > 0) {
         hipLaunchKernelGGL(sp_keys_kernel, dim3((unsigned)nt), dim3(256), 0, ctx->stream, (const i64 *)I, (const i64 *)J, (i64)len, (i64)m, (i64)n, rowbits,
-                           k0, v0, dtot + 1);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_tot + 12, dtot + 1, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
+                           k0, v0, dbad);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_tot + TOT_SP_BAD, dbad, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->h_tot[12] != 0)
+        if (ctx->h_tot[TOT_SP_BAD] != 0)
             return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "ArgumentError: row indices I[k] must satisfy 1 <= I[k] <= m and column indices J[k] 1 <= J[k] <= n");
-        size_t tmp = 0;
-        if (rocprim::radix_sort_pairs(nullptr, tmp, k0, k1, v0, v1, (size_t)len, 0, (unsigned)(rowbits + colbits), ctx->stream) != hipSuccess) return otmb_fail(ctx, OTMB_ERR_HIP, "radix_sort_pairs (size)");
-        if ((rc = otmb_reserve(ctx, ctx->sort[4], tmp + 16))) return rc;
-        if (rocprim::radix_sort_pairs(ctx->sort[4].p, tmp, k0, k1, v0, v1, (size_t)len, 0, (unsigned)(rowbits + colbits), ctx->stream) != hipSuccess) return otmb_fail(ctx, OTMB_ERR_HIP, "radix_sort_pairs");
+        if ((rc = otmb_sort_pairs(ctx, S.prim_tmp, k0, k1, v0, v1, len, rowbits + colbits))) return rc;
         hipLaunchKernelGGL(sp_heads_kernel<false>, dim3((unsigned)nt), dim3(256), 0, ctx->stream, (const u64 *)k1, (const u64 *)v1, V, (i64)len,
                            (uint32_t *)ctx->blocksums.p, (const i64 *)nullptr, (i64)n, (i64 *)nullptr, (i64 *)nullptr, (double *)nullptr,
                            (unsigned long long *)nullptr, (SpGap *)nullptr, rowbits);
         otmb_launch_tilescan(ctx->stream, (const uint32_t *)ctx->blocksums.p, (i64 *)ctx->blockoffs.p, dtot, nt, 1, (i64 *)ctx->blockoffs.p + nt + 1);
     }
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_tot + 11, dtot, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_tot + TOT_SP_NNZ, dtot, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->sp.I = I; ctx->sp.J = J; ctx->sp.V = V; ctx->sp.len = len; ctx->sp.m = m; ctx->sp.n = n; ctx->sp.nnz = ctx->h_tot[11]; ctx->sp.rowbits = rowbits;
+    ctx->sp.I = I; ctx->sp.J = J; ctx->sp.V = V; ctx->sp.len = len; ctx->sp.m = m; ctx->sp.n = n; ctx->sp.nnz = ctx->h_tot[TOT_SP_NNZ]; ctx->sp.rowbits = rowbits;
     *nnz = ctx->sp.nnz;
     return OTMB_OK;
 }
@@ -346,12 +322,13 @@ int32_t otmb_sparse_fill_dev(otmb_ctx *ctx, int64_t *colptr, int64_t *rowval, do
     const i64 runs = ((len + 1 < ncol / SP_GAP_SELF + 1) ? len + 1 : ncol / SP_GAP_SELF + 1);
     const size_t gap_bytes = 16 + (size_t)(runs + ncol / SP_GAP_PIECE + 2) * sizeof(SpGap);
     int32_t rc;
-    if ((rc = otmb_reserve(ctx, ctx->sort[0], gap_bytes))) return rc;  // (the unsorted keys are no longer needed)
-    unsigned long long *ngaps = (unsigned long long *)ctx->sort[0].p;
-    SpGap *gaps = (SpGap *)((char *)ctx->sort[0].p + 16);
+    SpScratch &S = ctx->sort;
+    if ((rc = otmb_reserve(ctx, S.keys_in, gap_bytes))) return rc;  // hand-over: the unsorted keys are spent, S.keys_in takes the gap list
+    unsigned long long *ngaps = (unsigned long long *)S.keys_in.p;
+    SpGap *gaps = (SpGap *)((char *)S.keys_in.p + 16);
     HIP_TRY(ctx, hipMemsetAsync(ngaps, 0, 16, ctx->stream));
-    hipLaunchKernelGGL(sp_heads_kernel<true>, dim3((unsigned)(nt > 0 ? nt : 1)), dim3(256), 0, ctx->stream, (const u64 *)ctx->sort[1].p,
-                       (const u64 *)ctx->sort[3].p, ctx->sp.V, len, (uint32_t *)nullptr, (const i64 *)ctx->blockoffs.p, ctx->sp.n, (i64 *)colptr,
+    hipLaunchKernelGGL(sp_heads_kernel<true>, dim3((unsigned)(nt > 0 ? nt : 1)), dim3(256), 0, ctx->stream, (const u64 *)S.keys_out.p,
+                       (const u64 *)S.idx_out.p, ctx->sp.V, len, (uint32_t *)nullptr, (const i64 *)ctx->blockoffs.p, ctx->sp.n, (i64 *)colptr,
                        (i64 *)rowval, nzval, ngaps, gaps, ctx->sp.rowbits);
     hipLaunchKernelGGL(sp_fill_gaps_kernel, dim3(1024), dim3(256), 0, ctx->stream, (const unsigned long long *)ngaps, (const SpGap *)gaps, (i64 *)colptr);
     HIP_TRY(ctx, hipGetLastError());

@@ -118,15 +118,14 @@ void otmb_ctx_destroy(otmb_ctx *ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     otmb_tm_plan_free(ctx);
     otmb_xfer_free(ctx);
-    for (DevBuf *b : {&ctx->blocksums, &ctx->blockoffs, &ctx->flags, &ctx->ring, &ctx->stamps, &ctx->tcount, &ctx->tfix[0], &ctx->tfix[1], &ctx->tfix[2], &ctx->tm_sums, &ctx->tm_offs, &ctx->sort[0], &ctx->sort[1], &ctx->sort[2], &ctx->sort[3], &ctx->sort[4], &ctx->ffc_sums[0], &ctx->ffc_sums[1], &ctx->xfer_narrow, &ctx->given_tmp[0], &ctx->given_tmp[1], &ctx->given_tmp[2], &ctx->given_tmp[3], &ctx->given_tmp[4], &ctx->given_tmp[5], &ctx->htab, &ctx->vrtab})
+    for (DevBuf *b : {&ctx->blocksums, &ctx->blockoffs, &ctx->flags, &ctx->ring, &ctx->stamps, &ctx->tcount, &ctx->tfix[0], &ctx->tfix[1], &ctx->tfix[2], &ctx->tm_sums, &ctx->tm_offs, &ctx->sort.keys_in, &ctx->sort.keys_out, &ctx->sort.idx_in, &ctx->sort.idx_out, &ctx->sort.prim_tmp, &ctx->ffc_sums[0], &ctx->ffc_sums[1], &ctx->xfer_narrow, &ctx->given_tmp[0], &ctx->given_tmp[1], &ctx->given_tmp[2], &ctx->given_tmp[3], &ctx->given_tmp[4], &ctx->given_tmp[5], &ctx->htab, &ctx->vrtab})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : ctx->stage)
         if (b.p) (void)hipFree(b.p);
-    for (DevBuf &b : ctx->lump)
-        if (b.p) (void)hipFree(b.p);
-    for (DevBuf &b : ctx->co)
-        if (b.p) (void)hipFree(b.p);
-    for (DevBuf *b : {&ctx->co_host, &ctx->co_out})
+    otmb_ctx::LumpScratch &l = ctx->lump;
+    otmb_ctx::CoScratch &c = ctx->co;
+    for (DevBuf *b : {&l.isanchor, &l.owner, &l.ncomp, &l.arank, &l.inc, &l.cbase, &l.labels, &l.cnum, &l.used, &l.prim_tmp, &l.covk, &c.flags, &c.woff, &c.cnt, &c.colptr,
+                      &c.keys, &c.idx, &c.val, &c.sid, &c.heads, &c.prim_tmp, &ctx->co_host, &ctx->co_out})
         if (b->p) (void)hipFree(b->p);
     if (ctx->mask.p) (void)hipFree(ctx->mask.p);
     if (ctx->order.p) (void)hipFree(ctx->order.p);

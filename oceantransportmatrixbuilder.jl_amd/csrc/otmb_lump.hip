@@ -22,10 +22,7 @@
 #include <cstring>
 #include <string.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
-#include "otmb_common.h"
+#include "otmb_prims.h"
 
 #define LS_THREADS 256
 #define LS_INF 0xFFFFu
@@ -220,10 +217,6 @@ __global__ void lump_number_kernel(LumpGrid g, i64 N, const i64 *__restrict__ lw
     cnum[w] = c;
     used[c] = 1;
 }
-__global__ void lump_widen_kernel(i64 n, const uint8_t *__restrict__ in, i64 *__restrict__ out) {
-    const i64 q = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < n) out[q] = in[q];
-}
 __global__ void lump_row_kernel(i64 N, const i64 *__restrict__ cnum, const i64 *__restrict__ newidx, i64 *__restrict__ crow,
                                 unsigned *__restrict__ counts) {
     const i64 w = (i64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -234,18 +227,10 @@ __global__ void lump_row_kernel(i64 N, const i64 *__restrict__ cnum, const i64 *
 }
 
 // ---- 5. fill ----------------------------------------------------------------------------------------------------------
-__global__ void lump_iota_kernel(i64 n, i64 *__restrict__ a, i64 first) {
-    const i64 q = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < n) a[q] = first + q;
-}
 __global__ void lump_colptr_kernel(i64 Nc, const i64 *__restrict__ offs, i64 N, i64 *__restrict__ colptr) {
     const i64 I = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (I < Nc) colptr[I] = offs[I] + 1;
     if (I == Nc) colptr[Nc] = N + 1;
-}
-__global__ void lump_counts_widen_kernel(i64 n, const unsigned *__restrict__ in, i64 *__restrict__ out) {
-    const i64 q = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < n) out[q] = in[q];
 }
 // vol_c = LUMP * vol (:96): mul! walks the columns (wet cells) in ascending order and does y[row] += 1 * vol[col]
 __global__ void lump_volc_kernel(i64 Nc, const i64 *__restrict__ spray_colptr, const i64 *__restrict__ spray_row,
@@ -266,23 +251,9 @@ __global__ void lump_values_kernel(i64 N, const i64 *__restrict__ crow, const do
     lump_val[w] = ((1.0 / vol_c[I]) * 1) * vol[w];
     spray_val[w] = 1.0;
 }
-__global__ void lump_plus1_kernel(i64 n, const i64 *__restrict__ in, i64 *__restrict__ out) {
-    const i64 q = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < n) out[q] = in[q] + 1;
-}
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
-static int32_t lump_scan(otmb_ctx *ctx, const i64 *in, i64 *out, i64 n) {  // exclusive sum; out[n] is NOT written
-    size_t tmp = 0;
-    if (rocprim::exclusive_scan(nullptr, tmp, in, out, (i64)0, (size_t)n, rocprim::plus<i64>(), ctx->stream) != hipSuccess)
-        return otmb_fail(ctx, OTMB_ERR_HIP, "exclusive_scan (size)");
-    int32_t rc;
-    if ((rc = otmb_reserve(ctx, ctx->lump[9], tmp + 16))) return rc;
-    if (rocprim::exclusive_scan(ctx->lump[9].p, tmp, in, out, (i64)0, (size_t)n, rocprim::plus<i64>(), ctx->stream) != hipSuccess)
-        return otmb_fail(ctx, OTMB_ERR_HIP, "exclusive_scan");
-    return OTMB_OK;
-}
-#define GRID(n) dim3((unsigned)(((n) + 255) / 256 > 0 ? ((n) + 255) / 256 : 1)), dim3(256), 0, ctx->stream
+#define GRID(n) OTMB_GRID_EXACT(n, ctx->stream)  // (every kernel of this file is one thread per element)
 
 extern "C" {
 
@@ -299,25 +270,24 @@ int32_t otmb_lump_and_spray_plan_dev(otmb_ctx *ctx, const uint8_t *wet3d, const 
     if (bv > LS_MAX_BLOCK || di > nx + 4096 || dj > 4096 || dk > 4096) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "di*dj*dk > 4096");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int32_t rc;
-    // scratch: [0] isanchor u8 G | [1] owner u32 G | [2] ncomp u32 G | [3] i64 G+2 (anchor rank, then reused) |
-    // [4] i64 G (increments) | [5] cbase i64 G | [6] labels | [7] cnum i64 N, crow i64 N | [8] used u8 / newidx | [9] scan temp
-    if ((rc = otmb_reserve(ctx, ctx->lump[0], (size_t)G + 16))) return rc;
-    if ((rc = otmb_reserve(ctx, ctx->lump[1], (size_t)G * 4 + 16))) return rc;
-    if ((rc = otmb_reserve(ctx, ctx->lump[2], (size_t)G * 4 + 16))) return rc;
-    if ((rc = otmb_reserve(ctx, ctx->lump[3], (size_t)(G + 2) * 8))) return rc;
-    if ((rc = otmb_reserve(ctx, ctx->lump[4], (size_t)(G + 2) * 8))) return rc;
-    if ((rc = otmb_reserve(ctx, ctx->lump[5], (size_t)(G + 2) * 8))) return rc;
-    uint8_t *isanchor = (uint8_t *)ctx->lump[0].p;
-    uint32_t *owner = (uint32_t *)ctx->lump[1].p, *ncomp = (uint32_t *)ctx->lump[2].p;
-    i64 *arank = (i64 *)ctx->lump[3].p, *inc = (i64 *)ctx->lump[4].p, *cbase = (i64 *)ctx->lump[5].p;
+    otmb_ctx::LumpScratch &S = ctx->lump;  // (otmb_common.h says what each member holds)
+    if ((rc = otmb_reserve(ctx, S.isanchor, (size_t)G + 16))) return rc;
+    if ((rc = otmb_reserve(ctx, S.owner, (size_t)G * 4 + 16))) return rc;
+    if ((rc = otmb_reserve(ctx, S.ncomp, (size_t)G * 4 + 16))) return rc;
+    if ((rc = otmb_reserve(ctx, S.arank, (size_t)(G + 2) * 8))) return rc;
+    if ((rc = otmb_reserve(ctx, S.inc, (size_t)(G + 2) * 8))) return rc;
+    if ((rc = otmb_reserve(ctx, S.cbase, (size_t)(G + 2) * 8))) return rc;
+    uint8_t *isanchor = (uint8_t *)S.isanchor.p;
+    uint32_t *owner = (uint32_t *)S.owner.p, *ncomp = (uint32_t *)S.ncomp.p;
+    i64 *arank = (i64 *)S.arank.p, *inc = (i64 *)S.inc.p, *cbase = (i64 *)S.cbase.p;
     int *dflags = (int *)ctx->flags.p;
     HIP_TRY(ctx, hipMemsetAsync(isanchor, 0, (size_t)G, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(dflags, 0, sizeof(int), ctx->stream));
     // 1. sweep
     int *covk = nullptr;
     if (dk > 1) {
-        if ((rc = otmb_reserve(ctx, ctx->lump[10], (size_t)nx * ny * 4 + 16))) return rc;
-        covk = (int *)ctx->lump[10].p;
+        if ((rc = otmb_reserve(ctx, S.covk, (size_t)nx * ny * 4 + 16))) return rc;
+        covk = (int *)S.covk.p;
         HIP_TRY(ctx, hipMemsetAsync(covk, 0xFF, (size_t)nx * ny * 4, ctx->stream));
     }
     {
@@ -330,22 +300,22 @@ int32_t otmb_lump_and_spray_plan_dev(otmb_ctx *ctx, const uint8_t *wet3d, const 
     }
     // anchor ranks (exclusive count of anchors before a cell) and their number
     hipLaunchKernelGGL(lump_anchor_flag_kernel, GRID(G), G, (const uint8_t *)isanchor, inc);
-    if ((rc = lump_scan(ctx, inc, arank, G))) return rc;
+    if ((rc = otmb_exclusive_scan(ctx, S.prim_tmp, inc, arank, G))) return rc;
     i64 last[2] = {0, 0};
     HIP_TRY(ctx, hipMemcpyAsync(&last[0], arank + (G - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(&last[1], inc + (G - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const i64 nanchor = last[0] + last[1];
     if ((size_t)nanchor * (size_t)bv * 2 > ((size_t)64 << 30)) return otmb_fail(ctx, OTMB_ERR_ALLOC, "component scratch over 64 GB");
-    if ((rc = otmb_reserve(ctx, ctx->lump[6], (size_t)nanchor * bv * 2 + 16))) return rc;
-    unsigned short *labels = (unsigned short *)ctx->lump[6].p;
+    if ((rc = otmb_reserve(ctx, S.labels, (size_t)nanchor * bv * 2 + 16))) return rc;
+    unsigned short *labels = (unsigned short *)S.labels.p;
     // 2. components
     LumpGrid g{(int)nx, (int)ny, (int)nz, (int)di, (int)dj, (int)dk, nx * ny};
     hipLaunchKernelGGL(lump_components_kernel, GRID(G), g, G, (const uint8_t *)isanchor, (const i64 *)arank, wet3d, (const i64 *)lwet3d,
                        (const i64 *)lwet, (const i64 *)t_colptr, (const i64 *)t_rowval, labels, ncomp, dflags);
     // 3. the counter c at every cell
     hipLaunchKernelGGL(lump_increment_kernel, GRID(G), G, mask, (const uint8_t *)isanchor, (const uint32_t *)ncomp, inc);
-    if ((rc = lump_scan(ctx, inc, cbase, G))) return rc;
+    if ((rc = otmb_exclusive_scan(ctx, S.prim_tmp, inc, cbase, G))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(&last[0], cbase + (G - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(&last[1], inc + (G - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_flags, dflags, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -353,26 +323,27 @@ int32_t otmb_lump_and_spray_plan_dev(otmb_ctx *ctx, const uint8_t *wet3d, const 
     if (ctx->h_flags[0]) return otmb_fail(ctx, OTMB_ERR_ASYMMETRIC_PATTERN);
     const i64 cmax = 2 + last[0] + last[1];  // numbers in use are 2 .. cmax-1
     // 4. numbers of the wet cells, surviving rows
-    if ((rc = otmb_reserve(ctx, ctx->lump[7], (size_t)(2 * N + 2) * 8))) return rc;
-    if ((rc = otmb_reserve(ctx, ctx->lump[8], (size_t)(cmax + 2) * 9 + 16))) return rc;
-    i64 *cnum = (i64 *)ctx->lump[7].p, *crow = cnum + N;
-    i64 *newidx = (i64 *)ctx->lump[8].p;
+    if ((rc = otmb_reserve(ctx, S.cnum, (size_t)(2 * N + 2) * 8))) return rc;
+    if ((rc = otmb_reserve(ctx, S.used, (size_t)(cmax + 2) * 9 + 16))) return rc;
+    i64 *cnum = (i64 *)S.cnum.p, *crow = cnum + N;
+    i64 *newidx = (i64 *)S.used.p;
     uint8_t *used = (uint8_t *)(newidx + cmax + 2);
     HIP_TRY(ctx, hipMemsetAsync(used, 0, (size_t)cmax + 1, ctx->stream));
     hipLaunchKernelGGL(lump_number_kernel, GRID(N), g, N, (const i64 *)lwet, mask, (const uint32_t *)owner, (const i64 *)arank,
                        (const i64 *)cbase, (const unsigned short *)labels, cnum, used);
-    // arank / inc are free again: widen the flags and scan them
-    if ((rc = otmb_reserve(ctx, ctx->lump[4], (size_t)(cmax + 2) * 8))) return rc;
-    inc = (i64 *)ctx->lump[4].p;
-    hipLaunchKernelGGL(lump_widen_kernel, GRID(cmax + 1), cmax + 1, (const uint8_t *)used, inc);
-    if ((rc = lump_scan(ctx, inc, newidx, cmax + 1))) return rc;
+    // hand-over: the increments are spent (cbase holds their scan), S.inc takes the widened `used` flags
+    if ((rc = otmb_reserve(ctx, S.inc, (size_t)(cmax + 2) * 8))) return rc;
+    inc = (i64 *)S.inc.p;
+    otmb_widen(ctx->stream, (const uint8_t *)used, cmax + 1, 0, inc);
+    if ((rc = otmb_exclusive_scan(ctx, S.prim_tmp, inc, newidx, cmax + 1))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(&last[0], newidx + cmax, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(&last[1], inc + cmax, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const i64 Nc = last[0] + last[1];
     // coarse row of every wet cell and the size of every coarse cell
-    if ((rc = otmb_reserve(ctx, ctx->lump[2], (size_t)(Nc + 2) * 4 + (size_t)G * 4 + 16))) return rc;
-    unsigned *counts = (unsigned *)ctx->lump[2].p;
+    // hand-over: ncomp is spent (the increments took it in), S.ncomp takes the counts
+    if ((rc = otmb_reserve(ctx, S.ncomp, (size_t)(Nc + 2) * 4 + (size_t)G * 4 + 16))) return rc;
+    unsigned *counts = (unsigned *)S.ncomp.p;
     HIP_TRY(ctx, hipMemsetAsync(counts, 0, (size_t)(Nc + 1) * 4, ctx->stream));
     hipLaunchKernelGGL(lump_row_kernel, GRID(N), N, (const i64 *)cnum, (const i64 *)newidx, crow, counts);
     HIP_TRY(ctx, hipGetLastError());
@@ -393,28 +364,23 @@ int32_t otmb_lump_and_spray_fill_dev(otmb_ctx *ctx, const double *vol, int64_t *
         return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int32_t rc;
-    i64 *cnum = (i64 *)ctx->lump[7].p, *crow = cnum + N;
-    unsigned *counts = (unsigned *)ctx->lump[2].p;
-    // SPRAY's column pointers: exclusive scan of the coarse cell sizes
-    if ((rc = otmb_reserve(ctx, ctx->lump[4], (size_t)(Nc + 2) * 16))) return rc;
-    i64 *wide = (i64 *)ctx->lump[4].p, *offs = wide + (Nc + 2);
-    hipLaunchKernelGGL(lump_counts_widen_kernel, GRID(Nc + 1), Nc + 1, (const unsigned *)counts, wide);
-    if ((rc = lump_scan(ctx, wide, offs, Nc + 1))) return rc;
+    otmb_ctx::LumpScratch &S = ctx->lump;
+    i64 *cnum = (i64 *)S.cnum.p, *crow = cnum + N;
+    unsigned *counts = (unsigned *)S.ncomp.p;  // (handed over by the plan)
+    // SPRAY's column pointers: exclusive scan of the coarse cell sizes.  Hand-over: S.inc takes the widened counts and their offsets
+    if ((rc = otmb_reserve(ctx, S.inc, (size_t)(Nc + 2) * 16))) return rc;
+    i64 *wide = (i64 *)S.inc.p, *offs = wide + (Nc + 2);
+    otmb_widen(ctx->stream, (const unsigned *)counts, Nc + 1, 0, wide);
+    if ((rc = otmb_exclusive_scan(ctx, S.prim_tmp, wide, offs, Nc + 1))) return rc;
     hipLaunchKernelGGL(lump_colptr_kernel, GRID(Nc + 1), Nc, (const i64 *)offs, N, (i64 *)spray_colptr);
-    hipLaunchKernelGGL(lump_iota_kernel, GRID(N + 1), N + 1, (i64 *)lump_colptr, (i64)1);  // one entry per column
+    otmb_iota(ctx->stream, (i64 *)lump_colptr, N + 1, 1);  // one entry per column
     if (N > 0) {
-        // SPRAY = LUMP' (:101): the wet cells sorted by coarse row; the sort is stable, so members stay ascending
-        if ((rc = otmb_reserve(ctx, ctx->lump[5], (size_t)N * 8 * 3 + 16))) return rc;
-        i64 *keys_out = (i64 *)ctx->lump[5].p, *vals_in = keys_out + N, *vals_out = vals_in + N;
-        hipLaunchKernelGGL(lump_iota_kernel, GRID(N), N, vals_in, (i64)1);
-        size_t tmp = 0;
-        int bits = 1;
-        while (bits < 63 && (1ll << bits) <= Nc) ++bits;
-        if (rocprim::radix_sort_pairs(nullptr, tmp, (const i64 *)crow, keys_out, (const i64 *)vals_in, vals_out, (size_t)N, 0, bits, ctx->stream) != hipSuccess)
-            return otmb_fail(ctx, OTMB_ERR_HIP, "radix_sort_pairs (size)");
-        if ((rc = otmb_reserve(ctx, ctx->lump[9], tmp + 16))) return rc;
-        if (rocprim::radix_sort_pairs(ctx->lump[9].p, tmp, (const i64 *)crow, keys_out, (const i64 *)vals_in, vals_out, (size_t)N, 0, bits, ctx->stream) != hipSuccess)
-            return otmb_fail(ctx, OTMB_ERR_HIP, "radix_sort_pairs");
+        // SPRAY = LUMP' (:101): the wet cells sorted by coarse row; the sort is stable, so members stay ascending.
+        // Hand-over: the plan's cbase is spent, S.cbase takes the sort's keys out, values in, values out
+        if ((rc = otmb_reserve(ctx, S.cbase, (size_t)N * 8 * 3 + 16))) return rc;
+        i64 *keys_out = (i64 *)S.cbase.p, *vals_in = keys_out + N, *vals_out = vals_in + N;
+        otmb_iota(ctx->stream, vals_in, N, 1);
+        if ((rc = otmb_sort_pairs(ctx, S.prim_tmp, (const i64 *)crow, keys_out, (const i64 *)vals_in, vals_out, N, otmb_bits(Nc)))) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(spray_rowval, vals_out, (size_t)N * 8, hipMemcpyDeviceToDevice, ctx->stream));
         hipLaunchKernelGGL(lump_volc_kernel, GRID(Nc), Nc, (const i64 *)spray_colptr, (const i64 *)spray_rowval, vol, vol_c);
         hipLaunchKernelGGL(lump_values_kernel, GRID(N), N, (const i64 *)crow, vol, (const double *)vol_c, (i64 *)lump_rowval, lump_nzval,
@@ -443,15 +409,14 @@ int32_t otmb_lump_and_spray(otmb_ctx *ctx, const uint8_t *wet3d, const uint8_t *
     const i64 tnnz = t_colptr[n_wet] - 1;
     if (tnnz < 0) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "T colptr");
     // one allocation: wet, mask, v3d, lwet3d, lwet, wet', vol, Tp, Ti, outputs
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_wet = take(G), o_mask = take(G), o_v = take(G * 8), o_lw3 = take(G * 8), o_lw = take(G * 8), o_wet2 = take(G),
-                 o_vol = take(N * 8 + 8), o_tp = take((N + 1) * 8), o_ti = take((size_t)tnnz * 8 + 8), o_lcp = take((N + 1) * 8),
-                 o_lrv = take(N * 8 + 8), o_lnz = take(N * 8 + 8), o_scp = take((N + 2) * 8), o_srv = take(N * 8 + 8),
-                 o_snz = take(N * 8 + 8), o_vc = take(N * 8 + 8);
+    DevArena A;
+    const size_t o_wet = A.take(G), o_mask = A.take(G), o_v = A.take(G * 8), o_lw3 = A.take(G * 8), o_lw = A.take(G * 8), o_wet2 = A.take(G),
+                 o_vol = A.take(N * 8 + 8), o_tp = A.take((N + 1) * 8), o_ti = A.take((size_t)tnnz * 8 + 8), o_lcp = A.take((N + 1) * 8),
+                 o_lrv = A.take(N * 8 + 8), o_lnz = A.take(N * 8 + 8), o_scp = A.take((N + 2) * 8), o_srv = A.take(N * 8 + 8),
+                 o_snz = A.take(N * 8 + 8), o_vc = A.take(N * 8 + 8);
     int32_t rc;
     DevBuf &pool = ctx->lump_host;
-    if ((rc = otmb_reserve(ctx, pool, off + 256))) return rc;
+    if ((rc = otmb_reserve(ctx, pool, A.total() + 256))) return rc;
     char *b = (char *)pool.p;
     HIP_TRY(ctx, hipMemcpyAsync(b + o_wet, wet3d, G, hipMemcpyHostToDevice, ctx->stream));
     if (mask) HIP_TRY(ctx, hipMemcpyAsync(b + o_mask, mask, G, hipMemcpyHostToDevice, ctx->stream));

@@ -16,8 +16,7 @@
 // and a column never sees another column.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
+#include "otmb_prims.h"
 #include "otmb_solve.h"
 
 typedef unsigned long long ull;
@@ -208,17 +207,12 @@ int32_t otmb_op_set_lines_dev(otmb_op *op, const int64_t *next) {
     HIP_TRY(ctx, hipSetDevice(op->device));
     hipStream_t st = ctx->stream;
     // everything is checked in scratch memory; the operator's own tables are written only afterwards
-    struct Scratch {
-        DevBuf b, scan;
-        ~Scratch() {
-            for (DevBuf *d : {&b, &scan})
-                if (d->p) (void)hipFree(d->p);
-        }
-    } sc;
+    DevScratch S;
+    DevBuf &tables = S.add(), &scan_tmp = S.add();
     int32_t rc;
     const size_t ints = 3 * (size_t)n + 2;  // nxt, prv, cnt (+ padding to 8 bytes)
-    if ((rc = otmb_reserve(ctx, sc.b, ints * 4 + 2 * (size_t)(n + 1) * 8 + 16))) return rc;
-    int *nxt = (int *)sc.b.p, *prv = nxt + n, *cnt = prv + n;
+    if ((rc = otmb_reserve(ctx, tables, ints * 4 + 2 * (size_t)(n + 1) * 8 + 16))) return rc;
+    int *nxt = (int *)tables.p, *prv = nxt + n, *cnt = prv + n;
     i64 *flag = (i64 *)(nxt + (ints & ~(size_t)1)), *pos = flag + (n + 1);
     ull *bad = (ull *)(pos + (n + 1));
     HIP_TRY(ctx, hipMemsetAsync(prv, 0xff, (size_t)n * 4, st));
@@ -240,12 +234,7 @@ int32_t otmb_op_set_lines_dev(otmb_op *op, const int64_t *next) {
         snprintf(msg, sizeof msg, "set_lines: index %lld is the successor of two unknowns (1-based; the first such index)", (long long)hb[1] + 1);
         return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, msg);
     }
-    size_t tmp = 0;
-    if (rocprim::exclusive_scan(nullptr, tmp, flag, pos, (i64)0, (size_t)(n + 1), rocprim::plus<i64>(), st) != hipSuccess)
-        return otmb_fail(ctx, OTMB_ERR_HIP, "scan (size)");
-    if ((rc = otmb_reserve(ctx, sc.scan, tmp + 16))) return rc;
-    if (rocprim::exclusive_scan(sc.scan.p, tmp, flag, pos, (i64)0, (size_t)(n + 1), rocprim::plus<i64>(), st) != hipSuccess)
-        return otmb_fail(ctx, OTMB_ERR_HIP, "scan");
+    if ((rc = otmb_exclusive_scan(ctx, scan_tmp, flag, pos, n + 1))) return rc;
     i64 nheads = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&nheads, pos + n, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));

@@ -24,12 +24,10 @@
 //   dst          the position of every stored entry (CSC order) in the two layouts above: "set values" is one streaming scatter.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include "otmb_op_fold.h"  // struct otmb_op, SP_ELL_MAX, SP_TCH; the walks over the layouts
+#include "otmb_prims.h"
 
-#define SP_GRID(n) dim3((unsigned)(((n) + 255) / 256 < 65536 ? (((n) + 255) / 256 > 0 ? ((n) + 255) / 256 : 1) : 65536)), dim3(256), 0, op->ctx->stream
+#define SP_GRID(n) OTMB_GRID_STRIDE(n, op->ctx->stream)
 
 // ---- device helpers ------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double sp_beta(const double *__restrict__ y, int bmode, double beta) {
@@ -185,41 +183,18 @@ __global__ __launch_bounds__(64) void spmv_cols_kernel(const i64 *__restrict__ c
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-static int32_t sp_reserve(otmb_op *op, DevBuf &b, size_t bytes) { return otmb_reserve(op->ctx, b, bytes > 0 ? bytes : 8); }
-static void sp_free(DevBuf &b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-}
+static int32_t sp_reserve(otmb_op *op, DevBuf &b, size_t bytes) { return otmb_reserve_some(op->ctx, b, bytes); }
 static void sp_free_all(otmb_op *op) {
     // the slots own the value arrays; an operator whose plan never stood has no slot yet, and nz and val are then its own
     for (OpSlot &s : op->slots) {
-        sp_free(s.nz);
-        sp_free(s.val);
+        otmb_free(s.nz);
+        otmb_free(s.val);
     }
     if (!op->slots.empty()) op->nz = op->val = DevBuf();
     op->slots.clear();
     for (DevBuf *b : {&op->cp, &op->rv, &op->nz, &op->dst, &op->elen, &op->sbase, &op->loff, &op->lrows, &op->val, &op->col, &op->xs, &op->ys, &op->ds, &op->sw, &op->st,
                       &op->pd, &op->mean.nz, &op->mean.val, &op->interp.nz, &op->interp.val, &op->season, &op->setab, &op->cb, &op->ln, &op->ob, &op->oh, &op->src})
-        sp_free(*b);
-}
-
-static int32_t sp_scan(otmb_op *op, DevBuf &tmpb, const i64 *in, i64 *out, i64 n) {
-    size_t tmp = 0;
-    otmb_ctx *ctx = op->ctx;
-    if (rocprim::exclusive_scan(nullptr, tmp, in, out, (i64)0, (size_t)n, rocprim::plus<i64>(), ctx->stream) != hipSuccess)
-        return otmb_fail(ctx, OTMB_ERR_HIP, "scan (size)");
-    int32_t rc;
-    if ((rc = sp_reserve(op, tmpb, tmp + 16))) return rc;
-    if (rocprim::exclusive_scan(tmpb.p, tmp, in, out, (i64)0, (size_t)n, rocprim::plus<i64>(), ctx->stream) != hipSuccess)
-        return otmb_fail(ctx, OTMB_ERR_HIP, "scan");
-    return OTMB_OK;
-}
-
-static int sp_bits(i64 v) {  // bits v needs: v < 2^bits
-    int b = 1;
-    while (b < 63 && (v >> b) != 0) ++b;
-    return b;
+        otmb_free(*b);
 }
 
 // The plan, on op->cp / a copy of rowval / op->nz already on the device (nnz known): checks, then the layouts.  Scratch is released before
@@ -228,14 +203,9 @@ static int32_t sp_plan(otmb_op *op, const i64 *rowval) {
     otmb_ctx *ctx = op->ctx;
     const i64 m = op->m, n = op->n, nnz = op->nnz;
     int32_t rc;
-    struct Scratch {  // freed on every return (hipFree waits for the kernels that use it)
-        DevBuf flags, iota, keys, perm, rowptr, tmpb, lflag, lent, lidx, swidth;
-        ~Scratch() {
-            for (DevBuf *b : {&flags, &iota, &keys, &perm, &rowptr, &tmpb, &lflag, &lent, &lidx, &swidth}) sp_free(*b);
-        }
-    } S;
-    DevBuf &flags = S.flags, &iota = S.iota, &keys = S.keys, &perm = S.perm, &rowptr = S.rowptr, &tmpb = S.tmpb, &lflag = S.lflag, &lent = S.lent,
-           &lidx = S.lidx, &swidth = S.swidth;
+    DevScratch S;
+    DevBuf &flags = S.add(), &iota = S.add(), &keys = S.add(), &perm = S.add(), &rowptr = S.add(), &tmpb = S.add(), &lflag = S.add(), &lent = S.add(),
+           &lidx = S.add(), &swidth = S.add();
     if ((rc = sp_reserve(op, flags, 16))) return rc;
     if ((rc = sp_reserve(op, op->rv, (size_t)nnz * 4))) return rc;
     if ((rc = sp_reserve(op, iota, (size_t)nnz * 8))) return rc;
@@ -258,16 +228,8 @@ static int32_t sp_plan(otmb_op *op, const i64 *rowval) {
     if ((rc = sp_reserve(op, rowptr, (size_t)(m + 1) * 8))) return rc;
     unsigned *sk = (unsigned *)keys.p;
     i64 *pm = (i64 *)perm.p;
-    if (nnz > 0) {
-        size_t tmp = 0;
-        const unsigned bits = (unsigned)sp_bits(m);
-        if (rocprim::radix_sort_pairs(nullptr, tmp, (const unsigned *)op->rv.p, sk, (const i64 *)iota.p, pm, (size_t)nnz, 0, bits, ctx->stream) != hipSuccess)
-            return otmb_fail(ctx, OTMB_ERR_HIP, "radix_sort_pairs (size)");
-        if ((rc = sp_reserve(op, tmpb, tmp + 16))) return rc;
-        if (rocprim::radix_sort_pairs(tmpb.p, tmp, (const unsigned *)op->rv.p, sk, (const i64 *)iota.p, pm, (size_t)nnz, 0, bits, ctx->stream) != hipSuccess)
-            return otmb_fail(ctx, OTMB_ERR_HIP, "radix_sort_pairs");
-    }
-    sp_free(iota);
+    if (nnz > 0 && (rc = otmb_sort_pairs(ctx, tmpb, (const unsigned *)op->rv.p, sk, (const i64 *)iota.p, pm, nnz, otmb_bits(m)))) return rc;
+    otmb_free(iota);
     i64 *rp = (i64 *)rowptr.p;
     hipLaunchKernelGGL(spmv_rowptr_kernel, SP_GRID(m + 1), (const unsigned *)sk, nnz, m, rp);
     // slices and long rows
@@ -284,9 +246,9 @@ static int32_t sp_plan(otmb_op *op, const i64 *rowval) {
         const i64 threads = (ns + 1) * 64;  // every slice and one more wave for the trailing zeros
         hipLaunchKernelGGL(spmv_slice_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, (const i64 *)rp, m, ns, el, sw, lf, le);
     }
-    if ((rc = sp_scan(op, tmpb, sw, sb, ns + 1))) return rc;
-    if ((rc = sp_scan(op, tmpb, lf, li, m + 1))) return rc;
-    if ((rc = sp_scan(op, tmpb, le, lo, m + 1))) return rc;
+    if ((rc = otmb_exclusive_scan(ctx, tmpb, sw, sb, ns + 1))) return rc;
+    if ((rc = otmb_exclusive_scan(ctx, tmpb, lf, li, m + 1))) return rc;
+    if ((rc = otmb_exclusive_scan(ctx, tmpb, le, lo, m + 1))) return rc;
     HIP_TRY(ctx, hipGetLastError());
     i64 tot[3] = {0, 0, 0};
     HIP_TRY(ctx, hipMemcpyAsync(&tot[0], sb + ns, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -365,7 +327,7 @@ static int32_t sp_create(otmb_ctx *ctx, int64_t m, int64_t n, const int64_t *col
     if (nnz > 0 && (!rowval || !nzval)) return otmb_fail(ctx, OTMB_ERR_INVALID_ARG, "null argument");
     struct Rows {  // rowval as given (Int64), for the plan's checks only
         DevBuf b;
-        ~Rows() { sp_free(b); }
+        ~Rows() { otmb_free(b); }
     } rows;
     if ((rc = sp_reserve(op, rows.b, (size_t)nnz * 8))) return rc;
     if ((rc = sp_reserve(op, op->nz, (size_t)nnz * 8))) return rc;
@@ -489,8 +451,8 @@ int32_t otmb_op_set_slots(otmb_op *op, int64_t nslots) {
         if (rc || e != hipSuccess) {
             (void)hipStreamSynchronize(ctx->stream);
             for (OpSlot &s : add) {
-                sp_free(s.nz);
-                sp_free(s.val);
+                otmb_free(s.nz);
+                otmb_free(s.val);
             }
             return rc ? rc : otmb_fail(ctx, OTMB_ERR_HIP, "set_slots: copying the selected slot");
         }
@@ -499,8 +461,8 @@ int32_t otmb_op_set_slots(otmb_op *op, int64_t nslots) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (enqueued work may still read the slots that go; a failure changes nothing)
         if (op->sel >= nslots) sp_select(op, 0);
         for (i64 s = nslots; s < have; ++s) {
-            sp_free(op->slots[(size_t)s].nz);
-            sp_free(op->slots[(size_t)s].val);
+            otmb_free(op->slots[(size_t)s].nz);
+            otmb_free(op->slots[(size_t)s].val);
         }
         op->slots.resize((size_t)nslots);
     }

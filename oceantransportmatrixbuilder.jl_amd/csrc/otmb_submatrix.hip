@@ -6,7 +6,7 @@
 //   1  rank tables: rrank[i] / crank[j] = the position of row i / column j in the selection, -1 when dropped (Int32; the same kernel checks
 //      the lists -- strictly ascending inside 1..m / 1..n -- and whether the selection is principal);
 //   2  keep[e] = 1 when the parent's stored entry e lies in a selected row and column (its column is col[dst[e]] of the parent's row layout);
-//   3  pos = the exclusive scan of keep (rocPRIM): the child's position of every kept entry, pos[nnz] = the child's nnz;
+//   3  pos = the exclusive scan of keep (otmb_prims.h): the child's position of every kept entry, pos[nnz] = the child's nnz;
 //   4  colptr'[j'] = 1 + pos[colptr[cols[j']] - 1], colptr'[nc] = 1 + pos[nnz]: dropped columns hold no kept entry in between;
 //   5  every kept entry to pos[e]: its row's rank (Int64, 1-based: what the plan of otmb_op_create_dev reads), src[pos[e]] = e (the gather
 //      table the child keeps) and the value of the parent's slot 0.
@@ -16,13 +16,10 @@
 // spmv_relayout_kernel, two entries per lane (16-byte loads of src and dst, a 16-byte store of nz), no temporary nzval.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "otmb_op.h"
+#include "otmb_prims.h"
 
 typedef unsigned long long ull;
-
-#define SB_GRID(n, st) dim3((unsigned)(((n) + 255) / 256 < 65536 ? (((n) + 255) / 256 > 0 ? ((n) + 255) / 256 : 1) : 65536)), dim3(256), 0, st
 
 // ---- the plan's kernels ------------------------------------------------------------------------------------------------------------------
 // rank[idx[p] - 1] = p for a list idx (1-based) that must ascend strictly inside 1..lim; bad = the first position p (0-based) whose entry is
@@ -90,39 +87,12 @@ __global__ __launch_bounds__(256) void sub_take_kernel(const double *__restrict_
     }
 }
 
-// out[e] = in[e] + 1: the Int32 row indices (0-based) and successors (-1 = none) back as otmb_op_create / otmb_op_set_lines took them
-__global__ __launch_bounds__(256) void sub_widen_kernel(const int *__restrict__ in, i64 cnt, i64 *__restrict__ out) {
-    for (i64 e = (i64)blockIdx.x * 256 + threadIdx.x; e < cnt; e += (i64)gridDim.x * 256) out[e] = (i64)in[e] + 1;
-}
-
 // ---- host ----------------------------------------------------------------------------------------------------------------------------------
-struct SbScratch {  // freed on every return (hipFree waits for the kernels that use it)
-    std::vector<DevBuf> bufs;
-    DevBuf &add() {
-        bufs.emplace_back();
-        return bufs.back();
-    }
-    SbScratch() { bufs.reserve(16); }  // (the references add() hands out stay valid)
-    ~SbScratch() {
-        for (DevBuf &b : bufs)
-            if (b.p) (void)hipFree(b.p);
-    }
-};
-static int32_t sb_reserve(otmb_ctx *ctx, DevBuf &b, size_t bytes) { return otmb_reserve(ctx, b, bytes > 0 ? bytes : 8); }
-
-static int32_t sb_scan(otmb_ctx *ctx, DevBuf &tmpb, const i64 *in, i64 *out, i64 n) {
-    size_t tmp = 0;
-    if (rocprim::exclusive_scan(nullptr, tmp, in, out, (i64)0, (size_t)n, rocprim::plus<i64>(), ctx->stream) != hipSuccess)
-        return otmb_fail(ctx, OTMB_ERR_HIP, "scan (size)");
-    int32_t rc;
-    if ((rc = sb_reserve(ctx, tmpb, tmp + 16))) return rc;
-    if (rocprim::exclusive_scan(tmpb.p, tmp, in, out, (i64)0, (size_t)n, rocprim::plus<i64>(), ctx->stream) != hipSuccess)
-        return otmb_fail(ctx, OTMB_ERR_HIP, "scan");
-    return OTMB_OK;
-}
+// the Int32 row indices (0-based) and successors (-1 = none) back as otmb_op_create / otmb_op_set_lines took them: + 1, Int64
+static void sb_widen(hipStream_t st, const int *in, i64 cnt, i64 *out) { otmb_widen(st, in, cnt, 1, out); }
 
 static void sb_take(otmb_op *child, const double *pnz, const OpSlot &to) {
-    hipLaunchKernelGGL(sub_take_kernel, SB_GRID((child->nnz + 1) / 2, child->ctx->stream), pnz, (const i64 *)child->src.p, (const i64 *)child->dst.p, child->nnz,
+    hipLaunchKernelGGL(sub_take_kernel, OTMB_GRID_STRIDE((child->nnz + 1) / 2, child->ctx->stream), pnz, (const i64 *)child->src.p, (const i64 *)child->dst.p, child->nnz,
                        (double *)to.nz.p, (double *)to.val.p);
 }
 
@@ -141,18 +111,18 @@ static int32_t sb_submatrix(otmb_op *parent, i64 nr, const i64 *rows, i64 nc, co
     hipStream_t st = ctx->stream;
     const i64 m = parent->m, n = parent->n, nnz = parent->nnz;
     int32_t rc;
-    SbScratch S;
+    DevScratch S;
     DevBuf &ranks = S.add(), &words = S.add();
-    if ((rc = sb_reserve(ctx, ranks, (size_t)(m + n) * 4))) return rc;
-    if ((rc = sb_reserve(ctx, words, 24))) return rc;
+    if ((rc = otmb_reserve_some(ctx, ranks, (size_t)(m + n) * 4))) return rc;
+    if ((rc = otmb_reserve_some(ctx, words, 24))) return rc;
     int *rrank = (int *)ranks.p, *crank = rrank + m;
     ull *bad = (ull *)words.p;  // the first offending row position, column position; whether rows and cols differ
     unsigned *differs = (unsigned *)(bad + 2);
     if (m + n > 0) HIP_TRY(ctx, hipMemsetAsync(rrank, 0xff, (size_t)(m + n) * 4, st));
     HIP_TRY(ctx, hipMemsetAsync(bad, 0xff, 16, st));
     HIP_TRY(ctx, hipMemsetAsync(differs, 0, 8, st));
-    if (nr > 0) hipLaunchKernelGGL(sub_rank_kernel, SB_GRID(nr, st), rows, nr, m, rrank, bad, (const i64 *)nullptr, differs);
-    if (nc > 0) hipLaunchKernelGGL(sub_rank_kernel, SB_GRID(nc, st), cols, nc, n, crank, bad + 1, nr == nc ? rows : (const i64 *)nullptr, differs);
+    if (nr > 0) hipLaunchKernelGGL(sub_rank_kernel, OTMB_GRID_STRIDE(nr, st), rows, nr, m, rrank, bad, (const i64 *)nullptr, differs);
+    if (nc > 0) hipLaunchKernelGGL(sub_rank_kernel, OTMB_GRID_STRIDE(nc, st), cols, nc, n, crank, bad + 1, nr == nc ? rows : (const i64 *)nullptr, differs);
     HIP_TRY(ctx, hipGetLastError());
     ull hw[3] = {0, 0, 0};
     HIP_TRY(ctx, hipMemcpyAsync(hw, bad, 24, hipMemcpyDeviceToHost, st));
@@ -162,12 +132,12 @@ static int32_t sb_submatrix(otmb_op *parent, i64 nr, const i64 *rows, i64 nc, co
     const bool principal = nr == nc && (unsigned)hw[2] == 0;
     // the kept entries and their positions
     DevBuf &keepb = S.add(), &posb = S.add(), &tmpb = S.add();
-    if ((rc = sb_reserve(ctx, keepb, (size_t)(nnz + 1) * 8))) return rc;
-    if ((rc = sb_reserve(ctx, posb, (size_t)(nnz + 1) * 8))) return rc;
+    if ((rc = otmb_reserve_some(ctx, keepb, (size_t)(nnz + 1) * 8))) return rc;
+    if ((rc = otmb_reserve_some(ctx, posb, (size_t)(nnz + 1) * 8))) return rc;
     i64 *keep = (i64 *)keepb.p, *pos = (i64 *)posb.p;
-    hipLaunchKernelGGL(sub_keep_kernel, SB_GRID(nnz + 1, st), (const int *)parent->rv.p, (const int *)parent->col.p, (const i64 *)parent->dst.p, nnz,
+    hipLaunchKernelGGL(sub_keep_kernel, OTMB_GRID_STRIDE(nnz + 1, st), (const int *)parent->rv.p, (const int *)parent->col.p, (const i64 *)parent->dst.p, nnz,
                        (const int *)rrank, (const int *)crank, keep);
-    if ((rc = sb_scan(ctx, tmpb, keep, pos, nnz + 1))) return rc;
+    if ((rc = otmb_exclusive_scan(ctx, tmpb, keep, pos, nnz + 1))) return rc;
     HIP_TRY(ctx, hipGetLastError());
     i64 total = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&total, pos + nnz, 8, hipMemcpyDeviceToHost, st));
@@ -185,13 +155,13 @@ static int32_t sb_submatrix(otmb_op *parent, i64 nr, const i64 *rows, i64 nc, co
     op->n = nc;
     op->nnz = total;
     DevBuf &rowsb = S.add();
-    if ((rc = sb_reserve(ctx, op->cp, (size_t)(nc + 1) * 8))) return rc;
-    if ((rc = sb_reserve(ctx, rowsb, (size_t)total * 8))) return rc;
-    if ((rc = sb_reserve(ctx, op->nz, (size_t)total * 8))) return rc;
-    if ((rc = sb_reserve(ctx, op->src, (size_t)total * 8))) return rc;
-    hipLaunchKernelGGL(sub_colptr_kernel, SB_GRID(nc + 1, st), (const i64 *)parent->cp.p, cols, nc, (const i64 *)pos, nnz, (i64 *)op->cp.p);
+    if ((rc = otmb_reserve_some(ctx, op->cp, (size_t)(nc + 1) * 8))) return rc;
+    if ((rc = otmb_reserve_some(ctx, rowsb, (size_t)total * 8))) return rc;
+    if ((rc = otmb_reserve_some(ctx, op->nz, (size_t)total * 8))) return rc;
+    if ((rc = otmb_reserve_some(ctx, op->src, (size_t)total * 8))) return rc;
+    hipLaunchKernelGGL(sub_colptr_kernel, OTMB_GRID_STRIDE(nc + 1, st), (const i64 *)parent->cp.p, cols, nc, (const i64 *)pos, nnz, (i64 *)op->cp.p);
     if (total > 0)
-        hipLaunchKernelGGL(sub_scatter_kernel, SB_GRID(nnz, st), (const i64 *)keep, (const i64 *)pos, (const int *)parent->rv.p,
+        hipLaunchKernelGGL(sub_scatter_kernel, OTMB_GRID_STRIDE(nnz, st), (const i64 *)keep, (const i64 *)pos, (const int *)parent->rv.p,
                            (const double *)parent->slots[0].nz.p, nnz, (const int *)rrank, (i64 *)rowsb.p, (i64 *)op->src.p, (double *)op->nz.p);
     HIP_TRY(ctx, hipGetLastError());
     if ((rc = sp_plan_resident(op, (const i64 *)rowsb.p))) return rc;
@@ -204,8 +174,8 @@ static int32_t sb_submatrix(otmb_op *parent, i64 nr, const i64 *rows, i64 nc, co
     // the lines of a principal selection, through the line setup that makes the predecessor and head tables
     if (principal && parent->lines && parent->m == parent->n) {
         DevBuf &nextb = S.add();
-        if ((rc = sb_reserve(ctx, nextb, (size_t)nr * 8))) return rc;
-        if (nr > 0) hipLaunchKernelGGL(sub_lines_kernel, SB_GRID(nr, st), rows, nr, (const int *)parent->ln.p, (const int *)rrank, (i64 *)nextb.p);
+        if ((rc = otmb_reserve_some(ctx, nextb, (size_t)nr * 8))) return rc;
+        if (nr > 0) hipLaunchKernelGGL(sub_lines_kernel, OTMB_GRID_STRIDE(nr, st), rows, nr, (const int *)parent->ln.p, (const int *)rrank, (i64 *)nextb.p);
         HIP_TRY(ctx, hipGetLastError());
         if ((rc = otmb_op_set_lines_dev(op, (const int64_t *)nextb.p))) return rc;
     }
@@ -250,9 +220,9 @@ int32_t otmb_op_submatrix(otmb_op *parent, int64_t nr, const int64_t *rows, int6
     int32_t rc;
     if ((rc = sb_submatrix_args(parent, nr, rows, nc, cols, out))) return rc;
     otmb_ctx *ctx = parent->ctx;
-    SbScratch S;
+    DevScratch S;
     DevBuf &lists = S.add();
-    if ((rc = sb_reserve(ctx, lists, (size_t)(nr + nc) * 8))) return rc;
+    if ((rc = otmb_reserve_some(ctx, lists, (size_t)(nr + nc) * 8))) return rc;
     i64 *dr = (i64 *)lists.p, *dc = dr + nr;
     if (nr > 0) HIP_TRY(ctx, hipMemcpyAsync(dr, rows, (size_t)nr * 8, hipMemcpyHostToDevice, ctx->stream));
     if (nc > 0) HIP_TRY(ctx, hipMemcpyAsync(dc, cols, (size_t)nc * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -288,7 +258,7 @@ int32_t otmb_op_fetch_dev(const otmb_op *op, int64_t slot, int64_t *colptr, int6
     HIP_TRY(ctx, hipSetDevice(op->device));
     hipStream_t st = ctx->stream;
     if (colptr) HIP_TRY(ctx, hipMemcpyAsync(colptr, op->cp.p, (size_t)(op->n + 1) * 8, hipMemcpyDeviceToDevice, st));
-    if (rowval && op->nnz > 0) hipLaunchKernelGGL(sub_widen_kernel, SB_GRID(op->nnz, st), (const int *)op->rv.p, op->nnz, rowval);
+    if (rowval && op->nnz > 0) sb_widen(st, (const int *)op->rv.p, op->nnz, rowval);
     if (nzval && op->nnz > 0) HIP_TRY(ctx, hipMemcpyAsync(nzval, from->nz.p, (size_t)op->nnz * 8, hipMemcpyDeviceToDevice, st));
     HIP_TRY(ctx, hipGetLastError());
     return OTMB_OK;
@@ -302,12 +272,12 @@ int32_t otmb_op_fetch(const otmb_op *op, int64_t slot, int64_t *colptr, int64_t 
     if ((rc = sb_slot(op, slot, "fetch", from))) return rc;
     HIP_TRY(ctx, hipSetDevice(op->device));
     hipStream_t st = ctx->stream;
-    SbScratch S;
+    DevScratch S;
     if (colptr) HIP_TRY(ctx, hipMemcpyAsync(colptr, op->cp.p, (size_t)(op->n + 1) * 8, hipMemcpyDeviceToHost, st));
     if (rowval && op->nnz > 0) {  // widened on the device, in scratch: the operator is not touched
         DevBuf &wide = S.add();
-        if ((rc = sb_reserve(ctx, wide, (size_t)op->nnz * 8))) return rc;
-        hipLaunchKernelGGL(sub_widen_kernel, SB_GRID(op->nnz, st), (const int *)op->rv.p, op->nnz, (i64 *)wide.p);
+        if ((rc = otmb_reserve_some(ctx, wide, (size_t)op->nnz * 8))) return rc;
+        sb_widen(st, (const int *)op->rv.p, op->nnz, (i64 *)wide.p);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(rowval, wide.p, (size_t)op->nnz * 8, hipMemcpyDeviceToHost, st));
     }
@@ -322,7 +292,7 @@ int32_t otmb_op_get_lines_dev(const otmb_op *op, int64_t *next, int32_t *has_lin
     if (has_lines) *has_lines = op->lines ? 1 : 0;
     if (!op->lines || !next || op->n == 0) return OTMB_OK;
     HIP_TRY(ctx, hipSetDevice(op->device));
-    hipLaunchKernelGGL(sub_widen_kernel, SB_GRID(op->n, ctx->stream), (const int *)op->ln.p, op->n, next);
+    sb_widen(ctx->stream, (const int *)op->ln.p, op->n, next);
     HIP_TRY(ctx, hipGetLastError());
     return OTMB_OK;
 }
@@ -333,11 +303,11 @@ int32_t otmb_op_get_lines(const otmb_op *op, int64_t *next, int32_t *has_lines) 
     if (has_lines) *has_lines = op->lines ? 1 : 0;
     if (!op->lines || !next || op->n == 0) return OTMB_OK;
     HIP_TRY(ctx, hipSetDevice(op->device));
-    SbScratch S;
+    DevScratch S;
     DevBuf &wide = S.add();
     int32_t rc;
-    if ((rc = sb_reserve(ctx, wide, (size_t)op->n * 8))) return rc;
-    hipLaunchKernelGGL(sub_widen_kernel, SB_GRID(op->n, ctx->stream), (const int *)op->ln.p, op->n, (i64 *)wide.p);
+    if ((rc = otmb_reserve_some(ctx, wide, (size_t)op->n * 8))) return rc;
+    sb_widen(ctx->stream, (const int *)op->ln.p, op->n, (i64 *)wide.p);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(next, wide.p, (size_t)op->n * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
