@@ -52,7 +52,9 @@ typedef enum {
                                     * entry point that cannot add it (the asynchronous and the multi-slab builds): use otmb_transportmatrix_plan[_dev] */
     OTMB_ERR_SINGULAR_PRECONDITIONER = 18, /* otmb_op_solve: an entry of diag(σ·I + diag(d) + A) -- with OTMB_PRECOND_LINES: a pivot of the line
                                               factorisation -- is zero or not finite (the message names the first) */
-    OTMB_ERR_NOT_CONVERGED = 19    /* otmb_op_solve: some column stopped for another reason than convergence (reason[], relres[], iters[] say which) */
+    OTMB_ERR_NOT_CONVERGED = 19,   /* otmb_op_solve: some column stopped for another reason than convergence (reason[], relres[], iters[] say which) */
+    OTMB_ERR_TSINK_NAN = 20,       /* "Tsink contains NaNs."  otmb_build_sink: the wording of the reference's own operators (no reference function) */
+    OTMB_ERR_PATTERN_NOT_CONTAINED = 21 /* otmb_op_add_matrix: B stores an entry the operator does not (the message names the first; nothing was written) */
 } otmb_status;
 
 /* gridmetrics.gridtopology (src/gridtopology.jl:1-16) */
@@ -624,6 +626,30 @@ int32_t otmb_spadd_fill_dev(otmb_ctx *ctx, int64_t n, const int64_t *Ap, const i
 int32_t otmb_spadd(otmb_ctx *ctx, int64_t n, const int64_t *Ap, const int64_t *Ai, const double *Ax, const int64_t *Bp,
                    const int64_t *Bi, const double *Bx, int64_t *Cp, int64_t *Ci, double *Cx, int64_t *nnz_out);
 
+/* ---- buildTsink: the settling operator S of particles that sink through the water column at a speed w >= 0 (m/s, positive downward),
+ *      ∂x/∂t + (T + S)·x = …  No function of the reference builds it: the contract below is this library's own, written in the style of
+ *      vertical_diffusion_operator_sparse_entries (src/matrixbuilding.jl:438-479) and restated in numpy by tests/sink_ref.py.
+ * For every wet cell c at (i, j, k), ascending in wet order: a = area2d[i, j], w_c = the speed at the BOTTOM face of c, b = the wet cell at
+ *      (i, j, k + 1) if there is one.  Entry (c, c) = (w_c * a) / v3d[c]; if b exists, entry (b, c) = -((w_c * a) / v3d[b]).  One IEEE
+ *      operation per step, no FMA.  closed != 0 (a closed seafloor): a cell without a wet cell below stores (c, c) = +0.0; closed == 0: it
+ *      stores the value above, and what leaves through the seafloor is buried.
+ * The pattern is a grid constant under both options: nnz = n_wet + the wet cells with a wet cell below; CSC with ascending rows (b > c in wet
+ *      order), every diagonal entry stored.  Its entries are among those TκVdeep stores, so the pattern lies inside T's: otmb_op_add_matrix.
+ * w by w_form: 0 the scalar w_scalar (w unused); 1 w[nz], the bottom face of each level; 2 w[nx*ny*nz], the bottom face of each cell.  The
+ *      three give the same bits where they agree.  w is read on wet cells only (garbage on land does not matter).  A negative, NaN or
+ *      infinite w on the bottom face of a wet cell, n_wet or a size below zero, another w_form: OTMB_ERR_INVALID_ARG; a NaN value in the
+ *      result (from the metrics): OTMB_ERR_TSINK_NAN; lwet / lwet3d that are not makeindices' (each index is checked before anything is read
+ *      through it): OTMB_ERR_NONCANONICAL_INDICES; nnz > cap: OTMB_ERR_CAPACITY.  *nnz (host memory) is written whenever the checks on w,
+ *      the result and the indices passed.  Nothing is written to colptr / rowval / nzval unless the call returns OTMB_OK.
+ * colptr: n_wet + 1; rowval, nzval: capacity cap entries (2 * n_wet always suffices).
+ * otmb_build_sink_dev: device pointers, on the context's stream (the call waits for its own checks).  otmb_build_sink: host pointers. */
+int32_t otmb_build_sink_dev(otmb_ctx *ctx, int32_t w_form, double w_scalar, const double *w, const double *v3d, const double *area2d,
+                            const int64_t *lwet3d, const int64_t *lwet, int64_t n_wet, int64_t nx, int64_t ny, int64_t nz, int32_t closed,
+                            int64_t *colptr, int64_t *rowval, double *nzval, int64_t cap, int64_t *nnz);
+int32_t otmb_build_sink(otmb_ctx *ctx, int32_t w_form, double w_scalar, const double *w, const double *v3d, const double *area2d,
+                        const int64_t *lwet3d, const int64_t *lwet, int64_t n_wet, int64_t nx, int64_t ny, int64_t nz, int32_t closed,
+                        int64_t *colptr, int64_t *rowval, double *nzval, int64_t cap, int64_t *nnz);
+
 /* ---- lump_and_spray(wet3D, vol, T, mask = trues(size(wet3D)); di = 2, dj = 2, dk = 1) -- src/extratools.jl:38-119:
  *      the coarsening operators LUMP (Nc x N, volume weighted: LUMP * x is the coarse vector), SPRAY (N x Nc, ones:
  *      LUMP * T * SPRAY is the coarse operator) and the coarse volumes vol_c.  Cells are lumped in di x dj x dk blocks,
@@ -792,6 +818,28 @@ int32_t otmb_op_slots(const otmb_op *op, int64_t *nslots, int64_t *selected);
  *      usable.  otmb_op_combine_slots_dev enqueues on the context's stream; otmb_op_combine_slots waits for it.                          */
 int32_t otmb_op_combine_slots_dev(otmb_op *op, const double *w, int64_t dst);
 int32_t otmb_op_combine_slots(otmb_op *op, const double *w, int64_t dst);
+
+/* ---- otmb_op_add_matrix[_dev]: slot = slot + α·B in place, for a matrix B whose pattern lies inside the operator's -- the settling operator
+ *      of otmb_build_sink added to a year of monthly T, or a diffusivity retuned without a rebuild (T is linear in κH, κVML and κVdeep:
+ *      B = TκH, α = κ'/κ - 1).  The pattern, the layouts, the lines and every other slot stay as they are.
+ * B: m x n CSC arrays (Int64, 1-based) of the operator's shape, rows in any order.  Checked before anything is read through them, each
+ *      OTMB_ERR_INVALID_ARG: m, n are the operator's, colptr[1] == 1, colptr non-decreasing, every row in 1..m.
+ * Matching: the stored entry (r, c) of B belongs to the FIRST stored entry (r, c) of the operator's column c in stored order (an operator may
+ *      store unsorted and duplicate rows: later duplicates are never written).  An entry of B without a partner:
+ *      OTMB_ERR_PATTERN_NOT_CONTAINED, the message names the first such entry in B's stored order (its 1-based position, row and column).
+ *      Match first, write afterwards: after any error every slot has the bits it had.
+ * In bits, for each requested slot, each matched position p and the entries e of B that belong to it, in B's stored order:
+ *      nz[p] = nz[p] + (α * B[e]), one multiplication and one addition, no FMA; the row layout's copy of p receives the same bits.  Entries B
+ *      does not name are not rewritten.  α == 0 (and an empty B, and nsel == 0) checks everything and writes nothing.
+ * slots: HOST array (both variants) of nsel different slots in 0..nslots-1, or NULL: every slot.  α must be finite.
+ * Cost: a match of Σ_c len_B(c)·len_A(c) index comparisons (columns of a transport matrix hold at most 19 entries), once per call; then one
+ *      streaming launch over B's entries that updates all requested slots: a read-modify-write of nnz(B) entries in two arrays per slot.
+ * A child of otmb_op_submatrix does not follow: otmb_op_take_values refreshes it.
+ * otmb_op_add_matrix_dev: B in device memory, on the context's stream (the call waits for its own checks).  otmb_op_add_matrix: host pointers. */
+int32_t otmb_op_add_matrix_dev(otmb_op *op, int64_t m, int64_t n, const int64_t *colptr, const int64_t *rowval, const double *nzval, double alpha,
+                               int64_t nsel, const int64_t *slots);
+int32_t otmb_op_add_matrix(otmb_op *op, int64_t m, int64_t n, const int64_t *colptr, const int64_t *rowval, const double *nzval, double alpha,
+                           int64_t nsel, const int64_t *slots);
 
 /* ---- The operator's domain: A[rows, cols] as a new resident operator, without leaving the device -- prescribed (Dirichlet) boundary values
  *      (A_II·x_I = s_I - A_IB·x_B needs the blocks A[I, I] and A[I, B]), regional problems -- and what an operator can say of itself.

@@ -40,7 +40,7 @@ export DeviceOperator, setvalues!
 export solve!, solve
 export setlines!, verticallines, precondition!
 export setslots!, selectslot!, slots, step!   # (`step` extends Base.step for this module's operators: nothing to export)
-export periodic!, periodic, combineslots!
+export periodic!, periodic, combineslots!, addmatrix!
 export observe, stepobserve!
 export stepsched!, periodicsched!
 export stepinterp!, periodicinterp!, interpschedule
@@ -497,6 +497,23 @@ function combineslots!(D::DeviceOperator, w::Vector{Float64}, dst::Integer)
         check(ccall(slots_fn, Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), D.handle, nslots, C_NULL))
         length(w) == nslots[] || throw(DimensionMismatch("w has $(length(w)) weights, the operator $(nslots[]) slots"))
         check(ccall(combine_slots_fn, Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64), D.handle, w, Int64(dst - 1)))
+    end
+    return D
+end
+# `addmatrix!(D, B; alpha = 1.0, slots = nothing)`: slot = slot + alpha·B in place (otmb_op_add_matrix; include/otmb.h states the contract) for a
+# matrix B of D's size whose pattern lies inside D's -- `buildTsink`'s S added to a year of monthly T, or a diffusivity retuned without a
+# rebuild (T is linear in κH: B = TκH, alpha = κ′/κ - 1).  slots: `nothing` (every slot), a slot or a vector of different slots, numbered from 1.
+# Each stored entry of B goes to the first stored entry of D with its row and column; an entry D does not store throws (status 21, naming the
+# first) and leaves every slot untouched; alpha == 0 checks the pattern and writes nothing.  A submatrix does not follow: `takevalues!`.
+function addmatrix!(D::DeviceOperator, B::SparseMatrixCSC{Float64,Int64}; alpha::Real = 1.0, slots::Union{Nothing,Integer,AbstractVector{<:Integer}} = nothing)
+    size(B) == size(D) || throw(DimensionMismatch("B is $(size(B)), the operator $(size(D))"))
+    sel = slots === nothing ? Int64[] : Int64[s - 1 for s in slots]
+    nsel = Int64(length(sel))
+    lock(CALL_LOCK) do
+        D.handle == C_NULL && throw(ArgumentError("the DeviceOperator has been released"))
+        add_matrix_fn = sym(:otmb_op_add_matrix)
+        check(ccall(add_matrix_fn, Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Float64, Int64, Ptr{Int64}),
+            D.handle, D.m, D.n, B.colptr, B.rowval, B.nzval, Float64(alpha), nsel, slots === nothing ? C_NULL : sel))
     end
     return D
 end
@@ -1339,6 +1356,34 @@ buildTadv(; ϕ, gridmetrics, indices, ρ, upwind = true) = build_operator(2; gri
 buildTκH(; gridmetrics, indices, ρ = 1035.0, κH) = build_operator(3; gridmetrics, indices, κ = (κH, 0.1, 1.0e-5))
 buildTκVML(; mlotst, gridmetrics, indices, κVML) = build_operator(4; gridmetrics, indices, mlotst, κ = (500.0, κVML, 1.0e-5))
 buildTκVdeep(; mlotst = nothing, gridmetrics, indices, κVdeep) = build_operator(5; gridmetrics, indices, κ = (500.0, 0.1, κVdeep))
+
+# `buildTsink(; w, gridmetrics, indices, seafloor = :open)`: the settling operator S of particles that sink at the speed w >= 0 (m/s, positive
+# downward), ∂x/∂t + (T + S)·x = … (otmb_build_sink).  No function of the reference builds it: include/otmb.h states the contract.  w: a number,
+# nz values (the bottom face of each level) or an (nx, ny, nz) array (`missing` on land is fine: land is never read).  seafloor = :open: what
+# reaches the seafloor is buried; :closed: the bottom cell keeps it (a stored 0.0).  S's pattern lies inside T's: `addmatrix!(D, S)`.
+function buildTsink(; w, gridmetrics, indices, seafloor::Symbol = :open)
+    seafloor in (:open, :closed) || throw(ArgumentError("seafloor must be :open or :closed, not :$seafloor"))
+    (; v3D, area2D) = gridmetrics
+    nx, ny, nz = size(v3D)
+    v = asis(v3D); ar = asis(area2D)
+    lw3 = lwet3d_of(indices, false)
+    lw = indices.Lwet isa Vector{Int64} ? indices.Lwet : Vector{Int64}(indices.Lwet)
+    N = Int64(indices.N)
+    wform = w isa Number ? Int32(0) : ndims(w) == 1 ? Int32(1) : Int32(2)
+    wa = w isa Number ? Float64[] : f64(w)
+    w isa Number || size(wa) == (nz,) || size(wa) == (nx, ny, nz) || throw(DimensionMismatch("w is $(size(wa)), expected a number, ($nz,) or $((nx, ny, nz))"))
+    cap = max(2N, 1)
+    colptr = Vector{Int64}(undef, N + 1); rowval = Vector{Int64}(undef, cap); nzval = Vector{Float64}(undef, cap)
+    k = Ref{Int64}(0)
+    lock(CALL_LOCK) do
+        build_sink_fn = sym(:otmb_build_sink)
+        check(ccall(build_sink_fn, Int32,
+            (Ptr{Cvoid}, Int32, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Int64, Int64, Int64, Int64, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Int64}),
+            context(), wform, w isa Number ? Float64(w) : 0.0, wa, v, ar, lw3, lw, N, nx, ny, nz, Int32(seafloor === :closed), colptr, rowval, nzval, cap, k))
+    end
+    resize!(rowval, k[]); resize!(nzval, k[])
+    return SparseMatrixCSC{Float64,Int64}(N, N, colptr, rowval, nzval)
+end
 
 # the arguments of one build, flattened for the C ABI; `keep` holds every converted array alive across the calls
 function tmargs(ϕ, mlotst, gridmetrics, indices, ρ, κH, κVML, κVdeep, upwind, operators, reuse_grid, ignore_ops::Int32, given = nothing,

@@ -20,7 +20,7 @@ def __getattr__(name):
     if name in ("makeindices", "facefluxesfrommasstransport", "facefluxes", "transportmatrix", "velocity2fluxes",
                 "fluxes2velocity", "facefluxesfromvelocities", "interpolateontodefaultCgrid", "lump_and_spray", "as2D", "as3D",
                 "spadd", "coarsen", "DeviceOperator", "bolus_GM_velocity",
-                "buildTadv", "buildTκH", "buildTκVML", "buildTκVdeep", "buildTkH", "buildTkVML", "buildTkVdeep"):
+                "buildTadv", "buildTκH", "buildTκVML", "buildTκVdeep", "buildTkH", "buildTkVML", "buildTkVdeep", "buildTsink"):
         from . import api
         return getattr(api, name)
     raise AttributeError(name)

@@ -732,6 +732,40 @@ def buildTκVdeep(*, mlotst=None, gridmetrics, indices, κVdeep=None, kappaVdeep
     return _build_operator("TκVdeep", gridmetrics=gridmetrics, indices=indices, kappa=(500.0, 0.1, float(k)), device=device)
 
 
+def buildTsink(*, w, gridmetrics, indices, seafloor="open", device=0):
+    """The settling operator S of particles that sink at the speed w >= 0 (m/s, positive downward): ∂x/∂t + (T + S)·x = … (otmb_build_sink;
+    include/otmb.h states the contract, which is this library's own -- no function of the reference builds S -- and tests/sink_ref.py
+    restates it).  w: a number, nz values (the bottom face of each level) or an (nx, ny, nz) array (the bottom face of each cell; values
+    on land are never read).  seafloor = "open" (default): what reaches the seafloor leaves (is buried); "closed": the bottom cell of a
+    column keeps it (a stored +0.0 on its diagonal).  The pattern -- the diagonal and (cell below, cell) -- is a grid constant and lies
+    inside T's: DeviceOperator.add_matrix adds S to resident slots in place.  A negative, NaN or infinite w on a wet cell raises
+    OtmbError (INVALID_ARG), a NaN in the result "Tsink contains NaNs."."""
+    ctx = context(device)
+    closed = capi.seafloor_code(seafloor)
+    v3d = _f64(gridmetrics["v3D"])
+    nx, ny, nz = v3d.shape
+    area = _f64(gridmetrics["area2D"])
+    lwet3d = np.asfortranarray(indices["Lwet3D"], dtype=np.int64)
+    lwet = np.ascontiguousarray(indices["Lwet"], dtype=np.int64)
+    N = int(indices["N"])
+    if area.shape != (nx, ny) or lwet3d.shape != v3d.shape or lwet.shape != (N,):
+        raise capi.OtmbError(11, f"DimensionMismatch: v3D of {v3d.shape}, area2D of {area.shape}, Lwet3D of {lwet3d.shape}, Lwet of {lwet.shape}, N = {N}")
+    if np.ndim(w) == 0:
+        form, ws, wa = 0, float(w), None
+    else:
+        wa = _f64(w)
+        if wa.shape not in ((nz,), (nx, ny, nz)):
+            raise capi.OtmbError(11, f"DimensionMismatch: w of {wa.shape}, expected a number, {(nz,)} or {(nx, ny, nz)}")
+        form, ws = (1 if wa.ndim == 1 else 2), 0.0
+    cap = max(2 * N, 1)
+    cp, rv, nzv = np.empty(N + 1, dtype=np.int64), np.empty(cap, dtype=np.int64), np.empty(cap, dtype=np.float64)
+    nnz = C.c_int64(0)
+    ctx.check(capi.lib().otmb_build_sink(ctx.handle, form, ws, None if wa is None else wa.ctypes.data, v3d.ctypes.data, area.ctypes.data, lwet3d.ctypes.data,
+                                         lwet.ctypes.data, N, nx, ny, nz, closed, cp.ctypes.data, rv.ctypes.data, nzv.ctypes.data, cap, C.byref(nnz)))
+    k = int(nnz.value)
+    return SparseMatrixCSC(N, N, cp, rv[:k].copy(), nzv[:k].copy())
+
+
 buildTkH, buildTkVML, buildTkVdeep = buildTκH, buildTκVML, buildTκVdeep  # ASCII aliases
 
 
@@ -860,8 +894,8 @@ class DeviceOperator(OperatorCalls):
     The same C calls as the Julia shim's DeviceOperator: otmb_op_create; mul! -> otmb_op_mul; setvalues! -> otmb_op_set_values; solve! ->
     otmb_op_solve_pc; setlines! -> otmb_op_set_lines; precondition! -> otmb_op_precond; setslots! / selectslot! / step! -> otmb_op_set_slots /
     otmb_op_select_slot / otmb_op_step; observe / stepobserve! -> otmb_op_observe / otmb_op_step_obs; periodic! -> otmb_op_periodic (outer = :mean: otmb_op_periodic_pc); combineslots! ->
-    otmb_op_combine_slots; submatrix / getindex -> otmb_op_submatrix; takevalues! -> otmb_op_take_values; sparse -> otmb_op_fetch; lines ->
-    otmb_op_get_lines; the finalizer -> otmb_op_destroy.  submatrix, take_values, to_csc, lines, precondition, solve, observe, step and periodic are OperatorCalls' (a matrix d:
+    otmb_op_combine_slots; addmatrix! -> otmb_op_add_matrix; submatrix / getindex -> otmb_op_submatrix; takevalues! -> otmb_op_take_values; sparse -> otmb_op_fetch; lines ->
+    otmb_op_get_lines; the finalizer -> otmb_op_destroy.  add_matrix, submatrix, take_values, to_csc, lines, precondition, solve, observe, step and periodic are OperatorCalls' (a matrix d:
     the otmb_op_*_dk exports), over the numpy hooks below: a 1-D input gives a 1-D result, 2-D results are Fortran-ordered."""
 
     def __init__(self, A, *, device=0):
@@ -918,6 +952,14 @@ class DeviceOperator(OperatorCalls):
 
     def _csc(self, cp, rv, nz):
         return SparseMatrixCSC(self.shape[0], self.shape[1], cp, rv, nz)
+
+    def _csc_arrays(self, B):
+        if tuple(B.shape) != self.shape:
+            raise capi.OtmbError(11, f"DimensionMismatch: operator of {self.shape}, B of {tuple(B.shape)}")
+        p, i, v = (np.ascontiguousarray(x, dtype=t) for x, t in ((B.colptr, np.int64), (B.rowval, np.int64), (B.nzval, np.float64)))
+        if len(p) != B.n + 1 or len(i) < p[-1] - 1 or len(v) < p[-1] - 1:
+            raise capi.OtmbError(11, f"invalid argument: SparseMatrixCSC arrays of a {B.shape} matrix have lengths {len(p)}, {len(i)}, {len(v)}")
+        return p, i, v
 
     def _adopt(self, h):
         D = DeviceOperator.__new__(DeviceOperator)

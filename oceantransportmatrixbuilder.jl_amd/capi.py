@@ -10,7 +10,7 @@ STATUS_NAMES = {
     1: "RHO_NAN", 2: "TADV_NAN", 3: "TKH_NAN", 4: "TKVML_NAN", 5: "TKVDEEP_NAN", 6: "FLUX_INTO_LAND",
     7: "UNKNOWN_TOPOLOGY", 8: "ALL_MISSING", 9: "ALLOC", 10: "HIP", 11: "INVALID_ARG", 12: "NO_PLAN",
     13: "NONCANONICAL_INDICES", 14: "CAPACITY", 15: "PUSH_MASK", 16: "ASYMMETRIC_PATTERN", 17: "GIVEN_FOREIGN",
-    18: "SINGULAR_PRECONDITIONER", 19: "NOT_CONVERGED",
+    18: "SINGULAR_PRECONDITIONER", 19: "NOT_CONVERGED", 20: "TSINK_NAN", 21: "PATTERN_NOT_CONTAINED",
 }
 GIVEN_FOREIGN = 17
 CAPACITY = 14
@@ -20,6 +20,7 @@ PRECONDS = {"jacobi": 0, "lines": 1}  # otmb_precond
 PERIODIC_REASONS = ("converged", "maxcycles", "step_failed", "nonfinite")  # otmb_periodic_reason
 PERIODIC_PC_REASONS = PERIODIC_REASONS + ("precond_failed",)  # ... continued by otmb_periodic_pc_reason
 OUTERS = {"none": 0, "mean": 1}  # otmb_outer
+SEAFLOORS = {"open": 0, "closed": 1}  # otmb_build_sink's `closed`
 
 PHI_ORDER = ("east", "west", "north", "south", "top", "bottom")  # OTMB_EAST..OTMB_BOTTOM
 HDIRS = ("west", "east", "south", "north")  # OTMB_DIR_*
@@ -55,6 +56,13 @@ def outer_code(outer):
     if outer not in OUTERS:
         raise OtmbError(11, f"invalid argument: outer must be one of {sorted(OUTERS)}, not {outer!r}")
     return OUTERS[outer]
+
+
+def seafloor_code(seafloor):
+    """otmb_build_sink's `closed` of "open" / "closed" (the Julia shim's :open / :closed)."""
+    if seafloor not in SEAFLOORS:
+        raise OtmbError(11, f"invalid argument: seafloor must be one of {sorted(SEAFLOORS)}, not {seafloor!r}")
+    return SEAFLOORS[seafloor]
 
 
 class Csc(C.Structure):
@@ -193,6 +201,10 @@ SYMBOLS = {
     "otmb_spadd_plan_dev": (C.c_int32, [_vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _ip]),
     "otmb_spadd_fill_dev": (C.c_int32, [_vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "otmb_spadd": (C.c_int32, [_vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ip]),
+    "otmb_build_sink_dev": (C.c_int32, [_vp, C.c_int32, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp,
+                                         C.c_int64, _ip]),
+    "otmb_build_sink": (C.c_int32, [_vp, C.c_int32, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp,
+                                     C.c_int64, _ip]),
     "otmb_coarsen_plan_dev": (C.c_int32, [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _ip]),
     "otmb_coarsen_fill_dev": (C.c_int32, [_vp, _vp, _vp, _vp]),
     "otmb_coarsen_plan": (C.c_int32, [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _ip]),
@@ -265,6 +277,8 @@ SYMBOLS = {
                                              C.c_int64, _vp, _vp, _vp, C.c_int32, _vp]),
     "otmb_op_combine_slots_dev": (C.c_int32, [_vp, _vp, C.c_int64]),
     "otmb_op_combine_slots": (C.c_int32, [_vp, _vp, C.c_int64]),
+    "otmb_op_add_matrix_dev": (C.c_int32, [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_double, C.c_int64, _vp]),
+    "otmb_op_add_matrix": (C.c_int32, [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_double, C.c_int64, _vp]),
     "otmb_op_submatrix_dev": (C.c_int32, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.POINTER(_vp)]),
     "otmb_op_submatrix": (C.c_int32, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.POINTER(_vp)]),
     "otmb_op_take_values": (C.c_int32, [_vp, _vp, C.c_int64, C.c_int64]),

@@ -216,6 +216,14 @@ struct otmb_ctx {
         DevBuf prim_tmp;  // rocPRIM's temporary (scans, the sort)
     } co;
     DevBuf co_host, co_out;
+    // buildTsink (otmb_sink.hip): the scratch of a call, kept between calls (the pattern is a grid constant: a year of calls has one size)
+    struct SinkScratch {
+        DevBuf inc;       // i64 N + 1: entries of every column (1 or 2), then 0
+        DevBuf start;     // i64 N + 1: their exclusive scan; start[N] = nnz
+        DevBuf flags;     // unsigned: the SK_* bits
+        DevBuf prim_tmp;  // rocPRIM's temporary
+        DevBuf host;      // staging of the host-pointer entry point
+    } sink;
     // staging for the host-pointer entry points
     std::vector<DevBuf> stage;
     OtmbXfer *xfer = nullptr;

@@ -58,6 +58,8 @@ const char *otmb_status_string(int32_t s) {
         case OTMB_ERR_GIVEN_FOREIGN: return "a given operator is not what the library derives for these arguments: use the two-phase protocol";
         case OTMB_ERR_SINGULAR_PRECONDITIONER: return "singular preconditioner";
         case OTMB_ERR_NOT_CONVERGED: return "solve: not converged";
+        case OTMB_ERR_TSINK_NAN: return "Tsink contains NaNs.";
+        case OTMB_ERR_PATTERN_NOT_CONTAINED: return "the matrix has a stored entry outside the operator's pattern";
         default: return "unknown status";
     }
 }
@@ -118,7 +120,7 @@ void otmb_ctx_destroy(otmb_ctx *ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     otmb_tm_plan_free(ctx);
     otmb_xfer_free(ctx);
-    for (DevBuf *b : {&ctx->blocksums, &ctx->blockoffs, &ctx->flags, &ctx->ring, &ctx->stamps, &ctx->tcount, &ctx->tfix[0], &ctx->tfix[1], &ctx->tfix[2], &ctx->tm_sums, &ctx->tm_offs, &ctx->sort.keys_in, &ctx->sort.keys_out, &ctx->sort.idx_in, &ctx->sort.idx_out, &ctx->sort.prim_tmp, &ctx->ffc_sums[0], &ctx->ffc_sums[1], &ctx->xfer_narrow, &ctx->given_tmp[0], &ctx->given_tmp[1], &ctx->given_tmp[2], &ctx->given_tmp[3], &ctx->given_tmp[4], &ctx->given_tmp[5], &ctx->htab, &ctx->vrtab})
+    for (DevBuf *b : {&ctx->blocksums, &ctx->blockoffs, &ctx->flags, &ctx->ring, &ctx->stamps, &ctx->tcount, &ctx->tfix[0], &ctx->tfix[1], &ctx->tfix[2], &ctx->tm_sums, &ctx->tm_offs, &ctx->sort.keys_in, &ctx->sort.keys_out, &ctx->sort.idx_in, &ctx->sort.idx_out, &ctx->sort.prim_tmp, &ctx->ffc_sums[0], &ctx->ffc_sums[1], &ctx->xfer_narrow, &ctx->given_tmp[0], &ctx->given_tmp[1], &ctx->given_tmp[2], &ctx->given_tmp[3], &ctx->given_tmp[4], &ctx->given_tmp[5], &ctx->htab, &ctx->vrtab, &ctx->sink.inc, &ctx->sink.start, &ctx->sink.flags, &ctx->sink.prim_tmp, &ctx->sink.host})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : ctx->stage)
         if (b.p) (void)hipFree(b.p);

@@ -44,6 +44,7 @@ struct otmb_op {
     DevBuf season, setab;                 // otmb_op_step_season: d and the source of a blended step (n·kc + n·k doubles); the fold's table of terms beyond 16 (otmb_season.hip)
     DevBuf ob, oh;                        // the observations (otmb_observe.hip): the partial sums; the host entry points' staging of obs, W, X / Xbar
     DevBuf cb;                            // otmb_op_combine_slots: the table of slot pointers and weights, beyond the 16 that travel as arguments
+    DevBuf am;                            // otmb_op_add_matrix: the state words, B's positions in nzval, the table of slot pointers beyond 8 slots (otmb_addmat.hip)
     DevBuf ln;                            // otmb_op_set_lines (Int32, 0-based, -1 = none): successor (n), predecessor (n), line heads ascending (nheads)
     i64 nheads = 0;
     bool lines = false;                   // lines are set (they belong to the pattern: otmb_op_set_values keeps them)

@@ -193,7 +193,7 @@ static void sp_free_all(otmb_op *op) {
     if (!op->slots.empty()) op->nz = op->val = DevBuf();
     op->slots.clear();
     for (DevBuf *b : {&op->cp, &op->rv, &op->nz, &op->dst, &op->elen, &op->sbase, &op->loff, &op->lrows, &op->val, &op->col, &op->xs, &op->ys, &op->ds, &op->sw, &op->st,
-                      &op->pd, &op->mean.nz, &op->mean.val, &op->interp.nz, &op->interp.val, &op->season, &op->setab, &op->cb, &op->ln, &op->ob, &op->oh, &op->src})
+                      &op->pd, &op->mean.nz, &op->mean.val, &op->interp.nz, &op->interp.val, &op->season, &op->setab, &op->cb, &op->am, &op->ln, &op->ob, &op->oh, &op->src})
         otmb_free(*b);
 }
 

@@ -49,7 +49,7 @@ class Operator(OperatorCalls):
     """A resident sparse operator over device CSC arrays (otmb_op_create_dev): Y = α·A·X + β·Y and α·Aᵀ·X + β·Y on torch tensors, bit for
     bit SparseArrays' 5-argument mul! (api.DeviceOperator states the contract).  The operator owns device copies of the matrix;
     set_values_dev refreshes the values for the same pattern.  DeviceAssembler.operator() hands these out over its resident results.
-    precondition, solve, observe, step and periodic are OperatorCalls' over the tensor hooks below (the `_dev` exports): a column-major
+    add_matrix, precondition, solve, observe, step and periodic are OperatorCalls' over the tensor hooks below (the `_dev` exports): a column-major
     tensor, or a row slice of one, is passed uncopied with its parent's leading dimension; results are new tensors."""
 
     _suffix = "_dev"
@@ -120,6 +120,16 @@ class Operator(OperatorCalls):
         return torch.empty(n, dtype=getattr(torch, dtype), device=torch.device("cuda", self.device))
 
     def _csc(self, cp, rv, nz):
+        return cp, rv, nz
+
+    def _csc_arrays(self, B):
+        cp, rv, nz = B
+        for t, what, dtype in ((cp, "B's colptr", torch.int64), (rv, "B's rowval", torch.int64), (nz, "B's nzval", torch.float64)):
+            _on_device(t, self.device, what)
+            if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous():
+                raise capi.OtmbError(11, f"invalid argument: {what} must be a contiguous 1-D {dtype} tensor")
+        if cp.numel() != self.shape[1] + 1 or rv.numel() != nz.numel():
+            raise capi.OtmbError(11, f"DimensionMismatch: operator of {self.shape}, B's colptr of {cp.numel()}, rowval of {rv.numel()}, nzval of {nz.numel()}")
         return cp, rv, nz
 
     def _adopt(self, h):
@@ -857,6 +867,55 @@ class DeviceAssembler:
         rec = self._slotted(matrix)
         rec.op.combine_slots(weights, dst)
         if int(dst) == rec.op.slots[1]:
+            rec.dirty = True
+        return rec.op
+
+    def sinking(self, w, seafloor="open"):
+        """The settling operator S of particles that sink at the speed w >= 0 (m/s, positive downward) on the resident grid
+        (otmb_build_sink_dev; api.buildTsink states the contract): device tensors (colptr, rowval, nzval), no host round trip but the call's
+        own checks.  w: a number, nz values (the bottom face of each level) or nx·ny·nz values (the bottom face of each cell, in the grid's
+        column-major order; a (nx, ny, nz) array or tensor is taken in that order); a float64 tensor on this GPU is read where it lies, anything
+        else is uploaded.  seafloor: "open" (default) or "closed".  asm.add_matrix(asm.sinking(w)) adds S to the kept slots."""
+        closed = capi.seafloor_code(seafloor)
+        form, ws, wt = 0, 0.0, None
+        if torch.is_tensor(w) and w.dim() > 0:
+            _on_device(w, self.device.index, "w")
+            if w.dtype != torch.float64:
+                raise ValueError("w: a float64 tensor is required")
+            if w.dim() not in (1, 3) or (w.dim() == 3 and tuple(w.shape) != self.shape):
+                raise capi.OtmbError(11, f"DimensionMismatch: w of {tuple(w.shape)}, expected a number, {(self.nz,)}, {(self.G,)} or {self.shape}")
+            wt = (w.permute(2, 1, 0) if w.dim() == 3 else w).contiguous().view(-1)
+        elif np.ndim(w) > 0:
+            a = np.asarray(w, dtype=np.float64)
+            if a.ndim not in (1, 3) or (a.ndim == 3 and a.shape != self.shape):
+                raise capi.OtmbError(11, f"DimensionMismatch: w of {a.shape}, expected a number, {(self.nz,)} or {self.shape}")
+            wt = self._t(a)
+        else:
+            ws = float(w)
+        if wt is not None:
+            if wt.numel() not in (self.nz, self.G):
+                raise capi.OtmbError(11, f"DimensionMismatch: w of {wt.numel()} values, expected a number, {self.nz} or {self.G}")
+            form = 1 if wt.numel() == self.nz else 2  # (nz == nx·ny·nz is a grid of one column: the two forms are one)
+        cap = max(2 * self.N, 1)
+        cp, rv, nz = self._empty(self.N + 1, torch.int64), self._empty(cap, torch.int64), self._empty(cap, torch.float64)
+        nnz = C.c_int64(0)
+        self.ctx.check(self.lib.otmb_build_sink_dev(self.ctx.handle, form, ws, None if wt is None else wt.data_ptr(), self.v3d.data_ptr(),
+                                                    self.area.data_ptr(), self.lwet3d.data_ptr(), self.lwet.data_ptr(), self.N, self.nx, self.ny,
+                                                    self.nz, closed, cp.data_ptr(), rv.data_ptr(), nz.data_ptr(), cap, C.byref(nnz)))
+        k = int(nnz.value)
+        return cp, rv[:k], nz[:k]
+
+    def add_matrix(self, B, alpha=1.0, slots=None, matrix="T"):
+        """Operator.add_matrix on the resident operator over `matrix`: slot = slot + alpha·B in place over the slots keep_slot() filled (slots:
+        None = every slot, an int, or a list), for B = (colptr, rowval, nzval) device tensors whose pattern lies inside the matrix's --
+        sinking()'s S, or one of this assembler's own results (a diffusivity retuned: B = out["TκH"], alpha = κ'/κ - 1).  Like
+        combine_slots, a write to the selected slot makes the operator count as changed since the result was put there: operator() raises
+        until keep_slot() or forget_slots() says where the result goes."""
+        rec = self._slotted(matrix)
+        rec.op.add_matrix(B, alpha=alpha, slots=slots)
+        n, selected = rec.op.slots
+        written = range(n) if slots is None else [int(x) for x in np.atleast_1d(np.asarray(slots))]
+        if float(alpha) != 0.0 and B[1].numel() > 0 and selected in written:
             rec.dirty = True
         return rec.op
 

@@ -92,7 +92,7 @@ class PeriodicInfo:
 
 
 class OperatorCalls:
-    """precondition, solve, observe, step and periodic of a resident operator (its handle `_h`, `shape` and context `ctx`), written once.
+    """add_matrix, precondition, solve, observe, step and periodic of a resident operator (its handle `_h`, `shape` and context `ctx`), written once.
     Arrays below are numpy arrays for api.DeviceOperator and float64 tensors on the operator's GPU for device.Operator, whose results --
     the states, info.observations and info.mean -- are new device tensors; the reports' per-column records and time_weights are host values
     for both.  What a subclass says about its arrays:
@@ -109,6 +109,8 @@ class OperatorCalls:
       _empty(n, dtype)      an uninitialised 1-D array of "int64" or "float64" for the library to fill
       _csc(cp, rv, nz)      what to_csc returns of the three filled arrays
       _adopt(h)             a new operator of the class over the handle h, on this operator's context
+    and, for add_matrix:
+      _csc_arrays(B)        (colptr, rowval, nzval) of a matrix of the operator's shape as int64, int64 and float64 arrays of the class's kind
     Every refusal is raised before the library is called, but for the order of a selection's indices, which the library checks on the device."""
 
     _suffix = ""
@@ -213,6 +215,29 @@ class OperatorCalls:
         slot = self.slots[1] if slot is None else int(slot)
         parent_slot = slot if parent_slot is None else int(parent_slot)
         self.ctx.check(self._library().otmb_op_take_values(self._h, parent._h, parent_slot, slot))
+
+    def add_matrix(self, B, alpha=1.0, slots=None):
+        """slot = slot + alpha·B in place (otmb_op_add_matrix; include/otmb.h states the contract) for a CSC matrix B of the operator's shape
+        whose pattern lies inside the operator's -- the settling operator of buildTsink / DeviceAssembler.sinking added to a year of monthly
+        T, or a diffusivity retuned without a rebuild (B = TκH, alpha = κ'/κ - 1).  B: an api.SparseMatrixCSC for api.DeviceOperator, a
+        (colptr, rowval, nzval) triple of device tensors for device.Operator.  slots: None (every slot), an int, or a list of different slots.
+        Each stored entry of B goes to the first stored entry of the operator with its row and column: nz = nz + (alpha * B), no FMA, the
+        same bits into the row layout; entries B does not name are not rewritten; alpha == 0 checks the pattern and writes nothing.  An entry
+        of B that the operator does not store raises OtmbError (PATTERN_NOT_CONTAINED, naming the first) and leaves every slot untouched.
+        A submatrix child does not follow: child.take_values(self, slot) refreshes it."""
+        self._live()
+        m, n = self.shape
+        cp, rv, nz = self._csc_arrays(B)
+        if slots is None:
+            nsel, sel = 0, None
+        else:
+            sel = np.ascontiguousarray(np.atleast_1d(np.asarray(slots)))
+            if sel.ndim != 1 or not (np.issubdtype(sel.dtype, np.integer) or sel.size == 0):
+                raise capi.OtmbError(11, f"invalid argument: slots must be None, an int or a list of ints, got {slots!r}")
+            nsel = int(sel.size)
+            sel = sel.astype(np.int64) if nsel else np.zeros(1, dtype=np.int64)  # (never a null pointer: that is "every slot")
+        self.ctx.check(self._call("otmb_op_add_matrix", m, n, self._ptr(cp), self._ptr(rv), self._ptr(nz), float(alpha), nsel,
+                                  None if sel is None else sel.ctypes.data))
 
     def to_csc(self, slot=None):
         """The operator's matrix as it was created (otmb_op_fetch): colptr, 1-based rowval and the nzval of slot `slot` (None: the selected
